@@ -66,7 +66,13 @@ def parse():
     ap.add_argument("--no-lstm-roofline", action="store_true",
                     help="skip the LSTM-step microbenchmark (PMC passes profile the train step only)")
     ap.add_argument("--cpu-steps", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left its caller as DIR/<name>.npy (float32): "
+                         "loss, and every parameter the step updated, with the gradient that produced the update "
+                         "(at most 64 MB in all; larger arrays as a fixed seeded sample of their elements, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.conv_event_every <= 0:
         args.conv_event_every = 1 if args.batch >= 32 else 4
     if args.batch < 32 and not args.no_graph_trunk:
@@ -93,6 +99,44 @@ def pmc_traffic(key="conv_bytes_per_launch"):
         except Exception:
             continue
     return None, None
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outdir, loss, named, seed=0):
+    """--dump-outputs: the last timed step's results as `outdir`/<name>.npy, float32 -- `loss` (shape [1]) and, for
+    every (name, parameter) of `named` that has a gradient, `param.<name>` (after the update) and `grad.<name>` (the
+    gradient the update consumed, after the clamp). A parameter without a gradient took no part in the step (the style
+    branches of a decoder trained in another mode): Adam leaves it as it was, so it is no result and is not written.
+    The loss and the parameters, each with its gradient, share DUMP_BUDGET_BYTES evenly, smallest first; an array
+    larger than its share is written flat, as its elements at sorted indices drawn by a generator seeded with `seed`
+    (the same ones for a parameter and its gradient), so the same configuration writes the same elements on every run
+    and two builds can be compared file by file. Returns the number of bytes written."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    groups = [[("loss", loss.detach().reshape(1))]]
+    for name, p in named:
+        if p.grad is not None:
+            groups.append([("param." + name, p.detach()), ("grad." + name, p.grad.detach())])
+    # shares per group, so that a parameter and its gradient are sampled at the same elements
+    left = DUMP_BUDGET_BYTES // 4 - 64 * sum(map(len, groups))      # 256 bytes per file kept for the .npy header
+    arrays, take = [], []
+    for k, g in enumerate(sorted(groups, key=lambda g: g[0][1].numel())):
+        n = min(g[0][1].numel(), left // (len(groups) - k) // len(g))
+        left -= n * len(g)
+        arrays += g
+        take += [n] * len(g)
+    written = 0
+    for i, (name, t) in enumerate(arrays):
+        a = t.float()
+        if take[i] < a.numel():
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(seed))[:take[i]].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, a.cpu().numpy())
+        written += os.path.getsize(path)
+    return written
 
 
 def log(msg):
@@ -436,6 +480,12 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     ops.check_device_errors()
+    if args.dump_outputs and rank == 0:
+        trained = set(map(id, params))
+        named = [("decoder." + n, p) for n, p in decoder.named_parameters() if id(p) in trained]
+        named += [("encoder." + n, p) for n, p in encoder.named_parameters() if id(p) in trained]
+        nbytes = dump_outputs(args.dump_outputs, last, named)
+        log("outputs of the last timed step: %.1f MB in %s" % (nbytes / 2 ** 20, args.dump_outputs))
 
     roofline = None
     if conv_events:

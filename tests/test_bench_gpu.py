@@ -43,6 +43,33 @@ def test_bench_prints_one_json_line():
     assert d["roofline_lstm_step"]["bound"] == "hbm"
 
 
+def test_bench_dumps_the_last_step(tmp_path):
+    """--dump-outputs: loss, parameters and gradients of the last timed step, within the byte budget; the same
+    arguments give the same inputs, so two runs write the same arrays."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    got, lines = [], []
+    for run in ("a", "b"):
+        out = str(tmp_path / run)
+        lines.append(_run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                           "--no-lstm-roofline", "--no-conv-events", "--dump-outputs", out], {}))
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= bench.DUMP_BUDGET_BYTES
+        got.append({f: np.load(os.path.join(out, f)) for f in files})
+    a, b = got
+    assert lines[0]["steps"] == 2
+    assert "loss.npy" in a and "param.decoder.C.weight.npy" in a and "grad.decoder.C.weight.npy" in a
+    assert "param.encoder.linear.weight.npy" in a and "grad.encoder.bn.weight.npy" in a
+    # the factual step leaves the other styles' branches alone: they are no result of it
+    assert not [f for f in a if ".S_happy_" in f or ".S_sad_" in f or ".S_angry_" in f]
+    assert abs(float(a["loss.npy"][0]) - lines[0]["loss_last"]) < 1e-4
+    assert set(a) == set(b)
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all() and (a[f] != 0).any(), f
+        assert a[f].shape == b[f].shape and np.abs(a[f] - b[f]).max() <= 1e-5 * max(np.abs(b[f]).max(), 1e-30), f
+
+
 @pytest.mark.parametrize("extra", [["--decoder", "att", "--batch", "12"], ["--decoder", "nic"],
                                    ["--layers", "3", "--factored", "1024", "--batch", "16"]])
 def test_secondary_workloads_run(extra):

@@ -131,7 +131,14 @@ def test_attention_decoder_matches_reference(cname):
     for k, v in p.items():
         key = "grad." + k
         if key in c:
-            assert rel_err(v.grad, c[key]) < 2e-5, k
+            if k.endswith("full_att.bias"):
+                # the bias shifts every score in front of the attention softmax alike, so its gradient is exactly zero:
+                # fixture and oracle both hold fp32 rounding noise, whose digits depend on the CPU's vector width.
+                # Both must stay at rounding level against the gradient of the same layer's weight.
+                scale = float(p[k[:-len("bias")] + "weight"].grad.abs().max())
+                assert float(v.grad.abs().max()) < 1e-6 * scale and float(abs(c[key]).max()) < 1e-6 * scale, k
+            else:
+                assert rel_err(v.grad, c[key]) < 2e-5, k
             n += 1
         else:
             assert v.grad is None or float(v.grad.abs().max()) == 0.0, k
