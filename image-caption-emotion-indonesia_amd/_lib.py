@@ -115,6 +115,16 @@ SIGNATURES = {
                                     _vp, _vp]),
     "capnet_att_seq_backward": (_i, [_ip, _ip, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _vp, _vp,
                                      C.POINTER(_vp), C.c_float, C.c_ulonglong, _i, _vp]),
+    "capnet_att_stacked_saved_floats": (_sz, [_ip, _i]),
+    "capnet_att_stacked_saved_ints": (_sz, [_ip, _i]),
+    "capnet_att_stacked_fwd_scratch_floats": (_sz, [_ip, _i]),
+    "capnet_att_stacked_bwd_scratch_floats": (_sz, [_ip, _i]),
+    "capnet_att_seq_forward_stacked": (_i, [_ip, _i, _ip, C.POINTER(C.c_ubyte), _vp, _vp, _vp, C.POINTER(_vp), _vp, _vp,
+                                            C.c_float, C.c_ulonglong, _i, C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                            C.POINTER(_vp), _vp, _vp, _vp]),
+    "capnet_att_seq_backward_stacked": (_i, [_ip, _i, _ip, _vp, _vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp),
+                                             C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.c_float,
+                                             C.c_ulonglong, _i, _vp]),
     "capnet_embedding_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "capnet_lstm_pointwise_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),

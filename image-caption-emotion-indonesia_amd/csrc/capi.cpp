@@ -522,6 +522,68 @@ int capnet_att_seq_backward(const int* dims, const int* batch_sizes, const float
                           saved, saved_i, scratch, g, dropout_p, seed, training, S(stream));
 }
 
+size_t capnet_att_stacked_saved_floats(const int* dims, int layer) { return att_stacked_saved_floats(to_adims(dims), layer); }
+size_t capnet_att_stacked_saved_ints(const int* dims, int layer) { return att_stacked_saved_ints(to_adims(dims), layer); }
+size_t capnet_att_stacked_fwd_scratch_floats(const int* dims, int nlayers) {
+  return att_stacked_fwd_scratch_floats(to_adims(dims), nlayers);
+}
+size_t capnet_att_stacked_bwd_scratch_floats(const int* dims, int nlayers) {
+  return att_stacked_bwd_scratch_floats(to_adims(dims), nlayers);
+}
+
+int capnet_att_seq_forward_stacked(const int* dims, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
+                                   const long long* captions, const float* features, const float* emb,
+                                   const float* const* weights, const float* Cw, const float* Cb, float dropout_p,
+                                   unsigned long long seed, int training, float* const* saved, int* const* saved_i,
+                                   float* scratch, float* const* hiddens, float* alphas, int* err_flag,
+                                   capnet_stream_t stream) {
+  CAPNET_REQUIRE(dims && weights && nlayers >= 1 && nlayers <= 8, "att_seq_forward_stacked: null dims / weights or layers %d",
+                 nlayers);
+  CAPNET_REQUIRE(dims[11] == kCellFactored, "att_seq_forward_stacked: the factored cell only");
+  AttWeights w0;
+  int rc = to_aweights(weights, &w0, dims[11]);
+  if (rc) return rc;
+  SeqWeights wu[8];
+  UpperInit iu[8];
+  for (int l = 1; l < nlayers; ++l) {
+    const float* const* p = weights + 44 + 36 * (l - 1);
+    for (int i = 0; i < 36; ++i) CAPNET_REQUIRE(p[i], "att_seq_forward_stacked: weight %d of layer %d is null", i, l);
+    to_weights(p, wu[l - 1]);
+    iu[l - 1] = UpperInit{p[32], p[33], p[34], p[35]};
+  }
+  return att_seq_forward_stacked(to_adims(dims), nlayers, batch_sizes, tf_mask, captions, features, emb, w0, wu, iu, Cw, Cb,
+                                 dropout_p, seed, training, saved, saved_i, scratch, hiddens, alphas, err_flag, S(stream));
+}
+
+int capnet_att_seq_backward_stacked(const int* dims, int nlayers, const int* batch_sizes, const float* d_hiddens,
+                                    const float* d_alphas, const float* const* hiddens, const float* features,
+                                    const float* const* weights, const float* const* saved, const int* const* saved_i,
+                                    float* scratch, float* const* dh_work, float* const* grads, float dropout_p,
+                                    unsigned long long seed, int training, capnet_stream_t stream) {
+  CAPNET_REQUIRE(dims && weights && grads && nlayers >= 1 && nlayers <= 8,
+                 "att_seq_backward_stacked: null dims / weights / grads or layers %d", nlayers);
+  CAPNET_REQUIRE(dims[11] == kCellFactored, "att_seq_backward_stacked: the factored cell only");
+  AttWeights w0;
+  int rc = to_aweights(weights, &w0, dims[11]);
+  if (rc) return rc;
+  AttGrads g;
+  g.dVcat = grads[0]; g.dbV = grads[1]; g.dScat = grads[2]; g.dbS = grads[3]; g.dUcat = grads[4];
+  g.dWz = grads[5]; g.dbz = grads[6]; g.dWe = grads[7]; g.dbe = grads[8]; g.dwf = grads[9];
+  g.dbf = grads[10]; g.dWih = grads[11]; g.dbih = grads[12]; g.dWic = grads[13]; g.dbic = grads[14];
+  g.dEmb = grads[15];
+  SeqGrads gu[8];
+  UpperInitGrads giu[8];
+  for (int l = 1; l < nlayers; ++l) {
+    float* const* q = grads + 16 + 11 * (l - 1);
+    for (int i = 0; i < 11; ++i) CAPNET_REQUIRE(q[i], "att_seq_backward_stacked: gradient %d of layer %d is null", i, l);
+    gu[l - 1].dVcat = q[0]; gu[l - 1].dbV = q[1]; gu[l - 1].dScat = q[2]; gu[l - 1].dbS = q[3]; gu[l - 1].dUcat = q[4];
+    gu[l - 1].dbUW = q[5]; gu[l - 1].dWcat = q[6]; gu[l - 1].dEmb = nullptr; gu[l - 1].dFeat = nullptr;
+    giu[l - 1] = UpperInitGrads{q[7], q[8], q[9], q[10]};
+  }
+  return att_seq_backward_stacked(to_adims(dims), nlayers, batch_sizes, d_hiddens, d_alphas, hiddens, features, w0, saved,
+                                  saved_i, scratch, dh_work, g, gu, giu, dropout_p, seed, training, S(stream));
+}
+
 int capnet_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets,
                     float* lse, float* row_loss, float* loss, int* err_flag,
                     capnet_stream_t stream) {

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "seq_layers.h"
 
 namespace capnet {
 
@@ -150,21 +151,43 @@ size_t att_bwd_scratch_floats(const AttDims& d) {
          kAttSplitKFloats + (d.B <= 128 ? (size_t)cdiv(L.ZW, 64) * d.B * d.H : 4) + 4;
 }
 
-int att_seq_forward(const AttDims& d, const int* bs, const unsigned char* tf,
-                    const long long* captions, const float* feat, const float* emb,
-                    const AttWeights& w, const float* Cw, const float* Cb, float dropout_p,
-                    unsigned long long seed, int training, float* saved, int* saved_i,
-                    float* scratch, float* hiddens, float* alphas_bt, int* err_flag,
-                    hipStream_t s) {
+namespace {
+// one forward call of the attention cell: what its steps share (att_fwd_begin), so that the single-layer driver and the
+// stacked one step through the same code
+struct AttFwd {
+  AttDims d;
+  ALayout L;
+  std::vector<int> off;
+  const unsigned char* tf;
+  const long long* captions;
+  const float *feat, *emb, *Cw, *Cb;
+  float dropout_p;
+  unsigned long long seed;
+  const float *w_full, *b_full;
+  float *sv, *scratch, *skws, *escore, *hiddens, *alphas_bt;
+  int *svi, *skctr, *err_flag;
+  bool one_product, fac;
+  GateOrderA go;
+  hipStream_t s;
+};
+
+// row bookkeeping, weight packing, the collapsed chain, the time-invariant products and the teacher-forced inputs
+int att_fwd_begin(AttFwd& f, const AttDims& d, const int* bs, const unsigned char* tf, const long long* captions,
+                  const float* feat, const float* emb, const AttWeights& w, const float* Cw, const float* Cb,
+                  float dropout_p, unsigned long long seed, int training, float* saved, int* saved_i, float* scratch,
+                  float* hiddens, float* alphas_bt, int* err_flag, hipStream_t s) {
   RC(check(d, bs));
   CAPNET_REQUIRE(tf && captions && feat && emb && Cw && Cb && saved && saved_i && scratch &&
                      hiddens && alphas_bt && err_flag,
                  "att_seq_forward: null argument");
   CAPNET_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "att_seq_forward: dropout p");
-  const ALayout L = make_alayout(d);
-  const int E = d.E, F = d.F, H = d.H, N = d.N, A = d.A, P = d.P, C = d.C, ZW = L.ZW, XW = L.XW;
+  f.d = d;
+  f.L = make_alayout(d);
+  const ALayout& L = f.L;
+  const int E = d.E, F = d.F, H = d.H, N = d.N, A = d.A, P = d.P, C = d.C, XW = L.XW;
   float* sv = saved;
-  std::vector<int> off(d.steps + 1, 0);
+  std::vector<int>& off = f.off;
+  off.assign(d.steps + 1, 0);
   for (int t = 0; t < d.steps; ++t) off[t + 1] = off[t] + bs[t];
   {
     SeqMeta m;
@@ -233,45 +256,79 @@ int att_seq_forward(const AttDims& d, const int* bs, const unsigned char* tf,
   RC(gather_inputs(captions, d.T, nullptr, emb, E, d.V, saved_i + L.row_sample, saved_i + L.row_col,
                    saved_i + L.row_token, sv + L.XA, XW, 0, N, dropout_p, seed,
                    training && dropout_p > 0.f, 0, err_flag, s));
+  f.tf = tf; f.captions = captions; f.feat = feat; f.emb = emb; f.Cw = Cw; f.Cb = Cb;
+  f.dropout_p = dropout_p; f.seed = seed; f.w_full = w.full_att_w; f.b_full = w.full_att_b;
+  f.sv = sv; f.scratch = scratch; f.skws = skws; f.escore = escore; f.hiddens = hiddens; f.alphas_bt = alphas_bt;
+  f.svi = saved_i; f.skctr = skctr; f.err_flag = err_flag;
+  f.one_product = one_product; f.fac = fac; f.go = go; f.s = s;
+  return kOk;
+}
 
-  for (int t = 0; t < d.steps; ++t) {
-    const int b = bs[t], r0 = off[t];
-    const float* hprev = t > 0 ? hiddens + (size_t)off[t - 1] * H : sv + L.h0;
-    const float* cprev = t > 0 ? sv + L.Cst + (size_t)off[t - 1] * H : sv + L.c0;
-    float* Z = sv + L.Zf + (size_t)r0 * ZW;
-    // Z = h . Wz^T + bz  ->  [recurrent gate pre-acts | att2 | f_beta(h)]
-    RC(sgemm_splitk(false, true, b, ZW, H, hprev, H, sv + L.Wz, H, Z, ZW, sv + L.bz, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-    RC(att_step_fwd(sv + L.att1, feat, Z + 4 * H, Z + 4 * H + A, ZW, w.full_att_w, w.full_att_b, b, P,
-                    A, C, sv + L.alpha + (size_t)r0 * P, alphas_bt, d.steps, t,
-                    sv + L.awe + (size_t)r0 * C, sv + L.XA + (size_t)r0 * XW + E, XW, escore, s));
-    if (t > 0 && !tf[t]) {
-      RC(sgemm_splitk(false, true, b, d.V, H, hprev, H, Cw, H, scratch, d.V, Cb, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-      RC(argmax_rows(scratch, b, d.V, d.V, saved_i + L.row_token + r0, s));
-      RC(gather_inputs(captions, d.T, nullptr, emb, E, d.V, saved_i + L.row_sample,
-                       saved_i + L.row_col, saved_i + L.row_token, sv + L.XA, XW, r0, r0 + b,
-                       dropout_p, seed, 0, 1, err_flag, s));
-    }
-    int x_slabs = 0;      // the input product's K-chunk partials, summed by the gate kernel (no hand-off inside the product's launch)
-    // one product per step: [x | gated context] . Wx^T with Wx = U S V (the collapsed chain) or nn.LSTMCell's weight_ih
-    const float* Wx = one_product ? sv + L.Weff : (fac ? nullptr : sv + L.Vcat);
-    if (Wx) {
-      RC(product_slabs(true, b, 4 * H, XW, sv + L.XA + (size_t)r0 * XW, XW, Wx, XW, skws, kAttSplitKWs, &x_slabs, s));
-      if (!x_slabs)
-        RC(sgemm_splitk(false, true, b, 4 * H, XW, sv + L.XA + (size_t)r0 * XW, XW, Wx, XW, Z, ZW, nullptr, 1, skws,
-                        kAttSplitKWs, s, skctr, kSplitKCounters));
-    } else {
-      // factored chain on [x | gated context]
-      RC(sgemm_splitk(false, true, b, 4 * F, XW, sv + L.XA + (size_t)r0 * XW, XW, sv + L.Vcat, XW,
-                      sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.bV, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-      RC(sgemm_splitk_batched(false, true, b, F, F, sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.Scat,
-                              F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.bS, 0, 4, F,
-                              (long)F * F, F, F, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-      RC(sgemm_splitk_batched(false, true, b, H, F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.Ucat,
-                              F, Z, ZW, nullptr, 1, 4, F, (long)H * F, H, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-    }
-    RC(lstm_pointwise_fwd(Z, ZW, cprev, sv + L.Cst + (size_t)r0 * H, hiddens + (size_t)r0 * H, b, H,
-                          go.gi, go.gf, go.go, go.gg, go.tanh_out, s, x_slabs ? skws : nullptr, x_slabs));
+// step t of the attention cell. h_feed: the rows of step t - 1 whose argmax(C h) is fed back when step t is free running
+// (the cell's own hiddens; the top layer's in a stack)
+int att_fwd_step(AttFwd& f, int t, const float* h_feed) {
+  const AttDims& d = f.d;
+  const ALayout& L = f.L;
+  const std::vector<int>& off = f.off;
+  const int E = d.E, F = d.F, H = d.H, A = d.A, P = d.P, C = d.C, ZW = L.ZW, XW = L.XW;
+  float* sv = f.sv;
+  float* skws = f.skws;
+  int* skctr = f.skctr;
+  const bool fac = f.fac, one_product = f.one_product;
+  const GateOrderA go = f.go;
+  hipStream_t s = f.s;
+  const int b = off[t + 1] - off[t], r0 = off[t];
+  const float* hprev = t > 0 ? f.hiddens + (size_t)off[t - 1] * H : sv + L.h0;
+  const float* cprev = t > 0 ? sv + L.Cst + (size_t)off[t - 1] * H : sv + L.c0;
+  float* Z = sv + L.Zf + (size_t)r0 * ZW;
+  // Z = h . Wz^T + bz  ->  [recurrent gate pre-acts | att2 | f_beta(h)]
+  RC(sgemm_splitk(false, true, b, ZW, H, hprev, H, sv + L.Wz, H, Z, ZW, sv + L.bz, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
+  RC(att_step_fwd(sv + L.att1, f.feat, Z + 4 * H, Z + 4 * H + A, ZW, f.w_full, f.b_full, b, P,
+                  A, C, sv + L.alpha + (size_t)r0 * P, f.alphas_bt, d.steps, t,
+                  sv + L.awe + (size_t)r0 * C, sv + L.XA + (size_t)r0 * XW + E, XW, f.escore, s));
+  if (t > 0 && !f.tf[t]) {
+    RC(sgemm_splitk(false, true, b, d.V, H, h_feed, H, f.Cw, H, f.scratch, d.V, f.Cb, 0, skws, kAttSplitKWs, s, skctr,
+                    kSplitKCounters));
+    RC(argmax_rows(f.scratch, b, d.V, d.V, f.svi + L.row_token + r0, s));
+    RC(gather_inputs(f.captions, d.T, nullptr, f.emb, E, d.V, f.svi + L.row_sample,
+                     f.svi + L.row_col, f.svi + L.row_token, sv + L.XA, XW, r0, r0 + b,
+                     f.dropout_p, f.seed, 0, 1, f.err_flag, s));
   }
+  int x_slabs = 0;      // the input product's K-chunk partials, summed by the gate kernel (no hand-off inside the product's launch)
+  // one product per step: [x | gated context] . Wx^T with Wx = U S V (the collapsed chain) or nn.LSTMCell's weight_ih
+  const float* Wx = one_product ? sv + L.Weff : (fac ? nullptr : sv + L.Vcat);
+  if (Wx) {
+    RC(product_slabs(true, b, 4 * H, XW, sv + L.XA + (size_t)r0 * XW, XW, Wx, XW, skws, kAttSplitKWs, &x_slabs, s));
+    if (!x_slabs)
+      RC(sgemm_splitk(false, true, b, 4 * H, XW, sv + L.XA + (size_t)r0 * XW, XW, Wx, XW, Z, ZW, nullptr, 1, skws,
+                      kAttSplitKWs, s, skctr, kSplitKCounters));
+  } else {
+    // factored chain on [x | gated context]
+    RC(sgemm_splitk(false, true, b, 4 * F, XW, sv + L.XA + (size_t)r0 * XW, XW, sv + L.Vcat, XW,
+                    sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.bV, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
+    RC(sgemm_splitk_batched(false, true, b, F, F, sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.Scat,
+                            F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.bS, 0, 4, F,
+                            (long)F * F, F, F, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
+    RC(sgemm_splitk_batched(false, true, b, H, F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.Ucat,
+                            F, Z, ZW, nullptr, 1, 4, F, (long)H * F, H, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
+  }
+  RC(lstm_pointwise_fwd(Z, ZW, cprev, sv + L.Cst + (size_t)r0 * H, f.hiddens + (size_t)r0 * H, b, H,
+                        go.gi, go.gf, go.go, go.gg, go.tanh_out, s, x_slabs ? skws : nullptr, x_slabs));
+  return kOk;
+}
+}  // namespace
+
+int att_seq_forward(const AttDims& d, const int* bs, const unsigned char* tf,
+                    const long long* captions, const float* feat, const float* emb,
+                    const AttWeights& w, const float* Cw, const float* Cb, float dropout_p,
+                    unsigned long long seed, int training, float* saved, int* saved_i,
+                    float* scratch, float* hiddens, float* alphas_bt, int* err_flag,
+                    hipStream_t s) {
+  AttFwd f;
+  RC(att_fwd_begin(f, d, bs, tf, captions, feat, emb, w, Cw, Cb, dropout_p, seed, training, saved, saved_i, scratch, hiddens,
+                   alphas_bt, err_flag, s));
+  for (int t = 0; t < d.steps; ++t)
+    RC(att_fwd_step(f, t, t > 0 ? hiddens + (size_t)f.off[t - 1] * d.H : nullptr));
   return kOk;
 }
 
@@ -401,6 +458,186 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
                         saved_i + L.row_token, g.dEmb, nullptr, d.V, dropout_p, seed,
                         training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kAttSplitKWs));
   return kOk;
+}
+
+// ---- stacked attention decoder (capnet.stacked_att) -------------------------------------------------------------------
+// PERF-ONLY, PARITY UNPINNED: the reference accepts num_layers and ignores it (stylenet/model_att.py:81). Layer 0 is the
+// cell above, unchanged; its attention and f_beta gate read layer 0's own h^0_{t-1}. Layer l > 0 is the factored cell on
+// dropout_l(h^{l-1}_t) with its own parameters and initial state init_h{l} / init_c{l}(mean over pixels); only the top
+// layer feeds C. As the attention stays inside layer 0, a run of teacher-forced steps goes up the stack run by run: layer
+// 0 steps through the run, then each upper layer takes the run's rows (decoder_seq.cpp's layer machinery: one persistent
+// launch per run, or per lone step the fused upper step below). An upper layer's buffers carry a LEADING STATE STEP: step
+// 0 of its rows is the initial state (B rows), packed row r of the decoder is its row B + r.
+namespace {
+SeqDims upper_ext_dims(const AttDims& d) {
+  SeqDims u;
+  u.B = d.B; u.T = d.T + 1; u.steps = d.steps + 1; u.N = d.N + d.B; u.E = d.H; u.F = d.F; u.H = d.H; u.V = d.V;
+  u.has_features = 0; u.cell = kCellFactored;
+  return u;
+}
+// after the layer's seq layout: the collapsed chain of the fused upper step, Weff [4H][H] = U_g S_g V_g, US [4H][F],
+// c1 [4F] = S_g bV_g + bS_g, beff [4H] = U_g c1_g + bU_g + bW_g
+struct UpperExtra { size_t Weff, US, c1, beff, total; };
+UpperExtra upper_extra(const SeqDims& u) {
+  const size_t base = seqd::make_layout(u).total, H = u.H, F = u.F;
+  UpperExtra x;
+  x.Weff = base;
+  x.US = x.Weff + 4 * H * H;
+  x.c1 = x.US + 4 * H * F;
+  x.beff = x.c1 + (4 * F + 3) / 4 * 4;
+  x.total = x.beff + 4 * H;
+  return x;
+}
+bool fused_upper_enabled() {        // read at every call: CAPNET_NO_FUSED_UPPER_STEP=1 takes the composed step
+  const char* e = getenv("CAPNET_NO_FUSED_UPPER_STEP");
+  return !(e && e[0] == '1');
+}
+}  // namespace
+
+size_t att_stacked_saved_floats(const AttDims& d, int layer) {
+  return layer == 0 ? att_saved_floats(d) : upper_extra(upper_ext_dims(d)).total;
+}
+size_t att_stacked_saved_ints(const AttDims& d, int layer) {
+  return layer == 0 ? att_saved_ints(d) : seqd::make_layout(upper_ext_dims(d)).itotal;
+}
+size_t att_stacked_fwd_scratch_floats(const AttDims& d, int nlayers) {
+  (void)nlayers;           // the upper layers work in the attention cell's slab area
+  return att_fwd_scratch_floats(d);
+}
+size_t att_stacked_bwd_scratch_floats(const AttDims& d, int nlayers) {
+  size_t n = att_bwd_scratch_floats(d);
+  if (nlayers > 1) {
+    const size_t u = seqd::seq_bwd_upper_scratch_floats(upper_ext_dims(d));
+    n = (n > u ? n : u) + 4 + 2 * (size_t)d.B * d.H;
+  }
+  return n;
+}
+
+int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const unsigned char* tf, const long long* captions,
+                            const float* feat, const float* emb, const AttWeights& w0, const SeqWeights* wu,
+                            const UpperInit* iu, const float* Cw, const float* Cb, float dropout_p, unsigned long long seed,
+                            int training, float* const* saved, int* const* saved_i, float* scratch, float* const* hiddens,
+                            float* alphas_bt, int* err_flag, hipStream_t s) {
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8 && saved && saved_i && hiddens && (nlayers == 1 || (wu && iu)),
+                 "att_seq_forward_stacked: bad argument (layers %d)", nlayers);
+  CAPNET_REQUIRE(nlayers == 1 || d.cell == kCellFactored, "att_seq_forward_stacked: stacked layers are the factored cell's");
+  CAPNET_REQUIRE(nlayers == 1 || d.steps + 1 <= kMaxSteps, "att_seq_forward_stacked: %d steps", d.steps);
+  for (int l = 0; l < nlayers; ++l)
+    CAPNET_REQUIRE(saved[l] && saved_i[l] && hiddens[l], "att_seq_forward_stacked: null buffer of layer %d", l);
+  AttFwd f;
+  RC(att_fwd_begin(f, d, bs, tf, captions, feat, emb, w0, Cw, Cb, dropout_p, seed, training, saved[0], saved_i[0], scratch,
+                   hiddens[0], alphas_bt, err_flag, s));
+  const int B = d.B, H = d.H, F = d.F, C = d.C;
+  if (nlayers == 1) {
+    for (int t = 0; t < d.steps; ++t) RC(att_fwd_step(f, t, t > 0 ? hiddens[0] + (size_t)f.off[t - 1] * H : nullptr));
+    return kOk;
+  }
+  const SeqDims ud = upper_ext_dims(d);
+  const UpperExtra ux = upper_extra(ud);
+  std::vector<int> bse(ud.steps), offe(ud.steps + 1, 0);
+  bse[0] = B;
+  for (int t = 0; t < d.steps; ++t) bse[t + 1] = bs[t];
+  for (int t = 0; t < ud.steps; ++t) offe[t + 1] = offe[t] + bse[t];
+  const bool fused = fused_upper_enabled();
+  const bool drop = training && dropout_p > 0.f;
+  const float* mean = f.sv + f.L.mean;
+  std::vector<seqd::LayerCtx> up(nlayers);
+  for (int l = 1; l < nlayers; ++l) {
+    seqd::LayerCtx& c = up[l];
+    c.d = ud;
+    c.L = seqd::make_layout(ud);
+    c.sv = saved[l]; c.svi = saved_i[l]; c.hid = hiddens[l];
+    SeqMeta m;
+    m.N = ud.N; m.steps = ud.steps; m.has_features = 0;
+    for (int t = 0; t <= ud.steps; ++t) m.off[t] = offe[t];
+    m.tf[0] = 1;
+    for (int t = 0; t < d.steps; ++t) m.tf[t + 1] = tf[t] ? 1 : 0;
+    RC(build_rows(m, c.svi + c.L.row_sample, c.svi + c.L.row_col, c.svi + c.L.row_token, c.svi + c.L.prev_row, s));
+    RC(seqd::pack_layer(c, wu[l - 1], bse.data(), s));
+    // the leading state step: h0 = init_h{l}(mean), c0 = init_c{l}(mean)
+    RC(sgemm_splitk(false, true, B, H, C, mean, C, iu[l - 1].init_h_w, C, c.hid, H, iu[l - 1].init_h_b, 0, f.skws, kAttSplitKWs, s,
+                    f.skctr, kSplitKCounters));
+    RC(sgemm_splitk(false, true, B, H, C, mean, C, iu[l - 1].init_c_w, C, c.sv + c.L.Cst, H, iu[l - 1].init_c_b, 0, f.skws,
+                    kAttSplitKWs, s, f.skctr, kSplitKCounters));
+    if (fused) {
+      float* sv = c.sv;
+      RC(sgemm(false, false, H, F, F, sv + c.L.Ucat, F, sv + c.L.Scat, F, sv + ux.US, F, nullptr, 0, 4, (long)H * F, (long)F * F,
+               (long)H * F, 0, 0, s));
+      RC(sgemm(false, false, H, H, F, sv + ux.US, F, sv + c.L.Vcat, H, sv + ux.Weff, H, nullptr, 0, 4, (long)H * F,
+               (long)F * H, (long)H * H, 0, 0, s));
+      RC(sgemm_splitk_batched(false, true, 1, F, F, sv + c.L.bV, F, sv + c.L.Scat, F, sv + ux.c1, F, sv + c.L.bS, 0, 4, F,
+                              (long)F * F, F, F, f.skws, kAttSplitKWs, s, f.skctr, kSplitKCounters));
+      CAPNET_HIP_CHECK(hipMemcpyAsync(sv + ux.beff, sv + c.L.bUW, (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+      RC(sgemm_splitk_batched(false, true, 1, H, F, sv + ux.c1, F, sv + c.L.Ucat, F, sv + ux.beff, H, nullptr, 1, 4, F,
+                              (long)H * F, H, 0, f.skws, kAttSplitKWs, s, f.skctr, kSplitKCounters));
+    }
+  }
+  const seqd::LayerCtx& top = up[nlayers - 1];
+  for (int t = 0; t < d.steps;) {
+    int t1 = t + 1;
+    while (t1 < d.steps && tf[t1]) ++t1;
+    // layer 0 through the run (only its first step can be free running: it feeds back argmax(C h^top_{t-1}))
+    for (int u = t; u < t1; ++u) RC(att_fwd_step(f, u, u > 0 ? top.hid + (size_t)offe[u] * H : nullptr));
+    const int b = bs[t], r0 = f.off[t], r1 = f.off[t1];
+    for (int l = 1; l < nlayers; ++l) {
+      seqd::LayerCtx& c = up[l];
+      const float* below = l == 1 ? hiddens[0] : up[l - 1].hid + (size_t)B * H;     // packed row 0 of the layer below
+      if (fused && t1 == t + 1 && lstm_upper_step_supported(b, H)) {
+        const size_t pr = offe[t + 1], cr = offe[t];     // this step's rows; the previous step's (or the initial state)
+        RC(lstm_upper_step(below + (size_t)r0 * H, c.hid + cr * H, c.sv + c.L.Cst + cr * H, c.sv + ux.Weff, c.sv + c.L.Wcat,
+                           c.sv + ux.beff, c.sv + c.L.X + pr * H, c.sv + c.L.G + pr * 4 * H, c.sv + c.L.Cst + pr * H,
+                           c.hid + pr * H, b, H, r0, dropout_p, seed, l, drop, s));
+        continue;
+      }
+      RC(rows_dropout(below, c.sv + c.L.X + (size_t)B * H, r0, r1, H, dropout_p, seed, l, drop, s));
+      RC(seqd::input_chain(c.d, c.L, c.sv, B + r0, B + r1, f.skws, kSplitKWs, s, f.skctr));
+      RC(seqd::recur(c, offe, bse.data(), t + 1, t1 + 1, f.skws, f.skctr, err_flag, s));
+    }
+    t = t1;
+  }
+  return kOk;
+}
+
+// BPTT of att_seq_forward_stacked, top layer first: a layer's input gradient is the hidden-state gradient of the layer
+// below (only the top layer feeds C); layer 0's backward is att_seq_backward on it.
+int att_seq_backward_stacked(const AttDims& d, int nlayers, const int* bs, const float* dH_top, const float* dalphas_bt,
+                             const float* const* hiddens, const float* feat, const AttWeights& w0,
+                             const float* const* saved, const int* const* saved_i, float* scratch, float* const* dH_work,
+                             const AttGrads& g0, const SeqGrads* gu, const UpperInitGrads* giu, float dropout_p,
+                             unsigned long long seed, int training, hipStream_t s) {
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8 && hiddens && saved && saved_i && scratch &&
+                     (nlayers == 1 || (dH_work && gu && giu)),
+                 "att_seq_backward_stacked: bad argument (layers %d)", nlayers);
+  const float* dH = dH_top;
+  if (nlayers > 1) {
+    RC(check(d, bs));
+    const SeqDims ud = upper_ext_dims(d);
+    const int B = d.B, H = d.H, C = d.C;
+    std::vector<int> bse(ud.steps);
+    bse[0] = B;
+    for (int t = 0; t < d.steps; ++t) bse[t + 1] = bs[t];
+    size_t o = att_bwd_scratch_floats(d);
+    const size_t u = seqd::seq_bwd_upper_scratch_floats(ud);
+    o = ((o > u ? o : u) + 3) / 4 * 4;
+    float* dh0 = scratch + o;
+    float* dc0 = dh0 + (size_t)B * H;
+    const float* mean = saved[0] + make_alayout(d).mean;
+    for (int l = nlayers - 1; l >= 1; --l) {
+      CAPNET_REQUIRE(dH_work[l - 1] && hiddens[l] && saved[l] && saved_i[l], "att_seq_backward_stacked: null buffer of layer %d", l);
+      const UpperInitGrads& gi = giu[l - 1];
+      CAPNET_REQUIRE(gi.dWih && gi.dbih && gi.dWic && gi.dbic, "att_seq_backward_stacked: null initial-state gradient");
+      RC(seqd::seq_backward_upper(ud, bse.data(), dH, hiddens[l], saved[l], saved_i[l], scratch, gu[l - 1], dropout_p, seed,
+                                  training, l, dH_work[l - 1], dh0, dc0, s));
+      // init_h{l} / init_c{l}: all B rows are alive at the first step
+      RC(sgemm(true, false, H, C, B, dh0, H, mean, C, gi.dWih, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+      RC(colsum(dh0, H, B, H, gi.dbih, 0, s));
+      RC(sgemm(true, false, H, C, B, dc0, H, mean, C, gi.dWic, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+      RC(colsum(dc0, H, B, H, gi.dbic, 0, s));
+      dH = dH_work[l - 1];
+    }
+  }
+  return att_seq_backward(d, bs, dH, dalphas_bt, hiddens[0], feat, w0, saved[0], saved_i[0], scratch, g0, dropout_p, seed,
+                          training, s);
 }
 
 }  // namespace capnet

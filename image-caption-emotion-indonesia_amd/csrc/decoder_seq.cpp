@@ -17,16 +17,11 @@
 #include "common.h"
 #include "kernels.h"
 
+#include "seq_layers.h"
+
 namespace capnet {
 
-namespace {
-
-struct Layout {
-  // saved float buffer
-  size_t X, A1, A2, G, Cst, Vcat, Scat, Ucat, Wcat, Wfrag, Wp, bV, bS, bUW, total;
-  // int buffer
-  size_t row_sample, row_col, row_token, prev_row, ctl, itotal;
-};
+namespace seqd {
 
 Layout make_layout(const SeqDims& d) {
   Layout L;
@@ -85,13 +80,10 @@ int check_dims(const SeqDims& d, const int* batch_sizes) {
   return kOk;
 }
 
-struct GateOrder { int gi, gf, go, gg, tanh_out; };
 GateOrder gate_order(int cell) {
   // FactoredLSTM packs i,f,o,c~ ; nn.LSTMCell stores i,f,g,o
   return cell == kCellFactored ? GateOrder{0, 1, 2, 3, 0} : GateOrder{0, 1, 3, 2, 1};
 }
-
-#define RC(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
 int copy_d2d(float* dst, const float* src, size_t n, hipStream_t s) {
   CAPNET_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -101,7 +93,7 @@ int copy_d2d(float* dst, const float* src, size_t n, hipStream_t s) {
 // gate pre-activations of rows [r0, r1) from their inputs X. ws: slab workspace of the per-step
 // (few rows) products; the all-rows call up front has enough tiles for the plain kernel.
 int input_chain(const SeqDims& d, const Layout& L, float* sv, int r0, int r1, float* ws,
-                size_t ws_floats, hipStream_t s, int* ctr = nullptr) {
+                size_t ws_floats, hipStream_t s, int* ctr) {
   const int n = r1 - r0;
   if (n <= 0) return kOk;
   const int E = d.E, F = d.F, H = d.H;
@@ -127,13 +119,12 @@ int input_chain(const SeqDims& d, const Layout& L, float* sv, int r0, int r1, fl
   return kOk;
 }
 
-}  // namespace
+}  // namespace seqd
+
+using namespace seqd;
 
 size_t seq_saved_floats(const SeqDims& d) { return make_layout(d).total; }
 size_t seq_saved_ints(const SeqDims& d) { return make_layout(d).itotal; }
-
-constexpr size_t kSplitKFloats = 32ull * 64 * 2048;  // slabs for the per-step skinny GEMMs (16 MB)
-constexpr size_t kSplitKWs = kSplitKFloats - kSplitKCounters;   // slabs | tile counters of the one-launch products (<= 16 rows)
 
 size_t seq_fwd_scratch_floats(const SeqDims& d) { return (size_t)d.B * d.V + 64 + kSplitKFloats; }
 
@@ -144,18 +135,7 @@ size_t seq_bwd_scratch_floats(const SeqDims& d) {
   return n;
 }
 
-namespace {
-// one layer of the (possibly stacked) recurrence: its dims (E = its input width), saved buffers and output rows
-struct LayerCtx {
-  SeqDims d;
-  Layout L;
-  float* sv;
-  int* svi;
-  float* hid;
-  bool fused_step = false, persist = false;
-  int segment = 0;
-};
-
+namespace seqd {
 // gate-concatenated weight copies, the fused-step fragment image and the persistent kernel's image
 int pack_layer(LayerCtx& c, const SeqWeights& w, const int* batch_sizes, hipStream_t s) {
   const SeqDims& d = c.d;
@@ -238,7 +218,7 @@ SeqDims upper_dims(const SeqDims& d0) {
   d.has_features = 0;
   return d;
 }
-}  // namespace
+}  // namespace seqd
 
 SeqDims seq_upper_dims(const SeqDims& d0) { return upper_dims(d0); }
 
@@ -337,19 +317,22 @@ int seq_forward(const SeqDims& d, const int* batch_sizes, const unsigned char* t
 }
 
 // layer > 0 (a stacked layer above the first): the input gradient goes to dH_below = d hidden of the layer below (through
-// the dropout between the layers) instead of the embedding / feature scatter
+// the dropout between the layers) instead of the embedding / feature scatter.
+// lead = 1: step 0 is the layer's given initial state (seq_backward_upper); lead = 0: the state starts at zero.
 static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,
                               const float* saved, const int* saved_i, float* scratch, const SeqGrads& g,
                               float dropout_p, unsigned long long seed, int training, int layer, float* dH_below,
-                              hipStream_t s) {
+                              hipStream_t s, int lead = 0, float* dh0 = nullptr, float* dc0 = nullptr) {
   RC(check_dims(d, batch_sizes));
   CAPNET_REQUIRE(dH && hiddens && saved && saved_i && scratch, "seq_backward: null argument");
   CAPNET_REQUIRE(g.dWcat && g.dbUW && g.dVcat && (layer > 0 ? dH_below != nullptr : g.dEmb != nullptr), "seq_backward: null gradient buffer");
+  CAPNET_REQUIRE(lead == 0 || (layer > 0 && d.steps > 1 && dh0 && dc0 && d.cell == kCellFactored), "seq_backward: leading state step");
   const Layout L = make_layout(d);
   const int E = d.E, F = d.F, H = d.H, N = d.N;
   const GateOrder go = gate_order(d.cell);
   std::vector<int> off(d.steps + 1, 0);
   for (int t = 0; t < d.steps; ++t) off[t + 1] = off[t] + batch_sizes[t];
+  const int R0 = off[lead], Nr = N - R0;       // rows computed by the forward (the leading state step's are given)
 
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
@@ -365,17 +348,20 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
     dA1 = scratch + take((size_t)N * 4 * F);
   }
   float* skws = scratch + take(kSplitKFloats);
+  // the chain's intermediate rows: saved by the forward, or (lead) formed here over all rows
+  float* A1c = lead ? scratch + take((size_t)Nr * 4 * F) : nullptr;
+  float* A2c = lead ? scratch + take((size_t)Nr * 4 * F) : nullptr;
   const float* sv = saved;
   CAPNET_HIP_CHECK(hipMemsetAsync(dh_rec, 0, (size_t)d.B * H * sizeof(float), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(dc, 0, (size_t)d.B * H * sizeof(float), s));
 
   int slabs = 0;   // > 0: dh of the following step is still in `skws` as K-chunk slabs
-  for (int t = d.steps - 1; t >= 0; --t) {
+  for (int t = d.steps - 1; t >= lead; --t) {
     const int b = batch_sizes[t], r0 = off[t];
     const int b_next = (t + 1 < d.steps) ? batch_sizes[t + 1] : 0;
     RC(lstm_pointwise_bwd(sv + L.G + (size_t)r0 * 4 * H, 4 * H, sv + L.Cst + (size_t)r0 * H,
                           t > 0 ? sv + L.Cst + (size_t)off[t - 1] * H : nullptr,
-                          dH + (size_t)r0 * H, slabs > 0 ? skws : dh_rec, dc, dPre + (size_t)r0 * 4 * H,
+                          dH + (size_t)(r0 - R0) * H, slabs > 0 ? skws : dh_rec, dc, dPre + (size_t)r0 * 4 * H,
                           4 * H, b, b_next, H, go.gi, go.gf, go.go, go.gg, go.tanh_out, s, slabs,
                           (long)b_next * H));
     slabs = 0;
@@ -389,35 +375,51 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
                         dh_rec, H, nullptr, 0, skws, kSplitKFloats, s));
     }
   }
+  if (lead) {
+    // d h0 (all rows of the first step are alive), d c0
+    if (slabs) RC(reduce_slabs(skws, slabs, batch_sizes[0], H, dh_rec, H, nullptr, 0, s));
+    RC(copy_d2d(dh0, dh_rec, (size_t)batch_sizes[0] * H, s));
+    RC(copy_d2d(dc0, dc, (size_t)batch_sizes[0] * H, s));
+  }
+  const float* X = sv + L.X + (size_t)R0 * E;
+  const float* A1 = sv + L.A1;
+  const float* A2 = sv + L.A2;
+  if (lead) {
+    RC(sgemm_splitk(false, true, Nr, 4 * F, E, X, E, sv + L.Vcat, E, A1c, 4 * F, sv + L.bV, 0, skws, kSplitKFloats, s));
+    RC(sgemm(false, true, Nr, F, F, A1c, 4 * F, sv + L.Scat, F, A2c, 4 * F, sv + L.bS, 0, 4, F, (long)F * F, F, F, 0, s));
+    A1 = A1c;
+    A2 = A2c;
+  }
   // recurrent weight gradient over all steps at once: dWcat = dPre^T . h_{t-1}
-  RC(gather_rows(hiddens, saved_i + L.prev_row, Hprev, N, H, s));
-  RC(sgemm_splitk(true, false, 4 * H, H, N, dPre, 4 * H, Hprev, H, g.dWcat, H, nullptr, 0, skws, kSplitKFloats, s));
-  RC(colsum(dPre, 4 * H, N, 4 * H, g.dbUW, 0, s));
+  dPre += (size_t)R0 * 4 * H;
+  RC(gather_rows(hiddens, saved_i + L.prev_row + R0, Hprev, Nr, H, s));
+  RC(sgemm_splitk(true, false, 4 * H, H, Nr, dPre, 4 * H, Hprev, H, g.dWcat, H, nullptr, 0, skws, kSplitKFloats, s));
+  RC(colsum(dPre, 4 * H, Nr, 4 * H, g.dbUW, 0, s));
 
   if (d.cell == kCellFactored) {
     CAPNET_REQUIRE(g.dUcat && g.dScat && g.dbS && g.dbV, "seq_backward: null factored gradient buffer");
     // U: dU_g = dPre_g^T . A2_g ; dA2_g = dPre_g . U_g
-    RC(sgemm(true, false, H, F, N, dPre, 4 * H, sv + L.A2, 4 * F, g.dUcat, F, nullptr, 0, 4, H, F,
+    RC(sgemm(true, false, H, F, Nr, dPre, 4 * H, A2, 4 * F, g.dUcat, F, nullptr, 0, 4, H, F,
              (long)H * F, 0, 0, s));
-    RC(sgemm(false, false, N, F, H, dPre, 4 * H, sv + L.Ucat, F, dA2, 4 * F, nullptr, 0, 4, H,
+    RC(sgemm(false, false, Nr, F, H, dPre, 4 * H, sv + L.Ucat, F, dA2, 4 * F, nullptr, 0, 4, H,
              (long)H * F, F, 0, 0, s));
-    RC(colsum(dA2, 4 * F, N, 4 * F, g.dbS, 0, s));
+    RC(colsum(dA2, 4 * F, Nr, 4 * F, g.dbS, 0, s));
     // S: dS_g = dA2_g^T . A1_g ; dA1_g = dA2_g . S_g
-    RC(sgemm(true, false, F, F, N, dA2, 4 * F, sv + L.A1, 4 * F, g.dScat, F, nullptr, 0, 4, F, F,
+    RC(sgemm(true, false, F, F, Nr, dA2, 4 * F, A1, 4 * F, g.dScat, F, nullptr, 0, 4, F, F,
              (long)F * F, 0, 0, s));
-    RC(sgemm(false, false, N, F, F, dA2, 4 * F, sv + L.Scat, F, dA1, 4 * F, nullptr, 0, 4, F,
+    RC(sgemm(false, false, Nr, F, F, dA2, 4 * F, sv + L.Scat, F, dA1, 4 * F, nullptr, 0, 4, F,
              (long)F * F, F, 0, 0, s));
-    RC(colsum(dA1, 4 * F, N, 4 * F, g.dbV, 0, s));
+    RC(colsum(dA1, 4 * F, Nr, 4 * F, g.dbV, 0, s));
     // V: dVcat = dA1^T . X ; dX = dA1 . Vcat
-    RC(sgemm(true, false, 4 * F, E, N, dA1, 4 * F, sv + L.X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-    RC(sgemm_splitk(false, false, N, E, 4 * F, dA1, 4 * F, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
+    RC(sgemm(true, false, 4 * F, E, Nr, dA1, 4 * F, X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+    RC(sgemm_splitk(false, false, Nr, E, 4 * F, dA1, 4 * F, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
                     kSplitKFloats, s));
   } else {
     RC(sgemm(true, false, 4 * H, E, N, dPre, 4 * H, sv + L.X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
     RC(sgemm_splitk(false, false, N, E, 4 * H, dPre, 4 * H, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
                     kSplitKFloats, s));
   }
-  if (layer > 0) return rows_dropout(dX, dH_below, 0, N, E, dropout_p, seed, layer, training && dropout_p > 0.f, s);
+  if (layer > 0) return rows_dropout(dX, dH_below, 0, Nr, E, dropout_p, seed, layer, training && dropout_p > 0.f, s);
   CAPNET_HIP_CHECK(hipMemsetAsync(g.dEmb, 0, (size_t)d.V * E * sizeof(float), s));
   if (g.dFeat) CAPNET_HIP_CHECK(hipMemsetAsync(g.dFeat, 0, (size_t)d.B * E * sizeof(float), s));
   // (the split-K slab area is free by now: the scatter's two integer tables over the vocabulary go there)
@@ -425,6 +427,18 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
                         saved_i + L.row_token, g.dEmb, g.dFeat, d.V, dropout_p, seed,
                         training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kSplitKFloats));
   return kOk;
+}
+
+int seqd::seq_backward_upper(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,
+                             const float* saved, const int* saved_i, float* scratch, const SeqGrads& g, float dropout_p,
+                             unsigned long long seed, int training, int layer, float* dH_below, float* dh0, float* dc0,
+                             hipStream_t s) {
+  return seq_backward_layer(d, batch_sizes, dH, hiddens, saved, saved_i, scratch, g, dropout_p, seed, training, layer,
+                            dH_below, s, 1, dh0, dc0);
+}
+
+size_t seqd::seq_bwd_upper_scratch_floats(const SeqDims& d) {
+  return seq_bwd_scratch_floats(d) + 2 * ((size_t)d.N * 4 * d.F + 4);
 }
 
 int seq_backward(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,

@@ -238,6 +238,13 @@ int lstm_step_fused(const float* hprev, const float* Wfrag, float* G, long ldg, 
                     float* c_out, float* h_out, int b, int H, int gi, int gf, int go, int gg,
                     int tanh_out, hipStream_t stream, unsigned long long* stamps = nullptr);
 
+// lstm_upper_step.hip: one step of a stacked layer above the first (<= 16 rows): dropout of the layer below's rows, the
+// collapsed chain and the recurrent product as one product, the gates -- one launch
+bool lstm_upper_step_supported(int b, int H);
+int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
+                    const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
+                    unsigned long long seed, int layer, int use_dropout, hipStream_t stream);
+
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
 size_t lstm_persist_w_floats();
@@ -396,5 +403,25 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
                      const float* hiddens, const float* feat, const AttWeights& w,
                      const float* saved, const int* saved_i, float* scratch, const AttGrads& g,
                      float dropout_p, unsigned long long seed, int training, hipStream_t s);
+
+// stacked attention decoder (capnet.stacked_att): layer 0 is att_seq_forward's cell, layers l > 0 the factored cell on
+// dropout(h^{l-1}_t) with initial state init_h{l} / init_c{l} of the mean feature. hiddens[0]: [N][H]; hiddens[l > 0]:
+// [B + N][H], rows 0..B-1 the initial state. Upper weights: SeqWeights + init_h{l} w, b, init_c{l} w, b.
+struct UpperInit { const float* init_h_w; const float* init_h_b; const float* init_c_w; const float* init_c_b; };
+struct UpperInitGrads { float* dWih; float* dbih; float* dWic; float* dbic; };
+size_t att_stacked_saved_floats(const AttDims& d, int layer);
+size_t att_stacked_saved_ints(const AttDims& d, int layer);
+size_t att_stacked_fwd_scratch_floats(const AttDims& d, int nlayers);
+size_t att_stacked_bwd_scratch_floats(const AttDims& d, int nlayers);
+int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const unsigned char* tf, const long long* captions,
+                            const float* feat, const float* emb, const AttWeights& w0, const SeqWeights* wu,
+                            const UpperInit* iu, const float* Cw, const float* Cb, float dropout_p, unsigned long long seed,
+                            int training, float* const* saved, int* const* saved_i, float* scratch, float* const* hiddens,
+                            float* alphas_bt, int* err_flag, hipStream_t s);
+int att_seq_backward_stacked(const AttDims& d, int nlayers, const int* bs, const float* dH_top, const float* dalphas_bt,
+                             const float* const* hiddens, const float* feat, const AttWeights& w0,
+                             const float* const* saved, const int* const* saved_i, float* scratch, float* const* dH_work,
+                             const AttGrads& g0, const SeqGrads* gu, const UpperInitGrads* giu, float dropout_p,
+                             unsigned long long seed, int training, hipStream_t s);
 
 }  // namespace capnet

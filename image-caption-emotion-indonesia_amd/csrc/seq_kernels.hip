@@ -4,24 +4,11 @@
 // Packed ("time-major") row order is torch's pack_padded_sequence order used by
 // stylenet/model.py:173-194: rows of step t are contiguous, sample order preserved.
 #include "common.h"
+#include "dropout_mask.h"
 #include "kernels.h"
 
 namespace capnet {
 
-// counter-based dropout mask: keep iff u(seed, sample, col, e) >= p. Recomputed in backward.
-__device__ __forceinline__ float dropout_scale(unsigned long long seed, int sample, int col, int e,
-                                               float p, float inv_keep) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull *
-                                    ((((unsigned long long)(unsigned)sample << 20) ^
-                                      ((unsigned long long)(unsigned)col << 10)) *
-                                         1000003ull +
-                                     (unsigned long long)(unsigned)e + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
-  return u >= p ? inv_keep : 0.f;
-}
 
 // ---- row bookkeeping, built on device from kernel arguments (no H2D copy, no sync) -------
 // row r of step t (rows of a step are contiguous, sample j at offset j):

@@ -438,6 +438,35 @@ int capnet_att_seq_backward(const int* dims, const int* batch_sizes, const float
                             float* scratch, float* const* grads, float dropout_p,
                             unsigned long long seed, int training, capnet_stream_t stream);
 
+/* Stacked attention decoder (capnet.stacked_att.StackedFactoredLSTMAtt; PERF-ONLY, PARITY UNPINNED: the reference
+ * ignores num_layers). Layer 0 is capnet_att_seq_forward's cell (factored only); layer l > 0 is the factored cell on
+ * dropout_l(h^{l-1}_t) (the mask capnet_rows_dropout draws for layer l, training only) with initial state
+ * init_h{l} / init_c{l}(mean over pixels); only the top layer feeds C (the argmax of free-running steps).
+ * dims: as capnet_att_seq_forward. saved[l] / saved_i[l]: capnet_att_stacked_saved_floats / _ints(dims, l) each;
+ * hiddens[0]: [N][H]; hiddens[l > 0]: [B + N][H] (rows 0..B-1 the layer's initial state, then the packed rows).
+ * weights: layer 0's 44 tensors of capnet_att_seq_forward, then per layer l > 0 36: the 32 of capnet_seq_forward (V w x4
+ * ([F][H]), V b x4, S w x4, S b x4, U w x4, U b x4, W w x4, W b x4), init_h{l} w [H][C], b, init_c{l} w, b.
+ * A lone step of an upper layer with <= 16 rows is one launch (the fused upper step) unless the environment has
+ * CAPNET_NO_FUSED_UPPER_STEP=1 at the call. */
+size_t capnet_att_stacked_saved_floats(const int* dims, int layer);
+size_t capnet_att_stacked_saved_ints(const int* dims, int layer);
+size_t capnet_att_stacked_fwd_scratch_floats(const int* dims, int nlayers);
+size_t capnet_att_stacked_bwd_scratch_floats(const int* dims, int nlayers);
+int capnet_att_seq_forward_stacked(const int* dims, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
+                                   const long long* captions, const float* features, const float* emb,
+                                   const float* const* weights, const float* Cw, const float* Cb, float dropout_p,
+                                   unsigned long long seed, int training, float* const* saved, int* const* saved_i,
+                                   float* scratch, float* const* hiddens, float* alphas, int* err_flag,
+                                   capnet_stream_t stream);
+/* grads: layer 0's 16 buffers of capnet_att_seq_backward, then per layer l > 0 eleven: d V [4F][H], d bV [4F],
+ * d S [4][F][F], d bS [4F], d U [4][H][F], d bUW [4H] (of both the U and the W bias), d W [4H][H], d init_h{l} w [H][C],
+ * b [H], d init_c{l} w, b. d_hiddens: the top layer's packed rows [N][H]; dh_work: nlayers - 1 buffers [N][H]. */
+int capnet_att_seq_backward_stacked(const int* dims, int nlayers, const int* batch_sizes, const float* d_hiddens,
+                                    const float* d_alphas, const float* const* hiddens, const float* features,
+                                    const float* const* weights, const float* const* saved, const int* const* saved_i,
+                                    float* scratch, float* const* dh_work, float* const* grads, float dropout_p,
+                                    unsigned long long seed, int training, capnet_stream_t stream);
+
 /* Single-step pieces used by forward_step() / sample() (no autograd):
  *   out[r] = emb[idx[r]]                      -- self.B(k_prev_words), stylenet/model.py:221
  *   gate pointwise on pre-activations [b][4H] (in place: overwritten by the activated gates),
