@@ -471,9 +471,27 @@ def _resolve_tf_mask(tf_mask, n_steps, teacher_forcing_ratio):
     return [bool(x) for x in tf_mask[:n_steps]]
 
 
+def _splitmix64(x):
+    """splitmix64 of x: a bijection of the 64-bit integers."""
+    m = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
 def _dropout_seed(training, p):
+    """Seed of the decoders' dropout mask (csrc/dropout_mask.h), one torch draw per forward. Under an initialised
+    process group of more than one rank the draw is XORed with splitmix64(rank): ranks seed torch alike and key the
+    mask by their LOCAL sample index, so without it local row i would get the same mask on every rank. Every rank still
+    consumes the same draw, the seeds are pairwise different (XOR with a bijection of the rank), and a process
+    without a process group keeps the plain draw."""
     if training and p > 0:
-        return int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            seed ^= _splitmix64(dist.get_rank())
+        return seed
     return 0
 
 

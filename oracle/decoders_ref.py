@@ -94,26 +94,36 @@ def factored_lstm_forward(p, captions, lengths, features, tf_mask, mode="factual
                 p["C.bias"], captions, lengths, features, tf_mask, H, drop_mask)[0]
 
 
-def stacked_factored_lstm_forward(p, captions, lengths, features, tf_mask, mode="factual", num_layers=2):
+def stacked_factored_lstm_forward(p, captions, lengths, features, tf_mask, mode="factual", num_layers=2,
+                                  drop_mask=None, layer_masks=None):
     """capnet.stacked.StackedFactoredLSTM.forward restated on the CPU. PARITY UNPINNED: the reference ignores num_layers
     (stylenet/model.py:37); this is SURVEY App. A-1's definition -- layer l > 0 is the factored cell of model.py:115-155
     on the hidden state of the layer below at the same step (parameters `V1_i`, `S1_fi`, ...), the top layer feeds C,
-    the loop is model.py:157-196 -- and what it pins is the GPU engine to an independent statement of that definition."""
+    the loop is model.py:157-196 -- and what it pins is the GPU engine to an independent statement of that definition.
+
+    drop_mask: optional [B, T, E] mask of the embeddings, as in _run. layer_masks: optional {l: [N, H]} masks (already
+    scaled) of layer l > 0's input, indexed by packed row; a layer without an entry takes its input unmasked."""
     H = p["W_i.weight"].shape[0]
     B = captions.size(0)
     emb_w = p["B.weight"]
     embeddings = emb_w[captions]
+    if drop_mask is not None:
+        embeddings = embeddings * drop_mask
     if features is not None:
         embeddings = torch.cat((features.unsqueeze(1), embeddings), 1)
     bs = batch_sizes(lengths)
+    layer_masks = layer_masks or {}
     hs = [torch.zeros(B, H, dtype=emb_w.dtype) for _ in range(num_layers)]
     cs = [torch.zeros(B, H, dtype=emb_w.dtype) for _ in range(num_layers)]
     sfx = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}[mode]
     hiddens = []
     predicted = captions[:, 0:1]
+    r0 = 0
     for i, b in enumerate(bs):
         x = embeddings[:b, i, :] if tf_mask[i] else emb_w[predicted][:b, 0, :]
         for l in range(num_layers):
+            if l in layer_masks:
+                x = x * layer_masks[l][r0:r0 + b]
             tag = "" if l == 0 else str(l)
             pre = []
             for g in "ifoc":
@@ -126,6 +136,7 @@ def stacked_factored_lstm_forward(p, captions, lengths, features, tf_mask, mode=
             x = hs[l]
         hiddens.append(x)
         predicted = Fn.linear(x, p["C.weight"], p["C.bias"]).max(1)[1].unsqueeze(1)
+        r0 += b
     return Fn.linear(torch.cat(hiddens, 0), p["C.weight"], p["C.bias"])
 
 

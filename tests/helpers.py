@@ -27,3 +27,13 @@ def golden_params(z):
 def golden_case(z, cname):
     pre = "case.%s." % cname
     return {k[len(pre):]: z[k] for k in z.files if k.startswith(pre)}
+
+
+def pin_dropout_seed(k):
+    """torch.manual_seed(k) and the dropout seed the next decoder forward (training, p > 0, no process group) will
+    draw: capnet.model._dropout_seed's one torch.randint(0, 2**62, (1,)), the first torch draw of a forward. The
+    generator is left re-seeded with k, so call the decoder right after this."""
+    torch.manual_seed(k)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    torch.manual_seed(k)
+    return seed
