@@ -10,14 +10,22 @@ decoder forward (teacher forcing 0.8, dropout 0.5) + softmax-NLL + backward + el
 + Adam, on a batch of 64 synthetic 224x224 images per GPU (BASELINE.json configs[1]; weak
 scaling for N > 1 with one RCCL all-reduce of the flat gradient buffer per step). Inputs are
 resident in HBM before the timed region. Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the
+line (with the trunk's conv roofline, which the timed steps measure themselves). `--full` adds everything that takes
+runs of its own: the conv launches once more with nothing beside them, the LSTM-step / vocabulary-projection /
+attention-step microbenchmarks, the CPU baseline and the loss-parity leg against the oracle.
 """
+import time
+
+T_START = time.perf_counter()     # before torch's import: what a plain run spends outside its steps is logged
+
 import argparse
 import ctypes as C
 import json
 import os
 import random
 import sys
-import time
 
 import torch
 
@@ -43,7 +51,13 @@ def parse():
                     help="factored = BASELINE configs[1] (the headline); nic = config 0's decoder; "
                          "att = config 3's attention decoder (secondary workloads)")
     ap.add_argument("--dropout", type=float, default=0.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, after the timed steps: the conv "
+                         "roofline once more without the overlapped decoder, the LSTM-step, vocabulary-projection and "
+                         "attention-step rooflines, the CPU baseline and the loss parity against the oracle "
+                         "(--no-cpu-baseline / --no-lstm-roofline leave parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the loss-parity leg")
     ap.add_argument("--no-conv-events", action="store_true",
                     help="do not bracket conv kernels with hipEvents (roofline becomes null)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -64,8 +78,8 @@ def parse():
     ap.add_argument("--pipeline-depth", type=int, default=3,
                     help="trunk passes in flight ahead of the decoder")
     ap.add_argument("--no-lstm-roofline", action="store_true",
-                    help="skip the LSTM-step microbenchmark (PMC passes profile the train step only)")
-    ap.add_argument("--cpu-steps", type=int, default=5)
+                    help="with --full: skip the LSTM-step, vocabulary-projection and attention-step microbenchmarks")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="with --full: timed steps of the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one left its caller as DIR/<name>.npy (float32): "
                          "loss, and every parameter the step updated, with the gradient that produced the update "
@@ -553,7 +567,7 @@ def main():
                 "frac": round(f32x * per_s / MFMA_F32_PEAK_TFLOPS + (bf16x + f16x) * per_s / MFMA_BF16_PEAK_TFLOPS, 4),
                 "note": "flops the matrix pipes issued per second of conv time; frac = sum over the pipes of issued / "
                         "peak = roofline.frac"}
-            if pipe is not None:
+            if pipe is not None and args.full:
                 # In the timed region the convolutions share the chip with the previous batch's
                 # decoder (that is where the throughput comes from, and it lengthens each conv a
                 # little). For reference: the same kernels with nothing else running, 3 extra
@@ -575,7 +589,7 @@ def main():
     # secondary roofline: the recurrent LSTM step (5.77 MB of algorithmic HBM
     # traffic per step at b=64, H=512), timed with events on the launch stream
     lstm = None
-    if rank == 0 and not args.no_lstm_roofline:
+    if rank == 0 and args.full and not args.no_lstm_roofline:
         Hh, bb = 512, 64
         hp = torch.randn(bb, Hh, device=dev) * 0.1
         wc = torch.randn(4 * Hh, Hh, device=dev) * 0.05
@@ -693,7 +707,7 @@ def main():
     # the two other rooflines SURVEY.md 8(d) names, timed with events on the launch stream:
     # the vocabulary projection (MFMA) and the attention step after the encoder_att hoist (HBM)
     extra = None
-    if rank == 0 and not args.no_lstm_roofline:
+    if rank == 0 and args.full and not args.no_lstm_roofline:
         def timed(fn, reps):
             for _ in range(3):
                 fn()
@@ -775,8 +789,9 @@ def main():
                 "configs[1]: StyleNet FactoredLSTM (factored 512, hidden 512, 1 layer,",
                 "secondary (PERF-ONLY, PARITY UNPINNED: the reference ignores num_layers, capnet.stacked defines the "
                 "stacking): FactoredLSTM (factored %d, hidden 512, %d layers," % (args.factored, args.layers))
-        if world == 1 and not args.no_cpu_baseline and args.decoder == "factored" and args.layers == 1 and args.factored == 512:
-            # `metric` says "+ NLL loss match": the evidence is in the line itself. Untimed.
+        if (args.full and world == 1 and not args.no_cpu_baseline and args.decoder == "factored" and args.layers == 1
+                and args.factored == 512):
+            # `metric` says "+ NLL loss match": a --full line carries the evidence itself. Untimed.
             parity = gpu_parity_losses(dev, B, V)
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_steps, parity=parity)
             out["loss_parity"] = parity
@@ -786,6 +801,9 @@ def main():
         else:
             out["cpu_baseline"] = None
             out["loss_parity"] = None
+        wall = time.perf_counter() - T_START
+        log("%.1f s since start, %.1f s of it outside warm-up + timed steps counted at ms_per_step"
+            % (wall, wall - (args.warmup + args.steps) * elapsed / args.steps))
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     os.close(json_fd)
     if dist.is_initialized():

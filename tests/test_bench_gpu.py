@@ -26,7 +26,7 @@ def _run(cmd, env_extra, timeout=600):
 
 
 def test_bench_prints_one_json_line():
-    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
+    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], {})
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "images/sec" and d["scaling"] == "weak"
     assert d["value"] > 0 and math.isfinite(d["loss_last"]) and d["dtype"].startswith("f32 (")
     r = d["roofline"]
@@ -41,6 +41,19 @@ def test_bench_prints_one_json_line():
     assert abs(sum(e[pipe]["share_of_algorithmic_flops"] for pipe in ("f32_mfma", "f16_mfma", "bf16_mfma")) - 1) < 1e-3
     assert r["traffic"] is None or "offline" in r["traffic_source"]
     assert d["roofline_lstm_step"]["bound"] == "hbm"
+    assert r["alone"]["achieved"] > 0 and d["roofline_other"]["vocab_projection"]["bound"] == "mfma"
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full the line carries what the timed steps measured (the headline and the conv roofline of their
+    trunk passes) and nothing that takes runs of its own: no second trunk pass, no microbenchmark, no CPU leg."""
+    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"], {})
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["ms_per_step"] - 64 * 1e3 / d["value"]) < 1e-2 * d["ms_per_step"]
+    assert d["metric"].startswith("images/sec") and d["higher_is_better"] is True and d["dtype"].startswith("f32 (")
+    assert d["roofline"]["frac"] > 0 and "alone" not in d["roofline"]
+    assert d["roofline_lstm_step"] is None and d["roofline_other"] is None
+    assert d["cpu_baseline"] is None and d["loss_parity"] is None
 
 
 def test_bench_dumps_the_last_step(tmp_path):
