@@ -305,6 +305,23 @@ int capnet_lstm_pointwise_fwd(float* pre, const float* c_prev, float* c_out, flo
   return lstm_pointwise_fwd(pre, 4L * H, c_prev, c_out, h_out, b, H, 0, 1, 3, 2, 1, S(stream));
 }
 
+int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                               const float* const* wcat, const float* const* beff, const float* state_in,
+                               float* state_out, float* h_top, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "stacked_decode_step: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(rows >= 1, "stacked_decode_step: rows %d", rows);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H), "stacked_decode_step: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE(x && wcat && beff && state_in && state_out && h_top, "stacked_decode_step: null argument");
+  CAPNET_REQUIRE(!tokens || (err_flag && V >= 1), "stacked_decode_step: token ids need err_flag and V >= 1");
+  CAPNET_REQUIRE(state_in != state_out, "stacked_decode_step: state_in and state_out must differ");
+  CAPNET_REQUIRE(aligned16(state_in) && aligned16(state_out), "stacked_decode_step: state alignment");
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "stacked_decode_step: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "stacked_decode_step: weights of layer %d not 16-B aligned", l);
+  }
+  return stacked_decode_step(nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top, err_flag,
+                             S(stream));
+}
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream) {
   CAPNET_REQUIRE(gates && c && dh && dc_io && dpre && b >= 0 && H > 0, "lstm_pointwise_bwd: bad argument");

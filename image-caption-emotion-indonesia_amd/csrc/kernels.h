@@ -245,6 +245,13 @@ int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, co
                     const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
                     unsigned long long seed, int layer, int use_dropout, hipStream_t stream);
 
+// lstm_decode_step.hip: one inference step of every layer of a stacked factored LSTM (beam search), one launch per
+// layer, any number of rows: [x | h] . [Weff | W]^T + beff and the gates; layer 0 gathers its embedding rows by token id
+bool stacked_decode_supported(int E, int H);
+int stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                        const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
+                        float* h_top, int* err_flag, hipStream_t stream);
+
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
 size_t lstm_persist_w_floats();

@@ -1,0 +1,211 @@
+// One inference step of one factored-LSTM layer of capnet.stacked.StackedFactoredLSTM, for any number of rows, in ONE
+// launch (beam-search decoding: k rows per image, n k rows per batched decode step):
+//   gates = [x | h_prev] . [Weff | W]^T + beff      Weff_g = U_g S_g V_g, beff_g = U_g (S_g bV_g + bS_g) + bU_g + bW_g
+//   i, f, o = sigmoid, c~ = tanh;  c = f c_prev + i c~;  h = o c      (no tanh on c, stylenet/model.py:147-153)
+// Inference has no dropout between V, S and U, so the chain folds into one H x in matrix per gate (the host folds it once
+// per decode, capnet.stacked). Layer 0's x is a row of the embedding table picked by token id (or a given input row),
+// layer l > 0's x is h of layer l-1 at the same step, which the previous launch of the same call has just written.
+//
+// Mapping: a workgroup owns 4 hidden units = 16 gate columns (one N tile of v_mfma_f32_16x16x4_f32) and ALL rows. Its 8
+// waves split K = kin + H (kin = in rounded up to the 16-wide k group; the weights carry zero columns there) into eight
+// contiguous ranges of k groups. Each lane loads its column's weights for its range once (NJ f32x4 registers: the
+// layer's weights cross HBM once per launch) and keeps them while the workgroup walks the rows 16 TM at a time: per pass a
+// lane reads 16 B of x or h_prev per k group for each of TM 16-row tiles -- k = 16 g + 4 (lane >> 4) + e feeds MFMA step
+// (g, e) in both operands, so row-major weights need no fragment image -- runs the tiles' MFMA chains interleaved (TM = 2;
+// TM = 1 at 16 groups per wave, where two tiles' operands and the weights would not fit in 256 VGPRs),
+// and the eight K-partial tiles are summed through LDS by the epilogue, which applies the gates and writes c, h (and the
+// top layer's h once more, densely, for the vocabulary projection). Plain vector loads and stores only.
+#include "common.h"
+#include "kernels.h"
+
+namespace capnet {
+
+typedef float f32x4d __attribute__((ext_vector_type(4)));
+
+constexpr int kDecWaves = 8;
+constexpr int kDecMaxK = 2048;       // kin + H <= 8 waves x 16 groups x 16
+
+struct DecodeLayerArgs {
+  const long long* tok;  // layer 0 with token ids: x row = x + tok[r] * ldx (else x + r * ldx)
+  const float* x;
+  long ldx;
+  int xn;                // valid columns of an x row (E or H); columns [xn, kin) read as zero
+  int xvec;              // x rows 16-B aligned and xn % 4 == 0: f32x4 loads
+  int V;                 // token ids must lie in [0, V)
+  int* err;              // set to 1 on an out-of-range id (the row then reads token 0)
+  const float* hprev;    // [rows] x stride lds_in
+  const float* cprev;
+  long lds_in;
+  float* h_out;
+  float* c_out;
+  long lds_out;
+  float* h_top;          // optional dense [rows, H] copy of h
+  const float* w;        // [4H, kin + H] = [Weff | W], gate blocks i, f, o, c~
+  const float* b;        // [4H]
+  int kin, rows, H;
+};
+
+__device__ __forceinline__ float sigm_d(float x) { return 1.f / (1.f + expf(-x)); }
+
+template <int NJ, int TM>  // k groups per wave (at most), 16-row tiles per pass
+__global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a) {
+  constexpr int kPass = 16 * TM;
+  __shared__ float red[kDecWaves][kPass][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lq = lane >> 4;
+  const int H = a.H, u0 = blockIdx.x * 4;
+  const int K = a.kin + H, KG = K >> 4, inG = a.kin >> 4;
+  const int g0 = wave * KG / kDecWaves, ng = (wave + 1) * KG / kDecWaves - g0;   // this wave's groups [g0, g0 + ng)
+  // B operand: column li = gate role li >> 2 (i, f, o, c~), unit u0 + (li & 3)
+  const float* wrow = a.w + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
+  f32x4d wv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    wv[j] = f32x4d{0.f, 0.f, 0.f, 0.f};
+    if (j < ng) wv[j] = *reinterpret_cast<const f32x4d*>(wrow + 16 * (g0 + j));
+  }
+  // epilogue thread: (row er of the pass, unit eu); threads 0 .. 64 TM - 1
+  const int er = tid >> 2, eu = tid & 3;
+  const bool ethread = tid < 4 * kPass;
+  float bias[4] = {0.f, 0.f, 0.f, 0.f};
+  if (ethread) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bias[g] = a.b[g * H + u0 + eu];
+  }
+  for (int r0 = 0; r0 < a.rows; r0 += kPass) {
+    f32x4d av[TM][NJ];
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      int row = r0 + 16 * m + li;
+      row = row < a.rows ? row : a.rows - 1;             // rows beyond the last: a clamped copy, never stored
+      long xr = row;
+      if (a.tok) {
+        const long long t = a.tok[row];
+        const bool ok = t >= 0 && t < a.V;
+        if (!ok && a.err) *a.err = 1;
+        xr = ok ? (long)t : 0;
+      }
+      const float* xrow = a.x + xr * a.ldx;
+      const float* hrow = a.hprev + (long)row * a.lds_in;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        f32x4d v = {0.f, 0.f, 0.f, 0.f};
+        const int g = g0 + j, k = 16 * g + 4 * lq;
+        if (j < ng) {
+          if (g >= inG) {
+            v = *reinterpret_cast<const f32x4d*>(hrow + (k - a.kin));
+          } else if (a.xvec) {
+            if (k < a.xn) v = *reinterpret_cast<const f32x4d*>(xrow + k);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = k + e < a.xn ? xrow[k + e] : 0.f;
+          }
+        }
+        av[m][j] = v;
+      }
+    }
+    const int erow = r0 + er;
+    const bool estore = ethread && erow < a.rows;
+    const float cp = estore ? a.cprev[(long)erow * a.lds_in + u0 + eu] : 0.f;
+    f32x4d acc[TM];
+#pragma unroll
+    for (int m = 0; m < TM; ++m) acc[m] = f32x4d{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (j < ng) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int m = 0; m < TM; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][j][e], wv[j][e], acc[m], 0, 0, 0);
+      }
+    }
+    // D layout of a 16x16 tile: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int m = 0; m < TM; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][16 * m + 4 * lq + r][li] = acc[m][r];
+    __syncthreads();
+    if (estore) {
+      float pre[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float s = bias[g];
+#pragma unroll
+        for (int w = 0; w < kDecWaves; ++w) s += red[w][er][g * 4 + eu];
+        pre[g] = s;
+      }
+      const float i = sigm_d(pre[0]), f = sigm_d(pre[1]), og = sigm_d(pre[2]), gt = tanhf(pre[3]);
+      const float c = f * cp + i * gt;
+      const float h = og * c;
+      a.c_out[(long)erow * a.lds_out + u0 + eu] = c;
+      a.h_out[(long)erow * a.lds_out + u0 + eu] = h;
+      if (a.h_top) a.h_top[(long)erow * H + u0 + eu] = h;
+    }
+    __syncthreads();   // red is rewritten by the next pass
+  }
+}
+
+static int round16(int v) { return (v + 15) / 16 * 16; }
+
+bool stacked_decode_supported(int E, int H) {
+  return E >= 1 && (H == 64 || H == 128 || H == 256 || H == 512 || H == 1024) && round16(E) + H <= kDecMaxK;
+}
+
+template <int NJ>
+static void launch_decode(const DecodeLayerArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
+}
+
+static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
+  const int per_wave = ((a.kin + a.H) / 16 + kDecWaves - 1) / kDecWaves;
+  if (per_wave <= 2) launch_decode<2>(a, stream);
+  else if (per_wave <= 4) launch_decode<4>(a, stream);
+  else if (per_wave <= 6) launch_decode<6>(a, stream);
+  else if (per_wave <= 8) launch_decode<8>(a, stream);
+  else if (per_wave <= 12) launch_decode<12>(a, stream);
+  else launch_decode<16>(a, stream);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                        const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
+                        float* h_top, int* err_flag, hipStream_t stream) {
+  const long lds = 2L * nlayers * H;
+  for (int l = 0; l < nlayers; ++l) {
+    DecodeLayerArgs a;
+    if (l == 0) {
+      a.tok = tokens;
+      a.x = x;
+      a.ldx = E;
+      a.xn = E;
+      a.xvec = E % 4 == 0 && aligned16(x);
+      a.kin = round16(E);
+    } else {
+      a.tok = nullptr;
+      a.x = state_out + (long)(2 * l - 2) * H;
+      a.ldx = lds;
+      a.xn = H;
+      a.xvec = 1;
+      a.kin = H;
+    }
+    a.V = V;
+    a.err = err_flag;
+    a.hprev = state_in + (long)(2 * l) * H;
+    a.cprev = state_in + (long)(2 * l + 1) * H;
+    a.lds_in = lds;
+    a.h_out = state_out + (long)(2 * l) * H;
+    a.c_out = state_out + (long)(2 * l + 1) * H;
+    a.lds_out = lds;
+    a.h_top = l == nlayers - 1 ? h_top : nullptr;
+    a.w = wcat[l];
+    a.b = beff[l];
+    a.rows = rows;
+    a.H = H;
+    int rc = launch_decode_layer(a, stream);
+    if (rc != kOk) return rc;
+  }
+  return kOk;
+}
+
+}  // namespace capnet

@@ -301,6 +301,45 @@ def lstm_cell(pre, c_prev, cell=0):
     return LstmCellFn.apply(pre, c_prev, cell)
 
 
+
+DECODE_HIDDEN = (64, 128, 256, 512, 1024)
+
+
+def stacked_decode_supported(E, H):
+    """The shapes capnet_stacked_decode_step takes (csrc/lstm_decode_step.hip: stacked_decode_supported)."""
+    return E >= 1 and H in DECODE_HIDDEN and (E + 15) // 16 * 16 + H <= 2048
+
+
+def stacked_decode_step(state, wcat, beff, x, tokens=None):
+    """One inference step of every layer of a stacked factored LSTM (capnet_stacked_decode_step, one launch per layer).
+    state [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = c); wcat[l] [4H, kin_l + H] = [folded chain | W], beff[l] [4H];
+    x: the embedding table [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E].
+    Returns (top-layer h [rows, H], the new state [rows, 2L, H])."""
+    _need_cuda(state, x, tokens, *wcat, *beff)
+    rows, L2, H = state.shape
+    nl = L2 // 2
+    if L2 != 2 * nl or len(wcat) != nl or len(beff) != nl:
+        raise CapnetError("stacked_decode_step: state [rows, 2L, H] and L weight pairs")
+    state, x = _c(state), _c(x)
+    E = x.shape[1]
+    if tokens is not None:
+        tokens = _c(tokens)
+        if tokens.dtype != torch.int64 or tokens.numel() != rows:
+            raise CapnetError("stacked_decode_step: tokens must be int64 [rows]")
+    elif x.shape[0] != rows:
+        raise CapnetError("stacked_decode_step: inputs must be [rows, E]")
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = (E + 15) // 16 * 16 if l == 0 else H
+        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
+            raise CapnetError("stacked_decode_step: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    out = torch.empty_like(state)
+    top = torch.empty((rows, H), dtype=torch.float32, device=state.device)
+    check(_lib.lib().capnet_stacked_decode_step(nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens),
+                                                ptr(x), ptr_array(wcat), ptr_array(beff), ptr(state), ptr(out), ptr(top),
+                                                ptr(err_flag(state.device)), current_stream()),
+          "capnet_stacked_decode_step")
+    return top, out
+
 def packed_targets(captions, lengths):
     """pack_padded_sequence(captions, lengths, batch_first=True)[0] for int64 captions."""
     _need_cuda(captions)

@@ -24,7 +24,17 @@ own backward through time (LstmRunFn below; H = 512, <= 128 rows) -- or, for a l
 kernel does not take, step by step (W GEMM + the fused cell kernel, ops.lstm_cell, torch autograd composing the
 backward). torch is glue here (embedding gather, dropout masks, bias adds, concatenations). The single-layer path's
 fused sequence driver (csrc/decoder_seq.cpp) is still the faster structure; it does not apply to stacked cells yet
-(DESIGN 7)."""
+(DESIGN 7).
+
+Decoding (forward_step / sample / sample_batch) runs the same stack at inference: no dropout anywhere, so each gate's
+chain folds into one matrix, Weff_g = U_g S_g V_g (H x in), and beff_g = U_g (S_g bV_g + bS_g) + bU_g + bW_g. The fold is
+done once per sample / sample_batch call, per layer, for the requested mode, with the library's GEMMs. A beam step is then
+one launch per layer (capnet_stacked_decode_step, csrc/lstm_decode_step.hip: [x | h] . [Weff | W]^T + beff and the gates;
+layer 0 gathers its embedding rows by token id itself), plus C and capnet_beam_topk. The beam state is ONE tensor
+[rows, 2L, H] (slot 2l = h of layer l, 2l+1 = its c), so re-ordering the beams is one index_select per step.
+CAPNET_NO_FUSED_DECODE_STEP=1 (read at every call) takes the composed step instead -- per layer the V, S, U and W
+products and the pointwise cell, unfolded -- which is also the path for shapes the kernel does not take."""
+import os
 import random
 import sys
 
@@ -40,6 +50,13 @@ from .model import Embedding as _Embedding, Linear as _Linear
 
 MODES = ("factual", "happy", "sad", "angry")
 _S_PREFIX = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}
+FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
+
+
+def _check_mode(mode):
+    if mode not in MODES:
+        sys.stderr.write("mode name wrong!")
+        raise ValueError("unknown mode %r" % (mode,))
 
 
 class LstmRunFn(torch.autograd.Function):
@@ -321,13 +338,111 @@ class StackedFactoredLSTM(nn.Module):
         _, _, _, W = self._mods(l, mode)
         return torch.cat([w.weight for w in W], 0), torch.cat([w.bias for w in W], 0)
 
+    # ---- decoding -----------------------------------------------------------------------------
+    def _fold(self, mode):
+        """[(wcat, beff)] per layer for capnet_stacked_decode_step: wcat [4H, kin + H] = [U_g S_g V_g, zero columns up
+        to kin | W_g] in gate blocks i, f, o, c~ (kin: the layer's input width rounded up to 16), beff [4H] =
+        U_g (S_g bV_g + bS_g) + bU_g + bW_g. Products on the GPU (capnet_sgemm)."""
+        H, dev = self.hidden_size, self.B.weight.device
+        out = []
+        for l in range(self.num_layers):
+            V, S, U, W = self._mods(l, mode)
+            n_in = V[0].in_features
+            kin = (n_in + 15) // 16 * 16
+            wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
+            beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
+            for g in range(4):
+                blk, bb = wcat[g * H:(g + 1) * H], beff[g * H:(g + 1) * H]
+                ops.sgemm(U[g].weight, ops.sgemm(S[g].weight, V[g].weight), out=blk[:, :n_in])       # [H, F][F, F][F, in]
+                blk[:, kin:].copy_(W[g].weight)
+                sb = ops.sgemm(V[g].bias.view(1, -1), S[g].weight, transB=True, bias=S[g].bias)       # S bV + bS
+                ops.sgemm(sb, U[g].weight, transB=True, bias=U[g].bias, out=bb.view(1, H))
+                bb += W[g].bias
+            out.append((wcat, beff))
+        return out
+
+    def _composed_step(self, x, state, mode):
+        """One inference step of the stack, unfolded: per layer the V, S, U and W products and the pointwise cell."""
+        new = torch.empty_like(state)
+        for l in range(self.num_layers):
+            V, S, U, W = self._mods(l, mode)
+            h = state[:, 2 * l].contiguous()
+            pre = torch.cat([U[k](S[k](V[k](x))) + W[k](h) for k in range(4)], 1)
+            h, c = ops.lstm_pointwise(pre, state[:, 2 * l + 1], ops.CELL_FACTORED)
+            new[:, 2 * l], new[:, 2 * l + 1] = h, c
+            x = h
+        return x, new
+
+    def _decode_stepper(self, mode):
+        """step(x, tokens, state [rows, 2L, H]) -> (top h [rows, H], state'): x is the embedding table when `tokens` is
+        given, else layer 0's inputs. The fused step (weights folded here, once) unless CAPNET_NO_FUSED_DECODE_STEP=1
+        or the shape is one the kernel does not take."""
+        fused = (os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and self.num_layers <= 8 and
+                 ops.stacked_decode_supported(self.embed_size, self.hidden_size))
+        if fused:
+            folded = self._fold(mode)
+            wcat, beff = [w for w, _ in folded], [b for _, b in folded]
+
+            def step(x, tokens, state):
+                return ops.stacked_decode_step(state, wcat, beff, x, tokens)
+        else:
+            def step(x, tokens, state):
+                if tokens is not None:
+                    x = ops.embedding(tokens, x)
+                return self._composed_step(x, state, mode)
+        return step
+
+    def forward_step(self, embedded, states, mode):
+        """One decode step of the stack at inference (no dropout) on layer 0's input `embedded` [rows, E]. states: every
+        layer's (h, c), as one tensor [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = its c) or a sequence of L (h, c)
+        pairs. Returns (the top layer's h [rows, H], the new states [rows, 2L, H]). Folds the weights on every call:
+        sample() / sample_batch() fold once per decode."""
+        _check_mode(mode)
+        with torch.no_grad():
+            if not isinstance(states, torch.Tensor):
+                states = torch.stack([t for hc in states for t in hc], 1)
+            return self._decode_stepper(mode)(embedded.detach(), None, states.detach())
+
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+        """Beam search, stylenet/model.py:198-294, over the stack: as DecoderFactoredLSTM.sample, the image is NOT an
+        input (`features` only fixes the device), every layer's state starts at zero, the first input is B(<start>) and
+        factual_limit is ignored. Returns LongTensor [1, L]."""
+        from .beam import beam_search
+        _check_mode(mode)
+        dev = self.B.weight.device
+        with torch.no_grad():
+            step, emb = self._decode_stepper(mode), self.B.weight.detach()
+
+            def step_fn(prev_words, state):
+                top, st = step(emb, prev_words, state[0])
+                return self.C(top), (st,)
+
+            zeros = torch.zeros((k, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=dev)
+            return beam_search(step_fn, (zeros,), self.vocab_size, start_token, end_token, k, self.max_seq_length, dev)
+
+    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+        """sample() for every row of `features` at once (capnet.beam.beam_search_batched). Returns a list of token lists,
+        each equal to sample(features[i:i+1], ...)[0].tolist()."""
+        from .beam import beam_search_batched
+        _check_mode(mode)
+        dev = self.B.weight.device
+        n = features.size(0)
+        with torch.no_grad():
+            step, emb = self._decode_stepper(mode), self.B.weight.detach()
+
+            def step_fn(prev_words, state):
+                top, st = step(emb, prev_words, state[0])
+                return self.C(top), (st,)
+
+            zeros = torch.zeros((n * k, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=dev)
+            return beam_search_batched(step_fn, (zeros,), n, self.vocab_size, start_token, end_token, k,
+                                       self.max_seq_length, dev)
+
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, captions, lengths, features=None, teacher_forcing_ratio=0.8, mode="factual", tf_mask=None):
         """-> packed logits [sum(lengths), V] in pack_padded_sequence order (stylenet/model.py:157-196 with stacked
         cells). tf_mask: the per-step teacher-forcing decisions (else one random.random() draw per step)."""
-        if mode not in MODES:
-            sys.stderr.write("mode name wrong!")
-            raise ValueError("unknown mode %r" % (mode,))
+        _check_mode(mode)
         if not captions.is_cuda:
             raise CapnetError("StackedFactoredLSTM runs on the GPU only")
         L, H = self.num_layers, self.hidden_size

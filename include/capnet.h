@@ -481,6 +481,21 @@ int capnet_lstm_pointwise_fwd(float* pre, const float* c_prev, float* c_out, flo
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream);
 
+/* One beam-search step of capnet.stacked.StackedFactoredLSTM (inference: no dropout), every layer, one launch per layer
+ * on `stream`; no host synchronisation, no allocation. Layer l computes, for `rows` rows,
+ *   gates = [x | h_prev] . wcat[l]^T + beff[l];  i, f, o = sigmoid, c~ = tanh;  c = f c_prev + i c~;  h = o c
+ * with wcat[l] [4H][kin_l + H] = [U_g S_g V_g (zero columns up to kin_l) | W_g] in gate blocks i, f, o, c~ and
+ * beff[l] [4H] = U_g (S_g bV_g + bS_g) + bU_g + bW_g (the chain folded on the host; stylenet/model.py:115-155 at
+ * inference). kin_0 = E rounded up to a multiple of 16, kin_l = H above. Layer 0's x: with `tokens` (int64 [rows]),
+ * row tokens[r] of the table x [V][E] (an id outside [0, V) sets *err_flag = 1 and reads row 0); without, x is the
+ * inputs [rows][E]. Layer l > 0's x is layer l-1's new h.
+ * state_in / state_out: [rows][2 nlayers][H] (slot 2l = h of layer l, 2l+1 = c), distinct, 16-B aligned;
+ * h_top [rows][H] receives the top layer's h once more. wcat / beff: HOST arrays of nlayers device pointers.
+ * H in {64, 128, 256, 512, 1024}, kin_0 + H <= 2048, 1 <= nlayers <= 8. */
+int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                               const float* const* wcat, const float* const* beff, const float* state_in,
+                               float* state_out, float* h_top, int* err_flag, capnet_stream_t stream);
+
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
  *   capnet_lstm_pack_wfrag image), then the gate
