@@ -15,6 +15,47 @@ static SeqDims to_dims(const int* d) {
   return r;
 }
 
+// the slots of a layer's 32-entry weight table its cell reads: all of the factored cell's; nn.LSTMCell's weight_ih,
+// bias_ih, weight_hh, bias_hh sit in slots 0 / 4 / 24 / 28 (V w, V b, W w, W b of the first gate)
+static bool weight_used(int cell, int i) { return cell == kCellFactored || i == 0 || i == 4 || i == 24 || i == 28; }
+template <class Weights>           // SeqWeights, or the cell part of AttWeights
+static void to_weights(const float* const* weights, Weights& w) {
+  for (int g = 0; g < 4; ++g) {
+    w.Vw[g] = weights[0 + g];  w.Vb[g] = weights[4 + g];
+    w.Sw[g] = weights[8 + g];  w.Sb[g] = weights[12 + g];
+    w.Uw[g] = weights[16 + g]; w.Ub[g] = weights[20 + g];
+    w.Ww[g] = weights[24 + g]; w.Wb[g] = weights[28 + g];
+  }
+}
+static void to_grads(float* const* q, SeqGrads& g) {
+  g.dVcat = q[0]; g.dbV = q[1]; g.dScat = q[2]; g.dbS = q[3]; g.dUcat = q[4];
+  g.dbUW = q[5]; g.dWcat = q[6]; g.dEmb = q[7]; g.dFeat = q[8];
+}
+
+static AttDims to_adims(const int* d) {
+  AttDims r;
+  r.B = d[0]; r.T = d[1]; r.steps = d[2]; r.N = d[3]; r.E = d[4]; r.F = d[5]; r.H = d[6];
+  r.V = d[7]; r.A = d[8]; r.P = d[9]; r.C = d[10]; r.cell = d[11];
+  return r;
+}
+static int to_aweights(const float* const* p, AttWeights* w, int cell) {
+  CAPNET_REQUIRE(p != nullptr, "att decoder: null weight table");
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "att decoder: unknown cell %d", cell);
+  for (int i = 0; i < 44; ++i)
+    CAPNET_REQUIRE(p[i] || (i < 32 && !weight_used(cell, i)), "att decoder: weight %d is null", i);
+  to_weights(p, *w);
+  w->init_h_w = p[32]; w->init_h_b = p[33]; w->init_c_w = p[34]; w->init_c_b = p[35];
+  w->enc_att_w = p[36]; w->enc_att_b = p[37]; w->dec_att_w = p[38]; w->dec_att_b = p[39];
+  w->full_att_w = p[40]; w->full_att_b = p[41]; w->f_beta_w = p[42]; w->f_beta_b = p[43];
+  return kOk;
+}
+static void to_agrads(float* const* q, AttGrads& g) {
+  g.dVcat = q[0]; g.dbV = q[1]; g.dScat = q[2]; g.dbS = q[3]; g.dUcat = q[4];
+  g.dWz = q[5]; g.dbz = q[6]; g.dWe = q[7]; g.dbe = q[8]; g.dwf = q[9];
+  g.dbf = q[10]; g.dWih = q[11]; g.dbih = q[12]; g.dWic = q[13]; g.dbic = q[14];
+  g.dEmb = q[15];
+}
+
 extern "C" {
 
 const char* capnet_last_error(void) { return last_error(); }
@@ -381,52 +422,6 @@ size_t capnet_seq_saved_ints(const int* dims) { return seq_saved_ints(to_dims(di
 size_t capnet_seq_fwd_scratch_floats(const int* dims) { return seq_fwd_scratch_floats(to_dims(dims)); }
 size_t capnet_seq_bwd_scratch_floats(const int* dims) { return seq_bwd_scratch_floats(to_dims(dims)); }
 
-int capnet_seq_forward(const int* dims, const int* batch_sizes, const unsigned char* tf_mask,
-                       const long long* captions, const float* features, const float* emb,
-                       const float* const* weights, const float* Cw, const float* Cb,
-                       float dropout_p, unsigned long long seed, int training, float* saved,
-                       int* saved_i, float* scratch, float* hiddens, int* err_flag,
-                       capnet_stream_t stream) {
-  CAPNET_REQUIRE(dims && weights, "seq_forward: null dims/weights");
-  SeqWeights w;
-  for (int g = 0; g < 4; ++g) {
-    w.Vw[g] = weights[0 + g];  w.Vb[g] = weights[4 + g];
-    w.Sw[g] = weights[8 + g];  w.Sb[g] = weights[12 + g];
-    w.Uw[g] = weights[16 + g]; w.Ub[g] = weights[20 + g];
-    w.Ww[g] = weights[24 + g]; w.Wb[g] = weights[28 + g];
-  }
-  const SeqDims d = to_dims(dims);
-  if (d.cell == kCellFactored) {
-    for (int i = 0; i < 32; ++i) CAPNET_REQUIRE(weights[i], "seq_forward: weight %d is null", i);
-  } else {
-    CAPNET_REQUIRE(d.cell == kCellLSTM, "seq_forward: unknown cell %d", d.cell);
-    CAPNET_REQUIRE(w.Vw[0] && w.Vb[0] && w.Ww[0] && w.Wb[0], "seq_forward: LSTM weight is null");
-  }
-  return seq_forward(d, batch_sizes, tf_mask, captions, features, emb, w, Cw, Cb, dropout_p, seed,
-                     training, saved, saved_i, scratch, hiddens, err_flag, S(stream));
-}
-
-int capnet_seq_backward(const int* dims, const int* batch_sizes, const float* d_hiddens,
-                        const float* hiddens, const float* saved, const int* saved_i,
-                        float* scratch, float* const* grads, float dropout_p,
-                        unsigned long long seed, int training, capnet_stream_t stream) {
-  CAPNET_REQUIRE(dims && grads, "seq_backward: null dims/grads");
-  SeqGrads g;
-  g.dVcat = grads[0]; g.dbV = grads[1]; g.dScat = grads[2]; g.dbS = grads[3]; g.dUcat = grads[4];
-  g.dbUW = grads[5]; g.dWcat = grads[6]; g.dEmb = grads[7]; g.dFeat = grads[8];
-  return seq_backward(to_dims(dims), batch_sizes, d_hiddens, hiddens, saved, saved_i, scratch, g,
-                      dropout_p, seed, training, S(stream));
-}
-
-static void to_weights(const float* const* weights, SeqWeights& w) {
-  for (int g = 0; g < 4; ++g) {
-    w.Vw[g] = weights[0 + g];  w.Vb[g] = weights[4 + g];
-    w.Sw[g] = weights[8 + g];  w.Sb[g] = weights[12 + g];
-    w.Uw[g] = weights[16 + g]; w.Ub[g] = weights[20 + g];
-    w.Ww[g] = weights[24 + g]; w.Wb[g] = weights[28 + g];
-  }
-}
-
 int capnet_seq_forward_stacked(const int* dims, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
                                const long long* captions, const float* features, const float* emb,
                                const float* const* weights, const float* Cw, const float* Cb, float dropout_p,
@@ -434,10 +429,12 @@ int capnet_seq_forward_stacked(const int* dims, int nlayers, const int* batch_si
                                float* scratch, float* const* hiddens, int* err_flag, capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && nlayers >= 1 && nlayers <= 8, "seq_forward_stacked: null dims / weights or layers %d", nlayers);
   const SeqDims d = to_dims(dims);
-  CAPNET_REQUIRE(d.cell == kCellFactored, "seq_forward_stacked: the factored cell only");
+  CAPNET_REQUIRE(d.cell == kCellFactored || (d.cell == kCellLSTM && nlayers == 1),
+                 "seq_forward_stacked: cell %d with %d layers (the LSTM cell is one layer)", d.cell, nlayers);
   SeqWeights w[8];
   for (int l = 0; l < nlayers; ++l) {
-    for (int i = 0; i < 32; ++i) CAPNET_REQUIRE(weights[32 * l + i], "seq_forward_stacked: weight %d of layer %d is null", i, l);
+    for (int i = 0; i < 32; ++i)
+      CAPNET_REQUIRE(!weight_used(d.cell, i) || weights[32 * l + i], "seq_forward_stacked: weight %d of layer %d is null", i, l);
     to_weights(weights + 32 * l, w[l]);
   }
   return seq_forward_stacked(d, nlayers, batch_sizes, tf_mask, captions, features, emb, w, Cw, Cb, dropout_p, seed, training,
@@ -450,40 +447,30 @@ int capnet_seq_backward_stacked(const int* dims, int nlayers, const int* batch_s
                                 unsigned long long seed, int training, capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && grads && nlayers >= 1 && nlayers <= 8, "seq_backward_stacked: null dims / grads or layers %d", nlayers);
   SeqGrads g[8];
-  for (int l = 0; l < nlayers; ++l) {
-    float* const* q = grads + 9 * l;
-    g[l].dVcat = q[0]; g[l].dbV = q[1]; g[l].dScat = q[2]; g[l].dbS = q[3]; g[l].dUcat = q[4];
-    g[l].dbUW = q[5]; g[l].dWcat = q[6]; g[l].dEmb = q[7]; g[l].dFeat = q[8];
-  }
+  for (int l = 0; l < nlayers; ++l) to_grads(grads + 9 * l, g[l]);
   return seq_backward_stacked(to_dims(dims), nlayers, batch_sizes, d_hiddens, hiddens, saved, saved_i, scratch, dh_work, g,
                               dropout_p, seed, training, S(stream));
 }
 
-static AttDims to_adims(const int* d) {
-  AttDims r;
-  r.B = d[0]; r.T = d[1]; r.steps = d[2]; r.N = d[3]; r.E = d[4]; r.F = d[5]; r.H = d[6];
-  r.V = d[7]; r.A = d[8]; r.P = d[9]; r.C = d[10]; r.cell = d[11];
-  return r;
+// the single-layer entries: the stacked ones at one layer
+int capnet_seq_forward(const int* dims, const int* batch_sizes, const unsigned char* tf_mask,
+                       const long long* captions, const float* features, const float* emb,
+                       const float* const* weights, const float* Cw, const float* Cb,
+                       float dropout_p, unsigned long long seed, int training, float* saved,
+                       int* saved_i, float* scratch, float* hiddens, int* err_flag,
+                       capnet_stream_t stream) {
+  return capnet_seq_forward_stacked(dims, 1, batch_sizes, tf_mask, captions, features, emb, weights, Cw, Cb, dropout_p, seed,
+                                    training, &saved, &saved_i, scratch, &hiddens, err_flag, stream);
 }
-static int to_aweights(const float* const* p, AttWeights* w, int cell) {
-  CAPNET_REQUIRE(p != nullptr, "att decoder: null weight table");
-  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "att decoder: unknown cell %d", cell);
-  for (int i = 0; i < 44; ++i) {
-    // nn.LSTMCell: only slot 0 of the V (weight_ih, bias_ih) and W (weight_hh, bias_hh) groups
-    const bool used = cell == kCellFactored || i >= 32 || i == 0 || i == 4 || i == 24 || i == 28;
-    CAPNET_REQUIRE(!used || p[i] != nullptr, "att decoder: weight %d is null", i);
-  }
-  for (int g = 0; g < 4; ++g) {
-    w->Vw[g] = p[0 + g];  w->Vb[g] = p[4 + g];
-    w->Sw[g] = p[8 + g];  w->Sb[g] = p[12 + g];
-    w->Uw[g] = p[16 + g]; w->Ub[g] = p[20 + g];
-    w->Ww[g] = p[24 + g]; w->Wb[g] = p[28 + g];
-  }
-  w->init_h_w = p[32]; w->init_h_b = p[33]; w->init_c_w = p[34]; w->init_c_b = p[35];
-  w->enc_att_w = p[36]; w->enc_att_b = p[37]; w->dec_att_w = p[38]; w->dec_att_b = p[39];
-  w->full_att_w = p[40]; w->full_att_b = p[41]; w->f_beta_w = p[42]; w->f_beta_b = p[43];
-  return kOk;
+
+int capnet_seq_backward(const int* dims, const int* batch_sizes, const float* d_hiddens,
+                        const float* hiddens, const float* saved, const int* saved_i,
+                        float* scratch, float* const* grads, float dropout_p,
+                        unsigned long long seed, int training, capnet_stream_t stream) {
+  return capnet_seq_backward_stacked(dims, 1, batch_sizes, d_hiddens, &hiddens, &saved, &saved_i, scratch, nullptr, grads,
+                                     dropout_p, seed, training, stream);
 }
+
 int capnet_att_set_chain_mode(int mode) { return att_set_chain_mode(mode); }
 size_t capnet_att_saved_floats(const int* dims) { return att_saved_floats(to_adims(dims)); }
 size_t capnet_att_saved_ints(const int* dims) { return att_saved_ints(to_adims(dims)); }
@@ -506,39 +493,6 @@ int capnet_att_step_fwd(const float* att1, const float* feat, const float* att2,
   return att_step_fwd(att1, feat, att2, gate_io, ldz, w_full, b_full, rows, P, A, C, alpha_out,
                       alphas_bt, steps, t, awe_out, xa_out, ldx, scores_ws, S(stream));
 }
-int capnet_att_seq_forward(const int* dims, const int* batch_sizes, const unsigned char* tf_mask,
-                           const long long* captions, const float* features, const float* emb,
-                           const float* const* weights, const float* Cw, const float* Cb,
-                           float dropout_p, unsigned long long seed, int training, float* saved,
-                           int* saved_i, float* scratch, float* hiddens, float* alphas,
-                           int* err_flag, capnet_stream_t stream) {
-  CAPNET_REQUIRE(dims != nullptr, "att_seq_forward: null dims");
-  AttWeights w;
-  int rc = to_aweights(weights, &w, dims ? dims[11] : 0);
-  if (rc) return rc;
-  return att_seq_forward(to_adims(dims), batch_sizes, tf_mask, captions, features, emb, w, Cw, Cb,
-                         dropout_p, seed, training, saved, saved_i, scratch, hiddens, alphas,
-                         err_flag, S(stream));
-}
-
-int capnet_att_seq_backward(const int* dims, const int* batch_sizes, const float* d_hiddens,
-                            const float* d_alphas, const float* hiddens, const float* features,
-                            const float* const* weights, const float* saved, const int* saved_i,
-                            float* scratch, float* const* grads, float dropout_p,
-                            unsigned long long seed, int training, capnet_stream_t stream) {
-  CAPNET_REQUIRE(dims && grads, "att_seq_backward: null dims/grads");
-  AttWeights w;
-  int rc = to_aweights(weights, &w, dims ? dims[11] : 0);
-  if (rc) return rc;
-  AttGrads g;
-  g.dVcat = grads[0]; g.dbV = grads[1]; g.dScat = grads[2]; g.dbS = grads[3]; g.dUcat = grads[4];
-  g.dWz = grads[5]; g.dbz = grads[6]; g.dWe = grads[7]; g.dbe = grads[8]; g.dwf = grads[9];
-  g.dbf = grads[10]; g.dWih = grads[11]; g.dbih = grads[12]; g.dWic = grads[13]; g.dbic = grads[14];
-  g.dEmb = grads[15];
-  return att_seq_backward(to_adims(dims), batch_sizes, d_hiddens, d_alphas, hiddens, features, w,
-                          saved, saved_i, scratch, g, dropout_p, seed, training, S(stream));
-}
-
 size_t capnet_att_stacked_saved_floats(const int* dims, int layer) { return att_stacked_saved_floats(to_adims(dims), layer); }
 size_t capnet_att_stacked_saved_ints(const int* dims, int layer) { return att_stacked_saved_ints(to_adims(dims), layer); }
 size_t capnet_att_stacked_fwd_scratch_floats(const int* dims, int nlayers) {
@@ -556,7 +510,7 @@ int capnet_att_seq_forward_stacked(const int* dims, int nlayers, const int* batc
                                    capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && nlayers >= 1 && nlayers <= 8, "att_seq_forward_stacked: null dims / weights or layers %d",
                  nlayers);
-  CAPNET_REQUIRE(dims[11] == kCellFactored, "att_seq_forward_stacked: the factored cell only");
+  CAPNET_REQUIRE(dims[11] == kCellFactored || nlayers == 1, "att_seq_forward_stacked: the LSTM cell is one layer");
   AttWeights w0;
   int rc = to_aweights(weights, &w0, dims[11]);
   if (rc) return rc;
@@ -579,26 +533,43 @@ int capnet_att_seq_backward_stacked(const int* dims, int nlayers, const int* bat
                                     unsigned long long seed, int training, capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && grads && nlayers >= 1 && nlayers <= 8,
                  "att_seq_backward_stacked: null dims / weights / grads or layers %d", nlayers);
-  CAPNET_REQUIRE(dims[11] == kCellFactored, "att_seq_backward_stacked: the factored cell only");
+  CAPNET_REQUIRE(dims[11] == kCellFactored || nlayers == 1, "att_seq_backward_stacked: the LSTM cell is one layer");
   AttWeights w0;
   int rc = to_aweights(weights, &w0, dims[11]);
   if (rc) return rc;
   AttGrads g;
-  g.dVcat = grads[0]; g.dbV = grads[1]; g.dScat = grads[2]; g.dbS = grads[3]; g.dUcat = grads[4];
-  g.dWz = grads[5]; g.dbz = grads[6]; g.dWe = grads[7]; g.dbe = grads[8]; g.dwf = grads[9];
-  g.dbf = grads[10]; g.dWih = grads[11]; g.dbih = grads[12]; g.dWic = grads[13]; g.dbic = grads[14];
-  g.dEmb = grads[15];
+  to_agrads(grads, g);
   SeqGrads gu[8];
   UpperInitGrads giu[8];
   for (int l = 1; l < nlayers; ++l) {
     float* const* q = grads + 16 + 11 * (l - 1);
     for (int i = 0; i < 11; ++i) CAPNET_REQUIRE(q[i], "att_seq_backward_stacked: gradient %d of layer %d is null", i, l);
-    gu[l - 1].dVcat = q[0]; gu[l - 1].dbV = q[1]; gu[l - 1].dScat = q[2]; gu[l - 1].dbS = q[3]; gu[l - 1].dUcat = q[4];
-    gu[l - 1].dbUW = q[5]; gu[l - 1].dWcat = q[6]; gu[l - 1].dEmb = nullptr; gu[l - 1].dFeat = nullptr;
+    to_grads(q, gu[l - 1]);
+    gu[l - 1].dEmb = gu[l - 1].dFeat = nullptr;       // (q[7..10]: init_h{l} / init_c{l}; no embedding, no features)
     giu[l - 1] = UpperInitGrads{q[7], q[8], q[9], q[10]};
   }
   return att_seq_backward_stacked(to_adims(dims), nlayers, batch_sizes, d_hiddens, d_alphas, hiddens, features, w0, saved,
                                   saved_i, scratch, dh_work, g, gu, giu, dropout_p, seed, training, S(stream));
+}
+
+// the single-layer entries: the stacked ones at one layer
+int capnet_att_seq_forward(const int* dims, const int* batch_sizes, const unsigned char* tf_mask,
+                           const long long* captions, const float* features, const float* emb,
+                           const float* const* weights, const float* Cw, const float* Cb,
+                           float dropout_p, unsigned long long seed, int training, float* saved,
+                           int* saved_i, float* scratch, float* hiddens, float* alphas,
+                           int* err_flag, capnet_stream_t stream) {
+  return capnet_att_seq_forward_stacked(dims, 1, batch_sizes, tf_mask, captions, features, emb, weights, Cw, Cb, dropout_p,
+                                        seed, training, &saved, &saved_i, scratch, &hiddens, alphas, err_flag, stream);
+}
+
+int capnet_att_seq_backward(const int* dims, const int* batch_sizes, const float* d_hiddens,
+                            const float* d_alphas, const float* hiddens, const float* features,
+                            const float* const* weights, const float* saved, const int* saved_i,
+                            float* scratch, float* const* grads, float dropout_p,
+                            unsigned long long seed, int training, capnet_stream_t stream) {
+  return capnet_att_seq_backward_stacked(dims, 1, batch_sizes, d_hiddens, d_alphas, &hiddens, features, weights, &saved,
+                                         &saved_i, scratch, nullptr, grads, dropout_p, seed, training, stream);
 }
 
 int capnet_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets,

@@ -318,20 +318,6 @@ int att_fwd_step(AttFwd& f, int t, const float* h_feed) {
 }
 }  // namespace
 
-int att_seq_forward(const AttDims& d, const int* bs, const unsigned char* tf,
-                    const long long* captions, const float* feat, const float* emb,
-                    const AttWeights& w, const float* Cw, const float* Cb, float dropout_p,
-                    unsigned long long seed, int training, float* saved, int* saved_i,
-                    float* scratch, float* hiddens, float* alphas_bt, int* err_flag,
-                    hipStream_t s) {
-  AttFwd f;
-  RC(att_fwd_begin(f, d, bs, tf, captions, feat, emb, w, Cw, Cb, dropout_p, seed, training, saved, saved_i, scratch, hiddens,
-                   alphas_bt, err_flag, s));
-  for (int t = 0; t < d.steps; ++t)
-    RC(att_fwd_step(f, t, t > 0 ? hiddens + (size_t)f.off[t - 1] * d.H : nullptr));
-  return kOk;
-}
-
 int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const float* dalphas_bt,
                      const float* hiddens, const float* feat, const AttWeights& w,
                      const float* saved, const int* saved_i, float* scratch, const AttGrads& g,

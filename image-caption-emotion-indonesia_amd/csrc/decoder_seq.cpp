@@ -222,9 +222,10 @@ SeqDims upper_dims(const SeqDims& d0) {
 
 SeqDims seq_upper_dims(const SeqDims& d0) { return upper_dims(d0); }
 
-// nlayers stacked cells (capnet.stacked: SURVEY App. A-1's semantics, PERF-ONLY / PARITY UNPINNED -- the reference ignores
-// num_layers, stylenet/model.py:37): layer 0 is seq_forward's cell on [feature, dropout(B(w))...]; layer l > 0 is the same
-// cell on dropout(hidden of layer l - 1) at the same step; the top layer's hidden feeds C on free-running steps.
+// The decoder recurrence of 1 to nlayers cells. One layer is DecoderFactoredLSTM / DecoderRNN (either cell). More are the
+// stacked factored cells (capnet.stacked: SURVEY App. A-1's semantics, PERF-ONLY / PARITY UNPINNED -- the reference ignores
+// num_layers, stylenet/model.py:37): layer 0 is the single-layer cell on [feature, dropout(B(w))...]; layer l > 0 is the
+// same cell on dropout(hidden of layer l - 1) at the same step; the top layer's hidden feeds C on free-running steps.
 // Runs of teacher-forced steps outside, layers inside: a run's rows go up the stack before the next run starts (a
 // free-running step's input needs the TOP layer's previous hidden state).
 int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
@@ -301,19 +302,6 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
     t = t1;
   }
   return kOk;
-}
-
-int seq_forward(const SeqDims& d, const int* batch_sizes, const unsigned char* tf_mask,
-                const long long* captions, const float* features, const float* emb,
-                const SeqWeights& w, const float* Cw, const float* Cb, float dropout_p,
-                unsigned long long seed, int training, float* saved, int* saved_i, float* scratch,
-                float* hiddens, int* err_flag, hipStream_t s) {
-  CAPNET_REQUIRE(saved && saved_i && hiddens, "seq_forward: null argument");
-  float* sv[1] = {saved};
-  int* svi[1] = {saved_i};
-  float* hid[1] = {hiddens};
-  return seq_forward_stacked(d, 1, batch_sizes, tf_mask, captions, features, emb, &w, Cw, Cb, dropout_p, seed, training, sv,
-                             svi, scratch, hid, err_flag, s);
 }
 
 // layer > 0 (a stacked layer above the first): the input gradient goes to dH_below = d hidden of the layer below (through
@@ -439,12 +427,6 @@ int seqd::seq_backward_upper(const SeqDims& d, const int* batch_sizes, const flo
 
 size_t seqd::seq_bwd_upper_scratch_floats(const SeqDims& d) {
   return seq_bwd_scratch_floats(d) + 2 * ((size_t)d.N * 4 * d.F + 4);
-}
-
-int seq_backward(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,
-                 const float* saved, const int* saved_i, float* scratch, const SeqGrads& g,
-                 float dropout_p, unsigned long long seed, int training, hipStream_t s) {
-  return seq_backward_layer(d, batch_sizes, dH, hiddens, saved, saved_i, scratch, g, dropout_p, seed, training, 0, nullptr, s);
 }
 
 // BPTT of seq_forward_stacked, top layer first: a layer's whole backward through time, then its input gradient becomes the

@@ -353,11 +353,6 @@ size_t seq_saved_floats(const SeqDims& d);
 size_t seq_saved_ints(const SeqDims& d);
 size_t seq_fwd_scratch_floats(const SeqDims& d);
 size_t seq_bwd_scratch_floats(const SeqDims& d);
-int seq_forward(const SeqDims& d, const int* batch_sizes, const unsigned char* tf_mask,
-                const long long* captions, const float* features, const float* emb,
-                const SeqWeights& w, const float* Cw, const float* Cb, float dropout_p,
-                unsigned long long seed, int training, float* saved, int* saved_i, float* scratch,
-                float* hiddens, int* err_flag, hipStream_t s);
 SeqDims seq_upper_dims(const SeqDims& d0);
 int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
                         const long long* captions, const float* features, const float* emb, const SeqWeights* w,
@@ -368,9 +363,6 @@ int seq_backward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes,
                          const float* const* hiddens, const float* const* saved, const int* const* saved_i, float* scratch,
                          float* const* dH_work, const SeqGrads* g, float dropout_p, unsigned long long seed, int training,
                          hipStream_t s);
-int seq_backward(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,
-                 const float* saved, const int* saved_i, float* scratch, const SeqGrads& g,
-                 float dropout_p, unsigned long long seed, int training, hipStream_t s);
 
 // decoder_att_seq.cpp -- DecoderFactoredLSTMAtt (stylenet/model_att.py:73-305)
 struct AttDims {
@@ -400,18 +392,13 @@ size_t att_saved_floats(const AttDims& d);
 size_t att_saved_ints(const AttDims& d);
 size_t att_fwd_scratch_floats(const AttDims& d);
 size_t att_bwd_scratch_floats(const AttDims& d);
-int att_seq_forward(const AttDims& d, const int* bs, const unsigned char* tf,
-                    const long long* captions, const float* feat, const float* emb,
-                    const AttWeights& w, const float* Cw, const float* Cb, float dropout_p,
-                    unsigned long long seed, int training, float* saved, int* saved_i,
-                    float* scratch, float* hiddens, float* alphas_bt, int* err_flag,
-                    hipStream_t s);
 int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const float* dalphas_bt,
                      const float* hiddens, const float* feat, const AttWeights& w,
                      const float* saved, const int* saved_i, float* scratch, const AttGrads& g,
                      float dropout_p, unsigned long long seed, int training, hipStream_t s);
 
-// stacked attention decoder (capnet.stacked_att): layer 0 is att_seq_forward's cell, layers l > 0 the factored cell on
+// the attention decoder of 1 to 8 layers (one: DecoderFactoredLSTMAtt / DecoderRNNAtt, either cell; more: capnet.stacked_att,
+// factored cells only): layer 0 is the attention cell (att_fwd_begin / att_fwd_step), layers l > 0 the factored cell on
 // dropout(h^{l-1}_t) with initial state init_h{l} / init_c{l} of the mean feature. hiddens[0]: [N][H]; hiddens[l > 0]:
 // [B + N][H], rows 0..B-1 the initial state. Upper weights: SeqWeights + init_h{l} w, b, init_c{l} w, b.
 struct UpperInit { const float* init_h_w; const float* init_h_b; const float* init_c_w; const float* init_c_b; };

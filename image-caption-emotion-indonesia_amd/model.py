@@ -603,7 +603,6 @@ class DecoderFactoredLSTM(nn.Module):
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
         weights = self._weights(mode)
         cfg = {
-            "cell": ops.CELL_FACTORED,
             "batch_sizes": batch_sizes,
             "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
             "hidden_size": self.hidden_size,
@@ -612,8 +611,7 @@ class DecoderFactoredLSTM(nn.Module):
             "seed": _dropout_seed(self.training, self.dropout.p),
             "training": self.training,
         }
-        hiddens = ops.decoder_sequence(cfg, captions, features, self.B.weight, self.C.weight,
-                                       self.C.bias, weights)
+        hiddens = ops.SeqFn.apply(cfg, captions, features, self.B.weight, self.C.weight, self.C.bias, *weights)
         outputs = self.C(hiddens)
         return outputs
 

@@ -166,6 +166,11 @@ class DecoderFactoredLSTMAtt(nn.Module):
             out += [m.weight, m.bias]
         return out
 
+    def _upper_layers(self, mode):
+        """(num_layers, the weights of the layers above layer 0) for the sequence call. One layer here: num_layers is
+        ignored, as in the reference (capnet.stacked_att stacks)."""
+        return 1, []
+
     def init_hidden_state(self, features):
         """h0, c0 = init_h / init_c (mean over pixels) -- stylenet/model_att.py:185-194."""
         mean_features = features.mean(dim=1)
@@ -261,7 +266,10 @@ class DecoderFactoredLSTMAtt(nn.Module):
         batch_size = captions.size(0)
         features = features.reshape(batch_size, -1, features.size(-1))
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
+        weights = self._weights(mode)
+        num_layers, upper = self._upper_layers(mode)
         cfg = {
+            "num_layers": num_layers,
             "batch_sizes": batch_sizes,
             "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
             "hidden_size": self.hidden_size,
@@ -271,6 +279,6 @@ class DecoderFactoredLSTMAtt(nn.Module):
             "seed": _dropout_seed(self.training, self.dropout.p),
             "training": self.training,
         }
-        hiddens, alphas = ops.decoder_att_sequence(cfg, captions, features.detach(), self.B.weight,
-                                                   self.C.weight, self.C.bias, self._weights(mode))
+        hiddens, alphas = ops.AttSeqFn.apply(cfg, captions, features.detach(), self.B.weight, self.C.weight, self.C.bias,
+                                             *weights, *upper)
         return self.C(hiddens), alphas

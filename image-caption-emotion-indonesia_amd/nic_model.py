@@ -83,8 +83,8 @@ class DecoderRNN(nn.Module):
             "training": self.training,
         }
         weights = [self.lstm.weight_ih, self.lstm.bias_ih, self.lstm.weight_hh, self.lstm.bias_hh]
-        hiddens = ops.decoder_sequence(cfg, captions, features, self.embed.weight,
-                                       self.linear.weight, self.linear.bias, weights)
+        hiddens = ops.SeqFn.apply(cfg, captions, features, self.embed.weight, self.linear.weight, self.linear.bias,
+                                  *weights)
         return self.linear(hiddens)
 
     def sample(self, features, start_token, end_token, k=5):

@@ -88,9 +88,8 @@ class DecoderRNNAtt(nn.Module):
             "seed": _dropout_seed(self.training, self.dropout.p),
             "training": self.training,
         }
-        hiddens, alphas = ops.decoder_att_sequence(cfg, captions, features.detach(), self.embed.weight,
-                                                   self.linear.weight, self.linear.bias,
-                                                   self._weights())
+        hiddens, alphas = ops.AttSeqFn.apply(cfg, captions, features.detach(), self.embed.weight, self.linear.weight,
+                                             self.linear.bias, *self._weights())
         return self.linear(hiddens), alphas
 
     def sample(self, features, start_token, end_token, k=5):

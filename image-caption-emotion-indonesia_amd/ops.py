@@ -633,145 +633,150 @@ def batch_sizes_from_lengths(lengths):
     return [sum(1 for l in lengths if l > t) for t in range(lengths[0])]
 
 
-class DecoderSeqFn(torch.autograd.Function):
-    """hiddens[N,H] of the scheduled-sampling recurrence; one C call forward, one backward.
+def _gate_grads(cell, F, H, dV, dbV, dS, dbS, dU, dbUW, dW):
+    """The gate-stacked gradients of one layer cut into the per-gate views of its weight table: V w x4, V b x4, S w x4,
+    S b x4, U w x4, U b x4, W w x4, W b x4 (b_U and b_W enter the same pre-activation: W b gets a copy of dbUW). The
+    LSTM cell: (weight_ih, bias_ih, weight_hh, bias_hh). dW / dbUW may run on past 4H rows (the attention cell's z
+    block): only the first 4H are the gates'."""
+    if cell != CELL_FACTORED:
+        return [dV, dbUW[:4 * H], dW[:4 * H], dbUW[:4 * H].clone()]
 
-    weights: cell 0 -> 32 tensors (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4, W w x4, W b x4)
-             cell 1 -> (weight_ih, bias_ih, weight_hh, bias_hh)
-    """
+    def gates(x, n):
+        return [x[g * n:(g + 1) * n] for g in range(4)]
+    return (gates(dV, F) + gates(dbV, F) + [dS[g] for g in range(4)] + gates(dbS, F) + [dU[g] for g in range(4)] +
+            gates(dbUW, H) + gates(dW, H) + [b.clone() for b in gates(dbUW, H)])
+
+
+def _seq_args(cfg, captions):
+    """-> (cell, num_layers) of cfg (defaults: the factored cell, one layer), with the checks both sequence Functions
+    make: the layer count (the LSTM cell takes one), int64 captions, batch_sizes / tf_mask against the batch."""
+    cell, nl = cfg.get("cell", CELL_FACTORED), cfg.get("num_layers", 1)
+    if not 1 <= nl <= 8 or (cell != CELL_FACTORED and nl != 1):
+        raise CapnetError("%d layers: the factored cell stacks 1 to 8, the LSTM cell is one layer" % nl)
+    if captions.dtype != torch.int64:
+        raise CapnetError("captions must be int64")
+    bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
+    if len(tf) != len(bs) or bs[0] != captions.shape[0]:
+        raise CapnetError("decoder: batch_sizes / tf_mask do not match the batch")
+    return cell, nl
+
+
+def _lstm_slots(ws):
+    """The LSTM cell's (weight_ih, bias_ih, weight_hh, bias_hh) in slots 0 / 4 / 24 / 28 of the factored cell's 32."""
+    slots = [None] * 32
+    slots[0], slots[4], slots[24], slots[28] = ws
+    return slots
+
+
+def _tf_bytes(tf):
+    return (C.c_ubyte * len(tf))(*[1 if x else 0 for x in tf])
+
+
+class SeqFn(torch.autograd.Function):
+    """The top layer's hiddens [N, H] (pack_padded_sequence order) of the scheduled-sampling recurrence of 1 to 8 stacked
+    layers: ONE C call each way (capnet_seq_forward_stacked / capnet_seq_backward_stacked, csrc/decoder_seq.cpp).
+    cfg: batch_sizes, tf_mask, hidden_size, factored_size (factored cell), dropout, seed, training; cell (default
+    CELL_FACTORED), num_layers (default 1; the LSTM cell takes one).
+    weights: the factored cell -> 32 tensors per layer, layer 0 first (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4,
+             W w x4, W b x4); the LSTM cell -> (weight_ih, bias_ih, weight_hh, bias_hh)."""
 
     @staticmethod
     def forward(ctx, cfg, captions, features, emb, Cw, Cb, *weights):
-        cell = cfg["cell"]
         _need_cuda(captions, features, emb, Cw, Cb, *weights)
         captions = _c(captions)
-        if captions.dtype != torch.int64:
-            raise CapnetError("captions must be int64")
+        cell, nl = _seq_args(cfg, captions)
+        ws = [_c(w) for w in weights]
+        if len(ws) != (32 * nl if cell == CELL_FACTORED else 4):
+            raise CapnetError("the factored cell takes 32 weight tensors per layer, the LSTM cell 4")
+        if cell != CELL_FACTORED:
+            ws = _lstm_slots(ws)
+        emb, Cw, Cb = _c(emb), _c(Cw), _c(Cb)
         dev = emb.device
-        bs = cfg["batch_sizes"]
-        tf = cfg["tf_mask"]
+        bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
         B, T = captions.shape
         V, E = emb.shape
-        H = cfg["hidden_size"]
-        F = cfg.get("factored_size", 0)
-        N = sum(bs)
-        if len(tf) != len(bs):
-            raise CapnetError("tf_mask has %d entries for %d steps" % (len(tf), len(bs)))
-        if bs[0] != B:
-            raise CapnetError("batch_sizes[0]=%d but captions has %d rows" % (bs[0], B))
-        dims = [B, T, len(bs), N, E, F, H, V, int(features is not None), cell]
-        ws = [_c(w) for w in weights]
-        if cell == CELL_FACTORED:
-            if len(ws) != 32:
-                raise CapnetError("factored cell takes 32 weight tensors")
-            wptrs = ws
-        else:
-            if len(ws) != 4:
-                raise CapnetError("LSTM cell takes 4 weight tensors")
-            wptrs = [None] * 32
-            wptrs[0], wptrs[4], wptrs[24], wptrs[28] = ws
+        H, F, N = cfg["hidden_size"], cfg.get("factored_size", 0), sum(bs)
         if features is not None:
             features = _c(features)
             if tuple(features.shape) != (B, E):
                 raise CapnetError("features must be [batch, embed_size]")
-        emb_c, Cw_c, Cb_c = _c(emb), _c(Cw), _c(Cb)
-        cdims = int_array(dims)
+        dims = [[B, T, len(bs), N, E if l == 0 else H, F, H, V, int(features is not None) if l == 0 else 0, cell]
+                for l in range(nl)]
         L = _lib.lib()
-        saved = torch.empty(L.capnet_seq_saved_floats(cdims), dtype=torch.float32, device=dev)
-        saved_i = torch.empty(L.capnet_seq_saved_ints(cdims), dtype=torch.int32, device=dev)
-        scratch = torch.empty(L.capnet_seq_fwd_scratch_floats(cdims), dtype=torch.float32, device=dev)
-        hiddens = torch.empty((N, H), dtype=torch.float32, device=dev)
-        tfm = (C.c_ubyte * len(tf))(*[1 if x else 0 for x in tf])
-        check(L.capnet_seq_forward(cdims, int_array(bs), tfm, ptr(captions), ptr(features),
-                                   ptr(emb_c), ptr_array(wptrs), ptr(Cw_c), ptr(Cb_c),
-                                   float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]),
-                                   ptr(saved), ptr(saved_i), ptr(scratch), ptr(hiddens),
-                                   ptr(err_flag(dev)), current_stream()), "capnet_seq_forward")
-        ctx.cfg = cfg
-        ctx.dims = dims
-        ctx.n_weights = len(ws)
-        ctx.has_features = features is not None
-        ctx.save_for_backward(saved, saved_i, hiddens)
-        return hiddens
+        cd = [int_array(d) for d in dims]
+        saved = [torch.empty(L.capnet_seq_saved_floats(c), dtype=torch.float32, device=dev) for c in cd]
+        saved_i = [torch.empty(L.capnet_seq_saved_ints(c), dtype=torch.int32, device=dev) for c in cd]
+        scratch = torch.empty(L.capnet_seq_fwd_scratch_floats(cd[0]), dtype=torch.float32, device=dev)
+        hid = [torch.empty((N, H), dtype=torch.float32, device=dev) for _ in range(nl)]
+        check(L.capnet_seq_forward_stacked(cd[0], nl, int_array(bs), _tf_bytes(tf), ptr(captions), ptr(features),
+                                           ptr(emb), ptr_array(ws), ptr(Cw), ptr(Cb), float(cfg["dropout"]),
+                                           int(cfg["seed"]), int(cfg["training"]), ptr_array(saved), ptr_array(saved_i),
+                                           ptr(scratch), ptr_array(hid), ptr(err_flag(dev)), current_stream()),
+              "capnet_seq_forward_stacked")
+        ctx.cfg, ctx.dims, ctx.has_features = cfg, dims, features is not None
+        ctx.save_for_backward(*(saved + saved_i + hid))
+        return hid[-1]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_hiddens):
-        saved, saved_i, hiddens = ctx.saved_tensors
         cfg, dims = ctx.cfg, ctx.dims
-        B, T, steps, N, E, F, H, V, _, cell = dims
-        dev = saved.device
-        d_hiddens = _c(d_hiddens)
+        nl = len(dims)
+        t = ctx.saved_tensors
+        saved, saved_i, hid = t[:nl], t[nl:2 * nl], t[2 * nl:]
+        B, T, steps, N, E, F, H, V, _, cell = dims[0]
+        dev = saved[0].device
         L = _lib.lib()
-        cdims = int_array(dims)
-        scratch = torch.empty(L.capnet_seq_bwd_scratch_floats(cdims), dtype=torch.float32, device=dev)
+        cd = [int_array(d) for d in dims]
+        scratch = torch.empty(max(L.capnet_seq_bwd_scratch_floats(c) for c in cd), dtype=torch.float32, device=dev)
 
         def new(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
 
         dEmb = new(V, E)
         dFeat = new(B, E) if ctx.has_features else None
-        dW = new(4 * H, H)
-        dbUW = new(4 * H)
-        if cell == CELL_FACTORED:
-            dV, dbV, dS, dbS, dU = new(4 * F, E), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F)
-        else:
-            dV, dbV, dS, dbS, dU = new(4 * H, E), None, None, None, None
-        grads = [dV, dbV, dS, dbS, dU, dbUW, dW, dEmb, dFeat]
-        check(L.capnet_seq_backward(cdims, int_array(cfg["batch_sizes"]), ptr(d_hiddens),
-                                    ptr(hiddens), ptr(saved), ptr(saved_i), ptr(scratch),
-                                    ptr_array(grads), float(cfg["dropout"]), int(cfg["seed"]),
-                                    int(cfg["training"]), current_stream()), "capnet_seq_backward")
-        if cell == CELL_FACTORED:
-            wg = ([dV[g * F:(g + 1) * F] for g in range(4)] +
-                  [dbV[g * F:(g + 1) * F] for g in range(4)] +
-                  [dS[g] for g in range(4)] +
-                  [dbS[g * F:(g + 1) * F] for g in range(4)] +
-                  [dU[g] for g in range(4)] +
-                  [dbUW[g * H:(g + 1) * H] for g in range(4)] +
-                  [dW[g * H:(g + 1) * H] for g in range(4)] +
-                  [dbUW[g * H:(g + 1) * H].clone() for g in range(4)])
-        else:
-            wg = [dV, dbUW, dW, dbUW.clone()]
+        grads, per_layer = [], []
+        for l in range(nl):
+            El = E if l == 0 else H
+            if cell == CELL_FACTORED:
+                g = [new(4 * F, El), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H)]
+            else:
+                g = [new(4 * H, El), None, None, None, None, new(4 * H), new(4 * H, H)]
+            grads += g + [dEmb if l == 0 else None, dFeat if l == 0 else None]
+            per_layer.append(g)
+        dh_work = [new(N, H) for _ in range(nl - 1)]
+        check(L.capnet_seq_backward_stacked(cd[0], nl, int_array(cfg["batch_sizes"]), ptr(_c(d_hiddens)), ptr_array(hid),
+                                            ptr_array(saved), ptr_array(saved_i), ptr(scratch),
+                                            ptr_array(dh_work) if dh_work else None, ptr_array(grads),
+                                            float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]), current_stream()),
+              "capnet_seq_backward_stacked")
+        wg = []
+        for g in per_layer:
+            wg += _gate_grads(cell, F, H, *g)
         # cfg, captions, features, emb, Cw, Cb, *weights
         return (None, None, dFeat, dEmb, None, None) + tuple(wg)
 
 
-def decoder_sequence(cfg, captions, features, emb, Cw, Cb, weights):
-    return DecoderSeqFn.apply(cfg, captions, features, emb, Cw, Cb, *weights)
-
-
-# ---------------------------------------------------------------------------------------
-# autograd: whole-sequence attention decoder (DecoderFactoredLSTMAtt)
-# ---------------------------------------------------------------------------------------
-def _att_slots(ws, cell):
-    """The 44-slot weight table of capnet_att_seq_forward/backward."""
-    if cell == CELL_FACTORED:
-        return ws
-    slots = [None] * 32
-    slots[0], slots[4], slots[24], slots[28] = ws[0], ws[1], ws[2], ws[3]
-    return slots + list(ws[4:])
-
-
-class DecoderAttSeqFn(torch.autograd.Function):
-    """(hiddens [N,H], alphas [B,steps,P]) of the attention recurrence.
-
-    weights, cfg["cell"] == CELL_FACTORED (default): 44 tensors in the order of
-    capnet_att_seq_forward (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4, W w x4, W b x4,
-    init_h w,b, init_c w,b, encoder_att w,b, decoder_att w,b, full_att w,b, f_beta w,b).
-    cfg["cell"] == CELL_LSTM (nic DecoderRNNAtt): 16 tensors weight_ih, bias_ih, weight_hh,
-    bias_hh followed by the same 12 attention / init tensors.
+class AttSeqFn(torch.autograd.Function):
+    """(top-layer hiddens [N, H], layer 0's alphas [B, steps, P]) of the attention recurrence of 1 to 8 stacked layers:
+    ONE C call each way (capnet_att_seq_forward_stacked / capnet_att_seq_backward_stacked, csrc/decoder_att_seq.cpp).
+    cfg: SeqFn's keys and attention_size.
+    weights: layer 0's 44 tensors (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4, W w x4, W b x4, init_h w,b, init_c w,b,
+    encoder_att w,b, decoder_att w,b, full_att w,b, f_beta w,b) -- the LSTM cell's 16: weight_ih, bias_ih, weight_hh,
+    bias_hh, then the same 12 --, then 36 per upper layer: its 32 in the same order, init_h{l} w, b, init_c{l} w, b.
     `features` gets no gradient (frozen trunk)."""
 
     @staticmethod
     def forward(ctx, cfg, captions, features, emb, Cw, Cb, *weights):
         _need_cuda(captions, features, emb, Cw, Cb, *weights)
-        cell = cfg.get("cell", CELL_FACTORED)
-        if len(weights) != (44 if cell == CELL_FACTORED else 16):
-            raise CapnetError("attention decoder takes 44 (factored) / 16 (LSTMCell) weight tensors")
         captions = _c(captions)
-        if captions.dtype != torch.int64:
-            raise CapnetError("captions must be int64")
+        cell, nl = _seq_args(cfg, captions)
+        ws = [_c(w) for w in weights]
+        if len(ws) != (44 + 36 * (nl - 1) if cell == CELL_FACTORED else 16):
+            raise CapnetError("attention decoder: 44 + 36 (num_layers - 1) weight tensors (factored) / 16 (LSTMCell)")
+        if cell != CELL_FACTORED:
+            ws = _lstm_slots(ws[:4]) + ws[4:]
+        emb, Cw, Cb = _c(emb), _c(Cw), _c(Cb)
         dev = emb.device
         bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
         B, T = captions.shape
@@ -783,82 +788,67 @@ class DecoderAttSeqFn(torch.autograd.Function):
             raise CapnetError("features must be [batch, pixels, feature_size]")
         P, Cf = features.shape[1], features.shape[2]
         N = sum(bs)
-        if len(tf) != len(bs) or bs[0] != B:
-            raise CapnetError("attention decoder: batch_sizes / tf_mask do not match the batch")
         dims = [B, T, len(bs), N, E, F, H, V, A, P, Cf, cell]
-        ws = [_c(w) for w in weights]
-        emb_c, Cw_c, Cb_c = _c(emb), _c(Cw), _c(Cb)
         cdims = int_array(dims)
         L = _lib.lib()
-        saved = torch.empty(L.capnet_att_saved_floats(cdims), dtype=torch.float32, device=dev)
-        saved_i = torch.empty(L.capnet_att_saved_ints(cdims), dtype=torch.int32, device=dev)
-        scratch = torch.empty(L.capnet_att_fwd_scratch_floats(cdims), dtype=torch.float32, device=dev)
-        hiddens = torch.empty((N, H), dtype=torch.float32, device=dev)
+        saved = [torch.empty(L.capnet_att_stacked_saved_floats(cdims, l), dtype=torch.float32, device=dev) for l in range(nl)]
+        saved_i = [torch.empty(L.capnet_att_stacked_saved_ints(cdims, l), dtype=torch.int32, device=dev) for l in range(nl)]
+        scratch = torch.empty(L.capnet_att_stacked_fwd_scratch_floats(cdims, nl), dtype=torch.float32, device=dev)
+        # upper layers: B leading rows hold the initial state
+        hid = [torch.empty((N if l == 0 else B + N, H), dtype=torch.float32, device=dev) for l in range(nl)]
         alphas = torch.empty((B, len(bs), P), dtype=torch.float32, device=dev)
-        tfm = (C.c_ubyte * len(tf))(*[1 if x else 0 for x in tf])
-        check(L.capnet_att_seq_forward(cdims, int_array(bs), tfm, ptr(captions), ptr(features),
-                                       ptr(emb_c), ptr_array(_att_slots(ws, cell)), ptr(Cw_c), ptr(Cb_c),
-                                       float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]),
-                                       ptr(saved), ptr(saved_i), ptr(scratch), ptr(hiddens),
-                                       ptr(alphas), ptr(err_flag(dev)), current_stream()),
-              "capnet_att_seq_forward")
-        ctx.cfg, ctx.dims = cfg, dims
-        ctx.save_for_backward(saved, saved_i, hiddens, features, *ws)
-        return hiddens, alphas
+        check(L.capnet_att_seq_forward_stacked(cdims, nl, int_array(bs), _tf_bytes(tf), ptr(captions), ptr(features),
+                                               ptr(emb), ptr_array(ws), ptr(Cw), ptr(Cb), float(cfg["dropout"]),
+                                               int(cfg["seed"]), int(cfg["training"]), ptr_array(saved), ptr_array(saved_i),
+                                               ptr(scratch), ptr_array(hid), ptr(alphas), ptr(err_flag(dev)),
+                                               current_stream()), "capnet_att_seq_forward_stacked")
+        ctx.cfg, ctx.dims, ctx.nl = cfg, dims, nl
+        ctx.save_for_backward(*(saved + saved_i + hid), features, *ws)
+        return (hid[0] if nl == 1 else hid[-1][B:]), alphas
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_hiddens, d_alphas):
-        saved, saved_i, hiddens, features = ctx.saved_tensors[:4]
-        ws = list(ctx.saved_tensors[4:])
-        cfg, dims = ctx.cfg, ctx.dims
+        cfg, dims, nl = ctx.cfg, ctx.dims, ctx.nl
+        t = ctx.saved_tensors
+        saved, saved_i, hid, features, ws = t[:nl], t[nl:2 * nl], t[2 * nl:3 * nl], t[3 * nl], t[3 * nl + 1:]
         B, T, steps, N, E, F, H, V, A, P, Cf, cell = dims
-        dev = saved.device
+        dev = features.device
         L = _lib.lib()
         cdims = int_array(dims)
-        scratch = torch.empty(L.capnet_att_bwd_scratch_floats(cdims), dtype=torch.float32, device=dev)
-        d_hiddens = _c(d_hiddens)
-        d_alphas = _c(d_alphas) if d_alphas is not None else None
+        scratch = torch.empty(L.capnet_att_stacked_bwd_scratch_floats(cdims, nl), dtype=torch.float32, device=dev)
 
         def new(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
 
-        ZW, XW = 4 * H + A + Cf, E + Cf
+        d_hiddens = _c(d_hiddens) if d_hiddens is not None else torch.zeros((N, H), dtype=torch.float32, device=dev)
+        d_alphas = _c(d_alphas) if d_alphas is not None else None
+        XW = E + Cf
         if cell == CELL_FACTORED:
             dV, dbV, dS, dbS, dU = new(4 * F, XW), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F)
         else:
             dV, dbV, dS, dbS, dU = new(4 * H, XW), None, None, None, None
-        dWz, dbz = new(ZW, H), new(ZW)
+        dWz, dbz = new(4 * H + A + Cf, H), new(4 * H + A + Cf)
         dWe, dbe, dwf, dbf = new(A, Cf), new(A), new(1, A), new(1)
         dWih, dbih, dWic, dbic = new(H, Cf), new(H), new(H, Cf), new(H)
         dEmb = new(V, E)
         grads = [dV, dbV, dS, dbS, dU, dWz, dbz, dWe, dbe, dwf, dbf, dWih, dbih, dWic, dbic, dEmb]
-        check(L.capnet_att_seq_backward(cdims, int_array(cfg["batch_sizes"]), ptr(d_hiddens),
-                                        ptr(d_alphas), ptr(hiddens), ptr(features),
-                                        ptr_array(_att_slots(ws, cell)),
-                                        ptr(saved), ptr(saved_i), ptr(scratch), ptr_array(grads),
-                                        float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]),
-                                        current_stream()), "capnet_att_seq_backward")
-        tail = [dWih, dbih, dWic, dbic, dWe, dbe,
-                dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
-                dWz[4 * H + A:], dbz[4 * H + A:]]
-        if cell != CELL_FACTORED:
-            wg = [dV, dbz[:4 * H], dWz[:4 * H], dbz[:4 * H].clone()] + tail
-            return (None, None, None, dEmb, None, None) + tuple(wg)
-        wg = ([dV[g * F:(g + 1) * F] for g in range(4)] +
-              [dbV[g * F:(g + 1) * F] for g in range(4)] +
-              [dS[g] for g in range(4)] +
-              [dbS[g * F:(g + 1) * F] for g in range(4)] +
-              [dU[g] for g in range(4)] +
-              [dbz[g * H:(g + 1) * H] for g in range(4)] +
-              [dWz[g * H:(g + 1) * H] for g in range(4)] +
-              [dbz[g * H:(g + 1) * H].clone() for g in range(4)] +
-              [dWih, dbih, dWic, dbic, dWe, dbe,
-               dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
-               dWz[4 * H + A:], dbz[4 * H + A:]])
+        upper = []
+        for _ in range(1, nl):
+            g = [new(4 * F, H), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H),
+                 new(H, Cf), new(H), new(H, Cf), new(H)]
+            grads += g
+            upper.append(g)
+        dh_work = [new(N, H) for _ in range(nl - 1)]
+        check(L.capnet_att_seq_backward_stacked(cdims, nl, int_array(cfg["batch_sizes"]), ptr(d_hiddens), ptr(d_alphas),
+                                                ptr_array(hid), ptr(features), ptr_array(ws), ptr_array(saved),
+                                                ptr_array(saved_i), ptr(scratch), ptr_array(dh_work) if dh_work else None,
+                                                ptr_array(grads), float(cfg["dropout"]), int(cfg["seed"]),
+                                                int(cfg["training"]), current_stream()), "capnet_att_seq_backward_stacked")
+        wg = _gate_grads(cell, F, H, dV, dbV, dS, dbS, dU, dbz, dWz)
+        wg += [dWih, dbih, dWic, dbic, dWe, dbe, dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
+               dWz[4 * H + A:], dbz[4 * H + A:]]
+        for g in upper:
+            wg += _gate_grads(CELL_FACTORED, F, H, *g[:7]) + g[7:]
         # cfg, captions, features, emb, Cw, Cb, *weights
         return (None, None, None, dEmb, None, None) + tuple(wg)
-
-
-def decoder_att_sequence(cfg, captions, features, emb, Cw, Cb, weights):
-    return DecoderAttSeqFn.apply(cfg, captions, features, emb, Cw, Cb, *weights)

@@ -22,125 +22,21 @@ Why the attention query is layer 0's state and not the top layer's: the attentio
 teacher-forced steps goes up the stack run by run (layer 0 steps through the run, then each upper layer takes the run's
 rows in one persistent launch). A query from the top layer would serialise every layer at every step.
 
-Engine: the whole recurrence is ONE C call each way (StackedAttSeqFn -> capnet_att_seq_forward_stacked /
-capnet_att_seq_backward_stacked, csrc/decoder_att_seq.cpp). A lone step of an upper layer with <= 16 rows (every
-free-running step, at 12 rows per GPU) is one launch of csrc/lstm_upper_step.hip; CAPNET_NO_FUSED_UPPER_STEP=1 takes
-the composed path (rows_dropout, three chain products, the fused recurrent step) instead. capnet.parallel is
-parameter-generic: data-parallel training needs nothing more.
+Engine: the whole recurrence is ONE C call each way: DecoderFactoredLSTMAtt.forward with this class's upper layers
+(_upper_layers) -> ops.AttSeqFn -> capnet_att_seq_forward_stacked / capnet_att_seq_backward_stacked
+(csrc/decoder_att_seq.cpp). A lone step of an upper layer with <= 16 rows (every free-running step, at 12 rows per GPU)
+is one launch of csrc/lstm_upper_step.hip; CAPNET_NO_FUSED_UPPER_STEP=1 takes the composed path (rows_dropout, three
+chain products, the fused recurrent step) instead. capnet.parallel is parameter-generic: data-parallel training needs
+nothing more.
 """
 import torch
-import torch.nn as nn
 
-from torch.autograd.function import once_differentiable
-
-from . import _lib, ops
-from ._lib import CapnetError, check, current_stream, int_array, ptr
-from .model import Linear, _MODES, _dropout_seed, _resolve_tf_mask
+from . import ops
+from ._lib import CapnetError
+from .model import Linear, _MODES
 from .model_att import DecoderFactoredLSTMAtt
 
 _S_PREFIX = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}
-
-
-class StackedAttSeqFn(torch.autograd.Function):
-    """(top-layer hiddens [N, H], alphas [B, steps, P]) of the stacked attention recurrence.
-    weights: layer 0's 44 tensors (DecoderAttSeqFn's order), then 36 per upper layer: V w x4, V b x4, S w x4, S b x4,
-    U w x4, U b x4, W w x4, W b x4, init_h{l} w, b, init_c{l} w, b. `features` gets no gradient (frozen trunk)."""
-
-    @staticmethod
-    def forward(ctx, cfg, captions, features, emb, Cw, Cb, *weights):
-        ops._need_cuda(captions, features, emb, Cw, Cb, *weights)
-        nl = cfg["num_layers"]
-        if len(weights) != 44 + 36 * (nl - 1):
-            raise CapnetError("stacked attention decoder takes 44 + 36 (num_layers - 1) weight tensors")
-        captions = captions.contiguous()
-        if captions.dtype != torch.int64:
-            raise CapnetError("captions must be int64")
-        dev = emb.device
-        bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
-        B, T = captions.shape
-        V, E = emb.shape
-        H, A, F = cfg["hidden_size"], cfg["attention_size"], cfg["factored_size"]
-        features = features.contiguous()
-        if features.dim() != 3 or features.shape[0] != B:
-            raise CapnetError("features must be [batch, pixels, feature_size]")
-        P, Cf = features.shape[1], features.shape[2]
-        N = sum(bs)
-        if len(tf) != len(bs) or bs[0] != B:
-            raise CapnetError("attention decoder: batch_sizes / tf_mask do not match the batch")
-        dims = [B, T, len(bs), N, E, F, H, V, A, P, Cf, ops.CELL_FACTORED]
-        ws = [w.contiguous() for w in weights]
-        emb_c, Cw_c, Cb_c = emb.contiguous(), Cw.contiguous(), Cb.contiguous()
-        cdims = int_array(dims)
-        L = _lib.lib()
-        saved = [torch.empty(L.capnet_att_stacked_saved_floats(cdims, l), dtype=torch.float32, device=dev) for l in range(nl)]
-        saved_i = [torch.empty(L.capnet_att_stacked_saved_ints(cdims, l), dtype=torch.int32, device=dev) for l in range(nl)]
-        scratch = torch.empty(L.capnet_att_stacked_fwd_scratch_floats(cdims, nl), dtype=torch.float32, device=dev)
-        # upper layers: B leading rows hold the initial state
-        hid = [torch.empty((N if l == 0 else B + N, H), dtype=torch.float32, device=dev) for l in range(nl)]
-        alphas = torch.empty((B, len(bs), P), dtype=torch.float32, device=dev)
-        tfm = (_lib.C.c_ubyte * len(tf))(*[1 if x else 0 for x in tf])
-        check(L.capnet_att_seq_forward_stacked(cdims, nl, int_array(bs), tfm, ptr(captions), ptr(features), ptr(emb_c),
-                                               _lib.ptr_array(ws), ptr(Cw_c), ptr(Cb_c), float(cfg["dropout"]),
-                                               int(cfg["seed"]), int(cfg["training"]), _lib.ptr_array(saved),
-                                               _lib.ptr_array(saved_i), ptr(scratch), _lib.ptr_array(hid), ptr(alphas),
-                                               ptr(ops.err_flag(dev)), current_stream()),
-              "capnet_att_seq_forward_stacked")
-        ctx.cfg, ctx.dims = cfg, dims
-        ctx.save_for_backward(*(saved + saved_i + hid), features, *ws)
-        return (hid[0] if nl == 1 else hid[-1][B:]), alphas
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_hiddens, d_alphas):
-        cfg, dims = ctx.cfg, ctx.dims
-        nl = cfg["num_layers"]
-        t = ctx.saved_tensors
-        saved, saved_i, hid = list(t[:nl]), list(t[nl:2 * nl]), list(t[2 * nl:3 * nl])
-        features, ws = t[3 * nl], list(t[3 * nl + 1:])
-        B, T, steps, N, E, F, H, V, A, P, Cf, _ = dims
-        dev = features.device
-        L = _lib.lib()
-        cdims = int_array(dims)
-        scratch = torch.empty(L.capnet_att_stacked_bwd_scratch_floats(cdims, nl), dtype=torch.float32, device=dev)
-
-        def new(*shape):
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-
-        d_hiddens = d_hiddens.contiguous() if d_hiddens is not None else torch.zeros((N, H), dtype=torch.float32, device=dev)
-        d_alphas = d_alphas.contiguous() if d_alphas is not None else None
-        ZW, XW = 4 * H + A + Cf, E + Cf
-        dV, dbV, dS, dbS, dU = new(4 * F, XW), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F)
-        dWz, dbz = new(ZW, H), new(ZW)
-        dWe, dbe, dwf, dbf = new(A, Cf), new(A), new(1, A), new(1)
-        dWih, dbih, dWic, dbic = new(H, Cf), new(H), new(H, Cf), new(H)
-        dEmb = new(V, E)
-        grads = [dV, dbV, dS, dbS, dU, dWz, dbz, dWe, dbe, dwf, dbf, dWih, dbih, dWic, dbic, dEmb]
-        upper = []
-        for _ in range(1, nl):
-            g = [new(4 * F, H), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H),
-                 new(H, Cf), new(H), new(H, Cf), new(H)]
-            grads += g
-            upper.append(g)
-        dh_work = [new(N, H) for _ in range(nl - 1)]
-        check(L.capnet_att_seq_backward_stacked(cdims, nl, int_array(cfg["batch_sizes"]), ptr(d_hiddens), ptr(d_alphas),
-                                                _lib.ptr_array(hid), ptr(features), _lib.ptr_array(ws),
-                                                _lib.ptr_array(saved), _lib.ptr_array(saved_i), ptr(scratch),
-                                                _lib.ptr_array(dh_work) if dh_work else None, _lib.ptr_array(grads),
-                                                float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]),
-                                                current_stream()), "capnet_att_seq_backward_stacked")
-        wg = ([dV[g * F:(g + 1) * F] for g in range(4)] + [dbV[g * F:(g + 1) * F] for g in range(4)] +
-              [dS[g] for g in range(4)] + [dbS[g * F:(g + 1) * F] for g in range(4)] + [dU[g] for g in range(4)] +
-              [dbz[g * H:(g + 1) * H] for g in range(4)] + [dWz[g * H:(g + 1) * H] for g in range(4)] +
-              [dbz[g * H:(g + 1) * H].clone() for g in range(4)] +
-              [dWih, dbih, dWic, dbic, dWe, dbe, dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
-               dWz[4 * H + A:], dbz[4 * H + A:]])
-        for uV, ubV, uS, ubS, uU, ubUW, uW, uih, ubih, uic, ubic in upper:
-            wg += ([uV[g * F:(g + 1) * F] for g in range(4)] + [ubV[g * F:(g + 1) * F] for g in range(4)] +
-                   [uS[g] for g in range(4)] + [ubS[g * F:(g + 1) * F] for g in range(4)] + [uU[g] for g in range(4)] +
-                   [ubUW[g * H:(g + 1) * H] for g in range(4)] + [uW[g * H:(g + 1) * H] for g in range(4)] +
-                   [ubUW[g * H:(g + 1) * H].clone() for g in range(4)] + [uih, ubih, uic, ubic])
-        # cfg, captions, features, emb, Cw, Cb, *weights
-        return (None, None, None, dEmb, None, None) + tuple(wg)
 
 
 class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
@@ -199,6 +95,12 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
         for m in (getattr(self, "init_h%d" % l), getattr(self, "init_c%d" % l)):
             out += [m.weight, m.bias]
         return out
+
+    def _upper_layers(self, mode):
+        weights = []
+        for l in range(1, self.num_layers):
+            weights += self._upper_weights(l, mode)
+        return self.num_layers, weights
 
     def _upper_init(self, l, mean_features):
         return getattr(self, "init_h%d" % l)(mean_features), getattr(self, "init_c%d" % l)(mean_features)
@@ -293,27 +195,3 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
 
             return beam_search_batched(step_fn, tuple(state0 + [img]), n, self.vocab_size, start_token, end_token, k,
                                        self.max_seq_length, dev)
-
-    # ---- training -----------------------------------------------------------------------------------
-    def forward(self, captions, lengths, features, teacher_forcing_ratio=0.8, mode='factual', tf_mask=None):
-        """Returns (outputs [N, V], alphas [B, max(lengths), P]) -- layer 0's alphas."""
-        batch_size = captions.size(0)
-        features = features.reshape(batch_size, -1, features.size(-1))
-        batch_sizes = ops.batch_sizes_from_lengths(lengths)
-        weights = self._weights(mode)
-        for l in range(1, self.num_layers):
-            weights += self._upper_weights(l, mode)
-        cfg = {
-            "batch_sizes": batch_sizes,
-            "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
-            "hidden_size": self.hidden_size,
-            "factored_size": self.factored_size,
-            "attention_size": self.attention_size,
-            "num_layers": self.num_layers,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-        }
-        hiddens, alphas = StackedAttSeqFn.apply(cfg, captions, features.detach(), self.B.weight, self.C.weight,
-                                                self.C.bias, *weights)
-        return self.C(hiddens), alphas

@@ -342,7 +342,8 @@ int capnet_bn1d_bwd(const float* dy, const float* x, int B, int C, const float* 
  * steps, for the argmax feedback). hiddens [N][H] is the packed `torch.cat(hiddens, 0)`.
  * saved / saved_i / scratch: caller-provided device buffers of the sizes queried below; saved
  * buffers must reach the matching backward call untouched. err_flag: device int, set non-zero
- * when a token id is out of range (the caller checks it when it next synchronises). */
+ * when a token id is out of range (the caller checks it when it next synchronises).
+ * capnet_seq_forward / _backward are capnet_seq_forward_stacked / _backward_stacked at nlayers = 1. */
 size_t capnet_seq_saved_floats(const int* dims);
 size_t capnet_seq_saved_ints(const int* dims);
 size_t capnet_seq_fwd_scratch_floats(const int* dims);
@@ -365,7 +366,8 @@ int capnet_seq_backward(const int* dims, const int* batch_sizes, const float* d_
                         float* scratch, float* const* grads, float dropout_p,
                         unsigned long long seed, int training, capnet_stream_t stream);
 
-/* Stacked FactoredLSTM layers (BASELINE configs[3] / [4]: "2-layer", "3-layer"). PERF-ONLY, PARITY UNPINNED: the reference
+/* 1 to 8 layers: at nlayers = 1 either cell (capnet_seq_forward / _backward); more are stacked FactoredLSTM layers
+ * (cell 0 only; BASELINE configs[3] / [4]: "2-layer", "3-layer"). PERF-ONLY, PARITY UNPINNED: the reference
  * advertises lstm_layers 1, 2, 3 (README.md:24) but its decoders ignore num_layers (stylenet/model.py:37); the semantics
  * are SURVEY App. A-1's, modelled on the only stacking in the tree (seq2seq/model.py:45-49): layer l > 0 is the same
  * factored cell on dropout(hidden of layer l - 1) at the same step (V: Linear(H -> F)), the top layer's hidden feeds C.
@@ -397,7 +399,8 @@ int capnet_seq_backward_stacked(const int* dims, int nlayers, const int* batch_s
  * capnet_seq_forward (V_g is [F][E+C]); [32,33] init_h w,b  [34,35] init_c  [36,37] the selected
  * attention module's encoder_att  [38,39] decoder_att  [40,41] full_att  [42,43] f_beta.
  * Outputs: hiddens [N][H]; alphas [B][steps][P] (zero where a sequence has ended, :261,296).
- * encoder_att(features) is computed once per call, not once per step (:59,279). */
+ * encoder_att(features) is computed once per call, not once per step (:59,279).
+ * capnet_att_seq_forward / _backward are capnet_att_seq_forward_stacked / _backward_stacked at nlayers = 1. */
 /* Process-wide choice for the factored cell's input product U_g (S_g (V_g x + bV_g) + bS_g) (stylenet/model_att.py:196-236)
  * inside capnet_att_seq_forward/backward: 0 = by shape (batches of at most 16 rows run it as ONE product per step against
  * U_g S_g V_g, formed once per call, and form the intermediate rows for all steps at once in the backward: the steps of
@@ -438,8 +441,9 @@ int capnet_att_seq_backward(const int* dims, const int* batch_sizes, const float
                             float* scratch, float* const* grads, float dropout_p,
                             unsigned long long seed, int training, capnet_stream_t stream);
 
-/* Stacked attention decoder (capnet.stacked_att.StackedFactoredLSTMAtt; PERF-ONLY, PARITY UNPINNED: the reference
- * ignores num_layers). Layer 0 is capnet_att_seq_forward's cell (factored only); layer l > 0 is the factored cell on
+/* The attention decoder of 1 to 8 layers: at nlayers = 1 either cell (capnet_att_seq_forward / _backward); more layers are
+ * capnet.stacked_att.StackedFactoredLSTMAtt (cell 0 only; PERF-ONLY, PARITY UNPINNED: the reference ignores
+ * num_layers). Layer 0 is capnet_att_seq_forward's cell; layer l > 0 is the factored cell on
  * dropout_l(h^{l-1}_t) (the mask capnet_rows_dropout draws for layer l, training only) with initial state
  * init_h{l} / init_c{l}(mean over pixels); only the top layer feeds C (the argmax of free-running steps).
  * dims: as capnet_att_seq_forward. saved[l] / saved_i[l]: capnet_att_stacked_saved_floats / _ints(dims, l) each;

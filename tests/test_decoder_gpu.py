@@ -8,9 +8,11 @@ import pytest
 import torch
 
 import capnet
-from capnet import ops, synthetic
+from capnet import _lib, ops, synthetic
 from capnet.model import DecoderFactoredLSTM
+from capnet.model_att import DecoderFactoredLSTMAtt
 from capnet.nic_model import DecoderRNN
+from capnet.nic_model_att import DecoderRNNAtt
 from capnet.optim import Adam
 from capnet.utils import clip_gradient
 from helpers import golden_case, golden_params, load_golden, rel_err, t
@@ -212,6 +214,82 @@ def test_factored_full_size_losses_match_reference_scalars(dev):
     ops.check_device_errors()
 
 
+def _same_bits_as_the_single_layer_entries(fn, cfg, captions, feats, emb, Cw, Cb, weights, cdims, single):
+    """Runs fn (ops.SeqFn / ops.AttSeqFn) forward and backward on leaf copies of the inputs, then single(...) -- the same
+    forward and backward through the single-layer C entries -- and asserts bitwise-equal outputs and gradients."""
+    leaves = [w.detach().clone().requires_grad_(True) for w in (emb,) + tuple(weights)]
+    f = feats.detach().clone().requires_grad_(fn is ops.SeqFn) if feats is not None else None
+    outs = fn.apply(cfg, captions, f, leaves[0], Cw, Cb, *leaves[1:])
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    d_outs = [torch.randn(o.shape, generator=torch.Generator().manual_seed(7)).to(o.device) for o in outs]
+    torch.autograd.backward(outs, d_outs)
+    want_outs, want_grads = single(cfg, captions, f, emb.detach(), Cw, Cb, [w.detach() for w in weights], cdims, d_outs)
+    for got, want in zip(outs, want_outs):
+        assert torch.equal(got, want)
+    got_grads = [leaves[0].grad] + [w.grad for w in leaves[1:]] + ([f.grad] if fn is ops.SeqFn and f is not None else [])
+    assert len(got_grads) == len(want_grads)
+    for k, (got, want) in enumerate(zip(got_grads, want_grads)):
+        assert torch.equal(got, want), k
+
+
+def _single_seq(cfg, captions, feats, emb, Cw, Cb, ws, dims, d_outs):
+    """capnet_seq_forward / capnet_seq_backward -> ((hiddens,), [d emb, per-weight gradients, d features])."""
+    L, dev, cell = capnet.lib(), emb.device, dims[-1]
+    B, T, steps, N, E, F, H, V = dims[:8]
+    cd = _lib.int_array(dims)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    saved, saved_i = new(L.capnet_seq_saved_floats(cd)), torch.empty(L.capnet_seq_saved_ints(cd), dtype=torch.int32, device=dev)
+    hid = new(N, H)
+    table = _lib.ptr_array(ws if cell == ops.CELL_FACTORED else ops._lstm_slots(ws))
+    args = (float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]))
+    _lib.check(L.capnet_seq_forward(cd, _lib.int_array(cfg["batch_sizes"]), ops._tf_bytes(cfg["tf_mask"]), _lib.ptr(captions),
+                                    _lib.ptr(feats), _lib.ptr(emb), table, _lib.ptr(Cw), _lib.ptr(Cb), *args, _lib.ptr(saved),
+                                    _lib.ptr(saved_i), _lib.ptr(new(L.capnet_seq_fwd_scratch_floats(cd))), _lib.ptr(hid),
+                                    _lib.ptr(ops.err_flag(dev)), _lib.current_stream()), "capnet_seq_forward")
+    if cell == ops.CELL_FACTORED:
+        g = [new(4 * F, E), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H)]
+    else:
+        g = [new(4 * H, E), None, None, None, None, new(4 * H), new(4 * H, H)]
+    dEmb, dFeat = new(V, E), new(B, E) if feats is not None else None
+    _lib.check(L.capnet_seq_backward(cd, _lib.int_array(cfg["batch_sizes"]), _lib.ptr(d_outs[0]), _lib.ptr(hid),
+                                     _lib.ptr(saved), _lib.ptr(saved_i), _lib.ptr(new(L.capnet_seq_bwd_scratch_floats(cd))),
+                                     _lib.ptr_array(g + [dEmb, dFeat]), *args, _lib.current_stream()), "capnet_seq_backward")
+    return (hid,), [dEmb] + ops._gate_grads(cell, F, H, *g) + ([dFeat] if feats is not None else [])
+
+
+def _single_att(cfg, captions, feats, emb, Cw, Cb, ws, dims, d_outs):
+    """capnet_att_seq_forward / capnet_att_seq_backward -> ((hiddens, alphas), [d emb, per-weight gradients])."""
+    L, dev, cell = capnet.lib(), emb.device, dims[-1]
+    B, T, steps, N, E, F, H, V, A, P, Cf = dims[:11]
+    cd = _lib.int_array(dims)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    saved, saved_i = new(L.capnet_att_saved_floats(cd)), torch.empty(L.capnet_att_saved_ints(cd), dtype=torch.int32, device=dev)
+    hid, alphas = new(N, H), new(B, steps, P)
+    table = _lib.ptr_array(ws if cell == ops.CELL_FACTORED else ops._lstm_slots(ws[:4]) + ws[4:])
+    args = (float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]))
+    _lib.check(L.capnet_att_seq_forward(cd, _lib.int_array(cfg["batch_sizes"]), ops._tf_bytes(cfg["tf_mask"]),
+                                        _lib.ptr(captions), _lib.ptr(feats), _lib.ptr(emb), table, _lib.ptr(Cw), _lib.ptr(Cb),
+                                        *args, _lib.ptr(saved), _lib.ptr(saved_i),
+                                        _lib.ptr(new(L.capnet_att_fwd_scratch_floats(cd))), _lib.ptr(hid), _lib.ptr(alphas),
+                                        _lib.ptr(ops.err_flag(dev)), _lib.current_stream()), "capnet_att_seq_forward")
+    if cell == ops.CELL_FACTORED:
+        g = [new(4 * F, E + Cf), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F)]
+    else:
+        g = [new(4 * H, E + Cf), None, None, None, None]
+    dWz, dbz = new(4 * H + A + Cf, H), new(4 * H + A + Cf)
+    rest = [new(A, Cf), new(A), new(1, A), new(1), new(H, Cf), new(H), new(H, Cf), new(H)]
+    dWe, dbe, dwf, dbf, dWih, dbih, dWic, dbic = rest
+    dEmb = new(V, E)
+    _lib.check(L.capnet_att_seq_backward(cd, _lib.int_array(cfg["batch_sizes"]), _lib.ptr(d_outs[0]), _lib.ptr(d_outs[1]),
+                                         _lib.ptr(hid), _lib.ptr(feats), table, _lib.ptr(saved), _lib.ptr(saved_i),
+                                         _lib.ptr(new(L.capnet_att_bwd_scratch_floats(cd))),
+                                         _lib.ptr_array(g + [dWz, dbz] + rest + [dEmb]), *args, _lib.current_stream()),
+               "capnet_att_seq_backward")
+    return (hid, alphas), ([dEmb] + ops._gate_grads(cell, F, H, *g, dbz, dWz) +
+                           [dWih, dbih, dWic, dbic, dWe, dbe, dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
+                            dWz[4 * H + A:], dbz[4 * H + A:]])
+
+
 def test_dropout_is_deterministic_and_scaled(dev):
     E, H, F, V, B = 32, 32, 32, 101, 6
     dec = DecoderFactoredLSTM(E, H, F, V, 1, dropout=0.5).to(dev).train()
@@ -231,6 +309,29 @@ def test_dropout_is_deterministic_and_scaled(dev):
     dec.train(); random.seed(1)
     d2 = dec(captions.to(dev), lengths, feats, teacher_forcing_ratio=1.0)
     assert torch.equal(d1, d2)
+    # the single-layer C entries (the stacked entries at one layer; no Python path calls them) give the same bits as
+    # ops.SeqFn / ops.AttSeqFn, dropout on, scheduled sampling mixed, on a small case of each cell
+    random.seed(2)
+    bs, cap = ops.batch_sizes_from_lengths(lengths), captions.to(dev)
+    cfg = {"batch_sizes": bs, "tf_mask": [random.random() < 0.6 for _ in bs], "hidden_size": H, "dropout": 0.5,
+           "seed": 12345, "training": True}
+    N, P, A, Cf = sum(bs), 9, 16, 512
+    rnn = DecoderRNN(E, H, V, 1).to(dev)
+    lstm_w = [rnn.lstm.weight_ih, rnn.lstm.bias_ih, rnn.lstm.weight_hh, rnn.lstm.bias_hh]
+    for cell, ws in ((ops.CELL_FACTORED, dec._weights("happy")), (ops.CELL_LSTM, lstm_w)):
+        cf = dict(cfg, cell=cell, factored_size=F) if cell == ops.CELL_FACTORED else dict(cfg, cell=cell)
+        _same_bits_as_the_single_layer_entries(ops.SeqFn, cf, cap, feats, dec.B.weight, dec.C.weight,
+                                               dec.C.bias, ws, [B, cap.shape[1], len(bs), N, E, F if cell == 0 else 0, H, V,
+                                                                1, cell], _single_seq)
+    fmap = torch.randn(B, P, Cf, generator=torch.Generator().manual_seed(3)).to(dev)
+    att = DecoderFactoredLSTMAtt(A, E, H, F, V, 1, feature_size=Cf).to(dev)
+    natt = DecoderRNNAtt(A, E, H, V, 1, feature_size=Cf).to(dev)
+    for cell, ws in ((ops.CELL_FACTORED, att._weights("sad")), (ops.CELL_LSTM, natt._weights())):
+        _same_bits_as_the_single_layer_entries(ops.AttSeqFn, dict(cfg, cell=cell, factored_size=F, attention_size=A), cap, fmap,
+                                               dec.B.weight, dec.C.weight, dec.C.bias, ws,
+                                               [B, cap.shape[1], len(bs), N, E, F if cell == 0 else 4, H, V, A, P, Cf, cell],
+                                               _single_att)
+    ops.check_device_errors()
 
 
 @pytest.mark.parametrize("E,V,ratio,p", [(300, 7, 1.0, 0.0), (600, 7, 0.6, 0.0), (64, 23, 1.0, 0.5)])

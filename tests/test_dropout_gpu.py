@@ -325,12 +325,11 @@ def test_nic_att(dev, B, p):
     c.compare("nic att B=%d p=%.2f" % (B, p), 1e-4, 5e-4, control)
 
 
-# ---- StackedFactoredLSTM (engine "c"): embedding and between-layer masks, 2e-5 / 2e-4 (test_stacked_gpu.py) --------
+# ---- StackedFactoredLSTM: embedding and between-layer masks, 2e-5 / 2e-4 (test_stacked_gpu.py) --------
 @pytest.mark.parametrize("p,kind", [(0.22, "mixed"), (0.5, "teacher"), (0.5, "free")])
 def test_stacked(dev, p, kind):
     E, H, F, V, B, L = 300, 512, 1024, 500, 8, 3
     dec = StackedFactoredLSTM(E, H, F, V, L, dropout=p)
-    assert dec.engine == "c"
     prm = synthetic.decoder_state(dec.state_dict(), seed=11, bias_range=0.05)
     dec.load_state_dict(prm)
     dec.to(dev).train()

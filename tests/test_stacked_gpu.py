@@ -14,6 +14,7 @@ from capnet.model import DecoderFactoredLSTM
 from capnet.stacked import StackedFactoredLSTM
 from oracle import decoders_ref as D
 from helpers import rel_err
+from stacked_step_ref import stacked_step_forward
 
 pytestmark = pytest.mark.gpu
 
@@ -81,23 +82,21 @@ def test_one_layer_is_the_reference_decoder(dev):
     lb = ops.cross_entropy(b, ops.packed_targets(caps.to(dev), lens)); lb.backward()
     assert rel_err(dec.W_i.weight.grad, ref.W_i.weight.grad) < 1e-4
     assert rel_err(dec.B.weight.grad, ref.B.weight.grad) < 1e-4
+    with pytest.raises(capnet.CapnetError):         # the LSTM cell is one layer
+        ops.SeqFn.apply(dict(cell=ops.CELL_LSTM, num_layers=2), caps.to(dev), feats, dec.B.weight, dec.C.weight, dec.C.bias)
 
 
-@pytest.mark.parametrize("engine_a", ["c", "python"])
-def test_runs_through_the_persistent_kernel_equal_the_step_by_step_engine(dev, engine_a):
-    """Three layers at the size the persistent kernel takes (H = 512): logits, loss and every gradient of (c) the whole
-    recurrence as one C call each way (capnet_seq_forward_stacked / _backward_stacked) and of (python) the engine that runs
-    each teacher-forced run of a layer in one launch (capnet.stacked.LstmRunFn) against the step-by-step engine (W GEMM +
-    cell kernel per step, torch autograd composing the backward), same weights, same scheduled-sampling decisions,
-    shrinking batches."""
+def test_runs_through_the_persistent_kernel_equal_the_step_by_step_engine(dev):
+    """Three layers at the size the persistent kernel takes (H = 512): logits, loss and every gradient of the whole
+    recurrence as one C call each way (capnet_seq_forward_stacked / _backward_stacked) against the step-by-step engine
+    (tests/stacked_step_ref.py: W GEMM + cell kernel per step, torch autograd composing the backward), same weights, same
+    scheduled-sampling decisions, shrinking batches."""
     E, H, F, V, B, layers = 300, 512, 256, 500, 9, 3
     a = StackedFactoredLSTM(E, H, F, V, layers, dropout=0.0)
     p = synthetic.decoder_state(a.state_dict(), seed=21)
     a.load_state_dict(p)
     b = StackedFactoredLSTM(E, H, F, V, layers, dropout=0.0)
     b.load_state_dict(p)
-    b.engine, b.fast_runs = "python", False
-    a.engine = engine_a
     a.to(dev).train()
     b.to(dev).train()
     _, caps, lens = synthetic.make_batch(B, V, seed=4)
@@ -106,7 +105,7 @@ def test_runs_through_the_persistent_kernel_equal_the_step_by_step_engine(dev, e
     tf = [random.random() < 0.75 for _ in range(max(lens))]
     assert not all(tf) and sum(tf) >= 4
     oa = a(caps.to(dev), lens, feats, mode="happy", tf_mask=tf)
-    ob = b(caps.to(dev), lens, feats, mode="happy", tf_mask=tf)
+    ob = stacked_step_forward(b, caps.to(dev), lens, feats, tf, mode="happy")
     assert rel_err(oa, ob) < 1e-5
     la = ops.cross_entropy(oa, ops.packed_targets(caps.to(dev), lens)); la.backward()
     lb = ops.cross_entropy(ob, ops.packed_targets(caps.to(dev), lens)); lb.backward()
