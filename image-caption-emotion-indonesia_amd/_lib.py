@@ -129,6 +129,8 @@ SIGNATURES = {
     "capnet_lstm_pointwise_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "capnet_stacked_decode_step": (_i, [_i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp,
                                         _vp]),
+    "capnet_stacked_decode_step_cell": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                             _vp, _vp, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),
     "capnet_lstm_pack_wfrag": (_i, [_vp, _vp, _i, _i, _vp]),
     "capnet_lstm_step_fused": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -346,9 +346,11 @@ int capnet_lstm_pointwise_fwd(float* pre, const float* c_prev, float* c_out, flo
   return lstm_pointwise_fwd(pre, 4L * H, c_prev, c_out, h_out, b, H, 0, 1, 3, 2, 1, S(stream));
 }
 
-int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
-                               const float* const* wcat, const float* const* beff, const float* state_in,
-                               float* state_out, float* h_top, int* err_flag, capnet_stream_t stream) {
+int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                    const float* x, const float* const* wcat, const float* const* beff,
+                                    const float* state_in, float* state_out, float* h_top, int* err_flag,
+                                    capnet_stream_t stream) {
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "stacked_decode_step: unknown cell %d", cell);
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "stacked_decode_step: layers %d (1..8)", nlayers);
   CAPNET_REQUIRE(rows >= 1, "stacked_decode_step: rows %d", rows);
   CAPNET_REQUIRE(stacked_decode_supported(E, H), "stacked_decode_step: unsupported E=%d H=%d", E, H);
@@ -360,8 +362,15 @@ int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const
     CAPNET_REQUIRE(wcat[l] && beff[l], "stacked_decode_step: weights of layer %d are null", l);
     CAPNET_REQUIRE(aligned16(wcat[l]), "stacked_decode_step: weights of layer %d not 16-B aligned", l);
   }
-  return stacked_decode_step(nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top, err_flag,
+  return stacked_decode_step(cell, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top, err_flag,
                              S(stream));
+}
+
+int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                               const float* const* wcat, const float* const* beff, const float* state_in,
+                               float* state_out, float* h_top, int* err_flag, capnet_stream_t stream) {
+  return capnet_stacked_decode_step_cell(kCellFactored, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out,
+                                         h_top, err_flag, stream);
 }
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream) {
@@ -429,8 +438,7 @@ int capnet_seq_forward_stacked(const int* dims, int nlayers, const int* batch_si
                                float* scratch, float* const* hiddens, int* err_flag, capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && nlayers >= 1 && nlayers <= 8, "seq_forward_stacked: null dims / weights or layers %d", nlayers);
   const SeqDims d = to_dims(dims);
-  CAPNET_REQUIRE(d.cell == kCellFactored || (d.cell == kCellLSTM && nlayers == 1),
-                 "seq_forward_stacked: cell %d with %d layers (the LSTM cell is one layer)", d.cell, nlayers);
+  CAPNET_REQUIRE(d.cell == kCellFactored || d.cell == kCellLSTM, "seq_forward_stacked: unknown cell %d", d.cell);
   SeqWeights w[8];
   for (int l = 0; l < nlayers; ++l) {
     for (int i = 0; i < 32; ++i)
@@ -510,7 +518,6 @@ int capnet_att_seq_forward_stacked(const int* dims, int nlayers, const int* batc
                                    capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && nlayers >= 1 && nlayers <= 8, "att_seq_forward_stacked: null dims / weights or layers %d",
                  nlayers);
-  CAPNET_REQUIRE(dims[11] == kCellFactored || nlayers == 1, "att_seq_forward_stacked: the LSTM cell is one layer");
   AttWeights w0;
   int rc = to_aweights(weights, &w0, dims[11]);
   if (rc) return rc;
@@ -518,7 +525,9 @@ int capnet_att_seq_forward_stacked(const int* dims, int nlayers, const int* batc
   UpperInit iu[8];
   for (int l = 1; l < nlayers; ++l) {
     const float* const* p = weights + 44 + 36 * (l - 1);
-    for (int i = 0; i < 36; ++i) CAPNET_REQUIRE(p[i], "att_seq_forward_stacked: weight %d of layer %d is null", i, l);
+    for (int i = 0; i < 36; ++i)
+      CAPNET_REQUIRE(p[i] || (i < 32 && !weight_used(dims[11], i)), "att_seq_forward_stacked: weight %d of layer %d is null",
+                     i, l);
     to_weights(p, wu[l - 1]);
     iu[l - 1] = UpperInit{p[32], p[33], p[34], p[35]};
   }
@@ -533,7 +542,6 @@ int capnet_att_seq_backward_stacked(const int* dims, int nlayers, const int* bat
                                     unsigned long long seed, int training, capnet_stream_t stream) {
   CAPNET_REQUIRE(dims && weights && grads && nlayers >= 1 && nlayers <= 8,
                  "att_seq_backward_stacked: null dims / weights / grads or layers %d", nlayers);
-  CAPNET_REQUIRE(dims[11] == kCellFactored || nlayers == 1, "att_seq_backward_stacked: the LSTM cell is one layer");
   AttWeights w0;
   int rc = to_aweights(weights, &w0, dims[11]);
   if (rc) return rc;
@@ -543,7 +551,9 @@ int capnet_att_seq_backward_stacked(const int* dims, int nlayers, const int* bat
   UpperInitGrads giu[8];
   for (int l = 1; l < nlayers; ++l) {
     float* const* q = grads + 16 + 11 * (l - 1);
-    for (int i = 0; i < 11; ++i) CAPNET_REQUIRE(q[i], "att_seq_backward_stacked: gradient %d of layer %d is null", i, l);
+    for (int i = 0; i < 11; ++i)
+      CAPNET_REQUIRE(q[i] || (i >= 1 && i <= 4 && dims[11] != kCellFactored),
+                     "att_seq_backward_stacked: gradient %d of layer %d is null", i, l);
     to_grads(q, gu[l - 1]);
     gu[l - 1].dEmb = gu[l - 1].dFeat = nullptr;       // (q[7..10]: init_h{l} / init_c{l}; no embedding, no features)
     giu[l - 1] = UpperInitGrads{q[7], q[8], q[9], q[10]};

@@ -447,8 +447,9 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
 }
 
 // ---- stacked attention decoder (capnet.stacked_att) -------------------------------------------------------------------
-// PERF-ONLY, PARITY UNPINNED: the reference accepts num_layers and ignores it (stylenet/model_att.py:81). Layer 0 is the
-// cell above, unchanged; its attention and f_beta gate read layer 0's own h^0_{t-1}. Layer l > 0 is the factored cell on
+// PERF-ONLY, PARITY UNPINNED: the reference accepts num_layers and ignores it (stylenet/model_att.py:81, nic/model_att.py:79).
+// Layer 0 is the cell above, unchanged; its attention and f_beta gate read layer 0's own h^0_{t-1}. Layer l > 0 is layer 0's
+// cell (factored: capnet.stacked_att; nn.LSTMCell(H, H): capnet.nic_stacked) on
 // dropout_l(h^{l-1}_t) with its own parameters and initial state init_h{l} / init_c{l}(mean over pixels); only the top
 // layer feeds C. As the attention stays inside layer 0, a run of teacher-forced steps goes up the stack run by run: layer
 // 0 steps through the run, then each upper layer takes the run's rows (decoder_seq.cpp's layer machinery: one persistent
@@ -458,15 +459,21 @@ namespace {
 SeqDims upper_ext_dims(const AttDims& d) {
   SeqDims u;
   u.B = d.B; u.T = d.T + 1; u.steps = d.steps + 1; u.N = d.N + d.B; u.E = d.H; u.F = d.F; u.H = d.H; u.V = d.V;
-  u.has_features = 0; u.cell = kCellFactored;
+  u.has_features = 0; u.cell = d.cell;           // the upper layers are layer 0's cell
   return u;
 }
 // after the layer's seq layout: the collapsed chain of the fused upper step, Weff [4H][H] = U_g S_g V_g, US [4H][F],
-// c1 [4F] = S_g bV_g + bS_g, beff [4H] = U_g c1_g + bU_g + bW_g
+// c1 [4F] = S_g bV_g + bS_g, beff [4H] = U_g c1_g + bU_g + bW_g. The LSTM cell has no chain: its Weff is the layout's
+// weight_ih copy (Vcat) and its beff the summed biases (bUW), nothing is added.
 struct UpperExtra { size_t Weff, US, c1, beff, total; };
 UpperExtra upper_extra(const SeqDims& u) {
-  const size_t base = seqd::make_layout(u).total, H = u.H, F = u.F;
+  const seqd::Layout L = seqd::make_layout(u);
+  const size_t base = L.total, H = u.H, F = u.F;
   UpperExtra x;
+  if (u.cell != kCellFactored) {
+    x.Weff = L.Vcat; x.beff = L.bUW; x.US = x.c1 = 0; x.total = base;
+    return x;
+  }
   x.Weff = base;
   x.US = x.Weff + 4 * H * H;
   x.c1 = x.US + 4 * H * F;
@@ -506,7 +513,6 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
                             float* alphas_bt, int* err_flag, hipStream_t s) {
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8 && saved && saved_i && hiddens && (nlayers == 1 || (wu && iu)),
                  "att_seq_forward_stacked: bad argument (layers %d)", nlayers);
-  CAPNET_REQUIRE(nlayers == 1 || d.cell == kCellFactored, "att_seq_forward_stacked: stacked layers are the factored cell's");
   CAPNET_REQUIRE(nlayers == 1 || d.steps + 1 <= kMaxSteps, "att_seq_forward_stacked: %d steps", d.steps);
   for (int l = 0; l < nlayers; ++l)
     CAPNET_REQUIRE(saved[l] && saved_i[l] && hiddens[l], "att_seq_forward_stacked: null buffer of layer %d", l);
@@ -545,7 +551,7 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
                     f.skctr, kSplitKCounters));
     RC(sgemm_splitk(false, true, B, H, C, mean, C, iu[l - 1].init_c_w, C, c.sv + c.L.Cst, H, iu[l - 1].init_c_b, 0, f.skws,
                     kAttSplitKWs, s, f.skctr, kSplitKCounters));
-    if (fused) {
+    if (fused && d.cell == kCellFactored) {
       float* sv = c.sv;
       RC(sgemm(false, false, H, F, F, sv + c.L.Ucat, F, sv + c.L.Scat, F, sv + ux.US, F, nullptr, 0, 4, (long)H * F, (long)F * F,
                (long)H * F, 0, 0, s));
@@ -572,7 +578,7 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
         const size_t pr = offe[t + 1], cr = offe[t];     // this step's rows; the previous step's (or the initial state)
         RC(lstm_upper_step(below + (size_t)r0 * H, c.hid + cr * H, c.sv + c.L.Cst + cr * H, c.sv + ux.Weff, c.sv + c.L.Wcat,
                            c.sv + ux.beff, c.sv + c.L.X + pr * H, c.sv + c.L.G + pr * 4 * H, c.sv + c.L.Cst + pr * H,
-                           c.hid + pr * H, b, H, r0, dropout_p, seed, l, drop, s));
+                           c.hid + pr * H, b, H, r0, dropout_p, seed, l, drop, s, d.cell));
         continue;
       }
       RC(rows_dropout(below, c.sv + c.L.X + (size_t)B * H, r0, r1, H, dropout_p, seed, l, drop, s));

@@ -223,9 +223,10 @@ SeqDims upper_dims(const SeqDims& d0) {
 SeqDims seq_upper_dims(const SeqDims& d0) { return upper_dims(d0); }
 
 // The decoder recurrence of 1 to nlayers cells. One layer is DecoderFactoredLSTM / DecoderRNN (either cell). More are the
-// stacked factored cells (capnet.stacked: SURVEY App. A-1's semantics, PERF-ONLY / PARITY UNPINNED -- the reference ignores
-// num_layers, stylenet/model.py:37): layer 0 is the single-layer cell on [feature, dropout(B(w))...]; layer l > 0 is the
-// same cell on dropout(hidden of layer l - 1) at the same step; the top layer's hidden feeds C on free-running steps.
+// stacked cells of either kind (capnet.stacked, capnet.nic_stacked: SURVEY App. A-1's semantics -- the reference ignores
+// num_layers, stylenet/model.py:37, nic/model.py:35): layer 0 is the single-layer cell on [feature, dropout(B(w))...];
+// layer l > 0 is the same cell on dropout(hidden of layer l - 1) at the same step; the top layer's hidden feeds C on
+// free-running steps. For the LSTM cell this is torch.nn.LSTM(num_layers) under teacher forcing.
 // Runs of teacher-forced steps outside, layers inside: a run's rows go up the stack before the next run starts (a
 // free-running step's input needs the TOP layer's previous hidden state).
 int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
@@ -238,7 +239,6 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
   CAPNET_REQUIRE(tf_mask && captions && emb && scratch && err_flag, "seq_forward: null argument");
   CAPNET_REQUIRE(!d0.has_features || features, "seq_forward: features missing");
   CAPNET_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "seq_forward: dropout p=%f", dropout_p);
-  CAPNET_REQUIRE(nlayers == 1 || d0.cell == kCellFactored, "seq_forward_stacked: stacked layers are the factored cell's");
   const int E = d0.E, N = d0.N, H = d0.H;
   bool any_free = false;
   for (int t = 1; t < d0.steps; ++t) any_free |= !tf_mask[t];
@@ -314,7 +314,7 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
   RC(check_dims(d, batch_sizes));
   CAPNET_REQUIRE(dH && hiddens && saved && saved_i && scratch, "seq_backward: null argument");
   CAPNET_REQUIRE(g.dWcat && g.dbUW && g.dVcat && (layer > 0 ? dH_below != nullptr : g.dEmb != nullptr), "seq_backward: null gradient buffer");
-  CAPNET_REQUIRE(lead == 0 || (layer > 0 && d.steps > 1 && dh0 && dc0 && d.cell == kCellFactored), "seq_backward: leading state step");
+  CAPNET_REQUIRE(lead == 0 || (layer > 0 && d.steps > 1 && dh0 && dc0), "seq_backward: leading state step");
   const Layout L = make_layout(d);
   const int E = d.E, F = d.F, H = d.H, N = d.N;
   const GateOrder go = gate_order(d.cell);
@@ -336,9 +336,10 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
     dA1 = scratch + take((size_t)N * 4 * F);
   }
   float* skws = scratch + take(kSplitKFloats);
-  // the chain's intermediate rows: saved by the forward, or (lead) formed here over all rows
-  float* A1c = lead ? scratch + take((size_t)Nr * 4 * F) : nullptr;
-  float* A2c = lead ? scratch + take((size_t)Nr * 4 * F) : nullptr;
+  // the factored chain's intermediate rows: saved by the forward, or (lead) formed here over all rows
+  const bool chain_rows = lead && d.cell == kCellFactored;
+  float* A1c = chain_rows ? scratch + take((size_t)Nr * 4 * F) : nullptr;
+  float* A2c = chain_rows ? scratch + take((size_t)Nr * 4 * F) : nullptr;
   const float* sv = saved;
   CAPNET_HIP_CHECK(hipMemsetAsync(dh_rec, 0, (size_t)d.B * H * sizeof(float), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(dc, 0, (size_t)d.B * H * sizeof(float), s));
@@ -372,7 +373,7 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
   const float* X = sv + L.X + (size_t)R0 * E;
   const float* A1 = sv + L.A1;
   const float* A2 = sv + L.A2;
-  if (lead) {
+  if (chain_rows) {
     RC(sgemm_splitk(false, true, Nr, 4 * F, E, X, E, sv + L.Vcat, E, A1c, 4 * F, sv + L.bV, 0, skws, kSplitKFloats, s));
     RC(sgemm(false, true, Nr, F, F, A1c, 4 * F, sv + L.Scat, F, A2c, 4 * F, sv + L.bS, 0, 4, F, (long)F * F, F, F, 0, s));
     A1 = A1c;
@@ -403,8 +404,9 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
     RC(sgemm_splitk(false, false, Nr, E, 4 * F, dA1, 4 * F, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
                     kSplitKFloats, s));
   } else {
-    RC(sgemm(true, false, 4 * H, E, N, dPre, 4 * H, sv + L.X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-    RC(sgemm_splitk(false, false, N, E, 4 * H, dPre, 4 * H, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
+    // (the rows the forward computed: all of them unless a leading state step precedes)
+    RC(sgemm(true, false, 4 * H, E, Nr, dPre, 4 * H, X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+    RC(sgemm_splitk(false, false, Nr, E, 4 * H, dPre, 4 * H, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
                     kSplitKFloats, s));
   }
   if (layer > 0) return rows_dropout(dX, dH_below, 0, Nr, E, dropout_p, seed, layer, training && dropout_p > 0.f, s);

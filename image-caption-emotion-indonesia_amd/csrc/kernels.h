@@ -239,16 +239,18 @@ int lstm_step_fused(const float* hprev, const float* Wfrag, float* G, long ldg, 
                     int tanh_out, hipStream_t stream, unsigned long long* stamps = nullptr);
 
 // lstm_upper_step.hip: one step of a stacked layer above the first (<= 16 rows): dropout of the layer below's rows, the
-// collapsed chain and the recurrent product as one product, the gates -- one launch
+// collapsed chain and the recurrent product as one product, the gates -- one launch. cell: 0 = the factored cell (Weff =
+// the collapsed chain), 1 = nn.LSTMCell (Weff = weight_ih, gate blocks i, f, g, o, h = o tanh(c))
 bool lstm_upper_step_supported(int b, int H);
 int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
                     const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
-                    unsigned long long seed, int layer, int use_dropout, hipStream_t stream);
+                    unsigned long long seed, int layer, int use_dropout, hipStream_t stream, int cell = 0);
 
-// lstm_decode_step.hip: one inference step of every layer of a stacked factored LSTM (beam search), one launch per
-// layer, any number of rows: [x | h] . [Weff | W]^T + beff and the gates; layer 0 gathers its embedding rows by token id
+// lstm_decode_step.hip: one inference step of every layer of a stacked LSTM (beam search), one launch per layer, any
+// number of rows: [x | h] . [Weff | W]^T + beff and the gates (blocks i, f, o, c~); layer 0 gathers its embedding rows by
+// token id. cell 0: the factored cell, h = o c; cell 1: nn.LSTMCell, h = o tanh(c)
 bool stacked_decode_supported(int E, int H);
-int stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
                         float* h_top, int* err_flag, hipStream_t stream);
 

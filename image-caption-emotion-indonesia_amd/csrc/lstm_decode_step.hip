@@ -15,6 +15,9 @@
 // TM = 1 at 16 groups per wave, where two tiles' operands and the weights would not fit in 256 VGPRs),
 // and the eight K-partial tiles are summed through LDS by the epilogue, which applies the gates and writes c, h (and the
 // top layer's h once more, densely, for the vocabulary projection). Plain vector loads and stores only.
+// The nn.LSTMCell instance (TANH_OUT, capnet.nic_stacked) takes wcat = [weight_ih, zero columns up to kin | weight_hh]
+// and beff = bias_ih + bias_hh with the host's gate blocks reordered from torch's i, f, g, o to i, f, o, c~ = g: the
+// LSTM cell has no chain to fold, and only the epilogue differs, h = o tanh(c).
 #include "common.h"
 #include "kernels.h"
 
@@ -47,7 +50,7 @@ struct DecodeLayerArgs {
 
 __device__ __forceinline__ float sigm_d(float x) { return 1.f / (1.f + expf(-x)); }
 
-template <int NJ, int TM>  // k groups per wave (at most), 16-row tiles per pass
+template <int NJ, int TM, bool TANH_OUT>  // k groups per wave (at most), 16-row tiles per pass; h = o tanh(c)
 __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a) {
   constexpr int kPass = 16 * TM;
   __shared__ float red[kDecWaves][kPass][17];
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
       }
       const float i = sigm_d(pre[0]), f = sigm_d(pre[1]), og = sigm_d(pre[2]), gt = tanhf(pre[3]);
       const float c = f * cp + i * gt;
-      const float h = og * c;
+      const float h = TANH_OUT ? og * tanhf(c) : og * c;
       a.c_out[(long)erow * a.lds_out + u0 + eu] = c;
       a.h_out[(long)erow * a.lds_out + u0 + eu] = h;
       if (a.h_top) a.h_top[(long)erow * H + u0 + eu] = h;
@@ -151,24 +154,26 @@ bool stacked_decode_supported(int E, int H) {
   return E >= 1 && (H == 64 || H == 128 || H == 256 || H == 512 || H == 1024) && round16(E) + H <= kDecMaxK;
 }
 
-template <int NJ>
+template <int NJ, bool TANH_OUT>
 static void launch_decode(const DecodeLayerArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
+  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT>), dim3(a.H / 4), dim3(64 * kDecWaves), 0,
+                     stream, a);
 }
 
+template <bool TANH_OUT>
 static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
   const int per_wave = ((a.kin + a.H) / 16 + kDecWaves - 1) / kDecWaves;
-  if (per_wave <= 2) launch_decode<2>(a, stream);
-  else if (per_wave <= 4) launch_decode<4>(a, stream);
-  else if (per_wave <= 6) launch_decode<6>(a, stream);
-  else if (per_wave <= 8) launch_decode<8>(a, stream);
-  else if (per_wave <= 12) launch_decode<12>(a, stream);
-  else launch_decode<16>(a, stream);
+  if (per_wave <= 2) launch_decode<2, TANH_OUT>(a, stream);
+  else if (per_wave <= 4) launch_decode<4, TANH_OUT>(a, stream);
+  else if (per_wave <= 6) launch_decode<6, TANH_OUT>(a, stream);
+  else if (per_wave <= 8) launch_decode<8, TANH_OUT>(a, stream);
+  else if (per_wave <= 12) launch_decode<12, TANH_OUT>(a, stream);
+  else launch_decode<16, TANH_OUT>(a, stream);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
 
-int stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
                         float* h_top, int* err_flag, hipStream_t stream) {
   const long lds = 2L * nlayers * H;
@@ -202,7 +207,7 @@ int stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long l
     a.b = beff[l];
     a.rows = rows;
     a.H = H;
-    int rc = launch_decode_layer(a, stream);
+    int rc = cell == kCellLSTM ? launch_decode_layer<true>(a, stream) : launch_decode_layer<false>(a, stream);
     if (rc != kOk) return rc;
   }
   return kOk;

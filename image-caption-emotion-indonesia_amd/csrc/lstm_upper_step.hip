@@ -10,6 +10,9 @@
 // 4 (lane >> 4) + e feeds MFMA step (j, e) in both operands, so the row-major weights need no fragment image -- and all
 // of a wave's loads are in flight before its first MFMA. The eight K-partial tiles are summed through LDS; the epilogue
 // applies the gates and writes what BPTT reads: activated gates, c, h and the dropped-out input row.
+// The nn.LSTMCell instance (CELL = kCellLSTM, capnet.nic_stacked) takes Weff = weight_ih, W = weight_hh and
+// beff = bias_ih + bias_hh as they are, gate blocks i, f, g, o: only the epilogue differs -- gate roles 0, 1, 3, 2,
+// h = o tanh(c), and the activated gates stored where the LSTM cell's BPTT reads them (gate_order(kCellLSTM)).
 #include "common.h"
 #include "dropout_mask.h"
 #include "kernels.h"
@@ -23,7 +26,7 @@ constexpr int kUpperWaves = 8;
 
 __device__ __forceinline__ float sigm_u(float x) { return 1.f / (1.f + expf(-x)); }
 
-template <int NJ>  // 16-wide k groups per wave: H = 64 NJ
+template <int NJ, int CELL>  // 16-wide k groups per wave: H = 64 NJ; kCellFactored or kCellLSTM
 __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
     const float* __restrict__ xin, const float* __restrict__ hprev, const float* __restrict__ cprev,
     const float* __restrict__ Weff, const float* __restrict__ Wrec, const float* __restrict__ beff,
@@ -87,15 +90,16 @@ __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
       for (int w = 0; w < kUpperWaves; ++w) s += red[w][er][g * 4 + eu];
       pre[g] = s;
     }
-    const float i = sigm_u(pre[0]), f = sigm_u(pre[1]), og = sigm_u(pre[2]), gt = tanhf(pre[3]);
+    constexpr int GO = CELL == kCellLSTM ? 3 : 2, GG = CELL == kCellLSTM ? 2 : 3;   // blocks of o and c~ (g)
+    const float i = sigm_u(pre[0]), f = sigm_u(pre[1]), og = sigm_u(pre[GO]), gt = tanhf(pre[GG]);
     const float c = f * cp + i * gt;
     const long gr = (long)er * 4 * H + u0 + eu;
     G[gr] = i;
     G[gr + H] = f;
-    G[gr + 2 * H] = og;
-    G[gr + 3 * H] = gt;
+    G[gr + GO * H] = og;
+    G[gr + GG * H] = gt;
     c_out[(long)er * H + u0 + eu] = c;
-    h_out[(long)er * H + u0 + eu] = og * c;
+    h_out[(long)er * H + u0 + eu] = CELL == kCellLSTM ? og * tanhf(c) : og * c;
   }
 }
 
@@ -106,25 +110,30 @@ bool lstm_upper_step_supported(int b, int H) {
 template <int NJ>
 static void launch_upper(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
                          const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
-                         unsigned long long seed, int layer, int use_dropout, hipStream_t stream) {
-  hipLaunchKernelGGL(lstm_upper_step_kernel<NJ>, dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin, hprev, cprev, Weff,
-                     Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
+                         unsigned long long seed, int layer, int use_dropout, int cell, hipStream_t stream) {
+  if (cell == kCellLSTM)
+    hipLaunchKernelGGL((lstm_upper_step_kernel<NJ, kCellLSTM>), dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin, hprev,
+                       cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
+  else
+    hipLaunchKernelGGL((lstm_upper_step_kernel<NJ, kCellFactored>), dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin,
+                       hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
 }
 
 int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
                     const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
-                    unsigned long long seed, int layer, int use_dropout, hipStream_t stream) {
+                    unsigned long long seed, int layer, int use_dropout, hipStream_t stream, int cell) {
   CAPNET_REQUIRE(xin && hprev && cprev && Weff && Wrec && beff && x_out && G && c_out && h_out,
                  "lstm_upper_step: null argument");
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "lstm_upper_step: unknown cell %d", cell);
   CAPNET_REQUIRE(lstm_upper_step_supported(b, H), "lstm_upper_step: unsupported b=%d H=%d", b, H);
   CAPNET_REQUIRE(aligned16(xin) && aligned16(hprev) && aligned16(Weff) && aligned16(Wrec),
                  "lstm_upper_step: alignment");
   switch (H) {
-    case 64: launch_upper<1>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, stream); break;
-    case 128: launch_upper<2>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, stream); break;
-    case 256: launch_upper<4>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, stream); break;
-    case 512: launch_upper<8>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, stream); break;
-    default: launch_upper<16>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, stream); break;
+    case 64: launch_upper<1>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
+    case 128: launch_upper<2>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
+    case 256: launch_upper<4>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
+    case 512: launch_upper<8>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
+    default: launch_upper<16>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
   }
   CAPNET_LAUNCH_CHECK();
   return kOk;

@@ -71,10 +71,17 @@ class DecoderRNN(nn.Module):
         h_t, c_t = self.lstm(embedded, states)
         return h_t, (h_t, c_t)
 
+    def _upper_layers(self):
+        """(num_layers, the weights of the layers above layer 0) for the sequence call. One layer here: num_layers is
+        ignored, as in the reference (capnet.nic_stacked stacks)."""
+        return 1, []
+
     def forward(self, captions, lengths, features, teacher_forcing_ratio=0.8, tf_mask=None):
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
+        num_layers, upper = self._upper_layers()
         cfg = {
             "cell": ops.CELL_LSTM,
+            "num_layers": num_layers,
             "batch_sizes": batch_sizes,
             "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
             "hidden_size": self.hidden_size,
@@ -84,7 +91,7 @@ class DecoderRNN(nn.Module):
         }
         weights = [self.lstm.weight_ih, self.lstm.bias_ih, self.lstm.weight_hh, self.lstm.bias_hh]
         hiddens = ops.SeqFn.apply(cfg, captions, features, self.embed.weight, self.linear.weight, self.linear.bias,
-                                  *weights)
+                                  *weights, *upper)
         return self.linear(hiddens)
 
     def sample(self, features, start_token, end_token, k=5):

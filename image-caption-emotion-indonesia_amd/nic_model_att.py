@@ -73,13 +73,20 @@ class DecoderRNNAtt(nn.Module):
             out += [m.weight, m.bias]
         return out
 
+    def _upper_layers(self):
+        """(num_layers, the weights of the layers above layer 0) for the sequence call. One layer here: num_layers is
+        ignored, as in the reference (capnet.nic_stacked stacks)."""
+        return 1, []
+
     def forward(self, captions, lengths, features, teacher_forcing_ratio=0.8, tf_mask=None):
         """Returns (outputs [N, V], alphas [B, max(lengths), P]) -- nic/model_att.py:152-202."""
         batch_size = captions.size(0)
         features = features.reshape(batch_size, -1, features.size(-1))
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
+        num_layers, upper = self._upper_layers()
         cfg = {
             "cell": ops.CELL_LSTM,
+            "num_layers": num_layers,
             "batch_sizes": batch_sizes,
             "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
             "hidden_size": self.hidden_size,
@@ -89,7 +96,7 @@ class DecoderRNNAtt(nn.Module):
             "training": self.training,
         }
         hiddens, alphas = ops.AttSeqFn.apply(cfg, captions, features.detach(), self.embed.weight, self.linear.weight,
-                                             self.linear.bias, *self._weights())
+                                             self.linear.bias, *self._weights(), *upper)
         return self.linear(hiddens), alphas
 
     def sample(self, features, start_token, end_token, k=5):

@@ -310,11 +310,14 @@ def stacked_decode_supported(E, H):
     return E >= 1 and H in DECODE_HIDDEN and (E + 15) // 16 * 16 + H <= 2048
 
 
-def stacked_decode_step(state, wcat, beff, x, tokens=None):
-    """One inference step of every layer of a stacked factored LSTM (capnet_stacked_decode_step, one launch per layer).
-    state [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = c); wcat[l] [4H, kin_l + H] = [folded chain | W], beff[l] [4H];
-    x: the embedding table [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E].
+def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED):
+    """One inference step of every layer of a stacked LSTM (capnet_stacked_decode_step, or _cell for the LSTM cell: one
+    launch per layer). state [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = c); wcat[l] [4H, kin_l + H] = [folded chain |
+    W] (factored) or [weight_ih | weight_hh] (LSTM cell), gate blocks i, f, o, c~; beff[l] [4H]; x: the embedding table
+    [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E].
     Returns (top-layer h [rows, H], the new state [rows, 2L, H])."""
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("stacked_decode_step: unknown cell %r" % (cell,))
     _need_cuda(state, x, tokens, *wcat, *beff)
     rows, L2, H = state.shape
     nl = L2 // 2
@@ -334,10 +337,12 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None):
             raise CapnetError("stacked_decode_step: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
     out = torch.empty_like(state)
     top = torch.empty((rows, H), dtype=torch.float32, device=state.device)
-    check(_lib.lib().capnet_stacked_decode_step(nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens),
-                                                ptr(x), ptr_array(wcat), ptr_array(beff), ptr(state), ptr(out), ptr(top),
-                                                ptr(err_flag(state.device)), current_stream()),
-          "capnet_stacked_decode_step")
+    args = (nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens), ptr(x), ptr_array(wcat), ptr_array(beff),
+            ptr(state), ptr(out), ptr(top), ptr(err_flag(state.device)), current_stream())
+    if cell == CELL_FACTORED:
+        check(_lib.lib().capnet_stacked_decode_step(*args), "capnet_stacked_decode_step")
+    else:
+        check(_lib.lib().capnet_stacked_decode_step_cell(cell, *args), "capnet_stacked_decode_step_cell")
     return top, out
 
 def packed_targets(captions, lengths):
@@ -649,12 +654,17 @@ def _gate_grads(cell, F, H, dV, dbV, dS, dbS, dU, dbUW, dW):
 
 def _seq_args(cfg, captions):
     """-> (cell, num_layers) of cfg (defaults: the factored cell, one layer), with the checks both sequence Functions
-    make: the layer count (the LSTM cell takes one), int64 captions, batch_sizes / tf_mask against the batch."""
+    make: the cell, the layer count (either cell stacks 1 to 8), int64 captions, batch_sizes / tf_mask against the
+    batch."""
     cell, nl = cfg.get("cell", CELL_FACTORED), cfg.get("num_layers", 1)
-    if not 1 <= nl <= 8 or (cell != CELL_FACTORED and nl != 1):
-        raise CapnetError("%d layers: the factored cell stacks 1 to 8, the LSTM cell is one layer" % nl)
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("unknown cell %r" % (cell,))
+    if not 1 <= nl <= 8:
+        raise CapnetError("%d layers: a decoder stacks 1 to 8" % nl)
     if captions.dtype != torch.int64:
         raise CapnetError("captions must be int64")
+    if "batch_sizes" not in cfg or "tf_mask" not in cfg:
+        raise CapnetError("decoder: cfg needs batch_sizes and tf_mask")
     bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
     if len(tf) != len(bs) or bs[0] != captions.shape[0]:
         raise CapnetError("decoder: batch_sizes / tf_mask do not match the batch")
@@ -662,10 +672,14 @@ def _seq_args(cfg, captions):
 
 
 def _lstm_slots(ws):
-    """The LSTM cell's (weight_ih, bias_ih, weight_hh, bias_hh) in slots 0 / 4 / 24 / 28 of the factored cell's 32."""
-    slots = [None] * 32
-    slots[0], slots[4], slots[24], slots[28] = ws
-    return slots
+    """The LSTM cell's (weight_ih, bias_ih, weight_hh, bias_hh) of each layer in slots 0 / 4 / 24 / 28 of the factored
+    cell's 32 (4 tensors per layer in, 32 out)."""
+    out = []
+    for l in range(0, len(ws), 4):
+        slots = [None] * 32
+        slots[0], slots[4], slots[24], slots[28] = ws[l:l + 4]
+        out += slots
+    return out
 
 
 def _tf_bytes(tf):
@@ -676,9 +690,9 @@ class SeqFn(torch.autograd.Function):
     """The top layer's hiddens [N, H] (pack_padded_sequence order) of the scheduled-sampling recurrence of 1 to 8 stacked
     layers: ONE C call each way (capnet_seq_forward_stacked / capnet_seq_backward_stacked, csrc/decoder_seq.cpp).
     cfg: batch_sizes, tf_mask, hidden_size, factored_size (factored cell), dropout, seed, training; cell (default
-    CELL_FACTORED), num_layers (default 1; the LSTM cell takes one).
+    CELL_FACTORED), num_layers (default 1, at most 8).
     weights: the factored cell -> 32 tensors per layer, layer 0 first (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4,
-             W w x4, W b x4); the LSTM cell -> (weight_ih, bias_ih, weight_hh, bias_hh)."""
+             W w x4, W b x4); the LSTM cell -> 4 per layer, layer 0 first (weight_ih, bias_ih, weight_hh, bias_hh)."""
 
     @staticmethod
     def forward(ctx, cfg, captions, features, emb, Cw, Cb, *weights):
@@ -686,7 +700,7 @@ class SeqFn(torch.autograd.Function):
         captions = _c(captions)
         cell, nl = _seq_args(cfg, captions)
         ws = [_c(w) for w in weights]
-        if len(ws) != (32 * nl if cell == CELL_FACTORED else 4):
+        if len(ws) != (32 if cell == CELL_FACTORED else 4) * nl:
             raise CapnetError("the factored cell takes 32 weight tensors per layer, the LSTM cell 4")
         if cell != CELL_FACTORED:
             ws = _lstm_slots(ws)
@@ -763,7 +777,8 @@ class AttSeqFn(torch.autograd.Function):
     cfg: SeqFn's keys and attention_size.
     weights: layer 0's 44 tensors (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4, W w x4, W b x4, init_h w,b, init_c w,b,
     encoder_att w,b, decoder_att w,b, full_att w,b, f_beta w,b) -- the LSTM cell's 16: weight_ih, bias_ih, weight_hh,
-    bias_hh, then the same 12 --, then 36 per upper layer: its 32 in the same order, init_h{l} w, b, init_c{l} w, b.
+    bias_hh, then the same 12 --, then 36 per upper layer: its 32 in the same order, init_h{l} w, b, init_c{l} w, b --
+    the LSTM cell's 8: weight_ih, bias_ih, weight_hh, bias_hh, init_h{l} w, b, init_c{l} w, b.
     `features` gets no gradient (frozen trunk)."""
 
     @staticmethod
@@ -772,10 +787,15 @@ class AttSeqFn(torch.autograd.Function):
         captions = _c(captions)
         cell, nl = _seq_args(cfg, captions)
         ws = [_c(w) for w in weights]
-        if len(ws) != (44 + 36 * (nl - 1) if cell == CELL_FACTORED else 16):
-            raise CapnetError("attention decoder: 44 + 36 (num_layers - 1) weight tensors (factored) / 16 (LSTMCell)")
+        if len(ws) != (44 + 36 * (nl - 1) if cell == CELL_FACTORED else 16 + 8 * (nl - 1)):
+            raise CapnetError("attention decoder: 44 + 36 (num_layers - 1) weight tensors (factored) / "
+                              "16 + 8 (num_layers - 1) (LSTMCell)")
         if cell != CELL_FACTORED:
-            ws = _lstm_slots(ws[:4]) + ws[4:]
+            upper = []
+            for l in range(1, nl):
+                u = ws[16 + 8 * (l - 1):16 + 8 * l]
+                upper += _lstm_slots(u[:4]) + u[4:]
+            ws = _lstm_slots(ws[:4]) + ws[4:16] + upper
         emb, Cw, Cb = _c(emb), _c(Cw), _c(Cb)
         dev = emb.device
         bs, tf = cfg["batch_sizes"], cfg["tf_mask"]
@@ -835,8 +855,11 @@ class AttSeqFn(torch.autograd.Function):
         grads = [dV, dbV, dS, dbS, dU, dWz, dbz, dWe, dbe, dwf, dbf, dWih, dbih, dWic, dbic, dEmb]
         upper = []
         for _ in range(1, nl):
-            g = [new(4 * F, H), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H),
-                 new(H, Cf), new(H), new(H, Cf), new(H)]
+            if cell == CELL_FACTORED:
+                g = [new(4 * F, H), new(4 * F), new(4, F, F), new(4 * F), new(4, H, F), new(4 * H), new(4 * H, H)]
+            else:
+                g = [new(4 * H, H), None, None, None, None, new(4 * H), new(4 * H, H)]
+            g += [new(H, Cf), new(H), new(H, Cf), new(H)]
             grads += g
             upper.append(g)
         dh_work = [new(N, H) for _ in range(nl - 1)]
@@ -849,6 +872,6 @@ class AttSeqFn(torch.autograd.Function):
         wg += [dWih, dbih, dWic, dbic, dWe, dbe, dWz[4 * H:4 * H + A], dbz[4 * H:4 * H + A], dwf, dbf,
                dWz[4 * H + A:], dbz[4 * H + A:]]
         for g in upper:
-            wg += _gate_grads(CELL_FACTORED, F, H, *g[:7]) + g[7:]
+            wg += _gate_grads(cell, F, H, *g[:7]) + g[7:]
         # cfg, captions, features, emb, Cw, Cb, *weights
         return (None, None, None, dEmb, None, None) + tuple(wg)

@@ -500,6 +500,15 @@ int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const
                                const float* const* wcat, const float* const* beff, const float* state_in,
                                float* state_out, float* h_top, int* err_flag, capnet_stream_t stream);
 
+/* capnet_stacked_decode_step for either cell: cell 0 = the factored cell (exactly capnet_stacked_decode_step), cell 1 =
+ * nn.LSTMCell (capnet.nic_stacked: StackedDecoderRNN, the upper layers of StackedDecoderRNNAtt), whose h = o tanh(c):
+ * wcat[l] = [weight_ih (zero columns up to kin_l) | weight_hh] and beff[l] = bias_ih + bias_hh, with torch's gate
+ * blocks i, f, g, o reordered to i, f, o, c~ = g on the host. Same shapes, bounds and checks otherwise. */
+int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                    const float* x, const float* const* wcat, const float* const* beff,
+                                    const float* state_in, float* state_out, float* h_top, int* err_flag,
+                                    capnet_stream_t stream);
+
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
  *   capnet_lstm_pack_wfrag image), then the gate
