@@ -95,6 +95,7 @@ SIGNATURES = {
     "capnet_bn1d_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "capnet_seq_saved_floats": (_sz, [_ip]),
     "capnet_seq_saved_ints": (_sz, [_ip]),
+    "capnet_seq_saved_cell_offset": (_sz, [_ip]),
     "capnet_seq_fwd_scratch_floats": (_sz, [_ip]),
     "capnet_seq_bwd_scratch_floats": (_sz, [_ip]),
     "capnet_seq_forward": (_i, [_ip, _ip, C.POINTER(C.c_ubyte), _vp, _vp, _vp, C.POINTER(_vp),
@@ -131,6 +132,11 @@ SIGNATURES = {
                                         _vp]),
     "capnet_stacked_decode_step_cell": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                              _vp, _vp, _vp]),
+    "capnet_vocab_argmax_ws_bytes": (_sz, [_i, _i]),
+    "capnet_vocab_argmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "capnet_lstm_greedy_decode_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "capnet_lstm_greedy_decode": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),
     "capnet_lstm_pack_wfrag": (_i, [_vp, _vp, _i, _i, _vp]),
     "capnet_lstm_step_fused": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -372,6 +372,41 @@ int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const
   return capnet_stacked_decode_step_cell(kCellFactored, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out,
                                          h_top, err_flag, stream);
 }
+size_t capnet_vocab_argmax_ws_bytes(int rows, int V) { return rows >= 1 && V >= 1 ? vocab_argmax_ws_bytes(rows, V) : 0; }
+
+int capnet_vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* workspace,
+                        long long* tokens, capnet_stream_t stream) {
+  CAPNET_REQUIRE(rows >= 1 && V >= 1, "vocab_argmax: rows %d, V %d", rows, V);
+  CAPNET_REQUIRE(vocab_argmax_supported(H), "vocab_argmax: unsupported H=%d", H);
+  CAPNET_REQUIRE(h && w && workspace && tokens, "vocab_argmax: null argument");
+  CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_argmax: h, w and the workspace must be 16-B aligned");
+  return vocab_argmax(h, w, b, rows, H, V, workspace, tokens, nullptr, 0, S(stream));
+}
+
+size_t capnet_lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V) {
+  return nlayers >= 1 && nlayers <= 8 && rows >= 1 && H >= 1 && V >= 1 ? lstm_greedy_decode_ws_bytes(nlayers, rows, H, V) : 0;
+}
+
+int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                              void* workspace, long long* ids, float* state_out, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_greedy_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(rows >= 1 && steps >= 1 && V >= 1, "lstm_greedy_decode: rows %d, steps %d, V %d", rows, steps, V);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_argmax_supported(H), "lstm_greedy_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE((features != nullptr) != (start_tokens != nullptr),
+                 "lstm_greedy_decode: the first input is either features or start_tokens");
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && state_out && err_flag, "lstm_greedy_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && aligned16(state_out),
+                 "lstm_greedy_decode: workspace, Cw and the states must be 16-B aligned");
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_greedy_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_greedy_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return lstm_greedy_decode(nlayers, rows, E, H, V, steps, features, start_tokens, emb, wcat, beff, Cw, Cb, state0, workspace,
+                            ids, state_out, err_flag, S(stream));
+}
+
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream) {
   CAPNET_REQUIRE(gates && c && dh && dc_io && dpre && b >= 0 && H > 0, "lstm_pointwise_bwd: bad argument");
@@ -428,6 +463,7 @@ int capnet_lstm_persist_run(const float* w_img, float* gates, float* cell_states
 
 size_t capnet_seq_saved_floats(const int* dims) { return seq_saved_floats(to_dims(dims)); }
 size_t capnet_seq_saved_ints(const int* dims) { return seq_saved_ints(to_dims(dims)); }
+size_t capnet_seq_saved_cell_offset(const int* dims) { return seq_saved_cell_offset(to_dims(dims)); }
 size_t capnet_seq_fwd_scratch_floats(const int* dims) { return seq_fwd_scratch_floats(to_dims(dims)); }
 size_t capnet_seq_bwd_scratch_floats(const int* dims) { return seq_bwd_scratch_floats(to_dims(dims)); }
 

@@ -125,6 +125,7 @@ using namespace seqd;
 
 size_t seq_saved_floats(const SeqDims& d) { return make_layout(d).total; }
 size_t seq_saved_ints(const SeqDims& d) { return make_layout(d).itotal; }
+size_t seq_saved_cell_offset(const SeqDims& d) { return make_layout(d).Cst; }
 
 size_t seq_fwd_scratch_floats(const SeqDims& d) { return (size_t)d.B * d.V + 64 + kSplitKFloats; }
 
@@ -212,6 +213,13 @@ int recur(LayerCtx& c, const std::vector<int>& off, const int* batch_sizes, int 
   return kOk;
 }
 
+// `training` is a bit set: bit 0 = training (dropout on), kSeqInputDropoutOnly = dropout on layer 0's token embeddings
+// only and none between the layers (torch.nn.LSTM built without dropout=: capnet.seq2seq, seq2seq/model.py:46-49).
+// The attention stack (decoder_att_seq.cpp) calls seq_backward_upper with 0 / 1 and is unchanged.
+static bool between_layers(int training, float dropout_p) {
+  return (training & 1) && !(training & kSeqInputDropoutOnly) && dropout_p > 0.f;
+}
+
 SeqDims upper_dims(const SeqDims& d0) {
   SeqDims d = d0;
   d.E = d0.H;               // a layer above the first reads the hidden state of the layer below
@@ -293,8 +301,9 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
     for (int l = 0; l < nlayers; ++l) {
       LayerCtx& c = lay[l];
       if (l > 0) {
-        // X_l = dropout(hidden of the layer below) for the run's rows, then its input chain
-        RC(rows_dropout(lay[l - 1].hid, c.sv + c.L.X, r0, r1, H, dropout_p, seed, l, training && dropout_p > 0.f, s));
+        // X_l = dropout(hidden of the layer below) for the run's rows (kSeqInputDropoutOnly: a plain copy), then its
+        // input chain
+        RC(rows_dropout(lay[l - 1].hid, c.sv + c.L.X, r0, r1, H, dropout_p, seed, l, between_layers(training, dropout_p), s));
         RC(input_chain(c.d, c.L, c.sv, r0, r1, skws, kSplitKWs, s, skctr));
       }
       RC(recur(c, off, batch_sizes, t, t1, skws, skctr, err_flag, s));
@@ -409,7 +418,7 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
     RC(sgemm_splitk(false, false, Nr, E, 4 * H, dPre, 4 * H, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
                     kSplitKFloats, s));
   }
-  if (layer > 0) return rows_dropout(dX, dH_below, 0, Nr, E, dropout_p, seed, layer, training && dropout_p > 0.f, s);
+  if (layer > 0) return rows_dropout(dX, dH_below, 0, Nr, E, dropout_p, seed, layer, between_layers(training, dropout_p), s);
   CAPNET_HIP_CHECK(hipMemsetAsync(g.dEmb, 0, (size_t)d.V * E * sizeof(float), s));
   if (g.dFeat) CAPNET_HIP_CHECK(hipMemsetAsync(g.dFeat, 0, (size_t)d.B * E * sizeof(float), s));
   // (the split-K slab area is free by now: the scatter's two integer tables over the vocabulary go there)

@@ -254,6 +254,18 @@ int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, co
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
                         float* h_top, int* err_flag, hipStream_t stream);
 
+// vocab_argmax.hip: tok[r] = first argmax_v (h[r] . W[v] + b[v]) in one launch, no logits in memory (ws: vocab_argmax_ws_bytes,
+// its first 16 bytes zero before the first use); and capnet.seq2seq's greedy `sample` as one chain of launches
+bool vocab_argmax_supported(int H);
+size_t vocab_argmax_ws_bytes(int rows, int V);
+int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* ws, long long* tok,
+                 long long* ids, long ld_ids, hipStream_t stream);
+size_t lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V);
+int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
+                       const long long* start_tokens, const float* emb, const float* const* wcat,
+                       const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,
+                       long long* ids, float* state_out, int* err_flag, hipStream_t s);
+
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
 size_t lstm_persist_w_floats();
@@ -333,6 +345,8 @@ int bn1d_bwd(const float* dy, const float* x, int B, int C, const float* gamma,
 // decoder_seq.cpp
 constexpr int kCellFactored = 0;  // DecoderFactoredLSTM (stylenet/model.py)
 constexpr int kCellLSTM = 1;      // nn.LSTMCell (nic/model.py)
+constexpr int kSeqInputDropoutOnly = 2;   // bit of seq_forward_stacked's / seq_backward_stacked's `training`: no dropout
+                                          // between the layers (torch.nn.LSTM without dropout=), embeddings only
 struct SeqDims {
   int B, T, steps, N, E, F, H, V, has_features, cell;
 };
@@ -355,6 +369,7 @@ size_t seq_saved_floats(const SeqDims& d);
 size_t seq_saved_ints(const SeqDims& d);
 size_t seq_fwd_scratch_floats(const SeqDims& d);
 size_t seq_bwd_scratch_floats(const SeqDims& d);
+size_t seq_saved_cell_offset(const SeqDims& d);   // floats from the start of a layer's `saved` to its cell states [N][H]
 SeqDims seq_upper_dims(const SeqDims& d0);
 int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
                         const long long* captions, const float* features, const float* emb, const SeqWeights* w,

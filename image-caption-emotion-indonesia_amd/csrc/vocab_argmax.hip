@@ -1,0 +1,212 @@
+// Greedy decoding of capnet.seq2seq (seq2seq/model.py:100-122, 193-217): the vocabulary projection and its argmax in ONE
+// launch, without the logits ever reaching memory, and the whole `sample` loop as one C call.
+//   tok[r] = first argmax_v (h[r] . W[v] + b[v])        h [rows][H], W [V][H] (nn.Linear), b [V]
+//
+// Mapping (the arrangement of lstm_decode_step.hip): a workgroup owns 32 vocabulary entries = two N tiles of
+// v_mfma_f32_16x16x4_f32 and ALL rows. Its 8 waves are 2 tiles x 4 contiguous quarters of K = H; a lane loads its column's
+// weights for its quarter once (NJ f32x4 registers: the projection crosses the memory system once per launch) and keeps
+// them while the workgroup walks the rows 16 TM at a time. The four K-partial tiles are summed through LDS in a fixed order,
+// the bias is added, and 32 threads per row reduce (value, index) with a strict comparison, ties to the lower index.
+// Cross-workgroup: each workgroup writes one packed (value, index) word per row; the workgroup that arrives LAST at the one
+// counter (gemm_rows16_kernel's hand-off in gemm_f32.hip, cell by cell: every partial an 8-byte agent-scope store, every
+// storing wave drained, a workgroup barrier, one lane's agent-scope atomic add, the partials read back with agent-scope
+// loads) reduces them per row -- the winner does not depend on who was last, the comparison is a total order on
+// (value, index) -- writes the int64 token where the next step's layer-0 launch gathers its embedding row (and into the
+// ids matrix), and puts the counter back to zero. No workgroup waits on another. Plain vector loads and stores only.
+// NaN and -inf logits are never picked (strict `>` against -inf, as argmax_rows_kernel); a row with nothing to pick
+// yields 0.
+#include "common.h"
+#include "kernels.h"
+
+namespace capnet {
+
+typedef float f32x4a __attribute__((ext_vector_type(4)));
+
+constexpr int kVaWaves = 8;
+constexpr int kVaCols = 32;          // vocabulary entries per workgroup
+constexpr int kVaNone = 0x7fffffff;
+
+struct VocabArgmaxArgs {
+  const float* h;            // [rows][H]
+  const float* w;            // [V][H]
+  const float* b;            // [V] or null
+  unsigned long long* part;  // [workgroups][rows]: (value bits << 32) | index
+  int* counter;              // zero before the first use; zero again when the launch ends
+  long long* tok;            // optional [rows]
+  long long* ids;            // optional: ids[r * ld_ids]
+  long ld_ids;
+  int rows, H, V;
+};
+
+__device__ __forceinline__ bool va_better(float v, int i, float best, int bi) {
+  return v > best || (v == best && i < bi);
+}
+
+template <int NJ, int TM>
+__global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
+  constexpr int kPass = 16 * TM;
+  __shared__ float red[kVaWaves][kPass][17];
+  __shared__ int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lq = lane >> 4;
+  const int tile = wave >> 2, ks = wave & 3;
+  const int H = a.H, c0 = blockIdx.x * kVaCols;
+  const int g0 = ks * NJ;                                   // this wave's k groups [g0, g0 + NJ): H = 64 NJ
+  int wcol = c0 + 16 * tile + li;
+  wcol = wcol < a.V ? wcol : a.V - 1;                       // entries beyond V: a clamped copy, masked in the epilogue
+  const float* wrow = a.w + (long)wcol * H + 16 * g0 + 4 * lq;
+  f32x4a wv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) wv[j] = *reinterpret_cast<const f32x4a*>(wrow + 16 * j);
+  // epilogue thread: (row er of a 16-row tile, entry ec of the workgroup's 32)
+  const int er = tid >> 5, ec = tid & 31;
+  const int ecol = c0 + ec;
+  const float bias = (a.b && ecol < a.V) ? a.b[ecol] : 0.f;
+  unsigned long long* part = a.part + (long)blockIdx.x * a.rows;
+  for (int r0 = 0; r0 < a.rows; r0 += kPass) {
+    f32x4a acc[TM];
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      acc[m] = f32x4a{0.f, 0.f, 0.f, 0.f};
+      int row = r0 + 16 * m + li;
+      row = row < a.rows ? row : a.rows - 1;                // rows beyond the last: a clamped copy, never stored
+      const float* hrow = a.h + (long)row * H + 16 * g0 + 4 * lq;
+      f32x4a av[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) av[j] = *reinterpret_cast<const f32x4a*>(hrow + 16 * j);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j][e], wv[j][e], acc[m], 0, 0, 0);
+    }
+    // D layout of a 16x16 tile: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int m = 0; m < TM; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][16 * m + 4 * lq + r][li] = acc[m][r];
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      const int pr = 16 * m + er, row = r0 + pr;
+      const int t4 = (ec >> 4) * 4, cc = ec & 15;
+      const float v = bias + red[t4][pr][cc] + red[t4 + 1][pr][cc] + red[t4 + 2][pr][cc] + red[t4 + 3][pr][cc];
+      float best = -INFINITY;
+      int bi = kVaNone;
+      if (ecol < a.V && v > best) { best = v; bi = ecol; }
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) {                    // the row's 32 threads are one half of a wave
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (va_better(ov, oi, best, bi)) { best = ov; bi = oi; }
+      }
+      if (ec == 0 && row < a.rows)
+        __hip_atomic_store(part + row, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bi, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();   // red is rewritten by the next pass
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0)
+    s_last = __hip_atomic_fetch_add(a.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!s_last) return;
+  // the last arriver: a wave per row, the workgroups' partials across its lanes
+  const int nwg = gridDim.x;
+  for (int row = wave; row < a.rows; row += kVaWaves) {
+    float best = -INFINITY;
+    int bi = kVaNone;
+    for (int p0 = 0; p0 < nwg; p0 += 64 * 4) {
+      unsigned long long u[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int p = min(p0 + 64 * q + lane, nwg - 1);
+        u[q] = __hip_atomic_load(a.part + (long)p * a.rows + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float v = __uint_as_float((unsigned)(u[q] >> 32));
+        const int i = (int)(unsigned)u[q];
+        if (p0 + 64 * q + lane < nwg && va_better(v, i, best, bi)) { best = v; bi = i; }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o);
+      const int oi = __shfl_xor(bi, o);
+      if (va_better(ov, oi, best, bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) {
+      const long long t = bi == kVaNone ? 0 : bi;
+      if (a.tok) a.tok[row] = t;
+      if (a.ids) a.ids[(long)row * a.ld_ids] = t;
+    }
+  }
+  if (tid == 0) __hip_atomic_store(a.counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+static int va_workgroups(int V) { return (V + kVaCols - 1) / kVaCols; }
+
+bool vocab_argmax_supported(int H) { return H == 64 || H == 128 || H == 256 || H == 512 || H == 1024; }
+
+// workspace: 16 bytes whose first int is the counter, then one 8-byte partial per workgroup and row
+size_t vocab_argmax_ws_bytes(int rows, int V) { return 16 + (size_t)va_workgroups(V) * rows * 8; }
+
+int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* ws, long long* tok,
+                 long long* ids, long ld_ids, hipStream_t stream) {
+  VocabArgmaxArgs a;
+  a.h = h; a.w = w; a.b = b;
+  a.counter = reinterpret_cast<int*>(ws);
+  a.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);
+  a.tok = tok; a.ids = ids; a.ld_ids = ld_ids;
+  a.rows = rows; a.H = H; a.V = V;
+  const dim3 grid(va_workgroups(V)), block(64 * kVaWaves);
+  switch (H) {
+    case 64: hipLaunchKernelGGL((vocab_argmax_kernel<1, 2>), grid, block, 0, stream, a); break;
+    case 128: hipLaunchKernelGGL((vocab_argmax_kernel<2, 2>), grid, block, 0, stream, a); break;
+    case 256: hipLaunchKernelGGL((vocab_argmax_kernel<4, 2>), grid, block, 0, stream, a); break;
+    case 512: hipLaunchKernelGGL((vocab_argmax_kernel<8, 2>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((vocab_argmax_kernel<16, 1>), grid, block, 0, stream, a); break;
+  }
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// ---- the whole greedy `sample`: steps x (one decode-step launch per layer + one vocab_argmax launch) ------------------
+// ws: [state A | state B] ([rows][2L][H] each) | h_top [rows][H] | tok int64 [rows] | vocab_argmax's workspace
+static size_t gd_align(size_t n) { return (n + 15) / 16 * 16; }
+
+size_t lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V) {
+  const size_t st = gd_align((size_t)rows * 2 * nlayers * H * sizeof(float));
+  return 2 * st + gd_align((size_t)rows * H * sizeof(float)) + gd_align((size_t)rows * 8) + vocab_argmax_ws_bytes(rows, V);
+}
+
+int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
+                       const long long* start_tokens, const float* emb, const float* const* wcat,
+                       const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,
+                       long long* ids, float* state_out, int* err_flag, hipStream_t s) {
+  const size_t st_bytes = (size_t)rows * 2 * nlayers * H * sizeof(float), st = gd_align(st_bytes);
+  char* p = reinterpret_cast<char*>(ws);
+  float* state[2] = {reinterpret_cast<float*>(p), reinterpret_cast<float*>(p + st)};
+  p += 2 * st;
+  float* h_top = reinterpret_cast<float*>(p);
+  p += gd_align((size_t)rows * H * sizeof(float));
+  long long* tok = reinterpret_cast<long long*>(p);
+  p += gd_align((size_t)rows * 8);
+  void* va_ws = p;
+  if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
+  else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
+  if (start_tokens) CAPNET_HIP_CHECK(hipMemcpyAsync(tok, start_tokens, (size_t)rows * 8, hipMemcpyDeviceToDevice, s));
+  CAPNET_HIP_CHECK(hipMemsetAsync(va_ws, 0, 16, s));
+  for (int t = 0; t < steps; ++t) {
+    const bool feat = t == 0 && features;
+    int rc = stacked_decode_step(kCellLSTM, nlayers, rows, E, H, V, feat ? nullptr : tok, feat ? features : emb, wcat, beff,
+                                 state[t & 1], state[(t + 1) & 1], h_top, err_flag, s);
+    if (rc == kOk) rc = vocab_argmax(h_top, Cw, Cb, rows, H, V, va_ws, tok, ids + t, steps, s);
+    if (rc != kOk) return rc;
+  }
+  CAPNET_HIP_CHECK(hipMemcpyAsync(state_out, state[steps & 1], st_bytes, hipMemcpyDeviceToDevice, s));
+  return kOk;
+}
+
+}  // namespace capnet

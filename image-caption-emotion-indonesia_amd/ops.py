@@ -345,6 +345,74 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED):
         check(_lib.lib().capnet_stacked_decode_step_cell(cell, *args), "capnet_stacked_decode_step_cell")
     return top, out
 
+
+def vocab_argmax_workspace(rows, V, device):
+    """A zeroed workspace of capnet_vocab_argmax for `rows` rows (back-to-back calls on one stream may share it)."""
+    n = _lib.lib().capnet_vocab_argmax_ws_bytes(int(rows), int(V))
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vocab_argmax(h, w, b=None, workspace=None):
+    """tokens [rows] int64 = the first argmax over v of h[r] . w[v] + b[v] (capnet_vocab_argmax: the projection and the
+    argmax in one launch, no logits in memory). h [rows, H], w [V, H], b [V]; H in DECODE_HIDDEN."""
+    _need_cuda(h, w, b)
+    h, w = _c(h.detach()), _c(w.detach())
+    b = None if b is None else _c(b.detach())
+    rows, H = h.shape
+    V = w.shape[0]
+    if w.shape[1] != H or H not in DECODE_HIDDEN or rows < 1 or (b is not None and b.numel() != V):
+        raise CapnetError("vocab_argmax: h [rows, H], w [V, H], b [V] with H in %r" % (DECODE_HIDDEN,))
+    if workspace is None:
+        workspace = vocab_argmax_workspace(rows, V, h.device)
+    if workspace.numel() * workspace.element_size() < _lib.lib().capnet_vocab_argmax_ws_bytes(rows, V):
+        raise CapnetError("vocab_argmax: workspace too small")
+    out = torch.empty(rows, dtype=torch.int64, device=h.device)
+    check(_lib.lib().capnet_vocab_argmax(ptr(h), ptr(w), ptr(b), rows, H, V, ptr(workspace), ptr(out), current_stream()),
+          "capnet_vocab_argmax")
+    return out
+
+
+def lstm_greedy_decode(steps, wcat, beff, emb, Cw, Cb, features=None, start_tokens=None, state=None):
+    """`steps` greedy decode steps of a stacked nn.LSTM + nn.Linear in ONE C call (capnet_lstm_greedy_decode): tokens and
+    logits never leave the device. wcat / beff: capnet.nic_stacked._pack_cell of every layer; emb [V, E]; Cw [V, H], Cb [V].
+    The first input is `features` [rows, E] or emb[start_tokens] (int64 [rows]); state: [rows, 2L, H] or None for zeros.
+    Returns (ids [rows, steps] int64, the final state [rows, 2L, H])."""
+    if (features is None) == (start_tokens is None):
+        raise CapnetError("lstm_greedy_decode: either features or start_tokens")
+    _need_cuda(emb, Cw, Cb, features, start_tokens, state, *wcat, *beff)
+    emb, Cw, Cb = _c(emb.detach()), _c(Cw.detach()), _c(Cb.detach())
+    V, E = emb.shape
+    H, nl = Cw.shape[1], len(wcat)
+    rows = (features if features is not None else start_tokens).shape[0]
+    if features is not None:
+        features = _c(features.detach())
+        if tuple(features.shape) != (rows, E):
+            raise CapnetError("lstm_greedy_decode: features must be [rows, embed_size]")
+    else:
+        start_tokens = _c(start_tokens)
+        if start_tokens.dtype != torch.int64 or start_tokens.dim() != 1:
+            raise CapnetError("lstm_greedy_decode: start_tokens must be int64 [rows]")
+    if not stacked_decode_supported(E, H) or not 1 <= nl <= 8 or len(beff) != nl or tuple(Cw.shape) != (V, H):
+        raise CapnetError("lstm_greedy_decode: unsupported shape (E=%d, H=%d, %d layers)" % (E, H, nl))
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = (E + 15) // 16 * 16 if l == 0 else H
+        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
+            raise CapnetError("lstm_greedy_decode: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    dev = emb.device
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (rows, 2 * nl, H):
+            raise CapnetError("lstm_greedy_decode: state must be [rows, 2L, H]")
+    L = _lib.lib()
+    ws = torch.empty((L.capnet_lstm_greedy_decode_ws_bytes(nl, rows, H, V) + 7) // 8, dtype=torch.int64, device=dev)
+    ids = torch.empty((rows, int(steps)), dtype=torch.int64, device=dev)
+    out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
+    check(L.capnet_lstm_greedy_decode(nl, rows, E, H, V, int(steps), ptr(features), ptr(start_tokens), ptr(emb),
+                                      ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(ids),
+                                      ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_lstm_greedy_decode")
+    return ids, out
+
+
 def packed_targets(captions, lengths):
     """pack_padded_sequence(captions, lengths, batch_first=True)[0] for int64 captions."""
     _need_cuda(captions)
@@ -686,11 +754,19 @@ def _tf_bytes(tf):
     return (C.c_ubyte * len(tf))(*[1 if x else 0 for x in tf])
 
 
+def _seq_training(cfg):
+    """capnet_seq_forward_stacked's `training` bit set: 1 = training; + 2 (cfg["input_dropout_only"]) = dropout on the
+    token embeddings only, none between the layers (torch.nn.LSTM without dropout=, capnet.seq2seq)."""
+    return int(bool(cfg["training"])) | (2 if cfg.get("input_dropout_only") else 0)
+
+
 class SeqFn(torch.autograd.Function):
     """The top layer's hiddens [N, H] (pack_padded_sequence order) of the scheduled-sampling recurrence of 1 to 8 stacked
     layers: ONE C call each way (capnet_seq_forward_stacked / capnet_seq_backward_stacked, csrc/decoder_seq.cpp).
     cfg: batch_sizes, tf_mask, hidden_size, factored_size (factored cell), dropout, seed, training; cell (default
-    CELL_FACTORED), num_layers (default 1, at most 8).
+    CELL_FACTORED), num_layers (default 1, at most 8); input_dropout_only (default False: the same p between the layers).
+    With cfg["want_final_state"], forward leaves cfg["final_state"] = (h, c), each [num_layers, b_last, H]: the state after
+    the last step of the rows alive there (copies without a gradient path).
     weights: the factored cell -> 32 tensors per layer, layer 0 first (V w x4, V b x4, S w x4, S b x4, U w x4, U b x4,
              W w x4, W b x4); the LSTM cell -> 4 per layer, layer 0 first (weight_ih, bias_ih, weight_hh, bias_hh)."""
 
@@ -724,9 +800,13 @@ class SeqFn(torch.autograd.Function):
         hid = [torch.empty((N, H), dtype=torch.float32, device=dev) for _ in range(nl)]
         check(L.capnet_seq_forward_stacked(cd[0], nl, int_array(bs), _tf_bytes(tf), ptr(captions), ptr(features),
                                            ptr(emb), ptr_array(ws), ptr(Cw), ptr(Cb), float(cfg["dropout"]),
-                                           int(cfg["seed"]), int(cfg["training"]), ptr_array(saved), ptr_array(saved_i),
+                                           int(cfg["seed"]), _seq_training(cfg), ptr_array(saved), ptr_array(saved_i),
                                            ptr(scratch), ptr_array(hid), ptr(err_flag(dev)), current_stream()),
               "capnet_seq_forward_stacked")
+        if cfg.get("want_final_state"):
+            last = N - bs[-1]
+            cst = [saved[l][L.capnet_seq_saved_cell_offset(cd[l]):][:N * H].view(N, H) for l in range(nl)]
+            cfg["final_state"] = (torch.stack([h[last:] for h in hid]), torch.stack([c[last:] for c in cst]))
         ctx.cfg, ctx.dims, ctx.has_features = cfg, dims, features is not None
         ctx.save_for_backward(*(saved + saved_i + hid))
         return hid[-1]
@@ -762,7 +842,7 @@ class SeqFn(torch.autograd.Function):
         check(L.capnet_seq_backward_stacked(cd[0], nl, int_array(cfg["batch_sizes"]), ptr(_c(d_hiddens)), ptr_array(hid),
                                             ptr_array(saved), ptr_array(saved_i), ptr(scratch),
                                             ptr_array(dh_work) if dh_work else None, ptr_array(grads),
-                                            float(cfg["dropout"]), int(cfg["seed"]), int(cfg["training"]), current_stream()),
+                                            float(cfg["dropout"]), int(cfg["seed"]), _seq_training(cfg), current_stream()),
               "capnet_seq_backward_stacked")
         wg = []
         for g in per_layer:

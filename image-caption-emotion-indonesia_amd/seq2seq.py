@@ -1,0 +1,260 @@
+"""Seq2Seq caption-to-styled-caption model on the MI355X kernels: EncoderRNN, DecoderRNN, Seq2Seq.
+
+Mirrors seq2seq/model.py of the reference (factual caption in, happy / sad / angry caption out): constructor and method
+signatures, attribute names and state_dict keys in the reference's order. This is the one package of the reference whose
+`num_layers` is honoured (nn.LSTM(embed, hidden, num_layers, batch_first=True), seq2seq/model.py:46-49, 140-143), so the
+stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with the LSTM cell) is REFERENCE-PINNED here
+(tests/golden/seq2seq_tiny.npz), unlike capnet.stacked / capnet.nic_stacked.
+
+  * `lstm` is a parameter container with nn.LSTM's names and shapes (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0,
+    ..._l1, ...); torch's LSTM kernel is never called. Initial values follow torch's constructor defaults (Embedding
+    N(0, 1); LSTM and Linear U(+-1/sqrt(fan))), drawn in the reference's order; the reference has no reset_parameters /
+    init_weights in this package.
+  * Training: forward -> ops.SeqFn (LSTM cell, num_layers layers; `features` for the encoder, None for the decoders), one C
+    call each way. Dropout acts on the token embeddings ONLY: nn.LSTM is built without dropout=, so nothing is dropped
+    between the layers (cfg["input_dropout_only"]).
+  * Decoding: sample() is greedy over a whole batch for exactly max_seq_length steps, no end token, no dropout
+    (seq2seq/model.py:100-122, 193-217). One capnet_lstm_greedy_decode call: per step one launch per layer of
+    csrc/lstm_decode_step.hip's LSTM-cell instance and one launch of csrc/vocab_argmax.hip, tokens and logits never
+    leaving the device. CAPNET_NO_FUSED_GREEDY=1 (read at every sample call) takes the composed loop
+    (ops.stacked_decode_step -> linear -> ops.argmax_rows -> next tokens), which also serves the shapes the decode kernel
+    does not take (ops.stacked_decode_supported) and batches of more than FUSED_GREEDY_MAX_ROWS = 16 rows: measured
+    (profiles/README.md), the one call is 1.3x to 2.3x faster at 1 and 12 rows and no faster at 64 (slower at 2 and 3
+    layers), so a batch beyond one 16-row tile goes to the composed loop; 17 to 63 rows were not measured.
+"""
+import os
+import random
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import CapnetError
+from .model import Dropout, Embedding, Linear, _dropout_seed
+from .nic_model import LSTMCell
+from .nic_stacked import _pack_cell, _stepper
+
+device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # seq2seq/model.py:8
+
+FUSED_GREEDY_OFF = "CAPNET_NO_FUSED_GREEDY"
+FUSED_GREEDY_MAX_ROWS = 16
+_EMOTIONS = ("happy", "sad", "angry")
+
+
+class LSTM(nn.Module):
+    """nn.LSTM(input_size, hidden_size, num_layers) parameter container: weight_ih_l{k} [4H, in], weight_hh_l{k} [4H, H],
+    bias_ih_l{k}, bias_hh_l{k} [4H] per layer, gate order i, f, g, o, every tensor U(-1/sqrt(H), 1/sqrt(H))."""
+
+    def __init__(self, input_size, hidden_size, num_layers):
+        super().__init__()
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        k = 1.0 / hidden_size ** 0.5
+        for l in range(num_layers):
+            n_in = input_size if l == 0 else hidden_size
+            for name, shape in (("weight_ih", (4 * hidden_size, n_in)), ("weight_hh", (4 * hidden_size, hidden_size)),
+                                ("bias_ih", (4 * hidden_size,)), ("bias_hh", (4 * hidden_size,))):
+                setattr(self, "%s_l%d" % (name, l), nn.Parameter(torch.empty(shape).uniform_(-k, k)))
+
+    def layer(self, l):
+        return _Layer(self, l)
+
+
+class _Layer:
+    """Layer l of an LSTM container under nn.LSTMCell's names (what capnet.nic_stacked's step and packing read)."""
+
+    def __init__(self, lstm, l):
+        self.input_size = lstm.input_size if l == 0 else lstm.hidden_size
+        self.hidden_size = lstm.hidden_size
+        for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+            setattr(self, name, getattr(lstm, "%s_l%d" % (name, l)))
+
+    def __call__(self, x, states):
+        return LSTMCell.forward(self, x, states)
+
+
+def _to_rows(h, c):
+    """(h, c) [L, rows, H] -> the decode kernels' [rows, 2L, H] (slot 2l = h of layer l, 2l + 1 = c)."""
+    L, rows, H = h.shape
+    return torch.stack([h, c], 1).permute(2, 0, 1, 3).reshape(rows, 2 * L, H).contiguous()
+
+
+def _from_rows(state):
+    rows, L2, H = state.shape
+    hc = state.view(rows, L2 // 2, 2, H).permute(2, 1, 0, 3)
+    return hc[0].contiguous(), hc[1].contiguous()
+
+
+class _RNN(nn.Module):
+    """What EncoderRNN and DecoderRNN share: the modules in the reference's order, one step, the sequence call, greedy."""
+
+    def __init__(self, embed_size, hidden_size, vocab_size, num_layers, dropout=0.22, max_seq_length=40):
+        super().__init__()
+        if not 1 <= num_layers <= 8:
+            raise CapnetError("num_layers must be 1 to 8 (the sequence call's limit)")
+        self.max_seq_length = max_seq_length
+        self.num_layers = num_layers
+        self.hidden_size = hidden_size
+        self.embed_size = embed_size
+        self.vocab_size = vocab_size
+        self.dropout = Dropout(dropout)
+        self.embed = Embedding(vocab_size, embed_size)
+        self.lstm = LSTM(embed_size, hidden_size, num_layers)
+        self.linear = Linear(hidden_size, vocab_size)
+
+    def _layers(self):
+        return [self.lstm.layer(l) for l in range(self.num_layers)]
+
+    def _zeros(self, rows):
+        return torch.zeros((rows, 2 * self.num_layers, self.hidden_size), dtype=torch.float32,
+                           device=self.embed.weight.device)
+
+    def forward_step(self, embedded, states):
+        """One step at inference (no dropout) on `embedded` [b, E] or [b, 1, E]; states (h, c), each [num_layers, b, H]
+        or None for zeros. Returns (the top layer's hiddens [b, H], (h, c))."""
+        with torch.no_grad():
+            if embedded.dim() == 3:
+                embedded = embedded.squeeze(1)
+            h, c = states
+            b = embedded.size(0)
+            zeros = torch.zeros((self.num_layers, b, self.hidden_size), dtype=torch.float32, device=embedded.device)
+            state = _to_rows(zeros if h is None else h.detach(), zeros if c is None else c.detach())
+            top, state = _stepper(self._layers(), self.embed_size, self.hidden_size)(embedded.detach().contiguous(), None,
+                                                                                      state)
+            return top, _from_rows(state)
+
+    def _sequence(self, features, tokens, lengths, teacher_forcing_ratio):
+        """(packed logits [N, V], (h, c)): one random.random() draw per step, then ops.SeqFn."""
+        batch_sizes = ops.batch_sizes_from_lengths(lengths)
+        cfg = {
+            "cell": ops.CELL_LSTM,
+            "num_layers": self.num_layers,
+            "batch_sizes": batch_sizes,
+            "tf_mask": [random.random() < teacher_forcing_ratio for _ in batch_sizes],
+            "hidden_size": self.hidden_size,
+            "dropout": self.dropout.p if self.training else 0.0,
+            "seed": _dropout_seed(self.training, self.dropout.p),
+            "training": self.training,
+            "input_dropout_only": True,
+            "want_final_state": True,
+        }
+        weights = []
+        for c in self._layers():
+            weights += [c.weight_ih, c.bias_ih, c.weight_hh, c.bias_hh]
+        hiddens = ops.SeqFn.apply(cfg, tokens, features, self.embed.weight, self.linear.weight, self.linear.bias, *weights)
+        return self.linear(hiddens), cfg["final_state"]
+
+    def _advance_streams(self, lengths):
+        """Consume what _sequence consumes of `random` and of torch's generator, without its arithmetic."""
+        for _ in ops.batch_sizes_from_lengths(lengths):
+            random.random()
+        _dropout_seed(self.training, self.dropout.p)
+
+    def _greedy(self, features, start_tokens, state):
+        """max_seq_length greedy steps from `features` [rows, E] or emb[start_tokens]; state [rows, 2L, H].
+        Returns (ids [rows, max_seq_length] int64, state')."""
+        E, H, steps = self.embed_size, self.hidden_size, self.max_seq_length
+        emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
+        layers = self._layers()
+        with torch.no_grad():
+            if (os.environ.get(FUSED_GREEDY_OFF, "")[:1] != "1" and ops.stacked_decode_supported(E, H)
+                    and state.shape[0] <= FUSED_GREEDY_MAX_ROWS):
+                packed = [_pack_cell(c, (E + 15) // 16 * 16 if l == 0 else H) for l, c in enumerate(layers)]
+                return ops.lstm_greedy_decode(steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
+                                              features=features, start_tokens=start_tokens, state=state)
+            step = _stepper(layers, E, H)
+            ids, tokens = [], start_tokens
+            for t in range(steps):
+                if t == 0 and features is not None:
+                    top, state = step(features.detach().contiguous(), None, state)
+                else:
+                    top, state = step(emb, tokens, state)
+                tokens = ops.argmax_rows(ops.linear(top, Cw, Cb)).long()
+                ids.append(tokens)
+            return torch.stack(ids, 1), state
+
+
+class EncoderRNN(_RNN):
+    """seq2seq/model.py:30-122."""
+
+    def forward(self, features, src_tokens, lengths, teacher_forcing_ratio=0.5):
+        """Inputs [features, dropout(embed(w_0)), ...] packed by `lengths`; every layer starts at zero; a free-running
+        step feeds embed(argmax(linear(h_top))) without dropout, a free-running step 0 embed(src_tokens[:, 0]).
+        Returns (outputs [N, V], (h, c)) with h, c [num_layers, b_last, H]: the state after the last step of the rows
+        still alive there. The returned states are copies with NO gradient path (requires_grad=False): the reference
+        never differentiates through them."""
+        return self._sequence(features, src_tokens, lengths, teacher_forcing_ratio)
+
+    def sample(self, features, states=(None, None)):
+        """Greedy: (ids [B, max_seq_length] int64, (h, c) [num_layers, B, H]); the first input is `features`."""
+        h, c = states
+        rows = features.size(0)
+        if h is None and c is None:
+            state = None
+        else:
+            zeros = torch.zeros((self.num_layers, rows, self.hidden_size), dtype=torch.float32, device=features.device)
+            state = _to_rows(zeros if h is None else h, zeros if c is None else c)
+        ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
+        return ids, _from_rows(state)
+
+
+class DecoderRNN(_RNN):
+    """seq2seq/model.py:125-217."""
+
+    def forward(self, states, dst_tokens, lengths, teacher_forcing_ratio=0.5):
+        """Packed logits [N, V] of dst_tokens (no feature column). `states` is IGNORED and every layer starts at zero,
+        as in the reference (seq2seq/model.py:169-172): the encoder's state reaches the decoders in sample() only."""
+        return self._sequence(None, dst_tokens, lengths, teacher_forcing_ratio)[0]
+
+    def sample(self, start_token, states):
+        """Greedy from embed(start_token) and `states` (h, c) [num_layers, B, H] -> ids [B, max_seq_length] int64. The
+        start token is broadcast to the states' batch (the reference's own sample only works for B = 1, where the two
+        agree). An out-of-range start_token raises CapnetError through the device error word."""
+        h, c = states
+        given = h if h is not None else c
+        rows = 1 if given is None else given.size(1)
+        dev = self.embed.weight.device
+        zeros = torch.zeros((self.num_layers, rows, self.hidden_size), dtype=torch.float32, device=dev)
+        state = _to_rows(zeros if h is None else h, zeros if c is None else c)
+        tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
+        ids, _ = self._greedy(None, tokens, state)
+        ops.check_device_errors()
+        return ids
+
+
+class Seq2Seq(nn.Module):
+    """seq2seq/model.py:220-301: one encoder (the factual captioner) and one decoder per emotion."""
+
+    def __init__(self, embed_size, hidden_size, vocab_size, num_layers, dropout=0.22, max_seq_length=40):
+        super(Seq2Seq, self).__init__()
+        self.hidden_size = hidden_size
+        self.max_seq_length = max_seq_length
+        self.encoder = EncoderRNN(embed_size, hidden_size, vocab_size, num_layers, dropout=dropout)
+        self.decoder_happy = DecoderRNN(embed_size, hidden_size, vocab_size, num_layers, dropout=dropout)
+        self.decoder_sad = DecoderRNN(embed_size, hidden_size, vocab_size, num_layers, dropout=dropout)
+        self.decoder_angry = DecoderRNN(embed_size, hidden_size, vocab_size, num_layers, dropout=dropout)
+
+    def _decoder(self, mode):
+        if mode not in _EMOTIONS:
+            raise CapnetError("mode name wrong: %r (factual, happy, sad, angry)" % (mode,))
+        return getattr(self, "decoder_" + mode)
+
+    def forward(self, features, src, dst=(None, None), teacher_forcing_ratio=0.8, mode='factual'):
+        """factual: the encoder's packed logits of `src` = (tokens, lengths). An emotion mode: that decoder's packed
+        logits of `dst` from zero state; the reference runs the encoder first and discards its outputs, so here only its
+        draws are consumed (`random`, one per encoder step, and the dropout seed), exactly as if it had run."""
+        src_tokens, src_lengths = src
+        dst_tokens, dst_lengths = dst
+        if mode == 'factual':
+            return self.encoder(features, src_tokens, src_lengths, teacher_forcing_ratio)[0]
+        decoder = self._decoder(mode)
+        self.encoder._advance_streams(src_lengths)
+        return decoder((None, None), dst_tokens, dst_lengths, teacher_forcing_ratio)
+
+    def sample(self, features, start_token, states=(None, None), mode='factual'):
+        """factual: the encoder's greedy ids [B, max_seq_length]. An emotion mode: that decoder's greedy ids from
+        embed(start_token) and the encoder's final state."""
+        decoder = None if mode == 'factual' else self._decoder(mode)
+        sampled_ids, states = self.encoder.sample(features, states)
+        if decoder is None:
+            return sampled_ids
+        return decoder.sample(start_token, states)

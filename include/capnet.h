@@ -346,6 +346,9 @@ int capnet_bn1d_bwd(const float* dy, const float* x, int B, int C, const float* 
  * capnet_seq_forward / _backward are capnet_seq_forward_stacked / _backward_stacked at nlayers = 1. */
 size_t capnet_seq_saved_floats(const int* dims);
 size_t capnet_seq_saved_ints(const int* dims);
+/* Floats from the start of a layer's `saved` buffer to its cell states c [N][H] in packed row order (the final c of the
+ * rows alive at the last step is the tail; the final h is the tail of the layer's hiddens). Read-only for the caller. */
+size_t capnet_seq_saved_cell_offset(const int* dims);
 size_t capnet_seq_fwd_scratch_floats(const int* dims);
 size_t capnet_seq_bwd_scratch_floats(const int* dims);
 int capnet_seq_forward(const int* dims, const int* batch_sizes, const unsigned char* tf_mask,
@@ -375,7 +378,11 @@ int capnet_seq_backward(const int* dims, const int* batch_sizes, const float* d_
  * etc. with those dims). weights: nlayers x 32 pointers in capnet_seq_forward's order; saved / saved_i / hiddens: one
  * buffer per layer (the top layer's hiddens [N][H] are the output); scratch as capnet_seq_forward's.
  * Backward: d_hiddens of the top layer in; grads: nlayers x 9 pointers in capnet_seq_backward's order (dEmb / dFeat of
- * layer 0 only); dh_work: nlayers - 1 buffers [N][H]; scratch: the largest capnet_seq_bwd_scratch_floats of the layers. */
+ * layer 0 only); dh_work: nlayers - 1 buffers [N][H]; scratch: the largest capnet_seq_bwd_scratch_floats of the layers.
+ * `training` is a bit set in both calls: 0 = inference, 1 = training (dropout p on the token embeddings and between
+ * the layers), 3 = training with dropout on the token embeddings ONLY and none between the layers -- torch.nn.LSTM
+ * built without dropout=, the one stacking the reference has (capnet.seq2seq; seq2seq/model.py:46-49, 140-143), where
+ * cell 1 at nlayers > 1 is reference-pinned. Forward and backward of one step must get the same value. */
 int capnet_seq_forward_stacked(const int* dims, int nlayers, const int* batch_sizes, const unsigned char* tf_mask,
                                const long long* captions, const float* features, const float* emb,
                                const float* const* weights, const float* Cw, const float* Cb, float dropout_p,
@@ -508,6 +515,35 @@ int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int 
                                     const float* x, const float* const* wcat, const float* const* beff,
                                     const float* state_in, float* state_out, float* h_top, int* err_flag,
                                     capnet_stream_t stream);
+
+/* tokens[r] = the FIRST argmax over v of h[r] . w[v] + b[v], r < rows: the vocabulary projection (nn.Linear: w [V][H],
+ * b [V] or NULL) and the row argmax in one launch, fp32 throughout, the logits never stored. A -inf or NaN logit is never
+ * picked and a row with nothing to pick yields 0, as capnet_argmax_rows. rows >= 1, V >= 1, H in {64, 128, 256, 512,
+ * 1024}; h [rows][H], w and the workspace 16-B aligned. workspace: capnet_vocab_argmax_ws_bytes(rows, V) bytes of device
+ * memory whose first 16 bytes are ZERO before the first use (they hold the arrival counter of the in-launch reduction;
+ * every launch leaves them zero, so back-to-back calls on one stream may share a workspace; calls on different streams
+ * may not). tokens: int64 [rows]. */
+size_t capnet_vocab_argmax_ws_bytes(int rows, int V);
+int capnet_vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* workspace,
+                        long long* tokens, capnet_stream_t stream);
+
+/* Greedy decoding of a stacked nn.LSTM + nn.Linear for a fixed number of steps (capnet.seq2seq: EncoderRNN.sample /
+ * DecoderRNN.sample, seq2seq/model.py:100-122, 193-217; no end token, no dropout), the whole loop on `stream` with no
+ * host synchronisation, no allocation and nothing read back: per step one launch per layer of
+ * capnet_stacked_decode_step_cell's LSTM cell and one capnet_vocab_argmax launch, whose token the next step's layer 0
+ * gathers its embedding row by. The first step's input is features [rows][E] (the encoder) or emb[start_tokens[r]]
+ * (int64 [rows]; the decoders): exactly one of the two is non-NULL. emb [V][E]; wcat / beff: HOST arrays of nlayers device
+ * pointers packed as for capnet_stacked_decode_step_cell with cell 1; Cw [V][H] / Cb [V] (or NULL) the projection.
+ * state0: the initial [rows][2 nlayers][H] state (slot 2l = h of layer l, 2l+1 = c) or NULL for zeros; state_out receives
+ * the state after the last step in the same layout (it may be state0). ids: int64 [rows][steps].
+ * workspace: capnet_lstm_greedy_decode_ws_bytes(nlayers, rows, H, V) bytes, 16-B aligned, contents irrelevant.
+ * A token id outside [0, V) (only start_tokens can hold one) sets *err_flag = 1 and reads row 0.
+ * Shapes: those of capnet_stacked_decode_step_cell. */
+size_t capnet_lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V);
+int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                              void* workspace, long long* ids, float* state_out, int* err_flag, capnet_stream_t stream);
 
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
