@@ -151,7 +151,7 @@ static inline int fb_gram_rows(int K) { return K == 64 ? 512 : 256; }
 
 struct GArgs {
   const float* y2; const float* s2; const float* t2;
-  float* gp;            // [slices][pairs][64][64]
+  float* gp;            // [pairs][64 m][slices][64 n]
   float* cs;            // [slices][K]
   int M, K, in_exp, slices, pairs, slice_rows;
 };
@@ -163,6 +163,8 @@ struct GArgs {
 // K / 64 (K / 64 + 1) / 2 accumulators). Round 4's first form gave each pair its own workgroup and re-staged the rows per
 // pair: 26 VALU instructions per MFMA and 250 workgroups of 16 us where this is 49 of about the same length. A thread
 // stages 8 rows x 4 channels per item (eight 16-B loads); the next step's rows are requested before this step's MFMAs.
+// The slice's partial blocks go out as gp[pair][m][slice][64] (fb_gram_reduce_kernel reads a row's slices as one dense run),
+// its column sums as cs[slice][K].
 template <int K>
 __global__ __launch_bounds__(256) void fb_gram_kernel(const GArgs g) {
   constexpr int NBLK = K / 64, NPAIR = NBLK * (NBLK + 1) / 2;
@@ -255,13 +257,13 @@ __global__ __launch_bounds__(256) void fb_gram_kernel(const GArgs g) {
   }
   // D[m][n]: m = (r & 3) + 8 (r >> 2) + 4 lh = channel of block bi, n = li = channel of block bj; both operands carried 2^e
   const float osc = ldexpf(1.f, -2 * g.in_exp);
+  // partials [pair][m][slice][64]: the slices of a row lie 256 B apart for the reduction (a wave half stores a 128-B run)
 #pragma unroll
   for (int p = 0; p < NPAIR; ++p) {
-    float* out = g.gp + ((long)slice * NPAIR + p) * 4096;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      out[m * 64 + wn * 32 + li] = acc[p][r] * osc;
+      g.gp[(((long)p * 64 + m) * g.slices + slice) * 64 + wn * 32 + li] = acc[p][r] * osc;
     }
   }
   f32x4* cs_sh = reinterpret_cast<f32x4*>(lds);                // [256 / NCQ row-group lanes][NCQ channel quads]
@@ -275,49 +277,82 @@ __global__ __launch_bounds__(256) void fb_gram_kernel(const GArgs g) {
   }
 }
 
-// G (full, symmetric) and the column sums, summed over the slices in double, stored fp32: 8 threads share an entry's
-// slices, each with eight independent loads in flight per round. (Measured alternatives, K = 64 / 128 / 256: a plain loop
-// 7.4 / 6.5 / 12.9 us; 128 entries per workgroup with 32 loads per thread 20 / 22 / 15 us -- the partial blocks of one
-// entry lie 16-160 KB apart, more loads per thread only adds pages per thread; this form 4.8 / 9.9 / 13.5 us.)
+// G (full, symmetric) and the column sums, summed over the slices in double, stored fp32. An item is four adjacent n of
+// one row m of one pair's 64 x 64 block; 8 threads share an item's slices: thread `part` takes slices part + 8 u + 64 j, eight
+// independent 16-B loads in flight per round j, and the eight sums are added onto part 0's in the order q = 1..7 through LDS.
+// With the partials as [pair][m][slice][64] an item's slices lie 256 B apart in one dense run (12.5 KB at 49 slices) and
+// a workgroup of 32 items reads two such runs whole: pairs * 32 workgroups (320 / 96 / 32 for K = 256 / 128 / 64). Part 0
+// stores G[r][c..c+3] and, for a pair off the diagonal, the mirrored G[c+i][r]; a diagonal pair's block holds both of its
+// triangles itself. The last K / 32 workgroups sum the column sums cs [slice][K], one entry per 8 threads, same order.
+// (The first form kept the partials as [slice][pair][64][64] and gave every ENTRY of G its 8 threads: (K^2 + K) / 32
+// workgroups -- 2 056 at K = 256, every wave slot of the chip -- of 4-byte loads 16-160 KB apart, the lower triangle read
+// from the upper partials a second time: 4.8 / 9.9 / 13.5 us alone for K = 64 / 128 / 256, 12.4 us on average over a
+// trunk pass where this form takes 5.1.)
 __global__ __launch_bounds__(256) void fb_gram_reduce_kernel(const float* __restrict__ gp, const float* __restrict__ cs, float* __restrict__ G,
                                                              float* __restrict__ mu, int K, int slices, int pairs) {
-  __shared__ double sh[8][33];
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), part = threadIdx.x >> 5;
-  const int nG = K * K;
-  const float* p = nullptr;
-  long stride = 0;
-  if (e < nG) {
-    int r = e / K, c = e - r * K;
-    int bi = r >> 6, bj = c >> 6, m = r & 63, n = c & 63;
-    if (bi > bj) { int t = bi; bi = bj; bj = t; t = m; m = n; n = t; }
-    const int nb = K / 64;
-    const int pair = bi * nb - bi * (bi - 1) / 2 + (bj - bi);
-    p = gp + (long)pair * 4096 + m * 64 + n;
-    stride = (long)pairs * 4096;
-  } else if (e < nG + K) {
-    p = cs + (e - nG);
-    stride = K;
-  }
-  double s = 0.0;
-  if (p) {
+  __shared__ double sh[8][32][4];
+  const int it = threadIdx.x & 31, part = threadIdx.x >> 5;
+  const int item_wgs = pairs * 32;                 // pairs * 64 rows * 16 column quads / 32 items
+  if ((int)blockIdx.x < item_wgs) {
+    const int item = blockIdx.x * 32 + it;
+    const int n4 = item & 15, m = (item >> 4) & 63, pair = item >> 10;
+    const float* p = gp + ((long)(pair * 64 + m) * slices) * 64 + 4 * n4;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int s0 = part; s0 < slices; s0 += 64) {
-      float v[8];
+      f32x4 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int sl = s0 + 8 * u;
-        v[u] = p[(long)(sl < slices ? sl : part) * stride];
+        v[u] = *reinterpret_cast<const f32x4*>(p + (long)(sl < slices ? sl : part) * 64);
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) s += (s0 + 8 * u < slices) ? (double)v[u] : 0.0;
-    }
-  }
-  sh[part][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (part == 0) {
+      for (int u = 0; u < 8; ++u)
 #pragma unroll
-    for (int q = 1; q < 8; ++q) s += sh[q][threadIdx.x & 31];
-    if (e < nG) G[e] = (float)s;
-    else if (e < nG + K) mu[e - nG] = (float)s;
+        for (int i = 0; i < 4; ++i) s[i] += (s0 + 8 * u < slices) ? (double)v[u][i] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sh[part][it][i] = s[i];
+    __syncthreads();
+    if (part == 0) {
+#pragma unroll
+      for (int q = 1; q < 8; ++q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += sh[q][it][i];
+      const int nb = K / 64;
+      int bi = 0, bj = pair;                       // pair = bi nb - bi (bi - 1) / 2 + (bj - bi), bi <= bj
+      while (bj >= nb - bi) { bj -= nb - bi; ++bi; }
+      bj += bi;
+      const int r = bi * 64 + m, c = bj * 64 + 4 * n4;
+      const f32x4 o = {(float)s[0], (float)s[1], (float)s[2], (float)s[3]};
+      *reinterpret_cast<f32x4*>(G + (long)r * K + c) = o;
+      if (bi < bj) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) G[(long)(c + i) * K + r] = o[i];
+      }
+    }
+  } else {
+    const int e = ((int)blockIdx.x - item_wgs) * 32 + it;
+    double s = 0.0;
+    if (e < K) {
+      const float* p = cs + e;
+      for (int s0 = part; s0 < slices; s0 += 64) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int sl = s0 + 8 * u;
+          v[u] = p[(long)(sl < slices ? sl : part) * K];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += (s0 + 8 * u < slices) ? (double)v[u] : 0.0;
+      }
+    }
+    sh[part][it][0] = s;
+    __syncthreads();
+    if (part == 0 && e < K) {
+#pragma unroll
+      for (int q = 1; q < 8; ++q) s += sh[q][it][0];
+      mu[e] = (float)s;
+    }
   }
 }
 
@@ -1029,7 +1064,7 @@ int fused_block_stats(const float* y2, const float* s2, const float* t2, const u
   if (K == 256) hipLaunchKernelGGL(fb_gram_kernel<256>, dim3(a.slices), dim3(256), 0, stream, a);
   else if (K == 128) hipLaunchKernelGGL(fb_gram_kernel<128>, dim3(a.slices), dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(fb_gram_kernel<64>, dim3(a.slices), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(fb_gram_reduce_kernel, dim3(cdiv((long)K * K + K, 32)), dim3(256), 0, stream, a.gp, a.cs, G, mu, K, a.slices, a.pairs);
+  hipLaunchKernelGGL(fb_gram_reduce_kernel, dim3(a.pairs * 32 + K / 32), dim3(256), 0, stream, a.gp, a.cs, G, mu, K, a.slices, a.pairs);
   const double inv = 1.0 / (double)M, unbias = M > 1 ? (double)M / (double)(M - 1) : 1.0;
   const float* wcopy = reinterpret_cast<const float*>(w3img + kFHdr + (size_t)C * MID);
   if (K == 256)
