@@ -17,20 +17,14 @@
 // l h', h l', h h' accumulated in fp32 by v_mfma_f32_32x32x16_f16, accumulators x 2^-(ew + ea) in the epilogue.
 #include "common.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 #include "kernels.h"
 
 namespace capnet {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
 constexpr int RBM = 128;                 // rows of a workgroup: 4 waves x 32
 constexpr int RNB = 32;                  // output columns of one sweep step (a "granule" of weights: 32 columns x K)
-constexpr int kHdrWords = 4;             // conv_f16x3.hip's image header: [0] ew
 
 struct RArgs {
   const float* x;            // [M][Cin] dense
@@ -44,19 +38,6 @@ struct RArgs {
   int* err;                  // error word (launches without statistics check their outputs for non-finite values)
 };
 
-__device__ __forceinline__ void r_split4(const f32x4 v, h4& h, h4& l) {
-  const f2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const h2 ha = __builtin_convertvector(a, h2), hb = __builtin_convertvector(b, h2);      // v_cvt_pk_f16_f32
-  const f2 ra = a - __builtin_convertvector(ha, f2), rb = b - __builtin_convertvector(hb, f2);   // exact
-  const h2 la = __builtin_convertvector(ra, h2), lb = __builtin_convertvector(rb, h2);
-  h = h4{ha[0], ha[1], hb[0], hb[1]};
-  l = h4{la[0], la[1], lb[0], lb[1]};
-}
-// byte offset of weight cell (column n of the granule, 8-channel half c) inside one 1-KB piece -- conv_f16x3.hip's h_cell
-__device__ __forceinline__ unsigned r_cell(int row, int c) {
-  const int r = row & 15;
-  return (unsigned)((row * 2 + (c ^ ((r >> 3) & 1))) * 16);
-}
 
 template <int KG, bool PRE>
 __global__ __launch_bounds__(256) void conv1x1_areg_kernel(const RArgs g) {
@@ -72,9 +53,8 @@ __global__ __launch_bounds__(256) void conv1x1_areg_kernel(const RArgs g) {
   const int M = g.M, Cout = g.Cout;
   const int m0 = (int)blockIdx.x * RBM;
   const int n_gran = Cout / RNB, gran_per_tn = g.bn / RNB, nk = KG;
-  const int ew = (int)g.wimg[0];
-  const float oscale = ldexpf(1.f, -(ew + g.in_exp));
-  const unsigned char* const wbase = reinterpret_cast<const unsigned char*>(g.wimg + kHdrWords);
+  const float oscale = f16x3_out_scale(g.wimg[0], g.in_exp);
+  const unsigned char* const wbase = reinterpret_cast<const unsigned char*>(g.wimg + kF16x3HdrWords);
   const long sub_bytes = (long)g.bn * 32;            // one (plane, k16 group) sub-image of a (tn, kt) step
 
   // ---- weights: a granule = KG k-steps x 4 pieces (plane, k16 group) of 1 KB, LDS image [k-step][piece][1 KB]. Wave w
@@ -137,10 +117,10 @@ __global__ __launch_bounds__(256) void conv1x1_areg_kernel(const RArgs g) {
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], lo);
-        r_split4(v, hh[q], ll[q]);
+        split4(v, hh[q], ll[q]);
       }
-      ah[kk] = h8{hh[0][0], hh[0][1], hh[0][2], hh[0][3], hh[1][0], hh[1][1], hh[1][2], hh[1][3]};
-      al[kk] = h8{ll[0][0], ll[0][1], ll[0][2], ll[0][3], ll[1][0], ll[1][1], ll[1][2], ll[1][3]};
+      ah[kk] = cat8(hh[0], hh[1]);
+      al[kk] = cat8(ll[0], ll[1]);
       // finished HERE: left to itself hipcc sinks the fold + split of the later groups into the first sweep step,
       // behind its first MFMAs, and spills the raw loads on the way
       asm volatile("" : "+v"(ah[kk]), "+v"(al[kk]));
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(256) void conv1x1_areg_kernel(const RArgs g) {
     __builtin_amdgcn_sched_barrier(0);              // one batch of loads in flight at a time
   }
 
-  const unsigned char* const b_rd = bbuf + r_cell(li, lh);
+  const unsigned char* const b_rd = bbuf + f16x3_cell(li, lh);
   // ---- the column sweep: granule nb is in ring buffer nb % 3. Behind the barrier that opens it (every wave is then
   // through with granule nb - 1) the DMA of granule nb + 2 goes into the buffer granule nb - 1 occupied.
   // Waits are counted: what this wave issued after the DMA of granule nb is, at the top of iteration nb, the 16 stores of
@@ -157,10 +137,10 @@ __global__ __launch_bounds__(256) void conv1x1_areg_kernel(const RArgs g) {
   int buf = 0;
   for (int nb = 0; nb < n_gran; ++nb) {
     if (nb + 1 < n_gran) {
-      if (full && nb >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + 32) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+      if (full && nb >= 2) wait_vmcnt<NDMA + 32>();
+      else wait_vmcnt<NDMA>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     __syncthreads();                                // granule nb is in LDS; every wave is through with granule nb - 1
     if (nb + 2 < n_gran) dma_b(nb + 2, buf == 0 ? 2 : buf - 1);

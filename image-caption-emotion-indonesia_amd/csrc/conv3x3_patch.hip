@@ -20,16 +20,11 @@
 
 #include "common.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 #include "kernels.h"
 
 namespace capnet {
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 constexpr int PBM = 128;                 // output pixels of a tile
 constexpr int kPmax = 248;               // patch pixels: >= 128 + 2 * 56 + 2, = 8 mod 16 (the four channel groups 32 banks apart)
@@ -37,7 +32,6 @@ constexpr int kPatchSub = kPmax * 16;    // bytes of one (plane, 8-channel group
 constexpr int kPatch = 8 * kPatchSub;    // 2 planes x 4 groups
 constexpr int kThreads = 512;
 constexpr int kPL = (kPmax * 8 + kThreads - 1) / kThreads;   // 16-B loads per thread and chunk (4)
-constexpr int kHdrWords = 4;             // as conv_f16x3.hip: [0] ew
 static_assert(kPmax % 16 == 8 && kPmax >= PBM + 2 * 56 + 2, "patch size");
 
 struct PArgs {
@@ -61,19 +55,6 @@ struct PArgs {
   float* tail_out;
 };
 
-__device__ __forceinline__ void p_split4(const f32x4 v, h4& h, h4& l) {
-  const f2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const h2 ha = __builtin_convertvector(a, h2), hb = __builtin_convertvector(b, h2);      // v_cvt_pk_f16_f32
-  const f2 ra = a - __builtin_convertvector(ha, f2), rb = b - __builtin_convertvector(hb, f2);   // exact
-  const h2 la = __builtin_convertvector(ra, h2), lb = __builtin_convertvector(rb, h2);
-  h = h4{ha[0], ha[1], hb[0], hb[1]};
-  l = h4{la[0], la[1], lb[0], lb[1]};
-}
-// byte offset of weight cell (row n, 8-channel half c) inside one (plane, k16 group) sub-image -- conv_f16x3.hip's h_cell
-__device__ __forceinline__ unsigned p_cell(int row, int c) {
-  const int r = row & 15;
-  return (unsigned)((row * 2 + (c ^ ((r >> 3) & 1))) * 16);
-}
 
 // MODE 0: 4 x 2 waves of 32 rows x BN / 2 columns (<= 128 VGPRs); 1 (KSPLIT): four pairs of waves on 64 x BN / 2 blocks, the
 // two waves of a pair split K; 2 (BN = 256 only): 2 x 4 waves of 64 x 64 -- one 128 x 256 tile per row tile (the patch is
@@ -111,11 +92,11 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? 4 : 2) void conv3x3_patch_ker
   const int W = g.W, Cin = g.Cin;
   const int nkc = Cin / 32, nk = 9 * nkc;
   const int total = g.tiles_m * g.tiles_n, G = (int)gridDim.x;
-  const float oscale = ldexpf(1.f, -((int)g.wimg[0] + g.in_exp));
+  const float oscale = f16x3_out_scale(g.wimg[0], g.in_exp);
   const float iscale = ldexpf(1.f, g.in_exp);
   const int pq = tid & 7;                             // this thread's 4 channels of a chunk: 4 pq .. 4 pq + 3
   const unsigned char* const a_rd = patch + (kq2 * 2 + lh) * kPatchSub + (rows0 + li) * 16;      // + plane, k16, mt, tap offsets
-  const unsigned char* const b_rd = bbuf + p_cell(wn * (BN / WN) + li, lh);
+  const unsigned char* const b_rd = bbuf + f16x3_cell(wn * (BN / WN) + li, lh);
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const unsigned lds_b0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)bbuf);
 
@@ -141,7 +122,7 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? 4 : 2) void conv3x3_patch_ker
       }
       vmask[mt] = vm;
     }
-    const float* wsrc = reinterpret_cast<const float*>(g.wimg + kHdrWords) + (long)tn * nk * (kImgB / 4);
+    const float* wsrc = reinterpret_cast<const float*>(g.wimg + kF16x3HdrWords) + (long)tn * nk * (kImgB / 4);
 
     f32x4 pre[kPL], fs, ft;
     auto fetch_patch = [&](int c) {
@@ -178,7 +159,7 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? 4 : 2) void conv3x3_patch_ker
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
           }
           h4 h, l;
-          p_split4(v, h, l);
+          split4(v, h, l);
           *reinterpret_cast<h4*>(d + px * 16) = h;
           *reinterpret_cast<h4*>(d + 4 * kPatchSub + px * 16) = l;
         }
@@ -219,8 +200,8 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? 4 : 2) void conv3x3_patch_ker
         const int buf = t % kR;                                       // = step % kRing: 9 % kRing == 0
         // this wave's share of step `step` has landed once at most the DMAs of the kRing - 2 steps behind it are in
         // flight (vmcnt retires in issue order; anything else the wave has in flight only makes the wait longer)
-        if (step + kRing - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kRing - 2) * NDMA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (step + kRing - 2 < nk) wait_vmcnt<(kRing - 2) * NDMA>();
+        else wait_vmcnt<0>();
         __syncthreads();
         // the buffer of step - 1 is free now: the weights of step + kRing - 1 go there
         if (step + kRing - 1 < nk) {
@@ -360,11 +341,11 @@ __global__ __launch_bounds__(kThreads, BN == 256 ? 2 : 4) void conv1x1_tail_kern
   const int total = g.tiles_m * g.tiles_n, G = (int)gridDim.x;
   const int my_tiles = (total - 1 - (int)blockIdx.x) / G + 1;
   const int n_steps = my_tiles * nkc;
-  const float oscale = ldexpf(1.f, -((int)g.wimg[0] + g.in_exp));
+  const float oscale = f16x3_out_scale(g.wimg[0], g.in_exp);
   const float iscale = ldexpf(1.f, g.in_exp);
   const int pq = tid & 7, ppx = tid >> 3;              // this thread's 4 channels of a chunk and its pixel (and pixel + 64)
   const unsigned char* const a_rd = abuf + lh * kSubA + (wm * 32 * MT + li) * 16;
-  const unsigned char* const b_rd = bbuf + p_cell(wn * (BN / WN) + li, lh);
+  const unsigned char* const b_rd = bbuf + f16x3_cell(wn * (BN / WN) + li, lh);
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const unsigned lds_b0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)bbuf);
 
@@ -405,7 +386,7 @@ __global__ __launch_bounds__(kThreads, BN == 256 ? 2 : 4) void conv1x1_tail_kern
     int tm, tn;
     tile_of(s, tm, tn);
     const int c = s & (nkc - 1);
-    const float* src = reinterpret_cast<const float*>(g.wimg + kHdrWords) + ((long)tn * nkc + c) * (kImgB / 4);
+    const float* src = reinterpret_cast<const float*>(g.wimg + kF16x3HdrWords) + ((long)tn * nkc + c) * (kImgB / 4);
 #pragma unroll
     for (int q = 0; q < NDMA; ++q)
       glds16(src, (wave_u * NDMA + q) * 1024 + lane * 16, lds_b0 + (unsigned)(buf * kImgB + (wave_u * NDMA + q) * 1024));
@@ -431,7 +412,7 @@ __global__ __launch_bounds__(kThreads, BN == 256 ? 2 : 4) void conv1x1_tail_kern
       const int m = tm * PBM + ppx + 64 * u;
       if (real && tn == 0 && m < g.M) *reinterpret_cast<f32x4*>(g.tail_out + (long)m * Cin + c * 32 + 4 * pq) = v;
       h4 h, l;
-      p_split4(v * iscale, h, l);                      // (the written tail is unscaled; the A operand carries the prescale)
+      split4(v * iscale, h, l);                      // (the written tail is unscaled; the A operand carries the prescale)
       *reinterpret_cast<h4*>(d + (ppx + 64 * u) * 16) = h;
       *reinterpret_cast<h4*>(d + 4 * kSubA + (ppx + 64 * u) * 16) = l;
     }
@@ -462,8 +443,8 @@ __global__ __launch_bounds__(kThreads, BN == 256 ? 2 : 4) void conv1x1_tail_kern
     // the rows of step s + 1 (2 + 4 loads, behind the DMA in step s - 2), the DMA of step s + 1, the parameters of step
     // s + 1 and the rows of step s + 2 (step s - 1). More than that (a second BatchNorm's parameters, the tail's stores,
     // a tile's epilogue) only makes the wait longer, never shorter. (The loads are issued unconditionally, to the very end.)
-    if (s + 1 < n_steps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(12 + NDMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    if (s + 1 < n_steps) wait_vmcnt<12 + NDMA>();
+    else wait_vmcnt<12>();
     __syncthreads();                                   // step s is in LDS; every wave is through with step s - 1
     // staging first: its waits (the compiler's, for the rows requested two steps ago) then see only the compiler's own
     // younger loads; a DMA issued ahead of it would be counted as one of them and complete rows too early

@@ -43,22 +43,17 @@
 
 #include "common.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 #include "kernels.h"
 
 namespace capnet {
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HBM = 128, HBK = 32;
 // bytes from one (plane, k16 group) of the A image (128 rows x 2 cells) to the next; + 16: lanes 2i / 2i + 1 stage the same row
 // of the two groups, 4 KB apart they hit the same banks (SQ_LDS_BANK_CONFLICT: 3 % of the kernel's cycles)
 constexpr int kSubA = HBM * 2 * 16 + 16;
-constexpr int kHdrWords = 4;                     // image header: [0] ew, [1] bits of max |w| (pack scratch)
 constexpr int kFoldMaxH = 512;                   // input channels whose BatchNorm scale / shift live in LDS
 
 struct HArgs {
@@ -95,30 +90,11 @@ __device__ __forceinline__ void h_row_origin(const HArgs& g, int m, int& boff, i
   iw0 = ow * g.stride - g.pad;
 }
 
-// byte offset of cell (row, c) inside one (plane, group) sub-image
-__host__ __device__ inline unsigned h_cell(int row, int c) {
-  const int r = row & 15;
-  return (unsigned)((row * 2 + (c ^ ((r >> 3) & 1))) * 16);
-}
-
-// (x0, x1) -> packed f16 pairs of the two pieces; the subtraction is exact in fp32
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned& l) {
-  const f32x2 v = {x0, x1};
-  const f16x2 hh = __builtin_convertvector(v, f16x2);          // v_cvt_pk_f16_f32 (round to nearest even)
-  const f32x2 r = v - __builtin_convertvector(hh, f32x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
-
 template <int NBR>
 struct HRegs {
   f32x4 a[4], b[NBR];
   float lo, hi;      // TAPS > 1: the fold's bounds for this step's tap (0, 0 in the padding; PRE) or the factor 0 / 1 in hi
 };
-
-template <int N> __device__ __forceinline__ void h_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int BN, bool PRE, int TAPS>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
@@ -142,8 +118,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
   const int nk = TAPS * nkc;
   const int my_tiles = (total - 1 - (int)blockIdx.x) / G + 1;
   const int n_it = my_tiles * nk;
-  const float* wimg = reinterpret_cast<const float*>(g.wimg + kHdrWords);
-  const float oscale = ldexpf(1.f, -((int)g.wimg[0] + g.in_exp));
+  const float* wimg = reinterpret_cast<const float*>(g.wimg + kF16x3HdrWords);
+  const float oscale = f16x3_out_scale(g.wimg[0], g.in_exp);
   const float iscale = ldexpf(1.f, g.in_exp);
 
   const int arow = tid >> 1, ag = tid & 1;          // A staging: this thread's row and k16 group
@@ -253,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
   zero_acc();
 
   int st_k = 16 * ag;            // this thread's first channel of the step being staged (PRE)
-  const unsigned awr0 = h_cell(arow, 0), awr1 = h_cell(arow, 1);
+  const unsigned awr0 = f16x3_cell(arow, 0), awr1 = f16x3_cell(arow, 1);
   // fold + split of one pair of the staged step (pair p = floats 2p, 2p + 1 of the thread's 16)
   // (blo, bhi: the fold's bounds -- [lo, inf) inside the map, [0, 0] in the padding of a 3x3 convolution; without a
   //  fold bhi is the factor 1 / 0)
@@ -276,9 +252,9 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
     split2(x0, x1, h, l);
   };
 
-  const unsigned char* a_rd = lds + h_cell(wm * 64 + li, lh);
-  const unsigned char* b_rd = lds + kImgA + h_cell(wn * (BN / 2) + li, lh);
-  struct HTail { f16x8 ah[2], bh[NT]; };            // planes of the deferred term h h' of the second k16 group
+  const unsigned char* a_rd = lds + f16x3_cell(wm * 64 + li, lh);
+  const unsigned char* b_rd = lds + kImgA + f16x3_cell(wn * (BN / 2) + li, lh);
+  struct HTail { h8 ah[2], bh[NT]; };            // planes of the deferred term h h' of the second k16 group
   auto tail = [&](const HTail& T) {
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -300,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
         ft[4 * q + j] = PRE ? fold[kFoldMaxH + st_k + 4 * q + j] : 0.f;
       }
     if (PRE) { st_k += HBK; if (st_k >= g.Cin) st_k -= g.Cin; }
-    u32x4 ph[2], pl[2];
+    u4 ph[2], pl[2];
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
       unsigned h, l;
@@ -308,26 +284,26 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
       ph[p >> 2][p & 3] = h; pl[p >> 2][p & 3] = l;
     }
     unsigned char* d = lds + stage * kStage + ag * kSubA;
-    *reinterpret_cast<u32x4*>(d + awr0) = ph[0];
-    *reinterpret_cast<u32x4*>(d + awr1) = ph[1];
-    *reinterpret_cast<u32x4*>(d + 2 * kSubA + awr0) = pl[0];
-    *reinterpret_cast<u32x4*>(d + 2 * kSubA + awr1) = pl[1];
+    *reinterpret_cast<u4*>(d + awr0) = ph[0];
+    *reinterpret_cast<u4*>(d + awr1) = ph[1];
+    *reinterpret_cast<u4*>(d + 2 * kSubA + awr0) = pl[0];
+    *reinterpret_cast<u4*>(d + 2 * kSubA + awr1) = pl[1];
   };
 
   // One step: the MFMAs of LDS[stage] with fold + split of the next step's A cells (R -> LDS[1 - stage]) between them.
   auto body = [&](HRegs<NBR>& R, int stage, HTail& Tc, const HTail& Tp, bool pending, bool do_issue) {
     // fragments [group][plane]: plane 0 = h, 1 = l; read in the order the terms need them (l h', h l', h h');
     // the second group's are requested in phase 1, well ahead of their first MFMA
-    f16x8 af[2][2][2], bf[2][NT][2];
+    h8 af[2][2][2], bf[2][NT][2];
     auto read_frags = [&](int gq) {
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) af[gq][mt][1] = *reinterpret_cast<const f16x8*>(a_rd + stage * kStage + (2 + gq) * kSubA + mt * 1024);
+      for (int mt = 0; mt < 2; ++mt) af[gq][mt][1] = *reinterpret_cast<const h8*>(a_rd + stage * kStage + (2 + gq) * kSubA + mt * 1024);
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) bf[gq][nt][0] = *reinterpret_cast<const f16x8*>(b_rd + stage * kStage + gq * kSubB + nt * 1024);
+      for (int nt = 0; nt < NT; ++nt) bf[gq][nt][0] = *reinterpret_cast<const h8*>(b_rd + stage * kStage + gq * kSubB + nt * 1024);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) af[gq][mt][0] = *reinterpret_cast<const f16x8*>(a_rd + stage * kStage + gq * kSubA + mt * 1024);
+      for (int mt = 0; mt < 2; ++mt) af[gq][mt][0] = *reinterpret_cast<const h8*>(a_rd + stage * kStage + gq * kSubA + mt * 1024);
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) bf[gq][nt][1] = *reinterpret_cast<const f16x8*>(b_rd + stage * kStage + (2 + gq) * kSubB + nt * 1024);
+      for (int nt = 0; nt < NT; ++nt) bf[gq][nt][1] = *reinterpret_cast<const h8*>(b_rd + stage * kStage + (2 + gq) * kSubB + nt * 1024);
     };
     read_frags(0);
     // the previous BatchNorm's scale and shift of this thread's 16 channels, 8 at a time
@@ -353,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
     for (int q = 0; q < 4; ++q)
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[4 * q + j] = R.a[q][j];
-    u32x4 ph[2], pl[2];
+    u4 ph[2], pl[2];
     unsigned char* const dB = lds + (1 - stage) * kStage + kImgA;
     unsigned char* const dA = lds + (1 - stage) * kStage + ag * kSubA;
     // head MFMAs of this step: group 0 all three terms, group 1 the two small terms (its h h' is the next tail)
@@ -383,14 +359,14 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
       for (int idx = (phase * HP) / 8; idx < ((phase + 1) * HP) / 8; ++idx) head(idx);
       if (phase < NBR) *reinterpret_cast<f32x4*>(dB + (tid + 256 * phase) * 16) = R.b[phase];
       if (phase == 4) {
-        *reinterpret_cast<u32x4*>(dA + awr0) = ph[0];
-        *reinterpret_cast<u32x4*>(dA + 2 * kSubA + awr0) = pl[0];
+        *reinterpret_cast<u4*>(dA + awr0) = ph[0];
+        *reinterpret_cast<u4*>(dA + 2 * kSubA + awr0) = pl[0];
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     head(HP);
-    *reinterpret_cast<u32x4*>(dA + awr1) = ph[1];
-    *reinterpret_cast<u32x4*>(dA + 2 * kSubA + awr1) = pl[1];
+    *reinterpret_cast<u4*>(dA + awr1) = ph[1];
+    *reinterpret_cast<u4*>(dA + 2 * kSubA + awr1) = pl[1];
     __builtin_amdgcn_sched_barrier(0);
     head(HP + 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -497,9 +473,9 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
   issue(R0);
   if (n_it > 1) {
     issue(R1);
-    h_wait_vmcnt<NLD>();
+    wait_vmcnt<NLD>();
   } else {
-    h_wait_vmcnt<0>();
+    wait_vmcnt<0>();
   }
   landed(R0);
   store(R0, 0);
@@ -511,10 +487,10 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
   // registers into the stage nobody reads again -- because a branch there splits the scheduling region.
   HTail T0, T1;
   auto step = [&](HRegs<NBR>& R, int stage, int it, HTail& Tc, const HTail& Tp, bool second) {
-    if (it + 2 >= n_it) { h_wait_vmcnt<0>(); after_epi = 0; }     // nothing younger in flight
-    else if (after_epi > 0) { h_wait_vmcnt<kWaitEpi>(); --after_epi; }
-    else if (after_epi < 0) { h_wait_vmcnt<0>(); after_epi = 0; }
-    else h_wait_vmcnt<NLD>();
+    if (it + 2 >= n_it) { wait_vmcnt<0>(); after_epi = 0; }     // nothing younger in flight
+    else if (after_epi > 0) { wait_vmcnt<kWaitEpi>(); --after_epi; }
+    else if (after_epi < 0) { wait_vmcnt<0>(); after_epi = 0; }
+    else wait_vmcnt<NLD>();
     landed(R);
     body(R, stage, Tc, Tp, second || ckt > 0, it + 3 < n_it);
     __syncthreads();
@@ -530,11 +506,11 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const HArgs g) {
     step(R1, 0, it, T0, T1, false);
     step(R0, 1, it + 1, T1, T0, true);
   }
-  h_wait_vmcnt<0>();       // nothing of this workgroup may still be in flight when its LDS is handed on
+  wait_vmcnt<0>();       // nothing of this workgroup may still be in flight when its LDS is handed on
 }
 
 // max |w| as float bits (non-negative floats order like unsigned integers)
-__global__ __launch_bounds__(256) void conv1x1_f16x3_absmax_kernel(const float* __restrict__ w, unsigned* __restrict__ hdr, long n) {
+__global__ __launch_bounds__(256) void f16x3_absmax_kernel(const float* __restrict__ w, unsigned* __restrict__ hdr, long n) {
   float m = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
 #pragma unroll
@@ -542,20 +518,12 @@ __global__ __launch_bounds__(256) void conv1x1_f16x3_absmax_kernel(const float* 
   if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(hdr + 1, __float_as_uint(m));
 }
 
-__device__ __forceinline__ int h_weight_shift(unsigned absmax_bits) {
-  // max |w| 2^ew in [2^13, 2^14): a factor 4 below the f16 range, residuals of all but the smallest weights normal
-  if (absmax_bits == 0u) return 0;
-  const int e = (int)((absmax_bits >> 23) & 0xffu) - 127;       // floor(log2 max|w|)
-  const int ew = 13 - e;
-  return ew < -100 ? -100 : (ew > 100 ? 100 : ew);
-}
-
 // One thread per (tn, kt, plane, group, row, pos): 8 consecutive channels of output channel n and tap kt / (Cin / 32)
 // -> one 16-B cell. w is OIHW: [Cout][Cin][taps].
 template <int BN>
 __global__ __launch_bounds__(256) void conv_f16x3_pack_kernel(const float* __restrict__ w, unsigned* __restrict__ img,
                                                               int Cout, int Cin, int taps) {
-  const int ew = h_weight_shift(img[1]);
+  const int ew = f16x3_weight_shift(img[1]);
   if (blockIdx.x == 0 && threadIdx.x == 0) img[0] = (unsigned)ew;
   const float ws = ldexpf(1.f, ew);
   const int nkc = Cin / HBK, nk = taps * nkc, tiles_n = Cout / BN;
@@ -575,17 +543,28 @@ __global__ __launch_bounds__(256) void conv_f16x3_pack_kernel(const float* __res
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float x0 = src[(2 * q) * taps] * ws, x1 = src[(2 * q + 1) * taps] * ws;
-      const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1;
-      const _Float16 l0 = (_Float16)(x0 - (float)h0), l1 = (_Float16)(x1 - (float)h1);
-      const f16x2 p = plane == 0 ? f16x2{h0, h1} : f16x2{l0, l1};
+      _Float16 h0, l0, h1, l1;
+      split1(x0, h0, l0);
+      split1(x1, h1, l1);
+      const h2 p = plane == 0 ? h2{h0, h1} : h2{l0, l1};
       out[q] = __builtin_bit_cast(unsigned, p);
     }
-    unsigned* dst = img + kHdrWords + (((long)(tn * nk + kt) * 4 + sub) * BN * 2 + (long)row * 2 + pos) * 4;
+    unsigned* dst = img + kF16x3HdrWords + (((long)(tn * nk + kt) * 4 + sub) * BN * 2 + (long)row * 2 + pos) * 4;
     dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
   }
 }
 
 }  // namespace
+
+// The first step of every split-f16 weight pack (split_f16.h: the image header): zero the header, then max |w| over
+// the n weights into its word 1. The layout kernel that follows on the stream derives ew from it.
+int f16x3_pack_header(const float* w, unsigned* img, long n, hipStream_t stream) {
+  CAPNET_HIP_CHECK(hipMemsetAsync(img, 0, kF16x3HdrWords * 4, stream));
+  hipLaunchKernelGGL(f16x3_absmax_kernel, dim3((int)(cdiv(n, 256 * 8) > 1024 ? 1024 : cdiv(n, 256 * 8))), dim3(256), 0,
+                     stream, w, img, n);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
 
 bool conv_f16x3_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int Bn, int H, int W, int Cin,
                          int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift) {
@@ -605,18 +584,16 @@ int conv1x1_f16x3_bn(long M, int Cout) {
   (void)M;
   return Cout % 128 == 0 ? 128 : 64;
 }
-size_t conv_f16x3_weight_words(int Cin, int Cout, int k) { return (size_t)kHdrWords + (size_t)Cout * Cin * k * k; }
+size_t conv_f16x3_weight_words(int Cin, int Cout, int k) { return (size_t)kF16x3HdrWords + (size_t)Cout * Cin * k * k; }
 size_t conv1x1_f16x3_weight_words(int Cin, int Cout) { return conv_f16x3_weight_words(Cin, Cout, 1); }
 
 // w OIHW fp32 ([Cout][Cin][k][k]) -> header + the split f16 image for tile width bn
 int conv_f16x3_pack(const float* w, unsigned* img, int Cout, int Cin, int k, int bn, hipStream_t stream) {
   CAPNET_REQUIRE(w && img && Cin % HBK == 0 && (k == 1 || k == 3) && (bn == 64 || bn == 128 || bn == 256) && Cout % bn == 0 && aligned16(img),
                  "conv_f16x3_pack: bad argument (Cin=%d Cout=%d k=%d bn=%d)", Cin, Cout, k, bn);
-  CAPNET_HIP_CHECK(hipMemsetAsync(img, 0, kHdrWords * 4, stream));
   const long n = (long)Cout * Cin * k * k;
-  hipLaunchKernelGGL(conv1x1_f16x3_absmax_kernel, dim3((int)(cdiv(n, 256 * 8) > 1024 ? 1024 : cdiv(n, 256 * 8))), dim3(256), 0,
-                     stream, w, img, n);
-  CAPNET_LAUNCH_CHECK();
+  const int rh = f16x3_pack_header(w, img, n, stream);
+  if (rh) return rh;
   const long cells = n / 2;
   const int grid = (int)(cdiv(cells, 256) > 4096 ? 4096 : cdiv(cells, 256));
   if (bn == 256) hipLaunchKernelGGL(conv_f16x3_pack_kernel<256>, dim3(grid), dim3(256), 0, stream, w, img, Cout, Cin, k * k);   // (conv1x1_tail_kernel<256> only)

@@ -20,16 +20,11 @@
 
 #include "common.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 #include "kernels.h"
 
 namespace capnet {
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRows = 22;                 // (channel, kh) rows of the K axis: 21 + one of zero weights
 constexpr int kSteps = kRows / 2;         // MFMA steps of K = 16 (two rows x 8 taps)
@@ -39,7 +34,6 @@ constexpr int kGroups = kCols / 4;        // 16-B groups of a staged row (66)
 constexpr int kRowDw = 160;               // LDS row stride in dwords: >= kCols / 2, = 32 mod 64
 constexpr int kPlane = kRows * kRowDw * 4;                  // bytes of one f16 plane of the staged rows
 constexpr int kImgBytes = 2 * kSteps * 2 * 64 * 16;         // planes x steps x k-groups x channels x 16 B
-constexpr int kHdrWords = 4;              // image header: [0] ew, [1] bits of max |w| (pack scratch)
 constexpr int kLoads = (21 * kGroups + 255) / 256;          // 16-B loads per thread and segment (6)
 constexpr int kWgs = 512;
 static_assert(kRowDw * 2 >= kCols && kRowDw % 64 == 32, "staged row stride");
@@ -57,15 +51,6 @@ struct StemArgs {
   unsigned oh_mul, oh_sh;                  // (b oh) -> b, oh
 };
 
-__device__ __forceinline__ void split4(const f32x4 v, h4& h, h4& l) {
-  const f2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const h2 ha = __builtin_convertvector(a, h2), hb = __builtin_convertvector(b, h2);      // v_cvt_pk_f16_f32
-  const f2 ra = a - __builtin_convertvector(ha, f2), rb = b - __builtin_convertvector(hb, f2);   // exact
-  const h2 la = __builtin_convertvector(ra, h2), lb = __builtin_convertvector(rb, h2);
-  h = h4{ha[0], ha[1], hb[0], hb[1]};
-  l = h4{la[0], la[1], lb[0], lb[1]};
-}
-
 __global__ __launch_bounds__(256, 2) void conv_stem_f16x3_kernel(const StemArgs g) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kImgBytes + 2 * kPlane];
   __shared__ float s_red[2][4][64];
@@ -73,12 +58,12 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f16x3_kernel(const StemArgs 
   unsigned char* const xl = lds + kImgBytes;       // staged rows: plane h | plane l
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
-  const float oscale = ldexpf(1.f, -((int)g.wimg[0] + g.in_exp));
+  const float oscale = f16x3_out_scale(g.wimg[0], g.in_exp);
   const float iscale = ldexpf(1.f, g.in_exp);
 
   // ---- once per workgroup: weights into LDS, the zero-weight row to zero (its products must be finite)
   {
-    const u4* src = reinterpret_cast<const u4*>(g.wimg + kHdrWords);
+    const u4* src = reinterpret_cast<const u4*>(g.wimg + kF16x3HdrWords);
     for (int i = tid; i < kImgBytes / 16; i += 256) *reinterpret_cast<u4*>(wl + i * 16) = src[i];
     for (int i = tid; i < kRowDw; i += 256) {
       *reinterpret_cast<unsigned*>(xl + (21 * kRowDw + i) * 4) = 0u;
@@ -193,23 +178,9 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f16x3_kernel(const StemArgs 
   }
 }
 
-// max |w| as float bits (non-negative floats order like unsigned integers)
-__global__ __launch_bounds__(256) void stem_absmax_kernel(const float* __restrict__ w, unsigned* __restrict__ hdr, int n) {
-  float m = 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(hdr + 1, __float_as_uint(m));
-}
-
 // one thread per 16-B cell (plane, step, k-group, channel): taps e = 0..7 of row r = 2 step + k-group; w is OIHW [64][3][7][7]
 __global__ __launch_bounds__(256) void stem_pack_kernel(const float* __restrict__ w, unsigned* __restrict__ img) {
-  const unsigned bits = img[1];
-  int ew = 0;
-  if (bits != 0u) {      // max |w| 2^ew in [2^13, 2^14): a factor 4 below the f16 range
-    ew = 13 - ((int)((bits >> 23) & 0xffu) - 127);
-    ew = ew < -100 ? -100 : (ew > 100 ? 100 : ew);
-  }
+  const int ew = f16x3_weight_shift(img[1]);
   if (blockIdx.x == 0 && threadIdx.x == 0) img[0] = (unsigned)ew;
   const float ws = ldexpf(1.f, ew);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -225,12 +196,13 @@ __global__ __launch_bounds__(256) void stem_pack_kernel(const float* __restrict_
       const int e = 2 * q + j;
       x[j] = (r < 21 && e >= 1) ? w[((n * 3 + c) * 7 + kh) * 7 + (e - 1)] * ws : 0.f;
     }
-    const _Float16 h0 = (_Float16)x[0], h1 = (_Float16)x[1];
-    const _Float16 l0 = (_Float16)(x[0] - (float)h0), l1 = (_Float16)(x[1] - (float)h1);
+    _Float16 h0, l0, h1, l1;
+    split1(x[0], h0, l0);
+    split1(x[1], h1, l1);
     const h2 p = plane == 0 ? h2{h0, h1} : h2{l0, l1};
     out[q] = __builtin_bit_cast(unsigned, p);
   }
-  unsigned* dst = img + kHdrWords + (long)i * 4;
+  unsigned* dst = img + kF16x3HdrWords + (long)i * 4;
   dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
 }
 
@@ -243,7 +215,7 @@ bool conv_stem_f16x3_eligible(const float* x, long sxb, long sxc, long sxh, long
   return sxw == 1 && W % 4 == 0 && H >= 7 && W >= 8 && aligned16(x) && sxb % 4 == 0 && sxc % 4 == 0 && sxh % 4 == 0 &&
          (long)Bn * sxb < (1l << 31) && (long)Bn * OH * cdiv(OW, kSeg) < (1l << 24) && (long)Bn * OH * OW * 64 < (1l << 31);
 }
-size_t conv_stem_f16x3_weight_words() { return (size_t)kHdrWords + kImgBytes / 4; }
+size_t conv_stem_f16x3_weight_words() { return (size_t)kF16x3HdrWords + kImgBytes / 4; }
 // rows of the statistics partials one launch writes (one per workgroup)
 int conv_stem_f16x3_part_rows(int Bn, int H, int W) {
   const long OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
@@ -253,9 +225,8 @@ int conv_stem_f16x3_part_rows(int Bn, int H, int W) {
 
 int conv_stem_f16x3_pack(const float* w_oihw, unsigned* img, hipStream_t stream) {
   CAPNET_REQUIRE(w_oihw && img && aligned16(img), "conv_stem_f16x3_pack: bad argument");
-  CAPNET_HIP_CHECK(hipMemsetAsync(img, 0, kHdrWords * 4, stream));
-  hipLaunchKernelGGL(stem_absmax_kernel, dim3(4), dim3(256), 0, stream, w_oihw, img, 64 * 3 * 7 * 7);
-  CAPNET_LAUNCH_CHECK();
+  const int rh = f16x3_pack_header(w_oihw, img, 64 * 3 * 7 * 7, stream);
+  if (rh) return rh;
   hipLaunchKernelGGL(stem_pack_kernel, dim3(cdiv(kImgBytes / 16, 256)), dim3(256), 0, stream, w_oihw, img);
   CAPNET_LAUNCH_CHECK();
   return kOk;

@@ -27,47 +27,18 @@
 
 #include "common.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 #include "kernels.h"
 
 namespace capnet {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int kFHdr = 4;                  // image header words: [0] ew, [1] bits of max |w| (pack scratch)
-
 __host__ __device__ constexpr int fb_kslot(int g, int j) { return 16 * (j >> 2) + 4 * g + (j & 3); }
 
-__device__ __forceinline__ void fb_split4(const f32x4 v, h4& h, h4& l) {
-  const f2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const h2 ha = __builtin_convertvector(a, h2), hb = __builtin_convertvector(b, h2);
-  const f2 ra = a - __builtin_convertvector(ha, f2), rb = b - __builtin_convertvector(hb, f2);
-  const h2 la = __builtin_convertvector(ra, h2), lb = __builtin_convertvector(rb, h2);
-  h = h4{ha[0], ha[1], hb[0], hb[1]};
-  l = h4{la[0], la[1], lb[0], lb[1]};
-}
-__device__ __forceinline__ h8 fb_cat(const h4 a, const h4 b) { return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weight images
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void fb_absmax_kernel(const float* __restrict__ w, unsigned* __restrict__ hdr, long n) {
-  float m = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(hdr + 1, __float_as_uint(m));
-}
-__device__ __forceinline__ int fb_weight_shift(unsigned absmax_bits) {      // max |w| 2^ew in [2^13, 2^14) (conv_f16x3.hip)
-  if (absmax_bits == 0u) return 0;
-  const int e = (int)((absmax_bits >> 23) & 0xffu) - 127;
-  const int ew = 13 - e;
-  return ew < -100 ? -100 : (ew > 100 ? 100 : ew);
-}
-
 // role 0: W3 [C][MID] (conv3, the A operand of phase A): cells [chunk C/32][ks MID/32][blk 2][plane 2][lane 64] of 8 halfs
 //         = W3[32 chunk + 16 blk + (lane & 15)][32 ks + kslot(lane >> 4, j)], followed by an fp32 copy of W3 (the
 //         statistics' quadratic forms read the weights as they are; laid out [C / 16][MID][16]);
@@ -75,7 +46,7 @@ __device__ __forceinline__ int fb_weight_shift(unsigned absmax_bits) {      // m
 //         = W1[16 nb + (lane & 15)][32 chunk + kslot(lane >> 4, j)].
 __global__ __launch_bounds__(256) void fb_pack_kernel(const float* __restrict__ w, unsigned* __restrict__ img, int C, int MID,
                                                       int role, int wide) {
-  const int ew = fb_weight_shift(img[1]);
+  const int ew = f16x3_weight_shift(img[1]);
   if (blockIdx.x == 0 && threadIdx.x == 0) { img[0] = (unsigned)ew; img[2] = (unsigned)wide; }
   const float ws = ldexpf(1.f, ew);
   const long cells = (long)C * MID / 8 * 2;
@@ -124,18 +95,19 @@ __global__ __launch_bounds__(256) void fb_pack_kernel(const float* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float x0 = src[koff[2 * q]] * ws, x1 = src[koff[2 * q + 1]] * ws;
-      const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1;
-      const _Float16 l0 = (_Float16)(x0 - (float)h0), l1 = (_Float16)(x1 - (float)h1);
+      _Float16 h0, l0, h1, l1;
+      split1(x0, h0, l0);
+      split1(x1, h1, l1);
       const h2 p = plane == 0 ? h2{h0, h1} : h2{l0, l1};
       out[q] = __builtin_bit_cast(unsigned, p);
     }
-    unsigned* dst = img + kFHdr + i * 4;
+    unsigned* dst = img + kF16x3HdrWords + i * 4;
     dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
   }
   if (role == 0) {
     // fp32 copy for the statistics' quadratic forms, 16 channels interleaved: cp[c / 16][k][c % 16] = W3[c][k] (the 16
     // weights one k of a channel group needs sit in one 64-B line: scalar loads)
-    float* cp = reinterpret_cast<float*>(img + kFHdr + (long)C * MID);
+    float* cp = reinterpret_cast<float*>(img + kF16x3HdrWords + (long)C * MID);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)C * MID; i += (long)gridDim.x * blockDim.x) {
       const int c = (int)(i / MID), k = (int)(i - (long)c * MID);
       cp[((long)(c >> 4) * MID + k) * 16 + (c & 15)] = w[i];
@@ -216,11 +188,11 @@ __global__ __launch_bounds__(256) void fb_gram_kernel(const GArgs g) {
       for (int c = 0; c < 4; ++c) {
         const f32x4 a = {x[0][c], x[1][c], x[2][c], x[3][c]}, b = {x[4][c], x[5][c], x[6][c], x[7][c]};
         h4 ha, la, hb, lb;
-        fb_split4(a, ha, la);
-        fb_split4(b, hb, lb);
+        split4(a, ha, la);
+        split4(b, hb, lb);
         unsigned char* d = lds + (rg * K + 4 * chq + c) * 16;
-        *reinterpret_cast<h8*>(d) = fb_cat(ha, hb);
-        *reinterpret_cast<h8*>(d + kPlane) = fb_cat(la, lb);
+        *reinterpret_cast<h8*>(d) = cat8(ha, hb);
+        *reinterpret_cast<h8*>(d + kPlane) = cat8(la, lb);
       }
     }
   };
@@ -446,8 +418,6 @@ struct FArgs {
 #define CAPNET_FB_DBG 0        // probes only: 1 = no MFMAs (fragments still read), 2 = no weight DMA (waits and barriers stay),
                                // 3 = neither MFMAs nor fragment reads (DMA, barriers, tail), 4 = as 3 without the weight DMA
 #endif
-template <int N>
-__device__ __forceinline__ void fb_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // NW waves of RS 16-row strips each. NW = 4: one wave per SIMD (up to 512 registers: RS = 2 fits); NW = 8: two waves per
 // SIMD at <= 256 registers -- a lone wave issues its own loads, waits and tail arithmetic BETWEEN its MFMAs (SQ counters,
@@ -468,8 +438,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
   const unsigned ring0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
   const int tile0 = (int)blockIdx.x * TR;
   const bool fold_res = g.sd != nullptr;
-  const float* const w3img = reinterpret_cast<const float*>(g.w3 + kFHdr);
-  const float* const w1img = reinterpret_cast<const float*>(g.w1 + kFHdr);
+  const float* const w3img = reinterpret_cast<const float*>(g.w3 + kF16x3HdrWords);
+  const float* const w1img = reinterpret_cast<const float*>(g.w1 + kF16x3HdrWords);
 
   // LDS-DMA of chunk `cc` of an image into ring slot `slot`: wave w moves pieces [w NDMA, (w + 1) NDMA)
   auto dma = [&](const float* img, int cc, int slot) __attribute__((always_inline)) {
@@ -499,7 +469,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
   fetch_id(0, idA);
   fetch_id(NCH > 1 ? 1 : 0, idB);
   {
-    const float x3 = ldexpf(1.f, -((int)g.w3[0] + g.e3));
+    const float x3 = f16x3_out_scale(g.w3[0], g.e3);
     for (int i = tid; i < C; i += NT) {
       par[0][i] = g.s3[i] * x3;
       par[1][i] = g.t3[i];
@@ -525,14 +495,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
           v1[e] = fmaxf(fmaf(v1[e], sb[e], tb[e]), 0.f) * is3;
         }
         h4 h0, l0, h1, l1;
-        fb_split4(v0, h0, l0);
-        fb_split4(v1, h1, l1);
-        ah[s][ks] = fb_cat(h0, h1);
-        al[s][ks] = fb_cat(l0, l1);
+        split4(v0, h0, l0);
+        split4(v1, h1, l1);
+        ah[s][ks] = cat8(h0, h1);
+        al[s][ks] = cat8(l0, l1);
       }
     }
   }
-  fb_wait_vmcnt<0>();                 // everything of the prologue has landed: the loop's counted waits start from here
+  wait_vmcnt<0>();                 // everything of the prologue has landed: the loop's counted waits start from here
   CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
   if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
   __syncthreads();
@@ -633,7 +603,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
     for (int bb = 0; bb < FD; ++bb)
       if (bb < NBATB) read_b(bb);
     __builtin_amdgcn_sched_barrier(0);
-    fb_wait_vmcnt<4 * NDMA + 2 * L>();
+    wait_vmcnt<4 * NDMA + 2 * L>();
     if constexpr (RS == 2) CAPNET_LANDED4(id[0][0], id[0][1], id[1][0], id[1][1]);
     else CAPNET_LANDED2(id[0][0], id[0][1]);
     h8 oh[RS], ol[RS];
@@ -656,10 +626,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = fmaxf(fmaf(d[s][blk][e], sv[e], tv[e]) + r[e], 0.f);
         *reinterpret_cast<f32x4*>(g.out + (long)row * C + ch) = o;
-        fb_split4(o * is1, hh[blk], ll[blk]);
+        split4(o * is1, hh[blk], ll[blk]);
       }
-      oh[s] = fb_cat(hh[0], hh[1]);
-      ol[s] = fb_cat(ll[0], ll[1]);
+      oh[s] = cat8(hh[0], hh[1]);
+      ol[s] = cat8(ll[0], ll[1]);
     }
     fetch_id(cc + 2 < NCH ? cc + 2 : NCH - 1, id);
 #pragma unroll
@@ -687,7 +657,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
   auto head = [&](int k) __attribute__((always_inline)) {
     // (the counted wait assumes the steady stream behind D(k); the first iterations of the lagging group have run no B
     //  phase yet -- fewer operations are younger than D(k) than the count allows for -- so the first four drain instead)
-    if (k < 4) fb_wait_vmcnt<0>(); else fb_wait_vmcnt<NDMA + 2 * L>();
+    if (k < 4) wait_vmcnt<0>(); else wait_vmcnt<NDMA + 2 * L>();
     __syncthreads();
     const int p = k + 2 < 2 * NCH ? k + 2 : 2 * NCH - 2 + (k & 1);          // past the end: a last phase of the same kind, again
     dma((p & 1) ? w1img : w3img, p >> 1, (k + 2) & 3);
@@ -717,7 +687,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
       head(2 * NCH);
       if constexpr (LAG != 0) phase_b(NCH - 1, idB);
     }
-    fb_wait_vmcnt<0>();               // the clamped DMAs and loads past the end: nothing may be in flight when the LDS is re-used / handed on
+    wait_vmcnt<0>();               // the clamped DMAs and loads past the end: nothing may be in flight when the LDS is re-used / handed on
     CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
     if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
   };
@@ -726,7 +696,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
   __syncthreads();
 
   // ---- epilogue: y1 = acc 2^-(ew1 + e1); column statistics of the rows below M
-  const float osc = ldexpf(1.f, -((int)g.w1[0] + g.e1));
+  const float osc = f16x3_out_scale(g.w1[0], g.e1);
   float (*const scratch)[NW][MID] = reinterpret_cast<float (*)[NW][MID]>(ring);     // [sum | sumsq][wave][col]
   float bad = 0.f;
 #pragma unroll
@@ -790,8 +760,8 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
   const unsigned ring0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
   const int tile0 = (int)blockIdx.x * TR;
   const bool fold_res = g.sd != nullptr;
-  const float* const w3img = reinterpret_cast<const float*>(g.w3 + kFHdr);
-  const float* const w1img = reinterpret_cast<const float*>(g.w1 + kFHdr);
+  const float* const w3img = reinterpret_cast<const float*>(g.w3 + kF16x3HdrWords);
+  const float* const w1img = reinterpret_cast<const float*>(g.w1 + kF16x3HdrWords);
   auto dma = [&](const float* img, int cc, int slot) __attribute__((always_inline)) {
     const float* src = img + (long)cc * (SLOT / 4);
 #pragma unroll
@@ -811,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
   fetch_id(0, idA);
   fetch_id(NCH > 1 ? 1 : 0, idB);
   {
-    const float x3 = ldexpf(1.f, -((int)g.w3[0] + g.e3));
+    const float x3 = f16x3_out_scale(g.w3[0], g.e3);
     for (int i = tid; i < C; i += NT) {
       par[0][i] = g.s3[i] * x3;
       par[1][i] = g.t3[i];
@@ -835,13 +805,13 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
         v1[e] = fmaxf(fmaf(v1[e], sb[e], tb[e]), 0.f) * is3;
       }
       h4 h0, l0, h1, l1;
-      fb_split4(v0, h0, l0);
-      fb_split4(v1, h1, l1);
-      ah[ks] = fb_cat(h0, h1);
-      al[ks] = fb_cat(l0, l1);
+      split4(v0, h0, l0);
+      split4(v1, h1, l1);
+      ah[ks] = cat8(h0, h1);
+      al[ks] = cat8(l0, l1);
     }
   }
-  fb_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   CAPNET_LANDED4(idA[0], idA[1], idA[2], idA[3]);
   CAPNET_LANDED4(idB[0], idB[1], idB[2], idB[3]);
   __syncthreads();
@@ -900,7 +870,7 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
     for (int q = 0; q < GB; ++q)
       if (q < NG) { fb[0][q][0] = *(lds_h8)(wb + (q * 2) * 1024); fb[0][q][1] = *(lds_h8)(wb + (q * 2 + 1) * 1024); }
     __builtin_amdgcn_sched_barrier(0);
-    fb_wait_vmcnt<4 * NDMA + 2 * L>();
+    wait_vmcnt<4 * NDMA + 2 * L>();
     CAPNET_LANDED4(id[0], id[1], id[2], id[3]);
     h4 hh[4], ll[4];
 #pragma unroll
@@ -916,9 +886,9 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = fmaxf(fmaf(d[4 * q + e], sv[e], tv[e]) + r[e], 0.f);
       *reinterpret_cast<f32x4*>(g.out + (long)myrow * C + ch) = o;
-      fb_split4(o * is1, hh[q], ll[q]);
+      split4(o * is1, hh[q], ll[q]);
     }
-    const h8 oh[2] = {fb_cat(hh[0], hh[1]), fb_cat(hh[2], hh[3])}, ol[2] = {fb_cat(ll[0], ll[1]), fb_cat(ll[2], ll[3])};
+    const h8 oh[2] = {cat8(hh[0], hh[1]), cat8(hh[2], hh[3])}, ol[2] = {cat8(ll[0], ll[1]), cat8(ll[2], ll[3])};
     fetch_id(cc + 2 < NCH ? cc + 2 : NCH - 1, id);
 #pragma unroll
     for (int b = 0; b < NBATB; ++b) {
@@ -943,7 +913,7 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
     }
   };
   auto head = [&](int k) __attribute__((always_inline)) {
-    if (k < 4) fb_wait_vmcnt<0>(); else fb_wait_vmcnt<NDMA + 2 * L>();
+    if (k < 4) wait_vmcnt<0>(); else wait_vmcnt<NDMA + 2 * L>();
     __syncthreads();
     const int p = k + 2 < 2 * NCH ? k + 2 : 2 * NCH - 2 + (k & 1);
     dma((p & 1) ? w1img : w3img, p >> 1, (k + 2) & 3);
@@ -960,13 +930,13 @@ __global__ __launch_bounds__(256, 1) void fb_fused_wide_kernel(const FArgs g) {
     head(k + 3);
     phase_b(c0 + 1, idB);
   }
-  fb_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   CAPNET_LANDED4(idA[0], idA[1], idA[2], idA[3]);
   CAPNET_LANDED4(idB[0], idB[1], idB[2], idB[3]);
   __syncthreads();
 
   // ---- epilogue: y1 = acc 2^-(ew1 + e1); D[r]: row (r & 3) + 8 (r >> 2) + 4 lh, column 32 nb + li
-  const float osc = ldexpf(1.f, -((int)g.w1[0] + g.e1));
+  const float osc = f16x3_out_scale(g.w1[0], g.e1);
   float (*const scratch)[NW][MID] = reinterpret_cast<float (*)[NW][MID]>(ring);
   float bad = 0.f;
 #pragma unroll
@@ -1013,7 +983,7 @@ bool fused_block_shape_ok(long M, int MID) {
 }
 
 size_t fused_block_weight_words(int C, int MID, int role) {
-  return (size_t)kFHdr + (size_t)C * MID * (role == 0 ? 2 : 1);
+  return (size_t)kF16x3HdrWords + (size_t)C * MID * (role == 0 ? 2 : 1);
 }
 
 // 32-row strips on 32x32x16 MFMAs (fb_fused_wide_kernel) or 16-row strips on 16x16x32 ones: the weight images differ, so
@@ -1029,10 +999,9 @@ static bool fb_wide(int MID) {
 int fused_block_pack(const float* w, unsigned* img, int C, int MID, int role, hipStream_t stream) {
   CAPNET_REQUIRE(w && img && aligned16(img) && C == 4 * MID && (MID == 64 || MID == 128 || MID == 256) && (role == 0 || role == 1),
                  "fused_block_pack: bad argument (C=%d MID=%d role=%d)", C, MID, role);
-  CAPNET_HIP_CHECK(hipMemsetAsync(img, 0, kFHdr * 4, stream));
   const long n = (long)C * MID;
-  hipLaunchKernelGGL(fb_absmax_kernel, dim3((int)(cdiv(n, 256 * 8) > 1024 ? 1024 : cdiv(n, 256 * 8))), dim3(256), 0, stream, w, img, n);
-  CAPNET_LAUNCH_CHECK();
+  const int rh = f16x3_pack_header(w, img, n, stream);
+  if (rh) return rh;
   hipLaunchKernelGGL(fb_pack_kernel, dim3((int)(cdiv(n / 4, 256) > 2048 ? 2048 : cdiv(n / 4, 256))), dim3(256), 0, stream, w, img, C, MID, role, fb_wide(MID) ? 1 : 0);
   CAPNET_LAUNCH_CHECK();
   return kOk;
@@ -1066,7 +1035,7 @@ int fused_block_stats(const float* y2, const float* s2, const float* t2, const u
   else hipLaunchKernelGGL(fb_gram_kernel<64>, dim3(a.slices), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(fb_gram_reduce_kernel, dim3(a.pairs * 32 + K / 32), dim3(256), 0, stream, a.gp, a.cs, G, mu, K, a.slices, a.pairs);
   const double inv = 1.0 / (double)M, unbias = M > 1 ? (double)M / (double)(M - 1) : 1.0;
-  const float* wcopy = reinterpret_cast<const float*>(w3img + kFHdr + (size_t)C * MID);
+  const float* wcopy = reinterpret_cast<const float*>(w3img + kF16x3HdrWords + (size_t)C * MID);
   if (K == 256)
     hipLaunchKernelGGL(fb_quad_kernel<256>, dim3(cdiv(C, kQC)), dim3(K * 4), 0, stream, G, mu, wcopy, C, inv, unbias, gamma, beta,
                        running_mean, running_var, momentum, eps, scale, shift, batch_mean, batch_var, err);

@@ -75,6 +75,9 @@ int conv1x1_f16x3_bn(long M, int Cout);
 bool conv_f16x3_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int Bn, int H, int W, int Cin,
                          int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift);
 size_t conv_f16x3_weight_words(int Cin, int Cout, int k);
+// first step of every split-f16 weight pack (conv_f16x3_pack, fused_block_pack, conv_stem_f16x3_pack): zeroes the image
+// header (split_f16.h) and leaves the bits of max |w| over the n weights in its word 1 for the layout kernel that follows
+int f16x3_pack_header(const float* w, unsigned* img, long n, hipStream_t stream);
 int conv_f16x3_pack(const float* w_oihw, unsigned* img, int Cout, int Cin, int k, int bn, hipStream_t stream);
 int conv_fwd_f16x3(const float* x, long sxb, long sxh, long sxw, const unsigned* wimg, int bn, float* y,
                    const float* in_scale, const float* in_shift, int relu_in, float* part_sum, float* part_sq, int Bn,

@@ -46,10 +46,9 @@
 #include "common.h"
 #include "kernels.h"
 #include "mfma_core.h"
+#include "split_f16.h"
 
 namespace capnet {
-
-typedef float pf32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPH = 512;            // hidden size
 constexpr int kPShards = 8;
@@ -89,7 +88,7 @@ __device__ __forceinline__ void st_sc1_f32(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // 16-B load that bypasses the vector L1 (served by L2 or beyond); not valid before wait_vm0()
-template <int OFF> __device__ __forceinline__ void ld16_sc1(pf32x4& dst, const float* p) {
+template <int OFF> __device__ __forceinline__ void ld16_sc1(f32x4& dst, const float* p) {
   asm volatile("global_load_dwordx4 %0, %1, off offset:%2 sc1" : "=v"(dst) : "v"(p), "n"(OFF) : "memory");
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -115,48 +114,30 @@ __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" :
 // [batch row][4 unit + gate], the layout the epilogue reads (rows padded to 68 floats: the 16 lanes of a k-quarter
 // write 16 different rows at the same column, 4 banks apart).
 constexpr int kWExp = 10;
-typedef _Float16 ph16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ph16x2 __attribute__((ext_vector_type(2)));
-typedef float pf32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
-
-// (x0, x1) -> packed f16 pairs of the two pieces
-__device__ __forceinline__ void p_split2(float x0, float x1, unsigned& h, unsigned& l) {
-  const pf32x2 v = {x0, x1};
-  const ph16x2 hh = __builtin_convertvector(v, ph16x2);          // v_cvt_pk_f16_f32, round to nearest even
-  const pf32x2 r = v - __builtin_convertvector(hh, pf32x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, ph16x2));
-}
-__device__ __forceinline__ void p_split8(const pf32x4& x0, const pf32x4& x1, ph16x8& hi, ph16x8& lo) {
-  unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-  p_split2(x0[0], x0[1], h0, l0);
-  p_split2(x0[2], x0[3], h1, l1);
-  p_split2(x1[0], x1[1], h2, l2);
-  p_split2(x1[2], x1[3], h3, l3);
-  const pu32x4 h = {h0, h1, h2, h3}, l = {l0, l1, l2, l3};
-  hi = __builtin_bit_cast(ph16x8, h);
-  lo = __builtin_bit_cast(ph16x8, l);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+__device__ __forceinline__ void p_split8(const f32x4& x0, const f32x4& x1, h8& hi, h8& lo) {
+  unsigned hw[4], lw[4];
+  split2(x0[0], x0[1], hw[0], lw[0]);
+  split2(x0[2], x0[3], hw[1], lw[1]);
+  split2(x1[0], x1[1], hw[2], lw[2]);
+  split2(x1[2], x1[3], hw[3], lw[3]);
+  const u4 h = {hw[0], hw[1], hw[2], hw[3]}, l = {lw[0], lw[1], lw[2], lw[3]};
+  hi = __builtin_bit_cast(h8, h);
+  lo = __builtin_bit_cast(h8, l);
 }
 
 // wq[(4 nb + g) * 2 + plane]: the 8 f16 of (column block nb, k group g), plane 0 = hi, 1 = lo
-__device__ __forceinline__ void persist_mfma_group(const ph16x8& ahi, const ph16x8& alo, const pf32x4 (&wq)[32], int g,
-                                                   pf32x4 (&acc)[4]) {
+__device__ __forceinline__ void persist_mfma_group(const h8& ahi, const h8& alo, const f32x4 (&wq)[32], int g,
+                                                   f32x4 (&acc)[4]) {
   // product-major: an accumulator is touched again three MFMAs later, past the instruction's own latency
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
-    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph16x8, wq[(4 * nb + g) * 2]), alo, acc[nb], 0, 0, 0);
+    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wq[(4 * nb + g) * 2]), alo, acc[nb], 0, 0, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
-    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph16x8, wq[(4 * nb + g) * 2 + 1]), ahi, acc[nb], 0, 0, 0);
+    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wq[(4 * nb + g) * 2 + 1]), ahi, acc[nb], 0, 0, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
-    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph16x8, wq[(4 * nb + g) * 2]), ahi, acc[nb], 0, 0, 0);
+    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wq[(4 * nb + g) * 2]), ahi, acc[nb], 0, 0, 0);
 }
 
 // The 8 h loads of a step were issued in k order (group g = loads 2 g, 2 g + 1) and vmcnt retires in issue order:
@@ -169,10 +150,10 @@ template <int N> __device__ __forceinline__ void wait_h_loads(bool stores) {
   if (stores) wait_vmcnt<N + 9>();
   else wait_vmcnt<N + 4>();
 }
-__device__ __forceinline__ void persist_mfma(const pf32x4 (&hv)[8], const pf32x4 (&wq)[32], pf32x4 (&acc)[4], bool stores) {
+__device__ __forceinline__ void persist_mfma(const f32x4 (&hv)[8], const f32x4 (&wq)[32], f32x4 (&acc)[4], bool stores) {
 #pragma unroll
-  for (int nb = 0; nb < 4; ++nb) acc[nb] = pf32x4{0.f, 0.f, 0.f, 0.f};
-  ph16x8 ahi[2], alo[2];
+  for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  h8 ahi[2], alo[2];
   // (input-only markers for tools/isa_inflight_check.py: a "+v" tie here made hipcc copy the still-stale registers
   //  above the wait -- mfma_core.h, CAPNET_LANDED_IN)
   wait_h_loads<6>(stores);
@@ -222,9 +203,9 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
 
   // ---- weights of this wave: 128 VGPRs (16 (column block, k group) pairs x {hi, lo} x 8 f16), requested first so
   // that the handshake hides behind them
-  pf32x4 wq[32];
+  f32x4 wq[32];
   {
-    const pf32x4* wp = reinterpret_cast<const pf32x4*>(a.Wp) + ((long)(slot * 4 + wave) * 32) * 64 + lane;
+    const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp) + ((long)(slot * 4 + wave) * 32) * 64 + lane;
 #pragma unroll
     for (int q = 0; q < 32; ++q) wq[q] = wp[(long)q * 64];
   }
@@ -289,7 +270,7 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
   // the h store). hipcc's own loads in a loop make its waitcnt pass drain vmcnt(0) at points it
   // cannot see our in-flight operations from; only the poll is a compiler-visible (atomic) load,
   // and at that point nothing but the previous flag store is in flight.
-  pf32x4 dgate = {0.f, 0.f, 0.f, 0.f};    // activated gates + c of the previous step, stored one
+  f32x4 dgate = {0.f, 0.f, 0.f, 0.f};    // activated gates + c of the previous step, stored one
   float dcell = 0.f;                       // step late, behind the next step's h loads
   long drow = -1;
 
@@ -314,7 +295,7 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
     const bool evalid = em < rows_t;                  // (rows_t <= 16 by construction)
     const long erow = ro + (evalid ? grow : 0);       // row `ro` always exists (b_t >= 1)
     const bool product = t > 0;
-    pf32x4 hv[8];
+    f32x4 hv[8];
     if (product) {
       // ---- wait for h_{t-1}: produced inside this launch for t > t0, by earlier launches at t0
       if (t > a.t0) {
@@ -353,7 +334,7 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
     }
     // ---- pre-activations of this step (written by the input-chain GEMMs before this launch):
     // behind the h loads, they have the whole product to arrive
-    pf32x4 pre;
+    f32x4 pre;
     {
       const float* gp = a.G + erow * (4 * H) + u0 + eu;
       asm volatile("global_load_dword %0, %1, off" : "=v"(pre[0]) : "v"(gp + (long)gi * H) : "memory");
@@ -371,14 +352,14 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
       // Younger than the h loads: 4 loads and, if this wave executed them, the 5 deferred stores (the wave executes
       // them iff one of its lanes had a live row; if the count assumed here were too low the wait would only be
       // longer, never shorter).
-      pf32x4 acc[4];
+      f32x4 acc[4];
       const bool stores_in_flight = __any(had_deferred);
       persist_mfma(hv, wq, acc, stores_in_flight);
       if (DIAG) ts[2] = __builtin_amdgcn_s_memtime();
       // D: register i of lane (lm, kq) of column block nb = out[batch row lm][unit 4 nb + kq][gate i]
       if (lm < rows_t) {
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) *reinterpret_cast<pf32x4*>(&red[t & 1][wave][lm][4 * (4 * nb + kq)]) = acc[nb];
+        for (int nb = 0; nb < 4; ++nb) *reinterpret_cast<f32x4*>(&red[t & 1][wave][lm][4 * (4 * nb + kq)]) = acc[nb];
       }
     }
     wait_vm0();     // pre-activations (and the deferred stores, long gone)
@@ -386,9 +367,9 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
     if (product) {
       __syncthreads();
       if (evalid) {
-        pf32x4 sum = *reinterpret_cast<const pf32x4*>(&red[t & 1][0][em][4 * eu]);
+        f32x4 sum = *reinterpret_cast<const f32x4*>(&red[t & 1][0][em][4 * eu]);
 #pragma unroll
-        for (int w = 1; w < 4; ++w) sum += *reinterpret_cast<const pf32x4*>(&red[t & 1][w][em][4 * eu]);
+        for (int w = 1; w < 4; ++w) sum += *reinterpret_cast<const f32x4*>(&red[t & 1][w][em][4 * eu]);
         pre += sum * (1.f / (float)(1 << kWExp));
       }
     }
@@ -400,7 +381,7 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(const PersistArgs a) 
       float* hp = a.hiddens + erow * H + u0 + eu;
       if (local) st32(hp, h);
       else asm volatile("global_store_dword %0, %1, off sc1" :: "v"(hp), "v"(h) : "memory");
-      dgate = pf32x4{i, f, og, gt};
+      dgate = f32x4{i, f, og, gt};
       dcell = c_reg;
       drow = erow;
     }
@@ -452,7 +433,7 @@ __global__ __launch_bounds__(256) void lstm_persist_pack_kernel(const float* __r
     const int k = 128 * w + 32 * g + 16 * (jp >> 1) + 4 * kq + 2 * (jp & 1);
     const float* src = Wcat + ((long)grow[n & 3] * kPH + 16 * slot + 4 * nb + (n >> 2)) * kPH + k;
     unsigned h, l;
-    p_split2(src[0] * (float)(1 << kWExp), src[1] * (float)(1 << kWExp), h, l);
+    split2(src[0] * (float)(1 << kWExp), src[1] * (float)(1 << kWExp), h, l);
     const long q = ((long)(slot * 4 + w) * 32 + (4 * nb + g) * 2) * 256 + lane * 4 + jp;
     Wp[q] = h;
     Wp[q + 256] = l;

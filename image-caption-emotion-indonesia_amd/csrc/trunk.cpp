@@ -39,9 +39,16 @@ struct TrunkConv {
   bool fused3 = false, fused1 = false;
 };
 
+// One bottleneck block: the indices of its convolutions in Trunk::convs (id = -1: no downsample branch)
+struct TrunkBlock {
+  int stage, index;   // layer1..4 = stage 0..3, block within the stage
+  int i1, i2, i3, id;
+};
+
 struct Trunk {
   int B, H, W;
   std::vector<TrunkConv> convs;  // torchvision parameter order
+  std::vector<TrunkBlock> blocks;   // the block structure, recorded once by trunk_create; the forward passes walk it
   // workspace layout (float offsets)
   size_t off_x[2], off_y1, off_y2, off_y3, off_d, off_part, off_slab, off_gram, off_ss, total_floats;
   std::vector<size_t> ss_off;  // per conv: offset of [scale | shift] (2*Cout floats)
@@ -75,6 +82,8 @@ struct Trunk {
 };
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// a 16-B aligned non-null pointer for the eligibility predicates at plan time, when no tensor exists yet (never dereferenced)
+static const float* const kAlignedDummy = reinterpret_cast<const float*>(uintptr_t(256));
 
 int trunk_create(int B, int H, int W, Trunk** out) {
   CAPNET_REQUIRE(out != nullptr, "trunk_create: null out");
@@ -115,20 +124,16 @@ int trunk_create(int B, int H, int W, Trunk** out) {
     // ... and the kernels' 32-bit offset arithmetic must cover the whole tensor at this batch size: checked here,
     // on the dense NHWC strides every trunk tensor has, so that a shape they do not take is PLANNED for the f32 kernels
     // (with its K-major weight image) instead of failing at launch time
-    if (c.h3) {
-      const float* aligned = reinterpret_cast<const float*>(uintptr_t(256));
-      c.h3 = conv_f16x3_eligible(aligned, (long)h * w * cin, (long)w * cin, cin, 1, B, h, w, cin, cout, k, stride, pad,
-                                 activated_input ? nullptr : aligned, activated_input ? nullptr : aligned);
-    }
+    if (c.h3)
+      c.h3 = conv_f16x3_eligible(kAlignedDummy, (long)h * w * cin, (long)w * cin, cin, 1, B, h, w, cin, cout, k, stride, pad,
+                                 activated_input ? nullptr : kAlignedDummy, activated_input ? nullptr : kAlignedDummy);
     c.tile_n = c.h3 ? conv1x1_f16x3_bn((long)B * c.OH * c.OW, cout) : 0;
     if (c.h3 && tail_conv1 && wide_tails && cout % 256 == 0 && ((long)B * h * w + 127) / 128 >= wide_min_tiles &&
-        conv1x1_tail_eligible(reinterpret_cast<const float*>(uintptr_t(256)), reinterpret_cast<const float*>(uintptr_t(256)),
-                              (long)B * h * w, cin, cout))
+        conv1x1_tail_eligible(kAlignedDummy, kAlignedDummy, (long)B * h * w, cin, cout))
       c.tile_n = 256;
     if (c.h3 && wide_p3 && k == 3 && stride == 1 && cout % 256 == 0 &&
-        conv3x3_patch_eligible(reinterpret_cast<const float*>(uintptr_t(256)), (long)h * w * cin, (long)w * cin, cin, 1, B, h, w, cin,
-                               cout, k, stride, pad, reinterpret_cast<const float*>(uintptr_t(256)),
-                               reinterpret_cast<const float*>(uintptr_t(256))))
+        conv3x3_patch_eligible(kAlignedDummy, (long)h * w * cin, (long)w * cin, cin, 1, B, h, w, cin, cout, k, stride, pad,
+                               kAlignedDummy, kAlignedDummy))
       c.tile_n = 256;
     t->convs.push_back(c);
     return c;
@@ -151,12 +156,13 @@ int trunk_create(int B, int H, int W, Trunk** out) {
     for (int b = 0; b < blocks[L]; ++b) {
       const int stride = (b == 0 && L > 0) ? 2 : 1;
       const int p = planes[L];
+      const int i1 = (int)t->convs.size();
       TrunkConv c1 = add(inplanes, p, 1, 1, 0, h, w, true, !(L == 0 && b == 0));
       TrunkConv c2 = add(p, p, 3, stride, 1, h, w);
       TrunkConv c3 = add(p, p * 4, 1, 1, 0, c2.OH, c2.OW);
-      // the boundary (b - 1 -> b) inside a stage: the previous block's conv3 (three or four entries back) and this conv1
+      // the boundary (b - 1 -> b) inside a stage: the previous block's conv3 and this conv1
       if (b > 0 && L < 3 && ((t->fused_stages >> L) & 1) && c1.h3 && fused_block_shape_ok((long)B * h * w, p)) {
-        const size_t i1 = t->convs.size() - 3, i3p = i1 - (b == 1 ? 2 : 1);
+        const int i3p = t->blocks.back().i3;
         if (t->convs[i3p].h3 && t->convs[i3p].k == 1 && t->convs[i3p].Cout == inplanes && t->convs[i3p].Cin == p) {
           t->convs[i1].fused1 = true;
           t->convs[i3p].fused3 = true;
@@ -168,6 +174,7 @@ int trunk_create(int B, int H, int W, Trunk** out) {
       max_y1 = std::max(max_y1, (size_t)c1.OH * c1.OW * c1.Cout);
       max_y2 = std::max(max_y2, (size_t)c2.OH * c2.OW * c2.Cout);
       max_y3 = std::max(max_y3, (size_t)c3.OH * c3.OW * c3.Cout);
+      t->blocks.push_back(TrunkBlock{L, b, i1, i1 + 1, i1 + 2, b == 0 ? i1 + 3 : -1});
       if (b == 0) {
         TrunkConv d = add(inplanes, p * 4, 1, stride, 0, h, w, true);
         max_d = std::max(max_d, (size_t)d.OH * d.OW * d.Cout);
@@ -235,14 +242,14 @@ int trunk_time_next_pass(Trunk* t) {
   return kOk;
 }
 
-// Synchronises on the recorded events; returns total conv-kernel ms, launches and flops since
-// the last collect.
 int trunk_set_tail_balance(Trunk* t, int on) {
   CAPNET_REQUIRE(t != nullptr, "trunk_set_tail_balance: null");
   t->tail_balance = on != 0;
   return kOk;
 }
 
+// Synchronises on the recorded events; returns total conv-kernel ms, launches and flops since
+// the last collect.
 int trunk_collect_timing(Trunk* t, double* conv_ms, long* conv_launches, double* conv_flops) {
   CAPNET_REQUIRE(t && conv_ms && conv_launches && conv_flops, "trunk_collect_timing: null");
   // Time during which at least one timed conv launch was running: the union of the [start, end]
@@ -305,8 +312,7 @@ double trunk_conv_flops(const Trunk* t, int i) {
 
 double trunk_flops(const Trunk* t) {
   double f = 0;
-  for (auto& c : t->convs)
-    f += 2.0 * t->B * c.OH * c.OW * (double)c.Cout * c.k * c.k * c.Cin;
+  for (int i = 0; i < (int)t->convs.size(); ++i) f += trunk_conv_flops(t, i);
   return f;
 }
 
@@ -345,6 +351,22 @@ static int timing_end(Trunk* t, bool attach, hipStream_t s, hipEvent_t e0, hipEv
   t->timed_flops += flops;
   return kOk;
 }
+// One conv launch (`launch` returns its status) inside the timing bracket of a timed pass, a plain call otherwise.
+// attach: the launcher goes through CAPNET_LAUNCH_TIMED and takes the parked pair; a failed launch may have left it
+// parked, so it is cleared before the error is returned. flops: what the launch adds to the timed flops.
+template <class Launch>
+static int timed_launch(Trunk* t, bool attach, hipStream_t s, double flops, Launch&& launch) {
+  if (!t->timing_now) return launch();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const int rt = timing_begin(t, attach, s, &e0, &e1);
+  if (rt) return rt;
+  const int rc = launch();
+  if (rc) {
+    launch_events() = LaunchEvents{};
+    return rc;
+  }
+  return timing_end(t, attach, s, e0, e1, flops);
+}
 
 struct Ctx {
   Trunk* t;
@@ -366,6 +388,26 @@ struct Ctx {
   float* bmean(int i) const { return ws + t->bs_off[i]; }
   float* bvar(int i) const { return ws + t->bs_off[i] + t->convs[i].Cout; }
 };
+
+// (scale, shift) of BatchNorm i from the statistics partials its convolution wrote (train mode)
+static int finalize_bn(const Ctx& c, int i, const float* psum, const float* psq, int prows, long M) {
+  const bool defer = c.train == 2;   // running statistics deferred to trunk_update_running: batch mean / variance kept instead
+  return bn_finalize(psum, psq, prows, c.t->convs[i].Cout, M, c.gamma[i], c.beta[i], defer ? nullptr : c.rmean[i],
+                     defer ? nullptr : c.rvar[i], c.momentum, c.eps, c.scale(i), c.shift(i), c.s, defer ? c.bmean(i) : nullptr,
+                     defer ? c.bvar(i) : nullptr, c.err);
+}
+// inference: every BatchNorm's (scale, shift) from its running statistics, one launch
+static int eval_scale_shift_all(const Ctx& c) {
+  const int n = (int)c.t->convs.size();
+  std::vector<const float*> g(n), b(n), rm(n), rv(n);
+  std::vector<float*> sc(n), sh(n);
+  std::vector<int> C(n);
+  for (int i = 0; i < n; ++i) {
+    g[i] = c.gamma[i]; b[i] = c.beta[i]; rm[i] = c.rmean[i]; rv[i] = c.rvar[i];
+    sc[i] = c.scale(i); sh[i] = c.shift(i); C[i] = c.t->convs[i].Cout;
+  }
+  return bn_eval_multi(n, g.data(), b.data(), rm.data(), rv.data(), C.data(), sc.data(), sh.data(), c.eps, c.s);
+}
 
 // A bottleneck block's tail that has not run yet: out = relu(y3 * s1 + t1 + res (* s2 + t2)), [rows][C]
 struct BlockTail {
@@ -405,66 +447,45 @@ int conv_bn(const Ctx& c, int i, const float* x, long sxb, long sxh, long sxw, l
   const int prows = d.stem_h3 ? conv_stem_f16x3_part_rows(c.t->B, d.H, d.W) : d.h3 ? conv1x1_tiles_m(M) : conv_tiles_m((int)M, tile);
   float* psum = c.ws + c.t->off_part;
   float* psq = psum + (size_t)prows * d.Cout;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   const bool attach = fuse_tail || d.stem_h3 || d.h3;      // one kernel, launched through CAPNET_LAUNCH_TIMED
-  if (c.t->timing_now) {
-    const int rt = timing_begin(c.t, attach, c.s, &e0, &e1);
-    if (rt) return rt;
-  }
-  int rc;
-  if (fuse_tail) {
-    rc = conv1x1_fwd_tail(tail->y3, tail->s1, tail->t1, tail->res, tail->s2, tail->t2, tail->out,
-                          reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, c.train ? psum : nullptr,
-                          c.train ? psq : nullptr, M, d.Cin, d.Cout, c.s, c.in_exp(i), c.err);
-  } else if (d.stem_h3) {
-    CAPNET_REQUIRE(!in_scale && conv_stem_f16x3_eligible(x, sxb, sxc, sxh, sxw, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad),
-                   "trunk: the stem is planned for the split-f16 kernel but its operands are not eligible");
-    rc = conv_stem_fwd_f16x3(x, sxb, sxc, sxh, reinterpret_cast<const unsigned*>(c.w[i]), y, c.train ? psum : nullptr,
-                             c.train ? psq : nullptr, c.t->B, d.H, d.W, c.s, c.in_exp(i), c.err);
-  } else if (d.h3 && d.k == 3 && c.t->use_patch &&
-             conv3x3_patch_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, in_scale, in_shift)) {
-    // stride-1 3x3: the tile's input patch staged once instead of once per tap (conv3x3_patch.hip), same weight image
-    rc = conv3x3_fwd_patch(x, reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, in_scale, in_shift, relu_in,
-                           c.train ? psum : nullptr, c.train ? psq : nullptr, c.t->B, d.H, d.W, d.Cin, d.Cout, c.s,
-                           !c.t->tail_balance, c.in_exp(i), c.err);
-  } else if (d.h3 && d.k == 1 && d.stride == 1 && c.t->use_areg && sxc == 1 && sxw == d.Cin && sxh == (long)d.W * d.Cin &&
-             sxb == (long)d.H * d.W * d.Cin && conv1x1_areg_eligible(x, M, d.Cin, d.Cout, d.tile_n, in_scale, in_shift)) {
-    // short K (conv3 of stages 1-3): the A operand folded and split once per 128 rows, resident in registers
-    rc = conv1x1_fwd_areg(x, reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, in_scale, in_shift, relu_in,
-                          c.train ? psum : nullptr, c.train ? psq : nullptr, M, d.Cin, d.Cout, c.in_exp(i), c.s, c.err);
-  } else if (d.h3) {
-    CAPNET_REQUIRE(conv_f16x3_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, in_scale, in_shift),
-                   "trunk: conv %d planned for the split-f16 kernel but its operands are not eligible", i);
-    rc = conv_fwd_f16x3(x, sxb, sxh, sxw, reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, in_scale,
-                        in_shift, relu_in, c.train ? psum : nullptr, c.train ? psq : nullptr, c.t->B, d.H,
-                        d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, c.s, nullptr, nullptr, nullptr, 0, c.in_exp(i), c.err);
-  } else if (d.kmajor) {
-    CAPNET_REQUIRE(conv_v2_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.Cin, d.Cout, in_scale, in_shift),
-                   "trunk: conv %d planned for the K-major kernel but its operands are not eligible", i);
-    rc = conv2d_fwd_v2(x, sxb, sxh, sxw, c.w[i], d.Kw, y, in_scale, in_shift, relu_in,
-                       c.train ? psum : nullptr, c.train ? psq : nullptr, c.t->B, d.H, d.W, d.Cin,
-                       d.Cout, d.k, d.k, d.stride, d.pad, tile,
-                       c.t->tail_balance ? c.ws + c.t->off_slab : nullptr, c.s);
-  } else {
-    rc = conv2d_fwd(x, sxb, sxh, sxw, sxc, c.w[i], d.Kw, y, in_scale, in_shift, relu_in,
-                    c.train ? psum : nullptr, c.train ? psq : nullptr, c.t->B, d.H, d.W, d.Cin,
-                    d.Cout, d.k, d.k, d.stride, d.pad, tile, c.s);
-  }
-  if (c.t->timing_now) {
-    if (rc) launch_events() = LaunchEvents{};
-    else {
-      const int rt = timing_end(c.t, attach, c.s, e0, e1, 2.0 * (double)M * d.Cout * d.k * d.k * d.Cin);
-      if (rt) return rt;
+  const int rc = timed_launch(c.t, attach, c.s, trunk_conv_flops(c.t, i), [&]() -> int {
+    const unsigned* wimg = reinterpret_cast<const unsigned*>(c.w[i]);
+    float* ps = c.train ? psum : nullptr;
+    float* pq = c.train ? psq : nullptr;
+    if (fuse_tail)
+      return conv1x1_fwd_tail(tail->y3, tail->s1, tail->t1, tail->res, tail->s2, tail->t2, tail->out, wimg, d.tile_n, y, ps, pq, M,
+                              d.Cin, d.Cout, c.s, c.in_exp(i), c.err);
+    if (d.stem_h3) {
+      CAPNET_REQUIRE(!in_scale && conv_stem_f16x3_eligible(x, sxb, sxc, sxh, sxw, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad),
+                     "trunk: the stem is planned for the split-f16 kernel but its operands are not eligible");
+      return conv_stem_fwd_f16x3(x, sxb, sxc, sxh, wimg, y, ps, pq, c.t->B, d.H, d.W, c.s, c.in_exp(i), c.err);
     }
-  }
+    // stride-1 3x3: the tile's input patch staged once instead of once per tap (conv3x3_patch.hip), same weight image
+    if (d.h3 && d.k == 3 && c.t->use_patch &&
+        conv3x3_patch_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, in_scale, in_shift))
+      return conv3x3_fwd_patch(x, wimg, d.tile_n, y, in_scale, in_shift, relu_in, ps, pq, c.t->B, d.H, d.W, d.Cin, d.Cout, c.s,
+                               !c.t->tail_balance, c.in_exp(i), c.err);
+    // short K (conv3 of stages 1-3): the A operand folded and split once per 128 rows, resident in registers
+    if (d.h3 && d.k == 1 && d.stride == 1 && c.t->use_areg && sxc == 1 && sxw == d.Cin && sxh == (long)d.W * d.Cin &&
+        sxb == (long)d.H * d.W * d.Cin && conv1x1_areg_eligible(x, M, d.Cin, d.Cout, d.tile_n, in_scale, in_shift))
+      return conv1x1_fwd_areg(x, wimg, d.tile_n, y, in_scale, in_shift, relu_in, ps, pq, M, d.Cin, d.Cout, c.in_exp(i), c.s, c.err);
+    if (d.h3) {
+      CAPNET_REQUIRE(conv_f16x3_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, in_scale, in_shift),
+                     "trunk: conv %d planned for the split-f16 kernel but its operands are not eligible", i);
+      return conv_fwd_f16x3(x, sxb, sxh, sxw, wimg, d.tile_n, y, in_scale, in_shift, relu_in, ps, pq, c.t->B, d.H, d.W, d.Cin, d.Cout,
+                            d.k, d.stride, d.pad, c.s, nullptr, nullptr, nullptr, 0, c.in_exp(i), c.err);
+    }
+    if (d.kmajor) {
+      CAPNET_REQUIRE(conv_v2_eligible(x, sxb, sxh, sxw, sxc, c.t->B, d.Cin, d.Cout, in_scale, in_shift),
+                     "trunk: conv %d planned for the K-major kernel but its operands are not eligible", i);
+      return conv2d_fwd_v2(x, sxb, sxh, sxw, c.w[i], d.Kw, y, in_scale, in_shift, relu_in, ps, pq, c.t->B, d.H, d.W, d.Cin, d.Cout,
+                           d.k, d.k, d.stride, d.pad, tile, c.t->tail_balance ? c.ws + c.t->off_slab : nullptr, c.s);
+    }
+    return conv2d_fwd(x, sxb, sxh, sxw, sxc, c.w[i], d.Kw, y, in_scale, in_shift, relu_in, ps, pq, c.t->B, d.H, d.W, d.Cin, d.Cout,
+                      d.k, d.k, d.stride, d.pad, tile, c.s);
+  });
   if (rc) return rc;
-  if (c.train == 2)   // running statistics deferred to trunk_update_running
-    return bn_finalize(psum, psq, prows, d.Cout, M, c.gamma[i], c.beta[i],
-                       nullptr, nullptr, c.momentum, c.eps, c.scale(i), c.shift(i), c.s, c.bmean(i),
-                       c.bvar(i), c.err);
-  if (c.train)
-    return bn_finalize(psum, psq, prows, d.Cout, M, c.gamma[i], c.beta[i],
-                       c.rmean[i], c.rvar[i], c.momentum, c.eps, c.scale(i), c.shift(i), c.s, nullptr, nullptr, c.err);
+  if (c.train) return finalize_bn(c, i, psum, psq, prows, M);
   if (c.eval_ready) return kOk;
   return bn_eval_scale_shift(c.gamma[i], c.beta[i], c.rmean[i], c.rvar[i], c.eps, d.Cout,
                              c.scale(i), c.shift(i), c.s);
@@ -475,20 +496,14 @@ int fused_stats_bn(const Ctx& c, int i3, const float* y2, const float* s2, const
   const TrunkConv& d = c.t->convs[i3];
   const long M = (long)c.t->B * d.OH * d.OW;
   if (!c.train) return kOk;          // inference: every (scale, shift) is already there (eval_ready)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c.t->timing_now) {
-    const int rt = timing_begin(c.t, false, c.s, &e0, &e1);
-    if (rt) return rt;
-  }
   const bool defer = c.train == 2;
-  const int rc = fused_block_stats(y2, s2, t2, reinterpret_cast<const unsigned*>(c.w[i3]), M, d.Cin, c.in_exp(i3), c.gamma[i3],
-                                   c.beta[i3], defer ? nullptr : c.rmean[i3], defer ? nullptr : c.rvar[i3], c.momentum, c.eps,
-                                   c.scale(i3), c.shift(i3), defer ? c.bmean(i3) : nullptr, defer ? c.bvar(i3) : nullptr,
-                                   c.ws + c.t->off_gram, c.err, c.s);
-  if (rc) return rc;
   // (the statistics' launches are conv time without algorithmic flops: the product itself is timed with the fused launch)
-  if (c.t->timing_now) return timing_end(c.t, false, c.s, e0, e1, 0.0);
-  return kOk;
+  return timed_launch(c.t, false, c.s, 0.0, [&]() -> int {
+    return fused_block_stats(y2, s2, t2, reinterpret_cast<const unsigned*>(c.w[i3]), M, d.Cin, c.in_exp(i3), c.gamma[i3],
+                             c.beta[i3], defer ? nullptr : c.rmean[i3], defer ? nullptr : c.rvar[i3], c.momentum, c.eps,
+                             c.scale(i3), c.shift(i3), defer ? c.bmean(i3) : nullptr, defer ? c.bvar(i3) : nullptr,
+                             c.ws + c.t->off_gram, c.err, c.s);
+  });
 }
 // ... and its product, the block's tail and conv1 (i1) of block b + 1 are ONE launch
 struct FusedTail {
@@ -499,70 +514,38 @@ struct FusedTail {
 };
 int fused_conv1_bn(const Ctx& c, int i1, const FusedTail& f, float* y1) {
   const TrunkConv& d = c.t->convs[i1];
-  const TrunkConv& d3 = c.t->convs[f.i3];
   const long M = (long)c.t->B * d.OH * d.OW;
   const int prows = fused_block_tiles(M, d.Cout);
   float* psum = c.ws + c.t->off_part;
   float* psq = psum + (size_t)prows * d.Cout;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c.t->timing_now) {
-    const int rt = timing_begin(c.t, true, c.s, &e0, &e1);
-    if (rt) return rt;
-  }
-  const int rc = fused_block_forward(f.y2, f.s2, f.t2, reinterpret_cast<const unsigned*>(c.w[f.i3]), c.scale(f.i3), c.shift(f.i3),
-                                     f.res, f.sd, f.td, f.out, reinterpret_cast<const unsigned*>(c.w[i1]), y1,
-                                     c.train ? psum : nullptr, c.train ? psq : nullptr, M, d.Cout, c.in_exp(f.i3), c.in_exp(i1),
-                                     c.err, c.s);
-  if (c.t->timing_now) {
-    if (rc) launch_events() = LaunchEvents{};
-    else {
-      const int rt = timing_end(c.t, true, c.s, e0, e1, 2.0 * (double)M * d.Cout * d.Cin + 2.0 * (double)M * d3.Cout * d3.Cin);
-      if (rt) return rt;
-    }
-  }
+  // (one launch does the work of two convolutions: this conv1 and the previous block's conv3)
+  const int rc = timed_launch(c.t, true, c.s, trunk_conv_flops(c.t, i1) + trunk_conv_flops(c.t, f.i3), [&]() -> int {
+    return fused_block_forward(f.y2, f.s2, f.t2, reinterpret_cast<const unsigned*>(c.w[f.i3]), c.scale(f.i3), c.shift(f.i3),
+                               f.res, f.sd, f.td, f.out, reinterpret_cast<const unsigned*>(c.w[i1]), y1,
+                               c.train ? psum : nullptr, c.train ? psq : nullptr, M, d.Cout, c.in_exp(f.i3), c.in_exp(i1),
+                               c.err, c.s);
+  });
   if (rc) return rc;
-  if (c.train == 2)
-    return bn_finalize(psum, psq, prows, d.Cout, M, c.gamma[i1], c.beta[i1], nullptr, nullptr, c.momentum, c.eps, c.scale(i1),
-                       c.shift(i1), c.s, c.bmean(i1), c.bvar(i1), c.err);
-  if (c.train)
-    return bn_finalize(psum, psq, prows, d.Cout, M, c.gamma[i1], c.beta[i1], c.rmean[i1], c.rvar[i1], c.momentum, c.eps,
-                       c.scale(i1), c.shift(i1), c.s, nullptr, nullptr, c.err);
-  return kOk;
+  return c.train ? finalize_bn(c, i1, psum, psq, prows, M) : kOk;
 }
 
 // conv i with the BatchNorm that follows it folded into the epilogue (inference)
 int conv_folded(const Ctx& c, int i, const float* x, const float* res, int relu, float* y) {
   const TrunkConv& d = c.t->convs[i];
-  const long M = (long)c.t->B * d.OH * d.OW;
   const long sw = d.Cin, sh = (long)d.W * d.Cin, sb = (long)d.H * d.W * d.Cin;
   CAPNET_REQUIRE(d.tile_n != 256 && !d.fused3 && !d.fused1, "trunk: conv %d was planned for the wide tail kernel or for fused_block.hip; CAPNET_EVAL_FOLDED=1 must be set before the plan is made", i);
   CAPNET_REQUIRE(d.h3 || (d.kmajor && conv_v2_eligible(x, sb, sh, sw, 1, c.t->B, d.Cin, d.Cout, nullptr, nullptr)),
                  "trunk: conv %d is not eligible for the folded-BN kernel", i);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const bool attach = d.h3;
-  if (c.t->timing_now) {
-    const int rt = timing_begin(c.t, attach, c.s, &e0, &e1);
-    if (rt) return rt;
-  }
-  int rc;
-  if (d.h3) {
-    rc = conv_fwd_f16x3(x, sb, sh, sw, reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, nullptr, nullptr,
-                        0, nullptr, nullptr, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, c.s, c.scale(i),
-                        c.shift(i), res, relu, c.in_exp(i), c.err);
-  } else {
-    rc = conv2d_fwd_v2(x, sb, sh, sw, c.w[i], d.Kw, y, nullptr, nullptr, 0, nullptr, nullptr,
-                       c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.k, d.stride, d.pad, 0,
-                       c.t->tail_balance ? c.ws + c.t->off_slab : nullptr, c.s, c.scale(i),
-                       c.shift(i), res, relu);
-  }
-  if (c.t->timing_now) {
-    if (rc) launch_events() = LaunchEvents{};
-    else {
-      const int rt = timing_end(c.t, attach, c.s, e0, e1, 2.0 * (double)M * d.Cout * d.k * d.k * d.Cin);
-      if (rt) return rt;
-    }
-  }
-  return rc;
+  return timed_launch(c.t, d.h3, c.s, trunk_conv_flops(c.t, i), [&]() -> int {
+    if (d.h3)
+      return conv_fwd_f16x3(x, sb, sh, sw, reinterpret_cast<const unsigned*>(c.w[i]), d.tile_n, y, nullptr, nullptr,
+                            0, nullptr, nullptr, c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.stride, d.pad, c.s, c.scale(i),
+                            c.shift(i), res, relu, c.in_exp(i), c.err);
+    return conv2d_fwd_v2(x, sb, sh, sw, c.w[i], d.Kw, y, nullptr, nullptr, 0, nullptr, nullptr,
+                         c.t->B, d.H, d.W, d.Cin, d.Cout, d.k, d.k, d.stride, d.pad, 0,
+                         c.t->tail_balance ? c.ws + c.t->off_slab : nullptr, c.s, c.scale(i),
+                         c.shift(i), res, relu);
+  });
 }
 
 // Inference trunk (encoder.eval(): validation, sample()): every BatchNorm uses its running
@@ -578,20 +561,8 @@ int trunk_forward_eval(const Ctx& c, const float* images_nchw, float* out_pooled
   float* Y2 = ws + t->off_y2;
   float* Y3 = ws + t->off_y3;
   float* D = ws + t->off_d;
-  const int n = (int)t->convs.size();
-  {
-    std::vector<const float*> g(n), b(n), rm(n), rv(n);
-    std::vector<float*> sc(n), sh(n);
-    std::vector<int> C(n);
-    for (int i = 0; i < n; ++i) {
-      g[i] = c.gamma[i]; b[i] = c.beta[i]; rm[i] = c.rmean[i]; rv[i] = c.rvar[i];
-      sc[i] = c.scale(i); sh[i] = c.shift(i); C[i] = t->convs[i].Cout;
-    }
-    int rc = bn_eval_multi(n, g.data(), b.data(), rm.data(), rv.data(), C.data(), sc.data(), sh.data(),
-                           c.eps, c.s);
-    if (rc) return rc;
-  }
-  int rc;
+  int rc = eval_scale_shift_all(c);
+  if (rc) return rc;
   {
     // stem: the gather-loader kernel writes the raw conv, BN + ReLU ride on the max-pool
     const TrunkConv& d = t->convs[0];
@@ -607,29 +578,23 @@ int trunk_forward_eval(const Ctx& c, const float* images_nchw, float* out_pooled
     rc = bn_relu_maxpool(Y3, c.scale(0), c.shift(0), X[0], B, d.OH, d.OW, 64, c.s);
     if (rc) return rc;
   }
-  int ci = 1, cur = 0;
-  const int blocks[4] = {3, 8, 36, 3};
-  for (int L = 0; L < 4; ++L) {
-    for (int bk = 0; bk < blocks[L]; ++bk) {
-      const int i1 = ci, i2 = ci + 1, i3 = ci + 2;
-      const int id = (bk == 0) ? ci + 3 : -1;
-      ci += (bk == 0) ? 4 : 3;
-      const float* x = X[cur];
-      float* out = X[cur ^ 1];
-      rc = conv_folded(c, i1, x, nullptr, 1, Y1);
+  int cur = 0;
+  for (const TrunkBlock& blk : t->blocks) {
+    const float* x = X[cur];
+    float* out = X[cur ^ 1];
+    rc = conv_folded(c, blk.i1, x, nullptr, 1, Y1);
+    if (rc) return rc;
+    rc = conv_folded(c, blk.i2, Y1, nullptr, 1, Y2);
+    if (rc) return rc;
+    const float* res = x;
+    if (blk.id >= 0) {
+      rc = conv_folded(c, blk.id, x, nullptr, 0, D);
       if (rc) return rc;
-      rc = conv_folded(c, i2, Y1, nullptr, 1, Y2);
-      if (rc) return rc;
-      const float* res = x;
-      if (id >= 0) {
-        rc = conv_folded(c, id, x, nullptr, 0, D);
-        if (rc) return rc;
-        res = D;
-      }
-      rc = conv_folded(c, i3, Y2, res, 1, out);
-      if (rc) return rc;
-      cur ^= 1;
+      res = D;
     }
+    rc = conv_folded(c, blk.i3, Y2, res, 1, out);
+    if (rc) return rc;
+    cur ^= 1;
   }
   const int side = t->final_side;
   if (out_pooled) {
@@ -679,7 +644,6 @@ int trunk_forward(Trunk* t, const float* images_nchw, const float* const* w_pack
   float* Y3 = workspace + t->off_y3;
   float* D = workspace + t->off_d;
   int rc;
-  int ci = 0;
   // Inference. CAPNET_EVAL_FOLDED=1: the convolutions' epilogues apply the BatchNorms (+ residual + ReLU): the least
   // traffic, but that epilogue of the split-f16 kernel is slow (12.3 ms per pass at B = 64). Default: the training
   // pass's kernels with every (scale, shift) computed up front from the running statistics -- no statistics, no
@@ -687,15 +651,7 @@ int trunk_forward(Trunk* t, const float* images_nchw, const float* const* w_pack
   if (!train) {
     const char* fe = getenv("CAPNET_EVAL_FOLDED");      // (read per call: the tests run both paths in one process)
     if (fe && fe[0] == '1') return trunk_forward_eval(c, images_nchw, out_pooled, out_map);
-    const int n = (int)t->convs.size();
-    std::vector<const float*> g(n), b(n), rm(n), rv(n);
-    std::vector<float*> sc(n), sh(n);
-    std::vector<int> Cs(n);
-    for (int i = 0; i < n; ++i) {
-      g[i] = c.gamma[i]; b[i] = c.beta[i]; rm[i] = c.rmean[i]; rv[i] = c.rvar[i];
-      sc[i] = c.scale(i); sh[i] = c.shift(i); Cs[i] = t->convs[i].Cout;
-    }
-    rc = bn_eval_multi(n, g.data(), b.data(), rm.data(), rv.data(), Cs.data(), sc.data(), sh.data(), c.eps, c.s);
+    rc = eval_scale_shift_all(c);
     if (rc) return rc;
     c.eval_ready = true;
   }
@@ -707,76 +663,70 @@ int trunk_forward(Trunk* t, const float* images_nchw, const float* const* w_pack
     if (rc) return rc;
     rc = bn_relu_maxpool(Y3, c.scale(0), c.shift(0), X[0], B, d.OH, d.OW, 64, stream);
     if (rc) return rc;
-    ci = 1;
   }
   int cur = 0;
   BlockTail tail{};
   FusedTail ftail{};
   bool have_tail = false, have_ftail = false;
-  const int blocks[4] = {3, 8, 36, 3};
-  for (int L = 0; L < 4; ++L) {
-    for (int b = 0; b < blocks[L]; ++b) {
-      const int i1 = ci, i2 = ci + 1, i3 = ci + 2;
-      const int id = (b == 0) ? ci + 3 : -1;
-      ci += (b == 0) ? 4 : 3;
-      const TrunkConv& c1 = t->convs[i1];
-      const TrunkConv& c2 = t->convs[i2];
-      const TrunkConv& c3 = t->convs[i3];
-      const float* x = X[cur];
-      float* out = X[cur ^ 1];
-      auto nhwc = [](const TrunkConv& d, long* sb, long* sh, long* sw) {
-        *sw = d.Cin; *sh = (long)d.W * d.Cin; *sb = (long)d.H * d.W * d.Cin;
-      };
-      long sb, sh, sw;
-      nhwc(c1, &sb, &sh, &sw);
-      if (have_ftail) {
-        // the previous block's conv3 product, its tail (-> x = X[cur]) and this conv1: one launch (fused_block.hip)
-        CAPNET_REQUIRE(c1.fused1 && (c.train || c.eval_ready), "trunk: conv %d is not the fused boundary the plan made", i1);
-        rc = fused_conv1_bn(c, i1, ftail, Y1);
-        have_ftail = false;
-      } else {
-        CAPNET_REQUIRE(!c1.fused1, "trunk: conv %d was planned for fused_block.hip", i1);
-        rc = conv_bn(c, i1, x, sb, sh, sw, 1, nullptr, nullptr, 0, Y1, have_tail ? &tail : nullptr);
-      }
-      have_tail = false;
-      if (rc) return rc;
-      nhwc(c2, &sb, &sh, &sw);
-      rc = conv_bn(c, i2, Y1, sb, sh, sw, 1, c.scale(i1), c.shift(i1), 1, Y2);
-      if (rc) return rc;
-      const long rows = (long)B * c3.OH * c3.OW;
-      if (c3.fused3 && (c.train || c.eval_ready)) {
-        // y3 is never formed: statistics from y2's second moments now, the product inside the next block's conv1 launch
-        rc = fused_stats_bn(c, i3, Y2, c.scale(i2), c.shift(i2));
-        if (rc) return rc;
-        if (id >= 0) {
-          const TrunkConv& cd = t->convs[id];
-          nhwc(cd, &sb, &sh, &sw);
-          rc = conv_bn(c, id, x, sb, sh, sw, 1, nullptr, nullptr, 0, D);
-          if (rc) return rc;
-          ftail = FusedTail{i3, Y2, c.scale(i2), c.shift(i2), D, c.scale(id), c.shift(id), out};
-        } else {
-          ftail = FusedTail{i3, Y2, c.scale(i2), c.shift(i2), x, nullptr, nullptr, out};
-        }
-        have_ftail = true;
-        cur ^= 1;
-        continue;
-      }
-      CAPNET_REQUIRE(!c3.fused3, "trunk: conv %d was planned for fused_block.hip (the folded inference trunk must be chosen before the plan is made)", i3);
-      nhwc(c3, &sb, &sh, &sw);
-      rc = conv_bn(c, i3, Y2, sb, sh, sw, 1, c.scale(i2), c.shift(i2), 1, Y3);
+  for (const TrunkBlock& blk : t->blocks) {
+    const int i1 = blk.i1, i2 = blk.i2, i3 = blk.i3, id = blk.id;
+    const TrunkConv& c1 = t->convs[i1];
+    const TrunkConv& c2 = t->convs[i2];
+    const TrunkConv& c3 = t->convs[i3];
+    const float* x = X[cur];
+    float* out = X[cur ^ 1];
+    auto nhwc = [](const TrunkConv& d, long* sb, long* sh, long* sw) {
+      *sw = d.Cin; *sh = (long)d.W * d.Cin; *sb = (long)d.H * d.W * d.Cin;
+    };
+    long sb, sh, sw;
+    nhwc(c1, &sb, &sh, &sw);
+    if (have_ftail) {
+      // the previous block's conv3 product, its tail (-> x = X[cur]) and this conv1: one launch (fused_block.hip)
+      CAPNET_REQUIRE(c1.fused1 && (c.train || c.eval_ready), "trunk: conv %d is not the fused boundary the plan made", i1);
+      rc = fused_conv1_bn(c, i1, ftail, Y1);
+      have_ftail = false;
+    } else {
+      CAPNET_REQUIRE(!c1.fused1, "trunk: conv %d was planned for fused_block.hip", i1);
+      rc = conv_bn(c, i1, x, sb, sh, sw, 1, nullptr, nullptr, 0, Y1, have_tail ? &tail : nullptr);
+    }
+    have_tail = false;
+    if (rc) return rc;
+    nhwc(c2, &sb, &sh, &sw);
+    rc = conv_bn(c, i2, Y1, sb, sh, sw, 1, c.scale(i1), c.shift(i1), 1, Y2);
+    if (rc) return rc;
+    const long rows = (long)B * c3.OH * c3.OW;
+    if (c3.fused3 && (c.train || c.eval_ready)) {
+      // y3 is never formed: statistics from y2's second moments now, the product inside the next block's conv1 launch
+      rc = fused_stats_bn(c, i3, Y2, c.scale(i2), c.shift(i2));
       if (rc) return rc;
       if (id >= 0) {
         const TrunkConv& cd = t->convs[id];
         nhwc(cd, &sb, &sh, &sw);
         rc = conv_bn(c, id, x, sb, sh, sw, 1, nullptr, nullptr, 0, D);
         if (rc) return rc;
-        tail = BlockTail{Y3, c.scale(i3), c.shift(i3), D, c.scale(id), c.shift(id), out, rows, c3.Cout};
+        ftail = FusedTail{i3, Y2, c.scale(i2), c.shift(i2), D, c.scale(id), c.shift(id), out};
       } else {
-        tail = BlockTail{Y3, c.scale(i3), c.shift(i3), x, nullptr, nullptr, out, rows, c3.Cout};
+        ftail = FusedTail{i3, Y2, c.scale(i2), c.shift(i2), x, nullptr, nullptr, out};
       }
-      have_tail = true;      // runs inside the next block's conv1 (conv_bn), or below after the last block
+      have_ftail = true;
       cur ^= 1;
+      continue;
     }
+    CAPNET_REQUIRE(!c3.fused3, "trunk: conv %d was planned for fused_block.hip (the folded inference trunk must be chosen before the plan is made)", i3);
+    nhwc(c3, &sb, &sh, &sw);
+    rc = conv_bn(c, i3, Y2, sb, sh, sw, 1, c.scale(i2), c.shift(i2), 1, Y3);
+    if (rc) return rc;
+    if (id >= 0) {
+      const TrunkConv& cd = t->convs[id];
+      nhwc(cd, &sb, &sh, &sw);
+      rc = conv_bn(c, id, x, sb, sh, sw, 1, nullptr, nullptr, 0, D);
+      if (rc) return rc;
+      tail = BlockTail{Y3, c.scale(i3), c.shift(i3), D, c.scale(id), c.shift(id), out, rows, c3.Cout};
+    } else {
+      tail = BlockTail{Y3, c.scale(i3), c.shift(i3), x, nullptr, nullptr, out, rows, c3.Cout};
+    }
+    have_tail = true;      // runs inside the next block's conv1 (conv_bn), or below after the last block
+    cur ^= 1;
   }
   if (have_tail) {
     rc = run_tail(c, tail);
