@@ -1,0 +1,180 @@
+"""What the decoders' inference paths share: the beam-search front end, the attention beam step and its set-up, the
+composed factored cell, and the stepper of a stacked decoder. The decoder classes keep what is theirs: which modules a
+mode selects, the layout of their beam state, their weight fold.
+
+  * beam_decode: the one caller of capnet.beam's two loops. Every class builds (step_fn, initial state) in one private
+    `_beam` method; its sample() asks for one group of k beams, its sample_batch() for n groups.
+  * attend: Attention.forward, the single step outside a beam search.
+  * att_beam_start / att_beam_step: an attention decoder's beam search. The set-up (encoder_att once per image, the
+    initial state) is written once for one image and once for n; the step (z = [decoder_att; f_beta](h), the embedding
+    into xa, ops.attention_step, then the caller's cell, upper layers and vocabulary projection) once.
+  * factored_step: U_g(S_g(V_g(x))) + W_g(h) per gate and the pointwise cell, on torch.cat. DecoderFactoredLSTM's own
+    forward_step accumulates into column blocks instead and stays where it is.
+  * stack_stepper / cell_stepper / pack_cell / as_state / input_width: one step of a stack over a [rows, 2L, H] state
+    (slot 2l = h of layer l, 2l+1 = its c), on capnet_stacked_decode_step or composed. CAPNET_NO_FUSED_DECODE_STEP=1
+    (read here, at every stepper built) takes the composed step, which also serves the shapes the kernel does not take.
+"""
+import os
+
+import torch
+
+from . import ops
+from .beam import beam_search, beam_search_batched
+
+FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
+_GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torch's i, f, g, o
+
+
+# ---- beam search ------------------------------------------------------------------------------------
+def beam_decode(dec, step_fn, state, n, k, start_token, end_token):
+    """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
+    i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
+    together (beam_search_batched) -> a list of n token lists."""
+    dev = state[0].device
+    with torch.no_grad():
+        if n is None:
+            return beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
+        return beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
+
+
+def zero_state(rows, H, device):
+    """(h, c) [rows, H] of a single-layer decoder whose beams start at zero."""
+    zeros = torch.zeros(rows, H, dtype=torch.float32, device=device)
+    return zeros, zeros.clone()
+
+
+# ---- attention --------------------------------------------------------------------------------------
+@torch.no_grad()
+def attend(attention, encoder_out, decoder_hidden):
+    """Attention.forward: one step for s rows on their own maps -> (attention-weighted encoding [s, C], alpha [s, P])."""
+    s_rows, P, Cdim = encoder_out.shape
+    A = attention.encoder_att.weight.shape[0]
+    att1 = attention.encoder_att(encoder_out.reshape(s_rows * P, Cdim)).reshape(s_rows, P, A)
+    z = torch.zeros((s_rows, A + Cdim), dtype=torch.float32, device=encoder_out.device)
+    z[:, :A] = attention.decoder_att(decoder_hidden)
+    return ops.attention_step(att1.contiguous(), encoder_out.contiguous(), z, A, attention.full_att.weight,
+                              attention.full_att.bias)
+
+
+def att_beam_start(dec, attention, features, n, k):
+    """The set-up of an attention beam search -> (feat, att1_of, feat_of, h0, c0, img). encoder_att(features) is computed
+    once per image (the reference recomputes it for every beam and step); att1_of / feat_of (state, rows) give a step the
+    map rows of its live beams.
+    n None: `features` is the map of ONE image ([1, S, S, C] or [1, P, C]); feat [k, P, C] holds it k times, so
+    re-indexing by beam (model_att.py:413) is a slice; h0, c0 [k, H]; img None.
+    Else n images ([n, S, S, C] or [n, P, C]): feat [n, P, C]; a beam's rows are gathered by its image index, the LAST
+    entry of the beam state; h0, c0 [n k, H]; img [n k]."""
+    dev = attention.encoder_att.weight.device
+    A, Cdim = dec.attention_size, features.size(-1)
+    if n is None:
+        feat1 = features.reshape(1, -1, Cdim).to(dev).contiguous()
+        P = feat1.size(1)
+        feat = feat1.expand(k, P, Cdim).contiguous()
+        att1 = attention.encoder_att(feat1[0]).reshape(1, P, A).expand(k, P, A).contiguous()
+        h0, c0 = dec.init_hidden_state(feat)
+        return feat, lambda st, r: att1[:r], lambda st, r: feat[:r], h0, c0, None
+    feat = features.reshape(n, -1, Cdim).to(dev).contiguous()
+    P = feat.size(1)
+    att1 = attention.encoder_att(feat.reshape(n * P, Cdim)).reshape(n, P, A).contiguous()
+    h0, c0 = dec.init_hidden_state(feat)
+    img = torch.arange(n, device=dev).repeat_interleave(k)
+    h0, c0 = h0.index_select(0, img).contiguous(), c0.index_select(0, img).contiguous()
+    return feat, lambda st, r: att1.index_select(0, st[-1]), lambda st, r: feat.index_select(0, st[-1]), h0, c0, img
+
+
+def att_beam_step(attention, f_beta, embed, cell, project, att1_of, feat_of, n_att, upper=None):
+    """step_fn of an attention beam search over the state (h, c, *rest) of layer 0 and whatever follows it.
+    cell(xa, (h, c)) -> (h, c) is layer 0 on xa = [embedding | gated context]; project(top h) -> logits.
+    upper() -> step(h, rest) -> (top h, the layers' new entries): the layers above, whose entries lead `rest`; what
+    follows them (the image index) is carried over. It is called here, after [decoder_att ; f_beta] is stacked, so a
+    stepper that packs weights launches where it always did."""
+    E, A, dev = embed.weight.shape[1], attention.decoder_att.weight.shape[0], embed.weight.device
+    # [decoder_att ; f_beta] stacked: one product with h per step
+    wz = torch.cat([attention.decoder_att.weight, f_beta.weight], 0).contiguous()
+    bz = torch.cat([attention.decoder_att.bias, f_beta.bias], 0).contiguous()
+    upper_step = upper() if upper is not None else (lambda h, rest: (h, ()))
+
+    def step_fn(prev_words, state):
+        h, c, rest = state[0], state[1], tuple(state[2:])
+        s_rows = h.shape[0]
+        z = ops.linear(h, wz, bz).contiguous()
+        xa = torch.empty((s_rows, E + n_att), dtype=torch.float32, device=dev)
+        xa[:, :E] = embed(prev_words)
+        ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
+                           attention.full_att.bias, xa=xa, xa_col=E)
+        h, c = cell(xa, (h, c))
+        top, new = upper_step(h, rest)
+        return project(top), (h, c) + tuple(new) + rest[len(new):]
+    return step_fn
+
+
+# ---- cells ------------------------------------------------------------------------------------------
+def factored_step(V, S, U, W, x, h, c):
+    """One factored-LSTM step at inference -> (h, c): V, S, U, W are the four gates' Linears (i, f, o, c~)."""
+    pre = torch.cat([U[k](S[k](V[k](x))) + W[k](h) for k in range(4)], 1)
+    return ops.lstm_pointwise(pre, c, ops.CELL_FACTORED)
+
+
+def input_width(n_in):
+    """A layer's input width as capnet_stacked_decode_step reads it: rounded up to 16."""
+    return (n_in + 15) // 16 * 16
+
+
+def pack_cell(cell, kin):
+    """(wcat [4H, kin + H] = [weight_ih, zero columns up to kin | weight_hh], beff [4H] = bias_ih + bias_hh), gate
+    blocks reordered for capnet_stacked_decode_step_cell."""
+    H, n_in = cell.hidden_size, cell.input_size
+    dev = cell.weight_ih.device
+    wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
+    beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for dst, src in enumerate(_GATE_BLOCKS):
+            rows, srows = slice(dst * H, (dst + 1) * H), slice(src * H, (src + 1) * H)
+            wcat[rows, :n_in].copy_(cell.weight_ih[srows])
+            wcat[rows, kin:].copy_(cell.weight_hh[srows])
+            torch.add(cell.bias_ih[srows], cell.bias_hh[srows], out=beff[rows])
+    return wcat, beff
+
+
+def pack_cells(cells, E):
+    """[pack_cell] of every layer of a stack of LSTMCells whose first reads E columns."""
+    return [pack_cell(c, input_width(E) if l == 0 else c.hidden_size) for l, c in enumerate(cells)]
+
+
+# ---- stacks -----------------------------------------------------------------------------------------
+def as_state(states):
+    """A [rows, 2L, H] state from a tensor of that shape or a sequence of L (h, c) pairs."""
+    if isinstance(states, torch.Tensor):
+        return states
+    return torch.stack([t for hc in states for t in hc], 1)
+
+
+def stack_stepper(num_layers, E, H, cell, pack, composed):
+    """step(x, tokens, state [rows, 2L, H]) -> (top h [rows, H], state') of a stack of `num_layers` cells of kind `cell`,
+    the first reading E columns: x is the embedding table when `tokens` is given, else layer 0's inputs. The fused step
+    on pack() -> [(wcat, beff)] per layer, called here, once, unless CAPNET_NO_FUSED_DECODE_STEP=1 or the shape is one the
+    kernel does not take: then composed(x, state) -> (top h, state')."""
+    if (os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and num_layers <= 8 and ops.stacked_decode_supported(E, H)):
+        packed = pack()
+        wcat, beff = [w for w, _ in packed], [b for _, b in packed]
+
+        def step(x, tokens, state):
+            return ops.stacked_decode_step(state, wcat, beff, x, tokens, cell=cell)
+    else:
+        def step(x, tokens, state):
+            if tokens is not None:
+                x = ops.embedding(tokens, x)
+            return composed(x, state)
+    return step
+
+
+def cell_stepper(cells, E, H):
+    """stack_stepper over `cells` (L LSTMCells, the first reading E columns)."""
+    def composed(x, state):
+        new = torch.empty_like(state)
+        for l, c in enumerate(cells):
+            h, cc = c(x, (state[:, 2 * l].contiguous(), state[:, 2 * l + 1].contiguous()))
+            new[:, 2 * l], new[:, 2 * l + 1] = h, cc
+            x = h
+        return x, new
+    return stack_stepper(len(cells), E, H, ops.CELL_LSTM, lambda: pack_cells(cells, E), composed)

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr, ptr_array
+from .decode import beam_decode, zero_state
 
 random.seed(0)  # stylenet/model.py:7
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # stylenet/model.py:8
@@ -495,7 +496,28 @@ def _dropout_seed(training, p):
     return 0
 
 
+def _seq_cfg(dec, batch_sizes, p, tf_mask, teacher_forcing_ratio, **extra):
+    """The cfg dict of ops.SeqFn / ops.AttSeqFn for decoder `dec` with dropout p, `extra` being the keys of its class.
+    Consumes `random` first (one draw per step unless tf_mask is given), then torch's generator (_dropout_seed)."""
+    cfg = {"batch_sizes": batch_sizes,
+           "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
+           "hidden_size": dec.hidden_size,
+           "dropout": p if dec.training else 0.0,
+           "seed": _dropout_seed(dec.training, p),
+           "training": dec.training}
+    cfg.update(extra)
+    return cfg
+
+
 _MODES = ("factual", "happy", "sad", "angry")
+_S_PREFIX = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}
+
+
+def _layer_mods(dec, tag, mode):
+    """(V, S, U, W) of one factored layer of `dec`, each the four gates' Linears in the order i, f, o, c: V{tag}_g,
+    S{tag}_f{g} or S{tag}_{mode}_{g}, U{tag}_g, W{tag}_g. tag: "" for layer 0, the layer's number above it."""
+    return tuple([getattr(dec, "%s%s_%s%s" % (name, tag, _S_PREFIX[mode] if name == "S" else "", g)) for g in "ifoc"]
+                 for name in "VSUW")
 
 
 class DecoderFactoredLSTM(nn.Module):
@@ -602,50 +624,29 @@ class DecoderFactoredLSTM(nn.Module):
         are drawn from the global `random` module, one per step, as the reference does."""
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
         weights = self._weights(mode)
-        cfg = {
-            "batch_sizes": batch_sizes,
-            "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
-            "hidden_size": self.hidden_size,
-            "factored_size": self.factored_size,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-        }
+        cfg = _seq_cfg(self, batch_sizes, self.dropout.p, tf_mask, teacher_forcing_ratio, factored_size=self.factored_size)
         hiddens = ops.SeqFn.apply(cfg, captions, features, self.B.weight, self.C.weight, self.C.bias, *weights)
         outputs = self.C(hiddens)
         return outputs
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
-        """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
-        an input of the decode steps (the first input is B(<start>) and the state starts at zero):
-        `features` only fixes the device. Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        dev = self.B.weight.device
+    def _beam(self, rows, mode):
+        """(step_fn, the zero state of `rows` beams) of a beam search."""
         self._S(mode)   # validates the mode before any launch
 
         def step_fn(prev_words, state):
             hidden, (h, c) = self.forward_step(self.B(prev_words), state, mode=mode)
             return self.C(hidden), (h, c)
+        return step_fn, zero_state(rows, self.hidden_size, self.B.weight.device)
 
-        with torch.no_grad():
-            zeros = torch.zeros(k, self.hidden_size, dtype=torch.float32, device=dev)
-            return beam_search(step_fn, (zeros, zeros.clone()), self.vocab_size, start_token,
-                               end_token, k, self.max_seq_length, dev)
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+        """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
+        an input of the decode steps (the first input is B(<start>) and the state starts at zero):
+        `features` only fixes the device. Returns LongTensor [1, L]."""
+        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched): what the reference's test-set
         evaluator does image by image (stylenet/evaluator.py:76-84). Returns a list of token lists, each equal to
         sample(features[i:i+1], ...)[0].tolist()."""
-        from .beam import beam_search_batched
-        dev = self.B.weight.device
-        self._S(mode)
         n = features.size(0)
-
-        def step_fn(prev_words, state):
-            hidden, (h, c) = self.forward_step(self.B(prev_words), state, mode=mode)
-            return self.C(hidden), (h, c)
-
-        with torch.no_grad():
-            zeros = torch.zeros(n * k, self.hidden_size, dtype=torch.float32, device=dev)
-            return beam_search_batched(step_fn, (zeros, zeros.clone()), n, self.vocab_size, start_token, end_token, k,
-                                       self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token)

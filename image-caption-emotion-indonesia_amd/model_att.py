@@ -12,8 +12,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr
-from .model import (Dropout, Embedding, Linear, _Marker, _MODES, _TrunkRunner, _dropout_seed,
-                    _resnet152_children, _resolve_tf_mask)
+from .decode import att_beam_start, att_beam_step, attend, beam_decode, factored_step
+from .model import Dropout, Embedding, Linear, _Marker, _MODES, _TrunkRunner, _resnet152_children, _seq_cfg
 
 
 class EncoderCNN(nn.Module):
@@ -76,14 +76,7 @@ class Attention(nn.Module):
     def forward(self, encoder_out, decoder_hidden):
         """(attention-weighted encoding [s, C], alpha [s, P]) -- stylenet/model_att.py:51-70.
         Inference-only entry (no autograd); training goes through the fused sequence kernels."""
-        with torch.no_grad():
-            s_rows, P, Cdim = encoder_out.shape
-            A = self.encoder_att.weight.shape[0]
-            att1 = self.encoder_att(encoder_out.reshape(s_rows * P, Cdim)).reshape(s_rows, P, A)
-            z = torch.zeros((s_rows, A + Cdim), dtype=torch.float32, device=encoder_out.device)
-            z[:, :A] = self.decoder_att(decoder_hidden)
-            return ops.attention_step(att1.contiguous(), encoder_out.contiguous(), z, A,
-                                      self.full_att.weight, self.full_att.bias)
+        return attend(self, encoder_out, decoder_hidden)
 
 
 class DecoderFactoredLSTMAtt(nn.Module):
@@ -183,77 +176,35 @@ class DecoderFactoredLSTMAtt(nn.Module):
         V = [getattr(self, "V_" + g) for g in "ifoc"]
         U = [getattr(self, "U_" + g) for g in "ifoc"]
         W = [getattr(self, "W_" + g) for g in "ifoc"]
-        pre = torch.cat([U[k](S[k](V[k](embedded))) + W[k](h_t) for k in range(4)], 1)
-        h_t, c_t = ops.lstm_pointwise(pre, c_t, ops.CELL_FACTORED)
+        h_t, c_t = factored_step(V, S, U, W, embedded, h_t, c_t)
         return h_t, (h_t, c_t)
+
+    def _upper_beam(self, feat, img, mode):
+        """(the beam state's entries after layer 0's (h0, c0), att_beam_step's `upper`). One layer here."""
+        return (), None
+
+    @torch.no_grad()
+    def _beam(self, features, n, k, mode):
+        """(step_fn, initial state) of a beam search over one image (n None) or n images: the state is layer 0's (h, c),
+        then what _upper_beam adds, then (n images) every beam's image index."""
+        attention, _ = self._mode_modules(mode)
+        feat, att1_of, feat_of, h0, c0, img = att_beam_start(self, attention, features, n, k)
+        state, upper = self._upper_beam(feat, img, mode)
+        step_fn = att_beam_step(attention, self.f_beta, self.B, lambda xa, hc: self.forward_step(xa, hc, mode=mode)[1],
+                                self.C, att1_of, feat_of, features.size(-1), upper)
+        return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
-        of ONE image ([1, S, S, C] or [1, P, C]). encoder_att(features) is computed once (the
-        reference recomputes it for every beam and step). Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        dev = self.B.weight.device
-        attention, _ = self._mode_modules(mode)
-        E, A, Cdim = self.embed_size, self.attention_size, features.size(-1)
-        with torch.no_grad():
-            feat1 = features.reshape(1, -1, Cdim).to(dev).contiguous()
-            P = feat1.size(1)
-            feat_k = feat1.expand(k, P, Cdim).contiguous()
-            att1_k = attention.encoder_att(feat1[0]).reshape(1, P, A).expand(k, P, A).contiguous()
-            h0, c0 = self.init_hidden_state(feat_k)
-            # [decoder_att ; f_beta] stacked: one product with h per step
-            wz = torch.cat([attention.decoder_att.weight, self.f_beta.weight], 0).contiguous()
-            bz = torch.cat([attention.decoder_att.bias, self.f_beta.bias], 0).contiguous()
-
-            def step_fn(prev_words, state):
-                h, c = state
-                s_rows = h.shape[0]
-                z = ops.linear(h, wz, bz).contiguous()
-                xa = torch.empty((s_rows, E + Cdim), dtype=torch.float32, device=dev)
-                xa[:, :E] = self.B(prev_words)
-                # all beams look at the same image: rows of feat_k / att1_k are identical, so
-                # re-indexing them (model_att.py:413) is a slice
-                ops.attention_step(att1_k[:s_rows], feat_k[:s_rows], z, A, attention.full_att.weight,
-                                   attention.full_att.bias, xa=xa, xa_col=E)
-                hidden, (h, c) = self.forward_step(xa, (h, c), mode=mode)
-                return self.C(hidden), (h, c)
-
-            return beam_search(step_fn, (h0, c0), self.vocab_size, start_token, end_token, k,
-                               self.max_seq_length, dev)
+        of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L]."""
+        return beam_decode(self, *self._beam(features, None, k, mode), None, k, start_token, end_token)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once: the reference's evaluator
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
-        images take their decoder step together (capnet.beam.beam_search_batched). encoder_att(features) once per image;
-        a beam's rows of the map are gathered by its image index. Returns a list of token lists."""
-        from .beam import beam_search_batched
-        dev = self.B.weight.device
-        attention, _ = self._mode_modules(mode)
-        E, A, Cdim = self.embed_size, self.attention_size, features.size(-1)
+        images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists."""
         n = features.size(0)
-        with torch.no_grad():
-            feat = features.reshape(n, -1, Cdim).to(dev).contiguous()
-            P = feat.size(1)
-            att1 = attention.encoder_att(feat.reshape(n * P, Cdim)).reshape(n, P, A).contiguous()
-            h0, c0 = self.init_hidden_state(feat)
-            img = torch.arange(n, device=dev).repeat_interleave(k)
-            h0, c0 = h0.index_select(0, img).contiguous(), c0.index_select(0, img).contiguous()
-            wz = torch.cat([attention.decoder_att.weight, self.f_beta.weight], 0).contiguous()
-            bz = torch.cat([attention.decoder_att.bias, self.f_beta.bias], 0).contiguous()
-
-            def step_fn(prev_words, state):
-                h, c, im = state
-                s_rows = h.shape[0]
-                z = ops.linear(h, wz, bz).contiguous()
-                xa = torch.empty((s_rows, E + Cdim), dtype=torch.float32, device=dev)
-                xa[:, :E] = self.B(prev_words)
-                ops.attention_step(att1.index_select(0, im), feat.index_select(0, im), z, A, attention.full_att.weight,
-                                   attention.full_att.bias, xa=xa, xa_col=E)
-                hidden, (h, c) = self.forward_step(xa, (h, c), mode=mode)
-                return self.C(hidden), (h, c, im)
-
-            return beam_search_batched(step_fn, (h0, c0, img), n, self.vocab_size, start_token, end_token, k,
-                                       self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(features, n, k, mode), n, k, start_token, end_token)
 
     def forward(self,
                 captions,
@@ -268,17 +219,8 @@ class DecoderFactoredLSTMAtt(nn.Module):
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
         weights = self._weights(mode)
         num_layers, upper = self._upper_layers(mode)
-        cfg = {
-            "num_layers": num_layers,
-            "batch_sizes": batch_sizes,
-            "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
-            "hidden_size": self.hidden_size,
-            "factored_size": self.factored_size,
-            "attention_size": self.attention_size,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-        }
+        cfg = _seq_cfg(self, batch_sizes, self.dropout.p, tf_mask, teacher_forcing_ratio, num_layers=num_layers,
+                       factored_size=self.factored_size, attention_size=self.attention_size)
         hiddens, alphas = ops.AttSeqFn.apply(cfg, captions, features.detach(), self.B.weight, self.C.weight, self.C.bias,
                                              *weights, *upper)
         return self.C(hiddens), alphas

@@ -8,8 +8,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .model import (Dropout, Embedding, EncoderCNN, Linear, _dropout_seed,  # noqa: F401
-                    _resolve_tf_mask)
+from .decode import beam_decode, zero_state
+from .model import Dropout, Embedding, EncoderCNN, Linear, _seq_cfg  # noqa: F401
 
 
 class LSTMCell(nn.Module):
@@ -79,47 +79,26 @@ class DecoderRNN(nn.Module):
     def forward(self, captions, lengths, features, teacher_forcing_ratio=0.8, tf_mask=None):
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
         num_layers, upper = self._upper_layers()
-        cfg = {
-            "cell": ops.CELL_LSTM,
-            "num_layers": num_layers,
-            "batch_sizes": batch_sizes,
-            "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
-            "hidden_size": self.hidden_size,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-        }
+        cfg = _seq_cfg(self, batch_sizes, self.dropout.p, tf_mask, teacher_forcing_ratio, cell=ops.CELL_LSTM,
+                       num_layers=num_layers)
         weights = [self.lstm.weight_ih, self.lstm.bias_ih, self.lstm.weight_hh, self.lstm.bias_hh]
         hiddens = ops.SeqFn.apply(cfg, captions, features, self.embed.weight, self.linear.weight, self.linear.bias,
                                   *weights, *upper)
         return self.linear(hiddens)
 
+    def _beam(self, rows):
+        """(step_fn, the zero state of `rows` beams) of a beam search."""
+        def step_fn(prev_words, state):
+            hidden, (h, c) = self.forward_step(self.embed(prev_words), state)
+            return self.linear(hidden), (h, c)
+        return step_fn, zero_state(rows, self.hidden_size, self.embed.weight.device)
+
     def sample(self, features, start_token, end_token, k=5):
         """Beam search, nic/model.py:117-207 (the image features are not an input of the decode
         steps there either). Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        dev = self.embed.weight.device
-
-        def step_fn(prev_words, state):
-            hidden, (h, c) = self.forward_step(self.embed(prev_words), state)
-            return self.linear(hidden), (h, c)
-
-        with torch.no_grad():
-            zeros = torch.zeros(k, self.hidden_size, dtype=torch.float32, device=dev)
-            return beam_search(step_fn, (zeros, zeros.clone()), self.vocab_size, start_token,
-                               end_token, k, self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(k), None, k, start_token, end_token)
 
     def sample_batch(self, features, start_token, end_token, k=5):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched)."""
-        from .beam import beam_search_batched
-        dev = self.embed.weight.device
         n = features.size(0)
-
-        def step_fn(prev_words, state):
-            hidden, (h, c) = self.forward_step(self.embed(prev_words), state)
-            return self.linear(hidden), (h, c)
-
-        with torch.no_grad():
-            zeros = torch.zeros(n * k, self.hidden_size, dtype=torch.float32, device=dev)
-            return beam_search_batched(step_fn, (zeros, zeros.clone()), n, self.vocab_size, start_token, end_token, k,
-                                       self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(n * k), n, k, start_token, end_token)

@@ -9,7 +9,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .model import Dropout, Embedding, Linear, _Marker, _dropout_seed, _resolve_tf_mask
+from .decode import att_beam_start, att_beam_step, beam_decode
+from .model import Dropout, Embedding, Linear, _Marker, _seq_cfg
 from .model_att import Attention, EncoderCNN  # noqa: F401  (same classes as the StyleNet path)
 from .nic_model import LSTMCell
 
@@ -84,46 +85,26 @@ class DecoderRNNAtt(nn.Module):
         features = features.reshape(batch_size, -1, features.size(-1))
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
         num_layers, upper = self._upper_layers()
-        cfg = {
-            "cell": ops.CELL_LSTM,
-            "num_layers": num_layers,
-            "batch_sizes": batch_sizes,
-            "tf_mask": _resolve_tf_mask(tf_mask, len(batch_sizes), teacher_forcing_ratio),
-            "hidden_size": self.hidden_size,
-            "attention_size": self.attention_size,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-        }
+        cfg = _seq_cfg(self, batch_sizes, self.dropout.p, tf_mask, teacher_forcing_ratio, cell=ops.CELL_LSTM,
+                       num_layers=num_layers, attention_size=self.attention_size)
         hiddens, alphas = ops.AttSeqFn.apply(cfg, captions, features.detach(), self.embed.weight, self.linear.weight,
                                              self.linear.bias, *self._weights(), *upper)
         return self.linear(hiddens), alphas
 
+    def _upper_beam(self, feat, img):
+        """(the beam state's entries after layer 0's (h0, c0), att_beam_step's `upper`). One layer here."""
+        return (), None
+
+    @torch.no_grad()
+    def _beam(self, features, n, k):
+        """(step_fn, initial state) of a beam search over one image (n None) or n images: the state is layer 0's (h, c),
+        then what _upper_beam adds, then (n images) every beam's image index."""
+        feat, att1_of, feat_of, h0, c0, img = att_beam_start(self, self.attention, features, n, k)
+        state, upper = self._upper_beam(feat, img)
+        step_fn = att_beam_step(self.attention, self.f_beta, self.embed, self.lstm, self.linear, att1_of, feat_of,
+                                features.size(-1), upper)
+        return step_fn, (h0, c0) + state + (() if img is None else (img,))
+
     def sample(self, features, start_token, end_token, k=5):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        dev = self.embed.weight.device
-        attention = self.attention
-        E, A, Cdim = self.embed_size, self.attention_size, features.size(-1)
-        with torch.no_grad():
-            feat1 = features.reshape(1, -1, Cdim).to(dev).contiguous()
-            P = feat1.size(1)
-            feat_k = feat1.expand(k, P, Cdim).contiguous()
-            att1_k = attention.encoder_att(feat1[0]).reshape(1, P, A).expand(k, P, A).contiguous()
-            h0, c0 = self.init_hidden_state(feat_k)
-            wz = torch.cat([attention.decoder_att.weight, self.f_beta.weight], 0).contiguous()
-            bz = torch.cat([attention.decoder_att.bias, self.f_beta.bias], 0).contiguous()
-
-            def step_fn(prev_words, state):
-                h, c = state
-                s_rows = h.shape[0]
-                z = ops.linear(h, wz, bz).contiguous()
-                xa = torch.empty((s_rows, E + Cdim), dtype=torch.float32, device=dev)
-                xa[:, :E] = self.embed(prev_words)
-                ops.attention_step(att1_k[:s_rows], feat_k[:s_rows], z, A, attention.full_att.weight,
-                                   attention.full_att.bias, xa=xa, xa_col=E)
-                hidden, (h, c) = self.forward_step(xa, (h, c))
-                return self.linear(hidden), (h, c)
-
-            return beam_search(step_fn, (h0, c0), self.vocab_size, start_token, end_token, k,
-                               self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(features, None, k), None, k, start_token, end_token)

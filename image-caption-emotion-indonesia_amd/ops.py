@@ -374,7 +374,7 @@ def vocab_argmax(h, w, b=None, workspace=None):
 
 def lstm_greedy_decode(steps, wcat, beff, emb, Cw, Cb, features=None, start_tokens=None, state=None):
     """`steps` greedy decode steps of a stacked nn.LSTM + nn.Linear in ONE C call (capnet_lstm_greedy_decode): tokens and
-    logits never leave the device. wcat / beff: capnet.nic_stacked._pack_cell of every layer; emb [V, E]; Cw [V, H], Cb [V].
+    logits never leave the device. wcat / beff: capnet.decode.pack_cell of every layer; emb [V, E]; Cw [V, H], Cb [V].
     The first input is `features` [rows, E] or emb[start_tokens] (int64 [rows]); state: [rows, 2L, H] or None for zeros.
     Returns (ids [rows, steps] int64, the final state [rows, 2L, H])."""
     if (features is None) == (start_tokens is None):

@@ -30,9 +30,9 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .model import Dropout, Embedding, Linear, _dropout_seed
+from .decode import cell_stepper, pack_cells
+from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
-from .nic_stacked import _pack_cell, _stepper
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # seq2seq/model.py:8
 
@@ -60,7 +60,7 @@ class LSTM(nn.Module):
 
 
 class _Layer:
-    """Layer l of an LSTM container under nn.LSTMCell's names (what capnet.nic_stacked's step and packing read)."""
+    """Layer l of an LSTM container under nn.LSTMCell's names (what capnet.decode's step and packing read)."""
 
     def __init__(self, lstm, l):
         self.input_size = lstm.input_size if l == 0 else lstm.hidden_size
@@ -118,25 +118,15 @@ class _RNN(nn.Module):
             b = embedded.size(0)
             zeros = torch.zeros((self.num_layers, b, self.hidden_size), dtype=torch.float32, device=embedded.device)
             state = _to_rows(zeros if h is None else h.detach(), zeros if c is None else c.detach())
-            top, state = _stepper(self._layers(), self.embed_size, self.hidden_size)(embedded.detach().contiguous(), None,
-                                                                                      state)
+            step = cell_stepper(self._layers(), self.embed_size, self.hidden_size)
+            top, state = step(embedded.detach().contiguous(), None, state)
             return top, _from_rows(state)
 
     def _sequence(self, features, tokens, lengths, teacher_forcing_ratio):
         """(packed logits [N, V], (h, c)): one random.random() draw per step, then ops.SeqFn."""
         batch_sizes = ops.batch_sizes_from_lengths(lengths)
-        cfg = {
-            "cell": ops.CELL_LSTM,
-            "num_layers": self.num_layers,
-            "batch_sizes": batch_sizes,
-            "tf_mask": [random.random() < teacher_forcing_ratio for _ in batch_sizes],
-            "hidden_size": self.hidden_size,
-            "dropout": self.dropout.p if self.training else 0.0,
-            "seed": _dropout_seed(self.training, self.dropout.p),
-            "training": self.training,
-            "input_dropout_only": True,
-            "want_final_state": True,
-        }
+        cfg = _seq_cfg(self, batch_sizes, self.dropout.p, None, teacher_forcing_ratio, cell=ops.CELL_LSTM,
+                       num_layers=self.num_layers, input_dropout_only=True, want_final_state=True)
         weights = []
         for c in self._layers():
             weights += [c.weight_ih, c.bias_ih, c.weight_hh, c.bias_hh]
@@ -158,10 +148,10 @@ class _RNN(nn.Module):
         with torch.no_grad():
             if (os.environ.get(FUSED_GREEDY_OFF, "")[:1] != "1" and ops.stacked_decode_supported(E, H)
                     and state.shape[0] <= FUSED_GREEDY_MAX_ROWS):
-                packed = [_pack_cell(c, (E + 15) // 16 * 16 if l == 0 else H) for l, c in enumerate(layers)]
+                packed = pack_cells(layers, E)
                 return ops.lstm_greedy_decode(steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
                                               features=features, start_tokens=start_tokens, state=state)
-            step = _stepper(layers, E, H)
+            step = cell_stepper(layers, E, H)
             ids, tokens = [], start_tokens
             for t in range(steps):
                 if t == 0 and features is not None:

@@ -26,8 +26,8 @@ one launch per layer (capnet_stacked_decode_step, csrc/lstm_decode_step.hip: [x 
 layer 0 gathers its embedding rows by token id itself), plus C and capnet_beam_topk. The beam state is ONE tensor
 [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = its c), so re-ordering the beams is one index_select per step.
 CAPNET_NO_FUSED_DECODE_STEP=1 (read at every call) takes the composed step instead -- per layer the V, S, U and W
-products and the pointwise cell, unfolded -- which is also the path for shapes the kernel does not take."""
-import os
+products and the pointwise cell, unfolded -- which is also the path for shapes the kernel does not take. That choice and
+the beam-search front end are capnet.decode's (stack_stepper, beam_decode); this class adds its fold and its composed step."""
 import sys
 
 import torch
@@ -35,11 +35,10 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .model import Embedding as _Embedding, Linear as _Linear, _dropout_seed, _resolve_tf_mask
+from .decode import as_state, beam_decode, factored_step, input_width, stack_stepper
+from .model import Embedding as _Embedding, Linear as _Linear, _layer_mods, _seq_cfg
 
 MODES = ("factual", "happy", "sad", "angry")
-_S_PREFIX = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}
-FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
 
 
 def _check_mode(mode):
@@ -92,12 +91,7 @@ class StackedFactoredLSTM(nn.Module):
 
     # ---- one layer's pieces -------------------------------------------------------------------
     def _mods(self, l, mode):
-        tag = "" if l == 0 else str(l)
-        s = _S_PREFIX[mode]
-        return ([getattr(self, "V%s_%s" % (tag, g)) for g in "ifoc"],
-                [getattr(self, "S%s_%s%s" % (tag, s, g)) for g in "ifoc"],
-                [getattr(self, "U%s_%s" % (tag, g)) for g in "ifoc"],
-                [getattr(self, "W%s_%s" % (tag, g)) for g in "ifoc"])
+        return _layer_mods(self, "" if l == 0 else str(l), mode)
 
     # ---- decoding -----------------------------------------------------------------------------
     def _fold(self, mode):
@@ -109,7 +103,7 @@ class StackedFactoredLSTM(nn.Module):
         for l in range(self.num_layers):
             V, S, U, W = self._mods(l, mode)
             n_in = V[0].in_features
-            kin = (n_in + 15) // 16 * 16
+            kin = input_width(n_in)
             wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
             beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
             for g in range(4):
@@ -126,10 +120,7 @@ class StackedFactoredLSTM(nn.Module):
         """One inference step of the stack, unfolded: per layer the V, S, U and W products and the pointwise cell."""
         new = torch.empty_like(state)
         for l in range(self.num_layers):
-            V, S, U, W = self._mods(l, mode)
-            h = state[:, 2 * l].contiguous()
-            pre = torch.cat([U[k](S[k](V[k](x))) + W[k](h) for k in range(4)], 1)
-            h, c = ops.lstm_pointwise(pre, state[:, 2 * l + 1], ops.CELL_FACTORED)
+            h, c = factored_step(*self._mods(l, mode), x, state[:, 2 * l].contiguous(), state[:, 2 * l + 1])
             new[:, 2 * l], new[:, 2 * l + 1] = h, c
             x = h
         return x, new
@@ -138,20 +129,8 @@ class StackedFactoredLSTM(nn.Module):
         """step(x, tokens, state [rows, 2L, H]) -> (top h [rows, H], state'): x is the embedding table when `tokens` is
         given, else layer 0's inputs. The fused step (weights folded here, once) unless CAPNET_NO_FUSED_DECODE_STEP=1
         or the shape is one the kernel does not take."""
-        fused = (os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and self.num_layers <= 8 and
-                 ops.stacked_decode_supported(self.embed_size, self.hidden_size))
-        if fused:
-            folded = self._fold(mode)
-            wcat, beff = [w for w, _ in folded], [b for _, b in folded]
-
-            def step(x, tokens, state):
-                return ops.stacked_decode_step(state, wcat, beff, x, tokens)
-        else:
-            def step(x, tokens, state):
-                if tokens is not None:
-                    x = ops.embedding(tokens, x)
-                return self._composed_step(x, state, mode)
-        return step
+        return stack_stepper(self.num_layers, self.embed_size, self.hidden_size, ops.CELL_FACTORED,
+                             lambda: self._fold(mode), lambda x, state: self._composed_step(x, state, mode))
 
     def forward_step(self, embedded, states, mode):
         """One decode step of the stack at inference (no dropout) on layer 0's input `embedded` [rows, E]. states: every
@@ -160,44 +139,31 @@ class StackedFactoredLSTM(nn.Module):
         sample() / sample_batch() fold once per decode."""
         _check_mode(mode)
         with torch.no_grad():
-            if not isinstance(states, torch.Tensor):
-                states = torch.stack([t for hc in states for t in hc], 1)
-            return self._decode_stepper(mode)(embedded.detach(), None, states.detach())
+            return self._decode_stepper(mode)(embedded.detach(), None, as_state(states).detach())
+
+    @torch.no_grad()
+    def _beam(self, rows, mode):
+        """(step_fn, the zero state (one tensor [rows, 2L, H],)) of a beam search: the weights are folded here, once."""
+        _check_mode(mode)
+        step, emb = self._decode_stepper(mode), self.B.weight.detach()
+
+        def step_fn(prev_words, state):
+            top, st = step(emb, prev_words, state[0])
+            return self.C(top), (st,)
+        zeros = torch.zeros((rows, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=emb.device)
+        return step_fn, (zeros,)
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
         """Beam search, stylenet/model.py:198-294, over the stack: as DecoderFactoredLSTM.sample, the image is NOT an
         input (`features` only fixes the device), every layer's state starts at zero, the first input is B(<start>) and
         factual_limit is ignored. Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        _check_mode(mode)
-        dev = self.B.weight.device
-        with torch.no_grad():
-            step, emb = self._decode_stepper(mode), self.B.weight.detach()
-
-            def step_fn(prev_words, state):
-                top, st = step(emb, prev_words, state[0])
-                return self.C(top), (st,)
-
-            zeros = torch.zeros((k, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=dev)
-            return beam_search(step_fn, (zeros,), self.vocab_size, start_token, end_token, k, self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched). Returns a list of token lists,
         each equal to sample(features[i:i+1], ...)[0].tolist()."""
-        from .beam import beam_search_batched
-        _check_mode(mode)
-        dev = self.B.weight.device
         n = features.size(0)
-        with torch.no_grad():
-            step, emb = self._decode_stepper(mode), self.B.weight.detach()
-
-            def step_fn(prev_words, state):
-                top, st = step(emb, prev_words, state[0])
-                return self.C(top), (st,)
-
-            zeros = torch.zeros((n * k, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=dev)
-            return beam_search_batched(step_fn, (zeros,), n, self.vocab_size, start_token, end_token, k,
-                                       self.max_seq_length, dev)
+        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token)
 
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, captions, lengths, features=None, teacher_forcing_ratio=0.8, mode="factual", tf_mask=None):
@@ -207,10 +173,8 @@ class StackedFactoredLSTM(nn.Module):
         if not captions.is_cuda:
             raise CapnetError("StackedFactoredLSTM runs on the GPU only")
         bs = ops.batch_sizes_from_lengths(lengths)
-        cfg = {"batch_sizes": bs, "tf_mask": _resolve_tf_mask(tf_mask, len(bs), teacher_forcing_ratio),
-               "hidden_size": self.hidden_size, "factored_size": self.factored_size, "num_layers": self.num_layers,
-               "dropout": self.dropout_p if self.training else 0.0, "seed": _dropout_seed(self.training, self.dropout_p),
-               "training": self.training}
+        cfg = _seq_cfg(self, bs, self.dropout_p, tf_mask, teacher_forcing_ratio, factored_size=self.factored_size,
+                       num_layers=self.num_layers)
         weights = []
         for l in range(self.num_layers):
             for grp in self._mods(l, mode):

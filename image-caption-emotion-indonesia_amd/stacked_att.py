@@ -28,15 +28,15 @@ Engine: the whole recurrence is ONE C call each way: DecoderFactoredLSTMAtt.forw
 is one launch of csrc/lstm_upper_step.hip; CAPNET_NO_FUSED_UPPER_STEP=1 takes the composed path (rows_dropout, three
 chain products, the fused recurrent step) instead. capnet.parallel is parameter-generic: data-parallel training needs
 nothing more.
+
+Decoding: DecoderFactoredLSTMAtt's sample / sample_batch (capnet.decode's attention beam step) with this class's upper
+layers (_upper_beam): the beam state is every layer's (h, c), and each upper layer takes the composed step
+(capnet.decode.factored_step).
 """
-import torch
-
-from . import ops
 from ._lib import CapnetError
-from .model import Linear, _MODES
+from .decode import factored_step
+from .model import Linear, _MODES, _layer_mods
 from .model_att import DecoderFactoredLSTMAtt
-
-_S_PREFIX = {"factual": "f", "happy": "happy_", "sad": "sad_", "angry": "angry_"}
 
 
 class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
@@ -81,11 +81,7 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
     def _upper_mods(self, l, mode):
         if mode not in _MODES:
             self._mode_modules(mode)          # the reference's message and error
-        s = _S_PREFIX[mode]
-        return ([getattr(self, "V%d_%s" % (l, g)) for g in "ifoc"],
-                [getattr(self, "S%d_%s%s" % (l, s, g)) for g in "ifoc"],
-                [getattr(self, "U%d_%s" % (l, g)) for g in "ifoc"],
-                [getattr(self, "W%d_%s" % (l, g)) for g in "ifoc"])
+        return _layer_mods(self, str(l), mode)
 
     def _upper_weights(self, l, mode):
         out = []
@@ -107,91 +103,24 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
 
     def _upper_step(self, l, x, h, c, mode):
         """One step of layer l > 0 on its input x (no dropout: inference) -> (h, c)."""
-        V, S, U, W = self._upper_mods(l, mode)
-        pre = torch.cat([U[k](S[k](V[k](x))) + W[k](h) for k in range(4)], 1)
-        return ops.lstm_pointwise(pre, c, ops.CELL_FACTORED)
-
-    def _stack_state(self, mean_features, h0, c0, rows=None):
-        state = [h0, c0]
-        for l in range(1, self.num_layers):
-            h, c = self._upper_init(l, mean_features)
-            if rows is not None:
-                h, c = h.index_select(0, rows).contiguous(), c.index_select(0, rows).contiguous()
-            state += [h, c]
-        return state
-
-    def _step_upper_layers(self, hidden, state, mode):
-        new = []
-        x = hidden
-        for l in range(1, self.num_layers):
-            h, c = self._upper_step(l, x, state[2 * l], state[2 * l + 1], mode)
-            new += [h, c]
-            x = h
-        return x, new
+        return factored_step(*self._upper_mods(l, mode), x, h, c)
 
     # ---- decoding ---------------------------------------------------------------------------------
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
-        """Beam search with attention (stylenet/model_att.py:307-426) over the stack: the beam state is every layer's
-        (h, c). `features`: the encoder map of ONE image. Returns LongTensor [1, L]."""
-        from .beam import beam_search
-        dev = self.B.weight.device
-        attention, _ = self._mode_modules(mode)
-        E, A, Cdim = self.embed_size, self.attention_size, features.size(-1)
-        with torch.no_grad():
-            feat1 = features.reshape(1, -1, Cdim).to(dev).contiguous()
-            P = feat1.size(1)
-            feat_k = feat1.expand(k, P, Cdim).contiguous()
-            att1_k = attention.encoder_att(feat1[0]).reshape(1, P, A).expand(k, P, A).contiguous()
-            h0, c0 = self.init_hidden_state(feat_k)
-            state0 = self._stack_state(feat_k.mean(dim=1), h0, c0)
-            wz = torch.cat([attention.decoder_att.weight, self.f_beta.weight], 0).contiguous()
-            bz = torch.cat([attention.decoder_att.bias, self.f_beta.bias], 0).contiguous()
+    def _upper_beam(self, feat, img, mode):
+        """The beam state is every layer's (h, c): the upper layers' init_h{l} / init_c{l}(mean feature), tiled by image
+        index, and their step on the entries after layer 0's."""
+        mean_features, state = feat.mean(dim=1), ()
+        for l in range(1, self.num_layers):
+            h, c = self._upper_init(l, mean_features)
+            if img is not None:
+                h, c = h.index_select(0, img).contiguous(), c.index_select(0, img).contiguous()
+            state += (h, c)
 
-            def step_fn(prev_words, state):
-                h, c = state[0], state[1]
-                s_rows = h.shape[0]
-                z = ops.linear(h, wz, bz).contiguous()
-                xa = torch.empty((s_rows, E + Cdim), dtype=torch.float32, device=dev)
-                xa[:, :E] = self.B(prev_words)
-                ops.attention_step(att1_k[:s_rows], feat_k[:s_rows], z, A, attention.full_att.weight,
-                                   attention.full_att.bias, xa=xa, xa_col=E)
-                hidden, (h, c) = self.forward_step(xa, (h, c), mode=mode)
-                top, upper = self._step_upper_layers(hidden, state, mode)
-                return self.C(top), tuple([h, c] + upper)
-
-            return beam_search(step_fn, tuple(state0), self.vocab_size, start_token, end_token, k,
-                               self.max_seq_length, dev)
-
-    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
-        """sample() for every image of `features` at once (capnet.beam.beam_search_batched), as
-        DecoderFactoredLSTMAtt.sample_batch. Returns a list of token lists."""
-        from .beam import beam_search_batched
-        dev = self.B.weight.device
-        attention, _ = self._mode_modules(mode)
-        E, A, Cdim = self.embed_size, self.attention_size, features.size(-1)
-        n = features.size(0)
-        with torch.no_grad():
-            feat = features.reshape(n, -1, Cdim).to(dev).contiguous()
-            P = feat.size(1)
-            att1 = attention.encoder_att(feat.reshape(n * P, Cdim)).reshape(n, P, A).contiguous()
-            h0, c0 = self.init_hidden_state(feat)
-            img = torch.arange(n, device=dev).repeat_interleave(k)
-            h0, c0 = h0.index_select(0, img).contiguous(), c0.index_select(0, img).contiguous()
-            state0 = self._stack_state(feat.mean(dim=1), h0, c0, rows=img)
-            wz = torch.cat([attention.decoder_att.weight, self.f_beta.weight], 0).contiguous()
-            bz = torch.cat([attention.decoder_att.bias, self.f_beta.bias], 0).contiguous()
-
-            def step_fn(prev_words, state):
-                h, c, im = state[0], state[1], state[-1]
-                s_rows = h.shape[0]
-                z = ops.linear(h, wz, bz).contiguous()
-                xa = torch.empty((s_rows, E + Cdim), dtype=torch.float32, device=dev)
-                xa[:, :E] = self.B(prev_words)
-                ops.attention_step(att1.index_select(0, im), feat.index_select(0, im), z, A, attention.full_att.weight,
-                                   attention.full_att.bias, xa=xa, xa_col=E)
-                hidden, (h, c) = self.forward_step(xa, (h, c), mode=mode)
-                top, upper = self._step_upper_layers(hidden, state, mode)
-                return self.C(top), tuple([h, c] + upper + [im])
-
-            return beam_search_batched(step_fn, tuple(state0 + [img]), n, self.vocab_size, start_token, end_token, k,
-                                       self.max_seq_length, dev)
+        def step(hidden, rest):
+            new, x = [], hidden
+            for l in range(1, self.num_layers):
+                h, c = self._upper_step(l, x, rest[2 * l - 2], rest[2 * l - 1], mode)
+                new += [h, c]
+                x = h
+            return x, new
+        return state, lambda: step

@@ -25,9 +25,9 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import capnet  # noqa: E402,F401
-from capnet.nic_stacked import StackedDecoderRNN, StackedDecoderRNNAtt, _stepper  # noqa: E402
+from capnet.decode import FUSED_DECODE_OFF, cell_stepper  # noqa: E402
+from capnet.nic_stacked import StackedDecoderRNN, StackedDecoderRNNAtt  # noqa: E402
 from capnet.optim import Adam  # noqa: E402
-from capnet.stacked import FUSED_DECODE_OFF  # noqa: E402
 from capnet.train import CrossEntropyLoss, train_step, train_step_att  # noqa: E402
 
 A, E, H, C, P, V, K = 512, 300, 512, 2048, 196, 8192, 5
@@ -91,7 +91,7 @@ def time_step(dec, n, steps, fused, dev):
     tokens = torch.randint(3, V, (rows,), generator=g).to(dev)
     state = ((torch.rand(rows, 2 * dec.num_layers, H, generator=g) - 0.5) * 0.5).to(dev)
     with torch.no_grad():
-        step, emb = _stepper(dec._cells(), E, H), dec.embed.weight.detach()
+        step, emb = cell_stepper(dec._cells(), E, H), dec.embed.weight.detach()
         for _ in range(3):
             top, st = step(emb, tokens, state)
             dec.linear(top)

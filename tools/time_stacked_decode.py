@@ -23,7 +23,8 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 import capnet  # noqa: E402,F401
-from capnet.stacked import FUSED_DECODE_OFF, StackedFactoredLSTM  # noqa: E402
+from capnet.decode import FUSED_DECODE_OFF  # noqa: E402
+from capnet.stacked import StackedFactoredLSTM  # noqa: E402
 
 E, H, F, V, K = 300, 512, 1024, 8192, 5
 
