@@ -26,6 +26,8 @@
 
 namespace capnet {
 
+using seqd::Carve; using seqd::Chain; using seqd::GateOrder; using seqd::SkWs;
+
 namespace {
 
 struct ALayout {
@@ -38,8 +40,7 @@ ALayout make_alayout(const AttDims& d) {
   ALayout L;
   L.ZW = 4 * d.H + d.A + d.C;
   L.XW = d.E + d.C;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
+  Carve take, itake;
   const size_t N = d.N, F = d.F, H = d.H;
   const bool fac = d.cell == kCellFactored;
   L.XA = take(N * L.XW);
@@ -64,15 +65,16 @@ ALayout make_alayout(const AttDims& d) {
   L.US = take(fac ? 4 * H * F : 4);
   L.Weff = take(fac ? 4 * H * L.XW : 4);
   L.c1 = take(4 * F);
-  L.total = o;
-  size_t io = 0;
-  auto itake = [&](size_t n) { size_t r = io; io += (n + 3) / 4 * 4; return r; };
+  L.total = take.o;
   L.row_sample = itake(N);
   L.row_col = itake(N);
   L.row_token = itake(N);
   L.prev_row = itake(N);
-  L.itotal = io;
+  L.itotal = itake.o;
   return L;
+}
+Chain chain_of(const AttDims& d, const ALayout& L, const float* sv) {
+  return {sv + L.Vcat, sv + L.Scat, sv + L.Ucat, sv + L.bV, sv + L.bS, L.XW, d.F, d.H};
 }
 
 // Steps of at most 16 rows are a chain of dependent launches of 8-12 us each, whatever they compute (NOTEBOOK 4l): the
@@ -114,21 +116,44 @@ int check(const AttDims& d, const int* bs) {
                  "att decoder: E, H, A, F must be multiples of 4 and the feature size of 512 "
                  "(E=%d H=%d A=%d F=%d C=%d)", d.E, d.H, d.A, d.F, d.C);
   CAPNET_REQUIRE(bs != nullptr && d.steps <= kMaxSteps && d.steps <= d.T, "att decoder: steps");
-  long n = 0;
-  int prev = d.B;
   CAPNET_REQUIRE(bs[0] == d.B, "att decoder: batch_sizes[0] must equal the batch");
-  for (int t = 0; t < d.steps; ++t) {
-    CAPNET_REQUIRE(bs[t] > 0 && bs[t] <= prev, "att decoder: batch_sizes must be non-increasing");
-    prev = bs[t];
-    n += bs[t];
-  }
-  CAPNET_REQUIRE(n == d.N, "att decoder: sum(batch_sizes) != N");
-  return kOk;
+  return seqd::check_batch_sizes("att decoder", bs, d.steps, d.B, d.N);
 }
 
-#define RC(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
-struct GateOrderA { int gi, gf, go, gg, tanh_out; };  // column block of each gate role
+// Backward scratch. The chain's rows A1c, A2c have their full size whatever the chain mode, so that the size does not
+// depend on a switch that can change between the size query and the call.
+struct ABwdLayout {
+  size_t Zb, dA2, dA1, A1c, A2c, dXA, Hprev, dh_rec, dc, dalpha_part, datt1, dwf_rows, dbf_rows, de_all, skws, dh_slabs, total;
+  size_t dh_ws_floats;
+};
+ABwdLayout make_abwd_layout(const AttDims& d) {
+  ABwdLayout S;
+  Carve take;
+  const ALayout L = make_alayout(d);
+  const size_t N = d.N, B = d.B, rows4F = d.cell == kCellFactored ? N * 4 * d.F : 4;
+  S.Zb = take(N * L.ZW);
+  S.dA2 = take(rows4F);
+  S.dA1 = take(rows4F);
+  S.A1c = take(rows4F);     // the chain's intermediate rows, formed in the backward where the forward ran one product
+  S.A2c = take(rows4F);
+  S.dXA = take(N * L.XW);
+  S.Hprev = take(N * d.H);
+  S.dh_rec = take(B * d.H);
+  S.dc = take(B * d.H);
+  S.dalpha_part = take(B * (d.C / 256) * d.P);
+  S.datt1 = take(B * d.P * d.A);
+  S.dwf_rows = take(N * d.A);
+  S.dbf_rows = take(N);
+  S.de_all = take(N * d.P);   // softmax-backward scores of every row
+  S.skws = take(kAttSplitKFloats);
+  // dh_{t-1} = dZ_t . Wz has K = 4H + A + C: eighteen 256-k chunks. Its partials stay in the slab area and the gate kernel of
+  // step t - 1 -- the next launch -- sums them (<= 16 rows: the hand-off inside the launch was 8 of the product's 12.6 us;
+  // up to 128 rows: a splitk_reduce launch less per step)
+  S.dh_ws_floats = d.B <= 128 ? (size_t)cdiv(L.ZW, 64) * B * d.H : 4;
+  S.dh_slabs = take(S.dh_ws_floats);
+  S.total = take.o;
+  return S;
+}
 
 }  // namespace
 
@@ -143,13 +168,7 @@ size_t att_saved_ints(const AttDims& d) { return make_alayout(d).itotal; }
 size_t att_fwd_scratch_floats(const AttDims& d) {
   return (size_t)d.B * d.V + 64 + kAttSplitKFloats + (size_t)d.B * d.P + 64;
 }
-size_t att_bwd_scratch_floats(const AttDims& d) {
-  const ALayout L = make_alayout(d);
-  const size_t N = d.N;
-  return N * L.ZW + 4 * (d.cell == kCellFactored ? N * 4 * d.F : 8) + N * L.XW + N * d.H + 2 * (size_t)d.B * d.H +
-         (size_t)d.B * (d.C / 256) * d.P + (size_t)d.B * d.P * d.A + N * d.A + N + N * d.P + 4096 +
-         kAttSplitKFloats + (d.B <= 128 ? (size_t)cdiv(L.ZW, 64) * d.B * d.H : 4) + 4;
-}
+size_t att_bwd_scratch_floats(const AttDims& d) { return make_abwd_layout(d).total; }
 
 namespace {
 // one forward call of the attention cell: what its steps share (att_fwd_begin), so that the single-layer driver and the
@@ -159,15 +178,11 @@ struct AttFwd {
   ALayout L;
   std::vector<int> off;
   const unsigned char* tf;
-  const long long* captions;
-  const float *feat, *emb, *Cw, *Cb;
-  float dropout_p;
-  unsigned long long seed;
-  const float *w_full, *b_full;
-  float *sv, *scratch, *skws, *escore, *hiddens, *alphas_bt;
-  int *svi, *skctr, *err_flag;
-  bool one_product, fac;
-  GateOrderA go;
+  seqd::Feedback fb;       // a free-running step's token from the top layer's hidden state
+  const float *feat, *w_full, *b_full;
+  float *sv, *escore, *hiddens, *alphas_bt;
+  SkWs sk;
+  bool one_product;
   hipStream_t s;
 };
 
@@ -177,8 +192,7 @@ int att_fwd_begin(AttFwd& f, const AttDims& d, const int* bs, const unsigned cha
                   float dropout_p, unsigned long long seed, int training, float* saved, int* saved_i, float* scratch,
                   float* hiddens, float* alphas_bt, int* err_flag, hipStream_t s) {
   RC(check(d, bs));
-  CAPNET_REQUIRE(tf && captions && feat && emb && Cw && Cb && saved && saved_i && scratch &&
-                     hiddens && alphas_bt && err_flag,
+  CAPNET_REQUIRE(tf && captions && feat && emb && Cw && Cb && saved && saved_i && scratch && hiddens && alphas_bt && err_flag,
                  "att_seq_forward: null argument");
   CAPNET_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "att_seq_forward: dropout p");
   f.d = d;
@@ -186,81 +200,43 @@ int att_fwd_begin(AttFwd& f, const AttDims& d, const int* bs, const unsigned cha
   const ALayout& L = f.L;
   const int E = d.E, F = d.F, H = d.H, N = d.N, A = d.A, P = d.P, C = d.C, XW = L.XW;
   float* sv = saved;
-  std::vector<int>& off = f.off;
-  off.assign(d.steps + 1, 0);
-  for (int t = 0; t < d.steps; ++t) off[t + 1] = off[t] + bs[t];
-  {
-    SeqMeta m;
-    m.N = N; m.steps = d.steps; m.has_features = 0;
-    for (int t = 0; t <= d.steps; ++t) m.off[t] = off[t];
-    for (int t = 0; t < d.steps; ++t) m.tf[t] = tf[t] ? 1 : 0;
-    RC(build_rows(m, saved_i + L.row_sample, saved_i + L.row_col, saved_i + L.row_token,
-                  saved_i + L.prev_row, s));
-  }
+  f.off = seqd::step_offsets(bs, d.steps);
+  RC(seqd::build_row_tables(f.off, tf, 0, false, saved_i + L.row_sample, saved_i + L.row_col, saved_i + L.row_token,
+                            saved_i + L.prev_row, s));
   float* skws = scratch + (size_t)d.B * d.V + 64;
   float* escore = skws + kAttSplitKFloats;   // raw attention scores of the current step [b][P]
   // tile counters of the one-launch products for steps of <= 16 rows (gemm_rows16_kernel): the tail of the slab area
   int* skctr = reinterpret_cast<int*>(skws + kAttSplitKWs);
+  const SkWs sk{skws, kAttSplitKWs, skctr};
   CAPNET_HIP_CHECK(hipMemsetAsync(skctr, 0, kSplitKCounters * sizeof(int), s));
   // ---- pack weights
-  const bool fac = d.cell == kCellFactored;
-  const GateOrderA go = fac ? GateOrderA{0, 1, 2, 3, 0} : GateOrderA{0, 1, 3, 2, 1};
-  {
-    CopyTable ct;      // one launch for the whole packing
-    if (fac) {
-      for (int g = 0; g < 4; ++g) {
-        ct.add(sv + L.Vcat + (size_t)g * F * XW, w.Vw[g], (size_t)F * XW);
-        ct.add(sv + L.Scat + (size_t)g * F * F, w.Sw[g], (size_t)F * F);
-        ct.add(sv + L.Ucat + (size_t)g * H * F, w.Uw[g], (size_t)H * F);
-        ct.add(sv + L.Wz + (size_t)g * H * H, w.Ww[g], (size_t)H * H);
-        ct.add(sv + L.bV + (size_t)g * F, w.Vb[g], F);
-        ct.add(sv + L.bS + (size_t)g * F, w.Sb[g], F);
-        ct.add(sv + L.bz + (size_t)g * H, w.Ub[g], H, w.Wb[g]);
-      }
-    } else {
-      ct.add(sv + L.Vcat, w.Vw[0], (size_t)4 * H * XW);          // weight_ih
-      ct.add(sv + L.Wz, w.Ww[0], (size_t)4 * H * H);             // weight_hh
-      ct.add(sv + L.bz, w.Vb[0], 4 * H, w.Wb[0]);                // bias_ih + bias_hh
-    }
-    ct.add(sv + L.Wz + (size_t)4 * H * H, w.dec_att_w, (size_t)A * H);
-    ct.add(sv + L.Wz + (size_t)(4 * H + A) * H, w.f_beta_w, (size_t)C * H);
-    ct.add(sv + L.bz + 4 * H, w.dec_att_b, A);
-    ct.add(sv + L.bz + 4 * H + A, w.f_beta_b, C);
-    RC(multi_copy(ct, s));
-  }
+  CopyTable ct;      // one launch for the whole packing
+  seqd::add_cell_copies(ct, w, d.cell, XW, F, H, sv + L.Vcat, sv + L.Scat, sv + L.Ucat, sv + L.Wz, sv + L.bV, sv + L.bS, sv + L.bz);
+  ct.add(sv + L.Wz + (size_t)4 * H * H, w.dec_att_w, (size_t)A * H);
+  ct.add(sv + L.Wz + (size_t)(4 * H + A) * H, w.f_beta_w, (size_t)C * H);
+  ct.add(sv + L.bz + 4 * H, w.dec_att_b, A);
+  ct.add(sv + L.bz + 4 * H + A, w.f_beta_b, C);
+  RC(multi_copy(ct, s));
   const bool one_product = chain_collapsed(d);
-  if (one_product) {
-    // US_g = U_g S_g;  Weff_g = US_g V_g;  bz[gate g] += U_g (S_g bV_g + bS_g)
-    RC(sgemm(false, false, H, F, F, sv + L.Ucat, F, sv + L.Scat, F, sv + L.US, F, nullptr, 0, 4, (long)H * F, (long)F * F,
-             (long)H * F, 0, 0, s));
-    RC(sgemm(false, false, H, XW, F, sv + L.US, F, sv + L.Vcat, XW, sv + L.Weff, XW, nullptr, 0, 4, (long)H * F,
-             (long)F * XW, (long)H * XW, 0, 0, s));
-    RC(sgemm_splitk_batched(false, true, 1, F, F, sv + L.bV, F, sv + L.Scat, F, sv + L.c1, F, sv + L.bS, 0, 4, F, (long)F * F, F, F,
-                            skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-    RC(sgemm_splitk_batched(false, true, 1, H, F, sv + L.c1, F, sv + L.Ucat, F, sv + L.bz, H, nullptr, 1, 4, F, (long)H * F, H, 0,
-                            skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-  }
+  // bz[gate g] += U_g (S_g bV_g + bS_g)
+  if (one_product) RC(seqd::chain_collapse(chain_of(d, L, sv), sv + L.US, sv + L.Weff, sv + L.c1, sv + L.bz, sk, s));
 
   // ---- time-invariant parts
   RC(global_avgpool(feat, sv + L.mean, d.B, P, C, s));
-  // (B x 512 x 2048: a handful of 64 x 64 tiles walking the whole K took 80 us each at 12 rows; K-split: 9)
-  RC(sgemm_splitk(false, true, d.B, H, C, sv + L.mean, C, w.init_h_w, C, sv + L.h0, H, w.init_h_b, 0, skws, kAttSplitKWs, s,
-                  skctr, kSplitKCounters));
-  RC(sgemm_splitk(false, true, d.B, H, C, sv + L.mean, C, w.init_c_w, C, sv + L.c0, H, w.init_c_b, 0, skws, kAttSplitKWs, s,
-                  skctr, kSplitKCounters));
+  RC(seqd::init_state(sv + L.mean, d.B, H, C, UpperInit{w.init_h_w, w.init_h_b, w.init_c_w, w.init_c_b}, sv + L.h0, sv + L.c0,
+                      sk, s));
   // (through the K-split entry: with few images its 128 x 128 tiles are few and the product is cut over the chip)
   RC(sgemm_splitk(false, true, d.B * P, A, C, feat, C, w.enc_att_w, C, sv + L.att1, A, w.enc_att_b, 0, skws, kAttSplitKWs, s,
                   skctr, kSplitKCounters));
   CAPNET_HIP_CHECK(hipMemsetAsync(sv + L.XA, 0, (size_t)N * XW * sizeof(float), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(alphas_bt, 0, (size_t)d.B * d.steps * P * sizeof(float), s));
-  RC(gather_inputs(captions, d.T, nullptr, emb, E, d.V, saved_i + L.row_sample, saved_i + L.row_col,
-                   saved_i + L.row_token, sv + L.XA, XW, 0, N, dropout_p, seed,
-                   training && dropout_p > 0.f, 0, err_flag, s));
-  f.tf = tf; f.captions = captions; f.feat = feat; f.emb = emb; f.Cw = Cw; f.Cb = Cb;
-  f.dropout_p = dropout_p; f.seed = seed; f.w_full = w.full_att_w; f.b_full = w.full_att_b;
-  f.sv = sv; f.scratch = scratch; f.skws = skws; f.escore = escore; f.hiddens = hiddens; f.alphas_bt = alphas_bt;
-  f.svi = saved_i; f.skctr = skctr; f.err_flag = err_flag;
-  f.one_product = one_product; f.fac = fac; f.go = go; f.s = s;
+  RC(gather_inputs(captions, d.T, nullptr, emb, E, d.V, saved_i + L.row_sample, saved_i + L.row_col, saved_i + L.row_token,
+                   sv + L.XA, XW, 0, N, dropout_p, seed, training && dropout_p > 0.f, 0, err_flag, s));
+  f.tf = tf; f.feat = feat; f.w_full = w.full_att_w; f.b_full = w.full_att_b;
+  f.fb = seqd::Feedback{captions, nullptr, emb, Cw, Cb, d.T, E, d.V, H, dropout_p, seed, saved_i + L.row_sample,
+                        saved_i + L.row_col, saved_i + L.row_token, scratch, err_flag};
+  f.sv = sv; f.sk = sk; f.escore = escore; f.hiddens = hiddens; f.alphas_bt = alphas_bt;
+  f.one_product = one_product; f.s = s;
   return kOk;
 }
 
@@ -272,10 +248,10 @@ int att_fwd_step(AttFwd& f, int t, const float* h_feed) {
   const std::vector<int>& off = f.off;
   const int E = d.E, F = d.F, H = d.H, A = d.A, P = d.P, C = d.C, ZW = L.ZW, XW = L.XW;
   float* sv = f.sv;
-  float* skws = f.skws;
-  int* skctr = f.skctr;
-  const bool fac = f.fac, one_product = f.one_product;
-  const GateOrderA go = f.go;
+  float* skws = f.sk.ws;
+  int* skctr = f.sk.ctr;
+  const bool fac = d.cell == kCellFactored, one_product = f.one_product;
+  const GateOrder go = seqd::gate_order(d.cell);
   hipStream_t s = f.s;
   const int b = off[t + 1] - off[t], r0 = off[t];
   const float* hprev = t > 0 ? f.hiddens + (size_t)off[t - 1] * H : sv + L.h0;
@@ -286,14 +262,7 @@ int att_fwd_step(AttFwd& f, int t, const float* h_feed) {
   RC(att_step_fwd(sv + L.att1, f.feat, Z + 4 * H, Z + 4 * H + A, ZW, f.w_full, f.b_full, b, P,
                   A, C, sv + L.alpha + (size_t)r0 * P, f.alphas_bt, d.steps, t,
                   sv + L.awe + (size_t)r0 * C, sv + L.XA + (size_t)r0 * XW + E, XW, f.escore, s));
-  if (t > 0 && !f.tf[t]) {
-    RC(sgemm_splitk(false, true, b, d.V, H, h_feed, H, f.Cw, H, f.scratch, d.V, f.Cb, 0, skws, kAttSplitKWs, s, skctr,
-                    kSplitKCounters));
-    RC(argmax_rows(f.scratch, b, d.V, d.V, f.svi + L.row_token + r0, s));
-    RC(gather_inputs(f.captions, d.T, nullptr, f.emb, E, d.V, f.svi + L.row_sample,
-                     f.svi + L.row_col, f.svi + L.row_token, sv + L.XA, XW, r0, r0 + b,
-                     f.dropout_p, f.seed, 0, 1, f.err_flag, s));
-  }
+  if (t > 0 && !f.tf[t]) RC(seqd::feed_back(f.fb, h_feed, b, r0, sv + L.XA, XW, f.sk, s));
   int x_slabs = 0;      // the input product's K-chunk partials, summed by the gate kernel (no hand-off inside the product's launch)
   // one product per step: [x | gated context] . Wx^T with Wx = U S V (the collapsed chain) or nn.LSTMCell's weight_ih
   const float* Wx = one_product ? sv + L.Weff : (fac ? nullptr : sv + L.Vcat);
@@ -303,14 +272,9 @@ int att_fwd_step(AttFwd& f, int t, const float* h_feed) {
       RC(sgemm_splitk(false, true, b, 4 * H, XW, sv + L.XA + (size_t)r0 * XW, XW, Wx, XW, Z, ZW, nullptr, 1, skws,
                       kAttSplitKWs, s, skctr, kSplitKCounters));
   } else {
-    // factored chain on [x | gated context]
-    RC(sgemm_splitk(false, true, b, 4 * F, XW, sv + L.XA + (size_t)r0 * XW, XW, sv + L.Vcat, XW,
-                    sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.bV, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-    RC(sgemm_splitk_batched(false, true, b, F, F, sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.Scat,
-                            F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.bS, 0, 4, F,
-                            (long)F * F, F, F, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
-    RC(sgemm_splitk_batched(false, true, b, H, F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.Ucat,
-                            F, Z, ZW, nullptr, 1, 4, F, (long)H * F, H, 0, skws, kAttSplitKWs, s, skctr, kSplitKCounters));
+    // factored chain on [x | gated context], added to the recurrent product in Z
+    RC(seqd::chain_fwd(chain_of(d, L, sv), sv + L.XA + (size_t)r0 * XW, b, sv + L.A1 + (size_t)r0 * 4 * F,
+                       sv + L.A2 + (size_t)r0 * 4 * F, Z, ZW, nullptr, 1, f.sk, s));
   }
   RC(lstm_pointwise_fwd(Z, ZW, cprev, sv + L.Cst + (size_t)r0 * H, f.hiddens + (size_t)r0 * H, b, H,
                         go.gi, go.gf, go.go, go.gg, go.tanh_out, s, x_slabs ? skws : nullptr, x_slabs));
@@ -325,45 +289,29 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
   RC(check(d, bs));
   CAPNET_REQUIRE(dH && hiddens && feat && saved && saved_i && scratch, "att_seq_backward: null argument");
   const bool fac = d.cell == kCellFactored;
-  const GateOrderA go = fac ? GateOrderA{0, 1, 2, 3, 0} : GateOrderA{0, 1, 3, 2, 1};
+  const GateOrder go = seqd::gate_order(d.cell);
   CAPNET_REQUIRE(g.dVcat && g.dWz && g.dbz && g.dWe && g.dbe && g.dwf && g.dbf && g.dWih && g.dbih &&
                      g.dWic && g.dbic && g.dEmb && (!fac || (g.dbV && g.dScat && g.dbS && g.dUcat)),
                  "att_seq_backward: null gradient buffer");
   const ALayout L = make_alayout(d);
+  const ABwdLayout S = make_abwd_layout(d);
   const int E = d.E, F = d.F, H = d.H, N = d.N, A = d.A, P = d.P, C = d.C, ZW = L.ZW, XW = L.XW;
   const float* sv = saved;
-  std::vector<int> off(d.steps + 1, 0);
-  for (int t = 0; t < d.steps; ++t) off[t + 1] = off[t] + bs[t];
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  float* Zb = scratch + take((size_t)N * ZW);
-  float* dA2 = scratch + take(fac ? (size_t)N * 4 * F : 4);
-  float* dA1 = scratch + take(fac ? (size_t)N * 4 * F : 4);
+  const std::vector<int> off = seqd::step_offsets(bs, d.steps);
   const bool one_product = chain_collapsed(d);
-  float* A1c = scratch + take(one_product ? (size_t)N * 4 * F : 4);     // the chain's intermediate rows, formed here
-  float* A2c = scratch + take(one_product ? (size_t)N * 4 * F : 4);
-  const float* A1 = one_product ? A1c : sv + L.A1;
-  const float* A2 = one_product ? A2c : sv + L.A2;
-  float* dXA = scratch + take((size_t)N * XW);
-  float* Hprev = scratch + take((size_t)N * H);
-  float* dh_rec = scratch + take((size_t)d.B * H);
-  float* dc = scratch + take((size_t)d.B * H);
-  float* dalpha_part = scratch + take((size_t)d.B * (C / 256) * P);
-  float* datt1 = scratch + take((size_t)d.B * P * A);
-  float* dwf_rows = scratch + take((size_t)N * A);
-  float* dbf_rows = scratch + take((size_t)N);
-  float* de_all = scratch + take((size_t)N * P);   // softmax-backward scores of every row
-  float* skws = scratch + take(kAttSplitKFloats);
+  const Chain ch = chain_of(d, L, sv);
+  float *Zb = scratch + S.Zb, *dA2 = scratch + S.dA2, *dA1 = scratch + S.dA1, *dXA = scratch + S.dXA, *Hprev = scratch + S.Hprev;
+  float *dh_rec = scratch + S.dh_rec, *dc = scratch + S.dc, *dalpha_part = scratch + S.dalpha_part, *datt1 = scratch + S.datt1;
+  float *dwf_rows = scratch + S.dwf_rows, *dbf_rows = scratch + S.dbf_rows, *de_all = scratch + S.de_all;
+  float *skws = scratch + S.skws, *dh_slabs_ws = scratch + S.dh_slabs;
+  const size_t dh_ws_floats = S.dh_ws_floats;
+  const float* A1 = one_product ? scratch + S.A1c : sv + L.A1;
+  const float* A2 = one_product ? scratch + S.A2c : sv + L.A2;
   int* skctr = reinterpret_cast<int*>(skws + kAttSplitKWs);
   CAPNET_HIP_CHECK(hipMemsetAsync(skctr, 0, kSplitKCounters * sizeof(int), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(dh_rec, 0, (size_t)d.B * H * sizeof(float), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(dc, 0, (size_t)d.B * H * sizeof(float), s));
 
-  // dh_{t-1} = dZ_t . Wz has K = 4H + A + C: eighteen 256-k chunks. Its partials stay in the slab area and the gate kernel of
-  // step t - 1 -- the next launch -- sums them (<= 16 rows: the hand-off inside the launch was 8 of the product's 12.6 us;
-  // up to 128 rows: a splitk_reduce launch less per step)
-  const size_t dh_ws_floats = d.B <= 128 ? (size_t)cdiv(ZW, 64) * d.B * H : 4;
-  float* dh_slabs_ws = scratch + take(dh_ws_floats);
   int dh_slabs = 0;
   for (int t = d.steps - 1; t >= 0; --t) {
     const int b = bs[t], r0 = off[t];
@@ -406,27 +354,12 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
   RC(sgemm_splitk(true, false, ZW, H, N, Zb, ZW, Hprev, H, g.dWz, H, nullptr, 0, skws, kAttSplitKWs, s));
   RC(colsum(Zb, ZW, N, ZW, g.dbz, 0, s));
   if (one_product) {
-    // all rows at once: A1 = XA V^T + bV, A2_g = A1_g S_g^T + bS_g;  dA2_g = dgates_g U_g, dA1_g = dA2_g S_g
-    RC(sgemm_splitk(false, true, N, 4 * F, XW, sv + L.XA, XW, sv + L.Vcat, XW, A1c, 4 * F, sv + L.bV, 0, skws, kAttSplitKWs, s,
-                    skctr, kSplitKCounters));
-    RC(sgemm(false, true, N, F, F, A1c, 4 * F, sv + L.Scat, F, A2c, 4 * F, sv + L.bS, 0, 4, F, (long)F * F, F, F, 0, s));
-    RC(sgemm(false, false, N, F, H, Zb, ZW, sv + L.Ucat, F, dA2, 4 * F, nullptr, 0, 4, H, (long)H * F, F, 0, 0, s));
-    RC(sgemm(false, false, N, F, F, dA2, 4 * F, sv + L.Scat, F, dA1, 4 * F, nullptr, 0, 4, F, (long)F * F, F, 0, 0, s));
+    // the rows the steps did not form: A1, A2 and their gradients
+    RC(seqd::chain_rows(ch, sv + L.XA, N, scratch + S.A1c, scratch + S.A2c, SkWs{skws, kAttSplitKWs, skctr}, s));
+    RC(seqd::chain_bwd_rows(ch, Zb, ZW, N, dA2, dA1, s));
   }
-  if (fac) {
-    RC(sgemm(true, false, H, F, N, Zb, ZW, A2, 4 * F, g.dUcat, F, nullptr, 0, 4, H, F,
-             (long)H * F, 0, 0, s));
-    RC(colsum(dA2, 4 * F, N, 4 * F, g.dbS, 0, s));
-    RC(sgemm(true, false, F, F, N, dA2, 4 * F, A1, 4 * F, g.dScat, F, nullptr, 0, 4, F, F,
-             (long)F * F, 0, 0, s));
-    RC(colsum(dA1, 4 * F, N, 4 * F, g.dbV, 0, s));
-    RC(sgemm(true, false, 4 * F, XW, N, dA1, 4 * F, sv + L.XA, XW, g.dVcat, XW, nullptr, 0, 1, 0, 0, 0,
-             0, 0, s));
-  } else {
-    // d weight_ih [4H][E+C] = d gates^T . [x | ctx]   (d bias_ih = d bias_hh = dbz[0:4H])
-    RC(sgemm(true, false, 4 * H, XW, N, Zb, ZW, sv + L.XA, XW, g.dVcat, XW, nullptr, 0, 1, 0, 0, 0,
-             0, 0, s));
-  }
+  if (fac) RC(seqd::chain_wgrads(ch, Zb, ZW, sv + L.XA, A1, A2, dA2, dA1, N, seqd::ChainGrads{g.dVcat, g.dbV, g.dScat, g.dbS, g.dUcat}, s));
+  else RC(seqd::lstm_input_wgrad(Zb, ZW, sv + L.XA, XW, H, N, g.dVcat, s));     // (d bias_ih = d bias_hh = dbz[0:4H])
   RC(colsum(dwf_rows, A, N, A, g.dwf, 0, s));
   RC(colsum(dbf_rows, 1, N, 1, g.dbf, 0, s));
   // encoder_att: d att1 summed per sample over its steps in one pass over att1
@@ -435,15 +368,10 @@ int att_seq_backward(const AttDims& d, const int* bs, const float* dH, const flo
   RC(sgemm_splitk(true, false, A, C, d.B * P, datt1, A, feat, C, g.dWe, C, nullptr, 0, skws, kAttSplitKWs, s));
   RC(colsum(datt1, A, d.B * P, A, g.dbe, 0, s, skws, kAttSplitKWs));
   // init_h / init_c: dh0 = dh_rec, dc0 = dc (all B rows are alive at t = 0)
-  RC(sgemm(true, false, H, C, d.B, dh_rec, H, sv + L.mean, C, g.dWih, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-  RC(colsum(dh_rec, H, d.B, H, g.dbih, 0, s));
-  RC(sgemm(true, false, H, C, d.B, dc, H, sv + L.mean, C, g.dWic, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-  RC(colsum(dc, H, d.B, H, g.dbic, 0, s));
+  RC(seqd::init_state_grad(dh_rec, dc, sv + L.mean, d.B, H, C, UpperInitGrads{g.dWih, g.dbih, g.dWic, g.dbic}, s));
   CAPNET_HIP_CHECK(hipMemsetAsync(g.dEmb, 0, (size_t)d.V * E * sizeof(float), s));
-  RC(scatter_input_grad(dXA, XW, N, E, saved_i + L.row_sample, saved_i + L.row_col,
-                        saved_i + L.row_token, g.dEmb, nullptr, d.V, dropout_p, seed,
-                        training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kAttSplitKWs));
-  return kOk;
+  return scatter_input_grad(dXA, XW, N, E, saved_i + L.row_sample, saved_i + L.row_col, saved_i + L.row_token, g.dEmb, nullptr, d.V,
+                            dropout_p, seed, training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kAttSplitKWs);
 }
 
 // ---- stacked attention decoder (capnet.stacked_att) -------------------------------------------------------------------
@@ -497,13 +425,21 @@ size_t att_stacked_fwd_scratch_floats(const AttDims& d, int nlayers) {
   (void)nlayers;           // the upper layers work in the attention cell's slab area
   return att_fwd_scratch_floats(d);
 }
+// scratch of the stacked backward: layer 0's or an upper layer's, whichever is larger, then the gradient of an upper
+// layer's initial state
+struct StackedBwdLayout { size_t dh0, dc0, total; };
+static StackedBwdLayout make_stacked_bwd_layout(const AttDims& d) {
+  Carve take;
+  const size_t a = make_abwd_layout(d).total, u = seqd::make_bwd_layout(upper_ext_dims(d), 1).total;
+  take(a > u ? a : u);
+  StackedBwdLayout S;
+  S.dh0 = take((size_t)d.B * d.H);
+  S.dc0 = take((size_t)d.B * d.H);
+  S.total = take.o;
+  return S;
+}
 size_t att_stacked_bwd_scratch_floats(const AttDims& d, int nlayers) {
-  size_t n = att_bwd_scratch_floats(d);
-  if (nlayers > 1) {
-    const size_t u = seqd::seq_bwd_upper_scratch_floats(upper_ext_dims(d));
-    n = (n > u ? n : u) + 4 + 2 * (size_t)d.B * d.H;
-  }
-  return n;
+  return nlayers > 1 ? make_stacked_bwd_layout(d).total : att_bwd_scratch_floats(d);
 }
 
 int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const unsigned char* tf, const long long* captions,
@@ -519,17 +455,14 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
   AttFwd f;
   RC(att_fwd_begin(f, d, bs, tf, captions, feat, emb, w0, Cw, Cb, dropout_p, seed, training, saved[0], saved_i[0], scratch,
                    hiddens[0], alphas_bt, err_flag, s));
-  const int B = d.B, H = d.H, F = d.F, C = d.C;
+  const int B = d.B, H = d.H, C = d.C;
   if (nlayers == 1) {
     for (int t = 0; t < d.steps; ++t) RC(att_fwd_step(f, t, t > 0 ? hiddens[0] + (size_t)f.off[t - 1] * H : nullptr));
     return kOk;
   }
   const SeqDims ud = upper_ext_dims(d);
   const UpperExtra ux = upper_extra(ud);
-  std::vector<int> bse(ud.steps), offe(ud.steps + 1, 0);
-  bse[0] = B;
-  for (int t = 0; t < d.steps; ++t) bse[t + 1] = bs[t];
-  for (int t = 0; t < ud.steps; ++t) offe[t + 1] = offe[t] + bse[t];
+  const std::vector<int> bse = seqd::with_state_step(B, bs, d.steps), offe = seqd::step_offsets(bse.data(), ud.steps);
   const bool fused = fused_upper_enabled();
   const bool drop = training && dropout_p > 0.f;
   const float* mean = f.sv + f.L.mean;
@@ -539,29 +472,16 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
     c.d = ud;
     c.L = seqd::make_layout(ud);
     c.sv = saved[l]; c.svi = saved_i[l]; c.hid = hiddens[l];
-    SeqMeta m;
-    m.N = ud.N; m.steps = ud.steps; m.has_features = 0;
-    for (int t = 0; t <= ud.steps; ++t) m.off[t] = offe[t];
-    m.tf[0] = 1;
-    for (int t = 0; t < d.steps; ++t) m.tf[t + 1] = tf[t] ? 1 : 0;
-    RC(build_rows(m, c.svi + c.L.row_sample, c.svi + c.L.row_col, c.svi + c.L.row_token, c.svi + c.L.prev_row, s));
+    RC(seqd::build_row_tables(offe, tf, 0, true, c.svi + c.L.row_sample, c.svi + c.L.row_col, c.svi + c.L.row_token,
+                              c.svi + c.L.prev_row, s));
     RC(seqd::pack_layer(c, wu[l - 1], bse.data(), s));
     // the leading state step: h0 = init_h{l}(mean), c0 = init_c{l}(mean)
-    RC(sgemm_splitk(false, true, B, H, C, mean, C, iu[l - 1].init_h_w, C, c.hid, H, iu[l - 1].init_h_b, 0, f.skws, kAttSplitKWs, s,
-                    f.skctr, kSplitKCounters));
-    RC(sgemm_splitk(false, true, B, H, C, mean, C, iu[l - 1].init_c_w, C, c.sv + c.L.Cst, H, iu[l - 1].init_c_b, 0, f.skws,
-                    kAttSplitKWs, s, f.skctr, kSplitKCounters));
+    RC(seqd::init_state(mean, B, H, C, iu[l - 1], c.hid, c.sv + c.L.Cst, f.sk, s));
     if (fused && d.cell == kCellFactored) {
+      // beff = bU + bW, then += U_g c1_g
       float* sv = c.sv;
-      RC(sgemm(false, false, H, F, F, sv + c.L.Ucat, F, sv + c.L.Scat, F, sv + ux.US, F, nullptr, 0, 4, (long)H * F, (long)F * F,
-               (long)H * F, 0, 0, s));
-      RC(sgemm(false, false, H, H, F, sv + ux.US, F, sv + c.L.Vcat, H, sv + ux.Weff, H, nullptr, 0, 4, (long)H * F,
-               (long)F * H, (long)H * H, 0, 0, s));
-      RC(sgemm_splitk_batched(false, true, 1, F, F, sv + c.L.bV, F, sv + c.L.Scat, F, sv + ux.c1, F, sv + c.L.bS, 0, 4, F,
-                              (long)F * F, F, F, f.skws, kAttSplitKWs, s, f.skctr, kSplitKCounters));
       CAPNET_HIP_CHECK(hipMemcpyAsync(sv + ux.beff, sv + c.L.bUW, (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, s));
-      RC(sgemm_splitk_batched(false, true, 1, H, F, sv + ux.c1, F, sv + c.L.Ucat, F, sv + ux.beff, H, nullptr, 1, 4, F,
-                              (long)H * F, H, 0, f.skws, kAttSplitKWs, s, f.skctr, kSplitKCounters));
+      RC(seqd::chain_collapse(seqd::chain_of(ud, c.L, sv), sv + ux.US, sv + ux.Weff, sv + ux.c1, sv + ux.beff, f.sk, s));
     }
   }
   const seqd::LayerCtx& top = up[nlayers - 1];
@@ -582,8 +502,8 @@ int att_seq_forward_stacked(const AttDims& d, int nlayers, const int* bs, const 
         continue;
       }
       RC(rows_dropout(below, c.sv + c.L.X + (size_t)B * H, r0, r1, H, dropout_p, seed, l, drop, s));
-      RC(seqd::input_chain(c.d, c.L, c.sv, B + r0, B + r1, f.skws, kSplitKWs, s, f.skctr));
-      RC(seqd::recur(c, offe, bse.data(), t + 1, t1 + 1, f.skws, f.skctr, err_flag, s));
+      RC(seqd::input_chain(c.d, c.L, c.sv, B + r0, B + r1, SkWs{f.sk.ws, kSplitKWs, f.sk.ctr}, s));
+      RC(seqd::recur(c, offe, bse.data(), t + 1, t1 + 1, f.sk.ws, f.sk.ctr, err_flag, s));
     }
     t = t1;
   }
@@ -605,14 +525,9 @@ int att_seq_backward_stacked(const AttDims& d, int nlayers, const int* bs, const
     RC(check(d, bs));
     const SeqDims ud = upper_ext_dims(d);
     const int B = d.B, H = d.H, C = d.C;
-    std::vector<int> bse(ud.steps);
-    bse[0] = B;
-    for (int t = 0; t < d.steps; ++t) bse[t + 1] = bs[t];
-    size_t o = att_bwd_scratch_floats(d);
-    const size_t u = seqd::seq_bwd_upper_scratch_floats(ud);
-    o = ((o > u ? o : u) + 3) / 4 * 4;
-    float* dh0 = scratch + o;
-    float* dc0 = dh0 + (size_t)B * H;
+    const std::vector<int> bse = seqd::with_state_step(B, bs, d.steps);
+    const StackedBwdLayout S = make_stacked_bwd_layout(d);
+    float *dh0 = scratch + S.dh0, *dc0 = scratch + S.dc0;
     const float* mean = saved[0] + make_alayout(d).mean;
     for (int l = nlayers - 1; l >= 1; --l) {
       CAPNET_REQUIRE(dH_work[l - 1] && hiddens[l] && saved[l] && saved_i[l], "att_seq_backward_stacked: null buffer of layer %d", l);
@@ -621,10 +536,7 @@ int att_seq_backward_stacked(const AttDims& d, int nlayers, const int* bs, const
       RC(seqd::seq_backward_upper(ud, bse.data(), dH, hiddens[l], saved[l], saved_i[l], scratch, gu[l - 1], dropout_p, seed,
                                   training, l, dH_work[l - 1], dh0, dc0, s));
       // init_h{l} / init_c{l}: all B rows are alive at the first step
-      RC(sgemm(true, false, H, C, B, dh0, H, mean, C, gi.dWih, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-      RC(colsum(dh0, H, B, H, gi.dbih, 0, s));
-      RC(sgemm(true, false, H, C, B, dc0, H, mean, C, gi.dWic, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-      RC(colsum(dc0, H, B, H, gi.dbic, 0, s));
+      RC(seqd::init_state_grad(dh0, dc0, mean, B, H, C, gi, s));
       dH = dH_work[l - 1];
     }
   }

@@ -23,10 +23,45 @@ namespace capnet {
 
 namespace seqd {
 
+std::vector<int> step_offsets(const int* batch_sizes, int steps) {
+  std::vector<int> off(steps + 1, 0);
+  for (int t = 0; t < steps; ++t) off[t + 1] = off[t] + batch_sizes[t];
+  return off;
+}
+
+std::vector<int> with_state_step(int B, const int* batch_sizes, int steps) {
+  std::vector<int> bse(steps + 1, B);
+  for (int t = 0; t < steps; ++t) bse[t + 1] = batch_sizes[t];
+  return bse;
+}
+
+int check_batch_sizes(const char* who, const int* batch_sizes, int steps, int B, int N) {
+  CAPNET_REQUIRE(batch_sizes != nullptr, "%s: null batch_sizes", who);
+  long n = 0;
+  int prev = B;
+  for (int t = 0; t < steps; ++t) {
+    CAPNET_REQUIRE(batch_sizes[t] > 0 && batch_sizes[t] <= prev,
+                   "%s: batch_sizes must be positive and non-increasing (step %d: %d after %d)", who, t, batch_sizes[t], prev);
+    prev = batch_sizes[t];
+    n += batch_sizes[t];
+  }
+  CAPNET_REQUIRE(n == N, "%s: sum(batch_sizes)=%ld != N=%d", who, n, N);
+  return kOk;
+}
+
+int build_row_tables(const std::vector<int>& off, const unsigned char* tf_mask, int has_features, bool lead, int* row_sample,
+                     int* row_col, int* row_token, int* prev_row, hipStream_t s) {
+  SeqMeta m;
+  m.steps = (int)off.size() - 1; m.N = off.back(); m.has_features = has_features;
+  for (int t = 0; t <= m.steps; ++t) m.off[t] = off[t];
+  if (lead) m.tf[0] = 1;
+  for (int t = lead; t < m.steps; ++t) m.tf[t] = tf_mask[t - lead] ? 1 : 0;
+  return build_rows(m, row_sample, row_col, row_token, prev_row, s);
+}
+
 Layout make_layout(const SeqDims& d) {
   Layout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
+  Carve take, itake;
   const size_t N = d.N, E = d.E, F = d.F, H = d.H;
   L.X = take(N * E);
   L.G = take(N * 4 * H);
@@ -47,42 +82,44 @@ Layout make_layout(const SeqDims& d) {
     L.A1 = L.A2 = L.Scat = L.Ucat = L.bV = L.bS = 0;
     L.Vcat = take(4 * H * E);  // weight_ih copy (kept so backward sees the forward's weights)
   }
-  L.total = o;
-  size_t io = 0;
-  auto itake = [&](size_t n) { size_t r = io; io += (n + 3) / 4 * 4; return r; };
+  L.total = take.o;
   L.row_sample = itake(N);
   L.row_col = itake(N);
   L.row_token = itake(N);
   L.prev_row = itake(N);
   L.ctl = itake(lstm_persist_ctl_ints());
-  L.itotal = io;
+  L.itotal = itake.o;
   return L;
+}
+
+// scratch of seq_backward_layer (lead: the chain's rows of all steps, for any batch_sizes[0])
+BwdLayout make_bwd_layout(const SeqDims& d, int lead) {
+  BwdLayout S;
+  Carve take;
+  const size_t N = d.N, F = d.F, H = d.H;
+  const bool fac = d.cell == kCellFactored;
+  S.dPre = take(N * 4 * H);
+  S.Hprev = take(N * H);
+  S.dh_rec = take((size_t)d.B * H);
+  S.dc = take((size_t)d.B * H);
+  S.dX = take(N * d.E);
+  S.dA2 = take(fac ? N * 4 * F : 0);
+  S.dA1 = take(fac ? N * 4 * F : 0);
+  S.skws = take(kSplitKFloats);
+  S.A1c = take(fac && lead ? N * 4 * F : 0);
+  S.A2c = take(fac && lead ? N * 4 * F : 0);
+  S.total = take.o;
+  return S;
 }
 
 int check_dims(const SeqDims& d, const int* batch_sizes) {
   CAPNET_REQUIRE(d.B > 0 && d.T > 0 && d.steps > 0 && d.N > 0 && d.E > 0 && d.H > 0 && d.V > 0,
-                 "decoder: bad dims B=%d T=%d steps=%d N=%d E=%d H=%d V=%d", d.B, d.T, d.steps,
-                 d.N, d.E, d.H, d.V);
+                 "decoder: bad dims B=%d T=%d steps=%d N=%d E=%d H=%d V=%d", d.B, d.T, d.steps, d.N, d.E, d.H, d.V);
   CAPNET_REQUIRE(d.cell == kCellLSTM || d.F > 0, "decoder: factored size");
-  CAPNET_REQUIRE(batch_sizes != nullptr, "decoder: null batch_sizes");
-  long n = 0;
-  int prev = d.B;
-  for (int t = 0; t < d.steps; ++t) {
-    CAPNET_REQUIRE(batch_sizes[t] > 0 && batch_sizes[t] <= prev,
-                   "decoder: batch_sizes must be positive and non-increasing (step %d: %d after %d)",
-                   t, batch_sizes[t], prev);
-    prev = batch_sizes[t];
-    n += batch_sizes[t];
-  }
-  CAPNET_REQUIRE(n == d.N, "decoder: sum(batch_sizes)=%ld != N=%d", n, d.N);
+  RC(check_batch_sizes("decoder", batch_sizes, d.steps, d.B, d.N));
   CAPNET_REQUIRE(d.steps <= d.T + (d.has_features ? 1 : 0),
                  "decoder: %d steps need more caption columns than T=%d", d.steps, d.T);
   return kOk;
-}
-
-GateOrder gate_order(int cell) {
-  // FactoredLSTM packs i,f,o,c~ ; nn.LSTMCell stores i,f,g,o
-  return cell == kCellFactored ? GateOrder{0, 1, 2, 3, 0} : GateOrder{0, 1, 3, 2, 1};
 }
 
 int copy_d2d(float* dst, const float* src, size_t n, hipStream_t s) {
@@ -90,33 +127,88 @@ int copy_d2d(float* dst, const float* src, size_t n, hipStream_t s) {
   return kOk;
 }
 
-// gate pre-activations of rows [r0, r1) from their inputs X. ws: slab workspace of the per-step
-// (few rows) products; the all-rows call up front has enough tiles for the plain kernel.
-int input_chain(const SeqDims& d, const Layout& L, float* sv, int r0, int r1, float* ws,
-                size_t ws_floats, hipStream_t s, int* ctr) {
+static size_t nctr(const SkWs& k) { return k.ctr ? kSplitKCounters : 0; }
+
+int chain_fwd(const Chain& c, const float* X, int n, float* A1, float* A2, float* out, long ldo, const float* bias, int accumulate,
+              const SkWs& k, hipStream_t s) {
+  const int XW = c.XW, F = c.F, H = c.H;
+  RC(sgemm_splitk(false, true, n, 4 * F, XW, X, XW, c.Vcat, XW, A1, 4 * F, c.bV, 0, k.ws, k.floats, s, k.ctr, nctr(k)));
+  RC(sgemm_splitk_batched(false, true, n, F, F, A1, 4 * F, c.Scat, F, A2, 4 * F, c.bS, 0, 4, F, (long)F * F, F, F, k.ws, k.floats,
+                          s, k.ctr, nctr(k)));
+  return sgemm_splitk_batched(false, true, n, H, F, A2, 4 * F, c.Ucat, F, out, ldo, bias, accumulate, 4, F, (long)H * F, H,
+                              bias ? H : 0, k.ws, k.floats, s, k.ctr, nctr(k));
+}
+
+int chain_collapse(const Chain& c, float* US, float* Weff, float* c1, float* bias, const SkWs& k, hipStream_t s) {
+  const int XW = c.XW, F = c.F, H = c.H;
+  RC(sgemm(false, false, H, F, F, c.Ucat, F, c.Scat, F, US, F, nullptr, 0, 4, (long)H * F, (long)F * F, (long)H * F, 0, 0, s));
+  RC(sgemm(false, false, H, XW, F, US, F, c.Vcat, XW, Weff, XW, nullptr, 0, 4, (long)H * F, (long)F * XW, (long)H * XW, 0, 0, s));
+  RC(sgemm_splitk_batched(false, true, 1, F, F, c.bV, F, c.Scat, F, c1, F, c.bS, 0, 4, F, (long)F * F, F, F, k.ws, k.floats, s,
+                          k.ctr, nctr(k)));
+  return sgemm_splitk_batched(false, true, 1, H, F, c1, F, c.Ucat, F, bias, H, nullptr, 1, 4, F, (long)H * F, H, 0, k.ws, k.floats,
+                              s, k.ctr, nctr(k));
+}
+
+int chain_rows(const Chain& c, const float* X, int n, float* A1, float* A2, const SkWs& k, hipStream_t s) {
+  const int XW = c.XW, F = c.F;
+  RC(sgemm_splitk(false, true, n, 4 * F, XW, X, XW, c.Vcat, XW, A1, 4 * F, c.bV, 0, k.ws, k.floats, s, k.ctr, nctr(k)));
+  return sgemm(false, true, n, F, F, A1, 4 * F, c.Scat, F, A2, 4 * F, c.bS, 0, 4, F, (long)F * F, F, F, 0, s);
+}
+
+int chain_bwd_rows(const Chain& c, const float* dG, long ldg, int n, float* dA2, float* dA1, hipStream_t s) {
+  const int F = c.F, H = c.H;
+  RC(sgemm(false, false, n, F, H, dG, ldg, c.Ucat, F, dA2, 4 * F, nullptr, 0, 4, H, (long)H * F, F, 0, 0, s));
+  return sgemm(false, false, n, F, F, dA2, 4 * F, c.Scat, F, dA1, 4 * F, nullptr, 0, 4, F, (long)F * F, F, 0, 0, s);
+}
+
+int chain_wgrads(const Chain& c, const float* dG, long ldg, const float* X, const float* A1, const float* A2, const float* dA2,
+                 const float* dA1, int n, const ChainGrads& g, hipStream_t s) {
+  const int XW = c.XW, F = c.F, H = c.H;
+  // dU_g = dG_g^T . A2_g ; dS_g = dA2_g^T . A1_g ; dVcat = dA1^T . X
+  RC(sgemm(true, false, H, F, n, dG, ldg, A2, 4 * F, g.dUcat, F, nullptr, 0, 4, H, F, (long)H * F, 0, 0, s));
+  RC(colsum(dA2, 4 * F, n, 4 * F, g.dbS, 0, s));
+  RC(sgemm(true, false, F, F, n, dA2, 4 * F, A1, 4 * F, g.dScat, F, nullptr, 0, 4, F, F, (long)F * F, 0, 0, s));
+  RC(colsum(dA1, 4 * F, n, 4 * F, g.dbV, 0, s));
+  return sgemm(true, false, 4 * F, XW, n, dA1, 4 * F, X, XW, g.dVcat, XW, nullptr, 0, 1, 0, 0, 0, 0, 0, s);
+}
+
+int lstm_input_wgrad(const float* dG, long ldg, const float* X, int XW, int H, int n, float* dWih, hipStream_t s) {
+  return sgemm(true, false, 4 * H, XW, n, dG, ldg, X, XW, dWih, XW, nullptr, 0, 1, 0, 0, 0, 0, 0, s);
+}
+
+// ws: slab workspace of the per-step (few rows) products; the all-rows call up front has enough tiles for the plain kernel.
+int input_chain(const SeqDims& d, const Layout& L, float* sv, int r0, int r1, const SkWs& k, hipStream_t s) {
   const int n = r1 - r0;
   if (n <= 0) return kOk;
   const int E = d.E, F = d.F, H = d.H;
-  if (d.cell == kCellFactored) {
-    // A1 = X . Vcat^T + bV                          [n x 4F]
-    RC(sgemm_splitk(false, true, n, 4 * F, E, sv + L.X + (size_t)r0 * E, E, sv + L.Vcat, E,
-                    sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.bV, 0, n <= 128 ? ws : nullptr,
-                    ws_floats, s, ctr, kSplitKCounters));
-    // A2[:, g] = A1[:, g] . S_g^T + bS_g             4 gate groups
-    RC(sgemm_splitk_batched(false, true, n, F, F, sv + L.A1 + (size_t)r0 * 4 * F, 4 * F, sv + L.Scat, F,
-                            sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.bS, 0, 4, F, (long)F * F, F,
-                            F, n <= 128 ? ws : nullptr, ws_floats, s, ctr, kSplitKCounters));
-    // G[:, g] = A2[:, g] . U_g^T + (bU_g + bW_g)
-    RC(sgemm_splitk_batched(false, true, n, H, F, sv + L.A2 + (size_t)r0 * 4 * F, 4 * F, sv + L.Ucat, F,
-                            sv + L.G + (size_t)r0 * 4 * H, 4 * H, sv + L.bUW, 0, 4, F, (long)H * F, H,
-                            H, n <= 128 ? ws : nullptr, ws_floats, s, ctr, kSplitKCounters));
-  } else {
-    // G = X . W_ih^T + (b_ih + b_hh)
-    RC(sgemm_splitk(false, true, n, 4 * H, E, sv + L.X + (size_t)r0 * E, E, sv + L.Vcat, E,
-                    sv + L.G + (size_t)r0 * 4 * H, 4 * H, sv + L.bUW, 0, n <= 128 ? ws : nullptr,
-                    ws_floats, s, ctr, kSplitKCounters));
-  }
-  return kOk;
+  const SkWs kn{n <= 128 ? k.ws : nullptr, k.floats, k.ctr};
+  const float* X = sv + L.X + (size_t)r0 * E;
+  float* G = sv + L.G + (size_t)r0 * 4 * H;
+  if (d.cell == kCellFactored)
+    return chain_fwd(chain_of(d, L, sv), X, n, sv + L.A1 + (size_t)r0 * 4 * F, sv + L.A2 + (size_t)r0 * 4 * F, G, 4 * H, sv + L.bUW,
+                     0, kn, s);
+  // G = X . W_ih^T + (b_ih + b_hh)
+  return sgemm_splitk(false, true, n, 4 * H, E, X, E, sv + L.Vcat, E, G, 4 * H, sv + L.bUW, 0, kn.ws, kn.floats, s, kn.ctr, nctr(kn));
+}
+
+int init_state(const float* mean, int B, int H, int C, const UpperInit& w, float* h0, float* c0, const SkWs& k, hipStream_t s) {
+  // (B x 512 x 2048: a handful of 64 x 64 tiles walking the whole K took 80 us each at 12 rows; K-split: 9)
+  RC(sgemm_splitk(false, true, B, H, C, mean, C, w.init_h_w, C, h0, H, w.init_h_b, 0, k.ws, k.floats, s, k.ctr, nctr(k)));
+  return sgemm_splitk(false, true, B, H, C, mean, C, w.init_c_w, C, c0, H, w.init_c_b, 0, k.ws, k.floats, s, k.ctr, nctr(k));
+}
+
+int init_state_grad(const float* dh0, const float* dc0, const float* mean, int B, int H, int C, const UpperInitGrads& g, hipStream_t s) {
+  RC(sgemm(true, false, H, C, B, dh0, H, mean, C, g.dWih, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+  RC(colsum(dh0, H, B, H, g.dbih, 0, s));
+  RC(sgemm(true, false, H, C, B, dc0, H, mean, C, g.dWic, C, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
+  return colsum(dc0, H, B, H, g.dbic, 0, s);
+}
+
+int feed_back(const Feedback& f, const float* h_prev, int b, int r0, float* X, long ldx, const SkWs& k, hipStream_t s) {
+  RC(sgemm_splitk(false, true, b, f.V, f.H, h_prev, f.H, f.Cw, f.H, f.logits, f.V, f.Cb, 0, k.ws, k.floats, s, k.ctr, nctr(k)));
+  RC(argmax_rows(f.logits, b, f.V, f.V, f.row_token + r0, s));
+  return gather_inputs(f.captions, f.T, f.features, f.emb, f.E, f.V, f.row_sample, f.row_col, f.row_token, X, ldx, r0, r0 + b,
+                       f.dropout_p, f.seed, 0, 1, f.err_flag, s);
 }
 
 }  // namespace seqd
@@ -128,42 +220,18 @@ size_t seq_saved_ints(const SeqDims& d) { return make_layout(d).itotal; }
 size_t seq_saved_cell_offset(const SeqDims& d) { return make_layout(d).Cst; }
 
 size_t seq_fwd_scratch_floats(const SeqDims& d) { return (size_t)d.B * d.V + 64 + kSplitKFloats; }
-
-size_t seq_bwd_scratch_floats(const SeqDims& d) {
-  const size_t N = d.N;
-  size_t n = N * 4 * d.H + N * d.H + 2 * (size_t)d.B * d.H + N * d.E + 256 + kSplitKFloats;
-  if (d.cell == kCellFactored) n += 2 * N * 4 * d.F;
-  return n;
-}
+size_t seq_bwd_scratch_floats(const SeqDims& d) { return make_bwd_layout(d, 0).total; }
 
 namespace seqd {
-// gate-concatenated weight copies, the fused-step fragment image and the persistent kernel's image
 int pack_layer(LayerCtx& c, const SeqWeights& w, const int* batch_sizes, hipStream_t s) {
   const SeqDims& d = c.d;
   const Layout& L = c.L;
   float* sv = c.sv;
-  const int E = d.E, F = d.F, H = d.H;
+  const int H = d.H;
   const GateOrder go = gate_order(d.cell);
-  if (d.cell == kCellFactored) {
-    // gate-concatenated copies of the 4x6 per-gate tensors: one multi-tensor launch per group
-    auto concat4 = [&](const float* const* src, size_t n, float* dst) -> int {
-      float* ptrs[4];
-      long numel[4];
-      for (int g = 0; g < 4; ++g) { ptrs[g] = const_cast<float*>(src[g]); numel[g] = (long)n; }
-      return pack_tensors(4, ptrs, numel, dst, 0, 1.f, s);
-    };
-    RC(concat4(w.Vw, (size_t)F * E, sv + L.Vcat));
-    RC(concat4(w.Sw, (size_t)F * F, sv + L.Scat));
-    RC(concat4(w.Uw, (size_t)H * F, sv + L.Ucat));
-    RC(concat4(w.Ww, (size_t)H * H, sv + L.Wcat));
-    RC(concat4(w.Vb, F, sv + L.bV));
-    RC(concat4(w.Sb, F, sv + L.bS));
-    for (int g = 0; g < 4; ++g) RC(vec_add(w.Ub[g], w.Wb[g], sv + L.bUW + (size_t)g * H, H, s));
-  } else {
-    RC(copy_d2d(sv + L.Vcat, w.Vw[0], (size_t)4 * H * E, s));
-    RC(copy_d2d(sv + L.Wcat, w.Ww[0], (size_t)4 * H * H, s));
-    RC(vec_add(w.Vb[0], w.Wb[0], sv + L.bUW, 4 * H, s));
-  }
+  CopyTable ct;
+  add_cell_copies(ct, w, d.cell, d.E, d.F, H, sv + L.Vcat, sv + L.Scat, sv + L.Ucat, sv + L.Wcat, sv + L.bV, sv + L.bS, sv + L.bUW);
+  RC(multi_copy(ct, s));
   c.fused_step = H % 16 == 0 && lstm_step_fused_supported(batch_sizes[0], H);
   if (c.fused_step) RC(lstm_pack_wfrag(sv + L.Wcat, sv + L.Wfrag, H, go.gi, go.gf, go.go, go.gg, s));
   // runs of teacher-forced steps go to ONE launch of the persistent kernel (csrc/lstm_persist.hip)
@@ -252,8 +320,7 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
   for (int t = 1; t < d0.steps; ++t) any_free |= !tf_mask[t];
   CAPNET_REQUIRE(!any_free || (Cw && Cb), "seq_forward: output projection needed for free-running steps");
   CAPNET_REQUIRE(d0.steps <= kMaxSteps, "seq_forward: %d steps > %d", d0.steps, kMaxSteps);
-  std::vector<int> off(d0.steps + 1, 0);
-  for (int t = 0; t < d0.steps; ++t) off[t + 1] = off[t] + batch_sizes[t];
+  const std::vector<int> off = step_offsets(batch_sizes, d0.steps);
 
   std::vector<LayerCtx> lay(nlayers);
   for (int l = 0; l < nlayers; ++l) {
@@ -261,13 +328,8 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
     lay[l].d = l == 0 ? d0 : upper_dims(d0);
     lay[l].L = make_layout(lay[l].d);
     lay[l].sv = saved[l]; lay[l].svi = saved_i[l]; lay[l].hid = hiddens[l];
-    // ---- row bookkeeping, built on device from kernel arguments (no copy, no sync)
-    SeqMeta m;
-    m.N = N; m.steps = d0.steps; m.has_features = d0.has_features;
-    for (int t = 0; t <= d0.steps; ++t) m.off[t] = off[t];
-    for (int t = 0; t < d0.steps; ++t) m.tf[t] = tf_mask[t] ? 1 : 0;
-    RC(build_rows(m, lay[l].svi + lay[l].L.row_sample, lay[l].svi + lay[l].L.row_col, lay[l].svi + lay[l].L.row_token,
-                  lay[l].svi + lay[l].L.prev_row, s));
+    RC(build_row_tables(off, tf_mask, d0.has_features, false, lay[l].svi + lay[l].L.row_sample, lay[l].svi + lay[l].L.row_col,
+                        lay[l].svi + lay[l].L.row_token, lay[l].svi + lay[l].L.prev_row, s));
     RC(pack_layer(lay[l], w[l], batch_sizes, s));
   }
   LayerCtx& c0 = lay[0];
@@ -280,8 +342,11 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
                    err_flag, s));
   float* skws = scratch + (size_t)d0.B * d0.V + 64;
   int* skctr = reinterpret_cast<int*>(skws + kSplitKWs);
+  const SkWs sk{skws, kSplitKWs, skctr};
   CAPNET_HIP_CHECK(hipMemsetAsync(skctr, 0, kSplitKCounters * sizeof(int), s));
-  RC(input_chain(c0.d, c0.L, c0.sv, 0, N, skws, kSplitKWs, s, skctr));
+  RC(input_chain(c0.d, c0.L, c0.sv, 0, N, sk, s));
+  const Feedback fb{captions, features, emb, Cw, Cb, d0.T, E, d0.V, H, dropout_p, seed, c0.svi + c0.L.row_sample,
+                    c0.svi + c0.L.row_col, c0.svi + c0.L.row_token, scratch, err_flag};
 
   // ---- recurrence, run by run
   for (int t = 0; t < d0.steps;) {
@@ -290,13 +355,8 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
     const int b = batch_sizes[t], r0 = off[t], r1 = off[t1];
     if (t > 0 && !tf_mask[t]) {
       // predicted = argmax(C h_{t-1}) of the TOP layer for the b surviving rows; then this step's input chain
-      const float* h_prev = top.hid + (size_t)off[t - 1] * H;
-      RC(sgemm_splitk(false, true, b, d0.V, H, h_prev, H, Cw, H, scratch, d0.V, Cb, 0, skws, kSplitKWs, s, skctr,
-                      kSplitKCounters));
-      RC(argmax_rows(scratch, b, d0.V, d0.V, c0.svi + c0.L.row_token + r0, s));
-      RC(gather_inputs(captions, d0.T, features, emb, E, d0.V, c0.svi + c0.L.row_sample, c0.svi + c0.L.row_col,
-                       c0.svi + c0.L.row_token, c0.sv + c0.L.X, E, r0, r0 + b, dropout_p, seed, 0, 1, err_flag, s));
-      RC(input_chain(c0.d, c0.L, c0.sv, r0, r0 + b, skws, kSplitKWs, s, skctr));
+      RC(feed_back(fb, top.hid + (size_t)off[t - 1] * H, b, r0, c0.sv + c0.L.X, E, sk, s));
+      RC(input_chain(c0.d, c0.L, c0.sv, r0, r0 + b, sk, s));
     }
     for (int l = 0; l < nlayers; ++l) {
       LayerCtx& c = lay[l];
@@ -304,7 +364,7 @@ int seq_forward_stacked(const SeqDims& d0, int nlayers, const int* batch_sizes, 
         // X_l = dropout(hidden of the layer below) for the run's rows (kSeqInputDropoutOnly: a plain copy), then its
         // input chain
         RC(rows_dropout(lay[l - 1].hid, c.sv + c.L.X, r0, r1, H, dropout_p, seed, l, between_layers(training, dropout_p), s));
-        RC(input_chain(c.d, c.L, c.sv, r0, r1, skws, kSplitKWs, s, skctr));
+        RC(input_chain(c.d, c.L, c.sv, r0, r1, sk, s));
       }
       RC(recur(c, off, batch_sizes, t, t1, skws, skctr, err_flag, s));
     }
@@ -325,30 +385,14 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
   CAPNET_REQUIRE(g.dWcat && g.dbUW && g.dVcat && (layer > 0 ? dH_below != nullptr : g.dEmb != nullptr), "seq_backward: null gradient buffer");
   CAPNET_REQUIRE(lead == 0 || (layer > 0 && d.steps > 1 && dh0 && dc0), "seq_backward: leading state step");
   const Layout L = make_layout(d);
+  const BwdLayout S = make_bwd_layout(d, lead);
   const int E = d.E, F = d.F, H = d.H, N = d.N;
+  const bool fac = d.cell == kCellFactored;
   const GateOrder go = gate_order(d.cell);
-  std::vector<int> off(d.steps + 1, 0);
-  for (int t = 0; t < d.steps; ++t) off[t + 1] = off[t] + batch_sizes[t];
+  const std::vector<int> off = step_offsets(batch_sizes, d.steps);
   const int R0 = off[lead], Nr = N - R0;       // rows computed by the forward (the leading state step's are given)
-
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  float* dPre = scratch + take((size_t)N * 4 * H);
-  float* Hprev = scratch + take((size_t)N * H);
-  float* dh_rec = scratch + take((size_t)d.B * H);
-  float* dc = scratch + take((size_t)d.B * H);
-  float* dX = scratch + take((size_t)N * E);
-  float* dA2 = nullptr;
-  float* dA1 = nullptr;
-  if (d.cell == kCellFactored) {
-    dA2 = scratch + take((size_t)N * 4 * F);
-    dA1 = scratch + take((size_t)N * 4 * F);
-  }
-  float* skws = scratch + take(kSplitKFloats);
-  // the factored chain's intermediate rows: saved by the forward, or (lead) formed here over all rows
-  const bool chain_rows = lead && d.cell == kCellFactored;
-  float* A1c = chain_rows ? scratch + take((size_t)Nr * 4 * F) : nullptr;
-  float* A2c = chain_rows ? scratch + take((size_t)Nr * 4 * F) : nullptr;
+  float *dPre = scratch + S.dPre, *Hprev = scratch + S.Hprev, *dh_rec = scratch + S.dh_rec, *dc = scratch + S.dc;
+  float *dX = scratch + S.dX, *dA2 = scratch + S.dA2, *dA1 = scratch + S.dA1, *skws = scratch + S.skws;
   const float* sv = saved;
   CAPNET_HIP_CHECK(hipMemsetAsync(dh_rec, 0, (size_t)d.B * H * sizeof(float), s));
   CAPNET_HIP_CHECK(hipMemsetAsync(dc, 0, (size_t)d.B * H * sizeof(float), s));
@@ -380,52 +424,32 @@ static int seq_backward_layer(const SeqDims& d, const int* batch_sizes, const fl
     RC(copy_d2d(dc0, dc, (size_t)batch_sizes[0] * H, s));
   }
   const float* X = sv + L.X + (size_t)R0 * E;
-  const float* A1 = sv + L.A1;
-  const float* A2 = sv + L.A2;
-  if (chain_rows) {
-    RC(sgemm_splitk(false, true, Nr, 4 * F, E, X, E, sv + L.Vcat, E, A1c, 4 * F, sv + L.bV, 0, skws, kSplitKFloats, s));
-    RC(sgemm(false, true, Nr, F, F, A1c, 4 * F, sv + L.Scat, F, A2c, 4 * F, sv + L.bS, 0, 4, F, (long)F * F, F, F, 0, s));
-    A1 = A1c;
-    A2 = A2c;
-  }
+  // the factored chain's intermediate rows: saved by the forward, or (lead) formed here over all rows
+  const float* A1 = lead ? scratch + S.A1c : sv + L.A1;
+  const float* A2 = lead ? scratch + S.A2c : sv + L.A2;
+  const Chain ch = chain_of(d, L, sv);
+  if (fac && lead) RC(chain_rows(ch, X, Nr, scratch + S.A1c, scratch + S.A2c, SkWs{skws, kSplitKFloats, nullptr}, s));
   // recurrent weight gradient over all steps at once: dWcat = dPre^T . h_{t-1}
   dPre += (size_t)R0 * 4 * H;
   RC(gather_rows(hiddens, saved_i + L.prev_row + R0, Hprev, Nr, H, s));
   RC(sgemm_splitk(true, false, 4 * H, H, Nr, dPre, 4 * H, Hprev, H, g.dWcat, H, nullptr, 0, skws, kSplitKFloats, s));
   RC(colsum(dPre, 4 * H, Nr, 4 * H, g.dbUW, 0, s));
-
-  if (d.cell == kCellFactored) {
+  if (fac) {
     CAPNET_REQUIRE(g.dUcat && g.dScat && g.dbS && g.dbV, "seq_backward: null factored gradient buffer");
-    // U: dU_g = dPre_g^T . A2_g ; dA2_g = dPre_g . U_g
-    RC(sgemm(true, false, H, F, Nr, dPre, 4 * H, A2, 4 * F, g.dUcat, F, nullptr, 0, 4, H, F,
-             (long)H * F, 0, 0, s));
-    RC(sgemm(false, false, Nr, F, H, dPre, 4 * H, sv + L.Ucat, F, dA2, 4 * F, nullptr, 0, 4, H,
-             (long)H * F, F, 0, 0, s));
-    RC(colsum(dA2, 4 * F, Nr, 4 * F, g.dbS, 0, s));
-    // S: dS_g = dA2_g^T . A1_g ; dA1_g = dA2_g . S_g
-    RC(sgemm(true, false, F, F, Nr, dA2, 4 * F, A1, 4 * F, g.dScat, F, nullptr, 0, 4, F, F,
-             (long)F * F, 0, 0, s));
-    RC(sgemm(false, false, Nr, F, F, dA2, 4 * F, sv + L.Scat, F, dA1, 4 * F, nullptr, 0, 4, F,
-             (long)F * F, F, 0, 0, s));
-    RC(colsum(dA1, 4 * F, Nr, 4 * F, g.dbV, 0, s));
-    // V: dVcat = dA1^T . X ; dX = dA1 . Vcat
-    RC(sgemm(true, false, 4 * F, E, Nr, dA1, 4 * F, X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-    RC(sgemm_splitk(false, false, Nr, E, 4 * F, dA1, 4 * F, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
-                    kSplitKFloats, s));
+    RC(chain_bwd_rows(ch, dPre, 4 * H, Nr, dA2, dA1, s));
+    RC(chain_wgrads(ch, dPre, 4 * H, X, A1, A2, dA2, dA1, Nr, ChainGrads{g.dVcat, g.dbV, g.dScat, g.dbS, g.dUcat}, s));
   } else {
-    // (the rows the forward computed: all of them unless a leading state step precedes)
-    RC(sgemm(true, false, 4 * H, E, Nr, dPre, 4 * H, X, E, g.dVcat, E, nullptr, 0, 1, 0, 0, 0, 0, 0, s));
-    RC(sgemm_splitk(false, false, Nr, E, 4 * H, dPre, 4 * H, sv + L.Vcat, E, dX, E, nullptr, 0, skws,
-                    kSplitKFloats, s));
+    RC(lstm_input_wgrad(dPre, 4 * H, X, E, H, Nr, g.dVcat, s));
   }
+  // dX = (dA1 | dPre) . (Vcat | weight_ih)
+  const int K = fac ? 4 * F : 4 * H;
+  RC(sgemm_splitk(false, false, Nr, E, K, fac ? dA1 : dPre, K, sv + L.Vcat, E, dX, E, nullptr, 0, skws, kSplitKFloats, s));
   if (layer > 0) return rows_dropout(dX, dH_below, 0, Nr, E, dropout_p, seed, layer, between_layers(training, dropout_p), s);
   CAPNET_HIP_CHECK(hipMemsetAsync(g.dEmb, 0, (size_t)d.V * E * sizeof(float), s));
   if (g.dFeat) CAPNET_HIP_CHECK(hipMemsetAsync(g.dFeat, 0, (size_t)d.B * E * sizeof(float), s));
   // (the split-K slab area is free by now: the scatter's two integer tables over the vocabulary go there)
-  RC(scatter_input_grad(dX, E, N, E, saved_i + L.row_sample, saved_i + L.row_col,
-                        saved_i + L.row_token, g.dEmb, g.dFeat, d.V, dropout_p, seed,
-                        training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kSplitKFloats));
-  return kOk;
+  return scatter_input_grad(dX, E, N, E, saved_i + L.row_sample, saved_i + L.row_col, saved_i + L.row_token, g.dEmb, g.dFeat, d.V,
+                            dropout_p, seed, training && dropout_p > 0.f, s, reinterpret_cast<int*>(skws), kSplitKFloats);
 }
 
 int seqd::seq_backward_upper(const SeqDims& d, const int* batch_sizes, const float* dH, const float* hiddens,
@@ -434,10 +458,6 @@ int seqd::seq_backward_upper(const SeqDims& d, const int* batch_sizes, const flo
                              hipStream_t s) {
   return seq_backward_layer(d, batch_sizes, dH, hiddens, saved, saved_i, scratch, g, dropout_p, seed, training, layer,
                             dH_below, s, 1, dh0, dc0);
-}
-
-size_t seqd::seq_bwd_upper_scratch_floats(const SeqDims& d) {
-  return seq_bwd_scratch_floats(d) + 2 * ((size_t)d.N * 4 * d.F + 4);
 }
 
 // BPTT of seq_forward_stacked, top layer first: a layer's whole backward through time, then its input gradient becomes the

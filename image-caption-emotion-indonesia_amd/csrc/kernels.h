@@ -188,7 +188,6 @@ int embedding_fwd(const long long* idx, int n, const float* emb, int E, int V, f
                   int* err_flag, hipStream_t stream);
 int packed_targets(const SeqMeta& m, const long long* captions, int T, long long* out,
                    hipStream_t stream);
-int vec_add(const float* a, const float* b, float* out, int n, hipStream_t stream);
 // dst[i] = src[i] (+ src2[i] where given), up to 40 items in one launch
 struct CopyTable {
   static constexpr int kMax = 40;

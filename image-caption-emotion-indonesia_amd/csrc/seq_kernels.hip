@@ -141,23 +141,8 @@ int packed_targets(const SeqMeta& m, const long long* captions, int T, long long
   return kOk;
 }
 
-// out = a + b
-__global__ void vec_add_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                               float* __restrict__ out, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
-}
-
-int vec_add(const float* a, const float* b, float* out, int n, hipStream_t stream) {
-  CAPNET_REQUIRE(a && b && out && n > 0, "vec_add: bad argument");
-  hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, a, b, out, n);
-  CAPNET_LAUNCH_CHECK();
-  return kOk;
-}
-
 // ---- many small device-to-device copies / sums in ONE launch --------------------------------
-// dst[i] = src[i] (+ src2[i]): the per-forward weight packing of the attention decoder was 28 hipMemcpyAsync + 4
-// vec_add on the decoder's serial chain.
+// dst[i] = src[i] (+ src2[i]): a cell's per-forward weight packing (28 copies, 4 of them sums) on the decoder's serial chain.
 __global__ __launch_bounds__(256) void multi_copy_kernel(const CopyTable t) {
   const int it = blockIdx.y;
   const float* __restrict__ a = t.src[it];
