@@ -210,11 +210,10 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
                                                           int K, int tiles_n, long sA, long sB) {
   // blockIdx.z = batch member z: A + z*sA, B + z*sB, slab columns [z*N, (z+1)*N) of a row of
   // gridDim.z*N (the gate-batched S_g / U_g products of the factored chain)
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   typedef float f32x2v __attribute__((ext_vector_type(2)));
   constexpr int KQ = KC / 4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  f32x4v* a_cells = reinterpret_cast<f32x4v*>(lds);                  // [KQ][65] cells
+  f32x4* a_cells = reinterpret_cast<f32x4*>(lds);                    // [KQ][65] cells
   float* b_img = lds + (size_t)KQ * kSkCell * 4;                     // TB: [KQ][65] cells; else [KC][80]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tn = blockIdx.x % tiles_n, ks = blockIdx.x / tiles_n, tm = blockIdx.y;
@@ -223,13 +222,13 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
   B += (long)blockIdx.z * sB;
   const int kq_real = (min(KC, K - k0) + 3) / 4;   // K % 4 == 0 is required by the host
   constexpr int NA = (64 * KQ) / 256;              // cells per thread
-  f32x4v va[NA], vb[NA];
+  f32x4 va[NA], vb[NA];
 #pragma unroll
   for (int q = 0; q < NA; ++q) {
     const int idx = tid + 256 * q;
     const int row = idx / KQ, kq = idx - row * KQ;
     const int r = min(m0 + row, M - 1), kk = min(kq, kq_real - 1);
-    va[q] = *reinterpret_cast<const f32x4v*>(A + (long)r * lda + k0 + 4 * kk);
+    va[q] = *reinterpret_cast<const f32x4*>(A + (long)r * lda + k0 + 4 * kk);
   }
   if (TB) {
 #pragma unroll
@@ -237,7 +236,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
       const int idx = tid + 256 * q;
       const int row = idx / KQ, kq = idx - row * KQ;
       const int r = min(n0 + row, N - 1), kk = min(kq, kq_real - 1);
-      vb[q] = *reinterpret_cast<const f32x4v*>(B + (long)r * ldb + k0 + 4 * kk);
+      vb[q] = *reinterpret_cast<const f32x4*>(B + (long)r * ldb + k0 + 4 * kk);
     }
   } else {
     // [K][N]: thread -> (k row, 16-B column group); N % 4 == 0 required by the host
@@ -246,7 +245,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
       const int idx = tid + 256 * q;
       const int kr = idx >> 4, c4 = idx & 15;
       const int kk = min(k0 + kr, K - 1), nn = min(n0 + 4 * c4, N - 4);
-      vb[q] = *reinterpret_cast<const f32x4v*>(B + (long)kk * ldb + nn);
+      vb[q] = *reinterpret_cast<const f32x4*>(B + (long)kk * ldb + nn);
     }
   }
 #pragma unroll
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
     a_cells[kq * kSkCell + row] = va[q] * m;
   }
   if (TB) {
-    f32x4v* b_cells = reinterpret_cast<f32x4v*>(b_img);
+    f32x4* b_cells = reinterpret_cast<f32x4*>(b_img);
 #pragma unroll
     for (int q = 0; q < NA; ++q) {
       const int idx = tid + 256 * q;
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
       const int kr = idx >> 4, c4 = idx & 15;
       const bool ok = k0 + kr < K && n0 + 4 * c4 < N;   // N % 4 == 0: groups are all-or-nothing
       const float m = ok ? 1.f : 0.f;
-      *reinterpret_cast<f32x4v*>(b_img + kr * kSkLdb + 4 * c4) = vb[q] * m;
+      *reinterpret_cast<f32x4*>(b_img + kr * kSkLdb + 4 * c4) = vb[q] * m;
     }
   }
   __syncthreads();
@@ -359,11 +358,10 @@ struct R16Args {
 
 template <bool TB>
 __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   constexpr int KQ = kR16KC / 4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int s_last;
-  f32x4v* a_cells = reinterpret_cast<f32x4v*>(lds);                    // [KQ][17] cells
+  f32x4* a_cells = reinterpret_cast<f32x4*>(lds);                      // [KQ][17] cells
   float* b_img = lds + (size_t)KQ * kR16ACell * 4;                     // TB: [KQ][65] cells; else [KC][80]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tn = blockIdx.x % g.tiles_n, ks = blockIdx.x / g.tiles_n, z = blockIdx.z;
@@ -372,25 +370,25 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
   const float* B = g.B + (long)z * g.sB;
   // this workgroup's k range: `sub` chunks of 256, one load round trip each, the next one requested before the
   // MFMAs of the current one (the host sizes splits x sub so that the grid is one wave of workgroups)
-  f32x4v va[4], vb[16];
+  f32x4 va[4], vb[16];
   auto request = [&](int k0) {
     const int kq_real = (min(kR16KC, g.K - k0) + 3) / 4;   // K % 4 == 0 is required by the host
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int idx = tid + 256 * q, row = idx >> 6, kq = idx & 63;
-      va[q] = *reinterpret_cast<const f32x4v*>(A + (long)min(row, g.M - 1) * g.lda + k0 + 4 * min(kq, kq_real - 1));
+      va[q] = *reinterpret_cast<const f32x4*>(A + (long)min(row, g.M - 1) * g.lda + k0 + 4 * min(kq, kq_real - 1));
     }
     if (TB) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int idx = tid + 256 * q, col = idx >> 6, kq = idx & 63;
-        vb[q] = *reinterpret_cast<const f32x4v*>(B + (long)min(n0 + col, g.N - 1) * g.ldb + k0 + 4 * min(kq, kq_real - 1));
+        vb[q] = *reinterpret_cast<const f32x4*>(B + (long)min(n0 + col, g.N - 1) * g.ldb + k0 + 4 * min(kq, kq_real - 1));
       }
     } else {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int idx = tid + 256 * q, kr = idx >> 4, c4 = idx & 15;
-        vb[q] = *reinterpret_cast<const f32x4v*>(B + (long)min(k0 + kr, g.K - 1) * g.ldb + min(n0 + 4 * c4, g.N - 4));
+        vb[q] = *reinterpret_cast<const f32x4*>(B + (long)min(k0 + kr, g.K - 1) * g.ldb + min(n0 + 4 * c4, g.N - 4));
       }
     }
   };
@@ -402,7 +400,7 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
       a_cells[kq * kR16ACell + row] = va[q] * ((row < g.M && kq < kq_real) ? 1.f : 0.f);
     }
     if (TB) {
-      f32x4v* b_cells = reinterpret_cast<f32x4v*>(b_img);
+      f32x4* b_cells = reinterpret_cast<f32x4*>(b_img);
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int idx = tid + 256 * q, col = idx >> 6, kq = idx & 63;
@@ -412,14 +410,14 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int idx = tid + 256 * q, kr = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<f32x4v*>(b_img + kr * kR16Ldb + 4 * c4) =
+        *reinterpret_cast<f32x4*>(b_img + kr * kR16Ldb + 4 * c4) =
             vb[q] * ((k0 + kr < g.K && n0 + 4 * c4 < g.N) ? 1.f : 0.f);   // N % 4 == 0: groups are all-or-nothing
       }
     }
   };
   // lane (r, q): operand element r (a row of A / a column of the wave's strip), k = 16 i + 4 q + e
   const int r = lane & 15, q4 = lane >> 4;
-  f32x4v acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const int kbeg = ks * g.sub * kR16KC;
   request(kbeg);
   for (int sc = 0; sc < g.sub; ++sc) {
@@ -429,11 +427,11 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
     __syncthreads();
     if (sc + 1 < g.sub && k0 + kR16KC < g.K) request(k0 + kR16KC);
     if (TB) {
-      const f32x4v* b_cells = reinterpret_cast<const f32x4v*>(b_img);
+      const f32x4* b_cells = reinterpret_cast<const f32x4*>(b_img);
 #pragma unroll 4
       for (int i = 0; i < KQ / 4; ++i) {
-        const f32x4v a = a_cells[(4 * i + q4) * kR16ACell + r];
-        const f32x4v b = b_cells[(4 * i + q4) * kR16BCell + 16 * wave + r];
+        const f32x4 a = a_cells[(4 * i + q4) * kR16ACell + r];
+        const f32x4 b = b_cells[(4 * i + q4) * kR16BCell + 16 * wave + r];
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b[0], a[0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b[1], a[1], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b[2], a[2], acc, 0, 0, 0);
@@ -443,7 +441,7 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
       const float* bp = b_img + (4 * q4) * kR16Ldb + 16 * wave + r;
 #pragma unroll 4
       for (int i = 0; i < KQ / 4; ++i) {
-        const f32x4v a = a_cells[(4 * i + q4) * kR16ACell + r];
+        const f32x4 a = a_cells[(4 * i + q4) * kR16ACell + r];
         const float* bk = bp + (16 * i) * kR16Ldb;
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(bk[0], a[0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(bk[kR16Ldb], a[1], acc, 0, 0, 0);
@@ -458,16 +456,16 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
   const long ldo = (long)gridDim.z * g.N;               // a slab row: the batch members' columns side by side
   const long col = (long)z * g.N + n;
   if (g.slabs_only) {                                   // slab[ks][M][N]: the next launch on the stream sums them, in slab order
-    if (m < g.M && n < g.N) *reinterpret_cast<f32x4v*>(g.slab + ((long)ks * g.M + m) * ldo + col) = acc;
+    if (m < g.M && n < g.N) *reinterpret_cast<f32x4*>(g.slab + ((long)ks * g.M + m) * ldo + col) = acc;
     return;
   }
   if (g.splits == 1) {                                  // the whole K in this workgroup: no slab, no hand-off
     if (m < g.M && n < g.N) {
       float* o = g.C + (long)m * g.ldc + col;
-      f32x4v v = acc;
-      if (g.bias) v += *reinterpret_cast<const f32x4v*>(g.bias + col);
-      if (g.accumulate) v += *reinterpret_cast<const f32x4v*>(o);
-      *reinterpret_cast<f32x4v*>(o) = v;
+      f32x4 v = acc;
+      if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + col);
+      if (g.accumulate) v += *reinterpret_cast<const f32x4*>(o);
+      *reinterpret_cast<f32x4*>(o) = v;
     }
     return;
   }
@@ -488,9 +486,9 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
       const long rc = (long)z * g.N + rn;
       const float* p = g.slab + (long)rm * ldo + rc;
       const long slab_stride = (long)g.M * ldo;
-      f32x4v sum = {0.f, 0.f, 0.f, 0.f};
+      f32x4 sum = {0.f, 0.f, 0.f, 0.f};
       for (int k = 0; k < g.splits; k += 16) {
-        f32x4v v[16];
+        f32x4 v[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
           const float* pk = p + (long)min(k + u, g.splits - 1) * slab_stride;
@@ -502,9 +500,9 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
           if (k + u < g.splits) sum += v[u];
       }
       float* o = g.C + (long)rm * g.ldc + rc;
-      if (g.bias) sum += *reinterpret_cast<const f32x4v*>(g.bias + rc);
-      if (g.accumulate) sum += *reinterpret_cast<const f32x4v*>(o);
-      *reinterpret_cast<f32x4v*>(o) = sum;
+      if (g.bias) sum += *reinterpret_cast<const f32x4*>(g.bias + rc);
+      if (g.accumulate) sum += *reinterpret_cast<const f32x4*>(o);
+      *reinterpret_cast<f32x4*>(o) = sum;
     }
     if (tid == 0) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

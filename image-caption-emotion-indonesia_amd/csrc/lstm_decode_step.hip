@@ -6,12 +6,11 @@
 // per decode, capnet.stacked). Layer 0's x is a row of the embedding table picked by token id (or a given input row),
 // layer l > 0's x is h of layer l-1 at the same step, which the previous launch of the same call has just written.
 //
-// Mapping: a workgroup owns 4 hidden units = 16 gate columns (one N tile of v_mfma_f32_16x16x4_f32) and ALL rows. Its 8
+// Mapping: a workgroup owns 4 hidden units = 16 gate columns (one N tile of the 16-row product, step_core.h) and ALL rows. Its 8
 // waves split K = kin + H (kin = in rounded up to the 16-wide k group; the weights carry zero columns there) into eight
 // contiguous ranges of k groups. Each lane loads its column's weights for its range once (NJ f32x4 registers: the
 // layer's weights cross HBM once per launch) and keeps them while the workgroup walks the rows 16 TM at a time: per pass a
-// lane reads 16 B of x or h_prev per k group for each of TM 16-row tiles -- k = 16 g + 4 (lane >> 4) + e feeds MFMA step
-// (g, e) in both operands, so row-major weights need no fragment image -- runs the tiles' MFMA chains interleaved (TM = 2;
+// lane reads 16 B of x or h_prev per k group for each of TM 16-row tiles, runs the tiles' MFMA chains interleaved (TM = 2;
 // TM = 1 at 16 groups per wave, where two tiles' operands and the weights would not fit in 256 VGPRs),
 // and the eight K-partial tiles are summed through LDS by the epilogue, which applies the gates and writes c, h (and the
 // top layer's h once more, densely, for the vocabulary projection). Plain vector loads and stores only.
@@ -20,10 +19,9 @@
 // LSTM cell has no chain to fold, and only the epilogue differs, h = o tanh(c).
 #include "common.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace capnet {
-
-typedef float f32x4d __attribute__((ext_vector_type(4)));
 
 constexpr int kDecWaves = 8;
 constexpr int kDecMaxK = 2048;       // kin + H <= 8 waves x 16 groups x 16
@@ -48,8 +46,6 @@ struct DecodeLayerArgs {
   int kin, rows, H;
 };
 
-__device__ __forceinline__ float sigm_d(float x) { return 1.f / (1.f + expf(-x)); }
-
 template <int NJ, int TM, bool TANH_OUT>  // k groups per wave (at most), 16-row tiles per pass; h = o tanh(c)
 __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a) {
   constexpr int kPass = 16 * TM;
@@ -61,11 +57,11 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
   const int g0 = wave * KG / kDecWaves, ng = (wave + 1) * KG / kDecWaves - g0;   // this wave's groups [g0, g0 + ng)
   // B operand: column li = gate role li >> 2 (i, f, o, c~), unit u0 + (li & 3)
   const float* wrow = a.w + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
-  f32x4d wv[NJ];
+  f32x4 wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    wv[j] = f32x4d{0.f, 0.f, 0.f, 0.f};
-    if (j < ng) wv[j] = *reinterpret_cast<const f32x4d*>(wrow + 16 * (g0 + j));
+    wv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (j < ng) wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * (g0 + j));
   }
   // epilogue thread: (row er of the pass, unit eu); threads 0 .. 64 TM - 1
   const int er = tid >> 2, eu = tid & 3;
@@ -76,11 +72,10 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
     for (int g = 0; g < 4; ++g) bias[g] = a.b[g * H + u0 + eu];
   }
   for (int r0 = 0; r0 < a.rows; r0 += kPass) {
-    f32x4d av[TM][NJ];
+    f32x4 av[TM][NJ];
 #pragma unroll
     for (int m = 0; m < TM; ++m) {
-      int row = r0 + 16 * m + li;
-      row = row < a.rows ? row : a.rows - 1;             // rows beyond the last: a clamped copy, never stored
+      const int row = clamp_row(r0 + 16 * m + li, a.rows);
       long xr = row;
       if (a.tok) {
         const long long t = a.tok[row];
@@ -92,13 +87,13 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
       const float* hrow = a.hprev + (long)row * a.lds_in;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        f32x4d v = {0.f, 0.f, 0.f, 0.f};
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
         const int g = g0 + j, k = 16 * g + 4 * lq;
         if (j < ng) {
           if (g >= inG) {
-            v = *reinterpret_cast<const f32x4d*>(hrow + (k - a.kin));
+            v = *reinterpret_cast<const f32x4*>(hrow + (k - a.kin));
           } else if (a.xvec) {
-            if (k < a.xn) v = *reinterpret_cast<const f32x4d*>(xrow + k);
+            if (k < a.xn) v = *reinterpret_cast<const f32x4*>(xrow + k);
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = k + e < a.xn ? xrow[k + e] : 0.f;
@@ -110,9 +105,9 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
     const int erow = r0 + er;
     const bool estore = ethread && erow < a.rows;
     const float cp = estore ? a.cprev[(long)erow * a.lds_in + u0 + eu] : 0.f;
-    f32x4d acc[TM];
+    f32x4 acc[TM];
 #pragma unroll
-    for (int m = 0; m < TM; ++m) acc[m] = f32x4d{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < TM; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       if (j < ng) {
@@ -122,24 +117,17 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
           for (int m = 0; m < TM; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][j][e], wv[j][e], acc[m], 0, 0, 0);
       }
     }
-    // D layout of a 16x16 tile: column = lane & 15, rows 4 (lane >> 4) + r
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave][16 * m + 4 * lq + r][li] = acc[m][r];
     __syncthreads();
     if (estore) {
-      float pre[4];
+      float pre[4], i, f, og, gt, c;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float s = bias[g];
-#pragma unroll
-        for (int w = 0; w < kDecWaves; ++w) s += red[w][er][g * 4 + eu];
-        pre[g] = s;
-      }
-      const float i = sigm_d(pre[0]), f = sigm_d(pre[1]), og = sigm_d(pre[2]), gt = tanhf(pre[3]);
-      const float c = f * cp + i * gt;
-      const float h = TANH_OUT ? og * tanhf(c) : og * c;
+      for (int g = 0; g < 4; ++g) pre[g] = sum_partials<kDecWaves>(red, er, g * 4 + eu, bias[g]);
+      lstm_cell(pre[0], pre[1], pre[2], pre[3], cp, i, f, og, gt, c);
+      const float h = lstm_cell_h(og, c, TANH_OUT);
       a.c_out[(long)erow * a.lds_out + u0 + eu] = c;
       a.h_out[(long)erow * a.lds_out + u0 + eu] = h;
       if (a.h_top) a.h_top[(long)erow * H + u0 + eu] = h;
@@ -151,7 +139,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
 static int round16(int v) { return (v + 15) / 16 * 16; }
 
 bool stacked_decode_supported(int E, int H) {
-  return E >= 1 && (H == 64 || H == 128 || H == 256 || H == 512 || H == 1024) && round16(E) + H <= kDecMaxK;
+  return E >= 1 && step_hidden_supported(H) && round16(E) + H <= kDecMaxK;
 }
 
 template <int NJ, bool TANH_OUT>

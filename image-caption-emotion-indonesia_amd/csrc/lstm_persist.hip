@@ -76,8 +76,6 @@ struct PersistArgs {
   short b[kMaxSteps];
 };
 
-__device__ __forceinline__ float p_sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
 __device__ __forceinline__ int ld_sc1_i32(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -4,7 +4,7 @@
 //                                     (stylenet/model.py:147-153)
 //   nn.LSTMCell:                      gates i,f,g,o;  h = o tanh(c)          (nic/model.py:77)
 // Mapping (b = 64, H = 512: 256 workgroups = one per CU, 1024 waves = one per SIMD).
-//   A workgroup owns 4 hidden units = 16 gate columns (one N tile of v_mfma_f32_16x16x4_f32), 32
+//   A workgroup owns 4 hidden units = 16 gate columns (one N tile of the 16-row product, step_core.h), 32
 //   of the b rows (two 16-row M tiles) and the whole K = H. Its 4 waves take the 16-wide k groups
 //   round-robin; each wave keeps ITS slice of the recurrent weights in registers for the whole
 //   launch (H/16 VGPRs: "wavefront-resident" weights, read once per step as fully coalesced 1-KB
@@ -17,14 +17,10 @@
 // LDS exchange and one store. HBM traffic per step = W (4*H*H*4 B) + h,c in/out + pre-activations
 // in + gates out: the algorithmic 5.77 MB of SURVEY.md 8(d) at b = 64, H = 512.
 #include "common.h"
-#include "mfma_core.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace capnet {
-
-size_t lstm_wfrag_floats(int H);
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int kStepRows = 64;   // max rows (batch) per step
 constexpr int kWgRows = 32;     // rows per workgroup
@@ -32,11 +28,8 @@ constexpr int kWgRows = 32;     // rows per workgroup
 //   writes: ds_write_b128, lanes along kq (coalesced global reads of a row);
 //   reads:  ds_read_b128, lanes along rows: lane (i = l & 15, e = l >> 4) of k group g reads
 //           cell[4g + e][16 mt + i] and uses its four floats as the A operand of MFMA steps
-//           4g .. 4g+3 (k = 16g + 4e + step): any k <-> (step, lane quarter) bijection is a valid
-//           reduction order as long as the weight fragments use the same one.
+//           4g .. 4g+3 (k = 16g + 4e + step: step_core.h's k slots).
 constexpr int kCellStride = kWgRows + 1;
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 __host__ __device__ inline int step_ngw(int H) {  // 16-wide k groups per wave, padded to 1/2/4/8
   const int need = (H + 63) / 64;
@@ -77,8 +70,8 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
   if (stamps) ts[0] = __builtin_amdgcn_s_memtime();
   constexpr int KQP = NGW * 16;  // 16-B cells per row of the (zero padded) image
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  f32x4v* cells = reinterpret_cast<f32x4v*>(lds);
-  float* red = lds + (size_t)KQP * kCellStride * 4;  // [wave][mt][16 rows][17]
+  f32x4* cells = reinterpret_cast<f32x4*>(lds);
+  float* red = lds + (size_t)KQP * kCellStride * 4;  // [wave][mt][16 rows][17]: part of the dynamic block, so indexed by hand
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, le = lane >> 4;
   int ug, half;
@@ -95,9 +88,9 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
   constexpr int NH = (kWgRows * KQH) / 256;   // cells per thread per half
   constexpr int QH = NGW / NS;                // k groups per wave per half
   const int kq_real = H / 4;
-  f32x4v v[NS][NH];
-  f32x4v wreg[NGW];
-  const f32x4v* wf = reinterpret_cast<const f32x4v*>(Wfrag) + ((long)(ug * 4 + wave) * NGW) * 64 + lane;
+  f32x4 v[NS][NH];
+  f32x4 wreg[NGW];
+  const f32x4* wf = reinterpret_cast<const f32x4*>(Wfrag) + ((long)(ug * 4 + wave) * NGW) * 64 + lane;
 #pragma unroll
   for (int hh = 0; hh < NS; ++hh) {
 #pragma unroll
@@ -105,8 +98,8 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
       const int idx = tid + 256 * q;
       const int row = idx / KQH, kq = hh * KQH + (idx - row * KQH);
       // unconditional load from a clamped cell (a guarded load makes hipcc wait per load)
-      v[hh][q] = *reinterpret_cast<const f32x4v*>(
-          hprev + (long)(row0 + (row < nrows ? row : nrows - 1)) * H +
+      v[hh][q] = *reinterpret_cast<const f32x4*>(
+          hprev + (long)(row0 + clamp_row(row, nrows)) * H +
           4 * (kq < kq_real ? kq : kq_real - 1));
     }
 #pragma unroll
@@ -116,16 +109,16 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
   // ---- epilogue operands: thread -> (row er, unit eu) ----
   const int er = tid >> 2, eu = tid & 3;
   const bool evalid = tid < 4 * kWgRows && er < nrows;
-  const long erow = row0 + (er < nrows ? er : nrows - 1);
+  const long erow = row0 + clamp_row(er, nrows);
   float pre[4], cp;
 #pragma unroll
   for (int g = 0; g < 4; ++g) pre[g] = G[erow * ldg + (long)gsel[g] * H + u0 + eu];
   cp = cprev[erow * H + u0 + eu];
   __builtin_amdgcn_sched_barrier(0);
 
-  f32x4v acc[MT];
+  f32x4 acc[MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int hh = 0; hh < NS; ++hh) {
     // ---- this k half of the workgroup's rows of h_{t-1} -> cell image ----
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
     __syncthreads();
     if (stamps && hh == 0) ts[1] = __builtin_amdgcn_s_memtime();
     // ---- partial products over this wave's k groups (w, w+4, w+8, ...) of the half ----
-    f32x4v a[QH][MT];
+    f32x4 a[QH][MT];
 #pragma unroll
     for (int q = 0; q < QH; ++q)
 #pragma unroll
@@ -154,7 +147,6 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
           acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q][mt][e], wreg[hh * QH + q][e], acc[mt], 0, 0, 0);
   }
   if (stamps) ts[2] = __builtin_amdgcn_s_memtime();
-  // D layout of the 16x16 tile: column = lane & 15, rows 4 * (lane >> 4) + r
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -172,14 +164,14 @@ __global__ __launch_bounds__(256) void lstm_step_fused_kernel(
       for (int w = 0; w < 4; ++w) s += red[((w * 2 + mt) * 16 + rr) * 17 + g * 4 + eu];
       pre[g] = s;
     }
-    const float i = sigm(pre[0]), f = sigm(pre[1]), og = sigm(pre[2]), gt = tanhf(pre[3]);
-    const float c = f * cp + i * gt;
+    float i, f, og, gt, c;
+    lstm_cell(pre[0], pre[1], pre[2], pre[3], cp, i, f, og, gt, c);
     G[erow * ldg + (long)gi * H + u0 + eu] = i;
     G[erow * ldg + (long)gf * H + u0 + eu] = f;
     G[erow * ldg + (long)go * H + u0 + eu] = og;
     G[erow * ldg + (long)gg * H + u0 + eu] = gt;
     c_out[erow * H + u0 + eu] = c;
-    h_out[erow * H + u0 + eu] = tanh_out ? og * tanhf(c) : og * c;
+    h_out[erow * H + u0 + eu] = lstm_cell_h(og, c, tanh_out);
   }
   if (stamps) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -258,12 +250,11 @@ int lstm_step_fused(const float* hprev, const float* Wfrag, float* G, long ldg, 
   CAPNET_REQUIRE(hprev && Wfrag && G && cprev && c_out && h_out, "lstm_step_fused: null argument");
   CAPNET_REQUIRE(lstm_step_fused_supported(b, H), "lstm_step_fused: unsupported b=%d H=%d", b, H);
   CAPNET_REQUIRE(aligned16(hprev) && aligned16(Wfrag), "lstm_step_fused: alignment");
-  switch (step_ngw(H)) {
-    case 1: return launch_step<1>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
-    case 2: return launch_step<2>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
-    case 4: return launch_step<4>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
-    default: return launch_step<8>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
-  }
+  const auto launch = [&](auto ngw) {
+    return launch_step<ngw>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
+  };
+  const int ngw = step_ngw(H);   // 1, 2, 4 or 8: H is padded to 64 ngw here, so this is not dispatch_nj's map
+  return ngw == 1 ? launch(nj_t<1>{}) : ngw == 2 ? launch(nj_t<2>{}) : ngw == 4 ? launch(nj_t<4>{}) : launch(nj_t<8>{});
 }
 
 }  // namespace capnet

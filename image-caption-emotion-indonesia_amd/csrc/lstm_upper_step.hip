@@ -4,10 +4,9 @@
 //   i, f, o = sigmoid, c~ = tanh;  c = f c_{t-1} + i c~;  h = o c      (stylenet/model.py:147-153)
 // Composed, the same step is rows_dropout, three chain products and the fused recurrent step: five dependent launches of
 // 8-12 us each at a dozen rows, whatever they compute (NOTEBOOK 4l).
-// Mapping: a workgroup owns 4 hidden units = 16 gate columns (one N tile of v_mfma_f32_16x16x4_f32) and all rows (one
-// 16-row M tile); its 8 waves split K = 2H into eighths (waves 0-3 the dropped-out input, 4-7 the recurrent state). A lane
-// reads 16 B of its row and 16 B of its column's weight row per 16-wide k group straight from global memory -- k = 16 j +
-// 4 (lane >> 4) + e feeds MFMA step (j, e) in both operands, so the row-major weights need no fragment image -- and all
+// Mapping: a workgroup owns 4 hidden units = 16 gate columns (one N tile of the 16-row product, step_core.h) and all rows
+// (one 16-row M tile); its 8 waves split K = 2H into eighths (waves 0-3 the dropped-out input, 4-7 the recurrent state). A
+// lane reads 16 B of its row and 16 B of its column's weight row per 16-wide k group straight from global memory, and all
 // of a wave's loads are in flight before its first MFMA. The eight K-partial tiles are summed through LDS; the epilogue
 // applies the gates and writes what BPTT reads: activated gates, c, h and the dropped-out input row.
 // The nn.LSTMCell instance (CELL = kCellLSTM, capnet.nic_stacked) takes Weff = weight_ih, W = weight_hh and
@@ -16,15 +15,12 @@
 #include "common.h"
 #include "dropout_mask.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace capnet {
 
-typedef float f32x4u __attribute__((ext_vector_type(4)));
-
 constexpr int kUpperRows = 16;
 constexpr int kUpperWaves = 8;
-
-__device__ __forceinline__ float sigm_u(float x) { return 1.f / (1.f + expf(-x)); }
 
 template <int NJ, int CELL>  // 16-wide k groups per wave: H = 64 NJ; kCellFactored or kCellLSTM
 __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
@@ -37,23 +33,23 @@ __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
   const int li = lane & 15, lq = lane >> 4;
   const int u0 = blockIdx.x * 4;
   const float inv_keep = p < 1.f ? 1.f / (1.f - p) : 0.f;
-  const int row = li < b ? li : b - 1;                 // rows beyond b: a clamped copy, never stored
+  const int row = clamp_row(li, b);
   // this wave's eighth of K: waves 0-3 read the input half, 4-7 the recurrent half
   const bool rec = wave >= kUpperWaves / 2;
   const int k0 = (wave & 3) * (H / 4);                 // offset inside the half
   const float* arow = (rec ? hprev : xin) + (long)row * H + k0 + 4 * lq;
   const int n = li, grow = (n >> 2) * H + u0 + (n & 3);   // gate role n >> 2 (i, f, o, c~), unit u0 + (n & 3)
   const float* wrow = (rec ? Wrec : Weff) + (long)grow * H + k0 + 4 * lq;
-  f32x4u av[NJ], wv[NJ];
+  f32x4 av[NJ], wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    av[j] = *reinterpret_cast<const f32x4u*>(arow + 16 * j);
-    wv[j] = *reinterpret_cast<const f32x4u*>(wrow + 16 * j);
+    av[j] = *reinterpret_cast<const f32x4*>(arow + 16 * j);
+    wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * j);
   }
   // epilogue operands, requested before the products: thread -> (row er, unit eu)
   const int er = tid >> 2, eu = tid & 3;
   const bool evalid = tid < 4 * kUpperRows && er < b;
-  const int erow = er < b ? er : b - 1;
+  const int erow = clamp_row(er, b);
   float pre[4], cp = 0.f;
   if (tid < 4 * kUpperRows) {
 #pragma unroll
@@ -66,12 +62,8 @@ __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e) av[j][e] *= dropout_scale(seed, r0 + row, 0x40000000 + layer, k0 + 16 * j + 4 * lq + e, p, inv_keep);
   }
-  f32x4u acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j][e], wv[j][e], acc, 0, 0, 0);
-  // D layout of the 16x16 tile: column = lane & 15, rows 4 * (lane >> 4) + r
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  acc = mfma_chain<NJ>(av, wv, acc);
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wave][4 * lq + r][li] = acc[r];
   // the dropped-out input row for BPTT: this workgroup's 4 columns of every row
@@ -84,39 +76,22 @@ __global__ __launch_bounds__(512) void lstm_upper_step_kernel(
   __syncthreads();
   if (evalid) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float s = pre[g];
-#pragma unroll
-      for (int w = 0; w < kUpperWaves; ++w) s += red[w][er][g * 4 + eu];
-      pre[g] = s;
-    }
+    for (int g = 0; g < 4; ++g) pre[g] = sum_partials<kUpperWaves>(red, er, g * 4 + eu, pre[g]);
     constexpr int GO = CELL == kCellLSTM ? 3 : 2, GG = CELL == kCellLSTM ? 2 : 3;   // blocks of o and c~ (g)
-    const float i = sigm_u(pre[0]), f = sigm_u(pre[1]), og = sigm_u(pre[GO]), gt = tanhf(pre[GG]);
-    const float c = f * cp + i * gt;
+    float i, f, og, gt, c;
+    lstm_cell(pre[0], pre[1], pre[GO], pre[GG], cp, i, f, og, gt, c);
     const long gr = (long)er * 4 * H + u0 + eu;
     G[gr] = i;
     G[gr + H] = f;
     G[gr + GO * H] = og;
     G[gr + GG * H] = gt;
     c_out[(long)er * H + u0 + eu] = c;
-    h_out[(long)er * H + u0 + eu] = CELL == kCellLSTM ? og * tanhf(c) : og * c;
+    h_out[(long)er * H + u0 + eu] = lstm_cell_h(og, c, CELL == kCellLSTM);
   }
 }
 
 bool lstm_upper_step_supported(int b, int H) {
-  return b >= 1 && b <= kUpperRows && (H == 64 || H == 128 || H == 256 || H == 512 || H == 1024);
-}
-
-template <int NJ>
-static void launch_upper(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
-                         const float* beff, float* x_out, float* G, float* c_out, float* h_out, int b, int H, int r0, float p,
-                         unsigned long long seed, int layer, int use_dropout, int cell, hipStream_t stream) {
-  if (cell == kCellLSTM)
-    hipLaunchKernelGGL((lstm_upper_step_kernel<NJ, kCellLSTM>), dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin, hprev,
-                       cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
-  else
-    hipLaunchKernelGGL((lstm_upper_step_kernel<NJ, kCellFactored>), dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin,
-                       hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
+  return b >= 1 && b <= kUpperRows && step_hidden_supported(H);
 }
 
 int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, const float* Weff, const float* Wrec,
@@ -128,13 +103,11 @@ int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, co
   CAPNET_REQUIRE(lstm_upper_step_supported(b, H), "lstm_upper_step: unsupported b=%d H=%d", b, H);
   CAPNET_REQUIRE(aligned16(xin) && aligned16(hprev) && aligned16(Weff) && aligned16(Wrec),
                  "lstm_upper_step: alignment");
-  switch (H) {
-    case 64: launch_upper<1>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
-    case 128: launch_upper<2>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
-    case 256: launch_upper<4>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
-    case 512: launch_upper<8>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
-    default: launch_upper<16>(xin, hprev, cprev, Weff, Wrec, beff, x_out, G, c_out, h_out, b, H, r0, p, seed, layer, use_dropout, cell, stream); break;
-  }
+  dispatch_nj(H, [&](auto nj) {
+    const auto kern = cell == kCellLSTM ? lstm_upper_step_kernel<nj, kCellLSTM> : lstm_upper_step_kernel<nj, kCellFactored>;
+    hipLaunchKernelGGL(kern, dim3(H / 4), dim3(64 * kUpperWaves), 0, stream, xin, hprev, cprev, Weff, Wrec, beff, x_out, G,
+                       c_out, h_out, b, H, r0, p, seed, layer, use_dropout);
+  });
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "step_core.h"
+
 namespace capnet {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -282,8 +284,7 @@ __device__ __forceinline__ void flag_nonfinite(float t, int* err) {
   if (!(t < __builtin_inff())) atomicOr(err, 8);
 }
 
-// ---- helpers shared by the hand-scheduled conv kernels (conv_f32_v2.hip, conv_wino.hip) ----
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// ---- helpers shared by the hand-scheduled conv kernels (conv_f32_v2.hip, conv_wino.hip); f32x4: step_core.h ----
 
 // mul = ceil(2^k / d), k = 24 + ceil(log2 d): exact quotient for every n < 2^24
 static inline void magic_div(unsigned d, unsigned* mul, unsigned* sh) {

@@ -6,9 +6,9 @@
 #include "common.h"
 #include "dropout_mask.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace capnet {
-
 
 // ---- row bookkeeping, built on device from kernel arguments (no H2D copy, no sync) -------
 // row r of step t (rows of a step are contiguous, sample j at offset j):
@@ -184,8 +184,6 @@ int multi_copy(const CopyTable& t, hipStream_t stream) {
 // pre is overwritten with the ACTIVATED gates (saved for backward).
 // tanh_out = 0: h = o*c            (FactoredLSTM, stylenet/model.py:152-153)
 // tanh_out = 1: h = o*tanh(c)      (nn.LSTMCell, nic/model.py:77)
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ __launch_bounds__(256) void lstm_pointwise_fwd_kernel(
     float* __restrict__ pre, long ldp, const float* __restrict__ c_prev, float* __restrict__ c_out,
     float* __restrict__ h_out, int b, int H, int gi, int gf, int go, int gg, int tanh_out,
@@ -214,18 +212,15 @@ __global__ __launch_bounds__(256) void lstm_pointwise_fwd_kernel(
         }
     }
   }
-  const float i = sigmoidf_(x[0]);
-  const float f = sigmoidf_(x[1]);
-  const float o = sigmoidf_(x[2]);
-  const float g = tanhf(x[3]);
+  const float i = sigm(x[0]), f = sigm(x[1]), o = sigm(x[2]), g = tanhf(x[3]);
   const float cp = c_prev ? c_prev[(long)row * H + j] : 0.f;
-  const float c = f * cp + i * g;
+  const float c = f * cp + i * g;   // step_core.h's lstm_cell written out (c_prev is loaded late here): change both
   p[gi * H + j] = i;
   p[gf * H + j] = f;
   p[go * H + j] = o;
   p[gg * H + j] = g;
   c_out[(long)row * H + j] = c;
-  h_out[(long)row * H + j] = tanh_out ? o * tanhf(c) : o * c;
+  h_out[(long)row * H + j] = lstm_cell_h(o, c, tanh_out);
 }
 
 int lstm_pointwise_fwd(float* pre, long ldp, const float* c_prev, float* c_out, float* h_out, int b,

@@ -3,7 +3,7 @@
 //   tok[r] = first argmax_v (h[r] . W[v] + b[v])        h [rows][H], W [V][H] (nn.Linear), b [V]
 //
 // Mapping (the arrangement of lstm_decode_step.hip): a workgroup owns 32 vocabulary entries = two N tiles of
-// v_mfma_f32_16x16x4_f32 and ALL rows. Its 8 waves are 2 tiles x 4 contiguous quarters of K = H; a lane loads its column's
+// the 16-row product (step_core.h) and ALL rows. Its 8 waves are 2 tiles x 4 contiguous quarters of K = H; a lane loads its column's
 // weights for its quarter once (NJ f32x4 registers: the projection crosses the memory system once per launch) and keeps
 // them while the workgroup walks the rows 16 TM at a time. The four K-partial tiles are summed through LDS in a fixed order,
 // the bias is added, and 32 threads per row reduce (value, index) with a strict comparison, ties to the lower index.
@@ -17,10 +17,9 @@
 // yields 0.
 #include "common.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace capnet {
-
-typedef float f32x4a __attribute__((ext_vector_type(4)));
 
 constexpr int kVaWaves = 8;
 constexpr int kVaCols = 32;          // vocabulary entries per workgroup
@@ -52,34 +51,27 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
   const int tile = wave >> 2, ks = wave & 3;
   const int H = a.H, c0 = blockIdx.x * kVaCols;
   const int g0 = ks * NJ;                                   // this wave's k groups [g0, g0 + NJ): H = 64 NJ
-  int wcol = c0 + 16 * tile + li;
-  wcol = wcol < a.V ? wcol : a.V - 1;                       // entries beyond V: a clamped copy, masked in the epilogue
+  const int wcol = clamp_row(c0 + 16 * tile + li, a.V);      // entries beyond V: masked in the epilogue
   const float* wrow = a.w + (long)wcol * H + 16 * g0 + 4 * lq;
-  f32x4a wv[NJ];
+  f32x4 wv[NJ];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) wv[j] = *reinterpret_cast<const f32x4a*>(wrow + 16 * j);
+  for (int j = 0; j < NJ; ++j) wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * j);
   // epilogue thread: (row er of a 16-row tile, entry ec of the workgroup's 32)
   const int er = tid >> 5, ec = tid & 31;
   const int ecol = c0 + ec;
   const float bias = (a.b && ecol < a.V) ? a.b[ecol] : 0.f;
   unsigned long long* part = a.part + (long)blockIdx.x * a.rows;
   for (int r0 = 0; r0 < a.rows; r0 += kPass) {
-    f32x4a acc[TM];
+    f32x4 acc[TM];
 #pragma unroll
     for (int m = 0; m < TM; ++m) {
-      acc[m] = f32x4a{0.f, 0.f, 0.f, 0.f};
-      int row = r0 + 16 * m + li;
-      row = row < a.rows ? row : a.rows - 1;                // rows beyond the last: a clamped copy, never stored
+      const int row = clamp_row(r0 + 16 * m + li, a.rows);
       const float* hrow = a.h + (long)row * H + 16 * g0 + 4 * lq;
-      f32x4a av[NJ];
+      f32x4 av[NJ];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) av[j] = *reinterpret_cast<const f32x4a*>(hrow + 16 * j);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j][e], wv[j][e], acc[m], 0, 0, 0);
+      for (int j = 0; j < NJ; ++j) av[j] = *reinterpret_cast<const f32x4*>(hrow + 16 * j);
+      acc[m] = mfma_chain<NJ>(av, wv, f32x4{0.f, 0.f, 0.f, 0.f});
     }
-    // D layout of a 16x16 tile: column = lane & 15, rows 4 (lane >> 4) + r
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
 
 static int va_workgroups(int V) { return (V + kVaCols - 1) / kVaCols; }
 
-bool vocab_argmax_supported(int H) { return H == 64 || H == 128 || H == 256 || H == 512 || H == 1024; }
+bool vocab_argmax_supported(int H) { return step_hidden_supported(H); }
 
 // workspace: 16 bytes whose first int is the counter, then one 8-byte partial per workgroup and row
 size_t vocab_argmax_ws_bytes(int rows, int V) { return 16 + (size_t)va_workgroups(V) * rows * 8; }
@@ -161,13 +153,9 @@ int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H
   a.tok = tok; a.ids = ids; a.ld_ids = ld_ids;
   a.rows = rows; a.H = H; a.V = V;
   const dim3 grid(va_workgroups(V)), block(64 * kVaWaves);
-  switch (H) {
-    case 64: hipLaunchKernelGGL((vocab_argmax_kernel<1, 2>), grid, block, 0, stream, a); break;
-    case 128: hipLaunchKernelGGL((vocab_argmax_kernel<2, 2>), grid, block, 0, stream, a); break;
-    case 256: hipLaunchKernelGGL((vocab_argmax_kernel<4, 2>), grid, block, 0, stream, a); break;
-    case 512: hipLaunchKernelGGL((vocab_argmax_kernel<8, 2>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((vocab_argmax_kernel<16, 1>), grid, block, 0, stream, a); break;
-  }
+  dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
+    hipLaunchKernelGGL((vocab_argmax_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
+  });
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
