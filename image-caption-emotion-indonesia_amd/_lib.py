@@ -33,6 +33,11 @@ SIGNATURES = {
     "capnet_topk_correct": (_i, [_vp, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "capnet_beam_topk": (_i, [_vp, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "capnet_beam_topk_batched": (_i, [_vp, _l, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "capnet_beam_state_bytes": (_sz, [_i, _i, _i]),
+    "capnet_beam_init": (_i, [_vp, _i, _i, _i, C.c_longlong, _vp, _vp]),
+    "capnet_beam_advance": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),
+    "capnet_beam_finish": (_i, [_vp, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),
+    "capnet_beam_live": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "capnet_att_step_fwd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i,
                                  _vp, _vp, _l, _vp, _vp]),
     "capnet_trunk_create": (_i, [_i, _i, _i, C.POINTER(_vp)]),

@@ -9,6 +9,9 @@ Device work per step: the decoder's own step (C-ABI kernels) and ONE `capnet_bea
 (log-softmax + add + top-k fused); the k scores / indices come back in one transfer and the
 bookkeeping (sequence lists, which beam survives) is host Python, as in the reference.
 
+beam_search_device is the opt-in third loop: the same search with that bookkeeping done by the selecting workgroup
+(capnet_beam_advance), fixed rows per image and nothing read by the host until the end.
+
 Deviation from the reference text: `top_k_words / vocab_size` (model.py:249) is an integer
 division here. Under the torch 1.1 the reference pins it was one; under current torch the
 reference line raises.
@@ -59,6 +62,40 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
         return torch.tensor([[int(end_token)]], dtype=torch.long, device=device)
     best = complete_seqs_scores.index(max(complete_seqs_scores))
     return torch.tensor([complete_seqs[best]], dtype=torch.long, device=device)
+
+
+def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, poll_every=0):
+    """beam_search_batched with the bookkeeping on the device (capnet_beam_advance): no host read and no host-built
+    tensor per step. Image i keeps rows i k .. i k + k - 1 for the whole search -- its live beams in its first slots, in
+    the order beam_search_batched keeps them; dead slots still take the decoder step, their logits are never read -- so
+    every step runs on n k rows, and `state` is re-indexed by the parent rows the kernel wrote. T = max_seq_length + 1
+    steps, all the host loop can run; then capnet_beam_finish picks the winners and ONE copy brings sequences and lengths
+    to the host. poll_every = m > 0: after every m-th step the count of live beams is read (one blocking 4-byte copy)
+    and the loop stops at zero -- same result, for decoders whose beams end long before T.
+    Returns a list of n token lists (each starts with start_token)."""
+    if k > 16 or k > vocab_size:
+        raise ops.CapnetError("beam_search_device: k <= 16 and k <= vocab_size")
+    T = max_seq_length + 1
+    words = [torch.empty(n * k, dtype=torch.long, device=device) for _ in range(2)]
+    parent_rows = torch.empty(n * k, dtype=torch.long, device=device)
+    beam = ops.beam_init(n, k, T, start_token, words[0])
+    prev_words = words[0]
+    for step in range(1, T + 1):
+        logits, state = step_fn(prev_words, state)
+        if logits.shape[1] != vocab_size:
+            raise ops.CapnetError("beam_search_device: the step returned %d columns, vocab_size is %d" % (logits.shape[1], vocab_size))
+        next_words = words[step & 1]
+        ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows)
+        if poll_every > 0 and step % poll_every == 0 and step < T and not int(beam.live_total.item()):
+            break
+        state = tuple(s.index_select(0, parent_rows) for s in state)
+        prev_words = next_words
+    seqs, lengths, packed = ops.beam_finish(beam, end_token)
+    host = packed.cpu()
+    L = seqs.shape[1]
+    lens = host[n * L:].view(torch.int32)[:n].tolist()
+    rows = host[:n * L].view(n, L).tolist()
+    return [rows[i][:lens[i]] for i in range(n)]
 
 
 def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device):

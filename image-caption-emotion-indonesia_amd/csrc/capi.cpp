@@ -529,6 +529,23 @@ int capnet_beam_topk(const float* logits, long ld, int rows, int V, const float*
                      float* top_scores, long long* top_index, capnet_stream_t stream) {
   return beam_topk(logits, ld, rows, V, prev_scores, k, top_scores, top_index, S(stream));
 }
+size_t capnet_beam_state_bytes(int n, int k, int max_steps) { return beam_state_bytes(n, k, max_steps); }
+int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words,
+                     capnet_stream_t stream) {
+  return beam_init(beam, n, k, max_steps, start_token, prev_words, S(stream));
+}
+int capnet_beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                        long long end_token, long long* next_words, long long* parent_rows, capnet_stream_t stream) {
+  return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream));
+}
+int capnet_beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
+                       capnet_stream_t stream) {
+  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, S(stream));
+}
+int capnet_beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live,
+                     const float** scores) {
+  return beam_live(beam, n, k, max_steps, live_total, live, scores);
+}
 int capnet_att_step_fwd(const float* att1, const float* feat, const float* att2, float* gate_io,
                         long ldz, const float* w_full, const float* b_full, int rows, int P, int A,
                         int C, float* alpha_out, float* alphas_bt, int steps, int t, float* awe_out,

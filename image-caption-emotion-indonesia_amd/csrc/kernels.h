@@ -217,6 +217,14 @@ int beam_topk_batched(const float* logits, long ld, int V, const float* prev, co
                       long long* out_index, hipStream_t stream);
 int beam_topk(const float* logits, long ld, int rows, int V, const float* prev, int k,
               float* out_scores, long long* out_index, hipStream_t stream);
+// beam search with device-side bookkeeping (fixed slots: image i's beams at rows i k .. i k + k - 1 throughout)
+size_t beam_state_bytes(int n, int k, int max_steps);
+int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream);
+int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+                 long long* next_words, long long* parent_rows, hipStream_t stream);
+int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
+                hipStream_t stream);
+int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
 int gather_rows(const float* src, const int* idx, float* out, int rows, int C, hipStream_t stream);
 int colsum(const float* x, long ld, int rows, int C, float* out, int accumulate, hipStream_t stream,
            float* ws = nullptr, size_t ws_floats = 0);

@@ -481,6 +481,176 @@ int beam_topk_batched(const float* logits, long ld, int V, const float* prev, co
   return kOk;
 }
 
+// ---- beam search with its bookkeeping on the device (capnet.beam.beam_search_device) -------------------------------
+// Fixed slots: image i owns rows i k .. i k + k - 1 of the decoder step for the whole search; its live beams are its
+// first live[i] slots, in the top-k rank order of the survivors (the order capnet.beam keeps). The state, in 4-byte
+// words (L = max_steps + 2 tokens per sequence):
+//   [0] live_total  [1..3] unused | live[n] | n_done[n] | scores[n k] f32 | done_score[n k] f32 | done_len[n k] |
+//   seq[2][n][k][L] (step s reads buffer (s - 1) & 1 and writes the other) | done_seq[n][k][L]
+struct BeamState {
+  int *live_total, *live, *n_done, *done_len, *seq, *done_seq;
+  float *scores, *done_score;
+};
+static size_t beam_state_words(int n, int k, int max_steps) {
+  const size_t nk = (size_t)n * k;
+  return 4 + 2 * (size_t)n + 3 * nk + 3 * nk * (max_steps + 2);
+}
+__host__ __device__ static inline BeamState beam_state_of(void* beam, int n, int k, int max_steps) {
+  const long nk = (long)n * k;
+  int* w = static_cast<int*>(beam);
+  BeamState s;
+  s.live_total = w;
+  s.live = w + 4;
+  s.n_done = s.live + n;
+  s.scores = reinterpret_cast<float*>(s.n_done + n);
+  s.done_score = s.scores + nk;
+  s.done_len = reinterpret_cast<int*>(s.done_score + nk);
+  s.seq = s.done_len + nk;
+  s.done_seq = s.seq + 2 * nk * (max_steps + 2);
+  return s;
+}
+
+__global__ __launch_bounds__(256) void beam_init_kernel(void* beam, int n, int k, int max_steps, int start_token,
+                                                        long long* __restrict__ prev_words) {
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int L = max_steps + 2, nk = n * k;
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nk; t += gridDim.x * blockDim.x) {
+    s.scores[t] = 0.f;
+    s.seq[(long)t * L] = start_token;
+    prev_words[t] = start_token;
+    if (t < n) { s.live[t] = k; s.n_done[t] = 0; }
+    if (t == 0) *s.live_total = nk;
+  }
+}
+
+// one step of image blockIdx.x: beam_topk_body over its live rows (row 0 alone at step 1) for its live[i] best, then
+// what beam_search_batched does on the host -- <end> completes a beam (score and sequence appended to the image's
+// completed list, by step then rank), every other beam survives into the next free slot
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
+    void* beam, const float* __restrict__ logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+    long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_parent[kBeamMax], s_word[kBeamMax], s_dst[kBeamMax];   // s_dst: slot, or -1 - index in the completed list
+  __shared__ int s_alive;
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x, tid = threadIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const int live = s.live[i];
+  if (live > 0) {
+    beam_topk_body(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
+    if (tid == 0) {
+      int alive = 0, done = s.n_done[i];
+      for (int j = 0; j < live; ++j) {
+        const int w = (int)(s_flat[j] % V);
+        s_parent[j] = (int)(s_flat[j] / V);
+        s_word[j] = w;
+        s_dst[j] = w == end_token ? -1 - done++ : alive++;
+      }
+      s_alive = alive;
+      s.n_done[i] = done;
+      s.live[i] = alive;
+      if (alive != live) atomicAdd(s.live_total, alive - live);
+    }
+    __syncthreads();
+    // sequences: `step` tokens of the parent, then the word
+    const int* seq_in = s.seq + ((long)((step - 1) & 1) * n * k + row0) * L;
+    int* seq_out = s.seq + ((long)(step & 1) * n * k + row0) * L;
+    int* seq_done = s.done_seq + row0 * L;
+    for (int t = tid; t < live * (step + 1); t += kBeamThreads) {
+      const int j = t / (step + 1), e = t % (step + 1);
+      int* dst = s_dst[j] >= 0 ? seq_out + (long)s_dst[j] * L : seq_done + (long)(-1 - s_dst[j]) * L;
+      dst[e] = e < step ? seq_in[(long)s_parent[j] * L + e] : s_word[j];
+    }
+    if (tid < live) {
+      const int d = s_dst[tid];
+      if (d >= 0) {
+        s.scores[row0 + d] = s_score[tid];
+        next_words[row0 + d] = s_word[tid];
+        parent_rows[row0 + d] = row0 + s_parent[tid];
+      } else {
+        s.done_score[row0 - 1 - d] = s_score[tid];
+        s.done_len[row0 - 1 - d] = step + 1;
+      }
+    }
+  }
+  // dead slots still take the decoder step: <end> on their own row
+  const int alive = live > 0 ? s_alive : 0;
+  if (tid >= alive && tid < k) {
+    next_words[row0 + tid] = end_token;
+    parent_rows[row0 + tid] = row0 + tid;
+  }
+}
+
+// one wave per image: the first maximum of the completed scores in completion order; nothing completed -> [<end>]
+__global__ __launch_bounds__(64) void beam_finish_kernel(const void* beam, int n, int k, int max_steps, long long end_token,
+                                                         long long* __restrict__ seqs, int* __restrict__ lengths) {
+  const BeamState s = beam_state_of(const_cast<void*>(beam), n, k, max_steps);
+  const int i = blockIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const int done = s.n_done[i];
+  int best = 0;
+  for (int q = 1; q < done; ++q)
+    if (s.done_score[row0 + q] > s.done_score[row0 + best]) best = q;
+  const int len = done ? s.done_len[row0 + best] : 1;
+  const int* src = s.done_seq + (row0 + best) * L;
+  for (int e = threadIdx.x; e < L; e += 64) seqs[(long)i * L + e] = e >= len ? 0 : done ? src[e] : end_token;
+  if (threadIdx.x == 0) lengths[i] = len;
+}
+
+static int beam_check(const char* what, const void* beam, int n, int k, int max_steps) {
+  CAPNET_REQUIRE(beam != nullptr, "%s: null beam state", what);
+  CAPNET_REQUIRE(n >= 1 && k >= 1 && k <= kBeamMax && max_steps >= 1 && (long)n * k * (max_steps + 2) < (1L << 28),
+                 "%s: n=%d k=%d max_steps=%d (n, max_steps >= 1; 1 <= k <= %d)", what, n, k, max_steps, kBeamMax);
+  return kOk;
+}
+
+size_t beam_state_bytes(int n, int k, int max_steps) {
+  if (n < 1 || k < 1 || k > kBeamMax || max_steps < 1) return 0;
+  return beam_state_words(n, k, max_steps) * sizeof(int);
+}
+
+int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream) {
+  if (int rc = beam_check("beam_init", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(prev_words != nullptr, "beam_init: null argument");
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "beam_init: start_token %lld", start_token);
+  hipLaunchKernelGGL(beam_init_kernel, dim3((n * k + 255) / 256), dim3(256), 0, stream, beam, n, k, max_steps, (int)start_token,
+                     prev_words);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+                 long long* next_words, long long* parent_rows, hipStream_t stream) {
+  if (int rc = beam_check("beam_advance", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(logits && next_words && parent_rows, "beam_advance: null argument");
+  CAPNET_REQUIRE(V >= 1 && k <= V && ld >= V && step >= 1 && step <= max_steps,
+                 "beam_advance: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", V, k, ld, step,
+                 max_steps);
+  hipLaunchKernelGGL(beam_advance_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps, step,
+                     end_token, next_words, parent_rows);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
+                hipStream_t stream) {
+  if (int rc = beam_check("beam_finish", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(seqs && lengths, "beam_finish: null argument");
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(n), dim3(64), 0, stream, beam, n, k, max_steps, end_token, seqs, lengths);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores) {
+  if (int rc = beam_check("beam_live", beam, n, k, max_steps)) return rc;
+  const BeamState s = beam_state_of(const_cast<void*>(beam), n, k, max_steps);
+  if (live_total) *live_total = s.live_total;
+  if (live) *live = s.live;
+  if (scores) *scores = s.scores;
+  return kOk;
+}
+
 // ---- dropout between stacked layers: dst = src * mask / keep over rows [r0, r1) ------------------------------------
 __global__ __launch_bounds__(256) void rows_dropout_kernel(const float* __restrict__ src, float* __restrict__ dst, int r0,
                                                            int rows, int C, float p, unsigned long long seed, int layer,

@@ -19,19 +19,25 @@ import os
 import torch
 
 from . import ops
-from .beam import beam_search, beam_search_batched
+from .beam import beam_search, beam_search_batched, beam_search_device
 
 FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
 _GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torch's i, f, g, o
 
 
 # ---- beam search ------------------------------------------------------------------------------------
-def beam_decode(dec, step_fn, state, n, k, start_token, end_token):
+def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
-    together (beam_search_batched) -> a list of n token lists."""
+    together (beam_search_batched) -> a list of n token lists. on_device: the same results from
+    capnet.beam.beam_search_device, whose bookkeeping stays on the device (fixed rows, no host read per step; poll_every
+    as there)."""
     dev = state[0].device
     with torch.no_grad():
+        if on_device:
+            seqs = beam_search_device(step_fn, state, 1 if n is None else n, dec.vocab_size, start_token, end_token, k,
+                                      dec.max_seq_length, dev, poll_every)
+            return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
         if n is None:
             return beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
         return beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)

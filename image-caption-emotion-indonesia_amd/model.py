@@ -638,15 +638,17 @@ class DecoderFactoredLSTM(nn.Module):
             return self.C(hidden), (h, c)
         return step_fn, zero_state(rows, self.hidden_size, self.B.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0):
         """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
         an input of the decode steps (the first input is B(<start>) and the state starts at zero):
-        `features` only fixes the device. Returns LongTensor [1, L]."""
-        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token)
+        `features` only fixes the device. Returns LongTensor [1, L].
+        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
+        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token, on_device, poll_every)
 
-    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
+                     poll_every=0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched): what the reference's test-set
         evaluator does image by image (stylenet/evaluator.py:76-84). Returns a list of token lists, each equal to
         sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token)
+        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every)

@@ -93,12 +93,13 @@ class DecoderRNN(nn.Module):
             return self.linear(hidden), (h, c)
         return step_fn, zero_state(rows, self.hidden_size, self.embed.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
         """Beam search, nic/model.py:117-207 (the image features are not an input of the decode
-        steps there either). Returns LongTensor [1, L]."""
-        return beam_decode(self, *self._beam(k), None, k, start_token, end_token)
+        steps there either). Returns LongTensor [1, L].
+        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
+        return beam_decode(self, *self._beam(k), None, k, start_token, end_token, on_device, poll_every)
 
-    def sample_batch(self, features, start_token, end_token, k=5):
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched)."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k), n, k, start_token, end_token)
+        return beam_decode(self, *self._beam(n * k), n, k, start_token, end_token, on_device, poll_every)

@@ -35,7 +35,7 @@ pack_cell, att_beam_step); sample / sample_batch are the base classes' over this
 import torch
 
 from ._lib import CapnetError
-from .decode import as_state, beam_decode, cell_stepper
+from .decode import as_state, cell_stepper
 from .decode import pack_cell as _pack_cell  # noqa: F401  (the packing's name while it lived here; the tests pack by it)
 from .model import Linear
 from .nic_model import DecoderRNN, LSTMCell
@@ -193,8 +193,4 @@ class StackedDecoderRNNAtt(DecoderRNNAtt):
         """The beam state is layer 0's (h, c) and the upper layers' one tensor [rows, 2(L-1), H]."""
         return (self._upper_state(feat.mean(dim=1), rows=img),), self._beam_upper
 
-    def sample_batch(self, features, start_token, end_token, k=5):
-        """sample() for every image of `features` at once (capnet.beam.beam_search_batched). Returns a list of token
-        lists, each equal to sample(features[i:i+1], ...)[0].tolist()."""
-        n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k), n, k, start_token, end_token)
+    # sample / sample_batch: DecoderRNNAtt's, over _beam with this _upper_beam

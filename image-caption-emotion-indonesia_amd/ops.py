@@ -207,6 +207,62 @@ def beam_topk_batched(logits, prev_scores, meta):
     return scores, index
 
 
+class BeamState:
+    """The device-resident state of capnet.beam.beam_search_device (capnet_beam_*): n images x k fixed slots, at most
+    `max_steps` advances. live_total [1], live [n] (int32) and scores [n, k] (float32) are views into the state."""
+
+    def __init__(self, n, k, max_steps, device):
+        nbytes = _lib.lib().capnet_beam_state_bytes(n, k, max_steps)
+        if not nbytes:
+            raise CapnetError("beam state: n=%d k=%d max_steps=%d (n, max_steps >= 1; 1 <= k <= 16)" % (n, k, max_steps))
+        self.n, self.k, self.max_steps = n, k, max_steps
+        self.words = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+        p = [C.c_void_p() for _ in range(3)]
+        check(_lib.lib().capnet_beam_live(ptr(self.words), n, k, max_steps, *[C.byref(q) for q in p]), "capnet_beam_live")
+        at = [(q.value - self.words.data_ptr()) // 4 for q in p]
+        self.live_total = self.words[at[0]:at[0] + 1]
+        self.live = self.words[at[1]:at[1] + n]
+        self.scores = self.words[at[2]:at[2] + n * k].view(torch.float32).view(n, k)
+
+
+def beam_init(n, k, max_steps, start_token, prev_words):
+    """A fresh BeamState on prev_words' device: every beam live, score 0, sequence [start_token]; prev_words (int64
+    [n k], contiguous) is filled with start_token."""
+    _need_cuda(prev_words)
+    if prev_words.dtype != torch.int64 or prev_words.numel() != n * k or not prev_words.is_contiguous():
+        raise CapnetError("beam_init: prev_words must be a contiguous int64 [n k] tensor")
+    beam = BeamState(n, k, max_steps, prev_words.device)
+    check(_lib.lib().capnet_beam_init(ptr(beam.words), n, k, max_steps, int(start_token), ptr(prev_words), current_stream()),
+          "capnet_beam_init")
+    return beam
+
+
+def beam_advance(beam, logits, step, end_token, next_words, parent_rows):
+    """capnet_beam_advance: step `step` (1-based) of every image on logits [n k, V]; fills next_words and parent_rows
+    (int64 [n k], contiguous) -- see include/capnet.h."""
+    _need_cuda(logits, next_words, parent_rows)
+    nk = beam.n * beam.k
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
+        raise CapnetError("beam_advance: logits must be float32 [n k, V] with unit column stride")
+    for w in (next_words, parent_rows):
+        if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
+            raise CapnetError("beam_advance: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    check(_lib.lib().capnet_beam_advance(ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1],
+                                         logits.shape[1], beam.n, beam.k, beam.max_steps, int(step), int(end_token),
+                                         ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance")
+
+
+def beam_finish(beam, end_token):
+    """capnet_beam_finish -> (seqs int64 [n, max_steps + 2], lengths int32 [n], packed): the two are views of the one
+    int64 buffer `packed`, so a caller takes both to the host in one copy."""
+    n, L = beam.n, beam.max_steps + 2
+    packed = torch.empty(n * L + (n + 1) // 2, dtype=torch.int64, device=beam.words.device)
+    seqs, lengths = packed[:n * L].view(n, L), packed[n * L:].view(torch.int32)[:n]
+    check(_lib.lib().capnet_beam_finish(ptr(beam.words), n, beam.k, beam.max_steps, int(end_token), ptr(seqs), ptr(lengths),
+                                        current_stream()), "capnet_beam_finish")
+    return seqs, lengths, packed
+
+
 def attention_step(att1, feat, z, A, w_full, b_full, xa=None, xa_col=0):
     """One attention step for s rows (no autograd; Attention.forward / sample()).
     att1 [s, P, A] = encoder_att(features); feat [s, P, C]; z [s, A + C] = [decoder_att(h) |

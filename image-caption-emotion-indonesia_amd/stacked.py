@@ -153,17 +153,19 @@ class StackedFactoredLSTM(nn.Module):
         zeros = torch.zeros((rows, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=emb.device)
         return step_fn, (zeros,)
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0):
         """Beam search, stylenet/model.py:198-294, over the stack: as DecoderFactoredLSTM.sample, the image is NOT an
         input (`features` only fixes the device), every layer's state starts at zero, the first input is B(<start>) and
-        factual_limit is ignored. Returns LongTensor [1, L]."""
-        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token)
+        factual_limit is ignored. Returns LongTensor [1, L].
+        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
+        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token, on_device, poll_every)
 
-    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual'):
+    def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
+                     poll_every=0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched). Returns a list of token lists,
         each equal to sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token)
+        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every)
 
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, captions, lengths, features=None, teacher_forcing_ratio=0.8, mode="factual", tf_mask=None):

@@ -419,24 +419,27 @@ def val_emotion(encoder, decoder, vocab, criterion, data_loaders, tags, device=N
             [r[3] for r in res])
 
 
-def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=None, verbose=False):
+def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=None, verbose=False, on_device=False):
     """The test-set evaluator, stylenet/evaluator.py:55-120: encoder + decoder in eval mode, every test image decoded by
     beam search, corpus BLEU-1..4 with the reference's four weight tuples (references and hypotheses as the reference
     builds them: the captions' and the sampled ids as they are, <start> / <end> included). The reference calls
     decoder.sample() per image; here a loader batch is decoded at once (decoder.sample_batch: B x k rows per step) --
-    the same sequences (tests/test_sample_gpu.py). Returns (bleu_1, bleu_2, bleu_3, bleu_4)."""
+    the same sequences (tests/test_sample_gpu.py). on_device: passed on to the decoder (capnet.decode.beam_decode).
+    Returns (bleu_1, bleu_2, bleu_3, bleu_4)."""
     decoder.eval()
     encoder.eval()
     device = device or next(decoder.parameters()).device
     start, end = vocab.word2idx['<start>'], vocab.word2idx['<end>']
     kw = {} if mode is None else {"mode": mode}
+    if on_device:
+        kw["on_device"] = True
     references, hypotheses = [], []
     for images, captions, lengths, all_captions in data_loader:
         with torch.no_grad():
             features = encoder(images.to(device))
         if hasattr(decoder, "sample_batch"):
             seqs = decoder.sample_batch(features, start_token=start, end_token=end, k=k, **kw)
-        else:       # (nic DecoderRNNAtt: image by image, as the reference does)
+        else:       # (a decoder without one: image by image, as the reference does)
             seqs = [decoder.sample(features[i:i + 1], start_token=start, end_token=end, k=k, **kw)[0].tolist()
                     for i in range(features.size(0))]
         for sampled_ids, caps in zip(seqs, all_captions):

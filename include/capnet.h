@@ -101,6 +101,32 @@ int capnet_beam_topk(const float* logits, long ld, int rows, int V, const float*
 int capnet_beam_topk_batched(const float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
                              float* top_scores, long long* top_index, capnet_stream_t stream);
 
+/* Beam search whose bookkeeping stays on the device (capnet.beam.beam_search_device): what capnet.beam's loops do on the
+ * host after every capnet_beam_topk_batched -- which beam survives, the sequences, the completed list -- done by the
+ * workgroup that selected. Image i owns rows i k .. i k + k - 1 of the decoder step for the WHOLE search; its live beams
+ * are its first live[i] slots in top-k rank order, dead slots still take the step (their logits are never read).
+ * `beam`: capnet_beam_state_bytes(n, k, max_steps) bytes of caller-owned device memory, 4-byte aligned; max_steps is the
+ * number of capnet_beam_advance calls the search may make (max_seq_length + 1 for the decoders). 1 <= k <= 16, k <= V.
+ *   init:    every beam live with score 0 and the sequence [start_token]; prev_words[n k] = start_token.
+ *   advance: step = 1, 2, ... in order, on the logits [n k][ld] of that step. The selection is capnet_beam_topk_batched's
+ *            (row 0 alone at step 1). A selected <end> completes its beam (appended to the image's completed list, by step
+ *            then rank); any other word w of parent slot p survives into the image's next free slot s:
+ *            next_words[i k + s] = w, parent_rows[i k + s] = i k + p. Dead slots get end_token and their own row, so both
+ *            arrays are fully written by every call and the caller re-indexes its state by parent_rows.
+ *   finish:  per image the first maximum of the completed scores in completion order (the reference's
+ *            list.index(max(...))), [end_token] if nothing completed: seqs[n][max_steps + 2] (padded with 0), lengths[n].
+ *   live:    (host arithmetic only) device pointers into `beam`: live_total (the number of live beams of all images; zero
+ *            means every later advance is a no-op), live[n], scores[n k]. Any of the three may be NULL. */
+size_t capnet_beam_state_bytes(int n, int k, int max_steps);
+int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words,
+                     capnet_stream_t stream);
+int capnet_beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                        long long end_token, long long* next_words, long long* parent_rows, capnet_stream_t stream);
+int capnet_beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
+                       capnet_stream_t stream);
+int capnet_beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live,
+                     const float** scores);
+
 /* ---- ResNet-152 trunk -------------------------------------------------------------------
  * torchvision resnet152 children[:-1] (pooled [B][2048]) or [:-2] (NHWC map [B][S][S][2048]),
  * as run under torch.no_grad() by EncoderCNN.forward: stylenet/model.py:15-18,23-25,
