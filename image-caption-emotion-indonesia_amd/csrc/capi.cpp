@@ -346,16 +346,17 @@ int capnet_lstm_pointwise_fwd(float* pre, const float* c_prev, float* c_out, flo
   return lstm_pointwise_fwd(pre, 4L * H, c_prev, c_out, h_out, b, H, 0, 1, 3, 2, 1, S(stream));
 }
 
-int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
-                                    const float* x, const float* const* wcat, const float* const* beff,
-                                    const float* state_in, float* state_out, float* h_top, int* err_flag,
-                                    capnet_stream_t stream) {
+int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                      const float* x, const float* const* wcat, const float* const* beff,
+                                      const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
+                                      int* err_flag, capnet_stream_t stream) {
   CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "stacked_decode_step: unknown cell %d", cell);
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "stacked_decode_step: layers %d (1..8)", nlayers);
   CAPNET_REQUIRE(rows >= 1, "stacked_decode_step: rows %d", rows);
   CAPNET_REQUIRE(stacked_decode_supported(E, H), "stacked_decode_step: unsupported E=%d H=%d", E, H);
   CAPNET_REQUIRE(x && wcat && beff && state_in && state_out && h_top, "stacked_decode_step: null argument");
   CAPNET_REQUIRE(!tokens || (err_flag && V >= 1), "stacked_decode_step: token ids need err_flag and V >= 1");
+  CAPNET_REQUIRE(!parent_rows || err_flag, "stacked_decode_step: parent rows need err_flag");
   CAPNET_REQUIRE(state_in != state_out, "stacked_decode_step: state_in and state_out must differ");
   CAPNET_REQUIRE(aligned16(state_in) && aligned16(state_out), "stacked_decode_step: state alignment");
   for (int l = 0; l < nlayers; ++l) {
@@ -363,7 +364,15 @@ int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int 
     CAPNET_REQUIRE(aligned16(wcat[l]), "stacked_decode_step: weights of layer %d not 16-B aligned", l);
   }
   return stacked_decode_step(cell, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top, err_flag,
-                             S(stream));
+                             S(stream), parent_rows);
+}
+
+int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                    const float* x, const float* const* wcat, const float* const* beff,
+                                    const float* state_in, float* state_out, float* h_top, int* err_flag,
+                                    capnet_stream_t stream) {
+  return capnet_stacked_decode_step_gather(cell, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, nullptr, state_out,
+                                           h_top, err_flag, stream);
 }
 
 int capnet_stacked_decode_step(int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
@@ -405,6 +414,37 @@ int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int st
   }
   return lstm_greedy_decode(nlayers, rows, E, H, V, steps, features, start_tokens, emb, wcat, beff, Cw, Cb, state0, workspace,
                             ids, state_out, err_flag, S(stream));
+}
+
+size_t capnet_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps) {
+  return beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps);
+}
+
+int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                       long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                       const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                       size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                       capnet_stream_t stream) {
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "beam_decode: unknown cell %d", cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "beam_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(n >= 1 && max_steps >= 1 && V >= 1 && poll_every >= 0, "beam_decode: n %d, max_steps %d, V %d, poll_every %d", n,
+                 max_steps, V, poll_every);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
+  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28) && (long)n * k * V < (1L << 31), "beam_decode: n k too large");
+  CAPNET_REQUIRE(stacked_decode_supported(E, H), "beam_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "beam_decode: start_token %lld", start_token);
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && slab && seqs && lengths && err_flag, "beam_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && aligned16(slab) && aligned16(Cw) && (!state0 || aligned16(state0)),
+                 "beam_decode: workspace, slab, Cw and state0 must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "beam_decode: seqs / lengths alignment");
+  CAPNET_REQUIRE(slab_floats >= (size_t)n * k * V, "beam_decode: the slab holds %zu floats, one [n k][V] block is %zu", slab_floats,
+                 (size_t)n * k * V);
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "beam_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "beam_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
+                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream));
 }
 
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,

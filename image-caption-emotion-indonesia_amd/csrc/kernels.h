@@ -258,11 +258,12 @@ int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, co
 
 // lstm_decode_step.hip: one inference step of every layer of a stacked LSTM (beam search), one launch per layer, any
 // number of rows: [x | h] . [Weff | W]^T + beff and the gates (blocks i, f, o, c~); layer 0 gathers its embedding rows by
-// token id. cell 0: the factored cell, h = o c; cell 1: nn.LSTMCell, h = o tanh(c)
+// token id. cell 0: the factored cell, h = o c; cell 1: nn.LSTMCell, h = o tanh(c). parent_rows (int64 [rows], optional): row
+// r reads its previous h and c at row parent_rows[r] of state_in (a beam search's re-ordering, read in place)
 bool stacked_decode_supported(int E, int H);
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream);
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr);
 
 // vocab_argmax.hip: tok[r] = first argmax_v (h[r] . W[v] + b[v]) in one launch, no logits in memory (ws: vocab_argmax_ws_bytes,
 // its first 16 bytes zero before the first use); and capnet.seq2seq's greedy `sample` as one chain of launches
@@ -275,6 +276,13 @@ int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, co
                        const long long* start_tokens, const float* emb, const float* const* wcat,
                        const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,
                        long long* ids, float* state_out, int* err_flag, hipStream_t s);
+// ... and the beam search of a plain stack as one chain of launches: per step the gathered decode step, the vocabulary
+// projection (sgemm_splitk on the caller's slab) and beam_advance; poll_every > 0 reads live_total after every such step
+size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps);
+int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
+                const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s);
 
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);

@@ -14,6 +14,9 @@
 // TM = 1 at 16 groups per wave, where two tiles' operands and the weights would not fit in 256 VGPRs),
 // and the eight K-partial tiles are summed through LDS by the epilogue, which applies the gates and writes c, h (and the
 // top layer's h once more, densely, for the vocabulary projection). Plain vector loads and stores only.
+// GATHER (beam search: capnet_stacked_decode_step_gather, capnet_beam_decode): a row's h_prev and c_prev are those of row
+// parent[row] of state_in -- the re-ordering of the beams read in place instead of copied first. Only the two state reads
+// move: x, the token ids and every store stay on the row itself, and state_in != state_out makes repeated parents safe.
 // The nn.LSTMCell instance (TANH_OUT, capnet.nic_stacked) takes wcat = [weight_ih, zero columns up to kin | weight_hh]
 // and beff = bias_ih + bias_hh with the host's gate blocks reordered from torch's i, f, g, o to i, f, o, c~ = g: the
 // LSTM cell has no chain to fold, and only the epilogue differs, h = o tanh(c).
@@ -44,9 +47,24 @@ struct DecodeLayerArgs {
   const float* w;        // [4H, kin + H] = [Weff | W], gate blocks i, f, o, c~
   const float* b;        // [4H]
   int kin, rows, H;
+  const long long* parent;  // GATHER: int64 [rows], hprev / cprev are read at row parent[r] (outside [0, rows): err, row r)
 };
 
-template <int NJ, int TM, bool TANH_OUT>  // k groups per wave (at most), 16-row tiles per pass; h = o tanh(c)
+// the row whose previous state row `row` reads
+template <bool GATHER>
+__device__ __forceinline__ long state_row(const DecodeLayerArgs& a, int row) {
+  if constexpr (GATHER) {
+    const long long p = a.parent[row];
+    const bool ok = p >= 0 && p < a.rows;
+    if (!ok && a.err) *a.err = 1;
+    return ok ? (long)p : (long)row;
+  } else {
+    return row;
+  }
+}
+
+// k groups per wave (at most), 16-row tiles per pass; h = o tanh(c); the previous state through a.parent
+template <int NJ, int TM, bool TANH_OUT, bool GATHER>
 __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a) {
   constexpr int kPass = 16 * TM;
   __shared__ float red[kDecWaves][kPass][17];
@@ -84,7 +102,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
         xr = ok ? (long)t : 0;
       }
       const float* xrow = a.x + xr * a.ldx;
-      const float* hrow = a.hprev + (long)row * a.lds_in;
+      const float* hrow = a.hprev + state_row<GATHER>(a, row) * a.lds_in;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -104,7 +122,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
     }
     const int erow = r0 + er;
     const bool estore = ethread && erow < a.rows;
-    const float cp = estore ? a.cprev[(long)erow * a.lds_in + u0 + eu] : 0.f;
+    const float cp = estore ? a.cprev[state_row<GATHER>(a, erow) * a.lds_in + u0 + eu] : 0.f;
     f32x4 acc[TM];
 #pragma unroll
     for (int m = 0; m < TM; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -142,28 +160,28 @@ bool stacked_decode_supported(int E, int H) {
   return E >= 1 && step_hidden_supported(H) && round16(E) + H <= kDecMaxK;
 }
 
-template <int NJ, bool TANH_OUT>
+template <int NJ, bool TANH_OUT, bool GATHER>
 static void launch_decode(const DecodeLayerArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT>), dim3(a.H / 4), dim3(64 * kDecWaves), 0,
+  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0,
                      stream, a);
 }
 
-template <bool TANH_OUT>
+template <bool TANH_OUT, bool GATHER>
 static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
   const int per_wave = ((a.kin + a.H) / 16 + kDecWaves - 1) / kDecWaves;
-  if (per_wave <= 2) launch_decode<2, TANH_OUT>(a, stream);
-  else if (per_wave <= 4) launch_decode<4, TANH_OUT>(a, stream);
-  else if (per_wave <= 6) launch_decode<6, TANH_OUT>(a, stream);
-  else if (per_wave <= 8) launch_decode<8, TANH_OUT>(a, stream);
-  else if (per_wave <= 12) launch_decode<12, TANH_OUT>(a, stream);
-  else launch_decode<16, TANH_OUT>(a, stream);
+  if (per_wave <= 2) launch_decode<2, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 4) launch_decode<4, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 6) launch_decode<6, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 8) launch_decode<8, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 12) launch_decode<12, TANH_OUT, GATHER>(a, stream);
+  else launch_decode<16, TANH_OUT, GATHER>(a, stream);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
 
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream) {
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows) {
   const long lds = 2L * nlayers * H;
   for (int l = 0; l < nlayers; ++l) {
     DecodeLayerArgs a;
@@ -195,7 +213,10 @@ int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, co
     a.b = beff[l];
     a.rows = rows;
     a.H = H;
-    int rc = cell == kCellLSTM ? launch_decode_layer<true>(a, stream) : launch_decode_layer<false>(a, stream);
+    a.parent = parent_rows;
+    int rc;
+    if (parent_rows) rc = cell == kCellLSTM ? launch_decode_layer<true, true>(a, stream) : launch_decode_layer<false, true>(a, stream);
+    else rc = cell == kCellLSTM ? launch_decode_layer<true, false>(a, stream) : launch_decode_layer<false, false>(a, stream);
     if (rc != kOk) return rc;
   }
   return kOk;

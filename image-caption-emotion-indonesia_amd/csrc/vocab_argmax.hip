@@ -197,4 +197,69 @@ int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, co
   return kOk;
 }
 
+// ---- the whole beam search of a plain stack: steps x (one gathered decode-step launch per layer + the vocabulary
+// projection + one beam_advance launch), then beam_finish -- capnet.beam.beam_search_device's loop without its host side
+// ws: [state A | state B] ([n k][2L][H] each) | h_top [n k][H] | logits [n k][V] | words A | words B | parent_rows (int64
+// [n k] each) | the beam_state_bytes block; every part starts 16-B aligned
+struct BeamDecodeWs {
+  size_t state, h_top, logits, words, parent, beam, total;   // byte offsets (state B at state + (h_top - state) / 2)
+};
+static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, int max_steps) {
+  const size_t nk = (size_t)n * k;
+  BeamDecodeWs w;
+  w.state = 0;
+  w.h_top = 2 * gd_align(nk * 2 * nlayers * H * sizeof(float));
+  w.logits = w.h_top + gd_align(nk * H * sizeof(float));
+  w.words = w.logits + gd_align(nk * V * sizeof(float));
+  w.parent = w.words + 2 * gd_align(nk * 8);
+  w.beam = w.parent + gd_align(nk * 8);
+  w.total = w.beam + gd_align(beam_state_bytes(n, k, max_steps));
+  return w;
+}
+
+size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps) {
+  if (nlayers < 1 || nlayers > 8 || n < 1 || H < 1 || V < 1 || !beam_state_bytes(n, k, max_steps)) return 0;
+  return beam_decode_layout(nlayers, n, k, H, V, max_steps).total;
+}
+
+int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
+                const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+  const int nk = n * k;
+  const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps);
+  const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
+  char* p = reinterpret_cast<char*>(ws);
+  float* state[2] = {reinterpret_cast<float*>(p + w.state), reinterpret_cast<float*>(p + w.state + w.h_top / 2)};
+  float* h_top = reinterpret_cast<float*>(p + w.h_top);
+  float* logits = reinterpret_cast<float*>(p + w.logits);
+  long long* words[2] = {reinterpret_cast<long long*>(p + w.words),
+                         reinterpret_cast<long long*>(p + w.words + (w.parent - w.words) / 2)};
+  long long* parent = reinterpret_cast<long long*>(p + w.parent);
+  void* beam = p + w.beam;
+  const int* live_total = nullptr;
+  if (int rc = beam_live(beam, n, k, max_steps, &live_total, nullptr, nullptr)) return rc;
+  if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
+  else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
+  if (int rc = beam_init(beam, n, k, max_steps, start_token, words[0], s)) return rc;
+  int issued = 0;
+  for (int step = 1; step <= max_steps; ++step) {
+    // step 1: every beam is at its own (initial) row; afterwards the rows the previous beam_advance chose
+    int rc = stacked_decode_step(cell, nlayers, nk, E, H, V, words[(step - 1) & 1], emb, wcat, beff, state[(step - 1) & 1],
+                                 state[step & 1], h_top, err_flag, s, step == 1 ? nullptr : parent);
+    if (rc == kOk) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+    if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
+    if (rc != kOk) return rc;
+    issued = step;
+    if (poll_every > 0 && step % poll_every == 0 && step < max_steps) {
+      int live = 0;
+      CAPNET_HIP_CHECK(hipMemcpyAsync(&live, live_total, sizeof(int), hipMemcpyDeviceToHost, s));
+      CAPNET_HIP_CHECK(hipStreamSynchronize(s));
+      if (!live) break;
+    }
+  }
+  if (steps_run) *steps_run = issued;
+  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, s);
+}
+
 }  // namespace capnet

@@ -2,14 +2,17 @@
 composed factored cell, and the stepper of a stacked decoder. The decoder classes keep what is theirs: which modules a
 mode selects, the layout of their beam state, their weight fold.
 
-  * beam_decode: the one caller of capnet.beam's two loops. Every class builds (step_fn, initial state) in one private
-    `_beam` method; its sample() asks for one group of k beams, its sample_batch() for n groups.
+  * beam_decode: the one caller of capnet.beam's loops. Every class builds (step_fn, initial state) in one private
+    `_beam` method; its sample() asks for one group of k beams, its sample_batch() for n groups. one_call=True: the
+    whole search of a plain stack in one C call (ops.beam_decode) on the PlainStack a class attaches to its step_fn
+    (plain_stack: the fused step's packed weights, the embedding table and the projection).
   * attend: Attention.forward, the single step outside a beam search.
   * att_beam_start / att_beam_step: an attention decoder's beam search. The set-up (encoder_att once per image, the
     initial state) is written once for one image and once for n; the step (z = [decoder_att; f_beta](h), the embedding
     into xa, ops.attention_step, then the caller's cell, upper layers and vocabulary projection) once.
   * factored_step: U_g(S_g(V_g(x))) + W_g(h) per gate and the pointwise cell, on torch.cat. DecoderFactoredLSTM's own
     forward_step accumulates into column blocks instead and stays where it is.
+  * fold_factored: a factored layer's chain folded into the decode step's [Weff | W] and beff.
   * stack_stepper / cell_stepper / pack_cell / as_state / input_width: one step of a stack over a [rows, 2L, H] state
     (slot 2l = h of layer l, 2l+1 = its c), on capnet_stacked_decode_step or composed. CAPNET_NO_FUSED_DECODE_STEP=1
     (read here, at every stepper built) takes the composed step, which also serves the shapes the kernel does not take.
@@ -26,14 +29,41 @@ _GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torc
 
 
 # ---- beam search ------------------------------------------------------------------------------------
-def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0):
+class PlainStack:
+    """What ops.beam_decode needs of a decoder whose beam step is a plain stack on the fused decode step, starting at
+    zero: the cell kind, the packed weights [(wcat, beff)] per layer, the embedding table, the projection."""
+
+    def __init__(self, cell, packed, emb, Cw, Cb):
+        self.cell, self.emb, self.Cw, self.Cb = cell, emb.detach(), Cw.detach(), None if Cb is None else Cb.detach()
+        self.wcat, self.beff = [w for w, _ in packed], [b for _, b in packed]
+
+
+def plain_stack(step_fn, packed, cell, emb, C):
+    """step_fn with the PlainStack of `packed` attached -- a stack_stepper's .packed, None unless it runs the fused step
+    (the shape is the kernel's and CAPNET_NO_FUSED_DECODE_STEP is not set): beam_decode(one_call=True) then needs no
+    step_fn at all."""
+    if packed is not None:
+        step_fn.plain = PlainStack(cell, packed, emb, C.weight, C.bias)
+    return step_fn
+
+
+def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
     capnet.beam.beam_search_device, whose bookkeeping stays on the device (fixed rows, no host read per step; poll_every
-    as there)."""
+    as there). one_call: the same search as ONE C call (ops.beam_decode: the parent rows read by the step itself, no
+    Python per step) where step_fn carries a PlainStack and the shape is one ops.beam_decode_supported; everywhere else
+    -- a decoder without a plain stack, an unsupported shape, CAPNET_NO_FUSED_DECODE_STEP=1 -- it is on_device=True."""
     dev = state[0].device
     with torch.no_grad():
+        if one_call:
+            plain, on_device = getattr(step_fn, "plain", None), True
+            if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, dec.vocab_size,
+                                                               len(plain.wcat)):
+                seqs = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, 1 if n is None else n,
+                                       k, dec.max_seq_length + 1, start_token, end_token, poll_every)
+                return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
         if on_device:
             seqs = beam_search_device(step_fn, state, 1 if n is None else n, dec.vocab_size, start_token, end_token, k,
                                       dec.max_seq_length, dev, poll_every)
@@ -142,6 +172,25 @@ def pack_cell(cell, kin):
     return wcat, beff
 
 
+def fold_factored(V, S, U, W):
+    """(wcat, beff) of one factored layer for capnet_stacked_decode_step from its gates' Linears (i, f, o, c~): wcat
+    [4H, kin + H] = [U_g S_g V_g, zero columns up to kin | W_g] (kin: the layer's input width rounded up to 16), beff
+    [4H] = U_g (S_g bV_g + bS_g) + bU_g + bW_g. Products on the GPU (capnet_sgemm)."""
+    H, n_in, dev = W[0].weight.shape[0], V[0].weight.shape[1], W[0].weight.device
+    kin = input_width(n_in)
+    wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
+    beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for g in range(4):
+            blk, bb = wcat[g * H:(g + 1) * H], beff[g * H:(g + 1) * H]
+            ops.sgemm(U[g].weight, ops.sgemm(S[g].weight, V[g].weight), out=blk[:, :n_in])       # [H, F][F, F][F, in]
+            blk[:, kin:].copy_(W[g].weight)
+            sb = ops.sgemm(V[g].bias.view(1, -1), S[g].weight, transB=True, bias=S[g].bias)       # S bV + bS
+            ops.sgemm(sb, U[g].weight, transB=True, bias=U[g].bias, out=bb.view(1, H))
+            bb += W[g].bias
+    return wcat, beff
+
+
 def pack_cells(cells, E):
     """[pack_cell] of every layer of a stack of LSTMCells whose first reads E columns."""
     return [pack_cell(c, input_width(E) if l == 0 else c.hidden_size) for l, c in enumerate(cells)]
@@ -155,22 +204,30 @@ def as_state(states):
     return torch.stack([t for hc in states for t in hc], 1)
 
 
+def fused_decode_step(num_layers, E, H):
+    """Whether a stack of this shape runs on capnet_stacked_decode_step now (CAPNET_NO_FUSED_DECODE_STEP is read here)."""
+    return os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and num_layers <= 8 and ops.stacked_decode_supported(E, H)
+
+
 def stack_stepper(num_layers, E, H, cell, pack, composed):
     """step(x, tokens, state [rows, 2L, H]) -> (top h [rows, H], state') of a stack of `num_layers` cells of kind `cell`,
     the first reading E columns: x is the embedding table when `tokens` is given, else layer 0's inputs. The fused step
     on pack() -> [(wcat, beff)] per layer, called here, once, unless CAPNET_NO_FUSED_DECODE_STEP=1 or the shape is one the
-    kernel does not take: then composed(x, state) -> (top h, state')."""
-    if (os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and num_layers <= 8 and ops.stacked_decode_supported(E, H)):
+    kernel does not take: then composed(x, state) -> (top h, state'). step.packed: pack()'s result on the fused step,
+    else None."""
+    if fused_decode_step(num_layers, E, H):
         packed = pack()
         wcat, beff = [w for w, _ in packed], [b for _, b in packed]
 
         def step(x, tokens, state):
             return ops.stacked_decode_step(state, wcat, beff, x, tokens, cell=cell)
+        step.packed = packed
     else:
         def step(x, tokens, state):
             if tokens is not None:
                 x = ops.embedding(tokens, x)
             return composed(x, state)
+        step.packed = None
     return step
 
 

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr, ptr_array
-from .decode import beam_decode, zero_state
+from .decode import beam_decode, fold_factored, fused_decode_step, plain_stack, zero_state
 
 random.seed(0)  # stylenet/model.py:7
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # stylenet/model.py:8
@@ -629,26 +629,32 @@ class DecoderFactoredLSTM(nn.Module):
         outputs = self.C(hiddens)
         return outputs
 
-    def _beam(self, rows, mode):
-        """(step_fn, the zero state of `rows` beams) of a beam search."""
+    def _beam(self, rows, mode, plain=False):
+        """(step_fn, the zero state of `rows` beams) of a beam search. plain (one_call=True): the chain folded for the fused
+        decode step (capnet.decode.fold_factored, the fold of StackedFactoredLSTM's layer 0) rides on step_fn where that
+        step takes the shape (capnet.decode.plain_stack); the steps of step_fn itself stay the composed chain."""
         self._S(mode)   # validates the mode before any launch
 
         def step_fn(prev_words, state):
             hidden, (h, c) = self.forward_step(self.B(prev_words), state, mode=mode)
             return self.C(hidden), (h, c)
+        if plain and fused_decode_step(1, self.embed_size, self.hidden_size):
+            plain_stack(step_fn, [fold_factored(*_layer_mods(self, "", mode))], ops.CELL_FACTORED, self.B.weight, self.C)
         return step_fn, zero_state(rows, self.hidden_size, self.B.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0):
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
+               one_call=False):
         """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
         an input of the decode steps (the first input is B(<start>) and the state starts at zero):
         `features` only fixes the device. Returns LongTensor [1, L].
-        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
-        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token, on_device, poll_every)
+        on_device / poll_every / one_call: capnet.decode.beam_decode's (the bookkeeping on the device; the whole search
+        in one C call, on the folded chain; same sequences)."""
+        return beam_decode(self, *self._beam(k, mode, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0):
+                     poll_every=0, one_call=False):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched): what the reference's test-set
         evaluator does image by image (stylenet/evaluator.py:76-84). Returns a list of token lists, each equal to
         sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every)
+        return beam_decode(self, *self._beam(n * k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)

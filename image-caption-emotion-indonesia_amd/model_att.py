@@ -194,19 +194,22 @@ class DecoderFactoredLSTMAtt(nn.Module):
                                 self.C, att1_of, feat_of, features.size(-1), upper)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0):
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
+               one_call=False):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
         of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L].
-        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
-        return beam_decode(self, *self._beam(features, None, k, mode), None, k, start_token, end_token, on_device, poll_every)
+        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
+        one_call: accepted for every decoder; an attention step is no plain stack, so it is on_device=True here."""
+        return beam_decode(self, *self._beam(features, None, k, mode), None, k, start_token, end_token, on_device, poll_every,
+                           one_call)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0):
+                     poll_every=0, one_call=False):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once: the reference's evaluator
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
         images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k, mode), n, k, start_token, end_token, on_device, poll_every)
+        return beam_decode(self, *self._beam(features, n, k, mode), n, k, start_token, end_token, on_device, poll_every, one_call)
 
     def forward(self,
                 captions,

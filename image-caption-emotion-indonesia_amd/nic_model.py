@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .decode import beam_decode, zero_state
+from .decode import beam_decode, fused_decode_step, input_width, pack_cell, plain_stack, zero_state
 from .model import Dropout, Embedding, EncoderCNN, Linear, _seq_cfg  # noqa: F401
 
 
@@ -86,20 +86,24 @@ class DecoderRNN(nn.Module):
                                   *weights, *upper)
         return self.linear(hiddens)
 
-    def _beam(self, rows):
-        """(step_fn, the zero state of `rows` beams) of a beam search."""
+    def _beam(self, rows, plain=False):
+        """(step_fn, the zero state of `rows` beams) of a beam search. plain (one_call=True): the cell packed for the fused
+        decode step rides on step_fn where that step takes the shape (capnet.decode.plain_stack)."""
         def step_fn(prev_words, state):
             hidden, (h, c) = self.forward_step(self.embed(prev_words), state)
             return self.linear(hidden), (h, c)
+        if plain and fused_decode_step(1, self.embed_size, self.hidden_size):
+            plain_stack(step_fn, [pack_cell(self.lstm, input_width(self.embed_size))], ops.CELL_LSTM, self.embed.weight, self.linear)
         return step_fn, zero_state(rows, self.hidden_size, self.embed.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """Beam search, nic/model.py:117-207 (the image features are not an input of the decode
         steps there either). Returns LongTensor [1, L].
-        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
-        return beam_decode(self, *self._beam(k), None, k, start_token, end_token, on_device, poll_every)
+        on_device / poll_every / one_call: capnet.decode.beam_decode's (the bookkeeping on the device; the whole search
+        in one C call; same sequences)."""
+        return beam_decode(self, *self._beam(k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
 
-    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched)."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k), n, k, start_token, end_token, on_device, poll_every)
+        return beam_decode(self, *self._beam(n * k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)

@@ -105,13 +105,14 @@ class DecoderRNNAtt(nn.Module):
                                 features.size(-1), upper)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L].
-        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
-        return beam_decode(self, *self._beam(features, None, k), None, k, start_token, end_token, on_device, poll_every)
+        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
+        one_call: accepted for every decoder; an attention step is no plain stack, so it is on_device=True here."""
+        return beam_decode(self, *self._beam(features, None, k), None, k, start_token, end_token, on_device, poll_every, one_call)
 
-    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0):
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).
         Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k), n, k, start_token, end_token, on_device, poll_every)
+        return beam_decode(self, *self._beam(features, n, k), n, k, start_token, end_token, on_device, poll_every, one_call)

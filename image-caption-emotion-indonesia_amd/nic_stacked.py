@@ -34,8 +34,9 @@ pack_cell, att_beam_step); sample / sample_batch are the base classes' over this
 """
 import torch
 
+from . import ops
 from ._lib import CapnetError
-from .decode import as_state, cell_stepper
+from .decode import as_state, cell_stepper, plain_stack
 from .decode import pack_cell as _pack_cell  # noqa: F401  (the packing's name while it lived here; the tests pack by it)
 from .model import Linear
 from .nic_model import DecoderRNN, LSTMCell
@@ -89,8 +90,9 @@ class StackedDecoderRNN(DecoderRNN):
             return step(embedded.detach().contiguous(), None, as_state(states).detach().contiguous())
 
     @torch.no_grad()
-    def _beam(self, rows):
-        """(step_fn, the zero state (one tensor [rows, 2L, H],)) of a beam search: the weights are packed here, once."""
+    def _beam(self, rows, plain=False):
+        """(step_fn, the zero state (one tensor [rows, 2L, H],)) of a beam search: the weights are packed here, once (and
+        serve one_call=True as they are: `plain` asks for nothing more)."""
         emb = self.embed.weight.detach()
         zeros = torch.zeros((rows, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=emb.device)
         step = cell_stepper(self._cells(), self.embed_size, self.hidden_size)
@@ -98,7 +100,7 @@ class StackedDecoderRNN(DecoderRNN):
         def step_fn(prev_words, state):
             top, st = step(emb, prev_words, state[0])
             return self.linear(top), (st,)
-        return step_fn, (zeros,)
+        return plain_stack(step_fn, step.packed, ops.CELL_LSTM, emb, self.linear), (zeros,)
 
     # sample / sample_batch: DecoderRNN's, over this _beam (the image is NOT an input, every layer starts at zero)
 

@@ -137,6 +137,16 @@ def sgemm(A, B, transA=False, transB=False, bias=None, out=None, accumulate=Fals
 _splitk_ws = {}
 
 
+def splitk_slab(device):
+    """The cached 32 MB slab workspace of sgemm_splitk on `device`."""
+    key = torch.device(device).index or 0
+    ws = _splitk_ws.get(key)
+    if ws is None:
+        ws = torch.empty(8 * 1024 * 1024, dtype=torch.float32, device=device)
+        _splitk_ws[key] = ws
+    return ws
+
+
 def sgemm_splitk(A, B, transB=False, bias=None):
     """A @ op(B) + bias through capnet_sgemm_splitk: the library cuts K into slabs when the output
     has few tiles (per-step products; dH = dlogits @ C with K = vocab). One cached 32 MB slab
@@ -147,11 +157,7 @@ def sgemm_splitk(A, B, transB=False, bias=None):
     N = B.shape[0] if transB else B.shape[1]
     if (B.shape[1] if transB else B.shape[0]) != K:
         raise CapnetError("sgemm_splitk: inner dimensions differ")
-    key = A.device.index or 0
-    ws = _splitk_ws.get(key)
-    if ws is None:
-        ws = torch.empty(8 * 1024 * 1024, dtype=torch.float32, device=A.device)
-        _splitk_ws[key] = ws
+    ws = splitk_slab(A.device)
     out = torch.empty((M, N), dtype=torch.float32, device=A.device)
     check(_lib.lib().capnet_sgemm_splitk(0, int(transB), M, N, K, ptr(A), A.shape[1], ptr(B), B.shape[1],
                                          ptr(out), N, ptr(bias), 0, ptr(ws), ws.numel(),
@@ -366,11 +372,12 @@ def stacked_decode_supported(E, H):
     return E >= 1 and H in DECODE_HIDDEN and (E + 15) // 16 * 16 + H <= 2048
 
 
-def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED):
+def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, parent_rows=None):
     """One inference step of every layer of a stacked LSTM (capnet_stacked_decode_step, or _cell for the LSTM cell: one
     launch per layer). state [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = c); wcat[l] [4H, kin_l + H] = [folded chain |
     W] (factored) or [weight_ih | weight_hh] (LSTM cell), gate blocks i, f, o, c~; beff[l] [4H]; x: the embedding table
-    [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E].
+    [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E]. parent_rows (int64 [rows]): the step on
+    state.index_select(0, parent_rows) without that copy (capnet_stacked_decode_step_gather).
     Returns (top-layer h [rows, H], the new state [rows, 2L, H])."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("stacked_decode_step: unknown cell %r" % (cell,))
@@ -393,6 +400,16 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED):
             raise CapnetError("stacked_decode_step: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
     out = torch.empty_like(state)
     top = torch.empty((rows, H), dtype=torch.float32, device=state.device)
+    if parent_rows is not None:
+        _need_cuda(parent_rows)
+        parent_rows = _c(parent_rows)
+        if parent_rows.dtype != torch.int64 or parent_rows.numel() != rows:
+            raise CapnetError("stacked_decode_step: parent_rows must be int64 [rows]")
+        check(_lib.lib().capnet_stacked_decode_step_gather(
+            cell, nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens), ptr(x), ptr_array(wcat),
+            ptr_array(beff), ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(err_flag(state.device)), current_stream()),
+            "capnet_stacked_decode_step_gather")
+        return top, out
     args = (nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens), ptr(x), ptr_array(wcat), ptr_array(beff),
             ptr(state), ptr(out), ptr(top), ptr(err_flag(state.device)), current_stream())
     if cell == CELL_FACTORED:
@@ -467,6 +484,72 @@ def lstm_greedy_decode(steps, wcat, beff, emb, Cw, Cb, features=None, start_toke
                                       ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(ids),
                                       ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_lstm_greedy_decode")
     return ids, out
+
+
+_beam_decode_ws = {}
+
+
+def beam_decode_supported(E, H, k, V, num_layers):
+    """The shapes capnet_beam_decode takes: those of its parts (the decode step, capnet_beam_advance)."""
+    return stacked_decode_supported(E, H) and 1 <= k <= 16 and k <= V and 1 <= num_layers <= 8
+
+
+def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, poll_every=0, state=None,
+                return_steps=False):
+    """The beam search of a plain stack in ONE C call (capnet_beam_decode): n images x k beams, at most max_steps steps of
+    (gathered decode step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then capnet_beam_finish.
+    cell / wcat / beff: as stacked_decode_step; emb [V, E]; Cw [V, H], Cb [V] or None; state: [n k, 2L, H] or None for
+    zeros; poll_every as capnet.beam.beam_search_device. The workspace is cached per (device, shape). Sequences, lengths
+    and the device's error word come to the host in one copy; a set error word raises (check_device_errors).
+    Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("beam_decode: unknown cell %r" % (cell,))
+    _need_cuda(emb, Cw, Cb, state, *wcat, *beff)
+    emb, Cw = _c(emb.detach()), _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    V, E = emb.shape
+    H, nl = Cw.shape[1], len(wcat)
+    n, k, T = int(n), int(k), int(max_steps)
+    if n < 1 or T < 1 or len(beff) != nl or tuple(Cw.shape) != (V, H) or not beam_decode_supported(E, H, k, V, nl):
+        raise CapnetError("beam_decode: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
+                          % (E, H, V, k, nl, n, T))
+    if Cb is not None and Cb.numel() != V:
+        raise CapnetError("beam_decode: Cb must be [V]")
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = (E + 15) // 16 * 16 if l == 0 else H
+        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
+            raise CapnetError("beam_decode: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    dev = emb.device
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (n * k, 2 * nl, H):
+            raise CapnetError("beam_decode: state must be [n k, 2L, H]")
+    L = _lib.lib()
+    key = (dev.index or 0, nl, n, k, H, V, T)
+    ws = _beam_decode_ws.get(key)
+    if ws is None:
+        ws = torch.empty((L.capnet_beam_decode_ws_bytes(nl, n, k, H, V, T) + 7) // 8, dtype=torch.int64, device=dev)
+        _beam_decode_ws[key] = ws
+    slab = splitk_slab(dev)
+    SL = T + 2
+    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
+    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
+    tail = packed[n * SL:].view(torch.int32)
+    flag = err_flag(dev)
+    steps = C.c_int(0)
+    check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(emb), ptr_array(wcat),
+                               ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
+                               int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag),
+                               current_stream()), "capnet_beam_decode")
+    tail[n:n + 1].copy_(flag)
+    host = packed.cpu()
+    htail = host[n * SL:].view(torch.int32)
+    if int(htail[n]):
+        check_device_errors()
+    lens = htail[:n].tolist()
+    rows = host[:n * SL].view(n, SL).tolist()
+    out = [rows[i][:lens[i]] for i in range(n)]
+    return (out, steps.value) if return_steps else out
 
 
 def packed_targets(captions, lengths):

@@ -35,7 +35,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .decode import as_state, beam_decode, factored_step, input_width, stack_stepper
+from .decode import as_state, beam_decode, factored_step, fold_factored, plain_stack, stack_stepper
 from .model import Embedding as _Embedding, Linear as _Linear, _layer_mods, _seq_cfg
 
 MODES = ("factual", "happy", "sad", "angry")
@@ -97,24 +97,8 @@ class StackedFactoredLSTM(nn.Module):
     def _fold(self, mode):
         """[(wcat, beff)] per layer for capnet_stacked_decode_step: wcat [4H, kin + H] = [U_g S_g V_g, zero columns up
         to kin | W_g] in gate blocks i, f, o, c~ (kin: the layer's input width rounded up to 16), beff [4H] =
-        U_g (S_g bV_g + bS_g) + bU_g + bW_g. Products on the GPU (capnet_sgemm)."""
-        H, dev = self.hidden_size, self.B.weight.device
-        out = []
-        for l in range(self.num_layers):
-            V, S, U, W = self._mods(l, mode)
-            n_in = V[0].in_features
-            kin = input_width(n_in)
-            wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
-            beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
-            for g in range(4):
-                blk, bb = wcat[g * H:(g + 1) * H], beff[g * H:(g + 1) * H]
-                ops.sgemm(U[g].weight, ops.sgemm(S[g].weight, V[g].weight), out=blk[:, :n_in])       # [H, F][F, F][F, in]
-                blk[:, kin:].copy_(W[g].weight)
-                sb = ops.sgemm(V[g].bias.view(1, -1), S[g].weight, transB=True, bias=S[g].bias)       # S bV + bS
-                ops.sgemm(sb, U[g].weight, transB=True, bias=U[g].bias, out=bb.view(1, H))
-                bb += W[g].bias
-            out.append((wcat, beff))
-        return out
+        U_g (S_g bV_g + bS_g) + bU_g + bW_g (capnet.decode.fold_factored, layer by layer)."""
+        return [fold_factored(*self._mods(l, mode)) for l in range(self.num_layers)]
 
     def _composed_step(self, x, state, mode):
         """One inference step of the stack, unfolded: per layer the V, S, U and W products and the pointwise cell."""
@@ -142,8 +126,9 @@ class StackedFactoredLSTM(nn.Module):
             return self._decode_stepper(mode)(embedded.detach(), None, as_state(states).detach())
 
     @torch.no_grad()
-    def _beam(self, rows, mode):
-        """(step_fn, the zero state (one tensor [rows, 2L, H],)) of a beam search: the weights are folded here, once."""
+    def _beam(self, rows, mode, plain=False):
+        """(step_fn, the zero state (one tensor [rows, 2L, H],)) of a beam search: the weights are folded here, once (and
+        serve one_call=True as they are: `plain` asks for nothing more)."""
         _check_mode(mode)
         step, emb = self._decode_stepper(mode), self.B.weight.detach()
 
@@ -151,21 +136,23 @@ class StackedFactoredLSTM(nn.Module):
             top, st = step(emb, prev_words, state[0])
             return self.C(top), (st,)
         zeros = torch.zeros((rows, 2 * self.num_layers, self.hidden_size), dtype=torch.float32, device=emb.device)
-        return step_fn, (zeros,)
+        return plain_stack(step_fn, step.packed, ops.CELL_FACTORED, emb, self.C), (zeros,)
 
-    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0):
+    def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
+               one_call=False):
         """Beam search, stylenet/model.py:198-294, over the stack: as DecoderFactoredLSTM.sample, the image is NOT an
         input (`features` only fixes the device), every layer's state starts at zero, the first input is B(<start>) and
         factual_limit is ignored. Returns LongTensor [1, L].
-        on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences)."""
-        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token, on_device, poll_every)
+        on_device / poll_every / one_call: capnet.decode.beam_decode's (the bookkeeping on the device; the whole search
+        in one C call; same sequences)."""
+        return beam_decode(self, *self._beam(k, mode), None, k, start_token, end_token, on_device, poll_every, one_call)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0):
+                     poll_every=0, one_call=False):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched). Returns a list of token lists,
         each equal to sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every)
+        return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every, one_call)
 
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, captions, lengths, features=None, teacher_forcing_ratio=0.8, mode="factual", tf_mask=None):

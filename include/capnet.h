@@ -542,6 +542,16 @@ int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int 
                                     const float* state_in, float* state_out, float* h_top, int* err_flag,
                                     capnet_stream_t stream);
 
+/* capnet_stacked_decode_step_cell reading the previous state through a beam search's parent rows: with parent_rows (int64
+ * [rows], device), row r's h_prev and c_prev of every layer are those of row parent_rows[r] of state_in -- the result of
+ * the step on state_in.index_select(0, parent_rows), bit for bit, without that copy. x, tokens, state_out and h_top stay
+ * indexed by the row itself; parents may repeat (state_in != state_out). A parent outside [0, rows) sets *err_flag = 1
+ * and the row reads itself; parent_rows needs err_flag. parent_rows NULL: exactly capnet_stacked_decode_step_cell. */
+int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                      const float* x, const float* const* wcat, const float* const* beff,
+                                      const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
+                                      int* err_flag, capnet_stream_t stream);
+
 /* tokens[r] = the FIRST argmax over v of h[r] . w[v] + b[v], r < rows: the vocabulary projection (nn.Linear: w [V][H],
  * b [V] or NULL) and the row argmax in one launch, fp32 throughout, the logits never stored. A -inf or NaN logit is never
  * picked and a row with nothing to pick yields 0, as capnet_argmax_rows. rows >= 1, V >= 1, H in {64, 128, 256, 512,
@@ -570,6 +580,28 @@ int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int st
                               const long long* start_tokens, const float* emb, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0,
                               void* workspace, long long* ids, float* state_out, int* err_flag, capnet_stream_t stream);
+
+/* The whole beam search of a plain LSTM stack (capnet.beam.beam_search_device's loop for StackedFactoredLSTM /
+ * StackedDecoderRNN / DecoderFactoredLSTM / DecoderRNN) in one call: n images x k fixed slots, rows i k .. i k + k - 1 are
+ * image i's. Per step s = 1 .. max_steps, on `stream`: capnet_stacked_decode_step_gather on the previous step's words and
+ * parent rows (no parents at s = 1), logits [n k][V] = h_top . Cw^T + Cb by capnet_sgemm_splitk's entry on `slab` (the
+ * kernel choice and the logits of that call with that slab), capnet_beam_advance. Then capnet_beam_finish into seqs
+ * int64 [n][max_steps + 2] and lengths int32 [n] (caller-owned device memory, 8- / 4-byte aligned).
+ * cell, wcat, beff (HOST arrays of nlayers device pointers), emb [V][E]: as capnet_stacked_decode_step_cell; Cw [V][H],
+ * Cb [V] or NULL. state0: the initial [n k][2 nlayers][H] state, NULL for zeros. max_steps = max_seq_length + 1 for the
+ * decoders. workspace: capnet_beam_decode_ws_bytes(...) bytes of device memory, 16-B aligned, contents irrelevant (the two
+ * state buffers, h_top, the logits, two word buffers, the parent rows and the capnet_beam_state_bytes block, each part
+ * rounded up to 16 bytes; 0 for shapes outside 1 <= k <= 16, 1 <= nlayers <= 8). slab: at least n k V floats, 16-B aligned.
+ * The call allocates nothing. poll_every = 0: no host synchronisation and nothing read. poll_every = m > 0: after every
+ * m-th step short of the last, one blocking 4-byte read of the count of live beams; the loop stops at zero (same result).
+ * *steps_run (host, may be NULL): the steps issued. A token id outside [0, V) (start_token) sets *err_flag = 1.
+ * Every bad argument is refused before any launch. */
+size_t capnet_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps);
+int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                       long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                       const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                       size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                       capnet_stream_t stream);
 
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
