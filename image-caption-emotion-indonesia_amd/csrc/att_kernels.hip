@@ -33,6 +33,8 @@ __device__ __forceinline__ float wave_sum(float v) {
   return ((r0 + r1) + r2) + r3;
 }
 
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+
 // ---- forward 1: raw scores ----------------------------------------------------------------
 // grid = (rows of the step, pixel chunks): 4 chunks at b = 64 (256 workgroups), more for fewer rows so that a
 // 12-row step still makes ~150 workgroups (score_chunks). A pixel's score is one wave's sum whatever the chunking.
@@ -192,6 +194,206 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
   hipLaunchKernelGGL(att_context_fwd_kernel, dim3(rows, C / kCtxCh), dim3(kAttThreads),
                      (((P + 3) & ~3) + 4 * 64 * 4) * sizeof(float), stream, feat, escore, P, C, gate_io, ldz, alpha_out, alphas_bt, steps, t, awe_out,
                      xa_out, ldx);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// ---- beam search: the k beams of an image on ONE read of its maps ----------------------------------------------------
+// The fixed-slot search (capnet_att_beam_decode) keeps image i's beams at rows i k .. i k + k - 1, so att1 [n][P][A] and
+// feat [n][P][C] stay per image and a workgroup that loads a piece of a map uses it for all k <= 16 rows of the image
+// (KT = k rounded up to 4, 8 or 16 accumulator sets; rows past k repeat row k - 1 and are never stored). att2 and the gate
+// pre-activation of row r are read from z at row parent[r] -- z was computed from the previous step's ungathered h, so
+// the re-ordering of the beams costs no copy -- and z is only read: parents repeat, a sigmoid written back would be
+// applied twice. A parent outside [0, n k) raises the flag and the row reads itself; a token id outside [0, V) raises it
+// and reads row 0 (the gathered decode step's conventions). Two launches: scores, then softmax + context + gate, whose
+// first channel block of an image also copies emb[token[r]] into xa[r][0 .. E).
+struct AttBeamArgs {
+  const float* att1;         // [n][P][A]
+  const float* feat;         // [n][P][C]
+  const float* z;            // [n k][ldz] = [att2 (A) | gate pre-activation (C)]
+  long ldz;
+  const long long* parent;   // int64 [n k] or null
+  const float* wf;           // full_att weight [A], bias [1]
+  const float* bf;
+  const long long* tok;      // int64 [n k]
+  const float* emb;          // [V][E]
+  int V, E, n, k, P, A, C;
+  float* escore;             // [n k][P]
+  float* xa;                 // [n k][ldx] = [embedding (E) | gated context (C)]
+  long ldx;
+  int* err;
+};
+
+__device__ __forceinline__ long beam_src_row(const AttBeamArgs& a, int row) {
+  if (!a.parent) return row;
+  const long long p = a.parent[row];
+  const bool ok = p >= 0 && p < (long long)a.n * a.k;
+  if (!ok) *a.err = 1;
+  return ok ? (long)p : (long)row;
+}
+
+// grid = (images, pixel chunks); a wave takes PU pixels at a time (KT x PU sums: PU = 4, 2 at KT = 16). A (row, pixel)
+// score is one wave's sum in att_scores_fwd_kernel's order.
+template <int KT, int PU>
+__global__ __launch_bounds__(kAttThreads) void att_beam_scores_kernel(AttBeamArgs a) {
+  const int img = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int P = a.P, A = a.A, k = a.k;
+  const int pc = (P + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int p0 = blockIdx.y * pc, p1 = min(P, p0 + pc);
+  if (p0 >= p1) return;
+  const float* a1 = a.att1 + (long)img * P * A;
+  const float* y[KT];
+#pragma unroll
+  for (int r = 0; r < KT; ++r) y[r] = a.z + beam_src_row(a, img * k + min(r, k - 1)) * a.ldz;
+  const float b0 = a.bf[0];
+  for (int p = p0 + PU * wave; p < p1; p += PU * (kAttThreads / 64)) {
+    float s[KT][PU];
+#pragma unroll
+    for (int r = 0; r < KT; ++r)
+#pragma unroll
+      for (int u = 0; u < PU; ++u) s[r][u] = 0.f;
+    for (int c = lane * 4; c < A; c += 256) {
+      const float4 w = *reinterpret_cast<const float4*>(a.wf + c);
+      float4 x[PU];
+#pragma unroll
+      for (int u = 0; u < PU; ++u) x[u] = *reinterpret_cast<const float4*>(a1 + (long)min(p + u, p1 - 1) * A + c);
+#pragma unroll
+      for (int r = 0; r < KT; ++r) {
+        const float4 yv = *reinterpret_cast<const float4*>(y[r] + c);
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+          s[r][u] = fmaf(fmaxf(x[u].x + yv.x, 0.f), w.x, s[r][u]);
+          s[r][u] = fmaf(fmaxf(x[u].y + yv.y, 0.f), w.y, s[r][u]);
+          s[r][u] = fmaf(fmaxf(x[u].z + yv.z, 0.f), w.z, s[r][u]);
+          s[r][u] = fmaf(fmaxf(x[u].w + yv.w, 0.f), w.w, s[r][u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < KT; ++r)
+#pragma unroll
+      for (int u = 0; u < PU; ++u) {
+        const float t = wave_sum(s[r][u]);
+        if (lane == 0 && r < k && p + u < p1) a.escore[((long)img * k + r) * P + p + u] = t + b0;
+      }
+  }
+}
+
+// grid = (images, C/256); lane = 4 channels, the four waves split the pixels 8 at a time. The k softmaxes over P: each
+// wave computes the max and the sum of its rows from the raw scores, then alpha goes through LDS in chunks of 256 pixels
+// (zero past P and past row k), so P up to 4096 needs no more LDS than P = 256. The waves' partial contexts meet in LDS
+// four rows at a time and are added in wave order by the wave that gates and stores the row.
+constexpr int kBeamPix = 256;
+
+template <int KT>
+__global__ __launch_bounds__(kAttThreads) void att_beam_context_kernel(AttBeamArgs a) {
+  __shared__ __attribute__((aligned(16))) float al[KT][kBeamPix];
+  __shared__ float4 part[4][kAttThreads / 64][64];
+  __shared__ float mx[KT], inv[KT];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int P = a.P, C = a.C, k = a.k, E = a.E;
+  if (blockIdx.y == 0) {
+    const int e4 = E / 4;
+    for (int i = tid; i < k * e4; i += kAttThreads) {
+      const int r = i / e4, q = i - r * e4;
+      const long row = (long)img * k + r;
+      const long long t = a.tok[row];
+      const bool ok = t >= 0 && t < a.V;
+      if (!ok) *a.err = 1;
+      *reinterpret_cast<float4*>(a.xa + row * a.ldx + 4 * q) =
+          *reinterpret_cast<const float4*>(a.emb + (ok ? (long)t : 0L) * E + 4 * q);
+    }
+  }
+  for (int r = wave; r < k; r += kAttThreads / 64) {
+    const float* e = a.escore + ((long)img * k + r) * P;
+    float m = -INFINITY;
+    for (int p = lane; p < P; p += 64) m = fmaxf(m, e[p]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float zs = 0.f;
+    for (int p = lane; p < P; p += 64) zs += expf(e[p] - m);
+    zs = wave_sum(zs);
+    if (lane == 0) {
+      mx[r] = m;
+      inv[r] = 1.f / zs;
+    }
+  }
+  const int c = blockIdx.y * kCtxCh + lane * 4;
+  const float* f = a.feat + (long)img * P * C + c;
+  float4 s[KT];
+#pragma unroll
+  for (int r = 0; r < KT; ++r) s[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int pb = 0; pb < P; pb += kBeamPix) {
+    __syncthreads();   // mx / inv are written; the previous chunk's alpha is consumed
+    const int np = min(kBeamPix, P - pb);
+    for (int i = tid; i < KT * kBeamPix; i += kAttThreads) {
+      const int r = i / kBeamPix, q = i - r * kBeamPix;
+      al[r][q] = r < k && q < np ? expf(a.escore[((long)img * k + r) * P + pb + q] - mx[r]) * inv[r] : 0.f;
+    }
+    __syncthreads();
+    for (int q0 = 8 * wave; q0 < np; q0 += 8 * (kAttThreads / 64)) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(f + (long)(pb + min(q0 + u, np - 1)) * C);
+#pragma unroll
+      for (int r = 0; r < KT; ++r) {
+        const float4 w0 = *reinterpret_cast<const float4*>(&al[r][q0]), w1 = *reinterpret_cast<const float4*>(&al[r][q0 + 4]);
+        const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          s[r].x = fmaf(w[u], v[u].x, s[r].x); s[r].y = fmaf(w[u], v[u].y, s[r].y);
+          s[r].z = fmaf(w[u], v[u].z, s[r].z); s[r].w = fmaf(w[u], v[u].w, s[r].w);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int rb = 0; rb < KT; rb += 4) {
+    __syncthreads();   // the previous four rows are read
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[j][wave][lane] = s[rb + j];
+    __syncthreads();
+    const int r = rb + wave;
+    if (r < k) {
+      const float4 t0 = part[wave][0][lane], t1 = part[wave][1][lane], t2 = part[wave][2][lane], t3 = part[wave][3][lane];
+      const int row = img * k + r;
+      float4 g = *reinterpret_cast<const float4*>(a.z + beam_src_row(a, row) * a.ldz + a.A + c);
+      float4 o;
+      o.x = sigmoid_f(g.x) * (((t0.x + t1.x) + t2.x) + t3.x); o.y = sigmoid_f(g.y) * (((t0.y + t1.y) + t2.y) + t3.y);
+      o.z = sigmoid_f(g.z) * (((t0.z + t1.z) + t2.z) + t3.z); o.w = sigmoid_f(g.w) * (((t0.w + t1.w) + t2.w) + t3.w);
+      *reinterpret_cast<float4*>(a.xa + (long)row * a.ldx + E + c) = o;
+    }
+  }
+}
+
+bool att_beam_step_supported(int E, int C, int A, int P, int k) {
+  return E >= 4 && E % 4 == 0 && C >= 512 && C % 512 == 0 && A >= 4 && A % 4 == 0 && P >= 1 && P <= 4096 && k >= 1 && k <= 16;
+}
+
+template <int KT, int PU>
+static void launch_att_beam(const AttBeamArgs& a, hipStream_t stream) {
+  // pixel chunks of the scores: ~512 workgroups, at least one sweep of the four waves each
+  int chunks = (512 + a.n - 1) / a.n;
+  const int most = (a.P + 4 * PU - 1) / (4 * PU);
+  if (chunks > most) chunks = most;
+  hipLaunchKernelGGL((att_beam_scores_kernel<KT, PU>), dim3(a.n, chunks), dim3(kAttThreads), 0, stream, a);
+  hipLaunchKernelGGL((att_beam_context_kernel<KT>), dim3(a.n, a.C / kCtxCh), dim3(kAttThreads), 0, stream, a);
+}
+
+int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
+                      const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream) {
+  CAPNET_REQUIRE(att1 && feat && z && wf && bf && tokens && emb && escore && xa && err_flag, "att_beam_step_fwd: null argument");
+  CAPNET_REQUIRE(n >= 1 && V >= 1 && att_beam_step_supported(E, C, A, P, k),
+                 "att_beam_step_fwd: n=%d k=%d E=%d A=%d C=%d P=%d V=%d", n, k, E, A, C, P, V);
+  CAPNET_REQUIRE(aligned16(att1) && aligned16(feat) && aligned16(z) && aligned16(wf) && aligned16(emb) && aligned16(xa),
+                 "att_beam_step_fwd: 16-byte alignment of the rows");
+  AttBeamArgs a;
+  a.att1 = att1; a.feat = feat; a.z = z; a.ldz = (long)A + C; a.parent = parent_rows; a.wf = wf; a.bf = bf;
+  a.tok = tokens; a.emb = emb; a.V = V; a.E = E; a.n = n; a.k = k; a.P = P; a.A = A; a.C = C;
+  a.escore = escore; a.xa = xa; a.ldx = (long)E + C; a.err = err_flag;
+  if (k <= 4) launch_att_beam<4, 4>(a, stream);
+  else if (k <= 8) launch_att_beam<8, 4>(a, stream);
+  else launch_att_beam<16, 2>(a, stream);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

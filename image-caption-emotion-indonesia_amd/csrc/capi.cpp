@@ -447,6 +447,74 @@ int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V,
                      slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream));
 }
 
+int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {
+  return att_decode_supported(E, C, H, A, P, k, nlayers) ? 1 : 0;
+}
+size_t capnet_att_decode_step_ws_bytes(int n, int k, int P, int A, int C, int E) { return att_decode_step_ws_bytes(n, k, P, A, C, E); }
+
+// what capnet_att_decode_step and capnet_att_beam_decode check alike
+static int att_decode_check(const char* who, int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V,
+                            const float* att1, const float* feat, const float* emb, const float* wz, const float* bz,
+                            const float* w_full, const float* b_full, const float* const* wcat, const float* const* beff,
+                            const void* workspace, const float* slab, size_t slab_floats, const int* err_flag) {
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "%s: unknown cell %d", who, cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "%s: layers %d (1..8)", who, nlayers);
+  CAPNET_REQUIRE(n >= 1 && V >= 1, "%s: n %d, V %d", who, n, V);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "%s: k=%d (1 <= k <= 16, k <= V = %d)", who, k, V);
+  CAPNET_REQUIRE(att_decode_supported(E, C, H, A, P, k, nlayers), "%s: unsupported E=%d C=%d H=%d A=%d P=%d", who, E, C, H, A, P);
+  CAPNET_REQUIRE((long)n * k * V < (1L << 31) && (long)n * P * C < (1L << 40), "%s: n k too large", who);
+  CAPNET_REQUIRE(att1 && feat && emb && wz && bz && w_full && b_full && wcat && beff && workspace && slab && err_flag,
+                 "%s: null argument", who);
+  CAPNET_REQUIRE(aligned16(att1) && aligned16(feat) && aligned16(emb) && aligned16(wz) && aligned16(w_full) &&
+                     aligned16(workspace) && aligned16(slab), "%s: att1, feat, emb, wz, w_full, workspace and slab must be 16-B aligned", who);
+  const size_t need = (size_t)n * k * (size_t)(V > A + C ? V : A + C);
+  CAPNET_REQUIRE(slab_floats >= need, "%s: the slab holds %zu floats, one [n k][max(V, A + C)] block is %zu", who, slab_floats, need);
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "%s: weights of layer %d are null", who, l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "%s: weights of layer %d not 16-B aligned", who, l);
+  }
+  return kOk;
+}
+
+int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, const float* att1,
+                           const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
+                           const float* w_full, const float* b_full, const float* const* wcat, const float* const* beff,
+                           const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
+                           void* workspace, float* slab, size_t slab_floats, int* err_flag, capnet_stream_t stream) {
+  if (int rc = att_decode_check("att_decode_step", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
+                                wcat, beff, workspace, slab, slab_floats, err_flag))
+    return rc;
+  CAPNET_REQUIRE(tokens && state_in && state_out && h_top, "att_decode_step: null argument");
+  CAPNET_REQUIRE(state_in != state_out, "att_decode_step: state_in and state_out must differ");
+  CAPNET_REQUIRE(aligned16(state_in) && aligned16(state_out), "att_decode_step: state alignment (16-B aligned)");
+  return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full, wcat, beff,
+                         state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, S(stream));
+}
+
+size_t capnet_att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps) {
+  return att_beam_decode_ws_bytes(nlayers, n, k, P, A, C, E, H, V, max_steps);
+}
+
+int capnet_att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                           long long start_token, long long end_token, const float* att1, const float* feat, const float* emb,
+                           const float* wz, const float* bz, const float* w_full, const float* b_full,
+                           const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                           const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                           long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream) {
+  if (int rc = att_decode_check("att_beam_decode", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
+                                wcat, beff, workspace, slab, slab_floats, err_flag))
+    return rc;
+  CAPNET_REQUIRE(max_steps >= 1 && poll_every >= 0, "att_beam_decode: max_steps %d, poll_every %d", max_steps, poll_every);
+  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28), "att_beam_decode: n k too large");
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "att_beam_decode: start_token %lld", start_token);
+  CAPNET_REQUIRE(Cw && state0 && seqs && lengths, "att_beam_decode: null argument (state0 is required)");
+  CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0), "att_beam_decode: Cw and state0 must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "att_beam_decode: seqs / lengths alignment");
+  return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
+                         b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
+                         err_flag, S(stream));
+}
+
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream) {
   CAPNET_REQUIRE(gates && c && dh && dc_io && dpre && b >= 0 && H > 0, "lstm_pointwise_bwd: bad argument");

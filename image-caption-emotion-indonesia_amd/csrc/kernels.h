@@ -264,6 +264,18 @@ bool stacked_decode_supported(int E, int H);
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
                         float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr);
+// the same kernels' family for layer 0 of an attention decoder, kin + H up to 4096 (x rows of E % 4 == 0 columns, 16-B aligned)
+bool stacked_decode_wide_supported(int E, int H);
+// One beam step of an attention decoder without the projection: z = h_prev . [decoder_att; f_beta]^T + bz (sgemm_splitk on
+// `slab`), att_beam_step_fwd, layer 0 on xa = [embedding | gated context] (wide or narrow by shape), the upper layers.
+// ws: att_decode_step_ws_bytes (z | xa | escore)
+bool att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers);
+size_t att_decode_step_ws_bytes(int n, int k, int P, int A, int C, int E);
+int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, const float* att1,
+                    const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
+                    const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
+                    const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
+                    size_t slab_floats, int* err_flag, hipStream_t stream);
 
 // vocab_argmax.hip: tok[r] = first argmax_v (h[r] . W[v] + b[v]) in one launch, no logits in memory (ws: vocab_argmax_ws_bytes,
 // its first 16 bytes zero before the first use); and capnet.seq2seq's greedy `sample` as one chain of launches
@@ -283,6 +295,14 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
                 long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s);
+// beam_decode's loop around att_decode_step (att1 = encoder_att(feat), once per call, is the caller's; state0 is required)
+size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
+int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                    long long start_token, long long end_token, const float* att1, const float* feat, const float* emb,
+                    const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
+                    const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
+                    size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                    hipStream_t s);
 
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
@@ -299,6 +319,12 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
                  const float* wf, const float* bf, int rows, int P, int A, int C,
                  float* alpha_out, float* alphas_bt, int steps, int t, float* awe_out,
                  float* xa_out, long ldx, float* escore, hipStream_t stream);
+// the k beams of an image on one read of its maps: att1 [n][P][A], feat [n][P][C], row r of image r / k; att2 and the gate
+// from z [n k][A + C] at row parent_rows[r] (null: r), read only; xa [n k][E + C] = [emb[tokens[r]] | gated context]
+bool att_beam_step_supported(int E, int C, int A, int P, int k);
+int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
+                      const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream);
 int att_step_bwd(const float* att1, const float* feat, const float* att2, long ldz2,
                  const float* gate, long ldzg, const float* awe, const float* alpha,
                  const float* wf, float* dxa, long ldx, const float* dalphas_bt, int steps,

@@ -20,6 +20,9 @@
 // The nn.LSTMCell instance (TANH_OUT, capnet.nic_stacked) takes wcat = [weight_ih, zero columns up to kin | weight_hh]
 // and beff = bias_ih + bias_hh with the host's gate blocks reordered from torch's i, f, g, o to i, f, o, c~ = g: the
 // LSTM cell has no chain to fold, and only the epilogue differs, h = o tanh(c).
+// Layer 0 of an attention decoder reads [embedding | gated context], E + C columns: above kDecMaxK it runs on
+// lstm_decode_step_wide_kernel (below; K up to 4096, a wave's range in two halves), and att_decode_step at the end of
+// this file is the attention decoders' beam step around it (z, the beam-aware attention kernels of att_kernels.hip, the layers).
 #include "common.h"
 #include "kernels.h"
 #include "step_core.h"
@@ -27,7 +30,7 @@
 namespace capnet {
 
 constexpr int kDecWaves = 8;
-constexpr int kDecMaxK = 2048;       // kin + H <= 8 waves x 16 groups x 16
+constexpr int kDecMaxK = 2048;       // kin + H <= 8 waves x 16 groups x 16 (lstm_decode_step_wide_kernel: kDecWideMaxK)
 
 struct DecodeLayerArgs {
   const long long* tok;  // layer 0 with token ids: x row = x + tok[r] * ldx (else x + r * ldx)
@@ -154,10 +157,105 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
   }
 }
 
+// K = kin + H above kDecMaxK, up to kDecWideMaxK (layer 0 of an attention decoder: x = [embedding | gated context], E + C
+// columns): a wave's range is up to 2 NJ k groups, walked in two halves of at most NJ. Per pass of 32 rows and per half a
+// lane loads the half's weights (NJ f32x4) and, tile by tile, the activations of the pass's two 16-row tiles (NJ f32x4 at a
+// time); the two accumulators are carried across the halves. So up to 32 rows the weights cross HBM once per launch, as
+// above; past 32 rows every further pass reads them again (from L2: a workgroup's slice is 16 columns x K). Both halves'
+// weights resident (2 NJ f32x4) beside one half's activations did not fit in 256 VGPRs. x rows must take f32x4 loads.
+constexpr int kDecWideMaxK = 4096;   // 8 waves x 2 halves x 16 groups x 16
+
+template <int NJ, bool TANH_OUT, bool GATHER>
+__global__ __launch_bounds__(512) void lstm_decode_step_wide_kernel(DecodeLayerArgs a) {
+  __shared__ float red[kDecWaves][32][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lq = lane >> 4;
+  const int H = a.H, u0 = blockIdx.x * 4;
+  const int K = a.kin + H, KG = K >> 4, inG = a.kin >> 4;
+  const int g0 = wave * KG / kDecWaves, ng = (wave + 1) * KG / kDecWaves - g0;   // this wave's groups [g0, g0 + ng), ng <= 2 NJ
+  const float* wrow = a.w + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
+  const int er = tid >> 2, eu = tid & 3;
+  const bool ethread = tid < 128;
+  float bias[4] = {0.f, 0.f, 0.f, 0.f};
+  if (ethread) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bias[g] = a.b[g * H + u0 + eu];
+  }
+  for (int r0 = 0; r0 < a.rows; r0 += 32) {
+    const int tiles = r0 + 16 < a.rows ? 2 : 1;
+    const float* xrow[2];
+    const float* hrow[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int row = clamp_row(r0 + 16 * m + li, a.rows);
+      long xr = row;
+      if (a.tok) {
+        const long long t = a.tok[row];
+        const bool ok = t >= 0 && t < a.V;
+        if (!ok && a.err) *a.err = 1;
+        xr = ok ? (long)t : 0;
+      }
+      xrow[m] = a.x + xr * a.ldx;
+      hrow[m] = a.hprev + state_row<GATHER>(a, row) * a.lds_in;
+    }
+    const int erow = r0 + er;
+    const bool estore = ethread && erow < a.rows;
+    const float cp = estore ? a.cprev[state_row<GATHER>(a, erow) * a.lds_in + u0 + eu] : 0.f;
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll 1
+    for (int hf = 0; hf < 2; ++hf) {
+      const int j0 = hf * NJ;
+      f32x4 wv[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        wv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (j0 + j < ng) wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * (g0 + j0 + j));
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        if (m < tiles) {
+          f32x4 av[NJ];
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            const int g = g0 + j0 + j, k = 16 * g + 4 * lq;
+            if (j0 + j < ng) {
+              if (g >= inG) v = *reinterpret_cast<const f32x4*>(hrow[m] + (k - a.kin));
+              else if (k < a.xn) v = *reinterpret_cast<const f32x4*>(xrow[m] + k);
+            }
+            av[j] = v;
+          }
+          acc[m] = mfma_chain<NJ>(av, wv, acc[m]);
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][16 * m + 4 * lq + r][li] = acc[m][r];
+    __syncthreads();
+    if (estore) {
+      float pre[4], i, f, og, gt, c;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pre[g] = sum_partials<kDecWaves>(red, er, g * 4 + eu, bias[g]);
+      lstm_cell(pre[0], pre[1], pre[2], pre[3], cp, i, f, og, gt, c);
+      const float h = lstm_cell_h(og, c, TANH_OUT);
+      a.c_out[(long)erow * a.lds_out + u0 + eu] = c;
+      a.h_out[(long)erow * a.lds_out + u0 + eu] = h;
+      if (a.h_top) a.h_top[(long)erow * H + u0 + eu] = h;
+    }
+    __syncthreads();   // red is rewritten by the next pass
+  }
+}
+
 static int round16(int v) { return (v + 15) / 16 * 16; }
 
 bool stacked_decode_supported(int E, int H) {
   return E >= 1 && step_hidden_supported(H) && round16(E) + H <= kDecMaxK;
+}
+
+bool stacked_decode_wide_supported(int E, int H) {
+  return E >= 4 && E % 4 == 0 && step_hidden_supported(H) && round16(E) + H <= kDecWideMaxK;
 }
 
 template <int NJ, bool TANH_OUT, bool GATHER>
@@ -174,9 +272,42 @@ static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
   else if (per_wave <= 6) launch_decode<6, TANH_OUT, GATHER>(a, stream);
   else if (per_wave <= 8) launch_decode<8, TANH_OUT, GATHER>(a, stream);
   else if (per_wave <= 12) launch_decode<12, TANH_OUT, GATHER>(a, stream);
-  else launch_decode<16, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 16) launch_decode<16, TANH_OUT, GATHER>(a, stream);
+  else if (per_wave <= 24) hipLaunchKernelGGL((lstm_decode_step_wide_kernel<12, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
+  else hipLaunchKernelGGL((lstm_decode_step_wide_kernel<16, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
   CAPNET_LAUNCH_CHECK();
   return kOk;
+}
+
+// layer l of the stack on x rows of xn valid columns at stride ldx (token ids: rows of the table x)
+static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, const long long* tokens, const float* x, long ldx,
+                        int xn, const float* w, const float* b, const float* state_in, float* state_out, float* h_top,
+                        int* err_flag, hipStream_t stream, const long long* parent_rows) {
+  const long lds = 2L * nlayers * H;
+  DecodeLayerArgs a;
+  a.tok = tokens;
+  a.x = x;
+  a.ldx = ldx;
+  a.xn = xn;
+  a.xvec = xn % 4 == 0 && ldx % 4 == 0 && aligned16(x);
+  a.kin = round16(xn);
+  a.V = V;
+  a.err = err_flag;
+  a.hprev = state_in + (long)(2 * l) * H;
+  a.cprev = state_in + (long)(2 * l + 1) * H;
+  a.lds_in = lds;
+  a.h_out = state_out + (long)(2 * l) * H;
+  a.c_out = state_out + (long)(2 * l + 1) * H;
+  a.lds_out = lds;
+  a.h_top = l == nlayers - 1 ? h_top : nullptr;
+  a.w = w;
+  a.b = b;
+  a.rows = rows;
+  a.H = H;
+  a.parent = parent_rows;
+  CAPNET_REQUIRE(a.kin + H <= kDecMaxK || (a.xvec && a.kin + H <= kDecWideMaxK), "decode step: K = %d + %d", a.kin, H);
+  if (parent_rows) return cell == kCellLSTM ? launch_decode_layer<true, true>(a, stream) : launch_decode_layer<false, true>(a, stream);
+  return cell == kCellLSTM ? launch_decode_layer<true, false>(a, stream) : launch_decode_layer<false, false>(a, stream);
 }
 
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
@@ -184,42 +315,45 @@ int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, co
                         float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows) {
   const long lds = 2L * nlayers * H;
   for (int l = 0; l < nlayers; ++l) {
-    DecodeLayerArgs a;
-    if (l == 0) {
-      a.tok = tokens;
-      a.x = x;
-      a.ldx = E;
-      a.xn = E;
-      a.xvec = E % 4 == 0 && aligned16(x);
-      a.kin = round16(E);
-    } else {
-      a.tok = nullptr;
-      a.x = state_out + (long)(2 * l - 2) * H;
-      a.ldx = lds;
-      a.xn = H;
-      a.xvec = 1;
-      a.kin = H;
-    }
-    a.V = V;
-    a.err = err_flag;
-    a.hprev = state_in + (long)(2 * l) * H;
-    a.cprev = state_in + (long)(2 * l + 1) * H;
-    a.lds_in = lds;
-    a.h_out = state_out + (long)(2 * l) * H;
-    a.c_out = state_out + (long)(2 * l + 1) * H;
-    a.lds_out = lds;
-    a.h_top = l == nlayers - 1 ? h_top : nullptr;
-    a.w = wcat[l];
-    a.b = beff[l];
-    a.rows = rows;
-    a.H = H;
-    a.parent = parent_rows;
-    int rc;
-    if (parent_rows) rc = cell == kCellLSTM ? launch_decode_layer<true, true>(a, stream) : launch_decode_layer<false, true>(a, stream);
-    else rc = cell == kCellLSTM ? launch_decode_layer<true, false>(a, stream) : launch_decode_layer<false, false>(a, stream);
+    const int rc = l == 0 ? decode_layer(cell, 0, nlayers, rows, H, V, tokens, x, E, E, wcat[0], beff[0], state_in, state_out,
+                                         h_top, err_flag, stream, parent_rows)
+                          : decode_layer(cell, l, nlayers, rows, H, V, nullptr, state_out + (long)(2 * l - 2) * H, lds, H, wcat[l],
+                                         beff[l], state_in, state_out, h_top, err_flag, stream, parent_rows);
     if (rc != kOk) return rc;
   }
   return kOk;
+}
+
+// ---- one beam step of an attention decoder ---------------------------------------------------------------------------
+// ws (floats): z [n k][A + C] | xa [n k][E + C] | escore [n k][P rounded up to 4]; every part a multiple of 16 bytes
+bool att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {
+  return nlayers >= 1 && nlayers <= 8 && att_beam_step_supported(E, C, A, P, k) && stacked_decode_wide_supported(E + C, H);
+}
+
+size_t att_decode_step_ws_bytes(int n, int k, int P, int A, int C, int E) {
+  if (n < 1 || !att_beam_step_supported(E, C, A, P, k)) return 0;
+  return (size_t)n * k * ((size_t)A + 2 * (size_t)C + E + (P + 3) / 4 * 4) * sizeof(float);
+}
+
+int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, const float* att1,
+                    const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
+                    const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
+                    const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
+                    size_t slab_floats, int* err_flag, hipStream_t stream) {
+  const int nk = n * k;
+  const long lds = 2L * nlayers * H;
+  float* z = reinterpret_cast<float*>(ws);
+  float* xa = z + (size_t)nk * (A + C);
+  float* escore = xa + (size_t)nk * (E + C);
+  // z of every row from its OWN previous h (layer 0's, slot 0 of state_in); the kernels read it at the parent's row
+  int rc = sgemm_splitk(false, true, nk, A + C, H, state_in, lds, wz, H, z, A + C, bz, 0, slab, slab_floats, stream);
+  if (rc == kOk) rc = att_beam_step_fwd(att1, feat, z, parent_rows, wf, bf, tokens, emb, V, E, n, k, P, A, C, escore, xa, err_flag, stream);
+  if (rc == kOk) rc = decode_layer(cell, 0, nlayers, nk, H, V, nullptr, xa, E + C, E + C, wcat[0], beff[0], state_in, state_out,
+                                   h_top, err_flag, stream, parent_rows);
+  for (int l = 1; l < nlayers && rc == kOk; ++l)
+    rc = decode_layer(cell, l, nlayers, nk, H, V, nullptr, state_out + (long)(2 * l - 2) * H, lds, H, wcat[l], beff[l], state_in,
+                      state_out, h_top, err_flag, stream, parent_rows);
+  return rc;
 }
 
 }  // namespace capnet

@@ -222,10 +222,11 @@ size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_ste
   return beam_decode_layout(nlayers, n, k, H, V, max_steps).total;
 }
 
-int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
-                long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
-                const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+// the loop of both one-call searches: step(tokens, parent rows or null, state_in, state_out, h_top) is the decode step
+template <class Step>
+static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, long long start_token, long long end_token,
+                     const float* Cw, const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats,
+                     int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn) {
   const int nk = n * k;
   const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
@@ -245,8 +246,7 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
   int issued = 0;
   for (int step = 1; step <= max_steps; ++step) {
     // step 1: every beam is at its own (initial) row; afterwards the rows the previous beam_advance chose
-    int rc = stacked_decode_step(cell, nlayers, nk, E, H, V, words[(step - 1) & 1], emb, wcat, beff, state[(step - 1) & 1],
-                                 state[step & 1], h_top, err_flag, s, step == 1 ? nullptr : parent);
+    int rc = step_fn(words[(step - 1) & 1], step == 1 ? nullptr : parent, state[(step - 1) & 1], state[step & 1], h_top);
     if (rc == kOk) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
     if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
     if (rc != kOk) return rc;
@@ -260,6 +260,41 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
   }
   if (steps_run) *steps_run = issued;
   return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, s);
+}
+
+int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
+                const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+  return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
+                   lengths, steps_run, s,
+                   [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
+                     return stacked_decode_step(cell, nlayers, n * k, E, H, V, tok, emb, wcat, beff, sin, sout, h_top, err_flag, s,
+                                                parent);
+                   });
+}
+
+// ---- the same loop for the attention decoders: the step is att_decode_step (z, the two attention launches, layer 0 on
+// [embedding | gated context], the upper layers) ----
+// ws: beam_decode's layout, then att_decode_step's block (z | xa | escore)
+size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps) {
+  const size_t base = beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps), step = att_decode_step_ws_bytes(n, k, P, A, C, E);
+  return base && step ? base + gd_align(step) : 0;
+}
+
+int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                    long long start_token, long long end_token, const float* att1, const float* feat, const float* emb,
+                    const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
+                    const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
+                    size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                    hipStream_t s) {
+  void* step_ws = reinterpret_cast<char*>(ws) + beam_decode_layout(nlayers, n, k, H, V, max_steps).total;
+  return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
+                   lengths, steps_run, s,
+                   [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
+                     return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
+                                            sin, parent, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
+                   });
 }
 
 }  // namespace capnet

@@ -47,14 +47,47 @@ def plain_stack(step_fn, packed, cell, emb, C):
     return step_fn
 
 
+class AttStack:
+    """What ops.att_beam_decode needs of an attention decoder: the cell kind, the packed or folded weights [(wcat, beff)]
+    per layer (layer 0 reading E + C columns), wz / bz = [decoder_att; f_beta] stacked, full_att, the embedding table,
+    the projection, the maps feat [n, P, C] and att1 [n, P, A] = encoder_att(feat) PER IMAGE, and the initial state
+    [n k, 2L, H] (init_h / init_c of every layer, each image's row k times)."""
+
+    def __init__(self, cell, packed, wz, bz, full_att, emb, Cw, Cb, feat, att1, state):
+        self.cell, self.wz, self.bz, self.full_att = cell, wz, bz, full_att
+        self.emb, self.Cw, self.Cb = emb.detach(), Cw.detach(), None if Cb is None else Cb.detach()
+        self.wcat, self.beff = [w for w, _ in packed], [b for _, b in packed]
+        self.feat, self.att1, self.state = feat, att1, state
+
+
+def att_stack_supported(dec, E, Cdim, P, k, num_layers):
+    """Whether an attention decoder of this shape takes ops.att_beam_decode now (CAPNET_NO_FUSED_DECODE_STEP is read here)."""
+    return (os.environ.get(FUSED_DECODE_OFF, "")[:1] != "1" and E % 4 == 0 and k <= dec.vocab_size and
+            ops.att_decode_supported(E, Cdim, dec.hidden_size, dec.attention_size, P, k, num_layers))
+
+
+def att_stack(step_fn, dec, cell, pack, attention, embed, project, maps, k, entries):
+    """step_fn (att_beam_step's: it carries the stacked wz / bz) with the AttStack of an attention decoder attached where
+    the shape is supported: pack() -> [(wcat, beff)]
+    per layer is called only then (the fold or the packing costs launches). maps: att_beam_start's (feat, att1) per image;
+    entries: the beam state's tensors of every layer in order, [rows, H] or [rows, m, H] each."""
+    feat, att1 = maps
+    state = torch.cat([t.unsqueeze(1) if t.dim() == 2 else t for t in entries], 1).contiguous()
+    if att_stack_supported(dec, embed.weight.shape[1], feat.shape[2], feat.shape[1], k, state.shape[1] // 2):
+        step_fn.att = AttStack(cell, pack(), step_fn.wz, step_fn.bz, attention.full_att, embed.weight, project.weight,
+                               project.bias, feat, att1, state)
+    return step_fn
+
+
 def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
     capnet.beam.beam_search_device, whose bookkeeping stays on the device (fixed rows, no host read per step; poll_every
     as there). one_call: the same search as ONE C call (ops.beam_decode: the parent rows read by the step itself, no
-    Python per step) where step_fn carries a PlainStack and the shape is one ops.beam_decode_supported; everywhere else
-    -- a decoder without a plain stack, an unsupported shape, CAPNET_NO_FUSED_DECODE_STEP=1 -- it is on_device=True."""
+    Python per step) where step_fn carries a PlainStack and the shape is one ops.beam_decode_supported, or carries an
+    AttStack (ops.att_beam_decode; att_stack attaches it only for a supported shape); everywhere else -- an unsupported
+    shape, an embedding width that is no multiple of 4, CAPNET_NO_FUSED_DECODE_STEP=1 -- it is on_device=True."""
     dev = state[0].device
     with torch.no_grad():
         if one_call:
@@ -63,6 +96,12 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
                                                                len(plain.wcat)):
                 seqs = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, 1 if n is None else n,
                                        k, dec.max_seq_length + 1, start_token, end_token, poll_every)
+                return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
+            att = getattr(step_fn, "att", None)
+            if att is not None:
+                seqs = ops.att_beam_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
+                                           att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, k,
+                                           dec.max_seq_length + 1, start_token, end_token, poll_every)
                 return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
         if on_device:
             seqs = beam_search_device(step_fn, state, 1 if n is None else n, dec.vocab_size, start_token, end_token, k,
@@ -93,29 +132,32 @@ def attend(attention, encoder_out, decoder_hidden):
 
 
 def att_beam_start(dec, attention, features, n, k):
-    """The set-up of an attention beam search -> (feat, att1_of, feat_of, h0, c0, img). encoder_att(features) is computed
+    """The set-up of an attention beam search -> (feat, att1_of, feat_of, h0, c0, img, maps). encoder_att(features) is computed
     once per image (the reference recomputes it for every beam and step); att1_of / feat_of (state, rows) give a step the
     map rows of its live beams.
     n None: `features` is the map of ONE image ([1, S, S, C] or [1, P, C]); feat [k, P, C] holds it k times, so
     re-indexing by beam (model_att.py:413) is a slice; h0, c0 [k, H]; img None.
     Else n images ([n, S, S, C] or [n, P, C]): feat [n, P, C]; a beam's rows are gathered by its image index, the LAST
-    entry of the beam state; h0, c0 [n k, H]; img [n k]."""
+    entry of the beam state; h0, c0 [n k, H]; img [n k].
+    maps: (the feature map [n, P, C], att1 [n, P, A]) per image (n None: one image), what att_stack takes."""
     dev = attention.encoder_att.weight.device
     A, Cdim = dec.attention_size, features.size(-1)
     if n is None:
         feat1 = features.reshape(1, -1, Cdim).to(dev).contiguous()
         P = feat1.size(1)
         feat = feat1.expand(k, P, Cdim).contiguous()
-        att1 = attention.encoder_att(feat1[0]).reshape(1, P, A).expand(k, P, A).contiguous()
+        att1_1 = attention.encoder_att(feat1[0]).reshape(1, P, A)
+        att1 = att1_1.expand(k, P, A).contiguous()
         h0, c0 = dec.init_hidden_state(feat)
-        return feat, lambda st, r: att1[:r], lambda st, r: feat[:r], h0, c0, None
+        return feat, lambda st, r: att1[:r], lambda st, r: feat[:r], h0, c0, None, (feat1, att1_1)
     feat = features.reshape(n, -1, Cdim).to(dev).contiguous()
     P = feat.size(1)
     att1 = attention.encoder_att(feat.reshape(n * P, Cdim)).reshape(n, P, A).contiguous()
     h0, c0 = dec.init_hidden_state(feat)
     img = torch.arange(n, device=dev).repeat_interleave(k)
     h0, c0 = h0.index_select(0, img).contiguous(), c0.index_select(0, img).contiguous()
-    return feat, lambda st, r: att1.index_select(0, st[-1]), lambda st, r: feat.index_select(0, st[-1]), h0, c0, img
+    return (feat, lambda st, r: att1.index_select(0, st[-1]), lambda st, r: feat.index_select(0, st[-1]), h0, c0, img,
+            (feat, att1))
 
 
 def att_beam_step(attention, f_beta, embed, cell, project, att1_of, feat_of, n_att, upper=None):
@@ -134,13 +176,20 @@ def att_beam_step(attention, f_beta, embed, cell, project, att1_of, feat_of, n_a
         h, c, rest = state[0], state[1], tuple(state[2:])
         s_rows = h.shape[0]
         z = ops.linear(h, wz, bz).contiguous()
-        xa = torch.empty((s_rows, E + n_att), dtype=torch.float32, device=dev)
-        xa[:, :E] = embed(prev_words)
-        ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
-                           attention.full_att.bias, xa=xa, xa_col=E)
+        if E % 4 == 0:
+            xa = torch.empty((s_rows, E + n_att), dtype=torch.float32, device=dev)
+            xa[:, :E] = embed(prev_words)
+            ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
+                               attention.full_att.bias, xa=xa, xa_col=E)
+        else:       # the context kernel stores 16-B vectors: behind an embedding width off 4 the context is joined on
+            ctx = torch.empty((s_rows, n_att), dtype=torch.float32, device=dev)
+            ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
+                               attention.full_att.bias, xa=ctx)
+            xa = torch.cat([embed(prev_words).reshape(s_rows, E), ctx], 1)
         h, c = cell(xa, (h, c))
         top, new = upper_step(h, rest)
         return project(top), (h, c) + tuple(new) + rest[len(new):]
+    step_fn.wz, step_fn.bz = wz, bz
     return step_fn
 
 

@@ -12,8 +12,9 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr
-from .decode import att_beam_start, att_beam_step, attend, beam_decode, factored_step
-from .model import Dropout, Embedding, Linear, _Marker, _MODES, _TrunkRunner, _resnet152_children, _seq_cfg
+from . import decode
+from .decode import att_beam_start, att_beam_step, attend, beam_decode, factored_step, fold_factored
+from .model import Dropout, Embedding, Linear, _Marker, _MODES, _TrunkRunner, _layer_mods, _resnet152_children, _seq_cfg
 
 
 class EncoderCNN(nn.Module):
@@ -183,15 +184,26 @@ class DecoderFactoredLSTMAtt(nn.Module):
         """(the beam state's entries after layer 0's (h0, c0), att_beam_step's `upper`). One layer here."""
         return (), None
 
+    def _fold(self, mode):
+        """[(wcat, beff)] of every layer for capnet_att_decode_step: the factored chains folded (capnet.decode.fold_factored;
+        layer 0's reads E + C columns). One layer here."""
+        self._mode_modules(mode)          # the reference's message and error for an unknown mode
+        return [fold_factored(*_layer_mods(self, "", mode))]
+
     @torch.no_grad()
-    def _beam(self, features, n, k, mode):
+    def _beam(self, features, n, k, mode, one_call=False):
         """(step_fn, initial state) of a beam search over one image (n None) or n images: the state is layer 0's (h, c),
-        then what _upper_beam adds, then (n images) every beam's image index."""
+        then what _upper_beam adds, then (n images) every beam's image index. one_call: the AttStack of the search as one C
+        call rides on step_fn where the shape is supported (capnet.decode.att_stack: only then is anything folded); the
+        steps of step_fn itself stay the composed chain."""
         attention, _ = self._mode_modules(mode)
-        feat, att1_of, feat_of, h0, c0, img = att_beam_start(self, attention, features, n, k)
+        feat, att1_of, feat_of, h0, c0, img, maps = att_beam_start(self, attention, features, n, k)
         state, upper = self._upper_beam(feat, img, mode)
         step_fn = att_beam_step(attention, self.f_beta, self.B, lambda xa, hc: self.forward_step(xa, hc, mode=mode)[1],
                                 self.C, att1_of, feat_of, features.size(-1), upper)
+        if one_call:
+            decode.att_stack(step_fn, self, ops.CELL_FACTORED, lambda: self._fold(mode), attention, self.B, self.C,
+                             maps, k, (h0, c0) + state)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
@@ -199,8 +211,9 @@ class DecoderFactoredLSTMAtt(nn.Module):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
         of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
-        one_call: accepted for every decoder; an attention step is no plain stack, so it is on_device=True here."""
-        return beam_decode(self, *self._beam(features, None, k, mode), None, k, start_token, end_token, on_device, poll_every,
+        one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps,
+        the chain folded); on_device=True for a shape that call does not take. Same sequences."""
+        return beam_decode(self, *self._beam(features, None, k, mode, one_call), None, k, start_token, end_token, on_device, poll_every,
                            one_call)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
@@ -209,7 +222,7 @@ class DecoderFactoredLSTMAtt(nn.Module):
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
         images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k, mode), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
 
     def forward(self,
                 captions,

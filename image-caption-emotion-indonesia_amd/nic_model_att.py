@@ -8,8 +8,8 @@ libcapnet_hip.so (capnet_att_seq_forward/backward with cell = 1).
 import torch
 import torch.nn as nn
 
-from . import ops
-from .decode import att_beam_start, att_beam_step, beam_decode
+from . import decode, ops
+from .decode import att_beam_start, att_beam_step, beam_decode, pack_cells
 from .model import Dropout, Embedding, Linear, _Marker, _seq_cfg
 from .model_att import Attention, EncoderCNN  # noqa: F401  (same classes as the StyleNet path)
 from .nic_model import LSTMCell
@@ -95,24 +95,33 @@ class DecoderRNNAtt(nn.Module):
         """(the beam state's entries after layer 0's (h0, c0), att_beam_step's `upper`). One layer here."""
         return (), None
 
+    def _cells(self):
+        """The LSTMCells of every layer, bottom up. One layer here."""
+        return [self.lstm]
+
     @torch.no_grad()
-    def _beam(self, features, n, k):
+    def _beam(self, features, n, k, one_call=False):
         """(step_fn, initial state) of a beam search over one image (n None) or n images: the state is layer 0's (h, c),
-        then what _upper_beam adds, then (n images) every beam's image index."""
-        feat, att1_of, feat_of, h0, c0, img = att_beam_start(self, self.attention, features, n, k)
+        then what _upper_beam adds, then (n images) every beam's image index. one_call: the AttStack of the search as one C
+        call rides on step_fn where the shape is supported (capnet.decode.att_stack: only then are the cells packed)."""
+        feat, att1_of, feat_of, h0, c0, img, maps = att_beam_start(self, self.attention, features, n, k)
         state, upper = self._upper_beam(feat, img)
         step_fn = att_beam_step(self.attention, self.f_beta, self.embed, self.lstm, self.linear, att1_of, feat_of,
                                 features.size(-1), upper)
+        if one_call:
+            decode.att_stack(step_fn, self, ops.CELL_LSTM, lambda: pack_cells(self._cells(), self.lstm.input_size),
+                             self.attention, self.embed, self.linear, maps, k, (h0, c0) + state)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
-        one_call: accepted for every decoder; an attention step is no plain stack, so it is on_device=True here."""
-        return beam_decode(self, *self._beam(features, None, k), None, k, start_token, end_token, on_device, poll_every, one_call)
+        one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps);
+        on_device=True for a shape that call does not take. Same sequences."""
+        return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
 
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).
         Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(features, n, k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)

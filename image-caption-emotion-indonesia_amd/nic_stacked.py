@@ -138,6 +138,9 @@ class StackedDecoderRNNAtt(DecoderRNNAtt):
     def _upper_cells(self):
         return [getattr(self, "lstm%d" % l) for l in range(1, self.num_layers)]
 
+    def _cells(self):
+        return [self.lstm] + self._upper_cells()
+
     def _upper_layers(self):
         weights = []
         for l in range(1, self.num_layers):

@@ -552,6 +552,122 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     return (out, steps.value) if return_steps else out
 
 
+def att_decode_supported(E, Cdim, H, A, P, k, num_layers):
+    """The shapes capnet_att_decode_step / capnet_att_beam_decode take (capnet_att_decode_supported)."""
+    return bool(_lib.lib().capnet_att_decode_supported(int(E), int(Cdim), int(H), int(A), int(P), int(k), int(num_layers)))
+
+
+def _att_decode_args(who, cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state):
+    """The checked operands the two attention-decode calls share -> (tensors..., dims n, P, A, Cdim, E, H, V, nl)."""
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("%s: unknown cell %r" % (who, cell))
+    _need_cuda(att1, feat, emb, wz, bz, w_full, b_full, state, *wcat, *beff)
+    att1, feat, emb, wz, bz = _c(att1.detach()), _c(feat.detach()), _c(emb.detach()), _c(wz.detach()), _c(bz.detach())
+    wf, bf = _c(w_full.detach()).reshape(-1), _c(b_full.detach()).reshape(-1)
+    state = _c(state.detach())
+    n, P, A = att1.shape
+    Cdim, (V, E), nl, k = feat.shape[2], emb.shape, len(wcat), int(k)
+    H = state.shape[2]
+    if tuple(feat.shape[:2]) != (n, P) or tuple(wz.shape) != (A + Cdim, H) or bz.numel() != A + Cdim or wf.numel() != A:
+        raise CapnetError("%s: att1 [n, P, A], feat [n, P, C], wz [A + C, H], bz [A + C], w_full [A]" % who)
+    if len(beff) != nl or k < 1 or tuple(state.shape) != (n * k, 2 * nl, H) or not att_decode_supported(E, Cdim, H, A, P, k, nl):
+        raise CapnetError("%s: unsupported shape (E=%d, C=%d, H=%d, A=%d, P=%d, k=%d, %d layers, state %r)"
+                          % (who, E, Cdim, H, A, P, k, nl, tuple(state.shape)))
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = (E + Cdim + 15) // 16 * 16 if l == 0 else H
+        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
+            raise CapnetError("%s: layer %d weights must be [4H, %d] and [4H]" % (who, l, kin + H))
+    return att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl)
+
+
+def att_decode_step_workspace(n, k, P, A, Cdim, E, device):
+    """float32 workspace of capnet_att_decode_step: z [n k, A + C] first, then xa and the raw scores."""
+    return torch.empty(_lib.lib().capnet_att_decode_step_ws_bytes(n, k, P, A, Cdim, E) // 4, dtype=torch.float32, device=device)
+
+
+def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, beff, state, cell=CELL_FACTORED, parent_rows=None,
+                    workspace=None):
+    """One beam step of an attention decoder without the projection (capnet_att_decode_step): n images x k fixed slots, row
+    r on the maps of image r // k. att1 [n, P, A] = encoder_att(feat), feat [n, P, C]: per image, never per row. wz [A + C,
+    H] / bz = [decoder_att; f_beta]; w_full / b_full: full_att; wcat / beff: capnet.decode.pack_cell / fold_factored per
+    layer, layer 0 reading E + C columns; state [n k, 2L, H]; tokens int64 [n k]; parent_rows int64 [n k]: the step on
+    state.index_select(0, parent_rows) without that copy. workspace: att_decode_step_workspace(...) or None.
+    Returns (top-layer h [n k, H], the new state)."""
+    att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
+        "att_decode_step", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state)
+    rows, dev = n * int(k), state.device
+    _need_cuda(tokens, parent_rows, workspace)
+    for name, idx in (("tokens", tokens), ("parent_rows", parent_rows)):
+        if idx is not None and (idx.dtype != torch.int64 or idx.numel() != rows or not idx.is_contiguous()):
+            raise CapnetError("att_decode_step: %s must be contiguous int64 [n k]" % name)
+    if tokens is None:
+        raise CapnetError("att_decode_step: tokens are required")
+    L = _lib.lib()
+    if workspace is None:
+        workspace = att_decode_step_workspace(n, int(k), P, A, Cdim, E, dev)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or \
+            workspace.numel() * 4 < L.capnet_att_decode_step_ws_bytes(n, int(k), P, A, Cdim, E):
+        raise CapnetError("att_decode_step: workspace too small")
+    slab = splitk_slab(dev)
+    out = torch.empty_like(state)
+    top = torch.empty((rows, H), dtype=torch.float32, device=dev)
+    check(L.capnet_att_decode_step(cell, nl, n, int(k), P, A, Cdim, E, H, V, ptr(att1), ptr(feat), ptr(tokens), ptr(emb), ptr(wz),
+                                   ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(state), ptr(parent_rows),
+                                   ptr(out), ptr(top), ptr(workspace), ptr(slab), slab.numel(), ptr(err_flag(dev)),
+                                   current_stream()), "capnet_att_decode_step")
+    return top, out
+
+
+_att_beam_decode_ws = {}
+
+
+def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
+                    end_token, poll_every=0, return_steps=False):
+    """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
+    steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
+    capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
+    (init_h / init_c per layer and image, each image's row k times). The workspace is cached per (device, shape).
+    Sequences, lengths and the device's error word come to the host in one copy; a set error word raises
+    (check_device_errors). Returns the n token lists; with return_steps, (lists, the steps issued)."""
+    att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
+        "att_beam_decode", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state)
+    _need_cuda(Cw, Cb)
+    Cw = _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    k, T = int(k), int(max_steps)
+    if T < 1 or k > V or tuple(Cw.shape) != (V, H) or (Cb is not None and Cb.numel() != V):
+        raise CapnetError("att_beam_decode: Cw [V, H], Cb [V], k <= V, max_steps >= 1 (V=%d, k=%d, max_steps=%d)" % (V, k, T))
+    dev = emb.device
+    L = _lib.lib()
+    key = (dev.index or 0, nl, n, k, P, A, Cdim, E, H, V, T)
+    ws = _att_beam_decode_ws.get(key)
+    if ws is None:
+        ws = torch.empty((L.capnet_att_beam_decode_ws_bytes(nl, n, k, P, A, Cdim, E, H, V, T) + 7) // 8, dtype=torch.int64,
+                         device=dev)
+        _att_beam_decode_ws[key] = ws
+    slab = splitk_slab(dev)
+    SL = T + 2
+    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
+    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
+    tail = packed[n * SL:].view(torch.int32)
+    flag = err_flag(dev)
+    steps = C.c_int(0)
+    check(L.capnet_att_beam_decode(cell, nl, n, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat),
+                                   ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw),
+                                   ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(), int(poll_every), ptr(packed),
+                                   C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
+          "capnet_att_beam_decode")
+    tail[n:n + 1].copy_(flag)
+    host = packed.cpu()
+    htail = host[n * SL:].view(torch.int32)
+    if int(htail[n]):
+        check_device_errors()
+    lens = htail[:n].tolist()
+    rows = host[:n * SL].view(n, SL).tolist()
+    out = [rows[i][:lens[i]] for i in range(n)]
+    return (out, steps.value) if return_steps else out
+
+
 def packed_targets(captions, lengths):
     """pack_padded_sequence(captions, lengths, batch_first=True)[0] for int64 captions."""
     _need_cuda(captions)

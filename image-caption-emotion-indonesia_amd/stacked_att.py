@@ -31,10 +31,10 @@ nothing more.
 
 Decoding: DecoderFactoredLSTMAtt's sample / sample_batch (capnet.decode's attention beam step) with this class's upper
 layers (_upper_beam): the beam state is every layer's (h, c), and each upper layer takes the composed step
-(capnet.decode.factored_step).
+(capnet.decode.factored_step). one_call=True: the whole search in one C call on every layer's folded chain (_fold).
 """
 from ._lib import CapnetError
-from .decode import factored_step
+from .decode import factored_step, fold_factored
 from .model import Linear, _MODES, _layer_mods
 from .model_att import DecoderFactoredLSTMAtt
 
@@ -106,6 +106,11 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
         return factored_step(*self._upper_mods(l, mode), x, h, c)
 
     # ---- decoding ---------------------------------------------------------------------------------
+    def _fold(self, mode):
+        """DecoderFactoredLSTMAtt._fold with the upper layers' chains folded as well (H -> H cells)."""
+        return super(StackedFactoredLSTMAtt, self)._fold(mode) + [fold_factored(*self._upper_mods(l, mode))
+                                                                  for l in range(1, self.num_layers)]
+
     def _upper_beam(self, feat, img, mode):
         """The beam state is every layer's (h, c): the upper layers' init_h{l} / init_c{l}(mean feature), tiled by image
         index, and their step on the entries after layer 0's."""

@@ -603,6 +603,49 @@ int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V,
                        size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                        capnet_stream_t stream);
 
+/* One beam step of an attention decoder (DecoderFactoredLSTMAtt / DecoderRNNAtt and their stacked forms) without the
+ * vocabulary projection, for n images x k fixed slots (row r belongs to image r / k), on `stream`, in this order:
+ *   1. z [n k][A + C] = h_prev . wz^T + bz, wz = [decoder_att; f_beta] stacked ([A + C][H]), h_prev = layer 0's h of every
+ *      row of state_in, NOT gathered, by capnet_sgemm_splitk's entry on `slab`;
+ *   2. two attention launches that handle the k beams of an image together on ONE read of its maps: att1 [n][P][A]
+ *      (= encoder_att(feat), the caller's) and feat [n][P][C] are per image, never per row; att2 and the gate
+ *      pre-activation of row r are z's row parent_rows[r] (z is only read: no sigmoid is written back); the second launch
+ *      writes xa [n k][E + C] = [emb[tokens[r]] | sigmoid(gate) * context];
+ *   3. layer 0 of capnet_stacked_decode_step_gather's kernel family on the dense xa rows (E + C rounded up to 16, plus H,
+ *      may reach 4096: above 2048 the wide kernel of the family), h and c read at row parent_rows[r];
+ *   4. layers 1 .. nlayers - 1, plain H -> H cells on the layer below, as capnet_stacked_decode_step_gather.
+ * cell / wcat / beff (HOST arrays of nlayers device pointers) as capnet_stacked_decode_step_cell, wcat[0] [4H][kin + H] with
+ * kin = E + C rounded up to 16. state_in / state_out [n k][2 nlayers][H], different buffers; h_top [n k][H].
+ * parent_rows: int64 [n k] or NULL (every row its own parent); one outside [0, n k) sets *err_flag = 1 and the row reads
+ * itself. A token id outside [0, V) sets *err_flag = 1 and reads row 0 of emb [V][E].
+ * workspace: capnet_att_decode_step_ws_bytes(n, k, P, A, C, E) bytes, 16-B aligned: z, then xa, then the raw scores
+ * [n k][P rounded up to 4]. slab: at least n k max(V, A + C) floats, 16-B aligned.
+ * Shapes (capnet_att_decode_supported): A % 4 == 0, C % 512 == 0, 1 <= P <= 4096, E % 4 == 0, 1 <= k <= 16, H in {64, 128,
+ * 256, 512, 1024}, round16(E + C) + H <= 4096, 1 <= nlayers <= 8. Every bad argument is refused before any launch. */
+int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers);
+size_t capnet_att_decode_step_ws_bytes(int n, int k, int P, int A, int C, int E);
+int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, const float* att1,
+                           const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
+                           const float* w_full, const float* b_full, const float* const* wcat, const float* const* beff,
+                           const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
+                           void* workspace, float* slab, size_t slab_floats, int* err_flag, capnet_stream_t stream);
+
+/* The whole beam search of an attention decoder in one call: capnet_beam_decode's loop with capnet_att_decode_step as the
+ * step. Per step s = 1 .. max_steps: the attention step on the previous step's words and parent rows (no parents at
+ * s = 1), logits = h_top . Cw^T + Cb by capnet_sgemm_splitk's entry on `slab`, capnet_beam_advance; then
+ * capnet_beam_finish into seqs int64 [n][max_steps + 2] and lengths int32 [n]. state0 [n k][2 nlayers][H] is required (the
+ * attention decoders start at init_h / init_c of the mean feature). workspace: capnet_att_beam_decode_ws_bytes(...) bytes,
+ * 16-B aligned (capnet_beam_decode's parts, then capnet_att_decode_step's block; 0 for shapes outside the limits). The call
+ * allocates nothing and issues plain launches; poll_every and *steps_run as capnet_beam_decode. Every bad argument is
+ * refused before any launch. */
+size_t capnet_att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
+int capnet_att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                           long long start_token, long long end_token, const float* att1, const float* feat, const float* emb,
+                           const float* wz, const float* bz, const float* w_full, const float* b_full,
+                           const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                           const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                           long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream);
+
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
  *   capnet_lstm_pack_wfrag image), then the gate
