@@ -139,6 +139,8 @@ SIGNATURES = {
                                              _vp, _vp, _vp]),
     "capnet_stacked_decode_step_gather": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                                _vp, _vp, _vp, _vp]),
+    "capnet_stacked_decode_step_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                               _vp, _vp, _vp, _vp]),
     "capnet_vocab_argmax_ws_bytes": (_sz, [_i, _i]),
     "capnet_vocab_argmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "capnet_lstm_greedy_decode_ws_bytes": (_sz, [_i, _i, _i, _i]),
@@ -147,14 +149,22 @@ SIGNATURES = {
     "capnet_beam_decode_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "capnet_beam_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, C.POINTER(_vp),
                                 C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
+    "capnet_beam_decode_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, C.POINTER(_vp),
+                                       C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
     "capnet_att_decode_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step": (_i, [_i] * 10 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                                           _vp, _vp]),
+    "capnet_att_decode_step_groups": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                                 _sz, _vp, _vp]),
     "capnet_att_beam_decode_ws_bytes": (_sz, [_i] * 10),
     "capnet_att_beam_decode": (_i, [_i] * 11 + [C.c_longlong, C.c_longlong] + [_vp] * 7 + [C.POINTER(_vp), C.POINTER(_vp), _vp,
                                                                                            _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp,
                                                                                            C.POINTER(_i), _vp, _vp]),
+    "capnet_att_beam_decode_groups": (_i, [_i] * 12 + [C.c_longlong, C.c_longlong] + [_vp] * 7 + [C.POINTER(_vp), C.POINTER(_vp),
+                                                                                                  _vp, _vp, _vp, _vp, _vp, _sz,
+                                                                                                  _i, _vp, _vp, C.POINTER(_i),
+                                                                                                  _vp, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),
     "capnet_lstm_pack_wfrag": (_i, [_vp, _vp, _i, _i, _vp]),
     "capnet_lstm_step_fused": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),

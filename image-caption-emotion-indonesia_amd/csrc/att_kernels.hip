@@ -207,17 +207,21 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
 // applied twice. A parent outside [0, n k) raises the flag and the row reads itself; a token id outside [0, V) raises it
 // and reads row 0 (the gathered decode step's conventions). Two launches: scores, then softmax + context + gate, whose
 // first channel block of an image also copies emb[token[r]] into xa[r][0 .. E).
+// Weight groups (every style at once): the n beam groups are G weight groups x n_img images, group-major. Beam group q
+// keeps its own att1 (each mode has its encoder_att) but reads the map of image q % n_img -- feat is not copied per mode
+// -- and the full_att of weight group q / n_img.
 struct AttBeamArgs {
   const float* att1;         // [n][P][A]
-  const float* feat;         // [n][P][C]
+  const float* feat;         // [n_img][P][C]: beam group q reads image q % n_img
   const float* z;            // [n k][ldz] = [att2 (A) | gate pre-activation (C)]
   long ldz;
   const long long* parent;   // int64 [n k] or null
-  const float* wf;           // full_att weight [A], bias [1]
+  const float* wf;           // full_att weight [A], bias [1] per weight group: beam group q reads group q / n_img
   const float* bf;
   const long long* tok;      // int64 [n k]
   const float* emb;          // [V][E]
-  int V, E, n, k, P, A, C;
+  int V, E, n, k, P, A, C;   // n: beam groups (weight groups x images)
+  int n_img;                 // images: n_img = n with one weight group
   float* escore;             // [n k][P]
   float* xa;                 // [n k][ldx] = [embedding (E) | gated context (C)]
   long ldx;
@@ -245,7 +249,9 @@ __global__ __launch_bounds__(kAttThreads) void att_beam_scores_kernel(AttBeamArg
   const float* y[KT];
 #pragma unroll
   for (int r = 0; r < KT; ++r) y[r] = a.z + beam_src_row(a, img * k + min(r, k - 1)) * a.ldz;
-  const float b0 = a.bf[0];
+  const int wg = img / a.n_img;
+  const float* wf = a.wf + (long)wg * A;
+  const float b0 = a.bf[wg];
   for (int p = p0 + PU * wave; p < p1; p += PU * (kAttThreads / 64)) {
     float s[KT][PU];
 #pragma unroll
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(kAttThreads) void att_beam_scores_kernel(AttBeamArg
 #pragma unroll
       for (int u = 0; u < PU; ++u) s[r][u] = 0.f;
     for (int c = lane * 4; c < A; c += 256) {
-      const float4 w = *reinterpret_cast<const float4*>(a.wf + c);
+      const float4 w = *reinterpret_cast<const float4*>(wf + c);
       float4 x[PU];
 #pragma unroll
       for (int u = 0; u < PU; ++u) x[u] = *reinterpret_cast<const float4*>(a1 + (long)min(p + u, p1 - 1) * A + c);
@@ -318,7 +324,7 @@ __global__ __launch_bounds__(kAttThreads) void att_beam_context_kernel(AttBeamAr
     }
   }
   const int c = blockIdx.y * kCtxCh + lane * 4;
-  const float* f = a.feat + (long)img * P * C + c;
+  const float* f = a.feat + (long)(img % a.n_img) * P * C + c;
   float4 s[KT];
 #pragma unroll
   for (int r = 0; r < KT; ++r) s[r] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -381,7 +387,9 @@ static void launch_att_beam(const AttBeamArgs& a, hipStream_t stream) {
 
 int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
                       const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
-                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream) {
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img) {
+  if (n_img <= 0) n_img = n;
+  CAPNET_REQUIRE(n % n_img == 0, "att_beam_step_fwd: %d beam groups on %d images", n, n_img);
   CAPNET_REQUIRE(att1 && feat && z && wf && bf && tokens && emb && escore && xa && err_flag, "att_beam_step_fwd: null argument");
   CAPNET_REQUIRE(n >= 1 && V >= 1 && att_beam_step_supported(E, C, A, P, k),
                  "att_beam_step_fwd: n=%d k=%d E=%d A=%d C=%d P=%d V=%d", n, k, E, A, C, P, V);
@@ -390,7 +398,7 @@ int att_beam_step_fwd(const float* att1, const float* feat, const float* z, cons
   AttBeamArgs a;
   a.att1 = att1; a.feat = feat; a.z = z; a.ldz = (long)A + C; a.parent = parent_rows; a.wf = wf; a.bf = bf;
   a.tok = tokens; a.emb = emb; a.V = V; a.E = E; a.n = n; a.k = k; a.P = P; a.A = A; a.C = C;
-  a.escore = escore; a.xa = xa; a.ldx = (long)E + C; a.err = err_flag;
+  a.escore = escore; a.xa = xa; a.ldx = (long)E + C; a.err = err_flag; a.n_img = n_img;
   if (k <= 4) launch_att_beam<4, 4>(a, stream);
   else if (k <= 8) launch_att_beam<8, 4>(a, stream);
   else launch_att_beam<16, 2>(a, stream);

@@ -346,10 +346,10 @@ int capnet_lstm_pointwise_fwd(float* pre, const float* c_prev, float* c_out, flo
   return lstm_pointwise_fwd(pre, 4L * H, c_prev, c_out, h_out, b, H, 0, 1, 3, 2, 1, S(stream));
 }
 
-int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
-                                      const float* x, const float* const* wcat, const float* const* beff,
-                                      const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
-                                      int* err_flag, capnet_stream_t stream) {
+// what capnet_stacked_decode_step_gather and capnet_stacked_decode_step_groups check alike
+static int stacked_step_check(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
+                              const float* const* wcat, const float* const* beff, const float* state_in,
+                              const long long* parent_rows, const float* state_out, const float* h_top, const int* err_flag) {
   CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "stacked_decode_step: unknown cell %d", cell);
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "stacked_decode_step: layers %d (1..8)", nlayers);
   CAPNET_REQUIRE(rows >= 1, "stacked_decode_step: rows %d", rows);
@@ -363,8 +363,32 @@ int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, in
     CAPNET_REQUIRE(wcat[l] && beff[l], "stacked_decode_step: weights of layer %d are null", l);
     CAPNET_REQUIRE(aligned16(wcat[l]), "stacked_decode_step: weights of layer %d not 16-B aligned", l);
   }
+  return kOk;
+}
+
+int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
+                                      const float* x, const float* const* wcat, const float* const* beff,
+                                      const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
+                                      int* err_flag, capnet_stream_t stream) {
+  if (int rc = stacked_step_check(cell, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, parent_rows, state_out, h_top,
+                                  err_flag))
+    return rc;
   return stacked_decode_step(cell, nlayers, rows, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top, err_flag,
                              S(stream), parent_rows);
+}
+
+// (a group's weights follow the group before it at 4H (kin + H) floats, a multiple of 16 bytes: layer l's alignment is group 0's)
+int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int rows_per_group, int E, int H, int V,
+                                      const long long* tokens, const float* x, const float* const* wcat,
+                                      const float* const* beff, const float* state_in, const long long* parent_rows,
+                                      float* state_out, float* h_top, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "stacked_decode_step: groups %d (1..8)", groups);
+  CAPNET_REQUIRE(rows_per_group >= 1 && rows_per_group < (1 << 24), "stacked_decode_step: rows per group %d", rows_per_group);
+  if (int rc = stacked_step_check(cell, nlayers, groups * rows_per_group, E, H, V, tokens, x, wcat, beff, state_in, parent_rows,
+                                  state_out, h_top, err_flag))
+    return rc;
+  return stacked_decode_step(cell, nlayers, groups * rows_per_group, E, H, V, tokens, x, wcat, beff, state_in, state_out, h_top,
+                             err_flag, S(stream), parent_rows, groups);
 }
 
 int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
@@ -425,10 +449,22 @@ int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V,
                        const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
                        size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                        capnet_stream_t stream) {
+  return capnet_beam_decode_groups(cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
+                                   state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream);
+}
+
+// n below: the beam groups, groups x images
+int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n_images, int k, int E, int H, int V, int max_steps,
+                              long long start_token, long long end_token, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                              float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                              int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "beam_decode: groups %d (1..8)", groups);
+  const int n = n_images >= 1 && n_images < (1 << 24) ? groups * n_images : 0;
   CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "beam_decode: unknown cell %d", cell);
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "beam_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(n >= 1 && max_steps >= 1 && V >= 1 && poll_every >= 0, "beam_decode: n %d, max_steps %d, V %d, poll_every %d", n,
-                 max_steps, V, poll_every);
+  CAPNET_REQUIRE(n >= 1 && max_steps >= 1 && V >= 1 && poll_every >= 0, "beam_decode: n %d, max_steps %d, V %d, poll_every %d",
+                 n_images, max_steps, V, poll_every);
   CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
   CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28) && (long)n * k * V < (1L << 31), "beam_decode: n k too large");
   CAPNET_REQUIRE(stacked_decode_supported(E, H), "beam_decode: unsupported E=%d H=%d", E, H);
@@ -443,8 +479,8 @@ int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V,
     CAPNET_REQUIRE(wcat[l] && beff[l], "beam_decode: weights of layer %d are null", l);
     CAPNET_REQUIRE(aligned16(wcat[l]), "beam_decode: weights of layer %d not 16-B aligned", l);
   }
-  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
-                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream));
+  return beam_decode(cell, nlayers, n_images, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0,
+                     workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups);
 }
 
 int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {
@@ -456,10 +492,13 @@ size_t capnet_att_decode_step_ws_bytes(int n, int k, int P, int A, int C, int E)
 static int att_decode_check(const char* who, int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V,
                             const float* att1, const float* feat, const float* emb, const float* wz, const float* bz,
                             const float* w_full, const float* b_full, const float* const* wcat, const float* const* beff,
-                            const void* workspace, const float* slab, size_t slab_floats, const int* err_flag) {
+                            const void* workspace, const float* slab, size_t slab_floats, const int* err_flag, int groups = 1) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "%s: groups %d (1..8)", who, groups);
+  const int n_images = n;
+  n = n >= 1 && n < (1 << 24) ? groups * n : 0;   // the beam groups
   CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "%s: unknown cell %d", who, cell);
   CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "%s: layers %d (1..8)", who, nlayers);
-  CAPNET_REQUIRE(n >= 1 && V >= 1, "%s: n %d, V %d", who, n, V);
+  CAPNET_REQUIRE(n >= 1 && V >= 1, "%s: n %d, V %d", who, n_images, V);
   CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "%s: k=%d (1 <= k <= 16, k <= V = %d)", who, k, V);
   CAPNET_REQUIRE(att_decode_supported(E, C, H, A, P, k, nlayers), "%s: unsupported E=%d C=%d H=%d A=%d P=%d", who, E, C, H, A, P);
   CAPNET_REQUIRE((long)n * k * V < (1L << 31) && (long)n * P * C < (1L << 40), "%s: n k too large", who);
@@ -467,6 +506,7 @@ static int att_decode_check(const char* who, int cell, int nlayers, int n, int k
                  "%s: null argument", who);
   CAPNET_REQUIRE(aligned16(att1) && aligned16(feat) && aligned16(emb) && aligned16(wz) && aligned16(w_full) &&
                      aligned16(workspace) && aligned16(slab), "%s: att1, feat, emb, wz, w_full, workspace and slab must be 16-B aligned", who);
+  // (wz and w_full of group g lie (A + C) H and A floats on: multiples of 16 bytes, A % 4 == 0 and H % 4 == 0)
   const size_t need = (size_t)n * k * (size_t)(V > A + C ? V : A + C);
   CAPNET_REQUIRE(slab_floats >= need, "%s: the slab holds %zu floats, one [n k][max(V, A + C)] block is %zu", who, slab_floats, need);
   for (int l = 0; l < nlayers; ++l) {
@@ -481,14 +521,25 @@ int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, in
                            const float* w_full, const float* b_full, const float* const* wcat, const float* const* beff,
                            const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
                            void* workspace, float* slab, size_t slab_floats, int* err_flag, capnet_stream_t stream) {
+  return capnet_att_decode_step_groups(cell, nlayers, 1, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full,
+                                       wcat, beff, state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag,
+                                       stream);
+}
+
+int capnet_att_decode_step_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* state_in,
+                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                  size_t slab_floats, int* err_flag, capnet_stream_t stream) {
   if (int rc = att_decode_check("att_decode_step", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
-                                wcat, beff, workspace, slab, slab_floats, err_flag))
+                                wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
   CAPNET_REQUIRE(tokens && state_in && state_out && h_top, "att_decode_step: null argument");
   CAPNET_REQUIRE(state_in != state_out, "att_decode_step: state_in and state_out must differ");
   CAPNET_REQUIRE(aligned16(state_in) && aligned16(state_out), "att_decode_step: state alignment (16-B aligned)");
   return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full, wcat, beff,
-                         state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, S(stream));
+                         state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, S(stream), groups);
 }
 
 size_t capnet_att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps) {
@@ -501,18 +552,30 @@ int capnet_att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, in
                            const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
                            const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
                            long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream) {
+  return capnet_att_beam_decode_groups(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb,
+                                       wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every,
+                                       seqs, lengths, steps_run, err_flag, stream);
+}
+
+int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  int max_steps, long long start_token, long long end_token, const float* att1,
+                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream) {
   if (int rc = att_decode_check("att_beam_decode", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
-                                wcat, beff, workspace, slab, slab_floats, err_flag))
+                                wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
   CAPNET_REQUIRE(max_steps >= 1 && poll_every >= 0, "att_beam_decode: max_steps %d, poll_every %d", max_steps, poll_every);
-  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28), "att_beam_decode: n k too large");
+  CAPNET_REQUIRE((long)groups * n * k * (max_steps + 2) < (1L << 28), "att_beam_decode: n k too large");
   CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "att_beam_decode: start_token %lld", start_token);
   CAPNET_REQUIRE(Cw && state0 && seqs && lengths, "att_beam_decode: null argument (state0 is required)");
   CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0), "att_beam_decode: Cw and state0 must be 16-B aligned");
   CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "att_beam_decode: seqs / lengths alignment");
   return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
                          b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
-                         err_flag, S(stream));
+                         err_flag, S(stream), groups);
 }
 
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,

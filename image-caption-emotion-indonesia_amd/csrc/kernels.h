@@ -263,7 +263,8 @@ int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, co
 bool stacked_decode_supported(int E, int H);
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr);
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr, int groups = 1);
+// (groups: `rows` = groups x rows per group, group-major; wcat[l] [groups][4H][kin + H], beff[l] [groups][4H])
 // the same kernels' family for layer 0 of an attention decoder, kin + H up to 4096 (x rows of E % 4 == 0 columns, 16-B aligned)
 bool stacked_decode_wide_supported(int E, int H);
 // One beam step of an attention decoder without the projection: z = h_prev . [decoder_att; f_beta]^T + bz (sgemm_splitk on
@@ -275,7 +276,9 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
                     const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
                     const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
-                    size_t slab_floats, int* err_flag, hipStream_t stream);
+                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups = 1);
+// (groups: groups x n beam groups of k rows, group-major; att1 [groups n][P][A], feat [n][P][C], wz / bz / wf / bf and the
+// layers' weights with a leading groups dimension; ws: att_decode_step_ws_bytes at groups x n)
 
 // vocab_argmax.hip: tok[r] = first argmax_v (h[r] . W[v] + b[v]) in one launch, no logits in memory (ws: vocab_argmax_ws_bytes,
 // its first 16 bytes zero before the first use); and capnet.seq2seq's greedy `sample` as one chain of launches
@@ -294,7 +297,8 @@ size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_ste
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s);
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1);
+// (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
 // beam_decode's loop around att_decode_step (att1 = encoder_att(feat), once per call, is the caller's; state0 is required)
 size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
 int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
@@ -302,7 +306,7 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s);
+                    hipStream_t s, int groups = 1);
 
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
@@ -324,7 +328,9 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
 bool att_beam_step_supported(int E, int C, int A, int P, int k);
 int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
                       const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
-                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream);
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img = 0);
+// (n_img > 0, n = G n_img beam groups of G weight groups: group q reads att1 at q, feat [n_img][P][C] at q % n_img and
+// full_att wf [G][A], bf [G] at q / n_img)
 int att_step_bwd(const float* att1, const float* feat, const float* att2, long ldz2,
                  const float* gate, long ldzg, const float* awe, const float* alpha,
                  const float* wf, float* dxa, long ldx, const float* dalphas_bt, int steps,

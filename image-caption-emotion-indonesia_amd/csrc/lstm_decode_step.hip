@@ -20,6 +20,10 @@
 // The nn.LSTMCell instance (TANH_OUT, capnet.nic_stacked) takes wcat = [weight_ih, zero columns up to kin | weight_hh]
 // and beff = bias_ih + bias_hh with the host's gate blocks reordered from torch's i, f, g, o to i, f, o, c~ = g: the
 // LSTM cell has no chain to fold, and only the epilogue differs, h = o tanh(c).
+// Weight groups (every style at once: capnet_stacked_decode_step_groups, capnet_beam_decode_groups): the grid is (H / 4,
+// G), rows are group-major, and workgroup (., g) walks only rows [g rpg, (g + 1) rpg) on the weights w + g 4H (kin + H)
+// and b + g 4H. A 16-row tile never reaches into the next group (the row clamp and the store mask end at the group);
+// parents are checked against all the rows. G = 1 is the kernel as it was.
 // Layer 0 of an attention decoder reads [embedding | gated context], E + C columns: above kDecMaxK it runs on
 // lstm_decode_step_wide_kernel (below; K up to 4096, a wave's range in two halves), and att_decode_step at the end of
 // this file is the attention decoders' beam step around it (z, the beam-aware attention kernels of att_kernels.hip, the layers).
@@ -51,6 +55,8 @@ struct DecodeLayerArgs {
   const float* b;        // [4H]
   int kin, rows, H;
   const long long* parent;  // GATHER: int64 [rows], hprev / cprev are read at row parent[r] (outside [0, rows): err, row r)
+  int rpg;               // rows per weight group: workgroup (., g) walks rows [g rpg, (g + 1) rpg) on w + g wgs, b + g 4H
+  long wgs;              // floats between two groups' weights, 4H (kin + H)
 };
 
 // the row whose previous state row `row` reads
@@ -77,7 +83,8 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
   const int K = a.kin + H, KG = K >> 4, inG = a.kin >> 4;
   const int g0 = wave * KG / kDecWaves, ng = (wave + 1) * KG / kDecWaves - g0;   // this wave's groups [g0, g0 + ng)
   // B operand: column li = gate role li >> 2 (i, f, o, c~), unit u0 + (li & 3)
-  const float* wrow = a.w + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
+  const int grp = blockIdx.y, rbeg = grp * a.rpg, rend = rbeg + a.rpg;   // this group's rows; one group: [0, rows)
+  const float* wrow = a.w + grp * a.wgs + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
   f32x4 wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -90,13 +97,13 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
   float bias[4] = {0.f, 0.f, 0.f, 0.f};
   if (ethread) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bias[g] = a.b[g * H + u0 + eu];
+    for (int g = 0; g < 4; ++g) bias[g] = a.b[(grp * 4 + g) * H + u0 + eu];
   }
-  for (int r0 = 0; r0 < a.rows; r0 += kPass) {
+  for (int r0 = rbeg; r0 < rend; r0 += kPass) {
     f32x4 av[TM][NJ];
 #pragma unroll
     for (int m = 0; m < TM; ++m) {
-      const int row = clamp_row(r0 + 16 * m + li, a.rows);
+      const int row = clamp_row(r0 + 16 * m + li, rend);
       long xr = row;
       if (a.tok) {
         const long long t = a.tok[row];
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
       }
     }
     const int erow = r0 + er;
-    const bool estore = ethread && erow < a.rows;
+    const bool estore = ethread && erow < rend;
     const float cp = estore ? a.cprev[state_row<GATHER>(a, erow) * a.lds_in + u0 + eu] : 0.f;
     f32x4 acc[TM];
 #pragma unroll
@@ -173,21 +180,22 @@ __global__ __launch_bounds__(512) void lstm_decode_step_wide_kernel(DecodeLayerA
   const int H = a.H, u0 = blockIdx.x * 4;
   const int K = a.kin + H, KG = K >> 4, inG = a.kin >> 4;
   const int g0 = wave * KG / kDecWaves, ng = (wave + 1) * KG / kDecWaves - g0;   // this wave's groups [g0, g0 + ng), ng <= 2 NJ
-  const float* wrow = a.w + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
+  const int grp = blockIdx.y, rbeg = grp * a.rpg, rend = rbeg + a.rpg;   // this group's rows; one group: [0, rows)
+  const float* wrow = a.w + grp * a.wgs + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
   const int er = tid >> 2, eu = tid & 3;
   const bool ethread = tid < 128;
   float bias[4] = {0.f, 0.f, 0.f, 0.f};
   if (ethread) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bias[g] = a.b[g * H + u0 + eu];
+    for (int g = 0; g < 4; ++g) bias[g] = a.b[(grp * 4 + g) * H + u0 + eu];
   }
-  for (int r0 = 0; r0 < a.rows; r0 += 32) {
-    const int tiles = r0 + 16 < a.rows ? 2 : 1;
+  for (int r0 = rbeg; r0 < rend; r0 += 32) {
+    const int tiles = r0 + 16 < rend ? 2 : 1;
     const float* xrow[2];
     const float* hrow[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      const int row = clamp_row(r0 + 16 * m + li, a.rows);
+      const int row = clamp_row(r0 + 16 * m + li, rend);
       long xr = row;
       if (a.tok) {
         const long long t = a.tok[row];
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_wide_kernel(DecodeLayerA
       hrow[m] = a.hprev + state_row<GATHER>(a, row) * a.lds_in;
     }
     const int erow = r0 + er;
-    const bool estore = ethread && erow < a.rows;
+    const bool estore = ethread && erow < rend;
     const float cp = estore ? a.cprev[state_row<GATHER>(a, erow) * a.lds_in + u0 + eu] : 0.f;
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll 1
@@ -260,7 +268,7 @@ bool stacked_decode_wide_supported(int E, int H) {
 
 template <int NJ, bool TANH_OUT, bool GATHER>
 static void launch_decode(const DecodeLayerArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0,
+  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0,
                      stream, a);
 }
 
@@ -273,8 +281,8 @@ static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
   else if (per_wave <= 8) launch_decode<8, TANH_OUT, GATHER>(a, stream);
   else if (per_wave <= 12) launch_decode<12, TANH_OUT, GATHER>(a, stream);
   else if (per_wave <= 16) launch_decode<16, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 24) hipLaunchKernelGGL((lstm_decode_step_wide_kernel<12, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
-  else hipLaunchKernelGGL((lstm_decode_step_wide_kernel<16, TANH_OUT, GATHER>), dim3(a.H / 4), dim3(64 * kDecWaves), 0, stream, a);
+  else if (per_wave <= 24) hipLaunchKernelGGL((lstm_decode_step_wide_kernel<12, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
+  else hipLaunchKernelGGL((lstm_decode_step_wide_kernel<16, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
@@ -282,7 +290,7 @@ static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
 // layer l of the stack on x rows of xn valid columns at stride ldx (token ids: rows of the table x)
 static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, const long long* tokens, const float* x, long ldx,
                         int xn, const float* w, const float* b, const float* state_in, float* state_out, float* h_top,
-                        int* err_flag, hipStream_t stream, const long long* parent_rows) {
+                        int* err_flag, hipStream_t stream, const long long* parent_rows, int groups) {
   const long lds = 2L * nlayers * H;
   DecodeLayerArgs a;
   a.tok = tokens;
@@ -305,6 +313,9 @@ static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, co
   a.rows = rows;
   a.H = H;
   a.parent = parent_rows;
+  CAPNET_REQUIRE(groups >= 1 && rows % groups == 0, "decode step: %d rows in %d groups", rows, groups);
+  a.rpg = rows / groups;
+  a.wgs = 4L * H * (a.kin + H);
   CAPNET_REQUIRE(a.kin + H <= kDecMaxK || (a.xvec && a.kin + H <= kDecWideMaxK), "decode step: K = %d + %d", a.kin, H);
   if (parent_rows) return cell == kCellLSTM ? launch_decode_layer<true, true>(a, stream) : launch_decode_layer<false, true>(a, stream);
   return cell == kCellLSTM ? launch_decode_layer<true, false>(a, stream) : launch_decode_layer<false, false>(a, stream);
@@ -312,13 +323,13 @@ static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, co
 
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows) {
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows, int groups) {
   const long lds = 2L * nlayers * H;
   for (int l = 0; l < nlayers; ++l) {
     const int rc = l == 0 ? decode_layer(cell, 0, nlayers, rows, H, V, tokens, x, E, E, wcat[0], beff[0], state_in, state_out,
-                                         h_top, err_flag, stream, parent_rows)
+                                         h_top, err_flag, stream, parent_rows, groups)
                           : decode_layer(cell, l, nlayers, rows, H, V, nullptr, state_out + (long)(2 * l - 2) * H, lds, H, wcat[l],
-                                         beff[l], state_in, state_out, h_top, err_flag, stream, parent_rows);
+                                         beff[l], state_in, state_out, h_top, err_flag, stream, parent_rows, groups);
     if (rc != kOk) return rc;
   }
   return kOk;
@@ -339,20 +350,25 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
                     const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
                     const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
-                    size_t slab_floats, int* err_flag, hipStream_t stream) {
-  const int nk = n * k;
+                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups) {
+  const int gk = n * k, nk = groups * gk;     // rows of one weight group (n images), rows in all
   const long lds = 2L * nlayers * H;
   float* z = reinterpret_cast<float*>(ws);
   float* xa = z + (size_t)nk * (A + C);
   float* escore = xa + (size_t)nk * (E + C);
-  // z of every row from its OWN previous h (layer 0's, slot 0 of state_in); the kernels read it at the parent's row
-  int rc = sgemm_splitk(false, true, nk, A + C, H, state_in, lds, wz, H, z, A + C, bz, 0, slab, slab_floats, stream);
-  if (rc == kOk) rc = att_beam_step_fwd(att1, feat, z, parent_rows, wf, bf, tokens, emb, V, E, n, k, P, A, C, escore, xa, err_flag, stream);
+  // z of every row from its OWN previous h (layer 0's, slot 0 of state_in); the kernels read it at the parent's row.
+  // One product per weight group on the group's rows: the call a search of that group alone makes
+  int rc = kOk;
+  for (int g = 0; g < groups && rc == kOk; ++g)
+    rc = sgemm_splitk(false, true, gk, A + C, H, state_in + (long)g * gk * lds, lds, wz + (long)g * (A + C) * H, H,
+                      z + (long)g * gk * (A + C), A + C, bz + (long)g * (A + C), 0, slab, slab_floats, stream);
+  if (rc == kOk) rc = att_beam_step_fwd(att1, feat, z, parent_rows, wf, bf, tokens, emb, V, E, groups * n, k, P, A, C, escore, xa,
+                                        err_flag, stream, n);
   if (rc == kOk) rc = decode_layer(cell, 0, nlayers, nk, H, V, nullptr, xa, E + C, E + C, wcat[0], beff[0], state_in, state_out,
-                                   h_top, err_flag, stream, parent_rows);
+                                   h_top, err_flag, stream, parent_rows, groups);
   for (int l = 1; l < nlayers && rc == kOk; ++l)
     rc = decode_layer(cell, l, nlayers, nk, H, V, nullptr, state_out + (long)(2 * l - 2) * H, lds, H, wcat[l], beff[l], state_in,
-                      state_out, h_top, err_flag, stream, parent_rows);
+                      state_out, h_top, err_flag, stream, parent_rows, groups);
   return rc;
 }
 

@@ -265,12 +265,13 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups) {
+  n *= groups;   // beam groups: weight groups x images, group-major
   return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
                    lengths, steps_run, s,
                    [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
                      return stacked_decode_step(cell, nlayers, n * k, E, H, V, tok, emb, wcat, beff, sin, sout, h_top, err_flag, s,
-                                                parent);
+                                                parent, groups);
                    });
 }
 
@@ -287,13 +288,14 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s) {
-  void* step_ws = reinterpret_cast<char*>(ws) + beam_decode_layout(nlayers, n, k, H, V, max_steps).total;
-  return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
+                    hipStream_t s, int groups) {
+  const int nq = groups * n;   // beam groups: weight groups x images, group-major
+  void* step_ws = reinterpret_cast<char*>(ws) + beam_decode_layout(nlayers, nq, k, H, V, max_steps).total;
+  return beam_loop(nlayers, nq, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
                    lengths, steps_run, s,
                    [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
                      return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
-                                            sin, parent, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
+                                            sin, parent, sout, h_top, step_ws, slab, slab_floats, err_flag, s, groups);
                    });
 }
 

@@ -13,6 +13,9 @@ mode selects, the layout of their beam state, their weight fold.
   * factored_step: U_g(S_g(V_g(x))) + W_g(h) per gate and the pointwise cell, on torch.cat. DecoderFactoredLSTM's own
     forward_step accumulates into column blocks instead and stays where it is.
   * fold_factored: a factored layer's chain folded into the decode step's [Weff | W] and beff.
+  * check_styles / fold_styles / plain_styles / att_styles: sample_styles of the factored decoders -- every requested mode
+    folded into its slice of one buffer per layer and ONE grouped search (ops.beam_decode / ops.att_beam_decode with
+    groups=len(modes)) over modes x images x k rows; a loop of sample_batch(one_call=True) where that does not serve.
   * stack_stepper / cell_stepper / pack_cell / as_state / input_width: one step of a stack over a [rows, 2L, H] state
     (slot 2l = h of layer l, 2l+1 = its c), on capnet_stacked_decode_step or composed. CAPNET_NO_FUSED_DECODE_STEP=1
     (read here, at every stepper built) takes the composed step, which also serves the shapes the kernel does not take.
@@ -221,14 +224,18 @@ def pack_cell(cell, kin):
     return wcat, beff
 
 
-def fold_factored(V, S, U, W):
+def fold_factored(V, S, U, W, out=None):
     """(wcat, beff) of one factored layer for capnet_stacked_decode_step from its gates' Linears (i, f, o, c~): wcat
     [4H, kin + H] = [U_g S_g V_g, zero columns up to kin | W_g] (kin: the layer's input width rounded up to 16), beff
-    [4H] = U_g (S_g bV_g + bS_g) + bU_g + bW_g. Products on the GPU (capnet_sgemm)."""
+    [4H] = U_g (S_g bV_g + bS_g) + bU_g + bW_g. Products on the GPU (capnet_sgemm). out: (wcat, beff) to fold into --
+    one weight group's slices of fold_styles' buffers, wcat zero where the fold writes nothing."""
     H, n_in, dev = W[0].weight.shape[0], V[0].weight.shape[1], W[0].weight.device
     kin = input_width(n_in)
-    wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
-    beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
+    if out is not None:
+        wcat, beff = out
+    else:
+        wcat = torch.zeros((4 * H, kin + H), dtype=torch.float32, device=dev)
+        beff = torch.empty(4 * H, dtype=torch.float32, device=dev)
     with torch.no_grad():
         for g in range(4):
             blk, bb = wcat[g * H:(g + 1) * H], beff[g * H:(g + 1) * H]
@@ -238,6 +245,106 @@ def fold_factored(V, S, U, W):
             ops.sgemm(sb, U[g].weight, transB=True, bias=U[g].bias, out=bb.view(1, H))
             bb += W[g].bias
     return wcat, beff
+
+
+# ---- every style at once ----------------------------------------------------------------------------
+def check_styles(modes, check_mode):
+    """`modes` of a sample_styles call as a tuple: a non-empty sequence of distinct mode names. check_mode(name) is the
+    class's own check: an unknown name behaves as in its sample()."""
+    if isinstance(modes, str):
+        modes = (modes,)
+    modes = tuple(modes)
+    for m in modes:
+        check_mode(m)
+    if not modes or len(set(modes)) != len(modes):
+        raise ValueError("modes must be a non-empty sequence of distinct mode names, not %r" % (modes,))
+    return modes
+
+
+def fold_styles(layer_mods, num_layers, modes):
+    """[(wcat [G, 4H, kin_l + H], beff [G, 4H])] per layer for the grouped decode step: fold_factored of layer_mods(l,
+    mode) -> (V, S, U, W) for every requested mode, each into its slice of ONE buffer per layer."""
+    packed = []
+    with torch.no_grad():
+        for l in range(num_layers):
+            mods = [layer_mods(l, m) for m in modes]
+            V, _, _, W = mods[0]
+            H, kin, dev = W[0].weight.shape[0], input_width(V[0].weight.shape[1]), W[0].weight.device
+            wcat = torch.zeros((len(modes), 4 * H, kin + H), dtype=torch.float32, device=dev)
+            beff = torch.empty((len(modes), 4 * H), dtype=torch.float32, device=dev)
+            for g, md in enumerate(mods):
+                fold_factored(*md, out=(wcat[g], beff[g]))
+            packed.append((wcat, beff))
+    return packed
+
+
+def styles_images(n, G, k, width, device):
+    """How many of n images one grouped search takes: its G n k rows of `width` floats (the logits, the attention z) must
+    fit the split-K slab the single-mode searches use too. 0: take the loop. (No row count above which the loop wins
+    was found: at 1280 rows the grouped search still takes 0.63 - 0.71 of the loop's time)"""
+    return min(n, ops.splitk_slab(device).numel() // (G * k * width))
+
+
+def plain_styles(dec, layer_mods, num_layers, emb, C, n, k, start_token, end_token, modes, poll_every, loop):
+    """sample_styles of a plain factored decoder -> {mode: [n token lists]}: every mode's chain folded into one buffer per
+    layer (fold_styles) and ONE ops.beam_decode(groups=len(modes)) over modes x images x k rows (the images in as few
+    chunks as the slab allows). loop(mode) -> sample_batch(mode=mode, one_call=True): taken mode by mode where the fused
+    step does not serve the shape, CAPNET_NO_FUSED_DECODE_STEP=1 is set, or one mode is asked for."""
+    G, V, E = len(modes), dec.vocab_size, emb.shape[1]
+    with torch.no_grad():
+        per = styles_images(n, G, k, V, emb.device) if G > 1 else 0
+        if per < 1 or not fused_decode_step(num_layers, E, dec.hidden_size) or \
+                not ops.beam_decode_supported(E, dec.hidden_size, k, V, num_layers):
+            return {m: loop(m) for m in modes}
+        packed = fold_styles(layer_mods, num_layers, modes)
+        wcat, beff = [w for w, _ in packed], [b for _, b in packed]
+        out = {m: [] for m in modes}
+        for i0 in range(0, n, per):
+            ni = min(per, n - i0)
+            seqs = ops.beam_decode(ops.CELL_FACTORED, wcat, beff, emb.detach(), C.weight, C.bias, ni, k, dec.max_seq_length + 1,
+                                   start_token, end_token, poll_every, groups=G)
+            for g, m in enumerate(modes):
+                out[m] += seqs[g * ni:(g + 1) * ni]
+    return out
+
+
+def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token, modes, poll_every, loop):
+    """sample_styles of an attention decoder -> {mode: [n token lists]}: ONE ops.att_beam_decode(groups=len(modes)) over
+    modes x images x k rows. Per mode: its folded chain (fold_styles), its Attention module's encoder_att(feat) (att1
+    [G n, P, A]), [decoder_att; f_beta] and full_att; shared: the map feat [n, P, C], the embedding, the projection and
+    the initial state (init_h / init_c of every layer), repeated per mode. loop(mode) as plain_styles'."""
+    G, n, Cdim = len(modes), features.size(0), features.size(-1)
+    E, A, V = dec.B.weight.shape[1], dec.attention_size, dec.vocab_size
+    with torch.no_grad():
+        dev = dec.B.weight.device
+        feat = features.reshape(n, -1, Cdim).to(dev).contiguous()
+        P = feat.size(1)
+        per = styles_images(n, G, k, max(V, A + Cdim), dev) if G > 1 else 0
+        if per < 1 or not att_stack_supported(dec, E, Cdim, P, k, num_layers):
+            return {m: loop(m) for m in modes}
+        atts = [dec._mode_modules(m)[0] for m in modes]
+        packed = fold_styles(layer_mods, num_layers, modes)
+        wcat, beff = [w for w, _ in packed], [b for _, b in packed]
+        # [decoder_att ; f_beta] per mode (f_beta is shared: replicated), full_att per mode
+        wz = torch.stack([torch.cat([a.decoder_att.weight, dec.f_beta.weight], 0) for a in atts]).contiguous()
+        bz = torch.stack([torch.cat([a.decoder_att.bias, dec.f_beta.bias], 0) for a in atts]).contiguous()
+        wf = torch.stack([a.full_att.weight.reshape(-1) for a in atts]).contiguous()
+        bf = torch.cat([a.full_att.bias.reshape(-1) for a in atts]).contiguous()
+        out = {m: [] for m in modes}
+        for i0 in range(0, n, per):
+            fi = feat[i0:i0 + per]
+            ni = fi.size(0)
+            att1 = torch.cat([a.encoder_att(fi.reshape(ni * P, Cdim)).reshape(ni, P, A) for a in atts], 0).contiguous()
+            img = torch.arange(ni, device=dev).repeat_interleave(k)
+            h0, c0 = dec.init_hidden_state(fi)
+            upper, _ = dec._upper_beam(fi, img, modes[0])          # init_h{l} / init_c{l}: the same for every mode
+            entries = (h0.index_select(0, img), c0.index_select(0, img)) + tuple(upper)
+            state = torch.cat([t.unsqueeze(1) for t in entries], 1).repeat(G, 1, 1).contiguous()
+            seqs = ops.att_beam_decode(ops.CELL_FACTORED, att1, fi, dec.B.weight, wz, bz, wf, bf, wcat, beff, dec.C.weight,
+                                       dec.C.bias, state, k, dec.max_seq_length + 1, start_token, end_token, poll_every, groups=G)
+            for g, m in enumerate(modes):
+                out[m] += seqs[g * ni:(g + 1) * ni]
+    return out
 
 
 def pack_cells(cells, E):

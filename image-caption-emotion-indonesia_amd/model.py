@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr, ptr_array
-from .decode import beam_decode, fold_factored, fused_decode_step, plain_stack, zero_state
+from .decode import beam_decode, check_styles, fold_factored, fused_decode_step, plain_stack, plain_styles, zero_state
 
 random.seed(0)  # stylenet/model.py:7
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # stylenet/model.py:8
@@ -658,3 +658,16 @@ class DecoderFactoredLSTM(nn.Module):
         sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(n * k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
+
+    def sample_styles(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0):
+        """sample_batch(one_call=True) in every style of `modes` at once -> {mode: [n token lists]}, each list equal to
+        sample_batch(features, ..., mode=mode, one_call=True): ONE search over len(modes) x n x k rows on the grouped
+        decode step (capnet_beam_decode_groups), every mode's chain folded into its slice of one buffer. As in sample(),
+        the image is not an input. modes: a non-empty sequence of distinct mode names (an unknown one as in sample()).
+        Where the fused step does not serve (the shape, CAPNET_NO_FUSED_DECODE_STEP=1) the modes are decoded one
+        sample_batch(one_call=True) after the other. poll_every: capnet.decode.beam_decode's."""
+        modes = check_styles(modes, self._S)
+        return plain_styles(self, lambda l, m: _layer_mods(self, "", m), 1, self.B.weight, self.C, features.size(0), k,
+                            start_token, end_token, modes, poll_every,
+                            lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
+                                                        poll_every=poll_every))

@@ -224,6 +224,25 @@ class DecoderFactoredLSTMAtt(nn.Module):
         n = features.size(0)
         return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
 
+    def _style_layers(self):
+        """The layers sample_styles folds: one here (capnet.stacked_att: num_layers)."""
+        return 1
+
+    def sample_styles(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0):
+        """sample_batch(one_call=True) in every style of `modes` at once -> {mode: [n token lists]}, each list equal to
+        sample_batch(features, ..., mode=mode, one_call=True): ONE search over len(modes) x n x k rows
+        (capnet_att_beam_decode_groups). A mode brings its folded chains and its Attention module (encoder_att(feat) per
+        mode, [decoder_att; f_beta], full_att); the maps, the embedding, f_beta, the projection and the initial state are
+        shared, the maps read in place by every mode. modes: a non-empty sequence of distinct mode names (an unknown one
+        as in sample()). A shape capnet_att_beam_decode does not take, an embedding width that is no multiple of 4 or
+        CAPNET_NO_FUSED_DECODE_STEP=1: the modes are decoded one sample_batch(one_call=True) after the other.
+        poll_every: capnet.decode.beam_decode's."""
+        modes = decode.check_styles(modes, self._mode_modules)
+        return decode.att_styles(self, lambda l, m: _layer_mods(self, "" if l == 0 else str(l), m), self._style_layers(),
+                                 features, k, start_token, end_token, modes, poll_every,
+                                 lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
+                                                             poll_every=poll_every))
+
     def forward(self,
                 captions,
                 lengths,

@@ -365,6 +365,7 @@ def lstm_cell(pre, c_prev, cell=0):
 
 
 DECODE_HIDDEN = (64, 128, 256, 512, 1024)
+MAX_GROUPS = 8        # weight groups of the grouped decode step (capnet_*_groups)
 
 
 def stacked_decode_supported(E, H):
@@ -372,17 +373,41 @@ def stacked_decode_supported(E, H):
     return E >= 1 and H in DECODE_HIDDEN and (E + 15) // 16 * 16 + H <= 2048
 
 
-def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, parent_rows=None):
+def _check_groups(who, groups):
+    groups = int(groups)
+    if not 1 <= groups <= MAX_GROUPS:
+        raise CapnetError("%s: groups %d (1..%d)" % (who, groups, MAX_GROUPS))
+    return groups
+
+
+def _check_layer_weights(who, wcat, beff, groups, H, kin0):
+    """wcat[l] [4H, kin_l + H] and beff[l] [4H], with a leading [groups] dimension when groups > 1."""
+    lead = () if groups == 1 else (groups,)
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = kin0 if l == 0 else H
+        if tuple(w.shape) != lead + (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != lead + (4 * H,) \
+                or (lead and not b.is_contiguous()):
+            raise CapnetError("%s: layer %d weights must be %s[4H, %d] and %s[4H]"
+                              % (who, l, "[groups]" if lead else "", kin + H, "[groups]" if lead else ""))
+
+
+def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, parent_rows=None, groups=1):
     """One inference step of every layer of a stacked LSTM (capnet_stacked_decode_step, or _cell for the LSTM cell: one
     launch per layer). state [rows, 2L, H] (slot 2l = h of layer l, 2l+1 = c); wcat[l] [4H, kin_l + H] = [folded chain |
     W] (factored) or [weight_ih | weight_hh] (LSTM cell), gate blocks i, f, o, c~; beff[l] [4H]; x: the embedding table
     [V, E] when `tokens` (int64 [rows]) is given, else layer 0's inputs [rows, E]. parent_rows (int64 [rows]): the step on
     state.index_select(0, parent_rows) without that copy (capnet_stacked_decode_step_gather).
+    groups > 1 (capnet_stacked_decode_step_groups): the rows are `groups` equal blocks, group-major, and block g runs on
+    wcat[l][g] / beff[l][g] -- wcat[l] [groups, 4H, kin_l + H], beff[l] [groups, 4H] -- in the same launches; each block's
+    rows equal the step of that block alone on its weights, bit for bit.
     Returns (top-layer h [rows, H], the new state [rows, 2L, H])."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("stacked_decode_step: unknown cell %r" % (cell,))
+    groups = _check_groups("stacked_decode_step", groups)
     _need_cuda(state, x, tokens, *wcat, *beff)
     rows, L2, H = state.shape
+    if rows % groups:
+        raise CapnetError("stacked_decode_step: %d rows in %d groups" % (rows, groups))
     nl = L2 // 2
     if L2 != 2 * nl or len(wcat) != nl or len(beff) != nl:
         raise CapnetError("stacked_decode_step: state [rows, 2L, H] and L weight pairs")
@@ -394,10 +419,7 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, p
             raise CapnetError("stacked_decode_step: tokens must be int64 [rows]")
     elif x.shape[0] != rows:
         raise CapnetError("stacked_decode_step: inputs must be [rows, E]")
-    for l, (w, b) in enumerate(zip(wcat, beff)):
-        kin = (E + 15) // 16 * 16 if l == 0 else H
-        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
-            raise CapnetError("stacked_decode_step: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    _check_layer_weights("stacked_decode_step", wcat, beff, groups, H, (E + 15) // 16 * 16)
     out = torch.empty_like(state)
     top = torch.empty((rows, H), dtype=torch.float32, device=state.device)
     if parent_rows is not None:
@@ -405,6 +427,13 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, p
         parent_rows = _c(parent_rows)
         if parent_rows.dtype != torch.int64 or parent_rows.numel() != rows:
             raise CapnetError("stacked_decode_step: parent_rows must be int64 [rows]")
+    if groups > 1:
+        check(_lib.lib().capnet_stacked_decode_step_groups(
+            cell, nl, groups, rows // groups, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens), ptr(x),
+            ptr_array(wcat), ptr_array(beff), ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(err_flag(state.device)),
+            current_stream()), "capnet_stacked_decode_step_groups")
+        return top, out
+    if parent_rows is not None:
         check(_lib.lib().capnet_stacked_decode_step_gather(
             cell, nl, rows, E, H, x.shape[0] if tokens is not None else 0, ptr(tokens), ptr(x), ptr_array(wcat),
             ptr_array(beff), ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(err_flag(state.device)), current_stream()),
@@ -495,15 +524,19 @@ def beam_decode_supported(E, H, k, V, num_layers):
 
 
 def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, poll_every=0, state=None,
-                return_steps=False):
+                return_steps=False, groups=1):
     """The beam search of a plain stack in ONE C call (capnet_beam_decode): n images x k beams, at most max_steps steps of
     (gathered decode step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then capnet_beam_finish.
     cell / wcat / beff: as stacked_decode_step; emb [V, E]; Cw [V, H], Cb [V] or None; state: [n k, 2L, H] or None for
     zeros; poll_every as capnet.beam.beam_search_device. The workspace is cached per (device, shape). Sequences, lengths
     and the device's error word come to the host in one copy; a set error word raises (check_device_errors).
+    groups > 1 (capnet_beam_decode_groups): the searches of `groups` weight groups over the n images in the same launches,
+    wcat[l] [groups, 4H, kin_l + H], beff[l] [groups, 4H]; state [groups n k, 2L, H]; groups n token lists come back,
+    group-major (list g n + i: group g, image i).
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("beam_decode: unknown cell %r" % (cell,))
+    groups = _check_groups("beam_decode", groups)
     _need_cuda(emb, Cw, Cb, state, *wcat, *beff)
     emb, Cw = _c(emb.detach()), _c(Cw.detach())
     Cb = None if Cb is None else _c(Cb.detach())
@@ -515,11 +548,9 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
                           % (E, H, V, k, nl, n, T))
     if Cb is not None and Cb.numel() != V:
         raise CapnetError("beam_decode: Cb must be [V]")
-    for l, (w, b) in enumerate(zip(wcat, beff)):
-        kin = (E + 15) // 16 * 16 if l == 0 else H
-        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
-            raise CapnetError("beam_decode: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    _check_layer_weights("beam_decode", wcat, beff, groups, H, (E + 15) // 16 * 16)
     dev = emb.device
+    n_img, n = n, groups * n       # from here on n counts the beam groups
     if state is not None:
         state = _c(state.detach())
         if tuple(state.shape) != (n * k, 2 * nl, H):
@@ -537,10 +568,14 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     tail = packed[n * SL:].view(torch.int32)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(emb), ptr_array(wcat),
-                               ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
-                               int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag),
-                               current_stream()), "capnet_beam_decode")
+    tail_args = (ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
+                 int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream())
+    if groups > 1:
+        check(L.capnet_beam_decode_groups(cell, nl, groups, n_img, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
+              "capnet_beam_decode_groups")
+    else:
+        check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
+              "capnet_beam_decode")
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)
@@ -557,26 +592,29 @@ def att_decode_supported(E, Cdim, H, A, P, k, num_layers):
     return bool(_lib.lib().capnet_att_decode_supported(int(E), int(Cdim), int(H), int(A), int(P), int(k), int(num_layers)))
 
 
-def _att_decode_args(who, cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state):
-    """The checked operands the two attention-decode calls share -> (tensors..., dims n, P, A, Cdim, E, H, V, nl)."""
+def _att_decode_args(who, cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state, groups=1):
+    """The checked operands the two attention-decode calls share -> (tensors..., dims n, P, A, Cdim, E, H, V, nl); n counts
+    the images. groups > 1: att1 [groups n, P, A], feat [n, P, C], wz [groups, A + C, H], bz [groups, A + C], w_full
+    [groups, A], b_full [groups], the layers' weights with a leading [groups], state [groups n k, 2L, H]."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("%s: unknown cell %r" % (who, cell))
     _need_cuda(att1, feat, emb, wz, bz, w_full, b_full, state, *wcat, *beff)
     att1, feat, emb, wz, bz = _c(att1.detach()), _c(feat.detach()), _c(emb.detach()), _c(wz.detach()), _c(bz.detach())
     wf, bf = _c(w_full.detach()).reshape(-1), _c(b_full.detach()).reshape(-1)
     state = _c(state.detach())
-    n, P, A = att1.shape
+    nq, P, A = att1.shape
+    n = feat.shape[0]
     Cdim, (V, E), nl, k = feat.shape[2], emb.shape, len(wcat), int(k)
     H = state.shape[2]
-    if tuple(feat.shape[:2]) != (n, P) or tuple(wz.shape) != (A + Cdim, H) or bz.numel() != A + Cdim or wf.numel() != A:
-        raise CapnetError("%s: att1 [n, P, A], feat [n, P, C], wz [A + C, H], bz [A + C], w_full [A]" % who)
-    if len(beff) != nl or k < 1 or tuple(state.shape) != (n * k, 2 * nl, H) or not att_decode_supported(E, Cdim, H, A, P, k, nl):
+    lead = () if groups == 1 else (groups,)
+    if nq != groups * n or feat.shape[1] != P or tuple(wz.shape) != lead + (A + Cdim, H) or bz.numel() != groups * (A + Cdim) \
+            or wf.numel() != groups * A or bf.numel() != groups:
+        raise CapnetError("%s: att1 [n, P, A], feat [n, P, C], wz [A + C, H], bz [A + C], w_full [A]%s"
+                          % (who, " (groups: att1 [groups n, P, A], [groups] in front of wz, bz, w_full, b_full)" if lead else ""))
+    if len(beff) != nl or k < 1 or tuple(state.shape) != (nq * k, 2 * nl, H) or not att_decode_supported(E, Cdim, H, A, P, k, nl):
         raise CapnetError("%s: unsupported shape (E=%d, C=%d, H=%d, A=%d, P=%d, k=%d, %d layers, state %r)"
                           % (who, E, Cdim, H, A, P, k, nl, tuple(state.shape)))
-    for l, (w, b) in enumerate(zip(wcat, beff)):
-        kin = (E + Cdim + 15) // 16 * 16 if l == 0 else H
-        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
-            raise CapnetError("%s: layer %d weights must be [4H, %d] and [4H]" % (who, l, kin + H))
+    _check_layer_weights(who, wcat, beff, groups, H, (E + Cdim + 15) // 16 * 16)
     return att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl)
 
 
@@ -586,16 +624,19 @@ def att_decode_step_workspace(n, k, P, A, Cdim, E, device):
 
 
 def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, beff, state, cell=CELL_FACTORED, parent_rows=None,
-                    workspace=None):
+                    workspace=None, groups=1):
     """One beam step of an attention decoder without the projection (capnet_att_decode_step): n images x k fixed slots, row
     r on the maps of image r // k. att1 [n, P, A] = encoder_att(feat), feat [n, P, C]: per image, never per row. wz [A + C,
     H] / bz = [decoder_att; f_beta]; w_full / b_full: full_att; wcat / beff: capnet.decode.pack_cell / fold_factored per
     layer, layer 0 reading E + C columns; state [n k, 2L, H]; tokens int64 [n k]; parent_rows int64 [n k]: the step on
     state.index_select(0, parent_rows) without that copy. workspace: att_decode_step_workspace(...) or None.
+    groups > 1 (capnet_att_decode_step_groups): `groups` weight groups on the same n images, operands as _att_decode_args
+    says, workspace att_decode_step_workspace(groups n, ...); each group's rows equal the step of that group alone.
     Returns (top-layer h [n k, H], the new state)."""
+    groups = _check_groups("att_decode_step", groups)
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
-        "att_decode_step", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state)
-    rows, dev = n * int(k), state.device
+        "att_decode_step", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state, groups)
+    rows, dev = groups * n * int(k), state.device
     _need_cuda(tokens, parent_rows, workspace)
     for name, idx in (("tokens", tokens), ("parent_rows", parent_rows)):
         if idx is not None and (idx.dtype != torch.int64 or idx.numel() != rows or not idx.is_contiguous()):
@@ -604,17 +645,20 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
         raise CapnetError("att_decode_step: tokens are required")
     L = _lib.lib()
     if workspace is None:
-        workspace = att_decode_step_workspace(n, int(k), P, A, Cdim, E, dev)
+        workspace = att_decode_step_workspace(groups * n, int(k), P, A, Cdim, E, dev)
     if workspace.dtype != torch.float32 or not workspace.is_contiguous() or \
-            workspace.numel() * 4 < L.capnet_att_decode_step_ws_bytes(n, int(k), P, A, Cdim, E):
+            workspace.numel() * 4 < L.capnet_att_decode_step_ws_bytes(groups * n, int(k), P, A, Cdim, E):
         raise CapnetError("att_decode_step: workspace too small")
     slab = splitk_slab(dev)
     out = torch.empty_like(state)
     top = torch.empty((rows, H), dtype=torch.float32, device=dev)
-    check(L.capnet_att_decode_step(cell, nl, n, int(k), P, A, Cdim, E, H, V, ptr(att1), ptr(feat), ptr(tokens), ptr(emb), ptr(wz),
-                                   ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(state), ptr(parent_rows),
-                                   ptr(out), ptr(top), ptr(workspace), ptr(slab), slab.numel(), ptr(err_flag(dev)),
-                                   current_stream()), "capnet_att_decode_step")
+    args = (n, int(k), P, A, Cdim, E, H, V, ptr(att1), ptr(feat), ptr(tokens), ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf),
+            ptr_array(wcat), ptr_array(beff), ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(workspace), ptr(slab),
+            slab.numel(), ptr(err_flag(dev)), current_stream())
+    if groups > 1:
+        check(L.capnet_att_decode_step_groups(cell, nl, groups, *args), "capnet_att_decode_step_groups")
+    else:
+        check(L.capnet_att_decode_step(cell, nl, *args), "capnet_att_decode_step")
     return top, out
 
 
@@ -622,15 +666,18 @@ _att_beam_decode_ws = {}
 
 
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
-                    end_token, poll_every=0, return_steps=False):
+                    end_token, poll_every=0, return_steps=False, groups=1):
     """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
     steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
     capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
     (init_h / init_c per layer and image, each image's row k times). The workspace is cached per (device, shape).
     Sequences, lengths and the device's error word come to the host in one copy; a set error word raises
-    (check_device_errors). Returns the n token lists; with return_steps, (lists, the steps issued)."""
+    (check_device_errors). groups > 1 (capnet_att_beam_decode_groups): the searches of `groups` weight groups over the same n
+    images in the same launches, operands as att_decode_step's; groups n token lists come back, group-major.
+    Returns the n token lists; with return_steps, (lists, the steps issued)."""
+    groups = _check_groups("att_beam_decode", groups)
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
-        "att_beam_decode", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state)
+        "att_beam_decode", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state, groups)
     _need_cuda(Cw, Cb)
     Cw = _c(Cw.detach())
     Cb = None if Cb is None else _c(Cb.detach())
@@ -639,6 +686,7 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
         raise CapnetError("att_beam_decode: Cw [V, H], Cb [V], k <= V, max_steps >= 1 (V=%d, k=%d, max_steps=%d)" % (V, k, T))
     dev = emb.device
     L = _lib.lib()
+    n_img, n = n, groups * n       # from here on n counts the beam groups
     key = (dev.index or 0, nl, n, k, P, A, Cdim, E, H, V, T)
     ws = _att_beam_decode_ws.get(key)
     if ws is None:
@@ -652,11 +700,13 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     tail = packed[n * SL:].view(torch.int32)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(L.capnet_att_beam_decode(cell, nl, n, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat),
-                                   ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw),
-                                   ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(), int(poll_every), ptr(packed),
-                                   C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
-          "capnet_att_beam_decode")
+    args = (n_img, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz),
+            ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
+            int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream())
+    if groups > 1:
+        check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
+    else:
+        check(L.capnet_att_beam_decode(cell, nl, *args), "capnet_att_beam_decode")
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)

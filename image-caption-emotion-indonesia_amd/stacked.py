@@ -35,7 +35,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .decode import as_state, beam_decode, factored_step, fold_factored, plain_stack, stack_stepper
+from .decode import as_state, beam_decode, check_styles, factored_step, fold_factored, plain_stack, plain_styles, stack_stepper
 from .model import Embedding as _Embedding, Linear as _Linear, _layer_mods, _seq_cfg
 
 MODES = ("factual", "happy", "sad", "angry")
@@ -153,6 +153,20 @@ class StackedFactoredLSTM(nn.Module):
         each equal to sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(n * k, mode), n, k, start_token, end_token, on_device, poll_every, one_call)
+
+    def sample_styles(self, features, start_token, end_token, k=5, modes=MODES, poll_every=0):
+        """sample_batch(one_call=True) in every style of `modes` at once -> {mode: [n token lists]}, each list equal to
+        sample_batch(features, ..., mode=mode, one_call=True). The modes differ only in the folded chains, so the search
+        runs ONCE over len(modes) x n x k rows on the grouped decode step (capnet_beam_decode_groups), every mode's chain
+        folded into its slice of one buffer per layer. As in sample(), the image is not an input: the styles of a plain
+        factored decoder differ, the images' captions do not. modes: a non-empty sequence of distinct names of MODES (an
+        unknown one as in sample()). Where the fused step does not serve (the shape, CAPNET_NO_FUSED_DECODE_STEP=1) the
+        modes are decoded one sample_batch(one_call=True) after the other. poll_every: capnet.decode.beam_decode's."""
+        modes = check_styles(modes, _check_mode)
+        return plain_styles(self, self._mods, self.num_layers, self.B.weight, self.C, features.size(0), k, start_token, end_token,
+                            modes, poll_every,
+                            lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
+                                                        poll_every=poll_every))
 
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, captions, lengths, features=None, teacher_forcing_ratio=0.8, mode="factual", tf_mask=None):

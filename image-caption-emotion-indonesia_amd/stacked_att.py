@@ -111,6 +111,9 @@ class StackedFactoredLSTMAtt(DecoderFactoredLSTMAtt):
         return super(StackedFactoredLSTMAtt, self)._fold(mode) + [fold_factored(*self._upper_mods(l, mode))
                                                                   for l in range(1, self.num_layers)]
 
+    def _style_layers(self):
+        return self.num_layers
+
     def _upper_beam(self, feat, img, mode):
         """The beam state is every layer's (h, c): the upper layers' init_h{l} / init_c{l}(mean feature), tiled by image
         index, and their step on the entries after layer 0's."""

@@ -465,3 +465,32 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
         for i, b in enumerate(out):
             print('BLEU-%d' % (i + 1), b)
     return out
+
+
+MODES = ("factual", "happy", "sad", "angry")
+
+
+def evaluate_styles(encoder, decoder, vocab, data_loader, modes=MODES, k=5, device=None):
+    """evaluate() in every style of `modes` on ONE pass over the loader -> {mode: (bleu_1, bleu_2, bleu_3, bleu_4)}, each
+    tuple equal to evaluate(..., mode=mode, one_call=True). Per loader batch the encoder runs once (evaluate per mode runs
+    it len(modes) times on the same images) and the decoder makes one sample_styles call. An image's references
+    (the loader's all_captions entry) are a list of captions, shared by every mode, or a dict mode -> list."""
+    decoder.eval()
+    encoder.eval()
+    device = device or next(decoder.parameters()).device
+    start, end = vocab.word2idx['<start>'], vocab.word2idx['<end>']
+    modes = tuple(modes)
+    references, hypotheses = {m: [] for m in modes}, {m: [] for m in modes}
+    for images, captions, lengths, all_captions in data_loader:
+        with torch.no_grad():
+            features = encoder(images.to(device))
+        styled = decoder.sample_styles(features, start_token=start, end_token=end, k=k, modes=modes)
+        for m in modes:
+            for sampled_ids, caps in zip(styled[m], all_captions):
+                caps = caps[m] if isinstance(caps, dict) else caps
+                references[m].append([[int(w) for w in (c.tolist() if hasattr(c, "tolist") else c)] for c in caps])
+                hypotheses[m].append([int(w) for w in sampled_ids])
+    ops.check_device_errors()
+    return {m: tuple(corpus_bleu(references[m], hypotheses[m], weights=w)
+                     for w in ((1, 0, 0, 0), (0.5, 0.5, 0, 0), (0.33, 0.33, 0.33, 0), (0.25, 0.25, 0.25, 0.25)))
+            for m in modes}

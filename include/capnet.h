@@ -552,6 +552,18 @@ int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, in
                                       const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
                                       int* err_flag, capnet_stream_t stream);
 
+/* capnet_stacked_decode_step_gather for `groups` weight groups in the same launches (every style of a factored decoder at
+ * once): rows = groups x rows_per_group, group-major -- group g owns rows g rows_per_group .. (g + 1) rows_per_group - 1
+ * -- and its rows run on ITS weights: wcat[l] is [groups][4H][kin_l + H] and beff[l] [groups][4H], one device buffer per
+ * layer. The grid of a layer's launch is (H / 4, groups); a 16-row tile never reaches into the next group. Row r of group
+ * g is, bit for bit, the row of capnet_stacked_decode_step_gather on group g's rows and weights alone. tokens, x,
+ * parent_rows, state_in, state_out and h_top cover all the rows; a parent is checked against [0, rows), not against its
+ * group. 1 <= groups <= 8; groups = 1 is exactly capnet_stacked_decode_step_gather. Same shapes and checks otherwise. */
+int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int rows_per_group, int E, int H, int V,
+                                      const long long* tokens, const float* x, const float* const* wcat,
+                                      const float* const* beff, const float* state_in, const long long* parent_rows,
+                                      float* state_out, float* h_top, int* err_flag, capnet_stream_t stream);
+
 /* tokens[r] = the FIRST argmax over v of h[r] . w[v] + b[v], r < rows: the vocabulary projection (nn.Linear: w [V][H],
  * b [V] or NULL) and the row argmax in one launch, fp32 throughout, the logits never stored. A -inf or NaN logit is never
  * picked and a row with nothing to pick yields 0, as capnet_argmax_rows. rows >= 1, V >= 1, H in {64, 128, 256, 512,
@@ -603,6 +615,19 @@ int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V,
                        size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                        capnet_stream_t stream);
 
+/* capnet_beam_decode over groups x n beam groups, beam group q = g n + i (weight group g, image i) at rows q k .. q k + k -
+ * 1 and on group g's weights (capnet_stacked_decode_step_groups with rows_per_group = n k: wcat[l] [groups][4H][kin_l + H],
+ * beff[l] [groups][4H]). emb, Cw, Cb and the beam bookkeeping are shared: the vocabulary projection is one product over all
+ * groups n k rows, so its kernel choice -- and the last bit of a logit -- may differ from a search of one group alone.
+ * workspace: capnet_beam_decode_ws_bytes(nlayers, groups n, ...); slab: at least groups n k V floats; seqs int64
+ * [groups n][max_steps + 2], lengths int32 [groups n]; state0 [groups n k][2 nlayers][H] or NULL. 1 <= groups <= 8; groups =
+ * 1 is exactly capnet_beam_decode. Every bad argument is refused before any launch. */
+int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                              long long start_token, long long end_token, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                              float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                              int* err_flag, capnet_stream_t stream);
+
 /* One beam step of an attention decoder (DecoderFactoredLSTMAtt / DecoderRNNAtt and their stacked forms) without the
  * vocabulary projection, for n images x k fixed slots (row r belongs to image r / k), on `stream`, in this order:
  *   1. z [n k][A + C] = h_prev . wz^T + bz, wz = [decoder_att; f_beta] stacked ([A + C][H]), h_prev = layer 0's h of every
@@ -630,6 +655,22 @@ int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, in
                            const float* state_in, const long long* parent_rows, float* state_out, float* h_top,
                            void* workspace, float* slab, size_t slab_floats, int* err_flag, capnet_stream_t stream);
 
+/* capnet_att_decode_step for `groups` weight groups on the same n images (every style at once): groups x n beam groups,
+ * beam group q = g n + i at rows q k .. q k + k - 1. att1 is [groups n][P][A] (each group has its own encoder_att), feat
+ * stays [n][P][C] (beam group q reads image q % n: the map is not copied per group), wz [groups][A + C][H], bz
+ * [groups][A + C], w_full [groups][A], b_full [groups], wcat[l] [groups][4H][kin_l + H], beff[l] [groups][4H]. z is one
+ * capnet_sgemm_splitk product per group on the group's n k rows -- the call a step of that group alone makes, so z, xa,
+ * the state and h_top of group g's rows equal capnet_att_decode_step's on that group bit for bit. tokens, parent_rows, the
+ * states and h_top cover all groups n k rows; a parent is checked against all of them. workspace:
+ * capnet_att_decode_step_ws_bytes(groups n, ...); slab: at least groups n k max(V, A + C) floats. 1 <= groups <= 8;
+ * groups = 1 is exactly capnet_att_decode_step. */
+int capnet_att_decode_step_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* state_in,
+                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                  size_t slab_floats, int* err_flag, capnet_stream_t stream);
+
 /* The whole beam search of an attention decoder in one call: capnet_beam_decode's loop with capnet_att_decode_step as the
  * step. Per step s = 1 .. max_steps: the attention step on the previous step's words and parent rows (no parents at
  * s = 1), logits = h_top . Cw^T + Cb by capnet_sgemm_splitk's entry on `slab`, capnet_beam_advance; then
@@ -645,6 +686,19 @@ int capnet_att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, in
                            const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
                            const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
                            long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream);
+
+/* capnet_att_beam_decode with capnet_att_decode_step_groups as the step: the searches of `groups` weight groups over the
+ * same n images in one loop (operands as that step's). The vocabulary projection is one product over all groups n k rows
+ * (Cw is shared), as in capnet_beam_decode_groups. workspace: capnet_att_beam_decode_ws_bytes(nlayers, groups n, ...); seqs
+ * int64 [groups n][max_steps + 2], lengths int32 [groups n]; state0 [groups n k][2 nlayers][H] is required. 1 <= groups <= 8;
+ * groups = 1 is exactly capnet_att_beam_decode. Every bad argument is refused before any launch. */
+int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  int max_steps, long long start_token, long long end_token, const float* att1,
+                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream);
 
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
