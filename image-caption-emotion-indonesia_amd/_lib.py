@@ -141,11 +141,18 @@ SIGNATURES = {
                                                _vp, _vp, _vp, _vp]),
     "capnet_stacked_decode_step_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                                _vp, _vp, _vp, _vp]),
+    "capnet_stacked_decode_step_tables": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                               _vp, _vp, _vp, _vp, _vp, _vp]),
     "capnet_vocab_argmax_ws_bytes": (_sz, [_i, _i]),
+    "capnet_vocab_argmax_groups_ws_bytes": (_sz, [_i, _i, _i]),
+    "capnet_vocab_argmax_groups": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, _vp]),
     "capnet_vocab_argmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "capnet_lstm_greedy_decode_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "capnet_lstm_greedy_decode": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp]),
+    "capnet_lstm_greedy_decode_groups_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "capnet_lstm_greedy_decode_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                              C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "capnet_beam_decode_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "capnet_beam_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, C.POINTER(_vp),
                                 C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),

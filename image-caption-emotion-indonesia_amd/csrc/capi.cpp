@@ -391,6 +391,21 @@ int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int row
                              err_flag, S(stream), parent_rows, groups);
 }
 
+int capnet_stacked_decode_step_tables(int cell, int nlayers, int groups, int rows_per_group, int E, int H, int V,
+                                      const long long* tokens, const float* const* tables, const float* const* wcat,
+                                      const float* const* beff, const float* state_in, const long long* parent_rows,
+                                      float* state_out, float* h_top, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "stacked_decode_step: groups %d (1..8)", groups);
+  CAPNET_REQUIRE(rows_per_group >= 1 && rows_per_group < (1 << 24), "stacked_decode_step: rows per group %d", rows_per_group);
+  CAPNET_REQUIRE(tokens && tables, "stacked_decode_step: per-group tables need token ids");
+  for (int g = 0; g < groups; ++g) CAPNET_REQUIRE(tables[g], "stacked_decode_step: table of group %d is null", g);
+  if (int rc = stacked_step_check(cell, nlayers, groups * rows_per_group, E, H, V, tokens, tables[0], wcat, beff, state_in,
+                                  parent_rows, state_out, h_top, err_flag))
+    return rc;
+  return stacked_decode_step(cell, nlayers, groups * rows_per_group, E, H, V, tokens, tables[0], wcat, beff, state_in, state_out,
+                             h_top, err_flag, S(stream), parent_rows, groups, tables);
+}
+
 int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
                                     const float* x, const float* const* wcat, const float* const* beff,
                                     const float* state_in, float* state_out, float* h_top, int* err_flag,
@@ -416,28 +431,82 @@ int capnet_vocab_argmax(const float* h, const float* w, const float* b, int rows
   return vocab_argmax(h, w, b, rows, H, V, workspace, tokens, nullptr, 0, S(stream));
 }
 
+size_t capnet_vocab_argmax_groups_ws_bytes(int groups, int rows_per_group, int V) {
+  return groups >= 1 && groups <= 8 && rows_per_group >= 1 && V >= 1 ? vocab_argmax_groups_ws_bytes(groups, rows_per_group, V) : 0;
+}
+
+int capnet_vocab_argmax_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                               int H, int V, void* workspace, long long* tokens, capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "vocab_argmax: groups %d (1..8)", groups);
+  CAPNET_REQUIRE(rows_per_group >= 1 && rows_per_group < (1 << 24) && V >= 1, "vocab_argmax: rows per group %d, V %d",
+                 rows_per_group, V);
+  CAPNET_REQUIRE(vocab_argmax_supported(H), "vocab_argmax: unsupported H=%d", H);
+  CAPNET_REQUIRE(h && w && workspace && tokens, "vocab_argmax: null argument");
+  CAPNET_REQUIRE(aligned16(h) && aligned16(workspace), "vocab_argmax: h, w and the workspace must be 16-B aligned");
+  for (int g = 0; g < groups; ++g)
+    CAPNET_REQUIRE(w[g] && aligned16(w[g]), "vocab_argmax: projection of group %d is null or not 16-B aligned", g);
+  return vocab_argmax_groups(h, w, b, groups, rows_per_group, H, V, workspace, tokens, nullptr, 0, S(stream));
+}
+
 size_t capnet_lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V) {
   return nlayers >= 1 && nlayers <= 8 && rows >= 1 && H >= 1 && V >= 1 ? lstm_greedy_decode_ws_bytes(nlayers, rows, H, V) : 0;
+}
+
+size_t capnet_lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int rows_per_group, int H, int V) {
+  return nlayers >= 1 && nlayers <= 8 && groups >= 1 && groups <= 8 && rows_per_group >= 1 && H >= 1 && V >= 1
+             ? lstm_greedy_decode_groups_ws_bytes(nlayers, groups, rows_per_group, H, V) : 0;
+}
+
+// what the two greedy entries check alike (features only with one group)
+static int greedy_check(int nlayers, int groups, int rpg, int E, int H, int V, int steps, const float* features,
+                        const long long* start_tokens, const float* const* emb, const float* const* wcat,
+                        const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
+                        const void* workspace, const long long* ids, const float* state_out, const int* err_flag) {
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_greedy_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "lstm_greedy_decode: groups %d (1..8)", groups);
+  CAPNET_REQUIRE(rpg >= 1 && rpg < (1 << 24) && steps >= 1 && V >= 1, "lstm_greedy_decode: rows %d, steps %d, V %d", rpg, steps, V);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_argmax_supported(H), "lstm_greedy_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE((features != nullptr) != (start_tokens != nullptr),
+                 "lstm_greedy_decode: the first input is either features or start_tokens");
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && Cb && workspace && ids && state_out && err_flag, "lstm_greedy_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && (!state0 || aligned16(state0)) && aligned16(state_out),
+                 "lstm_greedy_decode: workspace, Cw and the states must be 16-B aligned");
+  for (int g = 0; g < groups; ++g) {
+    CAPNET_REQUIRE(emb[g] && Cw[g], "lstm_greedy_decode: null argument (embedding or projection of group %d)", g);
+    CAPNET_REQUIRE(aligned16(Cw[g]), "lstm_greedy_decode: workspace, Cw and the states must be 16-B aligned (group %d)", g);
+  }
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_greedy_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_greedy_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return kOk;
+}
+
+int capnet_lstm_greedy_decode_groups(int nlayers, int groups, int rows_per_group, int E, int H, int V, int steps,
+                                     const long long* start_tokens, const float* const* emb, const float* const* wcat,
+                                     const float* const* beff, const float* const* Cw, const float* const* Cb,
+                                     const float* state0, void* workspace, long long* ids, float* state_out, int* err_flag,
+                                     capnet_stream_t stream) {
+  const float* no_bias[8] = {};
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "lstm_greedy_decode: groups %d (1..8)", groups);
+  for (int g = 0; Cb && g < groups; ++g) CAPNET_REQUIRE(Cb[g], "lstm_greedy_decode: null argument (bias of group %d)", g);
+  if (!Cb) Cb = no_bias;
+  if (int rc = greedy_check(nlayers, groups, rows_per_group, E, H, V, steps, nullptr, start_tokens, emb, wcat, beff, Cw, Cb,
+                            state0, workspace, ids, state_out, err_flag))
+    return rc;
+  return lstm_greedy_decode_groups(nlayers, groups, rows_per_group, E, H, V, steps, nullptr, start_tokens, emb, wcat, beff, Cw,
+                                   Cb, state0, workspace, ids, state_out, err_flag, S(stream));
 }
 
 int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
                               const long long* start_tokens, const float* emb, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0,
                               void* workspace, long long* ids, float* state_out, int* err_flag, capnet_stream_t stream) {
-  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_greedy_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(rows >= 1 && steps >= 1 && V >= 1, "lstm_greedy_decode: rows %d, steps %d, V %d", rows, steps, V);
-  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_argmax_supported(H), "lstm_greedy_decode: unsupported E=%d H=%d", E, H);
-  CAPNET_REQUIRE((features != nullptr) != (start_tokens != nullptr),
-                 "lstm_greedy_decode: the first input is either features or start_tokens");
-  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && state_out && err_flag, "lstm_greedy_decode: null argument");
-  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && aligned16(state_out),
-                 "lstm_greedy_decode: workspace, Cw and the states must be 16-B aligned");
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_greedy_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_greedy_decode: weights of layer %d not 16-B aligned", l);
-  }
-  return lstm_greedy_decode(nlayers, rows, E, H, V, steps, features, start_tokens, emb, wcat, beff, Cw, Cb, state0, workspace,
-                            ids, state_out, err_flag, S(stream));
+  if (int rc = greedy_check(nlayers, 1, rows, E, H, V, steps, features, start_tokens, &emb, wcat, beff, &Cw, &Cb, state0,
+                            workspace, ids, state_out, err_flag))
+    return rc;
+  return lstm_greedy_decode_groups(nlayers, 1, rows, E, H, V, steps, features, start_tokens, &emb, wcat, beff, &Cw, &Cb, state0,
+                                   workspace, ids, state_out, err_flag, S(stream));
 }
 
 size_t capnet_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps) {

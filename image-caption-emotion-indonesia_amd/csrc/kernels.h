@@ -263,8 +263,10 @@ int lstm_upper_step(const float* xin, const float* hprev, const float* cprev, co
 bool stacked_decode_supported(int E, int H);
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr, int groups = 1);
-// (groups: `rows` = groups x rows per group, group-major; wcat[l] [groups][4H][kin + H], beff[l] [groups][4H])
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows = nullptr, int groups = 1,
+                        const float* const* tables = nullptr);
+// (groups: `rows` = groups x rows per group, group-major; wcat[l] [groups][4H][kin + H], beff[l] [groups][4H]; tables:
+// `groups` host-side pointers, group g gathers its token rows from tables[g] [V][E] instead of x -- no table is copied)
 // the same kernels' family for layer 0 of an attention decoder, kin + H up to 4096 (x rows of E % 4 == 0 columns, 16-B aligned)
 bool stacked_decode_wide_supported(int E, int H);
 // One beam step of an attention decoder without the projection: z = h_prev . [decoder_att; f_beta]^T + bz (sgemm_splitk on
@@ -286,7 +288,20 @@ bool vocab_argmax_supported(int H);
 size_t vocab_argmax_ws_bytes(int rows, int V);
 int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* ws, long long* tok,
                  long long* ids, long ld_ids, hipStream_t stream);
+// weight groups: rows = groups x rpg, group-major; group g's rows are projected on w[g] / b[g] (host-side pointer tables,
+// b or any b[g] may be null) in the same launch, one arrival counter per group (ws: vocab_argmax_groups_ws_bytes, its first
+// 16 groups bytes zero before the first use)
+size_t vocab_argmax_groups_ws_bytes(int groups, int rpg, int V);
+int vocab_argmax_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V,
+                        void* ws, long long* tok, long long* ids, long ld_ids, hipStream_t stream);
 size_t lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V);
+size_t lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int rpg, int H, int V);
+int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, int V, int steps, const float* features,
+                              const long long* start_tokens, const float* const* emb, const float* const* wcat,
+                              const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
+                              void* ws, long long* ids, float* state_out, int* err_flag, hipStream_t s);
+// (the greedy loop of `groups` decoders at once: emb / Cw / Cb one pointer per group, wcat[l] / beff[l] with a leading
+// groups dimension, rows group-major; features only with one group)
 int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
                        const long long* start_tokens, const float* emb, const float* const* wcat,
                        const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,

@@ -24,6 +24,10 @@
 // G), rows are group-major, and workgroup (., g) walks only rows [g rpg, (g + 1) rpg) on the weights w + g 4H (kin + H)
 // and b + g 4H. A 16-row tile never reaches into the next group (the row clamp and the store mask end at the group);
 // parents are checked against all the rows. G = 1 is the kernel as it was.
+// Per-group layer-0 tables (every emotion of capnet.seq2seq at once: capnet_stacked_decode_step_tables,
+// capnet_lstm_greedy_decode_groups): workgroup (., g) gathers its token rows from xg[g], one table pointer per group held
+// by value in the argument struct and picked by blockIdx.y -- a scalar load from the kernel arguments, no copy of a table
+// and nothing per lane. Every other caller puts its one table (or its input rows) into all the slots.
 // Layer 0 of an attention decoder reads [embedding | gated context], E + C columns: above kDecMaxK it runs on
 // lstm_decode_step_wide_kernel (below; K up to 4096, a wave's range in two halves), and att_decode_step at the end of
 // this file is the attention decoders' beam step around it (z, the beam-aware attention kernels of att_kernels.hip, the layers).
@@ -35,6 +39,7 @@ namespace capnet {
 
 constexpr int kDecWaves = 8;
 constexpr int kDecMaxK = 2048;       // kin + H <= 8 waves x 16 groups x 16 (lstm_decode_step_wide_kernel: kDecWideMaxK)
+constexpr int kDecMaxGroups = 8;     // weight groups of one launch (capnet_*_groups)
 
 struct DecodeLayerArgs {
   const long long* tok;  // layer 0 with token ids: x row = x + tok[r] * ldx (else x + r * ldx)
@@ -57,6 +62,7 @@ struct DecodeLayerArgs {
   const long long* parent;  // GATHER: int64 [rows], hprev / cprev are read at row parent[r] (outside [0, rows): err, row r)
   int rpg;               // rows per weight group: workgroup (., g) walks rows [g rpg, (g + 1) rpg) on w + g wgs, b + g 4H
   long wgs;              // floats between two groups' weights, 4H (kin + H)
+  const float* xg[kDecMaxGroups];   // lstm_decode_step_kernel: group g's x (`x` itself unless the groups own their tables)
 };
 
 // the row whose previous state row `row` reads
@@ -85,6 +91,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
   // B operand: column li = gate role li >> 2 (i, f, o, c~), unit u0 + (li & 3)
   const int grp = blockIdx.y, rbeg = grp * a.rpg, rend = rbeg + a.rpg;   // this group's rows; one group: [0, rows)
   const float* wrow = a.w + grp * a.wgs + (long)((li >> 2) * H + u0 + (li & 3)) * K + 4 * lq;
+  const float* xbase = a.xg[grp];
   f32x4 wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
         if (!ok && a.err) *a.err = 1;
         xr = ok ? (long)t : 0;
       }
-      const float* xrow = a.x + xr * a.ldx;
+      const float* xrow = xbase + xr * a.ldx;
       const float* hrow = a.hprev + state_row<GATHER>(a, row) * a.lds_in;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -290,14 +297,21 @@ static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
 // layer l of the stack on x rows of xn valid columns at stride ldx (token ids: rows of the table x)
 static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, const long long* tokens, const float* x, long ldx,
                         int xn, const float* w, const float* b, const float* state_in, float* state_out, float* h_top,
-                        int* err_flag, hipStream_t stream, const long long* parent_rows, int groups) {
+                        int* err_flag, hipStream_t stream, const long long* parent_rows, int groups,
+                        const float* const* tables = nullptr) {
   const long lds = 2L * nlayers * H;
   DecodeLayerArgs a;
+  CAPNET_REQUIRE(groups >= 1 && groups <= kDecMaxGroups && rows % groups == 0, "decode step: %d rows in %d groups", rows, groups);
+  CAPNET_REQUIRE(!tables || tokens, "decode step: per-group tables are read by token id");
   a.tok = tokens;
-  a.x = x;
+  a.x = tables ? tables[0] : x;
   a.ldx = ldx;
   a.xn = xn;
-  a.xvec = xn % 4 == 0 && ldx % 4 == 0 && aligned16(x);
+  a.xvec = xn % 4 == 0 && ldx % 4 == 0;
+  for (int g = 0; g < kDecMaxGroups; ++g) {
+    a.xg[g] = tables && g < groups ? tables[g] : a.x;
+    a.xvec = a.xvec && aligned16(a.xg[g]);
+  }
   a.kin = round16(xn);
   a.V = V;
   a.err = err_flag;
@@ -313,21 +327,22 @@ static int decode_layer(int cell, int l, int nlayers, int rows, int H, int V, co
   a.rows = rows;
   a.H = H;
   a.parent = parent_rows;
-  CAPNET_REQUIRE(groups >= 1 && rows % groups == 0, "decode step: %d rows in %d groups", rows, groups);
   a.rpg = rows / groups;
   a.wgs = 4L * H * (a.kin + H);
   CAPNET_REQUIRE(a.kin + H <= kDecMaxK || (a.xvec && a.kin + H <= kDecWideMaxK), "decode step: K = %d + %d", a.kin, H);
+  CAPNET_REQUIRE(!tables || a.kin + H <= kDecMaxK, "decode step: per-group tables need K = %d + %d <= %d", a.kin, H, kDecMaxK);
   if (parent_rows) return cell == kCellLSTM ? launch_decode_layer<true, true>(a, stream) : launch_decode_layer<false, true>(a, stream);
   return cell == kCellLSTM ? launch_decode_layer<true, false>(a, stream) : launch_decode_layer<false, false>(a, stream);
 }
 
 int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens, const float* x,
                         const float* const* wcat, const float* const* beff, const float* state_in, float* state_out,
-                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows, int groups) {
+                        float* h_top, int* err_flag, hipStream_t stream, const long long* parent_rows, int groups,
+                        const float* const* tables) {
   const long lds = 2L * nlayers * H;
   for (int l = 0; l < nlayers; ++l) {
     const int rc = l == 0 ? decode_layer(cell, 0, nlayers, rows, H, V, tokens, x, E, E, wcat[0], beff[0], state_in, state_out,
-                                         h_top, err_flag, stream, parent_rows, groups)
+                                         h_top, err_flag, stream, parent_rows, groups, tables)
                           : decode_layer(cell, l, nlayers, rows, H, V, nullptr, state_out + (long)(2 * l - 2) * H, lds, H, wcat[l],
                                          beff[l], state_in, state_out, h_top, err_flag, stream, parent_rows, groups);
     if (rc != kOk) return rc;

@@ -15,6 +15,13 @@
 // ids matrix), and puts the counter back to zero. No workgroup waits on another. Plain vector loads and stores only.
 // NaN and -inf logits are never picked (strict `>` against -inf, as argmax_rows_kernel); a row with nothing to pick
 // yields 0.
+// Weight groups (every emotion of capnet.seq2seq at once: capnet_vocab_argmax_groups, capnet_lstm_greedy_decode_groups): the
+// grid is (ceil(V / 32), G), rows are group-major, and workgroup (., g) projects rows [g rpg, (g + 1) rpg) on w[g] / b[g]
+// -- one pointer per group held by value in the argument struct and picked by blockIdx.y, a scalar load from the kernel
+// arguments; no projection is copied. It writes its partials to group g's block and arrives at group g's OWN counter (16
+// bytes apart), where arrivals are counted against gridDim.x: group g's last arriver reduces group g's rows, writes their
+// tokens and re-arms that counter only. The groups never meet. G = 1 is the kernel as it was: the same grid, the same
+// addresses, the same bits.
 #include "common.h"
 #include "kernels.h"
 #include "step_core.h"
@@ -25,16 +32,18 @@ constexpr int kVaWaves = 8;
 constexpr int kVaCols = 32;          // vocabulary entries per workgroup
 constexpr int kVaNone = 0x7fffffff;
 
+constexpr int kVaMaxGroups = 8;      // weight groups of one launch
+
 struct VocabArgmaxArgs {
-  const float* h;            // [rows][H]
-  const float* w;            // [V][H]
-  const float* b;            // [V] or null
-  unsigned long long* part;  // [workgroups][rows]: (value bits << 32) | index
-  int* counter;              // zero before the first use; zero again when the launch ends
+  const float* h;            // [rows][H], group-major
+  unsigned long long* part;  // [groups][workgroups][rpg]: (value bits << 32) | index
+  int* counter;              // group g's at counter + 4 g; zero before the first use, zero again when the launch ends
   long long* tok;            // optional [rows]
   long long* ids;            // optional: ids[r * ld_ids]
   long ld_ids;
-  int rows, H, V;
+  int rpg, H, V;             // rows per group: workgroup (., g) owns rows [g rpg, (g + 1) rpg)
+  const float* w[kVaMaxGroups];   // [V][H] of group g
+  const float* b[kVaMaxGroups];   // [V] of group g, or null
 };
 
 __device__ __forceinline__ bool va_better(float v, int i, float best, int bi) {
@@ -52,20 +61,23 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
   const int H = a.H, c0 = blockIdx.x * kVaCols;
   const int g0 = ks * NJ;                                   // this wave's k groups [g0, g0 + NJ): H = 64 NJ
   const int wcol = clamp_row(c0 + 16 * tile + li, a.V);      // entries beyond V: masked in the epilogue
-  const float* wrow = a.w + (long)wcol * H + 16 * g0 + 4 * lq;
+  const int grp = blockIdx.y, rbeg = grp * a.rpg, rend = rbeg + a.rpg;   // this group's rows; one group: [0, rows)
+  const float* bg = a.b[grp];
+  const float* wrow = a.w[grp] + (long)wcol * H + 16 * g0 + 4 * lq;
   f32x4 wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * j);
   // epilogue thread: (row er of a 16-row tile, entry ec of the workgroup's 32)
   const int er = tid >> 5, ec = tid & 31;
   const int ecol = c0 + ec;
-  const float bias = (a.b && ecol < a.V) ? a.b[ecol] : 0.f;
-  unsigned long long* part = a.part + (long)blockIdx.x * a.rows;
-  for (int r0 = 0; r0 < a.rows; r0 += kPass) {
+  const float bias = (bg && ecol < a.V) ? bg[ecol] : 0.f;
+  unsigned long long* gpart = a.part + (long)grp * gridDim.x * a.rpg;    // the group's block, [workgroups][rpg]
+  unsigned long long* part = gpart + (long)blockIdx.x * a.rpg;
+  for (int r0 = rbeg; r0 < rend; r0 += kPass) {
     f32x4 acc[TM];
 #pragma unroll
     for (int m = 0; m < TM; ++m) {
-      const int row = clamp_row(r0 + 16 * m + li, a.rows);
+      const int row = clamp_row(r0 + 16 * m + li, rend);
       const float* hrow = a.h + (long)row * H + 16 * g0 + 4 * lq;
       f32x4 av[NJ];
 #pragma unroll
@@ -91,8 +103,8 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
         const int oi = __shfl_xor(bi, o);
         if (va_better(ov, oi, best, bi)) { best = ov; bi = oi; }
       }
-      if (ec == 0 && row < a.rows)
-        __hip_atomic_store(part + row, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bi, __ATOMIC_RELAXED,
+      if (ec == 0 && row < rend)
+        __hip_atomic_store(part + (row - rbeg), ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bi, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();   // red is rewritten by the next pass
@@ -100,12 +112,12 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0)
-    s_last = __hip_atomic_fetch_add(a.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    s_last = __hip_atomic_fetch_add(a.counter + 4 * grp, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
   __syncthreads();
   if (!s_last) return;
-  // the last arriver: a wave per row, the workgroups' partials across its lanes
+  // the group's last arriver: a wave per row of the group, the workgroups' partials across its lanes
   const int nwg = gridDim.x;
-  for (int row = wave; row < a.rows; row += kVaWaves) {
+  for (int row = rbeg + wave; row < rend; row += kVaWaves) {
     float best = -INFINITY;
     int bi = kVaNone;
     for (int p0 = 0; p0 < nwg; p0 += 64 * 4) {
@@ -113,7 +125,7 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int p = min(p0 + 64 * q + lane, nwg - 1);
-        u[q] = __hip_atomic_load(a.part + (long)p * a.rows + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        u[q] = __hip_atomic_load(gpart + (long)p * a.rpg + (row - rbeg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -134,25 +146,38 @@ __global__ __launch_bounds__(512) void vocab_argmax_kernel(VocabArgmaxArgs a) {
       if (a.ids) a.ids[(long)row * a.ld_ids] = t;
     }
   }
-  if (tid == 0) __hip_atomic_store(a.counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(a.counter + 4 * grp, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 static int va_workgroups(int V) { return (V + kVaCols - 1) / kVaCols; }
 
 bool vocab_argmax_supported(int H) { return step_hidden_supported(H); }
 
-// workspace: 16 bytes whose first int is the counter, then one 8-byte partial per workgroup and row
-size_t vocab_argmax_ws_bytes(int rows, int V) { return 16 + (size_t)va_workgroups(V) * rows * 8; }
+// workspace: per group 16 bytes whose first int is the group's counter, then one 8-byte partial per group, workgroup and row
+size_t vocab_argmax_groups_ws_bytes(int groups, int rpg, int V) {
+  return 16 * (size_t)groups + (size_t)groups * va_workgroups(V) * rpg * 8;
+}
+size_t vocab_argmax_ws_bytes(int rows, int V) { return vocab_argmax_groups_ws_bytes(1, rows, V); }
 
 int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* ws, long long* tok,
                  long long* ids, long ld_ids, hipStream_t stream) {
+  return vocab_argmax_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, ws, tok, ids, ld_ids, stream);
+}
+
+int vocab_argmax_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V,
+                        void* ws, long long* tok, long long* ids, long ld_ids, hipStream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= kVaMaxGroups && rpg >= 1, "vocab_argmax: %d groups of %d rows", groups, rpg);
   VocabArgmaxArgs a;
-  a.h = h; a.w = w; a.b = b;
+  a.h = h;
+  for (int g = 0; g < kVaMaxGroups; ++g) {
+    a.w[g] = w[g < groups ? g : 0];
+    a.b[g] = b ? b[g < groups ? g : 0] : nullptr;
+  }
   a.counter = reinterpret_cast<int*>(ws);
-  a.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);
+  a.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16 * (size_t)groups);
   a.tok = tok; a.ids = ids; a.ld_ids = ld_ids;
-  a.rows = rows; a.H = H; a.V = V;
-  const dim3 grid(va_workgroups(V)), block(64 * kVaWaves);
+  a.rpg = rpg; a.H = H; a.V = V;
+  const dim3 grid(va_workgroups(V), groups), block(64 * kVaWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
     hipLaunchKernelGGL((vocab_argmax_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
   });
@@ -164,15 +189,29 @@ int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H
 // ws: [state A | state B] ([rows][2L][H] each) | h_top [rows][H] | tok int64 [rows] | vocab_argmax's workspace
 static size_t gd_align(size_t n) { return (n + 15) / 16 * 16; }
 
+size_t lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int rpg, int H, int V) {
+  const size_t rows = (size_t)groups * rpg, st = gd_align(rows * 2 * nlayers * H * sizeof(float));
+  return 2 * st + gd_align(rows * H * sizeof(float)) + gd_align(rows * 8) + vocab_argmax_groups_ws_bytes(groups, rpg, V);
+}
+
 size_t lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V) {
-  const size_t st = gd_align((size_t)rows * 2 * nlayers * H * sizeof(float));
-  return 2 * st + gd_align((size_t)rows * H * sizeof(float)) + gd_align((size_t)rows * 8) + vocab_argmax_ws_bytes(rows, V);
+  return lstm_greedy_decode_groups_ws_bytes(nlayers, 1, rows, H, V);
 }
 
 int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
                        const long long* start_tokens, const float* emb, const float* const* wcat,
                        const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,
                        long long* ids, float* state_out, int* err_flag, hipStream_t s) {
+  return lstm_greedy_decode_groups(nlayers, 1, rows, E, H, V, steps, features, start_tokens, &emb, wcat, beff, &Cw, &Cb, state0,
+                                   ws, ids, state_out, err_flag, s);
+}
+
+// group g's rows [g rpg, (g + 1) rpg) decode on emb[g], wcat[l] + g 4H (kin + H), beff[l] + g 4H, Cw[g], Cb[g]
+int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, int V, int steps, const float* features,
+                              const long long* start_tokens, const float* const* emb, const float* const* wcat,
+                              const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
+                              void* ws, long long* ids, float* state_out, int* err_flag, hipStream_t s) {
+  const int rows = groups * rpg;
   const size_t st_bytes = (size_t)rows * 2 * nlayers * H * sizeof(float), st = gd_align(st_bytes);
   char* p = reinterpret_cast<char*>(ws);
   float* state[2] = {reinterpret_cast<float*>(p), reinterpret_cast<float*>(p + st)};
@@ -185,12 +224,12 @@ int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, co
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
   else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
   if (start_tokens) CAPNET_HIP_CHECK(hipMemcpyAsync(tok, start_tokens, (size_t)rows * 8, hipMemcpyDeviceToDevice, s));
-  CAPNET_HIP_CHECK(hipMemsetAsync(va_ws, 0, 16, s));
+  CAPNET_HIP_CHECK(hipMemsetAsync(va_ws, 0, 16 * (size_t)groups, s));
   for (int t = 0; t < steps; ++t) {
-    const bool feat = t == 0 && features;
-    int rc = stacked_decode_step(kCellLSTM, nlayers, rows, E, H, V, feat ? nullptr : tok, feat ? features : emb, wcat, beff,
-                                 state[t & 1], state[(t + 1) & 1], h_top, err_flag, s);
-    if (rc == kOk) rc = vocab_argmax(h_top, Cw, Cb, rows, H, V, va_ws, tok, ids + t, steps, s);
+    const bool feat = t == 0 && features;    // (one group only: capnet_lstm_greedy_decode)
+    int rc = stacked_decode_step(kCellLSTM, nlayers, rows, E, H, V, feat ? nullptr : tok, feat ? features : emb[0], wcat, beff,
+                                 state[t & 1], state[(t + 1) & 1], h_top, err_flag, s, nullptr, groups, feat ? nullptr : emb);
+    if (rc == kOk) rc = vocab_argmax_groups(h_top, Cw, Cb, groups, rpg, H, V, va_ws, tok, ids + t, steps, s);
     if (rc != kOk) return rc;
   }
   CAPNET_HIP_CHECK(hipMemcpyAsync(state_out, state[steps & 1], st_bytes, hipMemcpyDeviceToDevice, s));

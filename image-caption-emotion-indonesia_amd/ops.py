@@ -448,6 +448,107 @@ def stacked_decode_step(state, wcat, beff, x, tokens=None, cell=CELL_FACTORED, p
     return top, out
 
 
+def _check_tables(who, tables, shape, groups=None):
+    """One contiguous fp32 tensor of `shape` per group, used where it lies (a table is never stacked or copied)."""
+    tables = list(tables)
+    if groups is None:
+        groups = _check_groups(who, len(tables))
+    if len(tables) != groups:
+        raise CapnetError("%s: %d tables for %d groups" % (who, len(tables), groups))
+    for t in tables:
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise CapnetError("%s: one contiguous float32 %r tensor per group" % (who, tuple(shape)))
+    _need_cuda(*tables)
+    return [t.detach() for t in tables]
+
+
+def _first_shape(tables):
+    tables = list(tables)
+    return tuple(tables[0].shape) if tables and tables[0] is not None else ()
+
+
+def _grouped_layer_weights(who, wcat, beff, groups, H, kin0):
+    """The layers' weights with their leading [groups] dimension, also for one group."""
+    for l, (w, b) in enumerate(zip(wcat, beff)):
+        kin = kin0 if l == 0 else H
+        if tuple(w.shape) != (groups, 4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (groups, 4 * H) \
+                or not b.is_contiguous():
+            raise CapnetError("%s: layer %d weights must be [groups, 4H, %d] and [groups, 4H]" % (who, l, kin + H))
+    return list(wcat), list(beff)
+
+
+def stacked_decode_step_tables(state, wcat, beff, tables, tokens, cell=CELL_LSTM, parent_rows=None):
+    """stacked_decode_step over len(tables) weight groups whose layer 0 reads ITS OWN table (capnet_stacked_decode_step_
+    tables): rows group-major, block g on wcat[l][g] / beff[l][g] and on tables[g] [V, E] by tokens (int64 [rows]). Each
+    block's rows equal stacked_decode_step of that block alone on its weights and table, bit for bit.
+    Returns (top-layer h [rows, H], the new state [rows, 2L, H])."""
+    who = "stacked_decode_step"
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("%s: unknown cell %r" % (who, cell))
+    tables = _check_tables(who, tables, _first_shape(tables))
+    groups = len(tables)
+    _need_cuda(state, tokens, parent_rows, *wcat, *beff)
+    rows, L2, H = state.shape
+    nl = L2 // 2
+    if rows % groups or L2 != 2 * nl or len(wcat) != nl or len(beff) != nl or tables[0].dim() != 2:
+        raise CapnetError("%s: state [groups rows, 2L, H], L weight pairs, tables [V, E]" % who)
+    V, E = tables[0].shape
+    state, tokens = _c(state), _c(tokens)
+    if tokens.dtype != torch.int64 or tokens.numel() != rows:
+        raise CapnetError("%s: tokens must be int64 [rows]" % who)
+    if parent_rows is not None:
+        parent_rows = _c(parent_rows)
+        if parent_rows.dtype != torch.int64 or parent_rows.numel() != rows:
+            raise CapnetError("%s: parent_rows must be int64 [rows]" % who)
+    wcat, beff = _grouped_layer_weights(who, wcat, beff, groups, H, (E + 15) // 16 * 16)
+    out = torch.empty_like(state)
+    top = torch.empty((rows, H), dtype=torch.float32, device=state.device)
+    check(_lib.lib().capnet_stacked_decode_step_tables(
+        cell, nl, groups, rows // groups, E, H, V, ptr(tokens), ptr_array(tables), ptr_array(wcat), ptr_array(beff),
+        ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(err_flag(state.device)), current_stream()),
+        "capnet_stacked_decode_step_tables")
+    return top, out
+
+
+def vocab_argmax_groups_workspace(groups, rows_per_group, V, device):
+    """A zeroed workspace of capnet_vocab_argmax_groups (back-to-back calls on one stream may share it)."""
+    n = _lib.lib().capnet_vocab_argmax_groups_ws_bytes(int(groups), int(rows_per_group), int(V))
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vocab_argmax_groups(h, ws, bs=None, workspace=None):
+    """vocab_argmax of len(ws) projections in one launch (capnet_vocab_argmax_groups): h [groups rows, H], group-major;
+    block g on ws[g] [V, H] / bs[g] [V] (bs or any bs[g] None: no bias), each tensor used where it lies. Every block's
+    tokens equal vocab_argmax of that block alone, bit for bit. Returns tokens [groups rows] int64."""
+    who = "vocab_argmax"
+    ws = _check_tables(who, ws, _first_shape(ws))
+    groups = len(ws)
+    _need_cuda(h)
+    h = _c(h.detach())
+    if h.dim() != 2 or ws[0].dim() != 2:
+        raise CapnetError("%s: h [groups rows, H], w [V, H] per group" % who)
+    rows, H = h.shape
+    V = ws[0].shape[0]
+    if ws[0].shape[1] != H or H not in DECODE_HIDDEN or rows < groups or rows % groups:
+        raise CapnetError("%s: h [groups rows, H], w [V, H] per group with H in %r" % (who, DECODE_HIDDEN))
+    if bs is not None:
+        bs = list(bs)
+        present = [b for b in bs if b is not None]
+        if len(bs) != groups:
+            raise CapnetError("%s: one bias (or None) per group" % who)
+        _check_tables(who, present, (V,), len(present))
+        bs = [None if b is None else b.detach() for b in bs]
+    rpg = rows // groups
+    if workspace is None:
+        workspace = vocab_argmax_groups_workspace(groups, rpg, V, h.device)
+    if workspace.numel() * workspace.element_size() < _lib.lib().capnet_vocab_argmax_groups_ws_bytes(groups, rpg, V):
+        raise CapnetError("%s: workspace too small" % who)
+    out = torch.empty(rows, dtype=torch.int64, device=h.device)
+    check(_lib.lib().capnet_vocab_argmax_groups(ptr(h), ptr_array(ws), None if bs is None else ptr_array(bs), groups, rpg, H, V,
+                                                ptr(workspace), ptr(out), current_stream()), "capnet_vocab_argmax_groups")
+    return out
+
+
 def vocab_argmax_workspace(rows, V, device):
     """A zeroed workspace of capnet_vocab_argmax for `rows` rows (back-to-back calls on one stream may share it)."""
     n = _lib.lib().capnet_vocab_argmax_ws_bytes(int(rows), int(V))
@@ -512,6 +613,48 @@ def lstm_greedy_decode(steps, wcat, beff, emb, Cw, Cb, features=None, start_toke
     check(L.capnet_lstm_greedy_decode(nl, rows, E, H, V, int(steps), ptr(features), ptr(start_tokens), ptr(emb),
                                       ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(ids),
                                       ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_lstm_greedy_decode")
+    return ids, out
+
+
+def lstm_greedy_decode_groups(steps, wcat, beff, embs, Cws, Cbs, start_tokens, state=None):
+    """lstm_greedy_decode of len(embs) decoders in ONE C call (capnet_lstm_greedy_decode_groups): rows group-major, block
+    g on embs[g] [V, E], wcat[l][g] / beff[l][g] and Cws[g] [V, H] / Cbs[g] [V]. The embeddings and projections are used
+    where they lie (one pointer per group; nothing is stacked or copied); wcat[l] [groups, 4H, kin_l + H] and beff[l]
+    [groups, 4H] are capnet.decode.pack_cell of every decoder's layer l, stacked. The first input is
+    embs[g][start_tokens[r]] (int64 [groups rows]); state: [groups rows, 2L, H] or None for zeros.
+    Returns (ids [groups rows, steps] int64, the final state [groups rows, 2L, H])."""
+    who = "lstm_greedy_decode"
+    embs = _check_tables(who, embs, _first_shape(embs))
+    groups = len(embs)
+    Cws = list(Cws)
+    if embs[0].dim() != 2 or not Cws or Cws[0] is None or Cws[0].dim() != 2:
+        raise CapnetError("%s: emb [V, E] and Cw [V, H] per group" % who)
+    V, E = embs[0].shape
+    H, nl = Cws[0].shape[1], len(wcat)
+    Cws = _check_tables(who, Cws, (V, H), groups)
+    Cbs = _check_tables(who, Cbs, (V,), groups)
+    _need_cuda(start_tokens, state, *wcat, *beff)
+    if not stacked_decode_supported(E, H) or not 1 <= nl <= 8 or len(beff) != nl:
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, %d layers)" % (who, E, H, nl))
+    start_tokens = _c(start_tokens)
+    rows = start_tokens.numel()
+    if start_tokens.dtype != torch.int64 or start_tokens.dim() != 1 or rows < groups or rows % groups or int(steps) < 1:
+        raise CapnetError("%s: start_tokens must be int64 [groups rows], steps >= 1" % who)
+    wcat, beff = _grouped_layer_weights(who, wcat, beff, groups, H, (E + 15) // 16 * 16)
+    dev = embs[0].device
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (rows, 2 * nl, H):
+            raise CapnetError("%s: state must be [groups rows, 2L, H]" % who)
+    L = _lib.lib()
+    rpg = rows // groups
+    ws = torch.empty((L.capnet_lstm_greedy_decode_groups_ws_bytes(nl, groups, rpg, H, V) + 7) // 8, dtype=torch.int64, device=dev)
+    ids = torch.empty((rows, int(steps)), dtype=torch.int64, device=dev)
+    out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
+    check(L.capnet_lstm_greedy_decode_groups(nl, groups, rpg, E, H, V, int(steps), ptr(start_tokens), ptr_array(embs),
+                                             ptr_array(wcat), ptr_array(beff), ptr_array(Cws), ptr_array(Cbs), ptr(state),
+                                             ptr(ws), ptr(ids), ptr(out), ptr(err_flag(dev)), current_stream()),
+          "capnet_lstm_greedy_decode_groups")
     return ids, out
 
 

@@ -21,6 +21,11 @@ stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with 
     does not take (ops.stacked_decode_supported) and batches of more than FUSED_GREEDY_MAX_ROWS = 16 rows: measured
     (profiles/README.md), the one call is 1.3x to 2.3x faster at 1 and 12 rows and no faster at 64 (slower at 2 and 3
     layers), so a batch beyond one 16-row tile goes to the composed loop; 17 to 63 rows were not measured.
+  * Every emotion at once: Seq2Seq.sample_styles runs the encoder's greedy loop ONCE and then the emotion decoders as ONE
+    capnet_lstm_greedy_decode_groups call from the encoder's final state repeated per decoder: per step one launch per
+    layer on a (H / 4, decoders) grid and one vocab_argmax launch on a (V / 32, decoders) grid, workgroup (., g) on
+    decoder g's own embedding, LSTM weights and projection. The embeddings and projections are used where they lie (one
+    pointer per decoder); only the packed LSTM weights are stacked. Every entry equals sample(mode=...) exactly.
 """
 import os
 import random
@@ -30,7 +35,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .decode import cell_stepper, pack_cells
+from .decode import cell_stepper, check_styles, pack_cells
 from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
 
@@ -248,3 +253,47 @@ class Seq2Seq(nn.Module):
         if decoder is None:
             return sampled_ids
         return decoder.sample(start_token, states)
+
+    def _check_mode(self, mode):
+        if mode != 'factual':
+            self._decoder(mode)
+
+    def _grouped_greedy_ok(self, decoders, rows):
+        """Whether `decoders` decode `rows` rows each in one grouped call now (CAPNET_NO_FUSED_GREEDY is read here)."""
+        d = decoders[0]
+        same = all((x.embed_size, x.hidden_size, x.vocab_size, x.num_layers, x.max_seq_length) ==
+                   (d.embed_size, d.hidden_size, d.vocab_size, d.num_layers, d.max_seq_length) for x in decoders)
+        return (same and 2 <= len(decoders) <= ops.MAX_GROUPS and os.environ.get(FUSED_GREEDY_OFF, "")[:1] != "1"
+                and ops.stacked_decode_supported(d.embed_size, d.hidden_size) and rows <= FUSED_GREEDY_MAX_ROWS)
+
+    def sample_styles(self, features, start_token, states=(None, None), modes=('factual', 'happy', 'sad', 'angry')):
+        """{mode: ids [B, max_seq_length] int64} for every mode of `modes` (a non-empty sequence of distinct names), each
+        entry equal to sample(features, start_token, states, mode=mode). The encoder's greedy loop runs once, whatever is
+        asked for; its ids are the `factual` entry. Two or more emotions then decode as ONE grouped call
+        (ops.lstm_greedy_decode_groups) from the encoder's final state, copied once per decoder. One emotion, more than
+        FUSED_GREEDY_MAX_ROWS rows, a shape the decode kernel does not take or CAPNET_NO_FUSED_GREEDY=1: one
+        DecoderRNN.sample after the other on that one encoder run."""
+        modes = check_styles(modes, self._check_mode)
+        emotions = [m for m in modes if m != 'factual']
+        decoders = [self._decoder(m) for m in emotions]
+        factual, (h, c) = self.encoder.sample(features, states)
+        out = {'factual': factual}
+        rows = h.size(1)
+        if decoders and self._grouped_greedy_ok(decoders, rows):
+            d, G = decoders[0], len(decoders)
+            with torch.no_grad():
+                packed = [pack_cells(x._layers(), d.embed_size) for x in decoders]
+                wcat = [torch.stack([p[l][0] for p in packed]) for l in range(d.num_layers)]
+                beff = [torch.stack([p[l][1] for p in packed]) for l in range(d.num_layers)]
+                state = _to_rows(h, c).repeat(G, 1, 1)
+                tokens = torch.full((G * rows,), int(start_token), dtype=torch.int64, device=h.device)
+                ids, _ = ops.lstm_greedy_decode_groups(
+                    d.max_seq_length, wcat, beff, [x.embed.weight.detach() for x in decoders],
+                    [x.linear.weight.detach() for x in decoders], [x.linear.bias.detach() for x in decoders], tokens, state)
+            ops.check_device_errors()
+            for g, m in enumerate(emotions):
+                out[m] = ids[g * rows:(g + 1) * rows]
+        else:
+            for m, x in zip(emotions, decoders):
+                out[m] = x.sample(start_token, (h, c))
+        return {m: out[m] for m in modes}

@@ -564,6 +564,18 @@ int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int row
                                       const float* const* beff, const float* state_in, const long long* parent_rows,
                                       float* state_out, float* h_top, int* err_flag, capnet_stream_t stream);
 
+/* capnet_stacked_decode_step_groups with one layer-0 table PER GROUP (capnet.seq2seq: every emotion's DecoderRNN owns its
+ * embedding): tables is a HOST array of `groups` device pointers, tables[g] [V][E], and row r of group g reads
+ * tables[g][tokens[r]] -- the kernel receives the pointers by value and picks its group's by the workgroup's group index;
+ * no table is copied or stacked. tokens is required (there are no input rows); V is the same for every group. Row r of
+ * group g is, bit for bit, the row of capnet_stacked_decode_step_gather on group g's rows, weights and table alone. A
+ * token id outside [0, V) sets *err_flag = 1 and reads row 0 of its group's table. E + H (E rounded up to 16) <= 2048,
+ * the narrow kernel. Every tables[g] non-NULL. Same shapes and checks otherwise. */
+int capnet_stacked_decode_step_tables(int cell, int nlayers, int groups, int rows_per_group, int E, int H, int V,
+                                      const long long* tokens, const float* const* tables, const float* const* wcat,
+                                      const float* const* beff, const float* state_in, const long long* parent_rows,
+                                      float* state_out, float* h_top, int* err_flag, capnet_stream_t stream);
+
 /* tokens[r] = the FIRST argmax over v of h[r] . w[v] + b[v], r < rows: the vocabulary projection (nn.Linear: w [V][H],
  * b [V] or NULL) and the row argmax in one launch, fp32 throughout, the logits never stored. A -inf or NaN logit is never
  * picked and a row with nothing to pick yields 0, as capnet_argmax_rows. rows >= 1, V >= 1, H in {64, 128, 256, 512,
@@ -574,6 +586,17 @@ int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int row
 size_t capnet_vocab_argmax_ws_bytes(int rows, int V);
 int capnet_vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* workspace,
                         long long* tokens, capnet_stream_t stream);
+
+/* capnet_vocab_argmax for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's
+ * rows are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL;
+ * every w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival
+ * counter and its own block of partials, so no group waits on another, and tokens of group g are, bit for bit, those of
+ * capnet_vocab_argmax on group g's rows and projection alone. workspace: capnet_vocab_argmax_groups_ws_bytes(groups,
+ * rows_per_group, V) bytes whose first 16 groups bytes are ZERO before the first use (and are left zero). 1 <= groups <=
+ * 8; groups = 1 is exactly capnet_vocab_argmax (the same grid, the same workspace layout). */
+size_t capnet_vocab_argmax_groups_ws_bytes(int groups, int rows_per_group, int V);
+int capnet_vocab_argmax_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                               int H, int V, void* workspace, long long* tokens, capnet_stream_t stream);
 
 /* Greedy decoding of a stacked nn.LSTM + nn.Linear for a fixed number of steps (capnet.seq2seq: EncoderRNN.sample /
  * DecoderRNN.sample, seq2seq/model.py:100-122, 193-217; no end token, no dropout), the whole loop on `stream` with no
@@ -592,6 +615,25 @@ int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int st
                               const long long* start_tokens, const float* emb, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0,
                               void* workspace, long long* ids, float* state_out, int* err_flag, capnet_stream_t stream);
+
+/* capnet_lstm_greedy_decode for `groups` decoders at once (capnet.seq2seq.Seq2Seq.sample_styles: every emotion's
+ * DecoderRNN from the encoder's final state): rows = groups x rows_per_group, group-major, and group g decodes on ITS
+ * embedding emb[g] [V][E], LSTM weights and projection Cw[g] [V][H] / Cb[g] [V] -- per step one launch per layer of
+ * capnet_stacked_decode_step_tables and one capnet_vocab_argmax_groups launch, so the launches of one decoder serve all.
+ * emb, Cw, Cb: HOST arrays of `groups` device pointers (Cb itself may be NULL: no bias); nothing is stacked or copied. wcat[l]
+ * [groups][4H][kin_l + H] and beff[l] [groups][4H], one device buffer per layer, as capnet_stacked_decode_step_groups. The
+ * first input is emb[g][start_tokens[r]] (int64 [rows], required; features are not an input: the encoder is one group and
+ * keeps capnet_lstm_greedy_decode). state0 [rows][2 nlayers][H] or NULL for zeros; ids int64 [rows][steps], group-major;
+ * state_out as capnet_lstm_greedy_decode. Row r of group g is, bit for bit, the row of capnet_lstm_greedy_decode on group
+ * g's rows and parameters alone. workspace: capnet_lstm_greedy_decode_groups_ws_bytes(nlayers, groups, rows_per_group, H,
+ * V) bytes, 16-B aligned, contents irrelevant. Refused before any launch: groups outside 1..8, rows_per_group < 1, steps <
+ * 1, layers outside 1..8, unsupported E / H, a NULL or misaligned pointer, a NULL entry of any table. */
+size_t capnet_lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int rows_per_group, int H, int V);
+int capnet_lstm_greedy_decode_groups(int nlayers, int groups, int rows_per_group, int E, int H, int V, int steps,
+                                     const long long* start_tokens, const float* const* emb, const float* const* wcat,
+                                     const float* const* beff, const float* const* Cw, const float* const* Cb,
+                                     const float* state0, void* workspace, long long* ids, float* state_out, int* err_flag,
+                                     capnet_stream_t stream);
 
 /* The whole beam search of a plain LSTM stack (capnet.beam.beam_search_device's loop for StackedFactoredLSTM /
  * StackedDecoderRNN / DecoderFactoredLSTM / DecoderRNN) in one call: n images x k fixed slots, rows i k .. i k + k - 1 are
