@@ -552,6 +552,56 @@ int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n_images, i
                      workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups);
 }
 
+size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
+
+int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
+                      float* values, int* index, float* lse, capnet_stream_t stream) {
+  CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1, "vocab_topk: rows %d, V %d", rows, V);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "vocab_topk: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
+  CAPNET_REQUIRE(vocab_topk_supported(H, k, V), "vocab_topk: unsupported H=%d", H);
+  CAPNET_REQUIRE(h && w && workspace && values && index && lse, "vocab_topk: null argument");
+  CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_topk: h, w and the workspace must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)lse % 4 == 0, "vocab_topk: output alignment");
+  return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream));
+}
+
+size_t capnet_lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
+  return lstm_beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps, fused_topk);
+}
+
+int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                            long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
+                            const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                            float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
+                            int* steps_run, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "lstm_beam_decode: unknown cell %d", cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_beam_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(n >= 1 && n < (1 << 24) && max_steps >= 1 && V >= 1 && poll_every >= 0,
+                 "lstm_beam_decode: n %d, max_steps %d, V %d, poll_every %d", n, max_steps, V, poll_every);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "lstm_beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
+  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28) && (long)n * k * V < (1L << 31) && (long)n * k < (1L << 24),
+                 "lstm_beam_decode: n k too large");
+  CAPNET_REQUIRE(stacked_decode_supported(E, H), "lstm_beam_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE(!fused_topk || vocab_topk_supported(H, k, V), "lstm_beam_decode: the fused top-k does not take H=%d", H);
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "lstm_beam_decode: start_token %lld", start_token);
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && seqs && lengths && err_flag, "lstm_beam_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!first_inputs || aligned16(first_inputs)),
+                 "lstm_beam_decode: workspace, Cw, state0 and first_inputs must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "lstm_beam_decode: seqs / lengths alignment");
+  if (!fused_topk) {
+    CAPNET_REQUIRE(slab && aligned16(slab), "lstm_beam_decode: without the fused top-k the slab is required, 16-B aligned");
+    CAPNET_REQUIRE(slab_floats >= (size_t)n * k * V, "lstm_beam_decode: the slab holds %zu floats, one [n k][V] block is %zu",
+                   slab_floats, (size_t)n * k * V);
+  }
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_beam_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_beam_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return lstm_beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb, wcat, beff, Cw, Cb,
+                          state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
+                          S(stream));
+}
+
 int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {
   return att_decode_supported(E, C, H, A, P, k, nlayers) ? 1 : 0;
 }
@@ -777,6 +827,11 @@ int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_to
 int capnet_beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step,
                         long long end_token, long long* next_words, long long* parent_rows, capnet_stream_t stream) {
   return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream));
+}
+int capnet_beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k,
+                             int max_steps, int step, long long end_token, long long* next_words, long long* parent_rows,
+                             capnet_stream_t stream) {
+  return beam_advance_topk(beam, values, index, lse, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream));
 }
 int capnet_beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
                        capnet_stream_t stream) {

@@ -222,6 +222,9 @@ size_t beam_state_bytes(int n, int k, int max_steps);
 int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream);
 int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
                  long long* next_words, long long* parent_rows, hipStream_t stream);
+// (beam_advance on a step's k best logits per row and the rows' log-sum-exp, vocab_topk's outputs, instead of its logits)
+int beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k, int max_steps,
+                      int step, long long end_token, long long* next_words, long long* parent_rows, hipStream_t stream);
 int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
                 hipStream_t stream);
 int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
@@ -314,6 +317,21 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
                 long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1);
 // (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
+// vocab_topk.hip: per row the k best of h[r] . W[v] + b[v] (logit descending, index ascending; fewer pickable entries: the
+// tail is (-inf, -1)) and log sum_v exp, one launch, no logits in memory (ws: vocab_topk_ws_bytes, its first 16 bytes zero
+// before the first use)
+bool vocab_topk_supported(int H, int k, int V);
+size_t vocab_topk_ws_bytes(int rows, int k, int V);
+int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
+               int* index, float* lse, hipStream_t stream);
+// beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set; fused_topk: a step's
+// projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else beam_decode's
+size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
+int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                     long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
+                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
+                     size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                     int* err_flag, hipStream_t s);
 // beam_decode's loop around att_decode_step (att1 = encoder_att(feat), once per call, is the caller's; state0 is required)
 size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
 int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,

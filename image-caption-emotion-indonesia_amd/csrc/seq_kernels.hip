@@ -523,25 +523,24 @@ __global__ __launch_bounds__(256) void beam_init_kernel(void* beam, int n, int k
   }
 }
 
-// one step of image blockIdx.x: beam_topk_body over its live rows (row 0 alone at step 1) for its live[i] best, then
-// what beam_search_batched does on the host -- <end> completes a beam (score and sequence appended to the image's
-// completed list, by step then rank), every other beam survives into the next free slot
-__global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
-    void* beam, const float* __restrict__ logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
-    long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
-  __shared__ float s_score[kBeamMax];
-  __shared__ long long s_flat[kBeamMax];
+// what a step does with an image's `picked` best candidates (s_score / s_flat, flat = row in image * V + word, visible to
+// the whole workgroup) -- what beam_search_batched does on the host: <end> completes a beam (score and sequence appended to
+// the image's completed list, by step then rank), every other beam survives into the next free slot; dead slots still
+// take the decoder step, <end> on their own row. `live`: the image's live beams before the step (picked == live unless
+// the step had fewer candidates to offer). THREADS: the workgroup's size.
+template <int THREADS>
+__device__ __forceinline__ void beam_advance_tail(const BeamState& s, int i, int n, int k, int max_steps, int step,
+                                                  long long end_token, int V, int live, int picked, const float* s_score,
+                                                  const long long* s_flat, long long* __restrict__ next_words,
+                                                  long long* __restrict__ parent_rows) {
   __shared__ int s_parent[kBeamMax], s_word[kBeamMax], s_dst[kBeamMax];   // s_dst: slot, or -1 - index in the completed list
   __shared__ int s_alive;
-  const BeamState s = beam_state_of(beam, n, k, max_steps);
-  const int i = blockIdx.x, tid = threadIdx.x, L = max_steps + 2;
+  const int tid = threadIdx.x, L = max_steps + 2;
   const long row0 = (long)i * k;
-  const int live = s.live[i];
   if (live > 0) {
-    beam_topk_body(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
     if (tid == 0) {
       int alive = 0, done = s.n_done[i];
-      for (int j = 0; j < live; ++j) {
+      for (int j = 0; j < picked; ++j) {
         const int w = (int)(s_flat[j] % V);
         s_parent[j] = (int)(s_flat[j] / V);
         s_word[j] = w;
@@ -557,12 +556,12 @@ __global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
     const int* seq_in = s.seq + ((long)((step - 1) & 1) * n * k + row0) * L;
     int* seq_out = s.seq + ((long)(step & 1) * n * k + row0) * L;
     int* seq_done = s.done_seq + row0 * L;
-    for (int t = tid; t < live * (step + 1); t += kBeamThreads) {
+    for (int t = tid; t < picked * (step + 1); t += THREADS) {
       const int j = t / (step + 1), e = t % (step + 1);
       int* dst = s_dst[j] >= 0 ? seq_out + (long)s_dst[j] * L : seq_done + (long)(-1 - s_dst[j]) * L;
       dst[e] = e < step ? seq_in[(long)s_parent[j] * L + e] : s_word[j];
     }
-    if (tid < live) {
+    if (tid < picked) {
       const int d = s_dst[tid];
       if (d >= 0) {
         s.scores[row0 + d] = s_score[tid];
@@ -580,6 +579,80 @@ __global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
     next_words[row0 + tid] = end_token;
     parent_rows[row0 + tid] = row0 + tid;
   }
+}
+
+// one step of image blockIdx.x: beam_topk_body over its live rows (row 0 alone at step 1) for its live[i] best, then
+// beam_advance_tail
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
+    void* beam, const float* __restrict__ logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+    long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x;
+  const long row0 = (long)i * k;
+  const int live = s.live[i];
+  if (live > 0) beam_topk_body(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
+  beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, live, s_score, s_flat, next_words,
+                                  parent_rows);
+}
+
+// beam_advance_kernel on a step's candidates instead of its logits (capnet_vocab_topk: values / index [n k][k] best first,
+// index -1 = nothing; lse [n k]): image blockIdx.x takes its live[i] best of scores[row] - lse[row] + values[row][j] over
+// its live rows (row 0 alone at step 1) and j < k, ties to the lower flat index row * V + index -- beam_topk_body's
+// selection whenever no two scores tie after rounding, since a row's members of the image's top-live are among that
+// row's top-live logits (fp32 addition is monotone). At most 16 x 16 candidates: a thread per candidate, its rank the
+// number of candidates that beat it. A padded candidate is never chosen and never an address; an image that is offered
+// fewer candidates than it has live beams keeps that many.
+constexpr int kBeamTopkThreads = kBeamMax * kBeamMax;
+__global__ __launch_bounds__(kBeamTopkThreads) void beam_advance_topk_kernel(
+    void* beam, const float* __restrict__ values, const int* __restrict__ index, const float* __restrict__ lse, int V, int n,
+    int k, int max_steps, int step, long long end_token, long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ float s_cv[kBeamTopkThreads];
+  __shared__ long long s_cf[kBeamTopkThreads];
+  __shared__ int s_valid;
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const long row0 = (long)i * k;
+  const int live = s.live[i];
+  int picked = 0;
+  if (live > 0) {
+    const int rows = step == 1 ? 1 : live, nc = rows * k;
+    if (tid == 0) s_valid = 0;
+    __syncthreads();
+    float v = -INFINITY;
+    long long flat = 0x7fffffffffffffffLL;
+    bool ok = false;
+    if (tid < nc) {
+      const int r = tid / k, j = tid % k;
+      const int w = index[(row0 + r) * k + j];
+      ok = w >= 0 && w < V;
+      if (ok) {
+        const float base = s.scores[row0 + r] - lse[row0 + r];
+        v = base + values[(row0 + r) * k + j];
+        flat = (long long)r * V + w;
+        atomicAdd(&s_valid, 1);
+      }
+    }
+    s_cv[tid] = v;
+    s_cf[tid] = flat;
+    __syncthreads();
+    picked = min(live, s_valid);
+    if (ok) {
+      int rank = 0;
+      for (int c = 0; c < nc; ++c) {
+        const float ov = s_cv[c];
+        const long long of = s_cf[c];
+        rank += (of != 0x7fffffffffffffffLL && (ov > v || (ov == v && of < flat))) ? 1 : 0;
+      }
+      if (rank < picked) { s_score[rank] = v; s_flat[rank] = flat; }
+    }
+    __syncthreads();
+  }
+  beam_advance_tail<kBeamTopkThreads>(s, i, n, k, max_steps, step, end_token, V, live, picked, s_score, s_flat, next_words,
+                                      parent_rows);
 }
 
 // one wave per image: the first maximum of the completed scores in completion order; nothing completed -> [<end>]
@@ -629,6 +702,18 @@ int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, 
                  max_steps);
   hipLaunchKernelGGL(beam_advance_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps, step,
                      end_token, next_words, parent_rows);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k, int max_steps,
+                      int step, long long end_token, long long* next_words, long long* parent_rows, hipStream_t stream) {
+  if (int rc = beam_check("beam_advance_topk", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(values && index && lse && next_words && parent_rows, "beam_advance_topk: null argument");
+  CAPNET_REQUIRE(V >= 1 && k <= V && step >= 1 && step <= max_steps,
+                 "beam_advance_topk: V=%d k=%d step=%d max_steps=%d (k <= V; 1 <= step <= max_steps)", V, k, step, max_steps);
+  hipLaunchKernelGGL(beam_advance_topk_kernel, dim3(n), dim3(kBeamTopkThreads), 0, stream, beam, values, index, lse, V, n, k,
+                     max_steps, step, end_token, next_words, parent_rows);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

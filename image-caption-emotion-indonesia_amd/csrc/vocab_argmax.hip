@@ -239,17 +239,28 @@ int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, in
 // ---- the whole beam search of a plain stack: steps x (one gathered decode-step launch per layer + the vocabulary
 // projection + one beam_advance launch), then beam_finish -- capnet.beam.beam_search_device's loop without its host side
 // ws: [state A | state B] ([n k][2L][H] each) | h_top [n k][H] | logits [n k][V] | words A | words B | parent_rows (int64
-// [n k] each) | the beam_state_bytes block; every part starts 16-B aligned
+// [n k] each) | the beam_state_bytes block; every part starts 16-B aligned. fused (capnet_lstm_beam_decode on
+// capnet_vocab_topk): no logits block; in its place values f32 [n k][k] | index int32 [n k][k] | lse f32 [n k] |
+// vocab_topk's workspace
 struct BeamDecodeWs {
   size_t state, h_top, logits, words, parent, beam, total;   // byte offsets (state B at state + (h_top - state) / 2)
+  size_t tk_values, tk_index, tk_lse, tk_ws;                 // fused only
 };
-static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, int max_steps) {
+static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, int max_steps, bool fused = false) {
   const size_t nk = (size_t)n * k;
   BeamDecodeWs w;
   w.state = 0;
   w.h_top = 2 * gd_align(nk * 2 * nlayers * H * sizeof(float));
   w.logits = w.h_top + gd_align(nk * H * sizeof(float));
-  w.words = w.logits + gd_align(nk * V * sizeof(float));
+  w.words = w.logits + (fused ? 0 : gd_align(nk * V * sizeof(float)));
+  w.tk_values = w.tk_index = w.tk_lse = w.tk_ws = 0;
+  if (fused) {
+    w.tk_values = w.words;
+    w.tk_index = w.tk_values + gd_align(nk * k * sizeof(float));
+    w.tk_lse = w.tk_index + gd_align(nk * k * sizeof(int));
+    w.tk_ws = w.tk_lse + gd_align(nk * sizeof(float));
+    w.words = w.tk_ws + gd_align(vocab_topk_ws_bytes((int)nk, k, V));
+  }
   w.parent = w.words + 2 * gd_align(nk * 8);
   w.beam = w.parent + gd_align(nk * 8);
   w.total = w.beam + gd_align(beam_state_bytes(n, k, max_steps));
@@ -261,18 +272,25 @@ size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_ste
   return beam_decode_layout(nlayers, n, k, H, V, max_steps).total;
 }
 
-// the loop of both one-call searches: step(tokens, parent rows or null, state_in, state_out, h_top) is the decode step
+// the loop of the one-call searches: step(tokens, parent rows or null, state_in, state_out, h_top) is the decode step
+// (parent rows null: step 1). fused: the projection and the selection as vocab_topk + beam_advance_topk, no logits
+// block and no slab; else sgemm_splitk on the slab + beam_advance
 template <class Step>
 static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, long long start_token, long long end_token,
                      const float* Cw, const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats,
-                     int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn) {
+                     int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
+                     bool fused = false) {
   const int nk = n * k;
-  const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps);
+  const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
   char* p = reinterpret_cast<char*>(ws);
   float* state[2] = {reinterpret_cast<float*>(p + w.state), reinterpret_cast<float*>(p + w.state + w.h_top / 2)};
   float* h_top = reinterpret_cast<float*>(p + w.h_top);
   float* logits = reinterpret_cast<float*>(p + w.logits);
+  float* tk_values = reinterpret_cast<float*>(p + w.tk_values);
+  int* tk_index = reinterpret_cast<int*>(p + w.tk_index);
+  float* tk_lse = reinterpret_cast<float*>(p + w.tk_lse);
+  void* tk_ws = p + w.tk_ws;
   long long* words[2] = {reinterpret_cast<long long*>(p + w.words),
                          reinterpret_cast<long long*>(p + w.words + (w.parent - w.words) / 2)};
   long long* parent = reinterpret_cast<long long*>(p + w.parent);
@@ -282,12 +300,19 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
   else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
   if (int rc = beam_init(beam, n, k, max_steps, start_token, words[0], s)) return rc;
+  if (fused) CAPNET_HIP_CHECK(hipMemsetAsync(tk_ws, 0, 16, s));   // vocab_topk's counter
   int issued = 0;
   for (int step = 1; step <= max_steps; ++step) {
     // step 1: every beam is at its own (initial) row; afterwards the rows the previous beam_advance chose
     int rc = step_fn(words[(step - 1) & 1], step == 1 ? nullptr : parent, state[(step - 1) & 1], state[step & 1], h_top);
-    if (rc == kOk) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
-    if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
+    if (fused) {
+      if (rc == kOk) rc = vocab_topk(h_top, Cw, Cb, nk, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s);
+      if (rc == kOk)
+        rc = beam_advance_topk(beam, tk_values, tk_index, tk_lse, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
+    } else {
+      if (rc == kOk) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+      if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
+    }
     if (rc != kOk) return rc;
     issued = step;
     if (poll_every > 0 && step % poll_every == 0 && step < max_steps) {
@@ -312,6 +337,29 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
                      return stacked_decode_step(cell, nlayers, n * k, E, H, V, tok, emb, wcat, beff, sin, sout, h_top, err_flag, s,
                                                 parent, groups);
                    });
+}
+
+// ---- capnet.seq2seq's beam search: the same loop from a given state, step 1 on given inputs (EncoderRNN's feature
+// column) when first_inputs is set, the projection and selection fused (vocab_topk.hip) or as beam_decode's ----
+size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
+  if (nlayers < 1 || nlayers > 8 || n < 1 || H < 1 || V < 1 || k > V || !beam_state_bytes(n, k, max_steps)) return 0;
+  if ((long)n * k >= (1L << 24) || (fused_topk && !vocab_topk_supported(H, k, V))) return 0;
+  return beam_decode_layout(nlayers, n, k, H, V, max_steps, fused_topk != 0).total;
+}
+
+int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                     long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
+                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
+                     size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                     int* err_flag, hipStream_t s) {
+  return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
+                   lengths, steps_run, s,
+                   [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
+                     const bool given = !parent && first_inputs;     // step 1 on the caller's rows
+                     return stacked_decode_step(cell, nlayers, n * k, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
+                                                wcat, beff, sin, sout, h_top, err_flag, s, parent);
+                   },
+                   fused_topk != 0);
 }
 
 // ---- the same loop for the attention decoders: the step is att_decode_step (z, the two attention launches, layer 0 on

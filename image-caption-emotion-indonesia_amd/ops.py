@@ -258,6 +258,26 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows):
                                          ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance")
 
 
+def beam_advance_topk(beam, values, index, lse, step, end_token, next_words, parent_rows, V=None):
+    """capnet_beam_advance_topk: beam_advance on a step's candidates instead of its logits -- values float32 [n k, k] and
+    index int32 [n k, k] (per row its k best logits and their vocabulary entries, best first; -1: nothing), lse float32
+    [n k] (vocab_topk's outputs). V: the vocabulary size; it only bounds the indices and orders ties by (row, index), so
+    None (any bound above every index) selects the same."""
+    _need_cuda(values, index, lse, next_words, parent_rows)
+    nk, k = beam.n * beam.k, beam.k
+    if values.dtype != torch.float32 or tuple(values.shape) != (nk, k) or not values.is_contiguous() \
+            or index.dtype != torch.int32 or tuple(index.shape) != (nk, k) or not index.is_contiguous() \
+            or lse.dtype != torch.float32 or lse.numel() != nk or not lse.is_contiguous():
+        raise CapnetError("beam_advance_topk: values float32 [n k, k], index int32 [n k, k], lse float32 [n k], contiguous")
+    for w in (next_words, parent_rows):
+        if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
+            raise CapnetError("beam_advance_topk: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    check(_lib.lib().capnet_beam_advance_topk(ptr(beam.words), ptr(values), ptr(index), ptr(lse),
+                                              0x7fffffff if V is None else int(V), beam.n, k, beam.max_steps, int(step),
+                                              int(end_token), ptr(next_words), ptr(parent_rows), current_stream()),
+          "capnet_beam_advance_topk")
+
+
 def beam_finish(beam, end_token):
     """capnet_beam_finish -> (seqs int64 [n, max_steps + 2], lengths int32 [n], packed): the two are views of the one
     int64 buffer `packed`, so a caller takes both to the host in one copy."""
@@ -658,7 +678,45 @@ def lstm_greedy_decode_groups(steps, wcat, beff, embs, Cws, Cbs, start_tokens, s
     return ids, out
 
 
+def vocab_topk_workspace(rows, k, V, device):
+    """A zeroed workspace of capnet_vocab_topk for `rows` rows (back-to-back calls on one stream may share it)."""
+    n = _lib.lib().capnet_vocab_topk_ws_bytes(int(rows), int(k), int(V))
+    if not n:
+        raise CapnetError("vocab_topk: rows=%d k=%d V=%d (rows >= 1; 1 <= k <= 16; k <= V)" % (rows, k, V))
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vocab_topk(h, w, b=None, k=5, workspace=None):
+    """(values [rows, k] float32, index [rows, k] int32, lse [rows] float32) of the rows' logits h[r] . w[v] + b[v]
+    (capnet_vocab_topk: the projection, the k best per row -- logit descending, index ascending -- and the row's
+    log-sum-exp in one launch, no logits in memory). h [rows, H], w [V, H], b [V]; H in DECODE_HIDDEN; 1 <= k <= 16, k <= V.
+    A NaN or -inf logit is never picked; a row with fewer than k pickable entries ends in (-inf, -1)."""
+    _need_cuda(h, w, b)
+    h, w = _c(h.detach()), _c(w.detach())
+    b = None if b is None else _c(b.detach())
+    k = int(k)
+    if h.dim() != 2 or w.dim() != 2:
+        raise CapnetError("vocab_topk: h [rows, H], w [V, H]")
+    rows, H = h.shape
+    V = w.shape[0]
+    if w.shape[1] != H or H not in DECODE_HIDDEN or rows < 1 or (b is not None and b.numel() != V):
+        raise CapnetError("vocab_topk: h [rows, H], w [V, H], b [V] with H in %r" % (DECODE_HIDDEN,))
+    if not 1 <= k <= 16 or k > V:
+        raise CapnetError("vocab_topk: k=%d (1 <= k <= 16, k <= V = %d)" % (k, V))
+    if workspace is None:
+        workspace = vocab_topk_workspace(rows, k, V, h.device)
+    if workspace.numel() * workspace.element_size() < _lib.lib().capnet_vocab_topk_ws_bytes(rows, k, V):
+        raise CapnetError("vocab_topk: workspace too small")
+    values = torch.empty((rows, k), dtype=torch.float32, device=h.device)
+    index = torch.empty((rows, k), dtype=torch.int32, device=h.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=h.device)
+    check(_lib.lib().capnet_vocab_topk(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(workspace), ptr(values), ptr(index), ptr(lse),
+                                       current_stream()), "capnet_vocab_topk")
+    return values, index, lse
+
+
 _beam_decode_ws = {}
+_lstm_beam_decode_ws = {}
 
 
 def beam_decode_supported(E, H, k, V, num_layers):
@@ -719,6 +777,76 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     else:
         check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode")
+    tail[n:n + 1].copy_(flag)
+    host = packed.cpu()
+    htail = host[n * SL:].view(torch.int32)
+    if int(htail[n]):
+        check_device_errors()
+    lens = htail[:n].tolist()
+    rows = host[:n * SL].view(n, SL).tolist()
+    out = [rows[i][:lens[i]] for i in range(n)]
+    return (out, steps.value) if return_steps else out
+
+
+def lstm_beam_decode_supported(E, H, k, V, num_layers):
+    """The shapes capnet_lstm_beam_decode takes, fused top-k or not: those of its parts (the decode step, capnet_vocab_topk,
+    capnet_beam_advance)."""
+    return beam_decode_supported(E, H, k, V, num_layers)
+
+
+def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, first_inputs=None, state=None,
+                     fused_topk=True, poll_every=0, return_steps=False):
+    """The beam search of a stack from a given state in ONE C call (capnet_lstm_beam_decode): n sentences x k beams, at most
+    max_steps steps, then capnet_beam_finish. fused_topk: a step is (gathered decode step, capnet_vocab_topk,
+    capnet_beam_advance_topk) -- no logits in memory; else beam_decode's step (the projection on sgemm_splitk's slab,
+    capnet_beam_advance) in the same call. first_inputs [n k, E]: step 1 feeds these rows to layer 0 instead of
+    emb[start_token] (EncoderRNN's feature column). state: [n k, 2L, H] or None for zeros. Everything else as beam_decode:
+    the workspace is cached per (device, shape); sequences, lengths and the error word come to the host in one copy.
+    Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("lstm_beam_decode: unknown cell %r" % (cell,))
+    _need_cuda(emb, Cw, Cb, state, first_inputs, *wcat, *beff)
+    emb, Cw = _c(emb.detach()), _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    V, E = emb.shape
+    H, nl = Cw.shape[1], len(wcat)
+    n, k, T, fused = int(n), int(k), int(max_steps), int(bool(fused_topk))
+    if n < 1 or T < 1 or len(beff) != nl or tuple(Cw.shape) != (V, H) or not lstm_beam_decode_supported(E, H, k, V, nl):
+        raise CapnetError("lstm_beam_decode: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
+                          % (E, H, V, k, nl, n, T))
+    if Cb is not None and Cb.numel() != V:
+        raise CapnetError("lstm_beam_decode: Cb must be [V]")
+    _check_layer_weights("lstm_beam_decode", wcat, beff, 1, H, (E + 15) // 16 * 16)
+    dev = emb.device
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (n * k, 2 * nl, H):
+            raise CapnetError("lstm_beam_decode: state must be [n k, 2L, H]")
+    if first_inputs is not None:
+        first_inputs = _c(first_inputs.detach())
+        if tuple(first_inputs.shape) != (n * k, E) or first_inputs.dtype != torch.float32:
+            raise CapnetError("lstm_beam_decode: first_inputs must be float32 [n k, E]")
+    L = _lib.lib()
+    key = (dev.index or 0, nl, n, k, H, V, T, fused)
+    ws = _lstm_beam_decode_ws.get(key)
+    if ws is None:
+        nbytes = L.capnet_lstm_beam_decode_ws_bytes(nl, n, k, H, V, T, fused)
+        if not nbytes:
+            raise CapnetError("lstm_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        _lstm_beam_decode_ws[key] = ws
+    slab = None if fused else splitk_slab(dev)
+    SL = T + 2
+    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
+    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
+    tail = packed[n * SL:].view(torch.int32)
+    flag = err_flag(dev)
+    steps = C.c_int(0)
+    check(L.capnet_lstm_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(first_inputs), ptr(emb),
+                                    ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
+                                    0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
+                                    C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
+          "capnet_lstm_beam_decode")
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)

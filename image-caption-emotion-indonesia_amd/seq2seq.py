@@ -26,6 +26,15 @@ stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with 
     layer on a (H / 4, decoders) grid and one vocab_argmax launch on a (V / 32, decoders) grid, workgroup (., g) on
     decoder g's own embedding, LSTM weights and projection. The embeddings and projections are used where they lie (one
     pointer per decoder); only the packed LSTM weights are stacked. Every entry equals sample(mode=...) exactly.
+  * Beam search: sample_beam on all three classes (the reference has none here; the loop is the image decoders',
+    oracle.beam_ref._beam) -- B sentences x k beams as ONE capnet_lstm_beam_decode call from the given state, the
+    encoder's first step on `features`. Per step one gathered decode-step launch per layer, then either the FUSED
+    selection (csrc/vocab_topk.hip: projection, per-row top-k and log-sum-exp in one launch, no logits in memory, and
+    capnet_beam_advance_topk on the candidates) or capnet_beam_decode's (sgemm_splitk's logits block, capnet_beam_advance).
+    fused_topk=None routes by FUSED_TOPK_MAX_ROWS, set from profiles/time_seq2seq_beam.jsonl; CAPNET_NO_FUSED_TOPK=1 (read
+    at every call) forces the unfused step. A shape the decode kernel does not take, or CAPNET_NO_FUSED_DECODE_STEP=1:
+    capnet.beam.beam_search_device on cell_stepper. Same lists on every route (under the margin rule: the fused logits
+    differ from the slab's in the last bits).
 """
 import os
 import random
@@ -35,7 +44,8 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .decode import cell_stepper, check_styles, pack_cells
+from .beam import beam_search_device
+from .decode import cell_stepper, check_styles, fused_decode_step, pack_cells
 from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
 
@@ -43,6 +53,10 @@ device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # seq2seq
 
 FUSED_GREEDY_OFF = "CAPNET_NO_FUSED_GREEDY"
 FUSED_GREEDY_MAX_ROWS = 16
+FUSED_TOPK_OFF = "CAPNET_NO_FUSED_TOPK"
+# the largest n k at which the fused step's median beat the unfused step's by more than the spread at 1, 2 and 3 layers
+# (profiles/time_seq2seq_beam.jsonl); above it fused_topk=None takes the unfused step in the same C call
+FUSED_TOPK_MAX_ROWS = 15
 _EMOTIONS = ("happy", "sad", "angry")
 
 
@@ -168,6 +182,50 @@ class _RNN(nn.Module):
             return torch.stack(ids, 1), state
 
 
+    def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk):
+        """Beam search of B = state.shape[0] sentences x k beams from `state` [B, 2L, H]; the first input is `features`
+        [B, E] or, None, embed(start_token). max_seq_length + 1 steps at most. Returns B token lists, each starting with
+        start_token ([end_token] where nothing completed). Routing: the module's docstring."""
+        E, H, V, L = self.embed_size, self.hidden_size, self.vocab_size, self.num_layers
+        k = int(k)
+        if not 1 <= k <= 16 or k > V:
+            raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, V))
+        emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
+        layers = self._layers()
+        B = state.shape[0]
+        with torch.no_grad():
+            state = state.detach().repeat_interleave(k, 0).contiguous()
+            first = None if features is None else features.detach().float().repeat_interleave(k, 0).contiguous()
+            if fused_decode_step(L, E, H) and ops.lstm_beam_decode_supported(E, H, k, V, L):
+                if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
+                    fused = False
+                elif fused_topk is None:
+                    fused = B * k <= FUSED_TOPK_MAX_ROWS
+                else:
+                    fused = bool(fused_topk)
+                packed = pack_cells(layers, E)
+                return ops.lstm_beam_decode(ops.CELL_LSTM, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb, B, k,
+                                            self.max_seq_length + 1, start_token, end_token, first_inputs=first, state=state,
+                                            fused_topk=fused, poll_every=poll_every)
+            step = cell_stepper(layers, E, H)
+            calls = [0]
+
+            def step_fn(prev_words, st):
+                calls[0] += 1
+                if calls[0] == 1 and first is not None:
+                    top, new = step(first, None, st[0])
+                else:
+                    top, new = step(emb, prev_words, st[0])
+                return ops.linear(top, Cw, Cb), (new,)
+            return beam_search_device(step_fn, (state,), B, V, start_token, end_token, k, self.max_seq_length,
+                                      emb.device, poll_every)
+
+    def _rows_state(self, states, rows, dev):
+        h, c = states
+        zeros = torch.zeros((self.num_layers, rows, self.hidden_size), dtype=torch.float32, device=dev)
+        return _to_rows(zeros if h is None else h, zeros if c is None else c)
+
+
 class EncoderRNN(_RNN):
     """seq2seq/model.py:30-122."""
 
@@ -190,6 +248,16 @@ class EncoderRNN(_RNN):
             state = _to_rows(zeros if h is None else h, zeros if c is None else c)
         ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
         return ids, _from_rows(state)
+
+    def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None):
+        """Beam search (k beams per sentence, max_seq_length + 1 steps at most, a beam completes at end_token) whose first
+        input is `features` [B, E]: a list of B token lists. start_token only seeds the bookkeeping (no step reads its
+        embedding), so it is dropped from every list that has more than one element; [end_token] where nothing completed.
+        poll_every as capnet.beam.beam_search_device; fused_topk: None routes by FUSED_TOPK_MAX_ROWS, True / False force
+        the fused / unfused step (CAPNET_NO_FUSED_TOPK=1 forces False)."""
+        state = self._rows_state(states, features.size(0), features.device)
+        lists = self._beam_search(features, start_token, end_token, state, k, poll_every, fused_topk)
+        return [s[1:] if len(s) > 1 else s for s in lists]
 
 
 class DecoderRNN(_RNN):
@@ -214,6 +282,17 @@ class DecoderRNN(_RNN):
         ids, _ = self._greedy(None, tokens, state)
         ops.check_device_errors()
         return ids
+
+    def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None):
+        """Beam search from embed(start_token) and `states` (h, c) [num_layers, B, H]: a list of B token lists, one per
+        column of `states`, each what oracle.beam_ref._beam returns for that sentence -- it begins with start_token, and is
+        [end_token] where nothing completed. max_seq_length + 1 steps at most. poll_every / fused_topk: as
+        EncoderRNN.sample_beam. An out-of-range start_token raises CapnetError through the device error word."""
+        h, c = states
+        given = h if h is not None else c
+        rows = 1 if given is None else given.size(1)
+        state = self._rows_state(states, rows, self.embed.weight.device)
+        return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk)
 
 
 class Seq2Seq(nn.Module):
@@ -253,6 +332,17 @@ class Seq2Seq(nn.Module):
         if decoder is None:
             return sampled_ids
         return decoder.sample(start_token, states)
+
+    def sample_beam(self, features, start_token, end_token, states=(None, None), mode='factual', k=5, poll_every=0,
+                    fused_topk=None):
+        """factual: the encoder's beam search (EncoderRNN.sample_beam). An emotion mode: the encoder's GREEDY sample for
+        the state, as sample() does, then that decoder's beam search from it (DecoderRNN.sample_beam). A list of B token
+        lists."""
+        decoder = None if mode == 'factual' else self._decoder(mode)
+        if decoder is None:
+            return self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk)
+        _, states = self.encoder.sample(features, states)
+        return decoder.sample_beam(start_token, end_token, states, k, poll_every, fused_topk)
 
     def _check_mode(self, mode):
         if mode != 'factual':

@@ -124,6 +124,17 @@ int capnet_beam_advance(void* beam, const float* logits, long ld, int V, int n, 
                         long long end_token, long long* next_words, long long* parent_rows, capnet_stream_t stream);
 int capnet_beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
                        capnet_stream_t stream);
+/* capnet_beam_advance on a step's CANDIDATES instead of its logits (capnet_vocab_topk's outputs): values f32 [n k][k] and
+ * index int32 [n k][k], per row its k best logits and their vocabulary entries, best first, index -1 where a row had
+ * fewer; lse f32 [n k], the rows' log-sum-exp. Image i takes its live[i] best of scores[row] - lse[row] + values[row][j]
+ * over its live rows (row 0 alone at step 1) and j < k, ties to the lower flat index row_in_image V + index[row][j]; from
+ * there on it is capnet_beam_advance (one device function serves both). fp32 addition is monotone, so a row's members of
+ * the image's top-live are among that row's top-live logits: the selection is capnet_beam_advance's on the same logits
+ * whenever no two candidate scores tie after rounding. A padded candidate is never chosen and never used as an address;
+ * an image that is offered fewer candidates than it has live beams keeps that many beams. 1 <= k <= 16, k <= V. */
+int capnet_beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k,
+                             int max_steps, int step, long long end_token, long long* next_words, long long* parent_rows,
+                             capnet_stream_t stream);
 int capnet_beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live,
                      const float** scores);
 
@@ -669,6 +680,42 @@ int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, i
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                               float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
                               int* err_flag, capnet_stream_t stream);
+
+/* The vocabulary projection of a beam step without its logits: for every row r < rows, over logit[v] = h[r] . w[v] + b[v]
+ * (nn.Linear: w [V][H], b [V] or NULL), in ONE launch, fp32 throughout:
+ *   index[r][0..k)  the k best entries by (logit descending, index ascending)       int32 [rows][k]
+ *   values[r][j]    their logits                                                    f32 [rows][k]
+ *   lse[r]          log(sum_v exp(logit[v]))                                        f32 [rows]
+ * A NaN or -inf logit is never picked and does not enter the sum; a row with fewer than k pickable entries pads its tail
+ * with (-inf, -1). A workgroup owns 32 entries and all rows and emits, per row, its maximum m_w, s_w = sum expf(logit -
+ * m_w) and its k best; the workgroup that arrives last at the arrival counter merges them in a fixed order (M = max m_w,
+ * lse = M + logf(sum s_w expf(m_w - M))), so the result does not depend on which workgroup that is. No workgroup waits on
+ * another. 1 <= k <= 16, k <= V, rows >= 1, H in {64, 128, 256, 512, 1024}; h, w and the workspace 16-B aligned.
+ * workspace: capnet_vocab_topk_ws_bytes(rows, k, V) bytes (0 outside the limits) of device memory whose first 16 bytes are
+ * ZERO before the first use (the arrival counter; every launch leaves them zero, so back-to-back calls on one stream may
+ * share a workspace; calls on different streams may not). Bad arguments are refused before any launch. */
+size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V);
+int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
+                      float* values, int* index, float* lse, capnet_stream_t stream);
+
+/* capnet_beam_decode's loop for a stack that starts from a GIVEN state and, optionally, from given first inputs
+ * (capnet.seq2seq: DecoderRNN.sample_beam from the encoder's state, EncoderRNN.sample_beam from the feature column), one
+ * weight group. first_inputs non-NULL ([n k][E], 16-B aligned): step 1 feeds those rows to layer 0 instead of
+ * emb[start_token]; start_token then only seeds the sequences.
+ * fused_topk = 1: a step is the gathered decode step (one launch per layer), capnet_vocab_topk on h_top and
+ * capnet_beam_advance_topk; the workspace has no logits block and slab may be NULL. fused_topk = 0: a step is
+ * capnet_beam_decode's (capnet_sgemm_splitk's entry on `slab`, at least n k V floats, then capnet_beam_advance).
+ * workspace: capnet_lstm_beam_decode_ws_bytes(...) bytes, 16-B aligned, contents irrelevant (the two state buffers, h_top,
+ * the logits or, fused, values | index | lse | capnet_vocab_topk's workspace, two word buffers, the parent rows and the
+ * beam state; 0 outside the limits). Everything else -- cell, wcat, beff, emb, Cw, Cb, state0, seqs, lengths,
+ * poll_every, *steps_run, the error word -- as capnet_beam_decode. The call allocates nothing; every bad argument is
+ * refused before any launch. */
+size_t capnet_lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
+int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                            long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
+                            const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                            float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
+                            int* steps_run, int* err_flag, capnet_stream_t stream);
 
 /* One beam step of an attention decoder (DecoderFactoredLSTMAtt / DecoderRNNAtt and their stacked forms) without the
  * vocabulary projection, for n images x k fixed slots (row r belongs to image r / k), on `stream`, in this order:
