@@ -160,10 +160,16 @@ SIGNATURES = {
                                        C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
     "capnet_vocab_topk_ws_bytes": (_sz, [_i, _i, _i]),
     "capnet_vocab_topk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_vocab_topk_groups_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "capnet_vocab_topk_groups": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "capnet_beam_advance_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),
     "capnet_lstm_beam_decode_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "capnet_lstm_beam_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, _vp, C.POINTER(_vp),
                                      C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
+    "capnet_lstm_beam_decode_groups_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "capnet_lstm_beam_decode_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.POINTER(_vp),
+                                            C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _sz,
+                                            _i, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
     "capnet_att_decode_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step": (_i, [_i] * 10 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _sz,

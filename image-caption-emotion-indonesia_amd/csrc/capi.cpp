@@ -565,6 +565,26 @@ int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, 
   return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream));
 }
 
+size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
+  return vocab_topk_groups_ws_bytes(groups, rows_per_group, k, V);
+}
+
+int capnet_vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                             int H, int V, int k, void* workspace, float* values, int* index, float* lse,
+                             capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "vocab_topk: groups %d (1..8)", groups);
+  CAPNET_REQUIRE(rows_per_group >= 1 && rows_per_group < (1 << 24) && V >= 1, "vocab_topk: rows per group %d, V %d",
+                 rows_per_group, V);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "vocab_topk: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
+  CAPNET_REQUIRE(vocab_topk_supported(H, k, V), "vocab_topk: unsupported H=%d", H);
+  CAPNET_REQUIRE(h && w && workspace && values && index && lse, "vocab_topk: null argument");
+  CAPNET_REQUIRE(aligned16(h) && aligned16(workspace), "vocab_topk: h, w and the workspace must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)lse % 4 == 0, "vocab_topk: output alignment");
+  for (int g = 0; g < groups; ++g)
+    CAPNET_REQUIRE(w[g] && aligned16(w[g]), "vocab_topk: projection of group %d is null or not 16-B aligned", g);
+  return vocab_topk_groups(h, w, b, groups, rows_per_group, H, V, k, workspace, values, index, lse, S(stream));
+}
+
 size_t capnet_lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
   return lstm_beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps, fused_topk);
 }
@@ -600,6 +620,52 @@ int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, i
   return lstm_beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb, wcat, beff, Cw, Cb,
                           state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
                           S(stream));
+}
+
+size_t capnet_lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps,
+                                               int fused_topk) {
+  return lstm_beam_decode_groups_ws_bytes(nlayers, groups, n, k, H, V, max_steps, fused_topk);
+}
+
+// n below: the sentences of one group; the checks are capnet_lstm_beam_decode's at groups x n sentences
+int capnet_lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                                   long long start_token, long long end_token, const float* const* emb,
+                                   const float* const* wcat, const float* const* beff, const float* const* Cw,
+                                   const float* const* Cb, const float* state0, void* workspace, float* slab,
+                                   size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
+                                   int* steps_run, int* err_flag, capnet_stream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "lstm_beam_decode: groups %d (1..8)", groups);
+  const long nq = n >= 1 && n < (1 << 24) ? (long)groups * n : 0;
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "lstm_beam_decode: unknown cell %d", cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_beam_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(nq >= 1 && nq < (1 << 24) && max_steps >= 1 && V >= 1 && poll_every >= 0,
+                 "lstm_beam_decode: n %d, max_steps %d, V %d, poll_every %d", n, max_steps, V, poll_every);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "lstm_beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
+  CAPNET_REQUIRE(nq * k * (max_steps + 2) < (1L << 28) && nq * k * V < (1L << 31) && nq * k < (1L << 24),
+                 "lstm_beam_decode: n k too large");
+  CAPNET_REQUIRE(stacked_decode_supported(E, H), "lstm_beam_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE(!fused_topk || vocab_topk_supported(H, k, V), "lstm_beam_decode: the fused top-k does not take H=%d", H);
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "lstm_beam_decode: start_token %lld", start_token);
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && seqs && lengths && err_flag, "lstm_beam_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && (!state0 || aligned16(state0)),
+                 "lstm_beam_decode: workspace, Cw and state0 must be 16-B aligned");
+  for (int g = 0; g < groups; ++g) {
+    CAPNET_REQUIRE(emb[g] && Cw[g], "lstm_beam_decode: null argument (embedding or projection of group %d)", g);
+    CAPNET_REQUIRE(aligned16(emb[g]) && aligned16(Cw[g]), "lstm_beam_decode: emb and Cw must be 16-B aligned (group %d)", g);
+  }
+  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "lstm_beam_decode: seqs / lengths alignment");
+  if (!fused_topk) {
+    CAPNET_REQUIRE(slab && aligned16(slab), "lstm_beam_decode: without the fused top-k the slab is required, 16-B aligned");
+    CAPNET_REQUIRE(slab_floats >= (size_t)nq * k * V, "lstm_beam_decode: the slab holds %zu floats, one [n k][V] block is %zu",
+                   slab_floats, (size_t)nq * k * V);
+  }
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_beam_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_beam_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return lstm_beam_decode_groups(cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
+                                 state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
+                                 S(stream));
 }
 
 int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {

@@ -324,6 +324,12 @@ bool vocab_topk_supported(int H, int k, int V);
 size_t vocab_topk_ws_bytes(int rows, int k, int V);
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
                int* index, float* lse, hipStream_t stream);
+// weight groups, as vocab_argmax_groups: rows = groups x rpg, group-major; group g's rows on w[g] / b[g] (host-side pointer
+// tables, b or any b[g] may be null) in the same launch, one arrival counter and one block of partials per group (ws:
+// vocab_topk_groups_ws_bytes, its first 16 groups bytes zero before the first use); outputs [groups rpg][k] / [groups rpg]
+size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V);
+int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream);
 // beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set; fused_topk: a step's
 // projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else beam_decode's
 size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
@@ -332,6 +338,15 @@ int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, i
                      const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                      size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths, int* steps_run,
                      int* err_flag, hipStream_t s);
+// the same loop over groups x n sentences, group-major, group g on emb[g] / wcat[l] + g 4H (kin + H) / beff[l] + g 4H / Cw[g] /
+// Cb[g] (host-side pointer tables; Cb or any Cb[g] may be null): per step the gathered decode step on per-group tables,
+// then vocab_topk_groups + beam_advance_topk, or one sgemm_splitk per group into its row block of the logits + beam_advance
+size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk);
+int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                            long long start_token, long long end_token, const float* const* emb, const float* const* wcat,
+                            const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
+                            void* ws, float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
+                            int* lengths, int* steps_run, int* err_flag, hipStream_t s);
 // beam_decode's loop around att_decode_step (att1 = encoder_att(feat), once per call, is the caller's; state0 is required)
 size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
 int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,

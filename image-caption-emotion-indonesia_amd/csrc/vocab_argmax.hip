@@ -246,7 +246,8 @@ struct BeamDecodeWs {
   size_t state, h_top, logits, words, parent, beam, total;   // byte offsets (state B at state + (h_top - state) / 2)
   size_t tk_values, tk_index, tk_lse, tk_ws;                 // fused only
 };
-static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, int max_steps, bool fused = false) {
+static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, int max_steps, bool fused = false,
+                                       int groups = 1) {   // n: all sentences, groups x sentences per group
   const size_t nk = (size_t)n * k;
   BeamDecodeWs w;
   w.state = 0;
@@ -259,7 +260,7 @@ static BeamDecodeWs beam_decode_layout(int nlayers, int n, int k, int H, int V, 
     w.tk_index = w.tk_values + gd_align(nk * k * sizeof(float));
     w.tk_lse = w.tk_index + gd_align(nk * k * sizeof(int));
     w.tk_ws = w.tk_lse + gd_align(nk * sizeof(float));
-    w.words = w.tk_ws + gd_align(vocab_topk_ws_bytes((int)nk, k, V));
+    w.words = w.tk_ws + gd_align(vocab_topk_groups_ws_bytes(groups, (int)nk / groups, k, V));
   }
   w.parent = w.words + 2 * gd_align(nk * 8);
   w.beam = w.parent + gd_align(nk * 8);
@@ -274,14 +275,16 @@ size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_ste
 
 // the loop of the one-call searches: step(tokens, parent rows or null, state_in, state_out, h_top) is the decode step
 // (parent rows null: step 1). fused: the projection and the selection as vocab_topk + beam_advance_topk, no logits
-// block and no slab; else sgemm_splitk on the slab + beam_advance
+// block and no slab; else sgemm_splitk on the slab + beam_advance. Cwg / Cbg (capnet_lstm_beam_decode_groups): n = groups x
+// sentences per group, group-major, and group g's rows are projected on Cwg[g] / Cbg[g] -- fused, one vocab_topk_groups
+// launch; else one sgemm_splitk per group into the group's row block of the logits, one after the other on the one slab
 template <class Step>
 static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, long long start_token, long long end_token,
                      const float* Cw, const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats,
                      int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
-                     bool fused = false) {
-  const int nk = n * k;
-  const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused);
+                     bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr) {
+  const int nk = n * k, rpg = nk / groups;
+  const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused, groups);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
   char* p = reinterpret_cast<char*>(ws);
   float* state[2] = {reinterpret_cast<float*>(p + w.state), reinterpret_cast<float*>(p + w.state + w.h_top / 2)};
@@ -300,17 +303,22 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
   else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
   if (int rc = beam_init(beam, n, k, max_steps, start_token, words[0], s)) return rc;
-  if (fused) CAPNET_HIP_CHECK(hipMemsetAsync(tk_ws, 0, 16, s));   // vocab_topk's counter
+  if (fused) CAPNET_HIP_CHECK(hipMemsetAsync(tk_ws, 0, 16 * (size_t)groups, s));   // vocab_topk's counters, one per group
   int issued = 0;
   for (int step = 1; step <= max_steps; ++step) {
     // step 1: every beam is at its own (initial) row; afterwards the rows the previous beam_advance chose
     int rc = step_fn(words[(step - 1) & 1], step == 1 ? nullptr : parent, state[(step - 1) & 1], state[step & 1], h_top);
     if (fused) {
-      if (rc == kOk) rc = vocab_topk(h_top, Cw, Cb, nk, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s);
+      if (rc == kOk)
+        rc = Cwg ? vocab_topk_groups(h_top, Cwg, Cbg, groups, rpg, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s)
+                 : vocab_topk(h_top, Cw, Cb, nk, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s);
       if (rc == kOk)
         rc = beam_advance_topk(beam, tk_values, tk_index, tk_lse, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
     } else {
-      if (rc == kOk) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+      for (int g = 0; Cwg && g < groups && rc == kOk; ++g)
+        rc = sgemm_splitk(false, true, rpg, V, H, h_top + (size_t)g * rpg * H, H, Cwg[g], H, logits + (size_t)g * rpg * V, V,
+                          Cbg ? Cbg[g] : nullptr, 0, slab, slab_floats, s);
+      if (rc == kOk && !Cwg) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
       if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
     }
     if (rc != kOk) return rc;
@@ -360,6 +368,29 @@ int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, i
                                                 wcat, beff, sin, sout, h_top, err_flag, s, parent);
                    },
                    fused_topk != 0);
+}
+
+// ---- every emotion decoder of capnet.seq2seq in one search: groups x n sentences, group g on its own embedding, LSTM
+// weights and projection (the decode step on a (H / 4, groups) grid with per-group tables, parents gathered in the kernel)
+size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk) {
+  if (groups < 1 || groups > 8 || n < 1 || n >= (1 << 24)) return 0;
+  if (!lstm_beam_decode_ws_bytes(nlayers, groups * n, k, H, V, max_steps, fused_topk)) return 0;
+  return beam_decode_layout(nlayers, groups * n, k, H, V, max_steps, fused_topk != 0, groups).total;
+}
+
+int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                            long long start_token, long long end_token, const float* const* emb, const float* const* wcat,
+                            const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
+                            void* ws, float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
+                            int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+  const int nq = groups * n;
+  return beam_loop(nlayers, nq, k, H, V, max_steps, start_token, end_token, nullptr, nullptr, state0, ws, slab, slab_floats,
+                   poll_every, seqs, lengths, steps_run, s,
+                   [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
+                     return stacked_decode_step(cell, nlayers, nq * k, E, H, V, tok, emb[0], wcat, beff, sin, sout, h_top, err_flag,
+                                                s, parent, groups, emb);
+                   },
+                   fused_topk != 0, groups, Cw, Cb);
 }
 
 // ---- the same loop for the attention decoders: the step is att_decode_step (z, the two attention launches, layer 0 on

@@ -24,6 +24,15 @@
 //   the winning lane re-reads its lists' heads (a list's head position is the number of winners so far in its 32
 //   columns). A row with fewer than k pickable entries pads with (-inf, -1).
 // The counter is zero before the first use and zero again when the launch ends. Plain vector loads and stores only.
+// Weight groups (every emotion of capnet.seq2seq at once: capnet_vocab_topk_groups, capnet_lstm_beam_decode_groups):
+// vocab_argmax_kernel's grouping to the letter. The grid is (ceil(V / 32), G), rows are group-major, and workgroup (., g)
+// walks only rows [g rpg, (g + 1) rpg) on w[g] / b[g] -- one pointer per group held by value in the argument struct and picked
+// by blockIdx.y, a scalar load from the kernel arguments; no projection is stacked or copied. Everything below the pick
+// works on the group's own rows, numbered from 0: the row clamp and the store mask end at the group, so a 16-row tile
+// never reaches into the next one. Group g owns its block of stat and cand and its OWN arrival counter (16 bytes apart),
+// where arrivals are counted against gridDim.x: group g's last arriver merges group g's rows only (lpr by rpg, not by the
+// total row count) and re-arms that counter only. The groups never meet. G = 1 is the kernel as it was: the same grid,
+// the same addresses, the same bits.
 #include "common.h"
 #include "kernels.h"
 #include "step_core.h"
@@ -36,17 +45,19 @@ constexpr int kVtNone = 0x7fffffff;
 constexpr int kVtMaxK = 16;
 constexpr int kVtBatch = 8;          // independent loads in flight per lane in the merge
 
+constexpr int kVtMaxGroups = 8;      // weight groups of one launch
+
 struct VocabTopkArgs {
-  const float* h;            // [rows][H]
-  const float* w;            // [V][H]
-  const float* b;            // [V] or null
-  unsigned long long* stat;  // [workgroups][rows]: (m_w bits << 32) | s_w bits
-  unsigned long long* cand;  // [workgroups][rows][k]: (value bits << 32) | index, best first; index -1 = nothing
-  int* counter;              // zero before the first use, zero again when the launch ends
-  float* values;             // [rows][k]
-  int* index;                // [rows][k]
-  float* lse;                // [rows]
-  int rows, H, V, k;
+  const float* h;            // [groups rpg][H], group-major
+  unsigned long long* stat;  // [groups][workgroups][rpg]: (m_w bits << 32) | s_w bits
+  unsigned long long* cand;  // [groups][workgroups][rpg][k]: (value bits << 32) | index, best first; index -1 = nothing
+  int* counter;              // group g's at counter + 4 g; zero before the first use, zero again when the launch ends
+  float* values;             // [groups rpg][k]
+  int* index;                // [groups rpg][k]
+  float* lse;                // [groups rpg]
+  int rpg, H, V, k;          // rows per group: workgroup (., g) owns rows [g rpg, (g + 1) rpg)
+  const float* w[kVtMaxGroups];   // [V][H] of group g
+  const float* b[kVtMaxGroups];   // [V] of group g, or null
 };
 
 __device__ __forceinline__ unsigned long long vt_pack(float hi, unsigned lo) {
@@ -70,25 +81,36 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lq = lane >> 4;
   const int tile = wave >> 2, ks = wave & 3;
-  const int H = a.H, rows = a.rows, k = a.k, c0 = blockIdx.x * kVtCols;
+  const int H = a.H, rows = a.rpg, k = a.k, c0 = blockIdx.x * kVtCols;
+  // this group's rows, numbered from 0 below: its slice of h and of the outputs, its blocks of stat and cand, its counter
+  const int grp = blockIdx.y;
+  const long rbeg = (long)grp * rows;
+  const float* gh = a.h + rbeg * H;
+  const float* bg = a.b[grp];
+  unsigned long long* gstat = a.stat + (long)grp * gridDim.x * rows;
+  unsigned long long* gcand = a.cand + (long)grp * gridDim.x * rows * k;
+  float* gvalues = a.values + rbeg * k;
+  int* gindex = a.index + rbeg * k;
+  float* glse = a.lse + rbeg;
+  int* gcounter = a.counter + 4 * grp;
   const int g0 = ks * NJ;                                   // this wave's k groups [g0, g0 + NJ): H = 64 NJ
   const int wcol = clamp_row(c0 + 16 * tile + li, a.V);      // entries beyond V: masked in the epilogue
-  const float* wrow = a.w + (long)wcol * H + 16 * g0 + 4 * lq;
+  const float* wrow = a.w[grp] + (long)wcol * H + 16 * g0 + 4 * lq;
   f32x4 wv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) wv[j] = *reinterpret_cast<const f32x4*>(wrow + 16 * j);
   // epilogue thread: (row er of a 16-row tile, entry ec of the workgroup's 32)
   const int er = tid >> 5, ec = tid & 31;
   const int ecol = c0 + ec;
-  const float bias = (a.b && ecol < a.V) ? a.b[ecol] : 0.f;
-  unsigned long long* stat = a.stat + (long)blockIdx.x * rows;
-  unsigned long long* cand = a.cand + (long)blockIdx.x * rows * k;
+  const float bias = (bg && ecol < a.V) ? bg[ecol] : 0.f;
+  unsigned long long* stat = gstat + (long)blockIdx.x * rows;
+  unsigned long long* cand = gcand + (long)blockIdx.x * rows * k;
   for (int r0 = 0; r0 < rows; r0 += kPass) {
     f32x4 acc[TM];
 #pragma unroll
     for (int m = 0; m < TM; ++m) {
       const int row = clamp_row(r0 + 16 * m + li, rows);
-      const float* hrow = a.h + (long)row * H + 16 * g0 + 4 * lq;
+      const float* hrow = gh + (long)row * H + 16 * g0 + 4 * lq;
       f32x4 av[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j) av[j] = *reinterpret_cast<const f32x4*>(hrow + 16 * j);
@@ -132,10 +154,10 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0)
-    s_last = __hip_atomic_fetch_add(a.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    s_last = __hip_atomic_fetch_add(gcounter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
   __syncthreads();
   if (!s_last) return;
-  // the last arriver: `lpr` lanes per row (a whole wave for few rows, a quarter for many: the merge of a row is a chain of
+  // the group's last arriver: `lpr` lanes per row (a whole wave for few rows, a quarter for many: the merge of a row is a chain of
   // dependent loads, so rows side by side hide it), the workgroups across those lanes. Every lane runs every shuffle; a
   // lane group without a row works on a copy of the last row and stores nothing.
   const int nwg = gridDim.x;
@@ -152,7 +174,7 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
     for (int p0 = sl; p0 < nwg; p0 += kVtBatch * lpr) {
       unsigned long long u[kVtBatch];
 #pragma unroll
-      for (int q = 0; q < kVtBatch; ++q) u[q] = vt_load(a.stat + (long)min(p0 + q * lpr, nwg - 1) * rows + row);
+      for (int q = 0; q < kVtBatch; ++q) u[q] = vt_load(gstat + (long)min(p0 + q * lpr, nwg - 1) * rows + row);
 #pragma unroll
       for (int q = 0; q < kVtBatch; ++q)
         if (p0 + q * lpr < nwg) M = fmaxf(M, __uint_as_float((unsigned)(u[q] >> 32)));
@@ -162,7 +184,7 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
     for (int p0 = sl; p0 < nwg; p0 += kVtBatch * lpr) {
       unsigned long long u[kVtBatch];
 #pragma unroll
-      for (int q = 0; q < kVtBatch; ++q) u[q] = vt_load(a.stat + (long)min(p0 + q * lpr, nwg - 1) * rows + row);
+      for (int q = 0; q < kVtBatch; ++q) u[q] = vt_load(gstat + (long)min(p0 + q * lpr, nwg - 1) * rows + row);
 #pragma unroll
       for (int q = 0; q < kVtBatch; ++q) {
         const float mw = __uint_as_float((unsigned)(u[q] >> 32)), sw = __uint_as_float((unsigned)u[q]);
@@ -170,7 +192,7 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
       }
     }
     for (int o = lpr >> 1; o > 0; o >>= 1) S += __shfl_xor(S, o);
-    if (sl == 0 && valid) a.lse[row] = M + logf(S);
+    if (sl == 0 && valid) glse[row] = M + logf(S);
     // the k best: `sel` holds the winners so far (every lane of the row the same)
     int sel[kVtMaxK];
 #pragma unroll
@@ -192,7 +214,7 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
 #pragma unroll
             for (int q = 0; q < kVtMaxK; ++q) pos += (sel[q] >= 0 && (sel[q] >> 5) == p) ? 1 : 0;
             live[b] = p0 + b * lpr < nwg && pos < k;
-            u[b] = vt_load(a.cand + ((long)p * rows + row) * k + min(pos, k - 1));
+            u[b] = vt_load(gcand + ((long)p * rows + row) * k + min(pos, k - 1));
           }
 #pragma unroll
           for (int b = 0; b < kVtBatch; ++b) {
@@ -211,8 +233,8 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
       }
       const bool none = bi == kVtNone;       // (the same in every lane of the row) nothing left: this slot and the rest are padding
       if (sl == 0 && valid) {
-        a.values[(long)row * k + j] = none ? -INFINITY : bv;
-        a.index[(long)row * k + j] = none ? -1 : bi;
+        gvalues[(long)row * k + j] = none ? -INFINITY : bv;
+        gindex[(long)row * k + j] = none ? -1 : bi;
       }
 #pragma unroll
       for (int q = 0; q < kVtMaxK; ++q)
@@ -220,30 +242,42 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
       rescan = !none && ((bi >> 5) & (lpr - 1)) == sl;
     }
   }
-  if (tid == 0) __hip_atomic_store(a.counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(gcounter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 static int vt_workgroups(int V) { return (V + kVtCols - 1) / kVtCols; }
 
 bool vocab_topk_supported(int H, int k, int V) { return step_hidden_supported(H) && k >= 1 && k <= kVtMaxK && k <= V; }
 
-// workspace: 16 bytes whose first int is the counter | stat [workgroups][rows] | cand [workgroups][rows][k], 8-byte words
-size_t vocab_topk_ws_bytes(int rows, int k, int V) {
-  if (rows < 1 || k < 1 || k > kVtMaxK || V < k) return 0;
-  return 16 + (size_t)vt_workgroups(V) * rows * 8 * (1 + (size_t)k);
+// workspace: per group 16 bytes whose first int is the group's counter | stat [groups][workgroups][rpg] | cand
+// [groups][workgroups][rpg][k], 8-byte words
+size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V) {
+  if (groups < 1 || groups > kVtMaxGroups || rpg < 1 || k < 1 || k > kVtMaxK || V < k) return 0;
+  return 16 * (size_t)groups + (size_t)groups * vt_workgroups(V) * rpg * 8 * (1 + (size_t)k);
 }
+size_t vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_groups_ws_bytes(1, rows, k, V); }
 
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
                int* index, float* lse, hipStream_t stream) {
-  CAPNET_REQUIRE(rows >= 1 && vocab_topk_supported(H, k, V), "vocab_topk: rows %d, H %d, V %d, k %d", rows, H, V, k);
+  return vocab_topk_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, k, ws, values, index, lse, stream);
+}
+
+int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= kVtMaxGroups && rpg >= 1 && vocab_topk_supported(H, k, V),
+                 "vocab_topk: %d groups of %d rows, H %d, V %d, k %d", groups, rpg, H, V, k);
   VocabTopkArgs a;
-  a.h = h; a.w = w; a.b = b;
+  a.h = h;
+  for (int g = 0; g < kVtMaxGroups; ++g) {
+    a.w[g] = w[g < groups ? g : 0];
+    a.b[g] = b ? b[g < groups ? g : 0] : nullptr;
+  }
   a.counter = reinterpret_cast<int*>(ws);
-  a.stat = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);
-  a.cand = a.stat + (size_t)vt_workgroups(V) * rows;
+  a.stat = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16 * (size_t)groups);
+  a.cand = a.stat + (size_t)groups * vt_workgroups(V) * rpg;
   a.values = values; a.index = index; a.lse = lse;
-  a.rows = rows; a.H = H; a.V = V; a.k = k;
-  const dim3 grid(vt_workgroups(V)), block(64 * kVtWaves);
+  a.rpg = rpg; a.H = H; a.V = V; a.k = k;
+  const dim3 grid(vt_workgroups(V), groups), block(64 * kVtWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
     hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
   });

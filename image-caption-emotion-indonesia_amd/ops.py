@@ -715,8 +715,58 @@ def vocab_topk(h, w, b=None, k=5, workspace=None):
     return values, index, lse
 
 
+def vocab_topk_groups_workspace(groups, rows_per_group, k, V, device):
+    """A zeroed workspace of capnet_vocab_topk_groups (back-to-back calls on one stream may share it)."""
+    n = _lib.lib().capnet_vocab_topk_groups_ws_bytes(int(groups), int(rows_per_group), int(k), int(V))
+    if not n:
+        raise CapnetError("vocab_topk: groups=%d rows=%d k=%d V=%d (1 <= groups <= 8; rows >= 1; 1 <= k <= 16; k <= V)"
+                          % (groups, rows_per_group, k, V))
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
+    """vocab_topk of len(ws) projections in one launch (capnet_vocab_topk_groups): h [groups rows, H], group-major; block g
+    on ws[g] [V, H] / bs[g] [V] (bs or any bs[g] None: no bias), each tensor used where it lies. Every block's values, index
+    and lse equal vocab_topk of that block alone, bit for bit.
+    Returns (values [groups rows, k] float32, index [groups rows, k] int32, lse [groups rows] float32)."""
+    who = "vocab_topk"
+    ws = _check_tables(who, ws, _first_shape(ws))
+    groups = len(ws)
+    _need_cuda(h)
+    h = _c(h.detach())
+    k = int(k)
+    if h.dim() != 2 or ws[0].dim() != 2:
+        raise CapnetError("%s: h [groups rows, H], w [V, H] per group" % who)
+    rows, H = h.shape
+    V = ws[0].shape[0]
+    if ws[0].shape[1] != H or H not in DECODE_HIDDEN or rows < groups or rows % groups:
+        raise CapnetError("%s: h [groups rows, H], w [V, H] per group with H in %r" % (who, DECODE_HIDDEN))
+    if not 1 <= k <= 16 or k > V:
+        raise CapnetError("%s: k=%d (1 <= k <= 16, k <= V = %d)" % (who, k, V))
+    if bs is not None:
+        bs = list(bs)
+        present = [b for b in bs if b is not None]
+        if len(bs) != groups:
+            raise CapnetError("%s: one bias (or None) per group" % who)
+        _check_tables(who, present, (V,), len(present))
+        bs = [None if b is None else b.detach() for b in bs]
+    rpg = rows // groups
+    if workspace is None:
+        workspace = vocab_topk_groups_workspace(groups, rpg, k, V, h.device)
+    if workspace.numel() * workspace.element_size() < _lib.lib().capnet_vocab_topk_groups_ws_bytes(groups, rpg, k, V):
+        raise CapnetError("%s: workspace too small" % who)
+    values = torch.empty((rows, k), dtype=torch.float32, device=h.device)
+    index = torch.empty((rows, k), dtype=torch.int32, device=h.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=h.device)
+    check(_lib.lib().capnet_vocab_topk_groups(ptr(h), ptr_array(ws), None if bs is None else ptr_array(bs), groups, rpg, H, V, k,
+                                              ptr(workspace), ptr(values), ptr(index), ptr(lse), current_stream()),
+          "capnet_vocab_topk_groups")
+    return values, index, lse
+
+
 _beam_decode_ws = {}
 _lstm_beam_decode_ws = {}
+_lstm_beam_decode_groups_ws = {}
 
 
 def beam_decode_supported(E, H, k, V, num_layers):
@@ -855,6 +905,81 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
     lens = htail[:n].tolist()
     rows = host[:n * SL].view(n, SL).tolist()
     out = [rows[i][:lens[i]] for i in range(n)]
+    return (out, steps.value) if return_steps else out
+
+
+def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, start_token, end_token, state=None,
+                            fused_topk=True, poll_every=0, return_steps=False):
+    """lstm_beam_decode of len(embs) decoders in ONE C call (capnet_lstm_beam_decode_groups): groups x n sentences x k beams,
+    group-major, group g on embs[g] [V, E], wcat[l][g] / beff[l][g] and Cws[g] [V, H] / Cbs[g] [V] (Cbs or any Cbs[g] None:
+    no bias). The embeddings and projections are used where they lie (one pointer per group; nothing is stacked or copied);
+    wcat[l] [groups, 4H, kin_l + H] and beff[l] [groups, 4H] are capnet.decode.pack_cell of every decoder's layer l, stacked
+    as for lstm_greedy_decode_groups. Per step one gathered decode-step launch per layer on a (H / 4, groups) grid, then
+    fused_topk: one capnet_vocab_topk_groups launch and one capnet_beam_advance_topk; else one sgemm_splitk per group into
+    its row block of the logits and one capnet_beam_advance. There are no first_inputs. state: [groups n k, 2L, H] or None
+    for zeros. Everything else as lstm_beam_decode.
+    Returns the groups n token lists, group-major (list g n + i: group g, sentence i); with return_steps, (lists, the steps
+    issued)."""
+    who = "lstm_beam_decode_groups"
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("%s: unknown cell %r" % (who, cell))
+    embs = _check_tables(who, embs, _first_shape(embs))
+    groups = len(embs)
+    Cws = list(Cws)
+    if embs[0].dim() != 2 or not Cws or Cws[0] is None or Cws[0].dim() != 2:
+        raise CapnetError("%s: emb [V, E] and Cw [V, H] per group" % who)
+    V, E = embs[0].shape
+    H, nl = Cws[0].shape[1], len(wcat)
+    Cws = _check_tables(who, Cws, (V, H), groups)
+    if Cbs is not None:
+        Cbs = list(Cbs)
+        if len(Cbs) != groups:
+            raise CapnetError("%s: one bias (or None) per group" % who)
+        present = [b for b in Cbs if b is not None]
+        _check_tables(who, present, (V,), len(present))
+        Cbs = [None if b is None else b.detach() for b in Cbs]
+    _need_cuda(state, *wcat, *beff)
+    n, k, T, fused = int(n), int(k), int(max_steps), int(bool(fused_topk))
+    if n < 1 or T < 1 or len(beff) != nl or not lstm_beam_decode_supported(E, H, k, V, nl):
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
+                          % (who, E, H, V, k, nl, n, T))
+    wcat, beff = _grouped_layer_weights(who, wcat, beff, groups, H, (E + 15) // 16 * 16)
+    dev = embs[0].device
+    nq = groups * n
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (nq * k, 2 * nl, H):
+            raise CapnetError("%s: state must be [groups n k, 2L, H]" % who)
+    L = _lib.lib()
+    key = (dev.index or 0, nl, groups, n, k, H, V, T, fused)
+    ws = _lstm_beam_decode_groups_ws.get(key)
+    if ws is None:
+        nbytes = L.capnet_lstm_beam_decode_groups_ws_bytes(nl, groups, n, k, H, V, T, fused)
+        if not nbytes:
+            raise CapnetError("%s: groups=%d n=%d k=%d V=%d max_steps=%d outside the limits" % (who, groups, n, k, V, T))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        _lstm_beam_decode_groups_ws[key] = ws
+    slab = None if fused else splitk_slab(dev)
+    SL = T + 2
+    # seqs int64 [nq, SL] | lengths int32 [nq] | the error word: one buffer, one copy
+    packed = torch.empty(nq * SL + nq // 2 + 1, dtype=torch.int64, device=dev)
+    tail = packed[nq * SL:].view(torch.int32)
+    flag = err_flag(dev)
+    steps = C.c_int(0)
+    check(L.capnet_lstm_beam_decode_groups(cell, nl, groups, n, k, E, H, V, T, int(start_token), int(end_token), ptr_array(embs),
+                                           ptr_array(wcat), ptr_array(beff), ptr_array(Cws),
+                                           None if Cbs is None else ptr_array(Cbs), ptr(state), ptr(ws), ptr(slab),
+                                           0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
+                                           C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
+          "capnet_lstm_beam_decode_groups")
+    tail[nq:nq + 1].copy_(flag)
+    host = packed.cpu()
+    htail = host[nq * SL:].view(torch.int32)
+    if int(htail[nq]):
+        check_device_errors()
+    lens = htail[:nq].tolist()
+    rows = host[:nq * SL].view(nq, SL).tolist()
+    out = [rows[i][:lens[i]] for i in range(nq)]
     return (out, steps.value) if return_steps else out
 
 

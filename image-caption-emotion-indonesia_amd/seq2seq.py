@@ -35,6 +35,15 @@ stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with 
     at every call) forces the unfused step. A shape the decode kernel does not take, or CAPNET_NO_FUSED_DECODE_STEP=1:
     capnet.beam.beam_search_device on cell_stepper. Same lists on every route (under the margin rule: the fused logits
     differ from the slab's in the last bits).
+  * Beam search in every emotion at once: Seq2Seq.sample_beam_styles runs the encoder's greedy loop ONCE and then the
+    emotion decoders' searches as ONE capnet_lstm_beam_decode_groups call over decoders x B sentences, from the encoder's
+    final state repeated per decoder: per step one gathered decode-step launch per layer on a (H / 4, decoders) grid and
+    either one capnet_vocab_topk_groups launch on a (V / 32, decoders) grid (workgroup (., g) on decoder g's projection,
+    its own partials and its own arrival counter) with one capnet_beam_advance_topk, or one sgemm_splitk per decoder and one
+    capnet_beam_advance. fused_topk=None routes on the rows per decoder (B k) by FUSED_TOPK_GROUPS_MAX_ROWS, set from
+    profiles/time_seq2seq_beam_styles.jsonl. `factual` is the encoder's own sample_beam, not a group. Every entry equals
+    sample_beam(mode=...). One emotion, unequal decoder shapes, a shape the decode kernel does not take or
+    CAPNET_NO_FUSED_DECODE_STEP=1: one DecoderRNN.sample_beam after the other on the one encoder run.
 """
 import os
 import random
@@ -57,6 +66,10 @@ FUSED_TOPK_OFF = "CAPNET_NO_FUSED_TOPK"
 # the largest n k at which the fused step's median beat the unfused step's by more than the spread at 1, 2 and 3 layers
 # (profiles/time_seq2seq_beam.jsonl); above it fused_topk=None takes the unfused step in the same C call
 FUSED_TOPK_MAX_ROWS = 15
+# the same for the grouped search of sample_beam_styles, in rows PER DECODER (B k): the largest measured row count at which
+# the grouped fused step's median beat the grouped unfused step's by more than the spread at 1 and 3 layers
+# (profiles/time_seq2seq_beam_styles.jsonl); above it fused_topk=None takes the unfused step in the same C call
+FUSED_TOPK_GROUPS_MAX_ROWS = 15
 _EMOTIONS = ("happy", "sad", "angry")
 
 
@@ -386,4 +399,63 @@ class Seq2Seq(nn.Module):
         else:
             for m, x in zip(emotions, decoders):
                 out[m] = x.sample(start_token, (h, c))
+        return {m: out[m] for m in modes}
+
+    def _grouped_beam_ok(self, decoders, k):
+        """Whether `decoders` search in one grouped call now (CAPNET_NO_FUSED_DECODE_STEP is read here)."""
+        d = decoders[0]
+        same = all((x.embed_size, x.hidden_size, x.vocab_size, x.num_layers, x.max_seq_length) ==
+                   (d.embed_size, d.hidden_size, d.vocab_size, d.num_layers, d.max_seq_length) for x in decoders)
+        return (same and 2 <= len(decoders) <= ops.MAX_GROUPS and fused_decode_step(d.num_layers, d.embed_size, d.hidden_size)
+                and ops.lstm_beam_decode_supported(d.embed_size, d.hidden_size, k, d.vocab_size, d.num_layers))
+
+    def sample_beam_styles(self, features, start_token, end_token, states=(None, None),
+                           modes=('factual', 'happy', 'sad', 'angry'), k=5, poll_every=0, fused_topk=None):
+        """{mode: [B token lists]} for every mode of `modes` (a non-empty sequence of distinct names), each entry equal to
+        sample_beam(features, start_token, end_token, states, mode=mode, k=k). `factual` is the encoder's own sample_beam
+        (its first input is `features`, it starts from `states`). The encoder's greedy sample runs once, and only if an
+        emotion is asked for. Two or more emotions with equal shapes then search as ONE grouped call
+        (ops.lstm_beam_decode_groups) from the encoder's final state, repeated per decoder; fused_topk=None routes that call
+        on the rows per decoder (B k) by FUSED_TOPK_GROUPS_MAX_ROWS, True / False force the fused / unfused step
+        (CAPNET_NO_FUSED_TOPK=1 forces False). One emotion, unequal decoder shapes, a shape the decode kernel does not take
+        or CAPNET_NO_FUSED_DECODE_STEP=1: one DecoderRNN.sample_beam after the other on that one encoder run. An
+        out-of-range start_token raises CapnetError through the device error word."""
+        try:
+            modes = check_styles(modes, self._check_mode)
+        except ValueError as e:                    # an empty or repeated list: refused as every other bad argument here
+            raise CapnetError("sample_beam_styles: %s" % e)
+        emotions = [m for m in modes if m != 'factual']
+        decoders = [self._decoder(m) for m in emotions]
+        out = {}
+        if 'factual' in modes:
+            out['factual'] = self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk)
+        if decoders:
+            _, (h, c) = self.encoder.sample(features, states)
+            B, k = h.size(1), int(k)
+            d, G = decoders[0], len(decoders)
+            if not 1 <= k <= 16 or k > d.vocab_size:
+                raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, d.vocab_size))
+            if self._grouped_beam_ok(decoders, k):
+                if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
+                    fused = False
+                elif fused_topk is None:
+                    fused = B * k <= FUSED_TOPK_GROUPS_MAX_ROWS
+                else:
+                    fused = bool(fused_topk)
+                with torch.no_grad():
+                    packed = [pack_cells(x._layers(), d.embed_size) for x in decoders]
+                    wcat = [torch.stack([p[l][0] for p in packed]) for l in range(d.num_layers)]
+                    beff = [torch.stack([p[l][1] for p in packed]) for l in range(d.num_layers)]
+                    state = _to_rows(h, c).repeat(G, 1, 1).repeat_interleave(k, 0).contiguous()
+                    lists = ops.lstm_beam_decode_groups(
+                        ops.CELL_LSTM, wcat, beff, [x.embed.weight.detach() for x in decoders],
+                        [x.linear.weight.detach() for x in decoders], [x.linear.bias.detach() for x in decoders], B, k,
+                        d.max_seq_length + 1, start_token, end_token, state=state, fused_topk=fused, poll_every=poll_every)
+                ops.check_device_errors()
+                for g, m in enumerate(emotions):
+                    out[m] = lists[g * B:(g + 1) * B]
+            else:
+                for m, x in zip(emotions, decoders):
+                    out[m] = x.sample_beam(start_token, end_token, (h, c), k, poll_every, fused_topk)
+                ops.check_device_errors()
         return {m: out[m] for m in modes}

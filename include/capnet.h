@@ -698,6 +698,20 @@ size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V);
 int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
                       float* values, int* index, float* lse, capnet_stream_t stream);
 
+/* capnet_vocab_topk for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's rows
+ * are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL; every
+ * w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival counter
+ * and its own block of partials, and its last arriver merges its rows only, so no group waits on another, and values, index
+ * and lse of group g ([groups rows_per_group][k], [groups rows_per_group][k], [groups rows_per_group], group-major) are, bit
+ * for bit, those of capnet_vocab_topk on group g's rows and projection alone. workspace:
+ * capnet_vocab_topk_groups_ws_bytes(groups, rows_per_group, k, V) bytes (0 outside 1 <= groups <= 8 or capnet_vocab_topk's
+ * limits) whose first 16 groups bytes are ZERO before the first use (and are left zero). groups = 1 is exactly
+ * capnet_vocab_topk (the same grid, the same workspace layout). */
+size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V);
+int capnet_vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                             int H, int V, int k, void* workspace, float* values, int* index, float* lse,
+                             capnet_stream_t stream);
+
 /* capnet_beam_decode's loop for a stack that starts from a GIVEN state and, optionally, from given first inputs
  * (capnet.seq2seq: DecoderRNN.sample_beam from the encoder's state, EncoderRNN.sample_beam from the feature column), one
  * weight group. first_inputs non-NULL ([n k][E], 16-B aligned): step 1 feeds those rows to layer 0 instead of
@@ -716,6 +730,30 @@ int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, i
                             const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                             float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                             int* steps_run, int* err_flag, capnet_stream_t stream);
+
+/* capnet_lstm_beam_decode for `groups` decoders at once (capnet.seq2seq.Seq2Seq.sample_beam_styles: every emotion's
+ * DecoderRNN from the encoder's final state): the search runs over groups x n sentences, sentence q = g n + i (group g,
+ * sentence i) at rows q k .. q k + k - 1, and group g decodes on ITS embedding emb[g] [V][E], LSTM weights and projection
+ * Cw[g] [V][H] / Cb[g] [V]. Per step: one launch per layer of capnet_stacked_decode_step_tables with the parent rows (a (H /
+ * 4, groups) grid), then, fused_topk = 1, ONE capnet_vocab_topk_groups launch and one capnet_beam_advance_topk over all
+ * groups n sentences; fused_topk = 0, one capnet_sgemm_splitk per group into that group's row block of the logits (same
+ * stream, the one slab) and one capnet_beam_advance. emb, Cw, Cb: HOST arrays of `groups` device pointers, every emb[g] and
+ * Cw[g] non-NULL and 16-B aligned (Cb itself or any Cb[g] may be NULL: no bias); nothing is stacked or copied. wcat[l]
+ * [groups][4H][kin_l + H] and beff[l] [groups][4H], one device buffer per layer, as capnet_stacked_decode_step_groups. There
+ * are no first_inputs: the emotion decoders never take a feature column. state0 [groups n k][2 nlayers][H] or NULL; seqs
+ * int64 [groups n][max_steps + 2], lengths int32 [groups n]; slab (unfused) at least groups n k V floats. workspace:
+ * capnet_lstm_beam_decode_groups_ws_bytes(...) bytes (0 outside 1 <= groups <= 8 or capnet_lstm_beam_decode's limits at
+ * groups n sentences), 16-B aligned, contents irrelevant. The lists of group g are those of capnet_lstm_beam_decode on group
+ * g's sentences and parameters alone; groups = 1 returns capnet_lstm_beam_decode's lists (without first_inputs). Everything
+ * else as capnet_lstm_beam_decode; every bad argument is refused before any launch. */
+size_t capnet_lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps,
+                                               int fused_topk);
+int capnet_lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                                   long long start_token, long long end_token, const float* const* emb,
+                                   const float* const* wcat, const float* const* beff, const float* const* Cw,
+                                   const float* const* Cb, const float* state0, void* workspace, float* slab,
+                                   size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
+                                   int* steps_run, int* err_flag, capnet_stream_t stream);
 
 /* One beam step of an attention decoder (DecoderFactoredLSTMAtt / DecoderRNNAtt and their stacked forms) without the
  * vocabulary projection, for n images x k fixed slots (row r belongs to image r / k), on `stream`, in this order:
