@@ -20,8 +20,8 @@
 // operand of phase B (row n, k slots of lane group g) without leaving the registers: k slot j of lane group g stands for
 // channel 16 (j >> 2) + 4 g + (j & 3) of the chunk in BOTH weight images (fb_kslot). a2 of the wave's rows stays in
 // registers for the whole tile (folded and split once); W3 / W1 chunks stream through a 4-slot LDS ring by LDS-DMA, three
-// phases ahead, one barrier per phase; the identity rows come two chunks ahead by hand-issued loads (counted vmcnt;
-// tools/isa_inflight_check.py checks the discipline on the shipped ISA).
+// phases ahead, one barrier per phase; the identity rows come two chunks ahead (one, at MID <= 128) by hand-issued loads
+// (counted vmcnt; tools/isa_inflight_check.py checks the discipline on the shipped ISA).
 #include <cstdlib>
 #include <type_traits>
 
@@ -32,6 +32,18 @@
 
 namespace capnet {
 namespace {
+
+// gload16 with a constant byte offset in the instruction instead of a register of its own
+template <int IMM>
+__device__ __forceinline__ void gload16_imm(f32x4& dst, const float* sbase, unsigned voff_bytes) {
+  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=&v"(dst) : "v"(voff_bytes), "s"(sbase), "n"(IMM) : "memory");
+}
+
+// the matching 16-B store (s_nop 1 behind it: a store of more than 8 bytes with a scalar base still reads its data up to two states after issue)
+template <int IMM>
+__device__ __forceinline__ void gstore16_imm(float* sbase, unsigned voff_bytes, const f32x4& v) {
+  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff_bytes), "v"(v), "s"(sbase), "n"(IMM) : "memory");
+}
 
 __host__ __device__ constexpr int fb_kslot(int g, int j) { return 16 * (j >> 2) + 4 * g + (j & 3); }
 
@@ -422,15 +434,24 @@ struct FArgs {
 // NW waves of RS 16-row strips each. NW = 4: one wave per SIMD (up to 512 registers: RS = 2 fits); NW = 8: two waves per
 // SIMD at <= 256 registers -- a lone wave issues its own loads, waits and tail arithmetic BETWEEN its MFMAs (SQ counters,
 // 4 waves x 32 rows: matrix pipe busy 40 % of the wave's time, 40 % issue stalls, 24 % waits), a second wave fills those gaps.
+// Waves per SIMD the registers are budgeted for. Eight waves at MID <= 128 (stages 1 and 2, launches that fill the chip):
+// four, i.e. <= 128 registers and TWO workgroups per CU (LDS: 36 / 72 KB each). Sized for MID = 256 and merely instantiated,
+// the kernel took 142 / 172 registers there -- one workgroup per CU, a quarter of the wave slots, and nothing else on the CU to
+// hide a barrier interval's latency. The lean form (LEAN below) recovers the registers where MID is small: one identity
+// set one chunk ahead instead of two sets two ahead, no fragment read-ahead (the other workgroup's waves cover the LDS
+// round trip), identity loads and out stores on a uniform base with immediate offsets instead of address registers.
+__host__ __device__ constexpr int fb_waves_per_simd(int MID, int NW) { return NW == 8 && MID <= 128 ? 4 : NW / 4; }
 template <int MID, int RS, int NW>
-__global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g) {
+__global__ __launch_bounds__(64 * NW, fb_waves_per_simd(MID, NW)) void fb_fused_kernel(const FArgs g) {
   constexpr int C = 4 * MID, KS = MID / 32, NB = MID / 16, NCH = C / 32;
   constexpr int SLOT = MID * 128;                     // bytes of one chunk image (either role)
   constexpr int NDMA = SLOT / 1024 / NW;              // 1-KB LDS-DMA instructions per wave and phase
   constexpr int L = 2 * RS;                           // identity loads = out stores per wave and chunk
   constexpr int TR = 16 * RS * NW;                    // rows of a tile
   constexpr int NT = 64 * NW;                         // threads
+  constexpr bool LEAN = fb_waves_per_simd(MID, NW) >= 4;
   static_assert(NDMA >= 1 && 4 * NDMA + 2 * L <= 63, "vmcnt range");
+  static_assert(!LEAN || RS == 1, "the lean form: one strip per wave");
   __shared__ __attribute__((aligned(16))) unsigned char ring[4 * SLOT];
   __shared__ __attribute__((aligned(16))) float par[4][C];          // s3 2^-(ew3 + e3), t3, sd, td
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, gq = lane >> 4, ln = lane & 15;
@@ -455,19 +476,26 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
     const int row = min(tile0 + (wave * RS + s) * 16 + ln, g.M - 1);
     idoff[s] = (unsigned)(((long)row * C + 4 * gq) * 4);
   }
-  f32x4 idA[RS][2], idB[RS][2];
+  f32x4 idA[RS][2], idB[RS][2];                        // two sets, the rows two chunks ahead; lean: idA alone, one chunk ahead
+  f32x4 (&idO)[RS][2] = LEAN ? idA : idB;              // the set of the odd chunks
   auto fetch_id = [&](int cc, f32x4 (&id)[RS][2]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int s = 0; s < RS; ++s)
+    for (int s = 0; s < RS; ++s) {
+      if constexpr (LEAN) {
+        gload16_imm<0>(id[s][0], g.res + 32 * cc, idoff[s]);
+        gload16_imm<64>(id[s][1], g.res + 32 * cc, idoff[s]);
+      } else {
 #pragma unroll
-      for (int blk = 0; blk < 2; ++blk) gload16(id[s][blk], g.res, idoff[s] + (unsigned)((32 * cc + 16 * blk) * 4));
+        for (int blk = 0; blk < 2; ++blk) gload16(id[s][blk], g.res, idoff[s] + (unsigned)((32 * cc + 16 * blk) * 4));
+      }
+    }
   };
 
   // ---- prologue: the first two phases' weights, the first two chunks' identity rows, the parameters, a2
   dma(w3img, 0, 0);
   dma(w1img, 0, 1);
   fetch_id(0, idA);
-  fetch_id(NCH > 1 ? 1 : 0, idB);
+  if constexpr (!LEAN) fetch_id(NCH > 1 ? 1 : 0, idB);
   {
     const float x3 = f16x3_out_scale(g.w3[0], g.e3);
     for (int i = tid; i < C; i += NT) {
@@ -503,8 +531,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
     }
   }
   wait_vmcnt<0>();                 // everything of the prologue has landed: the loop's counted waits start from here
-  CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
-  if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
+  if constexpr (LEAN) {
+    CAPNET_LANDED2(idA[0][0], idA[0][1]);
+  } else {
+    CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
+    if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
+  }
   __syncthreads();
 
   f32x4 acc[RS][NB];
@@ -524,6 +556,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
   // behind them ST x L, LD x L. The same stream for both groups, one iteration apart.
   //   before barrier k: D(k), issued in iteration k - 2; younger than it: one A and one B iteration      -> NDMA + 2 L
   //   the tail of B(c): LD(c), issued by B(c - 2), four iterations back; younger: D, D ST LD, D, D        -> 4 NDMA + 2 L
+  // The lean form keeps ONE identity set: B(c)'s tail consumes it and then requests chunk c + 1 into the same registers
+  // (ST x L, LD x L as before, so the stream's shape and the wait before the barrier do not change):
+  //   before barrier k: as above                                                                           -> NDMA + 2 L
+  //   the tail of B(c): LD(c), issued by B(c - 1), two iterations back, the last operation of that iteration;
+  //                     younger: D of the A iteration between, D of this iteration's head                  -> 2 NDMA
+  // (no store is younger than the awaited load any more: the count cannot be satisfied early by stores completing
+  //  out of order with loads)
 #ifndef CAPNET_FB_GB8
 #define CAPNET_FB_GB8 2
 #endif
@@ -531,7 +570,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
 #ifndef CAPNET_FB_FD
 #define CAPNET_FB_FD 1
 #endif
-  constexpr int FD = CAPNET_FB_FD;                     // batches read ahead
+  constexpr int FD = LEAN ? 0 : CAPNET_FB_FD;          // batches read ahead (lean: none, four waves per SIMD cover the round trip)
   typedef const __attribute__((address_space(3))) unsigned char* lds_bytes;
   const lds_bytes ring3 = (lds_bytes)ring;
   f32x4 d[RS][2];
@@ -603,7 +642,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
     for (int bb = 0; bb < FD; ++bb)
       if (bb < NBATB) read_b(bb);
     __builtin_amdgcn_sched_barrier(0);
-    wait_vmcnt<4 * NDMA + 2 * L>();
+    wait_vmcnt<LEAN ? 2 * NDMA : 4 * NDMA + 2 * L>();
     if constexpr (RS == 2) CAPNET_LANDED4(id[0][0], id[0][1], id[1][0], id[1][1]);
     else CAPNET_LANDED2(id[0][0], id[0][1]);
     h8 oh[RS], ol[RS];
@@ -625,13 +664,21 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = fmaxf(fmaf(d[s][blk][e], sv[e], tv[e]) + r[e], 0.f);
-        *reinterpret_cast<f32x4*>(g.out + (long)row * C + ch) = o;
+        if constexpr (LEAN) {
+          // out has the identity's layout: the same per-lane offset, chunk in the uniform base, block in the immediate
+          if (blk == 0) gstore16_imm<0>(g.out + 32 * cc, idoff[s], o);
+          else gstore16_imm<64>(g.out + 32 * cc, idoff[s], o);
+        } else {
+          *reinterpret_cast<f32x4*>(g.out + (long)row * C + ch) = o;
+        }
         split4(o * is1, hh[blk], ll[blk]);
+        if constexpr (LEAN) __builtin_amdgcn_sched_barrier(0);       // one block's parameters and temporaries at a time
       }
       oh[s] = cat8(hh[0], hh[1]);
       ol[s] = cat8(ll[0], ll[1]);
     }
-    fetch_id(cc + 2 < NCH ? cc + 2 : NCH - 1, id);
+    if constexpr (LEAN) fetch_id(cc + 1 < NCH ? cc + 1 : NCH - 1, id);
+    else fetch_id(cc + 2 < NCH ? cc + 2 : NCH - 1, id);
 #pragma unroll
     for (int b = 0; b < NBATB; ++b) {
       if (b + FD < NBATB) read_b(b + FD);
@@ -672,7 +719,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
       const int c0 = k >> 1;                       // chunks c0 (even: idA) and c0 + 1 (odd: idB)
       head(k);
       if constexpr (LAG == 0) phase_a(c0);
-      else { if (c0 > 0) phase_b(c0 - 1, idB); }
+      else { if (c0 > 0) phase_b(c0 - 1, idO); }
       head(k + 1);
       if constexpr (LAG == 0) phase_b(c0, idA);
       else phase_a(c0);
@@ -680,16 +727,20 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void fb_fused_kernel(const FArgs g
       if constexpr (LAG == 0) phase_a(c0 + 1);
       else phase_b(c0, idA);
       head(k + 3);
-      if constexpr (LAG == 0) phase_b(c0 + 1, idB);
+      if constexpr (LAG == 0) phase_b(c0 + 1, idO);
       else phase_a(c0 + 1);
     }
     if constexpr (NW == 8) {
       head(2 * NCH);
-      if constexpr (LAG != 0) phase_b(NCH - 1, idB);
+      if constexpr (LAG != 0) phase_b(NCH - 1, idO);
     }
     wait_vmcnt<0>();               // the clamped DMAs and loads past the end: nothing may be in flight when the LDS is re-used / handed on
-    CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
-    if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
+    if constexpr (LEAN) {
+      CAPNET_LANDED2(idA[0][0], idA[0][1]);
+    } else {
+      CAPNET_LANDED4(idA[0][0], idA[0][1], idB[0][0], idB[0][1]);
+      if constexpr (RS == 2) CAPNET_LANDED4(idA[1][0], idA[1][1], idB[1][0], idB[1][1]);
+    }
   };
   if (NW == 4 || wave_u < 4) run(std::integral_constant<int, 0>{});
   else run(std::integral_constant<int, 1>{});
