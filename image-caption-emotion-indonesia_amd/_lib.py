@@ -184,6 +184,16 @@ SIGNATURES = {
                                                                                                   _vp, _vp, _vp, _vp, _vp, _sz,
                                                                                                   _i, _vp, _vp, C.POINTER(_i),
                                                                                                   _vp, _vp]),
+    "capnet_beam_trace_bytes": (_sz, [_i, _i, _i]),
+    "capnet_beam_advance_traced": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),
+    "capnet_beam_finish_traced": (_i, [_vp, _vp, _i, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "capnet_att_decode_step_alphas": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                                 _sz, _vp, _vp, _vp]),
+    "capnet_att_beam_decode_alphas_ws_bytes": (_sz, [_i] * 11),
+    "capnet_att_beam_decode_alphas": (_i, [_i] * 12 + [C.c_longlong, C.c_longlong] + [_vp] * 7 + [C.POINTER(_vp), C.POINTER(_vp),
+                                                                                                  _vp, _vp, _vp, _vp, _vp, _sz,
+                                                                                                  _i, _vp, _vp, C.POINTER(_i),
+                                                                                                  _vp, _vp, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),
     "capnet_lstm_pack_wfrag": (_i, [_vp, _vp, _i, _i, _vp]),
     "capnet_lstm_step_fused": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -206,7 +206,8 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
 // the re-ordering of the beams costs no copy -- and z is only read: parents repeat, a sigmoid written back would be
 // applied twice. A parent outside [0, n k) raises the flag and the row reads itself; a token id outside [0, V) raises it
 // and reads row 0 (the gathered decode step's conventions). Two launches: scores, then softmax + context + gate, whose
-// first channel block of an image also copies emb[token[r]] into xa[r][0 .. E).
+// first channel block of an image also copies emb[token[r]] into xa[r][0 .. E) and, where alpha_out is set (a search that
+// returns its attention maps), stores the k softmaxes it multiplies the map with: alpha_out[row][P], along the pixels.
 // Weight groups (every style at once): the n beam groups are G weight groups x n_img images, group-major. Beam group q
 // keeps its own att1 (each mode has its encoder_att) but reads the map of image q % n_img -- feat is not copied per mode
 // -- and the full_att of weight group q / n_img.
@@ -226,6 +227,7 @@ struct AttBeamArgs {
   float* xa;                 // [n k][ldx] = [embedding (E) | gated context (C)]
   long ldx;
   int* err;
+  float* alpha_out;          // optional [n k][P]: the softmax of every row over the pixels (the maps of a traced search)
 };
 
 __device__ __forceinline__ long beam_src_row(const AttBeamArgs& a, int row) {
@@ -328,12 +330,17 @@ __global__ __launch_bounds__(kAttThreads) void att_beam_context_kernel(AttBeamAr
   float4 s[KT];
 #pragma unroll
   for (int r = 0; r < KT; ++r) s[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool store_alpha = a.alpha_out && blockIdx.y == 0;
   for (int pb = 0; pb < P; pb += kBeamPix) {
     __syncthreads();   // mx / inv are written; the previous chunk's alpha is consumed
     const int np = min(kBeamPix, P - pb);
     for (int i = tid; i < KT * kBeamPix; i += kAttThreads) {
       const int r = i / kBeamPix, q = i - r * kBeamPix;
-      al[r][q] = r < k && q < np ? expf(a.escore[((long)img * k + r) * P + pb + q] - mx[r]) * inv[r] : 0.f;
+      const bool in = r < k && q < np;
+      const float v = in ? expf(a.escore[((long)img * k + r) * P + pb + q] - mx[r]) * inv[r] : 0.f;
+      al[r][q] = v;
+      // the maps out (optional): the image's first channel block stores what it is about to multiply with, along the pixels
+      if (store_alpha && in) a.alpha_out[((long)img * k + r) * P + pb + q] = v;
     }
     __syncthreads();
     for (int q0 = 8 * wave; q0 < np; q0 += 8 * (kAttThreads / 64)) {
@@ -387,7 +394,7 @@ static void launch_att_beam(const AttBeamArgs& a, hipStream_t stream) {
 
 int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
                       const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
-                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img) {
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img, float* alpha_out) {
   if (n_img <= 0) n_img = n;
   CAPNET_REQUIRE(n % n_img == 0, "att_beam_step_fwd: %d beam groups on %d images", n, n_img);
   CAPNET_REQUIRE(att1 && feat && z && wf && bf && tokens && emb && escore && xa && err_flag, "att_beam_step_fwd: null argument");
@@ -399,6 +406,7 @@ int att_beam_step_fwd(const float* att1, const float* feat, const float* z, cons
   a.att1 = att1; a.feat = feat; a.z = z; a.ldz = (long)A + C; a.parent = parent_rows; a.wf = wf; a.bf = bf;
   a.tok = tokens; a.emb = emb; a.V = V; a.E = E; a.n = n; a.k = k; a.P = P; a.A = A; a.C = C;
   a.escore = escore; a.xa = xa; a.ldx = (long)E + C; a.err = err_flag; a.n_img = n_img;
+  a.alpha_out = alpha_out;
   if (k <= 4) launch_att_beam<4, 4>(a, stream);
   else if (k <= 8) launch_att_beam<8, 4>(a, stream);
   else launch_att_beam<16, 2>(a, stream);

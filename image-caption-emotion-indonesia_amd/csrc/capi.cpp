@@ -711,20 +711,45 @@ int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, in
                                        stream);
 }
 
-int capnet_att_decode_step_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
-                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
-                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
-                                  const float* const* wcat, const float* const* beff, const float* state_in,
-                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
-                                  size_t slab_floats, int* err_flag, capnet_stream_t stream) {
+// capnet_att_decode_step_groups and capnet_att_decode_step_alphas (with_alphas: the maps are required)
+static int att_decode_step_entry(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                 const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                 const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                 const float* const* wcat, const float* const* beff, const float* state_in,
+                                 const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                 size_t slab_floats, int* err_flag, capnet_stream_t stream, bool with_alphas, float* alphas) {
   if (int rc = att_decode_check("att_decode_step", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
                                 wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
   CAPNET_REQUIRE(tokens && state_in && state_out && h_top, "att_decode_step: null argument");
   CAPNET_REQUIRE(state_in != state_out, "att_decode_step: state_in and state_out must differ");
   CAPNET_REQUIRE(aligned16(state_in) && aligned16(state_out), "att_decode_step: state alignment (16-B aligned)");
+  CAPNET_REQUIRE(!with_alphas || alphas, "att_decode_step: null argument (alphas is required)");
+  CAPNET_REQUIRE((size_t)alphas % 4 == 0, "att_decode_step: alphas alignment");
   return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full, wcat, beff,
-                         state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, S(stream), groups);
+                         state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, S(stream), groups, alphas);
+}
+
+int capnet_att_decode_step_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* state_in,
+                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                  size_t slab_floats, int* err_flag, capnet_stream_t stream) {
+  return att_decode_step_entry(cell, nlayers, groups, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full, wcat,
+                               beff, state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, stream, false,
+                               nullptr);
+}
+
+int capnet_att_decode_step_alphas(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* state_in,
+                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                  size_t slab_floats, int* err_flag, capnet_stream_t stream, float* alphas) {
+  return att_decode_step_entry(cell, nlayers, groups, n, k, P, A, C, E, H, V, att1, feat, tokens, emb, wz, bz, w_full, b_full, wcat,
+                               beff, state_in, parent_rows, state_out, h_top, workspace, slab, slab_floats, err_flag, stream, true,
+                               alphas);
 }
 
 size_t capnet_att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps) {
@@ -742,13 +767,14 @@ int capnet_att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, in
                                        seqs, lengths, steps_run, err_flag, stream);
 }
 
-int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
-                                  int max_steps, long long start_token, long long end_token, const float* att1,
-                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
-                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
-                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
-                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                                  capnet_stream_t stream) {
+// capnet_att_beam_decode_groups and capnet_att_beam_decode_alphas (with_alphas: the maps are required)
+static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                 int max_steps, long long start_token, long long end_token, const float* att1,
+                                 const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                 const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                 const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                 int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                 capnet_stream_t stream, bool with_alphas, float* alphas) {
   if (int rc = att_decode_check("att_beam_decode", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
                                 wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
@@ -758,9 +784,40 @@ int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int 
   CAPNET_REQUIRE(Cw && state0 && seqs && lengths, "att_beam_decode: null argument (state0 is required)");
   CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0), "att_beam_decode: Cw and state0 must be 16-B aligned");
   CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "att_beam_decode: seqs / lengths alignment");
+  CAPNET_REQUIRE(!with_alphas || alphas, "att_beam_decode: null argument (alphas is required)");
+  CAPNET_REQUIRE((size_t)alphas % 4 == 0, "att_beam_decode: alphas alignment");
   return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
                          b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
-                         err_flag, S(stream), groups);
+                         err_flag, S(stream), groups, alphas);
+}
+
+int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  int max_steps, long long start_token, long long end_token, const float* att1,
+                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream) {
+  return att_beam_decode_entry(cell, nlayers, groups, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz,
+                               bz, w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs,
+                               lengths, steps_run, err_flag, stream, false, nullptr);
+}
+
+size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps) {
+  return att_beam_decode_alphas_ws_bytes(nlayers, groups, n, k, P, A, C, E, H, V, max_steps);
+}
+
+int capnet_att_beam_decode_alphas(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  int max_steps, long long start_token, long long end_token, const float* att1,
+                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream, float* alphas) {
+  return att_beam_decode_entry(cell, nlayers, groups, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz,
+                               bz, w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs,
+                               lengths, steps_run, err_flag, stream, true, alphas);
 }
 
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
@@ -902,6 +959,21 @@ int capnet_beam_advance_topk(void* beam, const float* values, const int* index, 
 int capnet_beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
                        capnet_stream_t stream) {
   return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, S(stream));
+}
+size_t capnet_beam_trace_bytes(int n, int k, int max_steps) { return beam_trace_bytes(n, k, max_steps); }
+int capnet_beam_advance_traced(void* beam, void* trace, const float* logits, long ld, int V, int n, int k, int max_steps,
+                               int step, long long end_token, long long* next_words, long long* parent_rows,
+                               capnet_stream_t stream) {
+  CAPNET_REQUIRE(trace != nullptr, "beam_advance_traced: null trace");
+  CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0, "beam_advance_traced: the state and the trace must be 4-byte aligned");
+  return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream), trace);
+}
+int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
+                              long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {
+  CAPNET_REQUIRE(trace && rows, "beam_finish_traced: null trace or rows");
+  CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0 && (size_t)rows % 4 == 0,
+                 "beam_finish_traced: the state, the trace and the rows must be 4-byte aligned");
+  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, S(stream), trace, rows);
 }
 int capnet_beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live,
                      const float** scores) {

@@ -221,12 +221,16 @@ int beam_topk(const float* logits, long ld, int rows, int V, const float* prev, 
 size_t beam_state_bytes(int n, int k, int max_steps);
 int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream);
 int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
-                 long long* next_words, long long* parent_rows, hipStream_t stream);
+                 long long* next_words, long long* parent_rows, hipStream_t stream, void* trace = nullptr);
+// (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
+// done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
+// winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)
+size_t beam_trace_bytes(int n, int k, int max_steps);
 // (beam_advance on a step's k best logits per row and the rows' log-sum-exp, vocab_topk's outputs, instead of its logits)
 int beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k, int max_steps,
                       int step, long long end_token, long long* next_words, long long* parent_rows, hipStream_t stream);
 int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
-                hipStream_t stream);
+                hipStream_t stream, const void* trace = nullptr, int* rows = nullptr);
 int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
 int gather_rows(const float* src, const int* idx, float* out, int rows, int C, hipStream_t stream);
 int colsum(const float* x, long ld, int rows, int C, float* out, int accumulate, hipStream_t stream,
@@ -281,7 +285,8 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
                     const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
                     const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
-                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups = 1);
+                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups = 1, float* alphas = nullptr);
+// (alphas [groups n k][P], optional: the step's attention maps, att_beam_step_fwd's alpha_out)
 // (groups: groups x n beam groups of k rows, group-major; att1 [groups n][P][A], feat [n][P][C], wz / bz / wf / bf and the
 // layers' weights with a leading groups dimension; ws: att_decode_step_ws_bytes at groups x n)
 
@@ -354,7 +359,12 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups = 1);
+                    hipStream_t s, int groups = 1, float* alphas = nullptr);
+// alphas [groups n][max_steps][P], optional (ws: att_beam_decode_alphas_ws_bytes): row e - 1 of a caption is the softmax over
+// the pixels that preceded its word e, rows past its length - 1 are zero. ws then continues: the row trace | the winners'
+// rows | the history [max_steps][groups n k][P] of every step's maps
+size_t att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                       int max_steps);
 
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);
@@ -376,9 +386,11 @@ int att_step_fwd(const float* att1, const float* feat, const float* att2, float*
 bool att_beam_step_supported(int E, int C, int A, int P, int k);
 int att_beam_step_fwd(const float* att1, const float* feat, const float* z, const long long* parent_rows, const float* wf,
                       const float* bf, const long long* tokens, const float* emb, int V, int E, int n, int k, int P, int A,
-                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img = 0);
+                      int C, float* escore, float* xa, int* err_flag, hipStream_t stream, int n_img = 0,
+                      float* alpha_out = nullptr);
 // (n_img > 0, n = G n_img beam groups of G weight groups: group q reads att1 at q, feat [n_img][P][C] at q % n_img and
-// full_att wf [G][A], bf [G] at q / n_img)
+// full_att wf [G][A], bf [G] at q / n_img; alpha_out [n k][P], optional: every row's softmax over the pixels, stored by
+// the image's first channel block -- the arithmetic is the same with it and without)
 int att_step_bwd(const float* att1, const float* feat, const float* att2, long ldz2,
                  const float* gate, long ldzg, const float* awe, const float* alpha,
                  const float* wf, float* dxa, long ldx, const float* dalphas_bt, int steps,

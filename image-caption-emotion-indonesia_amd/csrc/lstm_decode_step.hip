@@ -365,7 +365,7 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* feat, const long long* tokens, const float* emb, const float* wz, const float* bz,
                     const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
                     const float* state_in, const long long* parent_rows, float* state_out, float* h_top, void* ws, float* slab,
-                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups) {
+                    size_t slab_floats, int* err_flag, hipStream_t stream, int groups, float* alphas) {
   const int gk = n * k, nk = groups * gk;     // rows of one weight group (n images), rows in all
   const long lds = 2L * nlayers * H;
   float* z = reinterpret_cast<float*>(ws);
@@ -378,7 +378,7 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
     rc = sgemm_splitk(false, true, gk, A + C, H, state_in + (long)g * gk * lds, lds, wz + (long)g * (A + C) * H, H,
                       z + (long)g * gk * (A + C), A + C, bz + (long)g * (A + C), 0, slab, slab_floats, stream);
   if (rc == kOk) rc = att_beam_step_fwd(att1, feat, z, parent_rows, wf, bf, tokens, emb, V, E, groups * n, k, P, A, C, escore, xa,
-                                        err_flag, stream, n);
+                                        err_flag, stream, n, alphas);
   if (rc == kOk) rc = decode_layer(cell, 0, nlayers, nk, H, V, nullptr, xa, E + C, E + C, wcat[0], beff[0], state_in, state_out,
                                    h_top, err_flag, stream, parent_rows, groups);
   for (int l = 1; l < nlayers && rc == kOk; ++l)

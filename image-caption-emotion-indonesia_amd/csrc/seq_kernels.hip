@@ -510,6 +510,20 @@ __host__ __device__ static inline BeamState beam_state_of(void* beam, int n, int
   return s;
 }
 
+// The row trace of a search whose attention maps are wanted (capnet_beam_advance_traced): a buffer of its own BESIDE the
+// state, in the sequences' shape -- rows[2][n][k][L] (the buffers swap as seq's do) | done_rows[n][k][L], int32. Entry e
+// (1 <= e <= step) of a hypothesis is the slot, within its image, that it occupied when the decoder ran step e: the row
+// whose step-e attention preceded its word e. Entry 0 is -1 (the start token has no map).
+struct BeamTrace {
+  int *rows, *done_rows;   // both null: no trace
+};
+__host__ __device__ static inline BeamTrace beam_trace_of(void* trace, int n, int k, int max_steps) {
+  BeamTrace t;
+  t.rows = static_cast<int*>(trace);
+  t.done_rows = trace ? t.rows + 2L * n * k * (max_steps + 2) : nullptr;
+  return t;
+}
+
 __global__ __launch_bounds__(256) void beam_init_kernel(void* beam, int n, int k, int max_steps, int start_token,
                                                         long long* __restrict__ prev_words) {
   const BeamState s = beam_state_of(beam, n, k, max_steps);
@@ -532,7 +546,7 @@ template <int THREADS>
 __device__ __forceinline__ void beam_advance_tail(const BeamState& s, int i, int n, int k, int max_steps, int step,
                                                   long long end_token, int V, int live, int picked, const float* s_score,
                                                   const long long* s_flat, long long* __restrict__ next_words,
-                                                  long long* __restrict__ parent_rows) {
+                                                  long long* __restrict__ parent_rows, const BeamTrace tr = BeamTrace{nullptr, nullptr}) {
   __shared__ int s_parent[kBeamMax], s_word[kBeamMax], s_dst[kBeamMax];   // s_dst: slot, or -1 - index in the completed list
   __shared__ int s_alive;
   const int tid = threadIdx.x, L = max_steps + 2;
@@ -561,6 +575,16 @@ __device__ __forceinline__ void beam_advance_tail(const BeamState& s, int i, int
       int* dst = s_dst[j] >= 0 ? seq_out + (long)s_dst[j] * L : seq_done + (long)(-1 - s_dst[j]) * L;
       dst[e] = e < step ? seq_in[(long)s_parent[j] * L + e] : s_word[j];
     }
+    if (tr.rows) {   // the same copy of the parent's row history, then the parent's slot: where this step's map lies
+      const int* rows_in = tr.rows + ((long)((step - 1) & 1) * n * k + row0) * L;
+      int* rows_out = tr.rows + ((long)(step & 1) * n * k + row0) * L;
+      int* rows_done = tr.done_rows + row0 * L;
+      for (int t = tid; t < picked * (step + 1); t += THREADS) {
+        const int j = t / (step + 1), e = t % (step + 1);
+        int* dst = s_dst[j] >= 0 ? rows_out + (long)s_dst[j] * L : rows_done + (long)(-1 - s_dst[j]) * L;
+        dst[e] = e == 0 ? -1 : e < step ? rows_in[(long)s_parent[j] * L + e] : s_parent[j];
+      }
+    }
     if (tid < picked) {
       const int d = s_dst[tid];
       if (d >= 0) {
@@ -585,7 +609,7 @@ __device__ __forceinline__ void beam_advance_tail(const BeamState& s, int i, int
 // beam_advance_tail
 __global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
     void* beam, const float* __restrict__ logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
-    long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+    long long* __restrict__ next_words, long long* __restrict__ parent_rows, void* trace) {
   __shared__ float s_score[kBeamMax];
   __shared__ long long s_flat[kBeamMax];
   const BeamState s = beam_state_of(beam, n, k, max_steps);
@@ -594,7 +618,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
   const int live = s.live[i];
   if (live > 0) beam_topk_body(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
   beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, live, s_score, s_flat, next_words,
-                                  parent_rows);
+                                  parent_rows, beam_trace_of(trace, n, k, max_steps));
 }
 
 // beam_advance_kernel on a step's candidates instead of its logits (capnet_vocab_topk: values / index [n k][k] best first,
@@ -657,7 +681,8 @@ __global__ __launch_bounds__(kBeamTopkThreads) void beam_advance_topk_kernel(
 
 // one wave per image: the first maximum of the completed scores in completion order; nothing completed -> [<end>]
 __global__ __launch_bounds__(64) void beam_finish_kernel(const void* beam, int n, int k, int max_steps, long long end_token,
-                                                         long long* __restrict__ seqs, int* __restrict__ lengths) {
+                                                         long long* __restrict__ seqs, int* __restrict__ lengths,
+                                                         const void* trace, int* __restrict__ rows) {
   const BeamState s = beam_state_of(const_cast<void*>(beam), n, k, max_steps);
   const int i = blockIdx.x, L = max_steps + 2;
   const long row0 = (long)i * k;
@@ -669,6 +694,13 @@ __global__ __launch_bounds__(64) void beam_finish_kernel(const void* beam, int n
   const int* src = s.done_seq + (row0 + best) * L;
   for (int e = threadIdx.x; e < L; e += 64) seqs[(long)i * L + e] = e >= len ? 0 : done ? src[e] : end_token;
   if (threadIdx.x == 0) lengths[i] = len;
+  if (rows) {   // the winner's rows as rows of the decoder step, i k + slot; -1 past its last word and for a slot out of range
+    const int* rsrc = beam_trace_of(const_cast<void*>(trace), n, k, max_steps).done_rows + (row0 + best) * L;
+    for (int e = threadIdx.x; e < max_steps; e += 64) {
+      const int slot = done && e + 1 < len ? rsrc[e + 1] : -1;
+      rows[(long)i * max_steps + e] = slot >= 0 && slot < k ? (int)row0 + slot : -1;
+    }
+  }
 }
 
 static int beam_check(const char* what, const void* beam, int n, int k, int max_steps) {
@@ -694,16 +726,21 @@ int beam_init(void* beam, int n, int k, int max_steps, long long start_token, lo
 }
 
 int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
-                 long long* next_words, long long* parent_rows, hipStream_t stream) {
+                 long long* next_words, long long* parent_rows, hipStream_t stream, void* trace) {
   if (int rc = beam_check("beam_advance", beam, n, k, max_steps)) return rc;
   CAPNET_REQUIRE(logits && next_words && parent_rows, "beam_advance: null argument");
   CAPNET_REQUIRE(V >= 1 && k <= V && ld >= V && step >= 1 && step <= max_steps,
                  "beam_advance: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", V, k, ld, step,
                  max_steps);
   hipLaunchKernelGGL(beam_advance_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps, step,
-                     end_token, next_words, parent_rows);
+                     end_token, next_words, parent_rows, trace);
   CAPNET_LAUNCH_CHECK();
   return kOk;
+}
+
+size_t beam_trace_bytes(int n, int k, int max_steps) {
+  if (n < 1 || k < 1 || k > kBeamMax || max_steps < 1) return 0;
+  return 3 * (size_t)n * k * (max_steps + 2) * sizeof(int);
 }
 
 int beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k, int max_steps,
@@ -719,10 +756,12 @@ int beam_advance_topk(void* beam, const float* values, const int* index, const f
 }
 
 int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
-                hipStream_t stream) {
+                hipStream_t stream, const void* trace, int* rows) {
   if (int rc = beam_check("beam_finish", beam, n, k, max_steps)) return rc;
   CAPNET_REQUIRE(seqs && lengths, "beam_finish: null argument");
-  hipLaunchKernelGGL(beam_finish_kernel, dim3(n), dim3(64), 0, stream, beam, n, k, max_steps, end_token, seqs, lengths);
+  CAPNET_REQUIRE(!trace == !rows, "beam_finish: the trace and the rows go together");
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(n), dim3(64), 0, stream, beam, n, k, max_steps, end_token, seqs, lengths, trace,
+                     rows);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -282,7 +282,8 @@ template <class Step>
 static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, long long start_token, long long end_token,
                      const float* Cw, const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats,
                      int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
-                     bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr) {
+                     bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr,
+                     void* trace = nullptr, int* trace_rows = nullptr) {   // (the row trace: beam_advance's, logits form only)
   const int nk = n * k, rpg = nk / groups;
   const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused, groups);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
@@ -319,7 +320,7 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
         rc = sgemm_splitk(false, true, rpg, V, H, h_top + (size_t)g * rpg * H, H, Cwg[g], H, logits + (size_t)g * rpg * V, V,
                           Cbg ? Cbg[g] : nullptr, 0, slab, slab_floats, s);
       if (rc == kOk && !Cwg) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
-      if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
+      if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);
     }
     if (rc != kOk) return rc;
     issued = step;
@@ -331,7 +332,7 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
     }
   }
   if (steps_run) *steps_run = issued;
-  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, s);
+  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, s, trace, trace_rows);
 }
 
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
@@ -396,6 +397,18 @@ int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int
 // ---- the same loop for the attention decoders: the step is att_decode_step (z, the two attention launches, layer 0 on
 // [embedding | gated context], the upper layers) ----
 // ws: beam_decode's layout, then att_decode_step's block (z | xa | escore)
+// the maps of the winners out of the per-step history: workgroup (i, e) copies hist[e][rows[i][e]] -- the row hypothesis i
+// occupied at step e + 1 -- to alphas[i][e]; a row of -1 (past the caption, nothing completed) or out of range gives zeros
+__global__ __launch_bounds__(256) void alpha_gather_kernel(const float* __restrict__ hist, const int* __restrict__ rows, int nk,
+                                                           int max_steps, int P, float* __restrict__ alphas) {
+  const int i = blockIdx.x, e = blockIdx.y;
+  const int r = rows[(long)i * max_steps + e];
+  const bool ok = r >= 0 && r < nk;
+  const float* src = hist + ((size_t)e * nk + (ok ? r : 0)) * P;
+  float* dst = alphas + ((size_t)i * max_steps + e) * P;
+  for (int p = threadIdx.x; p < P; p += 256) dst[p] = ok ? src[p] : 0.f;
+}
+
 size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps) {
   const size_t base = beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps), step = att_decode_step_ws_bytes(n, k, P, A, C, E);
   return base && step ? base + gd_align(step) : 0;
@@ -406,15 +419,47 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups) {
+                    hipStream_t s, int groups, float* alphas) {
   const int nq = groups * n;   // beam groups: weight groups x images, group-major
-  void* step_ws = reinterpret_cast<char*>(ws) + beam_decode_layout(nlayers, nq, k, H, V, max_steps).total;
-  return beam_loop(nlayers, nq, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
-                   lengths, steps_run, s,
-                   [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
-                     return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
-                                            sin, parent, sout, h_top, step_ws, slab, slab_floats, err_flag, s, groups);
-                   });
+  char* p = reinterpret_cast<char*>(ws);
+  void* step_ws = p + beam_decode_layout(nlayers, nq, k, H, V, max_steps).total;
+  // the maps (alphas set): behind the search's own workspace, trace | rows int32 [nq][max_steps] | history
+  // [max_steps][nq k][P] -- step e's attention writes slice e - 1, the advance records the rows, one gather at the end
+  void* trace = nullptr;
+  int* rows = nullptr;
+  float* hist = nullptr;
+  if (alphas) {
+    p += att_beam_decode_ws_bytes(nlayers, nq, k, P, A, C, E, H, V, max_steps);
+    trace = p;
+    p += gd_align(beam_trace_bytes(nq, k, max_steps));
+    rows = reinterpret_cast<int*>(p);
+    p += gd_align((size_t)nq * max_steps * sizeof(int));
+    hist = reinterpret_cast<float*>(p);
+  }
+  int calls = 0;   // the step the loop is at: it calls the step once per step, in order
+  const int rc = beam_loop(
+      nlayers, nq, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs, lengths,
+      steps_run, s,
+      [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
+        float* slice = hist ? hist + (size_t)calls++ * nq * k * P : nullptr;
+        return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff, sin, parent,
+                               sout, h_top, step_ws, slab, slab_floats, err_flag, s, groups, slice);
+      },
+      false, 1, nullptr, nullptr, trace, rows);
+  if (rc != kOk || !alphas) return rc;
+  hipLaunchKernelGGL(alpha_gather_kernel, dim3(nq, max_steps), dim3(256), 0, s, hist, rows, nq * k, max_steps, P, alphas);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+size_t att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                       int max_steps) {
+  if (groups < 1 || groups > 8 || n < 1 || n >= (1 << 24)) return 0;
+  const int nq = groups * n;
+  const size_t base = att_beam_decode_ws_bytes(nlayers, nq, k, P, A, C, E, H, V, max_steps);
+  if (!base) return 0;
+  return base + gd_align(beam_trace_bytes(nq, k, max_steps)) + gd_align((size_t)nq * max_steps * sizeof(int)) +
+         gd_align((size_t)max_steps * nq * k * P * sizeof(float));
 }
 
 }  // namespace capnet

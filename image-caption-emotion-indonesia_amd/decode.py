@@ -6,6 +6,10 @@ mode selects, the layout of their beam state, their weight fold.
     `_beam` method; its sample() asks for one group of k beams, its sample_batch() for n groups. one_call=True: the
     whole search of a plain stack in one C call (ops.beam_decode) on the PlainStack a class attaches to its step_fn
     (plain_stack: the fused step's packed weights, the embedding table and the projection).
+    return_alphas: the attention maps that preceded every word of the captions -- recorded by the one-call search
+    (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
+    re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
+    replay_alphas feeds the returned tokens back through the composed step, whose step_fn keeps its last maps in .alpha.
   * attend: Attention.forward, the single step outside a beam search.
   * att_beam_start / att_beam_step: an attention decoder's beam search. The set-up (encoder_att once per image, the
     initial state) is written once for one image and once for n; the step (z = [decoder_att; f_beta](h), the embedding
@@ -82,7 +86,55 @@ def att_stack(step_fn, dec, cell, pack, attention, embed, project, maps, k, entr
     return step_fn
 
 
-def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False):
+ALPHA_TRACE_MAX_BYTES = 256 << 20     # the one-call search's map history (steps x rows x P floats): a cap on memory
+
+
+def replay_alphas(step_fn, state, seqs, n, k):
+    """The attention maps of decoded captions by replay -> a list of float32 [len - 1, P] tensors, row e - 1 the softmax
+    over the pixels that preceded word e: the token lists `seqs` (one list, n None; else n lists) are fed back through
+    step_fn (att_beam_step's, which keeps the maps of its last step in .alpha) from the initial beam `state` of the search,
+    one row per caption -- the first of each image's k. All captions of a batch advance together; a finished one
+    repeats its last token and its maps are no longer kept. A caption [<end>] alone (nothing completed) has [0, P]."""
+    with torch.no_grad():
+        dev = state[0].device
+        lists = [list(seqs)] if n is None else [list(q) for q in seqs]
+        first = torch.arange(len(lists), device=dev) * k
+        state = tuple(t.index_select(0, first).contiguous() for t in state)
+        steps = [len(q) - 1 for q in lists]
+        maps = [[] for _ in lists]
+        for e in range(1, max(steps) + 1):
+            words = torch.tensor([q[min(e, len(q)) - 1] for q in lists], dtype=torch.long, device=dev)
+            _, state = step_fn(words, state)
+            for i, m in enumerate(steps):
+                if e <= m:
+                    maps[i].append(step_fn.alpha[i])
+        P = step_fn.alpha.shape[1]     # (no step here: every caption is [<end>], and the search itself ran step_fn)
+        return [torch.stack(m) if m else torch.zeros((0, P), dtype=torch.float32, device=dev) for m in maps]
+
+
+def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas):
+    """ops.att_beam_decode on an AttStack; with the maps, the images in as few chunks as keep the history [steps, rows, P]
+    under ALPHA_TRACE_MAX_BYTES."""
+    T, P = dec.max_seq_length + 1, att.feat.shape[1]
+
+    def call(a1, ft, st):
+        return ops.att_beam_decode(att.cell, a1, ft, att.emb, att.wz, att.bz, att.full_att.weight, att.full_att.bias, att.wcat,
+                                   att.beff, att.Cw, att.Cb, st, k, T, start_token, end_token, poll_every,
+                                   return_alphas=return_alphas)
+    per = max(1, ALPHA_TRACE_MAX_BYTES // (T * k * P * 4)) if return_alphas else n_img
+    if per >= n_img:
+        return call(att.att1, att.feat, att.state)
+    seqs, maps = [], []
+    for i0 in range(0, n_img, per):
+        i1 = min(n_img, i0 + per)
+        q, m = call(att.att1[i0:i1], att.feat[i0:i1], att.state[i0 * k:i1 * k])
+        seqs += q
+        maps += m
+    return seqs, maps
+
+
+def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False,
+                return_alphas=False):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
@@ -90,8 +142,21 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     as there). one_call: the same search as ONE C call (ops.beam_decode: the parent rows read by the step itself, no
     Python per step) where step_fn carries a PlainStack and the shape is one ops.beam_decode_supported, or carries an
     AttStack (ops.att_beam_decode; att_stack attaches it only for a supported shape); everywhere else -- an unsupported
-    shape, an embedding width that is no multiple of 4, CAPNET_NO_FUSED_DECODE_STEP=1 -- it is on_device=True."""
+    shape, an embedding width that is no multiple of 4, CAPNET_NO_FUSED_DECODE_STEP=1 -- it is on_device=True.
+    return_alphas (attention decoders: step_fn is att_beam_step's): the result is followed by the attention maps, float32
+    [len - 1, P] per caption on the decoder's device (n None: one tensor), row e - 1 the map that preceded word e. The
+    one-call search records them as it goes; every other route decodes as it does without the keyword and gets them from
+    replay_alphas. The tokens are those of the call without the keyword."""
     dev = state[0].device
+    if return_alphas:
+        att = getattr(step_fn, "att", None) if one_call else None
+        if att is not None:
+            with torch.no_grad():
+                seqs, maps = _one_call_att(dec, att, 1 if n is None else n, k, start_token, end_token, poll_every, True)
+            return (seqs, maps) if n is not None else (torch.tensor(seqs, dtype=torch.long, device=dev), maps[0])
+        seqs = beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call)
+        maps = replay_alphas(step_fn, state, seqs if n is not None else seqs[0].tolist(), n, k)
+        return (seqs, maps) if n is not None else (seqs, maps[0])
     with torch.no_grad():
         if one_call:
             plain, on_device = getattr(step_fn, "plain", None), True
@@ -182,17 +247,17 @@ def att_beam_step(attention, f_beta, embed, cell, project, att1_of, feat_of, n_a
         if E % 4 == 0:
             xa = torch.empty((s_rows, E + n_att), dtype=torch.float32, device=dev)
             xa[:, :E] = embed(prev_words)
-            ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
-                               attention.full_att.bias, xa=xa, xa_col=E)
+            _, step_fn.alpha = ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
+                                                  attention.full_att.bias, xa=xa, xa_col=E)
         else:       # the context kernel stores 16-B vectors: behind an embedding width off 4 the context is joined on
             ctx = torch.empty((s_rows, n_att), dtype=torch.float32, device=dev)
-            ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
-                               attention.full_att.bias, xa=ctx)
+            _, step_fn.alpha = ops.attention_step(att1_of(state, s_rows), feat_of(state, s_rows), z, A, attention.full_att.weight,
+                                                  attention.full_att.bias, xa=ctx)
             xa = torch.cat([embed(prev_words).reshape(s_rows, E), ctx], 1)
         h, c = cell(xa, (h, c))
         top, new = upper_step(h, rest)
         return project(top), (h, c) + tuple(new) + rest[len(new):]
-    step_fn.wz, step_fn.bz = wz, bz
+    step_fn.wz, step_fn.bz, step_fn.alpha = wz, bz, None      # .alpha: the maps [rows, P] of the step taken last
     return step_fn
 
 
@@ -308,11 +373,14 @@ def plain_styles(dec, layer_mods, num_layers, emb, C, n, k, start_token, end_tok
     return out
 
 
-def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token, modes, poll_every, loop):
+def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token, modes, poll_every, loop, return_alphas=False):
     """sample_styles of an attention decoder -> {mode: [n token lists]}: ONE ops.att_beam_decode(groups=len(modes)) over
     modes x images x k rows. Per mode: its folded chain (fold_styles), its Attention module's encoder_att(feat) (att1
     [G n, P, A]), [decoder_att; f_beta] and full_att; shared: the map feat [n, P, C], the embedding, the projection and
-    the initial state (init_h / init_c of every layer), repeated per mode. loop(mode) as plain_styles'."""
+    the initial state (init_h / init_c of every layer), repeated per mode. loop(mode) as plain_styles'.
+    return_alphas: -> ({mode: lists}, {mode: [n float32 [len - 1, P] tensors]}), the maps of every mode's own Attention
+    module recorded by the grouped search (loop(mode) then returns (lists, tensors)); the images in chunks that also keep
+    the map history under ALPHA_TRACE_MAX_BYTES."""
     G, n, Cdim = len(modes), features.size(0), features.size(-1)
     E, A, V = dec.B.weight.shape[1], dec.attention_size, dec.vocab_size
     with torch.no_grad():
@@ -321,7 +389,10 @@ def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token,
         P = feat.size(1)
         per = styles_images(n, G, k, max(V, A + Cdim), dev) if G > 1 else 0
         if per < 1 or not att_stack_supported(dec, E, Cdim, P, k, num_layers):
-            return {m: loop(m) for m in modes}
+            res = {m: loop(m) for m in modes}
+            return ({m: r[0] for m, r in res.items()}, {m: r[1] for m, r in res.items()}) if return_alphas else res
+        if return_alphas:
+            per = max(1, min(per, ALPHA_TRACE_MAX_BYTES // ((dec.max_seq_length + 1) * G * k * P * 4)))
         atts = [dec._mode_modules(m)[0] for m in modes]
         packed = fold_styles(layer_mods, num_layers, modes)
         wcat, beff = [w for w, _ in packed], [b for _, b in packed]
@@ -330,7 +401,7 @@ def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token,
         bz = torch.stack([torch.cat([a.decoder_att.bias, dec.f_beta.bias], 0) for a in atts]).contiguous()
         wf = torch.stack([a.full_att.weight.reshape(-1) for a in atts]).contiguous()
         bf = torch.cat([a.full_att.bias.reshape(-1) for a in atts]).contiguous()
-        out = {m: [] for m in modes}
+        out, maps = {m: [] for m in modes}, {m: [] for m in modes}
         for i0 in range(0, n, per):
             fi = feat[i0:i0 + per]
             ni = fi.size(0)
@@ -341,10 +412,15 @@ def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token,
             entries = (h0.index_select(0, img), c0.index_select(0, img)) + tuple(upper)
             state = torch.cat([t.unsqueeze(1) for t in entries], 1).repeat(G, 1, 1).contiguous()
             seqs = ops.att_beam_decode(ops.CELL_FACTORED, att1, fi, dec.B.weight, wz, bz, wf, bf, wcat, beff, dec.C.weight,
-                                       dec.C.bias, state, k, dec.max_seq_length + 1, start_token, end_token, poll_every, groups=G)
+                                       dec.C.bias, state, k, dec.max_seq_length + 1, start_token, end_token, poll_every, groups=G,
+                                       return_alphas=return_alphas)
+            if return_alphas:
+                seqs, alphas = seqs
             for g, m in enumerate(modes):
                 out[m] += seqs[g * ni:(g + 1) * ni]
-    return out
+                if return_alphas:
+                    maps[m] += alphas[g * ni:(g + 1) * ni]
+    return (out, maps) if return_alphas else out
 
 
 def pack_cells(cells, E):

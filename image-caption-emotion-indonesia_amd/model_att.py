@@ -207,22 +207,26 @@ class DecoderFactoredLSTMAtt(nn.Module):
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
-               one_call=False):
+               one_call=False, return_alphas=False):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
         of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
         one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps,
-        the chain folded); on_device=True for a shape that call does not take. Same sequences."""
+        the chain folded); on_device=True for a shape that call does not take. Same sequences.
+        return_alphas: -> (ids [1, L], alphas float32 [L - 1, P]), row e - 1 the map of the mode's Attention module that
+        preceded word e (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route)."""
         return beam_decode(self, *self._beam(features, None, k, mode, one_call), None, k, start_token, end_token, on_device, poll_every,
-                           one_call)
+                           one_call, return_alphas)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0, one_call=False):
+                     poll_every=0, one_call=False, return_alphas=False):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once: the reference's evaluator
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
-        images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists."""
+        images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists; with
+        return_alphas, (the n token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
+                           return_alphas)
 
     def _style_layers(self):
         """The layers sample_styles folds: one here (capnet.stacked_att: num_layers)."""
@@ -236,12 +240,23 @@ class DecoderFactoredLSTMAtt(nn.Module):
         shared, the maps read in place by every mode. modes: a non-empty sequence of distinct mode names (an unknown one
         as in sample()). A shape capnet_att_beam_decode does not take, an embedding width that is no multiple of 4 or
         CAPNET_NO_FUSED_DECODE_STEP=1: the modes are decoded one sample_batch(one_call=True) after the other.
-        poll_every: capnet.decode.beam_decode's."""
+        poll_every: capnet.decode.beam_decode's. (With the attention maps: sample_styles_alphas.)"""
+        return self._styles(features, start_token, end_token, k, modes, poll_every, False)
+
+    def sample_styles_alphas(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0):
+        """sample_styles with return_alphas=True -> ({mode: [n token lists]}, {mode: [n float32 [len - 1, P] tensors]}): the
+        lists are sample_styles', and each mode's maps are those of sample_batch(mode=mode, one_call=True,
+        return_alphas=True), from the mode's own Attention module, recorded by the one grouped search -- where the happy
+        caption looked next to where the angry one did. (A method of its own: sample_styles' parameters are pinned.)"""
+        return self._styles(features, start_token, end_token, k, modes, poll_every, True)
+
+    def _styles(self, features, start_token, end_token, k, modes, poll_every, return_alphas):
         modes = decode.check_styles(modes, self._mode_modules)
         return decode.att_styles(self, lambda l, m: _layer_mods(self, "" if l == 0 else str(l), m), self._style_layers(),
                                  features, k, start_token, end_token, modes, poll_every,
                                  lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
-                                                             poll_every=poll_every))
+                                                             poll_every=poll_every, return_alphas=return_alphas),
+                                 return_alphas)
 
     def forward(self,
                 captions,

@@ -113,15 +113,21 @@ class DecoderRNNAtt(nn.Module):
                              self.attention, self.embed, self.linear, maps, k, (h0, c0) + state)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, return_alphas=False):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
         one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps);
-        on_device=True for a shape that call does not take. Same sequences."""
-        return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
+        on_device=True for a shape that call does not take. Same sequences.
+        return_alphas: -> (ids [1, L], alphas float32 [L - 1, P]), row e - 1 the attention map that preceded word e
+        (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route)."""
+        return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
+                           return_alphas)
 
-    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False,
+                     return_alphas=False):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).
-        Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist()."""
+        Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist(); with return_alphas, (the n
+        token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(features, n, k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(features, n, k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
+                           return_alphas)

@@ -289,6 +289,53 @@ def beam_finish(beam, end_token):
     return seqs, lengths, packed
 
 
+def beam_trace(beam):
+    """The row trace of a BeamState (capnet_beam_trace_bytes): int32 words beside the state, for beam_advance_traced /
+    beam_finish_traced. It needs no initialisation."""
+    nbytes = _lib.lib().capnet_beam_trace_bytes(beam.n, beam.k, beam.max_steps)
+    if not nbytes:
+        raise CapnetError("beam trace: n=%d k=%d max_steps=%d" % (beam.n, beam.k, beam.max_steps))
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=beam.words.device)
+
+
+def _check_trace(who, beam, trace):
+    _need_cuda(trace)
+    if trace is None or trace.dtype != torch.int32 or not trace.is_contiguous() or \
+            trace.numel() * 4 < _lib.lib().capnet_beam_trace_bytes(beam.n, beam.k, beam.max_steps):
+        raise CapnetError("%s: trace must be beam_trace(beam)" % who)
+
+
+def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent_rows):
+    """capnet_beam_advance_traced: beam_advance that also records, in `trace` (beam_trace(beam)), the slot every hypothesis
+    occupied at this step -- see include/capnet.h."""
+    _need_cuda(logits, next_words, parent_rows)
+    _check_trace("beam_advance_traced", beam, trace)
+    nk = beam.n * beam.k
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
+        raise CapnetError("beam_advance_traced: logits must be float32 [n k, V] with unit column stride")
+    for w in (next_words, parent_rows):
+        if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
+            raise CapnetError("beam_advance_traced: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    check(_lib.lib().capnet_beam_advance_traced(ptr(beam.words), ptr(trace), ptr(logits),
+                                                logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
+                                                beam.max_steps, int(step), int(end_token), ptr(next_words), ptr(parent_rows),
+                                                current_stream()), "capnet_beam_advance_traced")
+
+
+def beam_finish_traced(beam, trace, end_token):
+    """capnet_beam_finish_traced -> (seqs int64 [n, max_steps + 2], lengths int32 [n], rows int32 [n, max_steps]): rows[i,
+    e - 1] is the decoder-step row (i k + slot) whose step-e attention preceded word e of the winner, -1 past length - 1."""
+    _check_trace("beam_finish_traced", beam, trace)
+    n, L = beam.n, beam.max_steps + 2
+    dev = beam.words.device
+    seqs = torch.empty((n, L), dtype=torch.int64, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    rows = torch.empty((n, beam.max_steps), dtype=torch.int32, device=dev)
+    check(_lib.lib().capnet_beam_finish_traced(ptr(beam.words), ptr(trace), n, beam.k, beam.max_steps, int(end_token), ptr(seqs),
+                                               ptr(lengths), ptr(rows), current_stream()), "capnet_beam_finish_traced")
+    return seqs, lengths, rows
+
+
 def attention_step(att1, feat, z, A, w_full, b_full, xa=None, xa_col=0):
     """One attention step for s rows (no autograd; Attention.forward / sample()).
     att1 [s, P, A] = encoder_att(features); feat [s, P, C]; z [s, A + C] = [decoder_att(h) |
@@ -1020,7 +1067,7 @@ def att_decode_step_workspace(n, k, P, A, Cdim, E, device):
 
 
 def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, beff, state, cell=CELL_FACTORED, parent_rows=None,
-                    workspace=None, groups=1):
+                    workspace=None, groups=1, alphas=None):
     """One beam step of an attention decoder without the projection (capnet_att_decode_step): n images x k fixed slots, row
     r on the maps of image r // k. att1 [n, P, A] = encoder_att(feat), feat [n, P, C]: per image, never per row. wz [A + C,
     H] / bz = [decoder_att; f_beta]; w_full / b_full: full_att; wcat / beff: capnet.decode.pack_cell / fold_factored per
@@ -1028,6 +1075,8 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
     state.index_select(0, parent_rows) without that copy. workspace: att_decode_step_workspace(...) or None.
     groups > 1 (capnet_att_decode_step_groups): `groups` weight groups on the same n images, operands as _att_decode_args
     says, workspace att_decode_step_workspace(groups n, ...); each group's rows equal the step of that group alone.
+    alphas: a contiguous float32 [groups n k, P] tensor that receives every row's attention map
+    (capnet_att_decode_step_alphas); the state and the top h are those of the call without it, bit for bit.
     Returns (top-layer h [n k, H], the new state)."""
     groups = _check_groups("att_decode_step", groups)
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
@@ -1051,7 +1100,12 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
     args = (n, int(k), P, A, Cdim, E, H, V, ptr(att1), ptr(feat), ptr(tokens), ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf),
             ptr_array(wcat), ptr_array(beff), ptr(state), ptr(parent_rows), ptr(out), ptr(top), ptr(workspace), ptr(slab),
             slab.numel(), ptr(err_flag(dev)), current_stream())
-    if groups > 1:
+    if alphas is not None:
+        _need_cuda(alphas)
+        if alphas.dtype != torch.float32 or tuple(alphas.shape) != (rows, P) or not alphas.is_contiguous():
+            raise CapnetError("att_decode_step: alphas must be a contiguous float32 [n k, P] tensor")
+        check(L.capnet_att_decode_step_alphas(cell, nl, groups, *args, ptr(alphas)), "capnet_att_decode_step_alphas")
+    elif groups > 1:
         check(L.capnet_att_decode_step_groups(cell, nl, groups, *args), "capnet_att_decode_step_groups")
     else:
         check(L.capnet_att_decode_step(cell, nl, *args), "capnet_att_decode_step")
@@ -1059,10 +1113,11 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
 
 
 _att_beam_decode_ws = {}
+_att_beam_decode_alphas_ws = {}
 
 
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
-                    end_token, poll_every=0, return_steps=False, groups=1):
+                    end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False):
     """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
     steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
     capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
@@ -1070,7 +1125,11 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     Sequences, lengths and the device's error word come to the host in one copy; a set error word raises
     (check_device_errors). groups > 1 (capnet_att_beam_decode_groups): the searches of `groups` weight groups over the same n
     images in the same launches, operands as att_decode_step's; groups n token lists come back, group-major.
-    Returns the n token lists; with return_steps, (lists, the steps issued)."""
+    return_alphas (capnet_att_beam_decode_alphas): the search also records its attention maps -- every step's maps into a
+    history, the winners' rows through the re-slotting, one gather at the end; the maps stay on the device. The token
+    lists are those of the call without it.
+    Returns the n token lists; with return_steps, (lists, the steps issued); with return_alphas the lists are followed by
+    the list of n float32 [len - 1, P] tensors: row e - 1 is the map that preceded word e."""
     groups = _check_groups("att_beam_decode", groups)
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
         "att_beam_decode", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state, groups)
@@ -1084,11 +1143,13 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     L = _lib.lib()
     n_img, n = n, groups * n       # from here on n counts the beam groups
     key = (dev.index or 0, nl, n, k, P, A, Cdim, E, H, V, T)
-    ws = _att_beam_decode_ws.get(key)
+    cache = _att_beam_decode_alphas_ws if return_alphas else _att_beam_decode_ws
+    ws = cache.get(key)
     if ws is None:
-        ws = torch.empty((L.capnet_att_beam_decode_ws_bytes(nl, n, k, P, A, Cdim, E, H, V, T) + 7) // 8, dtype=torch.int64,
-                         device=dev)
-        _att_beam_decode_ws[key] = ws
+        nbytes = L.capnet_att_beam_decode_alphas_ws_bytes(nl, groups, n_img, k, P, A, Cdim, E, H, V, T) if return_alphas else \
+            L.capnet_att_beam_decode_ws_bytes(nl, n, k, P, A, Cdim, E, H, V, T)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        cache[key] = ws
     slab = splitk_slab(dev)
     SL = T + 2
     # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
@@ -1099,7 +1160,11 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     args = (n_img, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz),
             ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
             int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream())
-    if groups > 1:
+    maps = None
+    if return_alphas:
+        maps = torch.empty((n, T, P), dtype=torch.float32, device=dev)
+        check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(maps)), "capnet_att_beam_decode_alphas")
+    elif groups > 1:
         check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
     else:
         check(L.capnet_att_beam_decode(cell, nl, *args), "capnet_att_beam_decode")
@@ -1111,7 +1176,10 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     lens = htail[:n].tolist()
     rows = host[:n * SL].view(n, SL).tolist()
     out = [rows[i][:lens[i]] for i in range(n)]
-    return (out, steps.value) if return_steps else out
+    res = (out, steps.value) if return_steps else (out,)
+    if return_alphas:
+        res += ([maps[i, :lens[i] - 1] for i in range(n)],)
+    return res if len(res) > 1 else out
 
 
 def packed_targets(captions, lengths):

@@ -827,6 +827,59 @@ int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int 
                                   int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                                   capnet_stream_t stream);
 
+/* The attention maps of the one-call search: for a caption [start, w_1 .. w_m], row e - 1 of its maps is the softmax over
+ * the P pixels that the decoder computed at step e, from the layer-0 hidden state reached on start, w_1 .. w_{e-1}.
+ *
+ * The row trace. Beams change slots at every step, so the search remembers, per hypothesis, the slot it occupied at
+ * every step: `trace`, capnet_beam_trace_bytes(n, k, max_steps) bytes of caller-owned device memory BESIDE the beam
+ * state (the state's layout and capnet_beam_state_bytes do not change), 4-byte aligned, in the sequences' own shape:
+ * rows int32 [2][n][k][max_steps + 2] (the two buffers swap as the state's sequences do) | done_rows [n][k][max_steps + 2].
+ * Entry e (1 <= e <= step) is the slot, within the image, whose step-e attention preceded word e; entry 0 is -1. It
+ * needs no initialisation: step 1 reads nothing of it.
+ *   capnet_beam_advance_traced: capnet_beam_advance (same selection, same state, same next_words / parent_rows) whose
+ *     copy of a survivor's or a completion's tokens also copies its parent's row history and appends the parent's slot.
+ *   capnet_beam_finish_traced: capnet_beam_finish, and rows int32 [n][max_steps]: entry e - 1 is the winner's row at step e
+ *     as a row of the decoder step, i k + slot; -1 past length - 1, everywhere where nothing completed, and for a
+ *     recorded slot outside [0, k) -- a recorded row is never used as an address unchecked.
+ * 0 bytes / an error for n < 1, k outside 1..16, max_steps < 1, a null or misaligned pointer. */
+size_t capnet_beam_trace_bytes(int n, int k, int max_steps);
+int capnet_beam_advance_traced(void* beam, void* trace, const float* logits, long ld, int V, int n, int k, int max_steps,
+                               int step, long long end_token, long long* next_words, long long* parent_rows,
+                               capnet_stream_t stream);
+int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
+                              long long* seqs, int* lengths, int* rows, capnet_stream_t stream);
+
+/* capnet_att_decode_step_groups with its maps out: alphas f32 [groups n k][P] (required, 4-byte aligned), row r = the
+ * softmax over the pixels of row r's scores, stored by the context kernel's first channel block of the image from the
+ * values it multiplies the map with. The state, h_top and the workspace's contents are those of the call without it,
+ * bit for bit. */
+int capnet_att_decode_step_alphas(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  const float* att1, const float* feat, const long long* tokens, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* state_in,
+                                  const long long* parent_rows, float* state_out, float* h_top, void* workspace, float* slab,
+                                  size_t slab_floats, int* err_flag, capnet_stream_t stream, float* alphas);
+
+/* capnet_att_beam_decode_groups that also returns the winners' maps: alphas f32 [groups n][max_steps][P] (required,
+ * 4-byte aligned); a caption of `length` tokens has length - 1 rows, the rest are zero ([<end>] alone: all zero). Step e
+ * writes every row's map into slice e - 1 of a history [max_steps][groups n k][P], the advance records rows
+ * (capnet_beam_advance_traced), and after capnet_beam_finish_traced one launch, a workgroup per (caption, step), gathers
+ * history[e - 1][rows[e - 1]]. Sequences and lengths are capnet_att_beam_decode_groups' own. workspace:
+ * capnet_att_beam_decode_alphas_ws_bytes(...) = capnet_att_beam_decode_ws_bytes(nlayers, groups n, ...) + the trace
+ * (capnet_beam_trace_bytes(groups n, k, max_steps)) + the rows (groups n max_steps int32) + the history (max_steps groups
+ * n k P floats), each part rounded up to 16 bytes; 0 for the shapes capnet_att_beam_decode_ws_bytes refuses and groups
+ * outside 1..8. poll_every and *steps_run as before (steps that were not issued leave their slices unread). Every bad
+ * argument is refused before any launch. */
+size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps);
+int capnet_att_beam_decode_alphas(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                  int max_steps, long long start_token, long long end_token, const float* att1,
+                                  const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream, float* alphas);
+
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
  *   capnet_lstm_pack_wfrag image), then the gate
