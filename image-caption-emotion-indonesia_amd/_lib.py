@@ -194,6 +194,12 @@ SIGNATURES = {
                                                                                                   _vp, _vp, _vp, _vp, _vp, _sz,
                                                                                                   _i, _vp, _vp, C.POINTER(_i),
                                                                                                   _vp, _vp, _vp]),
+    "capnet_beam_nbest": (_i, [_vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_beam_nbest_traced": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_beam_decode_ws_beam_offset": (_sz, [_i] * 8),
+    "capnet_att_beam_decode_alphas_ws_trace_offset": (_sz, [_i] * 11),
+    "capnet_att_beam_decode_alphas_ws_hist_offset": (_sz, [_i] * 11),
+    "capnet_alpha_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "capnet_lstm_wfrag_floats": (_sz, [_i]),
     "capnet_lstm_pack_wfrag": (_i, [_vp, _vp, _i, _i, _vp]),
     "capnet_lstm_step_fused": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -21,10 +21,23 @@ import torch
 from . import ops
 
 
-def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_length, device):
+def rank_completed(done, length_penalty=0.0):
+    """The n-best list of one image from its completed hypotheses `done`, (score, tokens) pairs in completion order ->
+    [(tokens, score)], best first: the key is score / (len(tokens) - 1)^length_penalty (len - 1: the generated words, <end>
+    included; penalty 0: the score itself), ties go to the earlier completion -- capnet_beam_nbest's rule. Entry 0 at
+    penalty 0 is the first maximum, the searches' winner."""
+    def key(q):
+        score, tokens = done[q]
+        return score if length_penalty == 0 else score / float(len(tokens) - 1) ** length_penalty
+    return [(list(done[q][1]), float(done[q][0])) for q in sorted(range(len(done)), key=lambda q: (-key(q), q))]
+
+
+def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False, length_penalty=0.0):
     """step_fn(prev_words LongTensor[s], state) -> (logits [s, V], state'); `state` is a tuple of
     tensors whose leading dimension is the beam and which are re-indexed here when beams are
-    re-ordered or retired. Returns LongTensor [1, L] (starts with start_token)."""
+    re-ordered or retired. Returns LongTensor [1, L] (starts with start_token); nbest: the list of
+    (LongTensor [1, L], score) of every completed sequence, rank_completed's order, empty where
+    nothing completed."""
     k_prev_words = torch.full((k,), start_token, dtype=torch.long, device=device)
     seqs = [[int(start_token)] for _ in range(k)]
     top_k_scores = torch.zeros(k, dtype=torch.float32, device=device)
@@ -58,13 +71,17 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
         if step > max_seq_length:
             break
         step += 1
+    if nbest:
+        return [(torch.tensor([q], dtype=torch.long, device=device), sc)
+                for q, sc in rank_completed(list(zip(complete_seqs_scores, complete_seqs)), length_penalty)]
     if not complete_seqs_scores:   # "prevent empty sequence", model.py:287-289
         return torch.tensor([[int(end_token)]], dtype=torch.long, device=device)
     best = complete_seqs_scores.index(max(complete_seqs_scores))
     return torch.tensor([complete_seqs[best]], dtype=torch.long, device=device)
 
 
-def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, poll_every=0):
+def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, poll_every=0,
+                       nbest=False, length_penalty=0.0):
     """beam_search_batched with the bookkeeping on the device (capnet_beam_advance): no host read and no host-built
     tensor per step. Image i keeps rows i k .. i k + k - 1 for the whole search -- its live beams in its first slots, in
     the order beam_search_batched keeps them; dead slots still take the decoder step, their logits are never read -- so
@@ -72,7 +89,8 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
     steps, all the host loop can run; then capnet_beam_finish picks the winners and ONE copy brings sequences and lengths
     to the host. poll_every = m > 0: after every m-th step the count of live beams is read (one blocking 4-byte copy)
     and the loop stops at zero -- same result, for decoders whose beams end long before T.
-    Returns a list of n token lists (each starts with start_token)."""
+    Returns a list of n token lists (each starts with start_token); nbest: per image the list of (tokens, score) of its
+    completed hypotheses, best first (capnet_beam_nbest in capnet_beam_finish's place, still one copy)."""
     if k > 16 or k > vocab_size:
         raise ops.CapnetError("beam_search_device: k <= 16 and k <= vocab_size")
     T = max_seq_length + 1
@@ -90,6 +108,9 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
             break
         state = tuple(s.index_select(0, parent_rows) for s in state)
         prev_words = next_words
+    if nbest:
+        packed = ops.beam_nbest(beam, end_token, length_penalty)[-1]
+        return ops.nbest_lists(packed, n, k, T + 2)[0]
     seqs, lengths, packed = ops.beam_finish(beam, end_token)
     host = packed.cpu()
     L = seqs.shape[1]
@@ -98,13 +119,14 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
     return [rows[i][:lens[i]] for i in range(n)]
 
 
-def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device):
+def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False,
+                        length_penalty=0.0):
     """beam_search for n images at once: the evaluator of the reference (stylenet/evaluator.py:63-120) calls sample() per
     test image, k rows per decode step; here the beams of ALL images advance together -- one decoder step over sum(live
     beams) rows and one capnet_beam_topk_batched launch per step -- with per image exactly beam_search's bookkeeping
     (first step: row 0 only; <end> retires a beam; the best completed sequence wins; empty -> [<end>]).
     `state`: tuple of tensors with n * k leading rows (image i's k beams at rows i k .. i k + k - 1).
-    Returns a list of n token lists (each starts with start_token)."""
+    Returns a list of n token lists (each starts with start_token); nbest: per image rank_completed of its completed list."""
     if k > 16:
         raise ops.CapnetError("beam_search_batched: k <= 16")
     live = [k] * n                                           # beams still open per image
@@ -146,6 +168,8 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
         prev_words = torch.tensor(next_words, dtype=torch.long, device=device)
         top_scores = torch.tensor(next_scores, dtype=torch.float32, device=device)
         step += 1
+    if nbest:
+        return [rank_completed(done[i], length_penalty) for i in range(n)]
     out = []
     for i in range(n):
         if not done[i]:

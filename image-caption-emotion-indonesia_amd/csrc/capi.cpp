@@ -975,6 +975,32 @@ int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k,
                  "beam_finish_traced: the state, the trace and the rows must be 4-byte aligned");
   return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, S(stream), trace, rows);
 }
+int capnet_beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
+                      float* scores, int* counts, capnet_stream_t stream) {
+  return beam_nbest(beam, n, k, max_steps, length_penalty, seqs, lengths, scores, counts, S(stream));
+}
+int capnet_beam_nbest_traced(const void* beam, const void* trace, int n, int k, int max_steps, float length_penalty,
+                             long long* seqs, int* lengths, float* scores, int* counts, int* rows, capnet_stream_t stream) {
+  CAPNET_REQUIRE(trace && rows, "beam_nbest_traced: null trace or rows");
+  CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0 && (size_t)rows % 4 == 0,
+                 "beam_nbest_traced: the state, the trace and the rows must be 4-byte aligned");
+  return beam_nbest(beam, n, k, max_steps, length_penalty, seqs, lengths, scores, counts, S(stream), trace, rows);
+}
+size_t capnet_beam_decode_ws_beam_offset(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, int groups) {
+  return beam_decode_ws_beam_offset(nlayers, n, k, H, V, max_steps, fused_topk, groups);
+}
+size_t capnet_att_beam_decode_alphas_ws_trace_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H,
+                                                     int V, int max_steps) {
+  return att_beam_decode_alphas_ws_trace_offset(nlayers, groups, n, k, P, A, C, E, H, V, max_steps);
+}
+size_t capnet_att_beam_decode_alphas_ws_hist_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H,
+                                                    int V, int max_steps) {
+  return att_beam_decode_alphas_ws_hist_offset(nlayers, groups, n, k, P, A, C, E, H, V, max_steps);
+}
+int capnet_alpha_gather(const float* hist, const int* rows, int captions, int nk, int max_steps, int P, float* alphas,
+                        capnet_stream_t stream) {
+  return alpha_gather(hist, rows, captions, nk, max_steps, P, alphas, S(stream));
+}
 int capnet_beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live,
                      const float** scores) {
   return beam_live(beam, n, k, max_steps, live_total, live, scores);

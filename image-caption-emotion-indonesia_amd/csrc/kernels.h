@@ -231,6 +231,11 @@ int beam_advance_topk(void* beam, const float* values, const int* index, const f
                       int step, long long end_token, long long* next_words, long long* parent_rows, hipStream_t stream);
 int beam_finish(const void* beam, int n, int k, int max_steps, long long end_token, long long* seqs, int* lengths,
                 hipStream_t stream, const void* trace = nullptr, int* rows = nullptr);
+// every completed hypothesis of every image, best first by done_score / (done_len - 1)^length_penalty (penalty 0: by
+// done_score itself), ties to the earlier completion: seqs [n][k][max_steps + 2], lengths / scores [n][k], counts [n]; with
+// the trace, rows [n][k][max_steps] as beam_finish's, per hypothesis. The state is only read.
+int beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
+               float* scores, int* counts, hipStream_t stream, const void* trace = nullptr, int* rows = nullptr);
 int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
 int gather_rows(const float* src, const int* idx, float* out, int rows, int C, hipStream_t stream);
 int colsum(const float* x, long ld, int rows, int C, float* out, int accumulate, hipStream_t stream,
@@ -365,6 +370,16 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
 // rows | the history [max_steps][groups n k][P] of every step's maps
 size_t att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
                                        int max_steps);
+// where a one-call search leaves what capnet_beam_nbest reads, as byte offsets into its workspace (0: a refused shape).
+// The beam state of beam_decode_layout (n: the sentences of one group; the attention searches share the unfused layout);
+// the trace and the history of att_beam_decode's maps.
+size_t beam_decode_ws_beam_offset(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, int groups);
+size_t att_beam_decode_alphas_ws_trace_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps);
+size_t att_beam_decode_alphas_ws_hist_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                             int max_steps);
+// alpha_gather_kernel on its own: alphas [captions][max_steps][P] = hist[e][rows[caption][e]], zeros for a row outside [0, nk)
+int alpha_gather(const float* hist, const int* rows, int captions, int nk, int max_steps, int P, float* alphas, hipStream_t s);
 
 // lstm_persist.hip: a run of teacher-forced steps [t0, t1) in one launch (H = 512, b <= 128)
 bool lstm_persist_supported(int b, int H);

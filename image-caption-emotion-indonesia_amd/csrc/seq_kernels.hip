@@ -703,6 +703,70 @@ __global__ __launch_bounds__(64) void beam_finish_kernel(const void* beam, int n
   }
 }
 
+// one wave per image: ALL of its completed hypotheses, best first (capnet_beam_nbest). The key is done_score itself at
+// length_penalty 0 -- no division, no powf: rank 0 is then beam_finish's winner bit for bit -- else done_score /
+// (done_len - 1)^length_penalty (done_len - 1: the generated words, <end> included). At most 16 hypotheses: a thread per
+// hypothesis, its rank the number that beat it (beam_advance_topk_kernel's way), ties to the earlier completion. The
+// state is only read. A completed count outside [0, k] is clamped, a recorded slot outside [0, k) gives -1: nothing read
+// from the state is an address unchecked.
+__global__ __launch_bounds__(64) void beam_nbest_kernel(const void* beam, int n, int k, int max_steps, float length_penalty,
+                                                        long long* __restrict__ seqs, int* __restrict__ lengths,
+                                                        float* __restrict__ scores, int* __restrict__ counts,
+                                                        const void* trace, int* __restrict__ rows) {
+  __shared__ float s_key[kBeamMax];
+  __shared__ int s_src[kBeamMax];   // rank -> index in the completed list
+  const BeamState s = beam_state_of(const_cast<void*>(beam), n, k, max_steps);
+  const int i = blockIdx.x, tid = threadIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const int done = min(max(s.n_done[i], 0), k);
+  float key = 0.f;
+  if (tid < done) {
+    key = s.done_score[row0 + tid];
+    if (length_penalty != 0.f) key = key / powf((float)(s.done_len[row0 + tid] - 1), length_penalty);
+    s_key[tid] = key;
+  }
+  if (tid < kBeamMax) s_src[tid] = tid;   // (a NaN key counts nothing: every rank still names a completed hypothesis)
+  __syncthreads();
+  int rank = 0;
+  if (tid < done) {
+    for (int q = 0; q < done; ++q) {
+      const float ok = s_key[q];
+      rank += (ok > key || (ok == key && q < tid)) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  if (tid < done) s_src[rank] = tid;
+  __syncthreads();
+  for (int t = tid; t < k * L; t += 64) {
+    const int r = t / L, e = t % L;
+    long long w = 0;
+    if (r < done) {
+      const long q = row0 + s_src[r];
+      if (e < s.done_len[q]) w = s.done_seq[q * L + e];
+    }
+    seqs[row0 * L + t] = w;
+  }
+  if (tid < k) {
+    const bool has = tid < done;
+    const long q = row0 + (has ? s_src[tid] : 0);
+    lengths[row0 + tid] = has ? s.done_len[q] : 0;
+    scores[row0 + tid] = has ? s.done_score[q] : 0.f;
+  }
+  if (tid == 0) counts[i] = done;
+  if (rows) {   // beam_finish_kernel's rule per hypothesis: i k + slot; -1 past its last word and for a slot out of range
+    const int* done_rows = beam_trace_of(const_cast<void*>(trace), n, k, max_steps).done_rows;
+    for (int t = tid; t < k * max_steps; t += 64) {
+      const int r = t / max_steps, e = t % max_steps;
+      int slot = -1;
+      if (r < done) {
+        const long q = row0 + s_src[r];
+        if (e + 1 < s.done_len[q]) slot = done_rows[q * L + e + 1];
+      }
+      rows[row0 * max_steps + t] = slot >= 0 && slot < k ? (int)row0 + slot : -1;
+    }
+  }
+}
+
 static int beam_check(const char* what, const void* beam, int n, int k, int max_steps) {
   CAPNET_REQUIRE(beam != nullptr, "%s: null beam state", what);
   CAPNET_REQUIRE(n >= 1 && k >= 1 && k <= kBeamMax && max_steps >= 1 && (long)n * k * (max_steps + 2) < (1L << 28),
@@ -762,6 +826,21 @@ int beam_finish(const void* beam, int n, int k, int max_steps, long long end_tok
   CAPNET_REQUIRE(!trace == !rows, "beam_finish: the trace and the rows go together");
   hipLaunchKernelGGL(beam_finish_kernel, dim3(n), dim3(64), 0, stream, beam, n, k, max_steps, end_token, seqs, lengths, trace,
                      rows);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
+               float* scores, int* counts, hipStream_t stream, const void* trace, int* rows) {
+  if (int rc = beam_check("beam_nbest", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(seqs && lengths && scores && counts, "beam_nbest: null argument");
+  CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0 && (size_t)scores % 4 == 0 &&
+                     (size_t)counts % 4 == 0,
+                 "beam_nbest: the state, lengths, scores and counts must be 4-byte aligned, seqs 8-byte aligned");
+  CAPNET_REQUIRE(std::isfinite(length_penalty), "beam_nbest: length_penalty must be finite");
+  CAPNET_REQUIRE(!trace == !rows, "beam_nbest: the trace and the rows go together");
+  hipLaunchKernelGGL(beam_nbest_kernel, dim3(n), dim3(64), 0, stream, beam, n, k, max_steps, length_penalty, seqs, lengths,
+                     scores, counts, trace, rows);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

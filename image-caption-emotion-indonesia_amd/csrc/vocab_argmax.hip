@@ -462,4 +462,35 @@ size_t att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, in
          gd_align((size_t)max_steps * nq * k * P * sizeof(float));
 }
 
+// ---- what the searches leave in the caller's workspace (capnet_beam_nbest after the search returns) ----
+size_t beam_decode_ws_beam_offset(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, int groups) {
+  if (!lstm_beam_decode_groups_ws_bytes(nlayers, groups, n, k, H, V, max_steps, fused_topk)) return 0;
+  return beam_decode_layout(nlayers, groups * n, k, H, V, max_steps, fused_topk != 0, groups).beam;
+}
+
+size_t att_beam_decode_alphas_ws_trace_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps) {
+  if (!att_beam_decode_alphas_ws_bytes(nlayers, groups, n, k, P, A, C, E, H, V, max_steps)) return 0;
+  return att_beam_decode_ws_bytes(nlayers, groups * n, k, P, A, C, E, H, V, max_steps);
+}
+
+size_t att_beam_decode_alphas_ws_hist_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
+                                             int max_steps) {
+  const size_t trace = att_beam_decode_alphas_ws_trace_offset(nlayers, groups, n, k, P, A, C, E, H, V, max_steps);
+  if (!trace) return 0;
+  const int nq = groups * n;
+  return trace + gd_align(beam_trace_bytes(nq, k, max_steps)) + gd_align((size_t)nq * max_steps * sizeof(int));
+}
+
+int alpha_gather(const float* hist, const int* rows, int captions, int nk, int max_steps, int P, float* alphas, hipStream_t s) {
+  CAPNET_REQUIRE(hist && rows && alphas, "alpha_gather: null argument");
+  CAPNET_REQUIRE((size_t)hist % 4 == 0 && (size_t)rows % 4 == 0 && (size_t)alphas % 4 == 0,
+                 "alpha_gather: hist, rows and alphas must be 4-byte aligned");
+  CAPNET_REQUIRE(captions >= 1 && nk >= 1 && max_steps >= 1 && max_steps <= 65535 && P >= 1,
+                 "alpha_gather: captions=%d nk=%d max_steps=%d P=%d (all >= 1, max_steps <= 65535)", captions, nk, max_steps, P);
+  hipLaunchKernelGGL(alpha_gather_kernel, dim3(captions, max_steps), dim3(256), 0, s, hist, rows, nk, max_steps, P, alphas);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
 }  // namespace capnet

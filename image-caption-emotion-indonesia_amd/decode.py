@@ -89,16 +89,21 @@ def att_stack(step_fn, dec, cell, pack, attention, embed, project, maps, k, entr
 ALPHA_TRACE_MAX_BYTES = 256 << 20     # the one-call search's map history (steps x rows x P floats): a cap on memory
 
 
-def replay_alphas(step_fn, state, seqs, n, k):
+def replay_alphas(step_fn, state, seqs, n, k, images=None):
     """The attention maps of decoded captions by replay -> a list of float32 [len - 1, P] tensors, row e - 1 the softmax
     over the pixels that preceded word e: the token lists `seqs` (one list, n None; else n lists) are fed back through
     step_fn (att_beam_step's, which keeps the maps of its last step in .alpha) from the initial beam `state` of the search,
     one row per caption -- the first of each image's k. All captions of a batch advance together; a finished one
-    repeats its last token and its maps are no longer kept. A caption [<end>] alone (nothing completed) has [0, P]."""
+    repeats its last token and its maps are no longer kept. A caption [<end>] alone (nothing completed) has [0, P].
+    images: the image of every caption of `seqs`, for several captions per image (an n-best list); no caption, no maps."""
     with torch.no_grad():
         dev = state[0].device
-        lists = [list(seqs)] if n is None else [list(q) for q in seqs]
+        lists = [list(seqs)] if n is None and images is None else [list(q) for q in seqs]
+        if not lists:
+            return []
         first = torch.arange(len(lists), device=dev) * k
+        if images is not None:
+            first = torch.tensor(images, dtype=torch.long, device=dev) * k
         state = tuple(t.index_select(0, first).contiguous() for t in state)
         steps = [len(q) - 1 for q in lists]
         maps = [[] for _ in lists]
@@ -112,15 +117,15 @@ def replay_alphas(step_fn, state, seqs, n, k):
         return [torch.stack(m) if m else torch.zeros((0, P), dtype=torch.float32, device=dev) for m in maps]
 
 
-def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas):
+def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, nbest=False, length_penalty=0.0):
     """ops.att_beam_decode on an AttStack; with the maps, the images in as few chunks as keep the history [steps, rows, P]
-    under ALPHA_TRACE_MAX_BYTES."""
+    under ALPHA_TRACE_MAX_BYTES. nbest: every chunk's n-best lists (and maps per hypothesis), image by image as without it."""
     T, P = dec.max_seq_length + 1, att.feat.shape[1]
 
     def call(a1, ft, st):
         return ops.att_beam_decode(att.cell, a1, ft, att.emb, att.wz, att.bz, att.full_att.weight, att.full_att.bias, att.wcat,
                                    att.beff, att.Cw, att.Cb, st, k, T, start_token, end_token, poll_every,
-                                   return_alphas=return_alphas)
+                                   return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty)
     per = max(1, ALPHA_TRACE_MAX_BYTES // (T * k * P * 4)) if return_alphas else n_img
     if per >= n_img:
         return call(att.att1, att.feat, att.state)
@@ -133,8 +138,21 @@ def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return
     return seqs, maps
 
 
+def _nbest_replay(step_fn, state, lists, k):
+    """replay_alphas of every hypothesis of the n-best `lists` (per image, (tokens, score) pairs) -> per image, the list of
+    its hypotheses' maps."""
+    images = [i for i, hyps in enumerate(lists) for _ in hyps]
+    flat = iter(replay_alphas(step_fn, state, [q for hyps in lists for q, _ in hyps], None, k, images))
+    return [[next(flat) for _ in hyps] for hyps in lists]
+
+
+def _one_image(lists, dev):
+    """An n-best list of token lists as sample() returns it: LongTensor [1, L] per entry."""
+    return [(torch.tensor([q], dtype=torch.long, device=dev), sc) for q, sc in lists]
+
+
 def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False,
-                return_alphas=False):
+                return_alphas=False, nbest=False, length_penalty=0.0):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
@@ -146,8 +164,19 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     return_alphas (attention decoders: step_fn is att_beam_step's): the result is followed by the attention maps, float32
     [len - 1, P] per caption on the decoder's device (n None: one tensor), row e - 1 the map that preceded word e. The
     one-call search records them as it goes; every other route decodes as it does without the keyword and gets them from
-    replay_alphas. The tokens are those of the call without the keyword."""
+    replay_alphas. The tokens are those of the call without the keyword.
+    nbest: where a call without it returns one token list (one tensor), it returns the list of (tokens, score) pairs of
+    every completed hypothesis, best first by score / (len - 1)^length_penalty (len - 1: the generated words, <end>
+    included; score: the summed log-probability, a float), ties to the earlier completion; an empty list where nothing
+    completed. Entry 0 at length_penalty 0 is the caption the call without the keyword returns. The search is unchanged:
+    the host loops rank the completed lists they hold (capnet.beam.rank_completed), the device routes read theirs with
+    capnet_beam_nbest. With return_alphas every hypothesis has its own maps, in the same nesting. length_penalty without
+    nbest raises CapnetError."""
+    length_penalty = ops.check_length_penalty("beam search", nbest, length_penalty)
     dev = state[0].device
+    if nbest:
+        return _beam_nbest(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas,
+                           length_penalty)
     if return_alphas:
         att = getattr(step_fn, "att", None) if one_call else None
         if att is not None:
@@ -178,6 +207,38 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
         if n is None:
             return beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
         return beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
+
+
+def _beam_nbest(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas,
+                length_penalty):
+    """beam_decode(nbest=True): the routes of beam_decode, each giving its n-best lists."""
+    dev, n_img, T = state[0].device, 1 if n is None else n, dec.max_seq_length + 1
+    nb = dict(nbest=True, length_penalty=length_penalty)
+    maps = None
+    with torch.no_grad():
+        plain = getattr(step_fn, "plain", None) if one_call else None
+        att = getattr(step_fn, "att", None) if one_call else None
+        if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, dec.vocab_size,
+                                                           len(plain.wcat)):
+            lists = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T, start_token,
+                                    end_token, poll_every, **nb)
+        elif att is not None:
+            lists = _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, **nb)
+            if return_alphas:
+                lists, maps = lists
+        elif on_device or one_call:
+            lists = beam_search_device(step_fn, state, n_img, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev,
+                                       poll_every, **nb)
+        elif n is None:
+            lists = [[(q[0].tolist(), sc) for q, sc in
+                      beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev, **nb)]]
+        else:
+            lists = beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev, **nb)
+    if return_alphas and maps is None:
+        maps = _nbest_replay(step_fn, state, lists, k)
+    if n is None:
+        lists, maps = _one_image(lists[0], dev), None if maps is None else maps[0]
+    return (lists, maps) if return_alphas else lists
 
 
 def zero_state(rows, H, device):
@@ -350,12 +411,15 @@ def styles_images(n, G, k, width, device):
     return min(n, ops.splitk_slab(device).numel() // (G * k * width))
 
 
-def plain_styles(dec, layer_mods, num_layers, emb, C, n, k, start_token, end_token, modes, poll_every, loop):
+def plain_styles(dec, layer_mods, num_layers, emb, C, n, k, start_token, end_token, modes, poll_every, loop, nbest=False,
+                 length_penalty=0.0):
     """sample_styles of a plain factored decoder -> {mode: [n token lists]}: every mode's chain folded into one buffer per
     layer (fold_styles) and ONE ops.beam_decode(groups=len(modes)) over modes x images x k rows (the images in as few
     chunks as the slab allows). loop(mode) -> sample_batch(mode=mode, one_call=True): taken mode by mode where the fused
-    step does not serve the shape, CAPNET_NO_FUSED_DECODE_STEP=1 is set, or one mode is asked for."""
+    step does not serve the shape, CAPNET_NO_FUSED_DECODE_STEP=1 is set, or one mode is asked for. nbest / length_penalty:
+    beam_decode's, per mode and image (loop(mode) passes them on itself)."""
     G, V, E = len(modes), dec.vocab_size, emb.shape[1]
+    length_penalty = ops.check_length_penalty("sample_styles", nbest, length_penalty)
     with torch.no_grad():
         per = styles_images(n, G, k, V, emb.device) if G > 1 else 0
         if per < 1 or not fused_decode_step(num_layers, E, dec.hidden_size) or \
@@ -367,20 +431,23 @@ def plain_styles(dec, layer_mods, num_layers, emb, C, n, k, start_token, end_tok
         for i0 in range(0, n, per):
             ni = min(per, n - i0)
             seqs = ops.beam_decode(ops.CELL_FACTORED, wcat, beff, emb.detach(), C.weight, C.bias, ni, k, dec.max_seq_length + 1,
-                                   start_token, end_token, poll_every, groups=G)
+                                   start_token, end_token, poll_every, groups=G, nbest=nbest, length_penalty=length_penalty)
             for g, m in enumerate(modes):
                 out[m] += seqs[g * ni:(g + 1) * ni]
     return out
 
 
-def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token, modes, poll_every, loop, return_alphas=False):
+def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token, modes, poll_every, loop, return_alphas=False,
+               nbest=False, length_penalty=0.0):
     """sample_styles of an attention decoder -> {mode: [n token lists]}: ONE ops.att_beam_decode(groups=len(modes)) over
     modes x images x k rows. Per mode: its folded chain (fold_styles), its Attention module's encoder_att(feat) (att1
     [G n, P, A]), [decoder_att; f_beta] and full_att; shared: the map feat [n, P, C], the embedding, the projection and
     the initial state (init_h / init_c of every layer), repeated per mode. loop(mode) as plain_styles'.
     return_alphas: -> ({mode: lists}, {mode: [n float32 [len - 1, P] tensors]}), the maps of every mode's own Attention
     module recorded by the grouped search (loop(mode) then returns (lists, tensors)); the images in chunks that also keep
-    the map history under ALPHA_TRACE_MAX_BYTES."""
+    the map history under ALPHA_TRACE_MAX_BYTES. nbest / length_penalty: beam_decode's, per mode and image, the maps per
+    hypothesis (loop(mode) passes them on itself)."""
+    length_penalty = ops.check_length_penalty("sample_styles", nbest, length_penalty)
     G, n, Cdim = len(modes), features.size(0), features.size(-1)
     E, A, V = dec.B.weight.shape[1], dec.attention_size, dec.vocab_size
     with torch.no_grad():
@@ -413,7 +480,7 @@ def att_styles(dec, layer_mods, num_layers, features, k, start_token, end_token,
             state = torch.cat([t.unsqueeze(1) for t in entries], 1).repeat(G, 1, 1).contiguous()
             seqs = ops.att_beam_decode(ops.CELL_FACTORED, att1, fi, dec.B.weight, wz, bz, wf, bf, wcat, beff, dec.C.weight,
                                        dec.C.bias, state, k, dec.max_seq_length + 1, start_token, end_token, poll_every, groups=G,
-                                       return_alphas=return_alphas)
+                                       return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty)
             if return_alphas:
                 seqs, alphas = seqs
             for g, m in enumerate(modes):

@@ -643,21 +643,25 @@ class DecoderFactoredLSTM(nn.Module):
         return step_fn, zero_state(rows, self.hidden_size, self.B.weight.device)
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
-               one_call=False):
+               one_call=False, nbest=False, length_penalty=0.0):
         """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
         an input of the decode steps (the first input is B(<start>) and the state starts at zero):
         `features` only fixes the device. Returns LongTensor [1, L].
         on_device / poll_every / one_call: capnet.decode.beam_decode's (the bookkeeping on the device; the whole search
-        in one C call, on the folded chain; same sequences)."""
-        return beam_decode(self, *self._beam(k, mode, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
+        in one C call, on the folded chain; same sequences).
+        nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
+        first, in place of the one caption."""
+        return beam_decode(self, *self._beam(k, mode, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
+                           nbest=nbest, length_penalty=length_penalty)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0, one_call=False):
+                     poll_every=0, one_call=False, nbest=False, length_penalty=0.0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched): what the reference's test-set
         evaluator does image by image (stylenet/evaluator.py:76-84). Returns a list of token lists, each equal to
         sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(n * k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
+                           nbest=nbest, length_penalty=length_penalty)
 
     def sample_styles(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0):
         """sample_batch(one_call=True) in every style of `modes` at once -> {mode: [n token lists]}, each list equal to
@@ -671,3 +675,14 @@ class DecoderFactoredLSTM(nn.Module):
                             start_token, end_token, modes, poll_every,
                             lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
                                                         poll_every=poll_every))
+
+    def sample_styles_nbest(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0, length_penalty=0.0):
+        """sample_styles with nbest=True -> {mode: [n lists of (tokens, score)]}, each equal to sample_batch(mode=mode,
+        one_call=True, nbest=True, length_penalty=length_penalty): the one grouped search, its completed lists read by
+        capnet_beam_nbest. (A method of its own: sample_styles' parameters are pinned.)"""
+        modes = check_styles(modes, self._S)
+        return plain_styles(self, lambda l, m: _layer_mods(self, "", m), 1, self.B.weight, self.C, features.size(0), k,
+                            start_token, end_token, modes, poll_every,
+                            lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
+                                                        poll_every=poll_every, nbest=True, length_penalty=length_penalty),
+                            nbest=True, length_penalty=length_penalty)

@@ -207,26 +207,28 @@ class DecoderFactoredLSTMAtt(nn.Module):
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
-               one_call=False, return_alphas=False):
+               one_call=False, return_alphas=False, nbest=False, length_penalty=0.0):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
         of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
         one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps,
         the chain folded); on_device=True for a shape that call does not take. Same sequences.
         return_alphas: -> (ids [1, L], alphas float32 [L - 1, P]), row e - 1 the map of the mode's Attention module that
-        preceded word e (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route)."""
+        preceded word e (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route).
+        nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
+        first, in place of the one caption. With return_alphas, every hypothesis's own maps beside the list."""
         return beam_decode(self, *self._beam(features, None, k, mode, one_call), None, k, start_token, end_token, on_device, poll_every,
-                           one_call, return_alphas)
+                           one_call, return_alphas, nbest, length_penalty)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0, one_call=False, return_alphas=False):
+                     poll_every=0, one_call=False, return_alphas=False, nbest=False, length_penalty=0.0):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once: the reference's evaluator
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
         images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists; with
         return_alphas, (the n token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas)
+                           return_alphas, nbest, length_penalty)
 
     def _style_layers(self):
         """The layers sample_styles folds: one here (capnet.stacked_att: num_layers)."""
@@ -250,13 +252,22 @@ class DecoderFactoredLSTMAtt(nn.Module):
         caption looked next to where the angry one did. (A method of its own: sample_styles' parameters are pinned.)"""
         return self._styles(features, start_token, end_token, k, modes, poll_every, True)
 
-    def _styles(self, features, start_token, end_token, k, modes, poll_every, return_alphas):
+    def sample_styles_nbest(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0, length_penalty=0.0,
+                            return_alphas=False):
+        """sample_styles with nbest=True -> {mode: [n lists of (tokens, score)]}, each equal to sample_batch(mode=mode,
+        one_call=True, nbest=True, length_penalty=length_penalty); with return_alphas, followed by {mode: [n lists of float32
+        [len - 1, P] tensors]}, every hypothesis's own maps. The one grouped search, its completed lists read by
+        capnet_beam_nbest. (A method of its own: sample_styles' parameters are pinned.)"""
+        return self._styles(features, start_token, end_token, k, modes, poll_every, return_alphas, True, length_penalty)
+
+    def _styles(self, features, start_token, end_token, k, modes, poll_every, return_alphas, nbest=False, length_penalty=0.0):
         modes = decode.check_styles(modes, self._mode_modules)
         return decode.att_styles(self, lambda l, m: _layer_mods(self, "" if l == 0 else str(l), m), self._style_layers(),
                                  features, k, start_token, end_token, modes, poll_every,
                                  lambda m: self.sample_batch(features, start_token, end_token, k=k, mode=m, one_call=True,
-                                                             poll_every=poll_every, return_alphas=return_alphas),
-                                 return_alphas)
+                                                             poll_every=poll_every, return_alphas=return_alphas, nbest=nbest,
+                                                             length_penalty=length_penalty),
+                                 return_alphas, nbest, length_penalty)
 
     def forward(self,
                 captions,

@@ -96,14 +96,20 @@ class DecoderRNN(nn.Module):
             plain_stack(step_fn, [pack_cell(self.lstm, input_width(self.embed_size))], ops.CELL_LSTM, self.embed.weight, self.linear)
         return step_fn, zero_state(rows, self.hidden_size, self.embed.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, nbest=False,
+               length_penalty=0.0):
         """Beam search, nic/model.py:117-207 (the image features are not an input of the decode
         steps there either). Returns LongTensor [1, L].
         on_device / poll_every / one_call: capnet.decode.beam_decode's (the bookkeeping on the device; the whole search
-        in one C call; same sequences)."""
-        return beam_decode(self, *self._beam(k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call)
+        in one C call; same sequences).
+        nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
+        first, in place of the one caption."""
+        return beam_decode(self, *self._beam(k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
+                           nbest=nbest, length_penalty=length_penalty)
 
-    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False):
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, nbest=False,
+                     length_penalty=0.0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched)."""
         n = features.size(0)
-        return beam_decode(self, *self._beam(n * k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call)
+        return beam_decode(self, *self._beam(n * k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
+                           nbest=nbest, length_penalty=length_penalty)

@@ -113,21 +113,24 @@ class DecoderRNNAtt(nn.Module):
                              self.attention, self.embed, self.linear, maps, k, (h0, c0) + state)
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, return_alphas=False):
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, return_alphas=False,
+               nbest=False, length_penalty=0.0):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
         one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps);
         on_device=True for a shape that call does not take. Same sequences.
         return_alphas: -> (ids [1, L], alphas float32 [L - 1, P]), row e - 1 the attention map that preceded word e
-        (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route)."""
+        (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route).
+        nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
+        first, in place of the one caption. With return_alphas, every hypothesis's own maps beside the list."""
         return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas)
+                           return_alphas, nbest, length_penalty)
 
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False,
-                     return_alphas=False):
+                     return_alphas=False, nbest=False, length_penalty=0.0):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).
         Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist(); with return_alphas, (the n
         token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(features, n, k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas)
+                           return_alphas, nbest, length_penalty)

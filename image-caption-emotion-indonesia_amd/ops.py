@@ -336,6 +336,100 @@ def beam_finish_traced(beam, trace, end_token):
     return seqs, lengths, rows
 
 
+def _nbest_alloc(n, k, L, device, flag=False):
+    """The outputs of capnet_beam_nbest as views of ONE int64 buffer, so that a caller takes all of them to the host in one
+    copy: seqs int64 [n, k, L] | lengths int32 [n, k] | scores float32 [n, k] | counts int32 [n] | with `flag`, one more
+    int32 for the device's error word -> (packed, seqs, lengths, scores, counts, the error word's view or None)."""
+    nk = n * k
+    packed = torch.empty(nk * L + (2 * nk + n + 2) // 2, dtype=torch.int64, device=device)
+    tail = packed[nk * L:].view(torch.int32)
+    return (packed, packed[:nk * L].view(n, k, L), tail[:nk].view(n, k), tail[nk:2 * nk].view(torch.float32).view(n, k),
+            tail[2 * nk:2 * nk + n], tail[2 * nk + n:2 * nk + n + 1] if flag else None)
+
+
+def nbest_lists(packed, n, k, L):
+    """_nbest_alloc's buffer in one copy to the host -> (per image the list of (tokens, score), best first; the lengths
+    [n][k]; the int32 words behind counts, on the host)."""
+    host = packed.cpu()
+    nk = n * k
+    tail = host[nk * L:].view(torch.int32)
+    lens = tail[:nk].view(n, k).tolist()
+    scores = tail[nk:2 * nk].view(torch.float32).view(n, k).tolist()
+    counts = tail[2 * nk:2 * nk + n].tolist()
+    rows = host[:nk * L].view(n, k, L).tolist()
+    return [[(rows[i][r][:lens[i][r]], scores[i][r]) for r in range(counts[i])] for i in range(n)], lens, tail[2 * nk + n:]
+
+
+def check_length_penalty(who, nbest, length_penalty):
+    length_penalty = float(length_penalty)
+    if length_penalty != 0.0 and not nbest:
+        raise CapnetError("%s: length_penalty=%r needs nbest=True (the call without it returns the reference's winner)"
+                          % (who, length_penalty))
+    if length_penalty != length_penalty or length_penalty in (float("inf"), float("-inf")):
+        raise CapnetError("%s: length_penalty must be finite" % who)
+    return length_penalty
+
+
+def beam_nbest(beam, end_token, length_penalty=0.0):
+    """capnet_beam_nbest -> (seqs int64 [n, k, max_steps + 2], lengths int32 [n, k], scores float32 [n, k], counts int32 [n],
+    packed): every completed hypothesis of every image, best first by score / (length - 1)^length_penalty (0: by the score
+    itself; entry 0 is then beam_finish's winner), ties to the earlier completion; zeros past counts[i]. The four are views
+    of the one int64 buffer `packed`. end_token is beam_finish's argument and fills nothing here: an image that completed
+    nothing has count 0. The state is only read."""
+    n, L = beam.n, beam.max_steps + 2
+    packed, seqs, lengths, scores, counts, _ = _nbest_alloc(n, beam.k, L, beam.words.device)
+    check(_lib.lib().capnet_beam_nbest(ptr(beam.words), n, beam.k, beam.max_steps, check_length_penalty("beam_nbest", True, length_penalty),
+                                       ptr(seqs), ptr(lengths), ptr(scores), ptr(counts), current_stream()), "capnet_beam_nbest")
+    return seqs, lengths, scores, counts, packed
+
+
+def beam_nbest_traced(beam, trace, end_token, length_penalty=0.0):
+    """capnet_beam_nbest_traced -> (seqs, lengths, scores, counts, rows int32 [n, k, max_steps]): beam_nbest, and per
+    hypothesis beam_finish_traced's rows."""
+    _check_trace("beam_nbest_traced", beam, trace)
+    n, L = beam.n, beam.max_steps + 2
+    _, seqs, lengths, scores, counts, _ = _nbest_alloc(n, beam.k, L, beam.words.device)
+    rows = torch.empty((n, beam.k, beam.max_steps), dtype=torch.int32, device=beam.words.device)
+    check(_lib.lib().capnet_beam_nbest_traced(ptr(beam.words), ptr(trace), n, beam.k, beam.max_steps,
+                                              check_length_penalty("beam_nbest_traced", True, length_penalty), ptr(seqs), ptr(lengths),
+                                              ptr(scores), ptr(counts), ptr(rows), current_stream()), "capnet_beam_nbest_traced")
+    return seqs, lengths, scores, counts, rows
+
+
+def _nbest_of_workspace(ws, beam_offset, n, k, max_steps, length_penalty, flag, maps=None):
+    """The n-best of a one-call search out of its workspace (capnet_beam_nbest on ws + beam_offset, a second, tiny call after
+    the search returned) -> per image the list of (tokens, score), best first. Sequences, lengths, scores, counts and the
+    error word `flag` come to the host in one copy; a set error word raises.
+    maps = (trace offset, history offset, P): the search recorded its attention maps -- capnet_beam_nbest_traced and ONE
+    capnet_alpha_gather over all n k hypotheses; the result is followed by, per image, its hypotheses' float32 [len - 1, P]
+    tensors (on the device)."""
+    if not beam_offset or (maps is not None and not (maps[0] and maps[1])):
+        raise CapnetError("n-best: no beam state in this workspace (n=%d k=%d max_steps=%d)" % (n, k, max_steps))
+    L, T, dev = _lib.lib(), max_steps, ws.device
+    packed, seqs, lengths, scores, counts, err = _nbest_alloc(n, k, T + 2, dev, flag=True)
+    base = ws.data_ptr()
+    beam = C.c_void_p(base + beam_offset)
+    alphas = None
+    if maps is None:
+        check(L.capnet_beam_nbest(beam, n, k, T, length_penalty, ptr(seqs), ptr(lengths), ptr(scores), ptr(counts),
+                                  current_stream()), "capnet_beam_nbest")
+    else:
+        trace_offset, hist_offset, P = maps
+        rows = torch.empty((n, k, T), dtype=torch.int32, device=dev)
+        check(L.capnet_beam_nbest_traced(beam, C.c_void_p(base + trace_offset), n, k, T, length_penalty, ptr(seqs), ptr(lengths),
+                                         ptr(scores), ptr(counts), ptr(rows), current_stream()), "capnet_beam_nbest_traced")
+        alphas = torch.empty((n * k, T, P), dtype=torch.float32, device=dev)
+        check(L.capnet_alpha_gather(C.c_void_p(base + hist_offset), ptr(rows), n * k, n * k, T, P, ptr(alphas), current_stream()),
+              "capnet_alpha_gather")
+    err.copy_(flag)
+    out, lens, word = nbest_lists(packed, n, k, T + 2)
+    if int(word[0]):
+        check_device_errors()
+    if alphas is None:
+        return out
+    return out, [[alphas[i * k + r, :lens[i][r] - 1] for r in range(len(out[i]))] for i in range(n)]
+
+
 def attention_step(att1, feat, z, A, w_full, b_full, xa=None, xa_col=0):
     """One attention step for s rows (no autograd; Attention.forward / sample()).
     att1 [s, P, A] = encoder_att(features); feat [s, P, C]; z [s, A + C] = [decoder_att(h) |
@@ -822,7 +916,7 @@ def beam_decode_supported(E, H, k, V, num_layers):
 
 
 def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, poll_every=0, state=None,
-                return_steps=False, groups=1):
+                return_steps=False, groups=1, nbest=False, length_penalty=0.0):
     """The beam search of a plain stack in ONE C call (capnet_beam_decode): n images x k beams, at most max_steps steps of
     (gathered decode step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then capnet_beam_finish.
     cell / wcat / beff: as stacked_decode_step; emb [V, E]; Cw [V, H], Cb [V] or None; state: [n k, 2L, H] or None for
@@ -831,9 +925,13 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     groups > 1 (capnet_beam_decode_groups): the searches of `groups` weight groups over the n images in the same launches,
     wcat[l] [groups, 4H, kin_l + H], beff[l] [groups, 4H]; state [groups n k, 2L, H]; groups n token lists come back,
     group-major (list g n + i: group g, image i).
+    nbest: instead of its winner, every image gives the list of its completed hypotheses as (tokens, score) pairs, best
+    first by score / (len(tokens) - 1)^length_penalty (_nbest_of_workspace: capnet_beam_nbest on the state the search left in
+    the workspace); the list is empty where nothing completed. The search itself is the same.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("beam_decode: unknown cell %r" % (cell,))
+    length_penalty = check_length_penalty("beam_decode", nbest, length_penalty)
     groups = _check_groups("beam_decode", groups)
     _need_cuda(emb, Cw, Cb, state, *wcat, *beff)
     emb, Cw = _c(emb.detach()), _c(Cw.detach())
@@ -874,6 +972,10 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     else:
         check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode")
+    if nbest:
+        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n_img, k, H, V, T, 0, groups), n, k, T,
+                                  length_penalty, flag)
+        return (out, steps.value) if return_steps else out
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)
@@ -892,16 +994,18 @@ def lstm_beam_decode_supported(E, H, k, V, num_layers):
 
 
 def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, first_inputs=None, state=None,
-                     fused_topk=True, poll_every=0, return_steps=False):
+                     fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0):
     """The beam search of a stack from a given state in ONE C call (capnet_lstm_beam_decode): n sentences x k beams, at most
     max_steps steps, then capnet_beam_finish. fused_topk: a step is (gathered decode step, capnet_vocab_topk,
     capnet_beam_advance_topk) -- no logits in memory; else beam_decode's step (the projection on sgemm_splitk's slab,
     capnet_beam_advance) in the same call. first_inputs [n k, E]: step 1 feeds these rows to layer 0 instead of
     emb[start_token] (EncoderRNN's feature column). state: [n k, 2L, H] or None for zeros. Everything else as beam_decode:
     the workspace is cached per (device, shape); sequences, lengths and the error word come to the host in one copy.
+    nbest / length_penalty: as beam_decode's, on either top-k route.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("lstm_beam_decode: unknown cell %r" % (cell,))
+    length_penalty = check_length_penalty("lstm_beam_decode", nbest, length_penalty)
     _need_cuda(emb, Cw, Cb, state, first_inputs, *wcat, *beff)
     emb, Cw = _c(emb.detach()), _c(Cw.detach())
     Cb = None if Cb is None else _c(Cb.detach())
@@ -944,6 +1048,10 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
                                     0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
                                     C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
           "capnet_lstm_beam_decode")
+    if nbest:
+        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, fused, 1), n, k, T, length_penalty,
+                                  flag)
+        return (out, steps.value) if return_steps else out
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)
@@ -956,7 +1064,7 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
 
 
 def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, start_token, end_token, state=None,
-                            fused_topk=True, poll_every=0, return_steps=False):
+                            fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0):
     """lstm_beam_decode of len(embs) decoders in ONE C call (capnet_lstm_beam_decode_groups): groups x n sentences x k beams,
     group-major, group g on embs[g] [V, E], wcat[l][g] / beff[l][g] and Cws[g] [V, H] / Cbs[g] [V] (Cbs or any Cbs[g] None:
     no bias). The embeddings and projections are used where they lie (one pointer per group; nothing is stacked or copied);
@@ -964,12 +1072,13 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
     as for lstm_greedy_decode_groups. Per step one gathered decode-step launch per layer on a (H / 4, groups) grid, then
     fused_topk: one capnet_vocab_topk_groups launch and one capnet_beam_advance_topk; else one sgemm_splitk per group into
     its row block of the logits and one capnet_beam_advance. There are no first_inputs. state: [groups n k, 2L, H] or None
-    for zeros. Everything else as lstm_beam_decode.
+    for zeros. Everything else as lstm_beam_decode, nbest / length_penalty included.
     Returns the groups n token lists, group-major (list g n + i: group g, sentence i); with return_steps, (lists, the steps
     issued)."""
     who = "lstm_beam_decode_groups"
     if cell not in (CELL_FACTORED, CELL_LSTM):
         raise CapnetError("%s: unknown cell %r" % (who, cell))
+    length_penalty = check_length_penalty(who, nbest, length_penalty)
     embs = _check_tables(who, embs, _first_shape(embs))
     groups = len(embs)
     Cws = list(Cws)
@@ -1019,6 +1128,10 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
                                            0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
                                            C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
           "capnet_lstm_beam_decode_groups")
+    if nbest:
+        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, fused, groups), nq, k, T,
+                                  length_penalty, flag)
+        return (out, steps.value) if return_steps else out
     tail[nq:nq + 1].copy_(flag)
     host = packed.cpu()
     htail = host[nq * SL:].view(torch.int32)
@@ -1117,7 +1230,8 @@ _att_beam_decode_alphas_ws = {}
 
 
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
-                    end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False):
+                    end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False, nbest=False,
+                    length_penalty=0.0):
     """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
     steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
     capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
@@ -1128,9 +1242,13 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     return_alphas (capnet_att_beam_decode_alphas): the search also records its attention maps -- every step's maps into a
     history, the winners' rows through the re-slotting, one gather at the end; the maps stay on the device. The token
     lists are those of the call without it.
+    nbest / length_penalty: as beam_decode's; with return_alphas every hypothesis has its own maps (capnet_beam_nbest_traced's
+    rows, one capnet_alpha_gather over all n k hypotheses): per image a list of float32 [len - 1, P] tensors beside its list
+    of (tokens, score) pairs.
     Returns the n token lists; with return_steps, (lists, the steps issued); with return_alphas the lists are followed by
     the list of n float32 [len - 1, P] tensors: row e - 1 is the map that preceded word e."""
     groups = _check_groups("att_beam_decode", groups)
+    length_penalty = check_length_penalty("att_beam_decode", nbest, length_penalty)
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
         "att_beam_decode", cell, att1, feat, k, emb, wz, bz, w_full, b_full, wcat, beff, state, groups)
     _need_cuda(Cw, Cb)
@@ -1168,6 +1286,15 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
         check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
     else:
         check(L.capnet_att_beam_decode(cell, nl, *args), "capnet_att_beam_decode")
+    if nbest:
+        dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
+        where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*dims), L.capnet_att_beam_decode_alphas_ws_hist_offset(*dims),
+                 P) if return_alphas else None
+        res = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, 0, 1), n, k, T, length_penalty, flag,
+                                  where)
+        res = res if return_alphas else (res,)
+        res = (res[0], steps.value) + res[1:] if return_steps else res
+        return res if len(res) > 1 else res[0]
     tail[n:n + 1].copy_(flag)
     host = packed.cpu()
     htail = host[n * SL:].view(torch.int32)

@@ -195,11 +195,13 @@ class _RNN(nn.Module):
             return torch.stack(ids, 1), state
 
 
-    def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk):
+    def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk, nbest=False, length_penalty=0.0):
         """Beam search of B = state.shape[0] sentences x k beams from `state` [B, 2L, H]; the first input is `features`
         [B, E] or, None, embed(start_token). max_seq_length + 1 steps at most. Returns B token lists, each starting with
-        start_token ([end_token] where nothing completed). Routing: the module's docstring."""
+        start_token ([end_token] where nothing completed). Routing: the module's docstring. nbest: per sentence the list of
+        (tokens, score) of its completed hypotheses, best first (capnet.decode.beam_decode's keyword), on every route."""
         E, H, V, L = self.embed_size, self.hidden_size, self.vocab_size, self.num_layers
+        length_penalty = ops.check_length_penalty("sample_beam", nbest, length_penalty)
         k = int(k)
         if not 1 <= k <= 16 or k > V:
             raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, V))
@@ -219,7 +221,7 @@ class _RNN(nn.Module):
                 packed = pack_cells(layers, E)
                 return ops.lstm_beam_decode(ops.CELL_LSTM, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb, B, k,
                                             self.max_seq_length + 1, start_token, end_token, first_inputs=first, state=state,
-                                            fused_topk=fused, poll_every=poll_every)
+                                            fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty)
             step = cell_stepper(layers, E, H)
             calls = [0]
 
@@ -231,7 +233,7 @@ class _RNN(nn.Module):
                     top, new = step(emb, prev_words, st[0])
                 return ops.linear(top, Cw, Cb), (new,)
             return beam_search_device(step_fn, (state,), B, V, start_token, end_token, k, self.max_seq_length,
-                                      emb.device, poll_every)
+                                      emb.device, poll_every, nbest=nbest, length_penalty=length_penalty)
 
     def _rows_state(self, states, rows, dev):
         h, c = states
@@ -262,14 +264,19 @@ class EncoderRNN(_RNN):
         ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
         return ids, _from_rows(state)
 
-    def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None):
+    def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None, nbest=False,
+                    length_penalty=0.0):
         """Beam search (k beams per sentence, max_seq_length + 1 steps at most, a beam completes at end_token) whose first
         input is `features` [B, E]: a list of B token lists. start_token only seeds the bookkeeping (no step reads its
         embedding), so it is dropped from every list that has more than one element; [end_token] where nothing completed.
         poll_every as capnet.beam.beam_search_device; fused_topk: None routes by FUSED_TOPK_MAX_ROWS, True / False force
-        the fused / unfused step (CAPNET_NO_FUSED_TOPK=1 forces False)."""
+        the fused / unfused step (CAPNET_NO_FUSED_TOPK=1 forces False). nbest / length_penalty: per sentence the list of
+        (tokens, score) of every completed hypothesis, best first, start_token dropped from each (the key still counts the
+        generated words: len(tokens) here); empty where nothing completed."""
         state = self._rows_state(states, features.size(0), features.device)
-        lists = self._beam_search(features, start_token, end_token, state, k, poll_every, fused_topk)
+        lists = self._beam_search(features, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty)
+        if nbest:
+            return [[(q[1:], sc) for q, sc in hyps] for hyps in lists]
         return [s[1:] if len(s) > 1 else s for s in lists]
 
 
@@ -296,16 +303,18 @@ class DecoderRNN(_RNN):
         ops.check_device_errors()
         return ids
 
-    def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None):
+    def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None, nbest=False, length_penalty=0.0):
         """Beam search from embed(start_token) and `states` (h, c) [num_layers, B, H]: a list of B token lists, one per
         column of `states`, each what oracle.beam_ref._beam returns for that sentence -- it begins with start_token, and is
         [end_token] where nothing completed. max_seq_length + 1 steps at most. poll_every / fused_topk: as
-        EncoderRNN.sample_beam. An out-of-range start_token raises CapnetError through the device error word."""
+        EncoderRNN.sample_beam. An out-of-range start_token raises CapnetError through the device error word.
+        nbest / length_penalty: per sentence the list of (tokens, score) of every completed hypothesis, best first by score /
+        (len(tokens) - 1)^length_penalty; empty where nothing completed."""
         h, c = states
         given = h if h is not None else c
         rows = 1 if given is None else given.size(1)
         state = self._rows_state(states, rows, self.embed.weight.device)
-        return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk)
+        return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty)
 
 
 class Seq2Seq(nn.Module):
@@ -347,15 +356,15 @@ class Seq2Seq(nn.Module):
         return decoder.sample(start_token, states)
 
     def sample_beam(self, features, start_token, end_token, states=(None, None), mode='factual', k=5, poll_every=0,
-                    fused_topk=None):
+                    fused_topk=None, nbest=False, length_penalty=0.0):
         """factual: the encoder's beam search (EncoderRNN.sample_beam). An emotion mode: the encoder's GREEDY sample for
         the state, as sample() does, then that decoder's beam search from it (DecoderRNN.sample_beam). A list of B token
-        lists."""
+        lists; nbest / length_penalty: of B n-best lists, as the two sample_beam."""
         decoder = None if mode == 'factual' else self._decoder(mode)
         if decoder is None:
-            return self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk)
+            return self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, nbest, length_penalty)
         _, states = self.encoder.sample(features, states)
-        return decoder.sample_beam(start_token, end_token, states, k, poll_every, fused_topk)
+        return decoder.sample_beam(start_token, end_token, states, k, poll_every, fused_topk, nbest, length_penalty)
 
     def _check_mode(self, mode):
         if mode != 'factual':
@@ -410,7 +419,8 @@ class Seq2Seq(nn.Module):
                 and ops.lstm_beam_decode_supported(d.embed_size, d.hidden_size, k, d.vocab_size, d.num_layers))
 
     def sample_beam_styles(self, features, start_token, end_token, states=(None, None),
-                           modes=('factual', 'happy', 'sad', 'angry'), k=5, poll_every=0, fused_topk=None):
+                           modes=('factual', 'happy', 'sad', 'angry'), k=5, poll_every=0, fused_topk=None, nbest=False,
+                           length_penalty=0.0):
         """{mode: [B token lists]} for every mode of `modes` (a non-empty sequence of distinct names), each entry equal to
         sample_beam(features, start_token, end_token, states, mode=mode, k=k). `factual` is the encoder's own sample_beam
         (its first input is `features`, it starts from `states`). The encoder's greedy sample runs once, and only if an
@@ -419,7 +429,9 @@ class Seq2Seq(nn.Module):
         on the rows per decoder (B k) by FUSED_TOPK_GROUPS_MAX_ROWS, True / False force the fused / unfused step
         (CAPNET_NO_FUSED_TOPK=1 forces False). One emotion, unequal decoder shapes, a shape the decode kernel does not take
         or CAPNET_NO_FUSED_DECODE_STEP=1: one DecoderRNN.sample_beam after the other on that one encoder run. An
-        out-of-range start_token raises CapnetError through the device error word."""
+        out-of-range start_token raises CapnetError through the device error word. nbest / length_penalty: {mode: [B n-best
+        lists]}, as sample_beam's, on the grouped call and on the loop."""
+        length_penalty = ops.check_length_penalty("sample_beam_styles", nbest, length_penalty)
         try:
             modes = check_styles(modes, self._check_mode)
         except ValueError as e:                    # an empty or repeated list: refused as every other bad argument here
@@ -428,7 +440,8 @@ class Seq2Seq(nn.Module):
         decoders = [self._decoder(m) for m in emotions]
         out = {}
         if 'factual' in modes:
-            out['factual'] = self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk)
+            out['factual'] = self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, nbest,
+                                                      length_penalty)
         if decoders:
             _, (h, c) = self.encoder.sample(features, states)
             B, k = h.size(1), int(k)
@@ -450,12 +463,13 @@ class Seq2Seq(nn.Module):
                     lists = ops.lstm_beam_decode_groups(
                         ops.CELL_LSTM, wcat, beff, [x.embed.weight.detach() for x in decoders],
                         [x.linear.weight.detach() for x in decoders], [x.linear.bias.detach() for x in decoders], B, k,
-                        d.max_seq_length + 1, start_token, end_token, state=state, fused_topk=fused, poll_every=poll_every)
+                        d.max_seq_length + 1, start_token, end_token, state=state, fused_topk=fused, poll_every=poll_every,
+                        nbest=nbest, length_penalty=length_penalty)
                 ops.check_device_errors()
                 for g, m in enumerate(emotions):
                     out[m] = lists[g * B:(g + 1) * B]
             else:
                 for m, x in zip(emotions, decoders):
-                    out[m] = x.sample_beam(start_token, end_token, (h, c), k, poll_every, fused_topk)
+                    out[m] = x.sample_beam(start_token, end_token, (h, c), k, poll_every, fused_topk, nbest, length_penalty)
                 ops.check_device_errors()
         return {m: out[m] for m in modes}

@@ -880,6 +880,46 @@ int capnet_att_beam_decode_alphas(int cell, int nlayers, int groups, int n, int 
                                   int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                                   capnet_stream_t stream, float* alphas);
 
+/* N-best: every completed hypothesis of every image, best first, read out of a beam state after its search (any search:
+ * the step-by-step calls above, or a one-call search through the offsets below). One launch, one wave per image; the
+ * state is only read, so capnet_beam_finish gives the same before and after.
+ *   key      done_score / (done_len - 1)^length_penalty; done_len - 1 is the number of generated words, <end> included.
+ *            length_penalty == 0: done_score itself, no division and no powf -- entry 0 is then capnet_beam_finish's winner
+ *            bit for bit. Ties go to the earlier completion. length_penalty must be finite.
+ *   seqs     int64 [n][k][max_steps + 2], zero past each length (8-byte aligned)
+ *   lengths  int32 [n][k]; scores f32 [n][k]: the raw summed log-probability whatever the penalty; counts int32 [n]: the
+ *            completed hypotheses of the image, <= k. Entries at and past counts[i] are zeros with length 0; an image with
+ *            nothing completed has count 0 (capnet_beam_finish's [<end>] is NOT among the entries).
+ *   capnet_beam_nbest_traced: also rows int32 [n][k][max_steps], capnet_beam_finish_traced's rule per hypothesis (i k + slot,
+ *            -1 past length - 1, past the count, and for a recorded slot outside [0, k)). Its checks are
+ *            capnet_beam_finish_traced's.
+ * An error for n < 1, k outside 1..16, max_steps < 1, a null or misaligned pointer. */
+int capnet_beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
+                      float* scores, int* counts, capnet_stream_t stream);
+int capnet_beam_nbest_traced(const void* beam, const void* trace, int n, int k, int max_steps, float length_penalty,
+                             long long* seqs, int* lengths, float* scores, int* counts, int* rows, capnet_stream_t stream);
+
+/* Where the one-call searches leave their beam state, trace and map history in the caller's workspace, as byte offsets:
+ * the n-best of such a search is capnet_beam_nbest on workspace + offset after the search returned (same stream).
+ *   capnet_beam_decode_ws_beam_offset: the beam state of capnet_beam_decode[_groups] / capnet_lstm_beam_decode[_groups]
+ *     (n: the sentences of ONE group, the state holds groups n images; fused_topk as the search's) and, with fused_topk 0
+ *     and groups 1 at n = all beam groups, of capnet_att_beam_decode[_groups / _alphas]. 0 where
+ *     capnet_lstm_beam_decode_groups_ws_bytes of the same arguments is 0.
+ *   capnet_att_beam_decode_alphas_ws_trace_offset / _hist_offset: the trace (capnet_beam_trace_bytes(groups n, ...)) and
+ *     the history f32 [max_steps][groups n k][P] of capnet_att_beam_decode_alphas. 0 where its _ws_bytes is 0. */
+size_t capnet_beam_decode_ws_beam_offset(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, int groups);
+size_t capnet_att_beam_decode_alphas_ws_trace_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H,
+                                                     int V, int max_steps);
+size_t capnet_att_beam_decode_alphas_ws_hist_offset(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H,
+                                                    int V, int max_steps);
+
+/* The gather of capnet_att_beam_decode_alphas on its own: alphas f32 [captions][max_steps][P], row (c, e) =
+ * hist[e][rows[c][e]] of a history f32 [max_steps][nk][P]; rows int32 [captions][max_steps], a row outside [0, nk) gives
+ * zeros. With captions = n k and capnet_beam_nbest_traced's rows: every hypothesis's maps in one launch. max_steps <=
+ * 65535; pointers 4-byte aligned. */
+int capnet_alpha_gather(const float* hist, const int* rows, int captions, int nk, int max_steps, int P, float* alphas,
+                        capnet_stream_t stream);
+
 /* One recurrent step in one launch (used inside capnet_seq_forward for t > 0):
  *   gates[b][4H] (in: U(S(V x)) + biases, ld ldg) += h_prev[b][H] . W[4H][H]^T (W given as the
  *   capnet_lstm_pack_wfrag image), then the gate
