@@ -565,6 +565,87 @@ int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, 
   return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream));
 }
 
+// ---- sampled decoding (vocab_sample.hip) ----
+float capnet_sample_uniform(unsigned long long seed, unsigned step, unsigned row, unsigned v) {
+  return sample_uniform_host(seed, step, row, v);
+}
+
+// what every sampling entry checks alike; sets inv_T
+static int sample_check(const char* who, int rows, int V, float temperature, unsigned step, unsigned row0, float* inv_T) {
+  CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1 && V <= (1 << 24), "%s: rows %d, V %d (rows < 2^24, V <= 2^24)", who, rows, V);
+  CAPNET_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature %g (finite, > 0)", who, (double)temperature);
+  CAPNET_REQUIRE(step <= 65535u && (unsigned long long)row0 + (unsigned)rows <= (1u << 24),
+                 "%s: step %u (<= 65535), row0 %u + rows %d (<= 2^24)", who, step, row0, rows);
+  *inv_T = 1.0f / temperature;
+  return kOk;
+}
+
+size_t capnet_vocab_sample_ws_bytes(int rows, int V) { return rows >= 1 && V >= 1 ? vocab_sample_ws_bytes(rows, V) : 0; }
+
+int capnet_vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                        unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens, float* logp,
+                        capnet_stream_t stream) {
+  float inv_T = 0.f;
+  if (int rc = sample_check("vocab_sample", rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(vocab_sample_supported(H), "vocab_sample: unsupported H=%d", H);
+  CAPNET_REQUIRE(h && w && workspace && tokens && logp, "vocab_sample: null argument");
+  CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_sample: h, w and the workspace must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "vocab_sample: output alignment");
+  return vocab_sample(h, w, b, rows, H, V, inv_T, seed, step, row0, workspace, tokens, nullptr, logp, 1, S(stream));
+}
+
+int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature, unsigned long long seed,
+                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+  float inv_T = 0.f;
+  if (int rc = sample_check("sample_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(k >= 1 && k <= 16, "sample_pick: k=%d (1 <= k <= 16)", k);
+  CAPNET_REQUIRE(values && index && tokens && logp, "sample_pick: null argument");
+  CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
+                 "sample_pick: alignment");
+  return sample_pick(values, index, rows, k, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+}
+
+int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed, unsigned step,
+                       unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+  float inv_T = 0.f;
+  if (int rc = sample_check("sample_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(ld >= V, "sample_rows: ld %ld < V %d", ld, V);
+  CAPNET_REQUIRE(logits && tokens && logp, "sample_rows: null argument");
+  CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "sample_rows: alignment");
+  return sample_rows(logits, rows, ld, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+}
+
+size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
+  if (nlayers < 1 || nlayers > 8 || rows < 1 || rows >= (1 << 24) || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
+  return sample_decode_ws_bytes(nlayers, rows, H, V, top_k);
+}
+
+int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
+                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out, int* err_flag,
+                         capnet_stream_t stream) {
+  float inv_T = 0.f;
+  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "sample_decode: steps %d (1..65535)", steps);
+  if (int rc = sample_check("sample_decode", rows, V, temperature, 0, 0, &inv_T)) return rc;
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "sample_decode: unknown cell %d", cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "sample_decode: layers %d (1..8)", nlayers);
+  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_decode: top_k=%d (0 = off, 1 .. 16, <= V = %d)", top_k, V);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_sample_supported(H), "sample_decode: unsupported E=%d H=%d", E, H);
+  CAPNET_REQUIRE((first_inputs != nullptr) != (start_tokens != nullptr),
+                 "sample_decode: the first input is either first_inputs or start_tokens");
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && logp && err_flag, "sample_decode: null argument");
+  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!state_out || aligned16(state_out)),
+                 "sample_decode: workspace, Cw and the states must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "sample_decode: ids / logp alignment");
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "sample_decode: weights of layer %d are null", l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "sample_decode: weights of layer %d not 16-B aligned", l);
+  }
+  return sample_decode(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
+                       top_k, seed, workspace, ids, logp, state_out, err_flag, S(stream));
+}
+
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
   return vocab_topk_groups_ws_bytes(groups, rows_per_group, k, V);
 }
@@ -801,6 +882,35 @@ int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int 
   return att_beam_decode_entry(cell, nlayers, groups, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz,
                                bz, w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs,
                                lengths, steps_run, err_flag, stream, false, nullptr);
+}
+
+size_t capnet_att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
+  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
+  return att_sample_decode_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
+}
+
+int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                             const float* wz, const float* bz, const float* w_full, const float* b_full,
+                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
+                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                             capnet_stream_t stream) {
+  if (int rc = att_decode_check("att_sample_decode", cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
+                                wcat, beff, workspace, slab, slab_floats, err_flag))
+    return rc;
+  float inv_T = 0.f;
+  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "att_sample_decode: steps %d (1..65535)", steps);
+  if (int rc = sample_check("att_sample_decode", n * m, V, temperature, 0, 0, &inv_T)) return rc;
+  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "att_sample_decode: top_k=%d (0 = off, 1 .. 16, <= V = %d)", top_k, V);
+  CAPNET_REQUIRE(vocab_sample_supported(H), "att_sample_decode: unsupported H=%d", H);
+  CAPNET_REQUIRE(start_tokens && Cw && state0 && ids && logp, "att_sample_decode: null argument (state0 is required)");
+  CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0) && (!state_out || aligned16(state_out)),
+                 "att_sample_decode: Cw and the states must be 16-B aligned");
+  CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "att_sample_decode: ids / logp alignment");
+  return att_sample_decode(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
+                           beff, Cw, Cb, state0, inv_T, top_k, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag,
+                           S(stream));
 }
 
 size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,

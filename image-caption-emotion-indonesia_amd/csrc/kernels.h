@@ -340,6 +340,34 @@ int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, 
 size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V);
 int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
                       void* ws, float* values, int* index, float* lse, hipStream_t stream);
+// vocab_sample.hip: per row a draw from softmax((h[r] . W + b) inv_T) by Gumbel-max on sample_rng.h's stream keyed (seed,
+// step, row0 + r, v), one launch, no logits in memory: tok[r] / ids[r ld] the token, logp[r ld] its log-probability (each
+// optional; ws: vocab_sample_ws_bytes, its first 16 bytes zero before the first use). sample_pick: the same draw among
+// vocab_topk's k candidates (logp renormalised over them); sample_rows: from a logits block in memory
+bool vocab_sample_supported(int H);
+float sample_uniform_host(unsigned long long seed, unsigned step, unsigned row, unsigned v);
+size_t vocab_sample_ws_bytes(int rows, int V);
+int vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float inv_T, unsigned long long seed,
+                 unsigned step, unsigned row0, void* ws, long long* tok, long long* ids, float* logp, long ld,
+                 hipStream_t stream);
+int sample_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, unsigned long long seed,
+                unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+int sample_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, unsigned long long seed, unsigned step,
+                unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+// lstm_greedy_decode's loop with the draw in place of the argmax (top_k == 0: vocab_sample; else vocab_topk + sample_pick)
+size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
+int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                  const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                  const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
+                  long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
+// the same for an attention decoder: n images x m samples each on att_decode_step (k = m, every row its own parent)
+size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
+int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                      const long long* start_tokens, const float* att1, const float* feat, const float* emb, const float* wz,
+                      const float* bz, const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
+                      const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
+                      void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                      hipStream_t s);
 // beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set; fused_topk: a step's
 // projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else beam_decode's
 size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);

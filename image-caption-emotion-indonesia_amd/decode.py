@@ -10,6 +10,10 @@ mode selects, the layout of their beam state, their weight fold.
     (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
     re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
     replay_alphas feeds the returned tokens back through the composed step, whose step_fn keeps its last maps in .alpha.
+  * sample_random: captions DRAWN from the decoder's distribution (temperature, top-k) with their log-probabilities, on the
+    same (step_fn, state) pair: one C call on the PlainStack / AttStack (ops.sample_decode / ops.att_sample_decode) or the
+    composed loop step_fn -> draw_step, the same stream and so the same tokens. CAPNET_NO_FUSED_SAMPLE=1 (read at every
+    call) takes the composed loop.
   * attend: Attention.forward, the single step outside a beam search.
   * att_beam_start / att_beam_step: an attention decoder's beam search. The set-up (encoder_att once per image, the
     initial state) is written once for one image and once for n; the step (z = [decoder_att; f_beta](h), the embedding
@@ -239,6 +243,88 @@ def _beam_nbest(dec, step_fn, state, n, k, start_token, end_token, on_device, po
     if n is None:
         lists, maps = _one_image(lists[0], dev), None if maps is None else maps[0]
     return (lists, maps) if return_alphas else lists
+
+
+# ---- sampled decoding -------------------------------------------------------------------------------
+FUSED_SAMPLE_OFF = "CAPNET_NO_FUSED_SAMPLE"
+# the largest measured row count at which the one-call sampler's median beat the composed loop's by more than the spread (the
+# larger of the two ranges) at every layer count and top_k measured (tools/time_sample_decode.py,
+# profiles/time_sample_decode.jsonl): capnet.seq2seq at 1, 12 and 64 rows -- it wins at 1 and 12 (1.3x to 2.2x) and
+# loses at 64 in three cells of four (one workgroup merges all rows); 13 to 63 rows were not measured. Above it sample_random
+# takes the composed loop.
+FUSED_SAMPLE_MAX_ROWS = 12
+# the same for the attention decoders, where the one call also spares the per-row copies of the maps: the one measured shape,
+# 12 images x 5 samples, wins 2.6x to 3.1x; nothing larger was measured
+FUSED_ATT_SAMPLE_MAX_ROWS = 60
+
+
+def fused_sample(rows, att=False):
+    """Whether a sampled decode of `rows` rows takes the one-call route now (CAPNET_NO_FUSED_SAMPLE is read here, at every
+    call; the shape and CAPNET_NO_FUSED_DECODE_STEP are the caller's to check)."""
+    return os.environ.get(FUSED_SAMPLE_OFF, "")[:1] != "1" and rows <= (FUSED_ATT_SAMPLE_MAX_ROWS if att else FUSED_SAMPLE_MAX_ROWS)
+
+
+def draw_step(logits, temperature, top_k, seed, step):
+    """The composed route's draw of stream step `step` from logits [rows, V] -> (tokens [rows] int64, logp [rows]): the
+    stream and the arithmetic of the one-call route's (ops.sample_rows; top_k > 0: torch.topk's candidates into
+    ops.sample_pick), so both routes return the same tokens wherever the best two keys are further apart than the logits'
+    last bits."""
+    if top_k == 0:
+        return ops.sample_rows(logits, temperature, seed, step)
+    values, index = torch.topk(logits, top_k, dim=1)
+    return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step)
+
+
+def cut_samples(ids, logp, n, m, start_token, end_token):
+    """ids / logp [n m, steps] of a sampled decode -> n lists of m (tokens, logprob): tokens = [start, w_1 .. w_j] cut after
+    the first end_token (none: every step), logprob the sum of the kept words' log-probabilities. One copy to the host."""
+    ids, logp = ids.cpu().tolist(), logp.double().cpu().tolist()
+    out = []
+    for i in range(n):
+        rows = []
+        for r in range(i * m, (i + 1) * m):
+            keep = ids[r].index(end_token) + 1 if end_token in ids[r] else len(ids[r])
+            rows.append(([int(start_token)] + ids[r][:keep], float(sum(logp[r][:keep]))))
+        out.append(rows)
+    return out
+
+
+def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None):
+    """`m` captions per image DRAWN from the decoder's distribution softmax(logits / temperature) (top_k > 0: renormalised
+    over the top_k best words of every step) -> n lists of m (tokens, logprob) pairs; row i m + j of the decode is sample j
+    of image i. step_fn / state: a class's _beam(...) with m in place of k and one_call=True, so step_fn carries a
+    PlainStack or an AttStack where the fused decode step takes the shape. Routes: ONE C call (ops.sample_decode /
+    ops.att_sample_decode) where that rides on step_fn, the rows are at most FUSED_SAMPLE_MAX_ROWS (FUSED_ATT_SAMPLE_MAX_ROWS) and
+    CAPNET_NO_FUSED_SAMPLE is not 1; else step_fn -> draw_step per step. Both run dec.max_seq_length steps without looking
+    at end_token (finished rows cost wasted steps; the host cuts), draw the same stream and so return the same lists.
+    seed: an integer makes the call a pure function; None draws one from torch's CPU generator."""
+    who = "sample_random"
+    m, steps, V = int(m), int(dec.max_seq_length), dec.vocab_size
+    temperature, top_k, seed = ops.check_sampling(who, temperature, top_k, seed, V)
+    if m < 1 or n < 1 or n * m >= ops.SAMPLE_MAX_ROWS or not 1 <= steps <= ops.SAMPLE_MAX_STEPS:
+        raise ops.CapnetError("%s: %d images x %d samples, %d steps" % (who, n, m, steps))
+    dev = state[0].device
+    with torch.no_grad():
+        plain, att = getattr(step_fn, "plain", None), getattr(step_fn, "att", None)
+        if fused_sample(n * m) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
+            tokens = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
+            ids, logp, _ = ops.sample_decode(plain.cell, steps, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb,
+                                             temperature, top_k, seed, start_tokens=tokens)
+        elif fused_sample(n * m, True) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
+            ids, logp = ops.att_sample_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
+                                              att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, m, steps,
+                                              start_token, temperature, top_k, seed)
+        else:
+            words = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
+            ids, logp = [], []
+            for t in range(steps):
+                logits, state = step_fn(words, state)
+                words, lp = draw_step(logits, temperature, top_k, seed, t)
+                ids.append(words)
+                logp.append(lp)
+            ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)
+    ops.check_device_errors()
+    return cut_samples(ids, logp, n, m, start_token, end_token)
 
 
 def zero_state(rows, H, device):

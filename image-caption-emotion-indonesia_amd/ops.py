@@ -856,6 +856,189 @@ def vocab_topk(h, w, b=None, k=5, workspace=None):
     return values, index, lse
 
 
+# ---- sampled decoding (csrc/vocab_sample.hip, csrc/sample_rng.h) ----------------------------------------------------------
+SAMPLE_MAX_STEPS = 65535          # the stream's step field
+SAMPLE_MAX_ROWS = 1 << 24         # the stream's row field (rows below it) and vocabulary field (V up to it)
+
+
+def sample_uniform(seed, step, row, v):
+    """u(seed, step, row, v) of the sampling stream (capnet_sample_uniform, a host function: no GPU): an odd multiple of
+    2^-24 strictly inside (0, 1). The kernels draw argmax_v (logit_v / T - log(-log u))."""
+    seed, step, row, v = int(seed), int(step), int(row), int(v)
+    if not (0 <= seed < 1 << 64 and 0 <= step <= SAMPLE_MAX_STEPS and 0 <= row < SAMPLE_MAX_ROWS and 0 <= v < SAMPLE_MAX_ROWS):
+        raise CapnetError("sample_uniform: seed %d step %d row %d v %d (seed < 2^64, step <= 65535, row, v < 2^24)"
+                          % (seed, step, row, v))
+    return float(_lib.lib().capnet_sample_uniform(seed, step, row, v))
+
+
+def draw_seed():
+    """A 63-bit seed from torch's CPU generator (what seed=None means in every sample_random): torch.manual_seed makes a
+    script reproducible."""
+    return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item()) * 2 + int(torch.randint(0, 2, (1,)).item())
+
+
+def check_sampling(who, temperature, top_k, seed, V=None):
+    """(temperature, top_k, seed) checked: temperature finite and > 0; top_k 0 (off) .. 16 and <= V; seed an integer in
+    [0, 2^64) or None (draw_seed)."""
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise CapnetError("%s: temperature %r" % (who, temperature))
+    if not (temperature > 0.0 and temperature <= 3.0e38) or not (float(torch.tensor(temperature, dtype=torch.float32)) > 0.0):
+        raise CapnetError("%s: temperature %r (finite, > 0)" % (who, temperature))
+    if isinstance(top_k, bool) or int(top_k) != top_k or not 0 <= int(top_k) <= 16 or (V is not None and int(top_k) > V):
+        raise CapnetError("%s: top_k=%r (0 = off, 1 .. 16, <= the vocabulary size)" % (who, top_k))
+    if seed is None:
+        seed = draw_seed()
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise CapnetError("%s: seed %r (an integer in [0, 2^64) or None)" % (who, seed))
+    return temperature, int(top_k), seed
+
+
+def _check_stream_pos(who, rows, V, step, row0):
+    step, row0 = int(step), int(row0)
+    if not (1 <= rows and 0 <= row0 and row0 + rows <= SAMPLE_MAX_ROWS and 1 <= V <= SAMPLE_MAX_ROWS and 0 <= step <= SAMPLE_MAX_STEPS):
+        raise CapnetError("%s: rows %d, V %d, step %d, row0 %d (row0 + rows <= 2^24, V <= 2^24, step <= 65535)"
+                          % (who, rows, V, step, row0))
+    return step, row0
+
+
+def vocab_sample_workspace(rows, V, device):
+    """A zeroed workspace of capnet_vocab_sample for `rows` rows (back-to-back calls on one stream may share it)."""
+    n = _lib.lib().capnet_vocab_sample_ws_bytes(int(rows), int(V))
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspace=None):
+    """(tokens [rows] int64, logp [rows] float32): per row a draw from softmax((h[r] . w + b) / temperature) and its
+    log-probability (capnet_vocab_sample: projection, Gumbel noise and argmax in one launch, no logits in memory). The noise
+    of row r and entry v is a function of (seed, step, row0 + r, v) alone (sample_uniform). h [rows, H], w [V, H], b [V]; H
+    in DECODE_HIDDEN. A NaN or -inf logit is never drawn; a row with nothing to draw gives (0, -inf)."""
+    temperature, _, seed = check_sampling("vocab_sample", temperature, 0, seed)
+    _need_cuda(h, w, b)
+    h, w = _c(h.detach()), _c(w.detach())
+    b = None if b is None else _c(b.detach())
+    if h.dim() != 2 or w.dim() != 2:
+        raise CapnetError("vocab_sample: h [rows, H], w [V, H]")
+    rows, H = h.shape
+    V = w.shape[0]
+    if w.shape[1] != H or H not in DECODE_HIDDEN or rows < 1 or (b is not None and b.numel() != V):
+        raise CapnetError("vocab_sample: h [rows, H], w [V, H], b [V] with H in %r" % (DECODE_HIDDEN,))
+    step, row0 = _check_stream_pos("vocab_sample", rows, V, step, row0)
+    if workspace is None:
+        workspace = vocab_sample_workspace(rows, V, h.device)
+    if workspace.numel() * workspace.element_size() < _lib.lib().capnet_vocab_sample_ws_bytes(rows, V):
+        raise CapnetError("vocab_sample: workspace too small")
+    tokens = torch.empty(rows, dtype=torch.int64, device=h.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=h.device)
+    check(_lib.lib().capnet_vocab_sample(ptr(h), ptr(w), ptr(b), rows, H, V, temperature, seed, step, row0, ptr(workspace),
+                                         ptr(tokens), ptr(logp), current_stream()), "capnet_vocab_sample")
+    return tokens, logp
+
+
+def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0):
+    """Top-k sampling on vocab_topk's (values, index) [rows, k], k <= 16 (capnet_sample_pick): (tokens [rows] int64, logp
+    [rows] float32), the draw among the k candidates with the noise keyed by their vocabulary index and logp renormalised
+    over the candidates. Padding slots (-inf, -1) are never drawn."""
+    temperature, _, seed = check_sampling("sample_pick", temperature, 0, seed)
+    _need_cuda(values, index)
+    values, index = _c(values.detach()), _c(index)
+    if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
+            or not 1 <= values.shape[1] <= 16 or values.shape[0] < 1:
+        raise CapnetError("sample_pick: values float32 [rows, k], index int32 [rows, k], 1 <= k <= 16")
+    rows, k = values.shape
+    step, row0 = _check_stream_pos("sample_pick", rows, int(V), step, row0)
+    tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=values.device)
+    check(_lib.lib().capnet_sample_pick(ptr(values), ptr(index), rows, k, int(V), temperature, seed, step, row0, ptr(tokens),
+                                        ptr(logp), current_stream()), "capnet_sample_pick")
+    return tokens, logp
+
+
+def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0):
+    """vocab_sample's draw from logits [rows, V] in memory (capnet_sample_rows, one workgroup per row): (tokens [rows] int64,
+    logp [rows] float32). Any V up to 2^24."""
+    temperature, _, seed = check_sampling("sample_rows", temperature, 0, seed)
+    _need_cuda(logits)
+    logits = logits.detach()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise CapnetError("sample_rows: logits float32 [rows, V]")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    rows, V = logits.shape
+    step, row0 = _check_stream_pos("sample_rows", rows, V, step, row0)
+    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    check(_lib.lib().capnet_sample_rows(ptr(logits), rows, logits.stride(0), V, temperature, seed, step, row0, ptr(tokens),
+                                        ptr(logp), current_stream()), "capnet_sample_rows")
+    return tokens, logp
+
+
+def sample_decode_supported(E, H, V, top_k=0):
+    """The shapes capnet_sample_decode takes: those of its parts (the decode step; capnet_vocab_topk when top_k > 0)."""
+    return stacked_decode_supported(E, H) and 1 <= V <= SAMPLE_MAX_ROWS and (top_k == 0 or vocab_topk_supported(H, top_k, V))
+
+
+def vocab_topk_supported(H, k, V):
+    """The shapes capnet_vocab_topk takes (csrc/vocab_topk.hip: vocab_topk_supported)."""
+    return H in DECODE_HIDDEN and 1 <= k <= 16 and k <= V
+
+
+def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed, first_inputs=None, start_tokens=None,
+                  state=None):
+    """`steps` sampled decode steps of a plain stack in ONE C call (capnet_sample_decode): per step one decode-step launch
+    per layer and the draw (top_k == 0: capnet_vocab_sample; else capnet_vocab_topk + capnet_sample_pick), tokens and logits
+    never leaving the device. wcat / beff: capnet.decode.pack_cell(s) of every layer; emb [V, E]; Cw [V, H], Cb [V] or None.
+    The first input is first_inputs [rows, E] or emb[start_tokens] (int64 [rows]); state [rows, 2L, H] or None for zeros.
+    Row r draws on stream row r, step t on stream step t. Returns (ids [rows, steps] int64, logp [rows, steps] float32,
+    the final state [rows, 2L, H])."""
+    who = "sample_decode"
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("%s: unknown cell %r" % (who, cell))
+    if (first_inputs is None) == (start_tokens is None):
+        raise CapnetError("%s: either first_inputs or start_tokens" % who)
+    if emb.dim() != 2 or Cw.dim() != 2:
+        raise CapnetError("%s: emb [V, E], Cw [V, H]" % who)
+    V, E = emb.shape
+    temperature, top_k, seed = check_sampling(who, temperature, top_k, seed, V)
+    _need_cuda(emb, Cw, Cb, first_inputs, start_tokens, state, *wcat, *beff)
+    emb, Cw = _c(emb.detach()), _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    H, nl, steps = Cw.shape[1], len(wcat), int(steps)
+    rows = (first_inputs if first_inputs is not None else start_tokens).shape[0]
+    if first_inputs is not None:
+        first_inputs = _c(first_inputs.detach())
+        if tuple(first_inputs.shape) != (rows, E):
+            raise CapnetError("%s: first_inputs must be [rows, embed_size]" % who)
+    else:
+        start_tokens = _c(start_tokens)
+        if start_tokens.dtype != torch.int64 or start_tokens.dim() != 1:
+            raise CapnetError("%s: start_tokens must be int64 [rows]" % who)
+    if not 1 <= steps <= SAMPLE_MAX_STEPS or not 1 <= rows < SAMPLE_MAX_ROWS:
+        raise CapnetError("%s: steps %d (1..65535), rows %d (1..2^24 - 1)" % (who, steps, rows))
+    if not sample_decode_supported(E, H, V, top_k) or not 1 <= nl <= 8 or len(beff) != nl or tuple(Cw.shape) != (V, H) \
+            or (Cb is not None and Cb.numel() != V):
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, top_k=%d)" % (who, E, H, V, nl, top_k))
+    _check_layer_weights(who, wcat, beff, 1, H, (E + 15) // 16 * 16)
+    dev = emb.device
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (rows, 2 * nl, H):
+            raise CapnetError("%s: state must be [rows, 2L, H]" % who)
+    L = _lib.lib()
+    nbytes = L.capnet_sample_decode_ws_bytes(nl, rows, H, V, top_k)
+    if not nbytes:
+        raise CapnetError("%s: unsupported shape (rows=%d, V=%d, top_k=%d)" % (who, rows, V, top_k))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
+    logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
+    out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
+    check(L.capnet_sample_decode(cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb), ptr_array(wcat),
+                                 ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, seed, ptr(ws), ptr(ids),
+                                 ptr(logp), ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_sample_decode")
+    return ids, logp, out
+
+
 def vocab_topk_groups_workspace(groups, rows_per_group, k, V, device):
     """A zeroed workspace of capnet_vocab_topk_groups (back-to-back calls on one stream may share it)."""
     n = _lib.lib().capnet_vocab_topk_groups_ws_bytes(int(groups), int(rows_per_group), int(k), int(V))
@@ -1307,6 +1490,39 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     if return_alphas:
         res += ([maps[i, :lens[i] - 1] for i in range(n)],)
     return res if len(res) > 1 else out
+
+
+def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,
+                      temperature, top_k, seed):
+    """`steps` sampled decode steps of an attention decoder in ONE C call (capnet_att_sample_decode): n images x m samples
+    each (row i m + j = sample j of image i), the step att_decode_step's with k = m and every row continuing from itself --
+    an image's maps are read once per step for all its samples -- then the draw as ops.sample_decode's. Operands as
+    att_beam_decode; state [n m, 2L, H]: the initial state. Returns (ids [n m, steps] int64, logp [n m, steps] float32)."""
+    who = "att_sample_decode"
+    att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
+        who, cell, att1, feat, m, emb, wz, bz, w_full, b_full, wcat, beff, state)
+    temperature, top_k, seed = check_sampling(who, temperature, top_k, seed, V)
+    _need_cuda(Cw, Cb)
+    Cw = _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    m, steps = int(m), int(steps)
+    if not 1 <= steps <= SAMPLE_MAX_STEPS or tuple(Cw.shape) != (V, H) or (Cb is not None and Cb.numel() != V):
+        raise CapnetError("%s: Cw [V, H], Cb [V], 1 <= steps <= 65535 (V=%d, steps=%d)" % (who, V, steps))
+    dev, rows = emb.device, n * m
+    L = _lib.lib()
+    nbytes = L.capnet_att_sample_decode_ws_bytes(nl, n, m, P, A, Cdim, E, H, V, top_k)
+    if not nbytes:
+        raise CapnetError("%s: unsupported shape (n=%d, m=%d, V=%d, top_k=%d)" % (who, n, m, V, top_k))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    slab = splitk_slab(dev)
+    tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
+    ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
+    logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
+    check(L.capnet_att_sample_decode(cell, nl, n, m, P, A, Cdim, E, H, V, steps, ptr(tokens), ptr(att1), ptr(feat), ptr(emb), ptr(wz),
+                                     ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state),
+                                     temperature, top_k, seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None,
+                                     ptr(err_flag(dev)), current_stream()), "capnet_att_sample_decode")
+    return ids, logp
 
 
 def packed_targets(captions, lengths):

@@ -44,6 +44,12 @@ stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with 
     profiles/time_seq2seq_beam_styles.jsonl. `factual` is the encoder's own sample_beam, not a group. Every entry equals
     sample_beam(mode=...). One emotion, unequal decoder shapes, a shape the decode kernel does not take or
     CAPNET_NO_FUSED_DECODE_STEP=1: one DecoderRNN.sample_beam after the other on the one encoder run.
+  * Sampled decoding: sample_random on all three classes -- sample() with every word a draw from softmax(logits /
+    temperature) (top_k: renormalised over the step's k best), returning (ids, logp); Gumbel-max on a counter-based stream
+    (csrc/sample_rng.h), so an integer seed makes a call a pure function. One capnet_sample_decode call (per step one launch
+    per layer and csrc/vocab_sample.hip, or capnet_vocab_topk + capnet_sample_pick) up to capnet.decode.FUSED_SAMPLE_MAX_ROWS
+    rows; CAPNET_NO_FUSED_SAMPLE=1 (read at every call), CAPNET_NO_FUSED_DECODE_STEP=1, more rows or a shape the decode
+    kernel does not take: the composed loop on the same stream, the same tokens.
 """
 import os
 import random
@@ -54,7 +60,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import CapnetError
 from .beam import beam_search_device
-from .decode import cell_stepper, check_styles, fused_decode_step, pack_cells
+from .decode import cell_stepper, check_styles, draw_step, fused_decode_step, fused_sample, pack_cells
 from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
 
@@ -195,6 +201,35 @@ class _RNN(nn.Module):
             return torch.stack(ids, 1), state
 
 
+    def _sampled(self, features, start_tokens, state, temperature, top_k, seed):
+        """max_seq_length SAMPLED steps from `features` [rows, E] or emb[start_tokens]; state [rows, 2L, H]: every word a draw
+        from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k best), row r on stream row r, step
+        t on stream step t. Returns (ids [rows, max_seq_length] int64, logp [rows, max_seq_length] float32, state').
+        One capnet_sample_decode call where the decode kernel takes the shape, the rows are at most
+        capnet.decode.FUSED_SAMPLE_MAX_ROWS and neither CAPNET_NO_FUSED_SAMPLE=1 nor CAPNET_NO_FUSED_DECODE_STEP=1 is set;
+        else the composed loop (step -> ops.linear -> capnet.decode.draw_step) on the same stream: the same tokens."""
+        E, H, V, steps = self.embed_size, self.hidden_size, self.vocab_size, self.max_seq_length
+        temperature, top_k, seed = ops.check_sampling("sample_random", temperature, top_k, seed, V)
+        emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
+        layers = self._layers()
+        with torch.no_grad():
+            if (fused_sample(state.shape[0]) and fused_decode_step(self.num_layers, E, H)
+                    and ops.sample_decode_supported(E, H, V, top_k)):
+                packed = pack_cells(layers, E)
+                return ops.sample_decode(ops.CELL_LSTM, steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
+                                         temperature, top_k, seed, first_inputs=features, start_tokens=start_tokens, state=state)
+            step = cell_stepper(layers, E, H)
+            ids, logp, tokens = [], [], start_tokens
+            for t in range(steps):
+                if t == 0 and features is not None:
+                    top, state = step(features.detach().float().contiguous(), None, state)
+                else:
+                    top, state = step(emb, tokens, state)
+                tokens, lp = draw_step(ops.linear(top, Cw, Cb), temperature, top_k, seed, t)
+                ids.append(tokens)
+                logp.append(lp)
+            return torch.stack(ids, 1), torch.stack(logp, 1), state
+
     def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk, nbest=False, length_penalty=0.0):
         """Beam search of B = state.shape[0] sentences x k beams from `state` [B, 2L, H]; the first input is `features`
         [B, E] or, None, embed(start_token). max_seq_length + 1 steps at most. Returns B token lists, each starting with
@@ -264,6 +299,16 @@ class EncoderRNN(_RNN):
         ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
         return ids, _from_rows(state)
 
+    def sample_random(self, features, states=(None, None), temperature=1.0, top_k=0, seed=None):
+        """sample() with every word DRAWN from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k
+        best words) instead of the argmax: (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32 -- each word's
+        log-probability under the distribution sampled from --, (h, c) [num_layers, B, H]); the first input is `features`.
+        seed: an integer makes the call a pure function; None draws one from torch's CPU generator (torch.manual_seed).
+        Routing: _RNN._sampled."""
+        state = self._rows_state(states, features.size(0), features.device)
+        ids, logp, state = self._sampled(features, None, state, temperature, top_k, seed)
+        return ids, logp, _from_rows(state)
+
     def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None, nbest=False,
                     length_penalty=0.0):
         """Beam search (k beams per sentence, max_seq_length + 1 steps at most, a beam completes at end_token) whose first
@@ -302,6 +347,20 @@ class DecoderRNN(_RNN):
         ids, _ = self._greedy(None, tokens, state)
         ops.check_device_errors()
         return ids
+
+    def sample_random(self, start_token, states, temperature=1.0, top_k=0, seed=None):
+        """sample() with every word drawn (EncoderRNN.sample_random): from embed(start_token) and `states` (h, c)
+        [num_layers, B, H] -> (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32). An out-of-range
+        start_token raises CapnetError through the device error word."""
+        h, c = states
+        given = h if h is not None else c
+        rows = 1 if given is None else given.size(1)
+        dev = self.embed.weight.device
+        state = self._rows_state(states, rows, dev)
+        tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
+        ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed)
+        ops.check_device_errors()
+        return ids, logp
 
     def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None, nbest=False, length_penalty=0.0):
         """Beam search from embed(start_token) and `states` (h, c) [num_layers, B, H]: a list of B token lists, one per
@@ -354,6 +413,17 @@ class Seq2Seq(nn.Module):
         if decoder is None:
             return sampled_ids
         return decoder.sample(start_token, states)
+
+    def sample_random(self, features, start_token, states=(None, None), mode='factual', temperature=1.0, top_k=0, seed=None):
+        """factual: the encoder's sampled (ids, logp) [B, max_seq_length] (EncoderRNN.sample_random). An emotion mode: the
+        encoder's GREEDY sample for the state, exactly as sample(mode=...) does, then that decoder's sampled (ids, logp)
+        from embed(start_token) and it: only the emotion decoder samples."""
+        decoder = None if mode == 'factual' else self._decoder(mode)
+        if decoder is None:
+            ids, logp, _ = self.encoder.sample_random(features, states, temperature, top_k, seed)
+            return ids, logp
+        _, states = self.encoder.sample(features, states)
+        return decoder.sample_random(start_token, states, temperature, top_k, seed)
 
     def sample_beam(self, features, start_token, end_token, states=(None, None), mode='factual', k=5, poll_every=0,
                     fused_topk=None, nbest=False, length_penalty=0.0):

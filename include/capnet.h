@@ -698,6 +698,63 @@ size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V);
 int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
                       float* values, int* index, float* lse, capnet_stream_t stream);
 
+/* ---- sampled decoding: temperature and top-k sampling (csrc/vocab_sample.hip, csrc/sample_rng.h) ----
+ * The random stream, on the HOST (no GPU): u(seed, step, row, v) = (2 b + 1) / 2^24, b the top 23 bits of the finalized
+ * hash of seed + 0x9E3779B97F4A7C15 (((step << 48) | (row << 24) | v) + 1): an odd multiple of 2^-24, strictly inside
+ * (0, 1), exact in fp32. step <= 65535, row < 2^24, v < 2^24. The kernels below draw
+ *   token = argmax_v (logit_v / T - logf(-logf(u(seed, step, row0 + r, v)))),   ties to the lower v
+ * a draw from softmax(logit / T) (Gumbel-max), so a caller can reproduce every draw from the logits alone. */
+float capnet_sample_uniform(unsigned long long seed, unsigned step, unsigned row, unsigned v);
+
+/* tokens[r] (int64) = a draw from softmax((h[r] . w + b) / temperature), logp[r] = its log-probability under that
+ * distribution, in ONE launch, the logits never in memory (capnet_vocab_argmax's mapping; noise in the epilogue). h [rows][H],
+ * w [V][H], b [V] or NULL; H in {64, 128, 256, 512, 1024}; rows < 2^24, V <= 2^24; temperature finite and > 0. A NaN or -inf
+ * logit is never drawn and adds nothing to the normaliser; a row with nothing to draw yields token 0 and logp = -inf.
+ * row0: the stream row of row 0 (rows split over launches draw what one launch draws). workspace:
+ * capnet_vocab_sample_ws_bytes(rows, V) bytes, 16-B aligned, whose first 16 bytes are ZERO before the first use and are
+ * left zero (back-to-back calls on one stream may share it). Deterministic: the same bits whichever workgroup merges. */
+size_t capnet_vocab_sample_ws_bytes(int rows, int V);
+int capnet_vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                        unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens, float* logp,
+                        capnet_stream_t stream);
+
+/* Top-k sampling on capnet_vocab_topk's outputs: the same draw among the k candidates values / index [rows][k] (1 <= k <= 16),
+ * the noise keyed by the candidate's vocabulary index (V bounds it), logp renormalised over the k candidates. Padding
+ * slots (-inf, -1) are never drawn; a row of padding yields token 0 and logp = -inf. */
+int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature, unsigned long long seed,
+                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream);
+
+/* The same draw as capnet_vocab_sample from logits [rows][ld] in memory (ld >= V), one workgroup per row: any H, any V. */
+int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed, unsigned step,
+                       unsigned row0, long long* tokens, float* logp, capnet_stream_t stream);
+
+/* `steps` sampled decode steps of a plain stack in ONE C call: capnet_lstm_greedy_decode's loop with the cell kind passed to
+ * capnet_stacked_decode_step_cell and, in place of the argmax, capnet_vocab_sample at stream step t (top_k == 0) or
+ * capnet_vocab_topk + capnet_sample_pick (1 <= top_k <= 16). The first input is first_inputs [rows][E] or
+ * emb[start_tokens] (exactly one of them); state0 [rows][2 nlayers][H] or NULL for zeros. ids int64 [rows][steps], logp
+ * float [rows][steps]; state_out [rows][2 nlayers][H] or NULL. No end token is looked at: all `steps` (<= 65535) steps run
+ * and the caller truncates. workspace: capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k) bytes (0: unsupported),
+ * 16-B aligned, contents irrelevant. */
+size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
+int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
+                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out, int* err_flag,
+                         capnet_stream_t stream);
+
+/* The same for an attention decoder: n images x m samples each (row i m + j = sample j of image i; 1 <= m <= 16), the step
+ * capnet_att_decode_step with k = m and every row continuing from itself, so an image's maps are read once per step for all
+ * its samples; operands as capnet_att_beam_decode (state0 [n m][2 nlayers][H] is required; start_tokens int64 [n m]).
+ * workspace: capnet_att_sample_decode_ws_bytes(...) bytes (0: unsupported), 16-B aligned; slab: the split-K slab. */
+size_t capnet_att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
+int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                             const float* wz, const float* bz, const float* w_full, const float* b_full,
+                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
+                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                             capnet_stream_t stream);
+
 /* capnet_vocab_topk for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's rows
  * are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL; every
  * w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival counter
