@@ -457,6 +457,49 @@ size_t capnet_lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int ro
              ? lstm_greedy_decode_groups_ws_bytes(nlayers, groups, rows_per_group, H, V) : 0;
 }
 
+// the per-layer weights of every one-call decode: wcat[l] and beff[l] given, wcat[l] 16-B aligned
+static int layer_weights_check(const char* who, int nlayers, const float* const* wcat, const float* const* beff) {
+  for (int l = 0; l < nlayers; ++l) {
+    CAPNET_REQUIRE(wcat[l] && beff[l], "%s: weights of layer %d are null", who, l);
+    CAPNET_REQUIRE(aligned16(wcat[l]), "%s: weights of layer %d not 16-B aligned", who, l);
+  }
+  return kOk;
+}
+
+// what the plain stacks' one-call beam searches check alike: `groups` weight groups of n sentences (images) each on `tables`
+// embeddings and projections (1: one of each for every group; groups: one per group); fused_topk: no slab is needed
+static int stack_decode_check(const char* who, int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                              long long start_token, int poll_every, int fused_topk, int tables, const float* const* emb,
+                              const float* const* wcat, const float* const* beff, const float* const* Cw, const float* state0,
+                              const void* workspace, const float* slab, size_t slab_floats, const long long* seqs,
+                              const int* lengths, const int* err_flag) {
+  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "%s: groups %d (1..8)", who, groups);
+  const long nq = n >= 1 && n < (1 << 24) ? (long)groups * n : 0;      // the beam groups
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "%s: unknown cell %d", who, cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "%s: layers %d (1..8)", who, nlayers);
+  CAPNET_REQUIRE(nq >= 1 && max_steps >= 1 && V >= 1 && poll_every >= 0, "%s: n %d, max_steps %d, V %d, poll_every %d", who, n,
+                 max_steps, V, poll_every);
+  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "%s: k=%d (1 <= k <= 16, k <= V = %d)", who, k, V);
+  CAPNET_REQUIRE(nq * k * (max_steps + 2) < (1L << 28) && nq * k * V < (1L << 31), "%s: n k too large", who);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H), "%s: unsupported E=%d H=%d", who, E, H);
+  CAPNET_REQUIRE(!fused_topk || vocab_topk_supported(H, k, V), "%s: the fused top-k does not take H=%d", who, H);
+  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "%s: start_token %lld", who, start_token);
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && seqs && lengths && err_flag, "%s: null argument", who);
+  CAPNET_REQUIRE(aligned16(workspace) && (!state0 || aligned16(state0)), "%s: workspace, Cw and state0 must be 16-B aligned", who);
+  for (int g = 0; g < tables; ++g) {
+    CAPNET_REQUIRE(emb[g] && Cw[g], "%s: null argument (embedding or projection of group %d)", who, g);
+    CAPNET_REQUIRE(aligned16(Cw[g]), "%s: workspace, Cw and state0 must be 16-B aligned (Cw of group %d)", who, g);
+  }
+  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "%s: seqs / lengths alignment", who);
+  if (!fused_topk) {
+    CAPNET_REQUIRE(slab, "%s: null argument (without the fused top-k the slab is required)", who);
+    CAPNET_REQUIRE(aligned16(slab), "%s: the slab must be 16-B aligned", who);
+    CAPNET_REQUIRE(slab_floats >= (size_t)nq * k * V, "%s: the slab holds %zu floats, one [n k][V] block is %zu", who, slab_floats,
+                   (size_t)nq * k * V);
+  }
+  return layer_weights_check(who, nlayers, wcat, beff);
+}
+
 // what the two greedy entries check alike (features only with one group)
 static int greedy_check(int nlayers, int groups, int rpg, int E, int H, int V, int steps, const float* features,
                         const long long* start_tokens, const float* const* emb, const float* const* wcat,
@@ -475,11 +518,7 @@ static int greedy_check(int nlayers, int groups, int rpg, int E, int H, int V, i
     CAPNET_REQUIRE(emb[g] && Cw[g], "lstm_greedy_decode: null argument (embedding or projection of group %d)", g);
     CAPNET_REQUIRE(aligned16(Cw[g]), "lstm_greedy_decode: workspace, Cw and the states must be 16-B aligned (group %d)", g);
   }
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_greedy_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_greedy_decode: weights of layer %d not 16-B aligned", l);
-  }
-  return kOk;
+  return layer_weights_check("lstm_greedy_decode", nlayers, wcat, beff);
 }
 
 int capnet_lstm_greedy_decode_groups(int nlayers, int groups, int rows_per_group, int E, int H, int V, int steps,
@@ -528,26 +567,9 @@ int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n_images, i
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                               float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
                               int* err_flag, capnet_stream_t stream) {
-  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "beam_decode: groups %d (1..8)", groups);
-  const int n = n_images >= 1 && n_images < (1 << 24) ? groups * n_images : 0;
-  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "beam_decode: unknown cell %d", cell);
-  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "beam_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(n >= 1 && max_steps >= 1 && V >= 1 && poll_every >= 0, "beam_decode: n %d, max_steps %d, V %d, poll_every %d",
-                 n_images, max_steps, V, poll_every);
-  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
-  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28) && (long)n * k * V < (1L << 31), "beam_decode: n k too large");
-  CAPNET_REQUIRE(stacked_decode_supported(E, H), "beam_decode: unsupported E=%d H=%d", E, H);
-  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "beam_decode: start_token %lld", start_token);
-  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && slab && seqs && lengths && err_flag, "beam_decode: null argument");
-  CAPNET_REQUIRE(aligned16(workspace) && aligned16(slab) && aligned16(Cw) && (!state0 || aligned16(state0)),
-                 "beam_decode: workspace, slab, Cw and state0 must be 16-B aligned");
-  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "beam_decode: seqs / lengths alignment");
-  CAPNET_REQUIRE(slab_floats >= (size_t)n * k * V, "beam_decode: the slab holds %zu floats, one [n k][V] block is %zu", slab_floats,
-                 (size_t)n * k * V);
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "beam_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "beam_decode: weights of layer %d not 16-B aligned", l);
-  }
+  if (int rc = stack_decode_check("beam_decode", cell, nlayers, groups, n_images, k, E, H, V, max_steps, start_token, poll_every, 0,
+                                  1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
+    return rc;
   return beam_decode(cell, nlayers, n_images, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0,
                      workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups);
 }
@@ -638,10 +660,7 @@ int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, i
   CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!state_out || aligned16(state_out)),
                  "sample_decode: workspace, Cw and the states must be 16-B aligned");
   CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "sample_decode: ids / logp alignment");
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "sample_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "sample_decode: weights of layer %d not 16-B aligned", l);
-  }
+  if (int rc = layer_weights_check("sample_decode", nlayers, wcat, beff)) return rc;
   return sample_decode(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
                        top_k, seed, workspace, ids, logp, state_out, err_flag, S(stream));
 }
@@ -675,29 +694,12 @@ int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, i
                             const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                             float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                             int* steps_run, int* err_flag, capnet_stream_t stream) {
-  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "lstm_beam_decode: unknown cell %d", cell);
-  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_beam_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(n >= 1 && n < (1 << 24) && max_steps >= 1 && V >= 1 && poll_every >= 0,
-                 "lstm_beam_decode: n %d, max_steps %d, V %d, poll_every %d", n, max_steps, V, poll_every);
-  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "lstm_beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
-  CAPNET_REQUIRE((long)n * k * (max_steps + 2) < (1L << 28) && (long)n * k * V < (1L << 31) && (long)n * k < (1L << 24),
-                 "lstm_beam_decode: n k too large");
-  CAPNET_REQUIRE(stacked_decode_supported(E, H), "lstm_beam_decode: unsupported E=%d H=%d", E, H);
-  CAPNET_REQUIRE(!fused_topk || vocab_topk_supported(H, k, V), "lstm_beam_decode: the fused top-k does not take H=%d", H);
-  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "lstm_beam_decode: start_token %lld", start_token);
-  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && seqs && lengths && err_flag, "lstm_beam_decode: null argument");
-  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!first_inputs || aligned16(first_inputs)),
-                 "lstm_beam_decode: workspace, Cw, state0 and first_inputs must be 16-B aligned");
-  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "lstm_beam_decode: seqs / lengths alignment");
-  if (!fused_topk) {
-    CAPNET_REQUIRE(slab && aligned16(slab), "lstm_beam_decode: without the fused top-k the slab is required, 16-B aligned");
-    CAPNET_REQUIRE(slab_floats >= (size_t)n * k * V, "lstm_beam_decode: the slab holds %zu floats, one [n k][V] block is %zu",
-                   slab_floats, (size_t)n * k * V);
-  }
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_beam_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_beam_decode: weights of layer %d not 16-B aligned", l);
-  }
+  if (int rc = stack_decode_check("lstm_beam_decode", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every,
+                                  fused_topk, 1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths,
+                                  err_flag))
+    return rc;
+  CAPNET_REQUIRE((long)n * k < (1L << 24), "lstm_beam_decode: n k too large");
+  CAPNET_REQUIRE(!first_inputs || aligned16(first_inputs), "lstm_beam_decode: first_inputs must be 16-B aligned");
   return lstm_beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb, wcat, beff, Cw, Cb,
                           state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
                           S(stream));
@@ -715,35 +717,13 @@ int capnet_lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int
                                    const float* const* Cb, const float* state0, void* workspace, float* slab,
                                    size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                                    int* steps_run, int* err_flag, capnet_stream_t stream) {
-  CAPNET_REQUIRE(groups >= 1 && groups <= 8, "lstm_beam_decode: groups %d (1..8)", groups);
-  const long nq = n >= 1 && n < (1 << 24) ? (long)groups * n : 0;
-  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "lstm_beam_decode: unknown cell %d", cell);
-  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "lstm_beam_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(nq >= 1 && nq < (1 << 24) && max_steps >= 1 && V >= 1 && poll_every >= 0,
-                 "lstm_beam_decode: n %d, max_steps %d, V %d, poll_every %d", n, max_steps, V, poll_every);
-  CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "lstm_beam_decode: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
-  CAPNET_REQUIRE(nq * k * (max_steps + 2) < (1L << 28) && nq * k * V < (1L << 31) && nq * k < (1L << 24),
-                 "lstm_beam_decode: n k too large");
-  CAPNET_REQUIRE(stacked_decode_supported(E, H), "lstm_beam_decode: unsupported E=%d H=%d", E, H);
-  CAPNET_REQUIRE(!fused_topk || vocab_topk_supported(H, k, V), "lstm_beam_decode: the fused top-k does not take H=%d", H);
-  CAPNET_REQUIRE(start_token >= 0 && start_token <= 0x7fffffffLL, "lstm_beam_decode: start_token %lld", start_token);
-  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && seqs && lengths && err_flag, "lstm_beam_decode: null argument");
-  CAPNET_REQUIRE(aligned16(workspace) && (!state0 || aligned16(state0)),
-                 "lstm_beam_decode: workspace, Cw and state0 must be 16-B aligned");
-  for (int g = 0; g < groups; ++g) {
-    CAPNET_REQUIRE(emb[g] && Cw[g], "lstm_beam_decode: null argument (embedding or projection of group %d)", g);
-    CAPNET_REQUIRE(aligned16(emb[g]) && aligned16(Cw[g]), "lstm_beam_decode: emb and Cw must be 16-B aligned (group %d)", g);
-  }
-  CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "lstm_beam_decode: seqs / lengths alignment");
-  if (!fused_topk) {
-    CAPNET_REQUIRE(slab && aligned16(slab), "lstm_beam_decode: without the fused top-k the slab is required, 16-B aligned");
-    CAPNET_REQUIRE(slab_floats >= (size_t)nq * k * V, "lstm_beam_decode: the slab holds %zu floats, one [n k][V] block is %zu",
-                   slab_floats, (size_t)nq * k * V);
-  }
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "lstm_beam_decode: weights of layer %d are null", l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "lstm_beam_decode: weights of layer %d not 16-B aligned", l);
-  }
+  if (int rc = stack_decode_check("lstm_beam_decode", cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, poll_every,
+                                  fused_topk, groups, emb, wcat, beff, Cw, state0, workspace, slab, slab_floats, seqs, lengths,
+                                  err_flag))
+    return rc;
+  CAPNET_REQUIRE((long)groups * n * k < (1L << 24), "lstm_beam_decode: n k too large");
+  for (int g = 0; g < groups; ++g)
+    CAPNET_REQUIRE(aligned16(emb[g]), "lstm_beam_decode: emb and Cw must be 16-B aligned (group %d)", g);
   return lstm_beam_decode_groups(cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
                                  state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
                                  S(stream));
@@ -775,11 +755,7 @@ static int att_decode_check(const char* who, int cell, int nlayers, int n, int k
   // (wz and w_full of group g lie (A + C) H and A floats on: multiples of 16 bytes, A % 4 == 0 and H % 4 == 0)
   const size_t need = (size_t)n * k * (size_t)(V > A + C ? V : A + C);
   CAPNET_REQUIRE(slab_floats >= need, "%s: the slab holds %zu floats, one [n k][max(V, A + C)] block is %zu", who, slab_floats, need);
-  for (int l = 0; l < nlayers; ++l) {
-    CAPNET_REQUIRE(wcat[l] && beff[l], "%s: weights of layer %d are null", who, l);
-    CAPNET_REQUIRE(aligned16(wcat[l]), "%s: weights of layer %d not 16-B aligned", who, l);
-  }
-  return kOk;
+  return layer_weights_check(who, nlayers, wcat, beff);
 }
 
 int capnet_att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, const float* att1,

@@ -6,6 +6,10 @@ mode selects, the layout of their beam state, their weight fold.
     `_beam` method; its sample() asks for one group of k beams, its sample_batch() for n groups. one_call=True: the
     whole search of a plain stack in one C call (ops.beam_decode) on the PlainStack a class attaches to its step_fn
     (plain_stack: the fused step's packed weights, the embedding table and the projection).
+    The route is chosen in ONE ladder, whatever the keywords: (1) one_call and a PlainStack of a supported shape:
+    ops.beam_decode; (2) one_call and an AttStack: ops.att_beam_decode (_one_call_att); (3) on_device, or one_call with
+    neither: capnet.beam.beam_search_device; (4) the host loops beam_search / beam_search_batched. nbest and length_penalty
+    go to whichever route runs; _beam_result then shapes what it gave (one image: tensors; maps attached) for all four.
     return_alphas: the attention maps that preceded every word of the captions -- recorded by the one-call search
     (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
     re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
@@ -177,71 +181,43 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     capnet_beam_nbest. With return_alphas every hypothesis has its own maps, in the same nesting. length_penalty without
     nbest raises CapnetError."""
     length_penalty = ops.check_length_penalty("beam search", nbest, length_penalty)
-    dev = state[0].device
-    if nbest:
-        return _beam_nbest(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas,
-                           length_penalty)
-    if return_alphas:
-        att = getattr(step_fn, "att", None) if one_call else None
-        if att is not None:
-            with torch.no_grad():
-                seqs, maps = _one_call_att(dec, att, 1 if n is None else n, k, start_token, end_token, poll_every, True)
-            return (seqs, maps) if n is not None else (torch.tensor(seqs, dtype=torch.long, device=dev), maps[0])
-        seqs = beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call)
-        maps = replay_alphas(step_fn, state, seqs if n is not None else seqs[0].tolist(), n, k)
-        return (seqs, maps) if n is not None else (seqs, maps[0])
+    dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
+    nb = dict(nbest=True, length_penalty=length_penalty) if nbest else {}
+    plain = getattr(step_fn, "plain", None) if one_call else None
+    att = getattr(step_fn, "att", None) if one_call else None
+    maps = one = None
     with torch.no_grad():
-        if one_call:
-            plain, on_device = getattr(step_fn, "plain", None), True
-            if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, dec.vocab_size,
-                                                               len(plain.wcat)):
-                seqs = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, 1 if n is None else n,
-                                       k, dec.max_seq_length + 1, start_token, end_token, poll_every)
-                return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
-            att = getattr(step_fn, "att", None)
-            if att is not None:
-                seqs = ops.att_beam_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
-                                           att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, k,
-                                           dec.max_seq_length + 1, start_token, end_token, poll_every)
-                return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
-        if on_device:
-            seqs = beam_search_device(step_fn, state, 1 if n is None else n, dec.vocab_size, start_token, end_token, k,
-                                      dec.max_seq_length, dev, poll_every)
-            return seqs if n is not None else torch.tensor(seqs, dtype=torch.long, device=dev)
-        if n is None:
-            return beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
-        return beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev)
-
-
-def _beam_nbest(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas,
-                length_penalty):
-    """beam_decode(nbest=True): the routes of beam_decode, each giving its n-best lists."""
-    dev, n_img, T = state[0].device, 1 if n is None else n, dec.max_seq_length + 1
-    nb = dict(nbest=True, length_penalty=length_penalty)
-    maps = None
-    with torch.no_grad():
-        plain = getattr(step_fn, "plain", None) if one_call else None
-        att = getattr(step_fn, "att", None) if one_call else None
-        if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, dec.vocab_size,
-                                                           len(plain.wcat)):
-            lists = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T, start_token,
+        if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, V, len(plain.wcat)):
+            lists = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T + 1, start_token,
                                     end_token, poll_every, **nb)
         elif att is not None:
             lists = _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, **nb)
             if return_alphas:
                 lists, maps = lists
         elif on_device or one_call:
-            lists = beam_search_device(step_fn, state, n_img, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev,
-                                       poll_every, **nb)
-        elif n is None:
-            lists = [[(q[0].tolist(), sc) for q, sc in
-                      beam_search(step_fn, state, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev, **nb)]]
+            lists = beam_search_device(step_fn, state, n_img, V, start_token, end_token, k, T, dev, poll_every, **nb)
+        elif n is not None:
+            lists = beam_search_batched(step_fn, state, n, V, start_token, end_token, k, T, dev, **nb)
+        elif nbest:
+            lists = [[(q[0].tolist(), sc) for q, sc in beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)]]
         else:
-            lists = beam_search_batched(step_fn, state, n, dec.vocab_size, start_token, end_token, k, dec.max_seq_length, dev, **nb)
+            one = beam_search(step_fn, state, V, start_token, end_token, k, T, dev)     # LongTensor [1, L] as it is returned
+            lists = [one[0].tolist()] if return_alphas else None
+    return _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest)
+
+
+def _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest):
+    """What beam_decode returns, from what its route gave. lists: per image its token list, or with nbest its list of
+    (tokens, score) pairs; maps: the one-call search's recording in the same nesting, else None: with return_alphas they
+    come from replay_alphas / _nbest_replay; one: the host loop's tensor of one image, returned as it is. n None: the one
+    image's entry, the tokens as LongTensor [1, L]."""
     if return_alphas and maps is None:
-        maps = _nbest_replay(step_fn, state, lists, k)
+        maps = _nbest_replay(step_fn, state, lists, k) if nbest else replay_alphas(step_fn, state, lists, len(lists), k)
     if n is None:
-        lists, maps = _one_image(lists[0], dev), None if maps is None else maps[0]
+        dev = state[0].device
+        if one is None:
+            one = _one_image(lists[0], dev) if nbest else torch.tensor(lists, dtype=torch.long, device=dev)
+        lists, maps = one, None if maps is None else maps[0]
     return (lists, maps) if return_alphas else lists
 
 

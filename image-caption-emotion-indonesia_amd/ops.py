@@ -628,6 +628,18 @@ def _first_shape(tables):
     return tuple(tables[0].shape) if tables and tables[0] is not None else ()
 
 
+def _group_biases(who, bs, groups, V):
+    """One bias [V] (or None) per group, used where it lies -> the list, or None where `bs` is None."""
+    if bs is None:
+        return None
+    bs = list(bs)
+    if len(bs) != groups:
+        raise CapnetError("%s: one bias (or None) per group" % who)
+    present = [b for b in bs if b is not None]
+    _check_tables(who, present, (V,), len(present))
+    return [None if b is None else b.detach() for b in bs]
+
+
 def _grouped_layer_weights(who, wcat, beff, groups, H, kin0):
     """The layers' weights with their leading [groups] dimension, also for one group."""
     for l, (w, b) in enumerate(zip(wcat, beff)):
@@ -692,13 +704,7 @@ def vocab_argmax_groups(h, ws, bs=None, workspace=None):
     V = ws[0].shape[0]
     if ws[0].shape[1] != H or H not in DECODE_HIDDEN or rows < groups or rows % groups:
         raise CapnetError("%s: h [groups rows, H], w [V, H] per group with H in %r" % (who, DECODE_HIDDEN))
-    if bs is not None:
-        bs = list(bs)
-        present = [b for b in bs if b is not None]
-        if len(bs) != groups:
-            raise CapnetError("%s: one bias (or None) per group" % who)
-        _check_tables(who, present, (V,), len(present))
-        bs = [None if b is None else b.detach() for b in bs]
+    bs = _group_biases(who, bs, groups, V)
     rpg = rows // groups
     if workspace is None:
         workspace = vocab_argmax_groups_workspace(groups, rpg, V, h.device)
@@ -758,10 +764,7 @@ def lstm_greedy_decode(steps, wcat, beff, emb, Cw, Cb, features=None, start_toke
             raise CapnetError("lstm_greedy_decode: start_tokens must be int64 [rows]")
     if not stacked_decode_supported(E, H) or not 1 <= nl <= 8 or len(beff) != nl or tuple(Cw.shape) != (V, H):
         raise CapnetError("lstm_greedy_decode: unsupported shape (E=%d, H=%d, %d layers)" % (E, H, nl))
-    for l, (w, b) in enumerate(zip(wcat, beff)):
-        kin = (E + 15) // 16 * 16 if l == 0 else H
-        if tuple(w.shape) != (4 * H, kin + H) or not w.is_contiguous() or tuple(b.shape) != (4 * H,):
-            raise CapnetError("lstm_greedy_decode: layer %d weights must be [4H, %d] and [4H]" % (l, kin + H))
+    _check_layer_weights("lstm_greedy_decode", wcat, beff, 1, H, (E + 15) // 16 * 16)
     dev = emb.device
     if state is not None:
         state = _c(state.detach())
@@ -993,19 +996,12 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
     Row r draws on stream row r, step t on stream step t. Returns (ids [rows, steps] int64, logp [rows, steps] float32,
     the final state [rows, 2L, H])."""
     who = "sample_decode"
-    if cell not in (CELL_FACTORED, CELL_LSTM):
-        raise CapnetError("%s: unknown cell %r" % (who, cell))
     if (first_inputs is None) == (start_tokens is None):
         raise CapnetError("%s: either first_inputs or start_tokens" % who)
-    if emb.dim() != 2 or Cw.dim() != 2:
-        raise CapnetError("%s: emb [V, E], Cw [V, H]" % who)
-    V, E = emb.shape
+    rows, steps = (first_inputs if first_inputs is not None else start_tokens).shape[0], int(steps)
+    emb, Cw, Cb, state, (V, E, H, nl) = _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, rows)
     temperature, top_k, seed = check_sampling(who, temperature, top_k, seed, V)
-    _need_cuda(emb, Cw, Cb, first_inputs, start_tokens, state, *wcat, *beff)
-    emb, Cw = _c(emb.detach()), _c(Cw.detach())
-    Cb = None if Cb is None else _c(Cb.detach())
-    H, nl, steps = Cw.shape[1], len(wcat), int(steps)
-    rows = (first_inputs if first_inputs is not None else start_tokens).shape[0]
+    _need_cuda(first_inputs, start_tokens)
     if first_inputs is not None:
         first_inputs = _c(first_inputs.detach())
         if tuple(first_inputs.shape) != (rows, E):
@@ -1016,15 +1012,9 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
             raise CapnetError("%s: start_tokens must be int64 [rows]" % who)
     if not 1 <= steps <= SAMPLE_MAX_STEPS or not 1 <= rows < SAMPLE_MAX_ROWS:
         raise CapnetError("%s: steps %d (1..65535), rows %d (1..2^24 - 1)" % (who, steps, rows))
-    if not sample_decode_supported(E, H, V, top_k) or not 1 <= nl <= 8 or len(beff) != nl or tuple(Cw.shape) != (V, H) \
-            or (Cb is not None and Cb.numel() != V):
+    if not sample_decode_supported(E, H, V, top_k):
         raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, top_k=%d)" % (who, E, H, V, nl, top_k))
-    _check_layer_weights(who, wcat, beff, 1, H, (E + 15) // 16 * 16)
     dev = emb.device
-    if state is not None:
-        state = _c(state.detach())
-        if tuple(state.shape) != (rows, 2 * nl, H):
-            raise CapnetError("%s: state must be [rows, 2L, H]" % who)
     L = _lib.lib()
     nbytes = L.capnet_sample_decode_ws_bytes(nl, rows, H, V, top_k)
     if not nbytes:
@@ -1067,13 +1057,7 @@ def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
         raise CapnetError("%s: h [groups rows, H], w [V, H] per group with H in %r" % (who, DECODE_HIDDEN))
     if not 1 <= k <= 16 or k > V:
         raise CapnetError("%s: k=%d (1 <= k <= 16, k <= V = %d)" % (who, k, V))
-    if bs is not None:
-        bs = list(bs)
-        present = [b for b in bs if b is not None]
-        if len(bs) != groups:
-            raise CapnetError("%s: one bias (or None) per group" % who)
-        _check_tables(who, present, (V,), len(present))
-        bs = [None if b is None else b.detach() for b in bs]
+    bs = _group_biases(who, bs, groups, V)
     rpg = rows // groups
     if workspace is None:
         workspace = vocab_topk_groups_workspace(groups, rpg, k, V, h.device)
@@ -1088,9 +1072,101 @@ def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
     return values, index, lse
 
 
-_beam_decode_ws = {}
-_lstm_beam_decode_ws = {}
-_lstm_beam_decode_groups_ws = {}
+# ---- what the one-call searches share: operand check, workspace cache, result buffer, reader, epilogue ----------------------
+_search_ws = {}       # (the C size function's name, device index, its dims) -> the int64 workspace of a one-call search
+
+
+def _search_workspace(size_fn, device, dims, outside):
+    """The cached workspace of a one-call search: one per size function, device and dims, sized by ONE call of
+    capnet_<...>_ws_bytes(*dims) when it is first asked for. A size of 0 raises CapnetError(outside)."""
+    key = (size_fn, torch.device(device).index or 0, tuple(dims))
+    ws = _search_ws.get(key)
+    if ws is None:
+        nbytes = getattr(_lib.lib(), size_fn)(*dims)
+        if not nbytes:
+            raise CapnetError(outside)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+        _search_ws[key] = ws
+    return ws
+
+
+def _tail_words(n):
+    """The int64 words behind the n sequences of a result buffer: n int32 lengths and the int32 error word."""
+    return n // 2 + 1
+
+
+def _result_buffer(n, max_steps, device):
+    """A search's results as ONE int64 buffer, so that they reach the host in one copy: seqs int64 [n, max_steps + 2] |
+    lengths int32 [n] | the error word -> (packed, the address of seqs, the address of lengths)."""
+    SL = max_steps + 2
+    packed = torch.empty(n * SL + _tail_words(n), dtype=torch.int64, device=device)
+    return packed, ptr(packed), C.c_void_p(packed.data_ptr() + 8 * n * SL)
+
+
+def split_result(host, n):
+    """_result_buffer's buffer on the HOST -> (the n token lists, each cut to its length; the lengths; the error word)."""
+    SL = (host.numel() - _tail_words(n)) // n
+    tail = host[n * SL:].view(torch.int32)
+    lens = tail[:n].tolist()
+    rows = host[:n * SL].view(n, SL).tolist()
+    return [rows[i][:lens[i]] for i in range(n)], lens, int(tail[n])
+
+
+def _read_result(packed, flag, n):
+    """_result_buffer's buffer with the device's error word `flag` copied in, in one copy to the host -> (token lists,
+    lengths); a set error word raises (check_device_errors)."""
+    packed[-_tail_words(n):].view(torch.int32)[n:n + 1].copy_(flag)
+    out, lens, word = split_result(packed.cpu(), n)
+    if word:
+        check_device_errors()
+    return out, lens
+
+
+def _search_result(ws, beam_at, packed, flag, n, k, max_steps, steps, return_steps, nbest, length_penalty, alphas=None):
+    """What a one-call search returns once its C call is issued. The token lists (_read_result), or with nbest the lists of
+    (tokens, score) out of the beam state the search left at capnet_beam_decode_ws_beam_offset(*beam_at) of `ws`
+    (_nbest_of_workspace); with return_steps followed by the steps issued; with alphas = (maps [n, max_steps, P], the dims
+    of capnet_att_beam_decode_alphas_ws_*_offset) followed by the maps, cut to len - 1 rows -- per caption, or with nbest
+    per hypothesis. One value comes back bare, several as a tuple."""
+    L = _lib.lib()
+    if nbest:
+        where = None
+        if alphas is not None:
+            maps, dims = alphas
+            where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*dims), L.capnet_att_beam_decode_alphas_ws_hist_offset(*dims),
+                     maps.shape[2])
+        res = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(*beam_at), n, k, max_steps, length_penalty, flag, where)
+        res = res if alphas is not None else (res,)
+    else:
+        out, lens = _read_result(packed, flag, n)
+        res = (out,) if alphas is None else (out, [alphas[0][i, :lens[i] - 1] for i in range(n)])
+    if return_steps:
+        res = (res[0], steps.value) + res[1:]
+    return res if len(res) > 1 else res[0]
+
+
+def _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, rows, groups=1):
+    """The checked operands of a plain stack's one-call decode -> (emb, Cw, Cb, state, (V, E, H, layers)): the cell kind;
+    emb [V, E]; Cw [V, H]; Cb [V] or None; 1 to 8 layers of weights (_check_layer_weights); state [rows, 2L, H] or None.
+    Whether the entry takes E, H and V is its caller's to say."""
+    if cell not in (CELL_FACTORED, CELL_LSTM):
+        raise CapnetError("%s: unknown cell %r" % (who, cell))
+    _need_cuda(emb, Cw, Cb, state, *wcat, *beff)
+    if emb.dim() != 2 or Cw.dim() != 2:
+        raise CapnetError("%s: emb [V, E], Cw [V, H]" % who)
+    emb, Cw = _c(emb.detach()), _c(Cw.detach())
+    Cb = None if Cb is None else _c(Cb.detach())
+    (V, E), H, nl = emb.shape, Cw.shape[1], len(wcat)
+    if not 1 <= nl <= 8 or len(beff) != nl or tuple(Cw.shape) != (V, H):
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, Cw %r)" % (who, E, H, V, nl, tuple(Cw.shape)))
+    if Cb is not None and Cb.numel() != V:
+        raise CapnetError("%s: Cb must be [V]" % who)
+    _check_layer_weights(who, wcat, beff, groups, H, (E + 15) // 16 * 16)
+    if state is not None:
+        state = _c(state.detach())
+        if tuple(state.shape) != (rows, 2 * nl, H):
+            raise CapnetError("%s: state must be [rows, 2L, H] = %r" % (who, (rows, 2 * nl, H)))
+    return emb, Cw, Cb, state, (V, E, H, nl)
 
 
 def beam_decode_supported(E, H, k, V, num_layers):
@@ -1112,62 +1188,33 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     first by score / (len(tokens) - 1)^length_penalty (_nbest_of_workspace: capnet_beam_nbest on the state the search left in
     the workspace); the list is empty where nothing completed. The search itself is the same.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
-    if cell not in (CELL_FACTORED, CELL_LSTM):
-        raise CapnetError("beam_decode: unknown cell %r" % (cell,))
-    length_penalty = check_length_penalty("beam_decode", nbest, length_penalty)
-    groups = _check_groups("beam_decode", groups)
-    _need_cuda(emb, Cw, Cb, state, *wcat, *beff)
-    emb, Cw = _c(emb.detach()), _c(Cw.detach())
-    Cb = None if Cb is None else _c(Cb.detach())
-    V, E = emb.shape
-    H, nl = Cw.shape[1], len(wcat)
-    n, k, T = int(n), int(k), int(max_steps)
-    if n < 1 or T < 1 or len(beff) != nl or tuple(Cw.shape) != (V, H) or not beam_decode_supported(E, H, k, V, nl):
-        raise CapnetError("beam_decode: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
-                          % (E, H, V, k, nl, n, T))
-    if Cb is not None and Cb.numel() != V:
-        raise CapnetError("beam_decode: Cb must be [V]")
-    _check_layer_weights("beam_decode", wcat, beff, groups, H, (E + 15) // 16 * 16)
+    who = "beam_decode"
+    length_penalty = check_length_penalty(who, nbest, length_penalty)
+    groups = _check_groups(who, groups)
+    n_img, k, T = int(n), int(k), int(max_steps)
+    n = groups * n_img             # the beam groups
+    emb, Cw, Cb, state, (V, E, H, nl) = _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, n * k, groups)
+    if n_img < 1 or T < 1 or not beam_decode_supported(E, H, k, V, nl):
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
+                          % (who, E, H, V, k, nl, n_img, T))
     dev = emb.device
-    n_img, n = n, groups * n       # from here on n counts the beam groups
-    if state is not None:
-        state = _c(state.detach())
-        if tuple(state.shape) != (n * k, 2 * nl, H):
-            raise CapnetError("beam_decode: state must be [n k, 2L, H]")
     L = _lib.lib()
-    key = (dev.index or 0, nl, n, k, H, V, T)
-    ws = _beam_decode_ws.get(key)
-    if ws is None:
-        ws = torch.empty((L.capnet_beam_decode_ws_bytes(nl, n, k, H, V, T) + 7) // 8, dtype=torch.int64, device=dev)
-        _beam_decode_ws[key] = ws
+    ws = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T),
+                           "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T))
     slab = splitk_slab(dev)
-    SL = T + 2
-    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
-    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
-    tail = packed[n * SL:].view(torch.int32)
+    packed, seqs, lengths = _result_buffer(n, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
     tail_args = (ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
-                 int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream())
+                 int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
     if groups > 1:
         check(L.capnet_beam_decode_groups(cell, nl, groups, n_img, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode_groups")
     else:
         check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode")
-    if nbest:
-        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n_img, k, H, V, T, 0, groups), n, k, T,
-                                  length_penalty, flag)
-        return (out, steps.value) if return_steps else out
-    tail[n:n + 1].copy_(flag)
-    host = packed.cpu()
-    htail = host[n * SL:].view(torch.int32)
-    if int(htail[n]):
-        check_device_errors()
-    lens = htail[:n].tolist()
-    rows = host[:n * SL].view(n, SL).tolist()
-    out = [rows[i][:lens[i]] for i in range(n)]
-    return (out, steps.value) if return_steps else out
+    return _search_result(ws, (nl, n_img, k, H, V, T, 0, groups), packed, flag, n, k, T, steps, return_steps, nbest,
+                          length_penalty)
 
 
 def lstm_beam_decode_supported(E, H, k, V, num_layers):
@@ -1186,64 +1233,30 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
     the workspace is cached per (device, shape); sequences, lengths and the error word come to the host in one copy.
     nbest / length_penalty: as beam_decode's, on either top-k route.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
-    if cell not in (CELL_FACTORED, CELL_LSTM):
-        raise CapnetError("lstm_beam_decode: unknown cell %r" % (cell,))
-    length_penalty = check_length_penalty("lstm_beam_decode", nbest, length_penalty)
-    _need_cuda(emb, Cw, Cb, state, first_inputs, *wcat, *beff)
-    emb, Cw = _c(emb.detach()), _c(Cw.detach())
-    Cb = None if Cb is None else _c(Cb.detach())
-    V, E = emb.shape
-    H, nl = Cw.shape[1], len(wcat)
+    who = "lstm_beam_decode"
+    length_penalty = check_length_penalty(who, nbest, length_penalty)
     n, k, T, fused = int(n), int(k), int(max_steps), int(bool(fused_topk))
-    if n < 1 or T < 1 or len(beff) != nl or tuple(Cw.shape) != (V, H) or not lstm_beam_decode_supported(E, H, k, V, nl):
-        raise CapnetError("lstm_beam_decode: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
-                          % (E, H, V, k, nl, n, T))
-    if Cb is not None and Cb.numel() != V:
-        raise CapnetError("lstm_beam_decode: Cb must be [V]")
-    _check_layer_weights("lstm_beam_decode", wcat, beff, 1, H, (E + 15) // 16 * 16)
-    dev = emb.device
-    if state is not None:
-        state = _c(state.detach())
-        if tuple(state.shape) != (n * k, 2 * nl, H):
-            raise CapnetError("lstm_beam_decode: state must be [n k, 2L, H]")
+    emb, Cw, Cb, state, (V, E, H, nl) = _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, n * k)
+    if n < 1 or T < 1 or not lstm_beam_decode_supported(E, H, k, V, nl):
+        raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
+                          % (who, E, H, V, k, nl, n, T))
     if first_inputs is not None:
+        _need_cuda(first_inputs)
         first_inputs = _c(first_inputs.detach())
         if tuple(first_inputs.shape) != (n * k, E) or first_inputs.dtype != torch.float32:
-            raise CapnetError("lstm_beam_decode: first_inputs must be float32 [n k, E]")
-    L = _lib.lib()
-    key = (dev.index or 0, nl, n, k, H, V, T, fused)
-    ws = _lstm_beam_decode_ws.get(key)
-    if ws is None:
-        nbytes = L.capnet_lstm_beam_decode_ws_bytes(nl, n, k, H, V, T, fused)
-        if not nbytes:
-            raise CapnetError("lstm_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T))
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        _lstm_beam_decode_ws[key] = ws
+            raise CapnetError("%s: first_inputs must be float32 [n k, E]" % who)
+    dev = emb.device
+    ws = _search_workspace("capnet_lstm_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T, fused),
+                           "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T))
     slab = None if fused else splitk_slab(dev)
-    SL = T + 2
-    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
-    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
-    tail = packed[n * SL:].view(torch.int32)
+    packed, seqs, lengths = _result_buffer(n, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(L.capnet_lstm_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(first_inputs), ptr(emb),
-                                    ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
-                                    0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
-                                    C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
-          "capnet_lstm_beam_decode")
-    if nbest:
-        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, fused, 1), n, k, T, length_penalty,
-                                  flag)
-        return (out, steps.value) if return_steps else out
-    tail[n:n + 1].copy_(flag)
-    host = packed.cpu()
-    htail = host[n * SL:].view(torch.int32)
-    if int(htail[n]):
-        check_device_errors()
-    lens = htail[:n].tolist()
-    rows = host[:n * SL].view(n, SL).tolist()
-    out = [rows[i][:lens[i]] for i in range(n)]
-    return (out, steps.value) if return_steps else out
+    check(_lib.lib().capnet_lstm_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(first_inputs),
+                                             ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws),
+                                             ptr(slab), 0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths,
+                                             C.byref(steps), ptr(flag), current_stream()), "capnet_lstm_beam_decode")
+    return _search_result(ws, (nl, n, k, H, V, T, fused, 1), packed, flag, n, k, T, steps, return_steps, nbest, length_penalty)
 
 
 def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, start_token, end_token, state=None,
@@ -1270,13 +1283,7 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
     V, E = embs[0].shape
     H, nl = Cws[0].shape[1], len(wcat)
     Cws = _check_tables(who, Cws, (V, H), groups)
-    if Cbs is not None:
-        Cbs = list(Cbs)
-        if len(Cbs) != groups:
-            raise CapnetError("%s: one bias (or None) per group" % who)
-        present = [b for b in Cbs if b is not None]
-        _check_tables(who, present, (V,), len(present))
-        Cbs = [None if b is None else b.detach() for b in Cbs]
+    Cbs = _group_biases(who, Cbs, groups, V)
     _need_cuda(state, *wcat, *beff)
     n, k, T, fused = int(n), int(k), int(max_steps), int(bool(fused_topk))
     if n < 1 or T < 1 or len(beff) != nl or not lstm_beam_decode_supported(E, H, k, V, nl):
@@ -1289,41 +1296,19 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
         state = _c(state.detach())
         if tuple(state.shape) != (nq * k, 2 * nl, H):
             raise CapnetError("%s: state must be [groups n k, 2L, H]" % who)
-    L = _lib.lib()
-    key = (dev.index or 0, nl, groups, n, k, H, V, T, fused)
-    ws = _lstm_beam_decode_groups_ws.get(key)
-    if ws is None:
-        nbytes = L.capnet_lstm_beam_decode_groups_ws_bytes(nl, groups, n, k, H, V, T, fused)
-        if not nbytes:
-            raise CapnetError("%s: groups=%d n=%d k=%d V=%d max_steps=%d outside the limits" % (who, groups, n, k, V, T))
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        _lstm_beam_decode_groups_ws[key] = ws
+    ws = _search_workspace("capnet_lstm_beam_decode_groups_ws_bytes", dev, (nl, groups, n, k, H, V, T, fused),
+                           "%s: groups=%d n=%d k=%d V=%d max_steps=%d outside the limits" % (who, groups, n, k, V, T))
     slab = None if fused else splitk_slab(dev)
-    SL = T + 2
-    # seqs int64 [nq, SL] | lengths int32 [nq] | the error word: one buffer, one copy
-    packed = torch.empty(nq * SL + nq // 2 + 1, dtype=torch.int64, device=dev)
-    tail = packed[nq * SL:].view(torch.int32)
+    packed, seqs, lengths = _result_buffer(nq, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(L.capnet_lstm_beam_decode_groups(cell, nl, groups, n, k, E, H, V, T, int(start_token), int(end_token), ptr_array(embs),
-                                           ptr_array(wcat), ptr_array(beff), ptr_array(Cws),
-                                           None if Cbs is None else ptr_array(Cbs), ptr(state), ptr(ws), ptr(slab),
-                                           0 if slab is None else slab.numel(), fused, int(poll_every), ptr(packed),
-                                           C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream()),
-          "capnet_lstm_beam_decode_groups")
-    if nbest:
-        out = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, fused, groups), nq, k, T,
-                                  length_penalty, flag)
-        return (out, steps.value) if return_steps else out
-    tail[nq:nq + 1].copy_(flag)
-    host = packed.cpu()
-    htail = host[nq * SL:].view(torch.int32)
-    if int(htail[nq]):
-        check_device_errors()
-    lens = htail[:nq].tolist()
-    rows = host[:nq * SL].view(nq, SL).tolist()
-    out = [rows[i][:lens[i]] for i in range(nq)]
-    return (out, steps.value) if return_steps else out
+    check(_lib.lib().capnet_lstm_beam_decode_groups(
+        cell, nl, groups, n, k, E, H, V, T, int(start_token), int(end_token), ptr_array(embs), ptr_array(wcat), ptr_array(beff),
+        ptr_array(Cws), None if Cbs is None else ptr_array(Cbs), ptr(state), ptr(ws), ptr(slab),
+        0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream()),
+        "capnet_lstm_beam_decode_groups")
+    return _search_result(ws, (nl, n, k, H, V, T, fused, groups), packed, flag, nq, k, T, steps, return_steps, nbest,
+                          length_penalty)
 
 
 def att_decode_supported(E, Cdim, H, A, P, k, num_layers):
@@ -1408,10 +1393,6 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
     return top, out
 
 
-_att_beam_decode_ws = {}
-_att_beam_decode_alphas_ws = {}
-
-
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
                     end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False, nbest=False,
                     length_penalty=0.0):
@@ -1443,53 +1424,28 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     dev = emb.device
     L = _lib.lib()
     n_img, n = n, groups * n       # from here on n counts the beam groups
-    key = (dev.index or 0, nl, n, k, P, A, Cdim, E, H, V, T)
-    cache = _att_beam_decode_alphas_ws if return_alphas else _att_beam_decode_ws
-    ws = cache.get(key)
-    if ws is None:
-        nbytes = L.capnet_att_beam_decode_alphas_ws_bytes(nl, groups, n_img, k, P, A, Cdim, E, H, V, T) if return_alphas else \
-            L.capnet_att_beam_decode_ws_bytes(nl, n, k, P, A, Cdim, E, H, V, T)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        cache[key] = ws
+    outside = "att_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T)
+    alpha_dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
+    if return_alphas:
+        ws = _search_workspace("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, outside)
+    else:
+        ws = _search_workspace("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), outside)
     slab = splitk_slab(dev)
-    SL = T + 2
-    # seqs int64 [n, SL] | lengths int32 [n] | the error word: one buffer, one copy
-    packed = torch.empty(n * SL + n // 2 + 1, dtype=torch.int64, device=dev)
-    tail = packed[n * SL:].view(torch.int32)
+    packed, seqs, lengths = _result_buffer(n, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
     args = (n_img, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz),
             ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
-            int(poll_every), ptr(packed), C.c_void_p(tail.data_ptr()), C.byref(steps), ptr(flag), current_stream())
-    maps = None
+            int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
+    alphas = None
     if return_alphas:
-        maps = torch.empty((n, T, P), dtype=torch.float32, device=dev)
-        check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(maps)), "capnet_att_beam_decode_alphas")
+        alphas = (torch.empty((n, T, P), dtype=torch.float32, device=dev), alpha_dims)
+        check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(alphas[0])), "capnet_att_beam_decode_alphas")
     elif groups > 1:
         check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
     else:
         check(L.capnet_att_beam_decode(cell, nl, *args), "capnet_att_beam_decode")
-    if nbest:
-        dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
-        where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*dims), L.capnet_att_beam_decode_alphas_ws_hist_offset(*dims),
-                 P) if return_alphas else None
-        res = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(nl, n, k, H, V, T, 0, 1), n, k, T, length_penalty, flag,
-                                  where)
-        res = res if return_alphas else (res,)
-        res = (res[0], steps.value) + res[1:] if return_steps else res
-        return res if len(res) > 1 else res[0]
-    tail[n:n + 1].copy_(flag)
-    host = packed.cpu()
-    htail = host[n * SL:].view(torch.int32)
-    if int(htail[n]):
-        check_device_errors()
-    lens = htail[:n].tolist()
-    rows = host[:n * SL].view(n, SL).tolist()
-    out = [rows[i][:lens[i]] for i in range(n)]
-    res = (out, steps.value) if return_steps else (out,)
-    if return_alphas:
-        res += ([maps[i, :lens[i] - 1] for i in range(n)],)
-    return res if len(res) > 1 else out
+    return _search_result(ws, (nl, n, k, H, V, T, 0, 1), packed, flag, n, k, T, steps, return_steps, nbest, length_penalty, alphas)
 
 
 def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,

@@ -79,6 +79,14 @@ FUSED_TOPK_GROUPS_MAX_ROWS = 15
 _EMOTIONS = ("happy", "sad", "angry")
 
 
+def _fused_topk(fused_topk, rows, max_rows):
+    """Whether a beam search of `rows` rows takes the fused top-k step now: never under CAPNET_NO_FUSED_TOPK=1 (read here, at
+    every call); else as fused_topk says, None meaning up to `max_rows` rows."""
+    if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
+        return False
+    return rows <= max_rows if fused_topk is None else bool(fused_topk)
+
+
 class LSTM(nn.Module):
     """nn.LSTM(input_size, hidden_size, num_layers) parameter container: weight_ih_l{k} [4H, in], weight_hh_l{k} [4H, H],
     bias_ih_l{k}, bias_hh_l{k} [4H] per layer, gate order i, f, g, o, every tensor U(-1/sqrt(H), 1/sqrt(H))."""
@@ -247,12 +255,7 @@ class _RNN(nn.Module):
             state = state.detach().repeat_interleave(k, 0).contiguous()
             first = None if features is None else features.detach().float().repeat_interleave(k, 0).contiguous()
             if fused_decode_step(L, E, H) and ops.lstm_beam_decode_supported(E, H, k, V, L):
-                if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
-                    fused = False
-                elif fused_topk is None:
-                    fused = B * k <= FUSED_TOPK_MAX_ROWS
-                else:
-                    fused = bool(fused_topk)
+                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_MAX_ROWS)
                 packed = pack_cells(layers, E)
                 return ops.lstm_beam_decode(ops.CELL_LSTM, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb, B, k,
                                             self.max_seq_length + 1, start_token, end_token, first_inputs=first, state=state,
@@ -328,6 +331,16 @@ class EncoderRNN(_RNN):
 class DecoderRNN(_RNN):
     """seq2seq/model.py:125-217."""
 
+    def _start(self, start_token, states):
+        """(start_token once per row -- None for None --, the state [rows, 2L, H]) of `states` (h, c) [num_layers, rows, H]:
+        either may be None for zeros, both for one row of them."""
+        h, c = states
+        given = h if h is not None else c
+        rows = 1 if given is None else given.size(1)
+        dev = self.embed.weight.device
+        state = self._rows_state(states, rows, dev)
+        return None if start_token is None else torch.full((rows,), int(start_token), dtype=torch.int64, device=dev), state
+
     def forward(self, states, dst_tokens, lengths, teacher_forcing_ratio=0.5):
         """Packed logits [N, V] of dst_tokens (no feature column). `states` is IGNORED and every layer starts at zero,
         as in the reference (seq2seq/model.py:169-172): the encoder's state reaches the decoders in sample() only."""
@@ -337,13 +350,7 @@ class DecoderRNN(_RNN):
         """Greedy from embed(start_token) and `states` (h, c) [num_layers, B, H] -> ids [B, max_seq_length] int64. The
         start token is broadcast to the states' batch (the reference's own sample only works for B = 1, where the two
         agree). An out-of-range start_token raises CapnetError through the device error word."""
-        h, c = states
-        given = h if h is not None else c
-        rows = 1 if given is None else given.size(1)
-        dev = self.embed.weight.device
-        zeros = torch.zeros((self.num_layers, rows, self.hidden_size), dtype=torch.float32, device=dev)
-        state = _to_rows(zeros if h is None else h, zeros if c is None else c)
-        tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
+        tokens, state = self._start(start_token, states)
         ids, _ = self._greedy(None, tokens, state)
         ops.check_device_errors()
         return ids
@@ -352,12 +359,7 @@ class DecoderRNN(_RNN):
         """sample() with every word drawn (EncoderRNN.sample_random): from embed(start_token) and `states` (h, c)
         [num_layers, B, H] -> (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32). An out-of-range
         start_token raises CapnetError through the device error word."""
-        h, c = states
-        given = h if h is not None else c
-        rows = 1 if given is None else given.size(1)
-        dev = self.embed.weight.device
-        state = self._rows_state(states, rows, dev)
-        tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
+        tokens, state = self._start(start_token, states)
         ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed)
         ops.check_device_errors()
         return ids, logp
@@ -369,11 +371,25 @@ class DecoderRNN(_RNN):
         EncoderRNN.sample_beam. An out-of-range start_token raises CapnetError through the device error word.
         nbest / length_penalty: per sentence the list of (tokens, score) of every completed hypothesis, best first by score /
         (len(tokens) - 1)^length_penalty; empty where nothing completed."""
-        h, c = states
-        given = h if h is not None else c
-        rows = 1 if given is None else given.size(1)
-        state = self._rows_state(states, rows, self.embed.weight.device)
+        _, state = self._start(None, states)
         return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty)
+
+
+def _groupable(decoders):
+    """Whether `decoders` can share a grouped call: 2 to ops.MAX_GROUPS of them, of equal shapes."""
+    shapes = {(x.embed_size, x.hidden_size, x.vocab_size, x.num_layers, x.max_seq_length) for x in decoders}
+    return 2 <= len(decoders) <= ops.MAX_GROUPS and len(shapes) == 1
+
+
+def _grouped_weights(decoders):
+    """(wcat, beff, embs, Cws, Cbs) of equal-shaped decoders as the grouped calls take them: per layer pack_cell of every
+    decoder stacked ([groups, 4H, kin_l + H], [groups, 4H]); per decoder its embedding, projection and bias where they lie."""
+    d = decoders[0]
+    packed = [pack_cells(x._layers(), d.embed_size) for x in decoders]
+    return ([torch.stack([p[l][0] for p in packed]) for l in range(d.num_layers)],
+            [torch.stack([p[l][1] for p in packed]) for l in range(d.num_layers)],
+            [x.embed.weight.detach() for x in decoders], [x.linear.weight.detach() for x in decoders],
+            [x.linear.bias.detach() for x in decoders])
 
 
 class Seq2Seq(nn.Module):
@@ -443,9 +459,7 @@ class Seq2Seq(nn.Module):
     def _grouped_greedy_ok(self, decoders, rows):
         """Whether `decoders` decode `rows` rows each in one grouped call now (CAPNET_NO_FUSED_GREEDY is read here)."""
         d = decoders[0]
-        same = all((x.embed_size, x.hidden_size, x.vocab_size, x.num_layers, x.max_seq_length) ==
-                   (d.embed_size, d.hidden_size, d.vocab_size, d.num_layers, d.max_seq_length) for x in decoders)
-        return (same and 2 <= len(decoders) <= ops.MAX_GROUPS and os.environ.get(FUSED_GREEDY_OFF, "")[:1] != "1"
+        return (_groupable(decoders) and os.environ.get(FUSED_GREEDY_OFF, "")[:1] != "1"
                 and ops.stacked_decode_supported(d.embed_size, d.hidden_size) and rows <= FUSED_GREEDY_MAX_ROWS)
 
     def sample_styles(self, features, start_token, states=(None, None), modes=('factual', 'happy', 'sad', 'angry')):
@@ -464,14 +478,10 @@ class Seq2Seq(nn.Module):
         if decoders and self._grouped_greedy_ok(decoders, rows):
             d, G = decoders[0], len(decoders)
             with torch.no_grad():
-                packed = [pack_cells(x._layers(), d.embed_size) for x in decoders]
-                wcat = [torch.stack([p[l][0] for p in packed]) for l in range(d.num_layers)]
-                beff = [torch.stack([p[l][1] for p in packed]) for l in range(d.num_layers)]
+                weights = _grouped_weights(decoders)
                 state = _to_rows(h, c).repeat(G, 1, 1)
                 tokens = torch.full((G * rows,), int(start_token), dtype=torch.int64, device=h.device)
-                ids, _ = ops.lstm_greedy_decode_groups(
-                    d.max_seq_length, wcat, beff, [x.embed.weight.detach() for x in decoders],
-                    [x.linear.weight.detach() for x in decoders], [x.linear.bias.detach() for x in decoders], tokens, state)
+                ids, _ = ops.lstm_greedy_decode_groups(d.max_seq_length, *weights, tokens, state)
             ops.check_device_errors()
             for g, m in enumerate(emotions):
                 out[m] = ids[g * rows:(g + 1) * rows]
@@ -483,9 +493,7 @@ class Seq2Seq(nn.Module):
     def _grouped_beam_ok(self, decoders, k):
         """Whether `decoders` search in one grouped call now (CAPNET_NO_FUSED_DECODE_STEP is read here)."""
         d = decoders[0]
-        same = all((x.embed_size, x.hidden_size, x.vocab_size, x.num_layers, x.max_seq_length) ==
-                   (d.embed_size, d.hidden_size, d.vocab_size, d.num_layers, d.max_seq_length) for x in decoders)
-        return (same and 2 <= len(decoders) <= ops.MAX_GROUPS and fused_decode_step(d.num_layers, d.embed_size, d.hidden_size)
+        return (_groupable(decoders) and fused_decode_step(d.num_layers, d.embed_size, d.hidden_size)
                 and ops.lstm_beam_decode_supported(d.embed_size, d.hidden_size, k, d.vocab_size, d.num_layers))
 
     def sample_beam_styles(self, features, start_token, end_token, states=(None, None),
@@ -519,22 +527,13 @@ class Seq2Seq(nn.Module):
             if not 1 <= k <= 16 or k > d.vocab_size:
                 raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, d.vocab_size))
             if self._grouped_beam_ok(decoders, k):
-                if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
-                    fused = False
-                elif fused_topk is None:
-                    fused = B * k <= FUSED_TOPK_GROUPS_MAX_ROWS
-                else:
-                    fused = bool(fused_topk)
+                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_GROUPS_MAX_ROWS)
                 with torch.no_grad():
-                    packed = [pack_cells(x._layers(), d.embed_size) for x in decoders]
-                    wcat = [torch.stack([p[l][0] for p in packed]) for l in range(d.num_layers)]
-                    beff = [torch.stack([p[l][1] for p in packed]) for l in range(d.num_layers)]
+                    weights = _grouped_weights(decoders)
                     state = _to_rows(h, c).repeat(G, 1, 1).repeat_interleave(k, 0).contiguous()
                     lists = ops.lstm_beam_decode_groups(
-                        ops.CELL_LSTM, wcat, beff, [x.embed.weight.detach() for x in decoders],
-                        [x.linear.weight.detach() for x in decoders], [x.linear.bias.detach() for x in decoders], B, k,
-                        d.max_seq_length + 1, start_token, end_token, state=state, fused_topk=fused, poll_every=poll_every,
-                        nbest=nbest, length_penalty=length_penalty)
+                        ops.CELL_LSTM, *weights, B, k, d.max_seq_length + 1, start_token, end_token, state=state,
+                        fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty)
                 ops.check_device_errors()
                 for g, m in enumerate(emotions):
                     out[m] = lists[g * B:(g + 1) * B]

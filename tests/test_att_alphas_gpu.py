@@ -334,10 +334,13 @@ def test_two_calls_on_one_workspace_give_equal_results(dev, monkeypatch):
     feats, end, kw = family.features().to(dev), family.end, family.kw
     a = dec.sample_batch(feats, START, end, k=5, one_call=True, return_alphas=True, **kw)
     other = dec.sample_batch(feats.flip(0).contiguous(), START, end, k=5, one_call=True, return_alphas=True, **kw)   # same shape: same workspace
-    assert len(ops._att_beam_decode_alphas_ws) >= 1
-    n_ws = len(ops._att_beam_decode_alphas_ws)
+
+    def alpha_workspaces():         # the unified cache's entries of this size function
+        return [key for key in ops._search_ws if key[0] == "capnet_att_beam_decode_alphas_ws_bytes"]
+    assert len(alpha_workspaces()) >= 1
+    n_ws = len(alpha_workspaces())
     b = dec.sample_batch(feats, START, end, k=5, one_call=True, return_alphas=True, **kw)
-    assert len(ops._att_beam_decode_alphas_ws) == n_ws
+    assert len(alpha_workspaces()) == n_ws
     assert a[0] == b[0] and all(torch.equal(x, y) for x, y in zip(a[1], b[1]))
     assert other[0] == a[0][::-1]
     assert capnet.lib().capnet_att_beam_decode_alphas_ws_bytes(2, 1, IMAGES, 5, 5, 20, 2048, 12, 64, 97, MAX_LEN + 1) > 0
