@@ -70,5 +70,6 @@ LaunchEvents& launch_events();     // thread-local
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 static inline bool aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
+static inline size_t align16(size_t n) { return (n + 15) / 16 * 16; }   // the parts of a workspace start 16-B aligned
 
 }  // namespace capnet

@@ -296,7 +296,7 @@ int att_decode_step(int cell, int nlayers, int n, int k, int P, int A, int C, in
 // layers' weights with a leading groups dimension; ws: att_decode_step_ws_bytes at groups x n)
 
 // vocab_argmax.hip: tok[r] = first argmax_v (h[r] . W[v] + b[v]) in one launch, no logits in memory (ws: vocab_argmax_ws_bytes,
-// its first 16 bytes zero before the first use); and capnet.seq2seq's greedy `sample` as one chain of launches
+// its first 16 bytes zero before the first use)
 bool vocab_argmax_supported(int H);
 size_t vocab_argmax_ws_bytes(int rows, int V);
 int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H, int V, void* ws, long long* tok,
@@ -307,6 +307,7 @@ int vocab_argmax(const float* h, const float* w, const float* b, int rows, int H
 size_t vocab_argmax_groups_ws_bytes(int groups, int rpg, int V);
 int vocab_argmax_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V,
                         void* ws, long long* tok, long long* ids, long ld_ids, hipStream_t stream);
+// decode_loops.hip: capnet.seq2seq's greedy `sample` as one chain of launches (per step the decode step and vocab_argmax)
 size_t lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V);
 size_t lstm_greedy_decode_groups_ws_bytes(int nlayers, int groups, int rpg, int H, int V);
 int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, int V, int steps, const float* features,
@@ -319,8 +320,9 @@ int lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, co
                        const long long* start_tokens, const float* emb, const float* const* wcat,
                        const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws,
                        long long* ids, float* state_out, int* err_flag, hipStream_t s);
-// ... and the beam search of a plain stack as one chain of launches: per step the gathered decode step, the vocabulary
-// projection (sgemm_splitk on the caller's slab) and beam_advance; poll_every > 0 reads live_total after every such step
+// decode_loops.hip: the beam search of a plain stack as one chain of launches: per step the gathered decode step, the
+// vocabulary projection (sgemm_splitk on the caller's slab) and beam_advance; poll_every > 0 reads live_total after every
+// such step
 size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps);
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
@@ -354,7 +356,8 @@ int sample_pick(const float* values, const int* index, int rows, int k, int V, f
                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
 int sample_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, unsigned long long seed, unsigned step,
                 unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
-// lstm_greedy_decode's loop with the draw in place of the argmax (top_k == 0: vocab_sample; else vocab_topk + sample_pick)
+// decode_loops.hip: lstm_greedy_decode's loop with the draw in place of the argmax (top_k == 0: vocab_sample; else vocab_topk
+// + sample_pick)
 size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
 int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
                   const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
@@ -368,8 +371,9 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
                       const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
                       void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                       hipStream_t s);
-// beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set; fused_topk: a step's
-// projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else beam_decode's
+// decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
+// fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
+// beam_decode's
 size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
 int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                      long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,

@@ -1,4 +1,4 @@
-// What the per-time-step kernels share (lstm_step.hip, lstm_upper_step.hip, lstm_decode_step.hip, vocab_argmax.hip, the
+// What the per-time-step kernels share (lstm_step.hip, lstm_upper_step.hip, lstm_decode_step.hip, vocab_core.h, the
 // gate kernel of seq_kernels.hip): the 16-row product on v_mfma_f32_16x16x4_f32, the LSTM cell, the supported hidden sizes.
 // The 16-row product: a workgroup owns a 16-column N tile (4 hidden units x 4 gate roles, or 16 vocabulary entries) and
 // walks the rows 16 at a time; its waves split K and each holds a K-partial 16x16 tile.

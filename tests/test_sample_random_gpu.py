@@ -13,6 +13,7 @@ import torch
 import sample_random_cases as C
 import sample_random_ref as R
 import seq2seq_cases as SC
+import vocab_edge_cases as VC
 from capnet import decode, ops
 from capnet.decode import FUSED_DECODE_OFF, FUSED_SAMPLE_OFF
 from capnet.seq2seq import Seq2Seq
@@ -88,6 +89,17 @@ def test_vocab_sample_row0_and_counter_rearm(dev, H, V):
         f, lf = ops.vocab_sample(hd, Wd, bd, temperature=1.0, seed=s, step=s)
         assert torch.equal(a, f) and torch.equal(la, lf)
     assert len({tuple(a.tolist()) for a, _ in outs}) > 1
+
+
+@pytest.mark.parametrize("case", VC.SAMPLE, ids=VC.case_id)
+def test_vocab_sample_edges_of_the_shared_front(dev, case):
+    """258 workgroups (the second pass of the last arriver's loops: winners and a fifth of the sum lie there) and one
+    workgroup (the only arriver is the last): tests/vocab_edge_cases.py, _check's rule."""
+    h, W, b, z = VC.sample_inputs(*case)
+    hd, Wd, bd = h.to(dev), W.to(dev), b.to(dev)
+    for T, inv_T, seed, step in VC.sample_launches(*case):
+        tok, lp = ops.vocab_sample(hd, Wd, bd, temperature=T, seed=seed, step=step)
+        _check(tok, lp, R.draw(z, inv_T, seed, step), inv_T, what=(case, T, step))
 
 
 def test_vocab_sample_never_draws_nan_or_minus_inf(dev):

@@ -82,6 +82,17 @@ def test_vocab_topk_against_fp64(dev, H, V, bias):
                 _check_topk(dev, h, w, b, k, logits)
 
 
+@pytest.mark.parametrize("rows", [1, 17])
+def test_vocab_topk_one_workgroup(dev, rows):
+    """V = 32: one workgroup, the last arriver is the only arriver and merges its own lists."""
+    for bias in (True, False):
+        for place in ("one-workgroup", "last-columns", "ends"):
+            h, w, b = _topk_inputs(64, 32, rows, bias, place, seed=6400 + 32 + rows)
+            logits = _fp64(h, w, b)
+            for k in TOPK_KS:
+                _check_topk(dev, h, w, b, k, logits)
+
+
 def test_vocab_topk_tie_goes_to_the_lower_index(dev):
     h, w, b = _topk_inputs(64, 37, 5, True, "ends", seed=1)
     free = [c for c in range(37) if float(b[c]) < 1.0]          # not a lifted column

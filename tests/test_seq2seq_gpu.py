@@ -14,6 +14,7 @@ import torch.nn.functional as Fn
 
 import seq2seq_cases as SC
 import seq2seq_ref as SR
+import vocab_edge_cases as VC
 from capnet import CapnetError, ops
 from capnet.nic_model import DecoderRNN as NicDecoderRNN
 from capnet.optim import Adam
@@ -260,6 +261,23 @@ def test_vocab_argmax_ties_and_counter_rearm(dev):
     for x, o in zip(hs, outs):
         assert torch.equal(o, ops.vocab_argmax(x, Wr))
         assert torch.equal(o.cpu(), (x.double().cpu() @ Wr.double().cpu().t()).argmax(1))
+
+
+@pytest.mark.parametrize("case", VC.ARGMAX, ids=VC.case_id)
+def test_vocab_argmax_edges_of_the_shared_front(dev, case):
+    """258 workgroups (the second pass of the last arriver's loop), one workgroup (the only arriver is the last), and the
+    one-row-tile instantiation of H = 1024 with one group and two: tests/vocab_edge_cases.py, the rule above."""
+    name, H, V, rows, groups = case
+    h, Ws, bs, logits = VC.argmax_inputs(*case)
+    hd, Wd, bd = h.to(dev), [W.to(dev) for W in Ws], [b.to(dev) for b in bs]
+    alone = [ops.vocab_argmax(hd[i * rows:(i + 1) * rows], Wd[i], bd[i]) for i in range(groups)]
+    for i, z in enumerate(logits):
+        clear = VC.argmax_clear(z)
+        assert clear.sum() >= rows - 1
+        assert alone[i].dtype == torch.int64 and tuple(alone[i].shape) == (rows,)
+        assert torch.equal(alone[i].cpu()[clear], z.argmax(1)[clear]), i
+    if groups > 1:
+        assert torch.equal(ops.vocab_argmax_groups(hd, Wd, bd), torch.cat(alone))
 
 
 # ---- 10. sample -----------------------------------------------------------------------------------------------------------
