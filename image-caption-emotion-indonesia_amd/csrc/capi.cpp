@@ -665,6 +665,72 @@ int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, i
                        top_k, seed, workspace, ids, logp, state_out, err_flag, S(stream));
 }
 
+// ---- nucleus (top-p) sampling (vocab_nucleus.hip) ----
+// top_p == 1 is "off": the stand-alone draws forward to the plain ones, the loops leave it to the plain loops
+static int top_p_check(const char* who, float top_p, bool allow_one) {
+  CAPNET_REQUIRE(top_p > 0.f && (top_p < 1.f || (allow_one && top_p == 1.f)), "%s: top_p %g (0 < top_p %s 1)", who, (double)top_p,
+                 allow_one ? "<=" : "<");
+  return kOk;
+}
+
+int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p, unsigned long long seed,
+                        unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+  if (int rc = top_p_check("nucleus_rows", top_p, true)) return rc;
+  if (top_p == 1.f) return capnet_sample_rows(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream);
+  float inv_T = 0.f;
+  if (int rc = sample_check("nucleus_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(ld >= V, "nucleus_rows: ld %ld < V %d", ld, V);
+  CAPNET_REQUIRE(logits && tokens && logp, "nucleus_rows: null argument");
+  CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "nucleus_rows: alignment");
+  return nucleus_rows(logits, rows, ld, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+}
+
+int capnet_nucleus_pick(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                        unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                        capnet_stream_t stream) {
+  if (int rc = top_p_check("nucleus_pick", top_p, true)) return rc;
+  if (top_p == 1.f) return capnet_sample_pick(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream);
+  float inv_T = 0.f;
+  if (int rc = sample_check("nucleus_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(k >= 1 && k <= 16, "nucleus_pick: k=%d (1 <= k <= 16)", k);
+  CAPNET_REQUIRE(values && index && tokens && logp, "nucleus_pick: null argument");
+  CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
+                 "nucleus_pick: alignment");
+  return nucleus_pick(values, index, rows, k, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+}
+
+size_t capnet_sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
+  if (!capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k)) return 0;
+  return sample_decode_nucleus_ws_bytes(nlayers, rows, H, V, top_k);
+}
+
+int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                 const long long* start_tokens, const float* emb, const float* const* wcat,
+                                 const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                 float temperature, int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
+                                 size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                                 capnet_stream_t stream) {
+  const char* who = "sample_decode_nucleus";
+  float inv_T = 0.f;
+  if (int rc = top_p_check(who, top_p, false)) return rc;
+  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "%s: steps %d (1..65535)", who, steps);
+  if (int rc = sample_check(who, rows, V, temperature, 0, 0, &inv_T)) return rc;
+  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "%s: unknown cell %d", who, cell);
+  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "%s: layers %d (1..8)", who, nlayers);
+  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "%s: top_k=%d (0 = off, 1 .. 16, <= V = %d)", who, top_k, V);
+  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_sample_supported(H), "%s: unsupported E=%d H=%d", who, E, H);
+  CAPNET_REQUIRE((first_inputs != nullptr) != (start_tokens != nullptr), "%s: the first input is either first_inputs or start_tokens",
+                 who);
+  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && logp && err_flag, "%s: null argument", who);
+  CAPNET_REQUIRE(top_k > 0 || (slab && aligned16(slab) && slab_floats > 0), "%s: the split-K slab (16-B aligned) is required", who);
+  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!state_out || aligned16(state_out)),
+                 "%s: workspace, Cw and the states must be 16-B aligned", who);
+  CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
+  if (int rc = layer_weights_check(who, nlayers, wcat, beff)) return rc;
+  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
+                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream));
+}
+
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
   return vocab_topk_groups_ws_bytes(groups, rows_per_group, k, V);
 }
@@ -887,6 +953,37 @@ int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, 
   return att_sample_decode(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
                            beff, Cw, Cb, state0, inv_T, top_k, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag,
                            S(stream));
+}
+
+size_t capnet_att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
+  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
+  return att_sample_decode_nucleus_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
+}
+
+int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                     const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                     const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                     const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                     const float* state0, float temperature, int top_k, float top_p, unsigned long long seed,
+                                     void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                     float* state_out, int* err_flag, capnet_stream_t stream) {
+  const char* who = "att_sample_decode_nucleus";
+  if (int rc = att_decode_check(who, cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
+                                workspace, slab, slab_floats, err_flag))
+    return rc;
+  float inv_T = 0.f;
+  if (int rc = top_p_check(who, top_p, false)) return rc;
+  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "%s: steps %d (1..65535)", who, steps);
+  if (int rc = sample_check(who, n * m, V, temperature, 0, 0, &inv_T)) return rc;
+  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "%s: top_k=%d (0 = off, 1 .. 16, <= V = %d)", who, top_k, V);
+  CAPNET_REQUIRE(vocab_sample_supported(H), "%s: unsupported H=%d", who, H);
+  CAPNET_REQUIRE(start_tokens && Cw && state0 && ids && logp, "%s: null argument (state0 is required)", who);
+  CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0) && (!state_out || aligned16(state_out)),
+                 "%s: Cw and the states must be 16-B aligned", who);
+  CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
+  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full,
+                                   wcat, beff, Cw, Cb, state0, inv_T, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
+                                   state_out, err_flag, S(stream));
 }
 
 size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,

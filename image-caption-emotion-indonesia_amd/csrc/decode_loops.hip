@@ -1,10 +1,11 @@
 // The one-call decodes: the host loops that chain a decode step and a vocabulary kernel per step, their workspace
 // layouts, and the gather of the attention maps. No loop reads the device except the beam search's optional poll.
 //   token loops: the greedy `sample` of capnet.seq2seq (seq2seq/model.py:100-122, 193-217; capnet_lstm_greedy_decode and
-//                its _groups form) and sampled decoding (capnet_sample_decode, capnet_att_sample_decode)
+//                its _groups form) and sampled decoding (capnet_sample_decode, capnet_att_sample_decode and their _nucleus
+//                forms)
 //   beam loops:  beam_decode, lstm_beam_decode, lstm_beam_decode_groups, att_beam_decode
 // The kernels they launch: lstm_decode_step.hip, att_kernels.hip, vocab_argmax.hip, vocab_topk.hip, vocab_sample.hip,
-// seq_kernels.hip (beam_advance), gemm_f32.hip.
+// vocab_nucleus.hip, seq_kernels.hip (beam_advance), gemm_f32.hip.
 #include "common.h"
 #include "kernels.h"
 
@@ -13,7 +14,8 @@ namespace capnet {
 // ---- the token loops: steps x (the decode step: one launch per layer + the draw: the step's token per row) ----------------
 // ws: [state A | state B] ([rows][2L][H] each) | h_top [rows][H] | tok int64 [rows] | top_k > 0 only: values f32 [rows][k] |
 // index int32 [rows][k] | lse f32 [rows] | the draw's workspace (vocab_argmax's, vocab_sample's or vocab_topk's: its
-// arrival counters first); every part starts 16-B aligned
+// arrival counters first; the nucleus draw without top_k: the step's logits f32 [rows][V], no counter); every part starts
+// 16-B aligned
 struct TokenDecodeWs {
   size_t state, h_top, tok, tk_values, tk_index, tk_lse, draw;   // byte offsets (state B at state + h_top / 2)
 };
@@ -46,7 +48,7 @@ static int token_loop(const TokenDecodeWs& w, int nlayers, int rows, int H, int 
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
   else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
   if (start_tokens) CAPNET_HIP_CHECK(hipMemcpyAsync(tok, start_tokens, (size_t)rows * 8, hipMemcpyDeviceToDevice, s));
-  CAPNET_HIP_CHECK(hipMemsetAsync(p + w.draw, 0, 16 * (size_t)counters, s));
+  if (counters) CAPNET_HIP_CHECK(hipMemsetAsync(p + w.draw, 0, 16 * (size_t)counters, s));
   for (int t = 0; t < steps; ++t) {
     int rc = step_fn(t, tok, state[t & 1], state[(t + 1) & 1], h_top);
     if (rc == kOk) rc = draw_fn(t, h_top, tok);
@@ -93,54 +95,108 @@ int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, in
       });
 }
 
-// ---- the sampling loops: the draw is vocab_sample (top_k == 0) or vocab_topk + sample_pick (top_k > 0) ----
-size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
-  const size_t draw = top_k == 0 ? vocab_sample_ws_bytes(rows, V) : vocab_topk_ws_bytes(rows, top_k, V);
+// ---- the sampling loops: the draw is vocab_sample (top_k == 0) or vocab_topk + sample_pick (top_k > 0); with a nucleus
+// (top_p < 1) the projection into the workspace's logits block (sgemm_splitk, the product of the composed route's ops.linear:
+// the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": today's launches, not a nucleus ----
+static size_t sample_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus) {
+  const size_t draw = top_k > 0 ? vocab_topk_ws_bytes(rows, top_k, V)
+                      : nucleus ? align16((size_t)rows * V * sizeof(float)) : vocab_sample_ws_bytes(rows, V);
   return draw ? token_decode_layout(nlayers, rows, H, top_k).draw + draw : 0;
+}
+
+size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
+  return sample_ws_bytes(nlayers, rows, H, V, top_k, false);
+}
+
+size_t sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
+  return sample_ws_bytes(nlayers, rows, H, V, top_k, true);
 }
 
 template <class Step>
 static int sample_loop(int nlayers, int rows, int H, int V, int steps, const long long* start_tokens, const float* Cw,
-                       const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
-                       long long* ids, float* logp, float* state_out, hipStream_t s, Step&& step_fn) {
+                       const float* Cb, const float* state0, float inv_T, int top_k, float top_p, unsigned long long seed, void* ws,
+                       float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, hipStream_t s,
+                       Step&& step_fn) {
   const TokenDecodeWs w = token_decode_layout(nlayers, rows, H, top_k);
+  const bool nucleus = top_p < 1.f;
   char* p = reinterpret_cast<char*>(ws);
   float* tk_values = reinterpret_cast<float*>(p + w.tk_values);
   int* tk_index = reinterpret_cast<int*>(p + w.tk_index);
   float* tk_lse = reinterpret_cast<float*>(p + w.tk_lse);
   void* draw_ws = p + w.draw;
-  return token_loop(w, nlayers, rows, H, steps, 1, start_tokens, state0, ws, state_out, s, step_fn,
+  float* logits = reinterpret_cast<float*>(p + w.draw);      // the nucleus draw without top_k
+  return token_loop(w, nlayers, rows, H, steps, nucleus && top_k == 0 ? 0 : 1, start_tokens, state0, ws, state_out, s, step_fn,
                     [&](int t, const float* h_top, long long* tok) {
-                      if (top_k == 0)
+                      if (top_k == 0 && !nucleus)
                         return vocab_sample(h_top, Cw, Cb, rows, H, V, inv_T, seed, (unsigned)t, 0, draw_ws, tok, ids + t, logp + t,
                                             steps, s);
+                      if (top_k == 0) {
+                        const int rc = sgemm_splitk(false, true, rows, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+                        if (rc != kOk) return rc;
+                        return nucleus_rows(logits, rows, V, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t, logp + t, steps, s);
+                      }
                       const int rc = vocab_topk(h_top, Cw, Cb, rows, H, V, top_k, draw_ws, tk_values, tk_index, tk_lse, s);
                       if (rc != kOk) return rc;
+                      if (nucleus)
+                        return nucleus_pick(tk_values, tk_index, rows, top_k, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t,
+                                            logp + t, steps, s);
                       return sample_pick(tk_values, tk_index, rows, top_k, V, inv_T, seed, (unsigned)t, 0, tok, ids + t, logp + t,
                                          steps, s);
                     });
 }
 
-int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                  const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                  const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
-                  long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
-  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, seed, ws, ids, logp, state_out, s,
-                     [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
+int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                          const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                          const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
+                          unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
+                          float* state_out, int* err_flag, hipStream_t s) {
+  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
+                     logp, state_out, s, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
                        const bool given = t == 0 && first_inputs;     // step 0 on the caller's rows
                        return stacked_decode_step(cell, nlayers, rows, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
                                                   wcat, beff, sin, sout, h_top, err_flag, s);
                      });
 }
 
+int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                  const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                  const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
+                  long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
+  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
+                               inv_T, top_k, 1.f, seed, ws, nullptr, 0, ids, logp, state_out, err_flag, s);
+}
+
 // ---- the same loop for the attention decoders: n images x m samples each, the step att_decode_step with k = m and every
 // row continuing from itself (parent_rows null at every step), so an image's maps are read once per step for all its
 // samples. No beam bookkeeping.
 // ws: sample_decode's layout at n m rows, then att_decode_step's block (z | xa | escore)
-size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
+static size_t att_sample_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus) {
   if (n < 1 || m < 1 || (long)n * m >= (1L << 24)) return 0;
-  const size_t base = sample_decode_ws_bytes(nlayers, n * m, H, V, top_k), step = att_decode_step_ws_bytes(n, m, P, A, C, E);
+  const size_t base = sample_ws_bytes(nlayers, n * m, H, V, top_k, nucleus), step = att_decode_step_ws_bytes(n, m, P, A, C, E);
   return base && step ? align16(base) + align16(step) : 0;
+}
+
+size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
+  return att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, false);
+}
+
+size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
+  return att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, true);
+}
+
+int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                              const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                              const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
+                              int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
+                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
+  const int rows = n * m;
+  void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f));
+  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
+                     logp, state_out, s, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
+                       return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
+                                              sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
+                     });
 }
 
 int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
@@ -149,13 +205,9 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
                       const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
                       void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                       hipStream_t s) {
-  const int rows = n * m;
-  void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_decode_ws_bytes(nlayers, rows, H, V, top_k));
-  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, seed, ws, ids, logp, state_out, s,
-                     [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
-                       return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
-                                              sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
-                     });
+  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, wf, bf, wcat,
+                                   beff, Cw, Cb, state0, inv_T, top_k, 1.f, seed, ws, slab, slab_floats, ids, logp, state_out, err_flag,
+                                   s);
 }
 
 // ---- the whole beam search of a plain stack: steps x (one gathered decode-step launch per layer + the vocabulary

@@ -371,6 +371,28 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
                       const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
                       void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                       hipStream_t s);
+// vocab_nucleus.hip: nucleus (top-p) sampling, 0 < top_p < 1: sample_rows' / sample_pick's draw among the smallest set of
+// best entries whose probability reaches top_p, logp renormalised over that set. nucleus_rows: one workgroup per row finds the
+// set's edge by an exact search (any V up to 2^24); nucleus_pick: among vocab_topk's k candidates (top_k first, then top_p)
+int nucleus_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, float top_p, unsigned long long seed,
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+int nucleus_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, float top_p, unsigned long long seed,
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+// decode_loops.hip: sample_decode / att_sample_decode with the nucleus draw, 0 < top_p < 1: per step the projection into a
+// logits block of the workspace (sgemm_splitk on the caller's slab) + nucleus_rows (top_k == 0), or vocab_topk + nucleus_pick
+size_t sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
+int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                          const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                          const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
+                          unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
+                          float* state_out, int* err_flag, hipStream_t s);
+size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
+int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                              const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                              const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
+                              int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
+                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
 // decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
 // fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
 // beam_decode's

@@ -23,13 +23,8 @@
 // sample_rows_kernel: the same draw from a [rows][ld] logits block in memory, one workgroup per row (the composed route).
 #include "common.h"
 #include "kernels.h"
-#include "sample_rng.h"
 #include "vocab_core.h"
-
-// No contraction into fused multiply-adds anywhere in this file: s = z inv_T is a rounded product wherever it is formed, so
-// the three kernels form the same key bits from the same logit, expf(s - M) of the largest s is exactly 1 and a single
-// candidate's logp is exactly 0 (hipcc contracts across statements by default, and __fmul_rn is a plain product to it).
-#pragma clang fp contract(off)
+#include "sample_key.h"   // vs_scaled, vs_key; no FMA contraction in this file
 
 namespace capnet {
 
@@ -50,12 +45,6 @@ struct VocabSampleArgs {
   unsigned long long seed;
   unsigned step, row0;
 };
-
-// the key of entry v of noise row `nrow`: separate roundings of the product and of the sum (see the pragma above)
-__device__ __forceinline__ float vs_scaled(float z, float inv_T) { return __fmul_rn(z, inv_T); }
-__device__ __forceinline__ float vs_key(float s, unsigned long long seed, unsigned step, unsigned nrow, unsigned v) {
-  return __fadd_rn(s, sample_gumbel(sample_uniform(seed, step, nrow, v)));
-}
 
 template <int NJ, int TM>
 __global__ __launch_bounds__(512) void vocab_sample_kernel(VocabSampleArgs a) {

@@ -14,7 +14,7 @@ mode selects, the layout of their beam state, their weight fold.
     (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
     re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
     replay_alphas feeds the returned tokens back through the composed step, whose step_fn keeps its last maps in .alpha.
-  * sample_random: captions DRAWN from the decoder's distribution (temperature, top-k) with their log-probabilities, on the
+  * sample_random: captions DRAWN from the decoder's distribution (temperature, top-k, top-p) with their log-probabilities, on the
     same (step_fn, state) pair: one C call on the PlainStack / AttStack (ops.sample_decode / ops.att_sample_decode) or the
     composed loop step_fn -> draw_step, the same stream and so the same tokens. CAPNET_NO_FUSED_SAMPLE=1 (read at every
     call) takes the composed loop.
@@ -234,21 +234,44 @@ FUSED_SAMPLE_MAX_ROWS = 12
 FUSED_ATT_SAMPLE_MAX_ROWS = 60
 
 
-def fused_sample(rows, att=False):
+# the thresholds of the nucleus draw (top_p < 1), from their own measurement by the same rule (tools/time_nucleus.py,
+# profiles/time_nucleus.jsonl; capnet.seq2seq at 1, 12 and 64 rows, top_p 0.9):
+#   without top_k the one call NEVER beats the composed loop by more than the spread (5.83 against 5.83 ms at 1 layer x 1 row,
+#   6.93 against 6.93 at 3 layers x 12 rows): a step is bound by the selection kernel, about 115 us at V 8192, longer than the
+#   host needs to issue it, so the launches the one call saves are hidden either way -- 0: the composed loop at every row count
+FUSED_NUCLEUS_MAX_ROWS = 0
+#   after top_k the draw is vocab_topk + the pick: the one call wins 1.3x to 1.5x at 1 and 12 rows and loses at 64 rows x 3 layers, as
+#   FUSED_SAMPLE_MAX_ROWS found without a nucleus
+FUSED_NUCLEUS_TOPK_MAX_ROWS = 12
+#   the attention decoders, 12 images x 5 samples: 2.2x (top_k 0) and 2.7x (top_k 5); nothing larger was measured
+FUSED_ATT_NUCLEUS_MAX_ROWS = 60
+
+
+def fused_sample(rows, att=False, top_p=1.0, top_k=0):
     """Whether a sampled decode of `rows` rows takes the one-call route now (CAPNET_NO_FUSED_SAMPLE is read here, at every
-    call; the shape and CAPNET_NO_FUSED_DECODE_STEP are the caller's to check)."""
-    return os.environ.get(FUSED_SAMPLE_OFF, "")[:1] != "1" and rows <= (FUSED_ATT_SAMPLE_MAX_ROWS if att else FUSED_SAMPLE_MAX_ROWS)
+    call; the shape and CAPNET_NO_FUSED_DECODE_STEP are the caller's to check). top_p < 1: the nucleus draw's thresholds."""
+    if top_p < 1.0:
+        most = FUSED_ATT_NUCLEUS_MAX_ROWS if att else FUSED_NUCLEUS_TOPK_MAX_ROWS if top_k else FUSED_NUCLEUS_MAX_ROWS
+    else:
+        most = FUSED_ATT_SAMPLE_MAX_ROWS if att else FUSED_SAMPLE_MAX_ROWS
+    return os.environ.get(FUSED_SAMPLE_OFF, "")[:1] != "1" and rows <= most
 
 
-def draw_step(logits, temperature, top_k, seed, step):
+def draw_step(logits, temperature, top_k, seed, step, top_p=1.0):
     """The composed route's draw of stream step `step` from logits [rows, V] -> (tokens [rows] int64, logp [rows]): the
     stream and the arithmetic of the one-call route's (ops.sample_rows; top_k > 0: torch.topk's candidates into
     ops.sample_pick), so both routes return the same tokens wherever the best two keys are further apart than the logits'
-    last bits."""
+    last bits. top_p < 1: the nucleus draw (ops.nucleus_rows; top_k > 0: ops.nucleus_pick on the same candidates); top_p ==
+    1.0 calls what it called before there was a top_p."""
+    if top_p == 1.0:
+        if top_k == 0:
+            return ops.sample_rows(logits, temperature, seed, step)
+        values, index = torch.topk(logits, top_k, dim=1)
+        return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step)
     if top_k == 0:
-        return ops.sample_rows(logits, temperature, seed, step)
+        return ops.nucleus_rows(logits, temperature, top_p, seed, step)
     values, index = torch.topk(logits, top_k, dim=1)
-    return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step)
+    return ops.nucleus_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, top_p, seed, step)
 
 
 def cut_samples(ids, logp, n, m, start_token, end_token):
@@ -265,37 +288,41 @@ def cut_samples(ids, logp, n, m, start_token, end_token):
     return out
 
 
-def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None):
+def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0):
     """`m` captions per image DRAWN from the decoder's distribution softmax(logits / temperature) (top_k > 0: renormalised
-    over the top_k best words of every step) -> n lists of m (tokens, logprob) pairs; row i m + j of the decode is sample j
+    over the top_k best words of every step; top_p < 1: over the nucleus, the smallest set of best words -- of the top_k
+    where that is set -- whose probability reaches top_p; logprob is that of the distribution drawn from) -> n lists of m
+    (tokens, logprob) pairs; row i m + j of the decode is sample j
     of image i. step_fn / state: a class's _beam(...) with m in place of k and one_call=True, so step_fn carries a
     PlainStack or an AttStack where the fused decode step takes the shape. Routes: ONE C call (ops.sample_decode /
-    ops.att_sample_decode) where that rides on step_fn, the rows are at most FUSED_SAMPLE_MAX_ROWS (FUSED_ATT_SAMPLE_MAX_ROWS) and
-    CAPNET_NO_FUSED_SAMPLE is not 1; else step_fn -> draw_step per step. Both run dec.max_seq_length steps without looking
+    ops.att_sample_decode) where that rides on step_fn, the rows are at most FUSED_SAMPLE_MAX_ROWS (FUSED_ATT_SAMPLE_MAX_ROWS;
+    top_p < 1: FUSED_NUCLEUS_MAX_ROWS, FUSED_NUCLEUS_TOPK_MAX_ROWS, FUSED_ATT_NUCLEUS_MAX_ROWS) and CAPNET_NO_FUSED_SAMPLE is not 1; else step_fn ->
+    draw_step per step. Both run dec.max_seq_length steps without looking
     at end_token (finished rows cost wasted steps; the host cuts), draw the same stream and so return the same lists.
     seed: an integer makes the call a pure function; None draws one from torch's CPU generator."""
     who = "sample_random"
     m, steps, V = int(m), int(dec.max_seq_length), dec.vocab_size
-    temperature, top_k, seed = ops.check_sampling(who, temperature, top_k, seed, V)
+    temperature, top_k, seed, top_p = ops.check_sampling(who, temperature, top_k, seed, V, top_p)
+    kw = {} if top_p == 1.0 else {"top_p": top_p}          # top_p == 1.0: the calls as they were before there was a top_p
     if m < 1 or n < 1 or n * m >= ops.SAMPLE_MAX_ROWS or not 1 <= steps <= ops.SAMPLE_MAX_STEPS:
         raise ops.CapnetError("%s: %d images x %d samples, %d steps" % (who, n, m, steps))
     dev = state[0].device
     with torch.no_grad():
         plain, att = getattr(step_fn, "plain", None), getattr(step_fn, "att", None)
-        if fused_sample(n * m) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
+        if fused_sample(n * m, False, top_p, top_k) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
             tokens = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp, _ = ops.sample_decode(plain.cell, steps, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb,
-                                             temperature, top_k, seed, start_tokens=tokens)
-        elif fused_sample(n * m, True) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
+                                             temperature, top_k, seed, start_tokens=tokens, **kw)
+        elif fused_sample(n * m, True, top_p, top_k) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
             ids, logp = ops.att_sample_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
                                               att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, m, steps,
-                                              start_token, temperature, top_k, seed)
+                                              start_token, temperature, top_k, seed, **kw)
         else:
             words = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp = [], []
             for t in range(steps):
                 logits, state = step_fn(words, state)
-                words, lp = draw_step(logits, temperature, top_k, seed, t)
+                words, lp = draw_step(logits, temperature, top_k, seed, t, **kw)
                 ids.append(words)
                 logp.append(lp)
             ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)

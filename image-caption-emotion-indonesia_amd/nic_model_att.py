@@ -126,9 +126,10 @@ class DecoderRNNAtt(nn.Module):
         return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
                            return_alphas, nbest, length_penalty)
 
-    def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None):
+    def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, top_p=1.0):
         """`samples` captions per image of `features` ([n, S, S, C] or [n, P, C]), DRAWN from the decoder's distribution
-        softmax(logits / temperature) (top_k > 0: renormalised over the top_k best words of every step) instead of searched
+        softmax(logits / temperature) (top_k > 0: renormalised over the top_k best words of every step;
+        top_p < 1: over the nucleus) instead of searched
         for: a list of n lists of `samples` (tokens, logprob) pairs, tokens = [start, w_1 .. w_j] cut after the first
         end_token (none: all max_seq_length words), logprob the float sum of the kept words' log-probabilities under the
         distribution sampled from. seed: an integer makes the call a pure function of its arguments; None draws a 63-bit
@@ -136,7 +137,7 @@ class DecoderRNNAtt(nn.Module):
         per step for all its samples) or the composed loop, the same lists: capnet.decode.sample_random."""
         n = features.size(0)
         return decode.sample_random(self, *self._beam(features, n, int(samples), True), n, samples, start_token, end_token,
-                                    temperature, top_k, seed)
+                                    temperature, top_k, seed, top_p)
 
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False,
                      return_alphas=False, nbest=False, length_penalty=0.0):

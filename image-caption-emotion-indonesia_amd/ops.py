@@ -6,6 +6,7 @@ this file computes on the CPU or through a torch operator. Inputs must be CUDA f
 """
 import ctypes as C
 
+import struct
 import sys
 import weakref
 
@@ -880,9 +881,21 @@ def draw_seed():
     return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item()) * 2 + int(torch.randint(0, 2, (1,)).item())
 
 
-def check_sampling(who, temperature, top_k, seed, V=None):
+def check_top_p(who, top_p):
+    """top_p of nucleus sampling as the kernels compare it: a number with 0 < top_p <= 1, rounded ONCE to fp32 (a value that
+    rounds to 0 or to above 1 is refused; one that rounds to 1.0 is 1.0, "off")."""
+    try:
+        p32 = struct.unpack("f", struct.pack("f", float(top_p)))[0]
+    except (TypeError, ValueError, OverflowError):
+        raise CapnetError("%s: top_p %r" % (who, top_p))
+    if isinstance(top_p, bool) or not 0.0 < p32 <= 1.0:           # NaN fails
+        raise CapnetError("%s: top_p %r (0 < top_p <= 1; 1 = off)" % (who, top_p))
+    return p32
+
+
+def check_sampling(who, temperature, top_k, seed, V=None, top_p=None):
     """(temperature, top_k, seed) checked: temperature finite and > 0; top_k 0 (off) .. 16 and <= V; seed an integer in
-    [0, 2^64) or None (draw_seed)."""
+    [0, 2^64) or None (draw_seed). With top_p given: (temperature, top_k, seed, top_p), top_p through check_top_p."""
     try:
         temperature = float(temperature)
     except (TypeError, ValueError):
@@ -895,6 +908,8 @@ def check_sampling(who, temperature, top_k, seed, V=None):
         seed = draw_seed()
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
         raise CapnetError("%s: seed %r (an integer in [0, 2^64) or None)" % (who, seed))
+    if top_p is not None:
+        return temperature, int(top_k), seed, check_top_p(who, top_p)
     return temperature, int(top_k), seed
 
 
@@ -977,6 +992,49 @@ def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0):
     return tokens, logp
 
 
+def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0):
+    """sample_rows' draw among the nucleus of every row (capnet_nucleus_rows): the smallest set of best entries -- scaled
+    logit descending, index ascending -- whose probability reaches top_p, found exactly by one workgroup per row; logp is
+    renormalised over that set. (tokens [rows] int64, logp [rows] float32). top_p == 1.0 is sample_rows itself."""
+    temperature, _, seed, top_p = check_sampling("nucleus_rows", temperature, 0, seed, top_p=top_p)
+    if top_p == 1.0:
+        return sample_rows(logits, temperature, seed, step, row0)
+    _need_cuda(logits)
+    logits = logits.detach()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise CapnetError("nucleus_rows: logits float32 [rows, V]")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    rows, V = logits.shape
+    step, row0 = _check_stream_pos("nucleus_rows", rows, V, step, row0)
+    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    check(_lib.lib().capnet_nucleus_rows(ptr(logits), rows, logits.stride(0), V, temperature, top_p, seed, step, row0, ptr(tokens),
+                                         ptr(logp), current_stream()), "capnet_nucleus_rows")
+    return tokens, logp
+
+
+def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0):
+    """top_k, then top_p (capnet_nucleus_pick): sample_pick's draw among the nucleus of the k candidates (values, index)
+    [rows, k], probabilities renormalised over the k and logp over the kept ones; the order of the list does not matter.
+    top_p == 1.0 is sample_pick itself."""
+    temperature, _, seed, top_p = check_sampling("nucleus_pick", temperature, 0, seed, top_p=top_p)
+    if top_p == 1.0:
+        return sample_pick(values, index, V, temperature, seed, step, row0)
+    _need_cuda(values, index)
+    values, index = _c(values.detach()), _c(index)
+    if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
+            or not 1 <= values.shape[1] <= 16 or values.shape[0] < 1:
+        raise CapnetError("nucleus_pick: values float32 [rows, k], index int32 [rows, k], 1 <= k <= 16")
+    rows, k = values.shape
+    step, row0 = _check_stream_pos("nucleus_pick", rows, int(V), step, row0)
+    tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=values.device)
+    check(_lib.lib().capnet_nucleus_pick(ptr(values), ptr(index), rows, k, int(V), temperature, top_p, seed, step, row0, ptr(tokens),
+                                         ptr(logp), current_stream()), "capnet_nucleus_pick")
+    return tokens, logp
+
+
 def sample_decode_supported(E, H, V, top_k=0):
     """The shapes capnet_sample_decode takes: those of its parts (the decode step; capnet_vocab_topk when top_k > 0)."""
     return stacked_decode_supported(E, H) and 1 <= V <= SAMPLE_MAX_ROWS and (top_k == 0 or vocab_topk_supported(H, top_k, V))
@@ -988,19 +1046,20 @@ def vocab_topk_supported(H, k, V):
 
 
 def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed, first_inputs=None, start_tokens=None,
-                  state=None):
+                  state=None, top_p=1.0):
     """`steps` sampled decode steps of a plain stack in ONE C call (capnet_sample_decode): per step one decode-step launch
     per layer and the draw (top_k == 0: capnet_vocab_sample; else capnet_vocab_topk + capnet_sample_pick), tokens and logits
     never leaving the device. wcat / beff: capnet.decode.pack_cell(s) of every layer; emb [V, E]; Cw [V, H], Cb [V] or None.
     The first input is first_inputs [rows, E] or emb[start_tokens] (int64 [rows]); state [rows, 2L, H] or None for zeros.
-    Row r draws on stream row r, step t on stream step t. Returns (ids [rows, steps] int64, logp [rows, steps] float32,
-    the final state [rows, 2L, H])."""
+    Row r draws on stream row r, step t on stream step t. top_p < 1: the nucleus draw (capnet_sample_decode_nucleus: per step
+    the projection into a logits block + capnet_nucleus_rows, or capnet_vocab_topk + capnet_nucleus_pick); top_p == 1.0 is
+    capnet_sample_decode. Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state [rows, 2L, H])."""
     who = "sample_decode"
     if (first_inputs is None) == (start_tokens is None):
         raise CapnetError("%s: either first_inputs or start_tokens" % who)
     rows, steps = (first_inputs if first_inputs is not None else start_tokens).shape[0], int(steps)
     emb, Cw, Cb, state, (V, E, H, nl) = _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, rows)
-    temperature, top_k, seed = check_sampling(who, temperature, top_k, seed, V)
+    temperature, top_k, seed, top_p = check_sampling(who, temperature, top_k, seed, V, top_p)
     _need_cuda(first_inputs, start_tokens)
     if first_inputs is not None:
         first_inputs = _c(first_inputs.detach())
@@ -1016,13 +1075,20 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
         raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, top_k=%d)" % (who, E, H, V, nl, top_k))
     dev = emb.device
     L = _lib.lib()
-    nbytes = L.capnet_sample_decode_ws_bytes(nl, rows, H, V, top_k)
+    nbytes = (L.capnet_sample_decode_nucleus_ws_bytes if top_p < 1.0 else L.capnet_sample_decode_ws_bytes)(nl, rows, H, V, top_k)
     if not nbytes:
         raise CapnetError("%s: unsupported shape (rows=%d, V=%d, top_k=%d)" % (who, rows, V, top_k))
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
     ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
     out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
+    if top_p < 1.0:
+        slab = splitk_slab(dev)
+        check(L.capnet_sample_decode_nucleus(cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb),
+                                             ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k,
+                                             top_p, seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out),
+                                             ptr(err_flag(dev)), current_stream()), "capnet_sample_decode_nucleus")
+        return ids, logp, out
     check(L.capnet_sample_decode(cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb), ptr_array(wcat),
                                  ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, seed, ptr(ws), ptr(ids),
                                  ptr(logp), ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_sample_decode")
@@ -1449,15 +1515,16 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
 
 
 def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,
-                      temperature, top_k, seed):
-    """`steps` sampled decode steps of an attention decoder in ONE C call (capnet_att_sample_decode): n images x m samples
+                      temperature, top_k, seed, top_p=1.0):
+    """`steps` sampled decode steps of an attention decoder in ONE C call (capnet_att_sample_decode; top_p < 1:
+    capnet_att_sample_decode_nucleus, the draw as ops.sample_decode's): n images x m samples
     each (row i m + j = sample j of image i), the step att_decode_step's with k = m and every row continuing from itself --
     an image's maps are read once per step for all its samples -- then the draw as ops.sample_decode's. Operands as
     att_beam_decode; state [n m, 2L, H]: the initial state. Returns (ids [n m, steps] int64, logp [n m, steps] float32)."""
     who = "att_sample_decode"
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
         who, cell, att1, feat, m, emb, wz, bz, w_full, b_full, wcat, beff, state)
-    temperature, top_k, seed = check_sampling(who, temperature, top_k, seed, V)
+    temperature, top_k, seed, top_p = check_sampling(who, temperature, top_k, seed, V, top_p)
     _need_cuda(Cw, Cb)
     Cw = _c(Cw.detach())
     Cb = None if Cb is None else _c(Cb.detach())
@@ -1466,7 +1533,9 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
         raise CapnetError("%s: Cw [V, H], Cb [V], 1 <= steps <= 65535 (V=%d, steps=%d)" % (who, V, steps))
     dev, rows = emb.device, n * m
     L = _lib.lib()
-    nbytes = L.capnet_att_sample_decode_ws_bytes(nl, n, m, P, A, Cdim, E, H, V, top_k)
+    nucleus = top_p < 1.0
+    nbytes = (L.capnet_att_sample_decode_nucleus_ws_bytes if nucleus else L.capnet_att_sample_decode_ws_bytes)(
+        nl, n, m, P, A, Cdim, E, H, V, top_k)
     if not nbytes:
         raise CapnetError("%s: unsupported shape (n=%d, m=%d, V=%d, top_k=%d)" % (who, n, m, V, top_k))
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
@@ -1474,10 +1543,13 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
     tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
     ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
-    check(L.capnet_att_sample_decode(cell, nl, n, m, P, A, Cdim, E, H, V, steps, ptr(tokens), ptr(att1), ptr(feat), ptr(emb), ptr(wz),
-                                     ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state),
-                                     temperature, top_k, seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None,
-                                     ptr(err_flag(dev)), current_stream()), "capnet_att_sample_decode")
+    head = (cell, nl, n, m, P, A, Cdim, E, H, V, steps, ptr(tokens), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf),
+            ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k)
+    tail = (seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None, ptr(err_flag(dev)), current_stream())
+    if nucleus:
+        check(L.capnet_att_sample_decode_nucleus(*head, top_p, *tail), "capnet_att_sample_decode_nucleus")
+    else:
+        check(L.capnet_att_sample_decode(*head, *tail), "capnet_att_sample_decode")
     return ids, logp
 
 

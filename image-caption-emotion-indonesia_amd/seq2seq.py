@@ -209,23 +209,25 @@ class _RNN(nn.Module):
             return torch.stack(ids, 1), state
 
 
-    def _sampled(self, features, start_tokens, state, temperature, top_k, seed):
+    def _sampled(self, features, start_tokens, state, temperature, top_k, seed, top_p=1.0):
         """max_seq_length SAMPLED steps from `features` [rows, E] or emb[start_tokens]; state [rows, 2L, H]: every word a draw
         from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k best), row r on stream row r, step
-        t on stream step t. Returns (ids [rows, max_seq_length] int64, logp [rows, max_seq_length] float32, state').
+        t on stream step t; top_p < 1: over the nucleus (capnet.decode.sample_random). Returns (ids [rows, max_seq_length] int64, logp [rows, max_seq_length] float32, state').
         One capnet_sample_decode call where the decode kernel takes the shape, the rows are at most
         capnet.decode.FUSED_SAMPLE_MAX_ROWS and neither CAPNET_NO_FUSED_SAMPLE=1 nor CAPNET_NO_FUSED_DECODE_STEP=1 is set;
         else the composed loop (step -> ops.linear -> capnet.decode.draw_step) on the same stream: the same tokens."""
         E, H, V, steps = self.embed_size, self.hidden_size, self.vocab_size, self.max_seq_length
-        temperature, top_k, seed = ops.check_sampling("sample_random", temperature, top_k, seed, V)
+        temperature, top_k, seed, top_p = ops.check_sampling("sample_random", temperature, top_k, seed, V, top_p)
+        kw = {} if top_p == 1.0 else {"top_p": top_p}      # top_p == 1.0: the calls as they were before there was a top_p
         emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
         layers = self._layers()
         with torch.no_grad():
-            if (fused_sample(state.shape[0]) and fused_decode_step(self.num_layers, E, H)
+            if (fused_sample(state.shape[0], False, top_p, top_k) and fused_decode_step(self.num_layers, E, H)
                     and ops.sample_decode_supported(E, H, V, top_k)):
                 packed = pack_cells(layers, E)
                 return ops.sample_decode(ops.CELL_LSTM, steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
-                                         temperature, top_k, seed, first_inputs=features, start_tokens=start_tokens, state=state)
+                                         temperature, top_k, seed, first_inputs=features, start_tokens=start_tokens, state=state,
+                                         **kw)
             step = cell_stepper(layers, E, H)
             ids, logp, tokens = [], [], start_tokens
             for t in range(steps):
@@ -233,7 +235,7 @@ class _RNN(nn.Module):
                     top, state = step(features.detach().float().contiguous(), None, state)
                 else:
                     top, state = step(emb, tokens, state)
-                tokens, lp = draw_step(ops.linear(top, Cw, Cb), temperature, top_k, seed, t)
+                tokens, lp = draw_step(ops.linear(top, Cw, Cb), temperature, top_k, seed, t, **kw)
                 ids.append(tokens)
                 logp.append(lp)
             return torch.stack(ids, 1), torch.stack(logp, 1), state
@@ -302,14 +304,14 @@ class EncoderRNN(_RNN):
         ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
         return ids, _from_rows(state)
 
-    def sample_random(self, features, states=(None, None), temperature=1.0, top_k=0, seed=None):
+    def sample_random(self, features, states=(None, None), temperature=1.0, top_k=0, seed=None, top_p=1.0):
         """sample() with every word DRAWN from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k
         best words) instead of the argmax: (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32 -- each word's
         log-probability under the distribution sampled from --, (h, c) [num_layers, B, H]); the first input is `features`.
         seed: an integer makes the call a pure function; None draws one from torch's CPU generator (torch.manual_seed).
         Routing: _RNN._sampled."""
         state = self._rows_state(states, features.size(0), features.device)
-        ids, logp, state = self._sampled(features, None, state, temperature, top_k, seed)
+        ids, logp, state = self._sampled(features, None, state, temperature, top_k, seed, top_p)
         return ids, logp, _from_rows(state)
 
     def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None, nbest=False,
@@ -355,12 +357,12 @@ class DecoderRNN(_RNN):
         ops.check_device_errors()
         return ids
 
-    def sample_random(self, start_token, states, temperature=1.0, top_k=0, seed=None):
+    def sample_random(self, start_token, states, temperature=1.0, top_k=0, seed=None, top_p=1.0):
         """sample() with every word drawn (EncoderRNN.sample_random): from embed(start_token) and `states` (h, c)
         [num_layers, B, H] -> (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32). An out-of-range
         start_token raises CapnetError through the device error word."""
         tokens, state = self._start(start_token, states)
-        ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed)
+        ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed, top_p)
         ops.check_device_errors()
         return ids, logp
 
@@ -430,16 +432,17 @@ class Seq2Seq(nn.Module):
             return sampled_ids
         return decoder.sample(start_token, states)
 
-    def sample_random(self, features, start_token, states=(None, None), mode='factual', temperature=1.0, top_k=0, seed=None):
+    def sample_random(self, features, start_token, states=(None, None), mode='factual', temperature=1.0, top_k=0, seed=None,
+                      top_p=1.0):
         """factual: the encoder's sampled (ids, logp) [B, max_seq_length] (EncoderRNN.sample_random). An emotion mode: the
         encoder's GREEDY sample for the state, exactly as sample(mode=...) does, then that decoder's sampled (ids, logp)
         from embed(start_token) and it: only the emotion decoder samples."""
         decoder = None if mode == 'factual' else self._decoder(mode)
         if decoder is None:
-            ids, logp, _ = self.encoder.sample_random(features, states, temperature, top_k, seed)
+            ids, logp, _ = self.encoder.sample_random(features, states, temperature, top_k, seed, top_p)
             return ids, logp
         _, states = self.encoder.sample(features, states)
-        return decoder.sample_random(start_token, states, temperature, top_k, seed)
+        return decoder.sample_random(start_token, states, temperature, top_k, seed, top_p)
 
     def sample_beam(self, features, start_token, end_token, states=(None, None), mode='factual', k=5, poll_every=0,
                     fused_topk=None, nbest=False, length_penalty=0.0):

@@ -755,6 +755,47 @@ int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, 
                              float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                              capnet_stream_t stream);
 
+/* ---- nucleus (top-p) sampling (csrc/vocab_nucleus.hip) ----
+ * The draw of capnet_sample_rows among the NUCLEUS of the row: with s_v = fl32(logit_v / T), the pickable entries (not NaN,
+ * not -inf, v < V) ordered by s descending, then v ascending, and p = softmax(s) over them,
+ *   before(v) = the sum of p_u over the entries strictly better than v,   N = { v : before(v) < top_p }
+ * -- the smallest set of best entries whose probability reaches top_p, always holding the best one -- and
+ *   token = argmax over N of (s_v - logf(-logf(u(seed, step, row0 + r, v)))),   logp = s_token - log sum_{v in N} exp(s_v),
+ * the log-probability under the distribution sampled from. 0 < top_p <= 1; top_p == 1 is "off": capnet_sample_rows itself
+ * (not a nucleus with p = 1, which would drop the tail once the fp32 mass rounds to 1). logits [rows][ld], ld >= V, any V up
+ * to 2^24; one workgroup per row finds the edge of N by an exact search over the integer images of s with the index breaking
+ * ties, every sum a fixed tree: the same bits at every call, whatever the order of the entries' arrival. */
+int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p, unsigned long long seed,
+                        unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream);
+
+/* top_k, then top_p: the same rule among capnet_vocab_topk's k candidates values / index [rows][k] (1 <= k <= 16), p and logp
+ * renormalised over the k, then over the kept ones. The order of the list does not matter. top_p == 1: capnet_sample_pick. */
+int capnet_nucleus_pick(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                        unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                        capnet_stream_t stream);
+
+/* capnet_sample_decode with the nucleus draw, 0 < top_p < 1 (top_p == 1 is capnet_sample_decode's): per step the projection
+ * into a logits block of the workspace (capnet_sgemm_splitk's product on `slab`, the split-K slab; it may be NULL when
+ * top_k > 0) + capnet_nucleus_rows, or capnet_vocab_topk + capnet_nucleus_pick (1 <= top_k <= 16). Every other operand as
+ * capnet_sample_decode; workspace: capnet_sample_decode_nucleus_ws_bytes(nlayers, rows, H, V, top_k) bytes (0: unsupported). */
+size_t capnet_sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
+int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                 const long long* start_tokens, const float* emb, const float* const* wcat,
+                                 const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                 float temperature, int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
+                                 size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                                 capnet_stream_t stream);
+
+/* The same for an attention decoder: capnet_att_sample_decode with the nucleus draw, 0 < top_p < 1. */
+size_t capnet_att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
+int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                     const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                     const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                     const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                     const float* state0, float temperature, int top_k, float top_p, unsigned long long seed,
+                                     void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                     float* state_out, int* err_flag, capnet_stream_t stream);
+
 /* capnet_vocab_topk for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's rows
  * are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL; every
  * w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival counter
