@@ -1,0 +1,28 @@
+// Max and sum over a workgroup of whole waves (at most four): a wave-64 butterfly, one LDS slot per wave, then every thread
+// adds the slots in wave order. One copy, so the row kernels of loss_optim.hip and policy_loss.hip reduce in the same order
+// and agree to the last bit where they compute the same thing.
+#pragma once
+#include "common.h"
+
+namespace capnet {
+
+__device__ __forceinline__ float block_reduce_max(float v, float* s) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = s[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = fmaxf(r, s[w]);
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ float block_reduce_sum(float v, float* s) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = s[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += s[w];
+  __syncthreads();
+  return r;
+}
+
+}  // namespace capnet

@@ -1310,6 +1310,18 @@ int capnet_att_loss_bwd(const float* gout, const float* colsum, int B, int steps
                         float* dalphas, capnet_stream_t stream) {
   return att_loss_bwd(gout, colsum, B, steps, P, alpha_c, dalphas, S(stream));
 }
+int capnet_policy_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets,
+                           const float* advantages, int B, const int* batch_sizes, int steps, float* lse,
+                           float* row_logp, float* caption_logp, float* loss, int* err_flag, capnet_stream_t stream) {
+  return policy_xent_fwd(logits, ld, N, V, targets, advantages, B, batch_sizes, steps, lse, row_logp, caption_logp, loss,
+                         err_flag, S(stream));
+}
+int capnet_policy_xent_bwd(const float* logits, long ld, int N, int V, const long long* targets, const float* lse,
+                           const float* advantages, int B, const int* batch_sizes, int steps, const float* grad_out,
+                           float* dlogits, long ldd, capnet_stream_t stream) {
+  return policy_xent_bwd(logits, ld, N, V, targets, lse, advantages, B, batch_sizes, steps, grad_out, dlogits, ldd,
+                         S(stream));
+}
 
 int capnet_clamp_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
                       float* const* exp_avg_sq, const long* numel, const int* step, float lr,

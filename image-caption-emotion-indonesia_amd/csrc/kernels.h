@@ -488,6 +488,13 @@ int att_loss_fwd(const float* nll, const float* alphas, int B, int steps, int P,
                  float* colsum, float* out, hipStream_t stream);
 int att_loss_bwd(const float* gout, const float* colsum, int B, int steps, int P, float alpha_c,
                  float* dalphas, hipStream_t stream);
+// policy_loss.hip
+int policy_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets, const float* adv, int B,
+                    const int* batch_sizes, int steps, float* lse, float* row_logp, float* caption_logp, float* loss,
+                    int* err_flag, hipStream_t stream);
+int policy_xent_bwd(const float* logits, long ld, int N, int V, const long long* targets, const float* lse,
+                    const float* adv, int B, const int* batch_sizes, int steps, const float* gout, float* dlogits,
+                    long ldd, hipStream_t stream);
 int lstm_persist_set_mode(int mode);
 int clamp_adam(int n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
                float* const* exp_avg_sq, const long* numel, const int* step, float lr, float b1,

@@ -6,29 +6,11 @@
 //   BatchNorm1d : EncoderCNN.bn (momentum 0.01)                 stylenet/model.py:20,26
 #include "common.h"
 #include "kernels.h"
+#include "block_reduce.h"
 
 namespace capnet {
 
-// ---- cross entropy ---------------------------------------------------------------------
-__device__ __forceinline__ float block_reduce_max(float v, float* s) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = s[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = fmaxf(r, s[w]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float block_reduce_sum(float v, float* s) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = s[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += s[w];
-  __syncthreads();
-  return r;
-}
-
+// ---- cross entropy (block_reduce_max / block_reduce_sum: block_reduce.h) -----------------
 // one workgroup per row: lse[row] = log sum exp, row_loss[row] = lse - logit[target]
 __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__ logits, long ld,
                                                        int V, const long long* __restrict__ target,

@@ -18,6 +18,9 @@ mode selects, the layout of their beam state, their weight fold.
     same (step_fn, state) pair: one C call on the PlainStack / AttStack (ops.sample_decode / ops.att_sample_decode) or the
     composed loop step_fn -> draw_step, the same stream and so the same tokens. CAPNET_NO_FUSED_SAMPLE=1 (read at every
     call) takes the composed loop.
+  * pack_samples / policy_logits / score_captions: drawn captions back through the teacher-forced forward, whose step-t
+    distribution is the one sample_random drew word t from -- what capnet.train.policy_step differentiates and what every
+    image decoder's score_captions reports (the model's log-probability of given captions).
   * attend: Attention.forward, the single step outside a beam search.
   * att_beam_start / att_beam_step: an attention decoder's beam search. The set-up (encoder_att once per image, the
     initial state) is written once for one image and once for n; the step (z = [decoder_att; f_beta](h), the embedding
@@ -328,6 +331,90 @@ def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature
             ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)
     ops.check_device_errors()
     return cut_samples(ids, logp, n, m, start_token, end_token)
+
+
+# ---- sampled captions back through the teacher-forced forward -----------------------------------------
+def flat_captions(captions):
+    """captions as score_captions / capnet.train.policy_step take them -> (token lists, image of each): a flat list of token
+    lists, caption r belonging to row r of the features, or the nested list sample_random returns (per image a list of
+    samples, each a token list or a (tokens, logprob) pair whose logprob is ignored)."""
+    tokens, image = [], []
+    for i, c in enumerate(captions):
+        if len(c) and isinstance(c[0], (list, tuple)):
+            for s in c:
+                pair = len(s) == 2 and isinstance(s[0], (list, tuple))
+                tokens.append([int(w) for w in (s[0] if pair else s)])
+                image.append(i)
+        else:
+            tokens.append([int(w) for w in c])
+            image.append(i)
+    return tokens, image
+
+
+def pack_samples(captions):
+    """Token lists [start, w_1 .. w_j], j >= 1 -> (inputs, lengths, targets, order) of their teacher-forced batch: order the
+    stable sort by descending j (caption order[r] becomes row r), inputs [B, T] int64 with row r = tokens[:-1] padded with 0,
+    lengths the j of every row, targets tokens[1:] in pack_padded_sequence order. Host tensors and lists; no GPU."""
+    if not len(captions):
+        raise ops.CapnetError("pack_samples: no captions")
+    caps = [[int(w) for w in c] for c in captions]
+    if min(len(c) for c in caps) < 2:
+        raise ops.CapnetError("pack_samples: a caption is [start, w_1 .. w_j] with at least one word")
+    order = sorted(range(len(caps)), key=lambda r: -len(caps[r]))      # sorted() is stable
+    rows = [caps[r] for r in order]
+    lengths = [len(c) - 1 for c in rows]
+    inputs = torch.zeros((len(rows), lengths[0]), dtype=torch.int64)
+    for r, c in enumerate(rows):
+        inputs[r, :len(c) - 1] = torch.tensor(c[:-1], dtype=torch.int64)
+    targets = torch.tensor([c[t + 1] for t in range(lengths[0]) for c in rows if len(c) - 1 > t], dtype=torch.int64)
+    return inputs, lengths, targets, order
+
+
+def is_attention(dec):
+    """Whether the image is an input of `dec`'s decoding (the four attention decoders)."""
+    return hasattr(dec, "attention_size")
+
+
+def policy_logits(dec, inputs, lengths, features, mode=None):
+    """Packed logits [sum(lengths), V] of the teacher-forced pass whose step-t distribution is the one sample_random drew word
+    t from: inputs / lengths of pack_samples on the device, every step teacher forced (tf_mask given, so the global `random`
+    stream is not consumed). The plain decoders run with features=None -- their decode steps start from the embedding of
+    <start> at a zero state and ignore the image, as the reference's sample does; the attention decoders take `features`,
+    the maps of every row in the batch's sorted order, and their alphas are dropped. mode: None where the class has none."""
+    kw = {} if mode is None else {"mode": mode}
+    tf_mask = [True] * inputs.shape[1]
+    if is_attention(dec):
+        return dec(inputs, lengths, features, teacher_forcing_ratio=1.0, tf_mask=tf_mask, **kw)[0]
+    return dec(inputs, lengths, None, teacher_forcing_ratio=1.0, tf_mask=tf_mask, **kw)
+
+
+def policy_batch(dec, features, captions):
+    """What policy_logits and ops.policy_loss need of `captions` (flat or nested, flat_captions), on dec's device:
+    (inputs, lengths, targets, order, features of every row in sorted order -- each image's maps once per sample of it; None
+    for a plain decoder)."""
+    tokens, image = flat_captions(captions)
+    inputs, lengths, targets, order = pack_samples(tokens)
+    dev = next(dec.parameters()).device
+    feats = None
+    if is_attention(dec):
+        if max(image) >= features.size(0):
+            raise ops.CapnetError("%d captions' images for %d rows of features" % (max(image) + 1, features.size(0)))
+        feats = features.index_select(0, torch.tensor([image[r] for r in order], dtype=torch.int64, device=features.device))
+    return inputs.to(dev), lengths, targets.to(dev), order, feats
+
+
+def score_captions(dec, features, captions, mode=None):
+    """float32 [number of captions] on the device: the model's log-probability of every caption, the sum over w_1 .. w_j
+    (<end> too where present), in the caller's order. captions: flat_captions'. Under no_grad; dropout follows
+    dec.training, as in forward. One teacher-forced pass (policy_logits) and capnet_policy_xent_fwd."""
+    with torch.no_grad():
+        inputs, lengths, targets, order, feats = policy_batch(dec, features, captions)
+        logits = policy_logits(dec, inputs, lengths, feats, mode)
+        zeros = torch.zeros(len(order), dtype=torch.float32, device=logits.device)
+        _, logp = ops.policy_loss(logits, targets, zeros, ops.batch_sizes_from_lengths(lengths))
+        out = torch.empty_like(logp)
+        out[torch.tensor(order, dtype=torch.int64, device=logp.device)] = logp
+    return out
 
 
 def zero_state(rows, H, device):

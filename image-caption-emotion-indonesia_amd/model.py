@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import CapnetError, check, current_stream, ptr, ptr_array
-from .decode import beam_decode, check_styles, fold_factored, fused_decode_step, plain_stack, plain_styles, sample_random, zero_state
+from .decode import beam_decode, check_styles, fold_factored, fused_decode_step, plain_stack, plain_styles, sample_random, score_captions, zero_state
 
 random.seed(0)  # stylenet/model.py:7
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')  # stylenet/model.py:8
@@ -667,6 +667,13 @@ class DecoderFactoredLSTM(nn.Module):
         n = features.size(0)
         return sample_random(self, *self._beam(n * int(samples), mode, True), n, samples, start_token, end_token, temperature,
                              top_k, seed, top_p)
+
+    def score_captions(self, features, captions, mode='factual'):
+        """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j], summed over
+        w_1 .. w_j (<end> too where present), in the caller's order. captions: a flat list of token lists, or the nested
+        list sample_random returns (the logprob of a (tokens, logprob) pair is ignored). As in sample(), the image is not an
+        input: `features` is not read. Under no_grad, dropout following self.training: capnet.decode.score_captions."""
+        return score_captions(self, features, captions, mode)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
                      poll_every=0, one_call=False, nbest=False, length_penalty=0.0):

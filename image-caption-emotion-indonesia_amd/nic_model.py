@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .decode import beam_decode, fused_decode_step, input_width, pack_cell, plain_stack, sample_random, zero_state
+from .decode import beam_decode, fused_decode_step, input_width, pack_cell, plain_stack, sample_random, score_captions, zero_state
 from .model import Dropout, Embedding, EncoderCNN, Linear, _seq_cfg  # noqa: F401
 
 
@@ -119,6 +119,13 @@ class DecoderRNN(nn.Module):
         n = features.size(0)
         return sample_random(self, *self._beam(n * int(samples), True), n, samples, start_token, end_token, temperature, top_k,
                              seed, top_p)
+
+    def score_captions(self, features, captions):
+        """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j], summed over
+        w_1 .. w_j (<end> too where present), in the caller's order. captions: a flat list of token lists, or the nested
+        list sample_random returns (the logprob of a (tokens, logprob) pair is ignored). As in sample(), the image is not an
+        input: `features` is not read. Under no_grad, dropout following self.training: capnet.decode.score_captions."""
+        return score_captions(self, features, captions)
 
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, nbest=False,
                      length_penalty=0.0):

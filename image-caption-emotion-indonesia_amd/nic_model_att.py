@@ -139,6 +139,14 @@ class DecoderRNNAtt(nn.Module):
         return decode.sample_random(self, *self._beam(features, n, int(samples), True), n, samples, start_token, end_token,
                                     temperature, top_k, seed, top_p)
 
+    def score_captions(self, features, captions):
+        """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j] given its
+        image, summed over w_1 .. w_j (<end> too where present), in the caller's order. captions: a flat list of token lists,
+        caption r on row r of `features` ([n, S, S, C] or [n, P, C]), or the nested list sample_random returns, list i on image
+        i (the logprob of a (tokens, logprob) pair is ignored). Under no_grad, dropout following self.training:
+        capnet.decode.score_captions."""
+        return decode.score_captions(self, features, captions)
+
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False,
                      return_alphas=False, nbest=False, length_penalty=0.0):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).

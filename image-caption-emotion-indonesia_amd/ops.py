@@ -1759,6 +1759,56 @@ def cross_entropy(logits, targets):
     return CrossEntropyFn.apply(logits, targets)
 
 
+class PolicyLossFn(torch.autograd.Function):
+    """-(1/N) sum_i advantages[cap(i)] * log p(target_i) over packed rows (capnet_policy_xent_fwd / _bwd): the loss of a
+    policy-gradient step on sampled captions. The gradient goes to the logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, advantages, batch_sizes):
+        _need_cuda(logits, targets, advantages)
+        logits, targets, advantages = _c(logits), _c(targets), _c(advantages)
+        if targets.dtype != torch.int64 or advantages.dtype != torch.float32:
+            raise CapnetError("policy loss: targets must be int64 and advantages float32")
+        n, v = logits.shape
+        bs = [int(b) for b in batch_sizes]
+        if targets.numel() != n or sum(bs) != n or not bs or advantages.numel() != bs[0]:
+            raise CapnetError("policy loss: %d logits rows, %d targets, %d advantages, batch_sizes summing to %d from %d"
+                              % (n, targets.numel(), advantages.numel(), sum(bs), bs[0] if bs else 0))
+        dev = logits.device
+        lse = torch.empty(n, dtype=torch.float32, device=dev)
+        row_logp = torch.empty(n, dtype=torch.float32, device=dev)
+        caption_logp = torch.empty(bs[0], dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        check(_lib.lib().capnet_policy_xent_fwd(ptr(logits), v, n, v, ptr(targets), ptr(advantages), bs[0], int_array(bs),
+                                                len(bs), ptr(lse), ptr(row_logp), ptr(caption_logp), ptr(loss),
+                                                ptr(err_flag(dev)), current_stream()), "capnet_policy_xent_fwd")
+        ctx.save_for_backward(logits, targets, lse, advantages)
+        ctx.batch_sizes = bs
+        ctx.mark_non_differentiable(caption_logp)
+        return loss, caption_logp
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, _):
+        logits, targets, lse, advantages = ctx.saved_tensors
+        n, v = logits.shape
+        bs = ctx.batch_sizes
+        gout = _c(gout.to(torch.float32)).reshape(1)
+        dlogits = torch.empty_like(logits)
+        check(_lib.lib().capnet_policy_xent_bwd(ptr(logits), v, n, v, ptr(targets), ptr(lse), ptr(advantages), bs[0],
+                                                int_array(bs), len(bs), ptr(gout), ptr(dlogits), v, current_stream()),
+              "capnet_policy_xent_bwd")
+        return dlogits, None, None, None
+
+
+def policy_loss(logits, targets, advantages, batch_sizes):
+    """(loss, caption_logp) of a packed batch of sampled captions: loss = -(1/N) sum over packed rows of
+    advantages[caption of the row] * log softmax(logits)[target], differentiable in `logits` only; caption_logp [B]
+    (detached) the model's log-probability of every caption. advantages [B] float32 on the device, in the batch's
+    sorted order; batch_sizes as ops.batch_sizes_from_lengths gives them."""
+    return PolicyLossFn.apply(logits, targets, advantages, batch_sizes)
+
+
 class AttentionLossFn(torch.autograd.Function):
     """nll + alpha_c * ((1 - alphas.sum(dim=1)) ** 2).mean()  (train_multitask_att.py:409-411)."""
 

@@ -35,7 +35,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .decode import (as_state, beam_decode, check_styles, factored_step, fold_factored, plain_stack, plain_styles, sample_random,
+from .decode import (as_state, beam_decode, check_styles, factored_step, fold_factored, plain_stack, plain_styles, sample_random, score_captions,
                      stack_stepper)
 from .model import Embedding as _Embedding, Linear as _Linear, _layer_mods, _seq_cfg
 
@@ -164,6 +164,13 @@ class StackedFactoredLSTM(nn.Module):
         n = features.size(0)
         return sample_random(self, *self._beam(n * int(samples), mode, True), n, samples, start_token, end_token, temperature,
                              top_k, seed, top_p)
+
+    def score_captions(self, features, captions, mode='factual'):
+        """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j], summed over
+        w_1 .. w_j (<end> too where present), in the caller's order. captions: a flat list of token lists, or the nested
+        list sample_random returns (the logprob of a (tokens, logprob) pair is ignored). As in sample(), the image is not an
+        input: `features` is not read. Under no_grad, dropout following self.training: capnet.decode.score_captions."""
+        return score_captions(self, features, captions, mode)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
                      poll_every=0, one_call=False, nbest=False, length_penalty=0.0):

@@ -2,6 +2,8 @@
 
   train_step     one iteration of the bodies of train_factual / train_emotion
                  (stylenet/train_multitask.py:373-389, 527-537; nic/train_transfer_fac.py:252-296)
+  policy_step / self_critical_step / bleu_reward   reward-based fine-tuning on sampled captions (self-critical sequence
+                 training, Rennie et al. 2017; no counterpart in the reference)
   train_factual  stylenet/train_multitask.py:364-408
   train_emotion  stylenet/train_multitask.py:511-557
   val_factual / val_emotion   stylenet/train_multitask.py:272-361, 411-508 (eval-mode trunk on the
@@ -15,7 +17,7 @@ import random
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import decode, ops
 from .metrics import corpus_bleu
 from .utils import AverageMeter, accuracy, clip_gradient
 
@@ -104,6 +106,91 @@ def train_step_att(encoder, decoder, optimizer, criterion, images, captions, len
     clip_gradient(optimizer, grad_clip)
     optimizer.step()
     return loss.detach()
+
+
+def policy_step(decoder, optimizer, features, captions, advantages, grad_clip, mode=None, loss_scale=None):
+    """One policy-gradient step on given captions: ascends sum_r advantages[r] * log p(caption r) / N, N the captions' words.
+    Returns (loss, caption_logp): the (device) loss -(1/N) sum_r advantages[r] log p(caption r) and the model's
+    log-probability of every caption before the update, float32 on the device in the caller's order.
+
+    captions: a flat list of token lists [start, w_1 .. w_j] (caption r on row r of `features`) or the nested list
+    sample_random returns (capnet.decode.flat_captions); advantages: one float per caption, in the same (flattened) order.
+    Deterministic: every step is teacher forced, so `random` is not consumed. Order of operations: pack ->
+    capnet.decode.policy_logits -> ops.policy_loss -> zero_grad -> backward -> clip_gradient -> optimizer.step.
+    features: the decoder's input, not images -- no encoder parameter receives a gradient (a plain decoder does not read
+    them at all; an attention decoder's trunk is frozen). mode: as train_step's; loss_scale: _backward's."""
+    inputs, lengths, targets, order, feats = decode.policy_batch(decoder, features, captions)
+    adv = [float(a) for a in (advantages.tolist() if torch.is_tensor(advantages) else advantages)]
+    if len(adv) != len(order):
+        raise ops.CapnetError("policy_step: %d advantages for %d captions" % (len(adv), len(order)))
+    adv = torch.tensor([adv[r] for r in order], dtype=torch.float32).to(inputs.device)
+    logits = decode.policy_logits(decoder, inputs, lengths, feats, mode)
+    loss, logp = ops.policy_loss(logits, targets, adv, ops.batch_sizes_from_lengths(lengths))
+    decoder.zero_grad()
+    _backward(loss, loss_scale)
+    clip_gradient(optimizer, grad_clip)
+    optimizer.step()
+    caption_logp = torch.empty_like(logp)
+    caption_logp[torch.tensor(order, dtype=torch.int64, device=logp.device)] = logp
+    return loss.detach(), caption_logp
+
+
+def mean_baseline(rewards):
+    """rewards [image][sample] -> baselines of the same shape: for every sample the mean reward of the image's OTHER samples
+    (so an image's advantages sum to 0). Needs at least two samples per image."""
+    out = []
+    for row in rewards:
+        if len(row) < 2:
+            raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
+        total = sum(row)
+        out.append([(total - r) / (len(row) - 1) for r in row])
+    return out
+
+
+def self_critical_step(decoder, optimizer, features, reward, start_token, end_token, grad_clip, samples=5, baseline='greedy',
+                       mode=None, temperature=1.0, top_k=0, top_p=1.0, seed=None, loss_scale=None):
+    """One step of self-critical sequence training (Rennie et al., 2017): draw `samples` captions per image with
+    decoder.sample_random, score them on the host with reward(image_index, tokens) -> float, subtract a baseline and take
+    policy_step on the advantages.
+
+    baseline: 'greedy' -- the reward of the image's width-1 beam caption (decoder.sample_batch(k=1)); 'mean' -- the mean
+    reward of the image's other samples (samples >= 2, ValueError otherwise).
+    temperature / top_k / top_p / seed are sample_random's and only shape the exploration: the gradient is always that of
+    the model's own, untempered and untruncated log-probability of the drawn captions (policy_step), not of the
+    distribution they were drawn from.
+    features: as policy_step's. Returns {'loss': the device loss, 'reward_mean', 'baseline_mean', 'advantage_abs_mean':
+    floats over all samples, 'zero_rows': the captions whose advantage is exactly 0 (under 'greedy': the samples that
+    scored what the greedy caption did, the greedy caption itself among them)}."""
+    if baseline not in ("greedy", "mean"):
+        raise ValueError("baseline %r (expected 'greedy' or 'mean')" % (baseline,))
+    if baseline == "mean" and int(samples) < 2:
+        raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
+    kw = {} if mode is None else {"mode": mode}
+    drawn = decoder.sample_random(features, start_token, end_token, samples=samples, temperature=temperature, top_k=top_k,
+                                  seed=seed, top_p=top_p, **kw)
+    rewards = [[float(reward(i, tokens)) for tokens, _ in row] for i, row in enumerate(drawn)]
+    if baseline == "mean":
+        base = mean_baseline(rewards)
+    else:
+        greedy = decoder.sample_batch(features, start_token, end_token, k=1, **kw)
+        base = [[float(reward(i, [int(w) for w in g]))] * len(rewards[i]) for i, g in enumerate(greedy)]
+    adv = [r - b for rr, bb in zip(rewards, base) for r, b in zip(rr, bb)]
+    loss, _ = policy_step(decoder, optimizer, features, drawn, adv, grad_clip, mode=mode, loss_scale=loss_scale)
+    n = float(len(adv))
+    return {"loss": loss,
+            "reward_mean": sum(r for rr in rewards for r in rr) / n,
+            "baseline_mean": sum(b for bb in base for b in bb) / n,
+            "advantage_abs_mean": sum(abs(a) for a in adv) / n,
+            "zero_rows": sum(1 for a in adv if a == 0.0)}
+
+
+def bleu_reward(references, weights=(0.25, 0.25, 0.25, 0.25)):
+    """A ready-made `reward` for self_critical_step: reward(i, tokens) = corpus_bleu of the one sentence `tokens` against
+    references[i], the list of reference token lists of image i. Tokens are taken as evaluate() takes them: as they are,
+    <start> / <end> included on both sides."""
+    def reward(i, tokens):
+        return corpus_bleu([references[i]], [[int(w) for w in tokens]], weights=weights)
+    return reward
 
 
 class TrunkPipeline(object):

@@ -1088,6 +1088,22 @@ int capnet_att_loss_fwd(const float* nll, const float* alphas, int B, int steps,
                         float* colsum, float* out, capnet_stream_t stream);
 int capnet_att_loss_bwd(const float* gout, const float* colsum, int B, int steps, int P, float alpha_c,
                         float* dalphas, capnet_stream_t stream);
+/* Policy-gradient loss over a packed batch of B sampled captions (self-critical sequence training):
+ *   loss = -(1/N) sum_i advantages[cap(i)] * (logits[i][targets[i]] - lse[i])
+ * logits [N][V] (leading dimension ld), targets [N] in pack_padded_sequence order; batch_sizes (host int[steps], steps
+ * <= 128, batch_sizes[0] == B) as for capnet_seq_forward: in the step whose first row is off_t, cap(i) = i - off_t.
+ * advantages [B] (device) in the batch's sorted order. The forward call writes lse [N], row_logp [N] (the log-probability
+ * of every target), caption_logp [B] (a caption's rows summed in step order) and the scalar loss; a target outside [0, V)
+ * raises bit 1 of err_flag, as in capnet_xent_fwd. The backward call writes
+ *   dlogits[i][:] = (softmax_i - onehot_i) * grad_out[0] * advantages[cap(i)] / N;
+ * a row whose advantage is exactly 0 is written as zeros without its logits being read. With every advantage 1.0f both
+ * calls give capnet_xent_fwd's loss and capnet_xent_bwd's dlogits bit for bit. */
+int capnet_policy_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets,
+                           const float* advantages, int B, const int* batch_sizes, int steps, float* lse,
+                           float* row_logp, float* caption_logp, float* loss, int* err_flag, capnet_stream_t stream);
+int capnet_policy_xent_bwd(const float* logits, long ld, int N, int V, const long long* targets, const float* lse,
+                           const float* advantages, int B, const int* batch_sizes, int steps, const float* grad_out,
+                           float* dlogits, long ldd, capnet_stream_t stream);
 
 /* ---- input pipeline (stylenet/train_multitask.py:62-69: Resize((336,336)) -> RandomCrop(224) ->
  * RandomHorizontalFlip -> ToTensor -> Normalize) on uint8 HWC device images ----------------------

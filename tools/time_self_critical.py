@@ -1,0 +1,113 @@
+"""Time one self-critical step (capnet.train.self_critical_step) and its parts, and append one JSON line per baseline to
+profiles/time_self_critical.jsonl. A record; nothing is chosen by these numbers.
+
+DecoderFactoredLSTMAtt at BASELINE configs[3]'s attention sizes (attention 512, embedding 300, hidden 512, factored 1024,
+maps of 2048 channels, V 8192) on 7 x 7 maps, 12 images x 5 samples, 20 steps, reward = capnet.train.bleu_reward against
+three random references per image (plus a hash of the tokens, so that the advantages are not all 0), capnet.optim.Adam.
+Timed, each on its own with the inputs the step would give it:
+  sample     decoder.sample_random(samples=5)                      the exploration
+  baseline   decoder.sample_batch(k=1)                             the greedy caption ('greedy' only)
+  reward     the host metric on every drawn caption (and the greedy ones)
+  policy     capnet.train.policy_step on the drawn captions        pack, teacher-forced forward, loss, backward, clamp + Adam
+  step       the whole self_critical_step
+Wall ms per call (host clock around the call, ended by a synchronise), the parts alternated, `--reps` times each in one
+process after `--warmup` untimed rounds; per part the median and the (min, max) of the repeats. The parameters move between
+repeats (the optimiser steps), the shapes do not: the seed of the draw is fixed and an untrained decoder rarely draws <end>.
+
+usage: python tools/time_self_critical.py [--baselines greedy,mean] [--reps R] [--warmup W]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import capnet  # noqa: E402,F401
+from capnet import train  # noqa: E402
+from capnet.model_att import DecoderFactoredLSTMAtt  # noqa: E402
+from capnet.optim import Adam  # noqa: E402
+
+A, E, H, F, V, CF = 512, 300, 512, 1024, 8192, 2048
+IMAGES, SAMPLES, STEPS, START, END = 12, 5, 20, 1, 2
+OUT = os.path.join(ROOT, "profiles", "time_self_critical.jsonl")
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--baselines", default="greedy,mean")
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    refs = [[torch.randint(4, V, (12,), generator=g).tolist() for _ in range(3)] for _ in range(IMAGES)]
+    bleu = train.bleu_reward(refs)
+
+    def reward(i, tokens):
+        # BLEU's host cost, plus a hash of the tokens: an untrained decoder's BLEU is 0 for every caption, and rows of
+        # advantage 0 would take the gradient kernel's short path
+        return bleu(i, tokens) + (sum(tokens) % 97) / 97.0
+    for baseline in a.baselines.split(","):
+        torch.manual_seed(3)
+        dec = DecoderFactoredLSTMAtt(A, E, H, F, V, 1, feature_size=CF, dropout=0.0, max_seq_length=STEPS).to(dev).train()
+        feats = torch.rand(IMAGES, 7, 7, CF, device=dev)
+        opt = Adam(dec.parameters(), lr=1e-4)
+        kw = dict(samples=SAMPLES, seed=7)
+        parts = {
+            "sample": lambda: dec.sample_random(feats, START, END, **kw),
+            "baseline": lambda: dec.sample_batch(feats, START, END, k=1),
+            "step": lambda: train.self_critical_step(dec, opt, feats, reward, START, END, 5.0, baseline=baseline, **kw),
+        }
+        if baseline != "greedy":
+            del parts["baseline"]
+        ms = {k: [] for k in list(parts) + ["reward", "policy"]}
+        words = 0
+        for it in range(a.warmup + a.reps):
+            t = {}
+            for name, fn in parts.items():
+                t[name], out = _timed(fn)
+                if name == "sample":
+                    drawn = out
+                elif name == "baseline":
+                    greedy = out
+            t0 = time.perf_counter()
+            rewards = [[reward(i, q) for q, _ in row] for i, row in enumerate(drawn)]
+            if baseline == "greedy":
+                base = [[reward(i, [int(w) for w in q])] * SAMPLES for i, q in enumerate(greedy)]
+            else:
+                base = train.mean_baseline(rewards)
+            t["reward"] = (time.perf_counter() - t0) * 1e3
+            adv = [r - b for rr, bb in zip(rewards, base) for r, b in zip(rr, bb)]
+            t["policy"], _ = _timed(lambda: train.policy_step(dec, opt, feats, drawn, adv, 5.0))
+            words = sum(len(q) - 1 for row in drawn for q, _ in row)
+            if it >= a.warmup:
+                for k, v in t.items():
+                    ms[k].append(v)
+        rec = {"tool": "time_self_critical", "decoder": "DecoderFactoredLSTMAtt", "A": A, "E": E, "H": H, "F": F, "V": V, "C": CF,
+               "P": 49, "images": IMAGES, "samples": SAMPLES, "steps": STEPS, "baseline": baseline, "packed_rows": words,
+               "reps": a.reps,
+               "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+                      for k, v in ms.items()}}
+        line = json.dumps(rec)
+        print(line, flush=True)
+        with open(OUT, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
