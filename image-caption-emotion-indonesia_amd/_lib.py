@@ -163,23 +163,37 @@ SIGNATURES = {
     "capnet_sample_uniform": (C.c_float, [C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint]),
     "capnet_vocab_sample_ws_bytes": (_sz, [_i, _i]),
     "capnet_vocab_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp, _vp]),
+    "capnet_vocab_sample_greedy": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp, C.c_uint, _vp]),
     "capnet_sample_pick": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp]),
+    "capnet_sample_pick_greedy": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp]),
     "capnet_sample_rows": (_i, [_vp, _i, _l, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp]),
+    "capnet_sample_rows_greedy": (_i, [_vp, _i, _l, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp]),
     "capnet_sample_decode_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "capnet_sample_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
                                   C.c_float, _i, C.c_ulonglong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_sample_decode_greedy": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
+                                  C.c_float, _i, C.c_ulonglong, _vp, _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     "capnet_att_sample_decode_ws_bytes": (_sz, [_i] * 10),
     "capnet_att_sample_decode": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
                                                             C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_att_sample_decode_greedy": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
+                                                            C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     "capnet_nucleus_rows": (_i, [_vp, _i, _l, _i, C.c_float, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp]),
+    "capnet_nucleus_rows_greedy": (_i, [_vp, _i, _l, _i, C.c_float, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp]),
     "capnet_nucleus_pick": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp]),
+    "capnet_nucleus_pick_greedy": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp]),
     "capnet_sample_decode_nucleus_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "capnet_sample_decode_nucleus": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
                                           C.c_float, _i, C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_sample_decode_nucleus_greedy": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
+                                          C.c_float, _i, C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     "capnet_att_sample_decode_nucleus_ws_bytes": (_sz, [_i] * 10),
     "capnet_att_sample_decode_nucleus": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
                                                                     C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
                                                                     _vp]),
+    "capnet_att_sample_decode_nucleus_greedy": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
+                                                                    C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                                    C.c_uint, _vp]),
     "capnet_vocab_topk_groups_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "capnet_vocab_topk_groups": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "capnet_beam_advance_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),
@@ -236,6 +250,8 @@ SIGNATURES = {
     "capnet_att_loss_bwd": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp, _vp]),
     "capnet_policy_xent_fwd": (_i, [_vp, _l, _i, _i, _vp, _vp, _i, _ip, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "capnet_policy_xent_bwd": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _i, _ip, _i, _vp, _vp, _l, _vp]),
+    "capnet_bleu_rows": (_i, [_vp, _l, _i, _i, C.c_longlong, C.c_longlong, _i, _vp, _vp, _i, _i, _i, C.POINTER(C.c_double), _i,
+                              _vp, _vp, _vp]),
     "capnet_clamp_adam": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                C.POINTER(_vp), C.POINTER(_l), _ip, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_float, _i, _vp, _vp]),

@@ -144,9 +144,9 @@ int capnet_conv3x3_fwd_patch(const float* x, const unsigned* image, int bn, floa
   return conv3x3_fwd_patch(x, image, bn, y, in_scale, in_shift, relu_in, part_sum, part_sq, B, H, W, Cin, Cout, S(stream),
                            shared_chip != 0);
 }
-int capnet_conv1x1_fwd_tail(const float* y3, const float* s1, const float* t1, const float* res, const float* s2,
-                            const float* t2, float* tail_out, const unsigned* image, int bn, float* y, float* part_sum,
-                            float* part_sq, long M, int Cin, int Cout, capnet_stream_t stream) {
+int capnet_conv1x1_fwd_tail(const float* y3, const float* s1, const float* t1, const float* res, const float* s2, const
+                            float* t2, float* tail_out, const unsigned* image, int bn, float* y, float* part_sum, float*
+                            part_sq, long M, int Cin, int Cout, capnet_stream_t stream) {
   return conv1x1_fwd_tail(y3, s1, t1, res, s2, t2, tail_out, image, bn, y, part_sum, part_sq, M, Cin, Cout, S(stream));
 }
 // the same three with the input's power-of-two prescale (capnet.h)
@@ -166,10 +166,10 @@ int capnet_conv3x3_fwd_patch_scaled(const float* x, const unsigned* image, int b
                            shared_chip != 0, in_exp);
 }
 int capnet_conv1x1_fwd_tail_scaled(const float* y3, const float* s1, const float* t1, const float* res, const float* s2,
-                                   const float* t2, float* tail_out, const unsigned* image, int bn, float* y,
-                                   float* part_sum, float* part_sq, long M, int Cin, int Cout, int in_exp,
-                                   capnet_stream_t stream) {
-  return conv1x1_fwd_tail(y3, s1, t1, res, s2, t2, tail_out, image, bn, y, part_sum, part_sq, M, Cin, Cout, S(stream), in_exp);
+                                   const float* t2, float* tail_out, const unsigned* image, int bn, float* y, float*
+                                   part_sum, float* part_sq, long M, int Cin, int Cout, int in_exp, capnet_stream_t stream) {
+  return conv1x1_fwd_tail(y3, s1, t1, res, s2, t2, tail_out, image, bn, y, part_sum, part_sq, M, Cin, Cout, S(stream),
+                          in_exp);
 }
 size_t capnet_conv_stem_f16x3_weight_words(void) { return conv_stem_f16x3_weight_words(); }
 int capnet_conv_stem_f16x3_part_rows(int B, int H, int W) { return conv_stem_f16x3_part_rows(B, H, W); }
@@ -602,39 +602,85 @@ static int sample_check(const char* who, int rows, int V, float temperature, uns
   return kOk;
 }
 
+// greedy_stride of the capnet_*_greedy entries (sample_key.h's vs_row_key): 0 = off; the loops: the rows come in whole groups
+// (rows % stride == 0; the attention loops: the stride IS the rows per image)
+static int greedy_stride_check(const char* who, int rows, unsigned greedy_stride, int per_image) {
+  CAPNET_REQUIRE(greedy_stride < (1u << 24), "%s: greedy_stride %u (< 2^24)", who, greedy_stride);
+  CAPNET_REQUIRE(!greedy_stride || !rows || rows % (int)greedy_stride == 0, "%s: %d rows in groups of greedy_stride %u", who, rows,
+                 greedy_stride);
+  CAPNET_REQUIRE(!greedy_stride || !per_image || per_image == (int)greedy_stride, "%s: greedy_stride %u with %d rows per image", who,
+                 greedy_stride, per_image);
+  return kOk;
+}
+
 size_t capnet_vocab_sample_ws_bytes(int rows, int V) { return rows >= 1 && V >= 1 ? vocab_sample_ws_bytes(rows, V) : 0; }
 
-int capnet_vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
-                        unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens, float* logp,
-                        capnet_stream_t stream) {
+static int vocab_sample_tail(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                             unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
+                             float* logp, capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("vocab_sample", 0, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
   if (int rc = sample_check("vocab_sample", rows, V, temperature, step, row0, &inv_T)) return rc;
   CAPNET_REQUIRE(vocab_sample_supported(H), "vocab_sample: unsupported H=%d", H);
   CAPNET_REQUIRE(h && w && workspace && tokens && logp, "vocab_sample: null argument");
   CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_sample: h, w and the workspace must be 16-B aligned");
   CAPNET_REQUIRE((size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "vocab_sample: output alignment");
-  return vocab_sample(h, w, b, rows, H, V, inv_T, seed, step, row0, workspace, tokens, nullptr, logp, 1, S(stream));
+  return vocab_sample(h, w, b, rows, H, V, inv_T, seed, step, row0, workspace, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                        unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
+                        float* logp, capnet_stream_t stream) {
+  return vocab_sample_tail(h, w, b, rows, H, V, temperature, seed, step, row0, workspace, tokens, logp, stream, 0);
+}
+int capnet_vocab_sample_greedy(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                               unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
+                               float* logp, unsigned greedy_stride, capnet_stream_t stream) {
+  return vocab_sample_tail(h, w, b, rows, H, V, temperature, seed, step, row0, workspace, tokens, logp, stream,
+                           greedy_stride);
 }
 
-int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature, unsigned long long seed,
-                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+static int sample_pick_tail(const float* values, const int* index, int rows, int k, int V, float temperature,
+                            unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                            capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("sample_pick", 0, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
   if (int rc = sample_check("sample_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
   CAPNET_REQUIRE(k >= 1 && k <= 16, "sample_pick: k=%d (1 <= k <= 16)", k);
   CAPNET_REQUIRE(values && index && tokens && logp, "sample_pick: null argument");
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
                  "sample_pick: alignment");
-  return sample_pick(values, index, rows, k, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+  return sample_pick(values, index, rows, k, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature,
+                       unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                       capnet_stream_t stream) {
+  return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_sample_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature,
+                              unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                              unsigned greedy_stride, capnet_stream_t stream) {
+  return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
 }
 
-int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed, unsigned step,
-                       unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+static int sample_rows_tail(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                            unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream,
+                            unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("sample_rows", 0, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
   if (int rc = sample_check("sample_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
   CAPNET_REQUIRE(ld >= V, "sample_rows: ld %ld < V %d", ld, V);
   CAPNET_REQUIRE(logits && tokens && logp, "sample_rows: null argument");
   CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "sample_rows: alignment");
-  return sample_rows(logits, rows, ld, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+  return sample_rows(logits, rows, ld, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+  return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_sample_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                              unsigned step, unsigned row0, long long* tokens, float* logp, unsigned greedy_stride,
+                              capnet_stream_t stream) {
+  return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
 }
 
 size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
@@ -642,11 +688,12 @@ size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int to
   return sample_decode_ws_bytes(nlayers, rows, H, V, top_k);
 }
 
-int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
-                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out, int* err_flag,
-                         capnet_stream_t stream) {
+static int sample_decode_tail(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                              float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
+                              float* logp, float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("sample_decode", rows, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
   CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "sample_decode: steps %d (1..65535)", steps);
   if (int rc = sample_check("sample_decode", rows, V, temperature, 0, 0, &inv_T)) return rc;
@@ -661,8 +708,25 @@ int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, i
                  "sample_decode: workspace, Cw and the states must be 16-B aligned");
   CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "sample_decode: ids / logp alignment");
   if (int rc = layer_weights_check("sample_decode", nlayers, wcat, beff)) return rc;
-  return sample_decode(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
-                       top_k, seed, workspace, ids, logp, state_out, err_flag, S(stream));
+  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
+                       top_k, 1.f, seed, workspace, nullptr, 0, ids, logp, state_out, err_flag, S(stream), greedy_stride);
+}
+int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
+                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out,
+                         int* err_flag, capnet_stream_t stream) {
+  return sample_decode_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
+                            temperature, top_k, seed, workspace, ids, logp, state_out, err_flag, stream, 0);
+}
+int capnet_sample_decode_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                const long long* start_tokens, const float* emb, const float* const* wcat,
+                                const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
+                                float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                                capnet_stream_t stream) {
+  return sample_decode_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
+                            temperature, top_k, seed, workspace, ids, logp, state_out, err_flag, stream, greedy_stride);
 }
 
 // ---- nucleus (top-p) sampling (vocab_nucleus.hip) ----
@@ -673,30 +737,54 @@ static int top_p_check(const char* who, float top_p, bool allow_one) {
   return kOk;
 }
 
-int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p, unsigned long long seed,
-                        unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+static int nucleus_rows_tail(const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                             unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                             capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("nucleus_rows", 0, greedy_stride, 0)) return rc;
   if (int rc = top_p_check("nucleus_rows", top_p, true)) return rc;
-  if (top_p == 1.f) return capnet_sample_rows(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream);
+  if (top_p == 1.f) return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
   float inv_T = 0.f;
   if (int rc = sample_check("nucleus_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
   CAPNET_REQUIRE(ld >= V, "nucleus_rows: ld %ld < V %d", ld, V);
   CAPNET_REQUIRE(logits && tokens && logp, "nucleus_rows: null argument");
   CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "nucleus_rows: alignment");
-  return nucleus_rows(logits, rows, ld, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+  return nucleus_rows(logits, rows, ld, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
 }
-
-int capnet_nucleus_pick(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p,
                         unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
                         capnet_stream_t stream) {
+  return nucleus_rows_tail(logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_nucleus_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                               unsigned greedy_stride, capnet_stream_t stream) {
+  return nucleus_rows_tail(logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, greedy_stride);
+}
+
+static int nucleus_pick_tail(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                             unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                             capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("nucleus_pick", 0, greedy_stride, 0)) return rc;
   if (int rc = top_p_check("nucleus_pick", top_p, true)) return rc;
-  if (top_p == 1.f) return capnet_sample_pick(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream);
+  if (top_p == 1.f) return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
   float inv_T = 0.f;
   if (int rc = sample_check("nucleus_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
   CAPNET_REQUIRE(k >= 1 && k <= 16, "nucleus_pick: k=%d (1 <= k <= 16)", k);
   CAPNET_REQUIRE(values && index && tokens && logp, "nucleus_pick: null argument");
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
                  "nucleus_pick: alignment");
-  return nucleus_pick(values, index, rows, k, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream));
+  return nucleus_pick(values, index, rows, k, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_nucleus_pick(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                        unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                        capnet_stream_t stream) {
+  return nucleus_pick_tail(values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_nucleus_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                               unsigned greedy_stride, capnet_stream_t stream) {
+  return nucleus_pick_tail(values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream,
+                           greedy_stride);
 }
 
 size_t capnet_sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
@@ -704,12 +792,14 @@ size_t capnet_sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V
   return sample_decode_nucleus_ws_bytes(nlayers, rows, H, V, top_k);
 }
 
-int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                                 const long long* start_tokens, const float* emb, const float* const* wcat,
-                                 const float* const* beff, const float* Cw, const float* Cb, const float* state0,
-                                 float temperature, int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
-                                 size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                                 capnet_stream_t stream) {
+static int sample_decode_nucleus_tail(int cell, int nlayers, int rows, int E, int H, int V, int steps,
+                                      const float* first_inputs, const long long* start_tokens, const float* emb,
+                                      const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                      const float* state0, float temperature, int top_k, float top_p,
+                                      unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                                      long long* ids, float* logp, float* state_out, int* err_flag, capnet_stream_t stream,
+                                      unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("sample_decode_nucleus", rows, greedy_stride, 0)) return rc;
   const char* who = "sample_decode_nucleus";
   float inv_T = 0.f;
   if (int rc = top_p_check(who, top_p, false)) return rc;
@@ -728,7 +818,28 @@ int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, 
   CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
   if (int rc = layer_weights_check(who, nlayers, wcat, beff)) return rc;
   return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
-                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream));
+                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream), greedy_stride);
+}
+int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                 const long long* start_tokens, const float* emb, const float* const* wcat,
+                                 const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                 float temperature, int top_k, float top_p, unsigned long long seed, void* workspace,
+                                 float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out,
+                                 int* err_flag, capnet_stream_t stream) {
+  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
+                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
+                                    state_out, err_flag, stream, 0);
+}
+int capnet_sample_decode_nucleus_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps,
+                                        const float* first_inputs, const long long* start_tokens, const float* emb,
+                                        const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                        const float* state0, float temperature, int top_k, float top_p,
+                                        unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                                        long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                                        capnet_stream_t stream) {
+  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
+                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
+                                    state_out, err_flag, stream, greedy_stride);
 }
 
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
@@ -931,13 +1042,14 @@ size_t capnet_att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A
   return att_sample_decode_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
 }
 
-int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                             const float* wz, const float* bz, const float* w_full, const float* b_full,
-                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
-                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                             capnet_stream_t stream) {
+static int att_sample_decode_tail(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                  const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, float temperature, int top_k, unsigned long long seed,
+                                  void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                  float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("att_sample_decode", n * m, greedy_stride, m)) return rc;
   if (int rc = att_decode_check("att_sample_decode", cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
                                 wcat, beff, workspace, slab, slab_floats, err_flag))
     return rc;
@@ -950,9 +1062,31 @@ int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, 
   CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0) && (!state_out || aligned16(state_out)),
                  "att_sample_decode: Cw and the states must be 16-B aligned");
   CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "att_sample_decode: ids / logp alignment");
-  return att_sample_decode(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
-                           beff, Cw, Cb, state0, inv_T, top_k, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag,
-                           S(stream));
+  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
+                           beff, Cw, Cb, state0, inv_T, top_k, 1.f, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag,
+                           S(stream), greedy_stride);
+}
+int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                             const float* wz, const float* bz, const float* w_full, const float* b_full,
+                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
+                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                             capnet_stream_t stream) {
+  return att_sample_decode_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full,
+                                b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, seed, workspace, slab, slab_floats,
+                                ids, logp, state_out, err_flag, stream, 0);
+}
+int capnet_att_sample_decode_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                    const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                    const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                    const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                    const float* state0, float temperature, int top_k, unsigned long long seed,
+                                    void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                    float* state_out, int* err_flag, unsigned greedy_stride, capnet_stream_t stream) {
+  return att_sample_decode_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full,
+                                b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, seed, workspace, slab, slab_floats,
+                                ids, logp, state_out, err_flag, stream, greedy_stride);
 }
 
 size_t capnet_att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
@@ -960,13 +1094,15 @@ size_t capnet_att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int 
   return att_sample_decode_nucleus_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
 }
 
-int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                                     const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                                     const float* wz, const float* bz, const float* w_full, const float* b_full,
-                                     const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                                     const float* state0, float temperature, int top_k, float top_p, unsigned long long seed,
-                                     void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
-                                     float* state_out, int* err_flag, capnet_stream_t stream) {
+static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
+                                          int steps, const long long* start_tokens, const float* att1, const float* feat,
+                                          const float* emb, const float* wz, const float* bz, const float* w_full,
+                                          const float* b_full, const float* const* wcat, const float* const* beff,
+                                          const float* Cw, const float* Cb, const float* state0, float temperature,
+                                          int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
+                                          size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                                          capnet_stream_t stream, unsigned greedy_stride) {
+  if (int rc = greedy_stride_check("att_sample_decode_nucleus", n * m, greedy_stride, m)) return rc;
   const char* who = "att_sample_decode_nucleus";
   if (int rc = att_decode_check(who, cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
                                 workspace, slab, slab_floats, err_flag))
@@ -983,7 +1119,30 @@ int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P,
   CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
   return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full,
                                    wcat, beff, Cw, Cb, state0, inv_T, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                   state_out, err_flag, S(stream));
+                                   state_out, err_flag, S(stream), greedy_stride);
+}
+int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
+                                     int steps, const long long* start_tokens, const float* att1, const float* feat,
+                                     const float* emb, const float* wz, const float* bz, const float* w_full,
+                                     const float* b_full, const float* const* wcat, const float* const* beff,
+                                     const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
+                                     float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                                     long long* ids, float* logp, float* state_out, int* err_flag, capnet_stream_t stream) {
+  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
+                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
+                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, 0);
+}
+int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
+                                            int steps, const long long* start_tokens, const float* att1, const float* feat,
+                                            const float* emb, const float* wz, const float* bz, const float* w_full,
+                                            const float* b_full, const float* const* wcat, const float* const* beff,
+                                            const float* Cw, const float* Cb, const float* state0, float temperature,
+                                            int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
+                                            size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                                            unsigned greedy_stride, capnet_stream_t stream) {
+  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
+                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
+                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride);
 }
 
 size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
@@ -1321,6 +1480,16 @@ int capnet_policy_xent_bwd(const float* logits, long ld, int N, int V, const lon
                            float* dlogits, long ldd, capnet_stream_t stream) {
   return policy_xent_bwd(logits, ld, N, V, targets, lse, advantages, B, batch_sizes, steps, grad_out, dlogits, ldd,
                          S(stream));
+}
+
+int capnet_bleu_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token,
+                     int per_image, const int* refs, const int* ref_len, int images, int R, int Lr, const double* weights,
+                     int smooth, float* reward, int* stats, capnet_stream_t stream) {
+  CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)refs % 4 == 0 && (size_t)ref_len % 4 == 0 && (size_t)reward % 4 == 0 &&
+                     (size_t)stats % 4 == 0,
+                 "bleu_rows: alignment");
+  return bleu_rows(ids, ld, rows, steps, start_token, end_token, per_image, refs, ref_len, images, R, Lr, weights, smooth, reward,
+                   stats, S(stream));
 }
 
 int capnet_clamp_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,

@@ -97,7 +97,10 @@ int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, in
 
 // ---- the sampling loops: the draw is vocab_sample (top_k == 0) or vocab_topk + sample_pick (top_k > 0); with a nucleus
 // (top_p < 1) the projection into the workspace's logits block (sgemm_splitk, the product of the composed route's ops.linear:
-// the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": today's launches, not a nucleus ----
+// the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": today's launches, not a nucleus.
+// greedy_stride (sample_key.h's vs_row_key; the capnet_*_greedy entries): g > 0 makes every g-th row the greedy decode of its
+// group -- the loops only pass it to the draw; on the attention loop the caller runs m = g rows per image, so the greedy
+// caption rides on the one read of the image's maps per step ----
 static size_t sample_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus) {
   const size_t draw = top_k > 0 ? vocab_topk_ws_bytes(rows, top_k, V)
                       : nucleus ? align16((size_t)rows * V * sizeof(float)) : vocab_sample_ws_bytes(rows, V);
@@ -116,7 +119,7 @@ template <class Step>
 static int sample_loop(int nlayers, int rows, int H, int V, int steps, const long long* start_tokens, const float* Cw,
                        const float* Cb, const float* state0, float inv_T, int top_k, float top_p, unsigned long long seed, void* ws,
                        float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, hipStream_t s,
-                       Step&& step_fn) {
+                       unsigned greedy_stride, Step&& step_fn) {
   const TokenDecodeWs w = token_decode_layout(nlayers, rows, H, top_k);
   const bool nucleus = top_p < 1.f;
   char* p = reinterpret_cast<char*>(ws);
@@ -129,19 +132,20 @@ static int sample_loop(int nlayers, int rows, int H, int V, int steps, const lon
                     [&](int t, const float* h_top, long long* tok) {
                       if (top_k == 0 && !nucleus)
                         return vocab_sample(h_top, Cw, Cb, rows, H, V, inv_T, seed, (unsigned)t, 0, draw_ws, tok, ids + t, logp + t,
-                                            steps, s);
+                                            steps, s, greedy_stride);
                       if (top_k == 0) {
                         const int rc = sgemm_splitk(false, true, rows, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
                         if (rc != kOk) return rc;
-                        return nucleus_rows(logits, rows, V, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t, logp + t, steps, s);
+                        return nucleus_rows(logits, rows, V, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t, logp + t, steps, s,
+                                            greedy_stride);
                       }
                       const int rc = vocab_topk(h_top, Cw, Cb, rows, H, V, top_k, draw_ws, tk_values, tk_index, tk_lse, s);
                       if (rc != kOk) return rc;
                       if (nucleus)
                         return nucleus_pick(tk_values, tk_index, rows, top_k, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t,
-                                            logp + t, steps, s);
+                                            logp + t, steps, s, greedy_stride);
                       return sample_pick(tk_values, tk_index, rows, top_k, V, inv_T, seed, (unsigned)t, 0, tok, ids + t, logp + t,
-                                         steps, s);
+                                         steps, s, greedy_stride);
                     });
 }
 
@@ -149,9 +153,9 @@ int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, 
                           const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
                           const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
                           unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s) {
+                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride) {
   return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
+                     logp, state_out, s, greedy_stride, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
                        const bool given = t == 0 && first_inputs;     // step 0 on the caller's rows
                        return stacked_decode_step(cell, nlayers, rows, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
                                                   wcat, beff, sin, sout, h_top, err_flag, s);
@@ -189,11 +193,12 @@ int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A,
                               const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
                               int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
-                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
+                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
+                              unsigned greedy_stride) {
   const int rows = n * m;
   void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f));
   return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
+                     logp, state_out, s, greedy_stride, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
                        return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
                                               sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
                      });

@@ -345,17 +345,20 @@ int vocab_topk_groups(const float* h, const float* const* w, const float* const*
 // vocab_sample.hip: per row a draw from softmax((h[r] . W + b) inv_T) by Gumbel-max on sample_rng.h's stream keyed (seed,
 // step, row0 + r, v), one launch, no logits in memory: tok[r] / ids[r ld] the token, logp[r ld] its log-probability (each
 // optional; ws: vocab_sample_ws_bytes, its first 16 bytes zero before the first use). sample_pick: the same draw among
-// vocab_topk's k candidates (logp renormalised over them); sample_rows: from a logits block in memory
+// vocab_topk's k candidates (logp renormalised over them); sample_rows: from a logits block in memory. greedy_stride (here,
+// in vocab_nucleus.hip and in the sampling loops): sample_key.h's vs_row_key -- g > 0: every g-th row is a greedy row (the
+// argmax, no noise) and the drawn rows keep the noise rows of the decode without them; 0: off
 bool vocab_sample_supported(int H);
 float sample_uniform_host(unsigned long long seed, unsigned step, unsigned row, unsigned v);
 size_t vocab_sample_ws_bytes(int rows, int V);
 int vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float inv_T, unsigned long long seed,
                  unsigned step, unsigned row0, void* ws, long long* tok, long long* ids, float* logp, long ld,
-                 hipStream_t stream);
+                 hipStream_t stream, unsigned greedy_stride = 0);
 int sample_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, unsigned long long seed,
-                unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+                unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                unsigned greedy_stride = 0);
 int sample_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, unsigned long long seed, unsigned step,
-                unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+                unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream, unsigned greedy_stride = 0);
 // decode_loops.hip: lstm_greedy_decode's loop with the draw in place of the argmax (top_k == 0: vocab_sample; else vocab_topk
 // + sample_pick)
 size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
@@ -375,9 +378,11 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
 // best entries whose probability reaches top_p, logp renormalised over that set. nucleus_rows: one workgroup per row finds the
 // set's edge by an exact search (any V up to 2^24); nucleus_pick: among vocab_topk's k candidates (top_k first, then top_p)
 int nucleus_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, float top_p, unsigned long long seed,
-                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                 unsigned greedy_stride = 0);
 int nucleus_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, float top_p, unsigned long long seed,
-                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream);
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                 unsigned greedy_stride = 0);
 // decode_loops.hip: sample_decode / att_sample_decode with the nucleus draw, 0 < top_p < 1: per step the projection into a
 // logits block of the workspace (sgemm_splitk on the caller's slab) + nucleus_rows (top_k == 0), or vocab_topk + nucleus_pick
 size_t sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
@@ -385,14 +390,15 @@ int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, 
                           const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
                           const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
                           unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s);
+                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride = 0);
 size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
 int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
                               const long long* start_tokens, const float* att1, const float* feat, const float* emb,
                               const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
                               int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
-                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
+                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
+                              unsigned greedy_stride = 0);
 // decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
 // fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
 // beam_decode's
@@ -495,6 +501,12 @@ int policy_xent_fwd(const float* logits, long ld, int N, int V, const long long*
 int policy_xent_bwd(const float* logits, long ld, int N, int V, const long long* targets, const float* lse,
                     const float* adv, int B, const int* batch_sizes, int steps, const float* gout, float* dlogits,
                     long ldd, hipStream_t stream);
+// caption_reward.hip: sentence BLEU of decoded rows. Limits: a hypothesis of at most kBleuMaxSteps + 1 words, at most
+// kBleuMaxRefs reference slots per image and kBleuRefWords padded reference words per image (slots x padded length)
+constexpr int kBleuMaxSteps = 128, kBleuMaxRefs = 16, kBleuRefWords = 4096;
+int bleu_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token, int per_image,
+              const int* refs, const int* ref_len, int images, int R, int Lr, const double* weights, int smooth, float* reward,
+              int* stats, hipStream_t stream);
 int lstm_persist_set_mode(int mode);
 int clamp_adam(int n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
                float* const* exp_avg_sq, const long* numel, const int* step, float lr, float b1,

@@ -4,7 +4,7 @@
 //   the total order of vocab_better: s descending, then v ascending
 //   before(v) = sum of e_u over the pickable u strictly better than v,  S = sum of e_u over all of them
 //   N = { v : before(v) < top_p S }  (top_p S one rounded product): always holds the best entry
-//   tok = argmax over N of vs_key(s_v, seed, step, row0 + r, v),  logp = s_tok - (M + logf(sum of e_v over N))
+//   tok = argmax over N of vs_row_key(s_v, seed, step, row0 + r, greedy_stride, v)  (a greedy row: the best entry, always in N),  logp = s_tok - (M + logf(sum of e_v over N))
 // A row with nothing pickable yields token 0 and logp = -inf.
 //
 // nucleus_rows_kernel: one workgroup per row of a [rows][ld] block of logits. Every sum of the kernel -- S, before(.) at a
@@ -76,8 +76,9 @@ __device__ __forceinline__ void nuc_sum(float (&a)[N], float (*part)[kNucWaves])
 
 __global__ __launch_bounds__(kNucThreads) void nucleus_rows_kernel(const float* __restrict__ logits, long ld_logits, int V,
                                                                    float inv_T, float top_p, unsigned long long seed,
-                                                                   unsigned step, unsigned row0, long long* __restrict__ tok,
-                                                                   long long* __restrict__ ids, float* __restrict__ logp, long ld) {
+                                                                   unsigned step, unsigned row0, unsigned greedy_stride,
+                                                                   long long* __restrict__ tok, long long* __restrict__ ids,
+                                                                   float* __restrict__ logp, long ld) {
   extern __shared__ float cache[];                     // the row's scaled logits where V <= kNucLdsEntries
   __shared__ float part[kNucCand][kNucWaves];
   __shared__ float pk[kNucWaves], ps[kNucWaves];
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(kNucThreads) void nucleus_rows_kernel(const float* 
     const float s = at(v);
     if (!(s > -INFINITY) || nuc_ckey(s, v) < cut) continue;
     kept[0] += expf(s - M);
-    const float key = vs_key(s, seed, step, row0 + (unsigned)row, (unsigned)v);
+    const float key = vs_row_key(s, seed, step, row0 + (unsigned)row, greedy_stride, (unsigned)v);
     if (vocab_better(key, v, bk, bi)) { bk = key; bi = v; bs = s; }
   }
   nuc_sum(kept, part);
@@ -191,8 +192,9 @@ __global__ __launch_bounds__(kNucThreads) void nucleus_rows_kernel(const float* 
 // one thread per row over the row's k candidates (k <= 16), walked in the total order
 __global__ __launch_bounds__(256) void nucleus_pick_kernel(const float* __restrict__ values, const int* __restrict__ index, int rows,
                                                            int k, int V, float inv_T, float top_p, unsigned long long seed,
-                                                           unsigned step, unsigned row0, long long* __restrict__ tok,
-                                                           long long* __restrict__ ids, float* __restrict__ logp, long ld) {
+                                                           unsigned step, unsigned row0, unsigned greedy_stride,
+                                                           long long* __restrict__ tok, long long* __restrict__ ids,
+                                                           float* __restrict__ logp, long ld) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   const float* val = values + (long)row * k;
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(256) void nucleus_pick_kernel(const float* __restri
   v = -1;
   while (kept < edge && next(s, v, s, v)) {              // kept is before(v) of the candidate that comes next
     kept += expf(s - M);
-    const float key = vs_key(s, seed, step, row0 + (unsigned)row, (unsigned)v);
+    const float key = vs_row_key(s, seed, step, row0 + (unsigned)row, greedy_stride, (unsigned)v);
     if (vocab_better(key, v, bk, bi)) { bk = key; bi = v; bs = s; }
   }
   const bool none = bi == kVocNone;
@@ -233,22 +235,24 @@ __global__ __launch_bounds__(256) void nucleus_pick_kernel(const float* __restri
 }
 
 int nucleus_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, float top_p, unsigned long long seed,
-                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream) {
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                 unsigned greedy_stride) {
   CAPNET_REQUIRE(rows >= 1 && V >= 1 && V <= (1 << 24) && ld_logits >= V, "nucleus_rows: rows %d, V %d, ld %ld", rows, V, ld_logits);
   CAPNET_REQUIRE(top_p > 0.f && top_p < 1.f, "nucleus_rows: top_p %g (0 < top_p < 1)", (double)top_p);
   const size_t lds = V <= kNucLdsEntries ? (size_t)V * sizeof(float) : 0;
   hipLaunchKernelGGL(nucleus_rows_kernel, dim3(rows), dim3(kNucThreads), lds, stream, logits, ld_logits, V, inv_T, top_p, seed, step,
-                     row0, tok, ids, logp, ld);
+                     row0, greedy_stride, tok, ids, logp, ld);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
 
 int nucleus_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, float top_p, unsigned long long seed,
-                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream) {
+                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                 unsigned greedy_stride) {
   CAPNET_REQUIRE(rows >= 1 && k >= 1 && k <= 16 && V >= 1, "nucleus_pick: rows %d, k %d, V %d", rows, k, V);
   CAPNET_REQUIRE(top_p > 0.f && top_p < 1.f, "nucleus_pick: top_p %g (0 < top_p < 1)", (double)top_p);
   hipLaunchKernelGGL(nucleus_pick_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, values, index, rows, k, V, inv_T, top_p,
-                     seed, step, row0, tok, ids, logp, ld);
+                     seed, step, row0, greedy_stride, tok, ids, logp, ld);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

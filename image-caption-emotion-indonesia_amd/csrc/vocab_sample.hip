@@ -2,6 +2,8 @@
 // capnet_sample_pick, capnet_sample_rows; the sampling loops around them: decode_loops.hip).
 //   z[r][v] = h[r] . W[v] + b[v]        h [rows][H], W [V][H] (nn.Linear), b [V]
 //   s = z inv_T,  key = s + sample_gumbel(sample_uniform(seed, step, row0 + r, v))          (sample_rng.h)
+//   (greedy_stride > 0: every greedy_stride-th row is a greedy row, key = s, and the drawn rows keep the noise rows they have
+//   without it: vs_row_key in sample_key.h, which every kernel here takes its keys from)
 //   tok[r] = argmax_v key (ties to the lower v),  logp[r] = s[tok] - log sum_v exp(s)
 // Gumbel-max: the argmax of the noised scaled logits IS a draw from softmax(z / T), so sampling is vocab_argmax with
 // counter-based noise in the epilogue; no prefix sum over the vocabulary. The noise is a pure function of (seed, step, row,
@@ -44,6 +46,7 @@ struct VocabSampleArgs {
   float inv_T;
   unsigned long long seed;
   unsigned step, row0;
+  unsigned greedy_stride;     // sample_key.h's vs_row_key: 0 = no greedy rows
 };
 
 template <int NJ, int TM>
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(512) void vocab_sample_kernel(VocabSampleArgs a) {
     const float s = vs_scaled(z, a.inv_T);
     const bool ok = ecol < a.V && s > -INFINITY;          // NaN fails the comparison
     const float ps = ok ? s : -INFINITY;
-    float bk = ok ? vs_key(s, a.seed, a.step, a.row0 + (unsigned)row, (unsigned)ecol) : -INFINITY;
+    float bk = ok ? vs_row_key(s, a.seed, a.step, a.row0 + (unsigned)row, a.greedy_stride, (unsigned)ecol) : -INFINITY;
     int bi = ok ? ecol : kVocNone;
     float bs = ps;
 #pragma unroll
@@ -135,8 +138,8 @@ __global__ __launch_bounds__(512) void vocab_sample_kernel(VocabSampleArgs a) {
 // one thread per row over the row's k candidates (k <= 16), in list order
 __global__ __launch_bounds__(256) void sample_pick_kernel(const float* __restrict__ values, const int* __restrict__ index, int rows,
                                                           int k, int V, float inv_T, unsigned long long seed, unsigned step,
-                                                          unsigned row0, long long* __restrict__ tok, long long* __restrict__ ids,
-                                                          float* __restrict__ logp, long ld) {
+                                                          unsigned row0, unsigned greedy_stride, long long* __restrict__ tok,
+                                                          long long* __restrict__ ids, float* __restrict__ logp, long ld) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   float bk = -INFINITY, bs = -INFINITY, M = -INFINITY;
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(const float* __restric
     const int v = index[(long)row * k + j];
     const float s = vs_scaled(values[(long)row * k + j], inv_T);
     if (v < 0 || v >= V || !(s > -INFINITY)) continue;      // padding, or nothing to pick
-    const float key = vs_key(s, seed, step, row0 + (unsigned)row, (unsigned)v);
+    const float key = vs_row_key(s, seed, step, row0 + (unsigned)row, greedy_stride, (unsigned)v);
     if (vocab_better(key, v, bk, bi)) { bk = key; bi = v; bs = s; }
     M = fmaxf(M, s);
   }
@@ -169,8 +172,8 @@ constexpr int kSrThreads = 256;
 
 __global__ __launch_bounds__(kSrThreads) void sample_rows_kernel(const float* __restrict__ logits, long ld_logits, int V, float inv_T,
                                                                  unsigned long long seed, unsigned step, unsigned row0,
-                                                                 long long* __restrict__ tok, long long* __restrict__ ids,
-                                                                 float* __restrict__ logp, long ld) {
+                                                                 unsigned greedy_stride, long long* __restrict__ tok,
+                                                                 long long* __restrict__ ids, float* __restrict__ logp, long ld) {
   __shared__ float sk[kSrThreads], ss[kSrThreads], sm[kSrThreads];
   __shared__ int si[kSrThreads];
   const int row = blockIdx.x, tid = threadIdx.x;
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(kSrThreads) void sample_rows_kernel(const float* __
   for (int v = tid; v < V; v += kSrThreads) {
     const float s = vs_scaled(x[v], inv_T);
     if (!(s > -INFINITY)) continue;
-    const float key = vs_key(s, seed, step, row0 + (unsigned)row, (unsigned)v);
+    const float key = vs_row_key(s, seed, step, row0 + (unsigned)row, greedy_stride, (unsigned)v);
     if (vocab_better(key, v, bk, bi)) { bk = key; bi = v; bs = s; }
     M = fmaxf(M, s);
   }
@@ -233,7 +236,7 @@ size_t vocab_sample_ws_bytes(int rows, int V) {
 
 int vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float inv_T, unsigned long long seed,
                  unsigned step, unsigned row0, void* ws, long long* tok, long long* ids, float* logp, long ld,
-                 hipStream_t stream) {
+                 hipStream_t stream, unsigned greedy_stride) {
   CAPNET_REQUIRE(rows >= 1 && V >= 1 && vocab_sample_supported(H), "vocab_sample: rows %d, H %d, V %d", rows, H, V);
   const size_t cells = (size_t)vocab_workgroups(V) * rows;
   VocabSampleArgs a;
@@ -244,7 +247,7 @@ int vocab_sample(const float* h, const float* w, const float* b, int rows, int H
   a.sval = reinterpret_cast<unsigned*>(a.stat + cells);
   a.tok = tok; a.ids = ids; a.logp = logp; a.ld = ld;
   a.rows = rows; a.H = H; a.V = V;
-  a.inv_T = inv_T; a.seed = seed; a.step = step; a.row0 = row0;
+  a.inv_T = inv_T; a.seed = seed; a.step = step; a.row0 = row0; a.greedy_stride = greedy_stride;
   const dim3 grid(vocab_workgroups(V)), block(64 * kVocWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
     hipLaunchKernelGGL((vocab_sample_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
@@ -254,19 +257,20 @@ int vocab_sample(const float* h, const float* w, const float* b, int rows, int H
 }
 
 int sample_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, unsigned long long seed,
-                unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream) {
+                unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
+                unsigned greedy_stride) {
   CAPNET_REQUIRE(rows >= 1 && k >= 1 && k <= 16 && V >= 1, "sample_pick: rows %d, k %d, V %d", rows, k, V);
   hipLaunchKernelGGL(sample_pick_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, values, index, rows, k, V, inv_T, seed,
-                     step, row0, tok, ids, logp, ld);
+                     step, row0, greedy_stride, tok, ids, logp, ld);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
 
 int sample_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, unsigned long long seed, unsigned step,
-                unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream) {
+                unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream, unsigned greedy_stride) {
   CAPNET_REQUIRE(rows >= 1 && V >= 1 && ld_logits >= V, "sample_rows: rows %d, V %d, ld %ld", rows, V, ld_logits);
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(kSrThreads), 0, stream, logits, ld_logits, V, inv_T, seed, step, row0, tok,
-                     ids, logp, ld);
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(kSrThreads), 0, stream, logits, ld_logits, V, inv_T, seed, step, row0,
+                     greedy_stride, tok, ids, logp, ld);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

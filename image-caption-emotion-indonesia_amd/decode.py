@@ -18,6 +18,9 @@ mode selects, the layout of their beam state, their weight fold.
     same (step_fn, state) pair: one C call on the PlainStack / AttStack (ops.sample_decode / ops.att_sample_decode) or the
     composed loop step_fn -> draw_step, the same stream and so the same tokens. CAPNET_NO_FUSED_SAMPLE=1 (read at every
     call) takes the composed loop.
+    greedy=True: the image's greedy caption as one more row of the same decode (csrc/sample_key.h: no noise on that row, the
+    drawn rows on the noise rows they have without it) -- the self-critical baseline without a second search;
+    sample_random_device also returns the raw ids / logp on the device, for a reward computed there (ops.bleu_rows).
   * pack_samples / policy_logits / score_captions: drawn captions back through the teacher-forced forward, whose step-t
     distribution is the one sample_random drew word t from -- what capnet.train.policy_step differentiates and what every
     image decoder's score_captions reports (the model's log-probability of given captions).
@@ -232,9 +235,10 @@ FUSED_SAMPLE_OFF = "CAPNET_NO_FUSED_SAMPLE"
 # loses at 64 in three cells of four (one workgroup merges all rows); 13 to 63 rows were not measured. Above it sample_random
 # takes the composed loop.
 FUSED_SAMPLE_MAX_ROWS = 12
-# the same for the attention decoders, where the one call also spares the per-row copies of the maps: the one measured shape,
-# 12 images x 5 samples, wins 2.6x to 3.1x; nothing larger was measured
-FUSED_ATT_SAMPLE_MAX_ROWS = 60
+# the same for the attention decoders, where the one call also spares the per-row copies of the maps: 12 images at 60, 72 (5
+# samples and the greedy row of sample_random(greedy=True)) and 96 physical rows, top_k 0 and 5 -- it wins 2.0x to 3.3x at all
+# three; nothing larger was measured
+FUSED_ATT_SAMPLE_MAX_ROWS = 96
 
 
 # the thresholds of the nucleus draw (top_p < 1), from their own measurement by the same rule (tools/time_nucleus.py,
@@ -246,8 +250,9 @@ FUSED_NUCLEUS_MAX_ROWS = 0
 #   after top_k the draw is vocab_topk + the pick: the one call wins 1.3x to 1.5x at 1 and 12 rows and loses at 64 rows x 3 layers, as
 #   FUSED_SAMPLE_MAX_ROWS found without a nucleus
 FUSED_NUCLEUS_TOPK_MAX_ROWS = 12
-#   the attention decoders, 12 images x 5 samples: 2.2x (top_k 0) and 2.7x (top_k 5); nothing larger was measured
-FUSED_ATT_NUCLEUS_MAX_ROWS = 60
+#   the attention decoders, 12 images x 5 samples: 2.2x (top_k 0) and 2.7x (top_k 5); at 72 and 96 rows 1.9x to 2.2x (the cells
+#   of FUSED_ATT_SAMPLE_MAX_ROWS at top_p 0.9); nothing larger was measured
+FUSED_ATT_NUCLEUS_MAX_ROWS = 96
 
 
 def fused_sample(rows, att=False, top_p=1.0, top_k=0):
@@ -260,21 +265,22 @@ def fused_sample(rows, att=False, top_p=1.0, top_k=0):
     return os.environ.get(FUSED_SAMPLE_OFF, "")[:1] != "1" and rows <= most
 
 
-def draw_step(logits, temperature, top_k, seed, step, top_p=1.0):
+def draw_step(logits, temperature, top_k, seed, step, top_p=1.0, greedy_stride=0):
     """The composed route's draw of stream step `step` from logits [rows, V] -> (tokens [rows] int64, logp [rows]): the
     stream and the arithmetic of the one-call route's (ops.sample_rows; top_k > 0: torch.topk's candidates into
     ops.sample_pick), so both routes return the same tokens wherever the best two keys are further apart than the logits'
     last bits. top_p < 1: the nucleus draw (ops.nucleus_rows; top_k > 0: ops.nucleus_pick on the same candidates); top_p ==
-    1.0 calls what it called before there was a top_p."""
+    1.0 calls what it called before there was a top_p. greedy_stride: ops.vocab_sample's (0: the calls as they were)."""
+    gs = {"greedy_stride": greedy_stride} if greedy_stride else {}
     if top_p == 1.0:
         if top_k == 0:
-            return ops.sample_rows(logits, temperature, seed, step)
+            return ops.sample_rows(logits, temperature, seed, step, **gs)
         values, index = torch.topk(logits, top_k, dim=1)
-        return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step)
+        return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step, **gs)
     if top_k == 0:
-        return ops.nucleus_rows(logits, temperature, top_p, seed, step)
+        return ops.nucleus_rows(logits, temperature, top_p, seed, step, **gs)
     values, index = torch.topk(logits, top_k, dim=1)
-    return ops.nucleus_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, top_p, seed, step)
+    return ops.nucleus_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, top_p, seed, step, **gs)
 
 
 def cut_samples(ids, logp, n, m, start_token, end_token):
@@ -291,7 +297,8 @@ def cut_samples(ids, logp, n, m, start_token, end_token):
     return out
 
 
-def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0):
+def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0,
+                         greedy=False):
     """`m` captions per image DRAWN from the decoder's distribution softmax(logits / temperature) (top_k > 0: renormalised
     over the top_k best words of every step; top_p < 1: over the nucleus, the smallest set of best words -- of the top_k
     where that is set -- whose probability reaches top_p; logprob is that of the distribution drawn from) -> n lists of m
@@ -302,35 +309,54 @@ def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature
     top_p < 1: FUSED_NUCLEUS_MAX_ROWS, FUSED_NUCLEUS_TOPK_MAX_ROWS, FUSED_ATT_NUCLEUS_MAX_ROWS) and CAPNET_NO_FUSED_SAMPLE is not 1; else step_fn ->
     draw_step per step. Both run dec.max_seq_length steps without looking
     at end_token (finished rows cost wasted steps; the host cuts), draw the same stream and so return the same lists.
-    seed: an integer makes the call a pure function; None draws one from torch's CPU generator."""
+    seed: an integer makes the call a pure function; None draws one from torch's CPU generator.
+    greedy: every image's m pairs are followed by one more, its GREEDY caption -- argmax_v logit_v at every step (ties to
+    the lower index), whatever the temperature, top_k or top_p, cut like the others, its logprob under the same distribution
+    as theirs. It is one more ROW of the same decode (physical row i (m + 1) + j is sample j of image i, row i (m + 1) + m
+    the greedy one; csrc/sample_key.h: the drawn rows keep noise row i m + j, so the first m pairs are those of the call
+    without the keyword): step_fn / state are then the class's _beam(...) for m + 1 rows per image, the row limits of the
+    routes apply to the n (m + 1) physical rows, and an attention decoder takes m + 1 <= 16.
+    Returns (the lists, ids int64 [rows, steps], logp float32 [rows, steps]): the decode's raw rows stay on the device beside
+    the cut lists, for what scores them there (ops.bleu_rows); sample_random returns the lists alone."""
     who = "sample_random"
     m, steps, V = int(m), int(dec.max_seq_length), dec.vocab_size
+    per = m + 1 if greedy else m                     # physical rows per image
+    gs = {"greedy_stride": per} if greedy else {}    # not greedy: the calls as they were before there was a greedy row
     temperature, top_k, seed, top_p = ops.check_sampling(who, temperature, top_k, seed, V, top_p)
     kw = {} if top_p == 1.0 else {"top_p": top_p}          # top_p == 1.0: the calls as they were before there was a top_p
-    if m < 1 or n < 1 or n * m >= ops.SAMPLE_MAX_ROWS or not 1 <= steps <= ops.SAMPLE_MAX_STEPS:
+    if m < 1 or n < 1 or n * per >= ops.SAMPLE_MAX_ROWS or not 1 <= steps <= ops.SAMPLE_MAX_STEPS:
         raise ops.CapnetError("%s: %d images x %d samples, %d steps" % (who, n, m, steps))
+    if greedy and is_attention(dec) and per > 16:
+        raise ops.CapnetError("%s: %d samples and the greedy row: an attention decoder takes at most 16 rows per image" % (who, m))
     dev = state[0].device
     with torch.no_grad():
         plain, att = getattr(step_fn, "plain", None), getattr(step_fn, "att", None)
-        if fused_sample(n * m, False, top_p, top_k) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
-            tokens = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
+        if fused_sample(n * per, False, top_p, top_k) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
+            tokens = torch.full((n * per,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp, _ = ops.sample_decode(plain.cell, steps, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb,
-                                             temperature, top_k, seed, start_tokens=tokens, **kw)
-        elif fused_sample(n * m, True, top_p, top_k) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
+                                             temperature, top_k, seed, start_tokens=tokens, **kw, **gs)
+        elif fused_sample(n * per, True, top_p, top_k) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
             ids, logp = ops.att_sample_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
-                                              att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, m, steps,
-                                              start_token, temperature, top_k, seed, **kw)
+                                              att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, per, steps,
+                                              start_token, temperature, top_k, seed, **kw, **({"greedy": True} if greedy else {}))
         else:
-            words = torch.full((n * m,), int(start_token), dtype=torch.int64, device=dev)
+            words = torch.full((n * per,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp = [], []
             for t in range(steps):
                 logits, state = step_fn(words, state)
-                words, lp = draw_step(logits, temperature, top_k, seed, t, **kw)
+                words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs)
                 ids.append(words)
                 logp.append(lp)
             ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)
     ops.check_device_errors()
-    return cut_samples(ids, logp, n, m, start_token, end_token)
+    return cut_samples(ids, logp, n, per, start_token, end_token), ids, logp
+
+
+def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0, device=False,
+                  greedy=False):
+    """The lists of sample_random_device; device=True: all it returns (lists, ids, logp)."""
+    out = sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temperature, top_k, seed, top_p, greedy)
+    return out if device else out[0]
 
 
 # ---- sampled captions back through the teacher-forced forward -----------------------------------------

@@ -655,7 +655,7 @@ class DecoderFactoredLSTM(nn.Module):
                            nbest=nbest, length_penalty=length_penalty)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, mode='factual',
-                      top_p=1.0):
+                      top_p=1.0, device=False, greedy=False):
         """`samples` captions per row of `features`, DRAWN from the decoder's distribution softmax(logits / temperature)
         (top_k > 0: renormalised over the top_k best words of every step;
         top_p < 1: over the nucleus) instead of searched for: a list of n lists of
@@ -663,10 +663,14 @@ class DecoderFactoredLSTM(nn.Module):
         max_seq_length words), logprob the float sum of the kept words' log-probabilities under the distribution sampled
         from. As in sample(), the image is not an input of the decode steps. seed: an integer makes the call a pure function
         of its arguments; None draws a 63-bit seed from torch's CPU generator (torch.manual_seed). One C call
-        (capnet_sample_decode) or the composed loop, the same lists: capnet.decode.sample_random."""
+        (capnet_sample_decode) or the composed loop, the same lists: capnet.decode.sample_random.
+        greedy=True: every image's pairs are followed by one more, its greedy caption (the argmax of every step), decoded as
+        one more row of the same call; the first `samples` pairs are those of the call without it.
+        device=True: (the lists, ids, logp), the decode's raw rows [n samples, max_seq_length] left on the device
+        (capnet.decode.sample_random_device)."""
         n = features.size(0)
-        return sample_random(self, *self._beam(n * int(samples), mode, True), n, samples, start_token, end_token, temperature,
-                             top_k, seed, top_p)
+        return sample_random(self, *self._beam(n * (int(samples) + bool(greedy)), mode, True), n, samples, start_token, end_token, temperature,
+                             top_k, seed, top_p, device, greedy)
 
     def score_captions(self, features, captions, mode='factual'):
         """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j], summed over

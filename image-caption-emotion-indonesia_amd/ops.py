@@ -921,18 +921,39 @@ def _check_stream_pos(who, rows, V, step, row0):
     return step, row0
 
 
+def _check_greedy_stride(who, greedy_stride, rows=None):
+    """greedy_stride of the sampling calls: 0 (off), or g >= 1 -- the rows come in groups of g, the last of each the group's
+    greedy row (csrc/sample_key.h); the loops need whole groups."""
+    if isinstance(greedy_stride, bool) or int(greedy_stride) != greedy_stride or not 0 <= int(greedy_stride) < SAMPLE_MAX_ROWS:
+        raise CapnetError("%s: greedy_stride=%r (0 = off, or the rows of a group)" % (who, greedy_stride))
+    if greedy_stride and rows is not None and rows % int(greedy_stride):
+        raise CapnetError("%s: %d rows in groups of greedy_stride %d" % (who, rows, greedy_stride))
+    return int(greedy_stride)
+
+
+def _call_sampler(name, greedy_stride, *args):
+    """capnet_<name>(*args, stream); with greedy rows capnet_<name>_greedy(*args, greedy_stride, stream)."""
+    if greedy_stride:
+        name, args = name + "_greedy", args + (greedy_stride,)
+    check(getattr(_lib.lib(), "capnet_" + name)(*(args + (current_stream(),))), "capnet_" + name)
+
+
 def vocab_sample_workspace(rows, V, device):
     """A zeroed workspace of capnet_vocab_sample for `rows` rows (back-to-back calls on one stream may share it)."""
     n = _lib.lib().capnet_vocab_sample_ws_bytes(int(rows), int(V))
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
-def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspace=None):
+def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspace=None, greedy_stride=0):
     """(tokens [rows] int64, logp [rows] float32): per row a draw from softmax((h[r] . w + b) / temperature) and its
     log-probability (capnet_vocab_sample: projection, Gumbel noise and argmax in one launch, no logits in memory). The noise
     of row r and entry v is a function of (seed, step, row0 + r, v) alone (sample_uniform). h [rows, H], w [V, H], b [V]; H
-    in DECODE_HIDDEN. A NaN or -inf logit is never drawn; a row with nothing to draw gives (0, -inf)."""
+    in DECODE_HIDDEN. A NaN or -inf logit is never drawn; a row with nothing to draw gives (0, -inf).
+    greedy_stride g > 0 (here and in sample_pick, sample_rows, nucleus_rows, nucleus_pick): the physical rows row0 + r come
+    in groups of g; the last of a group is its greedy row -- no noise: the argmax, ties to the lower index, logp under the
+    same distribution -- and row i g + j before it draws on noise row i (g - 1) + j, as in the call without greedy rows."""
     temperature, _, seed = check_sampling("vocab_sample", temperature, 0, seed)
+    greedy_stride = _check_greedy_stride("vocab_sample", greedy_stride)
     _need_cuda(h, w, b)
     h, w = _c(h.detach()), _c(w.detach())
     b = None if b is None else _c(b.detach())
@@ -949,16 +970,17 @@ def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspac
         raise CapnetError("vocab_sample: workspace too small")
     tokens = torch.empty(rows, dtype=torch.int64, device=h.device)
     logp = torch.empty(rows, dtype=torch.float32, device=h.device)
-    check(_lib.lib().capnet_vocab_sample(ptr(h), ptr(w), ptr(b), rows, H, V, temperature, seed, step, row0, ptr(workspace),
-                                         ptr(tokens), ptr(logp), current_stream()), "capnet_vocab_sample")
+    _call_sampler("vocab_sample", greedy_stride, ptr(h), ptr(w), ptr(b), rows, H, V, temperature, seed, step, row0, ptr(workspace),
+                  ptr(tokens), ptr(logp))
     return tokens, logp
 
 
-def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0):
+def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0, greedy_stride=0):
     """Top-k sampling on vocab_topk's (values, index) [rows, k], k <= 16 (capnet_sample_pick): (tokens [rows] int64, logp
     [rows] float32), the draw among the k candidates with the noise keyed by their vocabulary index and logp renormalised
     over the candidates. Padding slots (-inf, -1) are never drawn."""
     temperature, _, seed = check_sampling("sample_pick", temperature, 0, seed)
+    greedy_stride = _check_greedy_stride("sample_pick", greedy_stride)
     _need_cuda(values, index)
     values, index = _c(values.detach()), _c(index)
     if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
@@ -968,15 +990,16 @@ def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0):
     step, row0 = _check_stream_pos("sample_pick", rows, int(V), step, row0)
     tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
     logp = torch.empty(rows, dtype=torch.float32, device=values.device)
-    check(_lib.lib().capnet_sample_pick(ptr(values), ptr(index), rows, k, int(V), temperature, seed, step, row0, ptr(tokens),
-                                        ptr(logp), current_stream()), "capnet_sample_pick")
+    _call_sampler("sample_pick", greedy_stride, ptr(values), ptr(index), rows, k, int(V), temperature, seed, step, row0, ptr(tokens),
+                  ptr(logp))
     return tokens, logp
 
 
-def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0):
+def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0, greedy_stride=0):
     """vocab_sample's draw from logits [rows, V] in memory (capnet_sample_rows, one workgroup per row): (tokens [rows] int64,
     logp [rows] float32). Any V up to 2^24."""
     temperature, _, seed = check_sampling("sample_rows", temperature, 0, seed)
+    greedy_stride = _check_greedy_stride("sample_rows", greedy_stride)
     _need_cuda(logits)
     logits = logits.detach()
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -987,18 +1010,19 @@ def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0):
     step, row0 = _check_stream_pos("sample_rows", rows, V, step, row0)
     tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
     logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    check(_lib.lib().capnet_sample_rows(ptr(logits), rows, logits.stride(0), V, temperature, seed, step, row0, ptr(tokens),
-                                        ptr(logp), current_stream()), "capnet_sample_rows")
+    _call_sampler("sample_rows", greedy_stride, ptr(logits), rows, logits.stride(0), V, temperature, seed, step, row0, ptr(tokens),
+                  ptr(logp))
     return tokens, logp
 
 
-def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0):
+def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0, greedy_stride=0):
     """sample_rows' draw among the nucleus of every row (capnet_nucleus_rows): the smallest set of best entries -- scaled
     logit descending, index ascending -- whose probability reaches top_p, found exactly by one workgroup per row; logp is
     renormalised over that set. (tokens [rows] int64, logp [rows] float32). top_p == 1.0 is sample_rows itself."""
     temperature, _, seed, top_p = check_sampling("nucleus_rows", temperature, 0, seed, top_p=top_p)
     if top_p == 1.0:
-        return sample_rows(logits, temperature, seed, step, row0)
+        return sample_rows(logits, temperature, seed, step, row0, greedy_stride)
+    greedy_stride = _check_greedy_stride("nucleus_rows", greedy_stride)
     _need_cuda(logits)
     logits = logits.detach()
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -1009,18 +1033,19 @@ def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0):
     step, row0 = _check_stream_pos("nucleus_rows", rows, V, step, row0)
     tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
     logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    check(_lib.lib().capnet_nucleus_rows(ptr(logits), rows, logits.stride(0), V, temperature, top_p, seed, step, row0, ptr(tokens),
-                                         ptr(logp), current_stream()), "capnet_nucleus_rows")
+    _call_sampler("nucleus_rows", greedy_stride, ptr(logits), rows, logits.stride(0), V, temperature, top_p, seed, step, row0,
+                  ptr(tokens), ptr(logp))
     return tokens, logp
 
 
-def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0):
+def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0, greedy_stride=0):
     """top_k, then top_p (capnet_nucleus_pick): sample_pick's draw among the nucleus of the k candidates (values, index)
     [rows, k], probabilities renormalised over the k and logp over the kept ones; the order of the list does not matter.
     top_p == 1.0 is sample_pick itself."""
     temperature, _, seed, top_p = check_sampling("nucleus_pick", temperature, 0, seed, top_p=top_p)
     if top_p == 1.0:
-        return sample_pick(values, index, V, temperature, seed, step, row0)
+        return sample_pick(values, index, V, temperature, seed, step, row0, greedy_stride)
+    greedy_stride = _check_greedy_stride("nucleus_pick", greedy_stride)
     _need_cuda(values, index)
     values, index = _c(values.detach()), _c(index)
     if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
@@ -1030,8 +1055,8 @@ def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, r
     step, row0 = _check_stream_pos("nucleus_pick", rows, int(V), step, row0)
     tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
     logp = torch.empty(rows, dtype=torch.float32, device=values.device)
-    check(_lib.lib().capnet_nucleus_pick(ptr(values), ptr(index), rows, k, int(V), temperature, top_p, seed, step, row0, ptr(tokens),
-                                         ptr(logp), current_stream()), "capnet_nucleus_pick")
+    _call_sampler("nucleus_pick", greedy_stride, ptr(values), ptr(index), rows, k, int(V), temperature, top_p, seed, step, row0,
+                  ptr(tokens), ptr(logp))
     return tokens, logp
 
 
@@ -1046,20 +1071,23 @@ def vocab_topk_supported(H, k, V):
 
 
 def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed, first_inputs=None, start_tokens=None,
-                  state=None, top_p=1.0):
+                  state=None, top_p=1.0, greedy_stride=0):
     """`steps` sampled decode steps of a plain stack in ONE C call (capnet_sample_decode): per step one decode-step launch
     per layer and the draw (top_k == 0: capnet_vocab_sample; else capnet_vocab_topk + capnet_sample_pick), tokens and logits
     never leaving the device. wcat / beff: capnet.decode.pack_cell(s) of every layer; emb [V, E]; Cw [V, H], Cb [V] or None.
     The first input is first_inputs [rows, E] or emb[start_tokens] (int64 [rows]); state [rows, 2L, H] or None for zeros.
     Row r draws on stream row r, step t on stream step t. top_p < 1: the nucleus draw (capnet_sample_decode_nucleus: per step
     the projection into a logits block + capnet_nucleus_rows, or capnet_vocab_topk + capnet_nucleus_pick); top_p == 1.0 is
-    capnet_sample_decode. Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state [rows, 2L, H])."""
+    capnet_sample_decode. greedy_stride g > 0 (vocab_sample's; rows a multiple of g): every g-th row decodes greedily, the
+    others draw what they draw in the call of g - 1 rows per group without it (the capnet_*_greedy entries).
+    Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state [rows, 2L, H])."""
     who = "sample_decode"
     if (first_inputs is None) == (start_tokens is None):
         raise CapnetError("%s: either first_inputs or start_tokens" % who)
     rows, steps = (first_inputs if first_inputs is not None else start_tokens).shape[0], int(steps)
     emb, Cw, Cb, state, (V, E, H, nl) = _plain_stack(who, cell, wcat, beff, emb, Cw, Cb, state, rows)
     temperature, top_k, seed, top_p = check_sampling(who, temperature, top_k, seed, V, top_p)
+    greedy_stride = _check_greedy_stride(who, greedy_stride, rows)
     _need_cuda(first_inputs, start_tokens)
     if first_inputs is not None:
         first_inputs = _c(first_inputs.detach())
@@ -1084,14 +1112,13 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
     out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
     if top_p < 1.0:
         slab = splitk_slab(dev)
-        check(L.capnet_sample_decode_nucleus(cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb),
-                                             ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k,
-                                             top_p, seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out),
-                                             ptr(err_flag(dev)), current_stream()), "capnet_sample_decode_nucleus")
+        _call_sampler("sample_decode_nucleus", greedy_stride, cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens),
+                      ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, top_p, seed,
+                      ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out), ptr(err_flag(dev)))
         return ids, logp, out
-    check(L.capnet_sample_decode(cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb), ptr_array(wcat),
-                                 ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, seed, ptr(ws), ptr(ids),
-                                 ptr(logp), ptr(out), ptr(err_flag(dev)), current_stream()), "capnet_sample_decode")
+    _call_sampler("sample_decode", greedy_stride, cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb),
+                  ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, seed, ptr(ws), ptr(ids),
+                  ptr(logp), ptr(out), ptr(err_flag(dev)))
     return ids, logp, out
 
 
@@ -1515,12 +1542,14 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
 
 
 def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,
-                      temperature, top_k, seed, top_p=1.0):
+                      temperature, top_k, seed, top_p=1.0, greedy=False):
     """`steps` sampled decode steps of an attention decoder in ONE C call (capnet_att_sample_decode; top_p < 1:
     capnet_att_sample_decode_nucleus, the draw as ops.sample_decode's): n images x m samples
     each (row i m + j = sample j of image i), the step att_decode_step's with k = m and every row continuing from itself --
     an image's maps are read once per step for all its samples -- then the draw as ops.sample_decode's. Operands as
-    att_beam_decode; state [n m, 2L, H]: the initial state. Returns (ids [n m, steps] int64, logp [n m, steps] float32)."""
+    att_beam_decode; state [n m, 2L, H]: the initial state. Returns (ids [n m, steps] int64, logp [n m, steps] float32).
+    greedy: the last of an image's m rows decodes greedily (greedy_stride = m, ops.vocab_sample's) and the m - 1 before it draw
+    what the call with m - 1 rows per image draws: the greedy caption on the same read of the maps. m <= 16 either way."""
     who = "att_sample_decode"
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
         who, cell, att1, feat, m, emb, wz, bz, w_full, b_full, wcat, beff, state)
@@ -1545,11 +1574,12 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
     head = (cell, nl, n, m, P, A, Cdim, E, H, V, steps, ptr(tokens), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf),
             ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k)
-    tail = (seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None, ptr(err_flag(dev)), current_stream())
+    tail = (seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None, ptr(err_flag(dev)))
+    stride = m if greedy else 0
     if nucleus:
-        check(L.capnet_att_sample_decode_nucleus(*head, top_p, *tail), "capnet_att_sample_decode_nucleus")
+        _call_sampler("att_sample_decode_nucleus", stride, *head, top_p, *tail)
     else:
-        check(L.capnet_att_sample_decode(*head, *tail), "capnet_att_sample_decode")
+        _call_sampler("att_sample_decode", stride, *head, *tail)
     return ids, logp
 
 
@@ -1807,6 +1837,41 @@ def policy_loss(logits, targets, advantages, batch_sizes):
     (detached) the model's log-probability of every caption. advantages [B] float32 on the device, in the batch's
     sorted order; batch_sizes as ops.batch_sizes_from_lengths gives them."""
     return PolicyLossFn.apply(logits, targets, advantages, batch_sizes)
+
+
+BLEU_MAX_STEPS = 128          # capnet_bleu_rows: a hypothesis is [start] + at most this many decoded words
+BLEU_MAX_REFS = 16            # reference slots per image
+BLEU_MAX_REF_WORDS = 4096     # reference slots x padded reference length
+
+
+def bleu_rows(ids, start_token, end_token, per_image, refs, ref_len, weights=(0.25, 0.25, 0.25, 0.25), smooth=0, steps=None):
+    """(reward float32 [rows], stats int32 [rows, 10]) on the device: sentence BLEU of every row of a sampled decode against
+    the references of its image (capnet_bleu_rows) -- capnet.metrics.sentence_bleu of what decode.cut_samples makes of the
+    row. ids int64 [rows, ld] as the samplers leave them, the first `steps` columns read (None: all); row r belongs to image
+    r // per_image. refs int32 [images, R, Lr] zero padded and ref_len int32 [images, R] on the device, a length of 0 an
+    absent slot (capnet.train.DeviceBleuReward packs them). weights: four floats; smooth: 0, or 1 for add-one on n >= 2.
+    stats: num_1..4, den_1..4, the hypothesis length, the closest reference length. No host read."""
+    _need_cuda(ids, refs, ref_len)
+    if ids.dtype != torch.int64 or refs.dtype != torch.int32 or ref_len.dtype != torch.int32:
+        raise CapnetError("bleu_rows: ids must be int64, refs and ref_len int32")
+    if ids.dim() != 2 or refs.dim() != 3 or ref_len.dim() != 2 or tuple(ref_len.shape) != tuple(refs.shape[:2]):
+        raise CapnetError("bleu_rows: ids [rows, ld], refs [images, R, Lr], ref_len [images, R]; got %s, %s, %s"
+                          % (tuple(ids.shape), tuple(refs.shape), tuple(ref_len.shape)))
+    if ids.stride(1) != 1 or len(weights) != 4:
+        raise CapnetError("bleu_rows: the columns of ids must be adjacent, and there are four weights")
+    refs, ref_len = _c(refs), _c(ref_len)
+    rows = ids.shape[0]
+    steps = ids.shape[1] if steps is None else int(steps)
+    if not 1 <= steps <= ids.shape[1]:
+        raise CapnetError("bleu_rows: %d steps of %d columns" % (steps, ids.shape[1]))
+    images, R, Lr = refs.shape
+    reward = torch.empty(rows, dtype=torch.float32, device=ids.device)
+    stats = torch.empty((rows, 10), dtype=torch.int32, device=ids.device)
+    w = (C.c_double * 4)(*[float(x) for x in weights])
+    check(_lib.lib().capnet_bleu_rows(ptr(ids), ids.stride(0), rows, steps, int(start_token), int(end_token), int(per_image),
+                                      ptr(refs), ptr(ref_len), images, R, Lr, w, int(smooth), ptr(reward), ptr(stats),
+                                      current_stream()), "capnet_bleu_rows")
+    return reward, stats
 
 
 class AttentionLossFn(torch.autograd.Function):

@@ -2,8 +2,9 @@
 
   train_step     one iteration of the bodies of train_factual / train_emotion
                  (stylenet/train_multitask.py:373-389, 527-537; nic/train_transfer_fac.py:252-296)
-  policy_step / self_critical_step / bleu_reward   reward-based fine-tuning on sampled captions (self-critical sequence
-                 training, Rennie et al. 2017; no counterpart in the reference)
+  policy_step / self_critical_step / bleu_reward / DeviceBleuReward   reward-based fine-tuning on sampled captions
+                 (self-critical sequence training, Rennie et al. 2017; no counterpart in the reference); with a
+                 DeviceBleuReward the rewards and advantages are computed on the device (ops.bleu_rows)
   train_factual  stylenet/train_multitask.py:364-408
   train_emotion  stylenet/train_multitask.py:511-557
   val_factual / val_emotion   stylenet/train_multitask.py:272-361, 411-508 (eval-mode trunk on the
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import decode, ops
-from .metrics import corpus_bleu
+from .metrics import corpus_bleu, sentence_bleu
 from .utils import AverageMeter, accuracy, clip_gradient
 
 
@@ -114,16 +115,25 @@ def policy_step(decoder, optimizer, features, captions, advantages, grad_clip, m
     log-probability of every caption before the update, float32 on the device in the caller's order.
 
     captions: a flat list of token lists [start, w_1 .. w_j] (caption r on row r of `features`) or the nested list
-    sample_random returns (capnet.decode.flat_captions); advantages: one float per caption, in the same (flattened) order.
+    sample_random returns (capnet.decode.flat_captions); advantages: one float per caption, in the same (flattened) order -- a
+    list, a host tensor, or a tensor on the decoder's device, which is permuted into the batch's order there and never read
+    by the host (the same float32 values, so the same loss to the last bit).
     Deterministic: every step is teacher forced, so `random` is not consumed. Order of operations: pack ->
     capnet.decode.policy_logits -> ops.policy_loss -> zero_grad -> backward -> clip_gradient -> optimizer.step.
     features: the decoder's input, not images -- no encoder parameter receives a gradient (a plain decoder does not read
     them at all; an attention decoder's trunk is frozen). mode: as train_step's; loss_scale: _backward's."""
     inputs, lengths, targets, order, feats = decode.policy_batch(decoder, features, captions)
-    adv = [float(a) for a in (advantages.tolist() if torch.is_tensor(advantages) else advantages)]
-    if len(adv) != len(order):
-        raise ops.CapnetError("policy_step: %d advantages for %d captions" % (len(adv), len(order)))
-    adv = torch.tensor([adv[r] for r in order], dtype=torch.float32).to(inputs.device)
+    if torch.is_tensor(advantages) and advantages.device == inputs.device and advantages.is_cuda:
+        # advantages that were formed on the device stay there: permuted into the batch's order by a gather, no host read
+        if advantages.numel() != len(order):
+            raise ops.CapnetError("policy_step: %d advantages for %d captions" % (advantages.numel(), len(order)))
+        adv = advantages.detach().reshape(-1).to(torch.float32).index_select(
+            0, torch.tensor(order, dtype=torch.int64).to(inputs.device))
+    else:
+        adv = [float(a) for a in (advantages.tolist() if torch.is_tensor(advantages) else advantages)]
+        if len(adv) != len(order):
+            raise ops.CapnetError("policy_step: %d advantages for %d captions" % (len(adv), len(order)))
+        adv = torch.tensor([adv[r] for r in order], dtype=torch.float32).to(inputs.device)
     logits = decode.policy_logits(decoder, inputs, lengths, feats, mode)
     loss, logp = ops.policy_loss(logits, targets, adv, ops.batch_sizes_from_lengths(lengths))
     decoder.zero_grad()
@@ -160,12 +170,35 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     distribution they were drawn from.
     features: as policy_step's. Returns {'loss': the device loss, 'reward_mean', 'baseline_mean', 'advantage_abs_mean':
     floats over all samples, 'zero_rows': the captions whose advantage is exactly 0 (under 'greedy': the samples that
-    scored what the greedy caption did, the greedy caption itself among them)}."""
+    scored what the greedy caption did, the greedy caption itself among them)}.
+
+    reward a DeviceBleuReward: the device route. 'greedy': ONE decode, decoder.sample_random(greedy=True) -- the greedy
+    caption is one more row per image of the sampled decode, not a second search (it is the width-1 beam's caption wherever
+    that one reaches <end> within max_seq_length) -- and ONE ops.bleu_rows launch over all n (samples + 1) rows, on the ids
+    the sampler left on the device; advantage = reward[drawn] - reward[greedy row of its image], exactly 0 where the two
+    float32 rewards are equal. 'mean': the same launch without the greedy row and mean_baseline's formula in fp64. The
+    advantages are rounded once to float32 and policy_step takes them as a device tensor: the host reads the ids once, for
+    packing, and computes no reward and no advantage. The dict's 'reward_mean', 'baseline_mean', 'advantage_abs_mean' (fp64)
+    and 'zero_rows' (int64) are then 0-d device tensors -- reading one is the caller's synchronisation."""
     if baseline not in ("greedy", "mean"):
         raise ValueError("baseline %r (expected 'greedy' or 'mean')" % (baseline,))
     if baseline == "mean" and int(samples) < 2:
         raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
     kw = {} if mode is None else {"mode": mode}
+    if isinstance(reward, DeviceBleuReward):
+        m, greedy = int(samples), baseline == "greedy"
+        drawn, ids, _ = decoder.sample_random(features, start_token, end_token, samples=m, temperature=temperature, top_k=top_k,
+                                              seed=seed, top_p=top_p, device=True, greedy=greedy, **kw)
+        r = reward.rows(ids, start_token, end_token, m + greedy)[0].double().view(-1, m + greedy)
+        if greedy:
+            drawn, base, r = [row[:m] for row in drawn], r[:, m:].expand(-1, m), r[:, :m]
+        else:
+            base = (r.sum(1, keepdim=True) - r) / (m - 1)
+        adv = (r - base).reshape(-1)
+        loss, _ = policy_step(decoder, optimizer, features, drawn, adv.to(torch.float32), grad_clip, mode=mode,
+                              loss_scale=loss_scale)
+        return {"loss": loss, "reward_mean": r.mean(), "baseline_mean": base.mean(), "advantage_abs_mean": adv.abs().mean(),
+                "zero_rows": (adv == 0).sum()}
     drawn = decoder.sample_random(features, start_token, end_token, samples=samples, temperature=temperature, top_k=top_k,
                                   seed=seed, top_p=top_p, **kw)
     rewards = [[float(reward(i, tokens)) for tokens, _ in row] for i, row in enumerate(drawn)]
@@ -191,6 +224,69 @@ def bleu_reward(references, weights=(0.25, 0.25, 0.25, 0.25)):
     def reward(i, tokens):
         return corpus_bleu([references[i]], [[int(w) for w in tokens]], weights=weights)
     return reward
+
+
+class DeviceBleuReward(object):
+    """bleu_reward whose arithmetic can stay on the device: sentence BLEU (capnet.metrics.sentence_bleu; smooth=1: add-one
+    on n >= 2, so a caption without a matching 4-gram still scores) against references[i], the reference token lists of
+    image i, taken as they are. The references are packed once (pack) and uploaded once per device; rows() scores every
+    row of a sampled decode there (ops.bleu_rows). Called as reward(i, tokens) it is a host reward like bleu_reward's, so
+    it serves wherever one does. self_critical_step takes the device route for it (see there).
+    Every image needs at least one non-empty reference; at most ops.BLEU_MAX_REFS references per image and
+    ops.BLEU_MAX_REF_WORDS words in an image's padded block (references x the longest reference): ValueError beyond."""
+
+    def __init__(self, references, weights=(0.25, 0.25, 0.25, 0.25), smooth=0, device=None):
+        if len(weights) != 4:
+            raise ValueError("DeviceBleuReward: four weights (BLEU-1 .. BLEU-4), not %d" % len(weights))
+        if smooth not in (0, 1):
+            raise ValueError("smooth %r (0: none, 1: add one for n >= 2)" % (smooth,))
+        self.references = [[[int(w) for w in r] for r in refs] for refs in references]
+        self.weights, self.smooth = tuple(float(w) for w in weights), int(smooth)
+        self.refs, self.ref_len = self.pack(self.references)
+        self._on = {}
+        if device is not None:
+            self.on(device)
+
+    @staticmethod
+    def pack(references):
+        """references [image][reference][word] -> (refs int32 [n, R, Lr] zero padded, ref_len int32 [n, R]) on the host: R
+        the most references of an image, Lr the longest reference; an image with fewer references, or an empty one among
+        them, has slots of length 0, which the kernel skips."""
+        if not len(references):
+            raise ValueError("DeviceBleuReward: no images")
+        R = max(len(refs) for refs in references)
+        Lr = max([len(r) for refs in references for r in refs] + [0])
+        if any(not any(len(r) for r in refs) for refs in references):
+            raise ValueError("DeviceBleuReward: every image needs at least one non-empty reference")
+        if R > ops.BLEU_MAX_REFS or R * Lr > ops.BLEU_MAX_REF_WORDS:
+            raise ValueError("DeviceBleuReward: %d references of up to %d words (at most %d references, %d padded words per "
+                             "image)" % (R, Lr, ops.BLEU_MAX_REFS, ops.BLEU_MAX_REF_WORDS))
+        refs = torch.zeros((len(references), R, Lr), dtype=torch.int32)
+        ref_len = torch.zeros((len(references), R), dtype=torch.int32)
+        for i, rr in enumerate(references):
+            for j, r in enumerate(rr):
+                if len(r):
+                    refs[i, j, :len(r)] = torch.tensor(r, dtype=torch.int32)
+                    ref_len[i, j] = len(r)
+        return refs, ref_len
+
+    def on(self, device):
+        """(refs, ref_len) on `device`, uploaded at the first call for it."""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = (self.refs.to(device), self.ref_len.to(device))
+        return self._on[device]
+
+    def __call__(self, i, tokens):
+        return sentence_bleu(self.references[i], [int(w) for w in tokens], self.weights, self.smooth)
+
+    def rows(self, ids, start_token, end_token, per_image):
+        """(reward float32 [rows], stats int32 [rows, 10]) on the device for the ids [images x per_image, steps] of a
+        sampled decode of all the images, in order (ops.bleu_rows)."""
+        if ids.shape[0] != len(self.references) * int(per_image):
+            raise ops.CapnetError("DeviceBleuReward: %d rows for %d images x %d" % (ids.shape[0], len(self.references), per_image))
+        refs, ref_len = self.on(ids.device)
+        return ops.bleu_rows(ids, start_token, end_token, per_image, refs, ref_len, self.weights, self.smooth)
 
 
 class TrunkPipeline(object):

@@ -796,6 +796,59 @@ int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P,
                                      void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
                                      float* state_out, int* err_flag, capnet_stream_t stream);
 
+/* The sampling entries with greedy rows: each capnet_X_greedy is capnet_X with one more argument, greedy_stride, in front of
+ * the stream; with greedy_stride 0 it is capnet_X, bit for bit. greedy_stride g >= 1: the rows (for the stand-alone draws
+ * the PHYSICAL rows row0 + r) come in groups of g, an image's: row i g + j, j < g - 1, is sample j of image i and draws
+ * with the noise row i (g - 1) + j -- the row it has in the same call without greedy rows and g - 1 rows per image, so its
+ * tokens and log-probabilities are those of that call; row i g + g - 1 is the image's GREEDY row: its key is the scaled
+ * logit itself, so its token is argmax_v logit_v (ties to the lower index), whatever the temperature, top_k or top_p (the
+ * best word is in every truncation), and its logp is taken under the same distribution as a drawn row's. The loops
+ * require rows % g == 0; the attention loops g == m (the decode step then runs m rows per image on one read of the maps,
+ * m <= 16). The self-critical baseline of capnet.train.self_critical_step: one more row per image, not a second search. */
+int capnet_vocab_sample_greedy(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                               unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
+                               float* logp, unsigned greedy_stride, capnet_stream_t stream);
+int capnet_sample_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature,
+                              unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                              unsigned greedy_stride, capnet_stream_t stream);
+int capnet_sample_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                              unsigned step, unsigned row0, long long* tokens, float* logp, unsigned greedy_stride,
+                              capnet_stream_t stream);
+int capnet_sample_decode_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                const long long* start_tokens, const float* emb, const float* const* wcat,
+                                const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
+                                float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                                capnet_stream_t stream);
+int capnet_nucleus_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                               unsigned greedy_stride, capnet_stream_t stream);
+int capnet_nucleus_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                               unsigned greedy_stride, capnet_stream_t stream);
+int capnet_sample_decode_nucleus_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps,
+                                        const float* first_inputs, const long long* start_tokens, const float* emb,
+                                        const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                        const float* state0, float temperature, int top_k, float top_p,
+                                        unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                                        long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                                        capnet_stream_t stream);
+int capnet_att_sample_decode_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                    const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                    const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                    const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                    const float* state0, float temperature, int top_k, unsigned long long seed,
+                                    void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                    float* state_out, int* err_flag, unsigned greedy_stride, capnet_stream_t stream);
+int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
+                                            int steps, const long long* start_tokens, const float* att1, const float* feat,
+                                            const float* emb, const float* wz, const float* bz, const float* w_full,
+                                            const float* b_full, const float* const* wcat, const float* const* beff,
+                                            const float* Cw, const float* Cb, const float* state0, float temperature,
+                                            int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
+                                            size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                                            unsigned greedy_stride, capnet_stream_t stream);
+
 /* capnet_vocab_topk for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's rows
  * are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL; every
  * w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival counter
@@ -1104,6 +1157,24 @@ int capnet_policy_xent_fwd(const float* logits, long ld, int N, int V, const lon
 int capnet_policy_xent_bwd(const float* logits, long ld, int N, int V, const long long* targets, const float* lse,
                            const float* advantages, int B, const int* batch_sizes, int steps, const float* grad_out,
                            float* dlogits, long ldd, capnet_stream_t stream);
+/* The reward of decoded captions: sentence BLEU of every row of a sampled decode against the references of its image.
+ * ids int64 [rows][ld] as the sampling loops write them, `steps` columns (1 .. 128, ld >= steps). The hypothesis of a row
+ * is [start_token] + its ids through the first end_token inclusive (none: all `steps` columns); columns behind the first
+ * end_token do not enter the result. Row r belongs to image r / per_image (rows <= images * per_image).
+ * refs int32 [images][R][Lr], zero padded, ref_len int32 [images][R] (device): reference slot (i, j) holds ref_len[i][j]
+ * words, taken as they are; a length of 0 is an absent slot (skipped), a length outside [0, Lr] is clamped into it.
+ * Limits: R <= 16 and R * Lr <= 4096. weights: four doubles on the HOST; smooth 0 or 1.
+ *   num_n = sum over the distinct n-grams of the hypothesis of min(its count there, the MAXIMUM over the references of its
+ *           count in a reference),  den_n = max(1, L - n + 1),  L the hypothesis' words
+ *   closest = the reference length nearest to L, ties to the shorter;  bp = 1 if L > closest else exp(1 - closest / L)
+ *   reward = bp * exp(sum_n weights[n] log(num_n / den_n)), 0 where L is 0 or any num_n is 0 (whatever its weight)
+ *   smooth 1 (Lin & Och 2004, add one): (num_n + 1) / (den_n + 1) in place of num_n / den_n for n >= 2; then the reward
+ *   is 0 only where num_1 is 0.
+ * reward float32 [rows]: formed in fp64 and rounded once. stats int32 [rows][10]: num_1..4, den_1..4, L, closest (0 where
+ * the image has no reference). One workgroup per row; integer sums only, so the result does not depend on any order. */
+int capnet_bleu_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token,
+                     int per_image, const int* refs, const int* ref_len, int images, int R, int Lr, const double* weights,
+                     int smooth, float* reward, int* stats, capnet_stream_t stream);
 
 /* ---- input pipeline (stylenet/train_multitask.py:62-69: Resize((336,336)) -> RandomCrop(224) ->
  * RandomHorizontalFlip -> ToTensor -> Normalize) on uint8 HWC device images ----------------------

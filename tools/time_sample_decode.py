@@ -16,10 +16,12 @@ Cells:
   att   DecoderFactoredLSTMAtt at BASELINE configs[3]'s sizes (attention 512, embedding 300, hidden 512, factored 1024, maps
         of 2048 channels) on 7 x 7, 12 images x 5 samples, 20 steps, top_k 0 / 5; the yardstick is sample_batch(one_call=True)
         at k = 5 (a beam search: the same step on the same 60 rows, plus its bookkeeping)
+  att_rows  the same decoder at 60 / 72 / 96 physical rows: 12 x 5, 12 x 5 with the greedy row of sample_random(greedy=True)
+        and 12 x 7 with it, top_k 0 / 5 x top_p 1 / 0.9 -- what FUSED_ATT_SAMPLE_MAX_ROWS / FUSED_ATT_NUCLEUS_MAX_ROWS are set from
 Every route of a cell must return the same tokens where the restatement's margins allow; random weights do not guarantee
 that, so the tool reports "same_tokens" and does not fail on it.
 
-usage: python tools/time_sample_decode.py [--cells seq,att] [--rows 1,12,64] [--layers 1,3] [--reps R] [--warmup W]
+usage: python tools/time_sample_decode.py [--cells seq,att,att_rows] [--rows 1,12,64] [--layers 1,3] [--reps R] [--warmup W]
 """
 import argparse
 import json
@@ -112,6 +114,26 @@ def cell_att(a, dev):
               "same_tokens": tokens["one_call"] == tokens["composed"]})
 
 
+def cell_att_rows(a, dev):
+    """The attention decoder of cell `att` at 60, 72 and 96 physical rows: 12 images x 5 samples, the same with the greedy row
+    (12 x 6: capnet.train.self_critical_step's greedy baseline) and 12 x 7 with it (12 x 8); top_k 0 / 5 x top_p 1 / 0.9."""
+    A, F, CF, n, steps = 512, 1024, 2048, 12, 20
+    torch.manual_seed(3)
+    dec = DecoderFactoredLSTMAtt(A, E, H, F, V, 1, feature_size=CF, dropout=0.0, max_seq_length=steps).to(dev).eval()
+    feats = torch.rand(n, 7, 7, CF, device=dev)
+    for m, greedy in ((5, False), (5, True), (7, True)):
+        for top_k in (0, 5):
+            for top_p in (1.0, 0.9):
+                kw = dict(samples=m, temperature=1.0, top_k=top_k, top_p=top_p, seed=7, greedy=greedy)
+                res, last = compare({"one_call": (True, lambda: dec.sample_random(feats, 1, V, **kw)),
+                                     "composed": (False, lambda: dec.sample_random(feats, 1, V, **kw))}, a.reps, a.warmup)
+                tokens = {k: [q for img in last[k] for q, _ in img] for k in ("one_call", "composed")}
+                emit({"tool": "time_sample_decode", "cell": "att_rows", "decoder": "DecoderFactoredLSTMAtt", "A": A, "E": E, "H": H,
+                      "F": F, "V": V, "C": CF, "P": 49, "images": n, "samples": m, "greedy": greedy, "rows": n * (m + greedy),
+                      "steps": steps, "top_k": top_k, "top_p": top_p, "reps": a.reps, "ms": res,
+                      "same_tokens": tokens["one_call"] == tokens["composed"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", default="seq,att")
@@ -122,9 +144,9 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     # the one-call route at every row count: the constants come from this table
-    decode.FUSED_SAMPLE_MAX_ROWS = decode.FUSED_ATT_SAMPLE_MAX_ROWS = 1 << 30
+    decode.FUSED_SAMPLE_MAX_ROWS = decode.FUSED_ATT_SAMPLE_MAX_ROWS = decode.FUSED_ATT_NUCLEUS_MAX_ROWS = 1 << 30
     for cell in a.cells.split(","):
-        {"seq": cell_seq, "att": cell_att}[cell](a, dev)
+        {"seq": cell_seq, "att": cell_att, "att_rows": cell_att_rows}[cell](a, dev)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,14 @@ Wall ms per call (host clock around the call, ended by a synchronise), the parts
 process after `--warmup` untimed rounds; per part the median and the (min, max) of the repeats. The parameters move between
 repeats (the optimiser steps), the shapes do not: the seed of the draw is fixed and an untrained decoder rarely draws <end>.
 
-usage: python tools/time_self_critical.py [--baselines greedy,mean] [--reps R] [--warmup W]
+--routes: `host` is the above. `device`: reward = capnet.train.DeviceBleuReward (add-one BLEU), the step's device route -- one
+decode with the greedy caption as one more row ('greedy'), the rewards of all rows from one ops.bleu_rows launch, the
+advantages formed on the device; its parts: sample (sample_random(greedy=..., device=True)), reward (the launch, the
+advantages and a synchronise), policy, step. `host_smooth`: the host route with the same add-one BLEU as a plain function.
+For these two the decoder's output bias prefers sixteen words and the references are made of them, so that rewards differ
+between captions without the hash. The routes named in one run are alternated, part by part, in one process.
+
+usage: python tools/time_self_critical.py [--baselines greedy,mean] [--routes host,host_smooth,device] [--reps R] [--warmup W]
 """
 import argparse
 import json
@@ -47,66 +54,104 @@ def _timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def _route(route, baseline, dev, refs_host, refs_near):
+    """(parts, after) of one route: parts name -> fn, timed in order; after(t, outs) times what needs the parts' results (the
+    reward and the policy step) and returns the packed rows."""
+    torch.manual_seed(3)
+    dec = DecoderFactoredLSTMAtt(A, E, H, F, V, 1, feature_size=CF, dropout=0.0, max_seq_length=STEPS).to(dev).train()
+    feats = torch.rand(IMAGES, 7, 7, CF, device=dev)
+    opt = Adam(dec.parameters(), lr=1e-4)
+    kw = dict(samples=SAMPLES, seed=7)
+    greedy = baseline == "greedy"
+    if route == "host":
+        bleu = train.bleu_reward(refs_host)
+
+        def reward(i, tokens):
+            # BLEU's host cost, plus a hash of the tokens: an untrained decoder's BLEU is 0 for every caption, and rows of
+            # advantage 0 would take the gradient kernel's short path
+            return bleu(i, tokens) + (sum(tokens) % 97) / 97.0
+    else:
+        # host_smooth / device: the same add-one BLEU on both, and a decoder that prefers the references' sixteen words, so
+        # that the rewards differ between captions without a hash (which the device route has no place for)
+        with torch.no_grad():
+            dec.C.bias[4:20] += 9.0
+        scorer = train.DeviceBleuReward(refs_near, smooth=1, device=dev)
+        reward = scorer if route == "device" else (lambda i, tokens: scorer(i, tokens))
+    step = lambda: train.self_critical_step(dec, opt, feats, reward, START, END, 5.0, baseline=baseline, **kw)   # noqa: E731
+    if route == "device":
+        parts = {"sample": lambda: dec.sample_random(feats, START, END, greedy=greedy, device=True, **kw), "step": step}
+
+        def after(t, outs):
+            drawn, ids, _ = outs["sample"]
+            m = SAMPLES + greedy
+
+            def score():
+                r = scorer.rows(ids, START, END, m)[0].double().view(-1, m)
+                if greedy:
+                    return (r[:, :SAMPLES] - r[:, SAMPLES:]).reshape(-1).float()
+                return (r - (r.sum(1, keepdim=True) - r) / (SAMPLES - 1)).reshape(-1).float()
+            t["reward"], adv = _timed(score)
+            drawn = [row[:SAMPLES] for row in drawn]
+            t["policy"], _ = _timed(lambda: train.policy_step(dec, opt, feats, drawn, adv, 5.0))
+            return sum(len(q) - 1 for row in drawn for q, _ in row)
+        return parts, after
+    parts = {"sample": lambda: dec.sample_random(feats, START, END, **kw),
+             "baseline": lambda: dec.sample_batch(feats, START, END, k=1), "step": step}
+    if not greedy:
+        del parts["baseline"]
+
+    def after(t, outs):
+        drawn = outs["sample"]
+        t0 = time.perf_counter()
+        rewards = [[reward(i, q) for q, _ in row] for i, row in enumerate(drawn)]
+        if greedy:
+            base = [[reward(i, [int(w) for w in q])] * SAMPLES for i, q in enumerate(outs["baseline"])]
+        else:
+            base = train.mean_baseline(rewards)
+        t["reward"] = (time.perf_counter() - t0) * 1e3
+        adv = [r - b for rr, bb in zip(rewards, base) for r, b in zip(rr, bb)]
+        t["policy"], _ = _timed(lambda: train.policy_step(dec, opt, feats, drawn, adv, 5.0))
+        return sum(len(q) - 1 for row in drawn for q, _ in row)
+    return parts, after
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--baselines", default="greedy,mean")
+    ap.add_argument("--routes", default="host", help="host (bleu_reward + a hash, as DESIGN 4ah), host_smooth, device; the routes of "
+                    "one run are alternated, part by part, in one process")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(1)
-    refs = [[torch.randint(4, V, (12,), generator=g).tolist() for _ in range(3)] for _ in range(IMAGES)]
-    bleu = train.bleu_reward(refs)
-
-    def reward(i, tokens):
-        # BLEU's host cost, plus a hash of the tokens: an untrained decoder's BLEU is 0 for every caption, and rows of
-        # advantage 0 would take the gradient kernel's short path
-        return bleu(i, tokens) + (sum(tokens) % 97) / 97.0
+    refs_host = [[torch.randint(4, V, (12,), generator=g).tolist() for _ in range(3)] for _ in range(IMAGES)]
+    refs_near = [[[START] + torch.randint(4, 20, (12,), generator=g).tolist() + [END] for _ in range(3)] for _ in range(IMAGES)]
+    routes = a.routes.split(",")
     for baseline in a.baselines.split(","):
-        torch.manual_seed(3)
-        dec = DecoderFactoredLSTMAtt(A, E, H, F, V, 1, feature_size=CF, dropout=0.0, max_seq_length=STEPS).to(dev).train()
-        feats = torch.rand(IMAGES, 7, 7, CF, device=dev)
-        opt = Adam(dec.parameters(), lr=1e-4)
-        kw = dict(samples=SAMPLES, seed=7)
-        parts = {
-            "sample": lambda: dec.sample_random(feats, START, END, **kw),
-            "baseline": lambda: dec.sample_batch(feats, START, END, k=1),
-            "step": lambda: train.self_critical_step(dec, opt, feats, reward, START, END, 5.0, baseline=baseline, **kw),
-        }
-        if baseline != "greedy":
-            del parts["baseline"]
-        ms = {k: [] for k in list(parts) + ["reward", "policy"]}
-        words = 0
+        built = {r: _route(r, baseline, dev, refs_host, refs_near) for r in routes}
+        ms = {r: {} for r in routes}
+        words = {}
         for it in range(a.warmup + a.reps):
-            t = {}
-            for name, fn in parts.items():
-                t[name], out = _timed(fn)
-                if name == "sample":
-                    drawn = out
-                elif name == "baseline":
-                    greedy = out
-            t0 = time.perf_counter()
-            rewards = [[reward(i, q) for q, _ in row] for i, row in enumerate(drawn)]
-            if baseline == "greedy":
-                base = [[reward(i, [int(w) for w in q])] * SAMPLES for i, q in enumerate(greedy)]
-            else:
-                base = train.mean_baseline(rewards)
-            t["reward"] = (time.perf_counter() - t0) * 1e3
-            adv = [r - b for rr, bb in zip(rewards, base) for r, b in zip(rr, bb)]
-            t["policy"], _ = _timed(lambda: train.policy_step(dec, opt, feats, drawn, adv, 5.0))
-            words = sum(len(q) - 1 for row in drawn for q, _ in row)
-            if it >= a.warmup:
-                for k, v in t.items():
-                    ms[k].append(v)
-        rec = {"tool": "time_self_critical", "decoder": "DecoderFactoredLSTMAtt", "A": A, "E": E, "H": H, "F": F, "V": V, "C": CF,
-               "P": 49, "images": IMAGES, "samples": SAMPLES, "steps": STEPS, "baseline": baseline, "packed_rows": words,
-               "reps": a.reps,
-               "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
-                      for k, v in ms.items()}}
-        line = json.dumps(rec)
-        print(line, flush=True)
-        with open(OUT, "a") as f:
-            f.write(line + "\n")
+            for r in routes:
+                parts, after = built[r]
+                t, outs = {}, {}
+                for name, fn in parts.items():
+                    t[name], outs[name] = _timed(fn)
+                words[r] = after(t, outs)
+                if it >= a.warmup:
+                    for k, v in t.items():
+                        ms[r].setdefault(k, []).append(v)
+        for r in routes:
+            rec = {"tool": "time_self_critical", "decoder": "DecoderFactoredLSTMAtt", "A": A, "E": E, "H": H, "F": F, "V": V, "C": CF,
+                   "P": 49, "images": IMAGES, "samples": SAMPLES, "steps": STEPS, "baseline": baseline, "route": r,
+                   "alternated_with": [x for x in routes if x != r], "packed_rows": words[r], "reps": a.reps,
+                   "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+                          for k, v in ms[r].items()}}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            with open(OUT, "a") as f:
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":
