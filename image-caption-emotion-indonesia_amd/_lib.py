@@ -252,6 +252,8 @@ SIGNATURES = {
     "capnet_policy_xent_bwd": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _i, _ip, _i, _vp, _vp, _l, _vp]),
     "capnet_bleu_rows": (_i, [_vp, _l, _i, _i, C.c_longlong, C.c_longlong, _i, _vp, _vp, _i, _i, _i, C.POINTER(C.c_double), _i,
                               _vp, _vp, _vp]),
+    "capnet_cider_rows": (_i, [_vp, _l, _i, _i, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp),
+                               C.POINTER(_vp), _ip, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "capnet_clamp_adam": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                C.POINTER(_vp), C.POINTER(_l), _ip, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_float, _i, _vp, _vp]),

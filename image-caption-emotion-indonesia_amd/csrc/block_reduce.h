@@ -34,5 +34,16 @@ __device__ __forceinline__ int block_reduce_sum(int v, int* s) {
   __syncthreads();
   return r;
 }
+// and for fp64 terms (caption_reward.hip's CIDEr-D sums): the same butterfly, so the order of the additions is fixed by the
+// thread index alone and two launches on the same input agree to the last bit
+__device__ __forceinline__ double block_reduce_sum(double v, double* s) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = s[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += s[w];
+  __syncthreads();
+  return r;
+}
 
 }  // namespace capnet

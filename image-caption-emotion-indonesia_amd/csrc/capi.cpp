@@ -1491,6 +1491,18 @@ int capnet_bleu_rows(const long long* ids, long ld, int rows, int steps, long lo
   return bleu_rows(ids, ld, rows, steps, start_token, end_token, per_image, refs, ref_len, images, R, Lr, weights, smooth, reward,
                    stats, S(stream));
 }
+int capnet_cider_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token,
+                      int per_image, const int* refs, const int* ref_len, const double* ref_norm, int images, int R, int Lr,
+                      const int* const* keys, const double* const* idf, const int* counts, double log_n, double sigma,
+                      float* reward, double* parts, int* stats, capnet_stream_t stream) {
+  CAPNET_REQUIRE(keys && idf && counts, "cider_rows: null argument");
+  bool aligned = (size_t)ids % 8 == 0 && (size_t)refs % 4 == 0 && (size_t)ref_len % 4 == 0 && (size_t)ref_norm % 8 == 0 &&
+                 (size_t)reward % 4 == 0 && (size_t)parts % 8 == 0 && (size_t)stats % 4 == 0;
+  for (int n = 0; n < 4; ++n) aligned = aligned && (size_t)keys[n] % 4 == 0 && (size_t)idf[n] % 8 == 0;
+  CAPNET_REQUIRE(aligned, "cider_rows: alignment");
+  return cider_rows(ids, ld, rows, steps, start_token, end_token, per_image, refs, ref_len, ref_norm, images, R, Lr, keys, idf,
+                    counts, log_n, sigma, reward, parts, stats, S(stream));
+}
 
 int capnet_clamp_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
                       float* const* exp_avg_sq, const long* numel, const int* step, float lr,

@@ -507,6 +507,11 @@ constexpr int kBleuMaxSteps = 128, kBleuMaxRefs = 16, kBleuRefWords = 4096;
 int bleu_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token, int per_image,
               const int* refs, const int* ref_len, int images, int R, int Lr, const double* weights, int smooth, float* reward,
               int* stats, hipStream_t stream);
+// CIDEr-D of decoded rows under the same limits; keys / idf / counts: HOST arrays of four (device pointers, sizes), one per order
+int cider_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token, int per_image,
+               const int* refs, const int* ref_len, const double* ref_norm, int images, int R, int Lr, const int* const* keys,
+               const double* const* idf, const int* counts, double log_n, double sigma, float* reward, double* parts, int* stats,
+               hipStream_t stream);
 int lstm_persist_set_mode(int mode);
 int clamp_adam(int n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
                float* const* exp_avg_sq, const long* numel, const int* step, float lr, float b1,

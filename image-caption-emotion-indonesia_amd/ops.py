@@ -1874,6 +1874,54 @@ def bleu_rows(ids, start_token, end_token, per_image, refs, ref_len, weights=(0.
     return reward, stats
 
 
+def cider_rows(ids, start_token, end_token, per_image, refs, ref_len, ref_norm, tables, log_n, sigma=6.0, steps=None):
+    """(reward float32 [rows], parts float64 [rows, 4], stats int32 [rows, 9]) on the device: CIDEr-D of every row of a
+    sampled decode against the references of its image (capnet_cider_rows) -- capnet.metrics.sentence_cider_d / cider_d_parts
+    of what decode.cut_samples makes of the row. ids / per_image / refs / ref_len / steps: as bleu_rows. ref_norm float64
+    [images, R, 4]: norm_n of every reference slot; tables: four (keys int32 [count_n, n] ascending, idf float64 [count_n])
+    pairs on the device, one per order n = 1..4; log_n: ln of the corpus' image count, the idf of an n-gram no table holds
+    (capnet.metrics.CiderCorpus.on and capnet.train.DeviceCiderReward make all of these). stats: the hypothesis length, its
+    distinct n-grams for n = 1..4, and how many of those the tables hold. No host read; the same input gives the same bits."""
+    _need_cuda(ids, refs, ref_len)
+    if ids.dtype != torch.int64 or refs.dtype != torch.int32 or ref_len.dtype != torch.int32:
+        raise CapnetError("cider_rows: ids must be int64, refs and ref_len int32")
+    if ids.dim() != 2 or refs.dim() != 3 or ref_len.dim() != 2 or tuple(ref_len.shape) != tuple(refs.shape[:2]):
+        raise CapnetError("cider_rows: ids [rows, ld], refs [images, R, Lr], ref_len [images, R]; got %s, %s, %s"
+                          % (tuple(ids.shape), tuple(refs.shape), tuple(ref_len.shape)))
+    if ids.stride(1) != 1:
+        raise CapnetError("cider_rows: the columns of ids must be adjacent")
+    if not ref_norm.is_cuda or ref_norm.dtype != torch.float64 or tuple(ref_norm.shape) != tuple(refs.shape[:2]) + (4,):
+        raise CapnetError("cider_rows: ref_norm must be float64 [images, R, 4] on the device")
+    if len(tables) != 4:
+        raise CapnetError("cider_rows: four (keys, idf) tables, one per order, not %d" % len(tables))
+    keys, idfs = [], []
+    for n, (k, v) in enumerate(tables, 1):
+        if not (k.is_cuda and v.is_cuda and k.dtype == torch.int32 and v.dtype == torch.float64 and k.dim() == 2
+                and k.shape[1] == n and tuple(v.shape) == (k.shape[0],)):
+            raise CapnetError("cider_rows: order %d needs keys int32 [count, %d] and idf float64 [count] on the device" % (n, n))
+        keys.append(_c(k))
+        idfs.append(_c(v))
+    if not float(sigma) > 0.0:
+        raise CapnetError("cider_rows: sigma %r (must be positive)" % (sigma,))
+    refs, ref_len, ref_norm = _c(refs), _c(ref_len), _c(ref_norm)
+    rows = ids.shape[0]
+    steps = ids.shape[1] if steps is None else int(steps)
+    if not 1 <= steps <= ids.shape[1]:
+        raise CapnetError("cider_rows: %d steps of %d columns" % (steps, ids.shape[1]))
+    images, R, Lr = refs.shape
+    reward = torch.empty(rows, dtype=torch.float32, device=ids.device)
+    parts = torch.empty((rows, 4), dtype=torch.float64, device=ids.device)
+    stats = torch.empty((rows, 9), dtype=torch.int32, device=ids.device)
+    counts = [k.shape[0] for k in keys]
+    kp = (C.c_void_p * 4)(*[k.data_ptr() if c else None for k, c in zip(keys, counts)])
+    vp = (C.c_void_p * 4)(*[v.data_ptr() if c else None for v, c in zip(idfs, counts)])
+    check(_lib.lib().capnet_cider_rows(ptr(ids), ids.stride(0), rows, steps, int(start_token), int(end_token), int(per_image),
+                                       ptr(refs), ptr(ref_len), ptr(ref_norm), images, R, Lr, kp, vp, int_array(counts),
+                                       float(log_n), float(sigma), ptr(reward), ptr(parts), ptr(stats), current_stream()),
+          "capnet_cider_rows")
+    return reward, parts, stats
+
+
 class AttentionLossFn(torch.autograd.Function):
     """nll + alpha_c * ((1 - alphas.sum(dim=1)) ** 2).mean()  (train_multitask_att.py:409-411)."""
 

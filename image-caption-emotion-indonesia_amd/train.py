@@ -2,9 +2,10 @@
 
   train_step     one iteration of the bodies of train_factual / train_emotion
                  (stylenet/train_multitask.py:373-389, 527-537; nic/train_transfer_fac.py:252-296)
-  policy_step / self_critical_step / bleu_reward / DeviceBleuReward   reward-based fine-tuning on sampled captions
-                 (self-critical sequence training, Rennie et al. 2017; no counterpart in the reference); with a
-                 DeviceBleuReward the rewards and advantages are computed on the device (ops.bleu_rows)
+  policy_step / self_critical_step / bleu_reward / DeviceBleuReward / cider_reward / DeviceCiderReward   reward-based
+                 fine-tuning on sampled captions (self-critical sequence training, Rennie et al. 2017; no counterpart in the
+                 reference); with a DeviceBleuReward or a DeviceCiderReward the rewards and advantages are computed on the
+                 device (ops.bleu_rows, ops.cider_rows)
   train_factual  stylenet/train_multitask.py:364-408
   train_emotion  stylenet/train_multitask.py:511-557
   val_factual / val_emotion   stylenet/train_multitask.py:272-361, 411-508 (eval-mode trunk on the
@@ -19,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import decode, ops
-from .metrics import corpus_bleu, sentence_bleu
+from .metrics import CiderCorpus, corpus_bleu, corpus_cider_d, sentence_bleu, sentence_cider_d
 from .utils import AverageMeter, accuracy, clip_gradient
 
 
@@ -172,10 +173,11 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     floats over all samples, 'zero_rows': the captions whose advantage is exactly 0 (under 'greedy': the samples that
     scored what the greedy caption did, the greedy caption itself among them)}.
 
-    reward a DeviceBleuReward: the device route. 'greedy': ONE decode, decoder.sample_random(greedy=True) -- the greedy
-    caption is one more row per image of the sampled decode, not a second search (it is the width-1 beam's caption wherever
-    that one reaches <end> within max_seq_length) -- and ONE ops.bleu_rows launch over all n (samples + 1) rows, on the ids
-    the sampler left on the device; advantage = reward[drawn] - reward[greedy row of its image], exactly 0 where the two
+    reward a DeviceBleuReward or a DeviceCiderReward: the device route. 'greedy': ONE decode,
+    decoder.sample_random(greedy=True) -- the greedy caption is one more row per image of the sampled decode, not a second
+    search (it is the width-1 beam's caption wherever that one reaches <end> within max_seq_length) -- and ONE reward launch
+    (ops.bleu_rows or ops.cider_rows; only the first tensor reward.rows returns is used) over all n (samples + 1) rows, on
+    the ids the sampler left on the device; advantage = reward[drawn] - reward[greedy row of its image], exactly 0 where the two
     float32 rewards are equal. 'mean': the same launch without the greedy row and mean_baseline's formula in fp64. The
     advantages are rounded once to float32 and policy_step takes them as a device tensor: the host reads the ids once, for
     packing, and computes no reward and no advantage. The dict's 'reward_mean', 'baseline_mean', 'advantage_abs_mean' (fp64)
@@ -185,7 +187,7 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     if baseline == "mean" and int(samples) < 2:
         raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
     kw = {} if mode is None else {"mode": mode}
-    if isinstance(reward, DeviceBleuReward):
+    if isinstance(reward, (DeviceBleuReward, DeviceCiderReward)):
         m, greedy = int(samples), baseline == "greedy"
         drawn, ids, _ = decoder.sample_random(features, start_token, end_token, samples=m, temperature=temperature, top_k=top_k,
                                               seed=seed, top_p=top_p, device=True, greedy=greedy, **kw)
@@ -226,6 +228,30 @@ def bleu_reward(references, weights=(0.25, 0.25, 0.25, 0.25)):
     return reward
 
 
+def pack_references(references, who="pack_references"):
+    """references [image][reference][word] -> (refs int32 [n, R, Lr] zero padded, ref_len int32 [n, R]) on the host: R
+    the most references of an image, Lr the longest reference; an image with fewer references, or an empty one among
+    them, has slots of length 0, which the kernels skip. The one packing of DeviceBleuReward and DeviceCiderReward; `who`
+    names the caller in the ValueErrors."""
+    if not len(references):
+        raise ValueError("%s: no images" % who)
+    R = max(len(refs) for refs in references)
+    Lr = max([len(r) for refs in references for r in refs] + [0])
+    if any(not any(len(r) for r in refs) for refs in references):
+        raise ValueError("%s: every image needs at least one non-empty reference" % who)
+    if R > ops.BLEU_MAX_REFS or R * Lr > ops.BLEU_MAX_REF_WORDS:
+        raise ValueError("%s: %d references of up to %d words (at most %d references, %d padded words per "
+                         "image)" % (who, R, Lr, ops.BLEU_MAX_REFS, ops.BLEU_MAX_REF_WORDS))
+    refs = torch.zeros((len(references), R, Lr), dtype=torch.int32)
+    ref_len = torch.zeros((len(references), R), dtype=torch.int32)
+    for i, rr in enumerate(references):
+        for j, r in enumerate(rr):
+            if len(r):
+                refs[i, j, :len(r)] = torch.tensor(r, dtype=torch.int32)
+                ref_len[i, j] = len(r)
+    return refs, ref_len
+
+
 class DeviceBleuReward(object):
     """bleu_reward whose arithmetic can stay on the device: sentence BLEU (capnet.metrics.sentence_bleu; smooth=1: add-one
     on n >= 2, so a caption without a matching 4-gram still scores) against references[i], the reference token lists of
@@ -249,26 +275,8 @@ class DeviceBleuReward(object):
 
     @staticmethod
     def pack(references):
-        """references [image][reference][word] -> (refs int32 [n, R, Lr] zero padded, ref_len int32 [n, R]) on the host: R
-        the most references of an image, Lr the longest reference; an image with fewer references, or an empty one among
-        them, has slots of length 0, which the kernel skips."""
-        if not len(references):
-            raise ValueError("DeviceBleuReward: no images")
-        R = max(len(refs) for refs in references)
-        Lr = max([len(r) for refs in references for r in refs] + [0])
-        if any(not any(len(r) for r in refs) for refs in references):
-            raise ValueError("DeviceBleuReward: every image needs at least one non-empty reference")
-        if R > ops.BLEU_MAX_REFS or R * Lr > ops.BLEU_MAX_REF_WORDS:
-            raise ValueError("DeviceBleuReward: %d references of up to %d words (at most %d references, %d padded words per "
-                             "image)" % (R, Lr, ops.BLEU_MAX_REFS, ops.BLEU_MAX_REF_WORDS))
-        refs = torch.zeros((len(references), R, Lr), dtype=torch.int32)
-        ref_len = torch.zeros((len(references), R), dtype=torch.int32)
-        for i, rr in enumerate(references):
-            for j, r in enumerate(rr):
-                if len(r):
-                    refs[i, j, :len(r)] = torch.tensor(r, dtype=torch.int32)
-                    ref_len[i, j] = len(r)
-        return refs, ref_len
+        """pack_references(references): (refs int32 [n, R, Lr] zero padded, ref_len int32 [n, R]) on the host."""
+        return pack_references(references, "DeviceBleuReward")
 
     def on(self, device):
         """(refs, ref_len) on `device`, uploaded at the first call for it."""
@@ -287,6 +295,68 @@ class DeviceBleuReward(object):
             raise ops.CapnetError("DeviceBleuReward: %d rows for %d images x %d" % (ids.shape[0], len(self.references), per_image))
         refs, ref_len = self.on(ids.device)
         return ops.bleu_rows(ids, start_token, end_token, per_image, refs, ref_len, self.weights, self.smooth)
+
+
+def cider_reward(references, corpus=None, sigma=6.0):
+    """bleu_reward's counterpart for CIDEr-D: reward(i, tokens) = capnet.metrics.sentence_cider_d of `tokens` against
+    references[i], in [0, 10]. corpus: the capnet.metrics.CiderCorpus whose document frequencies weigh the n-grams (normally
+    the training set's); None: one built from `references`. Tokens are taken as they are."""
+    corpus = CiderCorpus(references) if corpus is None else corpus
+
+    def reward(i, tokens):
+        return sentence_cider_d(corpus, references[i], [int(w) for w in tokens], sigma)
+    return reward
+
+
+class DeviceCiderReward(object):
+    """cider_reward whose arithmetic can stay on the device, with DeviceBleuReward's interface: CIDEr-D
+    (capnet.metrics.sentence_cider_d, in [0, 10]) against references[i], the reference token lists of image i of the batch,
+    taken as they are. corpus: a capnet.metrics.CiderCorpus, normally built once from the whole training set and shared by
+    the reward objects of every batch (its tables are uploaded once per device); None: one built from `references`. The
+    references are packed once (pack_references), and the norm of every reference's tf-idf vector is computed here, on the
+    host, once (ref_norm float64 [images, R, 4]); rows() scores every row of a sampled decode on the device
+    (ops.cider_rows). Called as reward(i, tokens) it is a host reward. self_critical_step takes the device route for it.
+    The limits on the references are DeviceBleuReward's: ValueError beyond."""
+
+    def __init__(self, references, corpus=None, sigma=6.0, device=None):
+        if not float(sigma) > 0.0:
+            raise ValueError("sigma %r (must be positive)" % (sigma,))
+        self.references = [[[int(w) for w in r] for r in refs] for refs in references]
+        self.refs, self.ref_len = self.pack(self.references)
+        self.corpus = CiderCorpus(self.references) if corpus is None else corpus
+        self.sigma = float(sigma)
+        self.ref_norm = torch.zeros(tuple(self.ref_len.shape) + (4,), dtype=torch.float64)
+        for i, rr in enumerate(self.references):
+            for j, r in enumerate(rr):
+                if len(r):
+                    self.ref_norm[i, j] = torch.tensor(self.corpus.vectors(r)[1], dtype=torch.float64)
+        self._on = {}
+        if device is not None:
+            self.on(device)
+
+    @staticmethod
+    def pack(references):
+        """pack_references(references): (refs int32 [n, R, Lr] zero padded, ref_len int32 [n, R]) on the host."""
+        return pack_references(references, "DeviceCiderReward")
+
+    def on(self, device):
+        """(refs, ref_len, ref_norm, the corpus' tables) on `device`, uploaded at the first call for it."""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = (self.refs.to(device), self.ref_len.to(device), self.ref_norm.to(device), self.corpus.on(device))
+        return self._on[device]
+
+    def __call__(self, i, tokens):
+        return sentence_cider_d(self.corpus, self.references[i], [int(w) for w in tokens], self.sigma)
+
+    def rows(self, ids, start_token, end_token, per_image):
+        """(reward float32 [rows], parts float64 [rows, 4], stats int32 [rows, 9]) on the device for the ids
+        [images x per_image, steps] of a sampled decode of all the images, in order (ops.cider_rows)."""
+        if ids.shape[0] != len(self.references) * int(per_image):
+            raise ops.CapnetError("DeviceCiderReward: %d rows for %d images x %d" % (ids.shape[0], len(self.references), per_image))
+        refs, ref_len, ref_norm, tables = self.on(ids.device)
+        return ops.cider_rows(ids, start_token, end_token, per_image, refs, ref_len, ref_norm, tables, self.corpus.log_n,
+                              self.sigma)
 
 
 class TrunkPipeline(object):
@@ -603,13 +673,14 @@ def val_emotion(encoder, decoder, vocab, criterion, data_loaders, tags, device=N
 
 
 def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=None, verbose=False, on_device=False,
-             one_call=False):
+             one_call=False, cider=False):
     """The test-set evaluator, stylenet/evaluator.py:55-120: encoder + decoder in eval mode, every test image decoded by
     beam search, corpus BLEU-1..4 with the reference's four weight tuples (references and hypotheses as the reference
     builds them: the captions' and the sampled ids as they are, <start> / <end> included). The reference calls
     decoder.sample() per image; here a loader batch is decoded at once (decoder.sample_batch: B x k rows per step) --
     the same sequences (tests/test_sample_gpu.py). on_device / one_call: passed on to the decoder (capnet.decode.beam_decode).
-    Returns (bleu_1, bleu_2, bleu_3, bleu_4)."""
+    Returns (bleu_1, bleu_2, bleu_3, bleu_4); with cider=True a fifth entry, the mean CIDEr-D of the decoded captions
+    (capnet.metrics.corpus_cider_d, the corpus being the loader's own references, as the COCO scorer takes a test split)."""
     decoder.eval()
     encoder.eval()
     device = device or next(decoder.parameters()).device
@@ -642,12 +713,20 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
                     print(name, ' '.join(words))
     assert len(references) == len(hypotheses)
     ops.check_device_errors()
+    out = _scores(references, hypotheses, cider)
+    if verbose:
+        for i, b in enumerate(out[:4]):
+            print('BLEU-%d' % (i + 1), b)
+        if cider:
+            print('CIDEr-D', out[4])
+    return out
+
+
+def _scores(references, hypotheses, cider=False):
+    """evaluate's tuple: corpus BLEU-1..4 with the reference's four weight tuples, and with `cider` the corpus_cider_d mean."""
     out = tuple(corpus_bleu(references, hypotheses, weights=w)
                 for w in ((1, 0, 0, 0), (0.5, 0.5, 0, 0), (0.33, 0.33, 0.33, 0), (0.25, 0.25, 0.25, 0.25)))
-    if verbose:
-        for i, b in enumerate(out):
-            print('BLEU-%d' % (i + 1), b)
-    return out
+    return out + (corpus_cider_d(references, hypotheses)[0],) if cider else out
 
 
 MODES = ("factual", "happy", "sad", "angry")
@@ -674,6 +753,4 @@ def evaluate_styles(encoder, decoder, vocab, data_loader, modes=MODES, k=5, devi
                 references[m].append([[int(w) for w in (c.tolist() if hasattr(c, "tolist") else c)] for c in caps])
                 hypotheses[m].append([int(w) for w in sampled_ids])
     ops.check_device_errors()
-    return {m: tuple(corpus_bleu(references[m], hypotheses[m], weights=w)
-                     for w in ((1, 0, 0, 0), (0.5, 0.5, 0, 0), (0.33, 0.33, 0.33, 0), (0.25, 0.25, 0.25, 0.25)))
-            for m in modes}
+    return {m: _scores(references[m], hypotheses[m]) for m in modes}

@@ -1175,6 +1175,25 @@ int capnet_policy_xent_bwd(const float* logits, long ld, int N, int V, const lon
 int capnet_bleu_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token,
                      int per_image, const int* refs, const int* ref_len, int images, int R, int Lr, const double* weights,
                      int smooth, float* reward, int* stats, capnet_stream_t stream);
+/* CIDEr-D (Vedantam et al. 2015, as the COCO caption tools' cider_scorer forms it) of every row of a sampled decode against
+ * the references of its image. ids / steps / start_token / end_token / per_image / refs / ref_len / images / R / Lr, the
+ * hypothesis of a row and the limits: as capnet_bleu_rows. The corpus enters as four sorted tables, one per order n = 1..4:
+ * keys[n-1] int32 [counts[n-1]][n] (device) in strictly ascending lexicographic order and idf[n-1] float64 [counts[n-1]]
+ * (device), the value ln N - ln max(1, df) the host computed for that n-gram; keys, idf and counts themselves are HOST
+ * arrays of four. counts[n-1] >= 0; a table pointer may be null only where its count is 0. log_n = ln N is the idf of an
+ * n-gram no table holds. ref_norm float64 [images][R][4] (device): norm_n of every reference slot, computed by the host.
+ *   v_s(g) = (count of g in s) * idf(g);  norm_n(s) = sqrt(sum over the n-grams g of s of v_s(g)^2)
+ *   sim_n(r) = sum over the distinct n-grams g of the hypothesis of min(v_h(g), v_r(g)) * v_r(g), divided by
+ *              norm_n(h) * norm_n(r) where both are non-zero, times exp(-(L - ref_len)^2 / (2 sigma^2)),  sigma > 0
+ *   part_n = the mean of sim_n over the slots of non-zero length;  reward = 2.5 * (part_1 + part_2 + part_3 + part_4)
+ * reward float32 [rows] (formed in fp64, rounded once), parts float64 [rows][4], stats int32 [rows][9]: L, the number of
+ * distinct n-grams of the hypothesis for n = 1..4, and how many of them the table of order n holds. Every n-gram is looked
+ * up by binary search over whole keys; all sums are fp64 in a fixed order, without atomics: the same input gives the same
+ * bits. One workgroup per row. */
+int capnet_cider_rows(const long long* ids, long ld, int rows, int steps, long long start_token, long long end_token,
+                      int per_image, const int* refs, const int* ref_len, const double* ref_norm, int images, int R, int Lr,
+                      const int* const* keys, const double* const* idf, const int* counts, double log_n, double sigma,
+                      float* reward, double* parts, int* stats, capnet_stream_t stream);
 
 /* ---- input pipeline (stylenet/train_multitask.py:62-69: Resize((336,336)) -> RandomCrop(224) ->
  * RandomHorizontalFlip -> ToTensor -> Normalize) on uint8 HWC device images ----------------------

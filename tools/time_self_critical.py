@@ -19,9 +19,14 @@ decode with the greedy caption as one more row ('greedy'), the rewards of all ro
 advantages formed on the device; its parts: sample (sample_random(greedy=..., device=True)), reward (the launch, the
 advantages and a synchronise), policy, step. `host_smooth`: the host route with the same add-one BLEU as a plain function.
 For these two the decoder's output bias prefers sixteen words and the references are made of them, so that rewards differ
-between captions without the hash. The routes named in one run are alternated, part by part, in one process.
+between captions without the hash. `device_cider` / `host_cider`: the same two routes with CIDEr-D
+(capnet.train.DeviceCiderReward: ops.cider_rows on the device; the same object called as a host function), the same decoder
+with the same bias and the same references; the corpus is the 12 images' references plus 400 seeded random reference sets
+over the same words, so that the idf values are not all equal and the tables have thousands of keys. The routes named in one
+run are alternated, part by part, in one process.
 
-usage: python tools/time_self_critical.py [--baselines greedy,mean] [--routes host,host_smooth,device] [--reps R] [--warmup W]
+usage: python tools/time_self_critical.py [--baselines greedy,mean] [--routes host,host_smooth,device,host_cider,device_cider]
+                                          [--reps R] [--warmup W]
 """
 import argparse
 import json
@@ -37,7 +42,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 import capnet  # noqa: E402,F401
-from capnet import train  # noqa: E402
+from capnet import metrics, train  # noqa: E402
 from capnet.model_att import DecoderFactoredLSTMAtt  # noqa: E402
 from capnet.optim import Adam  # noqa: E402
 
@@ -52,6 +57,18 @@ def _timed(fn):
     out = fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, out
+
+
+_corpora = {}
+
+
+def _corpus(refs_near):
+    """The CIDEr-D corpus of the *_cider routes: the images' references and 400 random reference sets over the same words."""
+    if "c" not in _corpora:
+        g = torch.Generator().manual_seed(2)
+        more = [[[START] + torch.randint(4, 20, (12,), generator=g).tolist() + [END] for _ in range(3)] for _ in range(400)]
+        _corpora["c"] = metrics.CiderCorpus(list(refs_near) + more)
+    return _corpora["c"]
 
 
 def _route(route, baseline, dev, refs_host, refs_near):
@@ -75,10 +92,13 @@ def _route(route, baseline, dev, refs_host, refs_near):
         # that the rewards differ between captions without a hash (which the device route has no place for)
         with torch.no_grad():
             dec.C.bias[4:20] += 9.0
-        scorer = train.DeviceBleuReward(refs_near, smooth=1, device=dev)
-        reward = scorer if route == "device" else (lambda i, tokens: scorer(i, tokens))
+        if route.endswith("_cider"):
+            scorer = train.DeviceCiderReward(refs_near, _corpus(refs_near), device=dev)
+        else:
+            scorer = train.DeviceBleuReward(refs_near, smooth=1, device=dev)
+        reward = scorer if route.startswith("device") else (lambda i, tokens: scorer(i, tokens))
     step = lambda: train.self_critical_step(dec, opt, feats, reward, START, END, 5.0, baseline=baseline, **kw)   # noqa: E731
-    if route == "device":
+    if route.startswith("device"):
         parts = {"sample": lambda: dec.sample_random(feats, START, END, greedy=greedy, device=True, **kw), "step": step}
 
         def after(t, outs):
@@ -118,8 +138,8 @@ def _route(route, baseline, dev, refs_host, refs_near):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--baselines", default="greedy,mean")
-    ap.add_argument("--routes", default="host", help="host (bleu_reward + a hash, as DESIGN 4ah), host_smooth, device; the routes of "
-                    "one run are alternated, part by part, in one process")
+    ap.add_argument("--routes", default="host", help="host (bleu_reward + a hash, as DESIGN 4ah), host_smooth, device, host_cider, "
+                    "device_cider; the routes of one run are alternated, part by part, in one process")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     a = ap.parse_args()
