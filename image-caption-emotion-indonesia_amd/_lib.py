@@ -281,6 +281,20 @@ SIGNATURES = {
     "capnet_count_skipped": (_i, [_vp, _vp, _vp]),
     "capnet_pack_tensors": (_i, [_i, C.POINTER(_vp), C.POINTER(_l), _vp, _i, C.c_float, _vp]),
     "capnet_clamp": (_i, [_vp, _l, C.c_float, C.c_float, _vp]),
+    "capnet_beam_advance_constrained": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "capnet_beam_advance_constrained_traced": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _vp,
+                                                    _vp]),
+    "capnet_beam_topk_banned": (_i, [_vp, _l, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "capnet_beam_topk_batched_banned": (_i, [_vp, _l, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "capnet_beam_decode_constrained": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, C.POINTER(_vp),
+                                            C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp,
+                                            _i, _i, _vp, _i]),
+    "capnet_att_beam_decode_constrained": (_i, [_i] * 11 + [C.c_longlong, C.c_longlong] + [_vp] * 7 +
+                                           [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i),
+                                            _vp, _vp, _i, _i, _vp, _i]),
+    "capnet_att_beam_decode_alphas_constrained": (_i, [_i] * 11 + [C.c_longlong, C.c_longlong] + [_vp] * 7 +
+                                                  [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp,
+                                                   C.POINTER(_i), _vp, _vp, _vp, _i, _i, _vp, _i]),
 }
 
 

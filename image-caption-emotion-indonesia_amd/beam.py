@@ -12,6 +12,11 @@ bookkeeping (sequence lists, which beam survives) is host Python, as in the refe
 beam_search_device is the opt-in third loop: the same search with that bookkeeping done by the selecting workgroup
 (capnet_beam_advance), fixed rows per image and nothing read by the host until the end.
 
+Constraints / banned_words: what a search must not emit (no repeated n-gram, a minimum length, banned words),
+one rule for all three loops through their `constraints` keyword. The host loops, which hold the sequences, build every
+live row's list and hand it to capnet_beam_topk[_batched]_banned; beam_search_device leaves it to the selecting workgroup
+(capnet_beam_advance_constrained), which reads the sequences in the beam state. None: the loops as they were.
+
 Deviation from the reference text: `top_k_words / vocab_size` (model.py:249) is an integer
 division here. Under the torch 1.1 the reference pins it was one; under current torch the
 reference line raises.
@@ -32,7 +37,81 @@ def rank_completed(done, length_penalty=0.0):
     return [(list(done[q][1]), float(done[q][0])) for q in sorted(range(len(done)), key=lambda q: (-key(q), q))]
 
 
-def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False, length_penalty=0.0):
+class Constraints(object):
+    """What a beam search must not emit, the same rule on every route. At step s (1-based) a live hypothesis
+    is tokens = [start, w_1 .. w_{s-1}]; the candidate (hypothesis, word v) is excluded from that step's selection if
+      * v is in `banned` (a tuple of at most 32 distinct word ids, none of them end_token), or
+      * v == end_token and s <= min_words (a completed caption has at least min_words words between <start> and <end>), or
+      * g = no_repeat_ngram (0 to 4) >= 1, len(tokens) >= g, and appending v would complete a g-gram the hypothesis already
+        contains, <start> included (g = 1: no word twice; a context seen several times bans several words).
+    Excluded candidates leave AFTER the log-softmax: a survivor's score is the model's own summed log-probability, the number
+    score_captions returns; nothing is renormalised. Constraints() excludes nothing and runs the unconstrained code."""
+    MAX_NGRAM, MAX_BANNED = 4, 32
+
+    def __init__(self, no_repeat_ngram=0, min_words=0, banned=()):
+        for name, v in (("no_repeat_ngram", no_repeat_ngram), ("min_words", min_words)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ops.CapnetError("Constraints: %s must be an int, not %r" % (name, v))
+        if not 0 <= no_repeat_ngram <= self.MAX_NGRAM:
+            raise ops.CapnetError("Constraints: no_repeat_ngram=%d (0 .. %d)" % (no_repeat_ngram, self.MAX_NGRAM))
+        if min_words < 0:
+            raise ops.CapnetError("Constraints: min_words=%d (>= 0)" % min_words)
+        if isinstance(banned, (str, bytes)) or not hasattr(banned, "__iter__"):
+            raise ops.CapnetError("Constraints: banned must be a sequence of word ids, not %r" % (banned,))
+        banned = tuple(banned)
+        for w in banned:
+            if isinstance(w, bool) or not isinstance(w, int) or w < 0:
+                raise ops.CapnetError("Constraints: banned holds word ids (ints >= 0), not %r" % (w,))
+        if len(banned) > self.MAX_BANNED or len(set(banned)) != len(banned):
+            raise ops.CapnetError("Constraints: banned must be at most %d distinct word ids" % self.MAX_BANNED)
+        self.no_repeat_ngram, self.min_words, self.banned = no_repeat_ngram, min_words, banned
+
+    @property
+    def active(self):
+        return bool(self.no_repeat_ngram or self.min_words or self.banned)
+
+    def check(self, vocab_size, end_token, k, max_seq_length):
+        """The front end's check for one search (CapnetError): no banned id is end_token or outside the vocabulary, and
+        every step keeps k finite candidates -- V - len(banned) - 1 - (max_seq_length + 1) >= k (the banned words, <end>
+        and one word per token of the longest hypothesis gone from a row) and min_words < max_seq_length."""
+        if int(end_token) in self.banned or any(w >= vocab_size for w in self.banned):
+            raise ops.CapnetError("constraints: banned=%r must be word ids below %d other than end_token %d"
+                                  % (self.banned, vocab_size, int(end_token)))
+        if vocab_size - len(self.banned) - 1 - (max_seq_length + 1) < k:
+            raise ops.CapnetError("constraints: vocab_size %d - %d banned - 1 - (max_seq_length %d + 1) leaves fewer than k = %d "
+                                  "candidates" % (vocab_size, len(self.banned), max_seq_length, k))
+        if not self.min_words < max_seq_length:
+            raise ops.CapnetError("constraints: min_words=%d must be below max_seq_length %d" % (self.min_words, max_seq_length))
+
+    def __repr__(self):
+        return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r)" % (self.no_repeat_ngram, self.min_words, self.banned)
+
+
+def banned_words(tokens, step, end_token, constraints):
+    """Constraints' rule as code: the sorted word ids a hypothesis `tokens` = [start, w_1 .. w_{step-1}] may not take at step
+    `step` (1-based)."""
+    out = set(constraints.banned)
+    if step <= constraints.min_words:
+        out.add(int(end_token))
+    g, n = constraints.no_repeat_ngram, len(tokens)
+    if g >= 1 and n >= g:
+        tail = list(tokens[n - (g - 1):]) if g > 1 else []
+        for e in range(n - g + 1):
+            if list(tokens[e:e + g - 1]) == tail:
+                out.add(int(tokens[e + g - 1]))
+    return sorted(out)
+
+
+def _bans(rows_tokens, step, end_token, constraints, device):
+    """The ban lists of a step's logits rows as capnet_beam_topk[_batched]_banned takes them: int32 [rows, 1 + cap] on the
+    device, per row its count and its words."""
+    lists = [banned_words(t, step, end_token, constraints) for t in rows_tokens]
+    cap = max(1, max(len(b) for b in lists))
+    return torch.tensor([[len(b)] + b + [0] * (cap - len(b)) for b in lists], dtype=torch.int32, device=device)
+
+
+def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False, length_penalty=0.0,
+                constraints=None):
     """step_fn(prev_words LongTensor[s], state) -> (logits [s, V], state'); `state` is a tuple of
     tensors whose leading dimension is the beam and which are re-indexed here when beams are
     re-ordered or retired. Returns LongTensor [1, L] (starts with start_token); nbest: the list of
@@ -47,7 +126,11 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
         logits, state = step_fn(k_prev_words, state)
         # first step: all k beams are identical, only row 0 competes (model.py:240-242)
         rows = 1 if step == 1 else logits.shape[0]
-        scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k)
+        if constraints is None:
+            scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k)
+        else:       # the hypotheses are held here: every competing row's list, removed after the log-sum-exp
+            scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k,
+                                             bans=_bans(seqs[:rows], step, end_token, constraints, device))
         scores = scores_d.tolist()
         flat = flat_d.tolist()
         prev_word_inds = [f // vocab_size for f in flat]
@@ -81,7 +164,7 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
 
 
 def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, poll_every=0,
-                       nbest=False, length_penalty=0.0):
+                       nbest=False, length_penalty=0.0, constraints=None):
     """beam_search_batched with the bookkeeping on the device (capnet_beam_advance): no host read and no host-built
     tensor per step. Image i keeps rows i k .. i k + k - 1 for the whole search -- its live beams in its first slots, in
     the order beam_search_batched keeps them; dead slots still take the decoder step, their logits are never read -- so
@@ -103,7 +186,10 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
         if logits.shape[1] != vocab_size:
             raise ops.CapnetError("beam_search_device: the step returned %d columns, vocab_size is %d" % (logits.shape[1], vocab_size))
         next_words = words[step & 1]
-        ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows)
+        if constraints is None:
+            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows)
+        else:       # the sequences stay in the beam state: the selecting workgroup derives the exclusions from them
+            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints)
         if poll_every > 0 and step % poll_every == 0 and step < T and not int(beam.live_total.item()):
             break
         state = tuple(s.index_select(0, parent_rows) for s in state)
@@ -120,7 +206,7 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
 
 
 def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False,
-                        length_penalty=0.0):
+                        length_penalty=0.0, constraints=None):
     """beam_search for n images at once: the evaluator of the reference (stylenet/evaluator.py:63-120) calls sample() per
     test image, k rows per decode step; here the beams of ALL images advance together -- one decoder step over sum(live
     beams) rows and one capnet_beam_topk_batched launch per step -- with per image exactly beam_search's bookkeeping
@@ -141,7 +227,13 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
         for i in range(n):
             meta.append((row0, (1 if step == 1 else live[i]) if live[i] else 0, live[i]))
             row0 += live[i]
-        scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, torch.tensor(meta, dtype=torch.int32, device=device))
+        meta_d = torch.tensor(meta, dtype=torch.int32, device=device)
+        if constraints is None:
+            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d)
+        else:       # a list for every row of the logits: image i's live beams in order
+            live_seqs = [q for i in range(n) for q in seqs[i]]
+            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d,
+                                                     bans=_bans(live_seqs, step, end_token, constraints, device))
         scores, flat = scores_d.tolist(), flat_d.tolist()
         keep_rows, next_words, next_scores = [], [], []
         for i in range(n):

@@ -574,6 +574,21 @@ int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n_images, i
                      workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups);
 }
 
+int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                                   long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                                   const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                                   size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                                   int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                   int n_banned) {
+  if (int rc = stack_decode_check("beam_decode_constrained", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0,
+                                  1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
+    return rc;
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  if (int rc = beam_constraints_check("beam_decode_constrained", con)) return rc;
+  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
+                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
+}
+
 size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
 
 int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
@@ -1008,7 +1023,8 @@ static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k
                                  const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                                 capnet_stream_t stream, bool with_alphas, float* alphas) {
+                                 capnet_stream_t stream, bool with_alphas, float* alphas,
+                                 const BeamConstraints* con = nullptr) {
   if (int rc = att_decode_check("att_beam_decode", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
                                 wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
@@ -1020,9 +1036,11 @@ static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k
   CAPNET_REQUIRE((size_t)seqs % 8 == 0 && (size_t)lengths % 4 == 0, "att_beam_decode: seqs / lengths alignment");
   CAPNET_REQUIRE(!with_alphas || alphas, "att_beam_decode: null argument (alphas is required)");
   CAPNET_REQUIRE((size_t)alphas % 4 == 0, "att_beam_decode: alphas alignment");
+  if (con)
+    if (int rc = beam_constraints_check("att_beam_decode", *con)) return rc;
   return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
                          b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
-                         err_flag, S(stream), groups, alphas);
+                         err_flag, S(stream), groups, alphas, con);
 }
 
 int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
@@ -1162,6 +1180,35 @@ int capnet_att_beam_decode_alphas(int cell, int nlayers, int groups, int n, int 
                                lengths, steps_run, err_flag, stream, true, alphas);
 }
 
+int capnet_att_beam_decode_constrained(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                       long long start_token, long long end_token, const float* att1, const float* feat,
+                                       const float* emb, const float* wz, const float* bz, const float* w_full,
+                                       const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                       const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                       int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                       capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                       int n_banned) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  return att_beam_decode_entry(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz,
+                               w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths,
+                               steps_run, err_flag, stream, false, nullptr, &con);
+}
+
+int capnet_att_beam_decode_alphas_constrained(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps, long long start_token, long long end_token,
+                                              const float* att1, const float* feat, const float* emb, const float* wz,
+                                              const float* bz, const float* w_full, const float* b_full,
+                                              const float* const* wcat, const float* const* beff, const float* Cw,
+                                              const float* Cb, const float* state0, void* workspace, float* slab,
+                                              size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                                              int* err_flag, capnet_stream_t stream, float* alphas, int no_repeat_ngram,
+                                              int min_words, const int* banned, int n_banned) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  return att_beam_decode_entry(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz,
+                               w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths,
+                               steps_run, err_flag, stream, true, alphas, &con);
+}
+
 int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c_prev, const float* dh, float* dc_io,
                               float* dpre, int b, int H, int cell, capnet_stream_t stream) {
   CAPNET_REQUIRE(gates && c && dh && dc_io && dpre && b >= 0 && H > 0, "lstm_pointwise_bwd: bad argument");
@@ -1284,6 +1331,14 @@ int capnet_beam_topk(const float* logits, long ld, int rows, int V, const float*
                      float* top_scores, long long* top_index, capnet_stream_t stream) {
   return beam_topk(logits, ld, rows, V, prev_scores, k, top_scores, top_index, S(stream));
 }
+int capnet_beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev_scores, int k, const int* bans, int cap,
+                            float* top_scores, long long* top_index, capnet_stream_t stream) {
+  return beam_topk_banned(logits, ld, rows, V, prev_scores, k, bans, cap, top_scores, top_index, S(stream));
+}
+int capnet_beam_topk_batched_banned(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                    const int* bans, int cap, float* top_scores, long long* top_index, capnet_stream_t stream) {
+  return beam_topk_batched_banned(logits, ld, V, prev_scores, meta, n, bans, cap, top_scores, top_index, S(stream));
+}
 size_t capnet_beam_state_bytes(int n, int k, int max_steps) { return beam_state_bytes(n, k, max_steps); }
 int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words,
                      capnet_stream_t stream) {
@@ -1309,6 +1364,22 @@ int capnet_beam_advance_traced(void* beam, void* trace, const float* logits, lon
   CAPNET_REQUIRE(trace != nullptr, "beam_advance_traced: null trace");
   CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0, "beam_advance_traced: the state and the trace must be 4-byte aligned");
   return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream), trace);
+}
+int capnet_beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                                    long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                    long long* next_words, long long* parent_rows, capnet_stream_t stream) {
+  return beam_advance_constrained(beam, logits, ld, V, n, k, max_steps, step, end_token,
+                                  BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream));
+}
+int capnet_beam_advance_constrained_traced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps,
+                                           int step, long long end_token, int no_repeat_ngram, int min_words, const int* banned,
+                                           int n_banned, long long* next_words, long long* parent_rows, capnet_stream_t stream) {
+  CAPNET_REQUIRE(trace != nullptr, "beam_advance_constrained_traced: null trace");
+  CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0,
+                 "beam_advance_constrained_traced: the state and the trace must be 4-byte aligned");
+  return beam_advance_constrained(beam, logits, ld, V, n, k, max_steps, step, end_token,
+                                  BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream),
+                                  trace);
 }
 int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
                               long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {

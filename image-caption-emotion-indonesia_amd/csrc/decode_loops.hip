@@ -262,7 +262,8 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
                      const float* Cw, const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats,
                      int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
                      bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr,
-                     void* trace = nullptr, int* trace_rows = nullptr) {   // (the row trace: beam_advance's, logits form only)
+                     void* trace = nullptr, int* trace_rows = nullptr,   // (the row trace: beam_advance's, logits form only)
+                     const BeamConstraints* con = nullptr) {              // (constraints: the logits form only)
   const int nk = n * k, rpg = nk / groups;
   const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused, groups);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
@@ -299,7 +300,9 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
         rc = sgemm_splitk(false, true, rpg, V, H, h_top + (size_t)g * rpg * H, H, Cwg[g], H, logits + (size_t)g * rpg * V, V,
                           Cbg ? Cbg[g] : nullptr, 0, slab, slab_floats, s);
       if (rc == kOk && !Cwg) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
-      if (rc == kOk) rc = beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);
+      if (rc == kOk)
+        rc = con ? beam_advance_constrained(beam, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s, trace)
+                 : beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);
     }
     if (rc != kOk) return rc;
     issued = step;
@@ -317,14 +320,15 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups) {
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups, const BeamConstraints* con) {
   n *= groups;   // beam groups: weight groups x images, group-major
   return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
                    lengths, steps_run, s,
                    [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
                      return stacked_decode_step(cell, nlayers, n * k, E, H, V, tok, emb, wcat, beff, sin, sout, h_top, err_flag, s,
                                                 parent, groups);
-                   });
+                   },
+                   false, 1, nullptr, nullptr, nullptr, nullptr, con);
 }
 
 // ---- capnet.seq2seq's beam search: the same loop from a given state, step 1 on given inputs (EncoderRNN's feature
@@ -398,7 +402,7 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups, float* alphas) {
+                    hipStream_t s, int groups, float* alphas, const BeamConstraints* con) {
   const int nq = groups * n;   // beam groups: weight groups x images, group-major
   char* p = reinterpret_cast<char*>(ws);
   void* step_ws = p + beam_decode_layout(nlayers, nq, k, H, V, max_steps).total;
@@ -424,7 +428,7 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
         return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff, sin, parent,
                                sout, h_top, step_ws, slab, slab_floats, err_flag, s, groups, slice);
       },
-      false, 1, nullptr, nullptr, trace, rows);
+      false, 1, nullptr, nullptr, trace, rows, con);
   if (rc != kOk || !alphas) return rc;
   hipLaunchKernelGGL(alpha_gather_kernel, dim3(nq, max_steps), dim3(256), 0, s, hist, rows, nq * k, max_steps, P, alphas);
   CAPNET_LAUNCH_CHECK();

@@ -222,6 +222,23 @@ size_t beam_state_bytes(int n, int k, int max_steps);
 int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream);
 int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
                  long long* next_words, long long* parent_rows, hipStream_t stream, void* trace = nullptr);
+// constrained search: what a step must not select -- no g-gram twice in a hypothesis (0: off, at most 4), no
+// <end> at steps 1 .. min_words, none of the n_banned (<= 32) words of the DEVICE array banned. The excluded words are
+// overwritten with -inf in the logits block AFTER the rows' log-sum-exp: the block is modified, the scores are not.
+struct BeamConstraints {
+  int no_repeat_ngram, min_words;
+  const int* banned;
+  int n_banned;
+};
+int beam_constraints_check(const char* who, const BeamConstraints& c);
+int beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                             long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
+                             hipStream_t stream, void* trace = nullptr);
+// (the host routes' form: bans int32 [rows][1 + cap] on the device, per logits row its count and that many words)
+int beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev, int k, const int* bans, int cap,
+                     float* out_scores, long long* out_index, hipStream_t stream);
+int beam_topk_batched_banned(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
+                             float* out_scores, long long* out_index, hipStream_t stream);
 // (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
 // done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
 // winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)
@@ -327,8 +344,10 @@ size_t beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_ste
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1);
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1,
+                const BeamConstraints* con = nullptr);
 // (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
+// (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance_constrained)
 // vocab_topk.hip: per row the k best of h[r] . W[v] + b[v] (logit descending, index ascending; fewer pickable entries: the
 // tail is (-inf, -1)) and log sum_v exp, one launch, no logits in memory (ws: vocab_topk_ws_bytes, its first 16 bytes zero
 // before the first use)
@@ -424,7 +443,7 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups = 1, float* alphas = nullptr);
+                    hipStream_t s, int groups = 1, float* alphas = nullptr, const BeamConstraints* con = nullptr);
 // alphas [groups n][max_steps][P], optional (ws: att_beam_decode_alphas_ws_bytes): row e - 1 of a caption is the softmax over
 // the pixels that preceded its word e, rows past its length - 1 are zero. ws then continues: the row trace | the winners'
 // rows | the history [max_steps][groups n k][P] of every step's maps

@@ -369,10 +369,76 @@ __device__ __forceinline__ void beam_better(float v, long i, float& bv, long& bi
   if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
 
+// ---- constrained search: what a step must not select. An exclusion is a functor beam_topk_body runs AFTER the
+// rows' log-sum-exp (taken over the whole, unmodified rows) and BEFORE the k selection passes: it writes -INFINITY over
+// the excluded entries of the logits block itself -- the step's scratch, recomputed next step on every route -- so the
+// selection needs no second list to consult and the survivors' scores are the model's own log-probabilities. kActive
+// false: no code at all, and the logits stay const __restrict__ (the unconstrained kernels compile to what they were).
+constexpr int kBanMax = 32, kNgramMax = 4;
+typedef const float* __restrict__ beam_logits_ro;
+
+struct BeamNoExcl {
+  typedef beam_logits_ro logits_t;
+  static constexpr bool kActive = false;
+  __device__ __forceinline__ void operator()(logits_t, long, int, int) const {}
+};
+
+// the exclusions of the device routes, derived from the image's own hypotheses: tok = the image's rows of
+// BeamState.seq[(step - 1) & 1] ([k][L], `step` tokens each, <start> first). banned words on every row; <end> while step <=
+// min_words; g = no_repeat_ngram >= 1 and step >= g: a thread per (row, start position e), g - 1 compares -- the g - 1
+// words at e against the row's last g - 1 -- and where they agree the word behind them goes. Several threads may write the
+// same -INFINITY. A word outside [0, V) is never an address.
+struct BeamExclState {
+  typedef float* logits_t;
+  static constexpr bool kActive = true;
+  const int* tok;
+  int L, step, g, min_words;
+  long long end_token;
+  const int* banned;
+  int n_banned;
+  __device__ __forceinline__ void operator()(float* logits, long ld, int rows, int V) const {
+    const int tid = threadIdx.x, fixed = n_banned + 1;
+    for (int t = tid; t < rows * fixed; t += kBeamThreads) {
+      const int r = t / fixed, q = t % fixed;
+      const long long w = q < n_banned ? (long long)banned[q] : step <= min_words ? end_token : -1;
+      if (w >= 0 && w < V) logits[(long)r * ld + w] = -INFINITY;
+    }
+    if (g >= 1 && step >= g) {
+      const int starts = step - g + 1;
+      for (int t = tid; t < rows * starts; t += kBeamThreads) {
+        const int r = t / starts, e = t % starts;
+        const int* q = tok + (long)r * L;
+        bool same = true;
+        for (int c = 0; c < g - 1; ++c) same &= q[e + c] == q[step - (g - 1) + c];
+        const int w = q[e + g - 1];
+        if (same && w >= 0 && w < V) logits[(long)r * ld + w] = -INFINITY;
+      }
+    }
+  }
+};
+
+// the exclusions of the host routes, which hold the sequences in Python (capnet.beam.banned_words): bans int32
+// [rows][1 + cap], per row of the logits its count, then that many words
+struct BeamExclList {
+  typedef float* logits_t;
+  static constexpr bool kActive = true;
+  const int* bans;
+  int cap;
+  __device__ __forceinline__ void operator()(float* logits, long ld, int rows, int V) const {
+    for (int t = threadIdx.x; t < rows * cap; t += kBeamThreads) {
+      const int r = t / cap, q = t % cap;
+      const int* b = bans + (long)r * (1 + cap);
+      const int w = b[1 + q];
+      if (q < b[0] && w >= 0 && w < V) logits[(long)r * ld + w] = -INFINITY;
+    }
+  }
+};
+
 // the expansion of ONE image's beams (a whole workgroup)
-__device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits, long ld, int rows, int V,
+template <class Excl>
+__device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, long ld, int rows, int V,
                                                const float* __restrict__ prev, int k, float* __restrict__ out_scores,
-                                               long long* __restrict__ out_index) {
+                                               long long* __restrict__ out_index, const Excl excl = Excl()) {
   __shared__ float s_red[kBeamThreads / 64];
   __shared__ long s_idx[kBeamThreads / 64];
   __shared__ float s_lse[kBeamMax];
@@ -404,6 +470,10 @@ __device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits,
       for (int w = 0; w < kBeamThreads / 64; ++w) t += s_red[w];
       s_lse[r] = m + logf(t);
     }
+    __syncthreads();
+  }
+  if constexpr (Excl::kActive) {   // every row's log-sum-exp is taken: now the excluded words leave the selection
+    excl(logits, ld, rows, V);
     __syncthreads();
   }
   for (int j = 0; j < k; ++j) {
@@ -442,7 +512,7 @@ __device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits,
 __global__ __launch_bounds__(kBeamThreads) void beam_topk_kernel(
     const float* __restrict__ logits, long ld, int rows, int V, const float* __restrict__ prev,
     int k, float* __restrict__ out_scores, long long* __restrict__ out_index) {
-  beam_topk_body(logits, ld, rows, V, prev, k, out_scores, out_index);
+  beam_topk_body<BeamNoExcl>(logits, ld, rows, V, prev, k, out_scores, out_index);
 }
 
 // many images at once (the test-set evaluator, stylenet/evaluator.py:63-120, decodes a whole batch per step): workgroup
@@ -453,8 +523,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_topk_batched_kernel(
     float* __restrict__ out_scores, long long* __restrict__ out_index) {
   const int row0 = meta[3 * blockIdx.x], rows = meta[3 * blockIdx.x + 1], k = meta[3 * blockIdx.x + 2];
   if (k <= 0 || rows <= 0) return;
-  beam_topk_body(logits + (long)row0 * ld, ld, rows, V, prev + row0, k, out_scores + (long)blockIdx.x * kBeamMax,
-                 out_index + (long)blockIdx.x * kBeamMax);
+  beam_topk_body<BeamNoExcl>(logits + (long)row0 * ld, ld, rows, V, prev + row0, k, out_scores + (long)blockIdx.x * kBeamMax,
+                             out_index + (long)blockIdx.x * kBeamMax);
 }
 
 int beam_topk(const float* logits, long ld, int rows, int V, const float* prev, int k,
@@ -477,6 +547,50 @@ int beam_topk_batched(const float* logits, long ld, int V, const float* prev, co
   if (n == 0) return kOk;
   hipLaunchKernelGGL(beam_topk_batched_kernel, dim3(n), dim3(kBeamThreads), 0, stream, logits, ld, V, prev, meta, out_scores,
                      out_index);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// the two expansions with a ban list per row (capnet_beam_topk_banned / capnet_beam_topk_batched_banned): the same body,
+// BeamExclList between its log-sum-exp and its selection. bans rows follow the logits rows (the batched form: meta's)
+__global__ __launch_bounds__(kBeamThreads) void beam_topk_banned_kernel(float* logits, long ld, int rows, int V,
+                                                                        const float* __restrict__ prev, int k,
+                                                                        const int* __restrict__ bans, int cap,
+                                                                        float* __restrict__ out_scores,
+                                                                        long long* __restrict__ out_index) {
+  beam_topk_body<BeamExclList>(logits, ld, rows, V, prev, k, out_scores, out_index, BeamExclList{bans, cap});
+}
+
+__global__ __launch_bounds__(kBeamThreads) void beam_topk_batched_banned_kernel(
+    float* logits, long ld, int V, const float* __restrict__ prev, const int* __restrict__ meta, const int* __restrict__ bans,
+    int cap, float* __restrict__ out_scores, long long* __restrict__ out_index) {
+  const int row0 = meta[3 * blockIdx.x], rows = meta[3 * blockIdx.x + 1], k = meta[3 * blockIdx.x + 2];
+  if (k <= 0 || rows <= 0) return;
+  beam_topk_body<BeamExclList>(logits + (long)row0 * ld, ld, rows, V, prev + row0, k, out_scores + (long)blockIdx.x * kBeamMax,
+                               out_index + (long)blockIdx.x * kBeamMax, BeamExclList{bans + (long)row0 * (1 + cap), cap});
+}
+
+int beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev, int k, const int* bans, int cap,
+                     float* out_scores, long long* out_index, hipStream_t stream) {
+  CAPNET_REQUIRE(logits && prev && bans && out_scores && out_index, "beam_topk_banned: null argument");
+  CAPNET_REQUIRE(rows >= 1 && rows <= kBeamMax && k >= 1 && k <= kBeamMax && V >= 1 && ld >= V && (long)rows * V >= k,
+                 "beam_topk_banned: rows=%d k=%d V=%d (rows, k <= %d; k <= rows*V)", rows, k, V, kBeamMax);
+  CAPNET_REQUIRE(cap >= 1 && cap <= (1 << 16) && (size_t)bans % 4 == 0, "beam_topk_banned: cap=%d (1 .. 65536), bans 4-byte aligned", cap);
+  hipLaunchKernelGGL(beam_topk_banned_kernel, dim3(1), dim3(kBeamThreads), 0, stream, logits, ld, rows, V, prev, k, bans, cap,
+                     out_scores, out_index);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_topk_batched_banned(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
+                             float* out_scores, long long* out_index, hipStream_t stream) {
+  CAPNET_REQUIRE(logits && prev && meta && bans && out_scores && out_index && n >= 0 && V >= 1 && ld >= V,
+                 "beam_topk_batched_banned: bad argument");
+  CAPNET_REQUIRE(cap >= 1 && cap <= (1 << 16) && (size_t)bans % 4 == 0,
+                 "beam_topk_batched_banned: cap=%d (1 .. 65536), bans 4-byte aligned", cap);
+  if (n == 0) return kOk;
+  hipLaunchKernelGGL(beam_topk_batched_banned_kernel, dim3(n), dim3(kBeamThreads), 0, stream, logits, ld, V, prev, meta, bans,
+                     cap, out_scores, out_index);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
@@ -616,7 +730,30 @@ __global__ __launch_bounds__(kBeamThreads) void beam_advance_kernel(
   const int i = blockIdx.x;
   const long row0 = (long)i * k;
   const int live = s.live[i];
-  if (live > 0) beam_topk_body(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
+  if (live > 0)
+    beam_topk_body<BeamNoExcl>(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat);
+  beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, live, s_score, s_flat, next_words,
+                                  parent_rows, beam_trace_of(trace, n, k, max_steps));
+}
+
+// beam_advance_kernel under constraints (capnet_beam_advance_constrained): the same body and the same tail, BeamExclState
+// on the image's own sequences between the log-sum-exp and the selection. The logits block is written (-INFINITY over the
+// excluded words of the rows that compete), so it is neither const nor __restrict__ here.
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_constrained_kernel(
+    void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token, int no_repeat_ngram,
+    int min_words, const int* __restrict__ banned, int n_banned, long long* __restrict__ next_words,
+    long long* __restrict__ parent_rows, void* trace) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const int live = s.live[i];
+  if (live > 0) {
+    const BeamExclState excl{s.seq + ((long)((step - 1) & 1) * n * k + row0) * L, L, step, no_repeat_ngram, min_words, end_token,
+                             banned, n_banned};
+    beam_topk_body<BeamExclState>(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat, excl);
+  }
   beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, live, s_score, s_flat, next_words,
                                   parent_rows, beam_trace_of(trace, n, k, max_steps));
 }
@@ -798,6 +935,30 @@ int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, 
                  max_steps);
   hipLaunchKernelGGL(beam_advance_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps, step,
                      end_token, next_words, parent_rows, trace);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_constraints_check(const char* who, const BeamConstraints& c) {
+  CAPNET_REQUIRE(c.no_repeat_ngram >= 0 && c.no_repeat_ngram <= kNgramMax && c.min_words >= 0 && c.n_banned >= 0 &&
+                     c.n_banned <= kBanMax,
+                 "%s: no_repeat_ngram=%d (0 .. %d) min_words=%d (>= 0) n_banned=%d (0 .. %d)", who, c.no_repeat_ngram, kNgramMax,
+                 c.min_words, c.n_banned, kBanMax);
+  CAPNET_REQUIRE((c.banned || !c.n_banned) && (size_t)c.banned % 4 == 0, "%s: banned must be a 4-byte aligned device array", who);
+  return kOk;
+}
+
+int beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                             long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
+                             hipStream_t stream, void* trace) {
+  if (int rc = beam_check("beam_advance_constrained", beam, n, k, max_steps)) return rc;
+  if (int rc = beam_constraints_check("beam_advance_constrained", c)) return rc;
+  CAPNET_REQUIRE(logits && next_words && parent_rows, "beam_advance_constrained: null argument");
+  CAPNET_REQUIRE(V >= 1 && k <= V && ld >= V && step >= 1 && step <= max_steps,
+                 "beam_advance_constrained: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", V, k,
+                 ld, step, max_steps);
+  hipLaunchKernelGGL(beam_advance_constrained_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps,
+                     step, end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, next_words, parent_rows, trace);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -43,7 +43,7 @@ import os
 import torch
 
 from . import ops
-from .beam import beam_search, beam_search_batched, beam_search_device
+from .beam import Constraints, beam_search, beam_search_batched, beam_search_device
 
 FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
 _GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torch's i, f, g, o
@@ -131,15 +131,17 @@ def replay_alphas(step_fn, state, seqs, n, k, images=None):
         return [torch.stack(m) if m else torch.zeros((0, P), dtype=torch.float32, device=dev) for m in maps]
 
 
-def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, nbest=False, length_penalty=0.0):
+def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, nbest=False, length_penalty=0.0,
+                  constraints=None):
     """ops.att_beam_decode on an AttStack; with the maps, the images in as few chunks as keep the history [steps, rows, P]
     under ALPHA_TRACE_MAX_BYTES. nbest: every chunk's n-best lists (and maps per hypothesis), image by image as without it."""
     T, P = dec.max_seq_length + 1, att.feat.shape[1]
+    con = {} if constraints is None else {"constraints": constraints}
 
     def call(a1, ft, st):
         return ops.att_beam_decode(att.cell, a1, ft, att.emb, att.wz, att.bz, att.full_att.weight, att.full_att.bias, att.wcat,
                                    att.beff, att.Cw, att.Cb, st, k, T, start_token, end_token, poll_every,
-                                   return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty)
+                                   return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty, **con)
     per = max(1, ALPHA_TRACE_MAX_BYTES // (T * k * P * 4)) if return_alphas else n_img
     if per >= n_img:
         return call(att.att1, att.feat, att.state)
@@ -166,7 +168,7 @@ def _one_image(lists, dev):
 
 
 def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False,
-                return_alphas=False, nbest=False, length_penalty=0.0):
+                return_alphas=False, nbest=False, length_penalty=0.0, constraints=None):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
@@ -185,10 +187,23 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     completed. Entry 0 at length_penalty 0 is the caption the call without the keyword returns. The search is unchanged:
     the host loops rank the completed lists they hold (capnet.beam.rank_completed), the device routes read theirs with
     capnet_beam_nbest. With return_alphas every hypothesis has its own maps, in the same nesting. length_penalty without
-    nbest raises CapnetError."""
+    nbest raises CapnetError.
+    constraints (a capnet.beam.Constraints): what no hypothesis may contain -- a repeated n-gram, <end> before
+    min_words words, a banned word -- excluded inside every step's selection, after the log-softmax, on whichever route runs:
+    the host loops build each live row's list (capnet.beam.banned_words) for capnet_beam_topk[_batched]_banned, the device
+    routes derive it from the sequences in the beam state (capnet_beam_advance_constrained; the one-call searches'
+    _constrained entries). The scores stay the model's own log-probabilities. None, or a Constraints() that excludes
+    nothing: every route runs the code it runs without the keyword, unchecked. CapnetError where constraints that exclude
+    something could leave a step fewer than k candidates (Constraints.check)."""
     length_penalty = ops.check_length_penalty("beam search", nbest, length_penalty)
     dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
     nb = dict(nbest=True, length_penalty=length_penalty) if nbest else {}
+    if constraints is not None:
+        if not isinstance(constraints, Constraints):
+            raise ops.CapnetError("constraints must be a capnet.beam.Constraints, not %r" % (constraints,))
+        if constraints.active:                  # (not active: the calls as they were before there was the keyword, unchecked)
+            constraints.check(V, end_token, k, T)
+            nb["constraints"] = constraints
     plain = getattr(step_fn, "plain", None) if one_call else None
     att = getattr(step_fn, "att", None) if one_call else None
     maps = one = None
@@ -207,7 +222,7 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
         elif nbest:
             lists = [[(q[0].tolist(), sc) for q, sc in beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)]]
         else:
-            one = beam_search(step_fn, state, V, start_token, end_token, k, T, dev)     # LongTensor [1, L] as it is returned
+            one = beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)     # LongTensor [1, L] as it is returned
             lists = [one[0].tolist()] if return_alphas else None
     return _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest)
 

@@ -185,21 +185,37 @@ def argmax_rows(x):
     return out
 
 
-def beam_topk(logits, prev_scores, rows, k):
+def _check_bans(who, bans, rows):
+    """bans of beam_topk / beam_topk_batched: contiguous int32 [at least `rows`, 1 + cap] on the device -> cap."""
+    _need_cuda(bans)
+    if bans.dtype != torch.int32 or bans.dim() != 2 or bans.shape[0] < rows or bans.shape[1] < 2 or not bans.is_contiguous():
+        raise CapnetError("%s: bans must be a contiguous int32 [rows, 1 + cap] tensor with a row per logits row" % who)
+    return bans.shape[1] - 1
+
+
+def beam_topk(logits, prev_scores, rows, k, bans=None):
     """k best of prev_scores[r] + log_softmax(logits[r]) over the first `rows` rows, flattened.
-    Returns (scores [k] float32, flat_index [k] int64) on the device."""
+    Returns (scores [k] float32, flat_index [k] int64) on the device.
+    bans (capnet_beam_topk_banned): int32 [rows, 1 + cap], per row its count and that many words that may not be selected;
+    they are removed after the rows' log-sum-exp, by -inf written into `logits` (a float32 tensor: it is modified)."""
     _need_cuda(logits)
     logits = _c(logits)
     prev_scores = _c(prev_scores)
     scores = torch.empty(k, dtype=torch.float32, device=logits.device)
     index = torch.empty(k, dtype=torch.int64, device=logits.device)
+    if bans is not None:
+        cap = _check_bans("beam_topk", bans, rows)
+        check(_lib.lib().capnet_beam_topk_banned(ptr(logits), logits.shape[1], rows, logits.shape[1], ptr(prev_scores), k,
+                                                 ptr(bans), cap, ptr(scores), ptr(index), current_stream()),
+              "capnet_beam_topk_banned")
+        return scores, index
     check(_lib.lib().capnet_beam_topk(ptr(logits), logits.shape[1], rows, logits.shape[1],
                                       ptr(prev_scores), k, ptr(scores), ptr(index),
                                       current_stream()), "capnet_beam_topk")
     return scores, index
 
 
-def beam_topk_batched(logits, prev_scores, meta):
+def beam_topk_batched(logits, prev_scores, meta, bans=None):
     """capnet_beam_topk_batched: meta int32 [n, 3] on the device = (first row, competing rows, k) per image.
     Returns (scores [n, 16] float32, flat_index [n, 16] int64) on the device; only the first k entries of a row are set."""
     _need_cuda(logits, prev_scores, meta)
@@ -209,6 +225,12 @@ def beam_topk_batched(logits, prev_scores, meta):
     n = meta.shape[0]
     scores = torch.empty((n, 16), dtype=torch.float32, device=logits.device)
     index = torch.empty((n, 16), dtype=torch.int64, device=logits.device)
+    if bans is not None:     # capnet_beam_topk_batched_banned: beam_topk's bans, a row for every row of the logits
+        cap = _check_bans("beam_topk_batched", bans, logits.shape[0])
+        check(_lib.lib().capnet_beam_topk_batched_banned(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
+                                                         n, ptr(bans), cap, ptr(scores), ptr(index), current_stream()),
+              "capnet_beam_topk_batched_banned")
+        return scores, index
     check(_lib.lib().capnet_beam_topk_batched(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta), n,
                                               ptr(scores), ptr(index), current_stream()), "capnet_beam_topk_batched")
     return scores, index
@@ -244,9 +266,31 @@ def beam_init(n, k, max_steps, start_token, prev_words):
     return beam
 
 
-def beam_advance(beam, logits, step, end_token, next_words, parent_rows):
+_banned_dev = {}      # (banned, device index) -> the int32 device array of a Constraints' banned words
+BANNED_CACHE_MAX = 64   # distinct (ban list, device) pairs kept; one more empties the cache (an array is at most 32 ints)
+
+
+def constraint_args(constraints, device):
+    """The four trailing arguments of the capnet_*_constrained entries for a capnet.beam.Constraints: (no_repeat_ngram,
+    min_words, the banned words as a device int32 array, their count). The array is made once per (tuple, device) and kept,
+    so that a search's steps do not copy it again; the cache holds at most BANNED_CACHE_MAX arrays. (An array dropped from
+    it while a launch that reads it is queued stays valid: torch's allocator hands freed memory to later work of the same
+    stream only.)"""
+    banned = tuple(int(w) for w in constraints.banned)
+    key = (banned, torch.device(device).index or 0)
+    arr = _banned_dev.get(key)
+    if arr is None:
+        if len(_banned_dev) >= BANNED_CACHE_MAX:
+            _banned_dev.clear()
+        arr = _banned_dev[key] = torch.tensor(banned or (0,), dtype=torch.int32, device=device)
+    return int(constraints.no_repeat_ngram), int(constraints.min_words), ptr(arr), len(banned)
+
+
+def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None):
     """capnet_beam_advance: step `step` (1-based) of every image on logits [n k, V]; fills next_words and parent_rows
-    (int64 [n k], contiguous) -- see include/capnet.h."""
+    (int64 [n k], contiguous) -- see include/capnet.h. constraints (a capnet.beam.Constraints;
+    capnet_beam_advance_constrained): the selecting workgroup excludes what they forbid, from the sequences in the state;
+    `logits` is then modified (-inf over the excluded words)."""
     _need_cuda(logits, next_words, parent_rows)
     nk = beam.n * beam.k
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
@@ -254,6 +298,12 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows):
     for w in (next_words, parent_rows):
         if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
             raise CapnetError("beam_advance: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    if constraints is not None:
+        check(_lib.lib().capnet_beam_advance_constrained(
+            ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
+            beam.max_steps, int(step), int(end_token), *constraint_args(constraints, logits.device), ptr(next_words),
+            ptr(parent_rows), current_stream()), "capnet_beam_advance_constrained")
+        return
     check(_lib.lib().capnet_beam_advance(ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1],
                                          logits.shape[1], beam.n, beam.k, beam.max_steps, int(step), int(end_token),
                                          ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance")
@@ -306,7 +356,7 @@ def _check_trace(who, beam, trace):
         raise CapnetError("%s: trace must be beam_trace(beam)" % who)
 
 
-def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent_rows):
+def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints=None):
     """capnet_beam_advance_traced: beam_advance that also records, in `trace` (beam_trace(beam)), the slot every hypothesis
     occupied at this step -- see include/capnet.h."""
     _need_cuda(logits, next_words, parent_rows)
@@ -317,6 +367,12 @@ def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent
     for w in (next_words, parent_rows):
         if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
             raise CapnetError("beam_advance_traced: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    if constraints is not None:     # capnet_beam_advance_constrained_traced: beam_advance's constraints, the trace as here
+        check(_lib.lib().capnet_beam_advance_constrained_traced(
+            ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n,
+            beam.k, beam.max_steps, int(step), int(end_token), *constraint_args(constraints, logits.device), ptr(next_words),
+            ptr(parent_rows), current_stream()), "capnet_beam_advance_constrained_traced")
+        return
     check(_lib.lib().capnet_beam_advance_traced(ptr(beam.words), ptr(trace), ptr(logits),
                                                 logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
                                                 beam.max_steps, int(step), int(end_token), ptr(next_words), ptr(parent_rows),
@@ -1268,7 +1324,7 @@ def beam_decode_supported(E, H, k, V, num_layers):
 
 
 def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, poll_every=0, state=None,
-                return_steps=False, groups=1, nbest=False, length_penalty=0.0):
+                return_steps=False, groups=1, nbest=False, length_penalty=0.0, constraints=None):
     """The beam search of a plain stack in ONE C call (capnet_beam_decode): n images x k beams, at most max_steps steps of
     (gathered decode step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then capnet_beam_finish.
     cell / wcat / beff: as stacked_decode_step; emb [V, E]; Cw [V, H], Cb [V] or None; state: [n k, 2L, H] or None for
@@ -1280,6 +1336,8 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     nbest: instead of its winner, every image gives the list of its completed hypotheses as (tokens, score) pairs, best
     first by score / (len(tokens) - 1)^length_penalty (_nbest_of_workspace: capnet_beam_nbest on the state the search left in
     the workspace); the list is empty where nothing completed. The search itself is the same.
+    constraints (a capnet.beam.Constraints; capnet_beam_decode_constrained, one weight group): every step selects with
+    capnet_beam_advance_constrained; workspace and results as without.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     who = "beam_decode"
     length_penalty = check_length_penalty(who, nbest, length_penalty)
@@ -1300,7 +1358,12 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     steps = C.c_int(0)
     tail_args = (ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
                  int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
-    if groups > 1:
+    if constraints is not None:
+        if groups > 1:
+            raise CapnetError("%s: constraints take one weight group" % who)
+        check(L.capnet_beam_decode_constrained(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
+                                               *constraint_args(constraints, dev)), "capnet_beam_decode_constrained")
+    elif groups > 1:
         check(L.capnet_beam_decode_groups(cell, nl, groups, n_img, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode_groups")
     else:
@@ -1488,7 +1551,7 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
 
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
                     end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False, nbest=False,
-                    length_penalty=0.0):
+                    length_penalty=0.0, constraints=None):
     """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
     steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
     capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
@@ -1502,6 +1565,8 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     nbest / length_penalty: as beam_decode's; with return_alphas every hypothesis has its own maps (capnet_beam_nbest_traced's
     rows, one capnet_alpha_gather over all n k hypotheses): per image a list of float32 [len - 1, P] tensors beside its list
     of (tokens, score) pairs.
+    constraints (a capnet.beam.Constraints; capnet_att_beam_decode_constrained / capnet_att_beam_decode_alphas_constrained, one
+    weight group): every step selects with capnet_beam_advance_constrained; workspaces and results as without.
     Returns the n token lists; with return_steps, (lists, the steps issued); with return_alphas the lists are followed by
     the list of n float32 [len - 1, P] tensors: row e - 1 is the map that preceded word e."""
     groups = _check_groups("att_beam_decode", groups)
@@ -1531,9 +1596,18 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
             ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
             int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
     alphas = None
+    if constraints is not None and groups > 1:
+        raise CapnetError("att_beam_decode: constraints take one weight group")
+    con = () if constraints is None else constraint_args(constraints, dev)
     if return_alphas:
         alphas = (torch.empty((n, T, P), dtype=torch.float32, device=dev), alpha_dims)
-        check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(alphas[0])), "capnet_att_beam_decode_alphas")
+        if con:
+            check(L.capnet_att_beam_decode_alphas_constrained(cell, nl, *args, ptr(alphas[0]), *con),
+                  "capnet_att_beam_decode_alphas_constrained")
+        else:
+            check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(alphas[0])), "capnet_att_beam_decode_alphas")
+    elif con:
+        check(L.capnet_att_beam_decode_constrained(cell, nl, *args, *con), "capnet_att_beam_decode_constrained")
     elif groups > 1:
         check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
     else:

@@ -1294,6 +1294,67 @@ int capnet_count_skipped(const int* err_flag, int* counter, capnet_stream_t stre
 /* x[i] = min(max(x[i], lo), hi): utils.clip_gradient alone (stylenet/utils.py:57-60). */
 int capnet_clamp(float* x, long n, float lo, float hi, capnet_stream_t stream);
 
+/* ---- Constrained beam search (capnet.beam.Constraints; no reference counterpart: the reference patches its
+ * captions after the search) ----
+ * What a step must not select. At step s (1-based) a live hypothesis is tokens = [start, w_1 .. w_{s-1}]; the candidate
+ * (hypothesis, word v) is excluded if v is one of banned[0 .. n_banned) (a DEVICE int32 array, n_banned <= 32; may be NULL
+ * when n_banned is 0), or v == end_token and s <= min_words, or g = no_repeat_ngram (0: off, at most 4) is >= 1, s >= g and
+ * appending v would complete a g-gram the hypothesis already holds, <start> included (g = 1: no word twice).
+ * Exclusion comes AFTER the log-softmax: every row's log-sum-exp is taken over the whole, unmodified row, then the excluded
+ * entries of the logits block are overwritten with -inf and the selection runs as ever (row 0 alone at step 1, ties to the
+ * lower flat index). A survivor's score is still the model's own summed log-probability; nothing is renormalised. THE
+ * LOGITS BLOCK IS MODIFIED (hence neither const nor restrict): it is the step's scratch on every route. The caller
+ * guarantees k finite candidates per step: V - n_banned - 1 - max_steps >= k.
+ *   capnet_beam_advance_constrained: capnet_beam_advance with the exclusions derived by the selecting workgroup from the
+ *     image's own sequences in the beam state (the host never sees them): one thread per (competing row, start position)
+ *     and g - 1 compares each. Everything else -- state, next_words, parent_rows, completion order -- as capnet_beam_advance. */
+int capnet_beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                                    long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                    long long* next_words, long long* parent_rows, capnet_stream_t stream);
+/* capnet_beam_advance_traced under the same constraints: the row trace is recorded as there. */
+int capnet_beam_advance_constrained_traced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps,
+                                           int step, long long end_token, int no_repeat_ngram, int min_words, const int* banned,
+                                           int n_banned, long long* next_words, long long* parent_rows, capnet_stream_t stream);
+/* capnet_beam_topk with a ban list per row, for the host loops, which hold the sequences themselves
+ * (capnet.beam.banned_words): bans is a DEVICE int32 array [rows][1 + cap], per row of the logits its count (<= cap) and
+ * that many words; 1 <= cap <= 65536. The same removal after the log-sum-exp, in the same device function; the logits
+ * block is modified. */
+int capnet_beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev_scores, int k, const int* bans, int cap,
+                            float* top_scores, long long* top_index, capnet_stream_t stream);
+/* capnet_beam_topk_batched with ban lists: bans [all rows of the logits][1 + cap], row r of the array for row r of the
+ * logits (image i's lists start at row meta[3 i]). The logits block is modified. */
+int capnet_beam_topk_batched_banned(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                    const int* bans, int cap, float* top_scores, long long* top_index, capnet_stream_t stream);
+/* capnet_beam_decode (one weight group) whose every step selects with capnet_beam_advance_constrained: arguments, workspace
+ * (capnet_beam_decode_ws_bytes) and results as there, the constraints behind the stream. Always the stored-logits step. */
+int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                                   long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                                   const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                                   size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                                   int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                   int n_banned);
+/* capnet_att_beam_decode under constraints: arguments, workspace (capnet_att_beam_decode_ws_bytes) and results as there. */
+int capnet_att_beam_decode_constrained(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                       long long start_token, long long end_token, const float* att1, const float* feat,
+                                       const float* emb, const float* wz, const float* bz, const float* w_full,
+                                       const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                       const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                       int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                       capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                       int n_banned);
+/* capnet_att_beam_decode_alphas under constraints, one weight group (no `groups` argument, as
+ * capnet_att_beam_decode_constrained has none): the maps are recorded and gathered as there (workspace:
+ * capnet_att_beam_decode_alphas_ws_bytes with groups = 1); the constraints follow alphas. */
+int capnet_att_beam_decode_alphas_constrained(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V,
+                                              int max_steps, long long start_token, long long end_token,
+                                              const float* att1, const float* feat, const float* emb, const float* wz,
+                                              const float* bz, const float* w_full, const float* b_full,
+                                              const float* const* wcat, const float* const* beff, const float* Cw,
+                                              const float* Cb, const float* state0, void* workspace, float* slab,
+                                              size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                                              int* err_flag, capnet_stream_t stream, float* alphas, int no_repeat_ngram,
+                                              int min_words, const int* banned, int n_banned);
+
 #ifdef __cplusplus
 }
 #endif
