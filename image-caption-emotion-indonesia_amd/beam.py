@@ -17,6 +17,11 @@ one rule for all three loops through their `constraints` keyword. The host loops
 live row's list and hand it to capnet_beam_topk[_batched]_banned; beam_search_device leaves it to the selecting workgroup
 (capnet_beam_advance_constrained), which reads the sequences in the beam state. None: the loops as they were.
 
+Diversity / merge_groups: diverse beam search (beam groups that pay for the words earlier groups chose at the same step; DESIGN
+4al) through the `diversity` keyword of beam_search_batched and beam_search_device, which then keep their bookkeeping per
+(image, group) -- n D searches of k / D beams -- and select with capnet_beam_topk_batched_diverse /
+capnet_beam_advance_diverse, one workgroup per image walking its groups in order. None: the loops as they were.
+
 Deviation from the reference text: `top_k_words / vocab_size` (model.py:249) is an integer
 division here. Under the torch 1.1 the reference pins it was one; under current torch the
 reference line raises.
@@ -85,6 +90,81 @@ class Constraints(object):
 
     def __repr__(self):
         return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r)" % (self.no_repeat_ngram, self.min_words, self.banned)
+
+
+class Diversity(object):
+    """Diverse beam search (Vijayakumar et al. 2016), the same rule on every route. Image i's k beams form
+    `groups` = D groups of k' = k / D; group g holds slots g k' .. g k' + k' - 1 and is a beam search of its own with the
+    plain bookkeeping (step 1: its first row alone; <end> retires a beam; it ends when none is live). At each step the
+    groups select in order; group g takes its live best candidates (row, word v) by
+        key = score - strength * c_g(v),
+    score = the running score + the row's log-softmax, c_g(v) = the number of candidates selected at this step by groups
+    0 .. g - 1 of the same image whose word is v. <end> is counted like any word: that is the published rule and fairseq's.
+    A group with no live beam selects nothing and counts nothing; ties go to the lower flat index within the group. The
+    penalty shapes the selection only: a caption's score stays the model's own summed log-probability, the number
+    score_captions returns. With constraints, the exclusions apply first, then the penalty.
+    per_group (needs nbest=True): the result per image is D entries in group order, each the group's best (tokens, score)
+    by rank_completed's key, or None where the group completed nothing -- the "D different captions" call.
+    Diversity(1, x) is not active and runs the plain search."""
+    MAX_GROUPS = 16
+
+    def __init__(self, groups=2, strength=0.5, per_group=False):
+        if isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups <= self.MAX_GROUPS:
+            raise ops.CapnetError("Diversity: groups must be an int, 1 .. %d, not %r" % (self.MAX_GROUPS, groups))
+        if isinstance(strength, bool) or not isinstance(strength, (int, float)):
+            raise ops.CapnetError("Diversity: strength must be a float, not %r" % (strength,))
+        strength = float(strength)
+        if not 0.0 <= strength < float("inf"):      # (NaN fails both comparisons)
+            raise ops.CapnetError("Diversity: strength=%r must be finite and >= 0" % strength)
+        if not isinstance(per_group, bool):
+            raise ops.CapnetError("Diversity: per_group must be a bool, not %r" % (per_group,))
+        self.groups, self.strength, self.per_group = groups, strength, per_group
+
+    @property
+    def active(self):
+        return self.groups > 1
+
+    def check(self, k):
+        """The front end's check for one search (CapnetError): groups divides k (transformers' rule)."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < self.groups or k % self.groups:
+            raise ops.CapnetError("diversity: groups=%d must divide the beam size k=%r" % (self.groups, k))
+
+    def __repr__(self):
+        return "Diversity(groups=%d, strength=%r, per_group=%r)" % (self.groups, self.strength, self.per_group)
+
+
+def dedupe_completed(done):
+    """(score, tokens) pairs with every token list once: the first is kept, the order stays."""
+    seen, out = set(), []
+    for score, tokens in done:
+        key = tuple(int(w) for w in tokens)
+        if key not in seen:
+            seen.add(key)
+            out.append((score, tokens))
+    return out
+
+
+def merge_groups(done_groups, end_token, diversity, nbest=False, length_penalty=0.0):
+    """What a diverse search returns for ONE image from its groups' completed lists `done_groups` (D lists of (score,
+    tokens) in completion order). Without nbest: the token list with the highest score over all groups, ties to the lower
+    group, then the earlier completion; [end_token] where nothing completed. nbest: the lists concatenated in group order,
+    identical token lists once (two groups that find the same caption differ in the last bit of its score: the first is
+    kept), ranked by rank_completed. per_group: D entries, each group's rank_completed winner (tokens, score) or None."""
+    if diversity.per_group:
+        return [(rank_completed(d, length_penalty)[0] if d else None) for d in done_groups]
+    flat = [p for d in done_groups for p in d]
+    if nbest:
+        return rank_completed(dedupe_completed(flat), length_penalty)
+    if not flat:
+        return [int(end_token)]
+    return rank_completed(flat)[0][0]       # penalty 0: the first maximum in group, then completion order
+
+
+def by_completion(ranked):
+    """A state-image's capnet_beam_nbest list at length_penalty 0 ((tokens, score), score descending, ties to the earlier
+    completion) -> (score, tokens) in completion order: hypotheses complete by step, so by length, and those of one step
+    all end in <end> and share its count, so their rank at that step is their score order -- a stable sort by length."""
+    return [(sc, q) for q, sc in sorted(ranked, key=lambda p: len(p[0]))]
 
 
 def banned_words(tokens, step, end_token, constraints):
@@ -164,7 +244,7 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
 
 
 def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, poll_every=0,
-                       nbest=False, length_penalty=0.0, constraints=None):
+                       nbest=False, length_penalty=0.0, constraints=None, diversity=None):
     """beam_search_batched with the bookkeeping on the device (capnet_beam_advance): no host read and no host-built
     tensor per step. Image i keeps rows i k .. i k + k - 1 for the whole search -- its live beams in its first slots, in
     the order beam_search_batched keeps them; dead slots still take the decoder step, their logits are never read -- so
@@ -173,20 +253,26 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
     to the host. poll_every = m > 0: after every m-th step the count of live beams is read (one blocking 4-byte copy)
     and the loop stops at zero -- same result, for decoders whose beams end long before T.
     Returns a list of n token lists (each starts with start_token); nbest: per image the list of (tokens, score) of its
-    completed hypotheses, best first (capnet_beam_nbest in capnet_beam_finish's place, still one copy)."""
+    completed hypotheses, best first (capnet_beam_nbest in capnet_beam_finish's place, still one copy).
+    diversity (an active Diversity whose groups divide k): the state is that of n D searches of k / D beams, every step
+    selects with capnet_beam_advance_diverse, and the result is per image merge_groups of its groups' completed lists
+    (read with capnet_beam_nbest, one copy)."""
     if k > 16 or k > vocab_size:
         raise ops.CapnetError("beam_search_device: k <= 16 and k <= vocab_size")
     T = max_seq_length + 1
     words = [torch.empty(n * k, dtype=torch.long, device=device) for _ in range(2)]
     parent_rows = torch.empty(n * k, dtype=torch.long, device=device)
-    beam = ops.beam_init(n, k, T, start_token, words[0])
+    D = 1 if diversity is None else diversity.groups
+    beam = ops.beam_init(n * D, k // D, T, start_token, words[0])
     prev_words = words[0]
     for step in range(1, T + 1):
         logits, state = step_fn(prev_words, state)
         if logits.shape[1] != vocab_size:
             raise ops.CapnetError("beam_search_device: the step returned %d columns, vocab_size is %d" % (logits.shape[1], vocab_size))
         next_words = words[step & 1]
-        if constraints is None:
+        if diversity is not None:       # one workgroup per image walks its groups in order
+            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints, diversity=diversity)
+        elif constraints is None:
             ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows)
         else:       # the sequences stay in the beam state: the selecting workgroup derives the exclusions from them
             ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints)
@@ -194,6 +280,10 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
             break
         state = tuple(s.index_select(0, parent_rows) for s in state)
         prev_words = next_words
+    if diversity is not None:
+        per = ops.nbest_lists(ops.beam_nbest(beam, end_token, 0.0)[-1], n * D, k // D, T + 2)[0]
+        return [merge_groups([by_completion(per[i * D + g]) for g in range(D)], end_token, diversity, nbest, length_penalty)
+                for i in range(n)]
     if nbest:
         packed = ops.beam_nbest(beam, end_token, length_penalty)[-1]
         return ops.nbest_lists(packed, n, k, T + 2)[0]
@@ -206,15 +296,20 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
 
 
 def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False,
-                        length_penalty=0.0, constraints=None):
+                        length_penalty=0.0, constraints=None, diversity=None):
     """beam_search for n images at once: the evaluator of the reference (stylenet/evaluator.py:63-120) calls sample() per
     test image, k rows per decode step; here the beams of ALL images advance together -- one decoder step over sum(live
     beams) rows and one capnet_beam_topk_batched launch per step -- with per image exactly beam_search's bookkeeping
     (first step: row 0 only; <end> retires a beam; the best completed sequence wins; empty -> [<end>]).
     `state`: tuple of tensors with n * k leading rows (image i's k beams at rows i k .. i k + k - 1).
-    Returns a list of n token lists (each starts with start_token); nbest: per image rank_completed of its completed list."""
+    Returns a list of n token lists (each starts with start_token); nbest: per image rank_completed of its completed list.
+    diversity (an active Diversity whose groups divide k): the bookkeeping below is kept per (image, group) -- n D searches
+    of k / D beams, group g of image i at rows (i D + g) k / D .. -- and every step selects with
+    capnet_beam_topk_batched_diverse, one workgroup per image walking its groups; the result is merge_groups per image."""
     if k > 16:
         raise ops.CapnetError("beam_search_batched: k <= 16")
+    D = 1 if diversity is None else diversity.groups
+    n_img, n, k = n, n * D, k // D
     live = [k] * n                                           # beams still open per image
     seqs = [[[int(start_token)] for _ in range(k)] for _ in range(n)]
     done = [[] for _ in range(n)]                            # (score, sequence) of completed beams
@@ -228,7 +323,11 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
             meta.append((row0, (1 if step == 1 else live[i]) if live[i] else 0, live[i]))
             row0 += live[i]
         meta_d = torch.tensor(meta, dtype=torch.int32, device=device)
-        if constraints is None:
+        if diversity is not None:
+            bans = None if constraints is None else \
+                _bans([q for i in range(n) for q in seqs[i]], step, end_token, constraints, device)
+            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d, bans=bans, diversity=diversity)
+        elif constraints is None:
             scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d)
         else:       # a list for every row of the logits: image i's live beams in order
             live_seqs = [q for i in range(n) for q in seqs[i]]
@@ -260,6 +359,8 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
         prev_words = torch.tensor(next_words, dtype=torch.long, device=device)
         top_scores = torch.tensor(next_scores, dtype=torch.float32, device=device)
         step += 1
+    if diversity is not None:
+        return [merge_groups(done[i * D:(i + 1) * D], end_token, diversity, nbest, length_penalty) for i in range(n_img)]
     if nbest:
         return [rank_completed(done[i], length_penalty) for i in range(n)]
     out = []

@@ -589,6 +589,32 @@ int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, i
                      slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
 }
 
+// the teams of a diverse one-call search (capnet_beam_decode_diverse, capnet_att_beam_decode_diverse)
+static int beam_teams_check(const char* who, int n, int k, int teams, float strength, int max_steps) {
+  CAPNET_REQUIRE(teams >= 1 && teams <= 16 && k >= teams && k % teams == 0, "%s: teams=%d must divide k=%d (1 .. 16)", who, teams, k);
+  CAPNET_REQUIRE(strength >= 0.f && strength <= 3.0e38f, "%s: strength must be finite and >= 0", who);
+  CAPNET_REQUIRE(n >= 1 && (long)n * teams < (1L << 24) && beam_state_bytes(n * teams, k / teams, max_steps), "%s: n=%d teams=%d", who, n,
+                 teams);
+  return kOk;
+}
+
+int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int E, int H, int V, int max_steps,
+                               long long start_token, long long end_token, const float* emb, const float* const* wcat,
+                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                               float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                               int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                               int n_banned) {
+  if (int rc = stack_decode_check("beam_decode_diverse", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0, 1,
+                                  &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
+    return rc;
+  if (int rc = beam_teams_check("beam_decode_diverse", n, k, teams, strength, max_steps)) return rc;
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  if (int rc = beam_constraints_check("beam_decode_diverse", con)) return rc;
+  const BeamTeams dv{teams, strength, nullptr};
+  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
+                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con, &dv);
+}
+
 size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
 
 int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
@@ -1024,7 +1050,7 @@ static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k
                                  const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                                  capnet_stream_t stream, bool with_alphas, float* alphas,
-                                 const BeamConstraints* con = nullptr) {
+                                 const BeamConstraints* con = nullptr, const BeamTeams* teams = nullptr) {
   if (int rc = att_decode_check("att_beam_decode", cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
                                 wcat, beff, workspace, slab, slab_floats, err_flag, groups))
     return rc;
@@ -1038,9 +1064,26 @@ static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k
   CAPNET_REQUIRE((size_t)alphas % 4 == 0, "att_beam_decode: alphas alignment");
   if (con)
     if (int rc = beam_constraints_check("att_beam_decode", *con)) return rc;
+  if (teams)
+    if (int rc = beam_teams_check("att_beam_decode_diverse", groups * n, k, teams->teams, teams->strength, max_steps)) return rc;
   return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
                          b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
-                         err_flag, S(stream), groups, alphas, con);
+                         err_flag, S(stream), groups, alphas, con, teams);
+}
+
+int capnet_att_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int P, int A, int C, int E, int H,
+                                   int V, int max_steps, long long start_token, long long end_token, const float* att1,
+                                   const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                   const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                   const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                   int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                   capnet_stream_t stream, float* alphas, int no_repeat_ngram, int min_words, const int* banned,
+                                   int n_banned) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  const BeamTeams dv{teams, strength, nullptr};
+  return att_beam_decode_entry(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz,
+                               w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths,
+                               steps_run, err_flag, stream, false, alphas, &con, &dv);
 }
 
 int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
@@ -1380,6 +1423,19 @@ int capnet_beam_advance_constrained_traced(void* beam, void* trace, float* logit
   return beam_advance_constrained(beam, logits, ld, V, n, k, max_steps, step, end_token,
                                   BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream),
                                   trace);
+}
+int capnet_beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int teams, float strength,
+                                int max_steps, int step, long long end_token, int no_repeat_ngram, int min_words,
+                                const int* banned, int n_banned, long long* next_words, long long* parent_rows,
+                                capnet_stream_t stream) {
+  return beam_advance_diverse(beam, trace, logits, ld, V, n, k, teams, strength, max_steps, step, end_token,
+                              BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream));
+}
+int capnet_beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n, int teams,
+                                     float strength, const int* bans, int cap, float* top_scores, long long* top_index,
+                                     capnet_stream_t stream) {
+  return beam_topk_batched_diverse(logits, ld, V, prev_scores, meta, n, teams, strength, bans, cap, top_scores, top_index,
+                                   S(stream));
 }
 int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
                               long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {

@@ -263,7 +263,11 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
                      int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
                      bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr,
                      void* trace = nullptr, int* trace_rows = nullptr,   // (the row trace: beam_advance's, logits form only)
-                     const BeamConstraints* con = nullptr) {              // (constraints: the logits form only)
+                     const BeamConstraints* con = nullptr,                // (constraints: the logits form only)
+                     const BeamTeams* dv = nullptr) {                     // (diverse search: the logits form only)
+  // dv: the step still runs on n images of k rows; the beam state is that of n teams searches of k / teams beams and lies
+  // in the caller's block dv->beam, not in the layout's slot (which is sized for (n, k))
+  const int sn = dv ? n * dv->teams : n, sk = dv ? k / dv->teams : k;
   const int nk = n * k, rpg = nk / groups;
   const BeamDecodeWs w = beam_decode_layout(nlayers, n, k, H, V, max_steps, fused, groups);
   const size_t st_bytes = (size_t)nk * 2 * nlayers * H * sizeof(float);
@@ -278,12 +282,13 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
   long long* words[2] = {reinterpret_cast<long long*>(p + w.words),
                          reinterpret_cast<long long*>(p + w.words + (w.parent - w.words) / 2)};
   long long* parent = reinterpret_cast<long long*>(p + w.parent);
-  void* beam = p + w.beam;
+  void* beam = dv ? dv->beam : p + w.beam;
+  const BeamConstraints none{0, 0, nullptr, 0};
   const int* live_total = nullptr;
-  if (int rc = beam_live(beam, n, k, max_steps, &live_total, nullptr, nullptr)) return rc;
+  if (int rc = beam_live(beam, sn, sk, max_steps, &live_total, nullptr, nullptr)) return rc;
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
   else CAPNET_HIP_CHECK(hipMemsetAsync(state[0], 0, st_bytes, s));
-  if (int rc = beam_init(beam, n, k, max_steps, start_token, words[0], s)) return rc;
+  if (int rc = beam_init(beam, sn, sk, max_steps, start_token, words[0], s)) return rc;
   if (fused) CAPNET_HIP_CHECK(hipMemsetAsync(tk_ws, 0, 16 * (size_t)groups, s));   // vocab_topk's counters, one per group
   int issued = 0;
   for (int step = 1; step <= max_steps; ++step) {
@@ -300,7 +305,10 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
         rc = sgemm_splitk(false, true, rpg, V, H, h_top + (size_t)g * rpg * H, H, Cwg[g], H, logits + (size_t)g * rpg * V, V,
                           Cbg ? Cbg[g] : nullptr, 0, slab, slab_floats, s);
       if (rc == kOk && !Cwg) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
-      if (rc == kOk)
+      if (rc == kOk && dv)
+        rc = beam_advance_diverse(beam, trace, logits, V, V, n, k, dv->teams, dv->strength, max_steps, step, end_token,
+                                  con ? *con : none, words[step & 1], parent, s);
+      else if (rc == kOk)
         rc = con ? beam_advance_constrained(beam, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s, trace)
                  : beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);
     }
@@ -314,21 +322,24 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
     }
   }
   if (steps_run) *steps_run = issued;
-  return beam_finish(beam, n, k, max_steps, end_token, seqs, lengths, s, trace, trace_rows);
+  return beam_finish(beam, sn, sk, max_steps, end_token, seqs, lengths, s, trace, trace_rows);
 }
 
 int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
-                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups, const BeamConstraints* con) {
+                long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups, const BeamConstraints* con,
+                const BeamTeams* teams) {
   n *= groups;   // beam groups: weight groups x images, group-major
+  BeamTeams dv{0, 0.f, nullptr};
+  if (teams) dv = BeamTeams{teams->teams, teams->strength, reinterpret_cast<char*>(ws) + beam_decode_layout(nlayers, n, k, H, V, max_steps).total};
   return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
                    lengths, steps_run, s,
                    [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
                      return stacked_decode_step(cell, nlayers, n * k, E, H, V, tok, emb, wcat, beff, sin, sout, h_top, err_flag, s,
                                                 parent, groups);
                    },
-                   false, 1, nullptr, nullptr, nullptr, nullptr, con);
+                   false, 1, nullptr, nullptr, nullptr, nullptr, con, teams ? &dv : nullptr);
 }
 
 // ---- capnet.seq2seq's beam search: the same loop from a given state, step 1 on given inputs (EncoderRNN's feature
@@ -402,8 +413,9 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups, float* alphas, const BeamConstraints* con) {
+                    hipStream_t s, int groups, float* alphas, const BeamConstraints* con, const BeamTeams* teams) {
   const int nq = groups * n;   // beam groups: weight groups x images, group-major
+  const int D = teams ? teams->teams : 1;
   char* p = reinterpret_cast<char*>(ws);
   void* step_ws = p + beam_decode_layout(nlayers, nq, k, H, V, max_steps).total;
   // the maps (alphas set): behind the search's own workspace, trace | rows int32 [nq][max_steps] | history
@@ -419,6 +431,15 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
     p += align16((size_t)nq * max_steps * sizeof(int));
     hist = reinterpret_cast<float*>(p);
   }
+  // diverse: behind everything above, the state of nq D searches of k / D beams | with the maps, the winners' rows
+  // [nq D][max_steps] (the slot above holds nq of them only)
+  BeamTeams dv{0, 0.f, nullptr};
+  if (teams) {
+    char* tail = reinterpret_cast<char*>(ws) + (alphas ? att_beam_decode_alphas_ws_bytes(nlayers, groups, n, k, P, A, C, E, H, V, max_steps)
+                                                        : att_beam_decode_ws_bytes(nlayers, nq, k, P, A, C, E, H, V, max_steps));
+    dv = BeamTeams{D, teams->strength, tail};
+    if (alphas) rows = reinterpret_cast<int*>(tail + align16(beam_state_bytes(nq * D, k / D, max_steps)));
+  }
   int calls = 0;   // the step the loop is at: it calls the step once per step, in order
   const int rc = beam_loop(
       nlayers, nq, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs, lengths,
@@ -428,9 +449,9 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
         return att_decode_step(cell, nlayers, n, k, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff, sin, parent,
                                sout, h_top, step_ws, slab, slab_floats, err_flag, s, groups, slice);
       },
-      false, 1, nullptr, nullptr, trace, rows, con);
+      false, 1, nullptr, nullptr, trace, rows, con, teams ? &dv : nullptr);
   if (rc != kOk || !alphas) return rc;
-  hipLaunchKernelGGL(alpha_gather_kernel, dim3(nq, max_steps), dim3(256), 0, s, hist, rows, nq * k, max_steps, P, alphas);
+  hipLaunchKernelGGL(alpha_gather_kernel, dim3(nq * D, max_steps), dim3(256), 0, s, hist, rows, nq * k, max_steps, P, alphas);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

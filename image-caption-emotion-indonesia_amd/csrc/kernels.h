@@ -239,6 +239,21 @@ int beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev,
                      float* out_scores, long long* out_index, hipStream_t stream);
 int beam_topk_batched_banned(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
                              float* out_scores, long long* out_index, hipStream_t stream);
+// diverse search: n images x k beams as D teams of k / D; `beam` (and `trace`, nullable) are those of n D
+// searches of k / D beams. Team g of an image selects after teams 0 .. g - 1 by score - strength * (candidates they chose
+// at this step with the same word); the scores written are unpenalised. c: zeros mean no constraint. The logits block is
+// modified. beam_topk_batched_diverse: the host loops' form, meta [n D][3] per (image, team), bans nullable.
+int beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int D, float strength,
+                         int max_steps, int step, long long end_token, const BeamConstraints& c, long long* next_words,
+                         long long* parent_rows, hipStream_t stream);
+// (the one-call searches: beam -- the block that holds the state of n teams searches of k / teams beams)
+struct BeamTeams {
+  int teams;
+  float strength;
+  void* beam;
+};
+int beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev, const int* meta, int n, int D, float strength,
+                              const int* bans, int cap, float* out_scores, long long* out_index, hipStream_t stream);
 // (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
 // done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
 // winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)
@@ -345,7 +360,10 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
                 long long end_token, const float* emb, const float* const* wcat, const float* const* beff, const float* Cw,
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
                 long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1,
-                const BeamConstraints* con = nullptr);
+                const BeamConstraints* con = nullptr, const BeamTeams* teams = nullptr);
+// (teams, here and in att_beam_decode: the diverse search -- every step's selection is beam_advance_diverse on a state of
+// n teams searches of k / teams beams, which lies BEHIND the workspace described here (beam_state_bytes(n teams, k / teams,
+// max_steps) more bytes; teams->beam is ignored); seqs / lengths then hold n teams winners, one per (image, team))
 // (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
 // (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance_constrained)
 // vocab_topk.hip: per row the k best of h[r] . W[v] + b[v] (logit descending, index ascending; fewer pickable entries: the
@@ -443,7 +461,8 @@ int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, in
                     const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                     const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                     size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
-                    hipStream_t s, int groups = 1, float* alphas = nullptr, const BeamConstraints* con = nullptr);
+                    hipStream_t s, int groups = 1, float* alphas = nullptr, const BeamConstraints* con = nullptr,
+                    const BeamTeams* teams = nullptr);
 // alphas [groups n][max_steps][P], optional (ws: att_beam_decode_alphas_ws_bytes): row e - 1 of a caption is the softmax over
 // the pixels that preceded its word e, rows past its length - 1 are zero. ws then continues: the row trace | the winners'
 // rows | the history [max_steps][groups n k][P] of every step's maps

@@ -434,11 +434,58 @@ struct BeamExclList {
   }
 };
 
+// the exclusions of the diverse host route: BeamExclList, or nothing where bans is null
+struct BeamExclListOrNone {
+  typedef float* logits_t;
+  static constexpr bool kActive = true;
+  const int* bans;
+  int cap;
+  __device__ __forceinline__ void operator()(float* logits, long ld, int rows, int V) const {
+    if (bans) BeamExclList{bans, cap}(logits, ld, rows, V);
+  }
+};
+
+// ---- diverse search: the Hamming penalty of a later team. A penalty is a second functor beam_topk_body
+// runs after the exclusions: apply() writes logit - strength * count over the listed words of every competing row (at
+// most kBeamMax (word, count) pairs, the words distinct, so no two threads share an address) after saving the originals
+// in LDS; the selection passes then rank by the penalised key without consulting anything. score() gives back what is
+// carried forward and reported: (prev - lse) + the ORIGINAL logit, formed exactly as the plain selection forms it. At
+// strength 0 the key is the score bit for bit. kActive false: no code at all.
+struct BeamNoPen {
+  static constexpr bool kActive = false;
+};
+
+struct BeamPenList {
+  static constexpr bool kActive = true;
+  const int *word, *count;   // LDS, [kBeamMax]
+  int n_words;
+  float strength;
+  float* orig;               // LDS, [kBeamMax rows][kBeamMax words]
+  __device__ __forceinline__ void apply(float* logits, long ld, int rows, int V) const {
+    for (int t = threadIdx.x; t < rows * n_words; t += kBeamThreads) {
+      const int r = t / n_words, q = t % n_words, w = word[q];
+      if (w >= 0 && w < V) {
+        const float x = logits[(long)r * ld + w];
+        orig[r * kBeamMax + q] = x;
+        logits[(long)r * ld + w] = x - strength * (float)count[q];
+      }
+    }
+  }
+  __device__ __forceinline__ float score(const float* logits, long ld, int V, long flat, float base) const {
+    const int r = (int)(flat / V), w = (int)(flat % V);
+    float x = logits[(long)r * ld + w];
+    for (int q = 0; q < n_words; ++q)
+      if (word[q] == w) x = orig[r * kBeamMax + q];
+    return base + x;
+  }
+};
+
 // the expansion of ONE image's beams (a whole workgroup)
-template <class Excl>
+template <class Excl, class Pen = BeamNoPen>
 __device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, long ld, int rows, int V,
                                                const float* __restrict__ prev, int k, float* __restrict__ out_scores,
-                                               long long* __restrict__ out_index, const Excl excl = Excl()) {
+                                               long long* __restrict__ out_index, const Excl excl = Excl(),
+                                               const Pen pen = Pen()) {
   __shared__ float s_red[kBeamThreads / 64];
   __shared__ long s_idx[kBeamThreads / 64];
   __shared__ float s_lse[kBeamMax];
@@ -476,6 +523,10 @@ __device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, l
     excl(logits, ld, rows, V);
     __syncthreads();
   }
+  if constexpr (Pen::kActive) {   // after the exclusions: -inf stays -inf
+    pen.apply(logits, ld, rows, V);
+    __syncthreads();
+  }
   for (int j = 0; j < k; ++j) {
     float bv = -INFINITY;
     long bi = 0x7fffffffffffffffL;
@@ -502,6 +553,8 @@ __device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, l
       long i = s_idx[0];
       for (int w = 1; w < kBeamThreads / 64; ++w) beam_better(s_red[w], s_idx[w], v, i);
       s_sel[j] = i;
+      if constexpr (Pen::kActive)   // the unpenalised score (i past the rows: nothing was comparable, as in the plain body)
+        if (i / V < rows) v = pen.score(logits, ld, V, i, prev[i / V] - s_lse[i / V]);
       out_scores[j] = v;
       out_index[j] = i;
     }
@@ -959,6 +1012,126 @@ int beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, i
                  ld, step, max_steps);
   hipLaunchKernelGGL(beam_advance_constrained_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, logits, ld, V, n, k, max_steps,
                      step, end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, next_words, parent_rows, trace);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// ---- diverse beam search (Vijayakumar et al. 2016): image i's k beams are D teams of kt = k / D, team g in
+// slots g kt .. g kt + kt - 1 -- so the state of a diverse search over n images IS the plain BeamState of n D searches
+// of kt beams (state-image i D + g), and init, tail, finish, n-best and the trace are the plain ones. One workgroup per
+// image walks its teams in order: team g takes its live best by key = score - strength * c_g(v), c_g(v) the number of
+// candidates teams 0 .. g - 1 of the image selected at THIS step whose word is v (<end> counted like any word; a team
+// with no live beam selects nothing and adds nothing). The counts are a (word, count) list in LDS, at most k <= 16
+// entries, alive until the image's last team; the scores carried forward are unpenalised (BeamPenList).
+// every thread reaches every barrier: live is uniform over the workgroup, and a dead team skips the body as a whole.
+__device__ __forceinline__ void beam_team_count(const long long* s_flat, int picked, int V, int* s_word, int* s_count,
+                                                int* s_words) {
+  int m = *s_words;
+  for (int j = 0; j < picked; ++j) {
+    const int w = (int)(s_flat[j] % V);
+    int q = 0;
+    while (q < m && s_word[q] != w) ++q;
+    if (q < m) ++s_count[q];
+    else if (m < kBeamMax) { s_word[m] = w; s_count[m] = 1; ++m; }
+  }
+  *s_words = m;
+}
+
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_diverse_kernel(
+    void* beam, void* trace, float* logits, long ld, int V, int n, int k, int D, float strength, int max_steps, int step,
+    long long end_token, int no_repeat_ngram, int min_words, const int* __restrict__ banned, int n_banned,
+    long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_pw[kBeamMax], s_pc[kBeamMax], s_pn;
+  __shared__ float s_orig[kBeamMax * kBeamMax];
+  const int kt = k / D, nq = n * D, L = max_steps + 2;
+  const BeamState s = beam_state_of(beam, nq, kt, max_steps);
+  const BeamTrace tr = beam_trace_of(trace, nq, kt, max_steps);
+  if (threadIdx.x == 0) s_pn = 0;
+  __syncthreads();
+  for (int g = 0; g < D; ++g) {
+    const int q = blockIdx.x * D + g;
+    const long row0 = (long)q * kt;
+    const int live = s.live[q];
+    if (live > 0) {
+      const BeamExclState excl{s.seq + ((long)((step - 1) & 1) * nq * kt + row0) * L, L, step, no_repeat_ngram, min_words,
+                               end_token, banned, n_banned};
+      const BeamPenList pen{s_pw, s_pc, s_pn, strength, s_orig};
+      beam_topk_body<BeamExclState, BeamPenList>(logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score,
+                                                 s_flat, excl, pen);
+    }
+    beam_advance_tail<kBeamThreads>(s, q, nq, kt, max_steps, step, end_token, V, live, live, s_score, s_flat, next_words,
+                                    parent_rows, tr);
+    if (live > 0 && threadIdx.x == 0) beam_team_count(s_flat, live, V, s_pw, s_pc, &s_pn);
+    __syncthreads();   // the body's and the tail's arrays are the next team's
+  }
+}
+
+// the host loops' form (capnet_beam_topk_batched_diverse): workgroup i expands image i's D teams in order; meta [n D][3] =
+// (first row, rows that compete, live) per (image, team), flat indices local to the team, outputs [n D][16]
+__global__ __launch_bounds__(kBeamThreads) void beam_topk_batched_diverse_kernel(
+    float* logits, long ld, int V, const float* __restrict__ prev, const int* __restrict__ meta, int D, float strength,
+    const int* __restrict__ bans, int cap, float* __restrict__ out_scores, long long* __restrict__ out_index) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_pw[kBeamMax], s_pc[kBeamMax], s_pn;
+  __shared__ float s_orig[kBeamMax * kBeamMax];
+  if (threadIdx.x == 0) s_pn = 0;
+  __syncthreads();
+  for (int g = 0; g < D; ++g) {
+    const int q = blockIdx.x * D + g;
+    const int row0 = meta[3 * q], rows = meta[3 * q + 1], live = meta[3 * q + 2];
+    if (live > 0 && rows > 0 && live <= kBeamMax && rows <= kBeamMax) {   // (meta lives on the device: bounded here)
+      const BeamExclListOrNone excl{bans ? bans + (long)row0 * (1 + cap) : nullptr, cap};
+      const BeamPenList pen{s_pw, s_pc, s_pn, strength, s_orig};
+      beam_topk_body<BeamExclListOrNone, BeamPenList>(logits + (long)row0 * ld, ld, rows, V, prev + row0, live, s_score, s_flat,
+                                                      excl, pen);
+      if (threadIdx.x < live) {
+        out_scores[(long)q * kBeamMax + threadIdx.x] = s_score[threadIdx.x];
+        out_index[(long)q * kBeamMax + threadIdx.x] = s_flat[threadIdx.x];
+      }
+      if (threadIdx.x == 0) beam_team_count(s_flat, live, V, s_pw, s_pc, &s_pn);
+    }
+    __syncthreads();
+  }
+}
+
+static int beam_diverse_check(const char* who, int D, float strength) {
+  CAPNET_REQUIRE(D >= 1 && D <= kBeamMax, "%s: teams=%d (1 .. %d)", who, D, kBeamMax);
+  CAPNET_REQUIRE(strength >= 0.f && strength <= 3.0e38f, "%s: strength must be finite and >= 0", who);
+  return kOk;
+}
+
+int beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int D, float strength,
+                         int max_steps, int step, long long end_token, const BeamConstraints& c, long long* next_words,
+                         long long* parent_rows, hipStream_t stream) {
+  if (int rc = beam_diverse_check("beam_advance_diverse", D, strength)) return rc;
+  CAPNET_REQUIRE(n >= 1 && n <= (1 << 24) && k >= D && k <= kBeamMax && k % D == 0,
+                 "beam_advance_diverse: n=%d k=%d teams=%d (teams divides k <= %d)", n, k, D, kBeamMax);
+  if (int rc = beam_check("beam_advance_diverse", beam, n * D, k / D, max_steps)) return rc;
+  if (int rc = beam_constraints_check("beam_advance_diverse", c)) return rc;
+  CAPNET_REQUIRE(logits && next_words && parent_rows && (size_t)trace % 4 == 0, "beam_advance_diverse: null argument or trace alignment");
+  CAPNET_REQUIRE(V >= 1 && k <= V && ld >= V && step >= 1 && step <= max_steps,
+                 "beam_advance_diverse: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", V, k, ld,
+                 step, max_steps);
+  hipLaunchKernelGGL(beam_advance_diverse_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, trace, logits, ld, V, n, k, D,
+                     strength, max_steps, step, end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, next_words,
+                     parent_rows);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev, const int* meta, int n, int D, float strength,
+                              const int* bans, int cap, float* out_scores, long long* out_index, hipStream_t stream) {
+  CAPNET_REQUIRE(logits && prev && meta && out_scores && out_index && n >= 0 && V >= 1 && ld >= V,
+                 "beam_topk_batched_diverse: bad argument");
+  if (int rc = beam_diverse_check("beam_topk_batched_diverse", D, strength)) return rc;
+  CAPNET_REQUIRE(!bans || (cap >= 1 && cap <= (1 << 16) && (size_t)bans % 4 == 0),
+                 "beam_topk_batched_diverse: cap=%d (1 .. 65536), bans 4-byte aligned", cap);
+  if (n == 0) return kOk;
+  hipLaunchKernelGGL(beam_topk_batched_diverse_kernel, dim3(n), dim3(kBeamThreads), 0, stream, logits, ld, V, prev, meta, D,
+                     strength, bans, cap, out_scores, out_index);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -10,6 +10,8 @@ mode selects, the layout of their beam state, their weight fold.
     ops.beam_decode; (2) one_call and an AttStack: ops.att_beam_decode (_one_call_att); (3) on_device, or one_call with
     neither: capnet.beam.beam_search_device; (4) the host loops beam_search / beam_search_batched. nbest and length_penalty
     go to whichever route runs; _beam_result then shapes what it gave (one image: tensors; maps attached) for all four.
+    diversity (an active capnet.beam.Diversity): the same ladder in _diverse_decode -- the one-call entries' _diverse forms,
+    beam_search_device, or beam_search_batched for one image too -- and capnet.beam.merge_groups shapes the groups' lists.
     return_alphas: the attention maps that preceded every word of the captions -- recorded by the one-call search
     (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
     re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
@@ -43,7 +45,7 @@ import os
 import torch
 
 from . import ops
-from .beam import Constraints, beam_search, beam_search_batched, beam_search_device
+from .beam import Constraints, Diversity, beam_search, beam_search_batched, beam_search_device, by_completion, merge_groups
 
 FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
 _GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torch's i, f, g, o
@@ -132,11 +134,13 @@ def replay_alphas(step_fn, state, seqs, n, k, images=None):
 
 
 def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, nbest=False, length_penalty=0.0,
-                  constraints=None):
+                  constraints=None, diversity=None):
     """ops.att_beam_decode on an AttStack; with the maps, the images in as few chunks as keep the history [steps, rows, P]
     under ALPHA_TRACE_MAX_BYTES. nbest: every chunk's n-best lists (and maps per hypothesis), image by image as without it."""
     T, P = dec.max_seq_length + 1, att.feat.shape[1]
     con = {} if constraints is None else {"constraints": constraints}
+    if diversity is not None:       # (ops.att_beam_decode then returns a list per (image, group): chunks concatenate as ever)
+        con["diversity"] = diversity
 
     def call(a1, ft, st):
         return ops.att_beam_decode(att.cell, a1, ft, att.emb, att.wz, att.bz, att.full_att.weight, att.full_att.bias, att.wcat,
@@ -168,7 +172,7 @@ def _one_image(lists, dev):
 
 
 def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False,
-                return_alphas=False, nbest=False, length_penalty=0.0, constraints=None):
+                return_alphas=False, nbest=False, length_penalty=0.0, constraints=None, diversity=None):
     """Beam search over `step_fn` from `state` (a tuple of tensors: k leading rows, or n k with image i's beams at rows
     i k .. i k + k - 1). n None: one group (capnet.beam.beam_search) -> LongTensor [1, L]; else n groups advancing
     together (beam_search_batched) -> a list of n token lists. on_device: the same results from
@@ -194,7 +198,20 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     routes derive it from the sequences in the beam state (capnet_beam_advance_constrained; the one-call searches'
     _constrained entries). The scores stay the model's own log-probabilities. None, or a Constraints() that excludes
     nothing: every route runs the code it runs without the keyword, unchecked. CapnetError where constraints that exclude
-    something could leave a step fewer than k candidates (Constraints.check)."""
+    something could leave a step fewer than k candidates (Constraints.check).
+    diversity (a capnet.beam.Diversity): diverse beam search -- the k beams of an image as D groups of k / D
+    that select in order at every step, a later group paying `strength` for every candidate an earlier group chose at that
+    step with the same word (<end> counted like any word). The penalty shapes the selection only; the scores stay the
+    model's own log-probabilities. This is the one place that checks it (Diversity.check: D divides k; CapnetError). None,
+    or a Diversity(1, x): every route runs the code it runs without the keyword, unchecked. Routes: the host loop is
+    beam_search_batched with its bookkeeping per (image, group) on capnet_beam_topk_batched_diverse (one image: its n = 1
+    case); on_device is beam_search_device on capnet_beam_advance_diverse; one_call is capnet_beam_decode_diverse /
+    capnet_att_beam_decode_diverse where the plain route would take its one-call entry, else on_device. Results: without nbest the completed hypothesis with the highest score over all groups
+    (ties: the lower group, then the earlier completion; [<end>] where no group completed anything); nbest: all groups'
+    completed hypotheses, identical token lists once, ranked by rank_completed; Diversity(per_group=True), which needs
+    nbest=True: per image D entries in group order, each the group's best (tokens, score) or None. return_alphas: the maps
+    per returned hypothesis in the same nesting (None for None): recorded by the one-call attention search, by replay
+    elsewhere."""
     length_penalty = ops.check_length_penalty("beam search", nbest, length_penalty)
     dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
     nb = dict(nbest=True, length_penalty=length_penalty) if nbest else {}
@@ -204,6 +221,15 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
         if constraints.active:                  # (not active: the calls as they were before there was the keyword, unchecked)
             constraints.check(V, end_token, k, T)
             nb["constraints"] = constraints
+    if diversity is not None:
+        if not isinstance(diversity, Diversity):
+            raise ops.CapnetError("diversity must be a capnet.beam.Diversity, not %r" % (diversity,))
+        if diversity.active:                    # (not active: the calls as they were before there was the keyword, unchecked)
+            diversity.check(k)
+            if diversity.per_group and not nbest:
+                raise ops.CapnetError("diversity: per_group=True needs nbest=True (one (tokens, score) per group)")
+            return _diverse_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call,
+                                   return_alphas, nbest, length_penalty, nb.get("constraints"), diversity)
     plain = getattr(step_fn, "plain", None) if one_call else None
     att = getattr(step_fn, "att", None) if one_call else None
     maps = one = None
@@ -225,6 +251,61 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
             one = beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)     # LongTensor [1, L] as it is returned
             lists = [one[0].tolist()] if return_alphas else None
     return _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest)
+
+
+def _diverse_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas, nbest,
+                    length_penalty, constraints, diversity):
+    """beam_decode under an active Diversity, by beam_decode's own ladder: (1) / (2) one_call on a PlainStack / AttStack of a
+    supported shape: ops.beam_decode / ops.att_beam_decode with diversity=, whose per-(image, group) lists are merged here
+    (capnet.beam.merge_groups; the one-call attention search records the maps of every hypothesis); (3) on_device, or
+    one_call with neither: beam_search_device; (4) beam_search_batched (one image: n = 1). Then the result shaped as
+    beam_decode shapes it. per_group: an entry may be None, and so are its maps; off the one-call attention route the maps
+    come from replay_alphas."""
+    dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
+    D = diversity.groups
+    kw = dict(nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
+    con = {} if constraints is None else {"constraints": constraints}
+    plain = getattr(step_fn, "plain", None) if one_call else None
+    att = getattr(step_fn, "att", None) if one_call else None
+    maps = per = per_maps = None
+    with torch.no_grad():
+        if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, V, len(plain.wcat)):
+            per = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T + 1, start_token,
+                                  end_token, poll_every, diversity=diversity, **con)
+        elif att is not None:
+            per = _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, diversity=diversity, **con)
+            if return_alphas:
+                per, per_maps = per
+        elif on_device or one_call:
+            lists = beam_search_device(step_fn, state, n_img, V, start_token, end_token, k, T, dev, poll_every, **kw)
+        else:
+            lists = beam_search_batched(step_fn, state, n_img, V, start_token, end_token, k, T, dev, **kw)
+    if per is not None:
+        lists = [merge_groups([by_completion(per[i * D + g]) for g in range(D)], end_token, diversity, nbest, length_penalty)
+                 for i in range(n_img)]
+        if per_maps is not None:        # the recorded maps of what the merge kept: by its tokens, the first group that has them
+            def recorded(i, tokens):
+                for g in range(D):
+                    for (q, _), m in zip(per[i * D + g], per_maps[i * D + g]):
+                        if q == tokens:
+                            return m
+                return torch.zeros((0, att.feat.shape[1]), dtype=torch.float32, device=dev)       # [<end>]: nothing completed
+            maps = [[None if p is None else recorded(i, p[0]) for p in hyps] if nbest else recorded(i, hyps)
+                    for i, hyps in enumerate(lists)]
+    if return_alphas and maps is None and nbest:     # the hypotheses that are there, image by image; None keeps its place
+        there = [[p for p in hyps if p is not None] for hyps in lists]
+        got = [iter(m) for m in _nbest_replay(step_fn, state, there, k)]
+        maps = [[None if p is None else next(got[i]) for p in hyps] for i, hyps in enumerate(lists)]
+    elif return_alphas and maps is None:
+        maps = replay_alphas(step_fn, state, lists, n_img, k)
+    if n is None:
+        one = lists[0]
+        if nbest:
+            one = [None if p is None else (torch.tensor([p[0]], dtype=torch.long, device=dev), p[1]) for p in one]
+        else:
+            one = torch.tensor([one], dtype=torch.long, device=dev)
+        lists, maps = one, None if maps is None else maps[0]
+    return (lists, maps) if return_alphas else lists
 
 
 def _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest):

@@ -31,6 +31,20 @@ def _ngrams(tokens, n):
     return Counter(tuple(tokens[i:i + n]) for i in range(len(tokens) - n + 1))
 
 
+def distinct_n(list_of_token_lists, n):
+    """Distinct n-grams divided by total n-grams over the given token lists (Li et al. 2016's distinct-n, the usual number
+    for how different a set of captions is; tokens are taken as they are). 0.0 where there is no n-gram at all."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("distinct_n: n must be an int >= 1, not %r" % (n,))
+    seen, total = set(), 0
+    for tokens in list_of_token_lists:
+        tokens = [int(w) for w in tokens]
+        for i in range(len(tokens) - n + 1):
+            seen.add(tuple(tokens[i:i + n]))
+            total += 1
+    return len(seen) / float(total) if total else 0.0
+
+
 def _closest_ref_length(refs, hyp_len):
     return min((len(r) for r in refs), key=lambda rl: (abs(rl - hyp_len), rl))
 

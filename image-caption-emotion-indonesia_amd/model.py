@@ -643,7 +643,7 @@ class DecoderFactoredLSTM(nn.Module):
         return step_fn, zero_state(rows, self.hidden_size, self.B.weight.device)
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
-               one_call=False, constraints=None, nbest=False, length_penalty=0.0):
+               one_call=False, constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """Beam search, stylenet/model.py:198-294. As in the reference the image features are NOT
         an input of the decode steps (the first input is B(<start>) and the state starts at zero):
         `features` only fixes the device. Returns LongTensor [1, L].
@@ -651,10 +651,12 @@ class DecoderFactoredLSTM(nn.Module):
         in one C call, on the folded chain; same sequences).
         constraints: a capnet.beam.Constraints -- no n-gram twice, no <end> before min_words words, no banned word --
         kept inside the search on whichever route runs (capnet.decode.beam_decode); the scores stay the model's own.
+        diversity: a capnet.beam.Diversity -- the k beams as groups that pay for the words earlier groups chose at the same
+        step, for several different captions of one image (capnet.decode.beam_decode); the scores stay the model's own.
         nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
         first, in place of the one caption."""
         return beam_decode(self, *self._beam(k, mode, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
-                           nbest=nbest, length_penalty=length_penalty, constraints=constraints)
+                           nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, mode='factual',
                       top_p=1.0, device=False, greedy=False):
@@ -682,13 +684,13 @@ class DecoderFactoredLSTM(nn.Module):
         return score_captions(self, features, captions, mode)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0, one_call=False, constraints=None, nbest=False, length_penalty=0.0):
+                     poll_every=0, one_call=False, constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched): what the reference's test-set
         evaluator does image by image (stylenet/evaluator.py:76-84). Returns a list of token lists, each equal to
         sample(features[i:i+1], ...)[0].tolist()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(n * k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           nbest=nbest, length_penalty=length_penalty, constraints=constraints)
+                           nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
 
     def sample_styles(self, features, start_token, end_token, k=5, modes=_MODES, poll_every=0):
         """sample_batch(one_call=True) in every style of `modes` at once -> {mode: [n token lists]}, each list equal to

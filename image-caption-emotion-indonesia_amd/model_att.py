@@ -207,7 +207,7 @@ class DecoderFactoredLSTMAtt(nn.Module):
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False, poll_every=0,
-               one_call=False, return_alphas=False, constraints=None, nbest=False, length_penalty=0.0):
+               one_call=False, return_alphas=False, constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """Beam search with attention, stylenet/model_att.py:307-426. `features`: the encoder map
         of ONE image ([1, S, S, C] or [1, P, C]). Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
@@ -217,10 +217,12 @@ class DecoderFactoredLSTMAtt(nn.Module):
         preceded word e (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route).
         constraints: a capnet.beam.Constraints -- no n-gram twice, no <end> before min_words words, no banned word --
         kept inside the search on whichever route runs (capnet.decode.beam_decode); the scores stay the model's own.
+        diversity: a capnet.beam.Diversity -- the k beams as groups that pay for the words earlier groups chose at the same
+        step, for several different captions of one image (capnet.decode.beam_decode); the scores stay the model's own.
         nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
         first, in place of the one caption. With return_alphas, every hypothesis's own maps beside the list."""
         return beam_decode(self, *self._beam(features, None, k, mode, one_call), None, k, start_token, end_token, on_device, poll_every,
-                           one_call, return_alphas, nbest, length_penalty, constraints)
+                           one_call, return_alphas, nbest, length_penalty, constraints, diversity)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, mode='factual',
                       top_p=1.0, device=False, greedy=False):
@@ -249,14 +251,14 @@ class DecoderFactoredLSTMAtt(nn.Module):
         return decode.score_captions(self, features, captions, mode)
 
     def sample_batch(self, features, start_token, end_token, k=5, factual_limit=-1, mode='factual', on_device=False,
-                     poll_every=0, one_call=False, return_alphas=False, constraints=None, nbest=False, length_penalty=0.0):
+                     poll_every=0, one_call=False, return_alphas=False, constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once: the reference's evaluator
         (stylenet/evaluator.py:63-120) decodes its test images one sample() call at a time; here all live beams of all
         images take their decoder step together (capnet.beam.beam_search_batched). Returns a list of token lists; with
         return_alphas, (the n token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(features, n, k, mode, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas, nbest, length_penalty, constraints)
+                           return_alphas, nbest, length_penalty, constraints, diversity)
 
     def _style_layers(self):
         """The layers sample_styles folds: one here (capnet.stacked_att: num_layers)."""

@@ -96,7 +96,7 @@ class DecoderRNN(nn.Module):
             plain_stack(step_fn, [pack_cell(self.lstm, input_width(self.embed_size))], ops.CELL_LSTM, self.embed.weight, self.linear)
         return step_fn, zero_state(rows, self.hidden_size, self.embed.weight.device)
 
-    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, constraints=None, nbest=False,
+    def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, constraints=None, diversity=None, nbest=False,
                length_penalty=0.0):
         """Beam search, nic/model.py:117-207 (the image features are not an input of the decode
         steps there either). Returns LongTensor [1, L].
@@ -104,10 +104,12 @@ class DecoderRNN(nn.Module):
         in one C call; same sequences).
         constraints: a capnet.beam.Constraints -- no n-gram twice, no <end> before min_words words, no banned word --
         kept inside the search on whichever route runs (capnet.decode.beam_decode); the scores stay the model's own.
+        diversity: a capnet.beam.Diversity -- the k beams as groups that pay for the words earlier groups chose at the same
+        step, for several different captions of one image (capnet.decode.beam_decode); the scores stay the model's own.
         nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
         first, in place of the one caption."""
         return beam_decode(self, *self._beam(k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
-                           nbest=nbest, length_penalty=length_penalty, constraints=constraints)
+                           nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, top_p=1.0, device=False, greedy=False):
         """`samples` captions per row of `features`, DRAWN from the decoder's distribution softmax(logits / temperature)
@@ -133,9 +135,9 @@ class DecoderRNN(nn.Module):
         input: `features` is not read. Under no_grad, dropout following self.training: capnet.decode.score_captions."""
         return score_captions(self, features, captions)
 
-    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, constraints=None, nbest=False,
+    def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, constraints=None, diversity=None, nbest=False,
                      length_penalty=0.0):
         """sample() for every row of `features` at once (capnet.beam.beam_search_batched)."""
         n = features.size(0)
         return beam_decode(self, *self._beam(n * k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           nbest=nbest, length_penalty=length_penalty, constraints=constraints)
+                           nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)

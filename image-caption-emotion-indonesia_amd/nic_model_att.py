@@ -114,7 +114,7 @@ class DecoderRNNAtt(nn.Module):
         return step_fn, (h0, c0) + state + (() if img is None else (img,))
 
     def sample(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False, return_alphas=False,
-               constraints=None, nbest=False, length_penalty=0.0):
+               constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """Beam search with attention, nic/model_att.py:204-297. Returns LongTensor [1, L].
         on_device / poll_every: capnet.decode.beam_decode's (the bookkeeping on the device, same sequences).
         one_call: the whole search in one C call (capnet_att_beam_decode: the k beams of an image on one read of its maps);
@@ -123,10 +123,12 @@ class DecoderRNNAtt(nn.Module):
         (capnet.decode.beam_decode: recorded by the one-call search, replayed on every other route).
         constraints: a capnet.beam.Constraints -- no n-gram twice, no <end> before min_words words, no banned word --
         kept inside the search on whichever route runs (capnet.decode.beam_decode); the scores stay the model's own.
+        diversity: a capnet.beam.Diversity -- the k beams as groups that pay for the words earlier groups chose at the same
+        step, for several different captions of one image (capnet.decode.beam_decode); the scores stay the model's own.
         nbest / length_penalty: capnet.decode.beam_decode's -- every completed hypothesis as a (tokens, score) pair, best
         first, in place of the one caption. With return_alphas, every hypothesis's own maps beside the list."""
         return beam_decode(self, *self._beam(features, None, k, one_call), None, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas, nbest, length_penalty, constraints)
+                           return_alphas, nbest, length_penalty, constraints, diversity)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, top_p=1.0, device=False, greedy=False):
         """`samples` captions per image of `features` ([n, S, S, C] or [n, P, C]), DRAWN from the decoder's distribution
@@ -154,10 +156,10 @@ class DecoderRNNAtt(nn.Module):
         return decode.score_captions(self, features, captions)
 
     def sample_batch(self, features, start_token, end_token, k=5, on_device=False, poll_every=0, one_call=False,
-                     return_alphas=False, constraints=None, nbest=False, length_penalty=0.0):
+                     return_alphas=False, constraints=None, diversity=None, nbest=False, length_penalty=0.0):
         """sample() for every image of `features` ([n, S, S, C] or [n, P, C]) at once (capnet.beam.beam_search_batched).
         Returns a list of token lists, each equal to sample(features[i:i+1], ...)[0].tolist(); with return_alphas, (the n
         token lists, n float32 [len - 1, P] tensors) as sample()."""
         n = features.size(0)
         return beam_decode(self, *self._beam(features, n, k, one_call), n, k, start_token, end_token, on_device, poll_every, one_call,
-                           return_alphas, nbest, length_penalty, constraints)
+                           return_alphas, nbest, length_penalty, constraints, diversity)

@@ -215,9 +215,12 @@ def beam_topk(logits, prev_scores, rows, k, bans=None):
     return scores, index
 
 
-def beam_topk_batched(logits, prev_scores, meta, bans=None):
+def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None):
     """capnet_beam_topk_batched: meta int32 [n, 3] on the device = (first row, competing rows, k) per image.
-    Returns (scores [n, 16] float32, flat_index [n, 16] int64) on the device; only the first k entries of a row are set."""
+    Returns (scores [n, 16] float32, flat_index [n, 16] int64) on the device; only the first k entries of a row are set.
+    diversity (a capnet.beam.Diversity; capnet_beam_topk_batched_diverse): meta has a row per (image, team), image i's
+    teams at rows i D .. i D + D - 1, and one workgroup per image selects for its teams in order under the Hamming penalty
+    (include/capnet.h); bans as below or None. `logits` is modified."""
     _need_cuda(logits, prev_scores, meta)
     logits, prev_scores = _c(logits), _c(prev_scores)
     if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[1] != 3 or not meta.is_contiguous():
@@ -225,6 +228,17 @@ def beam_topk_batched(logits, prev_scores, meta, bans=None):
     n = meta.shape[0]
     scores = torch.empty((n, 16), dtype=torch.float32, device=logits.device)
     index = torch.empty((n, 16), dtype=torch.int64, device=logits.device)
+    if diversity is not None:
+        teams = int(diversity.groups)
+        if n % teams:
+            raise CapnetError("beam_topk_batched: %d rows of meta for teams of %d" % (n, teams))
+        if logits.dtype != torch.float32 or prev_scores.dtype != torch.float32:
+            raise CapnetError("beam_topk_batched: logits and prev_scores must be float32")
+        cap = 0 if bans is None else _check_bans("beam_topk_batched", bans, logits.shape[0])
+        check(_lib.lib().capnet_beam_topk_batched_diverse(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
+                                                          n // teams, teams, float(diversity.strength), ptr(bans), cap, ptr(scores),
+                                                          ptr(index), current_stream()), "capnet_beam_topk_batched_diverse")
+        return scores, index
     if bans is not None:     # capnet_beam_topk_batched_banned: beam_topk's bans, a row for every row of the logits
         cap = _check_bans("beam_topk_batched", bans, logits.shape[0])
         check(_lib.lib().capnet_beam_topk_batched_banned(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
@@ -286,11 +300,18 @@ def constraint_args(constraints, device):
     return int(constraints.no_repeat_ngram), int(constraints.min_words), ptr(arr), len(banned)
 
 
-def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None):
+NO_CONSTRAINTS = (0, 0, None, 0)     # the constraint arguments of an entry that takes them, zeros meaning none
+
+
+def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None, diversity=None, trace=None):
     """capnet_beam_advance: step `step` (1-based) of every image on logits [n k, V]; fills next_words and parent_rows
     (int64 [n k], contiguous) -- see include/capnet.h. constraints (a capnet.beam.Constraints;
     capnet_beam_advance_constrained): the selecting workgroup excludes what they forbid, from the sequences in the state;
-    `logits` is then modified (-inf over the excluded words)."""
+    `logits` is then modified (-inf over the excluded words).
+    diversity (a capnet.beam.Diversity; capnet_beam_advance_diverse): `beam` is the state of n D searches of k / D beams
+    (beam_init(n D, k / D, ...)), state-image i D + g being team g of image i; one workgroup per image walks its teams in
+    order under the Hamming penalty. constraints may be None; trace (beam_trace(beam)) or None, this form only. `logits`
+    is modified."""
     _need_cuda(logits, next_words, parent_rows)
     nk = beam.n * beam.k
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
@@ -298,6 +319,20 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constra
     for w in (next_words, parent_rows):
         if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
             raise CapnetError("beam_advance: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    if diversity is not None:
+        teams = int(diversity.groups)
+        if beam.n % teams:
+            raise CapnetError("beam_advance: a state of %d searches for teams of %d" % (beam.n, teams))
+        if trace is not None:
+            _check_trace("beam_advance", beam, trace)
+        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, logits.device)
+        check(_lib.lib().capnet_beam_advance_diverse(
+            ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1],
+            beam.n // teams, beam.k * teams, teams, float(diversity.strength), beam.max_steps, int(step), int(end_token), *con,
+            ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance_diverse")
+        return
+    if trace is not None:
+        raise CapnetError("beam_advance: trace= goes with diversity=; beam_advance_traced is the plain traced step")
     if constraints is not None:
         check(_lib.lib().capnet_beam_advance_constrained(
             ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
@@ -1239,6 +1274,32 @@ def _search_workspace(size_fn, device, dims, outside):
     return ws
 
 
+def _diverse_workspace(size_fn, device, dims, nq, kt, max_steps, rows_tail, outside):
+    """The cached workspace of a diverse one-call search -> (ws, the byte offset of its beam state): capnet_<...>_ws_bytes(*dims)
+    bytes, FOLLOWED BY the state of nq searches of kt beams (capnet_beam_state_bytes, rounded up to 16) and, with rows_tail,
+    4 nq max_steps bytes for the winners' rows -- the layout include/capnet.h gives for the _diverse entries."""
+    key = ("diverse", size_fn, torch.device(device).index or 0, tuple(dims), nq, kt, bool(rows_tail))
+    hit = _search_ws.get(key)
+    if hit is None:
+        base = getattr(_lib.lib(), size_fn)(*dims)
+        state = _lib.lib().capnet_beam_state_bytes(nq, kt, max_steps)
+        if not base or not state:
+            raise CapnetError(outside)
+        nbytes = base + (state + 15) // 16 * 16 + ((4 * nq * max_steps + 15) // 16 * 16 if rows_tail else 0)
+        hit = _search_ws[key] = (torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), base)
+    return hit
+
+
+def _teams(who, diversity, k, groups):
+    """(teams, strength) of a one-call search's `diversity` (a capnet.beam.Diversity whose groups divide k; one weight group)."""
+    teams = int(diversity.groups)
+    if groups > 1:
+        raise CapnetError("%s: diversity takes one weight group" % who)
+    if teams < 1 or k % teams:
+        raise CapnetError("%s: diversity: %d groups must divide k=%d" % (who, teams, k))
+    return teams, float(diversity.strength)
+
+
 def _tail_words(n):
     """The int64 words behind the n sequences of a result buffer: n int32 lengths and the int32 error word."""
     return n // 2 + 1
@@ -1324,7 +1385,7 @@ def beam_decode_supported(E, H, k, V, num_layers):
 
 
 def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, poll_every=0, state=None,
-                return_steps=False, groups=1, nbest=False, length_penalty=0.0, constraints=None):
+                return_steps=False, groups=1, nbest=False, length_penalty=0.0, constraints=None, diversity=None):
     """The beam search of a plain stack in ONE C call (capnet_beam_decode): n images x k beams, at most max_steps steps of
     (gathered decode step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then capnet_beam_finish.
     cell / wcat / beff: as stacked_decode_step; emb [V, E]; Cw [V, H], Cb [V] or None; state: [n k, 2L, H] or None for
@@ -1338,6 +1399,10 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     the workspace); the list is empty where nothing completed. The search itself is the same.
     constraints (a capnet.beam.Constraints; capnet_beam_decode_constrained, one weight group): every step selects with
     capnet_beam_advance_constrained; workspace and results as without.
+    diversity (a capnet.beam.Diversity whose groups D divide k; capnet_beam_decode_diverse, one weight group; constraints may
+    come with it): the diverse search. The result is then the RAW material of capnet.beam.merge_groups: n D lists, one per
+    (image, team) in that order, each capnet_beam_nbest's (tokens, score) pairs at length_penalty 0 -- whatever nbest and
+    length_penalty say, which are the merge's to apply.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     who = "beam_decode"
     length_penalty = check_length_penalty(who, nbest, length_penalty)
@@ -1350,8 +1415,23 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
                           % (who, E, H, V, k, nl, n_img, T))
     dev = emb.device
     L = _lib.lib()
-    ws = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T),
-                           "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T))
+    outside = "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T)
+    if diversity is not None:
+        teams, strength = _teams(who, diversity, k, groups)
+        ws, beam_at = _diverse_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), n * teams, k // teams, T, False,
+                                         outside)
+        slab = splitk_slab(dev)
+        packed, seqs, lengths = _result_buffer(n * teams, T, dev)
+        flag = err_flag(dev)
+        steps = C.c_int(0)
+        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev)
+        check(L.capnet_beam_decode_diverse(cell, nl, n, k, teams, strength, E, H, V, T, int(start_token), int(end_token), ptr(emb),
+                                           ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
+                                           slab.numel(), int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream(),
+                                           *con), "capnet_beam_decode_diverse")
+        lists = _nbest_of_workspace(ws, beam_at, n * teams, k // teams, T, 0.0, flag)
+        return (lists, steps.value) if return_steps else lists
+    ws = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), outside)
     slab = splitk_slab(dev)
     packed, seqs, lengths = _result_buffer(n, T, dev)
     flag = err_flag(dev)
@@ -1551,7 +1631,7 @@ def att_decode_step(att1, feat, k, tokens, emb, wz, bz, w_full, b_full, wcat, be
 
 def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, k, max_steps, start_token,
                     end_token, poll_every=0, return_steps=False, groups=1, return_alphas=False, nbest=False,
-                    length_penalty=0.0, constraints=None):
+                    length_penalty=0.0, constraints=None, diversity=None):
     """The beam search of an attention decoder in ONE C call (capnet_att_beam_decode): n images x k beams, at most max_steps
     steps of (att_decode_step's step, vocabulary projection on sgemm_splitk's slab, capnet_beam_advance), then
     capnet_beam_finish. Operands as att_decode_step; Cw [V, H], Cb [V] or None; state [n k, 2L, H]: the initial state
@@ -1567,6 +1647,9 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     of (tokens, score) pairs.
     constraints (a capnet.beam.Constraints; capnet_att_beam_decode_constrained / capnet_att_beam_decode_alphas_constrained, one
     weight group): every step selects with capnet_beam_advance_constrained; workspaces and results as without.
+    diversity (capnet_att_beam_decode_diverse, one weight group; constraints may come with it): as beam_decode's -- the
+    result is n D lists of (tokens, score), one per (image, team), capnet_beam_nbest's at length_penalty 0; with
+    return_alphas followed by the maps of every hypothesis in the same nesting.
     Returns the n token lists; with return_steps, (lists, the steps issued); with return_alphas the lists are followed by
     the list of n float32 [len - 1, P] tensors: row e - 1 is the map that preceded word e."""
     groups = _check_groups("att_beam_decode", groups)
@@ -1584,6 +1667,33 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     n_img, n = n, groups * n       # from here on n counts the beam groups
     outside = "att_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T)
     alpha_dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
+    if diversity is not None:
+        teams, strength = _teams("att_beam_decode", diversity, k, groups)
+        if return_alphas:
+            ws, beam_at = _diverse_workspace("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, n * teams, k // teams, T, True,
+                                             outside)
+        else:
+            ws, beam_at = _diverse_workspace("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), n * teams,
+                                             k // teams, T, False, outside)
+        slab = splitk_slab(dev)
+        packed, seqs, lengths = _result_buffer(n * teams, T, dev)
+        flag = err_flag(dev)
+        steps = C.c_int(0)
+        maps = torch.empty((n * teams, T, P), dtype=torch.float32, device=dev) if return_alphas else None
+        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev)
+        check(L.capnet_att_beam_decode_diverse(
+            cell, nl, n, k, teams, strength, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb),
+            ptr(wz), ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
+            slab.numel(), int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream(), ptr(maps), *con),
+            "capnet_att_beam_decode_diverse")
+        where = None
+        if return_alphas:
+            where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*alpha_dims),
+                     L.capnet_att_beam_decode_alphas_ws_hist_offset(*alpha_dims), P)
+        res = _nbest_of_workspace(ws, beam_at, n * teams, k // teams, T, 0.0, flag, where)
+        if return_steps:
+            res = (res[0], steps.value, res[1]) if return_alphas else (res, steps.value)
+        return res
     if return_alphas:
         ws = _search_workspace("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, outside)
     else:

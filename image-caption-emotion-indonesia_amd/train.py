@@ -673,13 +673,14 @@ def val_emotion(encoder, decoder, vocab, criterion, data_loaders, tags, device=N
 
 
 def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=None, verbose=False, on_device=False,
-             one_call=False, cider=False, constraints=None):
+             one_call=False, cider=False, constraints=None, diversity=None):
     """The test-set evaluator, stylenet/evaluator.py:55-120: encoder + decoder in eval mode, every test image decoded by
     beam search, corpus BLEU-1..4 with the reference's four weight tuples (references and hypotheses as the reference
     builds them: the captions' and the sampled ids as they are, <start> / <end> included). The reference calls
     decoder.sample() per image; here a loader batch is decoded at once (decoder.sample_batch: B x k rows per step) --
     the same sequences (tests/test_sample_gpu.py). on_device / one_call: passed on to the decoder (capnet.decode.beam_decode).
     constraints: a capnet.beam.Constraints, passed on likewise (None: the calls as they were).
+    diversity: a capnet.beam.Diversity, passed on likewise; the metrics are taken on the winner over all groups.
     Returns (bleu_1, bleu_2, bleu_3, bleu_4); with cider=True a fifth entry, the mean CIDEr-D of the decoded captions
     (capnet.metrics.corpus_cider_d, the corpus being the loader's own references, as the COCO scorer takes a test split)."""
     decoder.eval()
@@ -693,6 +694,8 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
         kw["one_call"] = True
     if constraints is not None:
         kw["constraints"] = constraints
+    if diversity is not None:
+        kw["diversity"] = diversity
     references, hypotheses = [], []
     for images, captions, lengths, all_captions in data_loader:
         with torch.no_grad():

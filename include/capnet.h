@@ -1355,6 +1355,62 @@ int capnet_att_beam_decode_alphas_constrained(int cell, int nlayers, int n, int 
                                               int* err_flag, capnet_stream_t stream, float* alphas, int no_repeat_ngram,
                                               int min_words, const int* banned, int n_banned);
 
+/* ---- Diverse beam search (capnet.beam.Diversity; Vijayakumar et al. 2016; no reference counterpart) ----
+ * Image i's k beams are `teams` = D teams of kt = k / D (D divides k; "teams", because `groups` already means weight
+ * groups); team g holds slots g kt .. g kt + kt - 1 of the image's k rows. Each team is a beam search of its own with
+ * capnet_beam_advance's bookkeeping (step 1: its first row alone; <end> retires a beam; its live beams are its first slots
+ * in rank order), so the state of a diverse search over n images IS the state of n D plain searches of kt beams:
+ * capnet_beam_state_bytes / _init / _finish / _nbest / _live and the trace are called with (n D, kt), state-image i D + g
+ * being team g of image i. At each step the teams of an image select in order; team g takes its live best candidates
+ * (row, word v) by
+ *     key = score - strength * c_g(v),
+ * score = the running score + the row's log-softmax (what capnet_beam_advance ranks), c_g(v) = the number of candidates
+ * selected at THIS step by teams 0 .. g - 1 of the same image whose word is v. <end> is counted like any word (the published
+ * rule). A team with no live beam selects nothing and counts nothing. Ties go to the lower flat index within the team. The
+ * penalty shapes the selection only: the score carried forward and reported is (prev - lse) + logit, unpenalised. With
+ * constraints (zeros: none; banned may then be NULL) the exclusions apply first, per row from that row's own hypothesis,
+ * then the penalty. strength: finite, >= 0; at 0 every team is exactly its plain search. THE LOGITS BLOCK IS MODIFIED.
+ *   capnet_beam_advance_diverse: one workgroup per image walks its teams; logits [n k][ld], next_words / parent_rows [n k]
+ *     (parent rows are global rows). trace: NULL, or the row trace of (n D, kt) as capnet_beam_advance_traced records it. */
+int capnet_beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int teams, float strength,
+                                int max_steps, int step, long long end_token, int no_repeat_ngram, int min_words,
+                                const int* banned, int n_banned, long long* next_words, long long* parent_rows,
+                                capnet_stream_t stream);
+/* The host loops' form: capnet_beam_topk_batched over n images x `teams` teams. meta is a DEVICE int32 array [n teams][3]
+ * = (first row, rows that compete, live) per (image, team), rows compacted as for capnet_beam_topk_batched; flat indices
+ * are local to the team (row within the team * V + word); outputs [n teams][16], the first `live` entries of a row set.
+ * bans: NULL, or capnet_beam_topk_batched_banned's lists, a row per logits row. */
+int capnet_beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n, int teams,
+                                     float strength, const int* bans, int cap, float* top_scores, long long* top_index,
+                                     capnet_stream_t stream);
+/* capnet_beam_decode (one weight group) as a diverse search: the decode step runs on n images of k rows as ever, every
+ * step's selection is capnet_beam_advance_diverse, and the beam state is that of n teams searches of k / teams beams.
+ * WORKSPACE: capnet_beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps) bytes laid out as there, FOLLOWED BY
+ * capnet_beam_state_bytes(n teams, k / teams, max_steps) bytes, which hold that state when the call returns (for
+ * capnet_beam_nbest with (n teams, k / teams), which yields the scores too). seqs [n teams][max_steps + 2] and lengths
+ * [n teams]: capnet_beam_finish's winner per (image, team), state-image i teams + g being team g of image i. The
+ * constraints follow the stream, zeros meaning none. Always the stored-logits step. */
+int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int E, int H, int V, int max_steps,
+                               long long start_token, long long end_token, const float* emb, const float* const* wcat,
+                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                               float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                               int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                               int n_banned);
+/* capnet_att_beam_decode (one weight group) as a diverse search; an image's maps are still read once for all its k beams.
+ * alphas: NULL, or [n teams][max_steps][P] for the maps of every (image, team)'s winner, recorded as
+ * capnet_att_beam_decode_alphas records them. WORKSPACE: capnet_att_beam_decode_ws_bytes(...) bytes (alphas NULL) or
+ * capnet_att_beam_decode_alphas_ws_bytes(..., groups = 1, ...) bytes (the trace and the history at its offsets: the trace
+ * is that of (n teams, k / teams)), FOLLOWED BY capnet_beam_state_bytes(n teams, k / teams, max_steps) bytes rounded up
+ * to 16 -- the state, as above -- and, with alphas, 4 n teams max_steps more bytes (the winners' rows). */
+int capnet_att_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int P, int A, int C, int E, int H,
+                                   int V, int max_steps, long long start_token, long long end_token, const float* att1,
+                                   const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
+                                   const float* b_full, const float* const* wcat, const float* const* beff, const float* Cw,
+                                   const float* Cb, const float* state0, void* workspace, float* slab, size_t slab_floats,
+                                   int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                   capnet_stream_t stream, float* alphas, int no_repeat_ngram, int min_words, const int* banned,
+                                   int n_banned);
+
 #ifdef __cplusplus
 }
 #endif
