@@ -295,6 +295,14 @@ SIGNATURES = {
     "capnet_att_beam_decode_alphas_constrained": (_i, [_i] * 11 + [C.c_longlong, C.c_longlong] + [_vp] * 7 +
                                                   [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp,
                                                    C.POINTER(_i), _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "capnet_beam_advance_forced": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "capnet_beam_topk_batched_forced": (_i, [_vp, _l, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_longlong, _vp, _vp, _vp]),
+    "capnet_beam_decode_forced": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, C.POINTER(_vp),
+                                       C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i), _vp, _vp,
+                                       _i, _i, _vp, _i, _vp, _i]),
+    "capnet_att_beam_decode_forced": (_i, [_i] * 11 + [C.c_longlong, C.c_longlong] + [_vp] * 7 +
+                                      [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, C.POINTER(_i),
+                                       _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "capnet_beam_advance_diverse": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, C.c_float, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp,
                                          _vp, _vp]),
     "capnet_beam_topk_batched_diverse": (_i, [_vp, _l, _i, _vp, _vp, _i, _i, C.c_float, _vp, _i, _vp, _vp, _vp]),

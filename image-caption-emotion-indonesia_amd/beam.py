@@ -22,6 +22,11 @@ Diversity / merge_groups: diverse beam search (beam groups that pay for the word
 (image, group) -- n D searches of k / D beams -- and select with capnet_beam_topk_batched_diverse /
 capnet_beam_advance_diverse, one workgroup per image walking its groups in order. None: the loops as they were.
 
+Constraints(forced=...) / forced_allocate / met_mask: words every completed caption must contain (dynamic beam allocation; DESIGN
+4am), through the same `constraints` keyword: the host loops hand every row's met mask beside its ban list to
+capnet_beam_topk_batched_forced (beam_search with n = 1), beam_search_device's ops.beam_advance selects with
+capnet_beam_advance_forced. Without forced words: the loops as they were.
+
 Deviation from the reference text: `top_k_words / vocab_size` (model.py:249) is an integer
 division here. Under the torch 1.1 the reference pins it was one; under current torch the
 reference line raises.
@@ -50,10 +55,18 @@ class Constraints(object):
       * g = no_repeat_ngram (0 to 4) >= 1, len(tokens) >= g, and appending v would complete a g-gram the hypothesis already
         contains, <start> included (g = 1: no word twice; a context seen several times bans several words).
     Excluded candidates leave AFTER the log-softmax: a survivor's score is the model's own summed log-probability, the number
-    score_captions returns; nothing is renormalised. Constraints() excludes nothing and runs the unconstrained code."""
-    MAX_NGRAM, MAX_BANNED = 4, 32
+    score_captions returns; nothing is renormalised. Constraints() excludes nothing and runs the unconstrained code.
+    forced (Post & Vilar 2018, dynamic beam allocation): a tuple of at most MAX_FORCED distinct word ids that
+    every completed caption must contain. The met count of a candidate (row r, word v) is the number of forced ids among
+    w_1 .. w_{s-1} of r or equal to v (<start> does not count). <end> is excluded on a row whose own met count is below
+    F = len(forced). The step's pool holds (1) the plain selection's `live` best non-excluded candidates, (2) for every
+    competing row every forced id not yet in it and not excluded on it, (3) every competing row's best non-excluded word --
+    a flat index once -- and forced_allocate deals the `live` slots out of it: banks by met count, each by score descending
+    with ties to the lower flat index, visited F, F - 1 .. 0, F ..; the order of taking is the output order. Scores stay the
+    model's own log-probabilities. Without `forced` every route runs exactly the code it runs without the field."""
+    MAX_NGRAM, MAX_BANNED, MAX_FORCED = 4, 32, 4
 
-    def __init__(self, no_repeat_ngram=0, min_words=0, banned=()):
+    def __init__(self, no_repeat_ngram=0, min_words=0, banned=(), forced=()):
         for name, v in (("no_repeat_ngram", no_repeat_ngram), ("min_words", min_words)):
             if isinstance(v, bool) or not isinstance(v, int):
                 raise ops.CapnetError("Constraints: %s must be an int, not %r" % (name, v))
@@ -69,11 +82,21 @@ class Constraints(object):
                 raise ops.CapnetError("Constraints: banned holds word ids (ints >= 0), not %r" % (w,))
         if len(banned) > self.MAX_BANNED or len(set(banned)) != len(banned):
             raise ops.CapnetError("Constraints: banned must be at most %d distinct word ids" % self.MAX_BANNED)
-        self.no_repeat_ngram, self.min_words, self.banned = no_repeat_ngram, min_words, banned
+        if isinstance(forced, (str, bytes)) or not hasattr(forced, "__iter__"):
+            raise ops.CapnetError("Constraints: forced must be a sequence of word ids, not %r" % (forced,))
+        forced = tuple(forced)
+        for w in forced:
+            if isinstance(w, bool) or not isinstance(w, int) or w < 0:
+                raise ops.CapnetError("Constraints: forced holds word ids (ints >= 0), not %r" % (w,))
+        if len(forced) > self.MAX_FORCED or len(set(forced)) != len(forced):
+            raise ops.CapnetError("Constraints: forced must be at most %d distinct word ids" % self.MAX_FORCED)
+        if set(forced) & set(banned):
+            raise ops.CapnetError("Constraints: forced=%r and banned=%r share a word id" % (forced, banned))
+        self.no_repeat_ngram, self.min_words, self.banned, self.forced = no_repeat_ngram, min_words, banned, forced
 
     @property
     def active(self):
-        return bool(self.no_repeat_ngram or self.min_words or self.banned)
+        return bool(self.no_repeat_ngram or self.min_words or self.banned or self.forced)
 
     def check(self, vocab_size, end_token, k, max_seq_length):
         """The front end's check for one search (CapnetError): no banned id is end_token or outside the vocabulary, and
@@ -87,9 +110,15 @@ class Constraints(object):
                                   "candidates" % (vocab_size, len(self.banned), max_seq_length, k))
         if not self.min_words < max_seq_length:
             raise ops.CapnetError("constraints: min_words=%d must be below max_seq_length %d" % (self.min_words, max_seq_length))
+        if int(end_token) in self.forced or any(w >= vocab_size for w in self.forced):
+            raise ops.CapnetError("constraints: forced=%r must be word ids below %d other than end_token %d"
+                                  % (self.forced, vocab_size, int(end_token)))
+        if self.forced and not len(self.forced) < max_seq_length:
+            raise ops.CapnetError("constraints: %d forced words must be fewer than max_seq_length %d" % (len(self.forced), max_seq_length))
 
     def __repr__(self):
-        return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r)" % (self.no_repeat_ngram, self.min_words, self.banned)
+        tail = ", forced=%r" % (self.forced,) if self.forced else ""
+        return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r%s)" % (self.no_repeat_ngram, self.min_words, self.banned, tail)
 
 
 class Diversity(object):
@@ -179,7 +208,43 @@ def banned_words(tokens, step, end_token, constraints):
         for e in range(n - g + 1):
             if list(tokens[e:e + g - 1]) == tail:
                 out.add(int(tokens[e + g - 1]))
+    if constraints.forced and met_mask(tokens, constraints.forced) != (1 << len(constraints.forced)) - 1:
+        out.add(int(end_token))       # forced words: no <end> before the hypothesis holds them all
     return sorted(out)
+
+
+def met_mask(tokens, forced):
+    """Bit f set where forced[f] occurs in `tokens` = [start, w_1 ..] behind <start>."""
+    words = set(int(w) for w in tokens[1:])
+    return sum(1 << f for f, w in enumerate(forced) if int(w) in words)
+
+
+def forced_allocate(pool, live, F):
+    """The allocation of Constraints' forced words as code. pool: [(score, flat, met)], a flat index once, met the
+    candidate's met count 0 .. F -> the entries taken, in taking order: within a bank (a met count) by score descending, ties
+    to the lower flat index; the banks are visited F, F - 1 .. 0, F .., a visit takes the bank's best untaken entry if it
+    has one, until `live` are taken or the pool is empty. (A flat index listed twice -- a candidate that entered the pool by
+    two of its parts -- counts once, its first entry.)"""
+    seen, once = set(), []
+    for p in pool:
+        if p[1] not in seen:
+            seen.add(p[1])
+            once.append(p)
+    pool = once
+    banks = [sorted((p for p in pool if p[2] == b), key=lambda p: (-p[0], p[1])) for b in range(F + 1)]
+    at, out, b = [0] * (F + 1), [], F
+    target = min(live, len(pool))
+    while len(out) < target:
+        if at[b] < len(banks[b]):
+            out.append(banks[b][at[b]])
+            at[b] += 1
+        b = F if b == 0 else b - 1
+    return out
+
+
+def _met(rows_tokens, constraints, device):
+    """The met masks of a step's logits rows as capnet_beam_topk_batched_forced takes them: int32 [rows] on the device."""
+    return torch.tensor([met_mask(t, constraints.forced) for t in rows_tokens], dtype=torch.int32, device=device)
 
 
 def _bans(rows_tokens, step, end_token, constraints, device):
@@ -208,6 +273,12 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
         rows = 1 if step == 1 else logits.shape[0]
         if constraints is None:
             scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k)
+        elif constraints.forced:    # forced words: capnet_beam_topk_batched_forced with n = 1, the rows' met masks beside their lists
+            meta_d = torch.tensor([[0, rows, k]], dtype=torch.int32, device=device)
+            scores_d, flat_d = ops.beam_topk_batched(logits, top_k_scores, meta_d,
+                                                     bans=_bans(seqs, step, end_token, constraints, device),
+                                                     forced=(constraints, _met(seqs, constraints, device), end_token))
+            scores_d, flat_d = scores_d[0, :k], flat_d[0, :k]
         else:       # the hypotheses are held here: every competing row's list, removed after the log-sum-exp
             scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k,
                                              bans=_bans(seqs[:rows], step, end_token, constraints, device))
@@ -329,6 +400,11 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
             scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d, bans=bans, diversity=diversity)
         elif constraints is None:
             scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d)
+        elif constraints.forced:    # forced words: every row's met mask beside its list
+            live_seqs = [q for i in range(n) for q in seqs[i]]
+            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d,
+                                                     bans=_bans(live_seqs, step, end_token, constraints, device),
+                                                     forced=(constraints, _met(live_seqs, constraints, device), end_token))
         else:       # a list for every row of the logits: image i's live beams in order
             live_seqs = [q for i in range(n) for q in seqs[i]]
             scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d,

@@ -589,6 +589,22 @@ int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, i
                      slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
 }
 
+int capnet_beam_decode_forced(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                              long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                              const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                              size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                              capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                              const int* forced, int n_forced) {
+  if (int rc = stack_decode_check("beam_decode_forced", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0, 1,
+                                  &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
+    return rc;
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
+  if (int rc = beam_constraints_check("beam_decode_forced", con)) return rc;
+  if (int rc = beam_forced_check("beam_decode_forced", con)) return rc;
+  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
+                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
+}
+
 // the teams of a diverse one-call search (capnet_beam_decode_diverse, capnet_att_beam_decode_diverse)
 static int beam_teams_check(const char* who, int n, int k, int teams, float strength, int max_steps) {
   CAPNET_REQUIRE(teams >= 1 && teams <= 16 && k >= teams && k % teams == 0, "%s: teams=%d must divide k=%d (1 .. 16)", who, teams, k);
@@ -1086,6 +1102,21 @@ int capnet_att_beam_decode_diverse(int cell, int nlayers, int n, int k, int team
                                steps_run, err_flag, stream, false, alphas, &con, &dv);
 }
 
+int capnet_att_beam_decode_forced(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                  long long start_token, long long end_token, const float* att1, const float* feat,
+                                  const float* emb, const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                                  long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                  float* alphas, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                  const int* forced, int n_forced) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
+  if (int rc = beam_forced_check("att_beam_decode_forced", con)) return rc;
+  return att_beam_decode_entry(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz,
+                               w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths,
+                               steps_run, err_flag, stream, false, alphas, &con);
+}
+
 int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
                                   int max_steps, long long start_token, long long end_token, const float* att1,
                                   const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
@@ -1436,6 +1467,20 @@ int capnet_beam_topk_batched_diverse(float* logits, long ld, int V, const float*
                                      capnet_stream_t stream) {
   return beam_topk_batched_diverse(logits, ld, V, prev_scores, meta, n, teams, strength, bans, cap, top_scores, top_index,
                                    S(stream));
+}
+int capnet_beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                               long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                               const int* forced, int n_forced, long long* next_words, long long* parent_rows,
+                               capnet_stream_t stream) {
+  return beam_advance_forced(beam, trace, logits, ld, V, n, k, max_steps, step, end_token,
+                             BeamConstraints{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced}, next_words,
+                             parent_rows, S(stream));
+}
+int capnet_beam_topk_batched_forced(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                    const int* bans, int cap, const int* met, const int* forced, int n_forced,
+                                    long long end_token, float* top_scores, long long* top_index, capnet_stream_t stream) {
+  return beam_topk_batched_forced(logits, ld, V, prev_scores, meta, n, bans, cap, met, forced, n_forced, end_token, top_scores,
+                                  top_index, S(stream));
 }
 int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
                               long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {

@@ -308,6 +308,8 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
       if (rc == kOk && dv)
         rc = beam_advance_diverse(beam, trace, logits, V, V, n, k, dv->teams, dv->strength, max_steps, step, end_token,
                                   con ? *con : none, words[step & 1], parent, s);
+      else if (rc == kOk && con && con->n_forced)   // (forced words: the selection swapped, all else as it is)
+        rc = beam_advance_forced(beam, trace, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s);
       else if (rc == kOk)
         rc = con ? beam_advance_constrained(beam, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s, trace)
                  : beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);

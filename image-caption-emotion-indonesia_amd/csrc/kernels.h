@@ -229,6 +229,10 @@ struct BeamConstraints {
   int no_repeat_ngram, min_words;
   const int* banned;
   int n_banned;
+  // forced words: n_forced (<= 4) distinct ids of the DEVICE array forced that every completed hypothesis must
+  // contain; 0: none. Only beam_advance_forced and the one-call loops read them.
+  const int* forced = nullptr;
+  int n_forced = 0;
 };
 int beam_constraints_check(const char* who, const BeamConstraints& c);
 int beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
@@ -254,6 +258,18 @@ struct BeamTeams {
 };
 int beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev, const int* meta, int n, int D, float strength,
                               const int* bans, int cap, float* out_scores, long long* out_index, hipStream_t stream);
+// forced words: beam_advance_constrained with c.forced -- <end> is excluded on a row that lacks a forced id, and
+// the `live` candidates are dealt out of a pool (the plain selection, every row's missing forced ids, every row's best word)
+// across banks by met count, F, F - 1 .. 0, F ..; the scores are the plain ones. trace nullable. The logits block is modified.
+// beam_topk_batched_forced: the host loops' form, meta as beam_topk_batched's, bans nullable, met int32 per logits row
+// (bit f: forced[f] is among the row's words).
+int beam_forced_check(const char* who, const BeamConstraints& c);
+int beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                        long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
+                        hipStream_t stream);
+int beam_topk_batched_forced(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
+                             const int* met, const int* forced, int n_forced, long long end_token, float* out_scores,
+                             long long* out_index, hipStream_t stream);
 // (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
 // done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
 // winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)
@@ -365,7 +381,8 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
 // n teams searches of k / teams beams, which lies BEHIND the workspace described here (beam_state_bytes(n teams, k / teams,
 // max_steps) more bytes; teams->beam is ignored); seqs / lengths then hold n teams winners, one per (image, team))
 // (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
-// (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance_constrained)
+// (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance_constrained, or
+// beam_advance_forced where con->n_forced > 0 and there are no teams)
 // vocab_topk.hip: per row the k best of h[r] . W[v] + b[v] (logit descending, index ascending; fewer pickable entries: the
 // tail is (-inf, -1)) and log sum_v exp, one launch, no logits in memory (ws: vocab_topk_ws_bytes, its first 16 bytes zero
 // before the first use)

@@ -480,12 +480,19 @@ struct BeamPenList {
   }
 };
 
+// ---- forced words: what runs behind the k plain passes. A pool is a third functor of beam_topk_body: it is
+// handed the rows' log-sum-exp and the plain selection (out_scores / out_index, which then lie in LDS) and replaces it
+// with its own. kActive false: no code at all.
+struct BeamNoPool {
+  static constexpr bool kActive = false;
+};
+
 // the expansion of ONE image's beams (a whole workgroup)
-template <class Excl, class Pen = BeamNoPen>
+template <class Excl, class Pen = BeamNoPen, class Pool = BeamNoPool>
 __device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, long ld, int rows, int V,
                                                const float* __restrict__ prev, int k, float* __restrict__ out_scores,
                                                long long* __restrict__ out_index, const Excl excl = Excl(),
-                                               const Pen pen = Pen()) {
+                                               const Pen pen = Pen(), const Pool pool = Pool()) {
   __shared__ float s_red[kBeamThreads / 64];
   __shared__ long s_idx[kBeamThreads / 64];
   __shared__ float s_lse[kBeamMax];
@@ -560,6 +567,7 @@ __device__ __forceinline__ void beam_topk_body(typename Excl::logits_t logits, l
     }
     __syncthreads();
   }
+  if constexpr (Pool::kActive) pool(logits, ld, rows, V, prev, s_lse, k, out_scores, out_index);
 }
 
 __global__ __launch_bounds__(kBeamThreads) void beam_topk_kernel(
@@ -1132,6 +1140,279 @@ int beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev, 
   if (n == 0) return kOk;
   hipLaunchKernelGGL(beam_topk_batched_diverse_kernel, dim3(n), dim3(kBeamThreads), 0, stream, logits, ld, V, prev, meta, D,
                      strength, bans, cap, out_scores, out_index);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// ---- forced words (Post & Vilar 2018, dynamic beam allocation): every completed hypothesis contains all F <= 4
+// forced ids. A row's met mask (bit f: forced[f] occurs among its words, <start> apart) is recomputed each step -- the
+// device form scans the row's `step` tokens in BeamState.seq, a thread per (row, forced id); the host form is handed it.
+// BeamExclForced is the exclusion: the inner functor's, then <end> on every row whose mask is not full. BeamForcedPool
+// runs behind the `live` plain passes, on their result in LDS:
+//   pool  [0, 16)   the plain selection (part 1)
+//         [16, 80)  (row r, forced[f]) at 16 + 4 r + f where bit f of r's mask is clear and the logit is not -inf (part 2)
+//         [80, 96)  row r's best word that is not -inf at 80 + r: one more pass over the block, each row split over the
+//                   waves (part 3)
+//   bank  the popcount of (the row's mask | the bits of the forced ids the word equals)
+//   an entry whose flat index an earlier entry holds leaves; within a bank the rank of an entry is the number of entries
+//   that beat it (score descending, ties to the lower flat index: a total order, flat indices being distinct by now);
+//   one thread then visits the banks F, F - 1 .. 0, F .. and takes each one's best untaken entry until `live` are taken
+//   or the pool is empty. The order of taking is the output order.
+// Scores are (prev - lse) + logit, the plain selection's expression on the same operands: the same bits. Static LDS: the
+// pool's 96 x (4 + 8 + 4 + 4) bytes, the 5 x 96 rank table, part 3's 16 x 16 partial bests (3 KB) and a few counters, 6.9 KB
+// beside the body's own.
+constexpr int kForcedMax = 4, kForcedPool = kBeamMax + kBeamMax * kForcedMax + kBeamMax;
+
+template <class Inner>
+struct BeamExclForced {
+  typedef float* logits_t;
+  static constexpr bool kActive = true;
+  Inner inner;
+  const int* tok;        // the image's rows of BeamState.seq ([k][L], `step` tokens each), or null: met_in holds the masks
+  int L, step;
+  const int* met_in;     // int32 per competing row (the host form), or null
+  const int* forced;     // DEVICE array [n_forced]
+  int n_forced;
+  long long end_token;
+  int* s_met;            // LDS [kBeamMax]: the masks, for the pool behind the selection too
+  __device__ __forceinline__ void operator()(float* logits, long ld, int rows, int V) const {
+    const int tid = threadIdx.x, full = (1 << n_forced) - 1;
+    if (tid < kBeamMax) s_met[tid] = (met_in && tid < rows) ? (met_in[tid] & full) : 0;
+    __syncthreads();
+    if (tok) {
+      for (int t = tid; t < rows * n_forced; t += kBeamThreads) {
+        const int r = t / n_forced, f = t % n_forced, w = forced[f];
+        const int* q = tok + (long)r * L;
+        bool hit = false;
+        for (int e = 1; e < step; ++e) hit |= q[e] == w;
+        if (hit) atomicOr(&s_met[r], 1 << f);
+      }
+      __syncthreads();
+    }
+    inner(logits, ld, rows, V);
+    if (tid < rows && s_met[tid] != full && end_token >= 0 && end_token < V) logits[(long)tid * ld + end_token] = -INFINITY;
+  }
+};
+
+struct BeamForcedPool {
+  static constexpr bool kActive = true;
+  const int* forced;     // DEVICE array [n_forced]
+  int n_forced;
+  const int* s_met;      // LDS [kBeamMax], BeamExclForced's
+  int* s_picked;         // LDS: how many were taken (live, unless the pool held fewer)
+  __device__ __forceinline__ void operator()(const float* logits, long ld, int rows, int V, const float* __restrict__ prev,
+                                             const float* s_lse, int live, float* sel_score, long long* sel_flat) const {
+    __shared__ float p_score[kForcedPool];
+    __shared__ long long p_flat[kForcedPool];
+    __shared__ int p_valid[kForcedPool], p_bank[kForcedPool];
+    __shared__ int s_at[(kForcedMax + 1) * kForcedPool], s_cnt[kForcedMax + 1], s_next[kForcedMax + 1];
+    constexpr int kWaves = kBeamThreads / 64;
+    __shared__ float s_pv[kBeamMax * kWaves];      // part 3: the waves' partial bests per row
+    __shared__ long s_pi[kBeamMax * kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long total = (long)rows * V;
+    // parts 1 and 2: a thread per slot
+    if (tid < kBeamMax + kBeamMax * kForcedMax) {
+      float v = 0.f;
+      long long flat = 0;
+      bool ok = false;
+      if (tid < kBeamMax) {
+        if (tid < live) {
+          v = sel_score[tid];
+          flat = sel_flat[tid];
+          ok = flat >= 0 && flat < total && v > -INFINITY;
+        }
+      } else {
+        const int r = (tid - kBeamMax) / kForcedMax, f = (tid - kBeamMax) % kForcedMax;
+        if (r < rows && f < n_forced && !((s_met[r] >> f) & 1)) {
+          const int w = forced[f];
+          if (w >= 0 && w < V) {
+            const float x = logits[(long)r * ld + w];
+            v = (prev[r] - s_lse[r]) + x;
+            flat = (long long)r * V + w;
+            ok = x > -INFINITY && v > -INFINITY;
+          }
+        }
+      }
+      p_score[tid] = v;
+      p_flat[tid] = flat;
+      p_valid[tid] = ok ? 1 : 0;
+    }
+    if (tid <= kForcedMax) { s_cnt[tid] = 0; s_next[tid] = 0; }
+    // part 3: every row's best word in one pass over the block -- each row split over the workgroup's waves (a wave's 64
+    // lanes alone on a row of 8192 would make 128 dependent trips), the waves' partial bests in LDS, one barrier for all
+    // rows, then thread r folds row r's partials
+    for (int r = 0; r < rows; ++r) {
+      const float* p = logits + (long)r * ld;
+      const float base = prev[r] - s_lse[r];
+      float bv = -INFINITY;
+      long bi = 0x7fffffffffffffffL;
+      for (int v = tid; v < V; v += kBeamThreads) {
+        const float x = p[v];
+        if (x > -INFINITY) beam_better(base + x, (long)r * V + v, bv, bi);
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o);
+        const long oi = __shfl_xor(bi, o);
+        beam_better(ov, oi, bv, bi);
+      }
+      if (lane == 0) { s_pv[r * kWaves + wave] = bv; s_pi[r * kWaves + wave] = bi; }
+    }
+    __syncthreads();
+    if (tid < kBeamMax) {
+      float bv = -INFINITY;
+      long bi = 0x7fffffffffffffffL;
+      if (tid < rows)
+        for (int w = 0; w < kWaves; ++w) beam_better(s_pv[tid * kWaves + w], s_pi[tid * kWaves + w], bv, bi);
+      const bool ok = tid < rows && bi < total && bv > -INFINITY;
+      p_score[kForcedPool - kBeamMax + tid] = bv;
+      p_flat[kForcedPool - kBeamMax + tid] = ok ? bi : 0;
+      p_valid[kForcedPool - kBeamMax + tid] = ok ? 1 : 0;
+    }
+    __syncthreads();
+    // the bank of every entry; an entry whose flat index an earlier entry holds leaves
+    if (tid < kForcedPool) {
+      int bank = -1;
+      if (p_valid[tid]) {
+        const long long flat = p_flat[tid];
+        bool dup = false;
+        for (int e = 0; e < tid; ++e) dup |= p_valid[e] && p_flat[e] == flat;
+        if (!dup) {
+          const int r = (int)(flat / V), w = (int)(flat % V);
+          int m = s_met[r];
+          for (int f = 0; f < n_forced; ++f)
+            if (forced[f] == w) m |= 1 << f;
+          bank = __popc(m);
+        }
+      }
+      p_bank[tid] = bank;
+    }
+    __syncthreads();
+    // the rank within the bank, by counting
+    if (tid < kForcedPool && p_bank[tid] >= 0) {
+      const int bank = p_bank[tid];
+      const float v = p_score[tid];
+      const long long flat = p_flat[tid];
+      int rank = 0;
+      for (int e = 0; e < kForcedPool; ++e) {
+        const float ov = p_score[e];
+        rank += (p_bank[e] == bank && (ov > v || (ov == v && p_flat[e] < flat))) ? 1 : 0;
+      }
+      s_at[bank * kForcedPool + rank] = tid;
+      atomicAdd(&s_cnt[bank], 1);
+    }
+    __syncthreads();
+    // the walk: banks F, F - 1 .. 0, F ..; the order of taking is the output order
+    if (tid == 0) {
+      int have = 0;
+      for (int b = 0; b <= n_forced; ++b) have += s_cnt[b];
+      const int target = min(live, have);
+      int taken = 0, b = n_forced;
+      while (taken < target) {
+        const int q = s_next[b];
+        if (q < s_cnt[b]) {
+          const int e = s_at[b * kForcedPool + q];
+          s_next[b] = q + 1;
+          sel_score[taken] = p_score[e];
+          sel_flat[taken] = p_flat[e];
+          ++taken;
+        }
+        b = b == 0 ? n_forced : b - 1;
+      }
+      *s_picked = taken;
+    }
+    __syncthreads();
+  }
+};
+
+// one step of image blockIdx.x under forced words (capnet_beam_advance_forced): beam_advance_constrained_kernel with the
+// met masks, the <end> exclusion and the pool around its selection; the tail is used as it is
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_forced_kernel(
+    void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+    int no_repeat_ngram, int min_words, const int* __restrict__ banned, int n_banned, const int* __restrict__ forced,
+    int n_forced, long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_met[kBeamMax], s_picked;
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const int live = s.live[i];
+  int picked = 0;
+  if (live > 0) {
+    const int* tok = s.seq + ((long)((step - 1) & 1) * n * k + row0) * L;
+    const BeamExclForced<BeamExclState> excl{
+        BeamExclState{tok, L, step, no_repeat_ngram, min_words, end_token, banned, n_banned}, tok, L, step, nullptr, forced,
+        n_forced, end_token, s_met};
+    beam_topk_body<BeamExclForced<BeamExclState>, BeamNoPen, BeamForcedPool>(
+        logits + row0 * ld, ld, step == 1 ? 1 : live, V, s.scores + row0, live, s_score, s_flat, excl, BeamNoPen(),
+        BeamForcedPool{forced, n_forced, s_met, &s_picked});
+    picked = s_picked;
+  }
+  beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, picked, s_score, s_flat, next_words,
+                                  parent_rows, beam_trace_of(trace, n, k, max_steps));
+}
+
+// the host loops' form (capnet_beam_topk_batched_forced): meta as capnet_beam_topk_batched's; bans nullable; met int32 per
+// logits row; outputs [n][16], the first `live` entries of a row set (fewer where the pool held fewer: the rest is
+// -inf / -1)
+__global__ __launch_bounds__(kBeamThreads) void beam_topk_batched_forced_kernel(
+    float* logits, long ld, int V, const float* __restrict__ prev, const int* __restrict__ meta, const int* __restrict__ bans,
+    int cap, const int* __restrict__ met, const int* __restrict__ forced, int n_forced, long long end_token,
+    float* __restrict__ out_scores, long long* __restrict__ out_index) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_met[kBeamMax], s_picked;
+  const int row0 = meta[3 * blockIdx.x], rows = meta[3 * blockIdx.x + 1], live = meta[3 * blockIdx.x + 2];
+  if (live <= 0 || rows <= 0 || live > kBeamMax || rows > kBeamMax) return;   // (meta lives on the device: bounded here)
+  const BeamExclForced<BeamExclListOrNone> excl{
+      BeamExclListOrNone{bans ? bans + (long)row0 * (1 + cap) : nullptr, cap}, nullptr, 0, 0, met + row0, forced, n_forced,
+      end_token, s_met};
+  beam_topk_body<BeamExclForced<BeamExclListOrNone>, BeamNoPen, BeamForcedPool>(
+      logits + (long)row0 * ld, ld, rows, V, prev + row0, live, s_score, s_flat, excl, BeamNoPen(),
+      BeamForcedPool{forced, n_forced, s_met, &s_picked});
+  if (threadIdx.x < live) {
+    const bool has = threadIdx.x < s_picked;
+    out_scores[(long)blockIdx.x * kBeamMax + threadIdx.x] = has ? s_score[threadIdx.x] : -INFINITY;
+    out_index[(long)blockIdx.x * kBeamMax + threadIdx.x] = has ? s_flat[threadIdx.x] : -1;
+  }
+}
+
+int beam_forced_check(const char* who, const BeamConstraints& c) {
+  CAPNET_REQUIRE(c.n_forced >= 1 && c.n_forced <= kForcedMax && c.forced && (size_t)c.forced % 4 == 0,
+                 "%s: n_forced=%d (1 .. %d), forced a 4-byte aligned device array", who, c.n_forced, kForcedMax);
+  return kOk;
+}
+
+int beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                        long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
+                        hipStream_t stream) {
+  if (int rc = beam_check("beam_advance_forced", beam, n, k, max_steps)) return rc;
+  if (int rc = beam_constraints_check("beam_advance_forced", c)) return rc;
+  if (int rc = beam_forced_check("beam_advance_forced", c)) return rc;
+  CAPNET_REQUIRE(logits && next_words && parent_rows && (size_t)trace % 4 == 0, "beam_advance_forced: null argument or trace alignment");
+  CAPNET_REQUIRE(V >= 1 && k <= V && ld >= V && step >= 1 && step <= max_steps,
+                 "beam_advance_forced: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", V, k, ld,
+                 step, max_steps);
+  hipLaunchKernelGGL(beam_advance_forced_kernel, dim3(n), dim3(kBeamThreads), 0, stream, beam, trace, logits, ld, V, n, k,
+                     max_steps, step, end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, c.forced, c.n_forced,
+                     next_words, parent_rows);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+int beam_topk_batched_forced(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
+                             const int* met, const int* forced, int n_forced, long long end_token, float* out_scores,
+                             long long* out_index, hipStream_t stream) {
+  CAPNET_REQUIRE(logits && prev && meta && met && out_scores && out_index && n >= 0 && V >= 1 && ld >= V,
+                 "beam_topk_batched_forced: bad argument");
+  CAPNET_REQUIRE(!bans || (cap >= 1 && cap <= (1 << 16) && (size_t)bans % 4 == 0),
+                 "beam_topk_batched_forced: cap=%d (1 .. 65536), bans 4-byte aligned", cap);
+  CAPNET_REQUIRE((size_t)met % 4 == 0, "beam_topk_batched_forced: met must be 4-byte aligned");
+  if (int rc = beam_forced_check("beam_topk_batched_forced", BeamConstraints{0, 0, nullptr, 0, forced, n_forced})) return rc;
+  if (n == 0) return kOk;
+  hipLaunchKernelGGL(beam_topk_batched_forced_kernel, dim3(n), dim3(kBeamThreads), 0, stream, logits, ld, V, prev, meta, bans,
+                     cap, met, forced, n_forced, end_token, out_scores, out_index);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -199,6 +199,10 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     _constrained entries). The scores stay the model's own log-probabilities. None, or a Constraints() that excludes
     nothing: every route runs the code it runs without the keyword, unchecked. CapnetError where constraints that exclude
     something could leave a step fewer than k candidates (Constraints.check).
+    Constraints(forced=...): words every completed caption must contain, by dynamic beam allocation inside the
+    selection, through the same keyword on the same routes -- capnet_beam_topk_batched_forced under the host loops,
+    capnet_beam_advance_forced on_device, capnet_beam_decode_forced / capnet_att_beam_decode_forced one_call (the latter
+    records the maps itself, as the constrained one-call search does). Not with an active diversity (CapnetError).
     diversity (a capnet.beam.Diversity): diverse beam search -- the k beams of an image as D groups of k / D
     that select in order at every step, a later group paying `strength` for every candidate an earlier group chose at that
     step with the same word (<end> counted like any word). The penalty shapes the selection only; the scores stay the
@@ -226,6 +230,8 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
             raise ops.CapnetError("diversity must be a capnet.beam.Diversity, not %r" % (diversity,))
         if diversity.active:                    # (not active: the calls as they were before there was the keyword, unchecked)
             diversity.check(k)
+            if ops.has_forced(nb.get("constraints")):
+                raise ops.CapnetError("constraints: forced words do not go with an active diversity (DESIGN 7)")
             if diversity.per_group and not nbest:
                 raise ops.CapnetError("diversity: per_group=True needs nbest=True (one (tokens, score) per group)")
             return _diverse_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call,

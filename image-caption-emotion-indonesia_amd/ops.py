@@ -215,12 +215,16 @@ def beam_topk(logits, prev_scores, rows, k, bans=None):
     return scores, index
 
 
-def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None):
+def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None, forced=None):
     """capnet_beam_topk_batched: meta int32 [n, 3] on the device = (first row, competing rows, k) per image.
     Returns (scores [n, 16] float32, flat_index [n, 16] int64) on the device; only the first k entries of a row are set.
     diversity (a capnet.beam.Diversity; capnet_beam_topk_batched_diverse): meta has a row per (image, team), image i's
     teams at rows i D .. i D + D - 1, and one workgroup per image selects for its teams in order under the Hamming penalty
-    (include/capnet.h); bans as below or None. `logits` is modified."""
+    (include/capnet.h); bans as below or None. `logits` is modified.
+    forced = (constraints, met, end_token) (capnet_beam_topk_batched_forced): a capnet.beam.Constraints with forced words,
+    met int32 [rows] on the device -- per logits row the mask of the forced ids its hypothesis holds -- and <end>, which the
+    kernel excludes on a row whose mask is not full; bans as below or None. The selection is the forced-word allocation
+    (include/capnet.h); `logits` is modified."""
     _need_cuda(logits, prev_scores, meta)
     logits, prev_scores = _c(logits), _c(prev_scores)
     if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[1] != 3 or not meta.is_contiguous():
@@ -228,6 +232,21 @@ def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None):
     n = meta.shape[0]
     scores = torch.empty((n, 16), dtype=torch.float32, device=logits.device)
     index = torch.empty((n, 16), dtype=torch.int64, device=logits.device)
+    if forced is not None:
+        constraints, met, end_token = forced
+        if diversity is not None:
+            raise CapnetError("beam_topk_batched: forced words do not go with diversity")
+        if logits.dtype != torch.float32 or prev_scores.dtype != torch.float32:
+            raise CapnetError("beam_topk_batched: logits and prev_scores must be float32")
+        _need_cuda(met)
+        if met.dtype != torch.int32 or met.dim() != 1 or met.numel() < logits.shape[0] or not met.is_contiguous():
+            raise CapnetError("beam_topk_batched: met must be a contiguous int32 tensor with an entry per logits row")
+        cap = 0 if bans is None else _check_bans("beam_topk_batched", bans, logits.shape[0])
+        check(_lib.lib().capnet_beam_topk_batched_forced(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
+                                                         n, ptr(bans), cap, ptr(met), *forced_args(constraints, logits.device),
+                                                         int(end_token), ptr(scores), ptr(index), current_stream()),
+              "capnet_beam_topk_batched_forced")
+        return scores, index
     if diversity is not None:
         teams = int(diversity.groups)
         if n % teams:
@@ -303,6 +322,34 @@ def constraint_args(constraints, device):
 NO_CONSTRAINTS = (0, 0, None, 0)     # the constraint arguments of an entry that takes them, zeros meaning none
 
 
+def has_forced(constraints):
+    """Whether `constraints` (a capnet.beam.Constraints or None) names forced words: the capnet_*_forced entries then."""
+    return constraints is not None and bool(getattr(constraints, "forced", ()))
+
+
+def forced_args(constraints, device):
+    """The two arguments behind constraint_args' four in the capnet_*_forced entries: (the forced ids as a device int32 array,
+    their count), the array kept as constraint_args keeps the banned words'."""
+    forced = tuple(int(w) for w in constraints.forced)
+    key = ("forced", forced, torch.device(device).index or 0)
+    arr = _banned_dev.get(key)
+    if arr is None:
+        if len(_banned_dev) >= BANNED_CACHE_MAX:
+            _banned_dev.clear()
+        arr = _banned_dev[key] = torch.tensor(forced or (0,), dtype=torch.int32, device=device)
+    return ptr(arr), len(forced)
+
+
+def _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints):
+    """capnet_beam_advance_forced on checked operands; trace None or checked."""
+    nk = beam.n * beam.k
+    dev = logits.device
+    check(_lib.lib().capnet_beam_advance_forced(
+        ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
+        beam.max_steps, int(step), int(end_token), *constraint_args(constraints, dev), *forced_args(constraints, dev),
+        ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance_forced")
+
+
 def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None, diversity=None, trace=None):
     """capnet_beam_advance: step `step` (1-based) of every image on logits [n k, V]; fills next_words and parent_rows
     (int64 [n k], contiguous) -- see include/capnet.h. constraints (a capnet.beam.Constraints;
@@ -331,8 +378,13 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constra
             beam.n // teams, beam.k * teams, teams, float(diversity.strength), beam.max_steps, int(step), int(end_token), *con,
             ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance_diverse")
         return
+    if has_forced(constraints):     # capnet_beam_advance_forced: the constraints' exclusions, then the forced-word allocation
+        if trace is not None:
+            _check_trace("beam_advance", beam, trace)
+        _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints)
+        return
     if trace is not None:
-        raise CapnetError("beam_advance: trace= goes with diversity=; beam_advance_traced is the plain traced step")
+        raise CapnetError("beam_advance: trace= goes with diversity= or forced words; beam_advance_traced is the plain traced step")
     if constraints is not None:
         check(_lib.lib().capnet_beam_advance_constrained(
             ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
@@ -402,6 +454,9 @@ def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent
     for w in (next_words, parent_rows):
         if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
             raise CapnetError("beam_advance_traced: next_words / parent_rows must be contiguous int64 [n k] tensors")
+    if has_forced(constraints):
+        _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints)
+        return
     if constraints is not None:     # capnet_beam_advance_constrained_traced: beam_advance's constraints, the trace as here
         check(_lib.lib().capnet_beam_advance_constrained_traced(
             ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n,
@@ -1398,7 +1453,8 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     first by score / (len(tokens) - 1)^length_penalty (_nbest_of_workspace: capnet_beam_nbest on the state the search left in
     the workspace); the list is empty where nothing completed. The search itself is the same.
     constraints (a capnet.beam.Constraints; capnet_beam_decode_constrained, one weight group): every step selects with
-    capnet_beam_advance_constrained; workspace and results as without.
+    capnet_beam_advance_constrained; workspace and results as without. With forced words (Constraints(forced=...)):
+    capnet_beam_decode_forced, every step selecting with capnet_beam_advance_forced.
     diversity (a capnet.beam.Diversity whose groups D divide k; capnet_beam_decode_diverse, one weight group; constraints may
     come with it): the diverse search. The result is then the RAW material of capnet.beam.merge_groups: n D lists, one per
     (image, team) in that order, each capnet_beam_nbest's (tokens, score) pairs at length_penalty 0 -- whatever nbest and
@@ -1441,8 +1497,13 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     if constraints is not None:
         if groups > 1:
             raise CapnetError("%s: constraints take one weight group" % who)
-        check(L.capnet_beam_decode_constrained(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
-                                               *constraint_args(constraints, dev)), "capnet_beam_decode_constrained")
+        if has_forced(constraints):
+            check(L.capnet_beam_decode_forced(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
+                                              *constraint_args(constraints, dev), *forced_args(constraints, dev)),
+                  "capnet_beam_decode_forced")
+        else:
+            check(L.capnet_beam_decode_constrained(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
+                                                   *constraint_args(constraints, dev)), "capnet_beam_decode_constrained")
     elif groups > 1:
         check(L.capnet_beam_decode_groups(cell, nl, groups, n_img, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
               "capnet_beam_decode_groups")
@@ -1646,7 +1707,8 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     rows, one capnet_alpha_gather over all n k hypotheses): per image a list of float32 [len - 1, P] tensors beside its list
     of (tokens, score) pairs.
     constraints (a capnet.beam.Constraints; capnet_att_beam_decode_constrained / capnet_att_beam_decode_alphas_constrained, one
-    weight group): every step selects with capnet_beam_advance_constrained; workspaces and results as without.
+    weight group): every step selects with capnet_beam_advance_constrained; workspaces and results as without. With forced
+    words (Constraints(forced=...)): capnet_att_beam_decode_forced, with or without the maps.
     diversity (capnet_att_beam_decode_diverse, one weight group; constraints may come with it): as beam_decode's -- the
     result is n D lists of (tokens, score), one per (image, team), capnet_beam_nbest's at length_penalty 0; with
     return_alphas followed by the maps of every hypothesis in the same nesting.
@@ -1711,6 +1773,10 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     con = () if constraints is None else constraint_args(constraints, dev)
     if return_alphas:
         alphas = (torch.empty((n, T, P), dtype=torch.float32, device=dev), alpha_dims)
+    if has_forced(constraints):     # capnet_att_beam_decode_forced: one entry, the maps nullable
+        check(L.capnet_att_beam_decode_forced(cell, nl, *args, ptr(alphas[0]) if alphas else None, *con,
+                                              *forced_args(constraints, dev)), "capnet_att_beam_decode_forced")
+    elif return_alphas:
         if con:
             check(L.capnet_att_beam_decode_alphas_constrained(cell, nl, *args, ptr(alphas[0]), *con),
                   "capnet_att_beam_decode_alphas_constrained")

@@ -1411,6 +1411,54 @@ int capnet_att_beam_decode_diverse(int cell, int nlayers, int n, int k, int team
                                    capnet_stream_t stream, float* alphas, int no_repeat_ngram, int min_words, const int* banned,
                                    int n_banned);
 
+/* ---- Forced words (capnet.beam.Constraints(forced=...); Post & Vilar 2018, dynamic beam allocation; no
+ * reference counterpart) ----
+ * forced: a DEVICE int32 array of n_forced (1 .. 4) distinct word ids, none of them end_token, that every completed
+ * hypothesis must contain. At step s a live hypothesis is [start, w_1 .. w_{s-1}]; its met mask has bit f set where
+ * forced[f] is among w_1 .. (<start> does not count). The met count of a candidate (row r, word v) is the popcount of
+ * (r's mask | the bits of the forced ids that equal v): its BANK, 0 .. F.
+ *   Exclusions: the constraint arguments' (zeros: none; banned may then be NULL), after the rows' log-sum-exp as ever, and
+ *   <end> on every row whose mask is not full.
+ *   Pool, for an image that selects `live` candidates from `rows` competing rows: (1) the `live` best non-excluded candidates
+ *   by score -- capnet_beam_advance's selection; (2) for every competing row r and every forced id not in r's mask and not
+ *   excluded on r, the candidate (r, that id); (3) every competing row's best non-excluded word. A flat index is in the pool
+ *   once. Scores are (prev - lse) + logit, formed as capnet_beam_advance forms them; nothing is renormalised.
+ *   Allocation: within a bank by score descending, ties to the lower flat index; the banks are visited F, F - 1 .. 0, F ..,
+ *   a visit takes the bank's best untaken candidate if it has one, until `live` are taken. The order of taking is the
+ *   output order: the survivors' slots and the completion order of the hypotheses that end at this step.
+ * Everything behind the selection is capnet_beam_advance's. THE LOGITS BLOCK IS MODIFIED.
+ *   capnet_beam_advance_forced: one workgroup per image; trace: NULL, or the row trace as capnet_beam_advance_traced
+ *     records it. */
+int capnet_beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                               long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                               const int* forced, int n_forced, long long* next_words, long long* parent_rows,
+                               capnet_stream_t stream);
+/* The host loops' form: capnet_beam_topk_batched (meta [n][3] = (first row, rows that compete, live), outputs [n][16]) with
+ * bans NULL or capnet_beam_topk_batched_banned's lists, a row per logits row -- the caller's lists hold <end> for a row
+ * that lacks a forced id or not, the kernel excludes it either way -- and met, a DEVICE int32 per logits row: the row's
+ * mask. Where the pool holds fewer than `live` candidates the remaining entries are -inf / -1. */
+int capnet_beam_topk_batched_forced(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                    const int* bans, int cap, const int* met, const int* forced, int n_forced,
+                                    long long end_token, float* top_scores, long long* top_index, capnet_stream_t stream);
+/* capnet_beam_decode_constrained with every step's selection capnet_beam_advance_forced; workspace and results as there. */
+int capnet_beam_decode_forced(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                              long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                              const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                              size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                              capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                              const int* forced, int n_forced);
+/* capnet_att_beam_decode_constrained (alphas NULL; workspace capnet_att_beam_decode_ws_bytes) or
+ * capnet_att_beam_decode_alphas_constrained (alphas [n][max_steps][P]; workspace capnet_att_beam_decode_alphas_ws_bytes with
+ * groups = 1) with every step's selection capnet_beam_advance_forced, the trace passed through. */
+int capnet_att_beam_decode_forced(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                  long long start_token, long long end_token, const float* att1, const float* feat,
+                                  const float* emb, const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                                  long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                  float* alphas, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                  const int* forced, int n_forced);
+
 #ifdef __cplusplus
 }
 #endif
