@@ -255,6 +255,25 @@ def _bans(rows_tokens, step, end_token, constraints, device):
     return torch.tensor([[len(b)] + b + [0] * (cap - len(b)) for b in lists], dtype=torch.int32, device=device)
 
 
+def _select(logits, scores, meta, rows_tokens, step, end_token, constraints, diversity, device):
+    """One step's selection for the host loops, which hold the hypotheses: every logits row's ban list where there are
+    constraints (removed after the log-sum-exp), every row's met mask where they force words, then ONE call.
+    meta: [(first row, competing rows, k)] per image -- per (image, group) with diversity -- for capnet_beam_topk_batched and
+    its _banned / _diverse / _forced forms -> (scores [n, 16], flat [n, 16]). A single such tuple: beam_search's one image ->
+    (scores [k], flat [k]) from capnet_beam_topk[_banned], the single-image kernel, or under forced words from
+    capnet_beam_topk_batched_forced with n = 1. rows_tokens: the token lists of the logits rows (None without constraints)."""
+    forced = constraints is not None and bool(constraints.forced) and diversity is None
+    if isinstance(meta, tuple) and not forced:
+        _, rows, k = meta
+        bans = None if constraints is None else _bans(rows_tokens[:rows], step, end_token, constraints, device)
+        return ops.beam_topk(logits, scores, rows, k, bans=bans)
+    meta_d = torch.tensor([meta] if isinstance(meta, tuple) else meta, dtype=torch.int32, device=device)
+    bans = None if constraints is None else _bans(rows_tokens, step, end_token, constraints, device)
+    met = (constraints, _met(rows_tokens, constraints, device), end_token) if forced else None
+    scores_d, flat_d = ops.beam_topk_batched(logits, scores, meta_d, bans=bans, diversity=diversity, forced=met)
+    return (scores_d[0, :meta[2]], flat_d[0, :meta[2]]) if isinstance(meta, tuple) else (scores_d, flat_d)
+
+
 def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_length, device, nbest=False, length_penalty=0.0,
                 constraints=None):
     """step_fn(prev_words LongTensor[s], state) -> (logits [s, V], state'); `state` is a tuple of
@@ -271,17 +290,7 @@ def beam_search(step_fn, state, vocab_size, start_token, end_token, k, max_seq_l
         logits, state = step_fn(k_prev_words, state)
         # first step: all k beams are identical, only row 0 competes (model.py:240-242)
         rows = 1 if step == 1 else logits.shape[0]
-        if constraints is None:
-            scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k)
-        elif constraints.forced:    # forced words: capnet_beam_topk_batched_forced with n = 1, the rows' met masks beside their lists
-            meta_d = torch.tensor([[0, rows, k]], dtype=torch.int32, device=device)
-            scores_d, flat_d = ops.beam_topk_batched(logits, top_k_scores, meta_d,
-                                                     bans=_bans(seqs, step, end_token, constraints, device),
-                                                     forced=(constraints, _met(seqs, constraints, device), end_token))
-            scores_d, flat_d = scores_d[0, :k], flat_d[0, :k]
-        else:       # the hypotheses are held here: every competing row's list, removed after the log-sum-exp
-            scores_d, flat_d = ops.beam_topk(logits, top_k_scores, rows, k,
-                                             bans=_bans(seqs[:rows], step, end_token, constraints, device))
+        scores_d, flat_d = _select(logits, top_k_scores, (0, rows, k), seqs, step, end_token, constraints, None, device)
         scores = scores_d.tolist()
         flat = flat_d.tolist()
         prev_word_inds = [f // vocab_size for f in flat]
@@ -341,12 +350,9 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
         if logits.shape[1] != vocab_size:
             raise ops.CapnetError("beam_search_device: the step returned %d columns, vocab_size is %d" % (logits.shape[1], vocab_size))
         next_words = words[step & 1]
-        if diversity is not None:       # one workgroup per image walks its groups in order
-            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints, diversity=diversity)
-        elif constraints is None:
-            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows)
-        else:       # the sequences stay in the beam state: the selecting workgroup derives the exclusions from them
-            ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints)
+        # (the sequences stay in the beam state: the selecting workgroup derives the exclusions from them, and with diversity
+        # walks the image's groups in order)
+        ops.beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints, diversity=diversity)
         if poll_every > 0 and step % poll_every == 0 and step < T and not int(beam.live_total.item()):
             break
         state = tuple(s.index_select(0, parent_rows) for s in state)
@@ -393,22 +399,8 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
         for i in range(n):
             meta.append((row0, (1 if step == 1 else live[i]) if live[i] else 0, live[i]))
             row0 += live[i]
-        meta_d = torch.tensor(meta, dtype=torch.int32, device=device)
-        if diversity is not None:
-            bans = None if constraints is None else \
-                _bans([q for i in range(n) for q in seqs[i]], step, end_token, constraints, device)
-            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d, bans=bans, diversity=diversity)
-        elif constraints is None:
-            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d)
-        elif constraints.forced:    # forced words: every row's met mask beside its list
-            live_seqs = [q for i in range(n) for q in seqs[i]]
-            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d,
-                                                     bans=_bans(live_seqs, step, end_token, constraints, device),
-                                                     forced=(constraints, _met(live_seqs, constraints, device), end_token))
-        else:       # a list for every row of the logits: image i's live beams in order
-            live_seqs = [q for i in range(n) for q in seqs[i]]
-            scores_d, flat_d = ops.beam_topk_batched(logits, top_scores, meta_d,
-                                                     bans=_bans(live_seqs, step, end_token, constraints, device))
+        live_seqs = None if constraints is None else [q for i in range(n) for q in seqs[i]]     # image i's live beams in order
+        scores_d, flat_d = _select(logits, top_scores, meta, live_seqs, step, end_token, constraints, diversity, device)
         scores, flat = scores_d.tolist(), flat_d.tolist()
         keep_rows, next_words, next_scores = [], [], []
         for i in range(n):

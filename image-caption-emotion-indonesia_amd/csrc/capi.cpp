@@ -552,26 +552,51 @@ size_t capnet_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int 
   return beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps);
 }
 
+// the teams of a diverse one-call search (capnet_beam_decode_diverse, capnet_att_beam_decode_diverse): beam_teams_check, and
+// the state of n teams searches of k / teams beams must exist
+static int decode_teams_check(const char* who, int n, int k, const BeamTeams& t, int max_steps) {
+  if (int rc = beam_teams_check(who, k, t.teams, t.strength)) return rc;
+  CAPNET_REQUIRE(n >= 1 && (long)n * t.teams < (1L << 24) && beam_state_bytes(n * t.teams, k / t.teams, max_steps), "%s: n=%d teams=%d",
+                 who, n, t.teams);
+  return kOk;
+}
+
+// every capnet_beam_decode* entry: stack_decode_check, then the checks of what is given. n: the images of one group
+static int beam_decode_entry(const char* who, int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                             long long start_token, long long end_token, const float* emb, const float* const* wcat,
+                             const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
+                             float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
+                             int* err_flag, capnet_stream_t stream, const BeamConstraints* con = nullptr,
+                             const BeamTeams* teams = nullptr) {
+  if (int rc = stack_decode_check(who, cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, poll_every, 0, 1, &emb, wcat, beff,
+                                  &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
+    return rc;
+  if (teams)
+    if (int rc = decode_teams_check(who, groups * n, k, *teams, max_steps)) return rc;
+  if (con)
+    if (int rc = beam_constraints_check(who, *con)) return rc;
+  if (con && con->n_forced)
+    if (int rc = beam_forced_check(who, *con)) return rc;
+  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
+                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups, con, teams);
+}
+
 int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                        long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
                        const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
                        size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                        capnet_stream_t stream) {
-  return capnet_beam_decode_groups(cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
-                                   state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream);
+  return beam_decode_entry("beam_decode", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
+                           state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream);
 }
 
-// n below: the beam groups, groups x images
 int capnet_beam_decode_groups(int cell, int nlayers, int groups, int n_images, int k, int E, int H, int V, int max_steps,
                               long long start_token, long long end_token, const float* emb, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                               float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
                               int* err_flag, capnet_stream_t stream) {
-  if (int rc = stack_decode_check("beam_decode", cell, nlayers, groups, n_images, k, E, H, V, max_steps, start_token, poll_every, 0,
-                                  1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
-    return rc;
-  return beam_decode(cell, nlayers, n_images, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0,
-                     workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), groups);
+  return beam_decode_entry("beam_decode", cell, nlayers, groups, n_images, k, E, H, V, max_steps, start_token, end_token, emb, wcat,
+                           beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream);
 }
 
 int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
@@ -580,13 +605,10 @@ int capnet_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, i
                                    size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
                                    int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
                                    int n_banned) {
-  if (int rc = stack_decode_check("beam_decode_constrained", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0,
-                                  1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
-    return rc;
   const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
-  if (int rc = beam_constraints_check("beam_decode_constrained", con)) return rc;
-  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
-                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
+  return beam_decode_entry("beam_decode_constrained", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat,
+                           beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream,
+                           &con);
 }
 
 int capnet_beam_decode_forced(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
@@ -595,23 +617,10 @@ int capnet_beam_decode_forced(int cell, int nlayers, int n, int k, int E, int H,
                               size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
                               capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
                               const int* forced, int n_forced) {
-  if (int rc = stack_decode_check("beam_decode_forced", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0, 1,
-                                  &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
-    return rc;
   const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
-  if (int rc = beam_constraints_check("beam_decode_forced", con)) return rc;
-  if (int rc = beam_forced_check("beam_decode_forced", con)) return rc;
-  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
-                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con);
-}
-
-// the teams of a diverse one-call search (capnet_beam_decode_diverse, capnet_att_beam_decode_diverse)
-static int beam_teams_check(const char* who, int n, int k, int teams, float strength, int max_steps) {
-  CAPNET_REQUIRE(teams >= 1 && teams <= 16 && k >= teams && k % teams == 0, "%s: teams=%d must divide k=%d (1 .. 16)", who, teams, k);
-  CAPNET_REQUIRE(strength >= 0.f && strength <= 3.0e38f, "%s: strength must be finite and >= 0", who);
-  CAPNET_REQUIRE(n >= 1 && (long)n * teams < (1L << 24) && beam_state_bytes(n * teams, k / teams, max_steps), "%s: n=%d teams=%d", who, n,
-                 teams);
-  return kOk;
+  if (int rc = beam_forced_check("beam_decode_forced", con)) return rc;   // (n_forced == 0 would be the constrained search)
+  return beam_decode_entry("beam_decode_forced", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff,
+                           Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream, &con);
 }
 
 int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int E, int H, int V, int max_steps,
@@ -620,15 +629,11 @@ int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, f
                                float* slab, size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run,
                                int* err_flag, capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
                                int n_banned) {
-  if (int rc = stack_decode_check("beam_decode_diverse", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every, 0, 1,
-                                  &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths, err_flag))
-    return rc;
-  if (int rc = beam_teams_check("beam_decode_diverse", n, k, teams, strength, max_steps)) return rc;
   const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
-  if (int rc = beam_constraints_check("beam_decode_diverse", con)) return rc;
   const BeamTeams dv{teams, strength, nullptr};
-  return beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace,
-                     slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, S(stream), 1, &con, &dv);
+  return beam_decode_entry("beam_decode_diverse", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff,
+                           Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream, &con,
+                           &dv);
 }
 
 size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
@@ -1081,7 +1086,7 @@ static int att_beam_decode_entry(int cell, int nlayers, int groups, int n, int k
   if (con)
     if (int rc = beam_constraints_check("att_beam_decode", *con)) return rc;
   if (teams)
-    if (int rc = beam_teams_check("att_beam_decode_diverse", groups * n, k, teams->teams, teams->strength, max_steps)) return rc;
+    if (int rc = decode_teams_check("att_beam_decode_diverse", groups * n, k, *teams, max_steps)) return rc;
   return att_beam_decode(cell, nlayers, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz, w_full,
                          b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run,
                          err_flag, S(stream), groups, alphas, con, teams);
@@ -1399,7 +1404,9 @@ size_t capnet_att_bwd_scratch_floats(const int* dims) { return att_bwd_scratch_f
 
 int capnet_beam_topk_batched(const float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
                              float* top_scores, long long* top_index, capnet_stream_t stream) {
-  return beam_topk_batched(logits, ld, V, prev_scores, meta, n, top_scores, top_index, S(stream));
+  // (no option given: the plain kernel, which only reads the logits)
+  return beam_topk_batched("beam_topk_batched", const_cast<float*>(logits), ld, V, prev_scores, meta, n, nullptr, 0, nullptr, nullptr,
+                           nullptr, 0, 0, top_scores, top_index, S(stream));
 }
 int capnet_beam_topk(const float* logits, long ld, int rows, int V, const float* prev_scores, int k,
                      float* top_scores, long long* top_index, capnet_stream_t stream) {
@@ -1411,7 +1418,9 @@ int capnet_beam_topk_banned(float* logits, long ld, int rows, int V, const float
 }
 int capnet_beam_topk_batched_banned(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
                                     const int* bans, int cap, float* top_scores, long long* top_index, capnet_stream_t stream) {
-  return beam_topk_batched_banned(logits, ld, V, prev_scores, meta, n, bans, cap, top_scores, top_index, S(stream));
+  CAPNET_REQUIRE(bans, "beam_topk_batched_banned: bad argument");
+  return beam_topk_batched("beam_topk_batched_banned", logits, ld, V, prev_scores, meta, n, bans, cap, nullptr, nullptr, nullptr, 0,
+                           0, top_scores, top_index, S(stream));
 }
 size_t capnet_beam_state_bytes(int n, int k, int max_steps) { return beam_state_bytes(n, k, max_steps); }
 int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words,
@@ -1420,7 +1429,9 @@ int capnet_beam_init(void* beam, int n, int k, int max_steps, long long start_to
 }
 int capnet_beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step,
                         long long end_token, long long* next_words, long long* parent_rows, capnet_stream_t stream) {
-  return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream));
+  // (no option given: the plain kernel, which only reads the logits)
+  return beam_advance("beam_advance", beam, const_cast<float*>(logits), ld, V, n, k, max_steps, step, end_token, nullptr, nullptr,
+                      next_words, parent_rows, nullptr, S(stream));
 }
 int capnet_beam_advance_topk(void* beam, const float* values, const int* index, const float* lse, int V, int n, int k,
                              int max_steps, int step, long long end_token, long long* next_words, long long* parent_rows,
@@ -1437,13 +1448,15 @@ int capnet_beam_advance_traced(void* beam, void* trace, const float* logits, lon
                                capnet_stream_t stream) {
   CAPNET_REQUIRE(trace != nullptr, "beam_advance_traced: null trace");
   CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0, "beam_advance_traced: the state and the trace must be 4-byte aligned");
-  return beam_advance(beam, logits, ld, V, n, k, max_steps, step, end_token, next_words, parent_rows, S(stream), trace);
+  return beam_advance("beam_advance_traced", beam, const_cast<float*>(logits), ld, V, n, k, max_steps, step, end_token, nullptr,
+                      nullptr, next_words, parent_rows, trace, S(stream));
 }
 int capnet_beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
                                     long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
                                     long long* next_words, long long* parent_rows, capnet_stream_t stream) {
-  return beam_advance_constrained(beam, logits, ld, V, n, k, max_steps, step, end_token,
-                                  BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream));
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  return beam_advance("beam_advance_constrained", beam, logits, ld, V, n, k, max_steps, step, end_token, &con, nullptr, next_words,
+                      parent_rows, nullptr, S(stream));
 }
 int capnet_beam_advance_constrained_traced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps,
                                            int step, long long end_token, int no_repeat_ngram, int min_words, const int* banned,
@@ -1451,36 +1464,41 @@ int capnet_beam_advance_constrained_traced(void* beam, void* trace, float* logit
   CAPNET_REQUIRE(trace != nullptr, "beam_advance_constrained_traced: null trace");
   CAPNET_REQUIRE((size_t)beam % 4 == 0 && (size_t)trace % 4 == 0,
                  "beam_advance_constrained_traced: the state and the trace must be 4-byte aligned");
-  return beam_advance_constrained(beam, logits, ld, V, n, k, max_steps, step, end_token,
-                                  BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream),
-                                  trace);
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  return beam_advance("beam_advance_constrained_traced", beam, logits, ld, V, n, k, max_steps, step, end_token, &con, nullptr,
+                      next_words, parent_rows, trace, S(stream));
 }
 int capnet_beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int teams, float strength,
                                 int max_steps, int step, long long end_token, int no_repeat_ngram, int min_words,
                                 const int* banned, int n_banned, long long* next_words, long long* parent_rows,
                                 capnet_stream_t stream) {
-  return beam_advance_diverse(beam, trace, logits, ld, V, n, k, teams, strength, max_steps, step, end_token,
-                              BeamConstraints{no_repeat_ngram, min_words, banned, n_banned}, next_words, parent_rows, S(stream));
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  const BeamTeams dv{teams, strength, nullptr};
+  return beam_advance("beam_advance_diverse", beam, logits, ld, V, n, k, max_steps, step, end_token, &con, &dv, next_words,
+                      parent_rows, trace, S(stream));
 }
 int capnet_beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n, int teams,
                                      float strength, const int* bans, int cap, float* top_scores, long long* top_index,
                                      capnet_stream_t stream) {
-  return beam_topk_batched_diverse(logits, ld, V, prev_scores, meta, n, teams, strength, bans, cap, top_scores, top_index,
-                                   S(stream));
+  const BeamTeams dv{teams, strength, nullptr};
+  return beam_topk_batched("beam_topk_batched_diverse", logits, ld, V, prev_scores, meta, n, bans, cap, &dv, nullptr, nullptr, 0, 0,
+                           top_scores, top_index, S(stream));
 }
 int capnet_beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
                                long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
                                const int* forced, int n_forced, long long* next_words, long long* parent_rows,
                                capnet_stream_t stream) {
-  return beam_advance_forced(beam, trace, logits, ld, V, n, k, max_steps, step, end_token,
-                             BeamConstraints{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced}, next_words,
-                             parent_rows, S(stream));
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
+  if (int rc = beam_forced_check("beam_advance_forced", con)) return rc;   // (n_forced == 0 would be the constrained step)
+  return beam_advance("beam_advance_forced", beam, logits, ld, V, n, k, max_steps, step, end_token, &con, nullptr, next_words,
+                      parent_rows, trace, S(stream));
 }
 int capnet_beam_topk_batched_forced(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
                                     const int* bans, int cap, const int* met, const int* forced, int n_forced,
                                     long long end_token, float* top_scores, long long* top_index, capnet_stream_t stream) {
-  return beam_topk_batched_forced(logits, ld, V, prev_scores, meta, n, bans, cap, met, forced, n_forced, end_token, top_scores,
-                                  top_index, S(stream));
+  if (int rc = beam_forced_check("beam_topk_batched_forced", BeamConstraints{0, 0, nullptr, 0, forced, n_forced})) return rc;
+  return beam_topk_batched("beam_topk_batched_forced", logits, ld, V, prev_scores, meta, n, bans, cap, nullptr, met, forced, n_forced,
+                           end_token, top_scores, top_index, S(stream));
 }
 int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
                               long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {

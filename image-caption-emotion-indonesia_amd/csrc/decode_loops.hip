@@ -5,7 +5,7 @@
 //                forms)
 //   beam loops:  beam_decode, lstm_beam_decode, lstm_beam_decode_groups, att_beam_decode
 // The kernels they launch: lstm_decode_step.hip, att_kernels.hip, vocab_argmax.hip, vocab_topk.hip, vocab_sample.hip,
-// vocab_nucleus.hip, seq_kernels.hip (beam_advance), gemm_f32.hip.
+// vocab_nucleus.hip, beam_search.hip (beam_advance), gemm_f32.hip.
 #include "common.h"
 #include "kernels.h"
 
@@ -283,7 +283,6 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
                          reinterpret_cast<long long*>(p + w.words + (w.parent - w.words) / 2)};
   long long* parent = reinterpret_cast<long long*>(p + w.parent);
   void* beam = dv ? dv->beam : p + w.beam;
-  const BeamConstraints none{0, 0, nullptr, 0};
   const int* live_total = nullptr;
   if (int rc = beam_live(beam, sn, sk, max_steps, &live_total, nullptr, nullptr)) return rc;
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
@@ -305,14 +304,8 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
         rc = sgemm_splitk(false, true, rpg, V, H, h_top + (size_t)g * rpg * H, H, Cwg[g], H, logits + (size_t)g * rpg * V, V,
                           Cbg ? Cbg[g] : nullptr, 0, slab, slab_floats, s);
       if (rc == kOk && !Cwg) rc = sgemm_splitk(false, true, nk, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
-      if (rc == kOk && dv)
-        rc = beam_advance_diverse(beam, trace, logits, V, V, n, k, dv->teams, dv->strength, max_steps, step, end_token,
-                                  con ? *con : none, words[step & 1], parent, s);
-      else if (rc == kOk && con && con->n_forced)   // (forced words: the selection swapped, all else as it is)
-        rc = beam_advance_forced(beam, trace, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s);
-      else if (rc == kOk)
-        rc = con ? beam_advance_constrained(beam, logits, V, V, n, k, max_steps, step, end_token, *con, words[step & 1], parent, s, trace)
-                 : beam_advance(beam, logits, V, V, n, k, max_steps, step, end_token, words[step & 1], parent, s, trace);
+      if (rc == kOk)   // (the kernel by what is given: teams, forced words, constraints, none)
+        rc = beam_advance("beam_advance", beam, logits, V, V, n, k, max_steps, step, end_token, con, dv, words[step & 1], parent, trace, s);
     }
     if (rc != kOk) return rc;
     issued = step;

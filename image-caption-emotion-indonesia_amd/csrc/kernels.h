@@ -213,15 +213,15 @@ int lstm_pointwise_bwd(const float* gates, long ldg, const float* c, const float
 int gather_prev_rows(const float* src, const int* idx, const float* first, const int* sample,
                      float* out, int rows, int C, hipStream_t stream);
 int argmax_rows(const float* x, int rows, int ld, int V, int* out, hipStream_t stream);
-int beam_topk_batched(const float* logits, long ld, int V, const float* prev, const int* meta, int n, float* out_scores,
-                      long long* out_index, hipStream_t stream);
+// ---- beam_search.hip: the selection step of beam search
 int beam_topk(const float* logits, long ld, int rows, int V, const float* prev, int k,
               float* out_scores, long long* out_index, hipStream_t stream);
+// (bans int32 [rows][1 + cap] on the device, per logits row its count and that many words)
+int beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev, int k, const int* bans, int cap,
+                     float* out_scores, long long* out_index, hipStream_t stream);
 // beam search with device-side bookkeeping (fixed slots: image i's beams at rows i k .. i k + k - 1 throughout)
 size_t beam_state_bytes(int n, int k, int max_steps);
 int beam_init(void* beam, int n, int k, int max_steps, long long start_token, long long* prev_words, hipStream_t stream);
-int beam_advance(void* beam, const float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
-                 long long* next_words, long long* parent_rows, hipStream_t stream, void* trace = nullptr);
 // constrained search: what a step must not select -- no g-gram twice in a hypothesis (0: off, at most 4), no
 // <end> at steps 1 .. min_words, none of the n_banned (<= 32) words of the DEVICE array banned. The excluded words are
 // overwritten with -inf in the logits block AFTER the rows' log-sum-exp: the block is modified, the scores are not.
@@ -230,46 +230,35 @@ struct BeamConstraints {
   const int* banned;
   int n_banned;
   // forced words: n_forced (<= 4) distinct ids of the DEVICE array forced that every completed hypothesis must
-  // contain; 0: none. Only beam_advance_forced and the one-call loops read them.
+  // contain; 0: none. <end> is excluded on a row that lacks a forced id, and the `live` candidates are dealt out of a pool (the
+  // plain selection, every row's missing forced ids, every row's best word) across banks by met count, F, F - 1 .. 0, F ..;
+  // the scores are the plain ones.
   const int* forced = nullptr;
   int n_forced = 0;
 };
-int beam_constraints_check(const char* who, const BeamConstraints& c);
-int beam_advance_constrained(void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
-                             long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
-                             hipStream_t stream, void* trace = nullptr);
-// (the host routes' form: bans int32 [rows][1 + cap] on the device, per logits row its count and that many words)
-int beam_topk_banned(float* logits, long ld, int rows, int V, const float* prev, int k, const int* bans, int cap,
-                     float* out_scores, long long* out_index, hipStream_t stream);
-int beam_topk_batched_banned(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
-                             float* out_scores, long long* out_index, hipStream_t stream);
-// diverse search: n images x k beams as D teams of k / D; `beam` (and `trace`, nullable) are those of n D
-// searches of k / D beams. Team g of an image selects after teams 0 .. g - 1 by score - strength * (candidates they chose
-// at this step with the same word); the scores written are unpenalised. c: zeros mean no constraint. The logits block is
-// modified. beam_topk_batched_diverse: the host loops' form, meta [n D][3] per (image, team), bans nullable.
-int beam_advance_diverse(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int D, float strength,
-                         int max_steps, int step, long long end_token, const BeamConstraints& c, long long* next_words,
-                         long long* parent_rows, hipStream_t stream);
-// (the one-call searches: beam -- the block that holds the state of n teams searches of k / teams beams)
+// diverse search: n images x k beams as `teams` teams of k / teams. Team g of an image selects after teams
+// 0 .. g - 1 by score - strength * (candidates they chose at this step with the same word); the scores written are
+// unpenalised. (beam: the one-call searches' -- the block that holds the state of n teams searches of k / teams beams)
 struct BeamTeams {
   int teams;
   float strength;
   void* beam;
 };
-int beam_topk_batched_diverse(float* logits, long ld, int V, const float* prev, const int* meta, int n, int D, float strength,
-                              const int* bans, int cap, float* out_scores, long long* out_index, hipStream_t stream);
-// forced words: beam_advance_constrained with c.forced -- <end> is excluded on a row that lacks a forced id, and
-// the `live` candidates are dealt out of a pool (the plain selection, every row's missing forced ids, every row's best word)
-// across banks by met count, F, F - 1 .. 0, F ..; the scores are the plain ones. trace nullable. The logits block is modified.
-// beam_topk_batched_forced: the host loops' form, meta as beam_topk_batched's, bans nullable, met int32 per logits row
-// (bit f: forced[f] is among the row's words).
-int beam_forced_check(const char* who, const BeamConstraints& c);
-int beam_advance_forced(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
-                        long long end_token, const BeamConstraints& c, long long* next_words, long long* parent_rows,
-                        hipStream_t stream);
-int beam_topk_batched_forced(float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans, int cap,
-                             const int* met, const int* forced, int n_forced, long long end_token, float* out_scores,
-                             long long* out_index, hipStream_t stream);
+int beam_constraints_check(const char* who, const BeamConstraints& c);
+int beam_forced_check(const char* who, const BeamConstraints& c);                  // (refuses n_forced == 0)
+int beam_teams_check(const char* who, int k, int teams, float strength);          // (the only check of either range)
+// One step on the device state, and the same selection in the host loops' form. con / bans, teams, forced ids and trace are
+// each nullable (0), and WHICH are given chooses the kernel: teams -> diverse (its constraints and ban lists optional);
+// else forced ids -> forced; else con / bans -> constrained; else plain, which leaves the logits block as it is (every
+// other kernel modifies it). With teams, beam and trace are those of n teams searches of k / teams beams and meta is
+// [n teams][3] per (image, team). who: the caller's name, in front of every message.
+int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                 long long end_token, const BeamConstraints* con, const BeamTeams* teams, long long* next_words,
+                 long long* parent_rows, void* trace, hipStream_t stream);
+// (met int32 per logits row, bit f: forced[f] is among the row's words)
+int beam_topk_batched(const char* who, float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans,
+                      int cap, const BeamTeams* teams, const int* met, const int* forced, int n_forced, long long end_token,
+                      float* out_scores, long long* out_index, hipStream_t stream);
 // (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
 // done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
 // winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)
@@ -285,6 +274,7 @@ int beam_finish(const void* beam, int n, int k, int max_steps, long long end_tok
 int beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
                float* scores, int* counts, hipStream_t stream, const void* trace = nullptr, int* rows = nullptr);
 int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
+// ---- seq_kernels.hip again
 int gather_rows(const float* src, const int* idx, float* out, int rows, int C, hipStream_t stream);
 int colsum(const float* x, long ld, int rows, int C, float* out, int accumulate, hipStream_t stream,
            float* ws = nullptr, size_t ws_floats = 0);
@@ -377,12 +367,12 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
                 const float* Cb, const float* state0, void* ws, float* slab, size_t slab_floats, int poll_every,
                 long long* seqs, int* lengths, int* steps_run, int* err_flag, hipStream_t s, int groups = 1,
                 const BeamConstraints* con = nullptr, const BeamTeams* teams = nullptr);
-// (teams, here and in att_beam_decode: the diverse search -- every step's selection is beam_advance_diverse on a state of
+// (teams, here and in att_beam_decode: the diverse search -- every step's selection is beam_advance's diverse form on a state of
 // n teams searches of k / teams beams, which lies BEHIND the workspace described here (beam_state_bytes(n teams, k / teams,
 // max_steps) more bytes; teams->beam is ignored); seqs / lengths then hold n teams winners, one per (image, team))
 // (groups: the search over groups x n beam groups, group g on its own weights; ws, seqs, lengths at groups x n)
-// (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance_constrained, or
-// beam_advance_forced where con->n_forced > 0 and there are no teams)
+// (con, here and in att_beam_decode: the constrained search -- every step's selection is beam_advance's constrained form, or
+// its forced form where con->n_forced > 0 and there are no teams)
 // vocab_topk.hip: per row the k best of h[r] . W[v] + b[v] (logit descending, index ascending; fewer pickable entries: the
 // tail is (-inf, -1)) and log sum_v exp, one launch, no logits in memory (ws: vocab_topk_ws_bytes, its first 16 bytes zero
 // before the first use)

@@ -10,8 +10,9 @@ mode selects, the layout of their beam state, their weight fold.
     ops.beam_decode; (2) one_call and an AttStack: ops.att_beam_decode (_one_call_att); (3) on_device, or one_call with
     neither: capnet.beam.beam_search_device; (4) the host loops beam_search / beam_search_batched. nbest and length_penalty
     go to whichever route runs; _beam_result then shapes what it gave (one image: tensors; maps attached) for all four.
-    diversity (an active capnet.beam.Diversity): the same ladder in _diverse_decode -- the one-call entries' _diverse forms,
-    beam_search_device, or beam_search_batched for one image too -- and capnet.beam.merge_groups shapes the groups' lists.
+    diversity (an active capnet.beam.Diversity): the same ladder -- the one-call entries' _diverse forms, beam_search_device,
+    or beam_search_batched for one image too; the loops merge their groups' lists themselves (capnet.beam.merge_groups),
+    the one-call searches' raw lists are merged in _beam_result.
     return_alphas: the attention maps that preceded every word of the captions -- recorded by the one-call search
     (ops.att_beam_decode(return_alphas=True): a history of every step's maps, the winners' rows traced through the
     re-slotting, one gather), in chunks of images that keep the history under ALPHA_TRACE_MAX_BYTES; on every other route
@@ -167,8 +168,8 @@ def _nbest_replay(step_fn, state, lists, k):
 
 
 def _one_image(lists, dev):
-    """An n-best list of token lists as sample() returns it: LongTensor [1, L] per entry."""
-    return [(torch.tensor([q], dtype=torch.long, device=dev), sc) for q, sc in lists]
+    """An n-best list of token lists as sample() returns it: LongTensor [1, L] per entry (None stays None)."""
+    return [None if p is None else (torch.tensor([p[0]], dtype=torch.long, device=dev), p[1]) for p in lists]
 
 
 def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=False, poll_every=0, one_call=False,
@@ -234,95 +235,64 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
                 raise ops.CapnetError("constraints: forced words do not go with an active diversity (DESIGN 7)")
             if diversity.per_group and not nbest:
                 raise ops.CapnetError("diversity: per_group=True needs nbest=True (one (tokens, score) per group)")
-            return _diverse_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call,
-                                   return_alphas, nbest, length_penalty, nb.get("constraints"), diversity)
+            nb.update(nbest=nbest, length_penalty=length_penalty, diversity=diversity)
+    teams = nb.get("diversity")                 # the active Diversity, or None
     plain = getattr(step_fn, "plain", None) if one_call else None
     att = getattr(step_fn, "att", None) if one_call else None
-    maps = one = None
+    maps = one = raw = None
     with torch.no_grad():
         if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, V, len(plain.wcat)):
             lists = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T + 1, start_token,
                                     end_token, poll_every, **nb)
+            raw = teams
         elif att is not None:
             lists = _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, **nb)
             if return_alphas:
                 lists, maps = lists
+            raw = teams
         elif on_device or one_call:
             lists = beam_search_device(step_fn, state, n_img, V, start_token, end_token, k, T, dev, poll_every, **nb)
-        elif n is not None:
-            lists = beam_search_batched(step_fn, state, n, V, start_token, end_token, k, T, dev, **nb)
+        elif n is not None or teams is not None:        # (one image in teams: the batched loop's n = 1 case)
+            lists = beam_search_batched(step_fn, state, n_img, V, start_token, end_token, k, T, dev, **nb)
         elif nbest:
             lists = [[(q[0].tolist(), sc) for q, sc in beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)]]
         else:
             one = beam_search(step_fn, state, V, start_token, end_token, k, T, dev, **nb)     # LongTensor [1, L] as it is returned
             lists = [one[0].tolist()] if return_alphas else None
-    return _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest)
+    return _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest,
+                        None if raw is None else (raw, end_token, length_penalty))
 
 
-def _diverse_decode(dec, step_fn, state, n, k, start_token, end_token, on_device, poll_every, one_call, return_alphas, nbest,
-                    length_penalty, constraints, diversity):
-    """beam_decode under an active Diversity, by beam_decode's own ladder: (1) / (2) one_call on a PlainStack / AttStack of a
-    supported shape: ops.beam_decode / ops.att_beam_decode with diversity=, whose per-(image, group) lists are merged here
-    (capnet.beam.merge_groups; the one-call attention search records the maps of every hypothesis); (3) on_device, or
-    one_call with neither: beam_search_device; (4) beam_search_batched (one image: n = 1). Then the result shaped as
-    beam_decode shapes it. per_group: an entry may be None, and so are its maps; off the one-call attention route the maps
-    come from replay_alphas."""
-    dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
-    D = diversity.groups
-    kw = dict(nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
-    con = {} if constraints is None else {"constraints": constraints}
-    plain = getattr(step_fn, "plain", None) if one_call else None
-    att = getattr(step_fn, "att", None) if one_call else None
-    maps = per = per_maps = None
-    with torch.no_grad():
-        if plain is not None and ops.beam_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], k, V, len(plain.wcat)):
-            per = ops.beam_decode(plain.cell, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb, n_img, k, T + 1, start_token,
-                                  end_token, poll_every, diversity=diversity, **con)
-        elif att is not None:
-            per = _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return_alphas, diversity=diversity, **con)
-            if return_alphas:
-                per, per_maps = per
-        elif on_device or one_call:
-            lists = beam_search_device(step_fn, state, n_img, V, start_token, end_token, k, T, dev, poll_every, **kw)
-        else:
-            lists = beam_search_batched(step_fn, state, n_img, V, start_token, end_token, k, T, dev, **kw)
-    if per is not None:
+def _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest, raw=None):
+    """What beam_decode returns, from what its route gave. lists: per image its token list, or with nbest its list of
+    (tokens, score) pairs, an entry None where a group of a per_group search completed nothing (its maps are None too);
+    maps: the one-call search's recording in the same nesting, else None: with return_alphas they come from replay_alphas /
+    _nbest_replay; one: the host loop's tensor of one image, returned as it is. n None: the one image's entry, the tokens as
+    LongTensor [1, L].
+    raw = (diversity, end_token, length_penalty), the one-call diverse searches: lists holds per (image, group) its
+    capnet_beam_nbest list at penalty 0 (and maps the recorded maps of every hypothesis) -> capnet.beam.merge_groups per
+    image, and the recorded maps of what the merge kept, looked up by tokens: the first group that has them."""
+    dev = state[0].device
+    if raw is not None:
+        diversity, end_token, length_penalty = raw
+        D, per, per_maps = diversity.groups, lists, maps
         lists = [merge_groups([by_completion(per[i * D + g]) for g in range(D)], end_token, diversity, nbest, length_penalty)
-                 for i in range(n_img)]
-        if per_maps is not None:        # the recorded maps of what the merge kept: by its tokens, the first group that has them
+                 for i in range(len(per) // D)]
+        if per_maps is not None:
             def recorded(i, tokens):
                 for g in range(D):
                     for (q, _), m in zip(per[i * D + g], per_maps[i * D + g]):
                         if q == tokens:
                             return m
-                return torch.zeros((0, att.feat.shape[1]), dtype=torch.float32, device=dev)       # [<end>]: nothing completed
+                return torch.zeros((0, step_fn.att.feat.shape[1]), dtype=torch.float32, device=dev)   # [<end>]: nothing completed
             maps = [[None if p is None else recorded(i, p[0]) for p in hyps] if nbest else recorded(i, hyps)
                     for i, hyps in enumerate(lists)]
     if return_alphas and maps is None and nbest:     # the hypotheses that are there, image by image; None keeps its place
-        there = [[p for p in hyps if p is not None] for hyps in lists]
-        got = [iter(m) for m in _nbest_replay(step_fn, state, there, k)]
+        got = [iter(m) for m in _nbest_replay(step_fn, state, [[p for p in hyps if p is not None] for hyps in lists], k)]
         maps = [[None if p is None else next(got[i]) for p in hyps] for i, hyps in enumerate(lists)]
     elif return_alphas and maps is None:
-        maps = replay_alphas(step_fn, state, lists, n_img, k)
+        maps = replay_alphas(step_fn, state, lists, len(lists), k)
     if n is None:
-        one = lists[0]
-        if nbest:
-            one = [None if p is None else (torch.tensor([p[0]], dtype=torch.long, device=dev), p[1]) for p in one]
-        else:
-            one = torch.tensor([one], dtype=torch.long, device=dev)
-        lists, maps = one, None if maps is None else maps[0]
-    return (lists, maps) if return_alphas else lists
-
-
-def _beam_result(step_fn, state, n, k, lists, maps, one, return_alphas, nbest):
-    """What beam_decode returns, from what its route gave. lists: per image its token list, or with nbest its list of
-    (tokens, score) pairs; maps: the one-call search's recording in the same nesting, else None: with return_alphas they
-    come from replay_alphas / _nbest_replay; one: the host loop's tensor of one image, returned as it is. n None: the one
-    image's entry, the tokens as LongTensor [1, L]."""
-    if return_alphas and maps is None:
-        maps = _nbest_replay(step_fn, state, lists, k) if nbest else replay_alphas(step_fn, state, lists, len(lists), k)
-    if n is None:
-        dev = state[0].device
         if one is None:
             one = _one_image(lists[0], dev) if nbest else torch.tensor(lists, dtype=torch.long, device=dev)
         lists, maps = one, None if maps is None else maps[0]

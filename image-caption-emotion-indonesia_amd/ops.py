@@ -229,43 +229,32 @@ def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None, forc
     logits, prev_scores = _c(logits), _c(prev_scores)
     if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[1] != 3 or not meta.is_contiguous():
         raise CapnetError("beam_topk_batched: meta must be a contiguous int32 [n, 3] tensor")
+    if forced is not None and diversity is not None:
+        raise CapnetError("beam_topk_batched: forced words do not go with diversity")
+    if (forced is not None or diversity is not None) and (logits.dtype != torch.float32 or prev_scores.dtype != torch.float32):
+        raise CapnetError("beam_topk_batched: logits and prev_scores must be float32")
+    cap = 0 if bans is None else _check_bans("beam_topk_batched", bans, logits.shape[0])   # a row for every row of the logits
     n = meta.shape[0]
     scores = torch.empty((n, 16), dtype=torch.float32, device=logits.device)
     index = torch.empty((n, 16), dtype=torch.int64, device=logits.device)
+    block = (ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta))
     if forced is not None:
         constraints, met, end_token = forced
-        if diversity is not None:
-            raise CapnetError("beam_topk_batched: forced words do not go with diversity")
-        if logits.dtype != torch.float32 or prev_scores.dtype != torch.float32:
-            raise CapnetError("beam_topk_batched: logits and prev_scores must be float32")
         _need_cuda(met)
         if met.dtype != torch.int32 or met.dim() != 1 or met.numel() < logits.shape[0] or not met.is_contiguous():
             raise CapnetError("beam_topk_batched: met must be a contiguous int32 tensor with an entry per logits row")
-        cap = 0 if bans is None else _check_bans("beam_topk_batched", bans, logits.shape[0])
-        check(_lib.lib().capnet_beam_topk_batched_forced(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
-                                                         n, ptr(bans), cap, ptr(met), *forced_args(constraints, logits.device),
-                                                         int(end_token), ptr(scores), ptr(index), current_stream()),
-              "capnet_beam_topk_batched_forced")
-        return scores, index
-    if diversity is not None:
+        name = "capnet_beam_topk_batched_forced"
+        args = block + (n, ptr(bans), cap, ptr(met)) + forced_args(constraints, logits.device) + (int(end_token),)
+    elif diversity is not None:
         teams = int(diversity.groups)
         if n % teams:
             raise CapnetError("beam_topk_batched: %d rows of meta for teams of %d" % (n, teams))
-        if logits.dtype != torch.float32 or prev_scores.dtype != torch.float32:
-            raise CapnetError("beam_topk_batched: logits and prev_scores must be float32")
-        cap = 0 if bans is None else _check_bans("beam_topk_batched", bans, logits.shape[0])
-        check(_lib.lib().capnet_beam_topk_batched_diverse(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
-                                                          n // teams, teams, float(diversity.strength), ptr(bans), cap, ptr(scores),
-                                                          ptr(index), current_stream()), "capnet_beam_topk_batched_diverse")
-        return scores, index
-    if bans is not None:     # capnet_beam_topk_batched_banned: beam_topk's bans, a row for every row of the logits
-        cap = _check_bans("beam_topk_batched", bans, logits.shape[0])
-        check(_lib.lib().capnet_beam_topk_batched_banned(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta),
-                                                         n, ptr(bans), cap, ptr(scores), ptr(index), current_stream()),
-              "capnet_beam_topk_batched_banned")
-        return scores, index
-    check(_lib.lib().capnet_beam_topk_batched(ptr(logits), logits.shape[1], logits.shape[1], ptr(prev_scores), ptr(meta), n,
-                                              ptr(scores), ptr(index), current_stream()), "capnet_beam_topk_batched")
+        name, args = "capnet_beam_topk_batched_diverse", block + (n // teams, teams, float(diversity.strength), ptr(bans), cap)
+    elif bans is not None:
+        name, args = "capnet_beam_topk_batched_banned", block + (n, ptr(bans), cap)
+    else:
+        name, args = "capnet_beam_topk_batched", block + (n,)
+    check(getattr(_lib.lib(), name)(*args, ptr(scores), ptr(index), current_stream()), name)
     return scores, index
 
 
@@ -303,20 +292,25 @@ _banned_dev = {}      # (banned, device index) -> the int32 device array of a Co
 BANNED_CACHE_MAX = 64   # distinct (ban list, device) pairs kept; one more empties the cache (an array is at most 32 ints)
 
 
-def constraint_args(constraints, device):
-    """The four trailing arguments of the capnet_*_constrained entries for a capnet.beam.Constraints: (no_repeat_ngram,
-    min_words, the banned words as a device int32 array, their count). The array is made once per (tuple, device) and kept,
-    so that a search's steps do not copy it again; the cache holds at most BANNED_CACHE_MAX arrays. (An array dropped from
-    it while a launch that reads it is queued stays valid: torch's allocator hands freed memory to later work of the same
-    stream only.)"""
-    banned = tuple(int(w) for w in constraints.banned)
-    key = (banned, torch.device(device).index or 0)
+def _device_ints(values, device):
+    """A tuple of ints -> (the pointer of a device int32 array that holds them, their count). The array is made once per
+    (tuple, device) and kept, so that a search's steps do not copy it again; the cache holds at most BANNED_CACHE_MAX arrays.
+    (An array dropped from it while a launch that reads it is queued stays valid: torch's allocator hands freed memory to
+    later work of the same stream only.)"""
+    values = tuple(int(w) for w in values)
+    key = (values, torch.device(device).index or 0)
     arr = _banned_dev.get(key)
     if arr is None:
         if len(_banned_dev) >= BANNED_CACHE_MAX:
             _banned_dev.clear()
-        arr = _banned_dev[key] = torch.tensor(banned or (0,), dtype=torch.int32, device=device)
-    return int(constraints.no_repeat_ngram), int(constraints.min_words), ptr(arr), len(banned)
+        arr = _banned_dev[key] = torch.tensor(values or (0,), dtype=torch.int32, device=device)
+    return ptr(arr), len(values)
+
+
+def constraint_args(constraints, device):
+    """The four trailing arguments of the capnet_*_constrained entries for a capnet.beam.Constraints: (no_repeat_ngram,
+    min_words, the banned words as a device int32 array, their count); the array is _device_ints'."""
+    return (int(constraints.no_repeat_ngram), int(constraints.min_words)) + _device_ints(constraints.banned, device)
 
 
 NO_CONSTRAINTS = (0, 0, None, 0)     # the constraint arguments of an entry that takes them, zeros meaning none
@@ -330,70 +324,50 @@ def has_forced(constraints):
 def forced_args(constraints, device):
     """The two arguments behind constraint_args' four in the capnet_*_forced entries: (the forced ids as a device int32 array,
     their count), the array kept as constraint_args keeps the banned words'."""
-    forced = tuple(int(w) for w in constraints.forced)
-    key = ("forced", forced, torch.device(device).index or 0)
-    arr = _banned_dev.get(key)
-    if arr is None:
-        if len(_banned_dev) >= BANNED_CACHE_MAX:
-            _banned_dev.clear()
-        arr = _banned_dev[key] = torch.tensor(forced or (0,), dtype=torch.int32, device=device)
-    return ptr(arr), len(forced)
+    return _device_ints(constraints.forced, device)
 
 
-def _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints):
-    """capnet_beam_advance_forced on checked operands; trace None or checked."""
-    nk = beam.n * beam.k
-    dev = logits.device
-    check(_lib.lib().capnet_beam_advance_forced(
-        ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
-        beam.max_steps, int(step), int(end_token), *constraint_args(constraints, dev), *forced_args(constraints, dev),
-        ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance_forced")
-
-
-def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None, diversity=None, trace=None):
+def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=None, diversity=None, trace=None,
+                 who="beam_advance"):
     """capnet_beam_advance: step `step` (1-based) of every image on logits [n k, V]; fills next_words and parent_rows
-    (int64 [n k], contiguous) -- see include/capnet.h. constraints (a capnet.beam.Constraints;
-    capnet_beam_advance_constrained): the selecting workgroup excludes what they forbid, from the sequences in the state;
-    `logits` is then modified (-inf over the excluded words).
+    (int64 [n k], contiguous) -- see include/capnet.h. The entry by what is given, not by what it holds:
     diversity (a capnet.beam.Diversity; capnet_beam_advance_diverse): `beam` is the state of n D searches of k / D beams
     (beam_init(n D, k / D, ...)), state-image i D + g being team g of image i; one workgroup per image walks its teams in
-    order under the Hamming penalty. constraints may be None; trace (beam_trace(beam)) or None, this form only. `logits`
-    is modified."""
+    order under the Hamming penalty; constraints may be None.
+    Else constraints with forced words (capnet_beam_advance_forced): their exclusions, then the forced-word allocation.
+    Else constraints (a capnet.beam.Constraints; capnet_beam_advance_constrained[_traced]): the selecting workgroup
+    excludes what they forbid, from the sequences in the state.
+    Else capnet_beam_advance[_traced], the only form that leaves `logits` as it is (the others write -inf over the
+    excluded words, the diverse one the penalised logits).
+    trace (beam_trace(beam)) or None: the slot every hypothesis occupied at this step is recorded in it.
+    who: the name in front of this function's own messages."""
     _need_cuda(logits, next_words, parent_rows)
-    nk = beam.n * beam.k
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
-        raise CapnetError("beam_advance: logits must be float32 [n k, V] with unit column stride")
+    n, k = beam.n, beam.k
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != n * k or logits.stride(1) != 1:
+        raise CapnetError("%s: logits must be float32 [n k, V] with unit column stride" % who)
     for w in (next_words, parent_rows):
-        if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
-            raise CapnetError("beam_advance: next_words / parent_rows must be contiguous int64 [n k] tensors")
+        if w.dtype != torch.int64 or w.numel() != n * k or not w.is_contiguous():
+            raise CapnetError("%s: next_words / parent_rows must be contiguous int64 [n k] tensors" % who)
+    if trace is not None:
+        _check_trace(who, beam, trace)
+    state, dev = (ptr(beam.words),), logits.device
+    block = (ptr(logits), logits.stride(0) if n * k > 1 else logits.shape[1], logits.shape[1])
+    at = (beam.max_steps, int(step), int(end_token))
     if diversity is not None:
         teams = int(diversity.groups)
-        if beam.n % teams:
-            raise CapnetError("beam_advance: a state of %d searches for teams of %d" % (beam.n, teams))
-        if trace is not None:
-            _check_trace("beam_advance", beam, trace)
-        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, logits.device)
-        check(_lib.lib().capnet_beam_advance_diverse(
-            ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1],
-            beam.n // teams, beam.k * teams, teams, float(diversity.strength), beam.max_steps, int(step), int(end_token), *con,
-            ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance_diverse")
-        return
-    if has_forced(constraints):     # capnet_beam_advance_forced: the constraints' exclusions, then the forced-word allocation
-        if trace is not None:
-            _check_trace("beam_advance", beam, trace)
-        _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints)
-        return
-    if trace is not None:
-        raise CapnetError("beam_advance: trace= goes with diversity= or forced words; beam_advance_traced is the plain traced step")
-    if constraints is not None:
-        check(_lib.lib().capnet_beam_advance_constrained(
-            ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
-            beam.max_steps, int(step), int(end_token), *constraint_args(constraints, logits.device), ptr(next_words),
-            ptr(parent_rows), current_stream()), "capnet_beam_advance_constrained")
-        return
-    check(_lib.lib().capnet_beam_advance(ptr(beam.words), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1],
-                                         logits.shape[1], beam.n, beam.k, beam.max_steps, int(step), int(end_token),
-                                         ptr(next_words), ptr(parent_rows), current_stream()), "capnet_beam_advance")
+        if n % teams:
+            raise CapnetError("%s: a state of %d searches for teams of %d" % (who, n, teams))
+        name = "capnet_beam_advance_diverse"
+        args = state + (ptr(trace),) + block + (n // teams, k * teams, teams, float(diversity.strength)) + at \
+            + (NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev))
+    elif has_forced(constraints):
+        name = "capnet_beam_advance_forced"
+        args = state + (ptr(trace),) + block + (n, k) + at + constraint_args(constraints, dev) + forced_args(constraints, dev)
+    else:
+        con = () if constraints is None else constraint_args(constraints, dev)
+        name = "capnet_beam_advance" + ("_constrained" if con else "") + ("" if trace is None else "_traced")
+        args = state + (() if trace is None else (ptr(trace),)) + block + (n, k) + at + con
+    check(getattr(_lib.lib(), name)(*args, ptr(next_words), ptr(parent_rows), current_stream()), name)
 
 
 def beam_advance_topk(beam, values, index, lse, step, end_token, next_words, parent_rows, V=None):
@@ -445,28 +419,11 @@ def _check_trace(who, beam, trace):
 
 def beam_advance_traced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints=None):
     """capnet_beam_advance_traced: beam_advance that also records, in `trace` (beam_trace(beam)), the slot every hypothesis
-    occupied at this step -- see include/capnet.h."""
-    _need_cuda(logits, next_words, parent_rows)
-    _check_trace("beam_advance_traced", beam, trace)
-    nk = beam.n * beam.k
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != nk or logits.stride(1) != 1:
-        raise CapnetError("beam_advance_traced: logits must be float32 [n k, V] with unit column stride")
-    for w in (next_words, parent_rows):
-        if w.dtype != torch.int64 or w.numel() != nk or not w.is_contiguous():
-            raise CapnetError("beam_advance_traced: next_words / parent_rows must be contiguous int64 [n k] tensors")
-    if has_forced(constraints):
-        _advance_forced(beam, trace, logits, step, end_token, next_words, parent_rows, constraints)
-        return
-    if constraints is not None:     # capnet_beam_advance_constrained_traced: beam_advance's constraints, the trace as here
-        check(_lib.lib().capnet_beam_advance_constrained_traced(
-            ptr(beam.words), ptr(trace), ptr(logits), logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n,
-            beam.k, beam.max_steps, int(step), int(end_token), *constraint_args(constraints, logits.device), ptr(next_words),
-            ptr(parent_rows), current_stream()), "capnet_beam_advance_constrained_traced")
-        return
-    check(_lib.lib().capnet_beam_advance_traced(ptr(beam.words), ptr(trace), ptr(logits),
-                                                logits.stride(0) if nk > 1 else logits.shape[1], logits.shape[1], beam.n, beam.k,
-                                                beam.max_steps, int(step), int(end_token), ptr(next_words), ptr(parent_rows),
-                                                current_stream()), "capnet_beam_advance_traced")
+    occupied at this step -- see include/capnet.h. beam_advance(trace=trace), the trace required."""
+    if trace is None:
+        _check_trace("beam_advance_traced", beam, trace)
+    beam_advance(beam, logits, step, end_token, next_words, parent_rows, constraints=constraints, trace=trace,
+                 who="beam_advance_traced")
 
 
 def beam_finish_traced(beam, trace, end_token):
@@ -1315,34 +1272,24 @@ def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
 _search_ws = {}       # (the C size function's name, device index, its dims) -> the int64 workspace of a one-call search
 
 
-def _search_workspace(size_fn, device, dims, outside):
+def _search_workspace(size_fn, device, dims, outside, teams=None):
     """The cached workspace of a one-call search: one per size function, device and dims, sized by ONE call of
-    capnet_<...>_ws_bytes(*dims) when it is first asked for. A size of 0 raises CapnetError(outside)."""
-    key = (size_fn, torch.device(device).index or 0, tuple(dims))
-    ws = _search_ws.get(key)
-    if ws is None:
-        nbytes = getattr(_lib.lib(), size_fn)(*dims)
-        if not nbytes:
-            raise CapnetError(outside)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
-        _search_ws[key] = ws
-    return ws
-
-
-def _diverse_workspace(size_fn, device, dims, nq, kt, max_steps, rows_tail, outside):
-    """The cached workspace of a diverse one-call search -> (ws, the byte offset of its beam state): capnet_<...>_ws_bytes(*dims)
-    bytes, FOLLOWED BY the state of nq searches of kt beams (capnet_beam_state_bytes, rounded up to 16) and, with rows_tail,
+    capnet_<...>_ws_bytes(*dims) when it is first asked for. A size of 0 raises CapnetError(outside).
+    teams = (nq, kt, max_steps, rows_tail), the diverse searches -> (ws, the byte offset of its beam state): those bytes,
+    FOLLOWED BY the state of nq searches of kt beams (capnet_beam_state_bytes, rounded up to 16) and, with rows_tail,
     4 nq max_steps bytes for the winners' rows -- the layout include/capnet.h gives for the _diverse entries."""
-    key = ("diverse", size_fn, torch.device(device).index or 0, tuple(dims), nq, kt, bool(rows_tail))
+    key = (size_fn, torch.device(device).index or 0, tuple(dims), teams)
     hit = _search_ws.get(key)
     if hit is None:
-        base = getattr(_lib.lib(), size_fn)(*dims)
-        state = _lib.lib().capnet_beam_state_bytes(nq, kt, max_steps)
-        if not base or not state:
+        base = nbytes = getattr(_lib.lib(), size_fn)(*dims)
+        if teams is not None and base:
+            nq, kt, max_steps, rows_tail = teams
+            state = _lib.lib().capnet_beam_state_bytes(nq, kt, max_steps)
+            nbytes = state and base + (state + 15) // 16 * 16 + ((4 * nq * max_steps + 15) // 16 * 16 if rows_tail else 0)
+        if not nbytes:
             raise CapnetError(outside)
-        nbytes = base + (state + 15) // 16 * 16 + ((4 * nq * max_steps + 15) // 16 * 16 if rows_tail else 0)
         hit = _search_ws[key] = (torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), base)
-    return hit
+    return hit[0] if teams is None else hit
 
 
 def _teams(who, diversity, k, groups):
@@ -1389,8 +1336,9 @@ def _read_result(packed, flag, n):
 
 def _search_result(ws, beam_at, packed, flag, n, k, max_steps, steps, return_steps, nbest, length_penalty, alphas=None):
     """What a one-call search returns once its C call is issued. The token lists (_read_result), or with nbest the lists of
-    (tokens, score) out of the beam state the search left at capnet_beam_decode_ws_beam_offset(*beam_at) of `ws`
-    (_nbest_of_workspace); with return_steps followed by the steps issued; with alphas = (maps [n, max_steps, P], the dims
+    (tokens, score) out of the beam state the search left at capnet_beam_decode_ws_beam_offset(*beam_at) of `ws` -- or at the
+    byte offset beam_at, where the caller knows it: the diverse searches, n and k then those of the teams'
+    searches (_nbest_of_workspace); with return_steps followed by the steps issued; with alphas = (maps [n, max_steps, P], the dims
     of capnet_att_beam_decode_alphas_ws_*_offset) followed by the maps, cut to len - 1 rows -- per caption, or with nbest
     per hypothesis. One value comes back bare, several as a tuple."""
     L = _lib.lib()
@@ -1400,7 +1348,8 @@ def _search_result(ws, beam_at, packed, flag, n, k, max_steps, steps, return_ste
             maps, dims = alphas
             where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*dims), L.capnet_att_beam_decode_alphas_ws_hist_offset(*dims),
                      maps.shape[2])
-        res = _nbest_of_workspace(ws, L.capnet_beam_decode_ws_beam_offset(*beam_at), n, k, max_steps, length_penalty, flag, where)
+        at = beam_at if isinstance(beam_at, int) else L.capnet_beam_decode_ws_beam_offset(*beam_at)
+        res = _nbest_of_workspace(ws, at, n, k, max_steps, length_penalty, flag, where)
         res = res if alphas is not None else (res,)
     else:
         out, lens = _read_result(packed, flag, n)
@@ -1470,48 +1419,37 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
         raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, k=%d, %d layers, n=%d, max_steps=%d)"
                           % (who, E, H, V, k, nl, n_img, T))
     dev = emb.device
-    L = _lib.lib()
     outside = "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T)
+    if constraints is not None and groups > 1:
+        raise CapnetError("%s: constraints take one weight group" % who)
+    nq, kq, beam_at = n, k, (nl, n_img, k, H, V, T, 0, groups)     # the searches whose state the call leaves, and where
     if diversity is not None:
         teams, strength = _teams(who, diversity, k, groups)
-        ws, beam_at = _diverse_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), n * teams, k // teams, T, False,
-                                         outside)
-        slab = splitk_slab(dev)
-        packed, seqs, lengths = _result_buffer(n * teams, T, dev)
-        flag = err_flag(dev)
-        steps = C.c_int(0)
-        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev)
-        check(L.capnet_beam_decode_diverse(cell, nl, n, k, teams, strength, E, H, V, T, int(start_token), int(end_token), ptr(emb),
-                                           ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
-                                           slab.numel(), int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream(),
-                                           *con), "capnet_beam_decode_diverse")
-        lists = _nbest_of_workspace(ws, beam_at, n * teams, k // teams, T, 0.0, flag)
-        return (lists, steps.value) if return_steps else lists
-    ws = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), outside)
+        nq, kq = n * teams, k // teams
+        ws, beam_at = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), outside, (nq, kq, T, False))
+    else:
+        ws = _search_workspace("capnet_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T), outside)
     slab = splitk_slab(dev)
-    packed, seqs, lengths = _result_buffer(n, T, dev)
+    packed, seqs, lengths = _result_buffer(nq, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    tail_args = (ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
-                 int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
-    if constraints is not None:
-        if groups > 1:
-            raise CapnetError("%s: constraints take one weight group" % who)
-        if has_forced(constraints):
-            check(L.capnet_beam_decode_forced(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
-                                              *constraint_args(constraints, dev), *forced_args(constraints, dev)),
-                  "capnet_beam_decode_forced")
-        else:
-            check(L.capnet_beam_decode_constrained(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args,
-                                                   *constraint_args(constraints, dev)), "capnet_beam_decode_constrained")
+    args = (E, H, V, T, int(start_token), int(end_token), ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state),
+            ptr(ws), ptr(slab), slab.numel(), int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
+    if diversity is not None:
+        name, args = "capnet_beam_decode_diverse", (n, k, teams, strength) + args \
+            + (NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev))
+    elif has_forced(constraints):
+        name, args = "capnet_beam_decode_forced", (n, k) + args + constraint_args(constraints, dev) + forced_args(constraints, dev)
+    elif constraints is not None:
+        name, args = "capnet_beam_decode_constrained", (n, k) + args + constraint_args(constraints, dev)
     elif groups > 1:
-        check(L.capnet_beam_decode_groups(cell, nl, groups, n_img, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
-              "capnet_beam_decode_groups")
+        name, args = "capnet_beam_decode_groups", (groups, n_img, k) + args
     else:
-        check(L.capnet_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), *tail_args),
-              "capnet_beam_decode")
-    return _search_result(ws, (nl, n_img, k, H, V, T, 0, groups), packed, flag, n, k, T, steps, return_steps, nbest,
-                          length_penalty)
+        name, args = "capnet_beam_decode", (n, k) + args
+    check(getattr(_lib.lib(), name)(cell, nl, *args), name)
+    if diversity is not None:       # the raw material of the merge: every team's list at penalty 0
+        nbest, length_penalty = True, 0.0
+    return _search_result(ws, beam_at, packed, flag, nq, kq, T, steps, return_steps, nbest, length_penalty)
 
 
 def lstm_beam_decode_supported(E, H, k, V, num_layers):
@@ -1725,70 +1663,47 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     if T < 1 or k > V or tuple(Cw.shape) != (V, H) or (Cb is not None and Cb.numel() != V):
         raise CapnetError("att_beam_decode: Cw [V, H], Cb [V], k <= V, max_steps >= 1 (V=%d, k=%d, max_steps=%d)" % (V, k, T))
     dev = emb.device
-    L = _lib.lib()
     n_img, n = n, groups * n       # from here on n counts the beam groups
     outside = "att_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T)
-    alpha_dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
-    if diversity is not None:
-        teams, strength = _teams("att_beam_decode", diversity, k, groups)
-        if return_alphas:
-            ws, beam_at = _diverse_workspace("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, n * teams, k // teams, T, True,
-                                             outside)
-        else:
-            ws, beam_at = _diverse_workspace("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), n * teams,
-                                             k // teams, T, False, outside)
-        slab = splitk_slab(dev)
-        packed, seqs, lengths = _result_buffer(n * teams, T, dev)
-        flag = err_flag(dev)
-        steps = C.c_int(0)
-        maps = torch.empty((n * teams, T, P), dtype=torch.float32, device=dev) if return_alphas else None
-        con = NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev)
-        check(L.capnet_att_beam_decode_diverse(
-            cell, nl, n, k, teams, strength, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb),
-            ptr(wz), ptr(bz), ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab),
-            slab.numel(), int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream(), ptr(maps), *con),
-            "capnet_att_beam_decode_diverse")
-        where = None
-        if return_alphas:
-            where = (L.capnet_att_beam_decode_alphas_ws_trace_offset(*alpha_dims),
-                     L.capnet_att_beam_decode_alphas_ws_hist_offset(*alpha_dims), P)
-        res = _nbest_of_workspace(ws, beam_at, n * teams, k // teams, T, 0.0, flag, where)
-        if return_steps:
-            res = (res[0], steps.value, res[1]) if return_alphas else (res, steps.value)
-        return res
-    if return_alphas:
-        ws = _search_workspace("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, outside)
-    else:
-        ws = _search_workspace("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), outside)
-    slab = splitk_slab(dev)
-    packed, seqs, lengths = _result_buffer(n, T, dev)
-    flag = err_flag(dev)
-    steps = C.c_int(0)
-    args = (n_img, k, P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz),
-            ptr(wf), ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
-            int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
-    alphas = None
     if constraints is not None and groups > 1:
         raise CapnetError("att_beam_decode: constraints take one weight group")
-    con = () if constraints is None else constraint_args(constraints, dev)
-    if return_alphas:
-        alphas = (torch.empty((n, T, P), dtype=torch.float32, device=dev), alpha_dims)
-    if has_forced(constraints):     # capnet_att_beam_decode_forced: one entry, the maps nullable
-        check(L.capnet_att_beam_decode_forced(cell, nl, *args, ptr(alphas[0]) if alphas else None, *con,
-                                              *forced_args(constraints, dev)), "capnet_att_beam_decode_forced")
-    elif return_alphas:
-        if con:
-            check(L.capnet_att_beam_decode_alphas_constrained(cell, nl, *args, ptr(alphas[0]), *con),
-                  "capnet_att_beam_decode_alphas_constrained")
-        else:
-            check(L.capnet_att_beam_decode_alphas(cell, nl, groups, *args, ptr(alphas[0])), "capnet_att_beam_decode_alphas")
-    elif con:
-        check(L.capnet_att_beam_decode_constrained(cell, nl, *args, *con), "capnet_att_beam_decode_constrained")
-    elif groups > 1:
-        check(L.capnet_att_beam_decode_groups(cell, nl, groups, *args), "capnet_att_beam_decode_groups")
+    alpha_dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
+    size = ("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, outside) if return_alphas else \
+        ("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), outside)
+    nq, kq, beam_at = n, k, (nl, n, k, H, V, T, 0, 1)     # the searches whose state the call leaves, and where
+    if diversity is not None:
+        teams, strength = _teams("att_beam_decode", diversity, k, groups)
+        nq, kq = n * teams, k // teams
+        ws, beam_at = _search_workspace(*size, (nq, kq, T, return_alphas))
     else:
-        check(L.capnet_att_beam_decode(cell, nl, *args), "capnet_att_beam_decode")
-    return _search_result(ws, (nl, n, k, H, V, T, 0, 1), packed, flag, n, k, T, steps, return_steps, nbest, length_penalty, alphas)
+        ws = _search_workspace(*size)
+    slab = splitk_slab(dev)
+    packed, seqs, lengths = _result_buffer(nq, T, dev)
+    flag = err_flag(dev)
+    steps = C.c_int(0)
+    alphas = (torch.empty((nq, T, P), dtype=torch.float32, device=dev), alpha_dims) if return_alphas else None
+    maps = (ptr(alphas[0]) if alphas else None,)
+    con = () if constraints is None else constraint_args(constraints, dev)
+    args = (P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz), ptr(wf),
+            ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
+            int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
+    if diversity is not None:       # one entry, the maps nullable
+        name, args = "capnet_att_beam_decode_diverse", (n, k, teams, strength) + args + maps + (con or NO_CONSTRAINTS)
+    elif has_forced(constraints):   # one entry, the maps nullable
+        name, args = "capnet_att_beam_decode_forced", (n_img, k) + args + maps + con + forced_args(constraints, dev)
+    elif return_alphas:
+        name, args = ("capnet_att_beam_decode_alphas_constrained", (n_img, k) + args + maps + con) if con else \
+            ("capnet_att_beam_decode_alphas", (groups, n_img, k) + args + maps)
+    elif con:
+        name, args = "capnet_att_beam_decode_constrained", (n_img, k) + args + con
+    elif groups > 1:
+        name, args = "capnet_att_beam_decode_groups", (groups, n_img, k) + args
+    else:
+        name, args = "capnet_att_beam_decode", (n_img, k) + args
+    check(getattr(_lib.lib(), name)(cell, nl, *args), name)
+    if diversity is not None:       # the raw material of the merge: every team's list at penalty 0
+        nbest, length_penalty = True, 0.0
+    return _search_result(ws, beam_at, packed, flag, nq, kq, T, steps, return_steps, nbest, length_penalty, alphas)
 
 
 def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,
