@@ -194,6 +194,19 @@ SIGNATURES = {
     "capnet_att_sample_decode_nucleus_greedy": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
                                                                     C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
                                                                     C.c_uint, _vp]),
+    "capnet_sample_exclusion_mask": (_i, [_vp, _l, _i, _vp, _i, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _vp]),
+    "capnet_mask_logits": (_i, [_vp, _i, _l, _i, _vp, _vp]),
+    "capnet_vocab_sample_masked": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_uint, C.c_uint, _vp, _vp, _vp, _vp,
+                                        C.c_uint, _vp]),
+    "capnet_vocab_topk_masked": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_sample_decode_excl_ws_bytes": (_sz, [_i, _i, _i, _i, _i, C.c_float]),
+    "capnet_sample_decode_excl": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
+                                       C.c_float, _i, C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_uint,
+                                       C.c_longlong, _i, _i, _vp, _i, _vp]),
+    "capnet_att_sample_decode_excl_ws_bytes": (_sz, [_i] * 10 + [C.c_float]),
+    "capnet_att_sample_decode_excl": (_i, [_i] * 11 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, C.c_float, _i,
+                                                                 C.c_float, C.c_ulonglong, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                                 C.c_uint, C.c_longlong, _i, _i, _vp, _i, _vp]),
     "capnet_vocab_topk_groups_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "capnet_vocab_topk_groups": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "capnet_beam_advance_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_longlong, _vp, _vp, _vp]),

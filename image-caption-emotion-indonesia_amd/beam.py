@@ -116,6 +116,22 @@ class Constraints(object):
         if self.forced and not len(self.forced) < max_seq_length:
             raise ops.CapnetError("constraints: %d forced words must be fewer than max_seq_length %d" % (len(self.forced), max_seq_length))
 
+    def check_exclude(self, vocab_size, end_token, top_k, max_seq_length):
+        """The front end's check for one sampled decode under `exclude=` (sample_random; CapnetError): no forced
+        words (they have no meaning for a draw), no banned id is end_token or outside the vocabulary, min_words <
+        max_seq_length, and every row keeps max(top_k, 1) words to choose among at every step -- check's count: V -
+        len(banned) - 1 - (max_seq_length + 1) >= max(top_k, 1)."""
+        if self.forced:
+            raise ops.CapnetError("exclude: forced=%r has no meaning for a draw" % (self.forced,))
+        if int(end_token) in self.banned or any(w >= vocab_size for w in self.banned):
+            raise ops.CapnetError("exclude: banned=%r must be word ids below %d other than end_token %d"
+                                  % (self.banned, vocab_size, int(end_token)))
+        if not self.min_words < max_seq_length:
+            raise ops.CapnetError("exclude: min_words=%d must be below max_seq_length %d" % (self.min_words, max_seq_length))
+        if vocab_size - len(self.banned) - 1 - (max_seq_length + 1) < max(int(top_k), 1):
+            raise ops.CapnetError("exclude: vocab_size %d - %d banned - 1 - (max_seq_length %d + 1) leaves fewer than max(top_k, 1) "
+                                  "= %d words" % (vocab_size, len(self.banned), max_seq_length, max(int(top_k), 1)))
+
     def __repr__(self):
         tail = ", forced=%r" % (self.forced,) if self.forced else ""
         return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r%s)" % (self.no_repeat_ngram, self.min_words, self.banned, tail)

@@ -638,15 +638,19 @@ int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, f
 
 size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
 
-int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
-                      float* values, int* index, float* lse, capnet_stream_t stream) {
+static int vocab_topk_tail(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
+                           float* values, int* index, float* lse, capnet_stream_t stream, const unsigned* mask) {
   CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1, "vocab_topk: rows %d, V %d", rows, V);
   CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "vocab_topk: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
   CAPNET_REQUIRE(vocab_topk_supported(H, k, V), "vocab_topk: unsupported H=%d", H);
   CAPNET_REQUIRE(h && w && workspace && values && index && lse, "vocab_topk: null argument");
   CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_topk: h, w and the workspace must be 16-B aligned");
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)lse % 4 == 0, "vocab_topk: output alignment");
-  return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream));
+  return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream), mask);
+}
+int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
+                      float* values, int* index, float* lse, capnet_stream_t stream) {
+  return vocab_topk_tail(h, w, b, rows, H, V, k, workspace, values, index, lse, stream, nullptr);
 }
 
 // ---- sampled decoding (vocab_sample.hip) ----
@@ -679,7 +683,7 @@ size_t capnet_vocab_sample_ws_bytes(int rows, int V) { return rows >= 1 && V >= 
 
 static int vocab_sample_tail(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
                              unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
-                             float* logp, capnet_stream_t stream, unsigned greedy_stride) {
+                             float* logp, capnet_stream_t stream, unsigned greedy_stride, const unsigned* mask = nullptr) {
   if (int rc = greedy_stride_check("vocab_sample", 0, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
   if (int rc = sample_check("vocab_sample", rows, V, temperature, step, row0, &inv_T)) return rc;
@@ -687,7 +691,7 @@ static int vocab_sample_tail(const float* h, const float* w, const float* b, int
   CAPNET_REQUIRE(h && w && workspace && tokens && logp, "vocab_sample: null argument");
   CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_sample: h, w and the workspace must be 16-B aligned");
   CAPNET_REQUIRE((size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "vocab_sample: output alignment");
-  return vocab_sample(h, w, b, rows, H, V, inv_T, seed, step, row0, workspace, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+  return vocab_sample(h, w, b, rows, H, V, inv_T, seed, step, row0, workspace, tokens, nullptr, logp, 1, S(stream), greedy_stride, mask);
 }
 int capnet_vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
                         unsigned long long seed, unsigned step, unsigned row0, void* workspace, long long* tokens,
@@ -860,11 +864,15 @@ static int sample_decode_nucleus_tail(int cell, int nlayers, int rows, int E, in
                                       const float* state0, float temperature, int top_k, float top_p,
                                       unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
                                       long long* ids, float* logp, float* state_out, int* err_flag, capnet_stream_t stream,
-                                      unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("sample_decode_nucleus", rows, greedy_stride, 0)) return rc;
-  const char* who = "sample_decode_nucleus";
+                                      unsigned greedy_stride, const char* who = "sample_decode_nucleus",
+                                      const SampleExcl* ex = nullptr) {   // (ex: capnet_sample_decode_excl, top_p == 1 allowed)
+  if (int rc = greedy_stride_check(who, rows, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
-  if (int rc = top_p_check(who, top_p, false)) return rc;
+  if (int rc = top_p_check(who, top_p, ex != nullptr)) return rc;
+  if (ex) {
+    if (int rc = sample_excl_check(who, *ex)) return rc;
+    CAPNET_REQUIRE(start_tokens, "%s: start_tokens is required (the hypotheses begin with them)", who);
+  }
   CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "%s: steps %d (1..65535)", who, steps);
   if (int rc = sample_check(who, rows, V, temperature, 0, 0, &inv_T)) return rc;
   CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "%s: unknown cell %d", who, cell);
@@ -874,13 +882,15 @@ static int sample_decode_nucleus_tail(int cell, int nlayers, int rows, int E, in
   CAPNET_REQUIRE((first_inputs != nullptr) != (start_tokens != nullptr), "%s: the first input is either first_inputs or start_tokens",
                  who);
   CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && logp && err_flag, "%s: null argument", who);
-  CAPNET_REQUIRE(top_k > 0 || (slab && aligned16(slab) && slab_floats > 0), "%s: the split-K slab (16-B aligned) is required", who);
+  CAPNET_REQUIRE(top_k > 0 || top_p == 1.f || (slab && aligned16(slab) && slab_floats > 0),
+                 "%s: the split-K slab (16-B aligned) is required", who);
   CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!state_out || aligned16(state_out)),
                  "%s: workspace, Cw and the states must be 16-B aligned", who);
   CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
   if (int rc = layer_weights_check(who, nlayers, wcat, beff)) return rc;
   return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
-                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream), greedy_stride);
+                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream), greedy_stride,
+                               ex);
 }
 int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
                                  const long long* start_tokens, const float* emb, const float* const* wcat,
@@ -902,6 +912,61 @@ int capnet_sample_decode_nucleus_greedy(int cell, int nlayers, int rows, int E, 
   return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
                                     state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
                                     state_out, err_flag, stream, greedy_stride);
+}
+
+// ---- sampled decoding with exclusions (sample_exclude.hip) ----
+int capnet_sample_exclusion_mask(const long long* ids, long ld, int steps, const long long* start_tokens, int rows, int t, int V,
+                                 long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                 unsigned* mask, capnet_stream_t stream) {
+  const char* who = "sample_exclusion_mask";
+  const SampleExcl c{end_token, no_repeat_ngram, min_words, banned, n_banned, mask};
+  if (int rc = sample_excl_check(who, c)) return rc;
+  CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1 && V <= (1 << 24), "%s: rows %d, V %d (rows < 2^24, V <= 2^24)", who, rows, V);
+  CAPNET_REQUIRE(steps >= 1 && steps <= 65535 && ld >= steps, "%s: steps %d (1..65535), ld %ld (>= steps)", who, steps, ld);
+  CAPNET_REQUIRE(t >= 0 && t <= steps, "%s: t=%d lies beyond steps %d", who, t, steps);
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "%s: mask is null or not 4-byte aligned", who);
+  CAPNET_REQUIRE((ids || !t) && (size_t)ids % 8 == 0 && (size_t)start_tokens % 8 == 0,
+                 "%s: ids is null (required from t = 1) or ids / start_tokens not 8-byte aligned", who);
+  return sample_exclusion_mask(ids, ld, start_tokens, rows, t, V, c, mask, S(stream));
+}
+
+int capnet_mask_logits(float* logits, int rows, long ld, int V, const unsigned* mask, capnet_stream_t stream) {
+  CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1 && V <= (1 << 24) && ld >= V, "mask_logits: rows %d, V %d, ld %ld (>= V)", rows,
+                 V, ld);
+  CAPNET_REQUIRE(logits && (size_t)logits % 4 == 0, "mask_logits: logits is null or not 4-byte aligned");
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "mask_logits: mask is null or not 4-byte aligned");
+  return mask_logits(logits, rows, ld, V, mask, S(stream));
+}
+
+int capnet_vocab_sample_masked(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                               unsigned long long seed, unsigned step, unsigned row0, const unsigned* mask, void* workspace,
+                               long long* tokens, float* logp, unsigned greedy_stride, capnet_stream_t stream) {
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "vocab_sample_masked: mask is null or not 4-byte aligned");
+  return vocab_sample_tail(h, w, b, rows, H, V, temperature, seed, step, row0, workspace, tokens, logp, stream, greedy_stride, mask);
+}
+
+int capnet_vocab_topk_masked(const float* h, const float* w, const float* b, int rows, int H, int V, int k, const unsigned* mask,
+                             void* workspace, float* values, int* index, float* lse, capnet_stream_t stream) {
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "vocab_topk_masked: mask is null or not 4-byte aligned");
+  return vocab_topk_tail(h, w, b, rows, H, V, k, workspace, values, index, lse, stream, mask);
+}
+
+size_t capnet_sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, float top_p) {
+  if (!capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k) || !(top_p > 0.f && top_p <= 1.f)) return 0;
+  return sample_decode_excl_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f);
+}
+
+int capnet_sample_decode_excl(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float temperature,
+                              int top_k, float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                              long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                              long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                              capnet_stream_t stream) {
+  const SampleExcl ex{end_token, no_repeat_ngram, min_words, banned, n_banned, nullptr};
+  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
+                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
+                                    state_out, err_flag, stream, greedy_stride, "sample_decode_excl", &ex);
 }
 
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
@@ -1198,14 +1263,17 @@ static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, i
                                           const float* Cw, const float* Cb, const float* state0, float temperature,
                                           int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
                                           size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                                          capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("att_sample_decode_nucleus", n * m, greedy_stride, m)) return rc;
-  const char* who = "att_sample_decode_nucleus";
+                                          capnet_stream_t stream, unsigned greedy_stride,
+                                          const char* who = "att_sample_decode_nucleus",
+                                          const SampleExcl* ex = nullptr) {   // (ex: capnet_att_sample_decode_excl, top_p == 1 allowed)
+  if (int rc = greedy_stride_check(who, n * m, greedy_stride, m)) return rc;
+  if (ex)
+    if (int rc = sample_excl_check(who, *ex)) return rc;
   if (int rc = att_decode_check(who, cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
                                 workspace, slab, slab_floats, err_flag))
     return rc;
   float inv_T = 0.f;
-  if (int rc = top_p_check(who, top_p, false)) return rc;
+  if (int rc = top_p_check(who, top_p, ex != nullptr)) return rc;
   CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "%s: steps %d (1..65535)", who, steps);
   if (int rc = sample_check(who, n * m, V, temperature, 0, 0, &inv_T)) return rc;
   CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "%s: top_k=%d (0 = off, 1 .. 16, <= V = %d)", who, top_k, V);
@@ -1216,7 +1284,7 @@ static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, i
   CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
   return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full,
                                    wcat, beff, Cw, Cb, state0, inv_T, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                   state_out, err_flag, S(stream), greedy_stride);
+                                   state_out, err_flag, S(stream), greedy_stride, ex);
 }
 int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
                                      int steps, const long long* start_tokens, const float* att1, const float* feat,
@@ -1240,6 +1308,27 @@ int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m,
   return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
                                         w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
                                         workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride);
+}
+
+size_t capnet_att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k,
+                                              float top_p) {
+  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V || !(top_p > 0.f && top_p <= 1.f)) return 0;
+  return att_sample_decode_excl_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, top_p < 1.f);
+}
+
+int capnet_att_sample_decode_excl(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                  const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, float temperature, int top_k, float top_p, unsigned long long seed,
+                                  void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                  float* state_out, int* err_flag, unsigned greedy_stride, long long end_token,
+                                  int no_repeat_ngram, int min_words, const int* banned, int n_banned, capnet_stream_t stream) {
+  const SampleExcl ex{end_token, no_repeat_ngram, min_words, banned, n_banned, nullptr};
+  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
+                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
+                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride,
+                                        "att_sample_decode_excl", &ex);
 }
 
 size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,

@@ -2,7 +2,7 @@
 // layouts, and the gather of the attention maps. No loop reads the device except the beam search's optional poll.
 //   token loops: the greedy `sample` of capnet.seq2seq (seq2seq/model.py:100-122, 193-217; capnet_lstm_greedy_decode and
 //                its _groups form) and sampled decoding (capnet_sample_decode, capnet_att_sample_decode and their _nucleus
-//                forms)
+//                and _excl forms)
 //   beam loops:  beam_decode, lstm_beam_decode, lstm_beam_decode_groups, att_beam_decode
 // The kernels they launch: lstm_decode_step.hip, att_kernels.hip, vocab_argmax.hip, vocab_topk.hip, vocab_sample.hip,
 // vocab_nucleus.hip, beam_search.hip (beam_advance), gemm_f32.hip.
@@ -100,7 +100,9 @@ int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, in
 // the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": today's launches, not a nucleus.
 // greedy_stride (sample_key.h's vs_row_key; the capnet_*_greedy entries): g > 0 makes every g-th row the greedy decode of its
 // group -- the loops only pass it to the draw; on the attention loop the caller runs m = g rows per image, so the greedy
-// caption rides on the one read of the image's maps per step ----
+// caption rides on the one read of the image's maps per step
+// exclusions (ex; the capnet_*_excl entries): one more launch per step, sample_exclusion_mask, and the draw takes
+// the mask -- vocab_sample / vocab_topk in their epilogues, the nucleus draw without top_k through mask_logits on its block ----
 static size_t sample_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus) {
   const size_t draw = top_k > 0 ? vocab_topk_ws_bytes(rows, top_k, V)
                       : nucleus ? align16((size_t)rows * V * sizeof(float)) : vocab_sample_ws_bytes(rows, V);
@@ -119,7 +121,10 @@ template <class Step>
 static int sample_loop(int nlayers, int rows, int H, int V, int steps, const long long* start_tokens, const float* Cw,
                        const float* Cb, const float* state0, float inv_T, int top_k, float top_p, unsigned long long seed, void* ws,
                        float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, hipStream_t s,
-                       unsigned greedy_stride, Step&& step_fn) {
+                       unsigned greedy_stride, const SampleExcl* ex, Step&& step_fn) {
+  // ex (the capnet_*_excl entries): a launch of its own builds the step's exclusion mask from ids and the start
+  // tokens, and the step's draw reads it; null: the launches as they were
+  const unsigned* mask = ex ? ex->mask : nullptr;
   const TokenDecodeWs w = token_decode_layout(nlayers, rows, H, top_k);
   const bool nucleus = top_p < 1.f;
   char* p = reinterpret_cast<char*>(ws);
@@ -130,16 +135,19 @@ static int sample_loop(int nlayers, int rows, int H, int V, int steps, const lon
   float* logits = reinterpret_cast<float*>(p + w.draw);      // the nucleus draw without top_k
   return token_loop(w, nlayers, rows, H, steps, nucleus && top_k == 0 ? 0 : 1, start_tokens, state0, ws, state_out, s, step_fn,
                     [&](int t, const float* h_top, long long* tok) {
+                      if (ex)
+                        if (int rc = sample_exclusion_mask(ids, steps, start_tokens, rows, t, V, *ex, ex->mask, s)) return rc;
                       if (top_k == 0 && !nucleus)
                         return vocab_sample(h_top, Cw, Cb, rows, H, V, inv_T, seed, (unsigned)t, 0, draw_ws, tok, ids + t, logp + t,
-                                            steps, s, greedy_stride);
+                                            steps, s, greedy_stride, mask);
                       if (top_k == 0) {
-                        const int rc = sgemm_splitk(false, true, rows, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+                        int rc = sgemm_splitk(false, true, rows, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
+                        if (rc == kOk && mask) rc = mask_logits(logits, rows, V, V, mask, s);
                         if (rc != kOk) return rc;
                         return nucleus_rows(logits, rows, V, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t, logp + t, steps, s,
                                             greedy_stride);
                       }
-                      const int rc = vocab_topk(h_top, Cw, Cb, rows, H, V, top_k, draw_ws, tk_values, tk_index, tk_lse, s);
+                      const int rc = vocab_topk(h_top, Cw, Cb, rows, H, V, top_k, draw_ws, tk_values, tk_index, tk_lse, s, mask);
                       if (rc != kOk) return rc;
                       if (nucleus)
                         return nucleus_pick(tk_values, tk_index, rows, top_k, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t,
@@ -149,13 +157,24 @@ static int sample_loop(int nlayers, int rows, int H, int V, int steps, const lon
                     });
 }
 
+size_t sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus) {
+  const size_t base = sample_ws_bytes(nlayers, rows, H, V, top_k, nucleus);
+  return base ? align16(base) + sample_mask_bytes(rows, V) : 0;
+}
+
 int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
                           const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
                           const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
                           unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride) {
+                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride, const SampleExcl* ex) {
+  SampleExcl placed;
+  if (ex) {   // the mask: behind the loop's own workspace
+    placed = *ex;
+    placed.mask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f)));
+    ex = &placed;
+  }
   return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, greedy_stride, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
+                     logp, state_out, s, greedy_stride, ex, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
                        const bool given = t == 0 && first_inputs;     // step 0 on the caller's rows
                        return stacked_decode_step(cell, nlayers, rows, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
                                                   wcat, beff, sin, sout, h_top, err_flag, s);
@@ -188,17 +207,29 @@ size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int 
   return att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, true);
 }
 
+size_t att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus) {
+  const size_t base = att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, nucleus);
+  return base ? align16(base) + sample_mask_bytes(n * m, V) : 0;
+}
+
 int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
                               const long long* start_tokens, const float* att1, const float* feat, const float* emb,
                               const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
                               int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
                               long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
-                              unsigned greedy_stride) {
+                              unsigned greedy_stride, const SampleExcl* ex) {
   const int rows = n * m;
   void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f));
+  SampleExcl placed;
+  if (ex) {   // the mask: behind the loop's own workspace
+    placed = *ex;
+    placed.mask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) +
+                                              align16(att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, top_p < 1.f)));
+    ex = &placed;
+  }
   return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, greedy_stride, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
+                     logp, state_out, s, greedy_stride, ex, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
                        return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
                                               sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
                      });

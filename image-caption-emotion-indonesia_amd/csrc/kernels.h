@@ -378,14 +378,16 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
 // before the first use)
 bool vocab_topk_supported(int H, int k, int V);
 size_t vocab_topk_ws_bytes(int rows, int k, int V);
+// (mask: sample_exclude.hip's exclusion mask [rows][ceil(V / 32)] or null -- a set bit is not pickable, lse is then over the
+// allowed entries; null: the kernel without the mask, bit for bit)
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
-               int* index, float* lse, hipStream_t stream);
+               int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr);
 // weight groups, as vocab_argmax_groups: rows = groups x rpg, group-major; group g's rows on w[g] / b[g] (host-side pointer
 // tables, b or any b[g] may be null) in the same launch, one arrival counter and one block of partials per group (ws:
 // vocab_topk_groups_ws_bytes, its first 16 groups bytes zero before the first use); outputs [groups rpg][k] / [groups rpg]
 size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V);
 int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
-                      void* ws, float* values, int* index, float* lse, hipStream_t stream);
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr);
 // vocab_sample.hip: per row a draw from softmax((h[r] . W + b) inv_T) by Gumbel-max on sample_rng.h's stream keyed (seed,
 // step, row0 + r, v), one launch, no logits in memory: tok[r] / ids[r ld] the token, logp[r ld] its log-probability (each
 // optional; ws: vocab_sample_ws_bytes, its first 16 bytes zero before the first use). sample_pick: the same draw among
@@ -397,7 +399,7 @@ float sample_uniform_host(unsigned long long seed, unsigned step, unsigned row, 
 size_t vocab_sample_ws_bytes(int rows, int V);
 int vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float inv_T, unsigned long long seed,
                  unsigned step, unsigned row0, void* ws, long long* tok, long long* ids, float* logp, long ld,
-                 hipStream_t stream, unsigned greedy_stride = 0);
+                 hipStream_t stream, unsigned greedy_stride = 0, const unsigned* mask = nullptr);   // (mask: as vocab_topk's)
 int sample_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, unsigned long long seed,
                 unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
                 unsigned greedy_stride = 0);
@@ -418,6 +420,24 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
                       const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
                       void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                       hipStream_t s);
+// sample_exclude.hip: what a sampled row may not draw (capnet.beam.banned_words on [start, the row's words so far], the same
+// rule as BeamConstraints' without forced words), as a bit mask [rows][sample_mask_words(V)]: bit v & 31 of word v >> 5 set =
+// word v excluded on that launch row. `mask` is left null by the callers of the loops, which place it in their workspace
+struct SampleExcl {
+  long long end_token;
+  int no_repeat_ngram, min_words;
+  const int* banned;   // device array
+  int n_banned;
+  unsigned* mask;
+};
+static inline int sample_mask_words(int V) { return (V + 31) / 32; }
+size_t sample_mask_bytes(int rows, int V);           // 16-B aligned
+int sample_excl_check(const char* who, const SampleExcl& c);
+// the mask of stream step t: ids[r ld + 0 .. t - 1] the row's words so far, start_tokens[r] its <start> (null: none)
+int sample_exclusion_mask(const long long* ids, long ld, const long long* start_tokens, int rows, int t, int V,
+                          const SampleExcl& c, unsigned* mask, hipStream_t stream);
+// -inf at the mask's set bits of logits [rows][ld]
+int mask_logits(float* logits, int rows, long ld, int V, const unsigned* mask, hipStream_t stream);
 // vocab_nucleus.hip: nucleus (top-p) sampling, 0 < top_p < 1: sample_rows' / sample_pick's draw among the smallest set of
 // best entries whose probability reaches top_p, logp renormalised over that set. nucleus_rows: one workgroup per row finds the
 // set's edge by an exact search (any V up to 2^24); nucleus_pick: among vocab_topk's k candidates (top_k first, then top_p)
@@ -434,7 +454,8 @@ int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, 
                           const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
                           const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
                           unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride = 0);
+                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride = 0,
+                          const SampleExcl* ex = nullptr);
 size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
 int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
                               const long long* start_tokens, const float* att1, const float* feat, const float* emb,
@@ -442,7 +463,12 @@ int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A,
                               const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
                               int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
                               long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
-                              unsigned greedy_stride = 0);
+                              unsigned greedy_stride = 0, const SampleExcl* ex = nullptr);
+// the same loops under exclusions (ex set; top_p == 1 allowed: the plain draws): per step sample_exclusion_mask into the mask
+// behind the loop's own workspace, then the step's draw on it -- vocab_sample / vocab_topk with the mask, or mask_logits on the
+// logits block in front of nucleus_rows. ws: the loop's own bytes, 16-B aligned, then sample_mask_bytes
+size_t sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus);
+size_t att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus);
 // decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
 // fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
 // beam_decode's

@@ -12,7 +12,9 @@
 // The mapping and the hand-off are vocab_core.h's (one group). Per row the workgroup emits
 //   its best (key, index) under the total order (one packed 8-byte word) and that entry's s, and
 //   vocab_topk's m_w = the maximum of its pickable s, s_w = sum expf(s - m_w) over them (one packed 8-byte word).
-// A logit that is NaN or -inf, or lies beyond V, is not pickable: never drawn, and it adds nothing to s_w.
+// A logit that is NaN or -inf, or lies beyond V, is not pickable: never drawn, and it adds nothing to s_w. With an exclusion
+// mask (sample_exclude.hip) an entry whose bit is set is not pickable either: the draw and logp are those of the distribution
+// renormalised over the allowed entries.
 // The last arriver merges a wave per row, the workgroups across its lanes: the winner under the total order; M = max m_w,
 // S = sum s_w expf(m_w - M) with lane l adding workgroups l, l + 64, ... in that order and the lanes then combined by the
 // xor tree, lse = M + logf(S): the same bits whoever arrives last (a rounded product and a sum here, a fused multiply-add
@@ -47,9 +49,13 @@ struct VocabSampleArgs {
   unsigned long long seed;
   unsigned step, row0;
   unsigned greedy_stride;     // sample_key.h's vs_row_key: 0 = no greedy rows
+  const unsigned* mask;       // MASKED only: [rows][workgroups], bit c of word b = entry 32 b + c is not pickable on that row
 };
 
-template <int NJ, int TM>
+// MASKED (sample_exclude.hip): an entry whose mask bit is set is treated as a -inf logit is. The workgroup needs
+// word blockIdx.x of each row: one 4-byte load per half-wave, all 32 lanes the same address. The unmasked kernel is an
+// instance of its own and does not read the field.
+template <int NJ, int TM, bool MASKED>
 __global__ __launch_bounds__(512) void vocab_sample_kernel(VocabSampleArgs a) {
   const int rows = a.rows;
   unsigned long long* best_w = a.best + (long)blockIdx.x * rows;
@@ -58,7 +64,8 @@ __global__ __launch_bounds__(512) void vocab_sample_kernel(VocabSampleArgs a) {
   vocab_front<NJ, TM>(a.h, rows, a.w, a.b, a.H, a.V, [&](int row, bool valid, float z) {
     const int ec = threadIdx.x & 31, ecol = blockIdx.x * kVocCols + ec;   // the thread's entry
     const float s = vs_scaled(z, a.inv_T);
-    const bool ok = ecol < a.V && s > -INFINITY;          // NaN fails the comparison
+    bool ok = ecol < a.V && s > -INFINITY;                // NaN fails the comparison
+    if (MASKED) ok = ok && !(valid && ((a.mask[(long)row * gridDim.x + blockIdx.x] >> ec) & 1u));
     const float ps = ok ? s : -INFINITY;
     float bk = ok ? vs_row_key(s, a.seed, a.step, a.row0 + (unsigned)row, a.greedy_stride, (unsigned)ecol) : -INFINITY;
     int bi = ok ? ecol : kVocNone;
@@ -236,7 +243,7 @@ size_t vocab_sample_ws_bytes(int rows, int V) {
 
 int vocab_sample(const float* h, const float* w, const float* b, int rows, int H, int V, float inv_T, unsigned long long seed,
                  unsigned step, unsigned row0, void* ws, long long* tok, long long* ids, float* logp, long ld,
-                 hipStream_t stream, unsigned greedy_stride) {
+                 hipStream_t stream, unsigned greedy_stride, const unsigned* mask) {
   CAPNET_REQUIRE(rows >= 1 && V >= 1 && vocab_sample_supported(H), "vocab_sample: rows %d, H %d, V %d", rows, H, V);
   const size_t cells = (size_t)vocab_workgroups(V) * rows;
   VocabSampleArgs a;
@@ -248,9 +255,11 @@ int vocab_sample(const float* h, const float* w, const float* b, int rows, int H
   a.tok = tok; a.ids = ids; a.logp = logp; a.ld = ld;
   a.rows = rows; a.H = H; a.V = V;
   a.inv_T = inv_T; a.seed = seed; a.step = step; a.row0 = row0; a.greedy_stride = greedy_stride;
+  a.mask = mask;
   const dim3 grid(vocab_workgroups(V)), block(64 * kVocWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
-    hipLaunchKernelGGL((vocab_sample_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
+    if (mask) hipLaunchKernelGGL((vocab_sample_kernel<nj, nj <= 8 ? 2 : 1, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((vocab_sample_kernel<nj, nj <= 8 ? 2 : 1, false>), grid, block, 0, stream, a);
   });
   CAPNET_LAUNCH_CHECK();
   return kOk;

@@ -37,9 +37,12 @@ struct VocabTopkArgs {
   float* lse;                // [groups rpg]
   int rpg, H, V, k;          // rows per group: workgroup (., g) owns rows [g rpg, (g + 1) rpg)
   VocabGroups g;
+  const unsigned* mask;      // MASKED only: [groups rpg][workgroups], bit c of word b = entry 32 b + c is not pickable on that row
 };
 
-template <int NJ, int TM>
+// MASKED (sample_exclude.hip): an entry whose mask bit is set is treated as a -inf logit is, so the k best and lse
+// are those of the allowed entries; one 4-byte load per half-wave. The unmasked kernel is an instance of its own.
+template <int NJ, int TM, bool MASKED>
 __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   const int rows = a.rpg, k = a.k;
   // this group's rows, numbered from 0 below: its slice of h and of the outputs, its blocks of stat and cand, its counter
@@ -55,7 +58,8 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   unsigned long long* cand = gcand + (long)blockIdx.x * rows * k;
   vocab_front<NJ, TM>(a.h + rbeg * a.H, rows, a.g.w[grp], a.g.b[grp], a.H, a.V, [&](int row, bool valid, float v) {
     const int lane = threadIdx.x & 63, ec = lane & 31, ecol = blockIdx.x * kVocCols + ec;   // the thread's entry
-    const bool ok = ecol < a.V && v > -INFINITY;          // NaN fails the comparison
+    bool ok = ecol < a.V && v > -INFINITY;                // NaN fails the comparison
+    if (MASKED) ok = ok && !(valid && ((a.mask[(rbeg + row) * gridDim.x + blockIdx.x] >> ec) & 1u));
     const float pv = ok ? v : -INFINITY;
     float mx, e;
     vocab_half_wave_stat(ok, pv, mx, e);
@@ -174,12 +178,12 @@ size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V) {
 size_t vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_groups_ws_bytes(1, rows, k, V); }
 
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
-               int* index, float* lse, hipStream_t stream) {
-  return vocab_topk_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, k, ws, values, index, lse, stream);
+               int* index, float* lse, hipStream_t stream, const unsigned* mask) {
+  return vocab_topk_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, k, ws, values, index, lse, stream, mask);
 }
 
 int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
-                      void* ws, float* values, int* index, float* lse, hipStream_t stream) {
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask) {
   CAPNET_REQUIRE(groups >= 1 && groups <= kVocMaxGroups && rpg >= 1 && vocab_topk_supported(H, k, V),
                  "vocab_topk: %d groups of %d rows, H %d, V %d, k %d", groups, rpg, H, V, k);
   VocabTopkArgs a;
@@ -190,9 +194,11 @@ int vocab_topk_groups(const float* h, const float* const* w, const float* const*
   a.cand = a.stat + (size_t)groups * vocab_workgroups(V) * rpg;
   a.values = values; a.index = index; a.lse = lse;
   a.rpg = rpg; a.H = H; a.V = V; a.k = k;
+  a.mask = mask;
   const dim3 grid(vocab_workgroups(V), groups), block(64 * kVocWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
-    hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1>), grid, block, 0, stream, a);
+    if (mask) hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, false>), grid, block, 0, stream, a);
   });
   CAPNET_LAUNCH_CHECK();
   return kOk;

@@ -337,13 +337,17 @@ def fused_sample(rows, att=False, top_p=1.0, top_k=0):
     return os.environ.get(FUSED_SAMPLE_OFF, "")[:1] != "1" and rows <= most
 
 
-def draw_step(logits, temperature, top_k, seed, step, top_p=1.0, greedy_stride=0):
+def draw_step(logits, temperature, top_k, seed, step, top_p=1.0, greedy_stride=0, mask=None):
     """The composed route's draw of stream step `step` from logits [rows, V] -> (tokens [rows] int64, logp [rows]): the
     stream and the arithmetic of the one-call route's (ops.sample_rows; top_k > 0: torch.topk's candidates into
     ops.sample_pick), so both routes return the same tokens wherever the best two keys are further apart than the logits'
     last bits. top_p < 1: the nucleus draw (ops.nucleus_rows; top_k > 0: ops.nucleus_pick on the same candidates); top_p ==
-    1.0 calls what it called before there was a top_p. greedy_stride: ops.vocab_sample's (0: the calls as they were)."""
+    1.0 calls what it called before there was a top_p. greedy_stride: ops.vocab_sample's (0: the calls as they were).
+    mask (ops.sample_exclusion_mask's; None: the calls as they were): ops.mask_logits writes -inf over the excluded words of
+    `logits` first, which every draw here treats as not pickable."""
     gs = {"greedy_stride": greedy_stride} if greedy_stride else {}
+    if mask is not None:
+        logits = ops.mask_logits(logits if logits.stride(1) == 1 else logits.contiguous(), mask)
     if top_p == 1.0:
         if top_k == 0:
             return ops.sample_rows(logits, temperature, seed, step, **gs)
@@ -370,7 +374,7 @@ def cut_samples(ids, logp, n, m, start_token, end_token):
 
 
 def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0,
-                         greedy=False):
+                         greedy=False, exclude=None):
     """`m` captions per image DRAWN from the decoder's distribution softmax(logits / temperature) (top_k > 0: renormalised
     over the top_k best words of every step; top_p < 1: over the nucleus, the smallest set of best words -- of the top_k
     where that is set -- whose probability reaches top_p; logprob is that of the distribution drawn from) -> n lists of m
@@ -388,6 +392,14 @@ def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temp
     the greedy one; csrc/sample_key.h: the drawn rows keep noise row i m + j, so the first m pairs are those of the call
     without the keyword): step_fn / state are then the class's _beam(...) for m + 1 rows per image, the row limits of the
     routes apply to the n (m + 1) physical rows, and an attention decoder takes m + 1 <= 16.
+    exclude (a capnet.beam.Constraints without forced words): what no row may draw -- at stream step t row r is
+    the hypothesis [start, its words so far] at step t + 1 of capnet.beam.banned_words, the tokens as drawn whether or not the
+    row has emitted <end>. An excluded word is NOT PICKABLE, exactly as a -inf logit: never drawn, never a top_k candidate,
+    never in the nucleus, and logprob is that of the distribution renormalised over the allowed words (the beam searches
+    renormalise nothing; hence a keyword of its own). The greedy row is the argmax over the allowed words. The routes are the
+    same and draw the same tokens: the one call is ops.sample_decode / ops.att_sample_decode with exclude= (the capnet_*_excl
+    entries), the composed loop builds ops.sample_exclusion_mask per step for draw_step. None or an inactive Constraints():
+    exactly the calls of the decode without the keyword.
     Returns (the lists, ids int64 [rows, steps], logp float32 [rows, steps]): the decode's raw rows stay on the device beside
     the cut lists, for what scores them there (ops.bleu_rows); sample_random returns the lists alone."""
     who = "sample_random"
@@ -401,22 +413,34 @@ def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temp
     if greedy and is_attention(dec) and per > 16:
         raise ops.CapnetError("%s: %d samples and the greedy row: an attention decoder takes at most 16 rows per image" % (who, m))
     dev = state[0].device
+    if exclude is not None:
+        exclude.check_exclude(V, end_token, top_k, steps)
+        if not exclude.active:
+            exclude = None
+    ex = {} if exclude is None else {"exclude": exclude, "end_token": int(end_token)}
     with torch.no_grad():
         plain, att = getattr(step_fn, "plain", None), getattr(step_fn, "att", None)
         if fused_sample(n * per, False, top_p, top_k) and plain is not None and ops.sample_decode_supported(plain.emb.shape[1], plain.Cw.shape[1], V, top_k):
             tokens = torch.full((n * per,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp, _ = ops.sample_decode(plain.cell, steps, plain.wcat, plain.beff, plain.emb, plain.Cw, plain.Cb,
-                                             temperature, top_k, seed, start_tokens=tokens, **kw, **gs)
+                                             temperature, top_k, seed, start_tokens=tokens, **kw, **gs, **ex)
         elif fused_sample(n * per, True, top_p, top_k) and att is not None and (top_k == 0 or ops.vocab_topk_supported(att.Cw.shape[1], top_k, V)):
             ids, logp = ops.att_sample_decode(att.cell, att.att1, att.feat, att.emb, att.wz, att.bz, att.full_att.weight,
                                               att.full_att.bias, att.wcat, att.beff, att.Cw, att.Cb, att.state, per, steps,
-                                              start_token, temperature, top_k, seed, **kw, **({"greedy": True} if greedy else {}))
+                                              start_token, temperature, top_k, seed, **kw, **({"greedy": True} if greedy else {}), **ex)
         else:
             words = torch.full((n * per,), int(start_token), dtype=torch.int64, device=dev)
             ids, logp = [], []
+            if exclude is not None:      # the mask kernel reads the rows' words so far from one [rows, steps] block
+                start, so_far, mask = words, torch.empty((n * per, steps), dtype=torch.int64, device=dev), None
             for t in range(steps):
                 logits, state = step_fn(words, state)
-                words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs)
+                if exclude is not None:
+                    mask = ops.sample_exclusion_mask(so_far, start, t, V, end_token, exclude, out=mask)
+                    words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs, mask=mask)
+                    so_far[:, t] = words
+                else:
+                    words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs)
                 ids.append(words)
                 logp.append(lp)
             ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)
@@ -425,9 +449,10 @@ def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temp
 
 
 def sample_random(dec, step_fn, state, n, m, start_token, end_token, temperature=1.0, top_k=0, seed=None, top_p=1.0, device=False,
-                  greedy=False):
+                  greedy=False, exclude=None):
     """The lists of sample_random_device; device=True: all it returns (lists, ids, logp)."""
-    out = sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temperature, top_k, seed, top_p, greedy)
+    ex = {} if exclude is None else {"exclude": exclude}      # None: the call as it was before there was an exclude
+    out = sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temperature, top_k, seed, top_p, greedy, **ex)
     return out if device else out[0]
 
 

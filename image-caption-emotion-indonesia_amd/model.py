@@ -659,7 +659,7 @@ class DecoderFactoredLSTM(nn.Module):
                            nbest=nbest, length_penalty=length_penalty, constraints=constraints, diversity=diversity)
 
     def sample_random(self, features, start_token, end_token, samples=1, temperature=1.0, top_k=0, seed=None, mode='factual',
-                      top_p=1.0, device=False, greedy=False):
+                      top_p=1.0, device=False, greedy=False, exclude=None):
         """`samples` captions per row of `features`, DRAWN from the decoder's distribution softmax(logits / temperature)
         (top_k > 0: renormalised over the top_k best words of every step;
         top_p < 1: over the nucleus) instead of searched for: a list of n lists of
@@ -671,10 +671,13 @@ class DecoderFactoredLSTM(nn.Module):
         greedy=True: every image's pairs are followed by one more, its greedy caption (the argmax of every step), decoded as
         one more row of the same call; the first `samples` pairs are those of the call without it.
         device=True: (the lists, ids, logp), the decode's raw rows [n samples, max_seq_length] left on the device
-        (capnet.decode.sample_random_device)."""
+        (capnet.decode.sample_random_device).
+        exclude (a capnet.beam.Constraints without forced words): what no caption may draw -- a repeated n-gram, <end> within
+        min_words, banned words -- excluded words being not pickable and logprob that of the distribution renormalised over
+        the allowed words (capnet.decode.sample_random_device); None: the call as it was."""
         n = features.size(0)
         return sample_random(self, *self._beam(n * (int(samples) + bool(greedy)), mode, True), n, samples, start_token, end_token, temperature,
-                             top_k, seed, top_p, device, greedy)
+                             top_k, seed, top_p, device, greedy, exclude)
 
     def score_captions(self, features, captions, mode='factual'):
         """float32 [len(captions)] on the device: the model's log-probability of every caption [start, w_1 .. w_j], summed over

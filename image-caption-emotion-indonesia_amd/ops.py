@@ -934,11 +934,13 @@ def vocab_topk_workspace(rows, k, V, device):
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
-def vocab_topk(h, w, b=None, k=5, workspace=None):
+def vocab_topk(h, w, b=None, k=5, workspace=None, mask=None):
     """(values [rows, k] float32, index [rows, k] int32, lse [rows] float32) of the rows' logits h[r] . w[v] + b[v]
     (capnet_vocab_topk: the projection, the k best per row -- logit descending, index ascending -- and the row's
     log-sum-exp in one launch, no logits in memory). h [rows, H], w [V, H], b [V]; H in DECODE_HIDDEN; 1 <= k <= 16, k <= V.
-    A NaN or -inf logit is never picked; a row with fewer than k pickable entries ends in (-inf, -1)."""
+    A NaN or -inf logit is never picked; a row with fewer than k pickable entries ends in (-inf, -1).
+    mask (sample_exclusion_mask's, int32 [rows, ceil(V / 32)]; capnet_vocab_topk_masked): a word whose bit is set is not
+    pickable either -- the k best of the allowed words, lse over the allowed words. None: capnet_vocab_topk."""
     _need_cuda(h, w, b)
     h, w = _c(h.detach()), _c(w.detach())
     b = None if b is None else _c(b.detach())
@@ -958,6 +960,11 @@ def vocab_topk(h, w, b=None, k=5, workspace=None):
     values = torch.empty((rows, k), dtype=torch.float32, device=h.device)
     index = torch.empty((rows, k), dtype=torch.int32, device=h.device)
     lse = torch.empty(rows, dtype=torch.float32, device=h.device)
+    if mask is not None:
+        mask = _check_mask("vocab_topk", mask, rows, V)
+        check(_lib.lib().capnet_vocab_topk_masked(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(mask), ptr(workspace), ptr(values),
+                                                  ptr(index), ptr(lse), current_stream()), "capnet_vocab_topk_masked")
+        return values, index, lse
     check(_lib.lib().capnet_vocab_topk(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(workspace), ptr(values), ptr(index), ptr(lse),
                                        current_stream()), "capnet_vocab_topk")
     return values, index, lse
@@ -1041,20 +1048,89 @@ def _call_sampler(name, greedy_stride, *args):
     check(getattr(_lib.lib(), "capnet_" + name)(*(args + (current_stream(),))), "capnet_" + name)
 
 
+# ---- exclusions of a sampled decode (csrc/sample_exclude.hip) ----
+def mask_words(V):
+    """W of the exclusion mask [rows, W]: one bit per word of the vocabulary, 32 to an int32."""
+    return (int(V) + 31) // 32
+
+
+def _check_mask(who, mask, rows, V):
+    _need_cuda(mask)
+    if mask.dtype != torch.int32 or tuple(mask.shape) != (rows, mask_words(V)) or not mask.is_contiguous():
+        raise CapnetError("%s: mask must be a contiguous int32 [rows, ceil(V / 32)] = [%d, %d] tensor" % (who, rows, mask_words(V)))
+    return mask
+
+
+def sample_exclusion_mask(ids, start_tokens, t, V, end_token, constraints, out=None):
+    """The exclusion mask of stream step `t` (0-based) of a sampled decode (capnet_sample_exclusion_mask): int32 [rows, ceil(V
+    / 32)], bit v & 31 of word v >> 5 of row r set where capnet.beam.banned_words([start_tokens[r]] + ids[r, :t], t + 1,
+    end_token, constraints) holds v. ids int64 [rows, steps] with unit column stride (columns from t on are not read);
+    start_tokens int64 [rows] or None (the hypotheses are then the words alone); constraints a capnet.beam.Constraints without
+    forced words. out: a mask to overwrite."""
+    who = "sample_exclusion_mask"
+    _need_cuda(ids, start_tokens)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1 or (ids.shape[1] > 1 and ids.stride(1) != 1):
+        raise CapnetError("%s: ids must be int64 [rows, steps] with unit column stride" % who)
+    rows, steps = ids.shape
+    ld = ids.stride(0) if rows > 1 else max(steps, ids.stride(0))
+    if start_tokens is not None:
+        start_tokens = _c(start_tokens)
+        if start_tokens.dtype != torch.int64 or start_tokens.numel() != rows:
+            raise CapnetError("%s: start_tokens must be int64 [rows]" % who)
+    if has_forced(constraints):
+        raise CapnetError("%s: forced words have no meaning for a draw" % who)
+    t, V = int(t), int(V)
+    if not 0 <= t <= steps or not 1 <= steps <= SAMPLE_MAX_STEPS or not 1 <= V <= SAMPLE_MAX_ROWS or ld < steps:
+        raise CapnetError("%s: t %d of %d steps (ld %d), V %d" % (who, t, steps, ld, V))
+    if out is None:
+        out = torch.empty((rows, mask_words(V)), dtype=torch.int32, device=ids.device)
+    _check_mask(who, out, rows, V)
+    check(_lib.lib().capnet_sample_exclusion_mask(ptr(ids), ld, steps, ptr(start_tokens), rows, t, V, int(end_token),
+                                                  *constraint_args(constraints, ids.device), ptr(out), current_stream()),
+          "capnet_sample_exclusion_mask")
+    return out
+
+
+def mask_logits(logits, mask):
+    """-inf IN PLACE at the mask's set bits of logits float32 [rows, V] (unit column stride; capnet_mask_logits) -> logits: what
+    sample_rows, nucleus_rows and a torch.topk in front of the picks then treat as not pickable."""
+    _need_cuda(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 \
+            or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise CapnetError("mask_logits: logits float32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    mask = _check_mask("mask_logits", mask, rows, V)
+    check(_lib.lib().capnet_mask_logits(ptr(logits), rows, logits.stride(0) if rows > 1 else V, V, ptr(mask), current_stream()),
+          "capnet_mask_logits")
+    return logits
+
+
+def _exclude_args(who, exclude, end_token, device):
+    """The five trailing arguments of the capnet_*_excl entries in front of the stream: end_token and constraint_args."""
+    if has_forced(exclude):
+        raise CapnetError("%s: forced words have no meaning for a draw" % who)
+    if end_token is None:
+        raise CapnetError("%s: exclude needs end_token" % who)
+    return (int(end_token),) + constraint_args(exclude, device)
+
+
 def vocab_sample_workspace(rows, V, device):
     """A zeroed workspace of capnet_vocab_sample for `rows` rows (back-to-back calls on one stream may share it)."""
     n = _lib.lib().capnet_vocab_sample_ws_bytes(int(rows), int(V))
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
-def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspace=None, greedy_stride=0):
+def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspace=None, greedy_stride=0, mask=None):
     """(tokens [rows] int64, logp [rows] float32): per row a draw from softmax((h[r] . w + b) / temperature) and its
     log-probability (capnet_vocab_sample: projection, Gumbel noise and argmax in one launch, no logits in memory). The noise
     of row r and entry v is a function of (seed, step, row0 + r, v) alone (sample_uniform). h [rows, H], w [V, H], b [V]; H
     in DECODE_HIDDEN. A NaN or -inf logit is never drawn; a row with nothing to draw gives (0, -inf).
     greedy_stride g > 0 (here and in sample_pick, sample_rows, nucleus_rows, nucleus_pick): the physical rows row0 + r come
     in groups of g; the last of a group is its greedy row -- no noise: the argmax, ties to the lower index, logp under the
-    same distribution -- and row i g + j before it draws on noise row i (g - 1) + j, as in the call without greedy rows."""
+    same distribution -- and row i g + j before it draws on noise row i (g - 1) + j, as in the call without greedy rows.
+    mask (sample_exclusion_mask's; capnet_vocab_sample_masked): a word whose bit is set on the row is never drawn and adds
+    nothing to the sum under logp -- the draw from the distribution renormalised over the allowed words; None: the calls as
+    they were."""
     temperature, _, seed = check_sampling("vocab_sample", temperature, 0, seed)
     greedy_stride = _check_greedy_stride("vocab_sample", greedy_stride)
     _need_cuda(h, w, b)
@@ -1073,6 +1149,12 @@ def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspac
         raise CapnetError("vocab_sample: workspace too small")
     tokens = torch.empty(rows, dtype=torch.int64, device=h.device)
     logp = torch.empty(rows, dtype=torch.float32, device=h.device)
+    if mask is not None:
+        mask = _check_mask("vocab_sample", mask, rows, V)
+        check(_lib.lib().capnet_vocab_sample_masked(ptr(h), ptr(w), ptr(b), rows, H, V, temperature, seed, step, row0, ptr(mask),
+                                                    ptr(workspace), ptr(tokens), ptr(logp), greedy_stride, current_stream()),
+              "capnet_vocab_sample_masked")
+        return tokens, logp
     _call_sampler("vocab_sample", greedy_stride, ptr(h), ptr(w), ptr(b), rows, H, V, temperature, seed, step, row0, ptr(workspace),
                   ptr(tokens), ptr(logp))
     return tokens, logp
@@ -1174,7 +1256,7 @@ def vocab_topk_supported(H, k, V):
 
 
 def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed, first_inputs=None, start_tokens=None,
-                  state=None, top_p=1.0, greedy_stride=0):
+                  state=None, top_p=1.0, greedy_stride=0, exclude=None, end_token=None):
     """`steps` sampled decode steps of a plain stack in ONE C call (capnet_sample_decode): per step one decode-step launch
     per layer and the draw (top_k == 0: capnet_vocab_sample; else capnet_vocab_topk + capnet_sample_pick), tokens and logits
     never leaving the device. wcat / beff: capnet.decode.pack_cell(s) of every layer; emb [V, E]; Cw [V, H], Cb [V] or None.
@@ -1183,6 +1265,9 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
     the projection into a logits block + capnet_nucleus_rows, or capnet_vocab_topk + capnet_nucleus_pick); top_p == 1.0 is
     capnet_sample_decode. greedy_stride g > 0 (vocab_sample's; rows a multiple of g): every g-th row decodes greedily, the
     others draw what they draw in the call of g - 1 rows per group without it (the capnet_*_greedy entries).
+    exclude (a capnet.beam.Constraints without forced words, with end_token; needs start_tokens): capnet_sample_decode_excl --
+    per step one more launch builds the rows' exclusion mask (sample_exclusion_mask's rule on the ids so far) and the draw
+    reads it; None: the calls as they were.
     Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state [rows, 2L, H])."""
     who = "sample_decode"
     if (first_inputs is None) == (start_tokens is None):
@@ -1206,13 +1291,26 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
         raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, top_k=%d)" % (who, E, H, V, nl, top_k))
     dev = emb.device
     L = _lib.lib()
-    nbytes = (L.capnet_sample_decode_nucleus_ws_bytes if top_p < 1.0 else L.capnet_sample_decode_ws_bytes)(nl, rows, H, V, top_k)
+    if exclude is not None:
+        if start_tokens is None:
+            raise CapnetError("%s: exclude needs start_tokens" % who)
+        excl = _exclude_args(who, exclude, end_token, dev)
+        nbytes = L.capnet_sample_decode_excl_ws_bytes(nl, rows, H, V, top_k, top_p)
+    else:
+        nbytes = (L.capnet_sample_decode_nucleus_ws_bytes if top_p < 1.0 else L.capnet_sample_decode_ws_bytes)(nl, rows, H, V, top_k)
     if not nbytes:
         raise CapnetError("%s: unsupported shape (rows=%d, V=%d, top_k=%d)" % (who, rows, V, top_k))
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
     ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
     out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
+    if exclude is not None:
+        slab = splitk_slab(dev)
+        check(L.capnet_sample_decode_excl(cell, nl, rows, E, H, V, steps, None, ptr(start_tokens), ptr(emb), ptr_array(wcat),
+                                          ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, top_p, seed, ptr(ws),
+                                          ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out), ptr(err_flag(dev)), greedy_stride,
+                                          *excl, current_stream()), "capnet_sample_decode_excl")
+        return ids, logp, out
     if top_p < 1.0:
         slab = splitk_slab(dev)
         _call_sampler("sample_decode_nucleus", greedy_stride, cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens),
@@ -1707,14 +1805,15 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
 
 
 def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state, m, steps, start_token,
-                      temperature, top_k, seed, top_p=1.0, greedy=False):
+                      temperature, top_k, seed, top_p=1.0, greedy=False, exclude=None, end_token=None):
     """`steps` sampled decode steps of an attention decoder in ONE C call (capnet_att_sample_decode; top_p < 1:
     capnet_att_sample_decode_nucleus, the draw as ops.sample_decode's): n images x m samples
     each (row i m + j = sample j of image i), the step att_decode_step's with k = m and every row continuing from itself --
     an image's maps are read once per step for all its samples -- then the draw as ops.sample_decode's. Operands as
     att_beam_decode; state [n m, 2L, H]: the initial state. Returns (ids [n m, steps] int64, logp [n m, steps] float32).
     greedy: the last of an image's m rows decodes greedily (greedy_stride = m, ops.vocab_sample's) and the m - 1 before it draw
-    what the call with m - 1 rows per image draws: the greedy caption on the same read of the maps. m <= 16 either way."""
+    what the call with m - 1 rows per image draws: the greedy caption on the same read of the maps. m <= 16 either way.
+    exclude / end_token: ops.sample_decode's (capnet_att_sample_decode_excl); None: the calls as they were."""
     who = "att_sample_decode"
     att1, feat, emb, wz, bz, wf, bf, state, (n, P, A, Cdim, E, H, V, nl) = _att_decode_args(
         who, cell, att1, feat, m, emb, wz, bz, w_full, b_full, wcat, beff, state)
@@ -1728,8 +1827,12 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
     dev, rows = emb.device, n * m
     L = _lib.lib()
     nucleus = top_p < 1.0
-    nbytes = (L.capnet_att_sample_decode_nucleus_ws_bytes if nucleus else L.capnet_att_sample_decode_ws_bytes)(
-        nl, n, m, P, A, Cdim, E, H, V, top_k)
+    if exclude is not None:
+        excl = _exclude_args(who, exclude, end_token, dev)
+        nbytes = L.capnet_att_sample_decode_excl_ws_bytes(nl, n, m, P, A, Cdim, E, H, V, top_k, top_p)
+    else:
+        nbytes = (L.capnet_att_sample_decode_nucleus_ws_bytes if nucleus else L.capnet_att_sample_decode_ws_bytes)(
+            nl, n, m, P, A, Cdim, E, H, V, top_k)
     if not nbytes:
         raise CapnetError("%s: unsupported shape (n=%d, m=%d, V=%d, top_k=%d)" % (who, n, m, V, top_k))
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
@@ -1741,7 +1844,9 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
             ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k)
     tail = (seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None, ptr(err_flag(dev)))
     stride = m if greedy else 0
-    if nucleus:
+    if exclude is not None:
+        check(L.capnet_att_sample_decode_excl(*head, top_p, *tail, stride, *excl, current_stream()), "capnet_att_sample_decode_excl")
+    elif nucleus:
         _call_sampler("att_sample_decode_nucleus", stride, *head, top_p, *tail)
     else:
         _call_sampler("att_sample_decode", stride, *head, *tail)

@@ -159,7 +159,7 @@ def mean_baseline(rewards):
 
 
 def self_critical_step(decoder, optimizer, features, reward, start_token, end_token, grad_clip, samples=5, baseline='greedy',
-                       mode=None, temperature=1.0, top_k=0, top_p=1.0, seed=None, loss_scale=None):
+                       mode=None, temperature=1.0, top_k=0, top_p=1.0, seed=None, loss_scale=None, exclude=None):
     """One step of self-critical sequence training (Rennie et al., 2017): draw `samples` captions per image with
     decoder.sample_random, score them on the host with reward(image_index, tokens) -> float, subtract a baseline and take
     policy_step on the advantages.
@@ -169,6 +169,11 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     temperature / top_k / top_p / seed are sample_random's and only shape the exploration: the gradient is always that of
     the model's own, untempered and untruncated log-probability of the drawn captions (policy_step), not of the
     distribution they were drawn from.
+    exclude (a capnet.beam.Constraints without forced words; None: the step as it was) is sample_random's too and shapes the
+    exploration in the same sense: no drawn caption repeats an n-gram, ends within min_words or holds a banned word, and the
+    step scores none that does. The greedy baseline obeys it as well: the greedy row of the one decode on the device route,
+    decoder.sample_batch(k=1, constraints=exclude) on the host route -- a width-1 beam under the same exclusions is the argmax
+    over the allowed words, the same caption.
     features: as policy_step's. Returns {'loss': the device loss, 'reward_mean', 'baseline_mean', 'advantage_abs_mean':
     floats over all samples, 'zero_rows': the captions whose advantage is exactly 0 (under 'greedy': the samples that
     scored what the greedy caption did, the greedy caption itself among them)}.
@@ -187,10 +192,11 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     if baseline == "mean" and int(samples) < 2:
         raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
     kw = {} if mode is None else {"mode": mode}
+    ex, con = ({}, {}) if exclude is None else ({"exclude": exclude}, {"constraints": exclude})
     if isinstance(reward, (DeviceBleuReward, DeviceCiderReward)):
         m, greedy = int(samples), baseline == "greedy"
         drawn, ids, _ = decoder.sample_random(features, start_token, end_token, samples=m, temperature=temperature, top_k=top_k,
-                                              seed=seed, top_p=top_p, device=True, greedy=greedy, **kw)
+                                              seed=seed, top_p=top_p, device=True, greedy=greedy, **kw, **ex)
         r = reward.rows(ids, start_token, end_token, m + greedy)[0].double().view(-1, m + greedy)
         if greedy:
             drawn, base, r = [row[:m] for row in drawn], r[:, m:].expand(-1, m), r[:, :m]
@@ -202,12 +208,12 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
         return {"loss": loss, "reward_mean": r.mean(), "baseline_mean": base.mean(), "advantage_abs_mean": adv.abs().mean(),
                 "zero_rows": (adv == 0).sum()}
     drawn = decoder.sample_random(features, start_token, end_token, samples=samples, temperature=temperature, top_k=top_k,
-                                  seed=seed, top_p=top_p, **kw)
+                                  seed=seed, top_p=top_p, **kw, **ex)
     rewards = [[float(reward(i, tokens)) for tokens, _ in row] for i, row in enumerate(drawn)]
     if baseline == "mean":
         base = mean_baseline(rewards)
     else:
-        greedy = decoder.sample_batch(features, start_token, end_token, k=1, **kw)
+        greedy = decoder.sample_batch(features, start_token, end_token, k=1, **kw, **con)
         base = [[float(reward(i, [int(w) for w in g]))] * len(rewards[i]) for i, g in enumerate(greedy)]
     adv = [r - b for rr, bb in zip(rewards, base) for r, b in zip(rr, bb)]
     loss, _ = policy_step(decoder, optimizer, features, drawn, adv, grad_clip, mode=mode, loss_scale=loss_scale)

@@ -849,6 +849,60 @@ int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m,
                                             size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                                             unsigned greedy_stride, capnet_stream_t stream);
 
+/* Sampled decoding with exclusions (csrc/sample_exclude.hip): words a row may not draw at a step -- no repeated n-gram, a
+ * minimum length, banned words; the rule of capnet_beam_advance_constrained, its four trailing arguments in the same order
+ * (no_repeat_ngram 0..4, min_words >= 0, banned: a DEVICE int32 array of n_banned <= 32 word ids, 4-byte aligned). Unlike in
+ * the beam search an excluded word is treated as a -inf logit is: never drawn, never a top-k candidate, never in the
+ * nucleus, and it adds nothing to any sum, so logp is that of the distribution renormalised over the allowed words.
+ * The mask: unsigned [rows][W], W = ceil(V / 32); bit v & 31 of word v >> 5 of row r set = word v is excluded on launch row r.
+ *
+ * capnet_sample_exclusion_mask: the mask of stream step t (0-based, 0 <= t <= steps) of a decode whose ids are
+ * [rows] x ld int64 (ld >= steps; words 0 .. t - 1 of a row are read; ids may be NULL at t = 0): row r is the hypothesis
+ * [start_tokens[r], ids[r][0] .. ids[r][t - 1]] at step t + 1 (start_tokens NULL: the words alone), the tokens as drawn
+ * whether or not the row has emitted end_token. Excluded: every banned word; end_token while t + 1 <= min_words; with g =
+ * no_repeat_ngram >= 1 and at least g tokens, every word that would complete a g-gram the hypothesis already contains
+ * (<start> counts; a context seen several times excludes several words). Every word of the mask is written.
+ * capnet_mask_logits: -inf at the mask's set bits of logits [rows][ld] (ld >= V), for the draws that read logits from memory
+ * (capnet_sample_rows, capnet_nucleus_rows, a top-k in front of capnet_sample_pick / capnet_nucleus_pick).
+ * capnet_vocab_sample_masked: capnet_vocab_sample_greedy (greedy_stride 0: capnet_vocab_sample) under a mask, which is required.
+ * A row with every word excluded gives token 0 and logp -inf.
+ * capnet_vocab_topk_masked: capnet_vocab_topk under a mask: the k best of the ALLOWED entries, and lse is the log-sum-exp
+ * over the allowed entries only.
+ * All refuse bad arguments on the host before any launch (the offending name in capnet_last_error()). */
+int capnet_sample_exclusion_mask(const long long* ids, long ld, int steps, const long long* start_tokens, int rows, int t, int V,
+                                 long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                 unsigned* mask, capnet_stream_t stream);
+int capnet_mask_logits(float* logits, int rows, long ld, int V, const unsigned* mask, capnet_stream_t stream);
+int capnet_vocab_sample_masked(const float* h, const float* w, const float* b, int rows, int H, int V, float temperature,
+                               unsigned long long seed, unsigned step, unsigned row0, const unsigned* mask, void* workspace,
+                               long long* tokens, float* logp, unsigned greedy_stride, capnet_stream_t stream);
+int capnet_vocab_topk_masked(const float* h, const float* w, const float* b, int rows, int H, int V, int k, const unsigned* mask,
+                             void* workspace, float* values, int* index, float* lse, capnet_stream_t stream);
+
+/* The sampling loops under exclusions, ONE pair that takes everything: capnet_sample_decode[_nucleus][_greedy] (top_p == 1:
+ * the plain draws; greedy_stride 0: no greedy rows) with one more launch per step, capnet_sample_exclusion_mask on the
+ * caller's ids and start_tokens (required), and the step's draw under that mask; the decode step is untouched. slab is needed
+ * only where top_p < 1 and top_k == 0. workspace: capnet_[att_]sample_decode_excl_ws_bytes (the loop's own bytes, then the
+ * mask: rows W 4 bytes, 16-B aligned; 0: unsupported). The other arguments are those of the entries they extend. */
+size_t capnet_sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, float top_p);
+int capnet_sample_decode_excl(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float temperature,
+                              int top_k, float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                              long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                              long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                              capnet_stream_t stream);
+size_t capnet_att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k,
+                                              float top_p);
+int capnet_att_sample_decode_excl(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                  const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, float temperature, int top_k, float top_p, unsigned long long seed,
+                                  void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                  float* state_out, int* err_flag, unsigned greedy_stride, long long end_token,
+                                  int no_repeat_ngram, int min_words, const int* banned, int n_banned, capnet_stream_t stream);
+
 /* capnet_vocab_topk for `groups` projections in one launch: rows = groups x rows_per_group, group-major, and group g's rows
  * are projected on w[g] [V][H] / b[g] [V] (w, b: HOST arrays of `groups` device pointers; b or any b[g] may be NULL; every
  * w[g] 16-B aligned; V the same for all groups). The grid is (ceil(V / 32), groups); each group has its own arrival counter
