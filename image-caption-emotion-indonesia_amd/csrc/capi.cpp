@@ -705,170 +705,112 @@ int capnet_vocab_sample_greedy(const float* h, const float* w, const float* b, i
                            greedy_stride);
 }
 
-static int sample_pick_tail(const float* values, const int* index, int rows, int k, int V, float temperature,
-                            unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                            capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("sample_pick", 0, greedy_stride, 0)) return rc;
-  float inv_T = 0.f;
-  if (int rc = sample_check("sample_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
-  CAPNET_REQUIRE(k >= 1 && k <= 16, "sample_pick: k=%d (1 <= k <= 16)", k);
-  CAPNET_REQUIRE(values && index && tokens && logp, "sample_pick: null argument");
-  CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
-                 "sample_pick: alignment");
-  return sample_pick(values, index, rows, k, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
-}
-int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature,
-                       unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                       capnet_stream_t stream) {
-  return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, 0);
-}
-int capnet_sample_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature,
-                              unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                              unsigned greedy_stride, capnet_stream_t stream) {
-  return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
-}
-
-static int sample_rows_tail(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
-                            unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream,
-                            unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("sample_rows", 0, greedy_stride, 0)) return rc;
-  float inv_T = 0.f;
-  if (int rc = sample_check("sample_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
-  CAPNET_REQUIRE(ld >= V, "sample_rows: ld %ld < V %d", ld, V);
-  CAPNET_REQUIRE(logits && tokens && logp, "sample_rows: null argument");
-  CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "sample_rows: alignment");
-  return sample_rows(logits, rows, ld, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
-}
-int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
-                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
-  return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, 0);
-}
-int capnet_sample_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
-                              unsigned step, unsigned row0, long long* tokens, float* logp, unsigned greedy_stride,
-                              capnet_stream_t stream) {
-  return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
-}
-
-size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
-  if (nlayers < 1 || nlayers > 8 || rows < 1 || rows >= (1 << 24) || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
-  return sample_decode_ws_bytes(nlayers, rows, H, V, top_k);
-}
-
-static int sample_decode_tail(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                              const long long* start_tokens, const float* emb, const float* const* wcat,
-                              const float* const* beff, const float* Cw, const float* Cb, const float* state0,
-                              float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
-                              float* logp, float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("sample_decode", rows, greedy_stride, 0)) return rc;
-  float inv_T = 0.f;
-  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "sample_decode: steps %d (1..65535)", steps);
-  if (int rc = sample_check("sample_decode", rows, V, temperature, 0, 0, &inv_T)) return rc;
-  CAPNET_REQUIRE(cell == kCellFactored || cell == kCellLSTM, "sample_decode: unknown cell %d", cell);
-  CAPNET_REQUIRE(nlayers >= 1 && nlayers <= 8, "sample_decode: layers %d (1..8)", nlayers);
-  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_decode: top_k=%d (0 = off, 1 .. 16, <= V = %d)", top_k, V);
-  CAPNET_REQUIRE(stacked_decode_supported(E, H) && vocab_sample_supported(H), "sample_decode: unsupported E=%d H=%d", E, H);
-  CAPNET_REQUIRE((first_inputs != nullptr) != (start_tokens != nullptr),
-                 "sample_decode: the first input is either first_inputs or start_tokens");
-  CAPNET_REQUIRE(emb && wcat && beff && Cw && workspace && ids && logp && err_flag, "sample_decode: null argument");
-  CAPNET_REQUIRE(aligned16(workspace) && aligned16(Cw) && (!state0 || aligned16(state0)) && (!state_out || aligned16(state_out)),
-                 "sample_decode: workspace, Cw and the states must be 16-B aligned");
-  CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "sample_decode: ids / logp alignment");
-  if (int rc = layer_weights_check("sample_decode", nlayers, wcat, beff)) return rc;
-  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
-                       top_k, 1.f, seed, workspace, nullptr, 0, ids, logp, state_out, err_flag, S(stream), greedy_stride);
-}
-int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
-                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out,
-                         int* err_flag, capnet_stream_t stream) {
-  return sample_decode_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
-                            temperature, top_k, seed, workspace, ids, logp, state_out, err_flag, stream, 0);
-}
-int capnet_sample_decode_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                                const long long* start_tokens, const float* emb, const float* const* wcat,
-                                const float* const* beff, const float* Cw, const float* Cb, const float* state0,
-                                float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
-                                float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
-                                capnet_stream_t stream) {
-  return sample_decode_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
-                            temperature, top_k, seed, workspace, ids, logp, state_out, err_flag, stream, greedy_stride);
-}
-
-// ---- nucleus (top-p) sampling (vocab_nucleus.hip) ----
-// top_p == 1 is "off": the stand-alone draws forward to the plain ones, the loops leave it to the plain loops
+// nucleus (top-p) sampling (vocab_nucleus.hip): top_p == 1 is "off" -- the stand-alone draws then ARE the plain ones and
+// report under their names, the _nucleus loops leave it to the plain loops (allow_one false)
 static int top_p_check(const char* who, float top_p, bool allow_one) {
   CAPNET_REQUIRE(top_p > 0.f && (top_p < 1.f || (allow_one && top_p == 1.f)), "%s: top_p %g (0 < top_p %s 1)", who, (double)top_p,
                  allow_one ? "<=" : "<");
   return kOk;
 }
 
-static int nucleus_rows_tail(const float* logits, int rows, long ld, int V, float temperature, float top_p,
-                             unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                             capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("nucleus_rows", 0, greedy_stride, 0)) return rc;
-  if (int rc = top_p_check("nucleus_rows", top_p, true)) return rc;
-  if (top_p == 1.f) return sample_rows_tail(logits, rows, ld, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
+// capnet_sample_pick* (who "sample_pick", top_p 1) and capnet_nucleus_pick* (who "nucleus_pick")
+static int pick_tail(const char* who, const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
+                     unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream,
+                     unsigned greedy_stride) {
+  if (int rc = greedy_stride_check(who, 0, greedy_stride, 0)) return rc;
+  if (int rc = top_p_check(who, top_p, true)) return rc;
+  if (top_p == 1.f) who = "sample_pick";
   float inv_T = 0.f;
-  if (int rc = sample_check("nucleus_rows", rows, V, temperature, step, row0, &inv_T)) return rc;
-  CAPNET_REQUIRE(ld >= V, "nucleus_rows: ld %ld < V %d", ld, V);
-  CAPNET_REQUIRE(logits && tokens && logp, "nucleus_rows: null argument");
-  CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "nucleus_rows: alignment");
-  return nucleus_rows(logits, rows, ld, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
-}
-int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p,
-                        unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                        capnet_stream_t stream) {
-  return nucleus_rows_tail(logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
-}
-int capnet_nucleus_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, float top_p,
-                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                               unsigned greedy_stride, capnet_stream_t stream) {
-  return nucleus_rows_tail(logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, greedy_stride);
-}
-
-static int nucleus_pick_tail(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
-                             unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
-                             capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("nucleus_pick", 0, greedy_stride, 0)) return rc;
-  if (int rc = top_p_check("nucleus_pick", top_p, true)) return rc;
-  if (top_p == 1.f) return sample_pick_tail(values, index, rows, k, V, temperature, seed, step, row0, tokens, logp, stream, greedy_stride);
-  float inv_T = 0.f;
-  if (int rc = sample_check("nucleus_pick", rows, V, temperature, step, row0, &inv_T)) return rc;
-  CAPNET_REQUIRE(k >= 1 && k <= 16, "nucleus_pick: k=%d (1 <= k <= 16)", k);
-  CAPNET_REQUIRE(values && index && tokens && logp, "nucleus_pick: null argument");
+  if (int rc = sample_check(who, rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(k >= 1 && k <= 16, "%s: k=%d (1 <= k <= 16)", who, k);
+  CAPNET_REQUIRE(values && index && tokens && logp, "%s: null argument", who);
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0,
-                 "nucleus_pick: alignment");
+                 "%s: alignment", who);
+  if (top_p == 1.f) return sample_pick(values, index, rows, k, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
   return nucleus_pick(values, index, rows, k, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_sample_pick(const float* values, const int* index, int rows, int k, int V, float temperature,
+                       unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                       capnet_stream_t stream) {
+  return pick_tail("sample_pick", values, index, rows, k, V, temperature, 1.f, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_sample_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature,
+                              unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                              unsigned greedy_stride, capnet_stream_t stream) {
+  return pick_tail("sample_pick", values, index, rows, k, V, temperature, 1.f, seed, step, row0, tokens, logp, stream, greedy_stride);
 }
 int capnet_nucleus_pick(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
                         unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
                         capnet_stream_t stream) {
-  return nucleus_pick_tail(values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
+  return pick_tail("nucleus_pick", values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
 }
 int capnet_nucleus_pick_greedy(const float* values, const int* index, int rows, int k, int V, float temperature, float top_p,
                                unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
                                unsigned greedy_stride, capnet_stream_t stream) {
-  return nucleus_pick_tail(values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream,
-                           greedy_stride);
+  return pick_tail("nucleus_pick", values, index, rows, k, V, temperature, top_p, seed, step, row0, tokens, logp, stream, greedy_stride);
 }
 
+// capnet_sample_rows* (who "sample_rows", top_p 1) and capnet_nucleus_rows* (who "nucleus_rows")
+static int rows_tail(const char* who, const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                     unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream,
+                     unsigned greedy_stride) {
+  if (int rc = greedy_stride_check(who, 0, greedy_stride, 0)) return rc;
+  if (int rc = top_p_check(who, top_p, true)) return rc;
+  if (top_p == 1.f) who = "sample_rows";
+  float inv_T = 0.f;
+  if (int rc = sample_check(who, rows, V, temperature, step, row0, &inv_T)) return rc;
+  CAPNET_REQUIRE(ld >= V, "%s: ld %ld < V %d", who, ld, V);
+  CAPNET_REQUIRE(logits && tokens && logp, "%s: null argument", who);
+  CAPNET_REQUIRE((size_t)logits % 4 == 0 && (size_t)tokens % 8 == 0 && (size_t)logp % 4 == 0, "%s: alignment", who);
+  if (top_p == 1.f) return sample_rows(logits, rows, ld, V, inv_T, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+  return nucleus_rows(logits, rows, ld, V, inv_T, top_p, seed, step, row0, tokens, nullptr, logp, 1, S(stream), greedy_stride);
+}
+int capnet_sample_rows(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                       unsigned step, unsigned row0, long long* tokens, float* logp, capnet_stream_t stream) {
+  return rows_tail("sample_rows", logits, rows, ld, V, temperature, 1.f, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_sample_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, unsigned long long seed,
+                              unsigned step, unsigned row0, long long* tokens, float* logp, unsigned greedy_stride,
+                              capnet_stream_t stream) {
+  return rows_tail("sample_rows", logits, rows, ld, V, temperature, 1.f, seed, step, row0, tokens, logp, stream, greedy_stride);
+}
+int capnet_nucleus_rows(const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                        unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                        capnet_stream_t stream) {
+  return rows_tail("nucleus_rows", logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, 0);
+}
+int capnet_nucleus_rows_greedy(const float* logits, int rows, long ld, int V, float temperature, float top_p,
+                               unsigned long long seed, unsigned step, unsigned row0, long long* tokens, float* logp,
+                               unsigned greedy_stride, capnet_stream_t stream) {
+  return rows_tail("nucleus_rows", logits, rows, ld, V, temperature, top_p, seed, step, row0, tokens, logp, stream, greedy_stride);
+}
+
+// ---- the sampled decode of a plain stack in one call (decode_loops.hip) ----
+size_t capnet_sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
+  if (nlayers < 1 || nlayers > 8 || rows < 1 || rows >= (1 << 24) || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
+  return sample_decode_ws_bytes(nlayers, rows, H, V, top_k, false, false);
+}
 size_t capnet_sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
   if (!capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k)) return 0;
-  return sample_decode_nucleus_ws_bytes(nlayers, rows, H, V, top_k);
+  return sample_decode_ws_bytes(nlayers, rows, H, V, top_k, true, false);
+}
+size_t capnet_sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, float top_p) {
+  if (!capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k) || !(top_p > 0.f && top_p <= 1.f)) return 0;
+  return sample_decode_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f, true);
 }
 
-static int sample_decode_nucleus_tail(int cell, int nlayers, int rows, int E, int H, int V, int steps,
-                                      const float* first_inputs, const long long* start_tokens, const float* emb,
-                                      const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                                      const float* state0, float temperature, int top_k, float top_p,
-                                      unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
-                                      long long* ids, float* logp, float* state_out, int* err_flag, capnet_stream_t stream,
-                                      unsigned greedy_stride, const char* who = "sample_decode_nucleus",
-                                      const SampleExcl* ex = nullptr) {   // (ex: capnet_sample_decode_excl, top_p == 1 allowed)
+// every capnet_sample_decode* entry. top_p_one: whether the entry admits top_p == 1 (the plain entries pass 1, the _nucleus
+// entries leave it to them, the _excl entry takes both draws); ex: the _excl entry's exclusions, which need the start tokens
+static int sample_decode_entry(const char* who, int cell, int nlayers, int rows, int E, int H, int V, int steps,
+                               const float* first_inputs, const long long* start_tokens, const float* emb,
+                               const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                               const float* state0, float temperature, int top_k, float top_p, bool top_p_one,
+                               unsigned long long seed, void* workspace, float* slab, size_t slab_floats, long long* ids,
+                               float* logp, float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride,
+                               const SampleExcl* ex = nullptr) {
   if (int rc = greedy_stride_check(who, rows, greedy_stride, 0)) return rc;
   float inv_T = 0.f;
-  if (int rc = top_p_check(who, top_p, ex != nullptr)) return rc;
+  if (int rc = top_p_check(who, top_p, top_p_one)) return rc;
   if (ex) {
     if (int rc = sample_excl_check(who, *ex)) return rc;
     CAPNET_REQUIRE(start_tokens, "%s: start_tokens is required (the hypotheses begin with them)", who);
@@ -888,9 +830,28 @@ static int sample_decode_nucleus_tail(int cell, int nlayers, int rows, int E, in
                  "%s: workspace, Cw and the states must be 16-B aligned", who);
   CAPNET_REQUIRE((size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
   if (int rc = layer_weights_check(who, nlayers, wcat, beff)) return rc;
-  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0, inv_T,
-                               top_k, top_p, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag, S(stream), greedy_stride,
-                               ex);
+  return sample_decode(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
+                       SampleOpts{inv_T, top_k, top_p, seed, greedy_stride, ex}, workspace, slab, slab_floats, ids, logp, state_out,
+                       err_flag, S(stream));
+}
+int capnet_sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                         const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                         const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
+                         unsigned long long seed, void* workspace, long long* ids, float* logp, float* state_out,
+                         int* err_flag, capnet_stream_t stream) {
+  return sample_decode_entry("sample_decode", cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
+                             state0, temperature, top_k, 1.f, true, seed, workspace, nullptr, 0, ids, logp, state_out, err_flag, stream,
+                             0);
+}
+int capnet_sample_decode_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                                const long long* start_tokens, const float* emb, const float* const* wcat,
+                                const float* const* beff, const float* Cw, const float* Cb, const float* state0,
+                                float temperature, int top_k, unsigned long long seed, void* workspace, long long* ids,
+                                float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                                capnet_stream_t stream) {
+  return sample_decode_entry("sample_decode", cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
+                             state0, temperature, top_k, 1.f, true, seed, workspace, nullptr, 0, ids, logp, state_out, err_flag, stream,
+                             greedy_stride);
 }
 int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
                                  const long long* start_tokens, const float* emb, const float* const* wcat,
@@ -898,9 +859,9 @@ int capnet_sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, 
                                  float temperature, int top_k, float top_p, unsigned long long seed, void* workspace,
                                  float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out,
                                  int* err_flag, capnet_stream_t stream) {
-  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
-                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                    state_out, err_flag, stream, 0);
+  return sample_decode_entry("sample_decode_nucleus", cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff,
+                             Cw, Cb, state0, temperature, top_k, top_p, false, seed, workspace, slab, slab_floats, ids, logp,
+                             state_out, err_flag, stream, 0);
 }
 int capnet_sample_decode_nucleus_greedy(int cell, int nlayers, int rows, int E, int H, int V, int steps,
                                         const float* first_inputs, const long long* start_tokens, const float* emb,
@@ -909,12 +870,24 @@ int capnet_sample_decode_nucleus_greedy(int cell, int nlayers, int rows, int E, 
                                         unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
                                         long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
                                         capnet_stream_t stream) {
-  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
-                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                    state_out, err_flag, stream, greedy_stride);
+  return sample_decode_entry("sample_decode_nucleus", cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff,
+                             Cw, Cb, state0, temperature, top_k, top_p, false, seed, workspace, slab, slab_floats, ids, logp,
+                             state_out, err_flag, stream, greedy_stride);
+}
+int capnet_sample_decode_excl(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                              const long long* start_tokens, const float* emb, const float* const* wcat,
+                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float temperature,
+                              int top_k, float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
+                              long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
+                              long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                              capnet_stream_t stream) {
+  const SampleExcl ex{end_token, no_repeat_ngram, min_words, banned, n_banned, nullptr};
+  return sample_decode_entry("sample_decode_excl", cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw,
+                             Cb, state0, temperature, top_k, top_p, true, seed, workspace, slab, slab_floats, ids, logp, state_out,
+                             err_flag, stream, greedy_stride, &ex);
 }
 
-// ---- sampled decoding with exclusions (sample_exclude.hip) ----
+// ---- the exclusions' own entries (sample_exclude.hip) ----
 int capnet_sample_exclusion_mask(const long long* ids, long ld, int steps, const long long* start_tokens, int rows, int t, int V,
                                  long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
                                  unsigned* mask, capnet_stream_t stream) {
@@ -949,24 +922,6 @@ int capnet_vocab_topk_masked(const float* h, const float* w, const float* b, int
                              void* workspace, float* values, int* index, float* lse, capnet_stream_t stream) {
   CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "vocab_topk_masked: mask is null or not 4-byte aligned");
   return vocab_topk_tail(h, w, b, rows, H, V, k, workspace, values, index, lse, stream, mask);
-}
-
-size_t capnet_sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, float top_p) {
-  if (!capnet_sample_decode_ws_bytes(nlayers, rows, H, V, top_k) || !(top_p > 0.f && top_p <= 1.f)) return 0;
-  return sample_decode_excl_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f);
-}
-
-int capnet_sample_decode_excl(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                              const long long* start_tokens, const float* emb, const float* const* wcat,
-                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float temperature,
-                              int top_k, float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
-                              long long* ids, float* logp, float* state_out, int* err_flag, unsigned greedy_stride,
-                              long long end_token, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
-                              capnet_stream_t stream) {
-  const SampleExcl ex{end_token, no_repeat_ngram, min_words, banned, n_banned, nullptr};
-  return sample_decode_nucleus_tail(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb,
-                                    state0, temperature, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                    state_out, err_flag, stream, greedy_stride, "sample_decode_excl", &ex);
 }
 
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
@@ -1199,73 +1154,33 @@ int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int 
                                lengths, steps_run, err_flag, stream, false, nullptr);
 }
 
+// the three size queries of the attention sampler: 0 for arguments the entries refuse
+static size_t att_sample_ws_query(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus,
+                                  bool excl) {
+  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
+  return att_sample_decode_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, nucleus, excl);
+}
 size_t capnet_att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
-  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
-  return att_sample_decode_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
+  return att_sample_ws_query(nlayers, n, m, P, A, C, E, H, V, top_k, false, false);
 }
-
-static int att_sample_decode_tail(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                                  const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                                  const float* wz, const float* bz, const float* w_full, const float* b_full,
-                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                                  const float* state0, float temperature, int top_k, unsigned long long seed,
-                                  void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
-                                  float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride) {
-  if (int rc = greedy_stride_check("att_sample_decode", n * m, greedy_stride, m)) return rc;
-  if (int rc = att_decode_check("att_sample_decode", cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, emb, wz, bz, w_full, b_full,
-                                wcat, beff, workspace, slab, slab_floats, err_flag))
-    return rc;
-  float inv_T = 0.f;
-  CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "att_sample_decode: steps %d (1..65535)", steps);
-  if (int rc = sample_check("att_sample_decode", n * m, V, temperature, 0, 0, &inv_T)) return rc;
-  CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "att_sample_decode: top_k=%d (0 = off, 1 .. 16, <= V = %d)", top_k, V);
-  CAPNET_REQUIRE(vocab_sample_supported(H), "att_sample_decode: unsupported H=%d", H);
-  CAPNET_REQUIRE(start_tokens && Cw && state0 && ids && logp, "att_sample_decode: null argument (state0 is required)");
-  CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0) && (!state_out || aligned16(state_out)),
-                 "att_sample_decode: Cw and the states must be 16-B aligned");
-  CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "att_sample_decode: ids / logp alignment");
-  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
-                           beff, Cw, Cb, state0, inv_T, top_k, 1.f, seed, workspace, slab, slab_floats, ids, logp, state_out, err_flag,
-                           S(stream), greedy_stride);
-}
-int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                             const float* wz, const float* bz, const float* w_full, const float* b_full,
-                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
-                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                             capnet_stream_t stream) {
-  return att_sample_decode_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full,
-                                b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, seed, workspace, slab, slab_floats,
-                                ids, logp, state_out, err_flag, stream, 0);
-}
-int capnet_att_sample_decode_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                                    const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                                    const float* wz, const float* bz, const float* w_full, const float* b_full,
-                                    const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
-                                    const float* state0, float temperature, int top_k, unsigned long long seed,
-                                    void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
-                                    float* state_out, int* err_flag, unsigned greedy_stride, capnet_stream_t stream) {
-  return att_sample_decode_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full,
-                                b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, seed, workspace, slab, slab_floats,
-                                ids, logp, state_out, err_flag, stream, greedy_stride);
-}
-
 size_t capnet_att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
-  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V) return 0;
-  return att_sample_decode_nucleus_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k);
+  return att_sample_ws_query(nlayers, n, m, P, A, C, E, H, V, top_k, true, false);
+}
+size_t capnet_att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k,
+                                              float top_p) {
+  if (!(top_p > 0.f && top_p <= 1.f)) return 0;
+  return att_sample_ws_query(nlayers, n, m, P, A, C, E, H, V, top_k, top_p < 1.f, true);
 }
 
-static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
-                                          int steps, const long long* start_tokens, const float* att1, const float* feat,
-                                          const float* emb, const float* wz, const float* bz, const float* w_full,
-                                          const float* b_full, const float* const* wcat, const float* const* beff,
-                                          const float* Cw, const float* Cb, const float* state0, float temperature,
-                                          int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
-                                          size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                                          capnet_stream_t stream, unsigned greedy_stride,
-                                          const char* who = "att_sample_decode_nucleus",
-                                          const SampleExcl* ex = nullptr) {   // (ex: capnet_att_sample_decode_excl, top_p == 1 allowed)
+// every capnet_att_sample_decode* entry; top_p_one and ex as sample_decode_entry's (the start tokens are required anyway)
+static int att_sample_decode_entry(const char* who, int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
+                                   int steps, const long long* start_tokens, const float* att1, const float* feat,
+                                   const float* emb, const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                   const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                   const float* state0, float temperature, int top_k, float top_p, bool top_p_one,
+                                   unsigned long long seed, void* workspace, float* slab, size_t slab_floats, long long* ids,
+                                   float* logp, float* state_out, int* err_flag, capnet_stream_t stream, unsigned greedy_stride,
+                                   const SampleExcl* ex = nullptr) {
   if (int rc = greedy_stride_check(who, n * m, greedy_stride, m)) return rc;
   if (ex)
     if (int rc = sample_excl_check(who, *ex)) return rc;
@@ -1273,7 +1188,7 @@ static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, i
                                 workspace, slab, slab_floats, err_flag))
     return rc;
   float inv_T = 0.f;
-  if (int rc = top_p_check(who, top_p, ex != nullptr)) return rc;
+  if (int rc = top_p_check(who, top_p, top_p_one)) return rc;
   CAPNET_REQUIRE(steps >= 1 && steps <= 65535, "%s: steps %d (1..65535)", who, steps);
   if (int rc = sample_check(who, n * m, V, temperature, 0, 0, &inv_T)) return rc;
   CAPNET_REQUIRE(top_k >= 0 && top_k <= 16 && top_k <= V, "%s: top_k=%d (0 = off, 1 .. 16, <= V = %d)", who, top_k, V);
@@ -1282,9 +1197,31 @@ static int att_sample_decode_nucleus_tail(int cell, int nlayers, int n, int m, i
   CAPNET_REQUIRE(aligned16(Cw) && aligned16(state0) && (!state_out || aligned16(state_out)),
                  "%s: Cw and the states must be 16-B aligned", who);
   CAPNET_REQUIRE((size_t)start_tokens % 8 == 0 && (size_t)ids % 8 == 0 && (size_t)logp % 4 == 0, "%s: ids / logp alignment", who);
-  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full,
-                                   wcat, beff, Cw, Cb, state0, inv_T, top_k, top_p, seed, workspace, slab, slab_floats, ids, logp,
-                                   state_out, err_flag, S(stream), greedy_stride, ex);
+  return att_sample_decode(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, w_full, b_full, wcat,
+                           beff, Cw, Cb, state0, SampleOpts{inv_T, top_k, top_p, seed, greedy_stride, ex}, workspace, slab,
+                           slab_floats, ids, logp, state_out, err_flag, S(stream));
+}
+int capnet_att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                             const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                             const float* wz, const float* bz, const float* w_full, const float* b_full,
+                             const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                             const float* state0, float temperature, int top_k, unsigned long long seed, void* workspace,
+                             float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
+                             capnet_stream_t stream) {
+  return att_sample_decode_entry("att_sample_decode", cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz,
+                                 bz, w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, 1.f, true, seed, workspace, slab,
+                                 slab_floats, ids, logp, state_out, err_flag, stream, 0);
+}
+int capnet_att_sample_decode_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                                    const long long* start_tokens, const float* att1, const float* feat, const float* emb,
+                                    const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                    const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                    const float* state0, float temperature, int top_k, unsigned long long seed,
+                                    void* workspace, float* slab, size_t slab_floats, long long* ids, float* logp,
+                                    float* state_out, int* err_flag, unsigned greedy_stride, capnet_stream_t stream) {
+  return att_sample_decode_entry("att_sample_decode", cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz,
+                                 bz, w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, 1.f, true, seed, workspace, slab,
+                                 slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride);
 }
 int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
                                      int steps, const long long* start_tokens, const float* att1, const float* feat,
@@ -1293,9 +1230,9 @@ int capnet_att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P,
                                      const float* Cw, const float* Cb, const float* state0, float temperature, int top_k,
                                      float top_p, unsigned long long seed, void* workspace, float* slab, size_t slab_floats,
                                      long long* ids, float* logp, float* state_out, int* err_flag, capnet_stream_t stream) {
-  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
-                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
-                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, 0);
+  return att_sample_decode_entry("att_sample_decode_nucleus", cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat,
+                                 emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, false, seed,
+                                 workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, 0);
 }
 int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V,
                                             int steps, const long long* start_tokens, const float* att1, const float* feat,
@@ -1305,17 +1242,10 @@ int capnet_att_sample_decode_nucleus_greedy(int cell, int nlayers, int n, int m,
                                             int top_k, float top_p, unsigned long long seed, void* workspace, float* slab,
                                             size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
                                             unsigned greedy_stride, capnet_stream_t stream) {
-  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
-                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
-                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride);
+  return att_sample_decode_entry("att_sample_decode_nucleus", cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat,
+                                 emb, wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, false, seed,
+                                 workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride);
 }
-
-size_t capnet_att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k,
-                                              float top_p) {
-  if (nlayers < 1 || nlayers > 8 || H < 1 || V < 1 || top_k < 0 || top_k > 16 || top_k > V || !(top_p > 0.f && top_p <= 1.f)) return 0;
-  return att_sample_decode_excl_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, top_p < 1.f);
-}
-
 int capnet_att_sample_decode_excl(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
                                   const long long* start_tokens, const float* att1, const float* feat, const float* emb,
                                   const float* wz, const float* bz, const float* w_full, const float* b_full,
@@ -1325,10 +1255,9 @@ int capnet_att_sample_decode_excl(int cell, int nlayers, int n, int m, int P, in
                                   float* state_out, int* err_flag, unsigned greedy_stride, long long end_token,
                                   int no_repeat_ngram, int min_words, const int* banned, int n_banned, capnet_stream_t stream) {
   const SampleExcl ex{end_token, no_repeat_ngram, min_words, banned, n_banned, nullptr};
-  return att_sample_decode_nucleus_tail(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz,
-                                        w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, seed,
-                                        workspace, slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride,
-                                        "att_sample_decode_excl", &ex);
+  return att_sample_decode_entry("att_sample_decode_excl", cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb,
+                                 wz, bz, w_full, b_full, wcat, beff, Cw, Cb, state0, temperature, top_k, top_p, true, seed, workspace,
+                                 slab, slab_floats, ids, logp, state_out, err_flag, stream, greedy_stride, &ex);
 }
 
 size_t capnet_att_beam_decode_alphas_ws_bytes(int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,

@@ -97,7 +97,7 @@ int lstm_greedy_decode_groups(int nlayers, int groups, int rpg, int E, int H, in
 
 // ---- the sampling loops: the draw is vocab_sample (top_k == 0) or vocab_topk + sample_pick (top_k > 0); with a nucleus
 // (top_p < 1) the projection into the workspace's logits block (sgemm_splitk, the product of the composed route's ops.linear:
-// the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": today's launches, not a nucleus.
+// the same logits) + nucleus_rows, or vocab_topk + nucleus_pick. top_p == 1 is "off": the plain launches, not a nucleus.
 // greedy_stride (sample_key.h's vs_row_key; the capnet_*_greedy entries): g > 0 makes every g-th row the greedy decode of its
 // group -- the loops only pass it to the draw; on the attention loop the caller runs m = g rows per image, so the greedy
 // caption rides on the one read of the image's maps per step
@@ -109,25 +109,33 @@ static size_t sample_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bo
   return draw ? token_decode_layout(nlayers, rows, H, top_k).draw + draw : 0;
 }
 
-size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
-  return sample_ws_bytes(nlayers, rows, H, V, top_k, false);
+// the exclusion mask lies behind a loop's own bytes: sample_loop places it there
+static size_t mask_offset(size_t own) { return align16(own); }
+static size_t with_mask(size_t own, int rows, int V, bool excl) {
+  return own && excl ? mask_offset(own) + sample_mask_bytes(rows, V) : own;
 }
 
-size_t sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k) {
-  return sample_ws_bytes(nlayers, rows, H, V, top_k, true);
+size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus, bool excl) {
+  return with_mask(sample_ws_bytes(nlayers, rows, H, V, top_k, nucleus), rows, V, excl);
 }
 
+// own: the bytes of ws in front of the mask (the family's size without exclusions)
 template <class Step>
 static int sample_loop(int nlayers, int rows, int H, int V, int steps, const long long* start_tokens, const float* Cw,
-                       const float* Cb, const float* state0, float inv_T, int top_k, float top_p, unsigned long long seed, void* ws,
-                       float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, hipStream_t s,
-                       unsigned greedy_stride, const SampleExcl* ex, Step&& step_fn) {
-  // ex (the capnet_*_excl entries): a launch of its own builds the step's exclusion mask from ids and the start
-  // tokens, and the step's draw reads it; null: the launches as they were
-  const unsigned* mask = ex ? ex->mask : nullptr;
+                       const float* Cb, const float* state0, const SampleOpts& o, void* ws, size_t own, float* slab,
+                       size_t slab_floats, long long* ids, float* logp, float* state_out, hipStream_t s, Step&& step_fn) {
+  const int top_k = o.top_k;
   const TokenDecodeWs w = token_decode_layout(nlayers, rows, H, top_k);
-  const bool nucleus = top_p < 1.f;
+  const bool nucleus = o.top_p < 1.f;
   char* p = reinterpret_cast<char*>(ws);
+  // ex: a launch of its own builds the step's exclusion mask from ids and the start tokens, and the step's draw reads it;
+  // null: the launches as they were
+  SampleExcl ex{};
+  if (o.ex) {
+    ex = *o.ex;
+    ex.mask = reinterpret_cast<unsigned*>(p + mask_offset(own));
+  }
+  const unsigned* mask = ex.mask;
   float* tk_values = reinterpret_cast<float*>(p + w.tk_values);
   int* tk_index = reinterpret_cast<int*>(p + w.tk_index);
   float* tk_lse = reinterpret_cast<float*>(p + w.tk_lse);
@@ -135,58 +143,39 @@ static int sample_loop(int nlayers, int rows, int H, int V, int steps, const lon
   float* logits = reinterpret_cast<float*>(p + w.draw);      // the nucleus draw without top_k
   return token_loop(w, nlayers, rows, H, steps, nucleus && top_k == 0 ? 0 : 1, start_tokens, state0, ws, state_out, s, step_fn,
                     [&](int t, const float* h_top, long long* tok) {
-                      if (ex)
-                        if (int rc = sample_exclusion_mask(ids, steps, start_tokens, rows, t, V, *ex, ex->mask, s)) return rc;
+                      if (mask)
+                        if (int rc = sample_exclusion_mask(ids, steps, start_tokens, rows, t, V, ex, ex.mask, s)) return rc;
                       if (top_k == 0 && !nucleus)
-                        return vocab_sample(h_top, Cw, Cb, rows, H, V, inv_T, seed, (unsigned)t, 0, draw_ws, tok, ids + t, logp + t,
-                                            steps, s, greedy_stride, mask);
+                        return vocab_sample(h_top, Cw, Cb, rows, H, V, o.inv_T, o.seed, (unsigned)t, 0, draw_ws, tok, ids + t,
+                                            logp + t, steps, s, o.greedy_stride, mask);
                       if (top_k == 0) {
                         int rc = sgemm_splitk(false, true, rows, V, H, h_top, H, Cw, H, logits, V, Cb, 0, slab, slab_floats, s);
                         if (rc == kOk && mask) rc = mask_logits(logits, rows, V, V, mask, s);
                         if (rc != kOk) return rc;
-                        return nucleus_rows(logits, rows, V, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t, logp + t, steps, s,
-                                            greedy_stride);
+                        return nucleus_rows(logits, rows, V, V, o.inv_T, o.top_p, o.seed, (unsigned)t, 0, tok, ids + t, logp + t,
+                                            steps, s, o.greedy_stride);
                       }
                       const int rc = vocab_topk(h_top, Cw, Cb, rows, H, V, top_k, draw_ws, tk_values, tk_index, tk_lse, s, mask);
                       if (rc != kOk) return rc;
                       if (nucleus)
-                        return nucleus_pick(tk_values, tk_index, rows, top_k, V, inv_T, top_p, seed, (unsigned)t, 0, tok, ids + t,
-                                            logp + t, steps, s, greedy_stride);
-                      return sample_pick(tk_values, tk_index, rows, top_k, V, inv_T, seed, (unsigned)t, 0, tok, ids + t, logp + t,
-                                         steps, s, greedy_stride);
+                        return nucleus_pick(tk_values, tk_index, rows, top_k, V, o.inv_T, o.top_p, o.seed, (unsigned)t, 0, tok,
+                                            ids + t, logp + t, steps, s, o.greedy_stride);
+                      return sample_pick(tk_values, tk_index, rows, top_k, V, o.inv_T, o.seed, (unsigned)t, 0, tok, ids + t,
+                                         logp + t, steps, s, o.greedy_stride);
                     });
-}
-
-size_t sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus) {
-  const size_t base = sample_ws_bytes(nlayers, rows, H, V, top_k, nucleus);
-  return base ? align16(base) + sample_mask_bytes(rows, V) : 0;
-}
-
-int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                          const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                          const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
-                          unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride, const SampleExcl* ex) {
-  SampleExcl placed;
-  if (ex) {   // the mask: behind the loop's own workspace
-    placed = *ex;
-    placed.mask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f)));
-    ex = &placed;
-  }
-  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, greedy_stride, ex, [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
-                       const bool given = t == 0 && first_inputs;     // step 0 on the caller's rows
-                       return stacked_decode_step(cell, nlayers, rows, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
-                                                  wcat, beff, sin, sout, h_top, err_flag, s);
-                     });
 }
 
 int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
                   const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                  const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
-                  long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
-  return sample_decode_nucleus(cell, nlayers, rows, E, H, V, steps, first_inputs, start_tokens, emb, wcat, beff, Cw, Cb, state0,
-                               inv_T, top_k, 1.f, seed, ws, nullptr, 0, ids, logp, state_out, err_flag, s);
+                  const float* Cw, const float* Cb, const float* state0, const SampleOpts& o, void* ws, float* slab,
+                  size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
+  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, o, ws,
+                     sample_ws_bytes(nlayers, rows, H, V, o.top_k, o.top_p < 1.f), slab, slab_floats, ids, logp, state_out, s,
+                     [&](int t, const long long* tok, const float* sin, float* sout, float* h_top) {
+                       const bool given = t == 0 && first_inputs;     // step 0 on the caller's rows
+                       return stacked_decode_step(cell, nlayers, rows, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
+                                                  wcat, beff, sin, sout, h_top, err_flag, s);
+                     });
 }
 
 // ---- the same loop for the attention decoders: n images x m samples each, the step att_decode_step with k = m and every
@@ -199,51 +188,25 @@ static size_t att_sample_ws_bytes(int nlayers, int n, int m, int P, int A, int C
   return base && step ? align16(base) + align16(step) : 0;
 }
 
-size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
-  return att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, false);
-}
-
-size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k) {
-  return att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, true);
-}
-
-size_t att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus) {
-  const size_t base = att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, nucleus);
-  return base ? align16(base) + sample_mask_bytes(n * m, V) : 0;
-}
-
-int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                              const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                              const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
-                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
-                              int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
-                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
-                              unsigned greedy_stride, const SampleExcl* ex) {
-  const int rows = n * m;
-  void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, top_k, top_p < 1.f));
-  SampleExcl placed;
-  if (ex) {   // the mask: behind the loop's own workspace
-    placed = *ex;
-    placed.mask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) +
-                                              align16(att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, top_p < 1.f)));
-    ex = &placed;
-  }
-  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, inv_T, top_k, top_p, seed, ws, slab, slab_floats, ids,
-                     logp, state_out, s, greedy_stride, ex, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
-                       return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
-                                              sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
-                     });
+size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus,
+                                  bool excl) {
+  return with_mask(att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, top_k, nucleus), n * m, V, excl);
 }
 
 int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
                       const long long* start_tokens, const float* att1, const float* feat, const float* emb, const float* wz,
                       const float* bz, const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
-                      const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
-                      void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                      hipStream_t s) {
-  return att_sample_decode_nucleus(cell, nlayers, n, m, P, A, C, E, H, V, steps, start_tokens, att1, feat, emb, wz, bz, wf, bf, wcat,
-                                   beff, Cw, Cb, state0, inv_T, top_k, 1.f, seed, ws, slab, slab_floats, ids, logp, state_out, err_flag,
-                                   s);
+                      const float* Cw, const float* Cb, const float* state0, const SampleOpts& o, void* ws, float* slab,
+                      size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s) {
+  const int rows = n * m;
+  const bool nucleus = o.top_p < 1.f;
+  void* step_ws = reinterpret_cast<char*>(ws) + align16(sample_ws_bytes(nlayers, rows, H, V, o.top_k, nucleus));
+  return sample_loop(nlayers, rows, H, V, steps, start_tokens, Cw, Cb, state0, o, ws,
+                     att_sample_ws_bytes(nlayers, n, m, P, A, C, E, H, V, o.top_k, nucleus), slab, slab_floats, ids, logp, state_out,
+                     s, [&](int, const long long* tok, const float* sin, float* sout, float* h_top) {
+                       return att_decode_step(cell, nlayers, n, m, P, A, C, E, H, V, att1, feat, tok, emb, wz, bz, wf, bf, wcat, beff,
+                                              sin, nullptr, sout, h_top, step_ws, slab, slab_floats, err_flag, s);
+                     });
 }
 
 // ---- the whole beam search of a plain stack: steps x (one gathered decode-step launch per layer + the vocabulary

@@ -405,24 +405,9 @@ int sample_pick(const float* values, const int* index, int rows, int k, int V, f
                 unsigned greedy_stride = 0);
 int sample_rows(const float* logits, int rows, long ld_logits, int V, float inv_T, unsigned long long seed, unsigned step,
                 unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream, unsigned greedy_stride = 0);
-// decode_loops.hip: lstm_greedy_decode's loop with the draw in place of the argmax (top_k == 0: vocab_sample; else vocab_topk
-// + sample_pick)
-size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
-int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                  const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                  const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed, void* ws,
-                  long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
-// the same for an attention decoder: n images x m samples each on att_decode_step (k = m, every row its own parent)
-size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
-int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                      const long long* start_tokens, const float* att1, const float* feat, const float* emb, const float* wz,
-                      const float* bz, const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
-                      const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, unsigned long long seed,
-                      void* ws, float* slab, size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag,
-                      hipStream_t s);
 // sample_exclude.hip: what a sampled row may not draw (capnet.beam.banned_words on [start, the row's words so far], the same
 // rule as BeamConstraints' without forced words), as a bit mask [rows][sample_mask_words(V)]: bit v & 31 of word v >> 5 set =
-// word v excluded on that launch row. `mask` is left null by the callers of the loops, which place it in their workspace
+// word v excluded on that launch row. `mask` is left null by the callers of the loops: sample_loop places it behind their workspace
 struct SampleExcl {
   long long end_token;
   int no_repeat_ngram, min_words;
@@ -447,28 +432,33 @@ int nucleus_rows(const float* logits, int rows, long ld_logits, int V, float inv
 int nucleus_pick(const float* values, const int* index, int rows, int k, int V, float inv_T, float top_p, unsigned long long seed,
                  unsigned step, unsigned row0, long long* tok, long long* ids, float* logp, long ld, hipStream_t stream,
                  unsigned greedy_stride = 0);
-// decode_loops.hip: sample_decode / att_sample_decode with the nucleus draw, 0 < top_p < 1: per step the projection into a
-// logits block of the workspace (sgemm_splitk on the caller's slab) + nucleus_rows (top_k == 0), or vocab_topk + nucleus_pick
-size_t sample_decode_nucleus_ws_bytes(int nlayers, int rows, int H, int V, int top_k);
-int sample_decode_nucleus(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
-                          const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
-                          const float* Cw, const float* Cb, const float* state0, float inv_T, int top_k, float top_p,
-                          unsigned long long seed, void* ws, float* slab, size_t slab_floats, long long* ids, float* logp,
-                          float* state_out, int* err_flag, hipStream_t s, unsigned greedy_stride = 0,
-                          const SampleExcl* ex = nullptr);
-size_t att_sample_decode_nucleus_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k);
-int att_sample_decode_nucleus(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
-                              const long long* start_tokens, const float* att1, const float* feat, const float* emb,
-                              const float* wz, const float* bz, const float* wf, const float* bf, const float* const* wcat,
-                              const float* const* beff, const float* Cw, const float* Cb, const float* state0, float inv_T,
-                              int top_k, float top_p, unsigned long long seed, void* ws, float* slab, size_t slab_floats,
-                              long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s,
-                              unsigned greedy_stride = 0, const SampleExcl* ex = nullptr);
-// the same loops under exclusions (ex set; top_p == 1 allowed: the plain draws): per step sample_exclusion_mask into the mask
-// behind the loop's own workspace, then the step's draw on it -- vocab_sample / vocab_topk with the mask, or mask_logits on the
-// logits block in front of nucleus_rows. ws: the loop's own bytes, 16-B aligned, then sample_mask_bytes
-size_t sample_decode_excl_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus);
-size_t att_sample_decode_excl_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus);
+// decode_loops.hip: lstm_greedy_decode's loop with the draw in place of the argmax. The draw by its options: top_p == 1 and
+// top_k == 0: vocab_sample; top_k > 0: vocab_topk + sample_pick (top_p < 1: + nucleus_pick); top_p < 1 without top_k: the
+// projection into a logits block of the workspace (sgemm_splitk on the caller's slab, else unused) + nucleus_rows. ex (top_p <=
+// 1; its mask left null): per step sample_exclusion_mask into the mask behind the loop's own workspace, then the step's draw on
+// it -- vocab_sample / vocab_topk with the mask, or mask_logits on the logits block in front of nucleus_rows
+struct SampleOpts {
+  float inv_T;
+  int top_k;             // 0: off
+  float top_p;           // 1: off
+  unsigned long long seed;
+  unsigned greedy_stride;
+  const SampleExcl* ex;  // null: none
+};
+// ws: the loop's own bytes (nucleus: with the logits block where top_k == 0); excl: 16-B aligned, then sample_mask_bytes
+size_t sample_decode_ws_bytes(int nlayers, int rows, int H, int V, int top_k, bool nucleus, bool excl);
+int sample_decode(int cell, int nlayers, int rows, int E, int H, int V, int steps, const float* first_inputs,
+                  const long long* start_tokens, const float* emb, const float* const* wcat, const float* const* beff,
+                  const float* Cw, const float* Cb, const float* state0, const SampleOpts& o, void* ws, float* slab,
+                  size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
+// the same for an attention decoder: n images x m samples each on att_decode_step (k = m, every row its own parent)
+size_t att_sample_decode_ws_bytes(int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int top_k, bool nucleus,
+                                  bool excl);
+int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, int E, int H, int V, int steps,
+                      const long long* start_tokens, const float* att1, const float* feat, const float* emb, const float* wz,
+                      const float* bz, const float* wf, const float* bf, const float* const* wcat, const float* const* beff,
+                      const float* Cw, const float* Cb, const float* state0, const SampleOpts& o, void* ws, float* slab,
+                      size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
 // decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
 // fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
 // beam_decode's

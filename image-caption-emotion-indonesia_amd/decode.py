@@ -348,15 +348,34 @@ def draw_step(logits, temperature, top_k, seed, step, top_p=1.0, greedy_stride=0
     gs = {"greedy_stride": greedy_stride} if greedy_stride else {}
     if mask is not None:
         logits = ops.mask_logits(logits if logits.stride(1) == 1 else logits.contiguous(), mask)
-    if top_p == 1.0:
-        if top_k == 0:
-            return ops.sample_rows(logits, temperature, seed, step, **gs)
-        values, index = torch.topk(logits, top_k, dim=1)
-        return ops.sample_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, seed, step, **gs)
+    tail = (temperature, seed, step) if top_p == 1.0 else (temperature, top_p, seed, step)
     if top_k == 0:
-        return ops.nucleus_rows(logits, temperature, top_p, seed, step, **gs)
+        return (ops.sample_rows if top_p == 1.0 else ops.nucleus_rows)(logits, *tail, **gs)
     values, index = torch.topk(logits, top_k, dim=1)
-    return ops.nucleus_pick(values.contiguous(), index.int().contiguous(), logits.shape[1], temperature, top_p, seed, step, **gs)
+    pick = ops.sample_pick if top_p == 1.0 else ops.nucleus_pick
+    return pick(values.contiguous(), index.int().contiguous(), logits.shape[1], *tail, **gs)
+
+
+def sample_steps(step, steps, tokens, state, temperature, top_k, seed, draw_kw, exclude=None, V=None, end_token=None):
+    """The composed sampled decode: per stream step t, step(t, tokens, state) -> (logits [rows, V], state'), then draw_step
+    (draw_kw: its top_p / greedy_stride keywords, where set) -> the next tokens. tokens: the rows' start tokens (None where
+    step 0 does not read them). exclude (an active Constraints, with V and end_token): per step ops.sample_exclusion_mask
+    on the rows' words so far -- which the kernel reads from one [rows, steps] block -- in front of the draw.
+    Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state)."""
+    ids, logp = [], []
+    if exclude is not None:
+        start, so_far, mask = tokens, torch.empty((tokens.shape[0], steps), dtype=torch.int64, device=tokens.device), None
+    for t in range(steps):
+        logits, state = step(t, tokens, state)
+        if exclude is not None:
+            mask = ops.sample_exclusion_mask(so_far, start, t, V, end_token, exclude, out=mask)
+            tokens, lp = draw_step(logits, temperature, top_k, seed, t, **draw_kw, mask=mask)
+            so_far[:, t] = tokens
+        else:
+            tokens, lp = draw_step(logits, temperature, top_k, seed, t, **draw_kw)
+        ids.append(tokens)
+        logp.append(lp)
+    return torch.stack(ids, 1), torch.stack(logp, 1), state
 
 
 def cut_samples(ids, logp, n, m, start_token, end_token):
@@ -430,20 +449,8 @@ def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temp
                                               start_token, temperature, top_k, seed, **kw, **({"greedy": True} if greedy else {}), **ex)
         else:
             words = torch.full((n * per,), int(start_token), dtype=torch.int64, device=dev)
-            ids, logp = [], []
-            if exclude is not None:      # the mask kernel reads the rows' words so far from one [rows, steps] block
-                start, so_far, mask = words, torch.empty((n * per, steps), dtype=torch.int64, device=dev), None
-            for t in range(steps):
-                logits, state = step_fn(words, state)
-                if exclude is not None:
-                    mask = ops.sample_exclusion_mask(so_far, start, t, V, end_token, exclude, out=mask)
-                    words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs, mask=mask)
-                    so_far[:, t] = words
-                else:
-                    words, lp = draw_step(logits, temperature, top_k, seed, t, **kw, **gs)
-                ids.append(words)
-                logp.append(lp)
-            ids, logp = torch.stack(ids, 1), torch.stack(logp, 1)
+            ids, logp, _ = sample_steps(lambda t, tokens, st: step_fn(tokens, st), steps, words, state, temperature, top_k, seed,
+                                        dict(kw, **gs), exclude, V, end_token)
     ops.check_device_errors()
     return cut_samples(ids, logp, n, per, start_token, end_token), ids, logp
 

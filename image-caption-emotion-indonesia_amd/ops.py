@@ -1041,11 +1041,31 @@ def _check_greedy_stride(who, greedy_stride, rows=None):
     return int(greedy_stride)
 
 
-def _call_sampler(name, greedy_stride, *args):
-    """capnet_<name>(*args, stream); with greedy rows capnet_<name>_greedy(*args, greedy_stride, stream)."""
-    if greedy_stride:
+def _call_sampler(name, greedy_stride, *args, excl=None):
+    """capnet_<name>(*args, stream); with greedy rows capnet_<name>_greedy(*args, greedy_stride, stream). excl (_exclude_args'
+    tuple, the *_excl entries): capnet_<name>(*args, greedy_stride, *excl, stream) -- they take the stride either way."""
+    if excl is not None:
+        args += (greedy_stride,) + excl
+    elif greedy_stride:
         name, args = name + "_greedy", args + (greedy_stride,)
     check(getattr(_lib.lib(), "capnet_" + name)(*(args + (current_stream(),))), "capnet_" + name)
+
+
+def _call_sampled_loop(who, dims, shape, head, top_k, top_p, seed, outs, greedy_stride, excl, dev, plain_slab=False):
+    """The one C call of ops.sample_decode / ops.att_sample_decode (`who`), chosen from (exclusions, top_p < 1, greedy_stride)
+    here and in _call_sampler: capnet_<who>_excl, capnet_<who>_nucleus or capnet_<who>, on a workspace of that entry's own
+    size query (`dims`: the query's arguments in front of top_k; `shape`: what an error says of them). The entry takes head,
+    top_k, top_p (but the plain one), seed, the workspace, the split-K slab (the plain one only with plain_slab), outs."""
+    form = "_excl" if excl is not None else "_nucleus" if top_p < 1.0 else ""
+    nbytes = getattr(_lib.lib(), "capnet_%s%s_ws_bytes" % (who, form))(*dims, top_k, *((top_p,) if excl is not None else ()))
+    if not nbytes:
+        raise CapnetError("%s: unsupported shape (%s, top_k=%d)" % (who, shape, top_k))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    args = head + ((top_k, top_p) if form else (top_k,)) + (seed, ptr(ws))
+    if form or plain_slab:
+        slab = splitk_slab(dev)
+        args += (ptr(slab), slab.numel())
+    _call_sampler(who + form, greedy_stride, *args, *outs, excl=excl)
 
 
 # ---- exclusions of a sampled decode (csrc/sample_exclude.hip; DESIGN 4an) ----
@@ -1160,44 +1180,54 @@ def vocab_sample(h, w, b=None, temperature=1.0, seed=0, step=0, row0=0, workspac
     return tokens, logp
 
 
-def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0, greedy_stride=0):
-    """Top-k sampling on vocab_topk's (values, index) [rows, k], k <= 16 (capnet_sample_pick): (tokens [rows] int64, logp
-    [rows] float32), the draw among the k candidates with the noise keyed by their vocabulary index and logp renormalised
-    over the candidates. Padding slots (-inf, -1) are never drawn."""
-    temperature, _, seed = check_sampling("sample_pick", temperature, 0, seed)
-    greedy_stride = _check_greedy_stride("sample_pick", greedy_stride)
+def _draw_pick(who, values, index, V, temperature, top_p, seed, step, row0, greedy_stride):
+    """sample_pick (top_p None: capnet_sample_pick) and nucleus_pick (capnet_nucleus_pick)."""
+    temperature, _, seed = check_sampling(who, temperature, 0, seed)
+    greedy_stride = _check_greedy_stride(who, greedy_stride)
     _need_cuda(values, index)
     values, index = _c(values.detach()), _c(index)
     if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
             or not 1 <= values.shape[1] <= 16 or values.shape[0] < 1:
-        raise CapnetError("sample_pick: values float32 [rows, k], index int32 [rows, k], 1 <= k <= 16")
+        raise CapnetError("%s: values float32 [rows, k], index int32 [rows, k], 1 <= k <= 16" % who)
     rows, k = values.shape
-    step, row0 = _check_stream_pos("sample_pick", rows, int(V), step, row0)
+    step, row0 = _check_stream_pos(who, rows, int(V), step, row0)
     tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
     logp = torch.empty(rows, dtype=torch.float32, device=values.device)
-    _call_sampler("sample_pick", greedy_stride, ptr(values), ptr(index), rows, k, int(V), temperature, seed, step, row0, ptr(tokens),
-                  ptr(logp))
+    _call_sampler(who, greedy_stride, ptr(values), ptr(index), rows, k, int(V), temperature, *(() if top_p is None else (top_p,)),
+                  seed, step, row0, ptr(tokens), ptr(logp))
     return tokens, logp
+
+
+def _draw_rows(who, logits, temperature, top_p, seed, step, row0, greedy_stride):
+    """sample_rows (top_p None: capnet_sample_rows) and nucleus_rows (capnet_nucleus_rows)."""
+    temperature, _, seed = check_sampling(who, temperature, 0, seed)
+    greedy_stride = _check_greedy_stride(who, greedy_stride)
+    _need_cuda(logits)
+    logits = logits.detach()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise CapnetError("%s: logits float32 [rows, V]" % who)
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    rows, V = logits.shape
+    step, row0 = _check_stream_pos(who, rows, V, step, row0)
+    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _call_sampler(who, greedy_stride, ptr(logits), rows, logits.stride(0), V, temperature, *(() if top_p is None else (top_p,)),
+                  seed, step, row0, ptr(tokens), ptr(logp))
+    return tokens, logp
+
+
+def sample_pick(values, index, V, temperature=1.0, seed=0, step=0, row0=0, greedy_stride=0):
+    """Top-k sampling on vocab_topk's (values, index) [rows, k], k <= 16 (capnet_sample_pick): (tokens [rows] int64, logp
+    [rows] float32), the draw among the k candidates with the noise keyed by their vocabulary index and logp renormalised
+    over the candidates. Padding slots (-inf, -1) are never drawn."""
+    return _draw_pick("sample_pick", values, index, V, temperature, None, seed, step, row0, greedy_stride)
 
 
 def sample_rows(logits, temperature=1.0, seed=0, step=0, row0=0, greedy_stride=0):
     """vocab_sample's draw from logits [rows, V] in memory (capnet_sample_rows, one workgroup per row): (tokens [rows] int64,
     logp [rows] float32). Any V up to 2^24."""
-    temperature, _, seed = check_sampling("sample_rows", temperature, 0, seed)
-    greedy_stride = _check_greedy_stride("sample_rows", greedy_stride)
-    _need_cuda(logits)
-    logits = logits.detach()
-    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
-        raise CapnetError("sample_rows: logits float32 [rows, V]")
-    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        logits = logits.contiguous()
-    rows, V = logits.shape
-    step, row0 = _check_stream_pos("sample_rows", rows, V, step, row0)
-    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    _call_sampler("sample_rows", greedy_stride, ptr(logits), rows, logits.stride(0), V, temperature, seed, step, row0, ptr(tokens),
-                  ptr(logp))
-    return tokens, logp
+    return _draw_rows("sample_rows", logits, temperature, None, seed, step, row0, greedy_stride)
 
 
 def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0, greedy_stride=0):
@@ -1207,20 +1237,7 @@ def nucleus_rows(logits, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0, gre
     temperature, _, seed, top_p = check_sampling("nucleus_rows", temperature, 0, seed, top_p=top_p)
     if top_p == 1.0:
         return sample_rows(logits, temperature, seed, step, row0, greedy_stride)
-    greedy_stride = _check_greedy_stride("nucleus_rows", greedy_stride)
-    _need_cuda(logits)
-    logits = logits.detach()
-    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1:
-        raise CapnetError("nucleus_rows: logits float32 [rows, V]")
-    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        logits = logits.contiguous()
-    rows, V = logits.shape
-    step, row0 = _check_stream_pos("nucleus_rows", rows, V, step, row0)
-    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    _call_sampler("nucleus_rows", greedy_stride, ptr(logits), rows, logits.stride(0), V, temperature, top_p, seed, step, row0,
-                  ptr(tokens), ptr(logp))
-    return tokens, logp
+    return _draw_rows("nucleus_rows", logits, temperature, top_p, seed, step, row0, greedy_stride)
 
 
 def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, row0=0, greedy_stride=0):
@@ -1230,19 +1247,7 @@ def nucleus_pick(values, index, V, temperature=1.0, top_p=1.0, seed=0, step=0, r
     temperature, _, seed, top_p = check_sampling("nucleus_pick", temperature, 0, seed, top_p=top_p)
     if top_p == 1.0:
         return sample_pick(values, index, V, temperature, seed, step, row0, greedy_stride)
-    greedy_stride = _check_greedy_stride("nucleus_pick", greedy_stride)
-    _need_cuda(values, index)
-    values, index = _c(values.detach()), _c(index)
-    if values.dim() != 2 or values.shape != index.shape or values.dtype != torch.float32 or index.dtype != torch.int32 \
-            or not 1 <= values.shape[1] <= 16 or values.shape[0] < 1:
-        raise CapnetError("nucleus_pick: values float32 [rows, k], index int32 [rows, k], 1 <= k <= 16")
-    rows, k = values.shape
-    step, row0 = _check_stream_pos("nucleus_pick", rows, int(V), step, row0)
-    tokens = torch.empty(rows, dtype=torch.int64, device=values.device)
-    logp = torch.empty(rows, dtype=torch.float32, device=values.device)
-    _call_sampler("nucleus_pick", greedy_stride, ptr(values), ptr(index), rows, k, int(V), temperature, top_p, seed, step, row0,
-                  ptr(tokens), ptr(logp))
-    return tokens, logp
+    return _draw_pick("nucleus_pick", values, index, V, temperature, top_p, seed, step, row0, greedy_stride)
 
 
 def sample_decode_supported(E, H, V, top_k=0):
@@ -1290,36 +1295,18 @@ def sample_decode(cell, steps, wcat, beff, emb, Cw, Cb, temperature, top_k, seed
     if not sample_decode_supported(E, H, V, top_k):
         raise CapnetError("%s: unsupported shape (E=%d, H=%d, V=%d, %d layers, top_k=%d)" % (who, E, H, V, nl, top_k))
     dev = emb.device
-    L = _lib.lib()
+    excl = None
     if exclude is not None:
         if start_tokens is None:
             raise CapnetError("%s: exclude needs start_tokens" % who)
         excl = _exclude_args(who, exclude, end_token, dev)
-        nbytes = L.capnet_sample_decode_excl_ws_bytes(nl, rows, H, V, top_k, top_p)
-    else:
-        nbytes = (L.capnet_sample_decode_nucleus_ws_bytes if top_p < 1.0 else L.capnet_sample_decode_ws_bytes)(nl, rows, H, V, top_k)
-    if not nbytes:
-        raise CapnetError("%s: unsupported shape (rows=%d, V=%d, top_k=%d)" % (who, rows, V, top_k))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
     ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
     out = torch.empty((rows, 2 * nl, H), dtype=torch.float32, device=dev)
-    if exclude is not None:
-        slab = splitk_slab(dev)
-        check(L.capnet_sample_decode_excl(cell, nl, rows, E, H, V, steps, None, ptr(start_tokens), ptr(emb), ptr_array(wcat),
-                                          ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, top_p, seed, ptr(ws),
-                                          ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out), ptr(err_flag(dev)), greedy_stride,
-                                          *excl, current_stream()), "capnet_sample_decode_excl")
-        return ids, logp, out
-    if top_p < 1.0:
-        slab = splitk_slab(dev)
-        _call_sampler("sample_decode_nucleus", greedy_stride, cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens),
-                      ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, top_p, seed,
-                      ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), ptr(out), ptr(err_flag(dev)))
-        return ids, logp, out
-    _call_sampler("sample_decode", greedy_stride, cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb),
-                  ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k, seed, ptr(ws), ptr(ids),
-                  ptr(logp), ptr(out), ptr(err_flag(dev)))
+    head = (cell, nl, rows, E, H, V, steps, ptr(first_inputs), ptr(start_tokens), ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw),
+            ptr(Cb), ptr(state), temperature)
+    _call_sampled_loop(who, (nl, rows, H, V), "rows=%d, V=%d" % (rows, V), head, top_k, top_p, seed,
+                       (ptr(ids), ptr(logp), ptr(out), ptr(err_flag(dev))), greedy_stride, excl, dev)
     return ids, logp, out
 
 
@@ -1825,31 +1812,14 @@ def att_sample_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff,
     if not 1 <= steps <= SAMPLE_MAX_STEPS or tuple(Cw.shape) != (V, H) or (Cb is not None and Cb.numel() != V):
         raise CapnetError("%s: Cw [V, H], Cb [V], 1 <= steps <= 65535 (V=%d, steps=%d)" % (who, V, steps))
     dev, rows = emb.device, n * m
-    L = _lib.lib()
-    nucleus = top_p < 1.0
-    if exclude is not None:
-        excl = _exclude_args(who, exclude, end_token, dev)
-        nbytes = L.capnet_att_sample_decode_excl_ws_bytes(nl, n, m, P, A, Cdim, E, H, V, top_k, top_p)
-    else:
-        nbytes = (L.capnet_att_sample_decode_nucleus_ws_bytes if nucleus else L.capnet_att_sample_decode_ws_bytes)(
-            nl, n, m, P, A, Cdim, E, H, V, top_k)
-    if not nbytes:
-        raise CapnetError("%s: unsupported shape (n=%d, m=%d, V=%d, top_k=%d)" % (who, n, m, V, top_k))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    slab = splitk_slab(dev)
+    excl = None if exclude is None else _exclude_args(who, exclude, end_token, dev)
     tokens = torch.full((rows,), int(start_token), dtype=torch.int64, device=dev)
     ids = torch.empty((rows, steps), dtype=torch.int64, device=dev)
     logp = torch.empty((rows, steps), dtype=torch.float32, device=dev)
     head = (cell, nl, n, m, P, A, Cdim, E, H, V, steps, ptr(tokens), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz), ptr(wf), ptr(bf),
-            ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature, top_k)
-    tail = (seed, ptr(ws), ptr(slab), slab.numel(), ptr(ids), ptr(logp), None, ptr(err_flag(dev)))
-    stride = m if greedy else 0
-    if exclude is not None:
-        check(L.capnet_att_sample_decode_excl(*head, top_p, *tail, stride, *excl, current_stream()), "capnet_att_sample_decode_excl")
-    elif nucleus:
-        _call_sampler("att_sample_decode_nucleus", stride, *head, top_p, *tail)
-    else:
-        _call_sampler("att_sample_decode", stride, *head, *tail)
+            ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), temperature)
+    _call_sampled_loop(who, (nl, n, m, P, A, Cdim, E, H, V), "n=%d, m=%d, V=%d" % (n, m, V), head, top_k, top_p, seed,
+                       (ptr(ids), ptr(logp), None, ptr(err_flag(dev))), m if greedy else 0, excl, dev, plain_slab=True)
     return ids, logp
 
 

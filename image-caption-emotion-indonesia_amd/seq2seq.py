@@ -60,7 +60,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import CapnetError
 from .beam import beam_search_device
-from .decode import cell_stepper, check_styles, draw_step, fused_decode_step, fused_sample, pack_cells
+from .decode import cell_stepper, check_styles, fused_decode_step, fused_sample, pack_cells, sample_steps
 from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
 
@@ -215,7 +215,7 @@ class _RNN(nn.Module):
         t on stream step t; top_p < 1: over the nucleus (capnet.decode.sample_random). Returns (ids [rows, max_seq_length] int64, logp [rows, max_seq_length] float32, state').
         One capnet_sample_decode call where the decode kernel takes the shape, the rows are at most
         capnet.decode.FUSED_SAMPLE_MAX_ROWS and neither CAPNET_NO_FUSED_SAMPLE=1 nor CAPNET_NO_FUSED_DECODE_STEP=1 is set;
-        else the composed loop (step -> ops.linear -> capnet.decode.draw_step) on the same stream: the same tokens."""
+        else the composed loop (capnet.decode.sample_steps on step -> ops.linear) on the same stream: the same tokens."""
         E, H, V, steps = self.embed_size, self.hidden_size, self.vocab_size, self.max_seq_length
         temperature, top_k, seed, top_p = ops.check_sampling("sample_random", temperature, top_k, seed, V, top_p)
         kw = {} if top_p == 1.0 else {"top_p": top_p}      # top_p == 1.0: the calls as they were before there was a top_p
@@ -228,17 +228,15 @@ class _RNN(nn.Module):
                 return ops.sample_decode(ops.CELL_LSTM, steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
                                          temperature, top_k, seed, first_inputs=features, start_tokens=start_tokens, state=state,
                                          **kw)
-            step = cell_stepper(layers, E, H)
-            ids, logp, tokens = [], [], start_tokens
-            for t in range(steps):
+            cells = cell_stepper(layers, E, H)
+
+            def step(t, tokens, state):
                 if t == 0 and features is not None:
-                    top, state = step(features.detach().float().contiguous(), None, state)
+                    top, state = cells(features.detach().float().contiguous(), None, state)
                 else:
-                    top, state = step(emb, tokens, state)
-                tokens, lp = draw_step(ops.linear(top, Cw, Cb), temperature, top_k, seed, t, **kw)
-                ids.append(tokens)
-                logp.append(lp)
-            return torch.stack(ids, 1), torch.stack(logp, 1), state
+                    top, state = cells(emb, tokens, state)
+                return ops.linear(top, Cw, Cb), state
+            return sample_steps(step, steps, start_tokens, state, temperature, top_k, seed, kw)
 
     def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk, nbest=False, length_penalty=0.0):
         """Beam search of B = state.shape[0] sentences x k beams from `state` [B, 2L, H]; the first input is `features`
