@@ -217,6 +217,19 @@ SIGNATURES = {
     "capnet_lstm_beam_decode_groups": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.POINTER(_vp),
                                             C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _sz,
                                             _i, _i, _vp, _vp, C.POINTER(_i), _vp, _vp]),
+    "capnet_beam_exclusion_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _vp]),
+    "capnet_vocab_topk_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capnet_vocab_topk_groups_masked": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    "capnet_lstm_beam_decode_constrained_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "capnet_lstm_beam_decode_constrained": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, _vp, _vp, C.POINTER(_vp),
+                                                 C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, C.POINTER(_i), _vp,
+                                                 _vp, _i, _i, _vp, _i, _vp, _i]),
+    "capnet_lstm_beam_decode_groups_constrained_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "capnet_lstm_beam_decode_groups_constrained": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong,
+                                                        C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                                        C.POINTER(_vp), _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, C.POINTER(_i), _vp,
+                                                        _vp, _i, _i, _vp, _i, _vp, _i]),
     "capnet_att_decode_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "capnet_att_decode_step": (_i, [_i] * 10 + [_vp] * 8 + [C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _sz,

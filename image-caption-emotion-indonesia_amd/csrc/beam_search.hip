@@ -1081,4 +1081,14 @@ int beam_live(const void* beam, int n, int k, int max_steps, const int** live_to
   return kOk;
 }
 
+// the hypotheses step `step` (1-based) reads: seq[(step - 1) & 1], [n k] rows of max_steps + 2 int32, `step` tokens each with
+// <start> first -- what BeamExclState reads, for sample_exclude.hip's mask kernel
+int beam_tokens(const void* beam, int n, int k, int max_steps, int step, const int** tokens) {
+  if (int rc = beam_check("beam_tokens", beam, n, k, max_steps)) return rc;
+  CAPNET_REQUIRE(step >= 1 && step <= max_steps && tokens, "beam_tokens: step=%d of %d", step, max_steps);
+  const BeamState s = beam_state_of(const_cast<void*>(beam), n, k, max_steps);
+  *tokens = s.seq + (long)((step - 1) & 1) * n * k * (max_steps + 2);
+  return kOk;
+}
+
 }  // namespace capnet

@@ -639,14 +639,15 @@ int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, f
 size_t capnet_vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_ws_bytes(rows, k, V); }
 
 static int vocab_topk_tail(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
-                           float* values, int* index, float* lse, capnet_stream_t stream, const unsigned* mask) {
+                           float* values, int* index, float* lse, capnet_stream_t stream, const unsigned* mask,
+                           bool select_only = false) {
   CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1, "vocab_topk: rows %d, V %d", rows, V);
   CAPNET_REQUIRE(k >= 1 && k <= 16 && k <= V, "vocab_topk: k=%d (1 <= k <= 16, k <= V = %d)", k, V);
   CAPNET_REQUIRE(vocab_topk_supported(H, k, V), "vocab_topk: unsupported H=%d", H);
   CAPNET_REQUIRE(h && w && workspace && values && index && lse, "vocab_topk: null argument");
   CAPNET_REQUIRE(aligned16(h) && aligned16(w) && aligned16(workspace), "vocab_topk: h, w and the workspace must be 16-B aligned");
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)lse % 4 == 0, "vocab_topk: output alignment");
-  return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream), mask);
+  return vocab_topk(h, w, b, rows, H, V, k, workspace, values, index, lse, S(stream), mask, select_only);
 }
 int capnet_vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* workspace,
                       float* values, int* index, float* lse, capnet_stream_t stream) {
@@ -924,13 +925,36 @@ int capnet_vocab_topk_masked(const float* h, const float* w, const float* b, int
   return vocab_topk_tail(h, w, b, rows, H, V, k, workspace, values, index, lse, stream, mask);
 }
 
+// ---- the fused beam step under constraints: the mask of a device beam's rows, and vocab_topk's select-only instance ----
+int capnet_beam_exclusion_mask(const void* beam, int n, int k, int max_steps, int step, int V, long long end_token,
+                               int no_repeat_ngram, int min_words, const int* banned, int n_banned, unsigned* mask,
+                               capnet_stream_t stream) {
+  const char* who = "beam_exclusion_mask";
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned};
+  if (int rc = beam_constraints_check(who, con)) return rc;
+  CAPNET_REQUIRE(beam && (size_t)beam % 4 == 0, "%s: the beam state is null or not 4-byte aligned", who);
+  CAPNET_REQUIRE(n >= 1 && k >= 1 && k <= 16 && max_steps >= 1 && (long)n * k < (1L << 24) &&
+                     (long)n * k * (max_steps + 2) < (1L << 28),
+                 "%s: n=%d k=%d max_steps=%d (n, max_steps >= 1; 1 <= k <= 16; n k < 2^24)", who, n, k, max_steps);
+  CAPNET_REQUIRE(V >= 1 && V <= (1 << 24), "%s: V %d (1 .. 2^24)", who, V);
+  CAPNET_REQUIRE(step >= 1 && step <= max_steps, "%s: step=%d (1 <= step <= max_steps = %d)", who, step, max_steps);
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "%s: mask is null or not 4-byte aligned", who);
+  return beam_exclusion_mask(beam, n, k, max_steps, step, V, end_token, con, mask, S(stream));
+}
+
+int capnet_vocab_topk_select(const float* h, const float* w, const float* b, int rows, int H, int V, int k, const unsigned* mask,
+                             void* workspace, float* values, int* index, float* lse, capnet_stream_t stream) {
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "vocab_topk_select: mask is null or not 4-byte aligned");
+  return vocab_topk_tail(h, w, b, rows, H, V, k, workspace, values, index, lse, stream, mask, true);
+}
+
 size_t capnet_vocab_topk_groups_ws_bytes(int groups, int rows_per_group, int k, int V) {
   return vocab_topk_groups_ws_bytes(groups, rows_per_group, k, V);
 }
 
-int capnet_vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
-                             int H, int V, int k, void* workspace, float* values, int* index, float* lse,
-                             capnet_stream_t stream) {
+static int vocab_topk_groups_tail(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                                  int H, int V, int k, void* workspace, float* values, int* index, float* lse,
+                                  capnet_stream_t stream, const unsigned* mask, bool select_only) {
   CAPNET_REQUIRE(groups >= 1 && groups <= 8, "vocab_topk: groups %d (1..8)", groups);
   CAPNET_REQUIRE(rows_per_group >= 1 && rows_per_group < (1 << 24) && V >= 1, "vocab_topk: rows per group %d, V %d",
                  rows_per_group, V);
@@ -941,11 +965,52 @@ int capnet_vocab_topk_groups(const float* h, const float* const* w, const float*
   CAPNET_REQUIRE((size_t)values % 4 == 0 && (size_t)index % 4 == 0 && (size_t)lse % 4 == 0, "vocab_topk: output alignment");
   for (int g = 0; g < groups; ++g)
     CAPNET_REQUIRE(w[g] && aligned16(w[g]), "vocab_topk: projection of group %d is null or not 16-B aligned", g);
-  return vocab_topk_groups(h, w, b, groups, rows_per_group, H, V, k, workspace, values, index, lse, S(stream));
+  return vocab_topk_groups(h, w, b, groups, rows_per_group, H, V, k, workspace, values, index, lse, S(stream), mask, select_only);
+}
+int capnet_vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                             int H, int V, int k, void* workspace, float* values, int* index, float* lse,
+                             capnet_stream_t stream) {
+  return vocab_topk_groups_tail(h, w, b, groups, rows_per_group, H, V, k, workspace, values, index, lse, stream, nullptr, false);
+}
+int capnet_vocab_topk_groups_masked(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                                    int H, int V, int k, const unsigned* mask, int select_only, void* workspace, float* values,
+                                    int* index, float* lse, capnet_stream_t stream) {
+  CAPNET_REQUIRE(mask && (size_t)mask % 4 == 0, "vocab_topk_groups_masked: mask is null or not 4-byte aligned");
+  CAPNET_REQUIRE(select_only == 0 || select_only == 1, "vocab_topk_groups_masked: select_only=%d (0 or 1)", select_only);
+  return vocab_topk_groups_tail(h, w, b, groups, rows_per_group, H, V, k, workspace, values, index, lse, stream, mask,
+                                select_only != 0);
 }
 
 size_t capnet_lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
   return lstm_beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps, fused_topk);
+}
+
+// the constraints of capnet_lstm_beam_decode[_groups]_constrained: the two existing checks, and no forced words on the fused step
+static int lstm_constraints_check(const char* who, const BeamConstraints& con, int fused_topk) {
+  if (int rc = beam_constraints_check(who, con)) return rc;
+  if (con.n_forced)      // (0: none, whatever `forced` points at)
+    if (int rc = beam_forced_check(who, con)) return rc;
+  CAPNET_REQUIRE(!(fused_topk && con.n_forced), "%s: forced words take the unfused step (fused_topk = 0)", who);
+  return kOk;
+}
+
+static int lstm_beam_decode_entry(const char* who, int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps,
+                                  long long start_token, long long end_token, const float* first_inputs, const float* emb,
+                                  const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                  const float* state0, void* workspace, float* slab, size_t slab_floats, int fused_topk,
+                                  int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                  capnet_stream_t stream, const BeamConstraints* con = nullptr) {
+  if (int rc = stack_decode_check(who, cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every,
+                                  fused_topk, 1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths,
+                                  err_flag))
+    return rc;
+  CAPNET_REQUIRE((long)n * k < (1L << 24), "%s: n k too large", who);
+  CAPNET_REQUIRE(!first_inputs || aligned16(first_inputs), "%s: first_inputs must be 16-B aligned", who);
+  if (con)
+    if (int rc = lstm_constraints_check(who, *con, fused_topk)) return rc;
+  return lstm_beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb, wcat, beff, Cw, Cb,
+                          state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
+                          S(stream), con);
 }
 
 int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
@@ -953,15 +1018,26 @@ int capnet_lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, i
                             const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
                             float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                             int* steps_run, int* err_flag, capnet_stream_t stream) {
-  if (int rc = stack_decode_check("lstm_beam_decode", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, poll_every,
-                                  fused_topk, 1, &emb, wcat, beff, &Cw, state0, workspace, slab, slab_floats, seqs, lengths,
-                                  err_flag))
-    return rc;
-  CAPNET_REQUIRE((long)n * k < (1L << 24), "lstm_beam_decode: n k too large");
-  CAPNET_REQUIRE(!first_inputs || aligned16(first_inputs), "lstm_beam_decode: first_inputs must be 16-B aligned");
-  return lstm_beam_decode(cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb, wcat, beff, Cw, Cb,
-                          state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
-                          S(stream));
+  return lstm_beam_decode_entry("lstm_beam_decode", cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token, first_inputs, emb,
+                                wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths,
+                                steps_run, err_flag, stream);
+}
+
+size_t capnet_lstm_beam_decode_constrained_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
+  return lstm_beam_decode_ws_bytes(nlayers, n, k, H, V, max_steps, fused_topk, true);
+}
+
+int capnet_lstm_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps,
+                                        long long start_token, long long end_token, const float* first_inputs, const float* emb,
+                                        const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                        const float* state0, void* workspace, float* slab, size_t slab_floats, int fused_topk,
+                                        int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                        capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                        int n_banned, const int* forced, int n_forced) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
+  return lstm_beam_decode_entry("lstm_beam_decode_constrained", cell, nlayers, n, k, E, H, V, max_steps, start_token, end_token,
+                                first_inputs, emb, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, fused_topk, poll_every,
+                                seqs, lengths, steps_run, err_flag, stream, &con);
 }
 
 size_t capnet_lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps,
@@ -970,22 +1046,55 @@ size_t capnet_lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, i
 }
 
 // n below: the sentences of one group; the checks are capnet_lstm_beam_decode's at groups x n sentences
+static int lstm_beam_decode_groups_entry(const char* who, int cell, int nlayers, int groups, int n, int k, int E, int H, int V,
+                                         int max_steps, long long start_token, long long end_token, const float* const* emb,
+                                         const float* const* wcat, const float* const* beff, const float* const* Cw,
+                                         const float* const* Cb, const float* state0, void* workspace, float* slab,
+                                         size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
+                                         int* steps_run, int* err_flag, capnet_stream_t stream,
+                                         const BeamConstraints* con = nullptr) {
+  if (int rc = stack_decode_check(who, cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, poll_every,
+                                  fused_topk, groups, emb, wcat, beff, Cw, state0, workspace, slab, slab_floats, seqs, lengths,
+                                  err_flag))
+    return rc;
+  CAPNET_REQUIRE((long)groups * n * k < (1L << 24), "%s: n k too large", who);
+  for (int g = 0; g < groups; ++g)
+    CAPNET_REQUIRE(aligned16(emb[g]), "%s: emb and Cw must be 16-B aligned (group %d)", who, g);
+  if (con)
+    if (int rc = lstm_constraints_check(who, *con, fused_topk)) return rc;
+  return lstm_beam_decode_groups(cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
+                                 state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
+                                 S(stream), con);
+}
+
 int capnet_lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
                                    long long start_token, long long end_token, const float* const* emb,
                                    const float* const* wcat, const float* const* beff, const float* const* Cw,
                                    const float* const* Cb, const float* state0, void* workspace, float* slab,
                                    size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                                    int* steps_run, int* err_flag, capnet_stream_t stream) {
-  if (int rc = stack_decode_check("lstm_beam_decode", cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, poll_every,
-                                  fused_topk, groups, emb, wcat, beff, Cw, state0, workspace, slab, slab_floats, seqs, lengths,
-                                  err_flag))
-    return rc;
-  CAPNET_REQUIRE((long)groups * n * k < (1L << 24), "lstm_beam_decode: n k too large");
-  for (int g = 0; g < groups; ++g)
-    CAPNET_REQUIRE(aligned16(emb[g]), "lstm_beam_decode: emb and Cw must be 16-B aligned (group %d)", g);
-  return lstm_beam_decode_groups(cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff, Cw, Cb,
-                                 state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs, lengths, steps_run, err_flag,
-                                 S(stream));
+  return lstm_beam_decode_groups_entry("lstm_beam_decode", cell, nlayers, groups, n, k, E, H, V, max_steps, start_token, end_token, emb,
+                                       wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, fused_topk, poll_every, seqs,
+                                       lengths, steps_run, err_flag, stream);
+}
+
+size_t capnet_lstm_beam_decode_groups_constrained_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps,
+                                                           int fused_topk) {
+  return lstm_beam_decode_groups_ws_bytes(nlayers, groups, n, k, H, V, max_steps, fused_topk, true);
+}
+
+int capnet_lstm_beam_decode_groups_constrained(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                                               long long start_token, long long end_token, const float* const* emb,
+                                               const float* const* wcat, const float* const* beff, const float* const* Cw,
+                                               const float* const* Cb, const float* state0, void* workspace, float* slab,
+                                               size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
+                                               int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                               int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                               const int* forced, int n_forced) {
+  const BeamConstraints con{no_repeat_ngram, min_words, banned, n_banned, forced, n_forced};
+  return lstm_beam_decode_groups_entry("lstm_beam_decode_groups_constrained", cell, nlayers, groups, n, k, E, H, V, max_steps,
+                                       start_token, end_token, emb, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats,
+                                       fused_topk, poll_every, seqs, lengths, steps_run, err_flag, stream, &con);
 }
 
 int capnet_att_decode_supported(int E, int C, int H, int A, int P, int k, int nlayers) {

@@ -214,7 +214,8 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
 // ws: [state A | state B] ([n k][2L][H] each) | h_top [n k][H] | logits [n k][V] | words A | words B | parent_rows (int64
 // [n k] each) | the beam_state_bytes block; every part starts 16-B aligned. fused (capnet_lstm_beam_decode on
 // capnet_vocab_topk): no logits block; in its place values f32 [n k][k] | index int32 [n k][k] | lse f32 [n k] |
-// vocab_topk's workspace
+// vocab_topk's workspace. fused under constraints: behind everything (at `total`, so no other offset moves and
+// capnet_beam_nbest finds the state where it was) the step's selection mask, sample_mask_bytes(n k, V)
 struct BeamDecodeWs {
   size_t state, h_top, logits, words, parent, beam, total;   // byte offsets (state B at state + (h_top - state) / 2)
   size_t tk_values, tk_index, tk_lse, tk_ws;                 // fused only
@@ -257,7 +258,7 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
                      int poll_every, long long* seqs, int* lengths, int* steps_run, hipStream_t s, Step&& step_fn,
                      bool fused = false, int groups = 1, const float* const* Cwg = nullptr, const float* const* Cbg = nullptr,
                      void* trace = nullptr, int* trace_rows = nullptr,   // (the row trace: beam_advance's, logits form only)
-                     const BeamConstraints* con = nullptr,                // (constraints: the logits form only)
+                     const BeamConstraints* con = nullptr,   // (constraints: beam_advance's forms; fused: the select-only top-k)
                      const BeamTeams* dv = nullptr) {                     // (diverse search: the logits form only)
   // dv: the step still runs on n images of k rows; the beam state is that of n teams searches of k / teams beams and lies
   // in the caller's block dv->beam, not in the layout's slot (which is sized for (n, k))
@@ -277,6 +278,9 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
                          reinterpret_cast<long long*>(p + w.words + (w.parent - w.words) / 2)};
   long long* parent = reinterpret_cast<long long*>(p + w.parent);
   void* beam = dv ? dv->beam : p + w.beam;
+  // fused under constraints: one more launch per step writes what each row may not select, and vocab_topk's select-only
+  // instance leaves those words out of its candidates (not out of lse); beam_advance_topk is the one it was
+  unsigned* sel_mask = fused && con ? reinterpret_cast<unsigned*>(p + w.total) : nullptr;
   const int* live_total = nullptr;
   if (int rc = beam_live(beam, sn, sk, max_steps, &live_total, nullptr, nullptr)) return rc;
   if (state0) CAPNET_HIP_CHECK(hipMemcpyAsync(state[0], state0, st_bytes, hipMemcpyDeviceToDevice, s));
@@ -288,9 +292,10 @@ static int beam_loop(int nlayers, int n, int k, int H, int V, int max_steps, lon
     // step 1: every beam is at its own (initial) row; afterwards the rows the previous beam_advance chose
     int rc = step_fn(words[(step - 1) & 1], step == 1 ? nullptr : parent, state[(step - 1) & 1], state[step & 1], h_top);
     if (fused) {
+      if (rc == kOk && sel_mask) rc = beam_exclusion_mask(beam, n, k, max_steps, step, V, end_token, *con, sel_mask, s);
       if (rc == kOk)
-        rc = Cwg ? vocab_topk_groups(h_top, Cwg, Cbg, groups, rpg, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s)
-                 : vocab_topk(h_top, Cw, Cb, nk, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s);
+        rc = Cwg ? vocab_topk_groups(h_top, Cwg, Cbg, groups, rpg, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s, sel_mask, true)
+                 : vocab_topk(h_top, Cw, Cb, nk, H, V, k, tk_ws, tk_values, tk_index, tk_lse, s, sel_mask, true);
       if (rc == kOk)
         rc = beam_advance_topk(beam, tk_values, tk_index, tk_lse, V, n, k, max_steps, step, end_token, words[step & 1], parent, s);
     } else {
@@ -333,17 +338,23 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
 
 // ---- capnet.seq2seq's beam search: the same loop from a given state, step 1 on given inputs (EncoderRNN's feature
 // column) when first_inputs is set, the projection and selection fused (vocab_topk.hip) or as beam_decode's ----
-size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk) {
+// the selection mask of the fused constrained step lies behind a layout's own bytes (beam_loop places it there)
+static size_t with_select_mask(size_t own, int nk, int V, bool fused, bool constrained) {
+  return own && fused && constrained ? own + sample_mask_bytes(nk, V) : own;
+}
+
+size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, bool constrained) {
   if (nlayers < 1 || nlayers > 8 || n < 1 || H < 1 || V < 1 || k > V || !beam_state_bytes(n, k, max_steps)) return 0;
   if ((long)n * k >= (1L << 24) || (fused_topk && !vocab_topk_supported(H, k, V))) return 0;
-  return beam_decode_layout(nlayers, n, k, H, V, max_steps, fused_topk != 0).total;
+  return with_select_mask(beam_decode_layout(nlayers, n, k, H, V, max_steps, fused_topk != 0).total, n * k, V, fused_topk != 0,
+                          constrained);
 }
 
 int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                      long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
                      const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                      size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths, int* steps_run,
-                     int* err_flag, hipStream_t s) {
+                     int* err_flag, hipStream_t s, const BeamConstraints* con) {
   return beam_loop(nlayers, n, k, H, V, max_steps, start_token, end_token, Cw, Cb, state0, ws, slab, slab_floats, poll_every, seqs,
                    lengths, steps_run, s,
                    [&](const long long* tok, const long long* parent, const float* sin, float* sout, float* h_top) {
@@ -351,22 +362,24 @@ int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, i
                      return stacked_decode_step(cell, nlayers, n * k, E, H, V, given ? nullptr : tok, given ? first_inputs : emb,
                                                 wcat, beff, sin, sout, h_top, err_flag, s, parent);
                    },
-                   fused_topk != 0);
+                   fused_topk != 0, 1, nullptr, nullptr, nullptr, nullptr, con);
 }
 
 // ---- every emotion decoder of capnet.seq2seq in one search: groups x n sentences, group g on its own embedding, LSTM
 // weights and projection (the decode step on a (H / 4, groups) grid with per-group tables, parents gathered in the kernel)
-size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk) {
+size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk,
+                                        bool constrained) {
   if (groups < 1 || groups > 8 || n < 1 || n >= (1 << 24)) return 0;
   if (!lstm_beam_decode_ws_bytes(nlayers, groups * n, k, H, V, max_steps, fused_topk)) return 0;
-  return beam_decode_layout(nlayers, groups * n, k, H, V, max_steps, fused_topk != 0, groups).total;
+  return with_select_mask(beam_decode_layout(nlayers, groups * n, k, H, V, max_steps, fused_topk != 0, groups).total,
+                          groups * n * k, V, fused_topk != 0, constrained);
 }
 
 int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
                             long long start_token, long long end_token, const float* const* emb, const float* const* wcat,
                             const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
                             void* ws, float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
-                            int* lengths, int* steps_run, int* err_flag, hipStream_t s) {
+                            int* lengths, int* steps_run, int* err_flag, hipStream_t s, const BeamConstraints* con) {
   const int nq = groups * n;
   return beam_loop(nlayers, nq, k, H, V, max_steps, start_token, end_token, nullptr, nullptr, state0, ws, slab, slab_floats,
                    poll_every, seqs, lengths, steps_run, s,
@@ -374,7 +387,7 @@ int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int
                      return stacked_decode_step(cell, nlayers, nq * k, E, H, V, tok, emb[0], wcat, beff, sin, sout, h_top, err_flag,
                                                 s, parent, groups, emb);
                    },
-                   fused_topk != 0, groups, Cw, Cb);
+                   fused_topk != 0, groups, Cw, Cb, nullptr, nullptr, con);
 }
 
 // ---- the same loop for the attention decoders: the step is att_decode_step (z, the two attention launches, layer 0 on

@@ -274,6 +274,8 @@ int beam_finish(const void* beam, int n, int k, int max_steps, long long end_tok
 int beam_nbest(const void* beam, int n, int k, int max_steps, float length_penalty, long long* seqs, int* lengths,
                float* scores, int* counts, hipStream_t stream, const void* trace = nullptr, int* rows = nullptr);
 int beam_live(const void* beam, int n, int k, int max_steps, const int** live_total, const int** live, const float** scores);
+// (the [n k] hypotheses step `step` reads: rows of max_steps + 2 int32, `step` tokens each, <start> first)
+int beam_tokens(const void* beam, int n, int k, int max_steps, int step, const int** tokens);
 // ---- seq_kernels.hip again
 int gather_rows(const float* src, const int* idx, float* out, int rows, int C, hipStream_t stream);
 int colsum(const float* x, long ld, int rows, int C, float* out, int accumulate, hipStream_t stream,
@@ -379,15 +381,17 @@ int beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int ma
 bool vocab_topk_supported(int H, int k, int V);
 size_t vocab_topk_ws_bytes(int rows, int k, int V);
 // (mask: sample_exclude.hip's exclusion mask [rows][ceil(V / 32)] or null -- a set bit is not pickable, lse is then over the
-// allowed entries; null: the kernel without the mask, bit for bit)
+// allowed entries; null: the kernel without the mask, bit for bit. select_only (the constrained beam search's): a
+// set bit leaves the k best alone -- lse stays the log-sum-exp over EVERY entry, the unmasked launch's bit for bit)
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
-               int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr);
+               int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr, bool select_only = false);
 // weight groups, as vocab_argmax_groups: rows = groups x rpg, group-major; group g's rows on w[g] / b[g] (host-side pointer
 // tables, b or any b[g] may be null) in the same launch, one arrival counter and one block of partials per group (ws:
 // vocab_topk_groups_ws_bytes, its first 16 groups bytes zero before the first use); outputs [groups rpg][k] / [groups rpg]
 size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V);
 int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
-                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr);
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask = nullptr,
+                      bool select_only = false);
 // vocab_sample.hip: per row a draw from softmax((h[r] . W + b) inv_T) by Gumbel-max on sample_rng.h's stream keyed (seed,
 // step, row0 + r, v), one launch, no logits in memory: tok[r] / ids[r ld] the token, logp[r ld] its log-probability (each
 // optional; ws: vocab_sample_ws_bytes, its first 16 bytes zero before the first use). sample_pick: the same draw among
@@ -421,6 +425,10 @@ int sample_excl_check(const char* who, const SampleExcl& c);
 // the mask of stream step t: ids[r ld + 0 .. t - 1] the row's words so far, start_tokens[r] its <start> (null: none)
 int sample_exclusion_mask(const long long* ids, long ld, const long long* start_tokens, int rows, int t, int V,
                           const SampleExcl& c, unsigned* mask, hipStream_t stream);
+// the same mask of the [n k] rows of a device beam search at step `step` (1-based), from the hypotheses in its state (c's
+// forced words are not the mask's: a forced search selects from logits)
+int beam_exclusion_mask(const void* beam, int n, int k, int max_steps, int step, int V, long long end_token,
+                        const BeamConstraints& c, unsigned* mask, hipStream_t stream);
 // -inf at the mask's set bits of logits [rows][ld]
 int mask_logits(float* logits, int rows, long ld, int V, const unsigned* mask, hipStream_t stream);
 // vocab_nucleus.hip: nucleus (top-p) sampling, 0 < top_p < 1: sample_rows' / sample_pick's draw among the smallest set of
@@ -461,22 +469,25 @@ int att_sample_decode(int cell, int nlayers, int n, int m, int P, int A, int C, 
                       size_t slab_floats, long long* ids, float* logp, float* state_out, int* err_flag, hipStream_t s);
 // decode_loops.hip: beam_decode's loop from a given state (one weight group), step 1 on first_inputs [n k][E] when set;
 // fused_topk: a step's projection and selection as vocab_topk + beam_advance_topk (no logits block in ws, slab unused), else
-// beam_decode's
-size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
+// beam_decode's. con: the constrained search -- unfused, beam_advance's constrained or forced form; fused (no
+// forced words), beam_exclusion_mask into a mask BEHIND the workspace's other parts (constrained = true in the size query:
+// sample_mask_bytes(n k, V) more, fused only) and vocab_topk's select-only instance in front of the unchanged beam_advance_topk
+size_t lstm_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk, bool constrained = false);
 int lstm_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
                      long long end_token, const float* first_inputs, const float* emb, const float* const* wcat,
                      const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* ws, float* slab,
                      size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths, int* steps_run,
-                     int* err_flag, hipStream_t s);
+                     int* err_flag, hipStream_t s, const BeamConstraints* con = nullptr);
 // the same loop over groups x n sentences, group-major, group g on emb[g] / wcat[l] + g 4H (kin + H) / beff[l] + g 4H / Cw[g] /
 // Cb[g] (host-side pointer tables; Cb or any Cb[g] may be null): per step the gathered decode step on per-group tables,
 // then vocab_topk_groups + beam_advance_topk, or one sgemm_splitk per group into its row block of the logits + beam_advance
-size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk);
+size_t lstm_beam_decode_groups_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps, int fused_topk,
+                                        bool constrained = false);
 int lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
                             long long start_token, long long end_token, const float* const* emb, const float* const* wcat,
                             const float* const* beff, const float* const* Cw, const float* const* Cb, const float* state0,
                             void* ws, float* slab, size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
-                            int* lengths, int* steps_run, int* err_flag, hipStream_t s);
+                            int* lengths, int* steps_run, int* err_flag, hipStream_t s, const BeamConstraints* con = nullptr);
 // beam_decode's loop around att_decode_step (att1 = encoder_att(feat), once per call, is the caller's; state0 is required)
 size_t att_beam_decode_ws_bytes(int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps);
 int att_beam_decode(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,

@@ -1,12 +1,17 @@
-// Sampled decoding with exclusions: what a row may not draw at a step, as a bit mask the draws read.
+// Exclusions as a bit mask: what a row may not draw -- or, in the fused beam step, may not select -- at a
+// step, for the vocabulary kernels' epilogues to read.
 //   mask [rows][W] of 32-bit words, W = ceil(V / 32): bit v & 31 of word v >> 5 of row r is set where word v is excluded on
 //   launch row r at this step. kVocCols is 32, so workgroup b of the vocabulary kernels needs exactly word b of every row.
-// sample_exclusion_mask_kernel: the mask of stream step t (0-based) from what is on the device -- capnet.beam.banned_words
-// on the hypothesis [start[r], ids[r][0] .. ids[r][t - 1]] at step t + 1 (start null: the words alone), the tokens as drawn
-// whether or not the row has emitted <end>:
-//   every word of `banned`; <end> while t + 1 <= min_words; g = no_repeat_ngram >= 1 and n >= g tokens: for every start
-//   position e of a g-gram whose first g - 1 tokens equal the hypothesis' last g - 1, the token behind them (g = 1: every
-//   token; a context seen several times excludes several words). A word outside [0, V) is never an address.
+// exclusion_mask_kernel<T>: capnet.beam.banned_words at step `step` on the hypothesis [start[r], words[r][0 .. m)] (start
+// null: the words alone), ONE kernel over both token sources --
+//   the sampler's (sample_exclusion_mask): T = int64, words = the caller's ids matrix, m = t drawn words, <start> beside
+//     them, step = t + 1, the tokens as drawn whether or not the row has emitted <end>;
+//   the beam state's (beam_exclusion_mask): T = int32, words = the rows of BeamState.seq[(step - 1) & 1] (row stride
+//     max_steps + 2), m = step tokens with <start> already first, no start array -- the tokens BeamExclState reads.
+// The rule: every word of `banned`; <end> while step <= min_words; g = no_repeat_ngram >= 1 and n >= g tokens: for every
+//   start position e of a g-gram whose first g - 1 tokens equal the hypothesis' last g - 1, the token behind them (g = 1:
+//   every token; a context seen several times excludes several words). A word outside [0, V) is never an address (the rows
+//   of dead beam slots hold stale tokens; their masks are never read).
 // One workgroup per row. The row's mask is built in LDS a chunk of kMaskChunk words at a time (one chunk up to V = 65536):
 // zero, LDS atomic OR per excluded word of the chunk, vector stores of the whole chunk -- every word of the row is written,
 // so the mask needs no clearing between steps.
@@ -20,14 +25,19 @@ namespace capnet {
 constexpr int kMaskThreads = 256;
 constexpr int kMaskChunk = 2048;      // mask words per pass: 8 KB of LDS
 
-__global__ __launch_bounds__(kMaskThreads) void sample_exclusion_mask_kernel(
-    const long long* __restrict__ ids, long ld, const long long* __restrict__ start, int t, int V, int W, long long end_token,
+template <class T>
+__global__ __launch_bounds__(kMaskThreads) void exclusion_mask_kernel(
+    const T* __restrict__ ids, long ld, const long long* __restrict__ start, int m, int step, int V, int W, long long end_token,
     int g, int min_words, const int* __restrict__ banned, int n_banned, unsigned* __restrict__ mask) {
   __shared__ unsigned bits[kMaskChunk];
   const int row = blockIdx.x, tid = threadIdx.x;
-  const long long* words = ids + (long)row * ld;     // read at 0 .. t - 1 only
-  const int lead = start ? 1 : 0, n = t + lead, step = t + 1;
-  auto tok = [&](int i) -> long long { return i < lead ? start[row] : words[i - lead]; };
+  const T* words = ids + (long)row * ld;             // read at 0 .. m - 1 only
+  const int lead = start ? 1 : 0, n = m + lead;
+  // <start> is read ONCE, here, behind a branch the whole workgroup takes alike. Read inside tok() its address is uniform but
+  // its condition is per thread, and the compiler then issues the load as a scalar load in a block it enters with an empty
+  // exec mask too: with start null that is a load from address 8 row.
+  const long long first = start ? start[row] : 0;
+  auto tok = [&](int i) -> long long { return i < lead ? first : (long long)words[i - lead]; };
   unsigned* out = mask + (long)row * W;
   for (int c0 = 0; c0 < W; c0 += kMaskChunk) {
     const int cw = min(kMaskChunk, W - c0);
@@ -82,8 +92,24 @@ int sample_exclusion_mask(const long long* ids, long ld, const long long* start_
                           const SampleExcl& c, unsigned* mask, hipStream_t stream) {
   CAPNET_REQUIRE(rows >= 1 && rows < (1 << 24) && V >= 1 && V <= (1 << 24) && t >= 0 && (ids || !t) && mask,
                  "sample_exclusion_mask: rows %d, V %d, t %d", rows, V, t);
-  hipLaunchKernelGGL(sample_exclusion_mask_kernel, dim3(rows), dim3(kMaskThreads), 0, stream, ids, ld, start_tokens, t, V,
-                     sample_mask_words(V), c.end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, mask);
+  hipLaunchKernelGGL(exclusion_mask_kernel<long long>, dim3(rows), dim3(kMaskThreads), 0, stream, ids, ld, start_tokens, t, t + 1,
+                     V, sample_mask_words(V), c.end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, mask);
+  CAPNET_LAUNCH_CHECK();
+  return kOk;
+}
+
+// the same kernel on the hypotheses a device beam search keeps: row r of the mask is row r of the decode step (image r / k,
+// slot r % k), its `step` tokens those of BeamState.seq[(step - 1) & 1]
+int beam_exclusion_mask(const void* beam, int n, int k, int max_steps, int step, int V, long long end_token,
+                        const BeamConstraints& c, unsigned* mask, hipStream_t stream) {
+  CAPNET_REQUIRE(beam && mask && n >= 1 && k >= 1 && (long)n * k < (1L << 24) && V >= 1 && V <= (1 << 24) && step >= 1 &&
+                     step <= max_steps,
+                 "beam_exclusion_mask: n %d, k %d, V %d, step %d of %d", n, k, V, step, max_steps);
+  const int* tokens = nullptr;
+  if (int rc = beam_tokens(beam, n, k, max_steps, step, &tokens)) return rc;
+  hipLaunchKernelGGL(exclusion_mask_kernel<int>, dim3(n * k), dim3(kMaskThreads), 0, stream, tokens, (long)(max_steps + 2),
+                     (const long long*)nullptr, step, step, V, sample_mask_words(V), end_token, c.no_repeat_ngram, c.min_words,
+                     c.banned, c.n_banned, mask);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

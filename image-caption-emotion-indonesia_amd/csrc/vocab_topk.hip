@@ -37,12 +37,18 @@ struct VocabTopkArgs {
   float* lse;                // [groups rpg]
   int rpg, H, V, k;          // rows per group: workgroup (., g) owns rows [g rpg, (g + 1) rpg)
   VocabGroups g;
-  const unsigned* mask;      // MASKED only: [groups rpg][workgroups], bit c of word b = entry 32 b + c is not pickable on that row
+  const unsigned* mask;      // masked instances only: [groups rpg][workgroups], bit c of word b = entry 32 b + c of that row
 };
 
-// MASKED (sample_exclude.hip): an entry whose mask bit is set is treated as a -inf logit is, so the k best and lse
-// are those of the allowed entries; one 4-byte load per half-wave. The unmasked kernel is an instance of its own.
-template <int NJ, int TM, bool MASKED>
+// The three instances by what a set mask bit means (one 4-byte load per half-wave; the unmasked kernel reads no mask):
+//   kVtPickMask (the sampler's, sample_exclude.hip): the entry is treated as a -inf logit is, so the k best AND lse
+//     are those of the allowed entries -- the distribution renormalised over them;
+//   kVtSelectMask (the constrained beam search's): the entry only leaves the SELECTION -- it is not ranked, not
+//     counted and never stored as a candidate, but (m_w, s_w) is formed from every finite in-range logit exactly as in the
+//     unmasked instance, so lse is the unmasked launch's bit for bit and a survivor's score stays the model's own
+//     log-probability.
+constexpr int kVtNoMask = 0, kVtPickMask = 1, kVtSelectMask = 2;
+template <int NJ, int TM, int MASK>
 __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   const int rows = a.rpg, k = a.k;
   // this group's rows, numbered from 0 below: its slice of h and of the outputs, its blocks of stat and cand, its counter
@@ -58,11 +64,13 @@ __global__ __launch_bounds__(512) void vocab_topk_kernel(VocabTopkArgs a) {
   unsigned long long* cand = gcand + (long)blockIdx.x * rows * k;
   vocab_front<NJ, TM>(a.h + rbeg * a.H, rows, a.g.w[grp], a.g.b[grp], a.H, a.V, [&](int row, bool valid, float v) {
     const int lane = threadIdx.x & 63, ec = lane & 31, ecol = blockIdx.x * kVocCols + ec;   // the thread's entry
-    bool ok = ecol < a.V && v > -INFINITY;                // NaN fails the comparison
-    if (MASKED) ok = ok && !(valid && ((a.mask[(rbeg + row) * gridDim.x + blockIdx.x] >> ec) & 1u));
+    const bool fin = ecol < a.V && v > -INFINITY;         // NaN fails the comparison
+    bool ok = fin;                                        // `fin` feeds the statistic, `ok` the rank, the count and the stores
+    if (MASK != kVtNoMask) ok = ok && !(valid && ((a.mask[(rbeg + row) * gridDim.x + blockIdx.x] >> ec) & 1u));
     const float pv = ok ? v : -INFINITY;
     float mx, e;
-    vocab_half_wave_stat(ok, pv, mx, e);
+    if (MASK == kVtSelectMask) vocab_half_wave_stat(fin, fin ? v : -INFINITY, mx, e);
+    else vocab_half_wave_stat(ok, pv, mx, e);
     int rank = 0;
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
@@ -178,12 +186,13 @@ size_t vocab_topk_groups_ws_bytes(int groups, int rpg, int k, int V) {
 size_t vocab_topk_ws_bytes(int rows, int k, int V) { return vocab_topk_groups_ws_bytes(1, rows, k, V); }
 
 int vocab_topk(const float* h, const float* w, const float* b, int rows, int H, int V, int k, void* ws, float* values,
-               int* index, float* lse, hipStream_t stream, const unsigned* mask) {
-  return vocab_topk_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, k, ws, values, index, lse, stream, mask);
+               int* index, float* lse, hipStream_t stream, const unsigned* mask, bool select_only) {
+  return vocab_topk_groups(h, &w, b ? &b : nullptr, 1, rows, H, V, k, ws, values, index, lse, stream, mask, select_only);
 }
 
 int vocab_topk_groups(const float* h, const float* const* w, const float* const* b, int groups, int rpg, int H, int V, int k,
-                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask) {
+                      void* ws, float* values, int* index, float* lse, hipStream_t stream, const unsigned* mask,
+                      bool select_only) {
   CAPNET_REQUIRE(groups >= 1 && groups <= kVocMaxGroups && rpg >= 1 && vocab_topk_supported(H, k, V),
                  "vocab_topk: %d groups of %d rows, H %d, V %d, k %d", groups, rpg, H, V, k);
   VocabTopkArgs a;
@@ -197,8 +206,9 @@ int vocab_topk_groups(const float* h, const float* const* w, const float* const*
   a.mask = mask;
   const dim3 grid(vocab_workgroups(V), groups), block(64 * kVocWaves);
   dispatch_nj(H, [&](auto nj) {   // two row tiles per pass where their operands fit beside the weights
-    if (mask) hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, false>), grid, block, 0, stream, a);
+    if (mask && select_only) hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, kVtSelectMask>), grid, block, 0, stream, a);
+    else if (mask) hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, kVtPickMask>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((vocab_topk_kernel<nj, nj <= 8 ? 2 : 1, kVtNoMask>), grid, block, 0, stream, a);
   });
   CAPNET_LAUNCH_CHECK();
   return kOk;

@@ -359,15 +359,16 @@ def draw_step(logits, temperature, top_k, seed, step, top_p=1.0, greedy_stride=0
 def sample_steps(step, steps, tokens, state, temperature, top_k, seed, draw_kw, exclude=None, V=None, end_token=None):
     """The composed sampled decode: per stream step t, step(t, tokens, state) -> (logits [rows, V], state'), then draw_step
     (draw_kw: its top_p / greedy_stride keywords, where set) -> the next tokens. tokens: the rows' start tokens (None where
-    step 0 does not read them). exclude (an active Constraints, with V and end_token): per step ops.sample_exclusion_mask
-    on the rows' words so far -- which the kernel reads from one [rows, steps] block -- in front of the draw.
+    step 0 does not read them; the hypotheses are then the words alone). exclude (an active Constraints, with V and end_token): per step
+    ops.sample_exclusion_mask on the rows' words so far -- which the kernel reads from one [rows, steps] block -- in front of the draw.
     Returns (ids [rows, steps] int64, logp [rows, steps] float32, the final state)."""
     ids, logp = [], []
-    if exclude is not None:
-        start, so_far, mask = tokens, torch.empty((tokens.shape[0], steps), dtype=torch.int64, device=tokens.device), None
+    start, so_far, mask = tokens, None, None
     for t in range(steps):
         logits, state = step(t, tokens, state)
         if exclude is not None:
+            if so_far is None:       # (sized by the step's rows: there are no start tokens where step 0 runs on given inputs)
+                so_far = torch.empty((logits.shape[0], steps), dtype=torch.int64, device=logits.device)
             mask = ops.sample_exclusion_mask(so_far, start, t, V, end_token, exclude, out=mask)
             tokens, lp = draw_step(logits, temperature, top_k, seed, t, **draw_kw, mask=mask)
             so_far[:, t] = tokens

@@ -390,6 +390,27 @@ def beam_advance_topk(beam, values, index, lse, step, end_token, next_words, par
           "capnet_beam_advance_topk")
 
 
+def beam_exclusion_mask(beam, step, V, end_token, constraints, out=None):
+    """What each of the n k rows of `beam` (a BeamState) may not select at step `step` (1-based), from the hypotheses in the
+    state (capnet_beam_exclusion_mask; the fused beam step's one extra launch): int32 [n k, ceil(V / 32)], bit v &
+    31 of word v >> 5 of row r set where capnet.beam.banned_words(row r's `step` tokens, step, end_token, constraints) holds
+    v -- sample_exclusion_mask's layout, for vocab_topk(mask=, select_only=True). constraints: a capnet.beam.Constraints;
+    forced words are not the mask's. Rows of dead slots get a mask nobody reads. out: a mask to overwrite."""
+    who = "beam_exclusion_mask"
+    if has_forced(constraints):
+        raise CapnetError("%s: forced words are selected from logits, not through a mask" % who)
+    step, V, rows = int(step), int(V), beam.n * beam.k
+    if not 1 <= step <= beam.max_steps or not 1 <= V <= SAMPLE_MAX_ROWS:
+        raise CapnetError("%s: step %d of %d, V %d" % (who, step, beam.max_steps, V))
+    if out is None:
+        out = torch.empty((rows, mask_words(V)), dtype=torch.int32, device=beam.words.device)
+    _check_mask(who, out, rows, V)
+    check(_lib.lib().capnet_beam_exclusion_mask(ptr(beam.words), beam.n, beam.k, beam.max_steps, step, V, int(end_token),
+                                                *constraint_args(constraints, beam.words.device), ptr(out), current_stream()),
+          "capnet_beam_exclusion_mask")
+    return out
+
+
 def beam_finish(beam, end_token):
     """capnet_beam_finish -> (seqs int64 [n, max_steps + 2], lengths int32 [n], packed): the two are views of the one
     int64 buffer `packed`, so a caller takes both to the host in one copy."""
@@ -934,13 +955,15 @@ def vocab_topk_workspace(rows, k, V, device):
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
-def vocab_topk(h, w, b=None, k=5, workspace=None, mask=None):
+def vocab_topk(h, w, b=None, k=5, workspace=None, mask=None, select_only=False):
     """(values [rows, k] float32, index [rows, k] int32, lse [rows] float32) of the rows' logits h[r] . w[v] + b[v]
     (capnet_vocab_topk: the projection, the k best per row -- logit descending, index ascending -- and the row's
     log-sum-exp in one launch, no logits in memory). h [rows, H], w [V, H], b [V]; H in DECODE_HIDDEN; 1 <= k <= 16, k <= V.
     A NaN or -inf logit is never picked; a row with fewer than k pickable entries ends in (-inf, -1).
     mask (sample_exclusion_mask's, int32 [rows, ceil(V / 32)]; capnet_vocab_topk_masked): a word whose bit is set is not
-    pickable either -- the k best of the allowed words, lse over the allowed words. None: capnet_vocab_topk."""
+    pickable either -- the k best of the allowed words, lse over the allowed words. None: capnet_vocab_topk.
+    select_only (with a mask; capnet_vocab_topk_select, the constrained beam search's meaning): a word whose bit is set only
+    leaves the k best -- lse stays the log-sum-exp over every word, capnet_vocab_topk's bit for bit."""
     _need_cuda(h, w, b)
     h, w = _c(h.detach()), _c(w.detach())
     b = None if b is None else _c(b.detach())
@@ -960,10 +983,13 @@ def vocab_topk(h, w, b=None, k=5, workspace=None, mask=None):
     values = torch.empty((rows, k), dtype=torch.float32, device=h.device)
     index = torch.empty((rows, k), dtype=torch.int32, device=h.device)
     lse = torch.empty(rows, dtype=torch.float32, device=h.device)
+    if select_only and mask is None:
+        raise CapnetError("vocab_topk: select_only needs a mask")
     if mask is not None:
         mask = _check_mask("vocab_topk", mask, rows, V)
-        check(_lib.lib().capnet_vocab_topk_masked(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(mask), ptr(workspace), ptr(values),
-                                                  ptr(index), ptr(lse), current_stream()), "capnet_vocab_topk_masked")
+        name = "capnet_vocab_topk_select" if select_only else "capnet_vocab_topk_masked"
+        check(getattr(_lib.lib(), name)(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(mask), ptr(workspace), ptr(values), ptr(index),
+                                        ptr(lse), current_stream()), name)
         return values, index, lse
     check(_lib.lib().capnet_vocab_topk(ptr(h), ptr(w), ptr(b), rows, H, V, k, ptr(workspace), ptr(values), ptr(index), ptr(lse),
                                        current_stream()), "capnet_vocab_topk")
@@ -1319,10 +1345,11 @@ def vocab_topk_groups_workspace(groups, rows_per_group, k, V, device):
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
-def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
+def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None, mask=None, select_only=False):
     """vocab_topk of len(ws) projections in one launch (capnet_vocab_topk_groups): h [groups rows, H], group-major; block g
     on ws[g] [V, H] / bs[g] [V] (bs or any bs[g] None: no bias), each tensor used where it lies. Every block's values, index
-    and lse equal vocab_topk of that block alone, bit for bit.
+    and lse equal vocab_topk of that block alone, bit for bit. mask / select_only (capnet_vocab_topk_groups_masked): vocab_topk's,
+    the mask int32 [groups rows, ceil(V / 32)] in the launch's row order.
     Returns (values [groups rows, k] float32, index [groups rows, k] int32, lse [groups rows] float32)."""
     who = "vocab_topk"
     ws = _check_tables(who, ws, _first_shape(ws))
@@ -1347,6 +1374,14 @@ def vocab_topk_groups(h, ws, bs=None, k=5, workspace=None):
     values = torch.empty((rows, k), dtype=torch.float32, device=h.device)
     index = torch.empty((rows, k), dtype=torch.int32, device=h.device)
     lse = torch.empty(rows, dtype=torch.float32, device=h.device)
+    if select_only and mask is None:
+        raise CapnetError("%s: select_only needs a mask" % who)
+    if mask is not None:
+        mask = _check_mask(who, mask, rows, V)
+        check(_lib.lib().capnet_vocab_topk_groups_masked(
+            ptr(h), ptr_array(ws), None if bs is None else ptr_array(bs), groups, rpg, H, V, k, ptr(mask), int(bool(select_only)),
+            ptr(workspace), ptr(values), ptr(index), ptr(lse), current_stream()), "capnet_vocab_topk_groups_masked")
+        return values, index, lse
     check(_lib.lib().capnet_vocab_topk_groups(ptr(h), ptr_array(ws), None if bs is None else ptr_array(bs), groups, rpg, H, V, k,
                                               ptr(workspace), ptr(values), ptr(index), ptr(lse), current_stream()),
           "capnet_vocab_topk_groups")
@@ -1543,8 +1578,18 @@ def lstm_beam_decode_supported(E, H, k, V, num_layers):
     return beam_decode_supported(E, H, k, V, num_layers)
 
 
+def _lstm_constrained(who, entry, constraints, fused, device):
+    """(the C entry's name, its trailing constraint arguments) of lstm_beam_decode[_groups]: `entry` and none without
+    constraints, entry + "_constrained" with constraint_args + forced_args; forced words are refused on the fused step."""
+    if constraints is None:
+        return entry, ()
+    if fused and has_forced(constraints):
+        raise CapnetError("%s: forced words take the unfused step (fused_topk=False)" % who)
+    return entry + "_constrained", constraint_args(constraints, device) + forced_args(constraints, device)
+
+
 def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end_token, first_inputs=None, state=None,
-                     fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0):
+                     fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0, constraints=None):
     """The beam search of a stack from a given state in ONE C call (capnet_lstm_beam_decode): n sentences x k beams, at most
     max_steps steps, then capnet_beam_finish. fused_topk: a step is (gathered decode step, capnet_vocab_topk,
     capnet_beam_advance_topk) -- no logits in memory; else beam_decode's step (the projection on sgemm_splitk's slab,
@@ -1552,6 +1597,9 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
     emb[start_token] (EncoderRNN's feature column). state: [n k, 2L, H] or None for zeros. Everything else as beam_decode:
     the workspace is cached per (device, shape); sequences, lengths and the error word come to the host in one copy.
     nbest / length_penalty: as beam_decode's, on either top-k route.
+    constraints (a capnet.beam.Constraints; capnet_lstm_beam_decode_constrained): every step selects under them -- unfused with
+    capnet_beam_advance_constrained (forced words: capnet_beam_advance_forced); fused (no forced words) through one more launch
+    per step, capnet_beam_exclusion_mask, and capnet_vocab_topk_select in capnet_vocab_topk's place. None: the call as it was.
     Returns the n token lists (each starts with start_token); with return_steps, (lists, the steps issued)."""
     who = "lstm_beam_decode"
     length_penalty = check_length_penalty(who, nbest, length_penalty)
@@ -1566,21 +1614,22 @@ def lstm_beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token
         if tuple(first_inputs.shape) != (n * k, E) or first_inputs.dtype != torch.float32:
             raise CapnetError("%s: first_inputs must be float32 [n k, E]" % who)
     dev = emb.device
-    ws = _search_workspace("capnet_lstm_beam_decode_ws_bytes", dev, (nl, n, k, H, V, T, fused),
+    name, con = _lstm_constrained(who, "capnet_lstm_beam_decode", constraints, fused, dev)
+    ws = _search_workspace(name + "_ws_bytes", dev, (nl, n, k, H, V, T, fused),
                            "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T))
     slab = None if fused else splitk_slab(dev)
     packed, seqs, lengths = _result_buffer(n, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(_lib.lib().capnet_lstm_beam_decode(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(first_inputs),
-                                             ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws),
-                                             ptr(slab), 0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths,
-                                             C.byref(steps), ptr(flag), current_stream()), "capnet_lstm_beam_decode")
+    check(getattr(_lib.lib(), name)(cell, nl, n, k, E, H, V, T, int(start_token), int(end_token), ptr(first_inputs),
+                                    ptr(emb), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws),
+                                    ptr(slab), 0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths,
+                                    C.byref(steps), ptr(flag), current_stream(), *con), name)
     return _search_result(ws, (nl, n, k, H, V, T, fused, 1), packed, flag, n, k, T, steps, return_steps, nbest, length_penalty)
 
 
 def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, start_token, end_token, state=None,
-                            fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0):
+                            fused_topk=True, poll_every=0, return_steps=False, nbest=False, length_penalty=0.0, constraints=None):
     """lstm_beam_decode of len(embs) decoders in ONE C call (capnet_lstm_beam_decode_groups): groups x n sentences x k beams,
     group-major, group g on embs[g] [V, E], wcat[l][g] / beff[l][g] and Cws[g] [V, H] / Cbs[g] [V] (Cbs or any Cbs[g] None:
     no bias). The embeddings and projections are used where they lie (one pointer per group; nothing is stacked or copied);
@@ -1588,7 +1637,8 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
     as for lstm_greedy_decode_groups. Per step one gathered decode-step launch per layer on a (H / 4, groups) grid, then
     fused_topk: one capnet_vocab_topk_groups launch and one capnet_beam_advance_topk; else one sgemm_splitk per group into
     its row block of the logits and one capnet_beam_advance. There are no first_inputs. state: [groups n k, 2L, H] or None
-    for zeros. Everything else as lstm_beam_decode, nbest / length_penalty included.
+    for zeros. Everything else as lstm_beam_decode, nbest / length_penalty and constraints
+    (capnet_lstm_beam_decode_groups_constrained: the same constraints on every group) included.
     Returns the groups n token lists, group-major (list g n + i: group g, sentence i); with return_steps, (lists, the steps
     issued)."""
     who = "lstm_beam_decode_groups"
@@ -1616,17 +1666,18 @@ def lstm_beam_decode_groups(cell, wcat, beff, embs, Cws, Cbs, n, k, max_steps, s
         state = _c(state.detach())
         if tuple(state.shape) != (nq * k, 2 * nl, H):
             raise CapnetError("%s: state must be [groups n k, 2L, H]" % who)
-    ws = _search_workspace("capnet_lstm_beam_decode_groups_ws_bytes", dev, (nl, groups, n, k, H, V, T, fused),
+    name, con = _lstm_constrained(who, "capnet_lstm_beam_decode_groups", constraints, fused, dev)
+    ws = _search_workspace(name + "_ws_bytes", dev, (nl, groups, n, k, H, V, T, fused),
                            "%s: groups=%d n=%d k=%d V=%d max_steps=%d outside the limits" % (who, groups, n, k, V, T))
     slab = None if fused else splitk_slab(dev)
     packed, seqs, lengths = _result_buffer(nq, T, dev)
     flag = err_flag(dev)
     steps = C.c_int(0)
-    check(_lib.lib().capnet_lstm_beam_decode_groups(
+    check(getattr(_lib.lib(), name)(
         cell, nl, groups, n, k, E, H, V, T, int(start_token), int(end_token), ptr_array(embs), ptr_array(wcat), ptr_array(beff),
         ptr_array(Cws), None if Cbs is None else ptr_array(Cbs), ptr(state), ptr(ws), ptr(slab),
-        0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream()),
-        "capnet_lstm_beam_decode_groups")
+        0 if slab is None else slab.numel(), fused, int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream(),
+        *con), name)
     return _search_result(ws, (nl, n, k, H, V, T, fused, groups), packed, flag, nq, k, T, steps, return_steps, nbest,
                           length_penalty)
 

@@ -50,6 +50,17 @@ stacked LSTM sequence path (capnet_seq_forward_stacked / _backward_stacked with 
     per layer and csrc/vocab_sample.hip, or capnet_vocab_topk + capnet_sample_pick) up to capnet.decode.FUSED_SAMPLE_MAX_ROWS
     rows; CAPNET_NO_FUSED_SAMPLE=1 (read at every call), CAPNET_NO_FUSED_DECODE_STEP=1, more rows or a shape the decode
     kernel does not take: the composed loop on the same stream, the same tokens.
+  * Constraints: EncoderRNN.sample_beam and DecoderRNN.sample_beam take constraints= (a capnet.beam.Constraints:
+    no repeated n-gram, a minimum length, banned words, forced words), the image decoders' rule on every route here; on
+    Seq2Seq the constrained searches are sample_beam_constrained and sample_beam_styles_constrained (its sample_beam and
+    sample_beam_styles keep their signatures). The fused step stays
+    the default for a handful of sentences: one more small launch per step writes what each beam row may not select
+    (capnet_beam_exclusion_mask, from the hypotheses in the beam state) and csrc/vocab_topk.hip's select-only instance keeps
+    those words out of its k candidates but IN the log-sum-exp, so a caption's score is still the model's own summed
+    log-probability; capnet_beam_advance_topk is unchanged. The unfused step selects with capnet_beam_advance_constrained.
+    Forced words always take the unfused in-call step (capnet_beam_advance_forced). sample_random takes exclude= / end_token=
+    (capnet.decode.sample_random's meaning: an excluded word is not pickable); EncoderRNN's goes through the composed loop,
+    since the one call's hypotheses begin with start tokens and the encoder's first input is the feature column.
 """
 import os
 import random
@@ -59,7 +70,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import CapnetError
-from .beam import beam_search_device
+from .beam import Constraints, beam_search_device
 from .decode import cell_stepper, check_styles, fused_decode_step, fused_sample, pack_cells, sample_steps
 from .model import Dropout, Embedding, Linear, _dropout_seed, _seq_cfg
 from .nic_model import LSTMCell
@@ -70,7 +81,8 @@ FUSED_GREEDY_OFF = "CAPNET_NO_FUSED_GREEDY"
 FUSED_GREEDY_MAX_ROWS = 16
 FUSED_TOPK_OFF = "CAPNET_NO_FUSED_TOPK"
 # the largest n k at which the fused step's median beat the unfused step's by more than the spread at 1, 2 and 3 layers
-# (profiles/time_seq2seq_beam.jsonl); above it fused_topk=None takes the unfused step in the same C call
+# (profiles/time_seq2seq_beam.jsonl); above it fused_topk=None takes the unfused step in the same C call. Under
+# constraints the crossover is where it was (profiles/time_seq2seq_constrained.jsonl)
 FUSED_TOPK_MAX_ROWS = 15
 # the same for the grouped search of sample_beam_styles, in rows PER DECODER (B k): the largest measured row count at which
 # the grouped fused step's median beat the grouped unfused step's by more than the spread at 1 and 3 layers
@@ -85,6 +97,39 @@ def _fused_topk(fused_topk, rows, max_rows):
     if os.environ.get(FUSED_TOPK_OFF, "")[:1] == "1":
         return False
     return rows <= max_rows if fused_topk is None else bool(fused_topk)
+
+
+def _check_constraints(constraints, V, end_token, k, T):
+    """sample_beam's `constraints` checked (Constraints.check(V, end_token, k, T), T = max_seq_length + 1) -> the Constraints,
+    or None for None and for one that excludes nothing (the calls then run as they did before there was the keyword)."""
+    if constraints is None:
+        return None
+    if not isinstance(constraints, Constraints):
+        raise CapnetError("constraints must be a capnet.beam.Constraints, not %r" % (constraints,))
+    if not constraints.active:
+        return None
+    constraints.check(V, end_token, k, T)
+    return constraints
+
+
+def _require_constraints(who, constraints):
+    if not isinstance(constraints, Constraints):
+        raise CapnetError("%s: constraints must be a capnet.beam.Constraints, not %r" % (who, constraints))
+
+
+def _check_exclude(exclude, end_token, V, top_k, steps):
+    """sample_random's `exclude` / `end_token` checked (Constraints.check_exclude) -> (the Constraints or None for one that
+    excludes nothing, end_token as an int). end_token is required where min_words > 0; without it no id is <end>."""
+    if exclude is None:
+        return None, None
+    if not isinstance(exclude, Constraints):
+        raise CapnetError("exclude must be a capnet.beam.Constraints, not %r" % (exclude,))
+    if end_token is None:
+        if exclude.min_words > 0:
+            raise CapnetError("sample_random: exclude with min_words=%d needs end_token" % exclude.min_words)
+        end_token = -1                          # no word id: nothing is <end>
+    exclude.check_exclude(V, end_token, top_k, steps)
+    return (exclude if exclude.active else None), int(end_token)
 
 
 class LSTM(nn.Module):
@@ -209,25 +254,31 @@ class _RNN(nn.Module):
             return torch.stack(ids, 1), state
 
 
-    def _sampled(self, features, start_tokens, state, temperature, top_k, seed, top_p=1.0):
+    def _sampled(self, features, start_tokens, state, temperature, top_k, seed, top_p=1.0, exclude=None, end_token=None):
         """max_seq_length SAMPLED steps from `features` [rows, E] or emb[start_tokens]; state [rows, 2L, H]: every word a draw
         from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k best), row r on stream row r, step
         t on stream step t; top_p < 1: over the nucleus (capnet.decode.sample_random). Returns (ids [rows, max_seq_length] int64, logp [rows, max_seq_length] float32, state').
         One capnet_sample_decode call where the decode kernel takes the shape, the rows are at most
         capnet.decode.FUSED_SAMPLE_MAX_ROWS and neither CAPNET_NO_FUSED_SAMPLE=1 nor CAPNET_NO_FUSED_DECODE_STEP=1 is set;
-        else the composed loop (capnet.decode.sample_steps on step -> ops.linear) on the same stream: the same tokens."""
+        else the composed loop (capnet.decode.sample_steps on step -> ops.linear) on the same stream: the same tokens.
+        exclude (a capnet.beam.Constraints without forced words; end_token required where min_words > 0): what no row may draw,
+        capnet.decode.sample_random_device's keyword -- a row is the hypothesis [its start token, its words so far] (from
+        `features`: the words alone). The one call is capnet_sample_decode_excl where there are start tokens; from `features`
+        the composed loop. None or a Constraints() that excludes nothing: the calls as they were."""
         E, H, V, steps = self.embed_size, self.hidden_size, self.vocab_size, self.max_seq_length
         temperature, top_k, seed, top_p = ops.check_sampling("sample_random", temperature, top_k, seed, V, top_p)
         kw = {} if top_p == 1.0 else {"top_p": top_p}      # top_p == 1.0: the calls as they were before there was a top_p
+        exclude, end_token = _check_exclude(exclude, end_token, V, top_k, steps)
+        ex = {} if exclude is None else {"exclude": exclude, "end_token": end_token}
         emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
         layers = self._layers()
         with torch.no_grad():
             if (fused_sample(state.shape[0], False, top_p, top_k) and fused_decode_step(self.num_layers, E, H)
-                    and ops.sample_decode_supported(E, H, V, top_k)):
+                    and ops.sample_decode_supported(E, H, V, top_k) and (exclude is None or start_tokens is not None)):
                 packed = pack_cells(layers, E)
                 return ops.sample_decode(ops.CELL_LSTM, steps, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb,
                                          temperature, top_k, seed, first_inputs=features, start_tokens=start_tokens, state=state,
-                                         **kw)
+                                         **kw, **ex)
             cells = cell_stepper(layers, E, H)
 
             def step(t, tokens, state):
@@ -236,18 +287,24 @@ class _RNN(nn.Module):
                 else:
                     top, state = cells(emb, tokens, state)
                 return ops.linear(top, Cw, Cb), state
-            return sample_steps(step, steps, start_tokens, state, temperature, top_k, seed, kw)
+            if exclude is None:
+                return sample_steps(step, steps, start_tokens, state, temperature, top_k, seed, kw)
+            return sample_steps(step, steps, start_tokens, state, temperature, top_k, seed, kw, exclude, V, end_token)
 
-    def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk, nbest=False, length_penalty=0.0):
+    def _beam_search(self, features, start_token, end_token, state, k, poll_every, fused_topk, nbest=False, length_penalty=0.0,
+                     constraints=None):
         """Beam search of B = state.shape[0] sentences x k beams from `state` [B, 2L, H]; the first input is `features`
         [B, E] or, None, embed(start_token). max_seq_length + 1 steps at most. Returns B token lists, each starting with
         start_token ([end_token] where nothing completed). Routing: the module's docstring. nbest: per sentence the list of
-        (tokens, score) of its completed hypotheses, best first (capnet.decode.beam_decode's keyword), on every route."""
+        (tokens, score) of its completed hypotheses, best first (capnet.decode.beam_decode's keyword), on every route.
+        constraints (a capnet.beam.Constraints, checked here): every route selects under them -- the fused step through the
+        selection mask (not with forced words: those take the unfused in-call step at every row count), the unfused step and
+        beam_search_device through capnet_beam_advance_constrained / _forced. None or a Constraints() that excludes nothing:
+        exactly the calls without the keyword."""
         E, H, V, L = self.embed_size, self.hidden_size, self.vocab_size, self.num_layers
         length_penalty = ops.check_length_penalty("sample_beam", nbest, length_penalty)
-        k = int(k)
-        if not 1 <= k <= 16 or k > V:
-            raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, V))
+        k, constraints = self._check_beam_args(k, end_token, constraints)
+        con = {} if constraints is None else {"constraints": constraints}
         emb, Cw, Cb = self.embed.weight.detach(), self.linear.weight.detach(), self.linear.bias.detach()
         layers = self._layers()
         B = state.shape[0]
@@ -255,11 +312,12 @@ class _RNN(nn.Module):
             state = state.detach().repeat_interleave(k, 0).contiguous()
             first = None if features is None else features.detach().float().repeat_interleave(k, 0).contiguous()
             if fused_decode_step(L, E, H) and ops.lstm_beam_decode_supported(E, H, k, V, L):
-                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_MAX_ROWS)
+                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_MAX_ROWS) and not ops.has_forced(constraints)
                 packed = pack_cells(layers, E)
                 return ops.lstm_beam_decode(ops.CELL_LSTM, [w for w, _ in packed], [b for _, b in packed], emb, Cw, Cb, B, k,
                                             self.max_seq_length + 1, start_token, end_token, first_inputs=first, state=state,
-                                            fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty)
+                                            fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty,
+                                            **con)
             step = cell_stepper(layers, E, H)
             calls = [0]
 
@@ -271,7 +329,14 @@ class _RNN(nn.Module):
                     top, new = step(emb, prev_words, st[0])
                 return ops.linear(top, Cw, Cb), (new,)
             return beam_search_device(step_fn, (state,), B, V, start_token, end_token, k, self.max_seq_length,
-                                      emb.device, poll_every, nbest=nbest, length_penalty=length_penalty)
+                                      emb.device, poll_every, nbest=nbest, length_penalty=length_penalty, **con)
+
+    def _check_beam_args(self, k, end_token, constraints):
+        """(k, the constraints or None for none that exclude anything) of a beam search on this stack, checked."""
+        k, V = int(k), self.vocab_size
+        if not 1 <= k <= 16 or k > V:
+            raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, V))
+        return k, _check_constraints(constraints, V, end_token, k, self.max_seq_length + 1)
 
     def _rows_state(self, states, rows, dev):
         h, c = states
@@ -302,27 +367,31 @@ class EncoderRNN(_RNN):
         ids, state = self._greedy(features, None, self._zeros(rows) if state is None else state)
         return ids, _from_rows(state)
 
-    def sample_random(self, features, states=(None, None), temperature=1.0, top_k=0, seed=None, top_p=1.0):
+    def sample_random(self, features, states=(None, None), temperature=1.0, top_k=0, seed=None, top_p=1.0, exclude=None,
+                      end_token=None):
         """sample() with every word DRAWN from softmax(logits / temperature) (top_k > 0: renormalised over the step's top_k
         best words) instead of the argmax: (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32 -- each word's
         log-probability under the distribution sampled from --, (h, c) [num_layers, B, H]); the first input is `features`.
         seed: an integer makes the call a pure function; None draws one from torch's CPU generator (torch.manual_seed).
+        exclude / end_token: what no row may draw (_RNN._sampled); the hypotheses are the drawn words alone.
         Routing: _RNN._sampled."""
         state = self._rows_state(states, features.size(0), features.device)
-        ids, logp, state = self._sampled(features, None, state, temperature, top_k, seed, top_p)
+        ids, logp, state = self._sampled(features, None, state, temperature, top_k, seed, top_p, exclude, end_token)
         return ids, logp, _from_rows(state)
 
-    def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None, nbest=False,
-                    length_penalty=0.0):
+    def sample_beam(self, features, start_token, end_token, states=(None, None), k=5, poll_every=0, fused_topk=None,
+                    constraints=None, nbest=False, length_penalty=0.0):
         """Beam search (k beams per sentence, max_seq_length + 1 steps at most, a beam completes at end_token) whose first
         input is `features` [B, E]: a list of B token lists. start_token only seeds the bookkeeping (no step reads its
         embedding), so it is dropped from every list that has more than one element; [end_token] where nothing completed.
         poll_every as capnet.beam.beam_search_device; fused_topk: None routes by FUSED_TOPK_MAX_ROWS, True / False force
         the fused / unfused step (CAPNET_NO_FUSED_TOPK=1 forces False). nbest / length_penalty: per sentence the list of
         (tokens, score) of every completed hypothesis, best first, start_token dropped from each (the key still counts the
-        generated words: len(tokens) here); empty where nothing completed."""
+        generated words: len(tokens) here); empty where nothing completed. constraints: a capnet.beam.Constraints
+        (_RNN._beam_search); the hypotheses begin with start_token, which counts as a token of the rule."""
         state = self._rows_state(states, features.size(0), features.device)
-        lists = self._beam_search(features, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty)
+        lists = self._beam_search(features, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty,
+                                  constraints)
         if nbest:
             return [[(q[1:], sc) for q, sc in hyps] for hyps in lists]
         return [s[1:] if len(s) > 1 else s for s in lists]
@@ -355,24 +424,27 @@ class DecoderRNN(_RNN):
         ops.check_device_errors()
         return ids
 
-    def sample_random(self, start_token, states, temperature=1.0, top_k=0, seed=None, top_p=1.0):
+    def sample_random(self, start_token, states, temperature=1.0, top_k=0, seed=None, top_p=1.0, exclude=None, end_token=None):
         """sample() with every word drawn (EncoderRNN.sample_random): from embed(start_token) and `states` (h, c)
         [num_layers, B, H] -> (ids [B, max_seq_length] int64, logp [B, max_seq_length] float32). An out-of-range
-        start_token raises CapnetError through the device error word."""
+        start_token raises CapnetError through the device error word. exclude / end_token: what no row may draw
+        (_RNN._sampled); a row's hypothesis is [start_token, its words so far]."""
         tokens, state = self._start(start_token, states)
-        ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed, top_p)
+        ids, logp, _ = self._sampled(None, tokens, state, temperature, top_k, seed, top_p, exclude, end_token)
         ops.check_device_errors()
         return ids, logp
 
-    def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None, nbest=False, length_penalty=0.0):
+    def sample_beam(self, start_token, end_token, states, k=5, poll_every=0, fused_topk=None, constraints=None, nbest=False,
+                    length_penalty=0.0):
         """Beam search from embed(start_token) and `states` (h, c) [num_layers, B, H]: a list of B token lists, one per
         column of `states`, each what oracle.beam_ref._beam returns for that sentence -- it begins with start_token, and is
         [end_token] where nothing completed. max_seq_length + 1 steps at most. poll_every / fused_topk: as
         EncoderRNN.sample_beam. An out-of-range start_token raises CapnetError through the device error word.
         nbest / length_penalty: per sentence the list of (tokens, score) of every completed hypothesis, best first by score /
-        (len(tokens) - 1)^length_penalty; empty where nothing completed."""
+        (len(tokens) - 1)^length_penalty; empty where nothing completed. constraints: a capnet.beam.Constraints
+        (_RNN._beam_search)."""
         _, state = self._start(None, states)
-        return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty)
+        return self._beam_search(None, start_token, end_token, state, k, poll_every, fused_topk, nbest, length_penalty, constraints)
 
 
 def _groupable(decoders):
@@ -431,27 +503,49 @@ class Seq2Seq(nn.Module):
         return decoder.sample(start_token, states)
 
     def sample_random(self, features, start_token, states=(None, None), mode='factual', temperature=1.0, top_k=0, seed=None,
-                      top_p=1.0):
+                      top_p=1.0, exclude=None, end_token=None):
         """factual: the encoder's sampled (ids, logp) [B, max_seq_length] (EncoderRNN.sample_random). An emotion mode: the
         encoder's GREEDY sample for the state, exactly as sample(mode=...) does, then that decoder's sampled (ids, logp)
-        from embed(start_token) and it: only the emotion decoder samples."""
+        from embed(start_token) and it: only the emotion decoder samples. exclude / end_token: what the sampling stack may
+        not draw (the two sample_random)."""
         decoder = None if mode == 'factual' else self._decoder(mode)
         if decoder is None:
-            ids, logp, _ = self.encoder.sample_random(features, states, temperature, top_k, seed, top_p)
+            ids, logp, _ = self.encoder.sample_random(features, states, temperature, top_k, seed, top_p, exclude, end_token)
             return ids, logp
+        if exclude is not None:          # refused before the encoder's pass runs (the decoder checks again)
+            _check_exclude(exclude, end_token, decoder.vocab_size, ops.check_sampling("sample_random", temperature, top_k, 0)[1],
+                           decoder.max_seq_length)
         _, states = self.encoder.sample(features, states)
-        return decoder.sample_random(start_token, states, temperature, top_k, seed, top_p)
+        return decoder.sample_random(start_token, states, temperature, top_k, seed, top_p, exclude, end_token)
 
     def sample_beam(self, features, start_token, end_token, states=(None, None), mode='factual', k=5, poll_every=0,
                     fused_topk=None, nbest=False, length_penalty=0.0):
         """factual: the encoder's beam search (EncoderRNN.sample_beam). An emotion mode: the encoder's GREEDY sample for
         the state, as sample() does, then that decoder's beam search from it (DecoderRNN.sample_beam). A list of B token
-        lists; nbest / length_penalty: of B n-best lists, as the two sample_beam."""
+        lists; nbest / length_penalty: of B n-best lists, as the two sample_beam. Under constraints:
+        sample_beam_constrained."""
+        return self._sample_beam(features, start_token, end_token, states, mode, k, poll_every, fused_topk, None, nbest,
+                                 length_penalty)
+
+    def sample_beam_constrained(self, features, start_token, end_token, constraints, states=(None, None), mode='factual', k=5,
+                                poll_every=0, fused_topk=None, nbest=False, length_penalty=0.0):
+        """sample_beam under `constraints` (a capnet.beam.Constraints, required) on the stack that searches -- the encoder's
+        or the decoder's sample_beam(constraints=...); the encoder's greedy pass for an emotion's state is not constrained.
+        A Constraints() that excludes nothing is sample_beam. (A method of its own: this class's sample_beam and
+        sample_beam_styles keep the signatures they had.)"""
+        _require_constraints("sample_beam_constrained", constraints)
+        return self._sample_beam(features, start_token, end_token, states, mode, k, poll_every, fused_topk, constraints, nbest,
+                                 length_penalty)
+
+    def _sample_beam(self, features, start_token, end_token, states, mode, k, poll_every, fused_topk, constraints, nbest,
+                     length_penalty):
         decoder = None if mode == 'factual' else self._decoder(mode)
         if decoder is None:
-            return self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, nbest, length_penalty)
+            return self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, constraints, nbest,
+                                            length_penalty)
+        decoder._check_beam_args(k, end_token, constraints)      # refused before the encoder's pass runs
         _, states = self.encoder.sample(features, states)
-        return decoder.sample_beam(start_token, end_token, states, k, poll_every, fused_topk, nbest, length_penalty)
+        return decoder.sample_beam(start_token, end_token, states, k, poll_every, fused_topk, constraints, nbest, length_penalty)
 
     def _check_mode(self, mode):
         if mode != 'factual':
@@ -509,7 +603,23 @@ class Seq2Seq(nn.Module):
         (CAPNET_NO_FUSED_TOPK=1 forces False). One emotion, unequal decoder shapes, a shape the decode kernel does not take
         or CAPNET_NO_FUSED_DECODE_STEP=1: one DecoderRNN.sample_beam after the other on that one encoder run. An
         out-of-range start_token raises CapnetError through the device error word. nbest / length_penalty: {mode: [B n-best
-        lists]}, as sample_beam's, on the grouped call and on the loop."""
+        lists]}, as sample_beam's, on the grouped call and on the loop. Under constraints: sample_beam_styles_constrained."""
+        return self._sample_beam_styles(features, start_token, end_token, states, modes, k, poll_every, fused_topk, None, nbest,
+                                        length_penalty)
+
+    def sample_beam_styles_constrained(self, features, start_token, end_token, constraints, states=(None, None),
+                                       modes=('factual', 'happy', 'sad', 'angry'), k=5, poll_every=0, fused_topk=None, nbest=False,
+                                       length_penalty=0.0):
+        """sample_beam_styles under `constraints` (a capnet.beam.Constraints, required), the same on every route -- the
+        encoder's own search, the grouped call (fused: capnet_vocab_topk_groups_masked under the selection mask; forced words:
+        its unfused step) and the loop: every entry equals sample_beam_constrained(..., mode=mode). A Constraints() that
+        excludes nothing is sample_beam_styles."""
+        _require_constraints("sample_beam_styles_constrained", constraints)
+        return self._sample_beam_styles(features, start_token, end_token, states, modes, k, poll_every, fused_topk, constraints,
+                                        nbest, length_penalty)
+
+    def _sample_beam_styles(self, features, start_token, end_token, states, modes, k, poll_every, fused_topk, constraints, nbest,
+                            length_penalty):
         length_penalty = ops.check_length_penalty("sample_beam_styles", nbest, length_penalty)
         try:
             modes = check_styles(modes, self._check_mode)
@@ -517,29 +627,31 @@ class Seq2Seq(nn.Module):
             raise CapnetError("sample_beam_styles: %s" % e)
         emotions = [m for m in modes if m != 'factual']
         decoders = [self._decoder(m) for m in emotions]
+        for x in [self.encoder] * ('factual' in modes) + decoders:      # refused before anything runs
+            x._check_beam_args(k, end_token, constraints)
         out = {}
         if 'factual' in modes:
-            out['factual'] = self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, nbest,
-                                                      length_penalty)
+            out['factual'] = self.encoder.sample_beam(features, start_token, end_token, states, k, poll_every, fused_topk, constraints,
+                                                      nbest, length_penalty)
         if decoders:
             _, (h, c) = self.encoder.sample(features, states)
             B, k = h.size(1), int(k)
             d, G = decoders[0], len(decoders)
-            if not 1 <= k <= 16 or k > d.vocab_size:
-                raise CapnetError("sample_beam: k=%d (1 <= k <= 16, k <= vocab_size = %d)" % (k, d.vocab_size))
+            con = d._check_beam_args(k, end_token, constraints)[1]
             if self._grouped_beam_ok(decoders, k):
-                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_GROUPS_MAX_ROWS)
+                fused = _fused_topk(fused_topk, B * k, FUSED_TOPK_GROUPS_MAX_ROWS) and not ops.has_forced(con)
                 with torch.no_grad():
                     weights = _grouped_weights(decoders)
                     state = _to_rows(h, c).repeat(G, 1, 1).repeat_interleave(k, 0).contiguous()
                     lists = ops.lstm_beam_decode_groups(
                         ops.CELL_LSTM, *weights, B, k, d.max_seq_length + 1, start_token, end_token, state=state,
-                        fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty)
+                        fused_topk=fused, poll_every=poll_every, nbest=nbest, length_penalty=length_penalty,
+                        **({} if con is None else {"constraints": con}))
                 ops.check_device_errors()
                 for g, m in enumerate(emotions):
                     out[m] = lists[g * B:(g + 1) * B]
             else:
                 for m, x in zip(emotions, decoders):
-                    out[m] = x.sample_beam(start_token, end_token, (h, c), k, poll_every, fused_topk, nbest, length_penalty)
+                    out[m] = x.sample_beam(start_token, end_token, (h, c), k, poll_every, fused_topk, constraints, nbest, length_penalty)
                 ops.check_device_errors()
         return {m: out[m] for m in modes}

@@ -960,6 +960,57 @@ int capnet_lstm_beam_decode_groups(int cell, int nlayers, int groups, int n, int
                                    size_t slab_floats, int fused_topk, int poll_every, long long* seqs, int* lengths,
                                    int* steps_run, int* err_flag, capnet_stream_t stream);
 
+/* capnet.seq2seq's beam searches under constraints (capnet.beam.Constraints; the rule and the trailing arguments of
+ * capnet_beam_decode_forced: no_repeat_ngram 0..4, min_words >= 0, banned a DEVICE int32 array of n_banned <= 32 ids, forced a
+ * DEVICE int32 array of n_forced <= 4 ids, n_forced = 0: none). An excluded word leaves a step's SELECTION only: it stays
+ * in the row's log-sum-exp, so a caption's score is the model's own summed log-probability, on either step.
+ *
+ * capnet_beam_exclusion_mask: what each of the n k rows of a device beam search (the state of capnet_beam_init /
+ * capnet_beam_advance*, n images x k slots, max_steps) may not select at step `step` (1-based, <= max_steps), as the bit mask
+ * of capnet_sample_exclusion_mask: unsigned [n k][ceil(V / 32)], every word written. Row r is the hypothesis in slot r % k of
+ * image r / k as step `step` reads it -- `step` tokens, <start> first, the tokens capnet_beam_advance_constrained derives its
+ * exclusions from -- under capnet.beam.banned_words (forced words are not part of it). The rows of dead slots get a mask
+ * nobody reads; a token outside [0, V) is never an address. One launch, the kernel of capnet_sample_exclusion_mask.
+ * capnet_vocab_topk_select: capnet_vocab_topk under a SELECTION mask: an entry whose bit is set is not ranked and never a
+ * candidate (a row with fewer than k allowed entries ends in (-inf, -1)), while lse is the log-sum-exp over every finite
+ * entry -- bit for bit capnet_vocab_topk's; values and index are bit for bit capnet_vocab_topk_masked's.
+ * capnet_vocab_topk_groups_masked: capnet_vocab_topk_groups under a mask [groups rows_per_group][ceil(V / 32)] indexed by the
+ * launch's row; select_only = 1: capnet_vocab_topk_select's meaning, 0: capnet_vocab_topk_masked's. Group g's outputs are bit
+ * for bit those of the single launch on its rows, projection and mask rows.
+ * capnet_lstm_beam_decode_constrained / capnet_lstm_beam_decode_groups_constrained: capnet_lstm_beam_decode[_groups] whose every
+ * step selects under the constraints. fused_topk = 0: capnet_beam_advance_constrained (n_forced > 0: capnet_beam_advance_forced)
+ * on the logits block. fused_topk = 1 (n_forced must be 0): the decode step, capnet_beam_exclusion_mask,
+ * capnet_vocab_topk_select (groups: capnet_vocab_topk_groups_masked, select_only = 1) and the unchanged
+ * capnet_beam_advance_topk -- one more small launch per step. workspace: the *_constrained_ws_bytes functions: the
+ * unconstrained layout and, fused, the mask behind it (n k ceil(V / 32) 4 bytes rounded up to 16), so
+ * capnet_beam_decode_ws_beam_offset still tells where the state lies. Every bad argument is refused before any launch. */
+int capnet_beam_exclusion_mask(const void* beam, int n, int k, int max_steps, int step, int V, long long end_token,
+                               int no_repeat_ngram, int min_words, const int* banned, int n_banned, unsigned* mask,
+                               capnet_stream_t stream);
+int capnet_vocab_topk_select(const float* h, const float* w, const float* b, int rows, int H, int V, int k, const unsigned* mask,
+                             void* workspace, float* values, int* index, float* lse, capnet_stream_t stream);
+int capnet_vocab_topk_groups_masked(const float* h, const float* const* w, const float* const* b, int groups, int rows_per_group,
+                                    int H, int V, int k, const unsigned* mask, int select_only, void* workspace, float* values,
+                                    int* index, float* lse, capnet_stream_t stream);
+size_t capnet_lstm_beam_decode_constrained_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps, int fused_topk);
+int capnet_lstm_beam_decode_constrained(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps,
+                                        long long start_token, long long end_token, const float* first_inputs, const float* emb,
+                                        const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                        const float* state0, void* workspace, float* slab, size_t slab_floats, int fused_topk,
+                                        int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                                        capnet_stream_t stream, int no_repeat_ngram, int min_words, const int* banned,
+                                        int n_banned, const int* forced, int n_forced);
+size_t capnet_lstm_beam_decode_groups_constrained_ws_bytes(int nlayers, int groups, int n, int k, int H, int V, int max_steps,
+                                                           int fused_topk);
+int capnet_lstm_beam_decode_groups_constrained(int cell, int nlayers, int groups, int n, int k, int E, int H, int V, int max_steps,
+                                               long long start_token, long long end_token, const float* const* emb,
+                                               const float* const* wcat, const float* const* beff, const float* const* Cw,
+                                               const float* const* Cb, const float* state0, void* workspace, float* slab,
+                                               size_t slab_floats, int fused_topk, int poll_every, long long* seqs,
+                                               int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                               int no_repeat_ngram, int min_words, const int* banned, int n_banned,
+                                               const int* forced, int n_forced);
+
 /* One beam step of an attention decoder (DecoderFactoredLSTMAtt / DecoderRNNAtt and their stacked forms) without the
  * vocabulary projection, for n images x k fixed slots (row r belongs to image r / k), on `stream`, in this order:
  *   1. z [n k][A + C] = h_prev . wz^T + bz, wz = [decoder_att; f_beta] stacked ([A + C][H]), h_prev = layer 0's h of every
