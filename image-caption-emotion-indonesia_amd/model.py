@@ -347,9 +347,11 @@ class _TrunkRunner:
             sig = (id(tables), images.dtype)
             st = plan.setdefault("graphs", {}).get(gkey)
             if st is None or st["sig"] != sig:
-                static_in = torch.empty_like(images)
+                # (a copy of this batch, not uninitialised memory: a NaN left there by an earlier owner would raise
+                # the error word in the warm-up below, and capnet.optim.Adam drops steps while it is set)
+                static_in = images.clone()
                 sp, sf = new_outputs()
-                launch(static_in, sp, sf)      # eager warm-up on garbage: one-time attribute calls
+                launch(static_in, sp, sf)      # eager warm-up: one-time attribute calls
                 g = torch.cuda.CUDAGraph()
                 # thread_local: other threads (an RCCL watchdog) may keep calling into HIP meanwhile
                 with torch.cuda.graph(g, stream=torch.cuda.current_stream(),

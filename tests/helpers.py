@@ -20,6 +20,13 @@ def rel_err(a, b):
     return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
 
 
+def encoder_state(enc):
+    """The seeded state of an EncoderCNN (product or oracle) that the trunk tests and tests/golden/trunk_b3.npz share:
+    kaiming-normal convolutions, BatchNorm2d weight 1 / bias 0 with fresh running statistics, a xavier head."""
+    from capnet import synthetic
+    return synthetic.encoder_state(enc.state_dict(), seed=1234)
+
+
 def golden_params(z):
     return {k[len("param."):]: t(z[k]) for k in z.files if k.startswith("param.")}
 

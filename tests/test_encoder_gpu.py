@@ -12,22 +12,10 @@ import capnet
 from capnet import synthetic
 from capnet.model import EncoderCNN, _BN2d
 from capnet import model_att
-from helpers import load_golden, rel_err, t
+from helpers import encoder_state as _encoder_state, load_golden, rel_err, t
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-3
-
-
-def _encoder_state(enc):
-    sd = enc.state_dict()
-    new = synthetic.trunk_state({k: v for k, v in sd.items() if k.startswith("resnet.")}, seed=1234)
-    new["linear.weight"] = synthetic.param_tensor("linear.weight", sd["linear.weight"].shape, 1234, "xavier")
-    new["linear.bias"] = synthetic.param_tensor("linear.bias", sd["linear.bias"].shape, 1234, "bias", 0.05)
-    new["bn.weight"] = synthetic.param_tensor("bn.weight", sd["bn.weight"].shape, 1234, "bias", 0.5) + 1.0
-    new["bn.bias"] = synthetic.param_tensor("bn.bias", sd["bn.bias"].shape, 1234, "bias", 0.2)
-    for k in ("bn.running_mean", "bn.running_var", "bn.num_batches_tracked"):
-        new[k] = sd[k]
-    return new
 
 
 @pytest.fixture(scope="module")
