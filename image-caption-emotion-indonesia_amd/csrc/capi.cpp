@@ -202,6 +202,79 @@ int capnet_colsum(const float* x, long ld, int rows, int C, float* out, int accu
   return colsum(x, ld, rows, C, out, accumulate, S(stream));
 }
 
+int capnet_colsum_ws(const float* x, long ld, int rows, int C, float* out, int accumulate, float* workspace,
+                     size_t workspace_floats, capnet_stream_t stream) {
+  CAPNET_REQUIRE(x && out && C > 0 && rows >= 0, "colsum: bad argument");
+  CAPNET_REQUIRE(ld >= C, "colsum: leading dimension too small (ld=%ld C=%d)", ld, C);
+  return colsum(x, ld, rows, C, out, accumulate, S(stream), workspace, workspace_floats);
+}
+int capnet_reduce_slabs(const float* slab, int count, int M, int N, float* out, long ldc, const float* bias,
+                        int accumulate, capnet_stream_t stream) {
+  CAPNET_REQUIRE(slab && out && count > 0 && M > 0 && N > 0, "reduce_slabs: bad argument");
+  CAPNET_REQUIRE(ldc >= N, "reduce_slabs: leading dimension too small (ldc=%ld N=%d)", ldc, N);
+  return reduce_slabs(slab, count, M, N, out, ldc, bias, accumulate, S(stream));
+}
+int capnet_sgemm_splitk_batched(int transA, int transB, int M, int N, int K, const float* A, long lda,
+                                const float* B, long ldb, float* C, long ldc, const float* bias, int accumulate,
+                                int batch, long strideA, long strideB, long strideC, long strideBias,
+                                float* workspace, size_t workspace_floats, int* counters, size_t n_counters,
+                                capnet_stream_t stream) {
+  CAPNET_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 0, "sgemm_splitk_batched: bad argument (negative dimension)");
+  if (M == 0 || N == 0 || batch == 0) return kOk;
+  CAPNET_REQUIRE(A && B && C, "sgemm_splitk_batched: bad argument (null operand)");
+  CAPNET_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N,
+                 "sgemm_splitk_batched: leading dimension too small (lda=%ld ldb=%ld ldc=%ld M=%d N=%d K=%d)", lda, ldb,
+                 ldc, M, N, K);
+  return sgemm_splitk_batched(transA != 0, transB != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch,
+                              strideA, strideB, strideC, strideBias, workspace, workspace_floats, S(stream), counters,
+                              n_counters);
+}
+int capnet_sgemm_splitk_slabs(int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                              float* workspace, size_t workspace_floats, int* n_slabs, capnet_stream_t stream) {
+  CAPNET_REQUIRE(n_slabs && A && B && M >= 0 && N >= 0 && K >= 0, "sgemm_splitk_slabs: bad argument");
+  CAPNET_REQUIRE(lda >= K && ldb >= (transB ? K : N), "sgemm_splitk_slabs: leading dimension too small (lda=%ld ldb=%ld)",
+                 lda, ldb);
+  return sgemm_splitk_slabs(transB != 0, M, N, K, A, lda, B, ldb, workspace, workspace_floats, n_slabs, S(stream));
+}
+int capnet_sgemm_rows16_slabs(int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                              float* workspace, size_t workspace_floats, int* n_slabs, capnet_stream_t stream) {
+  CAPNET_REQUIRE(n_slabs && A && B && M >= 0 && N >= 0 && K >= 0, "sgemm_rows16_slabs: bad argument");
+  CAPNET_REQUIRE(lda >= K && ldb >= (transB ? K : N), "sgemm_rows16_slabs: leading dimension too small (lda=%ld ldb=%ld)",
+                 lda, ldb);
+  return sgemm_rows16_slabs(transB != 0, M, N, K, A, lda, B, ldb, workspace, workspace_floats, n_slabs, S(stream));
+}
+
+static void route_detail(int* detail, bool vec, int splits, int chunk, int tiles) {
+  if (!detail) return;
+  detail[0] = vec ? 1 : 0; detail[1] = splits; detail[2] = chunk; detail[3] = tiles;
+}
+int capnet_sgemm_route(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                       const float* C, long ldc, const float* bias, int accumulate, int batch, long strideA,
+                       long strideB, long strideC, long strideBias, int force_tile, int* detail) {
+  SgemmPlan p;
+  const int rc = sgemm_plan(transA != 0, transB != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, strideA,
+                            strideB, strideC, strideBias, force_tile, &p);
+  if (rc != kOk) return rc;
+  route_detail(detail, p.vec, 1, 0, p.tiles_m * p.tiles_n);
+  return p.route;
+}
+int capnet_sgemm_splitk_route(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B,
+                              long ldb, const float* C, long ldc, const float* bias, int accumulate, int batch,
+                              long strideA, long strideB, long strideC, long strideBias, const float* workspace,
+                              size_t workspace_floats, const int* counters, size_t n_counters, int* detail) {
+  SplitkPlan p;
+  const int rc = sgemm_splitk_plan(transA != 0, transB != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch,
+                                   strideA, strideB, strideC, strideBias, workspace, workspace_floats, counters,
+                                   n_counters, true, &p);
+  if (rc != kOk) return rc;
+  if (p.route == kRouteFellThrough) {
+    route_detail(detail, p.inner.vec, 1, 0, p.inner.tiles_m * p.inner.tiles_n);
+    return p.inner.route == kRouteNone ? kRouteNone : (kRouteFellThrough | p.inner.route);
+  }
+  route_detail(detail, p.vec, p.splits, p.chunk, p.tiles);
+  return p.route;
+}
+
 int capnet_argmax_rows(const float* x, int rows, int ld, int V, int* out, capnet_stream_t stream) {
   CAPNET_REQUIRE(x && out && ld >= V && V > 0, "argmax_rows: bad argument");
   return argmax_rows(x, rows, ld, V, out, S(stream));

@@ -263,6 +263,20 @@ bool sgemm_b3_eligible(bool ta, bool tb, int M, int N, int K, const float* A, lo
   return true;
 }
 
+// the cut of K over blockIdx.z (host only; sgemm_b3 launches what this says)
+void sgemm_b3_plan(int M, int N, int K, int batch, const float* ws, size_t ws_floats, int* splits_out, int* steps_per_split,
+                   int* tiles_out) {
+  const int steps = cdiv(K, QK), tiles = cdiv(M, QM) * cdiv(N, QN);
+  int splits = 1;
+  if (ws && batch == 1 && tiles < 192 && steps >= 16) {
+    splits = min(cdiv(512, tiles), steps / 8);
+    while (splits > 1 && (size_t)splits * M * N > ws_floats) --splits;
+  }
+  *steps_per_split = cdiv(steps, splits);
+  *splits_out = cdiv(steps, *steps_per_split);
+  *tiles_out = tiles;
+}
+
 // ws (optional, batch == 1): room for split-K partials -- a product with few 128 x 128 tiles and a long K is cut over
 // blockIdx.z and summed by reduce_slabs
 int sgemm_b3(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc,
@@ -276,14 +290,8 @@ int sgemm_b3(bool ta, bool tb, int M, int N, int K, const float* A, long lda, co
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB; g.sC = sC; g.sBias = sBias;
   g.accumulate = accumulate;
   g.tiles_m = cdiv(M, QM); g.tiles_n = cdiv(N, QN);
-  const int steps = cdiv(K, QK), tiles = g.tiles_m * g.tiles_n;
-  int splits = 1;
-  if (ws && batch == 1 && tiles < 192 && steps >= 16) {
-    splits = min(cdiv(512, tiles), steps / 8);
-    while (splits > 1 && (size_t)splits * M * N > ws_floats) --splits;
-  }
-  g.steps_per_split = cdiv(steps, splits);
-  g.splits = cdiv(steps, g.steps_per_split);
+  int tiles = 0;
+  sgemm_b3_plan(M, N, K, batch, ws, ws_floats, &g.splits, &g.steps_per_split, &tiles);
   g.slab = ws;
   const dim3 grid(tiles, batch, g.splits), block(256);
   const bool a_kc = !ta, b_kc = tb;

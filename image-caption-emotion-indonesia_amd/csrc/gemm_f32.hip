@@ -135,9 +135,11 @@ static bool b3_enabled() {
 
 // Tile choice: the chip has 256 CUs and this kernel keeps ~3-4 workgroups per CU resident;
 // prefer the 128x128 tile (best operand reuse) once it alone fills the chip, else 64x64.
-int sgemm(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B,
-          long ldb, float* C, long ldc, const float* bias, int accumulate, int batch, long sA,
-          long sB, long sC, long sBias, int force_tile, hipStream_t stream) {
+// Host only: the argument checks and every choice sgemm makes, nothing launched (capnet_sgemm_route reports it).
+int sgemm_plan(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, const float* C,
+               long ldc, const float* bias, int accumulate, int batch, long sA, long sB, long sC, long sBias,
+               int force_tile, SgemmPlan* p) {
+  p->route = kRouteNone; p->vec = false; p->tiles_m = p->tiles_n = 0;
   CAPNET_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 0, "sgemm: negative dimension");
   if (M == 0 || N == 0 || batch == 0) return kOk;
   CAPNET_REQUIRE(A && B && C, "sgemm: null operand");
@@ -151,13 +153,49 @@ int sgemm(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const
   // (without a workspace for split-K partials it needs a grid of its own: a workgroup alone on its CU takes 1.8 us per
   //  32-k step, and below ~190 tiles of 128 x 128 the f32 kernels' 64 x 64 tiles win -- tools/probes/b3_small.py)
   if (force_tile == 0 && b3_enabled() && (long)cdiv(M, 128) * cdiv(N, 128) * batch >= 192 && (double)M * N * K * batch >= 2.5e8 &&
-      sgemm_b3_eligible(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, batch, sA, sB, sC, sBias))
-    return sgemm_b3(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, stream);
+      sgemm_b3_eligible(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, batch, sA, sB, sC, sBias)) {
+    p->route = kRouteB3; p->vec = true;
+    p->tiles_m = cdiv(M, 128); p->tiles_n = cdiv(N, 128);
+    return kOk;
+  }
   // y = x . W^T + b with dense K-contiguous operands and enough rows for 128-row tiles: the LDS-DMA
   // core (gemm_dma.hip) -- the vocabulary projection, encoder_att over all pixels, ...
   if (!ta && tb && batch == 1 && !accumulate && force_tile == 0 && M > 64 &&
-      (long)cdiv(M, 128) * (N / 64) >= 64 && sgemm_nt_dma_eligible(M, N, K, A, lda, B, ldb, C, ldc))
-    return sgemm_nt_dma(M, N, K, A, lda, B, C, bias, stream);
+      (long)cdiv(M, 128) * (N / 64) >= 64 && sgemm_nt_dma_eligible(M, N, K, A, lda, B, ldb, C, ldc)) {
+    p->route = kRouteNtDma; p->vec = true;
+    p->tiles_m = cdiv(M, 128); p->tiles_n = N / 64;
+    return kOk;
+  }
+  const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) &&
+                   (sA % 4 == 0) && (sB % 4 == 0);
+  const long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
+  int tile = force_tile;
+  if (tile == 0) tile = (t128 >= 384) ? 128 : 64;
+  if (tile == 128) {
+    p->tiles_m = cdiv(M, 128); p->tiles_n = cdiv(N, 128);
+    p->route = kRouteGeneric128;
+  } else if (tile == 64) {
+    p->tiles_m = cdiv(M, 64); p->tiles_n = cdiv(N, 64);
+    p->route = kRouteGeneric64;
+  } else if (tile == 6432) {   // 64x64 tile, 32-deep k slices: half the k-loop round trips
+    p->tiles_m = cdiv(M, 64); p->tiles_n = cdiv(N, 64);
+    p->route = kRouteGeneric6432;
+  } else {
+    CAPNET_REQUIRE(false, "sgemm: unknown tile %d", tile);
+  }
+  p->vec = vec;
+  return kOk;
+}
+
+int sgemm(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B,
+          long ldb, float* C, long ldc, const float* bias, int accumulate, int batch, long sA,
+          long sB, long sC, long sBias, int force_tile, hipStream_t stream) {
+  SgemmPlan p;
+  const int rc = sgemm_plan(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, force_tile, &p);
+  if (rc != kOk || p.route == kRouteNone) return rc;
+  if (p.route == kRouteB3)
+    return sgemm_b3(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, stream);
+  if (p.route == kRouteNtDma) return sgemm_nt_dma(M, N, K, A, lda, B, C, bias, stream);
   GemmArgs g;
   g.A = A; g.B = B; g.C = C; g.bias = bias;
   g.M = M; g.N = N; g.K = K;
@@ -166,23 +204,10 @@ int sgemm(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const
   g.accumulate = accumulate;
   g.splitk = 1;
   g.kchunk = K;
-  const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) &&
-                   (sA % 4 == 0) && (sB % 4 == 0);
-  const long t128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
-  int tile = force_tile;
-  if (tile == 0) tile = (t128 >= 384) ? 128 : 64;
-  if (tile == 128) {
-    g.tiles_m = cdiv(M, 128); g.tiles_n = cdiv(N, 128);
-    dispatch_layout<128, 128, 16>(g, batch, ta, tb, vec, stream);
-  } else if (tile == 64) {
-    g.tiles_m = cdiv(M, 64); g.tiles_n = cdiv(N, 64);
-    dispatch_layout<64, 64, 16>(g, batch, ta, tb, vec, stream);
-  } else if (tile == 6432) {   // 64x64 tile, 32-deep k slices: half the k-loop round trips
-    g.tiles_m = cdiv(M, 64); g.tiles_n = cdiv(N, 64);
-    dispatch_layout<64, 64, 32>(g, batch, ta, tb, vec, stream);
-  } else {
-    CAPNET_REQUIRE(false, "sgemm: unknown tile %d", tile);
-  }
+  g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+  if (p.route == kRouteGeneric128) dispatch_layout<128, 128, 16>(g, batch, ta, tb, p.vec, stream);
+  else if (p.route == kRouteGeneric64) dispatch_layout<64, 64, 16>(g, batch, ta, tb, p.vec, stream);
+  else dispatch_layout<64, 64, 32>(g, batch, ta, tb, p.vec, stream);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }
@@ -508,10 +533,9 @@ __global__ __launch_bounds__(256) void gemm_rows16_kernel(const R16Args g) {
   }
 }
 
-// true when the shape went to gemm_rows16_kernel
-static bool try_rows16(bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C,
-                       long ldc, const float* bias, int accumulate, int batch, long sA, long sB, float* ws,
-                       size_t ws_floats, int* counters, size_t n_counters, hipStream_t stream) {
+// true when the shape goes to gemm_rows16_kernel, then with its cut of K (host only)
+static bool rows16_plan(int M, int N, int K, const float* C, long ldc, const float* bias, int batch, const float* ws,
+                        size_t ws_floats, const int* counters, size_t n_counters, int* sub_out, int* splits_out) {
   if (!counters || M > 16 || N % 4 != 0 || N < 4 || ldc % 4 != 0 || !aligned16(C) || (bias && !aligned16(bias)) ||
       !aligned16(ws))
     return false;
@@ -530,6 +554,15 @@ static bool try_rows16(bool tb, int M, int N, int K, const float* A, long lda, c
     if (cost < best) { best = cost; sub = ns; splits = sp; }
   }
   if ((size_t)tiles_n * batch > n_counters || (splits > 1 && (size_t)splits * M * N * batch > ws_floats)) return false;
+  *sub_out = sub; *splits_out = splits;
+  return true;
+}
+
+// false when the kernel's LDS request was refused (the caller then plans again without this kernel)
+static bool launch_rows16(bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C,
+                          long ldc, const float* bias, int accumulate, int batch, long sA, long sB, float* ws,
+                          int* counters, int sub, int splits, hipStream_t stream) {
+  const int tiles_n = cdiv(N, 64);
   R16Args g;
   g.A = A; g.B = B; g.slab = ws; g.C = C; g.bias = bias; g.counters = counters;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB;
@@ -596,10 +629,14 @@ int reduce_slabs(const float* slab, int count, int M, int N, float* out, long ld
 
 // K-split product for M <= 128 rows, optionally batched over `batch` members whose outputs are
 // adjacent column blocks of C (sC == N, bias concatenated); falls back to sgemm otherwise.
-int sgemm_splitk_batched(bool ta, bool tb, int M, int N, int K, const float* A, long lda,
-                         const float* B, long ldb, float* C, long ldc, const float* bias,
-                         int accumulate, int batch, long sA, long sB, long sC, long sBias, float* ws,
-                         size_t ws_floats, hipStream_t stream, int* counters, size_t n_counters) {
+// Host only: every choice sgemm_splitk_batched makes, nothing launched (capnet_sgemm_splitk_route reports it).
+// allow_rows16 = false: what remains when gemm_rows16_kernel could not be set up.
+int sgemm_splitk_plan(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                      const float* C, long ldc, const float* bias, int accumulate, int batch, long sA, long sB, long sC,
+                      long sBias, const float* ws, size_t ws_floats, const int* counters, size_t n_counters,
+                      bool allow_rows16, SplitkPlan* p) {
+  p->route = kRouteNone; p->vec = true; p->splits = 1; p->chunk = 0; p->tiles = 0;
+  p->inner.route = kRouteNone; p->inner.vec = false; p->inner.tiles_m = p->inner.tiles_n = 0;
   if (M == 0 || N == 0 || batch == 0) return kOk;
   const bool skinny_ok = !ta && ws && M <= 128 && K % 4 == 0 && lda % 4 == 0 && aligned16(A) &&
                          aligned16(B) && ldb % 4 == 0 && (tb || N % 4 == 0) && N >= 4 && K >= 64 &&
@@ -613,7 +650,11 @@ int sgemm_splitk_batched(bool ta, bool tb, int M, int N, int K, const float* A, 
     if (ws && batch == 1 && M > 128 && K >= 512 && b3_enabled() && (double)M * N * K >= 2.5e8 &&
         sgemm_b3_eligible(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, 1, 0, 0, 0, 0)) {
       CAPNET_REQUIRE(A && B && C, "sgemm_splitk: null operand");
-      return sgemm_b3(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, 1, 0, 0, 0, 0, stream, ws, ws_floats);
+      int steps_per_split = 0;
+      sgemm_b3_plan(M, N, K, 1, ws, ws_floats, &p->splits, &steps_per_split, &p->tiles);
+      p->chunk = steps_per_split * 32;
+      p->route = kRouteB3Splitk;
+      return kOk;
     }
     if (ws && batch == 1 && M > 128 && tiles64 < 256 && K >= 1024) {
       CAPNET_REQUIRE(A && B && C, "sgemm_splitk: null operand");
@@ -621,28 +662,21 @@ int sgemm_splitk_batched(bool ta, bool tb, int M, int N, int K, const float* A, 
       if (splitk > K / 256) splitk = K / 256;
       while (splitk > 1 && (size_t)splitk * M * N > ws_floats) --splitk;
       if (splitk > 1) {
-        GemmArgs g;
-        g.A = A; g.B = B; g.C = ws; g.bias = nullptr;
-        g.M = M; g.N = N; g.K = K;
-        g.lda = lda; g.ldb = ldb; g.ldc = N;
-        g.sA = g.sB = g.sC = g.sBias = 0;
-        g.accumulate = 0;
-        g.kchunk = cdiv(cdiv(K, splitk), 16) * 16;
-        g.splitk = cdiv(K, g.kchunk);
-        g.tiles_m = cdiv(M, 64);
-        g.tiles_n = cdiv(N, 64);
-        const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0);
-        dispatch_layout<64, 64, 16>(g, 1, ta, tb, vec, stream);
-        return reduce_slabs(ws, g.splitk, M, N, C, ldc, bias, accumulate, stream);
+        p->chunk = cdiv(cdiv(K, splitk), 16) * 16;
+        p->splits = cdiv(K, p->chunk);
+        p->tiles = (int)tiles64;
+        p->vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0);
+        p->route = kRouteKloopSplitk;
+        return kOk;
       }
     }
-    return sgemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias,
-                 0, stream);
+    p->route = kRouteFellThrough;
+    return sgemm_plan(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, 0, &p->inner);
   }
   CAPNET_REQUIRE(A && B && C, "sgemm_splitk: null operand");
-  if (try_rows16(tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, ws, ws_floats, counters, n_counters,
-                 stream)) {
-    CAPNET_LAUNCH_CHECK();
+  if (allow_rows16 && rows16_plan(M, N, K, C, ldc, bias, batch, ws, ws_floats, counters, n_counters, &p->chunk, &p->splits)) {
+    p->tiles = cdiv(N, 64);
+    p->route = kRouteRows16;
     return kOk;
   }
   const long tiles = (long)cdiv(M, 64) * cdiv(N, 64) * batch;
@@ -650,20 +684,63 @@ int sgemm_splitk_batched(bool ta, bool tb, int M, int N, int K, const float* A, 
   // one K chunk per workgroup: 64 when that still leaves the chip under-filled, else 128
   int kc = tiles * cdiv(K, 128) < 200 ? 64 : 128;
   if ((size_t)cdiv(K, kc) * out_floats > ws_floats) kc = 128;
-  if ((size_t)cdiv(K, kc) * out_floats > ws_floats)
-    return sgemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias,
-                 0, stream);
-  const int splits = cdiv(K, kc);
-  if (kc == 64) {
+  if ((size_t)cdiv(K, kc) * out_floats > ws_floats) {
+    p->route = kRouteFellThrough;
+    return sgemm_plan(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, 0, &p->inner);
+  }
+  p->splits = cdiv(K, kc);
+  p->chunk = kc;
+  p->tiles = (int)tiles;
+  p->route = kc == 64 ? kRouteSkinny64 : kRouteSkinny128;
+  return kOk;
+}
+
+int sgemm_splitk_batched(bool ta, bool tb, int M, int N, int K, const float* A, long lda,
+                         const float* B, long ldb, float* C, long ldc, const float* bias,
+                         int accumulate, int batch, long sA, long sB, long sC, long sBias, float* ws,
+                         size_t ws_floats, hipStream_t stream, int* counters, size_t n_counters) {
+  SplitkPlan p;
+  int rc = sgemm_splitk_plan(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, ws,
+                             ws_floats, counters, n_counters, true, &p);
+  if (rc != kOk || p.route == kRouteNone) return rc;
+  if (p.route == kRouteRows16) {
+    if (launch_rows16(tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, ws, counters, p.chunk, p.splits,
+                      stream)) {
+      CAPNET_LAUNCH_CHECK();
+      return kOk;
+    }
+    rc = sgemm_splitk_plan(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, ws,
+                           ws_floats, counters, n_counters, false, &p);
+    if (rc != kOk) return rc;
+  }
+  if (p.route == kRouteFellThrough)
+    return sgemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, batch, sA, sB, sC, sBias, 0, stream);
+  if (p.route == kRouteB3Splitk)
+    return sgemm_b3(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, 1, 0, 0, 0, 0, stream, ws, ws_floats);
+  if (p.route == kRouteKloopSplitk) {
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = ws; g.bias = nullptr;
+    g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = N;
+    g.sA = g.sB = g.sC = g.sBias = 0;
+    g.accumulate = 0;
+    g.kchunk = p.chunk;
+    g.splitk = p.splits;
+    g.tiles_m = cdiv(M, 64);
+    g.tiles_n = cdiv(N, 64);
+    dispatch_layout<64, 64, 16>(g, 1, ta, tb, p.vec, stream);
+    return reduce_slabs(ws, g.splitk, M, N, C, ldc, bias, accumulate, stream);
+  }
+  if (p.route == kRouteSkinny64) {
     if (tb) launch_skinny<64, true>(A, lda, B, ldb, ws, M, N, K, batch, sA, sB, stream);
     else launch_skinny<64, false>(A, lda, B, ldb, ws, M, N, K, batch, sA, sB, stream);
   } else {
     if (tb) launch_skinny<128, true>(A, lda, B, ldb, ws, M, N, K, batch, sA, sB, stream);
     else launch_skinny<128, false>(A, lda, B, ldb, ws, M, N, K, batch, sA, sB, stream);
   }
-  const long total = (long)out_floats;
+  const long total = (long)M * N * batch;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)(cdiv(total, 256) > 2048 ? 2048 : cdiv(total, 256))),
-                     dim3(256), 0, stream, ws, splits, M, N * batch, C, ldc, bias, accumulate);
+                     dim3(256), 0, stream, ws, p.splits, M, N * batch, C, ldc, bias, accumulate);
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

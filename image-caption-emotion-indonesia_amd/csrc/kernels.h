@@ -18,6 +18,41 @@ int sgemm_b3(bool ta, bool tb, int M, int N, int K, const float* A, long lda, co
              const float* bias, int accumulate, int batch, long sA, long sB, long sC, long sBias, hipStream_t stream,
              float* ws = nullptr, size_t ws_floats = 0);
 
+// Which kernel a product is given (CAPNET_ROUTE_* of capnet.h). The two plan functions are host code: they make every
+// choice of sgemm / sgemm_splitk_batched -- the launch code consumes the plan -- and look at pointers for null and
+// alignment only.
+enum Route : int {
+  kRouteNone = 0,            // an empty product: nothing is launched
+  kRouteGeneric64 = 1, kRouteGeneric128 = 2, kRouteGeneric6432 = 3,   // gemm_f32_kernel's k-loop at that tile
+  kRouteNtDma = 4, kRouteB3 = 5, kRouteRows16 = 6, kRouteSkinny64 = 7, kRouteSkinny128 = 8,
+  kRouteKloopSplitk = 9,     // gemm_f32_kernel over K slabs + reduce_slabs
+  kRouteB3Splitk = 10,       // gemm_b3_kernel over K slabs + reduce_slabs
+  kRouteFellThrough = 64,    // sgemm_splitk_batched handed the product to sgemm, whose route is SplitkPlan::inner
+};
+struct SgemmPlan {
+  int route;
+  bool vec;                  // the generic kernel's loader form (16-B loads); true for nt_dma and b3
+  int tiles_m, tiles_n;
+};
+struct SplitkPlan {
+  int route;
+  bool vec;                  // k-loop split-K: the loader form; the other split-K kernels load 16 B
+  int splits;                // slabs of K
+  int chunk;                 // rows16: 256-k chunks per workgroup (sub); skinny: kc; k-loop / b3 split-K: k per slab
+  int tiles;                 // output tiles (rows16: 64-column tiles of one member)
+  SgemmPlan inner;           // kRouteFellThrough
+};
+int sgemm_plan(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, const float* C,
+               long ldc, const float* bias, int accumulate, int batch, long sA, long sB, long sC, long sBias,
+               int force_tile, SgemmPlan* p);
+int sgemm_splitk_plan(bool ta, bool tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                      const float* C, long ldc, const float* bias, int accumulate, int batch, long sA, long sB, long sC,
+                      long sBias, const float* ws, size_t ws_floats, const int* counters, size_t n_counters,
+                      bool allow_rows16, SplitkPlan* p);
+// gemm_b3.hip's own cut of K (splits = 1 without a workspace) and its 128 x 128 tile count
+void sgemm_b3_plan(int M, int N, int K, int batch, const float* ws, size_t ws_floats, int* splits, int* steps_per_split,
+                   int* tiles);
+
 // counters (optional): n_counters ints, zero before the first use and left zero by every call -- one per 64-column
 // output tile and batch member; with them, products of M <= 16 rows are ONE launch (gemm_rows16_kernel: the
 // workgroup that arrives last at a tile sums the K-chunk partials)

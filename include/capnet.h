@@ -40,7 +40,8 @@ int capnet_abi_version(void);
  * element strides. transA=0: A is [M][K]; 1: [K][M]. transB=0: B is [K][N]; 1: [N][K].
  * Replaces every nn.Linear forward and autograd matmul of the decoders and the encoder head:
  * stylenet/model.py:119-150 (V/S/U/W gates), :189-194 (C), :19,26 (encoder.linear);
- * nic/model.py:52,77,105-113. force_tile: 0 = auto, 64 or 128. */
+ * nic/model.py:52,77,105-113. force_tile: 0 = auto; 64, 128 or 6432 (64 x 64 tile, 32-deep k slices) keep the product
+ * on the generic k-loop kernel at that tile. */
 int capnet_sgemm(int transA, int transB, int M, int N, int K, const float* A, long lda,
                  const float* B, long ldb, float* C, long ldc, const float* bias, int accumulate,
                  int batch, long strideA, long strideB, long strideC, long strideBias,
@@ -82,6 +83,65 @@ int capnet_sgemm_splitk_fused(int transA, int transB, int M, int N, int K, const
 /* out[c] (+)= sum_r x[r][c]  -- bias gradients (autograd of nn.Linear bias). */
 int capnet_colsum(const float* x, long ld, int rows, int C, float* out, int accumulate,
                   capnet_stream_t stream);
+
+/* capnet_colsum with a workspace: inputs of more than 4096 rows are cut into row chunks (at most 32, workspace_floats >=
+ * chunks * C) whose partial sums capnet_reduce_slabs' kernel adds in chunk order. workspace NULL: capnet_colsum. */
+int capnet_colsum_ws(const float* x, long ld, int rows, int C, float* out, int accumulate, float* workspace,
+                     size_t workspace_floats, capnet_stream_t stream);
+
+/* out[m][n] = (((0 + slab[0][m][n]) + slab[1][m][n]) + ...) + bias[n], then + out[m][n] when accumulating: the fixed-order
+ * fp32 sum of `count` dense [M][N] partials that closes every split-K product. out has leading dimension ldc. */
+int capnet_reduce_slabs(const float* slab, int count, int M, int N, float* out, long ldc, const float* bias,
+                        int accumulate, capnet_stream_t stream);
+
+/* capnet_sgemm_splitk_fused over `batch` members (the four gates of the factored chain). The split-K kernels take the
+ * batch when the members' outputs are adjacent column blocks of C (strideC == N; bias concatenated, strideBias == N;
+ * strideA, strideB multiples of 4; batch <= 64); any other batch goes to capnet_sgemm's kernels. counters (optional):
+ * >= ceil(N/64) * batch ints. */
+int capnet_sgemm_splitk_batched(int transA, int transB, int M, int N, int K, const float* A, long lda,
+                                const float* B, long ldb, float* C, long ldc, const float* bias, int accumulate,
+                                int batch, long strideA, long strideB, long strideC, long strideBias,
+                                float* workspace, size_t workspace_floats, int* counters, size_t n_counters,
+                                capnet_stream_t stream);
+
+/* The K-chunk partial products only, A [M][K] not transposed: workspace[k][M][N] for k < *n_slabs, left for the consumer
+ * to sum in slab order (capnet_reduce_slabs, or a kernel that folds the sum in). *n_slabs = 0 and an untouched workspace
+ * when the shape does not qualify: _splitk_slabs is the M <= 128 kernel of capnet_sgemm_splitk, _rows16_slabs the
+ * M <= 16 kernel of capnet_sgemm_splitk_fused without its in-launch hand-off. */
+int capnet_sgemm_splitk_slabs(int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                              float* workspace, size_t workspace_floats, int* n_slabs, capnet_stream_t stream);
+int capnet_sgemm_rows16_slabs(int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                              float* workspace, size_t workspace_floats, int* n_slabs, capnet_stream_t stream);
+
+/* Which kernel capnet_sgemm / capnet_sgemm_splitk_batched gives a product: the dispatchers' own plan functions, run
+ * without launching anything (no device is needed; pointers are looked at for null and 16-B alignment only). Returns a
+ * CAPNET_ROUTE_* code, or a negative status where the call itself would be refused. detail (optional, 4 ints):
+ *   [0] loader form: 1 = 16-B vector loads, 0 = guarded scalar loads (odd leading dimension or stride, misaligned base)
+ *   [1] splits: slabs K is cut into (1: none)
+ *   [2] rows16: 256-k chunks per workgroup (sub); skinny: kc; k-loop / b3 split-K: k per slab (kchunk); else 0
+ *   [3] output tiles: 64 x 64 or 128 x 128 tiles of one batch member for the generic kernel, the k-loop split-K and b3;
+ *       64-column tiles of one member for rows16; 64 x 64 tiles of all members for skinny; ceil(M/128) * (N/64) for nt_dma
+ * tests/gemm_cases.py lists one product per branch with the route it must take. */
+#define CAPNET_ROUTE_NONE 0             /* empty product: nothing launched */
+#define CAPNET_ROUTE_GENERIC_64 1       /* gemm_f32_kernel, the k-loop, 64 x 64 tile, BK 16 */
+#define CAPNET_ROUTE_GENERIC_128 2      /* ... 128 x 128 tile */
+#define CAPNET_ROUTE_GENERIC_6432 3     /* ... 64 x 64 tile, BK 32 (force_tile 6432 only) */
+#define CAPNET_ROUTE_NT_DMA 4           /* nt_dma_kernel (gemm_dma.hip) */
+#define CAPNET_ROUTE_B3 5               /* gemm_b3_kernel (gemm_b3.hip) */
+#define CAPNET_ROUTE_ROWS16 6           /* gemm_rows16_kernel: M <= 16, one launch */
+#define CAPNET_ROUTE_SKINNY_64 7        /* gemm_skinny_kernel, kc = 64, + the slab reducer */
+#define CAPNET_ROUTE_SKINNY_128 8       /* ... kc = 128 */
+#define CAPNET_ROUTE_KLOOP_SPLITK 9     /* gemm_f32_kernel over K slabs + the slab reducer */
+#define CAPNET_ROUTE_B3_SPLITK 10       /* gemm_b3_kernel over K slabs + the slab reducer */
+#define CAPNET_ROUTE_FELL_THROUGH 64    /* flag: the split-K entry handed the product to capnet_sgemm; the low bits are
+                                           the route capnet_sgemm takes, `detail` is capnet_sgemm_route's */
+int capnet_sgemm_route(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                       const float* C, long ldc, const float* bias, int accumulate, int batch, long strideA,
+                       long strideB, long strideC, long strideBias, int force_tile, int* detail);
+int capnet_sgemm_splitk_route(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B,
+                              long ldb, const float* C, long ldc, const float* bias, int accumulate, int batch,
+                              long strideA, long strideB, long strideC, long strideBias, const float* workspace,
+                              size_t workspace_floats, const int* counters, size_t n_counters, int* detail);
 
 /* out[row] = index of the first maximum of x[row][0:V]  -- `output.max(1)` at
  * stylenet/model.py:190, nic/model.py:109. */
