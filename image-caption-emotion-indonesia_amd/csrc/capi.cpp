@@ -181,6 +181,35 @@ int capnet_conv_stem_fwd_f16x3(const float* x, long sxb, long sxc, long sxh, con
   return conv_stem_fwd_f16x3(x, sxb, sxc, sxh, image, y, part_sum, part_sq, B, H, W, S(stream));
 }
 
+// the convolution kernels' own eligibility predicates (host code, no device)
+int capnet_conv_v2_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int Cin, int Cout,
+                            const float* in_scale, const float* in_shift) {
+  return conv_v2_eligible(x, sxb, sxh, sxw, sxc, B, Cin, Cout, in_scale, in_shift) ? 1 : 0;
+}
+int capnet_conv1x1_dma_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                                int Cout, int stride) {
+  return conv1x1_dma_eligible(x, sxb, sxh, sxw, sxc, B, H, W, Cin, Cout, stride) ? 1 : 0;
+}
+int capnet_conv_f16x3_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                               int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift) {
+  return conv_f16x3_eligible(x, sxb, sxh, sxw, sxc, B, H, W, Cin, Cout, k, stride, pad, in_scale, in_shift) ? 1 : 0;
+}
+int capnet_conv3x3_patch_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                                  int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift) {
+  return conv3x3_patch_eligible(x, sxb, sxh, sxw, sxc, B, H, W, Cin, Cout, k, stride, pad, in_scale, in_shift) ? 1 : 0;
+}
+int capnet_conv1x1_areg_eligible(const float* x, long M, int Cin, int Cout, int bn, const float* in_scale,
+                                 const float* in_shift) {
+  return conv1x1_areg_eligible(x, M, Cin, Cout, bn, in_scale, in_shift) ? 1 : 0;
+}
+int capnet_conv1x1_tail_eligible(const float* y3, const float* res, long M, int Cin, int Cout) {
+  return conv1x1_tail_eligible(y3, res, M, Cin, Cout) ? 1 : 0;
+}
+int capnet_conv_stem_f16x3_eligible(const float* x, long sxb, long sxc, long sxh, long sxw, int B, int H, int W, int Cin,
+                                    int Cout, int k, int stride, int pad) {
+  return conv_stem_f16x3_eligible(x, sxb, sxc, sxh, sxw, B, H, W, Cin, Cout, k, stride, pad) ? 1 : 0;
+}
+
 int capnet_sgemm_splitk(int transA, int transB, int M, int N, int K, const float* A, long lda,
                         const float* B, long ldb, float* C, long ldc, const float* bias,
                         int accumulate, float* workspace, size_t workspace_floats,

@@ -402,6 +402,21 @@ void capnet_conv_kmajor_plan(int M, int Cout, int k_rows, int tile, int* out5);
 /* rows of the part_sum / part_sq arrays that call writes (tile = 0: its own choice) */
 int capnet_conv_kmajor_tiles_m(int M, int Cout, int k_rows, int tile);
 int capnet_conv_tiles_m(int M, int Cout, int tile);
+/* The convolution kernels' eligibility predicates as their launchers and the trunk apply them: 1 = the kernel takes this
+ * operand (address, strides in floats, shape), 0 = it refuses. Host code, no device; the pointers are only looked at. */
+int capnet_conv_v2_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int Cin, int Cout,
+                            const float* in_scale, const float* in_shift);
+int capnet_conv1x1_dma_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                                int Cout, int stride);
+int capnet_conv_f16x3_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                               int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift);
+int capnet_conv3x3_patch_eligible(const float* x, long sxb, long sxh, long sxw, long sxc, int B, int H, int W, int Cin,
+                                  int Cout, int k, int stride, int pad, const float* in_scale, const float* in_shift);
+int capnet_conv1x1_areg_eligible(const float* x, long M, int Cin, int Cout, int bn, const float* in_scale,
+                                 const float* in_shift);
+int capnet_conv1x1_tail_eligible(const float* y3, const float* res, long M, int Cin, int Cout);
+int capnet_conv_stem_f16x3_eligible(const float* x, long sxb, long sxc, long sxh, long sxw, int B, int H, int W, int Cin,
+                                    int Cout, int k, int stride, int pad);
 int capnet_bn_finalize(const float* part_sum, const float* part_sq, int tiles, int C, long count,
                        const float* gamma, const float* beta, float* running_mean,
                        float* running_var, float momentum, float eps, float* scale, float* shift,

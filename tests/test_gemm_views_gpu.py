@@ -15,11 +15,11 @@ import torch
 
 import gemm_cases as G
 from capnet._lib import current_stream, lib
+from helpers import SENTINEL, Window as FencedWindow
 
 pytestmark = pytest.mark.gpu
 
 BOUND = 2e-6
-SENTINEL = 0x7FC0BEEF                  # a NaN with a payload: int32 bits that no kernel writes
 WS_TAIL = 64
 WORST = {}                             # route -> worst |got - ref| / (BOUND * magnitude) seen so far
 
@@ -45,38 +45,13 @@ def problem(M, N, K, batch):
     return A, B, bias, C0, A.double() @ B.double(), A.double().abs() @ B.double().abs()
 
 
-class Window:
-    """values [batch][rows][cols] placed at (ld, off, stride) inside a flat device buffer with slack around it."""
-
-    def __init__(self, values, view, dev, poison_bits=None):
-        batch, rows, cols = values.shape
-        ld, off, stride = view
-        assert ld >= cols and (batch == 1 or stride >= cols)
-        pre, post = G.up4(ld) + 4, ld + 4                      # one whole row and more on either side
-        span = off + (batch - 1) * stride + (rows - 1) * ld + cols
-        z = torch.arange(batch).view(-1, 1, 1) * stride
-        r = torch.arange(rows).view(1, -1, 1) * ld
-        c = torch.arange(cols).view(1, 1, -1)
-        self.idx = (pre + off + z + r + c).reshape(-1).to(dev)
-        if poison_bits is None:
-            buf = torch.full((pre + span + post,), float("nan"), device=dev)
-        else:
-            buf = torch.full((pre + span + post,), poison_bits, dtype=torch.int32, device=dev).view(torch.float32)
-        buf[self.idx] = values.reshape(-1).to(dev)
-        self.buf, self.before, self.shape = buf, buf.clone(), values.shape
-        self.ptr = buf.data_ptr() + 4 * (pre + off)
-        assert (buf.data_ptr() + 4 * pre) % 16 == 0
-
-    def inside(self):
-        return self.buf[self.idx].view(self.shape)
-
-    def unchanged(self):
-        return torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
-
-    def outside_unchanged(self):
-        now = self.buf.clone()
-        now[self.idx] = self.before[self.idx]
-        return torch.equal(now.view(torch.int32), self.before.view(torch.int32))
+def Window(values, view, dev, poison_bits=None):
+    """values [batch][rows][cols] placed at (ld, off, stride) inside a flat device buffer with slack around it
+    (helpers.Window with one whole row and more on either side)."""
+    batch, rows, cols = values.shape
+    ld, off, stride = view
+    assert ld >= cols and (batch == 1 or stride >= cols)
+    return FencedWindow(values, (stride, ld, 1), dev, off=off, pre=G.up4(ld) + 4, post=ld + 4, fill_bits=poison_bits)
 
 
 def ws_used(case):
