@@ -27,6 +27,11 @@ Constraints(forced=...) / forced_allocate / met_mask: words every completed capt
 capnet_beam_topk_batched_forced (beam_search with n = 1), beam_search_device's ops.beam_advance selects with
 capnet_beam_advance_forced. Without forced words: the loops as they were.
 
+PerImage: a Constraints (or None) per image of a batched search, through the same keyword of
+beam_search_batched and beam_search_device: the host loop builds every row's ban list and met mask from its own image's
+entry for capnet_beam_topk_batched_rules; beam_search_device's ops.beam_advance selects with capnet_beam_advance_rules, one
+workgroup per image on its own row of the rule table.
+
 Deviation from the reference text: `top_k_words / vocab_size` (model.py:249) is an integer
 division here. Under the torch 1.1 the reference pins it was one; under current torch the
 reference line raises.
@@ -135,6 +140,90 @@ class Constraints(object):
     def __repr__(self):
         tail = ", forced=%r" % (self.forced,) if self.forced else ""
         return "Constraints(no_repeat_ngram=%d, min_words=%d, banned=%r%s)" % (self.no_repeat_ngram, self.min_words, self.banned, tail)
+
+
+MIXED = type("Mixed", (object,), {"__repr__": lambda self: "capnet.beam.MIXED", "__slots__": ()})()   # PerImage.uniform()
+
+
+class PerImage(object):
+    """A rule per image for a batched beam search: `entries`, one per image in batch order, each a Constraints
+    or None (no rule). Image i is searched exactly as it would be alone under entries[i]. It is NOT a Constraints: what takes
+    only a Constraints refuses it. The device routes read the rules from table() -- int32 [n][RULE_WORDS], row i: word 0
+    no_repeat_ngram, 1 min_words, 2 n_banned, 3 n_forced, 4 .. 35 banned, 36 .. 39 forced; a None or inactive entry is a row
+    of zeros (include/capnet.h) -- the host loops build every row's ban list and met mask from its own image's entry. len(),
+    indexing and slicing work; a slice is a PerImage."""
+    RULE_WORDS, BANNED_AT, FORCED_AT = 40, 4, 36
+
+    def __init__(self, entries):
+        if isinstance(entries, (str, bytes, Constraints)) or not hasattr(entries, "__iter__"):
+            raise ops.CapnetError("PerImage: entries must be a sequence of capnet.beam.Constraints or None, not %r" % (entries,))
+        entries = tuple(entries)
+        for c in entries:
+            if c is not None and not isinstance(c, Constraints):
+                raise ops.CapnetError("PerImage: every entry must be a capnet.beam.Constraints or None, not %r" % (c,))
+        self.entries = entries
+        self._tables = {}
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, i):
+        return PerImage(self.entries[i]) if isinstance(i, slice) else self.entries[i]
+
+    def __iter__(self):
+        return iter(self.entries)
+
+    @property
+    def active(self):
+        return any(c is not None and c.active for c in self.entries)
+
+    @staticmethod
+    def _fields(c):
+        return (0, 0, (), ()) if c is None else (c.no_repeat_ngram, c.min_words, c.banned, c.forced)
+
+    def uniform(self):
+        """The one Constraints all entries equal field by field (None where that is no rule: None and an inactive
+        Constraints() count as equal), or MIXED. An empty PerImage is None."""
+        fields = set(self._fields(c) for c in self.entries)
+        if len(fields) > 1:
+            return MIXED
+        first = self.entries[0] if self.entries else None
+        return first if first is not None and first.active else None
+
+    def check(self, vocab_size, end_token, k, max_seq_length, n):
+        """The front end's check (CapnetError): an entry per image, and every active entry's own Constraints.check."""
+        if len(self.entries) != n:
+            raise ops.CapnetError("constraints: a PerImage of %d entries for %d images" % (len(self.entries), n))
+        for c in self.entries:
+            if c is not None and c.active:
+                c.check(vocab_size, end_token, k, max_seq_length)
+
+    def rows(self):
+        """The table as n lists of RULE_WORDS ints."""
+        out = []
+        for c in self.entries:
+            g, m, banned, forced = self._fields(c)
+            out.append([g, m, len(banned), len(forced)] + list(banned) + [0] * (Constraints.MAX_BANNED - len(banned))
+                       + list(forced) + [0] * (Constraints.MAX_FORCED - len(forced)))
+        return out
+
+    def table(self, device):
+        """The rule table on `device`: contiguous int32 [n, RULE_WORDS], made once per device and kept."""
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = torch.tensor(self.rows(), dtype=torch.int32, device=device).reshape(len(self.entries), self.RULE_WORDS)
+        return self._tables[key]
+
+    def __repr__(self):
+        return "PerImage(%r)" % (list(self.entries),)
+
+
+def entry_of(constraints, image):
+    """The rule of image `image`: a PerImage's entry (None -> a Constraints() that excludes nothing), else `constraints`."""
+    if isinstance(constraints, PerImage):
+        c = constraints[image]
+        return Constraints() if c is None else c
+    return constraints
 
 
 class Diversity(object):
@@ -258,26 +347,37 @@ def forced_allocate(pool, live, F):
     return out
 
 
-def _met(rows_tokens, constraints, device):
-    """The met masks of a step's logits rows as capnet_beam_topk_batched_forced takes them: int32 [rows] on the device."""
-    return torch.tensor([met_mask(t, constraints.forced) for t in rows_tokens], dtype=torch.int32, device=device)
+def _met(rows_tokens, constraints, device, images=None):
+    """The met masks of a step's logits rows as capnet_beam_topk_batched_forced takes them: int32 [rows] on the device.
+    images (with a PerImage): the image of every row, whose own entry's forced ids are the row's (none: 0)."""
+    return torch.tensor([met_mask(t, entry_of(constraints, None if images is None else images[r]).forced)
+                         for r, t in enumerate(rows_tokens)], dtype=torch.int32, device=device)
 
 
-def _bans(rows_tokens, step, end_token, constraints, device):
+def _bans(rows_tokens, step, end_token, constraints, device, images=None):
     """The ban lists of a step's logits rows as capnet_beam_topk[_batched]_banned takes them: int32 [rows, 1 + cap] on the
-    device, per row its count and its words."""
-    lists = [banned_words(t, step, end_token, constraints) for t in rows_tokens]
+    device, per row its count and its words. images (with a PerImage): the image of every row, whose own entry is the row's
+    rule (None: an empty list)."""
+    lists = [banned_words(t, step, end_token, entry_of(constraints, None if images is None else images[r]))
+             for r, t in enumerate(rows_tokens)]
     cap = max(1, max(len(b) for b in lists))
     return torch.tensor([[len(b)] + b + [0] * (cap - len(b)) for b in lists], dtype=torch.int32, device=device)
 
 
-def _select(logits, scores, meta, rows_tokens, step, end_token, constraints, diversity, device):
+def _select(logits, scores, meta, rows_tokens, step, end_token, constraints, diversity, device, images=None):
     """One step's selection for the host loops, which hold the hypotheses: every logits row's ban list where there are
     constraints (removed after the log-sum-exp), every row's met mask where they force words, then ONE call.
     meta: [(first row, competing rows, k)] per image -- per (image, group) with diversity -- for capnet_beam_topk_batched and
     its _banned / _diverse / _forced forms -> (scores [n, 16], flat [n, 16]). A single such tuple: beam_search's one image ->
     (scores [k], flat [k]) from capnet_beam_topk[_banned], the single-image kernel, or under forced words from
-    capnet_beam_topk_batched_forced with n = 1. rows_tokens: the token lists of the logits rows (None without constraints)."""
+    capnet_beam_topk_batched_forced with n = 1. rows_tokens: the token lists of the logits rows (None without constraints).
+    constraints a PerImage (beam_search_batched; images: the image of every logits row): every row's list and mask under its
+    own image's entry, and capnet_beam_topk_batched_rules, which reads every image's forced ids from the rule table."""
+    if isinstance(constraints, PerImage):
+        meta_d = torch.tensor(meta, dtype=torch.int32, device=device)
+        bans = _bans(rows_tokens, step, end_token, constraints, device, images)
+        met = (constraints, _met(rows_tokens, constraints, device, images), end_token)
+        return ops.beam_topk_batched(logits, scores, meta_d, bans=bans, forced=met)
     forced = constraints is not None and bool(constraints.forced) and diversity is None
     if isinstance(meta, tuple) and not forced:
         _, rows, k = meta
@@ -355,6 +455,8 @@ def beam_search_device(step_fn, state, n, vocab_size, start_token, end_token, k,
     (read with capnet_beam_nbest, one copy)."""
     if k > 16 or k > vocab_size:
         raise ops.CapnetError("beam_search_device: k <= 16 and k <= vocab_size")
+    if isinstance(constraints, PerImage) and (diversity is not None or len(constraints) != n):
+        raise ops.CapnetError("beam_search_device: a PerImage takes an entry per image and no diversity")
     T = max_seq_length + 1
     words = [torch.empty(n * k, dtype=torch.long, device=device) for _ in range(2)]
     parent_rows = torch.empty(n * k, dtype=torch.long, device=device)
@@ -396,11 +498,14 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
     (first step: row 0 only; <end> retires a beam; the best completed sequence wins; empty -> [<end>]).
     `state`: tuple of tensors with n * k leading rows (image i's k beams at rows i k .. i k + k - 1).
     Returns a list of n token lists (each starts with start_token); nbest: per image rank_completed of its completed list.
+    constraints: a Constraints for all images, or a PerImage of n entries (without diversity): every row under its own image's.
     diversity (an active Diversity whose groups divide k): the bookkeeping below is kept per (image, group) -- n D searches
     of k / D beams, group g of image i at rows (i D + g) k / D .. -- and every step selects with
     capnet_beam_topk_batched_diverse, one workgroup per image walking its groups; the result is merge_groups per image."""
     if k > 16:
         raise ops.CapnetError("beam_search_batched: k <= 16")
+    if isinstance(constraints, PerImage) and (diversity is not None or len(constraints) != n):
+        raise ops.CapnetError("beam_search_batched: a PerImage takes an entry per image and no diversity")
     D = 1 if diversity is None else diversity.groups
     n_img, n, k = n, n * D, k // D
     live = [k] * n                                           # beams still open per image
@@ -416,7 +521,8 @@ def beam_search_batched(step_fn, state, n, vocab_size, start_token, end_token, k
             meta.append((row0, (1 if step == 1 else live[i]) if live[i] else 0, live[i]))
             row0 += live[i]
         live_seqs = None if constraints is None else [q for i in range(n) for q in seqs[i]]     # image i's live beams in order
-        scores_d, flat_d = _select(logits, top_scores, meta, live_seqs, step, end_token, constraints, diversity, device)
+        images = [i for i in range(n) for _ in seqs[i]] if isinstance(constraints, PerImage) else None
+        scores_d, flat_d = _select(logits, top_scores, meta, live_seqs, step, end_token, constraints, diversity, device, images)
         scores, flat = scores_d.tolist(), flat_d.tolist()
         keep_rows, next_words, next_scores = [], [], []
         for i in range(n):

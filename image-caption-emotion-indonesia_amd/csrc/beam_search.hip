@@ -941,8 +941,108 @@ int beam_forced_check(const char* who, const BeamConstraints& c) {
   return kOk;
 }
 
+// ---- per-image rules: the rule of a step as a row of a device table instead of kernel arguments. rules int32
+// [n][kBeamRuleWords]: word 0 no_repeat_ngram | 1 min_words | 2 n_banned | 3 n_forced | 4 .. 35 banned | 36 .. 39 forced;
+// a row of zeros is no rule. The host cannot read the table, so every count is clamped to its range as it is read: whatever
+// the table holds, banned and forced are indexed inside the row. The row's address depends on blockIdx alone, so what is
+// read from it is uniform over the workgroup and so is every branch taken on it.
+constexpr int kRuleBanned = 4, kRuleForced = kRuleBanned + kBanMax;
+static_assert(kRuleForced + kForcedMax == kBeamRuleWords, "the rule row: 4 counts, the banned words, the forced ids");
+
+struct BeamRule {
+  int g, min_words, n_banned, n_forced;
+  const int *banned, *forced;   // into the row
+  __device__ __forceinline__ bool excludes() const { return (g | min_words | n_banned) != 0; }
+};
+
+__device__ __forceinline__ BeamRule beam_rule_of(const int* __restrict__ rules, int image) {
+  const int* row = rules + (long)image * kBeamRuleWords;
+  BeamRule r;
+  r.g = min(max(row[0], 0), kNgramMax);
+  r.min_words = max(row[1], 0);
+  r.n_banned = min(max(row[2], 0), kBanMax);
+  r.n_forced = min(max(row[3], 0), kForcedMax);
+  r.banned = row + kRuleBanned;
+  r.forced = row + kRuleForced;
+  return r;
+}
+
+// one step of image blockIdx.x under ITS OWN rule (capnet_beam_advance_rules): the row decides, for the whole workgroup,
+// between the three selections of the kernels above -- forced ids: beam_advance_forced_kernel's; else anything excluded:
+// beam_advance_constrained_kernel's; else beam_advance_kernel's -- each the same beam_topk_body instance on the same
+// functors, built from the row where those kernels build them from their arguments. The tail is used as it is.
+__global__ __launch_bounds__(kBeamThreads) void beam_advance_rules_kernel(
+    void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step, long long end_token,
+    const int* __restrict__ rules, long long* __restrict__ next_words, long long* __restrict__ parent_rows) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_met[kBeamMax], s_picked;
+  const BeamState s = beam_state_of(beam, n, k, max_steps);
+  const int i = blockIdx.x, L = max_steps + 2;
+  const long row0 = (long)i * k;
+  const BeamRule r = beam_rule_of(rules, i);   // (in front of the branch on live: the two loads are in flight together)
+  const int live = s.live[i];
+  int picked = live;
+  if (live > 0) {
+    const int* tok = s.seq + ((long)((step - 1) & 1) * n * k + row0) * L;
+    const int rows = step == 1 ? 1 : live;
+    const BeamExclState own{tok, L, step, r.g, r.min_words, end_token, r.banned, r.n_banned};
+    if (r.n_forced > 0) {
+      const BeamExclForced<BeamExclState> excl{own, tok, L, step, nullptr, r.forced, r.n_forced, end_token, s_met};
+      beam_topk_body<BeamExclForced<BeamExclState>, BeamNoPen, BeamForcedPool>(
+          logits + row0 * ld, ld, rows, V, s.scores + row0, live, s_score, s_flat, excl, BeamNoPen(),
+          BeamForcedPool{r.forced, r.n_forced, s_met, &s_picked});
+      picked = s_picked;
+    } else if (r.excludes()) {
+      beam_topk_body<BeamExclState>(logits + row0 * ld, ld, rows, V, s.scores + row0, live, s_score, s_flat, own);
+    } else {
+      beam_topk_body<BeamNoExcl>(logits + row0 * ld, ld, rows, V, s.scores + row0, live, s_score, s_flat);
+    }
+  }
+  beam_advance_tail<kBeamThreads>(s, i, n, k, max_steps, step, end_token, V, live, picked, s_score, s_flat, next_words,
+                                  parent_rows, beam_trace_of(trace, n, k, max_steps));
+}
+
+// the host loops' form (capnet_beam_topk_batched_rules): beam_topk_batched_forced_kernel with the forced ids and their count
+// read from image blockIdx.x's row; bans (nullable) and met per logits row are Python's, built from each row's own image's
+// rule. An image without forced ids takes the banned selection on its rows, the plain one where bans is null. Outputs as
+// the forced form's: `live` entries of a row set, -inf / -1 where the pool held fewer.
+__global__ __launch_bounds__(kBeamThreads) void beam_topk_batched_rules_kernel(
+    float* logits, long ld, int V, const float* __restrict__ prev, const int* __restrict__ meta, const int* __restrict__ bans,
+    int cap, const int* __restrict__ met, const int* __restrict__ rules, long long end_token, float* __restrict__ out_scores,
+    long long* __restrict__ out_index) {
+  __shared__ float s_score[kBeamMax];
+  __shared__ long long s_flat[kBeamMax];
+  __shared__ int s_met[kBeamMax], s_picked;
+  const int row0 = meta[3 * blockIdx.x], rows = meta[3 * blockIdx.x + 1], live = meta[3 * blockIdx.x + 2];
+  if (live <= 0 || rows <= 0 || live > kBeamMax || rows > kBeamMax) return;   // (meta lives on the device: bounded here)
+  const BeamRule r = beam_rule_of(rules, blockIdx.x);
+  const BeamExclListOrNone own{bans ? bans + (long)row0 * (1 + cap) : nullptr, cap};
+  int picked = live;
+  if (r.n_forced > 0) {
+    const BeamExclForced<BeamExclListOrNone> excl{own, nullptr, 0, 0, met + row0, r.forced, r.n_forced, end_token, s_met};
+    beam_topk_body<BeamExclForced<BeamExclListOrNone>, BeamNoPen, BeamForcedPool>(
+        logits + (long)row0 * ld, ld, rows, V, prev + row0, live, s_score, s_flat, excl, BeamNoPen(),
+        BeamForcedPool{r.forced, r.n_forced, s_met, &s_picked});
+    picked = s_picked;
+  } else {
+    beam_topk_body<BeamExclListOrNone>(logits + (long)row0 * ld, ld, rows, V, prev + row0, live, s_score, s_flat, own);
+  }
+  if (threadIdx.x < live) {
+    const bool has = threadIdx.x < picked;
+    out_scores[(long)blockIdx.x * kBeamMax + threadIdx.x] = has ? s_score[threadIdx.x] : -INFINITY;
+    out_index[(long)blockIdx.x * kBeamMax + threadIdx.x] = has ? s_flat[threadIdx.x] : -1;
+  }
+}
+
+int beam_rules_check(const char* who, const int* rules) {
+  CAPNET_REQUIRE(rules != nullptr && (size_t)rules % 16 == 0,
+                 "%s: rules must be a 16-byte aligned device table of int32 [n][%d]", who, kBeamRuleWords);
+  return kOk;
+}
+
 // ---- the two launchers of the selection step. Both choose the kernel by WHICH options are given, never by what they
-// hold: teams -> the diverse kernel; else forced ids (n_forced != 0) -> the forced kernel; else constraints (a ban list)
+// hold: a rule table without teams -> the per-image kernel; teams -> the diverse kernel; else forced ids (n_forced != 0) -> the forced kernel; else constraints (a ban list)
 // -> the constrained (banned) kernel; else the plain kernel, which only reads the logits. `who` is the caller's name, in
 // front of every message.
 static int beam_team_range_check(const char* who, int D, float strength) {
@@ -961,15 +1061,18 @@ int beam_teams_check(const char* who, int k, int D, float strength) {
 int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
                  long long end_token, const BeamConstraints* con, const BeamTeams* teams, long long* next_words,
                  long long* parent_rows, void* trace, hipStream_t stream) {
-  const bool forced = con && con->n_forced && !teams;
+  const bool per_image = con && con->rules && !teams;   // (the table replaces the scalar fields, which are then not read)
+  const bool forced = con && con->n_forced && !teams && !per_image;
   int D = 1;
   if (teams) {
     if (int rc = beam_teams_check(who, k, teams->teams, teams->strength)) return rc;
     CAPNET_REQUIRE(n >= 1 && n <= (1 << 24), "%s: n=%d teams=%d", who, n, teams->teams);
     D = teams->teams;
   }
+  if (per_image)
+    if (int rc = beam_rules_check(who, con->rules)) return rc;
   if (int rc = beam_check(who, beam, n * D, k / D, max_steps)) return rc;
-  if (con)
+  if (con && !per_image)
     if (int rc = beam_constraints_check(who, *con)) return rc;
   if (forced)
     if (int rc = beam_forced_check(who, *con)) return rc;
@@ -978,7 +1081,10 @@ int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int
                  "%s: V=%d k=%d ld=%ld step=%d max_steps=%d (k <= V <= ld; 1 <= step <= max_steps)", who, V, k, ld, step, max_steps);
   const BeamConstraints c = con ? *con : BeamConstraints{0, 0, nullptr, 0};
   const dim3 grid(n), block(kBeamThreads);
-  if (teams)
+  if (per_image)
+    hipLaunchKernelGGL(beam_advance_rules_kernel, grid, block, 0, stream, beam, trace, logits, ld, V, n, k, max_steps, step,
+                       end_token, c.rules, next_words, parent_rows);
+  else if (teams)
     hipLaunchKernelGGL(beam_advance_diverse_kernel, grid, block, 0, stream, beam, trace, logits, ld, V, n, k, D, teams->strength,
                        max_steps, step, end_token, c.no_repeat_ngram, c.min_words, c.banned, c.n_banned, next_words, parent_rows);
   else if (forced)
@@ -997,12 +1103,15 @@ int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int
 
 // the host loops' form. meta: DEVICE array [n][3] = (first row, rows that compete, k) per image -- per (image, team), [n D][3],
 // with teams -- rows and k <= 16 (the caller checks: the values live on the device); outputs [n][16] ([n D][16]). bans
-// (with cap) nullable; met: int32 per logits row, required with forced ids.
+// (with cap) nullable; met: int32 per logits row, required with forced ids and with rules (the per-image table, which then
+// gives every image its forced ids; forced / n_forced are not read).
 int beam_topk_batched(const char* who, float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans,
                       int cap, const BeamTeams* teams, const int* met, const int* forced, int n_forced, long long end_token,
-                      float* out_scores, long long* out_index, hipStream_t stream) {
-  const bool forced_form = n_forced && !teams;
-  CAPNET_REQUIRE(logits && prev && meta && out_scores && out_index && n >= 0 && V >= 1 && ld >= V && (met || !forced_form),
+                      float* out_scores, long long* out_index, hipStream_t stream, const int* rules) {
+  const bool per_image = rules && !teams;
+  const bool forced_form = n_forced && !teams && !per_image;
+  CAPNET_REQUIRE(logits && prev && meta && out_scores && out_index && n >= 0 && V >= 1 && ld >= V &&
+                     (met || !(forced_form || per_image)),
                  "%s: bad argument", who);
   if (teams)
     if (int rc = beam_team_range_check(who, teams->teams, teams->strength)) return rc;
@@ -1012,9 +1121,16 @@ int beam_topk_batched(const char* who, float* logits, long ld, int V, const floa
     CAPNET_REQUIRE((size_t)met % 4 == 0, "%s: met must be 4-byte aligned", who);
     if (int rc = beam_forced_check(who, BeamConstraints{0, 0, nullptr, 0, forced, n_forced})) return rc;
   }
+  if (per_image) {
+    CAPNET_REQUIRE((size_t)met % 4 == 0, "%s: met must be 4-byte aligned", who);
+    if (int rc = beam_rules_check(who, rules)) return rc;
+  }
   if (n == 0) return kOk;
   const dim3 grid(n), block(kBeamThreads);
-  if (teams)
+  if (per_image)
+    hipLaunchKernelGGL(beam_topk_batched_rules_kernel, grid, block, 0, stream, logits, ld, V, prev, meta, bans, cap, met, rules,
+                       end_token, out_scores, out_index);
+  else if (teams)
     hipLaunchKernelGGL(beam_topk_batched_diverse_kernel, grid, block, 0, stream, logits, ld, V, prev, meta, teams->teams,
                        teams->strength, bans, cap, out_scores, out_index);
   else if (forced_form)

@@ -725,6 +725,18 @@ int capnet_beam_decode_forced(int cell, int nlayers, int n, int k, int E, int H,
                            Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream, &con);
 }
 
+int capnet_beam_decode_rules(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                             long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                             const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                             size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                             capnet_stream_t stream, const int* rules) {
+  if (int rc = beam_rules_check("beam_decode_rules", rules)) return rc;   // (NULL would be the plain search)
+  BeamConstraints con{0, 0, nullptr, 0};
+  con.rules = rules;
+  return beam_decode_entry("beam_decode_rules", cell, nlayers, 1, n, k, E, H, V, max_steps, start_token, end_token, emb, wcat, beff,
+                           Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths, steps_run, err_flag, stream, &con);
+}
+
 int capnet_beam_decode_diverse(int cell, int nlayers, int n, int k, int teams, float strength, int E, int H, int V, int max_steps,
                                long long start_token, long long end_token, const float* emb, const float* const* wcat,
                                const float* const* beff, const float* Cw, const float* Cb, const float* state0, void* workspace,
@@ -1353,6 +1365,21 @@ int capnet_att_beam_decode_forced(int cell, int nlayers, int n, int k, int P, in
                                steps_run, err_flag, stream, false, alphas, &con);
 }
 
+int capnet_att_beam_decode_rules(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                 long long start_token, long long end_token, const float* att1, const float* feat,
+                                 const float* emb, const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                 const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                 const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                                 long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                 float* alphas, const int* rules) {
+  if (int rc = beam_rules_check("att_beam_decode_rules", rules)) return rc;
+  BeamConstraints con{0, 0, nullptr, 0};
+  con.rules = rules;
+  return att_beam_decode_entry(cell, nlayers, 1, n, k, P, A, C, E, H, V, max_steps, start_token, end_token, att1, feat, emb, wz, bz,
+                               w_full, b_full, wcat, beff, Cw, Cb, state0, workspace, slab, slab_floats, poll_every, seqs, lengths,
+                               steps_run, err_flag, stream, false, alphas, &con);
+}
+
 int capnet_att_beam_decode_groups(int cell, int nlayers, int groups, int n, int k, int P, int A, int C, int E, int H, int V,
                                   int max_steps, long long start_token, long long end_token, const float* att1,
                                   const float* feat, const float* emb, const float* wz, const float* bz, const float* w_full,
@@ -1728,6 +1755,22 @@ int capnet_beam_topk_batched_forced(float* logits, long ld, int V, const float* 
   if (int rc = beam_forced_check("beam_topk_batched_forced", BeamConstraints{0, 0, nullptr, 0, forced, n_forced})) return rc;
   return beam_topk_batched("beam_topk_batched_forced", logits, ld, V, prev_scores, meta, n, bans, cap, nullptr, met, forced, n_forced,
                            end_token, top_scores, top_index, S(stream));
+}
+int capnet_beam_advance_rules(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                              long long end_token, const int* rules, long long* next_words, long long* parent_rows,
+                              capnet_stream_t stream) {
+  if (int rc = beam_rules_check("beam_advance_rules", rules)) return rc;   // (NULL would be the plain step)
+  BeamConstraints con{0, 0, nullptr, 0};
+  con.rules = rules;
+  return beam_advance("beam_advance_rules", beam, logits, ld, V, n, k, max_steps, step, end_token, &con, nullptr, next_words,
+                      parent_rows, trace, S(stream));
+}
+int capnet_beam_topk_batched_rules(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                   const int* bans, int cap, const int* met, const int* rules, long long end_token,
+                                   float* top_scores, long long* top_index, capnet_stream_t stream) {
+  if (int rc = beam_rules_check("beam_topk_batched_rules", rules)) return rc;
+  return beam_topk_batched("beam_topk_batched_rules", logits, ld, V, prev_scores, meta, n, bans, cap, nullptr, met, nullptr, 0,
+                           end_token, top_scores, top_index, S(stream), rules);
 }
 int capnet_beam_finish_traced(const void* beam, const void* trace, int n, int k, int max_steps, long long end_token,
                               long long* seqs, int* lengths, int* rows, capnet_stream_t stream) {

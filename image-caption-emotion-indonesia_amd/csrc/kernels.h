@@ -270,7 +270,12 @@ struct BeamConstraints {
   // the scores are the plain ones.
   const int* forced = nullptr;
   int n_forced = 0;
+  // per-image rules: a DEVICE int32 table [n][kBeamRuleWords], row i the rule of image i -- word 0
+  // no_repeat_ngram, 1 min_words, 2 n_banned, 3 n_forced, 4 .. 35 banned, 36 .. 39 forced; a row of zeros: no rule. Set: the
+  // fields above are not read, and every workgroup takes its own row, each count clamped to its range as it is read.
+  const int* rules = nullptr;
 };
+constexpr int kBeamRuleWords = 40;
 // diverse search: n images x k beams as `teams` teams of k / teams. Team g of an image selects after teams
 // 0 .. g - 1 by score - strength * (candidates they chose at this step with the same word); the scores written are
 // unpenalised. (beam: the one-call searches' -- the block that holds the state of n teams searches of k / teams beams)
@@ -281,10 +286,12 @@ struct BeamTeams {
 };
 int beam_constraints_check(const char* who, const BeamConstraints& c);
 int beam_forced_check(const char* who, const BeamConstraints& c);                  // (refuses n_forced == 0)
+int beam_rules_check(const char* who, const int* rules);                          // (non-null, 16-byte aligned)
 int beam_teams_check(const char* who, int k, int teams, float strength);          // (the only check of either range)
 // One step on the device state, and the same selection in the host loops' form. con / bans, teams, forced ids and trace are
-// each nullable (0), and WHICH are given chooses the kernel: teams -> diverse (its constraints and ban lists optional);
-// else forced ids -> forced; else con / bans -> constrained; else plain, which leaves the logits block as it is (every
+// each nullable (0), and WHICH are given chooses the kernel: con->rules without teams -> the per-image kernel, which takes
+// each image's branch from its row (rules in the host loops' form: met is required, bans optional, forced / n_forced
+// unread); teams -> diverse (its constraints and ban lists optional); else forced ids -> forced; else con / bans -> constrained; else plain, which leaves the logits block as it is (every
 // other kernel modifies it). With teams, beam and trace are those of n teams searches of k / teams beams and meta is
 // [n teams][3] per (image, team). who: the caller's name, in front of every message.
 int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int n, int k, int max_steps, int step,
@@ -293,7 +300,7 @@ int beam_advance(const char* who, void* beam, float* logits, long ld, int V, int
 // (met int32 per logits row, bit f: forced[f] is among the row's words)
 int beam_topk_batched(const char* who, float* logits, long ld, int V, const float* prev, const int* meta, int n, const int* bans,
                       int cap, const BeamTeams* teams, const int* met, const int* forced, int n_forced, long long end_token,
-                      float* out_scores, long long* out_index, hipStream_t stream);
+                      float* out_scores, long long* out_index, hipStream_t stream, const int* rules = nullptr);
 // (trace, optional, beam_trace_bytes: the row history of every hypothesis beside the state -- rows[2][n][k][L] |
 // done_rows[n][k][L] int32, entry e = the slot whose step-e attention preceded word e; beam_finish then also writes the
 // winner's rows [n][max_steps] as decoder-step rows i k + slot, -1 past length - 1)

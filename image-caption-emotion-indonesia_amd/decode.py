@@ -46,7 +46,7 @@ import os
 import torch
 
 from . import ops
-from .beam import Constraints, Diversity, beam_search, beam_search_batched, beam_search_device, by_completion, merge_groups
+from .beam import MIXED, Constraints, Diversity, PerImage, beam_search, beam_search_batched, beam_search_device, by_completion, merge_groups
 
 FUSED_DECODE_OFF = "CAPNET_NO_FUSED_DECODE_STEP"
 _GATE_BLOCKS = (0, 1, 3, 2)     # the kernel's gate blocks i, f, o, c~ from torch's i, f, g, o
@@ -143,17 +143,20 @@ def _one_call_att(dec, att, n_img, k, start_token, end_token, poll_every, return
     if diversity is not None:       # (ops.att_beam_decode then returns a list per (image, group): chunks concatenate as ever)
         con["diversity"] = diversity
 
-    def call(a1, ft, st):
+    def call(a1, ft, st, i0=0, i1=n_img):
+        kw = con
+        if isinstance(constraints, PerImage) and (i0, i1) != (0, n_img):     # a chunk of images: its own rows of the rule table
+            kw = dict(con, constraints=constraints[i0:i1])
         return ops.att_beam_decode(att.cell, a1, ft, att.emb, att.wz, att.bz, att.full_att.weight, att.full_att.bias, att.wcat,
                                    att.beff, att.Cw, att.Cb, st, k, T, start_token, end_token, poll_every,
-                                   return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty, **con)
+                                   return_alphas=return_alphas, nbest=nbest, length_penalty=length_penalty, **kw)
     per = max(1, ALPHA_TRACE_MAX_BYTES // (T * k * P * 4)) if return_alphas else n_img
     if per >= n_img:
         return call(att.att1, att.feat, att.state)
     seqs, maps = [], []
     for i0 in range(0, n_img, per):
         i1 = min(n_img, i0 + per)
-        q, m = call(att.att1[i0:i1], att.feat[i0:i1], att.state[i0 * k:i1 * k])
+        q, m = call(att.att1[i0:i1], att.feat[i0:i1], att.state[i0 * k:i1 * k], i0, i1)
         seqs += q
         maps += m
     return seqs, maps
@@ -204,6 +207,13 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     selection, through the same keyword on the same routes -- capnet_beam_topk_batched_forced under the host loops,
     capnet_beam_advance_forced on_device, capnet_beam_decode_forced / capnet_att_beam_decode_forced one_call (the latter
     records the maps itself, as the constrained one-call search does). Not with an active diversity (CapnetError).
+    constraints a capnet.beam.PerImage (n images: sample_batch): an entry per image, each a Constraints or None,
+    and image i is searched as it would be alone under entries[i]. PerImage.check runs first (an entry per image, every
+    active entry's own check), then PerImage.uniform: entries that all say the same are that one Constraints (or no keyword)
+    and run the code that ran before; only a mixed set takes the per-image entries, on the same routes --
+    capnet_beam_topk_batched_rules under the host loop, capnet_beam_advance_rules on_device, capnet_beam_decode_rules /
+    capnet_att_beam_decode_rules one_call (the map chunks each with their slice of the entries). Not for one image (n None)
+    and not with an active diversity (CapnetError).
     diversity (a capnet.beam.Diversity): diverse beam search -- the k beams of an image as D groups of k / D
     that select in order at every step, a later group paying `strength` for every candidate an earlier group chose at that
     step with the same word (<end> counted like any word). The penalty shapes the selection only; the scores stay the
@@ -220,7 +230,17 @@ def beam_decode(dec, step_fn, state, n, k, start_token, end_token, on_device=Fal
     length_penalty = ops.check_length_penalty("beam search", nbest, length_penalty)
     dev, n_img, V, T = state[0].device, 1 if n is None else n, dec.vocab_size, dec.max_seq_length
     nb = dict(nbest=True, length_penalty=length_penalty) if nbest else {}
-    if constraints is not None:
+    if isinstance(constraints, PerImage):       # a rule per image: checked, then one rule for all wherever that is what it says
+        if n is None:
+            raise ops.CapnetError("constraints: a PerImage belongs to sample_batch (sample decodes one image: hand it a Constraints)")
+        if diversity is not None and isinstance(diversity, Diversity) and diversity.active:
+            raise ops.CapnetError("constraints: a PerImage does not go with an active diversity (DESIGN 7)")
+        constraints.check(V, end_token, k, T, n_img)
+        one_rule = constraints.uniform()
+        if one_rule is MIXED:
+            nb["constraints"] = constraints
+        constraints = one_rule                  # (a Constraints or None: the call as with that keyword; MIXED: set above)
+    if constraints is not None and constraints is not MIXED:
         if not isinstance(constraints, Constraints):
             raise ops.CapnetError("constraints must be a capnet.beam.Constraints, not %r" % (constraints,))
         if constraints.active:                  # (not active: the calls as they were before there was the keyword, unchecked)
@@ -434,6 +454,8 @@ def sample_random_device(dec, step_fn, state, n, m, start_token, end_token, temp
         raise ops.CapnetError("%s: %d samples and the greedy row: an attention decoder takes at most 16 rows per image" % (who, m))
     dev = state[0].device
     if exclude is not None:
+        if not isinstance(exclude, Constraints):        # (a PerImage too: a draw takes one rule for all rows)
+            raise ops.CapnetError("exclude must be a capnet.beam.Constraints, not %r" % (exclude,))
         exclude.check_exclude(V, end_token, top_k, steps)
         if not exclude.active:
             exclude = None

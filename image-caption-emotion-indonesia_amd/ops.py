@@ -224,7 +224,9 @@ def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None, forc
     forced = (constraints, met, end_token) (capnet_beam_topk_batched_forced): a capnet.beam.Constraints with forced words,
     met int32 [rows] on the device -- per logits row the mask of the forced ids its hypothesis holds -- and <end>, which the
     kernel excludes on a row whose mask is not full; bans as below or None. The selection is the forced-word allocation
-    (include/capnet.h); `logits` is modified."""
+    (include/capnet.h); `logits` is modified. constraints a capnet.beam.PerImage of n entries
+    (capnet_beam_topk_batched_rules): every image's forced ids are read from its row of the rule table; met and bans hold
+    what each row's own image's entry gives."""
     _need_cuda(logits, prev_scores, meta)
     logits, prev_scores = _c(logits), _c(prev_scores)
     if meta.dtype != torch.int32 or meta.dim() != 2 or meta.shape[1] != 3 or not meta.is_contiguous():
@@ -243,8 +245,13 @@ def beam_topk_batched(logits, prev_scores, meta, bans=None, diversity=None, forc
         _need_cuda(met)
         if met.dtype != torch.int32 or met.dim() != 1 or met.numel() < logits.shape[0] or not met.is_contiguous():
             raise CapnetError("beam_topk_batched: met must be a contiguous int32 tensor with an entry per logits row")
-        name = "capnet_beam_topk_batched_forced"
-        args = block + (n, ptr(bans), cap, ptr(met)) + forced_args(constraints, logits.device) + (int(end_token),)
+        if is_per_image(constraints):
+            name = "capnet_beam_topk_batched_rules"
+            args = block + (n, ptr(bans), cap, ptr(met)) + rules_arg("beam_topk_batched", constraints, n, logits.device) \
+                + (int(end_token),)
+        else:
+            name = "capnet_beam_topk_batched_forced"
+            args = block + (n, ptr(bans), cap, ptr(met)) + forced_args(constraints, logits.device) + (int(end_token),)
     elif diversity is not None:
         teams = int(diversity.groups)
         if n % teams:
@@ -321,6 +328,27 @@ def has_forced(constraints):
     return constraints is not None and bool(getattr(constraints, "forced", ()))
 
 
+def is_per_image(constraints):
+    """Whether `constraints` is a capnet.beam.PerImage (a rule per image): the capnet_*_rules entries then."""
+    return hasattr(constraints, "entries") and hasattr(constraints, "table")
+
+
+RULE_WORDS = 40       # CAPNET_BEAM_RULE_WORDS
+
+
+def rules_arg(who, per_image, n, device):
+    """The `rules` argument of the capnet_*_rules entries for a capnet.beam.PerImage of n entries: the pointer of its table
+    on `device` (PerImage.table: int32 [n, RULE_WORDS], uploaded once per device and kept by the object), checked here
+    because the C entries cannot read it."""
+    if len(per_image) != n:
+        raise CapnetError("%s: a PerImage of %d entries for %d images" % (who, len(per_image), n))
+    table = per_image.table(device)
+    if table.dtype != torch.int32 or tuple(table.shape) != (n, RULE_WORDS) or not table.is_contiguous() or table.data_ptr() % 16:
+        raise CapnetError("%s: the rule table must be a contiguous, 16-byte aligned int32 [n, %d] tensor" % (who, RULE_WORDS))
+    _need_cuda(table)
+    return (ptr(table),)
+
+
 def forced_args(constraints, device):
     """The two arguments behind constraint_args' four in the capnet_*_forced entries: (the forced ids as a device int32 array,
     their count), the array kept as constraint_args keeps the banned words'."""
@@ -334,6 +362,8 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constra
     diversity (a capnet.beam.Diversity; capnet_beam_advance_diverse): `beam` is the state of n D searches of k / D beams
     (beam_init(n D, k / D, ...)), state-image i D + g being team g of image i; one workgroup per image walks its teams in
     order under the Hamming penalty; constraints may be None.
+    Else constraints a capnet.beam.PerImage of n entries (capnet_beam_advance_rules): every image's workgroup takes its rule
+    from its own row of the rule table.
     Else constraints with forced words (capnet_beam_advance_forced): their exclusions, then the forced-word allocation.
     Else constraints (a capnet.beam.Constraints; capnet_beam_advance_constrained[_traced]): the selecting workgroup
     excludes what they forbid, from the sequences in the state.
@@ -353,6 +383,8 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constra
     state, dev = (ptr(beam.words),), logits.device
     block = (ptr(logits), logits.stride(0) if n * k > 1 else logits.shape[1], logits.shape[1])
     at = (beam.max_steps, int(step), int(end_token))
+    if diversity is not None and is_per_image(constraints):
+        raise CapnetError("%s: a PerImage does not go with diversity" % who)
     if diversity is not None:
         teams = int(diversity.groups)
         if n % teams:
@@ -360,6 +392,9 @@ def beam_advance(beam, logits, step, end_token, next_words, parent_rows, constra
         name = "capnet_beam_advance_diverse"
         args = state + (ptr(trace),) + block + (n // teams, k * teams, teams, float(diversity.strength)) + at \
             + (NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev))
+    elif is_per_image(constraints):
+        name = "capnet_beam_advance_rules"
+        args = state + (ptr(trace),) + block + (n, k) + at + rules_arg(who, constraints, n, dev)
     elif has_forced(constraints):
         name = "capnet_beam_advance_forced"
         args = state + (ptr(trace),) + block + (n, k) + at + constraint_args(constraints, dev) + forced_args(constraints, dev)
@@ -1523,7 +1558,8 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     the workspace); the list is empty where nothing completed. The search itself is the same.
     constraints (a capnet.beam.Constraints; capnet_beam_decode_constrained, one weight group): every step selects with
     capnet_beam_advance_constrained; workspace and results as without. With forced words (Constraints(forced=...)):
-    capnet_beam_decode_forced, every step selecting with capnet_beam_advance_forced.
+    capnet_beam_decode_forced, every step selecting with capnet_beam_advance_forced. A capnet.beam.PerImage of n entries:
+    capnet_beam_decode_rules, every step selecting with capnet_beam_advance_rules on the object's rule table.
     diversity (a capnet.beam.Diversity whose groups D divide k; capnet_beam_decode_diverse, one weight group; constraints may
     come with it): the diverse search. The result is then the RAW material of capnet.beam.merge_groups: n D lists, one per
     (image, team) in that order, each capnet_beam_nbest's (tokens, score) pairs at length_penalty 0 -- whatever nbest and
@@ -1542,6 +1578,8 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     outside = "%s: n=%d k=%d V=%d max_steps=%d outside the limits" % (who, n, k, V, T)
     if constraints is not None and groups > 1:
         raise CapnetError("%s: constraints take one weight group" % who)
+    if diversity is not None and is_per_image(constraints):
+        raise CapnetError("%s: a PerImage does not go with diversity" % who)
     nq, kq, beam_at = n, k, (nl, n_img, k, H, V, T, 0, groups)     # the searches whose state the call leaves, and where
     if diversity is not None:
         teams, strength = _teams(who, diversity, k, groups)
@@ -1558,6 +1596,8 @@ def beam_decode(cell, wcat, beff, emb, Cw, Cb, n, k, max_steps, start_token, end
     if diversity is not None:
         name, args = "capnet_beam_decode_diverse", (n, k, teams, strength) + args \
             + (NO_CONSTRAINTS if constraints is None else constraint_args(constraints, dev))
+    elif is_per_image(constraints):
+        name, args = "capnet_beam_decode_rules", (n, k) + args + rules_arg(who, constraints, n, dev)
     elif has_forced(constraints):
         name, args = "capnet_beam_decode_forced", (n, k) + args + constraint_args(constraints, dev) + forced_args(constraints, dev)
     elif constraints is not None:
@@ -1782,7 +1822,8 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     of (tokens, score) pairs.
     constraints (a capnet.beam.Constraints; capnet_att_beam_decode_constrained / capnet_att_beam_decode_alphas_constrained, one
     weight group): every step selects with capnet_beam_advance_constrained; workspaces and results as without. With forced
-    words (Constraints(forced=...)): capnet_att_beam_decode_forced, with or without the maps.
+    words (Constraints(forced=...)): capnet_att_beam_decode_forced, with or without the maps. A capnet.beam.PerImage with an
+    entry per image: capnet_att_beam_decode_rules on the object's rule table, with or without the maps.
     diversity (capnet_att_beam_decode_diverse, one weight group; constraints may come with it): as beam_decode's -- the
     result is n D lists of (tokens, score), one per (image, team), capnet_beam_nbest's at length_penalty 0; with
     return_alphas followed by the maps of every hypothesis in the same nesting.
@@ -1803,6 +1844,9 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     outside = "att_beam_decode: n=%d k=%d V=%d max_steps=%d outside the limits" % (n, k, V, T)
     if constraints is not None and groups > 1:
         raise CapnetError("att_beam_decode: constraints take one weight group")
+    per_image = is_per_image(constraints)
+    if diversity is not None and per_image:
+        raise CapnetError("att_beam_decode: a PerImage does not go with diversity")
     alpha_dims = (nl, groups, n_img, k, P, A, Cdim, E, H, V, T)
     size = ("capnet_att_beam_decode_alphas_ws_bytes", dev, alpha_dims, outside) if return_alphas else \
         ("capnet_att_beam_decode_ws_bytes", dev, (nl, n, k, P, A, Cdim, E, H, V, T), outside)
@@ -1819,12 +1863,14 @@ def att_beam_decode(cell, att1, feat, emb, wz, bz, w_full, b_full, wcat, beff, C
     steps = C.c_int(0)
     alphas = (torch.empty((nq, T, P), dtype=torch.float32, device=dev), alpha_dims) if return_alphas else None
     maps = (ptr(alphas[0]) if alphas else None,)
-    con = () if constraints is None else constraint_args(constraints, dev)
+    con = () if constraints is None or per_image else constraint_args(constraints, dev)
     args = (P, A, Cdim, E, H, V, T, int(start_token), int(end_token), ptr(att1), ptr(feat), ptr(emb), ptr(wz), ptr(bz), ptr(wf),
             ptr(bf), ptr_array(wcat), ptr_array(beff), ptr(Cw), ptr(Cb), ptr(state), ptr(ws), ptr(slab), slab.numel(),
             int(poll_every), seqs, lengths, C.byref(steps), ptr(flag), current_stream())
     if diversity is not None:       # one entry, the maps nullable
         name, args = "capnet_att_beam_decode_diverse", (n, k, teams, strength) + args + maps + (con or NO_CONSTRAINTS)
+    elif per_image:                 # one entry, the maps nullable
+        name, args = "capnet_att_beam_decode_rules", (n_img, k) + args + maps + rules_arg("att_beam_decode", constraints, n_img, dev)
     elif has_forced(constraints):   # one entry, the maps nullable
         name, args = "capnet_att_beam_decode_forced", (n_img, k) + args + maps + con + forced_args(constraints, dev)
     elif return_alphas:

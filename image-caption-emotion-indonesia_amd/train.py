@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import decode, ops
+from .beam import Constraints, PerImage
 from .metrics import CiderCorpus, corpus_bleu, corpus_cider_d, sentence_bleu, sentence_cider_d
 from .utils import AverageMeter, accuracy, clip_gradient
 
@@ -192,6 +193,8 @@ def self_critical_step(decoder, optimizer, features, reward, start_token, end_to
     if baseline == "mean" and int(samples) < 2:
         raise ValueError("baseline='mean' needs samples >= 2 (the mean of the other samples)")
     kw = {} if mode is None else {"mode": mode}
+    if exclude is not None and not isinstance(exclude, Constraints):     # (a PerImage too: one rule for all rows)
+        raise ops.CapnetError("exclude must be a capnet.beam.Constraints, not %r" % (exclude,))
     ex, con = ({}, {}) if exclude is None else ({"exclude": exclude}, {"constraints": exclude})
     if isinstance(reward, (DeviceBleuReward, DeviceCiderReward)):
         m, greedy = int(samples), baseline == "greedy"
@@ -685,7 +688,9 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
     builds them: the captions' and the sampled ids as they are, <start> / <end> included). The reference calls
     decoder.sample() per image; here a loader batch is decoded at once (decoder.sample_batch: B x k rows per step) --
     the same sequences (tests/test_sample_gpu.py). on_device / one_call: passed on to the decoder (capnet.decode.beam_decode).
-    constraints: a capnet.beam.Constraints, passed on likewise (None: the calls as they were).
+    constraints: a capnet.beam.Constraints, passed on likewise (None: the calls as they were); or a capnet.beam.PerImage over
+    the whole loader in image order, every batch decoded under its slice -- CapnetError where the loader holds more images than
+    it has entries (at that batch) or fewer (at the end).
     diversity: a capnet.beam.Diversity, passed on likewise; the metrics are taken on the winner over all groups.
     Returns (bleu_1, bleu_2, bleu_3, bleu_4); with cider=True a fifth entry, the mean CIDEr-D of the decoded captions
     (capnet.metrics.corpus_cider_d, the corpus being the loader's own references, as the COCO scorer takes a test split)."""
@@ -698,7 +703,8 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
         kw["on_device"] = True
     if one_call:
         kw["one_call"] = True
-    if constraints is not None:
+    per_image = constraints if isinstance(constraints, PerImage) else None
+    if constraints is not None and per_image is None:
         kw["constraints"] = constraints
     if diversity is not None:
         kw["diversity"] = diversity
@@ -706,7 +712,15 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
     for images, captions, lengths, all_captions in data_loader:
         with torch.no_grad():
             features = encoder(images.to(device))
-        if hasattr(decoder, "sample_batch"):
+        if per_image is not None:       # this batch's entries, in image order
+            i0, i1 = len(hypotheses), len(hypotheses) + features.size(0)
+            if i1 > len(per_image):
+                raise ops.CapnetError("evaluate: a PerImage of %d entries, and the loader is at image %d" % (len(per_image), i1))
+            kw["constraints"] = per_image[i0:i1]
+        if per_image is not None and not hasattr(decoder, "sample_batch"):
+            seqs = [decoder.sample(features[i:i + 1], start_token=start, end_token=end, k=k,
+                                   **dict(kw, constraints=per_image[i0 + i]))[0].tolist() for i in range(features.size(0))]
+        elif hasattr(decoder, "sample_batch"):
             seqs = decoder.sample_batch(features, start_token=start, end_token=end, k=k, **kw)
         else:       # (a decoder without one: image by image, as the reference does)
             seqs = [decoder.sample(features[i:i + 1], start_token=start, end_token=end, k=k, **kw)[0].tolist()
@@ -724,6 +738,8 @@ def evaluate(encoder, decoder, vocab, data_loader, mode='factual', k=5, device=N
                             break
                     print(name, ' '.join(words))
     assert len(references) == len(hypotheses)
+    if per_image is not None and len(per_image) != len(hypotheses):
+        raise ops.CapnetError("evaluate: a PerImage of %d entries for a loader of %d images" % (len(per_image), len(hypotheses)))
     ops.check_device_errors()
     out = _scores(references, hypotheses, cider)
     if verbose:

@@ -1639,6 +1639,52 @@ int capnet_att_beam_decode_forced(int cell, int nlayers, int n, int k, int P, in
                                   float* alphas, int no_repeat_ngram, int min_words, const int* banned, int n_banned,
                                   const int* forced, int n_forced);
 
+/* ---- Per-image rules (capnet.beam.PerImage; no reference counterpart) ----
+ * Every image of a batched search under a rule of its own: the constraint and forced-word arguments above as ONE DEVICE
+ * table, rules int32 [n][CAPNET_BEAM_RULE_WORDS], row i the rule of image i (160 bytes a row, the table 16-byte aligned):
+ *   word 0        no_repeat_ngram (0 .. 4)
+ *   word 1        min_words (>= 0)
+ *   word 2        n_banned (0 .. 32)
+ *   word 3        n_forced (0 .. 4)
+ *   words 4..35   banned: the first n_banned are read
+ *   words 36..39  forced: the first n_forced are read
+ * A row of zeros is no rule: that image's search is capnet_beam_advance's. The host cannot read the table, so the kernels
+ * clamp each of the four counts to the range above as they read it: whatever the table holds, nothing outside the row is
+ * indexed, and a word id outside [0, V) is never an address (as everywhere above). What the ids must satisfy for the search
+ * to keep k candidates is the caller's to check (capnet.beam.PerImage.check). The entries refuse a NULL or misaligned
+ * rules on the host.
+ *   capnet_beam_advance_rules: capnet_beam_advance_forced's arguments with rules in place of the six constraint arguments.
+ *     One workgroup per image, as there; it reads its row once and takes, as a whole, the forced selection (n_forced > 0),
+ *     else the constrained one (any other count non-zero), else the plain one -- the selections of the entries above, on the
+ *     row's values. trace: NULL, or the row trace. THE LOGITS BLOCK IS MODIFIED. */
+#define CAPNET_BEAM_RULE_WORDS 40
+int capnet_beam_advance_rules(void* beam, void* trace, float* logits, long ld, int V, int n, int k, int max_steps, int step,
+                              long long end_token, const int* rules, long long* next_words, long long* parent_rows,
+                              capnet_stream_t stream);
+/* The host loops' form: capnet_beam_topk_batched_forced with the forced ids and their count read per image from rules
+ * (row i for meta row i); bans (NULL, or a list per logits row) and met (required, a mask per logits row) are built by the
+ * caller from each row's own image's rule. An image with n_forced == 0 takes capnet_beam_topk_batched_banned's selection
+ * on its rows (capnet_beam_topk_batched's where bans is NULL). */
+int capnet_beam_topk_batched_rules(float* logits, long ld, int V, const float* prev_scores, const int* meta, int n,
+                                   const int* bans, int cap, const int* met, const int* rules, long long end_token,
+                                   float* top_scores, long long* top_index, capnet_stream_t stream);
+/* capnet_beam_decode_forced with rules [n][CAPNET_BEAM_RULE_WORDS] in place of its six constraint arguments: every step
+ * selects with capnet_beam_advance_rules; workspace and results as there. */
+int capnet_beam_decode_rules(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
+                             long long end_token, const float* emb, const float* const* wcat, const float* const* beff,
+                             const float* Cw, const float* Cb, const float* state0, void* workspace, float* slab,
+                             size_t slab_floats, int poll_every, long long* seqs, int* lengths, int* steps_run, int* err_flag,
+                             capnet_stream_t stream, const int* rules);
+/* capnet_att_beam_decode_forced likewise: alphas NULL or [n][max_steps][P] with the workspaces named there, the trace
+ * passed through to capnet_beam_advance_rules. */
+int capnet_att_beam_decode_rules(int cell, int nlayers, int n, int k, int P, int A, int C, int E, int H, int V, int max_steps,
+                                 long long start_token, long long end_token, const float* att1, const float* feat,
+                                 const float* emb, const float* wz, const float* bz, const float* w_full, const float* b_full,
+                                 const float* const* wcat, const float* const* beff, const float* Cw, const float* Cb,
+                                 const float* state0, void* workspace, float* slab, size_t slab_floats, int poll_every,
+                                 long long* seqs, int* lengths, int* steps_run, int* err_flag, capnet_stream_t stream,
+                                 float* alphas, const int* rules);
+
 #ifdef __cplusplus
 }
 #endif
