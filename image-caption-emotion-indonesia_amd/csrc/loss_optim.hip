@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__
     lse[row] = l;
     const long long t = target[row];
     if (t < 0 || t >= V) {
-      atomicExch(err_flag, 2);
+      atomicOr(err_flag, 2);
       row_loss[row] = 0.f;
     } else {
       row_loss[row] = l - p[t];
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ x, 
 
 int xent_fwd(const float* logits, long ld, int N, int V, const long long* targets, float* lse,
              float* row_loss, float* loss, int* err_flag, hipStream_t stream) {
-  CAPNET_REQUIRE(logits && targets && lse && row_loss && loss && err_flag && N > 0 && V > 0,
+  CAPNET_REQUIRE(logits && targets && lse && row_loss && loss && err_flag && N > 0 && V > 0 && ld >= V,
                  "xent_fwd: bad argument");
   hipLaunchKernelGGL(xent_fwd_kernel, dim3(N), dim3(256), 0, stream, logits, ld, V, targets, lse,
                      row_loss, err_flag);
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
 
 int xent_bwd(const float* logits, long ld, int N, int V, const long long* targets,
              const float* lse, const float* gout, float* dlogits, long ldd, hipStream_t stream) {
-  CAPNET_REQUIRE(logits && targets && lse && gout && dlogits && N > 0 && V > 0,
+  CAPNET_REQUIRE(logits && targets && lse && gout && dlogits && N > 0 && V > 0 && ld >= V && ldd >= V,
                  "xent_bwd: bad argument");
   hipLaunchKernelGGL(xent_bwd_kernel, dim3(N), dim3(256), 0, stream, logits, ld, V, targets, lse,
                      gout, 1.f / (float)N, dlogits, ldd);
@@ -90,6 +90,12 @@ int xent_bwd(const float* logits, long ld, int N, int V, const long long* target
 }
 
 // ---- clamp + Adam, many tensors per launch ------------------------------------------------
+// torch.clamp: a NaN stays NaN (both comparisons are false). fminf(fmaxf(x, lo), hi) would hand back lo for it, and a NaN
+// gradient would become a finite step that nothing ever shows.
+__device__ __forceinline__ float clamp_keep_nan(float x, float lo, float hi) {
+  return x < lo ? lo : (x > hi ? hi : x);
+}
+
 constexpr int kAdamMaxTensors = 40;
 constexpr int kAdamChunk = 2048;  // elements per workgroup (256 threads x 2 float4)
 
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void clamp_adam_kernel(AdamTable t, float b1, 
     if (i >= n) break;
     float gi = g[i];
     if (clip > 0.f) {
-      gi = fminf(fmaxf(gi, -clip), clip);
+      gi = clamp_keep_nan(gi, -clip, clip);
       if (write_grad) g[i] = gi;
     }
     const float m0 = m[i];
@@ -273,7 +279,7 @@ __global__ __launch_bounds__(256) void topk_correct_kernel(const float* __restri
   const int row = blockIdx.x;
   const long long tg = targets[row];
   if (tg < 0 || tg >= V) {
-    if (threadIdx.x == 0) atomicMax(err_flag, 2);
+    if (threadIdx.x == 0) atomicOr(err_flag, 2);
     return;
   }
   const float* p = logits + (long)row * ld;
@@ -307,7 +313,7 @@ __global__ __launch_bounds__(256) void clamp_kernel(float* __restrict__ x, long 
                                                     float hi) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long)gridDim.x * blockDim.x)
-    x[i] = fminf(fmaxf(x[i], lo), hi);
+    x[i] = clamp_keep_nan(x[i], lo, hi);
 }
 
 int clamp_inplace(float* x, long n, float lo, float hi, hipStream_t stream) {

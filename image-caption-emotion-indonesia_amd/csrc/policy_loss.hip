@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void policy_xent_fwd_kernel(const float* __res
     lse[row] = l;
     const long long t = target[row];
     if (t < 0 || t >= V) {
-      atomicExch(err_flag, 2);
+      atomicOr(err_flag, 2);
       row_logp[row] = 0.f;
     } else {
       row_logp[row] = -(l - p[t]);   // xent_fwd_kernel's row loss, negated

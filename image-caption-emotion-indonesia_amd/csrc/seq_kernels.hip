@@ -72,7 +72,7 @@ __global__ __launch_bounds__(128) void gather_inputs_kernel(
       drop = (col >= 0) && use_dropout != 0;
     }
     if (tok < 0 || tok >= V) {  // out-of-range token id: flag it, read row 0 (never fault)
-      if (threadIdx.x == 0) atomicExch(err_flag, 1);
+      if (threadIdx.x == 0) atomicOr(err_flag, 1);
       tok = 0;
     }
     src = emb + (long)tok * E;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(128) void embedding_fwd_kernel(const long long* __r
   const int r = blockIdx.x;
   long long t = idx[r];
   if (t < 0 || t >= V) {
-    if (threadIdx.x == 0) atomicExch(err_flag, 1);
+    if (threadIdx.x == 0) atomicOr(err_flag, 1);
     t = 0;
   }
   for (int e = threadIdx.x; e < E; e += blockDim.x) out[(long)r * E + e] = emb[t * E + e];

@@ -1306,7 +1306,9 @@ int capnet_lstm_persist_run(const float* w_img, float* gates, float* cell_states
                             int* ctl, int* err_flag, unsigned long long* stamps,
                             capnet_stream_t stream);
 
-/* ---- loss: nn.CrossEntropyLoss() (mean) -- stylenet/train_multitask.py:134,383 ---------- */
+/* ---- loss: nn.CrossEntropyLoss() (mean) -- stylenet/train_multitask.py:134,383 ----------
+ * logits [N][V] with leading dimension ld >= V, dlogits likewise with ldd >= V (a smaller one is refused). A target
+ * outside [0, V) sets bit 1 (value 2) of err_flag, beside whatever bits the word already holds. */
 int capnet_xent_fwd(const float* logits, long ld, int N, int V, const long long* targets,
                     float* lse, float* row_loss, float* loss, int* err_flag,
                     capnet_stream_t stream);
@@ -1400,7 +1402,8 @@ int capnet_topk_correct(const float* logits, long ld, int N, int V, const long l
 /* ---- optimiser: utils.clip_gradient (element-wise clamp, stylenet/utils.py:51-60) fused with
  * torch.optim.Adam.step (stylenet/train_multitask.py:166-167,389; no weight decay, no amsgrad).
  * Host arrays of n device pointers / sizes / per-tensor step counts (>= 1, already
- * incremented). clip <= 0 disables the clamp; write_grad != 0 also stores the clamped grad.
+ * incremented). clip <= 0 disables the clamp; write_grad != 0 also stores the clamped grad. The clamp is
+ * torch.clamp's: a NaN gradient stays NaN, and so do the moments and the parameter it reaches.
  * skip_flag: NULL, or the device error word the step's kernels were given (err_flag): while it is non-zero
  * the launch leaves parameters, moments and gradients untouched -- a step whose inputs were invalid (token id or
  * target out of range, an expired wait of the persistent LSTM kernel) is dropped, not applied. */
@@ -1471,7 +1474,8 @@ int capnet_err_word_exchange(int* err_flag, float* slot, int direction, capnet_s
  * when check_device_errors() reports them. */
 int capnet_count_skipped(const int* err_flag, int* counter, capnet_stream_t stream);
 
-/* x[i] = min(max(x[i], lo), hi): utils.clip_gradient alone (stylenet/utils.py:57-60). */
+/* x[i] = min(max(x[i], lo), hi) as torch.clamp has it, a NaN staying NaN: utils.clip_gradient alone
+ * (stylenet/utils.py:57-60). */
 int capnet_clamp(float* x, long n, float lo, float hi, capnet_stream_t stream);
 
 /* ---- Constrained beam search (capnet.beam.Constraints; no reference counterpart: the reference patches its
