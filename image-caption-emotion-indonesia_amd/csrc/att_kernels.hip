@@ -234,7 +234,7 @@ __device__ __forceinline__ long beam_src_row(const AttBeamArgs& a, int row) {
   if (!a.parent) return row;
   const long long p = a.parent[row];
   const bool ok = p >= 0 && p < (long long)a.n * a.k;
-  if (!ok) *a.err = 1;
+  if (!ok) atomicOr(a.err, 1);
   return ok ? (long)p : (long)row;
 }
 
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(kAttThreads) void att_beam_context_kernel(AttBeamAr
       const long row = (long)img * k + r;
       const long long t = a.tok[row];
       const bool ok = t >= 0 && t < a.V;
-      if (!ok) *a.err = 1;
+      if (!ok) atomicOr(a.err, 1);
       *reinterpret_cast<float4*>(a.xa + row * a.ldx + 4 * q) =
           *reinterpret_cast<const float4*>(a.emb + (ok ? (long)t : 0L) * E + 4 * q);
     }

@@ -1575,6 +1575,28 @@ int capnet_lstm_step_fused_stamped(const float* h_prev, const float* w_frag, flo
 }
 int capnet_lstm_step_fused_supported(int b, int H) { return lstm_step_fused_supported(b, H) ? 1 : 0; }
 
+int capnet_lstm_step_fused_route(int b, int H, int* detail) {
+  StepFusedRoute r;
+  if (!lstm_step_fused_route(b, H, &r)) return 0;
+  if (detail) detail[0] = r.ngw, detail[1] = r.mt, detail[2] = r.halves, detail[3] = r.xcd_map;
+  return 1;
+}
+
+int capnet_stacked_decode_route(int E, int H, int xvec, int* detail) {
+  DecodeRoute r;
+  // stacked_decode_supported(1, H): H is one of the step kernels' hidden sizes, as every entry above the layer requires
+  if (E < 1 || E > (1 << 20) || !stacked_decode_supported(1, H) || !stacked_decode_route((E + 15) / 16 * 16, H, xvec, &r)) return 0;
+  if (detail) detail[0] = r.nj, detail[1] = r.tm;
+  return r.wide ? 2 : 1;
+}
+
+int capnet_lstm_upper_step(const float* xin, const float* h_prev, const float* c_prev, const float* w_eff, const float* w_rec,
+                           const float* b_eff, float* x_out, float* gates, float* c_out, float* h_out, int b, int H, int r0,
+                           float p, unsigned long long seed, int layer, int use_dropout, int cell, capnet_stream_t stream) {
+  return lstm_upper_step(xin, h_prev, c_prev, w_eff, w_rec, b_eff, x_out, gates, c_out, h_out, b, H, r0, p, seed, layer,
+                         use_dropout, S(stream), cell);
+}
+
 int capnet_lstm_persist_supported(int b, int H) { return lstm_persist_supported(b, H) ? 1 : 0; }
 int capnet_lstm_persist_set_mode(int mode) { return lstm_persist_set_mode(mode); }
 size_t capnet_lstm_persist_w_floats(void) { return lstm_persist_w_floats(); }

@@ -335,6 +335,10 @@ int scatter_input_grad(const float* dX, long ldx, int N, int E, const int* row_s
 
 // lstm_step.hip
 bool lstm_step_fused_supported(int b, int H);
+// the instance and grid lstm_step_fused launches at (b, H): k groups per wave (H padded to 64 ngw), 16-row tiles per
+// workgroup, row halves, and whether workgroup ids are dealt XCD-major (H / 4 unit groups a multiple of 8). Host only.
+struct StepFusedRoute { int ngw, mt, halves, xcd_map; };
+bool lstm_step_fused_route(int b, int H, StepFusedRoute* r);   // false: lstm_step_fused refuses (b, H)
 size_t lstm_wfrag_floats(int H);
 int lstm_pack_wfrag(const float* Wcat, float* Wfrag, int H, int gi, int gf, int go, int gg,
                     hipStream_t stream);
@@ -363,6 +367,10 @@ int stacked_decode_step(int cell, int nlayers, int rows, int E, int H, int V, co
 // `groups` host-side pointers, group g gathers its token rows from tables[g] [V][E] instead of x -- no table is copied)
 // the same kernels' family for layer 0 of an attention decoder, kin + H up to 4096 (x rows of E % 4 == 0 columns, 16-B aligned)
 bool stacked_decode_wide_supported(int E, int H);
+// the kernel a layer of kin (a multiple of 16) input columns runs on: lstm_decode_step_kernel<nj, tm> or, wide,
+// lstm_decode_step_wide_kernel<nj> (two 16-row tiles per pass); xvec: its x rows take 16-B loads. Host only.
+struct DecodeRoute { int wide, nj, tm; };
+bool stacked_decode_route(int kin, int H, int xvec, DecodeRoute* r);   // false: the layer is refused (K too large)
 // One beam step of an attention decoder without the projection: z = h_prev . [decoder_att; f_beta]^T + bz (sgemm_splitk on
 // `slab`), att_beam_step_fwd, layer 0 on xa = [embedding | gated context] (wide or narrow by shape), the upper layers.
 // ws: att_decode_step_ws_bytes (z | xa | escore)

@@ -48,7 +48,7 @@ struct DecodeLayerArgs {
   int xn;                // valid columns of an x row (E or H); columns [xn, kin) read as zero
   int xvec;              // x rows 16-B aligned and xn % 4 == 0: f32x4 loads
   int V;                 // token ids must lie in [0, V)
-  int* err;              // set to 1 on an out-of-range id (the row then reads token 0)
+  int* err;              // bit 0 is raised (atomicOr: the word's other bits stay) on an out-of-range id (the row then reads token 0)
   const float* hprev;    // [rows] x stride lds_in
   const float* cprev;
   long lds_in;
@@ -71,7 +71,7 @@ __device__ __forceinline__ long state_row(const DecodeLayerArgs& a, int row) {
   if constexpr (GATHER) {
     const long long p = a.parent[row];
     const bool ok = p >= 0 && p < a.rows;
-    if (!ok && a.err) *a.err = 1;
+    if (!ok && a.err) atomicOr(a.err, 1);
     return ok ? (long)p : (long)row;
   } else {
     return row;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_kernel(DecodeLayerArgs a
       if (a.tok) {
         const long long t = a.tok[row];
         const bool ok = t >= 0 && t < a.V;
-        if (!ok && a.err) *a.err = 1;
+        if (!ok && a.err) atomicOr(a.err, 1);
         xr = ok ? (long)t : 0;
       }
       const float* xrow = xbase + xr * a.ldx;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512) void lstm_decode_step_wide_kernel(DecodeLayerA
       if (a.tok) {
         const long long t = a.tok[row];
         const bool ok = t >= 0 && t < a.V;
-        if (!ok && a.err) *a.err = 1;
+        if (!ok && a.err) atomicOr(a.err, 1);
         xr = ok ? (long)t : 0;
       }
       xrow[m] = a.x + xr * a.ldx;
@@ -273,23 +273,44 @@ bool stacked_decode_wide_supported(int E, int H) {
   return E >= 4 && E % 4 == 0 && step_hidden_supported(H) && round16(E) + H <= kDecWideMaxK;
 }
 
+constexpr int dec_tm(int nj) { return nj <= 12 ? 2 : 1; }   // 16-row tiles per pass of lstm_decode_step_kernel<nj>
+
+// Host only: the instance launch_decode_layer gives a layer of kin (a multiple of 16) input columns, or false where
+// decode_layer refuses the shape (capnet_stacked_decode_route reports it). The wide kernel always walks two tiles.
+bool stacked_decode_route(int kin, int H, int xvec, DecodeRoute* r) {
+  const int K = kin + H;
+  if (!(K <= kDecMaxK || (xvec && K <= kDecWideMaxK))) return false;
+  const int per_wave = (K / 16 + kDecWaves - 1) / kDecWaves;
+  r->wide = per_wave > 16;
+  r->nj = per_wave <= 2 ? 2 : per_wave <= 4 ? 4 : per_wave <= 6 ? 6 : per_wave <= 8 ? 8 : per_wave <= 12 ? 12 : per_wave <= 16 ? 16
+          : per_wave <= 24 ? 12 : 16;
+  r->tm = r->wide ? 2 : dec_tm(r->nj);
+  return true;
+}
+
 template <int NJ, bool TANH_OUT, bool GATHER>
 static void launch_decode(const DecodeLayerArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, NJ <= 12 ? 2 : 1, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0,
+  hipLaunchKernelGGL((lstm_decode_step_kernel<NJ, dec_tm(NJ), TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0,
                      stream, a);
 }
 
 template <bool TANH_OUT, bool GATHER>
 static int launch_decode_layer(const DecodeLayerArgs& a, hipStream_t stream) {
-  const int per_wave = ((a.kin + a.H) / 16 + kDecWaves - 1) / kDecWaves;
-  if (per_wave <= 2) launch_decode<2, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 4) launch_decode<4, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 6) launch_decode<6, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 8) launch_decode<8, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 12) launch_decode<12, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 16) launch_decode<16, TANH_OUT, GATHER>(a, stream);
-  else if (per_wave <= 24) hipLaunchKernelGGL((lstm_decode_step_wide_kernel<12, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
-  else hipLaunchKernelGGL((lstm_decode_step_wide_kernel<16, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
+  DecodeRoute r;
+  CAPNET_REQUIRE(stacked_decode_route(a.kin, a.H, a.xvec, &r), "decode step: K = %d + %d", a.kin, a.H);
+  if (r.wide) {
+    if (r.nj == 12) hipLaunchKernelGGL((lstm_decode_step_wide_kernel<12, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
+    else hipLaunchKernelGGL((lstm_decode_step_wide_kernel<16, TANH_OUT, GATHER>), dim3(a.H / 4, a.rows / a.rpg), dim3(64 * kDecWaves), 0, stream, a);
+  } else {
+    switch (r.nj) {
+      case 2: launch_decode<2, TANH_OUT, GATHER>(a, stream); break;
+      case 4: launch_decode<4, TANH_OUT, GATHER>(a, stream); break;
+      case 6: launch_decode<6, TANH_OUT, GATHER>(a, stream); break;
+      case 8: launch_decode<8, TANH_OUT, GATHER>(a, stream); break;
+      case 12: launch_decode<12, TANH_OUT, GATHER>(a, stream); break;
+      default: launch_decode<16, TANH_OUT, GATHER>(a, stream); break;
+    }
+  }
   CAPNET_LAUNCH_CHECK();
   return kOk;
 }

@@ -39,8 +39,9 @@ __host__ __device__ inline int step_ngw(int H) {  // 16-wide k groups per wave, 
 // Workgroup id -> (unit group, row half). Consecutive unit groups share 128-B lines of G, c and
 // h, and the two row halves of a unit group share its weights: keep both inside one XCD (the
 // dispatcher deals workgroups round-robin over the 8 XCDs, each with its own L2).
+__host__ __device__ inline bool step_xcd_map(int nug) { return nug % 8 == 0; }
 __device__ __forceinline__ void step_map(int lid, int nug, int mh_shift, int& ug, int& half) {
-  if (nug % 8 == 0) {
+  if (step_xcd_map(nug)) {
     const int xcd = lid & 7, slot = lid >> 3;
     ug = xcd * (nug >> 3) + (slot >> mh_shift);
     half = slot & mh_shift;
@@ -220,14 +221,23 @@ bool lstm_step_fused_supported(int b, int H) {
   return b >= 1 && b <= kStepRows && H >= 16 && H <= 512 && H % 16 == 0;
 }
 
+bool lstm_step_fused_route(int b, int H, StepFusedRoute* r) {
+  if (!lstm_step_fused_supported(b, H)) return false;
+  r->ngw = step_ngw(H);
+  r->mt = b <= 16 ? 1 : 2;
+  r->halves = cdiv(b, kWgRows);
+  r->xcd_map = step_xcd_map(H >> 2) ? 1 : 0;
+  return true;
+}
+
 template <int NGW>
 static int launch_step(const float* hprev, const float* Wfrag, float* G, long ldg,
                        const float* cprev, float* c_out, float* h_out, int b, int H, int gi, int gf,
                        int go, int gg, int tanh_out, hipStream_t stream,
-                       unsigned long long* stamps) {
+                       unsigned long long* stamps, const StepFusedRoute& route) {
   const size_t lds_bytes = ((size_t)NGW * 16 * kCellStride * 4 + 4 * 2 * 16 * 17) * sizeof(float);
-  const int mh = cdiv(b, kWgRows);
-  const bool one_tile = b <= 16;
+  const int mh = route.halves;
+  const bool one_tile = route.mt == 1;
   auto kern = one_tile ? lstm_step_fused_kernel<NGW, 1> : lstm_step_fused_kernel<NGW, 2>;
   static bool attr_set[2] = {false, false};  // one-time opt-in to > 64 KB of dynamic LDS
   if (lds_bytes > 64 * 1024 && !attr_set[one_tile]) {
@@ -248,12 +258,13 @@ int lstm_step_fused(const float* hprev, const float* Wfrag, float* G, long ldg, 
                     float* c_out, float* h_out, int b, int H, int gi, int gf, int go, int gg,
                     int tanh_out, hipStream_t stream, unsigned long long* stamps) {
   CAPNET_REQUIRE(hprev && Wfrag && G && cprev && c_out && h_out, "lstm_step_fused: null argument");
-  CAPNET_REQUIRE(lstm_step_fused_supported(b, H), "lstm_step_fused: unsupported b=%d H=%d", b, H);
+  StepFusedRoute route;
+  CAPNET_REQUIRE(lstm_step_fused_route(b, H, &route), "lstm_step_fused: unsupported b=%d H=%d", b, H);
   CAPNET_REQUIRE(aligned16(hprev) && aligned16(Wfrag), "lstm_step_fused: alignment");
   const auto launch = [&](auto ngw) {
-    return launch_step<ngw>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps);
+    return launch_step<ngw>(hprev, Wfrag, G, ldg, cprev, c_out, h_out, b, H, gi, gf, go, gg, tanh_out, stream, stamps, route);
   };
-  const int ngw = step_ngw(H);   // 1, 2, 4 or 8: H is padded to 64 ngw here, so this is not dispatch_nj's map
+  const int ngw = route.ngw;   // 1, 2, 4 or 8: H is padded to 64 ngw here, so this is not dispatch_nj's map
   return ngw == 1 ? launch(nj_t<1>{}) : ngw == 2 ? launch(nj_t<2>{}) : ngw == 4 ? launch(nj_t<4>{}) : launch(nj_t<8>{});
 }
 

@@ -610,7 +610,7 @@ int capnet_lstm_pointwise_bwd(const float* gates, const float* c, const float* c
  * with wcat[l] [4H][kin_l + H] = [U_g S_g V_g (zero columns up to kin_l) | W_g] in gate blocks i, f, o, c~ and
  * beff[l] [4H] = U_g (S_g bV_g + bS_g) + bU_g + bW_g (the chain folded on the host; stylenet/model.py:115-155 at
  * inference). kin_0 = E rounded up to a multiple of 16, kin_l = H above. Layer 0's x: with `tokens` (int64 [rows]),
- * row tokens[r] of the table x [V][E] (an id outside [0, V) sets *err_flag = 1 and reads row 0); without, x is the
+ * row tokens[r] of the table x [V][E] (an id outside [0, V) sets bit 0 of *err_flag and reads row 0); without, x is the
  * inputs [rows][E]. Layer l > 0's x is layer l-1's new h.
  * state_in / state_out: [rows][2 nlayers][H] (slot 2l = h of layer l, 2l+1 = c), distinct, 16-B aligned;
  * h_top [rows][H] receives the top layer's h once more. wcat / beff: HOST arrays of nlayers device pointers.
@@ -631,7 +631,7 @@ int capnet_stacked_decode_step_cell(int cell, int nlayers, int rows, int E, int 
 /* capnet_stacked_decode_step_cell reading the previous state through a beam search's parent rows: with parent_rows (int64
  * [rows], device), row r's h_prev and c_prev of every layer are those of row parent_rows[r] of state_in -- the result of
  * the step on state_in.index_select(0, parent_rows), bit for bit, without that copy. x, tokens, state_out and h_top stay
- * indexed by the row itself; parents may repeat (state_in != state_out). A parent outside [0, rows) sets *err_flag = 1
+ * indexed by the row itself; parents may repeat (state_in != state_out). A parent outside [0, rows) sets bit 0 of *err_flag
  * and the row reads itself; parent_rows needs err_flag. parent_rows NULL: exactly capnet_stacked_decode_step_cell. */
 int capnet_stacked_decode_step_gather(int cell, int nlayers, int rows, int E, int H, int V, const long long* tokens,
                                       const float* x, const float* const* wcat, const float* const* beff,
@@ -655,7 +655,7 @@ int capnet_stacked_decode_step_groups(int cell, int nlayers, int groups, int row
  * tables[g][tokens[r]] -- the kernel receives the pointers by value and picks its group's by the workgroup's group index;
  * no table is copied or stacked. tokens is required (there are no input rows); V is the same for every group. Row r of
  * group g is, bit for bit, the row of capnet_stacked_decode_step_gather on group g's rows, weights and table alone. A
- * token id outside [0, V) sets *err_flag = 1 and reads row 0 of its group's table. E + H (E rounded up to 16) <= 2048,
+ * token id outside [0, V) sets bit 0 of *err_flag and reads row 0 of its group's table. E + H (E rounded up to 16) <= 2048,
  * the narrow kernel. Every tables[g] non-NULL. Same shapes and checks otherwise. */
 int capnet_stacked_decode_step_tables(int cell, int nlayers, int groups, int rows_per_group, int E, int H, int V,
                                       const long long* tokens, const float* const* tables, const float* const* wcat,
@@ -694,7 +694,7 @@ int capnet_vocab_argmax_groups(const float* h, const float* const* w, const floa
  * state0: the initial [rows][2 nlayers][H] state (slot 2l = h of layer l, 2l+1 = c) or NULL for zeros; state_out receives
  * the state after the last step in the same layout (it may be state0). ids: int64 [rows][steps].
  * workspace: capnet_lstm_greedy_decode_ws_bytes(nlayers, rows, H, V) bytes, 16-B aligned, contents irrelevant.
- * A token id outside [0, V) (only start_tokens can hold one) sets *err_flag = 1 and reads row 0.
+ * A token id outside [0, V) (only start_tokens can hold one) sets bit 0 of *err_flag and reads row 0.
  * Shapes: those of capnet_stacked_decode_step_cell. */
 size_t capnet_lstm_greedy_decode_ws_bytes(int nlayers, int rows, int H, int V);
 int capnet_lstm_greedy_decode(int nlayers, int rows, int E, int H, int V, int steps, const float* features,
@@ -734,7 +734,7 @@ int capnet_lstm_greedy_decode_groups(int nlayers, int groups, int rows_per_group
  * rounded up to 16 bytes; 0 for shapes outside 1 <= k <= 16, 1 <= nlayers <= 8). slab: at least n k V floats, 16-B aligned.
  * The call allocates nothing. poll_every = 0: no host synchronisation and nothing read. poll_every = m > 0: after every
  * m-th step short of the last, one blocking 4-byte read of the count of live beams; the loop stops at zero (same result).
- * *steps_run (host, may be NULL): the steps issued. A token id outside [0, V) (start_token) sets *err_flag = 1.
+ * *steps_run (host, may be NULL): the steps issued. A token id outside [0, V) (start_token) sets bit 0 of *err_flag.
  * Every bad argument is refused before any launch. */
 size_t capnet_beam_decode_ws_bytes(int nlayers, int n, int k, int H, int V, int max_steps);
 int capnet_beam_decode(int cell, int nlayers, int n, int k, int E, int H, int V, int max_steps, long long start_token,
@@ -1099,8 +1099,8 @@ int capnet_lstm_beam_decode_groups_constrained(int cell, int nlayers, int groups
  *   4. layers 1 .. nlayers - 1, plain H -> H cells on the layer below, as capnet_stacked_decode_step_gather.
  * cell / wcat / beff (HOST arrays of nlayers device pointers) as capnet_stacked_decode_step_cell, wcat[0] [4H][kin + H] with
  * kin = E + C rounded up to 16. state_in / state_out [n k][2 nlayers][H], different buffers; h_top [n k][H].
- * parent_rows: int64 [n k] or NULL (every row its own parent); one outside [0, n k) sets *err_flag = 1 and the row reads
- * itself. A token id outside [0, V) sets *err_flag = 1 and reads row 0 of emb [V][E].
+ * parent_rows: int64 [n k] or NULL (every row its own parent); one outside [0, n k) sets bit 0 of *err_flag and the row reads
+ * itself. A token id outside [0, V) sets bit 0 of *err_flag and reads row 0 of emb [V][E].
  * workspace: capnet_att_decode_step_ws_bytes(n, k, P, A, C, E) bytes, 16-B aligned: z, then xa, then the raw scores
  * [n k][P rounded up to 4]. slab: at least n k max(V, A + C) floats, 16-B aligned.
  * Shapes (capnet_att_decode_supported): A % 4 == 0, C % 512 == 0, 1 <= P <= 4096, E % 4 == 0, 1 <= k <= 16, H in {64, 128,
@@ -1256,7 +1256,9 @@ int capnet_alpha_gather(const float* hist, const int* rows, int captions, int nk
  *   capnet_lstm_pack_wfrag image), then the gate
  *   non-linearities, c = f*c_prev + i*g, h = o*c (cell 0) / o*tanh(c) (cell 1); gates are
  *   overwritten by the activated values. Each wave keeps its slice of w_cat in registers for
- *   the launch. b <= 64, H in {16,32,64,96,128,256,512} (capnet_lstm_step_fused_supported). */
+ *   the launch. 1 <= b <= 64, H any multiple of 16 in 16..512 (capnet_lstm_step_fused_supported):
+ *   H is padded with zero weights to 64, 128, 256 or 512 inside the fragment image. h_prev and
+ *   w_frag 16-byte aligned; gates, c_prev, c_out, h_out dense rows of 4-byte alignment, ldg >= 4H. */
 size_t capnet_lstm_wfrag_floats(int H);
 /* w_cat [4H][H] (gate blocks in the cell's storage order) -> the fragment-major image the step
  * kernel streams with fully coalesced 1-KB reads (one per 4 MFMA k-steps and wave) */
@@ -1271,6 +1273,26 @@ int capnet_lstm_step_fused_stamped(const float* h_prev, const float* w_frag, flo
                                    const float* c_prev, float* c_out, float* h_out, int b, int H,
                                    unsigned long long* stamps, capnet_stream_t stream);
 int capnet_lstm_step_fused_supported(int b, int H);
+/* Host only, nothing launched: the instance capnet_lstm_step_fused runs at (b, H). Returns 0 where the call refuses the
+ * shape, else 1 with detail[4] (optional) = { k groups per wave (1, 2, 4, 8: H padded to 64 times that), 16-row tiles per
+ * workgroup (1: b <= 16, else 2), row halves (2: b > 32), 1 where workgroup ids are dealt XCD-major (H / 4 a multiple
+ * of 8) else 0 }. */
+int capnet_lstm_step_fused_route(int b, int H, int* detail);
+/* Host only: the kernel a decode-step layer of E input columns (rounded up to 16) and hidden size H runs on, xvec = its
+ * input rows take 16-byte loads (E % 4 == 0, aligned rows). 0: refused (K = round16(E) + H above 2048 without xvec, above
+ * 4096, or an H outside {64, 128, 256, 512, 1024}); 1: the narrow kernel, 2: the wide one. detail[2] (optional) = { k
+ * groups per wave of the instance (narrow 2, 4, 6, 8, 12, 16; wide 12, 16 per half), 16-row tiles per pass }. */
+int capnet_stacked_decode_route(int E, int H, int xvec, int* detail);
+
+/* One training step of a stacked layer above the first on at most 16 rows, in one launch (the step capnet_att_seq_forward
+ * runs for its upper layers): x_out = dropout(xin) (use_dropout: the mask of (seed, row r0 + r, layer), scaled by 1 / (1 - p);
+ * else a copy), pre = [x_out | h_prev] . [w_eff | w_rec]^T + b_eff, gates [b][4H] = the activated gates in the cell's block
+ * order (cell 0: i, f, o, c~; cell 1: i, f, g, o), c_out = f c_prev + i g, h_out = o c_out (cell 0) or o tanh(c_out).
+ * xin, h_prev, c_prev, x_out, c_out, h_out [b][H] dense; w_eff, w_rec [4H][H]; b_eff [4H]. 1 <= b <= 16, H in {64, 128, 256,
+ * 512, 1024}; xin, h_prev, w_eff, w_rec 16-byte aligned. */
+int capnet_lstm_upper_step(const float* xin, const float* h_prev, const float* c_prev, const float* w_eff, const float* w_rec,
+                           const float* b_eff, float* x_out, float* gates, float* c_out, float* h_out, int b, int H, int r0,
+                           float p, unsigned long long seed, int layer, int use_dropout, int cell, capnet_stream_t stream);
 
 /* Persistent sequence kernel: steps [t0, t1) of the recurrence in ONE launch, the recurrent
  * weights register-resident for the launch (north star: "the LSTM step as a persistent

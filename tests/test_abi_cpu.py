@@ -41,6 +41,14 @@ def test_host_side_argument_checks_need_no_gpu():
     # 11.512 GMAC per image
     assert abs(lib.capnet_trunk_flops(h) / 2 / 2 / 1e9 - 11.512) < 0.01
     lib.capnet_trunk_destroy(h)
+    # the route queries of the step kernels are host code (tests/test_step_cases_cpu.py sweeps them)
+    d = (C.c_int * 4)()
+    assert lib.capnet_lstm_step_fused_route(64, 512, d) == 1 and list(d) == [8, 2, 2, 1]
+    assert lib.capnet_lstm_step_fused_route(65, 512, d) == 0
+    assert lib.capnet_stacked_decode_route(300, 512, 1, d) == 1 and list(d)[:2] == [8, 2]
+    assert lib.capnet_stacked_decode_route(2060, 64, 1, d) == 2 and lib.capnet_stacked_decode_route(2060, 64, 0, d) == 0
+    assert lib.capnet_lstm_upper_step(None, None, None, None, None, None, None, None, None, None, 1, 64, 0, 0.0, 0, 1, 0, 0,
+                                      None) != 0 and b"null" in lib.capnet_last_error()
 
 
 def test_ops_refuse_cpu_tensors():
